@@ -12,11 +12,18 @@ outputs the loop consumes) are synthetic and resident in HBM before the timed re
 N > 1, T = 5 (config 2): every rank runs its own replica of the clip (T=5 does not divide across ranks without changing
 the result -- docs/LOG_r01_r05.md section 6), scaling "weak", value = N * pixels / max-over-ranks time.
 N > 1, T = 5: behind the replica measurement the same ranks run ONE frame-sharded window (--sharded-T 40 --sharded-iters 20 = BASELINE config 4), checked
-against the unsharded result on rank 0 first; it is reported under `sharded` / `sharded_check`, never in `value`.
+against the unsharded result on rank 0 first; it is reported under `sharded` / `sharded_check`, never in `value` (with --full only).
 N > 1, --T divisible by N and >= 2 frames per rank (configs 4-5, e.g. --T 40): the window's frames are SHARDED over the
 ranks (ppmstereo_amd.dist.FrameShard: all-gather of the memory keys once per scale and of the values / confidences every
 iteration, +-2 / +-1 frame halos for the temporal convs), scaling "strong", value = pixels / max-over-ranks time.
 Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline figure needs: set-up, --warmup steps, the --steps timed steps, the outputs of the
+last timed step (--dump-outputs DIR) and the JSON line.  Everything else it can measure or check -- the per-kernel rooflines
+(HIP events around launches in the sampled timed steps, two extra event-timed steps), the latency and all-predictions clips,
+the encoder / whole-call timings, the CPU baseline and the extra frame-sharded window of N > 1 -- runs with --full only:
+
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full
 """
 import argparse
 import json
@@ -182,7 +189,7 @@ def dry_run(args, D, rank, world):
                dry_run=True, backend=torch.distributed.get_backend() if world > 1 else None, frames_over_ranks=frames,
                config=dict(workload="dry run: stub step, no GPU work", T=T, H=args.H, W=args.W, iters=args.iters,
                            parallelism=(f"frames sharded {T // world}/GPU x{world}" if sharded else f"replicas x{world}")))
-    if world > 1 and not sharded and args.sharded_T and args.sharded_T % world == 0 and args.sharded_T // world >= 2:
+    if args.full and world > 1 and not sharded and args.sharded_T and args.sharded_T % world == 0 and args.sharded_T // world >= 2:
         # the extra frame-sharded window of the real run (sharded_phase): planned and rehearsed on the stub (one all-reduce per repetition), under the
         # same guard: the replica line above is complete, a failure of the extra phase (--inject-sharded-failure RANK: that rank raises in front of a
         # collective the others have entered) must still print it once, with the error, and end every rank non-zero
@@ -271,13 +278,68 @@ def sharded_phase(args, D, model, rank, world, dev):
 
 BUILD_MODE = None
 TIMING_EVERY = 20         # per-launch events in steps 0, 20, 40, ... of the timed region (one step's launches: 117 convs, 20 attention calls)
+DUMP_LIMIT_BYTES = 60 << 20       # --dump-outputs: all arrays together (the .npy headers stay well inside 64 MB)
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: arrays (name -> tensor) as outdir/<name>.npy in float32.  If the whole set exceeds DUMP_LIMIT_BYTES, every array is cut to its
+    flattened elements 0, s, 2s, ... with the one stride s that brings the set under the cap -- a function of the shapes only, so two builds of the
+    project (same arguments, hence the same inputs) write the same elements.  Returns {name: dict(shape, stride)} for the result line."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    total = sum(4 * t.numel() for t in arrays.values())
+    done = {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        stride = 1 if total <= DUMP_LIMIT_BYTES else -(-total // DUMP_LIMIT_BYTES)
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a.reshape(-1)[::stride] if stride > 1 else a))
+        done[name] = dict(shape=list(a.shape), stride=stride)
+    return done
+
+
+def result_line(args, L, world, sharded, elapsed, step_ms, pipe, dumped):
+    """The fields of the JSON line that every run prints (rank 0): the headline measurement of the --steps timed steps and what ran."""
+    from ppmstereo_amd import build as _build
+    from ppmstereo_amd import engine as _eng
+    T, H, W, iters = args.T, args.H, args.W, args.iters
+    label = BASELINE_CONFIGS.get((T, H, W, iters), "custom configuration")
+    par = f"frames sharded {T // world}/GPU x{world} (RCCL all-gather of memory K/V + temporal halos)" if sharded else f"replicas x{world}"
+    try:
+        stamp = open(_build.STAMP).read().strip()
+    except OSError:
+        stamp = ""
+    value = (1 if sharded else world) * args.steps * T * H * W / elapsed
+    return dict(metric="disparity-px/s", value=round(value, 1), unit="disparity-px/s", n_gpus=world, steps=args.steps, warmup=args.warmup,
+                ms_per_step=round(1e3 * elapsed / args.steps, 3), ms_per_step_median=round(statistics.median(step_ms), 3),
+                ms_per_step_min=round(min(step_ms), 3), higher_is_better=True, scaling="strong" if sharded else "weak", vs_baseline=None, dtype="bf16",
+                precision=f"attention: Q K'^T on bf16 MFMA, fp32 softmax, P~ V on {_eng.TUNING['attn_p']} MFMA (V = the bf16-rounded values), fp32 accumulate; "
+                          "convs: bf16x3 split MFMA (fp32-accurate); correlation: fp32 MFMA",
+                data="synthetic", frames_per_s=round((1 if sharded else world) * args.steps * T / elapsed, 2),
+                config=dict(workload=f"{label}: T={T} clip at {H}x{W}, iters={iters}, hot path only (3-scale cascade from encoder outputs: "
+                                     "corr pyramid build + lookup, QAM pick, pick-and-play memory attention, ConvGRU3D update, heads, convex upsample, "
+                                     "test_mode=True as PPMStereo.forward_batch_test calls it: predictions[-1] is the output, so the mask head, the "
+                                     "convex upsampling and the full-resolution resize run only where their result is consumed -- the last iteration "
+                                     "of each scale; with --full, ms_per_step_all_predictions times the same clip with every iteration's prediction produced)",
+                            T=T, H=H, W=W, iters=iters, parallelism=par),
+                pipeline=("consecutive clips overlap: 1/16 + 1/8 scales of clip k + 1 on a second stream under the 1/4 scale of clip k (ClipPipeline); "
+                          "latency_ms_per_clip = one clip alone" if pipe is not None else "off: clips strictly one after the other"),
+                full=bool(args.full), outputs=dumped,
+                library=os.path.relpath(L.lib_path(), ROOT),
+                # the library that ran: "reused" = libppms.so.stamp matched the digest of the committed sources + flags when this process loaded it (it IS
+                # those sources, built earlier); "compiled" = this process (or a rank beside it) ran hipcc on them first
+                build_mode=BUILD_MODE, library_stamp=stamp[:12], library_stamp_matches_sources=bool(stamp and stamp == _build._digest()))
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None, help="ranks = GPUs of this node (one process per GPU); default: WORLD_SIZE when a launcher set it, else 1")
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (clips); ms_per_step = their wall time / steps")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline figure: rooflines, latency and "
+                    "all-predictions clips, encoders + whole call, CPU baseline, the extra frame-sharded window of N > 1 (the --no-* / --cpu-baseline / "
+                    "--sharded-* options below shape these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path returned in its last timed step (disparity, "
+                    "uncertainty: (T, 1, H, W) each) as DIR/<name>.npy in float32; above 64 MB in all, a fixed strided sample of each")
     ap.add_argument("--T", type=int, default=5)
     ap.add_argument("--H", type=int, default=320)
     ap.add_argument("--W", type=int, default=512)
@@ -303,6 +365,8 @@ def main():
     ap.add_argument("--dry-run", action="store_true", help="launch / rendezvous / argument plumbing only: the ranks form the process group, run a stub step "
                     "(no GPU work), take the barrier + max-over-ranks path and rank 0 prints a line with value = null (CPU rehearsal, tests/test_bench_launch.py)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if args.gpus is None:
         args.gpus = int(os.environ.get("WORLD_SIZE", "1")) if "RANK" in os.environ else 1
 
@@ -357,13 +421,14 @@ def main():
     if pipe is not None:
         pipe.done_events.clear()
 
-    # HIP events around every launch (in the sampled steps: TIMING_EVERY) of the two dominant kernel families (memory attention; the large-map implicit-GEMM
-    # convolution kernels conv6_kernel / conv5_kernel -- whichever the engine picked per conv), on the stream each is launched on
+    # --full: HIP events around every launch (in the sampled steps: TIMING_EVERY) of the two dominant kernel families (memory attention; the large-map
+    # implicit-GEMM convolution kernels conv6_kernel / conv5_kernel -- whichever the engine picked per conv), on the stream each is launched on
+    timing = args.full and not args.no_kernel_timing
     Tl = T // world if sharded else T
     engs = [(model.update_block16.engine(Tl, H // 16, W // 16, dev, shard), iters // 2), (model.update_block08.engine(Tl, H // 8, W // 8, dev, shard), iters // 2),
             (model.update_block04.engine(Tl, H // 4, W // 4, dev, shard), iters)]
     big, family = {}, {}
-    if not args.no_kernel_timing:
+    if timing:
         for (e, n_it), sc in zip(engs, (16, 8, 4)):
             e.enable_attn_timing(args.steps * n_it)
             for name, op in e.conv_family_ops().items():          # every convolution-family launch of every scale (roofline_3, timed in
@@ -380,11 +445,11 @@ def main():
     for i, (a, b) in enumerate(step_ev):
         # the per-launch HIP events of the roofline entries are recorded in every TIMING_EVERY-th step of the timed region only (steps 0, 20,
         # ...): ~330 event pairs per clip cost ~2 ms of the clip's 43, and `value` is the time of ALL steps
-        _engine.KERNEL_TIMING["on"] = (not args.no_kernel_timing) and i % TIMING_EVERY == 0
+        _engine.KERNEL_TIMING["on"] = timing and i % TIMING_EVERY == 0
         if pipe is not None:      # the steps whose launches carry events run un-overlapped (their durations are then the kernels' own): neither
-            pipe.serial = _engine.KERNEL_TIMING["on"] or ((not args.no_kernel_timing) and i > 0 and (i - 1) % TIMING_EVERY == 0)   # the step nor its successor overlaps it
+            pipe.serial = _engine.KERNEL_TIMING["on"] or (timing and i > 0 and (i - 1) % TIMING_EVERY == 0)   # the step nor its successor overlaps it
         a.record()
-        step()
+        result = step()
         b.record()
     _engine.KERNEL_TIMING["on"] = False               # nothing below is event-timed per launch
     torch.cuda.synchronize()
@@ -394,7 +459,20 @@ def main():
     if pipe is not None and len(pipe.done_events) == args.steps and args.steps > 1:      # pipelined: a step's time = completion to completion
         step_ms = [pipe.done_events[i - 1].elapsed_time(pipe.done_events[i]) for i in range(1, args.steps)]
         pipe.serial, pipe.record_done = False, False
-    attn_ms = [e.attn_times_ms() for e, _ in engs] if not args.no_kernel_timing else []
+    dumped = None
+    if args.dump_outputs:                             # the last timed step's return value, before any --full step below reuses the engines' buffers
+        outs = dict(zip(("disparity", "uncertainty"), result))
+        if sharded:                                   # this rank holds its frames only: the whole window, in frame order (a collective: every rank)
+            outs = {k: shard.all_gather(v.float().contiguous())[0] for k, v in outs.items()}
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, outs)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result_line(args, L, world, sharded, elapsed, step_ms, pipe, dumped)), flush=True)
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
+    attn_ms = [e.attn_times_ms() for e, _ in engs] if timing else []
     # the large-map convolution launches of the timed region: read their events NOW and detach the lists, so that the extra steps below (which
     # switch KERNEL_TIMING on again) cannot append a second step's launches to them (round 4 counted `total_ms_per_step` twice that way)
     big_ms = {k: [a.elapsed_time(b) for a, b in op.events] for k, op in big.items()}
@@ -451,8 +529,6 @@ def main():
                         avg_ms=None if lead is None else round(lead["avg_us"] / 1e3, 5), algorithmic_bytes_per_launch=None if lead is None else lead["algorithmic_mb"] * 1e6,
                         kernels=kernels)
     n_sampled = len(range(0, args.steps, TIMING_EVERY))                # steps whose launches carried events
-    px = T * H * W
-    value = (1 if sharded else world) * args.steps * px / elapsed
     ksel = min(5, T)
     roofs, family_roof, consistency = [], None, {}
     if not args.no_kernel_timing:
@@ -633,38 +709,13 @@ def main():
                 cpu = cpu_baseline_full(T, H, W, iters, cores)
                 cpu["sampled_seconds_per_clip"] = sampled["seconds_per_clip"]
                 cpu["sampled_vs_full"] = round(sampled["seconds_per_clip"] / cpu["seconds_per_clip"], 4)
-        label = BASELINE_CONFIGS.get((T, H, W, iters), "custom configuration")
-        par = f"frames sharded {T // world}/GPU x{world} (RCCL all-gather of memory K/V + temporal halos)" if sharded else f"replicas x{world}"
-        from ppmstereo_amd import build as _build
-        from ppmstereo_amd import engine as _eng
-        try:
-            stamp = open(_build.STAMP).read().strip()
-        except OSError:
-            stamp = ""
-        out = dict(metric="disparity-px/s", value=round(value, 1), unit="disparity-px/s", n_gpus=world, steps=args.steps, warmup=args.warmup,
-                   ms_per_step=round(1e3 * elapsed / args.steps, 3), ms_per_step_median=round(statistics.median(step_ms), 3),
-                   ms_per_step_min=round(min(step_ms), 3), higher_is_better=True, scaling="strong" if sharded else "weak", vs_baseline=None, dtype="bf16",
-                   precision=f"attention: Q K'^T on bf16 MFMA, fp32 softmax, P~ V on {_eng.TUNING['attn_p']} MFMA (V = the bf16-rounded values), fp32 accumulate; "
-                             "convs: bf16x3 split MFMA (fp32-accurate); correlation: fp32 MFMA",
-                   data="synthetic", frames_per_s=round((1 if sharded else world) * args.steps * T / elapsed, 2),
-                   config=dict(workload=f"{label}: T={T} clip at {H}x{W}, iters={iters}, hot path only (3-scale cascade from encoder outputs: "
-                                        "corr pyramid build + lookup, QAM pick, pick-and-play memory attention, ConvGRU3D update, heads, convex upsample, "
-                                        "test_mode=True as PPMStereo.forward_batch_test calls it: predictions[-1] is the output, so the mask head, the "
-                                        "convex upsampling and the full-resolution resize run only where their result is consumed -- the last iteration "
-                                        "of each scale; ms_per_step_all_predictions times the same clip with every iteration's prediction produced)",
-                                T=T, H=H, W=W, iters=iters, parallelism=par),
+        out = dict(result_line(args, L, world, sharded, elapsed, step_ms, pipe, dumped),
                    ms_per_step_all_predictions=None if all_ms is None else round(all_ms, 3),
                    latency_ms_per_clip=None if lat_ms is None else round(lat_ms, 3),
-                   pipeline=("consecutive clips overlap: 1/16 + 1/8 scales of clip k + 1 on a second stream under the 1/4 scale of clip k (ClipPipeline); "
-                             "latency_ms_per_clip = one clip alone" if pipe is not None else "off: clips strictly one after the other"),
                    roofline=roofs[0] if roofs else None, roofline_2=roofs[1] if len(roofs) > 1 else None,
                    roofline_3=family_roof if (not args.no_kernel_timing and family) else None, roofline_hbm=hbm_roof, roofline_consistency=consistency or None,
                    cpu_baseline=cpu, sharded=None, sharded_check=None,
                    whole_call_ms=None if not encoders else encoders["whole_call_ms"],
-                   library=os.path.relpath(L.lib_path(), ROOT),
-                   # the library that ran: "reused" = libppms.so.stamp matched the digest of the committed sources + flags when this process loaded it (it IS
-                   # those sources, built earlier); "compiled" = this process (or a rank beside it) ran hipcc on them first
-                   build_mode=BUILD_MODE, library_stamp=stamp[:12], library_stamp_matches_sources=bool(stamp and stamp == _build._digest()),
                    **({"encoders": encoders} if encoders else {}))
     exit_code = 0
     if world > 1 and not sharded and args.sharded_T and args.sharded_T % world == 0 and args.sharded_T // world >= 2:

@@ -26,7 +26,7 @@ def _line(stdout):
 
 @pytest.mark.parametrize("n,T,scaling,par", [(2, 5, "weak", "replicas x2"), (8, 40, "strong", "frames sharded 5/GPU x8"), (8, 5, "weak", "replicas x8")])
 def test_bench_gpus_n_launches_n_ranks(n, T, scaling, par):
-    r = _bench("--gpus", str(n), "--T", str(T), "--steps", "2", "--warmup", "1", "--dry-run")
+    r = _bench("--gpus", str(n), "--T", str(T), "--steps", "2", "--warmup", "1", "--dry-run", "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     out = _line(r.stdout)
     assert out["n_gpus"] == n and out["dry_run"] and out["value"] is None and out["backend"] == "gloo"
@@ -67,7 +67,7 @@ def test_extra_sharded_phase_failure_prints_the_replica_line_once_and_exits_nonz
     quickly: the blocked ranks leave on the launcher's SIGTERM (read from the signal wake-up pipe by a helper thread), not after a collective timeout."""
     import time
     t0 = time.time()
-    r = _bench("--gpus", "2", "--steps", "2", "--warmup", "1", "--dry-run", "--inject-sharded-failure", str(bad_rank), "--sharded-timeout", "120")
+    r = _bench("--gpus", "2", "--steps", "2", "--warmup", "1", "--dry-run", "--full", "--inject-sharded-failure", str(bad_rank), "--sharded-timeout", "120")
     took = time.time() - t0
     assert r.returncode != 0, (r.stdout, r.stderr[-1500:])
     out = _line(r.stdout)
@@ -77,3 +77,35 @@ def test_extra_sharded_phase_failure_prints_the_replica_line_once_and_exits_nonz
     else:
         assert "SIGTERM" in out["sharded"]["error"] or "injected" in out["sharded"]["error"], out["sharded"]
     assert took < 100, f"{took:.0f} s: the ranks waited for a timeout instead of leaving on the launcher's signal"
+
+
+def test_plain_run_leaves_the_extra_sharded_window_to_full():
+    """Without --full the N > 1 replica run is the headline measurement only: no frame-sharded window is planned behind it."""
+    r = _bench("--gpus", "2", "--steps", "2", "--warmup", "1", "--dry-run")
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = _line(r.stdout)
+    assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["sharded"] is None and out["steps"] == 2
+
+
+def test_steps_below_one_are_refused():
+    r = _bench("--steps", "0", "--dry-run")
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
+
+
+def test_dump_outputs_writes_float32_and_a_fixed_sample_above_the_cap(tmp_path, monkeypatch):
+    """bench.dump_outputs: every array as <name>.npy in float32; over the cap, the same stride for every array (a function of the shapes only)."""
+    import numpy as np
+    import torch
+    import bench
+    arrays = {"disparity": torch.arange(10, dtype=torch.float32).reshape(2, 1, 1, 5), "uncertainty": torch.ones(2, 1, 1, 5, dtype=torch.float64)}
+    info = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    assert info == {"disparity": dict(shape=[2, 1, 1, 5], stride=1), "uncertainty": dict(shape=[2, 1, 1, 5], stride=1)}
+    for name, t in arrays.items():
+        a = np.load(tmp_path / "a" / (name + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, t.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 40)           # 50 float32 = 200 bytes over a 40-byte cap: every 5th element
+    info = bench.dump_outputs(str(tmp_path / "b"), {"x": torch.arange(20.0), "y": torch.arange(30.0).reshape(5, 6)})
+    assert info == {"x": dict(shape=[20], stride=5), "y": dict(shape=[5, 6], stride=5)}
+    x, y = np.load(tmp_path / "b" / "x.npy"), np.load(tmp_path / "b" / "y.npy")
+    assert np.array_equal(x, np.arange(0, 20, 5, dtype=np.float32)) and np.array_equal(y, np.arange(0, 30, 5, dtype=np.float32))
+    assert 4 * (x.size + y.size) <= 40

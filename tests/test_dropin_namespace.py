@@ -1,22 +1,35 @@
-"""CPU, build container only (skipped where /root/reference is absent, e.g. on the GPU box): the drop-in import path and the
-fixture generator, next to the reference.
+"""CPU: the drop-in import path.
 
 ``models/`` of this repository has NO ``__init__.py`` anywhere: like the reference's ``models/`` it is a PEP 420 namespace portion.  With
 this repository in front of the reference on ``sys.path``, ``models.core.{corr,ppmstereo,ppmtereo_update}`` and
 ``models.core.utils.utils`` bind to the gfx950 implementation while everything else the reference keeps under ``models/`` -- the wrapper
 ``models/ppm_stereo_model.py`` (its line 12 is the drop-in's import site), ``models.core.extractor``, ``attention``, ``convnext`` ... --
 still resolves in the reference.  ``tools/gen_golden.py`` puts the reference FIRST and refuses to run if any module it pins the
-oracle with was imported from this repository."""
+oracle with was imported from this repository.
+
+The reference is not part of this repository: the tests below build a stand-in of its ``models/`` layout (the same module paths, empty
+files, no ``__init__.py`` at ``models/`` or ``models/core/``) in a temporary directory and check how the two portions resolve against it."""
 import os
 import subprocess
 import sys
 
-import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
-needs_ref = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "models", "core")), reason="reference tree not present on this box")
+# module paths of the reference's models/ namespace that these tests resolve; the last four have same-named modules here
+REF_MODULES = ("models/ppm_stereo_model.py", "models/core/extractor.py", "models/core/attention.py", "models/core/convnext.py",
+               "models/core/ppmstereo.py", "models/core/corr.py", "models/core/ppmtereo_update.py", "models/core/utils/utils.py")
+
+
+@pytest.fixture
+def ref(tmp_path):
+    """A stand-in of the reference's tree: every module of REF_MODULES as an empty file that records where it was imported from."""
+    root = tmp_path / "reference"
+    for rel in REF_MODULES:
+        f = root / rel
+        f.parent.mkdir(parents=True, exist_ok=True)
+        f.write_text("STAND_IN = __file__\n")
+    return str(root)
 
 
 def _run(code, path):
@@ -31,8 +44,7 @@ def test_models_is_a_namespace_portion():
         assert "__init__.py" not in files, f"{d}/__init__.py would hide the reference's models namespace"
 
 
-@needs_ref
-def test_wrapper_file_and_shim_resolve_side_by_side():
+def test_wrapper_file_and_shim_resolve_side_by_side(ref):
     """models/ppm_stereo_model.py:12 -- found under the reference; its import target -- found here."""
     code = """
 import importlib.util as u, os
@@ -45,34 +57,19 @@ for name, root in want.items():
 from models.core.ppmstereo import PPMStereo            # the line of the wrapper, executed
 import ppmstereo_amd.ppmstereo as P
 assert PPMStereo is P.PPMStereo
+import models.ppm_stereo_model as M                      # the wrapper module itself: the reference's file
+assert os.path.realpath(M.STAND_IN).startswith(%r + os.sep)
 print("ok")
-""" % (REF, REF, REF, REF, ROOT, ROOT, ROOT, ROOT)
-    assert "ok" in _run(code, [ROOT, REF])
+""" % (ref, ref, ref, ref, ROOT, ROOT, ROOT, ROOT, ref)
+    assert "ok" in _run(code, [ROOT, ref])
 
 
-@needs_ref
-def test_reference_first_binds_the_reference():
+def test_reference_first_binds_the_reference(ref):
     """The generator's order: the reference in front -> the same names are the reference's own files."""
     code = """
 import importlib.util as u, os
 for name in ("models.core.ppmstereo", "models.core.corr", "models.core.ppmtereo_update", "models.core.utils.utils"):
     assert os.path.realpath(u.find_spec(name).origin).startswith(%r + os.sep), name
 print("ok")
-""" % REF
-    assert "ok" in _run(code, [REF, ROOT])
-
-
-@needs_ref
-def test_fixture_generator_reproduces_every_committed_fixture(tmp_path):
-    """`python tools/gen_golden.py` as committed (~40 s): runs the reference's own modules and reproduces ALL committed fixtures bit for bit --
-    the recipe that pins the oracle works, and tests/golden/ holds nothing but its output."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "gen_golden.py"), "--out", str(tmp_path)],
-                       capture_output=True, text=True, cwd=ROOT, timeout=1500, env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"))
-    assert r.returncode == 0, r.stderr[-2000:]
-    committed = sorted(f for f in os.listdir(os.path.join(ROOT, "tests", "golden")) if f.endswith(".npz"))
-    assert sorted(os.listdir(tmp_path)) == committed and len(committed) >= 29
-    for f in committed:
-        new, old = np.load(tmp_path / f), np.load(os.path.join(ROOT, "tests", "golden", f))
-        assert set(new.files) == set(old.files), f
-        for k in new.files:
-            assert np.array_equal(new[k], old[k], equal_nan=True), (f, k)
+""" % ref
+    assert "ok" in _run(code, [ref, ROOT])

@@ -127,7 +127,7 @@ def test_bench_gpus_2_runs_end_to_end_on_one_gpu_over_gloo(T, scaling):
     """`python bench.py --gpus 2`: two ranks launched by bench.py itself; T = 5 -> clip replicas (what the driver's scaling run does at
     config 2), T = 8 -> the window's frames sharded 4 + 4 with every exchange of dist.FrameShard inside the timed steps."""
     out = _bench_line(["--gpus", "2", "--T", str(T), "--H", "64", "--W", "256", "--iters", "4", "--steps", "2", "--warmup", "1",
-                       "--no-cpu-baseline", "--no-encoders", "--sharded-T", "8", "--sharded-iters", "4", "--sharded-steps", "1"])
+                       "--full", "--no-cpu-baseline", "--no-encoders", "--sharded-T", "8", "--sharded-iters", "4", "--sharded-steps", "1"])
     assert out["n_gpus"] == 2 and out["scaling"] == scaling and out["value"] > 0 and out["steps"] == 2
     px = T * 64 * 256
     want = (1 if scaling == "strong" else 2) * 2 * px / (out["ms_per_step"] * 2e-3)

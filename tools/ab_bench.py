@@ -1,5 +1,5 @@
 """bench.py under the A/B switches of tools/ab_switches.py (PPMS_* environment variables -> ppmstereo_amd.engine.TUNING).
-usage (GPU box): PPMS_CONV5_PAD2X=0 python tools/ab_bench.py --steps 20 --no-cpu-baseline --no-encoders"""
+usage (on an MI355X): PPMS_CONV5_PAD2X=0 python tools/ab_bench.py --steps 20 --full --no-cpu-baseline --no-encoders"""
 import os
 import runpy
 import sys

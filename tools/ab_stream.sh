@@ -1,7 +1,7 @@
 # A/B of the register-streamed small-map kernel inside the clip (GPU box): bash tools/ab_stream.sh <outdir>
 out=${1:-gpurun_out/ab_stream}; mkdir -p $out
 for v in 0 1 all 0 1; do
-  PPMS_STREAM=$v timeout -k 10 200 python tools/ab_bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-encoders > $out/bench_$v.json 2> $out/bench_$v.err || exit 1
+  PPMS_STREAM=$v timeout -k 10 200 python tools/ab_bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-encoders > $out/bench_$v.json 2> $out/bench_$v.err || exit 1
   python - $out/bench_$v.json $v <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).readline())
