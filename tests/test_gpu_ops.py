@@ -111,8 +111,11 @@ def test_ops_refuse_cpu_tensors(lib):
 
 # ------------------------------------------------------------------------------------------------ conv GEMM
 def _run_conv(L, x_list, weight, bias, k3, T, H, W, act=0, kind=0, aux=None, z=None, scale=1.0, seg_pad=None, version=2, wm=0, pre=None, nslice=None, ysweep=False,
-              m_pad=None, lo_zero_from=0):
-    """x_list: list of (P, C_i) fp32 CPU tensors (channel-last).  Returns (P, Cout) fp32 from the SP output."""
+              m_pad=None, lo_zero_from=0, halo=0, ops=None):
+    """x_list: list of (P, C_i) fp32 CPU tensors (channel-last).  Returns (P, Cout) fp32 from the SP output.
+    halo > 0: a rank's window of a frame-sharded clip (ppms_conv.t_halo) -- x_list holds T + 2 halo frames, the middle T are the launch's own
+    frames and the outer ones fill the halo slabs around them (temporal taps read them); aux / z / pre stay (P, .) over the own frames.
+    nslice = -1: the library plans the K slices (conv_gemm5 / conv_gemm2; must find some).  ops: a list that receives the launched ConvOp."""
     from ppmstereo_amd.engine import ConvOp, epilogue
     from ppmstereo_amd.packing import pack_conv2, pack_conv4
     tile_px = 0
@@ -124,8 +127,11 @@ def _run_conv(L, x_list, weight, bias, k3, T, H, W, act=0, kind=0, aux=None, z=N
     segs, keep = [], []
     seg_pad = seg_pad or [((x.shape[1] + 31) // 32) * 32 for x in x_list]
     for x, cp in zip(x_list, seg_pad):
-        t = L.SPTensor(P, cp, DEV)
-        t.set_f32(x.to(DEV))
+        assert x.shape[0] == (T + 2 * halo) * H * W, (x.shape, T, halo)
+        t = L.SPTensor(P, cp, DEV, before=halo * H * W, after=halo * H * W)
+        hi = x.to(DEV).to(torch.bfloat16)                                   # every row: the halo slabs and the own frames
+        t.data[0, :, :x.shape[1]] = hi
+        t.data[1, :, :x.shape[1]] = (x.to(DEV) - hi.float()).to(torch.bfloat16)
         segs.append(t.view())
         keep.append(t)
     wpack = weight
@@ -163,11 +169,18 @@ def _run_conv(L, x_list, weight, bias, k3, T, H, W, act=0, kind=0, aux=None, z=N
     d.kt, d.kh, d.kw = k3
     d.M = d.m_split = meta["M"]
     d.lo_zero_from = lo_zero_from
+    d.t_halo = halo
     d.epi[0] = e
     if version == 5 and nslice is not None and nslice < 0:                 # -1: let the library plan the slices (must find some)
         nslice = int(L.load().ppms_conv_gemm5_slices(C.byref(d)))
         assert nslice >= 2, nslice
-    ConvOp(d, keep, version, tile_px if version == 5 else wm, nslice=nslice if nslice is not None else 1, ysweep=ysweep)()
+    if version == 2 and nslice is not None and nslice < 0:
+        nslice = int((L.load().ppms_conv_gemm2_ysweep_slices if ysweep else L.load().ppms_conv_gemm2_slices)(C.byref(d)))
+        assert nslice >= 2, nslice
+    op = ConvOp(d, keep, version, tile_px if version == 5 else wm, nslice=nslice if nslice is not None else 1, ysweep=ysweep)
+    op()
+    if ops is not None:
+        ops.append(op)
     torch.cuda.synchronize()
     sp = out.to_f32()[:, :cout].cpu()
     assert (sp - outf[:, :cout].cpu()).abs().max() < 2e-5 * (1 + sp.abs().max()), "SP and fp32 outputs of one launch disagree"
@@ -366,40 +379,165 @@ def test_conv_stream_epilogues_and_hoisted_share(lib):
     assert maxdiff(run(kind=L.EPI_GRU, aux=aux, z=z), (1 - z) * aux + z * torch.tanh(full)) < 5e-5
 
 
+# ------------------------------------------------------------------------------------------------ temporal halos (frame-sharded windows)
+# A rank of a frame-sharded clip (ppmstereo_amd/dist.py, HALO = 2) holds its T own frames between halo slabs that hold its neighbours' boundary
+# frames, and every conv with temporal taps reads them (ppms_conv.t_halo = HALO, engine.py).  Per-rank T: 2 (= HALO: T = 8 over 4 ranks) and 5
+# (BASELINE config 4: T = 40 over 8 GPUs); maps with ragged tiles in both directions (16 x 13 for conv_gemm6, 32-pixel rows / blocks elsewhere);
+# HALO_FULL_MAP = config 4's 1/4-scale map of one rank (250 conv_gemm6 tiles: the size the engine picks conv_gemm6 / conv_gemm5 for).
+HALO_GEOMS = [(2, 20, 30), (5, 37, 29)]
+HALO_FULL_MAP = (5, 80, 128)
+
+HALO_CASES = [
+    # name, version (5007 / 5008: conv_gemm5 with its 7- / 8-block tile forced), segs, cout, k3, m_pad, nslice (-1: the library's plan),
+    # lo_zero_from, wm (conv_stream's tile hint), with the GRU epilogue too, geometries (None: HALO_GEOMS)
+    # conv_gemm6: the STREAM form of the GRU's pass T (z | r to 256 rows; 128 rows too, though the engine packs it for > 128 rows only and runs
+    # q3 on conv_gemm2: g2_t5), its two-phase K loop (lo_zero_from), the 3x3x3 heads
+    ("g6_t5_m256", 8, [128, 256], 256, (5, 1, 1), 256, None, 0, 0, True, None),
+    ("g6_t5_m128", 8, [128, 256], 128, (5, 1, 1), 128, None, 0, 0, False, None),
+    ("g6_t5_m128_one_seg", 8, [128], 128, (5, 1, 1), 128, None, 0, 0, False, None),
+    ("g6_t5_m256_lz", 8, [128, 256], 256, (5, 1, 1), 256, None, 256, 0, False, None),
+    ("g6_t5_m128_lz", 8, [128, 256], 128, (5, 1, 1), 128, None, 256, 0, False, None),
+    ("g6_333_m256", 8, [128], 256, (3, 3, 3), 256, None, 0, 0, True, None),
+    ("g6_333_m192", 8, [128], 190, (3, 3, 3), 192, None, 0, 0, False, None),
+    # conv_gemm5: 2-D sweep, GEMM mode (kh = kw = 1), the K-sliced form (min_windows5 reads t_halo; >= 8 tiles for the library to slice)
+    ("g5_333", 5007, [128], 256, (3, 3, 3), None, None, 0, 0, False, None),
+    ("g5_t5_gemm_m256", 5008, [128, 256], 256, (5, 1, 1), None, None, 0, 0, True, None),
+    ("g5_t5_gemm_m128", 5007, [128, 256], 128, (5, 1, 1), None, None, 0, 0, False, None),
+    ("g5_333_sliced", 5, [128], 256, (3, 3, 3), None, -1, 0, 0, False, [(5, 20, 30), (2, 37, 29)]),
+    # conv_gemm2 un-sliced and K-sliced (the library's plan), conv_stream with both tiles
+    ("g2_t5", 2, [128, 64], 128, (5, 1, 1), None, None, 0, 0, False, None),
+    ("g2_t5_sliced", 2, [128, 64], 128, (5, 1, 1), None, -1, 0, 0, True, None),
+    ("g2_333_sliced", 2, [128], 256, (3, 3, 3), None, -1, 0, 0, False, None),
+    ("st_t5_32px", 7, [128, 64], 128, (5, 1, 1), None, None, 0, 1, False, None),
+    ("st_t5_64px", 7, [128, 64], 128, (5, 1, 1), None, None, 0, 2, False, None),
+    ("st_333_32px", 7, [128], 256, (3, 3, 3), None, None, 0, 1, True, None),
+    ("st_333_64px", 7, [128], 256, (3, 3, 3), None, None, 0, 2, False, None),
+]
+HALO_FULL_MAP_CASES = ("g6_t5_m256", "g6_t5_m128", "g6_t5_m256_lz", "g6_333_m256", "g5_t5_gemm_m256")
+
+
+def conv_form(op):
+    """A ConvOp's launch form as the halo census of tests/test_gpu_sharded.py counts it: (version, kt, kh, kw, M, K-sliced, y-swept)."""
+    d = op.desc
+    return (op.version, d.kt, d.kh, d.kw, d.M, op.nslice > 1, bool(op.ysweep))
+
+
+def _halo_case_form(case):
+    _, version, _, cout, k3, m_pad, nslice, _, _, _, _ = case
+    return (5 if version in (5, 5007, 5008) else version, *k3, m_pad or (128 if cout <= 128 else 256), nslice is not None and nslice != 1, False)
+
+
+# every launch form that test_conv_temporal_halo_vs_fp64 runs with a halo (each case asserts it launched its form): the sharded cascade's census
+# of t_halo > 0 launches must stay inside this set
+HALO_COVERED_FORMS = frozenset(_halo_case_form(c) for c in HALO_CASES)
+
+
+def _ref_conv64(x, weight, bias, k3, Tf, H, W, lo, hi):
+    """float64 conv3d over the whole Tf-frame volume x ((Tf H W, Cin), channel-last; zero padding at its ends), output frames [lo, hi) only
+    (one frame at a time: the unfolded operand of a 5 x 80 x 128 map would not be small)."""
+    kt, kh, kw = k3
+    x5 = F.pad(x.double().reshape(Tf, H, W, -1).permute(3, 0, 1, 2)[None], (0, 0, 0, 0, kt // 2, kt // 2))
+    w5 = (weight if weight.dim() == 5 else weight[:, :, None]).double()
+    b = None if bias is None else bias.double()
+    ys = [F.conv3d(x5[:, :, t:t + kt], w5, b, padding=(0, kh // 2, kw // 2)) for t in range(lo, hi)]
+    return torch.cat(ys, 2)[0].permute(1, 2, 3, 0).reshape((hi - lo) * H * W, -1)
+
+
+def _halo_inputs(segs, Tf, HW, lz, seed):
+    xs = [hash_normal((Tf * HW, c), seed + i) for i, c in enumerate(segs)]      # halo frames: random, non-zero data like the own frames
+    if lz:
+        xcat = torch.cat(xs, 1)
+        xcat[:, lz:] = xcat[:, lz:].to(torch.bfloat16).float()                # bf16-exact from channel lz on (the attention's read-out hid)
+        xs = list(torch.split(xcat, segs, 1))
+    return xs
+
+
+def _halo_params():
+    out = []
+    for case in HALO_CASES:
+        name, k3 = case[0], case[4]
+        geoms = list(case[10] or HALO_GEOMS) + ([HALO_FULL_MAP] if name in HALO_FULL_MAP_CASES else [])
+        for T, H, W in geoms:
+            for halo in sorted({2, k3[0] // 2}):              # HALO (deeper than a 3-frame kernel reaches) and exactly the taps' reach
+                out.append(pytest.param(case, T, H, W, halo, id=f"{name}-T{T}_{H}x{W}-halo{halo}"))
+    return out
+
+
+@pytest.mark.parametrize("case,T,H,W,halo", _halo_params())
+def test_conv_temporal_halo_vs_fp64(lib, case, T, H, W, halo):
+    """Every conv kernel form a frame-sharded window runs with t_halo > 0 (HALO_CASES) against the float64 conv3d of the whole (T + 2 halo)-frame
+    volume, middle T frames: the launch over the own frames reads the taps that reach past them from the halo slabs, never zero padding.  And
+    against the same kernel launched on the whole volume: conv_gemm6 and un-sliced conv_gemm5 with a fixed tile give the SAME BITS -- a tile's
+    window order is a function of its frame's temporal-tap range (kz0, kz1) alone, and those coincide (conv_gemm6.hip / conv_gemm5.hip) --;
+    conv_stream and conv_gemm2 tile the flattened pixels (a tile may span frames, so the tiles differ with T), and a K-sliced plan depends on the
+    tile count: there the two agree to fp32 rounding.  At config 4's 1/4-scale map the library must rate the halo'd launch as the engine does."""
+    name, version, segs, cout, k3, m_pad, nslice, lz, wm, gru, _ = case
+    Tf, HW = T + 2 * halo, H * W
+    xs = _halo_inputs(segs, Tf, HW, lz, 640)
+    cin = sum(segs)
+    wt = hash_normal((cout, cin, *k3), 650) / math.sqrt(cin * k3[0] * k3[1] * k3[2])
+    bs = hash_normal((cout,), 651) * 0.1
+    ref = _ref_conv64(torch.cat(xs, 1), wt, bs, k3, Tf, H, W, halo, halo + T)
+    tol = 3e-5 * max(1.0, ref.abs().max().item())
+    kw = dict(version=version, wm=wm, m_pad=m_pad, lo_zero_from=lz)
+    ops = []
+    got = _run_conv(lib, xs, wt, bs, k3, T, H, W, nslice=nslice, halo=halo, ops=ops, **kw)
+    assert maxdiff(got, ref) < tol, name
+    assert conv_form(ops[0]) == _halo_case_form(case) and ops[0].desc.t_halo == halo, (conv_form(ops[0]), name)
+    if (T, H, W) == HALO_FULL_MAP:
+        rate = lib.load().ppms_conv_gemm6_applicable if ops[0].version == 8 else lib.load().ppms_conv_gemm5_applicable
+        assert rate(C.byref(ops[0].desc)) == 1, name
+    whole = _run_conv(lib, xs, wt, bs, k3, Tf, H, W, **kw)[halo * HW:(halo + T) * HW]       # (un-sliced: the plan of Tf frames may slice differently)
+    if version == 8 or (version in (5007, 5008) and nslice is None):
+        assert torch.equal(got, whole), f"{name}: {int((got != whole).sum())} outputs differ from the whole-volume launch"
+    else:
+        assert maxdiff(got, whole) < tol, name
+    if gru:
+        aux = hash_normal((T * HW, cout), 652)
+        z = torch.sigmoid(hash_normal((T * HW, cout), 653))
+        got = _run_conv(lib, xs, wt, bs, k3, T, H, W, nslice=nslice, halo=halo, kind=lib.EPI_GRU, aux=aux, z=z, **kw)
+        assert maxdiff(got, (1 - z) * aux + z * torch.tanh(ref)) < 5e-5, name
+
+
+@pytest.mark.parametrize("edge", ["first", "last", "alone"])
+@pytest.mark.parametrize("name", ["g6_t5_m256", "g6_333_m192", "g5_333", "g5_t5_gemm_m256", "g2_t5_sliced", "g2_333_sliced", "st_t5_32px", "st_333_64px"])
+def test_conv_temporal_halo_edge_ranks(lib, name, edge):
+    """The ranks at the ends of the window: their outer halo slab stays zero (dist.FrameShard exchanges with neighbours only), which must equal the
+    zero padding of the whole-window conv -- the fp64 conv3d of the window as it really is, starting (first) / ending (last) at the rank's frames
+    ("alone": a window of one rank, both slabs zero)."""
+    case = next(c for c in HALO_CASES if c[0] == name)
+    _, version, segs, cout, k3, m_pad, nslice, lz, wm, _, _ = case
+    T, H, W, halo = 2, 20, 30, 2
+    Tf, HW = T + 2 * halo, H * W
+    xs = _halo_inputs(segs, Tf, HW, lz, 660)
+    lo, hi = (halo if edge in ("first", "alone") else 0), (Tf - halo if edge in ("last", "alone") else Tf)    # the window's frames
+    for x in xs:
+        x[:lo * HW] = 0
+        x[hi * HW:] = 0
+    cin = sum(segs)
+    wt = hash_normal((cout, cin, *k3), 661) / math.sqrt(cin * k3[0] * k3[1] * k3[2])
+    bs = hash_normal((cout,), 662) * 0.1
+    ref = _ref_conv64(torch.cat(xs, 1)[lo * HW:hi * HW], wt, bs, k3, hi - lo, H, W, halo - lo, halo - lo + T)
+    got = _run_conv(lib, xs, wt, bs, k3, T, H, W, version=version, wm=wm, m_pad=m_pad, nslice=nslice, lo_zero_from=lz, halo=halo)
+    assert maxdiff(got, ref) < 3e-5 * max(1.0, ref.abs().max().item()), (name, edge)
+
+
 @pytest.mark.parametrize("version", [7, 2])
 @pytest.mark.parametrize("T,H,W,halo,k3", [(3, 4, 8, 2, (5, 1, 1)), (2, 5, 7, 1, (3, 3, 3)), (1, 3, 5, 2, (5, 1, 1))])
 def test_conv_temporal_halo_slabs(lib, version, T, H, W, halo, k3):
     """ppms_conv.t_halo (frame-sharded windows, ppmstereo_amd/dist.py): the T frames of a rank sit between `halo` readable frames of its
     neighbours, and temporal taps read those instead of zero padding.  A conv over the middle T frames of a (T + 2 halo)-frame volume with
     t_halo = halo must equal the middle of the conv over the whole volume wherever the taps stay inside it (every output frame: the halo is as
-    deep as the taps reach) -- conv_stream (tiles that span frames, per-tile temporal-tap skipping) and conv_gemm2."""
-    from ppmstereo_amd.engine import ConvOp, epilogue
-    from ppmstereo_amd.packing import pack_conv2, pack_stream
-    L = lib
+    deep as the taps reach) -- conv_stream (tiles that span frames, per-tile temporal-tap skipping) and conv_gemm2, on tiny maps (the large-map
+    kernels and the K-sliced forms: test_conv_temporal_halo_vs_fp64)."""
     assert halo >= k3[0] // 2
     Tf, HW = T + 2 * halo, H * W
     cin, cout = 64, 64
     xf = hash_normal((Tf * HW, cin), 600)
     wt = hash_normal((cout, cin, *k3), 601) / math.sqrt(cin * k3[0] * k3[1] * k3[2])
     bs = hash_normal((cout,), 602) * 0.1
-    ref = _ref_conv([xf], wt, bs, k3, Tf, H, W)[halo * HW:(halo + T) * HW]
-    xt = L.SPTensor(T * HW, cin, DEV, before=halo * HW, after=halo * HW)
-    hi = xf.to(torch.bfloat16)
-    xt.data[0].copy_(hi.to(DEV))
-    xt.data[1].copy_((xf - hi.float()).to(torch.bfloat16).to(DEV))
-    packed, b, meta = (pack_stream if version == 7 else pack_conv2)(wt.to(DEV), bs.to(DEV), [cin], [cin])
-    out = L.SPTensor(T * HW, meta["M"], DEV)
-    d = L.Conv()
-    d.seg[0] = xt.view()
-    d.nseg, d.w, d.bias = 1, packed.data_ptr(), b.data_ptr()
-    d.T, d.H, d.W = T, H, W
-    d.kt, d.kh, d.kw = k3
-    d.t_halo = halo
-    d.M = d.m_split = meta["M"]
-    d.epi[0] = epilogue(n_valid=cout, out_sp=out.view())
-    ConvOp(d, [packed, b], version, nslice=1)()
-    torch.cuda.synchronize()
-    got = out.to_f32()[:, :cout].cpu()
+    ref = _ref_conv64(xf, wt, bs, k3, Tf, H, W, halo, halo + T)
+    got = _run_conv(lib, [xf], wt, bs, k3, T, H, W, version=version, nslice=1, halo=halo)
     assert maxdiff(got, ref) < 3e-5 * max(1.0, ref.abs().max().item())
 
 
@@ -1180,6 +1318,51 @@ def test_tap_gather_sum(lib, T, H, W):
     L.check(L.load().ppms_tap_gather_sum(yd.data_ptr(), 64, bd.data_ptr(), out2.data_ptr(), 4, None, 0, 2, 3, 3, 3, T, H, W, 0, L.stream_ptr()))
     torch.cuda.synchronize()
     assert torch.equal(out2, out)
+
+
+@pytest.mark.parametrize("k3", [(3, 3, 3), (3, 1, 3)])
+@pytest.mark.parametrize("t_halo", [1, 2])
+@pytest.mark.parametrize("T,H,W", [(2, 5, 9), (5, 10, 16)])
+def test_tap_gather_sum_temporal_halo(lib, T, H, W, t_halo, k3):
+    """ppms_tap_gather_sum with t_halo (the flow head's tail on a rank of a frame-sharded window reads the halo slabs of FH2Y): against the fp64 conv
+    of the whole (T + 2 t_halo)-frame volume, middle T frames.  The buffer has HALO = 2 frames on each side, as the engine's; frames beyond t_halo
+    hold NaN, so a read past the halo shows.  (3,3,3): the unrolled kernel, (3,1,3): the generic one."""
+    L = lib
+    HALO, HW, ntap = 2, H * W, k3[0] * k3[1] * k3[2]
+    Tf = T + 2 * t_halo
+    x = hash_normal((Tf * HW, 256), 520)
+    wt = hash_normal((2, 256, *k3), 521) / math.sqrt(256 * ntap)
+    bs = hash_normal((2,), 522)
+    w1 = wt.permute(2, 3, 4, 0, 1).reshape(ntap * 2, 256)                       # row = tap * 2 + cout
+    yd = torch.full(((T + 2 * HALO) * HW, 64), float("nan"), device=DEV)
+    yd[(HALO - t_halo) * HW:(HALO + T + t_halo) * HW, :2 * ntap] = (x.double() @ w1.double().t()).float().to(DEV)   # the 1x1 GEMM's output
+    out, bd = torch.zeros(T * HW, 4, device=DEV), bs.to(DEV)
+    L.check(L.load().ppms_tap_gather_sum(yd[HALO * HW:].data_ptr(), 64, bd.data_ptr(), out.data_ptr(), 4, None, 0, 2, *k3, T, H, W, t_halo,
+                                         L.stream_ptr()))
+    torch.cuda.synchronize()
+    assert maxdiff(out[:, :2], _ref_conv64(x, wt, bs, k3, Tf, H, W, t_halo, t_halo + T)) < 3e-5
+
+
+@pytest.mark.parametrize("t_halo", [1, 2])
+@pytest.mark.parametrize("T,H,W", [(2, 5, 9), (5, 8, 12)])
+def test_convex_upsample_3d_temporal_halo(lib, T, H, W, t_halo):
+    """ppms_convex_upsample_3d on a rank of a frame-sharded window (use_convex_3d): the 27 neighbours of a frame's pixel reach +-1 frame into the
+    flow's halo slabs.  Against the oracle on the extended volume with the mask zero outside the own frames (tests/sharded_oracle.py does the same
+    on the CPU), in float64; the engine passes t_halo = HALO = 2.  Frames of the buffer beyond t_halo hold NaN."""
+    L = lib
+    HALO, HW = 2, H * W
+    Tf = T + 2 * t_halo
+    fl, mk = hash_normal((Tf, 2, H, W), 530), hash_normal((T, 432, H, W), 531)
+    fd = torch.full(((T + 2 * HALO) * HW, 2), float("nan"), device=DEV)
+    fd[(HALO - t_halo) * HW:(HALO + T + t_halo) * HW] = fl.permute(0, 2, 3, 1).reshape(-1, 2).to(DEV)
+    md = mk.permute(0, 2, 3, 1).reshape(T * HW, 432).contiguous().to(DEV)
+    out = torch.zeros(T, 2, 4 * H, 4 * W, device=DEV)
+    L.check(L.load().ppms_convex_upsample_3d(fd[HALO * HW:].data_ptr(), md.data_ptr(), 432, out.data_ptr(), T, H, W, t_halo, L.stream_ptr()))
+    torch.cuda.synchronize()
+    m_ext = torch.zeros(Tf, 432, H, W, dtype=torch.float64)
+    m_ext[t_halo:t_halo + T] = mk.double()
+    ref = O.convex_upsample_3d(fl.double(), m_ext, 4, Tf)[t_halo:t_halo + T]
+    assert maxdiff(out, ref) < 5e-6 * max(1.0, ref.abs().max().item())
 
 
 @pytest.mark.parametrize("P", [5 * 7 * 9 + 3, 16384 + 128 + 5])

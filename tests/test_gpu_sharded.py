@@ -1,7 +1,8 @@
 """GPU: the frame-sharded engine (SURVEY.md section 8e level 2, BASELINE configs 4-5) on the real kernels.  One GPU box has one
 GPU, so two ranks share it and talk over gloo (dist.FrameShard stages device tensors through the host in that case; on a
 multi-GPU node the same calls go through RCCL).  Each rank runs its block of frames of a T = 8 window through the whole 3-scale
-cascade and compares with the unsharded cascade run in the same process."""
+cascade and compares with the unsharded cascade run in the same process -- and a T = 10 window over two ranks at the per-GPU geometry of
+BASELINE configs 4 and 5, where the 1/4 scale runs the large-map kernels with temporal halos."""
 import os
 import socket
 import sys
@@ -22,8 +23,9 @@ def _free_port():
     return p
 
 
-def _worker(rank, world, port, out, c3d):
+def _worker(rank, world, port, out, c3d, T=8, H=64, W=256, census=False):
     sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     from ppmstereo_amd import dist as D
     from ppmstereo_amd import weights as Wm
@@ -32,7 +34,7 @@ def _worker(rank, world, port, out, c3d):
     D.init_from_env("gloo")
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
-    T, H, W, iters = 8, 64, 256, 4
+    iters = 4
     model = PPMStereoHotPath(use_convex_3d=c3d).load_hot_path_weights(Wm.hot_path_weights(use_convex_3d=c3d)).to(dev).eval()
     feats = synth_cascade_feats(T, H, W, seed=5)
     shard = D.FrameShard(rank, world, T)
@@ -40,12 +42,23 @@ def _worker(rank, world, port, out, c3d):
     p1, u1 = [], []
     d_sh, c_sh = model.cascade(local, iters, T, p1, u1, shard=shard)
     torch.cuda.synchronize()
+    halo_forms = None
+    if census:                      # the launches of the 1/4-scale engine that read halo slabs, by launch form (test_gpu_ops.conv_form)
+        from ppmstereo_amd.engine import ConvOp
+        from test_gpu_ops import conv_form
+        eng = next(e for e in model.update_block04._engines.values() if e.halo > 0)
+        assert (eng.T, eng.h, eng.w) == (shard.f, H // 4, W // 4)
+        halo_forms = {}
+        for name, op in eng.op.items():
+            if isinstance(op, ConvOp) and op.desc.t_halo > 0:
+                assert op.desc.t_halo == eng.halo, name
+                halo_forms.setdefault(conv_form(op), []).append(name)
     D.barrier()
     d_full, c_full = model.cascade({k: v.to(dev) for k, v in feats.items()}, iters, T)
     torch.cuda.synchronize()
     sl = slice(shard.lo, shard.hi)
     res = dict(disp=(d_sh - d_full[sl]).abs().max().item(), unc=(c_sh - c_full[sl]).abs().max().item(), npred=len(p1),
-               finite=bool(torch.isfinite(d_sh).all()), scale=d_full.abs().max().item())
+               finite=bool(torch.isfinite(d_sh).all()), scale=d_full.abs().max().item(), census=halo_forms)
     torch.save(res, out + f".{rank}")
     D.barrier()
     torch.distributed.destroy_process_group()
@@ -64,6 +77,34 @@ def test_sharded_cascade_equals_unsharded_on_the_gpu(tmp_path, world, c3d):
     mp.spawn(_worker, args=(world, _free_port(), out, c3d), nprocs=world, join=True)
     for r in range(world):
         res = torch.load(out + f".{r}")
+        assert res["finite"] and res["npred"] == 8
+        assert res["disp"] <= 5e-5 * max(1.0, res["scale"]), res
+        assert res["unc"] <= 2e-4, res
+
+
+@pytest.mark.parametrize("H,W,c3d", [pytest.param(320, 512, False, id="config4"), pytest.param(320, 512, True, id="config4_c3d"),
+                                       pytest.param(736, 1280, False, id="config5")])
+def test_sharded_cascade_at_a_baseline_rank_geometry(tmp_path, H, W, c3d):
+    """BASELINE configs 4 / 5 per GPU: 5 frames of a T = 10 window on each of two ranks -- at 320 x 512 a 5 x 80 x 128 map at the 1/4 scale (config 4),
+    at 736 x 1280 a 5 x 184 x 320 one (config 5) -- large enough for the library to rate conv_gemm6 there, so the GRU's pass T (5,1,1) and the 3x3x3
+    heads run on the large-map kernels with t_halo > 0 (the T = 8, 64 x 256 test above runs only the small-map kernels).  Each rank takes a census of its 1/4-scale engine's halo'd launches by
+    form: it must hold conv_gemm6 launches with kt = 5 and kt = 3, and every form must be one that test_gpu_ops.test_conv_temporal_halo_vs_fp64
+    checks with a halo (HALO_COVERED_FORMS).  Then the same bounds as above against the unsharded cascade of the same process.
+    (What the census finds at both sizes: conv_gemm6 for the 256-row (5,1,1) convs pre_zr3 / zr3 / zr3_x and the 3x3x3 fh1 -- and m1 with
+    use_convex_3d --, conv_gemm2 for the 128-row (5,1,1) convs pre_q3 / q3 / q3_x: conv_gemm6's STREAM form is packed for > 128 rows only.)"""
+    from test_gpu_ops import HALO_COVERED_FORMS
+    world = 2
+    out = str(tmp_path / "shb.pt")
+    mp.spawn(_worker, args=(world, _free_port(), out, c3d, 10, H, W, True), nprocs=world, join=True)
+    for r in range(world):
+        res = torch.load(out + f".{r}")
+        census = res["census"]
+        print(f"[halo census] {H}x{W} rank {r} c3d={c3d}: " + "; ".join(f"{k}: {' '.join(v)}" for k, v in sorted(census.items())))
+        print(f"[sharded T=10 {H}x{W}] rank {r} c3d={c3d}: disp {res['disp']:.3e} (bound {5e-5 * max(1.0, res['scale']):.3e}), "
+              f"unc {res['unc']:.3e} (bound 2e-4)")
+        assert any(k[0] == 8 and k[1] == 5 for k in census) and any(k[0] == 8 and k[1] == 3 for k in census), census
+        missing = {k: v for k, v in census.items() if k not in HALO_COVERED_FORMS}
+        assert not missing, f"halo'd launch forms without a kernel-level halo test: {missing}"
         assert res["finite"] and res["npred"] == 8
         assert res["disp"] <= 5e-5 * max(1.0, res["scale"]), res
         assert res["unc"] <= 2e-4, res
