@@ -14,15 +14,13 @@ nearest upsampling and InstanceNorm are small kernels of encoder_ops.hip.  108 b
 from __future__ import annotations
 
 from collections import OrderedDict
-import ctypes as C
 from typing import Dict, List, Optional
 
 import torch
 import torch.nn as nn
 
 from . import _lib as L
-from . import packing as _packing
-from .engine import ConvOp, TUNING, epilogue
+from .convplan import CONV2, GEMM1, STREAM, conv_desc, epilogue, pack_conv, plan_conv
 from .weights import CNET_DEPTHS, CNET_DIMS
 
 
@@ -102,15 +100,8 @@ class Feature(nn.Module):
         vec: Dict[str, torch.Tensor] = {}
 
         def put(name, w, b, segs, pads=None):
-            w4 = w.detach().to(device)
-            if w4.dim() == 2:
-                w4 = w4[:, :, None, None]
-            packed, bias, meta = _packing.pack_conv2(w4, b.detach().to(device), segs, pads if pads is not None else [((c + 31) // 32) * 32 for c in segs])
-            pk[name] = (packed, bias, meta, tuple(w4.shape[2:]))
-            if tuple(w4.shape[2:]) == (1, 1) and sum(meta["seg_padded"]) % 64 == 0:          # 1x1 layers the thin-GEMM kernel may serve (gemm1.hip)
-                pk[name + "@1"] = _packing.pack_gemm1(w4, b.detach().to(device), segs, meta["seg_padded"], None, meta["M"])
-            if TUNING["stream"] and sum(meta["seg_padded"]) % 64 == 0:      # layers the register-streamed small-map kernel may serve (conv_stream.hip; same switch as the loop's engine)
-                pk[name + "@7"] = _packing.pack_stream(w4, b.detach().to(device), segs, meta["seg_padded"], None, meta["M"])
+            # the thin GEMM for the 1x1 layers, the register-streamed kernel for the small maps, else conv_gemm2
+            pk[name] = pack_conv(w.detach().to(device), b.detach().to(device), segs, pads, kernels=(CONV2, GEMM1, STREAM))
 
         def v(name, t):
             vec[name] = t.detach().float().reshape(-1).to(device).contiguous()
@@ -194,31 +185,7 @@ class _CnetEngine:
         self.ws = torch.empty(max(in_ws, grn_ws), device=device, dtype=torch.uint8)
 
         def conv(name, segs: List[L.SP], n_h_w, e0: L.Epilogue):
-            packed_w, bias, meta, k2 = pk[name]
-            dd = L.Conv()
-            for i, t in enumerate(segs):
-                dd.seg[i] = t
-            dd.nseg, dd.w, dd.bias = len(segs), packed_w.data_ptr(), bias.data_ptr()
-            dd.T, dd.H, dd.W = n_h_w
-            dd.kt, dd.kh, dd.kw = 1, k2[0], k2[1]
-            dd.M = dd.m_split = meta["M"]
-            assert [t.c for t in segs] == list(meta["seg_padded"]), (name, [t.c for t in segs], meta["seg_padded"])
-            dd.epi[0] = e0
-            if name + "@1" in pk:
-                p1, b1, _ = pk[name + "@1"]
-                d1 = L.Conv.from_buffer_copy(bytes(dd))
-                d1.w, d1.bias = p1.data_ptr(), b1.data_ptr()
-                if lib.ppms_gemm1_applicable(C.byref(d1)) == 1:
-                    self.steps.append(ConvOp(d1, [p1, b1], 6, device=device))
-                    return
-            if TUNING["stream"] and name + "@7" in pk:                        # small maps: no K slices, no reduce launch (the library rates it)
-                p7, b7, _ = pk[name + "@7"]
-                d7 = L.Conv.from_buffer_copy(bytes(dd))
-                d7.w, d7.bias = p7.data_ptr(), b7.data_ptr()
-                if lib.ppms_conv_stream_applicable(C.byref(d7)) == 1:
-                    self.steps.append(ConvOp(d7, [p7, b7], 7, wm_hint=TUNING["stream_hint"], device=device))
-                    return
-            self.steps.append(ConvOp(dd, [packed_w, bias], 2, device=device))
+            self.steps.append(plan_conv(conv_desc(segs, n_h_w, pk[name][CONV2][2]["taps"], e0), pk[name], device=device))
 
         def call(fn):
             self.steps.append(fn)

@@ -13,7 +13,6 @@ the data between the image and the NCHW feature maps; buffers and descriptors ar
 """
 from __future__ import annotations
 
-import ctypes as C
 from collections import OrderedDict
 from typing import Dict, List, Optional, Tuple
 
@@ -21,8 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from . import packing as _packing
-from .engine import TUNING, ConvOp, epilogue
+from .convplan import CONV2, CONV6, conv_desc, epilogue, pack_conv, plan_conv
 
 
 def _s2d_weight(w: torch.Tensor, pad: int) -> torch.Tensor:
@@ -87,15 +85,9 @@ class BasicEncoder(nn.Module):
         pk: Dict[str, tuple] = {}
 
         def put(name, w, b, cin_real, cin_pad):
-            packed, bias, meta = _packing.pack_conv2(w.detach().to(device), b.detach().to(device), [cin_real], [cin_pad])
-            pk[name] = (packed, bias, meta, tuple(w.shape[2:]))
-            kh, kw = w.shape[2:]
-            if kh == 3 and kw == 3 and cin_pad % 32 == 0 and 64 < w.shape[0] <= 128:
-                # the 3x3 layers with 96 / 128 couts (the 1/4-resolution stages): conv_gemm6 (conv_gemm6.hip; pack_conv6 with (ky, kx) flattened into
-                # the sweep axis, as engine.PackedBlock packs the update block's 3x3 convs) where the library rates its tile fill
-                w5 = w.detach().to(device)[:, :, None]
-                sweep = w5.reshape(w5.shape[0], w5.shape[1], 1, 1, kh * kw).contiguous()
-                pk[name + "@6"] = _packing.pack_conv6(sweep, b.detach().to(device), [cin_real], [cin_pad], None, 128)
+            # the 3x3 layers with 96 / 128 couts (the 1/4-resolution stages) may run on conv_gemm6 where the library rates its tile fill
+            cg6 = tuple(w.shape[2:]) == (3, 3) and cin_pad % 32 == 0 and 64 < w.shape[0] <= 128
+            pk[name] = pack_conv(w.detach().to(device), b.detach().to(device), [cin_real], [cin_pad], kernels=(CONV2, CONV6) if cg6 else (CONV2,))
 
         put("conv1", _s2d_weight(self.conv1.weight, 3), self.conv1.bias, 12, 32)
         for layer in (1, 2, 3):
@@ -170,23 +162,10 @@ class _FnetEngine:
         self.ops: List[tuple] = []                                   # ("conv", ConvOp) | ("call", fn)
 
         def conv(name, src: L.SPTensor, dst_f32: torch.Tensor, n, h, w):
-            packed, bias, meta, k2 = pk[name]
-            d = L.Conv()
-            d.seg[0] = src.view()
-            d.nseg, d.w, d.bias = 1, packed.data_ptr(), bias.data_ptr()
-            d.T, d.H, d.W = n, h, w
-            d.kt, d.kh, d.kw = 1, k2[0], k2[1]
-            d.M = d.m_split = meta["M"]
+            meta = pk[name][CONV2][2]
             assert src.channels == meta["cpad"] and dst_f32.shape[1] == meta["M"], (name, src.channels, meta["cpad"], dst_f32.shape, meta["M"])
-            d.epi[0] = epilogue(n_valid=meta["M"], out_f32=dst_f32, out_f32_ld=meta["M"])
-            if TUNING["conv6"] and name + "@6" in pk and meta["M"] == 128:      # (TUNING["conv6"] = False: every conv of the encoder on conv_gemm2, as the engine's fallback)
-                packed6, bias6, meta6 = pk[name + "@6"]
-                d6 = L.Conv.from_buffer_copy(bytes(d))
-                d6.w, d6.bias = packed6.data_ptr(), bias6.data_ptr()
-                if meta6["M"] == 128 and self.lib.ppms_conv_gemm6_applicable(C.byref(d6)) == 1:
-                    self.ops.append(("conv", ConvOp(d6, [src, dst_f32, packed6, bias6], 8, device=device)))
-                    return
-            self.ops.append(("conv", ConvOp(d, [src, dst_f32, packed, bias], 2, device=device)))
+            d = conv_desc([src.view()], (n, h, w), meta["taps"], epilogue(n_valid=meta["M"], out_f32=dst_f32, out_f32_ld=meta["M"]))
+            self.ops.append(("conv", plan_conv(d, pk[name], [src, dst_f32], device=device)))
 
         def norm(src_f32: torch.Tensor, C_, hw, dst: L.SPTensor, relu: bool, res: Optional[L.SPTensor] = None):
             ld = src_f32.shape[1]

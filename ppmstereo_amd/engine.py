@@ -18,7 +18,6 @@ Stage methods mirror the reference calls one to one:
 """
 from __future__ import annotations
 
-import contextlib
 import ctypes as C
 import math
 from typing import Dict, List, Optional
@@ -27,43 +26,10 @@ import torch
 
 from . import _lib as L
 from . import packing as _packing
+from .convplan import (ALL_KERNELS, CONV2, CONV2_SWEPT, CONV6, KERNEL_TIMING, TUNING, ConvOp, PwChain, TimedCall,  # (tests, tools, bench.py import them from here)
+                       attn_p_format, conv_desc, epilogue, pack_conv, plan_conv)
 
 TOP_K = 5
-# Which HIP kernel generation serves a convolution where more than one applies.  These are the measured-best settings (DESIGN.md
-# section 5); tools/ab_switches.py maps PPMS_* environment variables onto this table for A/B runs on the GPU box -- the product itself
-# reads no environment variable.  Every setting runs HIP kernels only.
-TUNING = dict(
-    conv5=True,           # one 8-wave workgroup per CU, 7- / 8-block tiles (conv_gemm5.hip) where it applies
-    conv6=True,           # one wave per SIMD on the 16x16x32 MFMA, 16 x 13-pixel tiles (conv_gemm6.hip, round 5) where the library rates its fill >= 85 %
-    conv6_stream=True,    # conv_gemm6's STREAM form for the (5,1,1) convs of the GRU's pass T (else conv_gemm5 / conv_gemm2)
-    conv6_pad2x=False,    # conv_gemm6 also for convs whose couts fill only half of the padded rows (convf2: 64 of 128 -- 50 us instead of 63 + 117 us of K-sliced launch + reduce, but on the side stream it takes whole CUs from convc2: 35.5 vs 35.4 ms per clip)
-    conv5_sliced=False,   # its K-sliced form on the 1/8, 1/16 maps: correct (tests) but slower than conv_gemm2's slicing there
-    conv5_gemm=True,      # its GEMM mode for the 256-cout convs without a spatial sweep ((5,1,1) GRU pass, 1x1 heads)
-    pwchain=True,         # fused per-pixel layer chains of the correlation encoder
-    ysweep=True,          # conv_gemm2: one y-swept window per (dt, chunk) for (1, kh, 1) convs
-    win2d=False,          # conv_gemm2: 2-D window for kh, kw > 1 (measured neutral to slower)
-    slices=True,          # grid-level K slicing of the convs of small maps (1/16, 1/8 scales)
-    hoist=True,           # iteration-invariant inp share of the GRU gates computed once per scale
-    gemm1=True,           # thin-GEMM kernel (gemm1.hip) for the 1x1 convolutions / Linear layers it serves
-    stream=True,          # register-streamed kernel (conv_stream.hip) where the library rates it faster (small maps: no K slices, no reduce launch);
-                          # "all": wherever it serves a conv of a map of <= 16 384 pixels (A/B runs)
-    stream_hint=0,        # its tile: 0 = the library chooses, 1 / 2 = 32- / 64-pixel tiles
-    hid_exact=True,       # hoisted blocks: the GRU convs read [h | mf, hid] with weights (W_mf + W_mfg | beta W_mfg) instead of [h | mf, mfg]; hid is a
-                          # bf16 tensor (all-zero lo plane), so the products with that plane are skipped (ppms_conv.lo_zero_from)
-    convf2_unsliced=False,  # the flow encoder's 3x3 128 -> 64 conv without K slices on large maps (measured neutral: 40.3 / 40.2 ms per clip)
-    conv5_m192=True,      # conv_gemm5's three-cout-block layout for the 190 / 192-cout convs (else padded to 256 rows)
-    fork_min_pixels=0,    # independent branches of an iteration run on the side stream only on maps with at least this many pixels (0: always)
-    conv6_grouped=True,   # the two 128 -> 128 (1,1,5) tails of convz1 / convr1 as ONE grouped conv_gemm6 launch (ppms_conv.groups = 2, M = 256 wave layout) where
-                          # conv_gemm6 serves the map, instead of two M = 128 launches on two streams
-    attn_p="fp16",        # format of the unnormalised probabilities P~ in the memory read-out's P~ V product (and of the V^T image the to_v conv writes):
-                          # "fp16" = 11 significand bits, "bf16" = 8 (what flash-attention itself uses) at the same MFMA count.  The reference fixtures were
-                          # generated with fp32 P (tools/gen_golden.py:89-95); with bf16 P~ the iters = 20 cascade ends 1.3e-3 px from them, with fp16 inside 1e-3
-    conv5_pad2x=False,    # conv_gemm5 also for convs whose couts fill only half of the padded rows (convf2: 64 of 128 -- 78 us instead of 65 + 143 us
-                          # of the K-sliced form, but on the side stream it then competes with convc2 for whole CUs: clip time unchanged, 40.8 ms)
-)
-
-
-pack_conv = _packing.pack_conv2
 
 
 def temporal_pe(T: int, channels: int) -> torch.Tensor:
@@ -80,169 +46,9 @@ def temporal_pe(T: int, channels: int) -> torch.Tensor:
     return pe
 
 
-def attn_p_format() -> int:
-    """TUNING["attn_p"] as ppms_mem_attn's p_format / ppms_epilogue.vt_f16 (include/ppms.h)."""
-    fmt = TUNING["attn_p"]
-    if fmt not in ("fp16", "bf16"):
-        raise ValueError(f"TUNING['attn_p'] must be 'fp16' or 'bf16', got {fmt!r}")
-    return L.ATTN_P_FP16 if fmt == "fp16" else L.ATTN_P_BF16
-
-
 def softmax_scale(c: int = 128) -> float:
     """ppmstereo.py:494: c^-0.5 * log_12000(key channels = 2c)."""
     return c ** -0.5 * math.log(2 * c, 12000)
-
-
-# Per-launch HIP events (ConvOp.events, Engine.enable_attn_timing) are only recorded while this is on: bench.py samples them in a
-# subset of its timed steps -- every event pair is two more packets in the queue, and with ~330 of them per clip the clip gets ~5 % slower.
-KERNEL_TIMING = {"on": True}
-
-
-class ConvOp:
-    """One implicit-GEMM launch: host descriptor (validated by the library) + its device copy."""
-
-    def __init__(self, desc: L.Conv, keep: list, version: int = 2, wm_hint: int = 0, nslice: Optional[int] = None, ysweep: bool = False,
-                 device=None):
-        self.desc, self.version, self.wm_hint, self.ysweep = desc, version, wm_hint, ysweep
-        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        raw = bytes(desc)
-        self.dev = torch.frombuffer(bytearray(raw), dtype=torch.uint8).clone().to(device)
-        self.keep = keep            # tensors whose storage the descriptor points at
-        self.events = None          # list collecting (start, stop) HIP events per launch when kernel timing is on
-        # small maps: K-sliced launch + reduce kernel (nslice None: ask the library; own workspace per op because ops
-        # of the two streams run concurrently)
-        self.nslice, self.ws = 1, None
-        if version == 5 and nslice is not None and nslice > 1:      # conv_gemm5's K-sliced form (same workspace layout as conv_gemm2's)
-            self.nslice = int(nslice)
-            self.ws = torch.empty(int(L.load().ppms_conv_gemm2_slice_workspace_bytes(C.byref(desc), self.nslice)), dtype=torch.uint8, device=device)
-        if version == 2 and wm_hint == 0 and (nslice is not None or TUNING["slices"]):
-            plan = L.load().ppms_conv_gemm2_ysweep_slices if ysweep else L.load().ppms_conv_gemm2_slices
-            self.nslice = max(1, int(plan(C.byref(desc)))) if nslice is None else nslice
-            if self.nslice > 1:
-                self.ws = torch.empty(int(L.load().ppms_conv_gemm2_slice_workspace_bytes(C.byref(desc), self.nslice)), dtype=torch.uint8, device=device)
-
-    def flops(self) -> float:
-        """Algorithmic FLOPs of one launch: 2 * pixels * stored couts * input channels of the launch * taps (zero-padding
-        taps included, as a FLOP counter on the reference conv would)."""
-        d = self.desc
-        cout = d.epi[0].n_valid + (d.epi[1].n_valid if d.m_split < d.M else 0)
-        cin = d.seg[0].c if d.groups == 2 else sum(d.seg[i].c for i in range(d.nseg))       # (grouped: every cout reads its own segment only)
-        return 2.0 * d.T * d.H * d.W * cout * cin * d.kt * d.kh * d.kw
-
-    def mfma_per_product(self) -> float:
-        """MFMAs the kernel issues per algorithmic bf16x3 product: 3 (hi*hi, lo*hi, hi*lo), less the hi*lo products conv_gemm5 / conv_gemm6 leave out for the
-        input channels from `lo_zero_from` on (bf16-exact activations: their lo plane is all zero).  bench.py prices a launch against
-        dense bf16 / this."""
-        d = self.desc
-        cin = sum(d.seg[i].c for i in range(d.nseg))
-        lz = int(d.lo_zero_from)
-        if self.version not in (5, 8) or lz <= 0 or lz >= cin or lz % (16 if self.version == 5 else 32):
-            return 3.0
-        if self.version == 8:
-            # conv_gemm6's K loop runs the windows with a lo plane first (phase 0) and needs an EVEN number of k32-steps there (its weight registers
-            # alternate between two stages): plan6 (conv_gemm6.hip) ignores lo_zero_from when (lo_zero_from / 32) * (k32-steps per window) is odd
-            nsweep = d.kh * d.kw if (d.kh > 1 or d.kw > 1) else 1
-            if ((lz // 32) * nsweep) & 1:
-                return 3.0
-        return 3.0 - (cin - lz) / cin
-
-    def __call__(self):
-        ev = self.events if KERNEL_TIMING["on"] else None
-        if ev is not None:                  # bench.py: HIP events on the launch stream around this launch
-            pair = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            pair[0].record()
-            self._launch()
-            pair[1].record()
-            ev.append(pair)
-        else:
-            self._launch()
-
-    def _launch(self):
-        if self.version == 5 and self.nslice > 1:
-            L.check(L.load().ppms_conv_gemm5_sliced(C.byref(self.desc), self.dev.data_ptr(), self.wm_hint, self.nslice, self.ws.data_ptr(), L.stream_ptr()))
-        elif self.version == 5:
-            L.check(L.load().ppms_conv_gemm5(C.byref(self.desc), self.dev.data_ptr(), self.wm_hint, L.stream_ptr()))
-        elif self.version == 8:
-            L.check(L.load().ppms_conv_gemm6(C.byref(self.desc), self.dev.data_ptr(), L.stream_ptr()))
-        elif self.version == 6:
-            L.check(L.load().ppms_gemm1(C.byref(self.desc), self.dev.data_ptr(), self.wm_hint, L.stream_ptr()))
-        elif self.version == 7:
-            L.check(L.load().ppms_conv_stream(C.byref(self.desc), self.dev.data_ptr(), self.wm_hint, L.stream_ptr()))
-        elif self.ysweep:
-            L.check(L.load().ppms_conv_gemm2_ysweep(C.byref(self.desc), self.dev.data_ptr(), self.nslice, L.ptr(self.ws), L.stream_ptr()))
-        elif self.nslice > 1:
-            L.check(L.load().ppms_conv_gemm2_sliced(C.byref(self.desc), self.dev.data_ptr(), self.nslice, self.ws.data_ptr(), L.stream_ptr()))
-        else:
-            L.check(L.load().ppms_conv_gemm2(C.byref(self.desc), self.dev.data_ptr(), self.wm_hint, L.stream_ptr()))
-
-
-def epilogue(kind=L.EPI_STORE, act=L.ACT_NONE, scale=1.0, n_valid=0, out_sp: Optional[L.SP] = None, out_f32=None, out_f32_ld=0,
-             out_vt=None, aux_sp: Optional[L.SP] = None, aux_f32=None, aux_f32_ld=0, pre_f32=None, pre_off=0, vt_f16=None) -> L.Epilogue:
-    e = L.Epilogue()
-    e.kind, e.act, e.scale, e.n_valid = kind, act, scale, n_valid
-    if out_sp is not None:
-        e.out_sp = out_sp
-    e.out_f32 = None if out_f32 is None else out_f32.data_ptr()
-    e.out_f32_ld = out_f32_ld
-    e.out_vt = None if out_vt is None else out_vt.data_ptr()
-    e.vt_f16 = attn_p_format() if vt_f16 is None else int(vt_f16)      # (only read with out_vt)
-    if aux_sp is not None:
-        e.aux_sp = aux_sp
-    e.aux_f32 = None if aux_f32 is None else aux_f32.data_ptr()
-    e.aux_f32_ld = aux_f32_ld
-    if pre_f32 is not None:                  # (P, ld) fp32, this half's columns start at pre_off
-        e.pre_f32, e.pre_f32_ld = pre_f32.data_ptr() + 4 * pre_off, pre_f32.shape[1]
-    return e
-
-
-class TimedCall:
-    """A small-kernel launch (python callable) that bench.py can bracket with HIP events like a ConvOp."""
-
-    def __init__(self, fn):
-        self.fn, self.events = fn, None
-
-    def __call__(self):
-        ev = self.events if KERNEL_TIMING["on"] else None
-        if ev is not None:
-            pair = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            pair[0].record()
-            self.fn()
-            pair[1].record()
-            ev.append(pair)
-        else:
-            self.fn()
-
-
-class PwChain:
-    """One fused per-pixel layer chain launch (pwchain.hip): host parameter block + device copy."""
-
-    def __init__(self, inp: L.SP, out: L.SP, layers, pixels: int, keep: list, device=None):
-        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        cp = L.ChainParams()
-        cp.inp, cp.out, cp.nlayers, cp.P = inp, out, len(layers), pixels
-        # (pwchain.hip keeps two activation buffers: the residual operand = the chain input survives only up to the second layer)
-        assert not any(resid for _, _, resid, _ in layers[2:]), "pwchain: a residual layer must be the first or the second of its chain"
-        for i, (pack, n_valid, resid, post) in enumerate(layers):
-            packed, bias, meta = pack
-            assert meta["nk"] == 2 and meta["version"] == 2, "chain layers are 1x1 convs with 64 (padded) input channels"
-            ly = cp.layer[i]
-            ly.w, ly.bias, ly.M, ly.n_valid, ly.resid = packed.data_ptr(), bias.data_ptr(), meta["M"], n_valid, int(resid)
-            ly.post_s = None if post is None else post[0].data_ptr()
-            ly.post_t = None if post is None else post[1].data_ptr()
-            keep += [packed, bias]
-        self.pixels, self.keep, self.cp = pixels, keep, cp
-        self.dev = torch.frombuffer(bytearray(bytes(cp)), dtype=torch.uint8).clone().to(device)
-        self.events = None
-
-    def __call__(self):
-        ev = self.events if KERNEL_TIMING["on"] else None
-        if ev is not None:
-            pair = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            pair[0].record()
-        L.check(L.load().ppms_pwchain(self.dev.data_ptr(), self.pixels, L.stream_ptr()))
-        if ev is not None:
-            pair[1].record()
-            ev.append(pair)
 
 
 class PackedBlock:
@@ -250,62 +56,20 @@ class PackedBlock:
 
     def __init__(self, sd: Dict[str, torch.Tensor], device):
         g = lambda k: sd[k].detach().to(device=device, dtype=torch.float32)
-        self.w: Dict[str, tuple] = {}
+        self.w: Dict[str, dict] = {}               # name -> the packs of every kernel that may serve the conv (convplan.pack_conv)
 
-        self.w4: Dict[str, tuple] = {}             # conv_gemm5 packs (MFMA-fragment order, sweep-ordered taps, M padded to 128)
-        self.w6: Dict[str, tuple] = {}             # conv_gemm6 packs (16-cout x 32-channel MFMA A-operand images, sweep-ordered taps)
-        self.w1: Dict[str, tuple] = {}             # gemm1 packs of the 1x1 convolutions (MFMA A-operand images per 32 couts x 16 channels)
-        self.w7: Dict[str, tuple] = {}             # conv_stream packs (the same images per tap, natural tap order) for the small maps
-
-        def put(name, weight, bias, segs, seg_pad=None, cout_map=None, m_pad=None):
-            self.w[name] = pack_conv(weight, bias, segs, seg_pad, cout_map, m_pad)
-            w5 = weight if weight.dim() == 5 else weight[:, :, None]
-            if TUNING["gemm1"] and tuple(w5.shape[2:]) == (1, 1, 1) and not name.endswith("_y"):
-                meta2 = self.w[name][2]
-                if sum(meta2["seg_padded"]) % 64 == 0:
-                    self.w1[name] = _packing.pack_gemm1(weight, bias, segs, meta2["seg_padded"], cout_map, meta2["M"])
-            if TUNING["stream"] and not name.endswith("_y") and sum(self.w[name][2]["seg_padded"]) % 64 == 0:
-                self.w7[name] = _packing.pack_stream(weight, bias, segs, self.w[name][2]["seg_padded"], cout_map, self.w[name][2]["M"])
-            sweep = w5                                                     # x sweep: natural order
-            if w5.shape[3] > 1 and w5.shape[4] > 1:
-                # k-step order of the 2-D window sweep: (ky, kx) flattened into the x axis
-                sweep = w5.reshape(w5.shape[0], w5.shape[1], w5.shape[2], 1, w5.shape[3] * w5.shape[4]).contiguous()
-                self.w[name + "_2d"] = pack_conv(sweep, bias, segs, seg_pad, cout_map, m_pad)
-            elif w5.shape[3] > 1:
-                sweep = w5.transpose(3, 4).contiguous()                      # y sweep: kh / kw swapped
-            rows = (max(cout_map) + 1) if cout_map is not None else w5.shape[0]
-            if TUNING["conv6"] and TUNING["conv6_stream"] and w5.shape[2] > 1 and w5.shape[3] == 1 and w5.shape[4] == 1 and rows > 128 and not name.endswith("_y"):
-                # (kt,1,1) convs to 256 couts (the z/r conv of the GRU's pass T): conv_gemm6's STREAM form -- one k32-step per 32-channel window of a temporal
-                # tap, three window buffers (1/4 scale: 131 us against conv_gemm5's 155; the 128-cout q conv stays on conv_gemm2: 85 us against 89 there)
-                pads6 = list(seg_pad) if seg_pad is not None else [((c + 31) // 32) * 32 for c in segs]
-                if all(p % 32 == 0 for p in pads6):
-                    self.w6[name] = _packing.pack_conv6(w5, bias, segs, pads6, cout_map, 128 if rows <= 128 else (192 if rows <= 192 else 256))
-            if TUNING["conv5"] and (w5.shape[3] > 1 or w5.shape[4] > 1) and not name.endswith("_y"):
-                # conv_gemm5 serves 128, 192 and 256 rows (192: three 64-cout blocks dealt over the eight waves, round 4 -- convc2's 192 and
-                # final_conv's 190 couts no longer run padded to 256)
-                m5 = 128 if rows <= 128 else (192 if rows <= 192 and TUNING["conv5_m192"] else 256)
-                self.w4[name] = _packing.pack_conv4(sweep, bias, segs, seg_pad, cout_map, m5)
-                pads6 = list(seg_pad) if seg_pad is not None else [((c + 31) // 32) * 32 for c in segs]
-                if TUNING["conv6"] and all(p % 32 == 0 for p in pads6):
-                    self.w6[name] = _packing.pack_conv6(sweep, bias, segs, pads6, cout_map, 128 if rows <= 128 else (192 if rows <= 192 else 256))
-            elif TUNING["conv5"] and TUNING["conv5_gemm"] and w5.shape[3] == 1 and w5.shape[4] == 1 and rows > 128 and not name.endswith("_y"):
-                # no spatial sweep: conv_gemm5's GEMM mode (windows of 64 channels) when the segments come in such multiples.  Only the
-                # 256-cout convs (GRU pass-T z/r 197 -> 164 us, mask_2d.2 62 -> 46 us at the 1/4 scale): with 128 couts the two K-groups
-                # get 32-channel windows = 2 k-steps per window, too short a DMA lookahead (pass-T q 110 -> 122 us, to_v 44 -> 66 us)
-                pads = list(seg_pad) if seg_pad is not None else [((c + 31) // 32) * 32 for c in segs]
-                if all(p % 32 == 0 for p in pads):
-                    self.w4[name] = _packing.pack_conv4(w5, bias, segs, pads, cout_map, (rows + 127) // 128 * 128)
-
+        def put(name, weight, bias, segs, seg_pad=None, cout_map=None, m_pad=None, kernels=ALL_KERNELS):
+            self.w[name] = pack_conv(weight, bias, segs, seg_pad, cout_map, m_pad, kernels)
 
         e = "encoder."
         put("init0", g(e + "init_conv.0.weight"), g(e + "init_conv.0.bias"), [128])
         put("init2", g(e + "init_conv.2.weight"), g(e + "init_conv.2.bias"), [64])
         c1 = e + "convc1."
-        put("ffn1_0", g(c1 + "ffn1.0.weight"), g(c1 + "ffn1.0.bias"), [36], [64])
-        put("ffn1_2", g(c1 + "ffn1.2.weight"), g(c1 + "ffn1.2.bias"), [54], [64])
-        put("pw", g(c1 + "pw.weight"), g(c1 + "pw.bias"), [36], [64])
-        put("ffn2_0", g(c1 + "ffn2.0.weight"), g(c1 + "ffn2.0.bias"), [36], [64])
-        put("ffn2_2", g(c1 + "ffn2.2.weight"), g(c1 + "ffn2.2.bias"), [54], [64])
+        put("ffn1_0", g(c1 + "ffn1.0.weight"), g(c1 + "ffn1.0.bias"), [36], [64], kernels=(CONV2,))
+        put("ffn1_2", g(c1 + "ffn1.2.weight"), g(c1 + "ffn1.2.bias"), [54], [64], kernels=(CONV2,))
+        put("pw", g(c1 + "pw.weight"), g(c1 + "pw.bias"), [36], [64], kernels=(CONV2,))
+        put("ffn2_0", g(c1 + "ffn2.0.weight"), g(c1 + "ffn2.0.bias"), [36], [64], kernels=(CONV2,))
+        put("ffn2_2", g(c1 + "ffn2.2.weight"), g(c1 + "ffn2.2.bias"), [54], [64], kernels=(CONV2,))
         self.dw = []
         for i, k in ((0, 1), (1, 7)):
             w = torch.zeros(64, k * k, device=device)
@@ -329,21 +93,17 @@ class PackedBlock:
         put("zr1_0", cat(gr + "convz1.0.weight", gr + "convr1.0.weight"), cat(gr + "convz1.0.bias", gr + "convr1.0.bias"), [128, 384])
         put("z1_2", g(gr + "convz1.2.weight"), g(gr + "convz1.2.bias"), [128])
         put("r1_2", g(gr + "convr1.2.weight"), g(gr + "convr1.2.bias"), [128])
-        self.zr1_2_grouped = None                   # z1_2 | r1_2 as one grouped convolution (conv_gemm6 only)
-        if TUNING["conv6"] and TUNING["conv6_grouped"]:
-            self.zr1_2_grouped = _packing.pack_conv6_grouped([g(gr + "convz1.2.weight"), g(gr + "convr1.2.weight")], [g(gr + "convz1.2.bias"), g(gr + "convr1.2.bias")], 128)
+        # z1_2 | r1_2 as one grouped convolution (conv_gemm6 only)
+        self.w["zr1_2"] = {CONV6: _packing.pack_conv6_grouped([g(gr + "convz1.2.weight"), g(gr + "convr1.2.weight")], [g(gr + "convz1.2.bias"), g(gr + "convr1.2.bias")], 128)}
         put("q1", g(gr + "convq1.weight"), g(gr + "convq1.bias"), [128, 384])
         for n in ("2", "3"):
             put("zr" + n, cat(gr + f"convz{n}.weight", gr + f"convr{n}.weight"), cat(gr + f"convz{n}.bias", gr + f"convr{n}.bias"), [128, 384])
             put("q" + n, g(gr + f"convq{n}.weight"), g(gr + f"convq{n}.bias"), [128, 384])
-        # the (1,5,1) pass again with kh / kw swapped: k-step order of conv_gemm2's y-swept form (one halo'd window per (dt, chunk))
-        put("zr2_y", cat(gr + "convz2.weight", gr + "convr2.weight").transpose(3, 4).contiguous(), cat(gr + "convz2.bias", gr + "convr2.bias"), [128, 384])
-        put("q2_y", g(gr + "convq2.weight").transpose(3, 4).contiguous(), g(gr + "convq2.bias"), [128, 384])
         # The GRU input is [h | inp, mf, mfg] (ppmtereo_update.py:292-310, 985-988) and inp does not change between the
         # iterations of one scale: its share of every gate pre-activation is computed once per scale ("*_i" packs, with
         # the bias) and added in the epilogue of the per-iteration convs over [h | mf, mfg] ("*_h" packs).  Not for
         # update_block16, whose time / space attention rewrites all of x every iteration.
-        self.hoist = "time_attn.temporal_fc.weight" not in sd and TUNING["hoist"]
+        self.hoist = "time_attn.temporal_fc.weight" not in sd
         if self.hoist:
             for name in ("zr1_0", "q1", "zr2", "q2", "zr3", "q3"):
                 if name.startswith("zr"):
@@ -352,19 +112,15 @@ class PackedBlock:
                 else:
                     wt, bs = g(gr + f"convq{name[1:]}.weight"), g(gr + f"convq{name[1:]}.bias")
                 w_h = torch.cat([wt[:, :128], wt[:, 256:]], 1).contiguous()
-                put(name + "_i", wt[:, 128:256].contiguous(), bs, [128])
+                # (the once-per-scale shares have never run on conv_gemm2's y-swept form: no such pack)
+                put(name + "_i", wt[:, 128:256].contiguous(), bs, [128], kernels=ALL_KERNELS - {CONV2_SWEPT})
                 put(name + "_h", w_h, None, [128, 256])
-                if name in ("zr2", "q2"):
-                    put(name + "_h_y", w_h.transpose(3, 4).contiguous(), None, [128, 256])
-                if TUNING["hid_exact"]:
-                    # W_mf mf + W_mfg (mf + beta hid) = (W_mf + W_mfg) mf + (beta W_mfg) hid  (ppmstereo.py:552, ppmtereo_update.py:985-988):
-                    # the third input block becomes the attention's bf16 read-out itself (sums formed in fp64, rounded once)
-                    beta = float(sd["aggregator.beta"].detach().double().reshape(-1)[0])
-                    wd = wt.double()
-                    w_x = torch.cat([wd[:, :128], wd[:, 256:384] + wd[:, 384:], beta * wd[:, 384:]], 1).float().contiguous()
-                    put(name + "_x", w_x, None, [128, 256])
-                    if name in ("zr2", "q2"):
-                        put(name + "_x_y", w_x.transpose(3, 4).contiguous(), None, [128, 256])
+                # W_mf mf + W_mfg (mf + beta hid) = (W_mf + W_mfg) mf + (beta W_mfg) hid  (ppmstereo.py:552, ppmtereo_update.py:985-988):
+                # the third input block becomes the attention's bf16 read-out itself (sums formed in fp64, rounded once)
+                beta = float(sd["aggregator.beta"].detach().double().reshape(-1)[0])
+                wd = wt.double()
+                w_x = torch.cat([wd[:, :128], wd[:, 256:384] + wd[:, 384:], beta * wd[:, 384:]], 1).float().contiguous()
+                put(name + "_x", w_x, None, [128, 256])
         put("fh1", g("flow_head.conv1.weight"), g("flow_head.conv1.bias"), [128])
         # flow_head.conv2 (256 -> 2, 3x3x3) as a 1x1 GEMM to 27*2 = 54 channels + shifted sum (ppms_tap_gather_sum)
         w2 = g("flow_head.conv2.weight")                                     # (2, 256, 3, 3, 3)
@@ -498,91 +254,11 @@ class ScaleEngine:
             self.shard.halo(full.view(self.T + 2 * self.halo, self.n, full.shape[1]), k)
 
     # ------------------------------------------------------------------ descriptors
-    def _conv(self, wname, segs: List[L.SP], k3, epi0: L.Epilogue, epi1: Optional[L.Epilogue] = None, m_split: Optional[int] = None,
-              keep=(), nslice: Optional[int] = None, lo_zero_from: int = 0) -> ConvOp:
-        packed, bias, meta = self.pk.w[wname] if isinstance(wname, str) else wname
-        d = L.Conv()
-        for i, s in enumerate(segs):
-            d.seg[i] = s
-        d.nseg = len(segs)
-        assert [s.c for s in segs] == meta["seg_padded"], (wname, [s.c for s in segs], meta["seg_padded"])
-        d.w, d.bias = packed.data_ptr(), bias.data_ptr()
-        d.T, d.H, d.W = self.T, self.h, self.w
-        d.t_halo = self.halo if k3[0] > 1 else 0        # temporal taps read the neighbour ranks' boundary frames from the halo slabs
-        d.lo_zero_from = lo_zero_from                    # input channels from here on are bf16-exact (all-zero lo plane): a promise, see ppms.h
-        d.kt, d.kh, d.kw = k3
-        d.M = meta["M"]
-        d.m_split = meta["M"] if m_split is None else m_split
-        d.epi[0] = epi0
-        if epi1 is not None:
-            d.epi[1] = epi1
-        version = 2
-        if TUNING["gemm1"] and isinstance(wname, str) and tuple(k3) == (1, 1, 1) and wname in self.pk.w1:
-            packed1, bias1, _ = self.pk.w1[wname]
-            d1 = L.Conv.from_buffer_copy(bytes(d))
-            d1.w, d1.bias = packed1.data_ptr(), bias1.data_ptr()
-            if self.lib.ppms_gemm1_applicable(C.byref(d1)) == 1:          # (2: served, but the implicit GEMM is as fast on a map this large)
-                return ConvOp(d1, [packed1, bias1, *keep], 6, device=self.dev)
-        if TUNING["stream"] and isinstance(wname, str) and wname in self.pk.w7:
-            # small maps (1/8, 1/16 scales): the register-streamed kernel -- no K slices, no reduce launch
-            packed7, bias7, _ = self.pk.w7[wname]
-            d7 = L.Conv.from_buffer_copy(bytes(d))
-            d7.w, d7.bias = packed7.data_ptr(), bias7.data_ptr()
-            rate = self.lib.ppms_conv_stream_applicable(C.byref(d7))
-            if rate == 1 or (rate == 2 and TUNING["stream"] == "all" and self.P <= 16384):      # ("all": A/B runs only)
-                return ConvOp(d7, [packed7, bias7, *keep], 7, wm_hint=TUNING["stream_hint"], device=self.dev)
-        if isinstance(wname, str):
-            op = self._try_fragment_kernels(wname, d, m_split, keep)
-            if op is not None:
-                return op
-        if TUNING["ysweep"] and isinstance(wname, str) and k3[1] > 1:
-            # kh > 1 on a map the large-map kernel does not take: conv_gemm2 with one window for all taps of a (dt, chunk)
-            # (y-swept "_y" pack for kw == 1, 2-D window "_2d" pack otherwise), when the halo'd window fits
-            key = wname + ("_y" if k3[2] == 1 else "_2d")
-            if (k3[2] == 1 or TUNING["win2d"]) and key in self.pk.w and self.lib.ppms_conv_gemm2_ysweep_slices(C.byref(d)) > 0:
-                packed_y, bias_y, _ = self.pk.w[key]
-                d.w, d.bias = packed_y.data_ptr(), bias_y.data_ptr()
-                return ConvOp(d, [packed_y, bias_y, *keep], 2, ysweep=True, device=self.dev)
-        return ConvOp(d, [packed, bias, *keep], version, nslice=nslice, device=self.dev)
-
-    def _try_fragment_kernels(self, wname: str, d: L.Conv, m_split, keep) -> Optional[ConvOp]:
-        """conv_gemm6 (one wave per SIMD, 16x16x32 MFMA, pack_conv6) where the library rates its tile fill, else conv_gemm5 (weights in
-        MFMA-fragment order, pack_conv4, couts padded to 128) when it serves the conv."""
-        if TUNING["conv6"] and wname in self.pk.w6 and (TUNING.get("conv6_only") is None or wname in TUNING["conv6_only"]):
-            packed6, bias6, meta6 = self.pk.w6[wname]
-            d6 = L.Conv.from_buffer_copy(bytes(d))
-            d6.w, d6.bias, d6.M = packed6.data_ptr(), bias6.data_ptr(), meta6["M"]
-            if m_split is None:
-                d6.m_split = meta6["M"]
-            real6 = d6.epi[0].n_valid + (d6.epi[1].n_valid if d6.m_split < d6.M else 0)
-            # (couts filling only half of the padded rows -- convf2's 64 of 128 -- still pay: 3x3 128 -> 64 at the 1/4 scale costs ~45 us here against
-            #  63 + 117 us for conv_gemm2's K-sliced launch + its reduce launch; TUNING["conv6_pad2x"])
-            if (2 * real6 > meta6["M"] or (TUNING["conv6_pad2x"] and 2 * real6 == meta6["M"])) and self.lib.ppms_conv_gemm6_applicable(C.byref(d6)) == 1:
-                return ConvOp(d6, [packed6, bias6, *keep], 8, device=self.dev)
-        if not TUNING["conv5"] or wname not in self.pk.w4:
-            return None
-        packed4, bias4, meta4 = self.pk.w4[wname]
-        d4 = L.Conv.from_buffer_copy(bytes(d))
-        d4.w, d4.bias, d4.M = packed4.data_ptr(), bias4.data_ptr(), meta4["M"]
-        if m_split is None:
-            d4.m_split = meta4["M"]
-        real = d4.epi[0].n_valid + (d4.epi[1].n_valid if d4.m_split < d4.M else 0)
-        if TUNING["conv5"] and (2 * real > meta4["M"] or (TUNING["conv5_pad2x"] and 2 * real == meta4["M"])) and self.lib.ppms_conv_gemm5_applicable(C.byref(d4)):
-            return ConvOp(d4, [packed4, bias4, *keep], 5, device=self.dev)
-        if TUNING["conv5"] and TUNING["conv5_sliced"] and 2 * real > meta4["M"]:
-            ns = int(self.lib.ppms_conv_gemm5_slices(C.byref(d4)))
-            if ns >= 2:
-                return ConvOp(d4, [packed4, bias4, *keep], 5, nslice=ns, device=self.dev)
-        return None
-
-    def _conv_padded(self, wname, *a, **k) -> ConvOp:
-        """The 190 / 192-cout convs (convc2, final_conv): conv_gemm5 / conv_gemm6 in their three-cout-block layout where they serve the map, else the
-        tight conv_gemm2 pack."""
-        if TUNING["conv5"] and wname in self.pk.w4:
-            op = self._conv(wname, *a, **k)
-            if op.version in (5, 8):
-                return op
-        return self._conv(wname, *a, **k)
+    def _conv(self, packs, segs: List[L.SP], k3, epi0: L.Epilogue, epi1: Optional[L.Epilogue] = None, m_split: int = 0, keep=(),
+              lo_zero_from: int = 0) -> ConvOp:
+        """packs: a PackedBlock weight name or a pack_conv result.  Temporal taps read the neighbour ranks' boundary frames from the halo slabs."""
+        d = conv_desc(segs, (self.T, self.h, self.w), k3, epi0, epi1, m_split, self.halo if k3[0] > 1 else 0, lo_zero_from)
+        return plan_conv(d, self.pk.w[packs] if isinstance(packs, str) else packs, keep, device=self.dev)
 
     def _build_descriptors(self):
         E, X, H = epilogue, self.X, self.Hb
@@ -592,34 +268,27 @@ class ScaleEngine:
         o = self.op
         self._qk_ops: Dict[int, ConvOp] = {}
         o["init0"] = self._conv("init0", [inp], k3, E(act=L.ACT_RELU, n_valid=64, out_sp=self.ZT.view(0, 64)))
-        if TUNING["pwchain"]:
-            w = self.pk.w
-            (w1, b1, _), _ = self.pk.dw
-            dw1 = (w1.reshape(64).contiguous(), b1)
-            # chain A: x1 = gelu(x + ffn1(x)); x2 = gelu(x1 + dw1x1(x1))      CORR -> C2
-            o["chainA"] = PwChain(self.CORR.view(), self.C2.view(), [(w["ffn1_0"], 54, False, None), (w["ffn1_2"], 36, True, dw1)], self.P, [dw1[0]],
-                                 device=self.dev)
-            # chain B: x4 = gelu(x3 + pw x3); cor = gelu(ffn2(x4))              C1 -> COR256
-            o["chainB"] = PwChain(self.C1.view(), self.COR256.view(), [(w["pw"], 36, True, None), (w["ffn2_0"], 54, False, None),
-                                                                       (w["ffn2_2"], 256, False, None)], self.P, [], device=self.dev)
-            (_, _, _), (w7, b7, _) = self.pk.dw
-            o["dw7"] = TimedCall(lambda: L.check(self.lib.ppms_dwconv_gelu(self.C2.view(0, 40), self.C1.view(0, 40), w7.data_ptr(), b7.data_ptr(), 7,
-                                                                            self.T, self.h, self.w, L.stream_ptr())))
-        o["ffn1_0"] = self._conv("ffn1_0", [self.CORR.view()], k1, E(act=L.ACT_GELU, n_valid=54, out_sp=self.T1.view()))
-        o["ffn1_2"] = self._conv("ffn1_2", [self.T1.view()], k1, E(L.EPI_RESID, L.ACT_GELU, n_valid=36, out_sp=self.C1.view(), aux_sp=self.CORR.view()))
-        o["pw"] = self._conv("pw", [self.C1.view()], k1, E(L.EPI_RESID, L.ACT_GELU, n_valid=36, out_sp=self.C2.view(), aux_sp=self.C1.view()))
-        o["ffn2_0"] = self._conv("ffn2_0", [self.C2.view()], k1, E(act=L.ACT_GELU, n_valid=54, out_sp=self.T1.view()))
-        o["ffn2_2"] = self._conv("ffn2_2", [self.T1.view()], k1, E(act=L.ACT_GELU, n_valid=256, out_sp=self.COR256.view()))
+        # the correlation encoder's per-pixel layers as fused chains (pwchain.hip) around the depthwise 7x7
+        w = {k: self.pk.w[k][CONV2] for k in ("ffn1_0", "ffn1_2", "pw", "ffn2_0", "ffn2_2")}
+        (w1, b1, _), (w7, b7, _) = self.pk.dw
+        dw1 = (w1.reshape(64).contiguous(), b1)
+        # chain A: x1 = gelu(x + ffn1(x)); x2 = gelu(x1 + dw1x1(x1))      CORR -> C2
+        o["chainA"] = PwChain(self.CORR.view(), self.C2.view(), [(w["ffn1_0"], 54, False, None), (w["ffn1_2"], 36, True, dw1)], self.P, [dw1[0]],
+                             device=self.dev)
+        # chain B: x4 = gelu(x3 + pw x3); cor = gelu(ffn2(x4))              C1 -> COR256
+        o["chainB"] = PwChain(self.C1.view(), self.COR256.view(), [(w["pw"], 36, True, None), (w["ffn2_0"], 54, False, None),
+                                                                   (w["ffn2_2"], 256, False, None)], self.P, [], device=self.dev)
+        o["dw7"] = TimedCall(lambda: L.check(self.lib.ppms_dwconv_gelu(self.C2.view(0, 40), self.C1.view(0, 40), w7.data_ptr(), b7.data_ptr(), 7,
+                                                                        self.T, self.h, self.w, L.stream_ptr())))
         o["convf1"] = self._conv("convf1", [self.PATCH.view()], k1, E(act=L.ACT_RELU, n_valid=128, out_sp=self.FLO1.view()))
         for par in (0, 1):
             cf, cf_next = self.CF[par], self.CF[1 - par]
             o[f"init2_{par}"] = self._conv("init2", [self.ZT.view(0, 64)], k3, E(n_valid=64, out_sp=cf.view(256, 64)))
-            o[f"convc2_{par}"] = self._conv_padded("convc2", [self.COR256.view()], k3, E(act=L.ACT_RELU, n_valid=192, out_sp=cf.view(0, 192)))
+            o[f"convc2_{par}"] = self._conv("convc2", [self.COR256.view()], k3, E(act=L.ACT_RELU, n_valid=192, out_sp=cf.view(0, 192)))
             # (on large maps the library cuts its 400 workgroups in two K slices, and the slice-reduce launch of this side-stream conv crawls on
-            # the CUs the main stream's convc2 leaves free -- 143 us, but off the critical path: unsliced is neither faster nor slower)
-            o[f"convf2_{par}"] = self._conv("convf2", [self.FLO1.view()], k3, E(act=L.ACT_RELU, n_valid=64, out_sp=cf.view(192, 64)),
-                                            nslice=1 if (TUNING["convf2_unsliced"] and self.P >= 32768) else None)
-            o[f"final_{par}"] = self._conv_padded("final", [cf.view()], k3, E(act=L.ACT_RELU, n_valid=126, out_sp=mf),
+            # the CUs the main stream's convc2 leaves free -- 143 us, but off the critical path: unsliced is neither faster nor slower, 40.3 / 40.2 ms per clip)
+            o[f"convf2_{par}"] = self._conv("convf2", [self.FLO1.view()], k3, E(act=L.ACT_RELU, n_valid=64, out_sp=cf.view(192, 64)))
+            o[f"final_{par}"] = self._conv("final", [cf.view()], k3, E(act=L.ACT_RELU, n_valid=126, out_sp=mf),
                                            E(act=L.ACT_RELU, n_valid=64, out_sp=cf_next.view(256, 64)), m_split=128)
         o["to_v"] = self._conv("to_v", [mf], k1, E(n_valid=128, out_sp=self.VAL.view(), out_vt=self.VT, vt_f16=self.attn_p))
         o["unc0"] = self._conv("unc0", [H[0].view(), self.VAL.view()], k3, E(act=L.ACT_RELU, n_valid=128, out_sp=self.U1.view()))
@@ -641,18 +310,16 @@ class ScaleEngine:
         # GRU pass along W (two-layer z / r), then H, then T: h cycles through Hb[0] -> Hb[1] -> Hb[2] -> Hb[0]
         o["z1_2"] = self._conv("z1_2", [self.ZT.view()], (1, 1, 5), E(act=L.ACT_SIGMOID, n_valid=128, out_f32=self.Z, out_f32_ld=128))
         o["r1_2"] = self._conv("r1_2", [self.RT.view()], (1, 1, 5), E(L.EPI_RH, n_valid=128, out_sp=self.RH.view(), aux_sp=H[0].view()))
-        if self.pk.zr1_2_grouped is not None and TUNING["conv6_grouped"]:       # both tails in one grouped launch where conv_gemm6 rates the map (else the two launches above)
-            packed_g, bias_g, meta_g = self.pk.zr1_2_grouped
-            dg = L.Conv.from_buffer_copy(bytes(o["z1_2"].desc))
-            dg.seg[0], dg.seg[1], dg.nseg, dg.groups = self.ZT.view(), self.RT.view(), 2, 2
-            dg.w, dg.bias, dg.M, dg.m_split = packed_g.data_ptr(), bias_g.data_ptr(), 256, 128
-            dg.epi[0], dg.epi[1] = o["z1_2"].desc.epi[0], o["r1_2"].desc.epi[0]
-            if self.lib.ppms_conv_gemm6_applicable(C.byref(dg)) == 1:
-                o["zr1_2"] = ConvOp(dg, [packed_g, bias_g, self.ZT, self.RT, self.Z, self.RH, H[0]], 8, device=self.dev)
+        if TUNING["conv6_grouped"]:                 # both tails in one grouped launch where conv_gemm6 rates the map (else the two launches above)
+            dg = conv_desc([self.ZT.view(), self.RT.view()], (self.T, self.h, self.w), (1, 1, 5), o["z1_2"].desc.epi[0], o["r1_2"].desc.epi[0], m_split=128)
+            dg.groups = 2
+            op = plan_conv(dg, self.pk.w["zr1_2"], [self.ZT, self.RT, self.Z, self.RH, H[0]], device=self.dev)
+            if op is not None:
+                o["zr1_2"] = op
         # the convs over x exist twice on hoisted blocks: "" reads [h | mf, mfg] (the reference's operands: update() driven with a caller's mfg),
         # "_x" reads [h | mf, hid] with the folded weights and skips the products with hid's all-zero lo plane (the loop: attend() leaves hid)
-        self.hid_mode = bool(hoist and TUNING["hid_exact"])
-        for tag, sfx, lz in ((("", "_h" if hoist else "", 0), ("_x", "_x", 256)) if self.hid_mode else (("", "_h" if hoist else "", 0),)):
+        self.hid_mode = hoist
+        for tag, sfx, lz in ((("", "_h", 0), ("_x", "_x", 256)) if hoist else (("", "", 0),)):
             o["zr1_0" + tag] = self._conv("zr1_0" + sfx, [H[0].view(), x_all], (1, 1, 15), E(act=L.ACT_GELU, n_valid=128, out_sp=self.ZT.view(), **pre("zr1_0")),
                                           E(act=L.ACT_GELU, n_valid=128, out_sp=self.RT.view(), **pre("zr1_0", 128)), m_split=128, lo_zero_from=lz)
             o["q1" + tag] = self._conv("q1" + sfx, [self.RH.view(), x_all], (1, 1, 5),
@@ -776,11 +443,11 @@ class ScaleEngine:
     # ------------------------------------------------------------------ once per scale
     def begin(self, pyramid: List[torch.Tensor], qk_pack):
         """q/k projection, Q operand, frame similarity, usage counter (ppmstereo.py:447-475).
-        pyramid: levels of CorrBlock1D; qk_pack: Attention_qk.packed(device)."""
+        pyramid: levels of CorrBlock1D; qk_pack: Attention_qk.packed(device) (a conv_gemm2 pack)."""
         self._drain_xa_halo()
         self.pyr = pyramid
         self.pyr_ptrs = (C.c_void_p * 4)(*[p.data_ptr() for p in pyramid[:4]])
-        key = qk_pack[0].data_ptr()
+        key = qk_pack[CONV2][0].data_ptr()
         if key not in self._qk_ops:
             self._qk_ops[key] = self._conv(qk_pack, [self.X.view(0, 128)], (1, 1, 1), epilogue(n_valid=256, out_f32=self.QK, out_f32_ld=256))
         self._qk_ops[key]()
@@ -817,20 +484,16 @@ class ScaleEngine:
                     corr_build=2 * 256 * T * n * 4.0 + 1.9375 * T * n * w * 4.0)
 
     def _fork(self):
-        if self.P < TUNING["fork_min_pixels"]:
-            return contextlib.nullcontext()
         self._ev_fork.record()
         self._side.wait_event(self._ev_fork)
         return torch.cuda.stream(self._side)
 
     def _join(self):
-        if self.P < TUNING["fork_min_pixels"]:
-            return
         self._ev_join.record(self._side)
         torch.cuda.current_stream().wait_event(self._ev_join)
 
     def motion_and_value(self):
-        o, s, par = self.op, self._s(), self.parity
+        o, par = self.op, self.parity
         with self._fork():                        # flow branch: convf1 (7x7 via im2col) -> convf2
             L.check(self.lib.ppms_flow_patch7(self.FLOW.data_ptr(), self.PATCH.view(), self.T, self.h, self.w, self._s()))
             o["convf1"]()
@@ -839,19 +502,9 @@ class ScaleEngine:
             o["init0"]()
             o[f"init2_{par}"]()
             self.have_mhs = True
-        (w1, b1, _), (w7, b7, _) = self.pk.dw
-        if "chainA" in o:                          # fused per-pixel chains around the depthwise 7x7 (pwchain.hip)
-            o["chainA"]()
-            o["dw7"]()
-            o["chainB"]()
-        else:
-            o["ffn1_0"]()
-            o["ffn1_2"]()
-            L.check(self.lib.ppms_dwconv_gelu(self.C1.view(0, 40), self.C2.view(0, 40), w1.data_ptr(), b1.data_ptr(), 1, self.T, self.h, self.w, s))
-            L.check(self.lib.ppms_dwconv_gelu(self.C2.view(0, 40), self.C1.view(0, 40), w7.data_ptr(), b7.data_ptr(), 7, self.T, self.h, self.w, s))
-            o["pw"]()
-            o["ffn2_0"]()
-            o["ffn2_2"]()
+        o["chainA"]()                             # fused per-pixel chains around the depthwise 7x7 (pwchain.hip)
+        o["dw7"]()
+        o["chainB"]()
         o[f"convc2_{par}"]()
         self._join()
         o[f"final_{par}"]()

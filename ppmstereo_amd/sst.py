@@ -10,7 +10,6 @@ the attn16.hip kernels (C = 256 instantiations); activations stay channel-last o
 """
 from __future__ import annotations
 
-import ctypes as C
 from collections import OrderedDict
 from typing import Dict, List, Optional
 
@@ -19,8 +18,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib as L
-from . import packing as _packing
-from .engine import ConvOp, epilogue
+from .convplan import CONV2, GEMM1, conv_desc, epilogue, pack_conv, plan_conv
 
 DIM, HEADS, DEPTH = 256, 8, 4
 
@@ -100,11 +98,8 @@ class SSTBlock(nn.Module):
         pk: Dict[str, tuple] = {}
 
         def put(name, w, b, segs):
-            w4 = w.detach().to(device)[:, :, None, None]
-            packed, bias, meta = _packing.pack_conv2(w4, None if b is None else b.detach().to(device), segs, segs)
-            pk[name] = (packed, bias, meta)
-            # every layer of the block is a 1x1 GEMM on 640 ... 3 680 pixels per frame: the thin-GEMM kernel's packs beside the implicit GEMM's
-            pk[name + "@1"] = _packing.pack_gemm1(w4, None if b is None else b.detach().to(device), segs, segs, None, meta["M"])
+            # every layer of the block is a 1x1 GEMM on 640 ... 3 680 pixels per frame: the thin-GEMM kernel where the library rates it, else conv_gemm2
+            pk[name] = pack_conv(w.detach().to(device), None if b is None else b.detach().to(device), segs, segs, kernels=(CONV2, GEMM1))
 
         ln: Dict[str, tuple] = {}
         for i in range(DEPTH):
@@ -168,27 +163,9 @@ class _SstEngine:
         none_sp = L.SP(None, None, 0, 0)
         s = L.stream_ptr
 
-        def conv(name, segs: List[L.SPTensor], e0: L.Epilogue, e1: Optional[L.Epilogue] = None, m_split: Optional[int] = None):
-            packed_w, bias, meta = pk[name]
-            d = L.Conv()
-            for i, t in enumerate(segs):
-                d.seg[i] = t.view()
-            d.nseg, d.w, d.bias = len(segs), packed_w.data_ptr(), bias.data_ptr()
-            d.T, d.H, d.W = T, h, w
-            d.kt = d.kh = d.kw = 1
-            d.M = meta["M"]
-            d.m_split = meta["M"] if m_split is None else m_split
-            d.epi[0] = e0
-            if e1 is not None:
-                d.epi[1] = e1
-            p1, b1, _ = pk[name + "@1"]
-            d1 = L.Conv.from_buffer_copy(bytes(d))
-            d1.w, d1.bias = p1.data_ptr(), b1.data_ptr()
-            if lib.ppms_gemm1_applicable(C.byref(d1)) == 1:           # (one memory round trip deep, no K slices: gemm1.hip)
-                op = ConvOp(d1, list(segs) + [p1, b1], 6, device=device)
-            else:
-                op = ConvOp(d, list(segs) + [packed_w, bias], 2, device=device)
-            self.steps.append(op)
+        def conv(name, segs: List[L.SPTensor], e0: L.Epilogue, e1: Optional[L.Epilogue] = None, m_split: int = 0):
+            d = conv_desc([t.view() for t in segs], (T, h, w), (1, 1, 1), e0, e1, m_split)
+            self.steps.append(plan_conv(d, pk[name], list(segs), device=device))
 
         def call(fn):
             self.steps.append(fn)

@@ -15,7 +15,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .engine import PackedBlock, ScaleEngine, pack_conv, temporal_pe
+from .convplan import CONV2, pack_conv
+from .engine import PackedBlock, ScaleEngine, temporal_pe
 
 
 @torch.no_grad()
@@ -138,8 +139,8 @@ class Attention_qk(nn.Module):
         self.register_load_state_dict_post_hook(lambda m, k: setattr(m, "_packed", None))
 
     def packed(self, device):
-        if self._packed is None or self._packed[0].device != torch.device(device):
-            self._packed = pack_conv(self.to_qk.weight.detach().to(device).float(), None, [128])
+        if self._packed is None or self._packed[CONV2][0].device != torch.device(device):
+            self._packed = pack_conv(self.to_qk.weight.detach().to(device).float(), None, [128], kernels=(CONV2,))
         return self._packed
 
     def forward(self, fmap):

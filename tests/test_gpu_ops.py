@@ -116,13 +116,11 @@ def _run_conv(L, x_list, weight, bias, k3, T, H, W, act=0, kind=0, aux=None, z=N
     halo > 0: a rank's window of a frame-sharded clip (ppms_conv.t_halo) -- x_list holds T + 2 halo frames, the middle T are the launch's own
     frames and the outer ones fill the halo slabs around them (temporal taps read them); aux / z / pre stay (P, .) over the own frames.
     nslice = -1: the library plans the K slices (conv_gemm5 / conv_gemm2; must find some).  ops: a list that receives the launched ConvOp."""
+    from ppmstereo_amd.convplan import CONV2_SWEPT, pack_for
     from ppmstereo_amd.engine import ConvOp, epilogue
-    from ppmstereo_amd.packing import pack_conv2, pack_conv4
     tile_px = 0
     if version in (5, 5007, 5008):                                         # conv_gemm5; 5007 / 5008 force the blocks per tile
         tile_px, version = (0 if version == 5 else version - 5000), 5
-    from ppmstereo_amd.packing import pack_conv6, pack_gemm1, pack_stream
-    pack_conv = pack_conv4 if version == 5 else pack_gemm1 if version == 6 else pack_stream if version == 7 else pack_conv6 if version == 8 else pack_conv2
     P = T * H * W
     segs, keep = [], []
     seg_pad = seg_pad or [((x.shape[1] + 31) // 32) * 32 for x in x_list]
@@ -134,14 +132,9 @@ def _run_conv(L, x_list, weight, bias, k3, T, H, W, act=0, kind=0, aux=None, z=N
         t.data[1, :, :x.shape[1]] = (x.to(DEV) - hi.float()).to(torch.bfloat16)
         segs.append(t.view())
         keep.append(t)
-    wpack = weight
-    if (version in (5, 8) or ysweep) and k3[2] == 1 and k3[1] > 1:       # y-swept kernels: pack with kh / kw swapped
-        wpack = (weight if weight.dim() == 5 else weight[:, :, None]).transpose(3, 4).contiguous()
-    if (version in (5, 8) or ysweep) and k3[2] > 1 and k3[1] > 1:        # 2-D swept: (ky, kx) flattened into the x axis
-        w5 = weight if weight.dim() == 5 else weight[:, :, None]
-        wpack = w5.reshape(w5.shape[0], w5.shape[1], w5.shape[2], 1, k3[1] * k3[2]).contiguous()
-    packed, b, meta = pack_conv(wpack.to(DEV), None if bias is None else bias.to(DEV), [x.shape[1] for x in x_list], seg_pad,
-                                **({} if m_pad is None else dict(m_pad=m_pad)))
+    # (the swept kernels -- conv_gemm5, conv_gemm6, conv_gemm2's one-window form -- get the sweep-ordered weights)
+    packed, b, meta = pack_for(CONV2_SWEPT if ysweep else version, weight.to(DEV), None if bias is None else bias.to(DEV), [x.shape[1] for x in x_list],
+                               seg_pad, None, m_pad)
     cout = weight.shape[0]
     out = L.SPTensor(P, meta["M"], DEV)
     outf = torch.zeros(P, meta["M"], device=DEV)

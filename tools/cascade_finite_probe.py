@@ -1,8 +1,6 @@
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch
-import ab_switches  # noqa
 from ppmstereo_amd import weights as Wm
 from ppmstereo_amd.ppmstereo import PPMStereoHotPath
 from ppmstereo_amd.synth import synth_cascade_feats

@@ -6,8 +6,6 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import ctypes as C
 import torch
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import ab_switches  # noqa: F401  (PPMS_LIB: another build of the library)
 from ppmstereo_amd import _lib as L
 from ppmstereo_amd.engine import ConvOp, epilogue
 from ppmstereo_amd.packing import pack_conv4, pack_conv6

@@ -6,8 +6,6 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import ab_switches  # noqa: F401,E402  (PPMS_CONV6=0 etc.: A/B of the kernel generations)
 from ppmstereo_amd import weights as Wm
 from ppmstereo_amd.ppmstereo import PPMStereoHotPath
 from ppmstereo_amd.weights import hash_normal
