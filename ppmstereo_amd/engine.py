@@ -447,10 +447,7 @@ class ScaleEngine:
         self._drain_xa_halo()
         self.pyr = pyramid
         self.pyr_ptrs = (C.c_void_p * 4)(*[p.data_ptr() for p in pyramid[:4]])
-        key = qk_pack[CONV2][0].data_ptr()
-        if key not in self._qk_ops:
-            self._qk_ops[key] = self._conv(qk_pack, [self.X.view(0, 128)], (1, 1, 1), epilogue(n_valid=256, out_f32=self.QK, out_f32_ld=256))
-        self._qk_ops[key]()
+        self.qk_op(qk_pack)()
         s = self._s()
         pe_local = self.PE.data_ptr() + self.f0 * 128 * 4
         L.check(self.lib.ppms_attn_prep_q(self.QK.data_ptr(), 256, pe_local, self.QB.data_ptr(), self.T, self.n, s))
@@ -463,6 +460,13 @@ class ScaleEngine:
             self.shard.all_gather(self.QK[:, 128:].contiguous(), out=self.KG)
         L.check(self.lib.ppms_qk_cos(self.POOLG.data_ptr(), self.SIM.data_ptr(), self.Tg, self.cells, s))
         self.STRIVE.fill_(1.0)
+
+    def qk_op(self, qk_pack) -> ConvOp:
+        """The q/k projection launch of begin() for this Attention_qk pack (planned on first use, then kept)."""
+        key = qk_pack[CONV2][0].data_ptr()
+        if key not in self._qk_ops:
+            self._qk_ops[key] = self._conv(qk_pack, [self.X.view(0, 128)], (1, 1, 1), epilogue(n_valid=256, out_f32=self.QK, out_f32_ld=256))
+        return self._qk_ops[key]
 
     # ------------------------------------------------------------------ iteration stages
     def lookup(self):
