@@ -31,11 +31,12 @@ HEADERS = ["common.h", "corr_lookup.h", "conv_epilogue.h", "conv5_asm.h", "conv6
 # with op_sel:[0,1] (low result = src0.lo op src1.hi -- the compiler picks that form freely, e.g. in the bilinear resize kernel) reads
 # src1.hi as 0 in lanes 48-63 whenever ANOTHER wave on the same SIMD is issuing MFMAs, and the engine runs MFMA kernels beside small
 # kernels on two streams.  Register-only reproducer: tools/pk_opsel_probe.py; evidence: profiles/r02_pk_opsel_probe.txt; static guard:
-# tools/check_no_packed_fp32.py (tests/test_host_logic.py); docs/LOG_r01_r05.md section 5.  Sources listed in PACKED_FP32_SOURCES keep the packed forms.
+# tools/check_no_packed_fp32.py (tests/test_host_logic.py); docs/LOG_r01_r05.md section 5.
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
 NO_PK = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA = [x for x in os.environ.get("PPMS_BUILD_DEFINES", "").split() if x]        # build-time A/B only, e.g. "-DPPMS_CONV5_TIMING"
-PACKED_FP32_SOURCES: tuple = tuple(x for x in os.environ.get("PPMS_BUILD_PACKED_FP32", "").split(",") if x)   # build-time A/B only
+# The one build-time setting: PPMS_BUILD_DEFINES switches on the phase-stamp diagnostics (-DPPMS_CONV2_TIMING, -DPPMS_CONV5_TIMING, -DPPMS_CONV6_TIMING,
+# -DPPMS_ATTN_TIMING; read by tools/*_phase_probe.py).  They add stores of clock values and leave the results as they are.
+EXTRA = [x for x in os.environ.get("PPMS_BUILD_DEFINES", "").split() if x]
 FLAGS = COMMON + NO_PK + EXTRA
 
 
@@ -43,7 +44,7 @@ def _digest() -> str:
     """sha256 over the flags and exactly the files that go into the library (editor temp files do not count).  The checkout's own location is
     taken out of the -I paths first: the library built here travels with the tree to the GPU box, where the tree sits under another path -- with
     absolute paths in the digest every fresh box found the stamp "stale" and spent its first minute recompiling identical sources (rounds 1-5)."""
-    h = hashlib.sha256(" ".join(x.replace(ROOT, "$ROOT") for x in FLAGS + list(PACKED_FP32_SOURCES)).encode())
+    h = hashlib.sha256(" ".join(x.replace(ROOT, "$ROOT") for x in FLAGS).encode())
     for f in SOURCES + HEADERS:
         with open(os.path.join(CSRC, f), "rb") as fh:
             h.update(os.path.basename(f).encode() + fh.read())
@@ -86,7 +87,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
                 procs = []
                 for src in SOURCES:                # compile the translation units in parallel (independent hipcc processes)
                     obj = os.path.join(tmp, src.replace(".hip", ".o"))
-                    cmd = [hipcc] + (COMMON + EXTRA if src in PACKED_FP32_SOURCES else FLAGS) + ["-c", os.path.join(CSRC, src), "-o", obj]
+                    cmd = [hipcc] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj]
                     if verbose:
                         print("[ppmstereo_amd.build]", " ".join(cmd), file=sys.stderr)
                     procs.append((cmd, subprocess.Popen(cmd, stderr=subprocess.PIPE, text=True)))

@@ -22,9 +22,6 @@
 namespace {
 
 constexpr int BK = 32;
-#ifndef CONV2_ABL_A
-#define CONV2_ABL_A 0        // ablation builds (-DCONV2_ABL_A=1): every k-step loads the FIRST step's weights (cache hits): wrong results, timing only
-#endif
 constexpr int A_BLK = 64 * BK * 2 * 2;       // one 64-cout block, hi + lo planes: 8 KiB
 
 struct Geo2 {
@@ -131,7 +128,7 @@ __global__ __launch_bounds__(128 * WM * KG) void conv2_kernel(const ppms_conv pv
 
     u32x4 ra[4], rbh[MAXSLOT], rbl[MAXSLOT];
     auto load_a = [&](int ks) {
-        const char* wp = wbase + (int64_t)(CONV2_ABL_A ? 0 : ks) * wstep;
+        const char* wp = wbase + (int64_t)ks * wstep;
 #pragma unroll
         for (int i = 0; i < 4; ++i) ra[i] = gload16(wp + i * NT * 16);
     };
@@ -483,12 +480,6 @@ int launch2(const ppms_conv* d, const ppms_conv* dev_desc, const Geo2& g, int nt
         ppms_set_error("conv_gemm2: LDS budget exceeded (%zu B)", lds);
         return PPMS_EINVAL;
     }
-#ifdef PPMS_CONV2_TIMING
-    Geo2 gd = g;
-    gd.dbg = g_conv2_dbg;
-    hipLaunchKernelGGL((conv2_kernel<WM, KG>), dim3(ntiles * g.mgroups, g.nslice), dim3(128 * WM * KG), lds, stream, *d, gd);
-    return ppms_check_launch("conv_gemm2");
-#endif
     hipLaunchKernelGGL((conv2_kernel<WM, KG>), dim3(ntiles * g.mgroups, g.nslice), dim3(128 * WM * KG), lds, stream, *d, g);
     return ppms_check_launch("conv_gemm2");
 }
@@ -671,6 +662,9 @@ static int conv2_launch(const ppms_conv* d, const ppms_conv* dev_desc, int wm_hi
         }
     g.part = part;
     g.P = (int64_t)d->T * d->H * d->W;
+#ifdef PPMS_CONV2_TIMING
+    g.dbg = g_conv2_dbg;
+#endif
     if (nslice > 1) {
         PPMS_REQUIRE((((ysweep || win2d) ? 1 : d->kh) * nchunk) % nslice == 0, "conv_gemm2: %d row-steps per temporal tap do not split into %d slices",
                      ((ysweep || win2d) ? 1 : d->kh) * nchunk, nslice);

@@ -75,15 +75,6 @@ __device__ __forceinline__ void vm_wait5(int n) {
 #undef PPMS_VMW
 }
 
-#ifndef CONV5_NOSYNC
-#define CONV5_NOSYNC 0       // ablation builds: 1 drops wait + barrier + DMA at the window switches, 2 the DMA, 3 the barrier: wrong results, timing only
-#endif
-#ifndef CONV5_PRIO
-#define CONV5_PRIO 0         // experiment builds: static issue priority for one of the two waves of a SIMD during the K loop (1: waves 0-3, 2: waves 4-7, 3: the 4-block waves)
-#endif
-#ifndef CONV5_ABL_A
-#define CONV5_ABL_A 0        // ablation builds (-DCONV5_ABL_A=1): every k-step loads the FIRST step's weights (L1 hits): wrong results, timing only
-#endif
 #include "conv5_asm.h"
 
 __global__ __launch_bounds__(512, 2) void conv5_kernel(const ppms_conv pv, const Geo5 g) {
@@ -252,7 +243,7 @@ __global__ __launch_bounds__(512, 2) void conv5_kernel(const ppms_conv pv, const
         __builtin_amdgcn_sched_barrier(0);                                                                                     \
         /* (every MFMA group is unconditional straight-line code: an if / else around asm groups that redefine the eight      */ \
         /*  accumulator tuples makes the register allocator copy and spill them; the last step simply re-requests data)        */ \
-        mfma_group1<NBW, MORE>(acc, areg[U][1], areg[U][3], bh, areg[(U) ^ 1], avoff, abase + (int64_t)(CONV5_ABL_A ? 0 : la_ks) * astep);         \
+        mfma_group1<NBW, MORE>(acc, areg[U][1], areg[U][3], bh, areg[(U) ^ 1], avoff, abase + (int64_t)la_ks * astep);                           \
         if (ahead >= 2) {                                                                                                      \
             ++la_ks;                                                                                                           \
             if (++la_s == g.nsweep) la_s = 0, la_ks += (wstride - 1) * g.nsweep; /* next window of this K-group */             \
@@ -267,10 +258,10 @@ __global__ __launch_bounds__(512, 2) void conv5_kernel(const ppms_conv pv, const
             wchunk += wstride;                                                                                                 \
             if (wchunk >= g.nchunk) wchunk -= g.nchunk;                                                                        \
             if (ahead > 0) {                                                                                                   \
-                if (CONV5_NOSYNC != 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");                                        \
-                if (CONV5_NOSYNC != 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                      \
-                if (CONV5_NOSYNC != 1 && CONV5_NOSYNC != 3) __builtin_amdgcn_s_barrier();                                      \
-                if (CONV5_NOSYNC != 1 && CONV5_NOSYNC != 2) if (w + 2 < nwin) dma_b(win0 + wstride * (w + 2), w & 1);          \
+                asm volatile("s_waitcnt vmcnt(4)" ::: "memory");                                                               \
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                             \
+                __builtin_amdgcn_s_barrier();                                                                                  \
+                if (w + 2 < nwin) dma_b(win0 + wstride * (w + 2), w & 1);                                                      \
             }                                                                                                                  \
             ++w;                                                                                                               \
         } else {                                                                                                               \
@@ -320,17 +311,7 @@ __global__ __launch_bounds__(512, 2) void conv5_kernel(const ppms_conv pv, const
     }
     static_assert(DEPTH5 == 2, "two A stages: U and U ^ 1; the step loop is unrolled twice");
     CONV5_STAMP(1)
-#if CONV5_PRIO == 1
-    if (wave < 4) __builtin_amdgcn_s_setprio(1);
-#elif CONV5_PRIO == 2
-    if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-#elif CONV5_PRIO == 3
-    if (nbw == 4) __builtin_amdgcn_s_setprio(1);
-#endif
     if (nbw == 4) CONV5_LOOP(4) else if (nbw == 3) CONV5_LOOP(3) else CONV5_LOOP(2)
-#if CONV5_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
     CONV5_STAMP(2)
 #undef CONV5_LOOP
 #undef CONV5_STEP

@@ -33,6 +33,7 @@ constexpr int MAXP6 = 14;                     // LDS-DMA pieces (16 B) per threa
 __host__ __device__ constexpr int conv6_np(int cr) { return cr == 16 ? 14 : 9; }
 constexpr int NBT6 = 13;                      // 16-pixel blocks (columns) per tile
 constexpr int STG6_ROWS = 7 * 16;             // pixels a wave stages per epilogue pass
+constexpr int EPI6_G = 2;                     // 8-pixel steps per epilogue group (operands of a group are fetched before its rows are finished)
 
 
 struct Geo6 {
@@ -82,34 +83,6 @@ __device__ __forceinline__ void dma16_6(unsigned off, const u32x4& srd, unsigned
 constexpr unsigned CONV6_NUM_RECORDS = 0xFFFFFF00u;     // range of a window's buffer resource; CONV6_OOB is beyond it
 constexpr unsigned CONV6_OOB = 0xFFFFFFF0u;
 
-#ifndef CONV6_EPI_G
-#define CONV6_EPI_G 2
-#endif
-#ifndef CONV6_ABL_NOWAIT_A
-#define CONV6_ABL_NOWAIT_A 0
-#endif
-#ifndef CONV6_XCD_ORDER
-#define CONV6_XCD_ORDER 0      // measured neutral (+-1 % on every 1/4-scale conv, the (3,3,3) flow-head conv -3 %): off; -DCONV6_XCD_ORDER=1 for A/B
-#endif
-#ifndef CONV6_SLACK
-#define CONV6_SLACK 0
-#endif
-#if CONV6_SLACK == 1
-#define CONV6_SWITCH_SLACK asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");
-#define CONV6_PRE_BARRIER
-#elif CONV6_SLACK == 2
-#define CONV6_SWITCH_SLACK asm volatile("s_sleep 20" ::: "memory");
-#define CONV6_PRE_BARRIER
-#elif CONV6_SLACK == 3
-#define CONV6_SWITCH_SLACK
-#define CONV6_PRE_BARRIER asm volatile("s_sleep 20" ::: "memory");
-#else
-#define CONV6_SWITCH_SLACK
-#define CONV6_PRE_BARRIER
-#endif
-#ifndef CONV6_KSPLIT
-#define CONV6_KSPLIT 1         // -DCONV6_KSPLIT=0: M = 128 convolutions always in the two-pixel-halves layout (A/B builds)
-#endif
 #include "conv6_asm.h"
 
 // MB: 16-cout blocks per wave -- 4 (M = 256, 128) or 3 (M = 192); CR: rows of a window column = 16 + y halo (16, 18, 20)
@@ -147,16 +120,10 @@ __global__ __launch_bounds__(NT6, 1) void conv6_kernel(const ppms_conv pv, const
     auto gchunk = [&](int grp, int c) { return c < g.lz0 ? grp * g.lz0 + c : g.lz0_full + grp * (g.nchunk - g.lz0) + (c - g.lz0); };
     auto wchunk = [&](int c) { return KS ? gchunk(kg, c) : c; };          // window index the WEIGHTS of this wave's step are stored under
     const int ncf = KS ? g.nchunk_full : g.nchunk;
-    // workgroups are dealt round-robin over the 8 XCDs (b and b + 8 share one; each XCD has its own L2): XCD k gets the k-th eighth of the tile
-    // list, so that the x / y neighbours whose windows overlap in their halo columns fetch them through ONE L2 (placement is a speed hint only)
+    // tiles in launch order: workgroups are dealt round-robin over the 8 XCDs, so x / y neighbours fetch their shared halo columns through different
+    // L2s; re-ordering the tile list so that every XCD gets one contiguous eighth was measured neutral (+-1 % on every 1/4-scale conv, the (3,3,3)
+    // flow-head conv -3 %)
     int tile = blockIdx.x;
-#if CONV6_XCD_ORDER
-    {
-        const int nt = (int)gridDim.x, per = (nt + 7) >> 3, full = nt - 8 * (per - 1);      // XCDs 0 .. full-1 hold `per` tiles, the others per - 1
-        const int xcd = tile & 7, slot = tile >> 3;
-        tile = xcd < full ? xcd * per + slot : full * per + (xcd - full) * (per - 1) + slot;
-    }
-#endif
     const int tx = tile % g.tiles_x;
     tile /= g.tiles_x;
     const int ty = tile % g.tiles_y;
@@ -337,14 +304,11 @@ __global__ __launch_bounds__(NT6, 1) void conv6_kernel(const ppms_conv pv, const
             /* window switch: everything this wave issued has landed (the next window's pieces are older than this step's weight  */ \
             /* loads), every wave is done reading the old window                                                                  */ \
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                                            \
-            CONV6_PRE_BARRIER                                                                                                      \
             __builtin_amdgcn_s_barrier();                                                                                          \
-            CONV6_SWITCH_SLACK                                                                                                     \
             w = n_w;                                                                                                               \
             ckz = nxkz, cch = nxch;                                                                                                \
             next_window(ckz, cch, nxkz, nxch);                                                                                     \
             conv6_prime<NBW, CR>(ring, bhn, bhn ^ 64u);                                                                             \
-        } else if (CONV6_ABL_NOWAIT_A) { /* timing experiment (wrong results): no wait for the next step's weight fragments */      \
         } else if (issue) { /* the next step's weight fragments: everything but the pieces this step issued behind them */           \
             if constexpr (NP == 18) asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); /* GRP: PPS0 = PPS1 = 9 */                     \
             else if constexpr (NP == 14) asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); /* PPS0 = PPS1 = 7 */                     \
@@ -600,9 +564,9 @@ __global__ __launch_bounds__(NT6, 1) void conv6_kernel(const ppms_conv pv, const
             using I5 = std::integral_constant<int, EPI_CLS_AUXPRE>;
             using G1 = std::integral_constant<int, 1>;
             using G2 = std::integral_constant<int, 2>;
-            using GL = std::integral_constant<int, CONV6_EPI_G>;
+            using GL = std::integral_constant<int, EPI6_G>;
             const int cls = epilogue_class(e);
-            // (groups of CONV6_EPI_G 8-pixel steps: the operands of a group are fetched before its rows are finished -- one wave per SIMD has nobody to
+            // (groups of EPI6_G 8-pixel steps: the operands of a group are fetched before its rows are finished -- one wave per SIMD has nobody to
             //  hide a memory round trip behind, so the epilogue's time is its number of such round trips)
             if (cls == EPI_CLS_PLAIN) rows(I0{}, G2{});
             else if (cls == EPI_CLS_PRE) rows(I1{}, GL{});
@@ -668,7 +632,7 @@ static bool plan6(const ppms_conv* d, Geo6& g) {
     g.ks = 0, g.nchunk_full = nchunk, g.lz0_full = g.lz0;
     // K-split form of M = 128 (the kernel's KS parameter): an even split of the windows with and of those without a lo plane over the two wave pairs, a
     // window image of <= 9 pieces (two images per buffer: 144 KiB), and -- as for the plain layout -- an even number of phase-0 steps per K group
-    if (CONV6_KSPLIT && d->M == 128 && !grouped && !stream && g.npieces <= 9 && (g.WH == 16 || g.WH == 18 || g.WH == 20) && g.nsweep >= 2 && nchunk % 2 == 0 &&
+    if (d->M == 128 && !grouped && !stream && g.npieces <= 9 && (g.WH == 16 || g.WH == 18 || g.WH == 20) && g.nsweep >= 2 && nchunk % 2 == 0 &&
         nchunk >= 4) {
         int lz = g.lz0;
         if (lz < nchunk && ((lz % 2) || ((nchunk - lz) % 2) || (((lz / 2) * g.nsweep) & 1))) lz = nchunk;      // uneven phases: every product is computed

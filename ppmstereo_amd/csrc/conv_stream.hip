@@ -283,17 +283,12 @@ bool plan7(const ppms_conv* d, Plan7& pl, int hint) {
     g.n0 = d->seg[0].c / 16;
     g.nsteps = (int)taps * g.nk16;
     g.nmb = d->M / 64;
-    if (hint > 2) {                                      // probes: (KG << 8) | (PB << 4) | D
-        pl.kg = hint >> 8, pl.pb = (hint >> 4) & 15, pl.depth = hint & 15;
-        if ((pl.kg != 4 && pl.kg != 8) || (pl.pb != 1 && pl.pb != 2) || g.nk16 % pl.kg) return false;
-    } else {
-        // tile: 32 pixels x 64 couts per workgroup fills the chip on the smallest maps (3 200 pixels x 128 couts = 200 workgroups); 64-pixel tiles
-        // halve the weight bytes per MFMA once the couts alone give enough workgroups (measured, tools/conv_stream_probe.py: 3 200 pixels -- M >= 192:
-        // 64-pixel tiles 27-37 us against 32-42; M = 128: 32-pixel tiles 18-22 against 25-31; 12 800 pixels: 64-pixel tiles throughout)
-        pl.pb = (hint == 1 || hint == 2) ? hint : ((P > 4096 || d->M >= 192) ? 2 : 1);
-        pl.depth = pl.pb == 2 ? 3 : 6;           // (sweep: deeper rings and 8-wave workgroups change nothing or lose -- the CU's L1 path is the bound)
-        pl.kg = 4;
-    }
+    // tile: 32 pixels x 64 couts per workgroup fills the chip on the smallest maps (3 200 pixels x 128 couts = 200 workgroups); 64-pixel tiles
+    // halve the weight bytes per MFMA once the couts alone give enough workgroups (measured, tools/conv_stream_probe.py: 3 200 pixels -- M >= 192:
+    // 64-pixel tiles 27-37 us against 32-42; M = 128: 32-pixel tiles 18-22 against 25-31; 12 800 pixels: 64-pixel tiles throughout)
+    pl.pb = (hint == 1 || hint == 2) ? hint : ((P > 4096 || d->M >= 192) ? 2 : 1);
+    pl.depth = pl.pb == 2 ? 3 : 6;               // (sweep: deeper rings and 8-wave workgroups change nothing or lose -- the CU's L1 path is the bound)
+    pl.kg = 4;
     g.npw = g.nk16 / pl.kg;
     return true;
 }
@@ -334,21 +329,13 @@ extern "C" int ppms_conv_stream_applicable(const ppms_conv* d) {
 extern "C" int ppms_conv_stream(const ppms_conv* d, const ppms_conv* dev_desc, int hint, void* stream) {
     (void)dev_desc;
     Plan7 pl;
-#ifdef PPMS_STREAM_PROBE
-    PPMS_REQUIRE(hint >= 0, "conv_stream: hint must be 0 (choose), 1 or 2 (32-pixel blocks per tile), or a probe encoding (KG << 8) | (PB << 4) | D");
-#else
     PPMS_REQUIRE(hint >= 0 && hint <= 2, "conv_stream: hint must be 0 (choose), 1 or 2 (32-pixel blocks per tile)");
-#endif
     PPMS_REQUIRE(plan7(d, pl, hint), "conv_stream: not a convolution this kernel serves (odd taps, input channels a multiple of 64 in 16-channel-aligned "
                                      "segments, M %% 64 == 0, pack_stream weights, aligned SP operands, no out_vt / ADDF32 epilogue; ppms_conv_stream_applicable tells)");
     hipStream_t st = (hipStream_t)stream;
 #define S7_CASE(PBV, DV, KGV) \
     if (pl.pb == PBV && pl.depth == DV && pl.kg == KGV) return launch7<2, PBV, DV, KGV>(d, pl, st);
     S7_CASE(1, 6, 4) S7_CASE(2, 3, 4)
-#ifdef PPMS_STREAM_PROBE        // (tools/conv_stream_probe.py builds: ring depth / K-group sweeps)
-    S7_CASE(1, 4, 4) S7_CASE(1, 8, 4) S7_CASE(1, 10, 4) S7_CASE(2, 6, 4) S7_CASE(1, 4, 8) S7_CASE(1, 6, 8) S7_CASE(1, 8, 8) S7_CASE(2, 4, 8) S7_CASE(2, 6, 8)
-    S7_CASE(2, 4, 4) S7_CASE(2, 3, 8)
-#endif
 #undef S7_CASE
     ppms_set_error("conv_stream: no instantiation for PB=%d D=%d KG=%d", pl.pb, pl.depth, pl.kg);
     return PPMS_EINVAL;

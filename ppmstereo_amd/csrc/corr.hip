@@ -101,9 +101,6 @@ __global__ __launch_bounds__(256) void corr_build_kernel(const float* __restrict
 // Algorithmic bytes: 2 * 256 * P * 4 in + 1.9375 * P * W * 4 out; at config 2's 1/4 scale 105 MB + 51 MB; the fp32 matrix
 // pipe needs 2 * 256 * P * W FLOP / 157 TFLOP/s = 21 us for the same launch, HBM at ~6.3 TB/s achievable 25 us: a balanced kernel.
 // ------------------------------------------------------------------------------------------------
-#ifndef CORR_ABL
-#define CORR_ABL 0                // ablation builds (timing only, wrong results): 1 no pyramid stores, 2 no MFMAs, 4 no feature DMA
-#endif
 constexpr int CORR_CK = 16;       // channels per LDS stage
 constexpr int CORR_NST = 4;       // stages in the ring (three requested ahead)
 constexpr int CORR_S = 18;        // store instructions of one tile's epilogue: 4 x (level 0, 1, 2) + 4 (level 3) + 2 (level 4)
@@ -188,7 +185,7 @@ __global__ __launch_bounds__((CorrGeo<R1LOG, R2LOG>::NT)) void corr_build_line_k
     const char* zpage = (const char*)g_corr_zero_page;
     asm volatile("" : "+s"(zpage));
     auto issue = [&](int it) {
-        const bool live = it < total && !(CORR_ABL & 4);
+        const bool live = it < total;
         const int bj = it < total ? it / nch : 0;
         const int c0 = (it - bj * nch) * CORR_CK;
         char* dst = smem + (it & (CORR_NST - 1)) * STAGE + wave * 1024;
@@ -236,7 +233,7 @@ __global__ __launch_bounds__((CorrGeo<R1LOG, R2LOG>::NT)) void corr_build_line_k
         issue(it + 3);                                        // into the ring slot of stage it - 1
         ++since;
         const int bj = it / nch;
-        if (computes && !(CORR_ABL & 2)) {
+        if (computes) {
             const float* st = (const float*)(smem + (it & (CORR_NST - 1)) * STAGE);
 #pragma unroll
             for (int u = 0; u < CORR_CK / 2; ++u)
@@ -250,7 +247,7 @@ __global__ __launch_bounds__((CorrGeo<R1LOG, R2LOG>::NT)) void corr_build_line_k
             for (int s = 0; s < TPW; ++s) {
                 const int x1 = x1b + t1[s] * 32 + li;
                 const int64_t prow = (int64_t)row * W + x1;
-                const bool rowok = x1 < W && !(CORR_ABL & 1);
+                const bool rowok = x1 < W;
                 const int x2t = bj * R2 + t2[s] * 32;
                 float d3[4];
 #pragma unroll

@@ -547,9 +547,7 @@ __global__ __launch_bounds__(256, 1) void mem_attn64_kernel(const bf16_t* __rest
         attn64_substep<0, P16>(sa, sb, qf, o, ring, vt, pf, pt, tt, lacc, ones, negm, scale_log2, kaddr, vaddr, delta, koff, voff, kp, vp, dst);
         attn64_substep<1, P16>(sb, sa, qf, o, ring, vt, pf, pt, tt, lacc, ones, negm, scale_log2, kaddr, vaddr, delta, koff, voff, kp, vp, dst);
         asm volatile("s_waitcnt vmcnt(8)" ::: "memory");          // tiles <= j + 2 have landed (this thread's share; the barrier covers the others')
-#if !defined(PPMS_ATTN_NOSYNC)
         __builtin_amdgcn_s_barrier();
-#endif
         if (j + 1 == nt) asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");      // drain the matrix pipe in front of whatever the compiler places at the exit
     }
     attn64_tail();

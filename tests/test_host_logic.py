@@ -408,21 +408,40 @@ def test_pack_stream_round_trip():
         pack_stream(hash_normal((8, 32, 1, 1), 80), None, [32])          # K = 32: not a multiple of 64
 
 
-@pytest.mark.parametrize("tool,header", [("gen_conv5_asm", "conv5_asm.h"), ("gen_attn_asm", "attn64_asm.h")])
+@pytest.mark.parametrize("tool,header", [("gen_conv5_asm", "conv5_asm.h"), ("gen_attn_asm", "attn64_asm.h"), ("gen_conv6_asm", "conv6_asm.h")])
 def test_committed_asm_headers_are_the_generators_default_output(tool, header):
-    """The hand-scheduled loops are generated files and the ablation scripts (tools/abl_*_phase.sh) rewrite them in place with wrong-results
-    settings: the committed header must be exactly what the generator emits with no knob set."""
+    """The hand-scheduled loops are generated files: the committed header must be exactly what its generator emits (the generators take no
+    settings, see test_kernels_and_generators_have_no_experiment_switches)."""
     import importlib.util
     import os
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    saved = {k: os.environ.pop(k) for k in list(os.environ) if k.startswith(("PPMS_CONV5_", "PPMS_ATTN_"))}
-    try:
-        spec = importlib.util.spec_from_file_location(f"_{tool}", os.path.join(root, "tools", tool + ".py"))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        assert mod.gen() == open(os.path.join(root, "ppmstereo_amd", "csrc", header)).read()
-    finally:
-        os.environ.update(saved)
+    spec = importlib.util.spec_from_file_location(f"_{tool}", os.path.join(root, "tools", tool + ".py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    assert mod.gen() == open(os.path.join(root, "ppmstereo_amd", "csrc", header)).read()
+
+
+def test_kernels_and_generators_have_no_experiment_switches():
+    """Every build of the library computes correct results: the loop generators read no environment variable, and the only conditional
+    compilation in the kernel sources is the C / C++ split of a header and the four phase-stamp diagnostics (PPMS_BUILD_DEFINES)."""
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for tool in ("gen_conv5_asm", "gen_conv6_asm", "gen_attn_asm"):
+        assert "environ" not in open(os.path.join(root, "tools", tool + ".py")).read(), tool
+    allowed = {"__cplusplus", "PPMS_CONV2_TIMING", "PPMS_CONV5_TIMING", "PPMS_CONV6_TIMING", "PPMS_ATTN_TIMING"}
+    csrc = os.path.join(root, "ppmstereo_amd", "csrc")
+    seen = 0
+    for name in sorted(os.listdir(csrc)):
+        if not name.endswith((".hip", ".h")):
+            continue
+        for no, line in enumerate(open(os.path.join(csrc, name)), 1):
+            m = re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b(.*)", line)
+            if m:
+                seen += 1
+                names = set(re.findall(r"[A-Za-z_]\w*", m.group(2).split("//")[0])) - {"defined"}
+                assert names and names <= allowed, f"{name}:{no}: {line.strip()}"
+    assert seen > 0
 
 
 def test_drop_in_constructor_keeps_the_reference_defaults():

@@ -1,9 +1,7 @@
 """Per-launch time of the update block's convolutions on the small maps (1/16 and 1/8 scales of config 2; 1/16 of config 3): the LDS-staged
 implicit GEMM as the library plans it (conv_gemm2: K slices + slice-reduce launch, y sweep where it applies) against the register-streamed
 kernel (conv_stream.hip) with 32- and 64-pixel tiles.  Back-to-back launches of one conv (weights L2-warm), HIP events around the batch.
-GPU box:  python tools/conv_stream_probe.py [scale ...]      (scales: 16 8 c3_16; default all)
-Sweep of the ring depth / waves per workgroup (a build with the extra instantiations):
-          PPMS_BUILD_DEFINES=-DPPMS_STREAM_PROBE python tools/conv_stream_probe.py --sweep 16 8"""
+GPU box:  python tools/conv_stream_probe.py [scale ...]      (scales: 16 8 c3_16; default all)"""
 import ctypes as C
 import math
 import os
@@ -45,19 +43,9 @@ def bench(op, n=40):
     return a.elapsed_time(b) / n * 1e3
 
 
-def hint_of(kg, pb, d):
-    return (kg << 8) | (pb << 4) | d
-
-
-SWEEP = [(4, 1, 6), (4, 1, 8), (4, 1, 10), (8, 1, 4), (8, 1, 6), (8, 1, 8), (4, 2, 3), (4, 2, 4), (4, 2, 6), (8, 2, 3), (8, 2, 4), (8, 2, 6)]
-
-
 def main():
     lib = L.load()
-    args = [a for a in sys.argv[1:] if a != "--sweep"]
-    sweep = "--sweep" in sys.argv[1:]
-    variants = [(7, hint_of(*v)) for v in SWEEP] if sweep else [(7, 1), (7, 2)]
-    for key in (args or list(SCALES)):
+    for key in (sys.argv[1:] or list(SCALES)):
         T, H, W, convs = SCALES[key]
         P = T * H * W
         tot = {"conv2": 0.0, "s1": 0.0, "s2": 0.0, "best": 0.0}
@@ -75,7 +63,7 @@ def main():
             out = L.SPTensor(P, M, DEV)
             gflop = 2.0 * P * cout * cin * k3[0] * k3[1] * k3[2] * 1e-9
             res, times = [], {}
-            for ver, hint in [(2, 0)] + variants:
+            for ver, hint in [(2, 0), (7, 1), (7, 2)]:
                 wp = w
                 ys = ver == 2 and k3[1] > 1 and k3[2] == 1
                 if ys:
@@ -99,13 +87,10 @@ def main():
                     times["conv2"] = t_us
                     res.append(f"conv2{'y' if ys else ' '} x{op.nslice}: {t_us:6.1f}")
                 else:
-                    if hint > 2 and (cin // 16) % (hint >> 8):
-                        continue
                     op = ConvOp(d, [packed, b], 7, hint)
                     t_us = bench(op)
                     times[f"s{hint}"] = t_us
-                    tag = f"pb={hint}" if hint <= 2 else "kg%d pb%d d%d" % (hint >> 8, (hint >> 4) & 15, hint & 15)
-                    res.append(f"{tag}: {t_us:6.1f}" + (f" ({gflop / t_us * 1e3:4.0f} TF/s)" if not sweep else ""))
+                    res.append(f"pb={hint}: {t_us:6.1f} ({gflop / t_us * 1e3:4.0f} TF/s)")
             best = min(v for k, v in times.items() if k != "conv2")
             for k in ("conv2", "s1", "s2"):
                 tot[k] += times.get(k, 0.0)

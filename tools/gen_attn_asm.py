@@ -30,10 +30,7 @@ MF = "v_mfma_f32_16x16x32_bf16"          # S^T = K' Q^T: bf16 operands, as the r
 MF_P = {False: "v_mfma_f32_16x16x32_bf16", True: "v_mfma_f32_16x16x32_f16"}      # O^T += V^T P~ and l += 1 P~: the format of P~ (and of the V^T image)
 CVT_P = {False: "v_cvt_pk_bf16_f32", True: "v_cvt_pk_f16_f32"}
 RINGK = 4
-ABL = int(os.environ.get("PPMS_ATTN_ABL", "0"))     # timing experiments only (wrong results): 1 drops the softmax VALU work, 2 the LDS
-                                                    # requests and waits, 4 the MFMAs, 8 the address upkeep
-SACC = "a" if ABL & 128 else "v"                    # (128, with 1: the S^T accumulators in the AGPR half -- what would the VGPR placement cost?)
-DSLOT = [int(x) for x in os.environ.get("PPMS_ATTN_DSLOT", "18,22,50,58").split(",")]
+DMA_SLOTS = [18, 22, 50, 58]                        # slots behind which the four LDS-DMA instructions of a substep are issued
 CUNIT = [0, 4, 8, 12, 24, 28, 32, 36]               # slot at which K unit u = (block row u >> 2, k-step u & 3) is first consumed
 
 
@@ -42,10 +39,6 @@ class Emit:
         self.lines = []
 
     def asm(self, text, outs=(), ins=()):
-        op = text.split()[0]
-        if ((ABL & 1 and op in ("v_exp_f32", "v_fma_f32", "v_cvt_pk_bf16_f32", "v_cvt_pk_f16_f32")) or (ABL & 2 and (op == "ds_read_b128" or "lgkmcnt" in text)) or
-                (ABL & 4 and op.startswith("v_mfma")) or (ABL & 8 and op == "v_add_u32")):
-            return
         ops = list(outs) + list(ins)
         for i, (nm, _, _) in enumerate(ops):
             text = text.replace("{" + nm + "}", "%" + str(i))
@@ -91,9 +84,9 @@ def substep(par, p16):
             u = (s >> 2) if s < 16 else 4 + ((s - 24) >> 2)
             b, ks, qb = u >> 2, u & 3, s & 3
             if ks == 0:
-                E.asm(f"{MF} {{c}}, {{a}}, {{b}}, 0", [("c", "=&" + SACC, f"nxt[{b}][{qb}]")], [("a", "v", f"ring[{u % RINGK}]"), ("b", "v", f"qf[{qb}][{ks}]")])
+                E.asm(f"{MF} {{c}}, {{a}}, {{b}}, 0", [("c", "=&v", f"nxt[{b}][{qb}]")], [("a", "v", f"ring[{u % RINGK}]"), ("b", "v", f"qf[{qb}][{ks}]")])
             else:
-                E.asm(f"{MF} {{c}}, {{a}}, {{b}}, {{c}}", [("c", "+" + SACC, f"nxt[{b}][{qb}]")], [("a", "v", f"ring[{u % RINGK}]"), ("b", "v", f"qf[{qb}][{ks}]")])
+                E.asm(f"{MF} {{c}}, {{a}}, {{b}}, {{c}}", [("c", "+v", f"nxt[{b}][{qb}]")], [("a", "v", f"ring[{u % RINGK}]"), ("b", "v", f"qf[{qb}][{ks}]")])
         else:
             qb, d = (3, s - 16) if s < 24 else (0, s - 40) if s < 48 else (1, s - 48) if s < 56 else (2, s - 56)
             E.asm(f"{MFP} {{c}}, {{a}}, {{b}}, {{c}}", [("c", "+a", f"o[{d}][{qb}]")], [("a", "v", f"vt[{d}]"), ("b", "v", f"pf[{qb}]")])
@@ -108,8 +101,8 @@ def substep(par, p16):
             queue.append(f"v{d}")
         # ---- LDS-DMA of the tile three ahead: K chunks in even substeps, V^T chunks in odd ones, one instruction per ~16 slots (issued in a
         #      burst at the top of the iteration -- no MFMA in flight behind the barrier -- the eight of them cost 6.5 % of the loop)
-        if s in DSLOT:
-            i = DSLOT.index(s)
+        if s in DMA_SLOTS:
+            i = DMA_SLOTS.index(s)
             E.asm("s_mov_b32 m0, {m}\\n\\ts_nop 0\\n\\tglobal_load_lds_dwordx4 {o}, {p}", [],
                   [("o", "v", f"{'koff' if par == 0 else 'voff'}[{i}]"), ("p", "s", "kp" if par == 0 else "vp"), ("m", "s", f"dst[{par * 4 + i}]")])
         # ---- VALU: pair p owns slots 4p .. 4p+3 -------------------------------------------------------------------------------------

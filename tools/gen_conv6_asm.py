@@ -14,8 +14,6 @@ usage: python tools/gen_conv6_asm.py
 import os
 
 MF = "v_mfma_f32_16x16x32_bf16"
-ABL = int(os.environ.get("PPMS_CONV6_ABL", "0"))     # timing experiments only (wrong results): 1 drops the LDS fragment reads and their waits,
-                                                     # 2 the weight-fragment loads, 4 the MFMAs, 8 the LDS-DMA pieces of the loop, 32 the waits for the LDS fragment reads (the reads stay)
 VARIANTS = [(4, 13), (3, 13), (4, 7), (4, 6)]        # (MB, NBW): M = 256, M = 192, the two pixel halves of M = 128
 
 
@@ -42,9 +40,6 @@ class Emit:
         self.lines = []
 
     def asm(self, text, outs=(), ins=(), clob='"memory"'):
-        op = text.split()[0]
-        if (ABL & 32 and "lgkmcnt" in text) or (ABL & 1 and (op == "ds_read_b128" or "lgkmcnt" in text)) or (ABL & 2 and op == "global_load_dwordx4") or (ABL & 4 and MF in text):
-            return
         ops = list(outs) + list(ins)
         for i, (nm, _, _) in enumerate(ops):
             text = text.replace("{" + nm + "}", "%" + str(i))
@@ -70,7 +65,7 @@ def step(mb, nbw, skip):
         # address register some time AFTER it has issued -- the next s_mov m0 / a write of that register within a few cycles of it misdirects the
         # transfer (tools/conv6_stress.py: back-to-back pieces left window rows stale; 64 cycles of distance: 300 launches clean)
         nonlocal slots
-        if pending == 0 and not (ABL & 8) and (mb >= 4 or group == 1):
+        if pending == 0 and (mb >= 4 or group == 1):
             E.c(f"hook({slots});")
             slots += 1
 
