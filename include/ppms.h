@@ -113,16 +113,26 @@ typedef struct ppms_conv {
 /* desc: host copy (validated, sizes the grid, and -- since ABI v2 -- copied into the kernel arguments at launch, so it may be
  * changed or freed as soon as the call returns); dev_desc: the same bytes in device memory (caller-owned; must be non-NULL, kept in
  * the signature for ABI stability: the kernels no longer read it -- a descriptor in the kernel arguments saves a dependent memory
- * round trip at the head of every launch and is known not to alias the kernel's stores). */
+ * round trip at the head of every launch and is known not to alias the kernel's stores).
+ *
+ * THE CONTRACT OF THE RATINGS.  Every kernel below has a rating function (*_applicable, *_slices) next to its launch entry point, and both
+ * run the same descriptor check (csrc/conv_check.h) and the same geometry planner: a non-zero rating, plus a descriptor that passes the
+ * operand tier, means the launch entry point returns 0 -- called with the library's own choice of hints (0) and, for the sliced forms, the
+ * returned slice count.  The check has two tiers.  Shape / addressing tier, what a rating relies on: nseg 1..2, groups, a volume > 0,
+ * t_halo 0..8, odd taps within the kernel's maxima, M / m_split, per segment non-NULL 16-byte-aligned planes, c a multiple of the
+ * kernel's chunk, ld % 8 == 0, and whether the kernel serves out_vt / PPMS_EPI_ADDF32.  Operand tier, what only a launch needs: w and
+ * bias, and per live epilogue half n_valid > 0, a known kind, the operands of that kind and their alignment (16 bytes; ld % 8 == 0 for SP
+ * views, % 4 for fp32).  ppms_conv_gemm2 / 5 / 6 ratings never look at the operand tier; ppms_gemm1_applicable and
+ * ppms_conv_stream_applicable check both.  A refusal leaves "<kernel>: <field>=<value> ..." in ppms_last_error(). */
 /* Data-reuse tiling: all couts of a pixel tile per workgroup, LDS activation window swept by the kw taps.
- * desc->w must be in the pack_conv2 layout (ppmstereo_amd/packing.py).
+ * desc->w must be in the pack_conv2 layout (ppmstereo_amd/packing.py); segments in multiples of 32 channels, M a multiple of 64, kw <= 15.
  * wm_hint: 64-cout blocks per workgroup (1..4), 0 = let the library choose from the grid size. */
 int ppms_conv_gemm2(const ppms_conv* desc, const ppms_conv* dev_desc, int wm_hint, void* stream);
 /* K-sliced form of the same kernel for small maps (1/16 and 1/8 scales: fewer workgroups than CUs, long K loops):
  * nslice workgroups share each output tile and leave fp32 partial sums in `workspace` (caller-owned,
  * ppms_conv_gemm2_slice_workspace_bytes() bytes), a second launch sums them in slice order (deterministic) and runs the
  * fused epilogue.  ppms_conv_gemm2_slices() returns the slice count that pays off for a descriptor (1: use
- * ppms_conv_gemm2).  Not for epilogues with out_vt. */
+ * ppms_conv_gemm2 -- also for what the kernel does not serve).  Not for epilogues with out_vt. */
 int ppms_conv_gemm2_slices(const ppms_conv* desc);
 int64_t ppms_conv_gemm2_slice_workspace_bytes(const ppms_conv* desc, int nslice);
 int ppms_conv_gemm2_sliced(const ppms_conv* desc, const ppms_conv* dev_desc, int nslice, void* workspace, void* stream);
@@ -137,7 +147,9 @@ int ppms_conv_gemm2_ysweep(const ppms_conv* desc, const ppms_conv* dev_desc, int
  * sweep-ordered: y-swept kernels with kh / kw swapped, 2-D swept ones with (ky, kx) flattened into x) and go from L2 straight to registers; the activation window holds 16 channels and is
  * double buffered, so the loop synchronises once per window instead of once per k-step.  One 8-wave workgroup per CU owns ALL
  * couts (M == 256, or M == 128 with the K loop split between two wave groups) of a tile of nbt = 7 or 8 blocks of 32 pixels, split
- * 4 + 3 (4 + 4) so that every SIMD carries the same load: 51 200 pixels = 240 tiles of 224 on 256 CUs.  nbt = 0: the library picks. */
+ * 4 + 3 (4 + 4) so that every SIMD carries the same load: 51 200 pixels = 240 tiles of 224 on 256 CUs.  nbt = 0: the library picks.
+ * M == 128 / 192 / 256, segments in multiples of 16 channels, kh, kw <= 15, < 2^22 pixels; out_vt with M != 192.  applicable: 1 = served and
+ * the map gives about a workgroup per CU. */
 int ppms_conv_gemm5_applicable(const ppms_conv* desc);
 int ppms_conv_gemm5(const ppms_conv* desc, const ppms_conv* dev_desc, int nbt, void* stream);
 /* K-sliced form of the same kernel for maps with fewer tiles than CUs (the 1/8 and 1/16 scales): nslice workgroups share each

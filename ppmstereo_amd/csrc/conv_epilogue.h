@@ -278,17 +278,3 @@ __device__ __forceinline__ void stage_read8(const float* stg, int prow, int q, f
         v[4 + j] = b[j];
     }
 }
-
-// host-side check shared by the kernels that use the coalesced form
-inline const char* epilogue_row8_check(const ppms_epilogue& e) {
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    if (e.out_sp.hi != nullptr && !(al16(e.out_sp.hi) && al16(e.out_sp.lo) && e.out_sp.ld % 8 == 0)) return "out_sp must be 16-byte aligned with ld % 8 == 0";
-    if ((e.kind == PPMS_EPI_RESID || e.kind == PPMS_EPI_RH || e.kind == PPMS_EPI_GRU) &&
-        !(al16(e.aux_sp.hi) && al16(e.aux_sp.lo) && e.aux_sp.ld % 8 == 0))
-        return "aux_sp must be 16-byte aligned with ld % 8 == 0";
-    if (e.out_f32 != nullptr && !(al16(e.out_f32) && e.out_f32_ld % 4 == 0)) return "out_f32 must be 16-byte aligned with ld % 4 == 0";
-    if (e.kind == PPMS_EPI_GRU && !(al16(e.aux_f32) && e.aux_f32_ld % 4 == 0)) return "aux_f32 must be 16-byte aligned with ld % 4 == 0";
-    if (e.pre_f32 != nullptr && !(al16(e.pre_f32) && e.pre_f32_ld % 4 == 0)) return "pre_f32 must be 16-byte aligned with ld % 4 == 0";
-    if (e.out_vt != nullptr && (e.kind != PPMS_EPI_STORE || e.pre_f32 != nullptr)) return "out_vt needs a STORE epilogue without pre_f32";
-    return nullptr;
-}

@@ -17,6 +17,7 @@
 // k-step = ((kz*kh + ky) * nchunk + chunk) * kw + kx.
 #include "common.h"
 #include "conv_epilogue.h"
+#include "conv_check.h"
 #include <type_traits>
 
 namespace {
@@ -467,162 +468,29 @@ __global__ __launch_bounds__(256) void conv_slice_reduce_kernel(const ppms_conv 
     epilogue_row8(p.epi[half], v, pix, c8 - (half ? p.m_split : 0), p.H * p.W);
 }
 
-template <int WM, int KG>
-int launch2(const ppms_conv* d, const ppms_conv* dev_desc, const Geo2& g, int ntiles, hipStream_t stream) {
-    size_t lds = (size_t)KG * ((size_t)2 * WM * A_BLK + (size_t)g.bstages * 2 * g.Wr * 64);
-    const size_t red = (size_t)(KG - 1) * 2 * WM * 64 * 64 * 4;          // partial-accumulator exchange reuses the staging area
-    if (red > lds) lds = red;
-    const size_t stg = (size_t)2 * WM * STG_WAVE;                        // so do the epilogue's transposition patches
-    if (stg > lds) lds = stg;
-    static ppms_device_once once;                                        // one per template instantiation
-    once.run([] { (void)hipFuncSetAttribute((const void*)conv2_kernel<WM, KG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-    if (lds > 160 * 1024) {
-        ppms_set_error("conv_gemm2: LDS budget exceeded (%zu B)", lds);
-        return PPMS_EINVAL;
-    }
-    hipLaunchKernelGGL((conv2_kernel<WM, KG>), dim3(ntiles * g.mgroups, g.nslice), dim3(128 * WM * KG), lds, stream, *d, g);
-    return ppms_check_launch("conv_gemm2");
-}
+constexpr ConvRules RULES2 = {"conv_gemm2", /*chunk*/ BK, /*M*/ 64, /*m_split*/ 64, /*kt, kh, kw <=*/ 0, 0, 15, /*grouped*/ false, /*out_vt*/ true, /*addf32*/ true, /*ld <=*/ 0};
 
-}  // namespace
+struct Plan2 {
+    Geo2 g;
+    int wm, kgs, ntiles;     // 64-cout blocks per workgroup, K-groups inside it, pixel tiles
+    size_t lds;
+};
 
-static int conv2_launch(const ppms_conv* d, const ppms_conv* dev_desc, int wm_hint, int nslice, float* part, void* stream, int ysweep = 0);
-#ifdef PPMS_CONV2_TIMING
-extern "C" void ppms_debug_conv2_timing(long long* p) { g_conv2_dbg = p; }      // debug builds only (tools/conv2_phase_probe.py)
-#endif
-
-// wm_hint: 0 = choose (all couts per workgroup when the grid still fills the chip, otherwise 64-cout blocks)
-extern "C" int ppms_conv_gemm2(const ppms_conv* d, const ppms_conv* dev_desc, int wm_hint, void* stream) {
-    return conv2_launch(d, dev_desc, wm_hint, 1, nullptr, stream);
-}
-
-// Small maps (fewer workgroups than the chip has CUs, long K loops): how many grid-level K slices pay off.  1 = none.
-extern "C" int ppms_conv_gemm2_slices(const ppms_conv* d) {
-    if (d == nullptr || d->nseg < 1 || d->nseg > 2 || d->M <= 0 || d->M % 64 != 0) return 1;
-    if (d->epi[0].out_vt != nullptr || (d->m_split < d->M && d->epi[1].out_vt != nullptr)) return 1;   // V^T is written from the accumulators
+// Patch / window geometry and launch shape: what only this kernel limits, after the shared shape tier (the one path of
+// ppms_conv_gemm2_ysweep_slices and every launch).
+// mode: 0 = taps along x (one window per (dt, dy)); 1 = (kt, kh, 1) kernel swept along y; 2 = 2-D window: all kh x kw taps of
+// a (dt, chunk) step one window with a halo in x and y (weights packed with (ky, kx) flattened into x)
+bool plan2(const ppms_conv* d, int wm_hint, int nslice, int mode, Plan2& pl) {
+    const bool ysweep = mode == 1, win2d = mode == 2;
+    Geo2& g = pl.g;
+    CONV_REFUSE_IF(ysweep && !(d->kw == 1 && d->kh > 1), "conv_gemm2: y sweep is for (kt, kh, 1) kernels (kh=%d kw=%d)", d->kh, d->kw);
+    CONV_REFUSE_IF(win2d && !(d->kw > 1 && d->kh > 1), "conv_gemm2: the 2-D window is for kernels with kh > 1 and kw > 1 (kh=%d kw=%d)", d->kh, d->kw);
+    // pixel INDICES are 32-bit inside the kernel (slot offsets, (dt, dy) shifts of up to kt / 2 frames); every byte offset is formed in 64 bits
+    CONV_REFUSE_IF((int64_t)(d->T + 2 * d->t_halo + d->kt) * d->H * d->W >= (1ll << 30), "conv_gemm2: volume %dx%dx%d too large for 32-bit pixel indices", d->T, d->H, d->W);
     int nchunk = 0;
     for (int s = 0; s < d->nseg; ++s) nchunk += d->seg[s].c / BK;
-    const int64_t P = (int64_t)d->T * d->H * d->W;
-    const int64_t nwg = (P + 127) / 128 * (d->M / 64);              // 64-cout x 128-pixel workgroups without slicing
-    if (nwg >= 512) return 1;
-    const int rs_per_kz = d->kh * nchunk;
-    const int64_t steps = (int64_t)d->kt * rs_per_kz * d->kw;        // k-steps of the whole K loop
-    // Short K loops: the unsliced launch splits K INSIDE the workgroup (2 or 4 K-groups, conv2_launch) and needs no reduce launch; it wins
-    // when that leaves <= 10 k-steps per K-group, the workgroups fit one round on the chip and still make >= 512 waves (tools/slice_tune.py,
-    // 1/16 and 1/8 scales of config 2: mask head 25.8 -> 21.6 us, the GRU's (1,1,5) tails 26 -> 18 us, the 384-wide 1x1 GEMMs 21.7 -> 16.5 us)
-    {
-        const int64_t ntiles = (P + 127) / 128;
-        const int kg = (ntiles < 160 || d->M == 64) ? ((nwg <= 128 && nchunk % 4 == 0) ? 4 : (nwg <= 512 && nchunk % 2 == 0) ? 2 : 1) : 1;
-        if (kg > 1 && steps / kg <= 10 && nwg <= 256 && nwg * kg * 2 >= 512) return 1;
-    }
-    int best = 1;
-    for (int s = 2; s <= 8; ++s)
-        if (rs_per_kz % s == 0 && nwg * s <= 1024 && steps / s >= 6) best = s;
-    return best;
-}
-
-// Same planner for the y-swept and the 2-D window forms (row-steps per temporal tap = chunks only)
-extern "C" int ppms_conv_gemm2_ysweep_slices(const ppms_conv* d) {
-    if (d == nullptr || d->kh <= 1) return 0;
-    if (d->kw > 1) {                   // 2-D window: some 128-pixel patch with its halo must fit the staging slots
-        bool fits = false;
-        for (int C = 16; C <= 128; C *= 2) fits = fits || (C + d->kw - 1) * (128 / C + d->kh - 1) <= 256;
-        if (!fits) return 0;
-    }
-    ppms_conv t = *d;
-    t.kw = d->kh * d->kw;              // as an x-swept (1, 1, taps) conv: same number of workgroups, row-steps and k-steps
-    t.kh = 1;
-    return ppms_conv_gemm2_slices(&t);
-}
-
-extern "C" int64_t ppms_conv_gemm2_slice_workspace_bytes(const ppms_conv* d, int nslice) {
-    if (d == nullptr || nslice <= 1) return 0;
-    return (int64_t)nslice * d->T * d->H * d->W * d->M * 4;
-}
-
-// second half of every K-sliced launch (also conv_gemm5.hip's): sums the slices' partial tiles, adds the bias, runs the fused epilogue
-int ppms_launch_slice_reduce(const ppms_conv* d, const ppms_conv* dev_desc, const float* workspace, int nslice, void* stream) {
-    const int64_t P = (int64_t)d->T * d->H * d->W;
-    const int64_t total = P * (d->M / 8);
-    hipLaunchKernelGGL(conv_slice_reduce_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, *d, workspace, nslice, P);
-    return ppms_check_launch("conv_slice_reduce");
-}
-
-// K-sliced form for small maps: nslice workgroups share each output tile (each takes every nslice-th row-step of the K loop
-// and writes fp32 partial sums to `workspace`), then a reduce kernel sums them in slice order and runs the fused epilogue.
-extern "C" int ppms_conv_gemm2_sliced(const ppms_conv* d, const ppms_conv* dev_desc, int nslice, void* workspace, void* stream) {
-    PPMS_REQUIRE(nslice >= 1 && nslice <= 16, "conv_gemm2_sliced: nslice=%d", nslice);
-    if (nslice == 1) return conv2_launch(d, dev_desc, 0, 1, nullptr, stream);
-    PPMS_REQUIRE(workspace != nullptr && ((uintptr_t)workspace & 15) == 0, "conv_gemm2_sliced: workspace missing or not 16-B aligned");
-    const int rc = conv2_launch(d, dev_desc, 1, nslice, (float*)workspace, stream);
-    if (rc != 0) return rc;
-    const int64_t P = (int64_t)d->T * d->H * d->W;
-    const int64_t total = P * (d->M / 8);
-    hipLaunchKernelGGL(conv_slice_reduce_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, *d, (const float*)workspace, nslice, P);
-    return ppms_check_launch("conv_gemm2_sliced");
-}
-
-// Convs with kh > 1 whose taps all step ONE halo'd window per (dt, chunk) (the plain entry loads a window per kernel row):
-// (kt, kh, 1) kernels are swept along y, weights packed with kh / kw swapped; kernels with kw > 1 too use a 2-D window, weights
-// packed with (ky, kx) flattened into x -- the sweep-ordered packs conv_gemm5 / conv_gemm6 use too.  nslice as in ppms_conv_gemm2_sliced.
-extern "C" int ppms_conv_gemm2_ysweep(const ppms_conv* d, const ppms_conv* dev_desc, int nslice, void* workspace, void* stream) {
-    PPMS_REQUIRE(d != nullptr && d->kh > 1, "conv_gemm2_ysweep: needs a kernel with kh > 1");
-    const int mode = d->kw > 1 ? 2 : 1;              // kw > 1: 2-D window over all kh x kw taps
-    PPMS_REQUIRE(nslice >= 1 && nslice <= 16, "conv_gemm2_ysweep: nslice=%d", nslice);
-    if (nslice == 1) return conv2_launch(d, dev_desc, 0, 1, nullptr, stream, mode);
-    PPMS_REQUIRE(workspace != nullptr && ((uintptr_t)workspace & 15) == 0, "conv_gemm2_ysweep: workspace missing or not 16-B aligned");
-    const int rc = conv2_launch(d, dev_desc, 1, nslice, (float*)workspace, stream, mode);
-    if (rc != 0) return rc;
-    const int64_t P = (int64_t)d->T * d->H * d->W;
-    const int64_t total = P * (d->M / 8);
-    hipLaunchKernelGGL(conv_slice_reduce_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, *d, (const float*)workspace, nslice, P);
-    return ppms_check_launch("conv_gemm2_ysweep");
-}
-
-static int conv2_launch(const ppms_conv* d, const ppms_conv* dev_desc, int wm_hint, int nslice, float* part, void* stream, int ysweep) {
-    PPMS_REQUIRE(d != nullptr && dev_desc != nullptr, "conv_gemm2: null descriptor (host copy and device copy are both required)");
-    PPMS_REQUIRE(d->nseg == 1 || d->nseg == 2, "conv_gemm2: nseg=%d", d->nseg);
-    PPMS_REQUIRE(d->groups <= 1, "conv_gemm2: a grouped convolution (groups=%d) is served by ppms_conv_gemm6 only", d->groups);
-    PPMS_REQUIRE(d->T > 0 && d->H > 0 && d->W > 0, "conv_gemm2: bad volume %dx%dx%d", d->T, d->H, d->W);
-    PPMS_REQUIRE(d->t_halo >= 0 && d->t_halo <= 8, "conv_gemm2: t_halo=%d", d->t_halo);
-    PPMS_REQUIRE((d->kt & 1) && (d->kh & 1) && (d->kw & 1) && d->kw <= 15, "conv_gemm2: kernel extents must be odd, kw <= 15");
-    PPMS_REQUIRE(d->M > 0 && d->M % 64 == 0 && d->m_split % 64 == 0, "conv_gemm2: M=%d / m_split=%d not multiples of 64", d->M, d->m_split);
-    PPMS_REQUIRE(d->w != nullptr && d->bias != nullptr, "conv_gemm2: weights/bias missing");
-    // pixel INDICES are 32-bit inside the kernel (slot offsets, (dt, dy) shifts of up to kt / 2 frames); every byte offset is formed in 64 bits
-    PPMS_REQUIRE((int64_t)(d->T + 2 * d->t_halo + d->kt) * d->H * d->W < (1ll << 30), "conv_gemm2: volume too large for 32-bit pixel indices");
-    int nchunk = 0;
-    for (int s = 0; s < d->nseg; ++s) {
-        PPMS_REQUIRE(d->seg[s].hi && d->seg[s].lo && d->seg[s].c > 0 && d->seg[s].c % BK == 0 && d->seg[s].ld % 8 == 0,
-                     "conv_gemm2: segment %d needs hi/lo planes, c %% 32 == 0 and ld %% 8 == 0 (c=%d ld=%d)", s, d->seg[s].c, d->seg[s].ld);
-        PPMS_REQUIRE(((uintptr_t)d->seg[s].hi & 15) == 0 && ((uintptr_t)d->seg[s].lo & 15) == 0, "conv_gemm2: segment %d not 16-B aligned", s);
-        nchunk += d->seg[s].c / BK;
-    }
-    for (int hlf = 0; hlf < 2; ++hlf) {
-        const ppms_epilogue& e = d->epi[hlf];
-        if (hlf == 1 && d->m_split >= d->M) break;
-        PPMS_REQUIRE(e.n_valid > 0, "conv_gemm2: epilogue %d has n_valid=%d", hlf, e.n_valid);
-        PPMS_REQUIRE(e.pre_f32 == nullptr || (e.n_valid % 4 == 0 && e.pre_f32_ld % 4 == 0), "conv_gemm2: pre_f32 needs n_valid and pre_f32_ld to be multiples of 4");
-        {
-            const char* why = epilogue_row8_check(e);
-            PPMS_REQUIRE(why == nullptr, "conv_gemm2: epilogue %d: %s", hlf, why ? why : "");
-        }
-        if (e.out_sp.hi) PPMS_REQUIRE(e.out_sp.lo && e.out_sp.ld % 4 == 0 && ((uintptr_t)e.out_sp.hi & 7) == 0 && ((uintptr_t)e.out_sp.lo & 7) == 0,
-                                      "conv_gemm2: epilogue %d SP output misaligned", hlf);
-        if (e.out_f32) PPMS_REQUIRE(e.out_f32_ld % 4 == 0 || e.kind == PPMS_EPI_ADDF32, "conv_gemm2: epilogue %d f32 ld", hlf);
-        if (e.kind == PPMS_EPI_RESID || e.kind == PPMS_EPI_RH || e.kind == PPMS_EPI_GRU)
-            PPMS_REQUIRE(e.aux_sp.hi && e.aux_sp.lo && e.aux_sp.ld % 4 == 0, "conv_gemm2: epilogue %d needs aux_sp", hlf);
-        if (e.kind == PPMS_EPI_GRU) PPMS_REQUIRE(e.aux_f32 != nullptr, "conv_gemm2: GRU epilogue needs z");
-        if (e.kind == PPMS_EPI_ADDF32) PPMS_REQUIRE(e.out_f32 != nullptr, "conv_gemm2: ADDF32 epilogue needs out_f32");
-    }
     // patch width: the power of two in [16,128] wasting the fewest pixels of the 128-pixel tile (ties: the widest for an x
     // sweep, the narrowest -- tallest patch, smallest halo share -- for a y sweep)
-    // ysweep: 0 = taps along x (one window per (dt, dy)); 1 = (kt, kh, 1) kernel swept along y; 2 = 2-D window: all kh x kw taps of
-    // a (dt, chunk) step one window with a halo in x and y (weights packed with (ky, kx) flattened into x)
-    const bool win2d = ysweep == 2;
-    ysweep = ysweep == 1;
-    PPMS_REQUIRE(!ysweep || (d->kw == 1 && d->kh > 1), "conv_gemm2: y sweep is for (kt, kh, 1) kernels");
-    PPMS_REQUIRE(!win2d || (d->kw > 1 && d->kh > 1), "conv_gemm2: the 2-D window is for kernels with kh > 1 and kw > 1");
-    Geo2 g;
     int bestC = 16;
     double bestw = 1e30;
     for (int C = 16; C <= 128; C *= 2) {
@@ -635,7 +503,7 @@ static int conv2_launch(const ppms_conv* d, const ppms_conv* dev_desc, int wm_hi
             bestC = C;
         }
     }
-    PPMS_REQUIRE(bestw < 1e29, "conv_gemm2: no patch shape fits the window");
+    CONV_REFUSE_IF(bestw >= 1e29, "conv_gemm2: no patch shape fits the window of kh=%d kw=%d", d->kh, d->kw);
     g.C = bestC;
     g.R = 128 / bestC;
     g.logC = 0;
@@ -660,17 +528,14 @@ static int conv2_launch(const ppms_conv* d, const ppms_conv* dev_desc, int wm_hi
             g.wr_magic = 0;
             break;
         }
-    g.part = part;
+    g.part = nullptr;
     g.P = (int64_t)d->T * d->H * d->W;
-#ifdef PPMS_CONV2_TIMING
-    g.dbg = g_conv2_dbg;
-#endif
+    g.kho = (ysweep || win2d) ? 1 : d->kh;                // kernel rows NOT swept inside a window
     if (nslice > 1) {
-        PPMS_REQUIRE((((ysweep || win2d) ? 1 : d->kh) * nchunk) % nslice == 0, "conv_gemm2: %d row-steps per temporal tap do not split into %d slices",
-                     ((ysweep || win2d) ? 1 : d->kh) * nchunk, nslice);
-        PPMS_REQUIRE(d->epi[0].out_vt == nullptr && (d->m_split >= d->M || d->epi[1].out_vt == nullptr), "conv_gemm2: sliced launch cannot write out_vt");
+        CONV_REFUSE_IF((g.kho * nchunk) % nslice != 0, "conv_gemm2: %d row-steps per temporal tap do not split into nslice=%d", g.kho * nchunk, nslice);
+        CONV_REFUSE_IF(conv_has_out_vt(d), "conv_gemm2: a sliced launch cannot write out_vt");
     }
-    const int ntiles = g.tiles_x * g.tiles_y * d->T;
+    pl.ntiles = g.tiles_x * g.tiles_y * d->T;
     const int mblocks = d->M / 64;
     int wm = wm_hint;
     if (wm <= 0) {
@@ -678,42 +543,145 @@ static int conv2_launch(const ppms_conv* d, const ppms_conv* dev_desc, int wm_hi
         wm = mblocks <= 3 ? mblocks : 2;
         if (mblocks == 4 && d->kw == 1 && d->kh == 1) wm = 4;   // no window reuse across taps (1x1, temporal): share each window among all couts
         if (mblocks % wm) wm = 1;
-        if (ntiles < 160 && mblocks > 1) wm = 1;          // small maps: spread cout blocks over more workgroups
+        if (pl.ntiles < 160 && mblocks > 1) wm = 1;          // small maps: spread cout blocks over more workgroups
     }
-    PPMS_REQUIRE(wm >= 1 && wm <= 4 && mblocks % wm == 0, "conv_gemm2: wm=%d does not divide M/64=%d", wm, mblocks);
+    CONV_REFUSE_IF(wm < 1 || wm > 4 || mblocks % wm != 0, "conv_gemm2: wm=%d does not divide M/64=%d", wm, mblocks);
+    pl.wm = wm;
     g.mgroups = mblocks / wm;
     // kw > 1: the window changes every kw-th k-step -> keep ONE copy (extra barrier per switch) so that three 4-wave
     // workgroups fit a CU's LDS; kw == 1: it changes every k-step -> double-buffer it
     g.bstages = (g.ksw == 1) ? 2 : 1;
     const int maxslot = wm == 4 ? 2 : wm == 3 ? 3 : wm == 2 ? 4 : 8;
-    PPMS_REQUIRE(g.Wr * 4 <= 128 * wm * maxslot, "conv_gemm2: window of %d rows does not fit the staging slots", g.Wr);
-    PPMS_REQUIRE(2 * wm * A_BLK + g.bstages * 2 * g.Wr * 64 <= 160 * 1024, "conv_gemm2: LDS budget exceeded");
-    hipStream_t st = (hipStream_t)stream;
+    CONV_REFUSE_IF(g.Wr * 4 > 128 * wm * maxslot, "conv_gemm2: window of %d rows (kh=%d kw=%d) does not fit the staging slots", g.Wr, d->kh, d->kw);
     // small maps: split K inside the workgroup so that more waves work on the few tiles there are
-    const int nwg = ntiles * g.mgroups;
+    const int nwg = pl.ntiles * g.mgroups;
     int kgs = 1;
     if (wm == 1 && wm_hint <= 0 && nslice == 1) {
         if (nwg <= 128 && nchunk % 4 == 0) kgs = 4;
         else if (nwg <= 512 && nchunk % 2 == 0) kgs = 2;   // ~68 KiB of LDS each: two such workgroups share a CU
     }
     if (kgs > 1) g.bstages = 1;                // K-groups keep ONE window copy each (LDS budget), at one more barrier per window
+    pl.kgs = kgs;
     {   // multiply-high reciprocals of the kernel's runtime divisors (fdiv)
         auto magic = [](int dd) { return dd == 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)dd) + 1u; };
-        g.kho = (ysweep || win2d) ? 1 : d->kh;
         const int64_t rows_all = (int64_t)d->kt * d->kh * nchunk;
         const int kstride = kgs * nslice;
-        PPMS_REQUIRE((int64_t)nwg * g.mgroups < (1ll << 32) && (int64_t)ntiles * g.tiles_x < (1ll << 32) && rows_all * nchunk < (1ll << 32) &&
-                         rows_all * kstride < (1ll << 32),
-                     "conv_gemm2: geometry too large for the 32-bit reciprocal divisions");
+        CONV_REFUSE_IF((int64_t)nwg * g.mgroups >= (1ll << 32) || (int64_t)pl.ntiles * g.tiles_x >= (1ll << 32) || rows_all * nchunk >= (1ll << 32) ||
+                           rows_all * kstride >= (1ll << 32),
+                       "conv_gemm2: geometry too large for the 32-bit reciprocal divisions (%d workgroups, %lld row-steps)", nwg, (long long)rows_all);
         g.m_mgroups = magic(g.mgroups), g.m_tiles_x = magic(g.tiles_x), g.m_tiles_y = magic(g.tiles_y), g.m_nchunk = magic(nchunk), g.m_kho = magic(g.kho),
         g.m_kstride = magic(kstride);
     }
-    if (kgs == 4) return launch2<1, 4>(d, dev_desc, g, ntiles, st);
-    if (kgs == 2) return launch2<1, 2>(d, dev_desc, g, ntiles, st);
-    switch (wm) {
-        case 1: return launch2<1, 1>(d, dev_desc, g, ntiles, st);
-        case 2: return launch2<2, 1>(d, dev_desc, g, ntiles, st);
-        case 3: return launch2<3, 1>(d, dev_desc, g, ntiles, st);
-        default: return launch2<4, 1>(d, dev_desc, g, ntiles, st);
+    // K-groups x (2 x wm x 8 KiB weight stages + the window copies); the partial-accumulator exchange and the epilogue's transposition
+    // patches reuse that area
+    pl.lds = (size_t)kgs * ((size_t)2 * wm * A_BLK + (size_t)g.bstages * 2 * g.Wr * 64);
+    const size_t red = (size_t)(kgs - 1) * 2 * wm * 64 * 64 * 4, stg = (size_t)2 * wm * STG_WAVE;
+    if (red > pl.lds) pl.lds = red;
+    if (stg > pl.lds) pl.lds = stg;
+    CONV_REFUSE_IF(pl.lds > 160 * 1024, "conv_gemm2: LDS budget exceeded (%zu B)", pl.lds);
+    return true;
+}
+
+template <int WM, int KG>
+int launch2(const ppms_conv* d, const Plan2& pl, hipStream_t stream) {
+    static ppms_device_once once;                                        // one per template instantiation
+    once.run([] { (void)hipFuncSetAttribute((const void*)conv2_kernel<WM, KG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
+    hipLaunchKernelGGL((conv2_kernel<WM, KG>), dim3(pl.ntiles * pl.g.mgroups, pl.g.nslice), dim3(128 * WM * KG), pl.lds, stream, *d, pl.g);
+    return ppms_check_launch("conv_gemm2");
+}
+
+// Small maps (fewer workgroups than the chip has CUs, long K loops): how many grid-level K slices pay off for a kernel of kh x kw spatial taps.  1 = none.
+int slices2(const ppms_conv* d, int kh, int kw) {
+    if (conv_has_out_vt(d)) return 1;                                 // V^T is written from the accumulators
+    int nchunk = 0;
+    for (int s = 0; s < d->nseg; ++s) nchunk += d->seg[s].c / BK;
+    const int64_t P = (int64_t)d->T * d->H * d->W;
+    const int64_t nwg = (P + 127) / 128 * (d->M / 64);              // 64-cout x 128-pixel workgroups without slicing
+    if (nwg >= 512) return 1;
+    const int rs_per_kz = kh * nchunk;
+    const int64_t steps = (int64_t)d->kt * rs_per_kz * kw;           // k-steps of the whole K loop
+    // Short K loops: the unsliced launch splits K INSIDE the workgroup (2 or 4 K-groups, plan2) and needs no reduce launch; it wins
+    // when that leaves <= 10 k-steps per K-group, the workgroups fit one round on the chip and still make >= 512 waves (tools/slice_tune.py,
+    // 1/16 and 1/8 scales of config 2: mask head 25.8 -> 21.6 us, the GRU's (1,1,5) tails 26 -> 18 us, the 384-wide 1x1 GEMMs 21.7 -> 16.5 us)
+    {
+        const int64_t ntiles = (P + 127) / 128;
+        const int kg = (ntiles < 160 || d->M == 64) ? ((nwg <= 128 && nchunk % 4 == 0) ? 4 : (nwg <= 512 && nchunk % 2 == 0) ? 2 : 1) : 1;
+        if (kg > 1 && steps / kg <= 10 && nwg <= 256 && nwg * kg * 2 >= 512) return 1;
     }
+    int best = 1;
+    for (int s = 2; s <= 8; ++s)
+        if (rs_per_kz % s == 0 && nwg * s <= 1024 && steps / s >= 6) best = s;
+    return best;
+}
+
+}  // namespace
+
+#ifdef PPMS_CONV2_TIMING
+extern "C" void ppms_debug_conv2_timing(long long* p) { g_conv2_dbg = p; }      // debug builds only (tools/conv2_phase_probe.py)
+#endif
+
+extern "C" int ppms_conv_gemm2_slices(const ppms_conv* d) { return conv_check_shape(RULES2, d) ? slices2(d, d->kh, d->kw) : 1; }
+
+// Same planner for the y-swept and the 2-D window forms: as an x-swept (1, 1, kh * kw) conv -- the same number of workgroups, row-steps (chunks
+// only) and k-steps.  0: not a candidate, or the halo'd window does not fit.
+extern "C" int ppms_conv_gemm2_ysweep_slices(const ppms_conv* d) {
+    Plan2 pl;
+    if (!conv_check_shape(RULES2, d) || d->kh <= 1) return 0;
+    const int ns = slices2(d, 1, d->kh * d->kw);
+    return plan2(d, ns > 1 ? 1 : 0, ns, d->kw > 1 ? 2 : 1, pl) ? ns : 0;
+}
+
+extern "C" int64_t ppms_conv_gemm2_slice_workspace_bytes(const ppms_conv* d, int nslice) {
+    if (d == nullptr || nslice <= 1) return 0;
+    return (int64_t)nslice * d->T * d->H * d->W * d->M * 4;
+}
+
+// second half of every K-sliced launch (also conv_gemm5.hip's): sums the slices' partial tiles, adds the bias, runs the fused epilogue
+int ppms_launch_slice_reduce(const ppms_conv* d, const ppms_conv* dev_desc, const float* workspace, int nslice, void* stream) {
+    const int64_t P = (int64_t)d->T * d->H * d->W;
+    const int64_t total = P * (d->M / 8);
+    hipLaunchKernelGGL(conv_slice_reduce_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, *d, workspace, nslice, P);
+    return ppms_check_launch("conv_slice_reduce");
+}
+
+// One launch of any form.  nslice > 1: nslice workgroups share each output tile (each takes every nslice-th row-step of the K loop and
+// writes fp32 partial sums to `workspace`), then the reduce kernel sums them in slice order and runs the fused epilogue.
+static int conv2_launch(const char* who, const ppms_conv* d, const ppms_conv* dev_desc, int wm_hint, int mode, int nslice, void* workspace, void* stream) {
+    PPMS_REQUIRE(nslice >= 1 && nslice <= 16, "%s: nslice=%d", who, nslice);
+    PPMS_REQUIRE(nslice == 1 || (workspace != nullptr && ((uintptr_t)workspace & 15) == 0), "%s: workspace missing or not 16-B aligned", who);
+    Plan2 pl;
+    if (!conv_check_shape(RULES2, d) || !conv_check_operands(RULES2, d) || !plan2(d, nslice > 1 ? 1 : wm_hint, nslice, mode, pl)) return PPMS_EINVAL;
+    PPMS_REQUIRE(dev_desc != nullptr, "conv_gemm2: null device descriptor (host copy and device copy are both required)");
+    pl.g.part = nslice > 1 ? (float*)workspace : nullptr;
+#ifdef PPMS_CONV2_TIMING
+    pl.g.dbg = g_conv2_dbg;
+#endif
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if (pl.kgs == 4) rc = launch2<1, 4>(d, pl, st);
+    else if (pl.kgs == 2) rc = launch2<1, 2>(d, pl, st);
+    else if (pl.wm == 1) rc = launch2<1, 1>(d, pl, st);
+    else if (pl.wm == 2) rc = launch2<2, 1>(d, pl, st);
+    else if (pl.wm == 3) rc = launch2<3, 1>(d, pl, st);
+    else rc = launch2<4, 1>(d, pl, st);
+    if (rc != 0 || nslice == 1) return rc;
+    return ppms_launch_slice_reduce(d, dev_desc, (const float*)workspace, nslice, stream);
+}
+
+// wm_hint: 0 = choose (all couts per workgroup when the grid still fills the chip, otherwise 64-cout blocks)
+extern "C" int ppms_conv_gemm2(const ppms_conv* d, const ppms_conv* dev_desc, int wm_hint, void* stream) {
+    return conv2_launch("conv_gemm2", d, dev_desc, wm_hint, 0, 1, nullptr, stream);
+}
+
+// K-sliced form for small maps
+extern "C" int ppms_conv_gemm2_sliced(const ppms_conv* d, const ppms_conv* dev_desc, int nslice, void* workspace, void* stream) {
+    return conv2_launch("conv_gemm2_sliced", d, dev_desc, 0, 0, nslice, workspace, stream);
+}
+
+// Convs with kh > 1 whose taps all step ONE halo'd window per (dt, chunk) (the plain entry loads a window per kernel row):
+// (kt, kh, 1) kernels are swept along y, weights packed with kh / kw swapped; kernels with kw > 1 too use a 2-D window, weights
+// packed with (ky, kx) flattened into x -- the sweep-ordered packs conv_gemm5 / conv_gemm6 use too.  nslice as in ppms_conv_gemm2_sliced.
+extern "C" int ppms_conv_gemm2_ysweep(const ppms_conv* d, const ppms_conv* dev_desc, int nslice, void* workspace, void* stream) {
+    PPMS_REQUIRE(d != nullptr && d->kh > 1, "conv_gemm2_ysweep: needs a kernel with kh > 1");
+    return conv2_launch("conv_gemm2_ysweep", d, dev_desc, 0, d->kw > 1 ? 2 : 1, nslice, workspace, stream);
 }

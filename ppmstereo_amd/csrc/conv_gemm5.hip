@@ -15,6 +15,7 @@
 // reduction (128 KiB) and the epilogue's transposition patches.
 #include "common.h"
 #include "conv_epilogue.h"
+#include "conv_check.h"
 #include <type_traits>
 
 namespace {
@@ -528,30 +529,14 @@ static bool plan5(const ppms_conv* d, Geo5& g, int force_nbt = 0, bool sliced = 
     g.nslice = 1;
     g.part = nullptr;
     g.P = (int64_t)d->T * d->H * d->W;
-    return g.npieces <= MAXS5 && nchunk % kgroups == 0;
+    return g.npieces >= 1 && g.npieces <= MAXS5 && nchunk % kgroups == 0 && g.nsweep >= 2;      // (a window must serve at least 2 k-steps)
 }
 
-}  // namespace
-
-// returns 1 when this kernel serves the convolution: M == 256 or 128 (all couts in one workgroup), a spatial sweep of >= 3 taps,
-// 16-channel-aligned segments, a halo'd window that fits, and at least ~a workgroup per CU
-// the packed window slots hold a pixel offset in 22 bits and a row index in 10 (conv5_launch checks the same)
-static bool conv5_volume_fits(const ppms_conv* d) { return (int64_t)d->T * d->H * d->W < (1ll << 22) && d->H < 480; }
-
-extern "C" int ppms_conv_gemm5_applicable(const ppms_conv* d) {
-    if (d == nullptr || (d->M != 256 && d->M != 192 && d->M != 128) || d->m_split % 64 != 0 || d->nseg < 1 || d->nseg > 2) return 0;
-    if (!conv5_volume_fits(d)) return 0;
-    for (int s = 0; s < d->nseg; ++s)
-        if (d->seg[s].c <= 0 || d->seg[s].c % 16 != 0) return 0;
-    Geo5 g;
-    if (!plan5(d, g)) return 0;                     // (kh = kw = 1: GEMM mode, segments in multiples of 64 / 32 channels)
-    if (d->M == 192 && (d->epi[0].out_vt != nullptr || (d->m_split < d->M && d->epi[1].out_vt != nullptr))) return 0;
-    return (int64_t)g.tiles_x * g.tiles_y * d->T >= ppms_num_cus() * 25 / 32 ? 1 : 0;   // (200 of 256) fewer workgroups than CUs: conv_gemm2's K slicing fills the chip better
-}
+constexpr ConvRules RULES5 = {"conv_gemm5", /*chunk*/ 16, /*M*/ 0, /*m_split*/ 64, /*kt, kh, kw <=*/ 0, 15, 15, /*grouped*/ false, /*out_vt*/ true, /*addf32*/ true, /*ld <=*/ 0};
 
 // smallest number of windows any (tile, K-group) pair of the launch sweeps: frames at the ends of the volume skip the temporal taps
 // that fall outside it
-static int min_windows5(const ppms_conv* d, const Geo5& g) {
+int min_windows5(const ppms_conv* d, const Geo5& g) {
     const int ht = d->kt >> 1;
     int kz_min = d->kt;
     for (int tf = 0; tf < d->T; ++tf) {
@@ -562,16 +547,43 @@ static int min_windows5(const ppms_conv* d, const Geo5& g) {
     return kz_min * (g.rdy ? d->kh : 1) * g.nchunk / g.kgroups;
 }
 
+size_t conv5_lds(const Geo5& g) {
+    size_t lds = (size_t)2 * g.kgroups * g.npieces * (NT5 / g.kgroups) * 16;        // the K-groups' pairs of window buffers (GEMM mode: 2 x 64 KiB)
+    if (g.kgroups == 2 && lds < (size_t)4 * 128 * 64 * 4) lds = (size_t)4 * 128 * 64 * 4;   // K-group exchange: 4 x 32 KiB
+    if (lds < (size_t)8 * STG_WAVE) lds = (size_t)8 * STG_WAVE;                  // the epilogue's transposition patches
+    return lds;
+}
+
+// What only this kernel limits, after the shared shape tier, and its geometry: the one path of the ratings and the launch.
+// nslice: 1 = the plain launch, 0 = the K-sliced form with a count still to choose (ppms_conv_gemm5_slices), > 1 = that count.
+bool serve5(const ppms_conv* d, Geo5& g, int nbt, int nslice) {
+    const bool sliced = nslice != 1;
+    // the packed window slots hold a pixel offset in 22 bits and a row index in 10
+    CONV_REFUSE_IF((int64_t)d->T * d->H * d->W >= (1ll << 22) || d->H >= 480, "conv_gemm5: volume %dx%dx%d too large for the packed window slots (< 2^22 pixels, H < 480)",
+                   d->T, d->H, d->W);
+    CONV_REFUSE_IF(d->M == 192 && sliced, "conv_gemm5: the 192-cout layout (M=192) has no K-sliced form");
+    CONV_REFUSE_IF((d->M == 192 || sliced) && conv_has_out_vt(d), "conv_gemm5: out_vt is written by neither the 192-cout layout nor a K-sliced launch");
+    CONV_REFUSE_IF(!plan5(d, g, nbt, sliced), "conv_gemm5: no tile shape fits the LDS window (segment channels c=%d in GEMM mode, or the halo'd window of kh=%d kw=%d)",
+                   d->seg[0].c, d->kh, d->kw);
+    CONV_REFUSE_IF(nslice > min_windows5(d, g), "conv_gemm5: nslice=%d for %d windows", nslice, min_windows5(d, g));
+    CONV_REFUSE_IF(conv5_lds(g) > 160 * 1024, "conv_gemm5: LDS budget exceeded (%zu B)", conv5_lds(g));
+    return true;
+}
+
+}  // namespace
+
+// 1 when this kernel serves the convolution and the map gives at least ~a workgroup per CU
+extern "C" int ppms_conv_gemm5_applicable(const ppms_conv* d) {
+    Geo5 g;
+    if (!conv_check_shape(RULES5, d) || !serve5(d, g, 0, 1)) return 0;
+    return (int64_t)g.tiles_x * g.tiles_y * d->T >= ppms_num_cus() * 25 / 32 ? 1 : 0;   // (200 of 256) fewer workgroups than CUs: conv_gemm2's K slicing fills the chip better
+}
+
 // Small maps (fewer tiles than CUs): how many grid-level K slices let this kernel fill the chip.  0: not applicable / not worth it.
 extern "C" int ppms_conv_gemm5_slices(const ppms_conv* d) {
-    if (d == nullptr || (d->M != 256 && d->M != 128) || d->m_split % 64 != 0 || d->nseg < 1 || d->nseg > 2) return 0;
-    if (d->kw == 1 && d->kh == 1) return 0;
-    if (!conv5_volume_fits(d)) return 0;
-    if (d->epi[0].out_vt != nullptr || (d->m_split < d->M && d->epi[1].out_vt != nullptr)) return 0;   // V^T is written from the accumulators
-    for (int s = 0; s < d->nseg; ++s)
-        if (d->seg[s].c <= 0 || d->seg[s].c % 16 != 0) return 0;
     Geo5 g;
-    if (!plan5(d, g, 0, true) || g.nsweep < 3) return 0;
+    if (!conv_check_shape(RULES5, d) || !serve5(d, g, 0, 0) || g.nsweep < 3) return 0;
+    if (d->kw == 1 && d->kh == 1) return 0;
     const int64_t tiles = (int64_t)g.tiles_x * g.tiles_y * d->T;
     const int cus = ppms_num_cus();
     if (tiles >= cus * 25 / 32 || tiles < 8) return 0;
@@ -605,56 +617,20 @@ extern "C" int ppms_conv_gemm5_sliced(const ppms_conv* d, const ppms_conv* dev_d
 }
 
 static int conv5_launch(const ppms_conv* d, const ppms_conv* dev_desc, int nbt, int nslice, float* part, void* stream) {
-    PPMS_REQUIRE(d != nullptr && dev_desc != nullptr, "conv_gemm5: null descriptor");
     PPMS_REQUIRE(nbt == 0 || nbt == 7 || nbt == 8, "conv_gemm5: nbt must be 0 (choose), 7 or 8");
-    PPMS_REQUIRE(d->nseg == 1 || d->nseg == 2, "conv_gemm5: nseg=%d", d->nseg);
-    PPMS_REQUIRE(d->groups <= 1, "conv_gemm5: a grouped convolution (groups=%d) is served by ppms_conv_gemm6 only", d->groups);
-    PPMS_REQUIRE(d->T > 0 && d->H > 0 && d->W > 0, "conv_gemm5: bad volume %dx%dx%d", d->T, d->H, d->W);
-    PPMS_REQUIRE((d->M == 256 || d->M == 192 || d->M == 128) && d->m_split % 64 == 0, "conv_gemm5: M=%d must be 128, 192 or 256", d->M);
-    PPMS_REQUIRE(d->M != 192 || nslice == 1, "conv_gemm5: the 192-cout layout has no K-sliced form");
-    PPMS_REQUIRE((d->kt & 1) && (d->kh & 1) && (d->kw & 1) && d->kw <= 15 && d->kh <= 15, "conv_gemm5: odd kernel extents <= 15");
-    PPMS_REQUIRE(d->w != nullptr && d->bias != nullptr, "conv_gemm5: weights/bias missing");
-    PPMS_REQUIRE(d->t_halo >= 0 && d->t_halo <= 8, "conv_gemm5: t_halo=%d", d->t_halo);
-    PPMS_REQUIRE(conv5_volume_fits(d), "conv_gemm5: volume too large for the packed window slots (< 2^22 pixels, H < 480)");
-    for (int s = 0; s < d->nseg; ++s) {
-        PPMS_REQUIRE(d->seg[s].hi && d->seg[s].lo && d->seg[s].c > 0 && d->seg[s].c % 16 == 0 && d->seg[s].ld % 8 == 0,
-                     "conv_gemm5: segment %d needs hi/lo planes, c %% 16 == 0 and ld %% 8 == 0", s);
-        PPMS_REQUIRE(((uintptr_t)d->seg[s].hi & 15) == 0 && ((uintptr_t)d->seg[s].lo & 15) == 0, "conv_gemm5: segment %d not 16-B aligned", s);
-    }
-    for (int hlf = 0; hlf < 2; ++hlf) {
-        const ppms_epilogue& e = d->epi[hlf];
-        if (hlf == 1 && d->m_split >= d->M) break;
-        PPMS_REQUIRE(e.n_valid > 0, "conv_gemm5: epilogue %d has n_valid=%d", hlf, e.n_valid);
-        PPMS_REQUIRE(e.pre_f32 == nullptr || (e.n_valid % 4 == 0 && e.pre_f32_ld % 4 == 0), "conv_gemm5: pre_f32 needs n_valid and pre_f32_ld to be multiples of 4");
-        {
-            const char* why = epilogue_row8_check(e);
-            PPMS_REQUIRE(why == nullptr, "conv_gemm5: epilogue %d: %s", hlf, why ? why : "");
-        }
-        if (e.out_sp.hi) PPMS_REQUIRE(e.out_sp.lo && e.out_sp.ld % 4 == 0, "conv_gemm5: epilogue %d SP output misaligned", hlf);
-        if (e.kind == PPMS_EPI_RESID || e.kind == PPMS_EPI_RH || e.kind == PPMS_EPI_GRU)
-            PPMS_REQUIRE(e.aux_sp.hi && e.aux_sp.lo && e.aux_sp.ld % 4 == 0, "conv_gemm5: epilogue %d needs aux_sp", hlf);
-        if (e.kind == PPMS_EPI_GRU) PPMS_REQUIRE(e.aux_f32 != nullptr, "conv_gemm5: GRU epilogue needs z");
-    }
     Geo5 g;
-    PPMS_REQUIRE(plan5(d, g, nbt, nslice > 1), "conv_gemm5: no tile shape fits the LDS window");
-    PPMS_REQUIRE(g.nsweep >= 2, "conv_gemm5: a window must serve at least 2 k-steps");
+    if (!conv_check_shape(RULES5, d) || !conv_check_operands(RULES5, d) || !serve5(d, g, nbt, nslice)) return PPMS_EINVAL;
+    PPMS_REQUIRE(dev_desc != nullptr, "conv_gemm5: null device descriptor");
     if (nslice > 1) {
-        PPMS_REQUIRE(d->epi[0].out_vt == nullptr && (d->m_split >= d->M || d->epi[1].out_vt == nullptr), "conv_gemm5: sliced launch cannot write out_vt");
-        PPMS_REQUIRE(nslice <= min_windows5(d, g), "conv_gemm5: %d slices for %d windows", nslice, min_windows5(d, g));
         g.nslice = nslice;
         g.part = part;
     }
-    PPMS_REQUIRE(g.npieces <= MAXS5 && g.npieces >= 1, "conv_gemm5: window of %d rows needs too many DMA pieces", g.Wr);
     const int ntiles = g.tiles_x * g.tiles_y * d->T;
-    size_t lds = (size_t)2 * g.kgroups * g.npieces * (NT5 / g.kgroups) * 16;        // the K-groups' pairs of window buffers (GEMM mode: 2 x 64 KiB)
-    if (g.kgroups == 2 && lds < (size_t)4 * 128 * 64 * 4) lds = (size_t)4 * 128 * 64 * 4;   // K-group exchange: 4 x 32 KiB
-    if (lds < (size_t)8 * STG_WAVE) lds = (size_t)8 * STG_WAVE;                  // the epilogue's transposition patches
-    PPMS_REQUIRE(lds <= 160 * 1024, "conv_gemm5: LDS budget exceeded (%zu B)", lds);
     static ppms_device_once once;
     once.run([] { (void)hipFuncSetAttribute((const void*)conv5_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
 #ifdef PPMS_CONV5_TIMING
     g.dbg = g_conv5_dbg;
 #endif
-    hipLaunchKernelGGL(conv5_kernel, dim3(ntiles, g.nslice), dim3(NT5), lds, (hipStream_t)stream, *d, g);
+    hipLaunchKernelGGL(conv5_kernel, dim3(ntiles, g.nslice), dim3(NT5), conv5_lds(g), (hipStream_t)stream, *d, g);
     return ppms_check_launch("conv_gemm5");
 }

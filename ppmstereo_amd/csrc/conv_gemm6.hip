@@ -20,6 +20,7 @@
 // Weights: pack_conv6 (ppmstereo_amd/packing.py): [k32-step][M/16][hi, lo][lane = 16 kg + r][8] = the MFMA A-operand images.
 #include "common.h"
 #include "conv_epilogue.h"
+#include "conv_check.h"
 #include <type_traits>
 
 namespace {
@@ -591,7 +592,6 @@ __global__ __launch_bounds__(NT6, 1) void conv6_kernel(const ppms_conv pv, const
 // window geometry for a descriptor; false when this kernel does not serve it
 static bool plan6(const ppms_conv* d, Geo6& g) {
     const bool grouped = d->groups == 2;
-    if (d->groups > 2 || d->groups < 0) return false;
     // two groups: segment s -> the couts of epilogue half s; served in the M = 256 layout for an x sweep of <= 5 taps (a 16 x 17 window: 9 pieces per group)
     if (grouped && !(d->nseg == 2 && d->seg[0].c == d->seg[1].c && d->M == 256 && d->m_split == 128 && d->kh == 1 && d->kw >= 3 && d->kw <= 5 && d->lo_zero_from == 0))
         return false;
@@ -600,10 +600,7 @@ static bool plan6(const ppms_conv* d, Geo6& g) {
     const int hx = (g.mode == 0 || g.mode == 2) ? d->kw - 1 : 0, hy = (g.mode == 1 || g.mode == 2) ? d->kh - 1 : 0;
     g.cpw = 32;
     int nchunk = 0;
-    for (int s = 0; s < d->nseg; ++s) {
-        if (d->seg[s].c <= 0 || d->seg[s].c % g.cpw) return false;
-        nchunk += d->seg[s].c / g.cpw;
-    }
+    for (int s = 0; s < d->nseg; ++s) nchunk += d->seg[s].c / g.cpw;
     if (grouped) nchunk = d->seg[0].c / g.cpw;           // the groups advance in lockstep: a window = one chunk of EACH segment
     g.nchunk = nchunk;
     g.n0 = grouped ? nchunk : d->seg[0].c / g.cpw;
@@ -650,7 +647,7 @@ static bool plan6(const ppms_conv* d, Geo6& g) {
     return (g.WH == 16 || g.WH == 18 || g.WH == 20) && g.npieces <= conv6_np(g.WH) && g.nsweep >= 2;
 }
 
-static bool conv6_volume_fits(const ppms_conv* d) { return (int64_t)d->T * d->H * d->W < (1ll << 22); }
+constexpr ConvRules RULES6 = {"conv_gemm6", /*chunk*/ 32, /*M*/ 0, /*m_split*/ 8, /*kt, kh, kw <=*/ 0, 5, 15, /*grouped*/ true, /*out_vt*/ false, /*addf32*/ true, /*ld <=*/ 1024};
 
 // a window's LDS-DMA addresses a lane's bytes as (the segment's hi plane + frame shift) + a 32-bit offset that also spans the distance to the lo plane:
 // both planes of a segment must lie inside one 4 GiB range above the hi plane (ppmstereo_amd's SPTensor keeps them in one allocation)
@@ -669,26 +666,30 @@ static size_t conv6_lds(const ppms_conv* d, const Geo6& g) {
     return lds < stg ? stg : lds;
 }
 
+// What only this kernel limits, after the shared shape tier, and its geometry: the one path of the rating and the launch.
+static bool serve6(const ppms_conv* d, Geo6& g) {
+    CONV_REFUSE_IF((int64_t)d->T * d->H * d->W >= (1ll << 22), "conv_gemm6: volume %dx%dx%d too large for the packed window slots (< 2^22 pixels)", d->T, d->H, d->W);
+    CONV_REFUSE_IF(!conv6_offsets_fit(d), "conv_gemm6: the lo plane of a segment must follow its hi plane inside one 4 GiB range (32-bit window offsets)");
+    CONV_REFUSE_IF(!plan6(d, g), "conv_gemm6: not a convolution this kernel serves (a halo'd 16 x 13 window of <= 14 DMA pieces per thread; groups=%d: two equal "
+                                 "segments, M = 256, m_split = 128, (1,1,3..5) taps)", d->groups);
+    CONV_REFUSE_IF(conv6_lds(d, g) > 160 * 1024, "conv_gemm6: LDS budget exceeded (%zu B)", conv6_lds(d, g));
+    return true;
+}
+
+template <int MB, int CR, bool STREAM = false, bool GRP = false, bool KS = false>
+static void launch6(const ppms_conv* d, const Geo6& g, hipStream_t st) {
+    static ppms_device_once once;                                        // one per template instantiation
+    once.run([] { (void)hipFuncSetAttribute((const void*)conv6_kernel<MB, CR, STREAM, GRP, KS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
+    hipLaunchKernelGGL((conv6_kernel<MB, CR, STREAM, GRP, KS>), dim3(g.tiles_x * g.tiles_y * d->T), dim3(NT6), conv6_lds(d, g), st, *d, g);
+}
+
 }  // namespace
 
 // 0: not served.  1: served, and the 208-pixel tiles fill the chip at least as well as conv_gemm5's 224- / 256-pixel tiles would (>= 85 % of the
 // CU-slots of the launch's rounds carry pixels).  2: served, but the fill is poor (the caller keeps conv_gemm5 there).
 extern "C" int ppms_conv_gemm6_applicable(const ppms_conv* d) {
-    if (d == nullptr || (d->M != 256 && d->M != 192 && d->M != 128) || d->nseg < 1 || d->nseg > 2) return 0;
-    if (d->m_split % 8 != 0 || !conv6_volume_fits(d)) return 0;
-    for (int s = 0; s < d->nseg; ++s)
-        if (d->seg[s].hi == nullptr || d->seg[s].lo == nullptr) return 0;
-    if (!conv6_offsets_fit(d)) return 0;
-    if (!(d->kt & 1) || !(d->kh & 1) || !(d->kw & 1)) return 0;
-    if (d->kw > 1 && d->kh > 1 && d->kh > 5) return 0;
-    if (d->kw > 15 || d->kh > 5) return 0;
-    for (int h = 0; h < 2; ++h) {
-        if (h == 1 && d->m_split >= d->M) break;
-        if (d->epi[h].out_vt != nullptr) return 0;                       // V^T is written from the accumulator layout: conv_gemm5 / gemm1
-    }
     Geo6 g;
-    if (!plan6(d, g)) return 0;
-    if (conv6_lds(d, g) > 160 * 1024) return 0;
+    if (!conv_check_shape(RULES6, d) || !serve6(d, g)) return 0;
     const int64_t tiles = (int64_t)g.tiles_x * g.tiles_y * d->T;
     const int64_t cus = ppms_num_cus();
     if (tiles < cus * 25 / 32) return 0;                                 // fewer workgroups than CUs: the K-sliced small-map kernels fill the chip better
@@ -701,72 +702,31 @@ extern "C" void ppms_debug_conv6_timing(long long* p) { g_conv6_dbg = p; }
 #endif
 
 extern "C" int ppms_conv_gemm6(const ppms_conv* d, const ppms_conv* dev_desc, void* stream) {
-    PPMS_REQUIRE(d != nullptr && dev_desc != nullptr, "conv_gemm6: null descriptor");
-    PPMS_REQUIRE(d->nseg == 1 || d->nseg == 2, "conv_gemm6: nseg=%d", d->nseg);
-    PPMS_REQUIRE(d->T > 0 && d->H > 0 && d->W > 0, "conv_gemm6: bad volume %dx%dx%d", d->T, d->H, d->W);
-    PPMS_REQUIRE((d->M == 256 || d->M == 192 || d->M == 128) && d->m_split % 8 == 0, "conv_gemm6: M=%d must be 128, 192 or 256 (m_split a multiple of 8)", d->M);
-    PPMS_REQUIRE((d->kt & 1) && (d->kh & 1) && (d->kw & 1) && d->kw <= 15 && d->kh <= 5, "conv_gemm6: odd kernel extents, kw <= 15, kh <= 5");
-    PPMS_REQUIRE(d->w != nullptr && d->bias != nullptr, "conv_gemm6: weights/bias missing");
-    PPMS_REQUIRE(d->t_halo >= 0 && d->t_halo <= 8, "conv_gemm6: t_halo=%d", d->t_halo);
-    PPMS_REQUIRE(conv6_volume_fits(d), "conv_gemm6: volume too large for the packed window slots (< 2^22 pixels)");
-    for (int s = 0; s < d->nseg; ++s) {
-        PPMS_REQUIRE(d->seg[s].hi && d->seg[s].lo && d->seg[s].c > 0 && d->seg[s].ld % 8 == 0 && d->seg[s].ld <= 1024,
-                     "conv_gemm6: segment %d needs hi/lo planes, ld %% 8 == 0 and ld <= 1024", s);
-        PPMS_REQUIRE(((uintptr_t)d->seg[s].hi & 15) == 0 && ((uintptr_t)d->seg[s].lo & 15) == 0, "conv_gemm6: segment %d not 16-B aligned", s);
-    }
-    for (int hlf = 0; hlf < 2; ++hlf) {
-        const ppms_epilogue& e = d->epi[hlf];
-        if (hlf == 1 && d->m_split >= d->M) break;
-        PPMS_REQUIRE(e.n_valid > 0, "conv_gemm6: epilogue %d has n_valid=%d", hlf, e.n_valid);
-        PPMS_REQUIRE(e.out_vt == nullptr, "conv_gemm6: no out_vt epilogue (use ppms_conv_gemm5 / ppms_gemm1)");
-        PPMS_REQUIRE(e.pre_f32 == nullptr || (e.n_valid % 4 == 0 && e.pre_f32_ld % 4 == 0), "conv_gemm6: pre_f32 needs n_valid and pre_f32_ld to be multiples of 4");
-        {
-            const char* why = epilogue_row8_check(e);
-            PPMS_REQUIRE(why == nullptr, "conv_gemm6: epilogue %d: %s", hlf, why ? why : "");
-        }
-        if (e.out_sp.hi) PPMS_REQUIRE(e.out_sp.lo && e.out_sp.ld % 4 == 0, "conv_gemm6: epilogue %d SP output misaligned", hlf);
-        if (e.kind == PPMS_EPI_RESID || e.kind == PPMS_EPI_RH || e.kind == PPMS_EPI_GRU)
-            PPMS_REQUIRE(e.aux_sp.hi && e.aux_sp.lo && e.aux_sp.ld % 4 == 0, "conv_gemm6: epilogue %d needs aux_sp", hlf);
-        if (e.kind == PPMS_EPI_GRU) PPMS_REQUIRE(e.aux_f32 != nullptr, "conv_gemm6: GRU epilogue needs z");
-    }
-    PPMS_REQUIRE(conv6_offsets_fit(d), "conv_gemm6: the lo plane of a segment must follow its hi plane inside one 4 GiB range (32-bit window offsets)");
     Geo6 g;
-    PPMS_REQUIRE(plan6(d, g), "conv_gemm6: not a convolution this kernel serves (segments in multiples of 32 channels, a halo'd 16 x 13 window of <= 14 DMA "
-                              "pieces per thread)");
-    const size_t lds = conv6_lds(d, g);
-    PPMS_REQUIRE(lds <= 160 * 1024, "conv_gemm6: LDS budget exceeded (%zu B)", lds);
-    const int ntiles = g.tiles_x * g.tiles_y * d->T;
-    PPMS_REQUIRE(g.WH == 16 || g.WH == 18 || g.WH == 20, "conv_gemm6: window columns of %d rows", g.WH);
-    static ppms_device_once once;
-    once.run([] {
-#define CONV6_ATTR(MBV, CRV) (void)hipFuncSetAttribute((const void*)conv6_kernel<MBV, CRV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        CONV6_ATTR(4, 16) CONV6_ATTR(4, 18) CONV6_ATTR(4, 20) CONV6_ATTR(3, 16) CONV6_ATTR(3, 18) CONV6_ATTR(3, 20)
-#undef CONV6_ATTR
-        (void)hipFuncSetAttribute((const void*)conv6_kernel<4, 16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv6_kernel<3, 16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv6_kernel<4, 16, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv6_kernel<4, 16, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv6_kernel<4, 18, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv6_kernel<4, 20, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    });
+    if (!conv_check_shape(RULES6, d) || !conv_check_operands(RULES6, d) || !serve6(d, g)) return PPMS_EINVAL;
+    PPMS_REQUIRE(dev_desc != nullptr, "conv_gemm6: null device descriptor");
 #ifdef PPMS_CONV6_TIMING
     g.dbg = g_conv6_dbg;
 #endif
-#define CONV6_GO(MBV, CRV) hipLaunchKernelGGL((conv6_kernel<MBV, CRV>), dim3(ntiles), dim3(NT6), lds, (hipStream_t)stream, *d, g)
-    if (d->groups == 2) {
-        hipLaunchKernelGGL((conv6_kernel<4, 16, false, true>), dim3(ntiles), dim3(NT6), lds, (hipStream_t)stream, *d, g);
-    } else if (g.ks) {
-        if (g.WH == 16) hipLaunchKernelGGL((conv6_kernel<4, 16, false, false, true>), dim3(ntiles), dim3(NT6), lds, (hipStream_t)stream, *d, g);
-        else if (g.WH == 18) hipLaunchKernelGGL((conv6_kernel<4, 18, false, false, true>), dim3(ntiles), dim3(NT6), lds, (hipStream_t)stream, *d, g);
-        else hipLaunchKernelGGL((conv6_kernel<4, 20, false, false, true>), dim3(ntiles), dim3(NT6), lds, (hipStream_t)stream, *d, g);
-    } else if (g.mode == 4) {
-        if (d->M == 192) hipLaunchKernelGGL((conv6_kernel<3, 16, true>), dim3(ntiles), dim3(NT6), lds, (hipStream_t)stream, *d, g);
-        else hipLaunchKernelGGL((conv6_kernel<4, 16, true>), dim3(ntiles), dim3(NT6), lds, (hipStream_t)stream, *d, g);
-    } else if (d->M == 192) {
-        if (g.WH == 16) CONV6_GO(3, 16); else if (g.WH == 18) CONV6_GO(3, 18); else CONV6_GO(3, 20);
+    hipStream_t st = (hipStream_t)stream;
+    // grouped, else K-split (M = 128), else the STREAM form (no spatial taps), else the plain layout by M and window height.  The branches
+    // stand in the order in which the twelve kernels have always been emitted into the code object, which keeps the device code bit-identical.
+    const bool grouped = d->groups == 2, plain = !grouped && !g.ks && g.mode != 4;
+    if (plain && d->M != 192) {
+        if (g.WH == 16) launch6<4, 16>(d, g, st); else if (g.WH == 18) launch6<4, 18>(d, g, st); else launch6<4, 20>(d, g, st);
+    } else if (plain) {
+        if (g.WH == 16) launch6<3, 16>(d, g, st); else if (g.WH == 18) launch6<3, 18>(d, g, st); else launch6<3, 20>(d, g, st);
+    } else if (!grouped && !g.ks) {
+        if (d->M != 192) launch6<4, 16, true>(d, g, st);
+        else launch6<3, 16, true>(d, g, st);
+    } else if (grouped) {
+        launch6<4, 16, false, true>(d, g, st);
+    } else if (g.WH == 16) {
+        launch6<4, 16, false, false, true>(d, g, st);
+    } else if (g.WH == 18) {
+        launch6<4, 18, false, false, true>(d, g, st);
     } else {
-        if (g.WH == 16) CONV6_GO(4, 16); else if (g.WH == 18) CONV6_GO(4, 18); else CONV6_GO(4, 20);
+        launch6<4, 20, false, false, true>(d, g, st);
     }
-#undef CONV6_GO
     return ppms_check_launch("conv_gemm6");
 }

@@ -20,6 +20,7 @@
 // No slices, no workspace, no reduce launch; the chip is filled by tiles x cout blocks (3 200 pixels x 256 couts = 400 workgroups).
 #include "common.h"
 #include "conv_epilogue.h"
+#include "conv_check.h"
 #include <type_traits>
 
 namespace {
@@ -252,31 +253,17 @@ struct Plan7 {
     Geo7 g;
 };
 
+constexpr ConvRules RULES7 = {"conv_stream", /*chunk*/ 16, /*M*/ 64, /*m_split*/ 64, /*kt, kh, kw <=*/ 0, 0, 0, /*grouped*/ false, /*out_vt*/ false, /*addf32*/ false, /*ld <=*/ 0};
+
+// What only this kernel limits, after the shared tiers, and its launch shape (the one path of the rating and the launch).
 bool plan7(const ppms_conv* d, Plan7& pl, int hint) {
-    if (d == nullptr || d->nseg < 1 || d->nseg > 2 || d->w == nullptr || d->bias == nullptr || d->groups > 1) return false;      // (grouped: conv_gemm6 only)
-    if (d->kt < 1 || d->kh < 1 || d->kw < 1 || !(d->kt & 1) || !(d->kh & 1) || !(d->kw & 1)) return false;
-    if (d->T <= 0 || d->H <= 0 || d->W <= 0 || d->t_halo < 0) return false;
-    if (d->M <= 0 || d->M % 64 != 0) return false;
     int K = 0;
-    for (int s = 0; s < d->nseg; ++s) {
-        if (d->seg[s].hi == nullptr || d->seg[s].lo == nullptr || d->seg[s].c <= 0 || d->seg[s].c % 16 != 0 || d->seg[s].ld % 8 != 0) return false;
-        if (((uintptr_t)d->seg[s].hi & 15) || ((uintptr_t)d->seg[s].lo & 15)) return false;
-        K += d->seg[s].c;
-    }
-    if (K % 64 != 0) return false;                       // every tap's chunks are dealt to the four waves in equal shares
+    for (int s = 0; s < d->nseg; ++s) K += d->seg[s].c;
+    CONV_REFUSE_IF(K % 64 != 0, "conv_stream: K=%d input channels must be a multiple of 64", K);      // every tap's chunks are dealt to the four waves in equal shares
     const int64_t P = (int64_t)d->T * d->H * d->W;
-    if (P >= (1ll << 31) / 8) return false;              // (pixel offsets incl. temporal halos stay in 32 bits)
+    CONV_REFUSE_IF(P >= (1ll << 31) / 8, "conv_stream: volume %dx%dx%d too large for 32-bit pixel offsets", d->T, d->H, d->W);      // (incl. the temporal halos)
     const int64_t taps = (int64_t)d->kt * d->kh * d->kw;
-    if (taps * (K / 16) >= (1 << 20)) return false;
-    const bool two = d->m_split < d->M;
-    if (two && d->m_split % 64 != 0) return false;
-    for (int hlf = 0; hlf < 2; ++hlf) {
-        const ppms_epilogue& e = d->epi[hlf];
-        if (hlf == 1 && !two) break;
-        if (e.n_valid <= 0) return false;
-        if (epilogue_row8_check(e) != nullptr) return false;
-        if (e.kind == PPMS_EPI_ADDF32 || e.out_vt != nullptr) return false;
-    }
+    CONV_REFUSE_IF(taps * (K / 16) >= (1 << 20), "conv_stream: %lld taps x K=%d: too many k-steps", (long long)taps, K);
     Geo7& g = pl.g;
     g.P = P;
     g.nk16 = K / 16;
@@ -316,7 +303,7 @@ int launch7(const ppms_conv* d, const Plan7& pl, hipStream_t st) {
 // against 156 and 74 against 101 at 18 400) up to 32 768 pixels, and 64-cout convs (16 against 24 us) up to 16 384.
 extern "C" int ppms_conv_stream_applicable(const ppms_conv* d) {
     Plan7 pl;
-    if (!plan7(d, pl, 0)) return 0;
+    if (!conv_check_shape(RULES7, d) || !conv_check_operands(RULES7, d) || !plan7(d, pl, 0)) return 0;
     const int64_t K = (int64_t)pl.g.nsteps * 16;
     const bool spatial = d->kh > 1 || d->kw > 1;
     if (pl.g.P <= 4096) return (double)pl.g.P * (double)K * d->M <= 4.0e9 ? 1 : 2;       // (3 200 pixels: K x M <= 1.25 M)
@@ -330,8 +317,7 @@ extern "C" int ppms_conv_stream(const ppms_conv* d, const ppms_conv* dev_desc, i
     (void)dev_desc;
     Plan7 pl;
     PPMS_REQUIRE(hint >= 0 && hint <= 2, "conv_stream: hint must be 0 (choose), 1 or 2 (32-pixel blocks per tile)");
-    PPMS_REQUIRE(plan7(d, pl, hint), "conv_stream: not a convolution this kernel serves (odd taps, input channels a multiple of 64 in 16-channel-aligned "
-                                     "segments, M %% 64 == 0, pack_stream weights, aligned SP operands, no out_vt / ADDF32 epilogue; ppms_conv_stream_applicable tells)");
+    if (!conv_check_shape(RULES7, d) || !conv_check_operands(RULES7, d) || !plan7(d, pl, hint)) return PPMS_EINVAL;
     hipStream_t st = (hipStream_t)stream;
 #define S7_CASE(PBV, DV, KGV) \
     if (pl.pb == PBV && pl.depth == DV && pl.kg == KGV) return launch7<2, PBV, DV, KGV>(d, pl, st);

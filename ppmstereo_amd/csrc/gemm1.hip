@@ -15,6 +15,7 @@
 // No operand LDS, no K loop barrier, no slices, no reduce launch.
 #include "common.h"
 #include "conv_epilogue.h"
+#include "conv_check.h"
 #include <type_traits>
 
 namespace {
@@ -168,29 +169,21 @@ struct Plan1 {
     int cb, ns, nk;
 };
 
+constexpr ConvRules RULES1 = {"gemm1", /*chunk*/ 16, /*M*/ 32, /*m_split*/ 32, /*kt, kh, kw <=*/ 1, 1, 1, /*grouped*/ false, /*out_vt*/ true, /*addf32*/ false, /*ld <=*/ 0};
+
+// What only this kernel limits, after the shared tiers, and its launch shape (the one path of the rating and the launch).
 // K = 64 NS with NS in {2, 3, 4, 6, 8}; CB (32-cout blocks per workgroup): 2 when that divides the cout blocks and keeps a workgroup inside
 // one epilogue half, else 1 (measured at config 2's sizes, tools/gemm1_probe.py: 2 is best or tied everywhere, 4 gains nothing).
 bool plan1(const ppms_conv* d, Plan1& pl, int cb_hint = 0) {
-    if (d == nullptr || d->kt != 1 || d->kh != 1 || d->kw != 1 || d->nseg < 1 || d->nseg > 2 || d->groups > 1) return false;      // (grouped: conv_gemm6 only)
-    if (d->M <= 0 || d->M % 32 != 0 || d->w == nullptr || d->bias == nullptr) return false;
     int K = 0;
-    for (int s = 0; s < d->nseg; ++s) {
-        if (d->seg[s].hi == nullptr || d->seg[s].lo == nullptr || d->seg[s].c <= 0 || d->seg[s].c % 16 != 0 || d->seg[s].ld % 8 != 0) return false;
-        if (((uintptr_t)d->seg[s].hi & 15) || ((uintptr_t)d->seg[s].lo & 15)) return false;
-        K += d->seg[s].c;
-    }
-    if (K % 64 != 0) return false;
+    for (int s = 0; s < d->nseg; ++s) K += d->seg[s].c;
     const int ns = K / 64;
     // (K = 768, i.e. 12 steps per wave, was built and measured: 48 operand requests per lane cost the occupancy that hides them -- the
     // 768 -> 768 Linear of update_block16 took 48 us against 45 us for the K-sliced implicit GEMM + reduce -- so such layers stay there)
-    if (ns != 2 && ns != 3 && ns != 4 && ns != 6 && ns != 8) return false;
-    const bool two = d->m_split < d->M;
-    if (two && d->m_split % 32 != 0) return false;
-    const int64_t P = (int64_t)d->T * d->H * d->W;
-    if (P <= 0 || P >= (1ll << 31)) return false;
-    const int64_t tiles = (P + 31) / 32;
+    CONV_REFUSE_IF(K % 64 != 0 || (ns != 2 && ns != 3 && ns != 4 && ns != 6 && ns != 8), "gemm1: K=%d input channels (128, 192, 256, 384 or 512)", K);
+    CONV_REFUSE_IF((int64_t)d->T * d->H * d->W >= (1ll << 31), "gemm1: volume %dx%dx%d too large for 32-bit pixel indices", d->T, d->H, d->W);
+    const bool two = conv_halves(d) == 2;
     const int mblocks = d->M / 32;
-    (void)tiles;
     int best = 0;
     for (int cb = (cb_hint > 0 ? cb_hint : 2); cb >= 1; cb >>= 1) {
         if (mblocks % cb || cb * ns > 16) continue;
@@ -198,14 +191,7 @@ bool plan1(const ppms_conv* d, Plan1& pl, int cb_hint = 0) {
         best = cb;
         break;
     }
-    if (best == 0) return false;
-    for (int hlf = 0; hlf < 2; ++hlf) {
-        const ppms_epilogue& e = d->epi[hlf];
-        if (hlf == 1 && !two) break;
-        if (e.n_valid <= 0) return false;
-        if (epilogue_row8_check(e) != nullptr) return false;
-        if (e.kind == PPMS_EPI_ADDF32) return false;
-    }
+    CONV_REFUSE_IF(best == 0, "gemm1: no cout blocking for M=%d m_split=%d K=%d", d->M, d->m_split, K);
     pl.cb = best;
     pl.ns = ns;
     pl.nk = K / 16;
@@ -231,7 +217,7 @@ int launch1(const ppms_conv* d, const Plan1& pl, hipStream_t st) {
 // 256 -> 54: 21 against 37 us) and loses on wide ones (256 -> 144: 46 against 42 us).  2: it serves it but the implicit GEMM is as fast.
 extern "C" int ppms_gemm1_applicable(const ppms_conv* d) {
     Plan1 pl;
-    if (!plan1(d, pl)) return 0;
+    if (!conv_check_shape(RULES1, d) || !conv_check_operands(RULES1, d) || !plan1(d, pl)) return 0;
     const int64_t P = (int64_t)d->T * d->H * d->W;
     return (P <= 16384 || d->M <= 64) ? 1 : 2;
 }
@@ -240,8 +226,7 @@ extern "C" int ppms_gemm1(const ppms_conv* d, const ppms_conv* dev_desc, int cb_
     (void)dev_desc;
     Plan1 pl;
     PPMS_REQUIRE(cb_hint == 0 || cb_hint == 1 || cb_hint == 2 || cb_hint == 4, "gemm1: cb_hint must be 0 (choose), 1, 2 or 4");
-    PPMS_REQUIRE(plan1(d, pl, cb_hint), "gemm1: not a 1x1 convolution this kernel serves (K = 128 / 192 / 256 / 384 / 512 in 16-channel-aligned segments, M %% 32 == 0, "
-                               "pack_gemm1 weights, aligned SP operands; ppms_gemm1_applicable tells)");
+    if (!conv_check_shape(RULES1, d) || !conv_check_operands(RULES1, d) || !plan1(d, pl, cb_hint)) return PPMS_EINVAL;
     hipStream_t st = (hipStream_t)stream;
 #define G1_CASE(CBV, NSV) \
     if (pl.cb == CBV && pl.ns == NSV) return launch1<CBV, NSV>(d, pl, st);
