@@ -320,6 +320,18 @@ int ppms_mem_attn(const void* qb, const void* kb, const void* vt, const int32_t*
  * many (5 = all picked frames in one workgroup: one partial set per clip; a per-call argument: the library keeps no mutable state).  The
  * same softmax either way (different summation order). */
 int64_t ppms_mem_attn_workspace_bytes(int T, int ksel, int n);
+/* The number of frame splits (partial sets per clip) ppms_mem_attn uses for these arguments when it is given a workspace: the launch's own
+ * planner, evaluated without launching.  frames_per_workgroup 1 .. 5: ceil(ksel / frames_per_workgroup); 0: the library's choice on the
+ * current device.  0 when the 64-query kernel does not serve the geometry (n % 64 != 0: no redo flags are written); PPMS_EINVAL on
+ * arguments ppms_mem_attn refuses. */
+int ppms_mem_attn_splits(int T, int ksel, int n, int frames_per_workgroup);
+/* Fix-up accounting of the 64-query kernel, counted on the device: enqueued on `stream` behind a ppms_mem_attn call that used the same
+ * split_ws, T, ksel, n and frames_per_workgroup, it reads the T * nsp * ceil(n / 256) redo flag pairs that call wrote (nsp =
+ * ppms_mem_attn_splits; one pair per (clip, split, 256-query block) tile) -- no other byte of the workspace, and it writes none -- and adds
+ * to counters (caller-owned device memory, int64 [3], zeroed by the caller): {calls += 1, tiles += T * nsp * ceil(n / 256), flagged +=
+ * tiles the fix-up pass recomputed}.  One small launch; no allocation, no host synchronisation: the caller reads the counters when it
+ * synchronises anyway.  Returns 0 without launching when ppms_mem_attn_splits is 0. */
+int ppms_attn_redo_accumulate(const void* split_ws, int T, int ksel, int n, int frames_per_workgroup, int64_t* counters, void* stream);
 
 /* Fused chain of up to three per-pixel (1x1, <= 64 input channels) layers with GELU, optional residual from the chain
  * input and optional depthwise-1x1 post step: the ffn1 / pw / ffn2 parts of PCBlock4_Deep_nopool_res

@@ -647,11 +647,52 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(const float* __restri
     *(bf16x8*)((bf16_t*)mfg.lo + pix * mfg.ld + d) = ol;
 }
 
+// diagnostics behind a ppms_mem_attn call (ppms_attn_redo_accumulate): counts the redo flag pairs mem_attn64_kernel wrote -- `entries` =
+// T * nsplit * gridDim.x of them, [clip][split][256-query block][2], both words of a pair carry the tile's flag -- and adds
+// {1, entries, flagged} to the caller's three counters.  One workgroup (the table has a few thousand entries at most): wave reduction,
+// LDS across the four waves, one atomic add per counter.  Reads the flags only.
+__global__ __launch_bounds__(256) void attn_redo_count_kernel(const int32_t* __restrict__ redo, int entries, unsigned long long* __restrict__ counters) {
+    __shared__ int part[NW];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int cnt = 0;
+    for (int i = tid; i < entries; i += 256) cnt += ((redo[2 * i] | redo[2 * i + 1]) != 0) ? 1 : 0;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
+    if (lane == 0) part[wave] = cnt;
+    __syncthreads();
+    if (tid == 0) {
+        atomicAdd(counters + 0, 1ull);
+        atomicAdd(counters + 1, (unsigned long long)entries);
+        atomicAdd(counters + 2, (unsigned long long)(part[0] + part[1] + part[2] + part[3]));
+    }
+}
+
 }  // namespace
 
 #ifdef PPMS_ATTN_TIMING
 extern "C" void ppms_debug_attn_timing(long long* p) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_attn_dbg_dev), &p, sizeof(p)); }   // tools/attn_phase_probe.py
 #endif
+// The 64-query kernel's plan for one call: does it serve the geometry (a workspace is given and n % 64 == 0), how many picked frames a
+// workgroup streams (sps) and how many partial sets / frame splits per clip that makes (nsp).  The launch, ppms_mem_attn_splits and
+// ppms_attn_redo_accumulate all read it here.
+struct attn64_plan {
+    bool use64;
+    int g64, sps, nsp;
+};
+static attn64_plan plan_attn64(int T, int ksel, int n, bool have_ws, int frames_per_workgroup) {
+    attn64_plan p = {have_ws && n % KT == 0, (int)ceil_div(n, 64 * NW), 1, ksel};
+    if (p.use64) {
+        // two picked frames per workgroup where the one-frame grid is at least two rounds of the chip (the 1/4 scale: 1000 workgroups)
+        p.sps = frames_per_workgroup ? frames_per_workgroup : ((p.g64 * T * ksel >= 2 * ppms_num_cus() && ksel > 1) ? 2 : 1);
+        p.nsp = (int)ceil_div(ksel, p.sps);
+    }
+    return p;
+}
+// the redo flags of the 64-query kernel sit behind the partials (ppms_mem_attn_workspace_bytes)
+static const int32_t* attn64_redo_flags(const void* split_ws, int T, int ksel, int n) {
+    return (const int32_t*)((const float*)split_ws + (size_t)T * ksel * n * (D + 2));
+}
+
 template <bool P16>
 static void launch_mem_attn(const void* qb, const void* kb, const void* vt, const int32_t* sel, int ksel, float scale_log2, const float* beta, ppms_sp mf,
                             ppms_sp mfg, void* out_bf16, int T, int n, void* split_ws, int frames_per_workgroup, hipStream_t st) {
@@ -662,17 +703,15 @@ static void launch_mem_attn(const void* qb, const void* kb, const void* vt, cons
         (void)hipFuncSetAttribute((const void*)mem_attn64_kernel<P16>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT_NS * ATT_STAGE);
     });
     // split over the picked frames when a workspace is given (ppms_mem_attn_workspace_bytes) and there is more than one
-    const bool use64 = split_ws != nullptr && n % KT == 0;      // (its state lives in the workspace partials)
+    const attn64_plan pl = plan_attn64(T, ksel, n, split_ws != nullptr, frames_per_workgroup);
+    const bool use64 = pl.use64;                                // (its state lives in the workspace partials)
     const bool split = use64 || (split_ws != nullptr && ksel > 1);
     float* part_o = split ? (float*)split_ws : nullptr;
     float* part_ml = split ? part_o + (size_t)T * ksel * n * D : nullptr;
-    int nsp = ksel;                                             // partial sets per clip
+    const int nsp = pl.nsp;                                     // partial sets per clip
     if (use64) {
-        const int g64 = (int)ceil_div(n, 64 * NW);
-        int32_t* redo = (int32_t*)(part_ml + (size_t)T * ksel * n * 2);
-        // two picked frames per workgroup where the one-frame grid is at least two rounds of the chip (the 1/4 scale: 1000 workgroups)
-        const int sps = frames_per_workgroup ? frames_per_workgroup : ((g64 * T * ksel >= 2 * ppms_num_cus() && ksel > 1) ? 2 : 1);
-        nsp = (int)ceil_div(ksel, sps);
+        const int g64 = pl.g64, sps = pl.sps;
+        int32_t* redo = const_cast<int32_t*>(attn64_redo_flags(split_ws, T, ksel, n));
         dim3 grid64(g64, T, nsp), grid32(ceil_div(n, QW * NW), T, nsp);
         hipLaunchKernelGGL(mem_attn64_kernel<P16>, grid64, dim3(256), ATT_NS * ATT_STAGE, st, (const bf16_t*)qb, (const bf16_t*)kb, (const bf16_t*)vt,
                            sel, ksel, scale_log2, n, part_o, part_ml, redo, sps);
@@ -713,4 +752,22 @@ extern "C" int ppms_mem_attn(const void* qb, const void* kb, const void* vt, con
 // partial O (T*ksel*n*128 fp32) + partial (m, l) (T*ksel*n*2 fp32) + redo flags of the 64-query kernel (2 per 256-query block)
 extern "C" int64_t ppms_mem_attn_workspace_bytes(int T, int ksel, int n) {
     return (int64_t)T * ksel * n * (D + 2) * 4 + (int64_t)T * ksel * ceil_div(n, 64 * NW) * 2 * 4;
+}
+
+extern "C" int ppms_mem_attn_splits(int T, int ksel, int n, int frames_per_workgroup) {
+    PPMS_REQUIRE(ksel >= 1 && ksel <= 5 && T >= 1 && n >= 1, "mem_attn_splits: bad sizes ksel=%d T=%d n=%d", ksel, T, n);
+    PPMS_REQUIRE(frames_per_workgroup >= 0 && frames_per_workgroup <= 5, "mem_attn_splits: frames_per_workgroup must be 0 (automatic) or 1 .. 5, got %d", frames_per_workgroup);
+    const attn64_plan pl = plan_attn64(T, ksel, n, true, frames_per_workgroup);
+    return pl.use64 ? pl.nsp : 0;
+}
+
+extern "C" int ppms_attn_redo_accumulate(const void* split_ws, int T, int ksel, int n, int frames_per_workgroup, int64_t* counters, void* stream) {
+    PPMS_REQUIRE(split_ws && counters, "attn_redo_accumulate: null workspace or counters");
+    PPMS_REQUIRE(ksel >= 1 && ksel <= 5 && T >= 1 && n >= 1, "attn_redo_accumulate: bad sizes ksel=%d T=%d n=%d", ksel, T, n);
+    PPMS_REQUIRE(frames_per_workgroup >= 0 && frames_per_workgroup <= 5, "attn_redo_accumulate: frames_per_workgroup must be 0 (automatic) or 1 .. 5, got %d", frames_per_workgroup);
+    const attn64_plan pl = plan_attn64(T, ksel, n, true, frames_per_workgroup);
+    if (!pl.use64) return 0;                                    // the 32-query kernel ran: no flags were written, nothing is counted
+    hipLaunchKernelGGL(attn_redo_count_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, attn64_redo_flags(split_ws, T, ksel, n), T * pl.nsp * pl.g64,
+                       (unsigned long long*)counters);
+    return ppms_check_launch("attn_redo_accumulate");
 }

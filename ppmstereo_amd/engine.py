@@ -227,6 +227,7 @@ class ScaleEngine:
         self.have_mhs = False
         self.lib = L.load()
         self._ev, self._ev_i = None, 0
+        self._health, self._health_on = None, False      # enable_attn_health(): int64 [3] device counters {calls, tiles, flagged}
         self._xa_halo = None        # handle of x's +-2-frame halo while it is in flight (sharded window)
         self._x_hid = False         # True: X[256:384] holds the attention read-out hid (attend()), not mfg = mf + beta hid (set_mfg())
         # independent branches of an iteration (flow encoder || correlation encoder, r-gate || z-gate, mask head || flow
@@ -548,6 +549,8 @@ class ScaleEngine:
         L.check(self.lib.ppms_mem_attn(self.QB.data_ptr(), self.KB.data_ptr(), self.VTG.data_ptr(), sel, self.ksel, self.scale,
                                        self.pk.beta.data_ptr(), mf_in, self.X.view(256, 128), L.ptr(out_bf16), self.T, self.n,
                                        self.ATT_WS.data_ptr(), 0, self.attn_p, s))
+        if self._health_on:                                           # same stream, same arguments: counts the flags that call just wrote
+            L.check(self.lib.ppms_attn_redo_accumulate(self.ATT_WS.data_ptr(), self.T, self.ksel, self.n, 0, self._health.data_ptr(), s))
         self._x_hid = self.hid_mode
         if ev is not None:
             ev[1].record()
@@ -571,7 +574,8 @@ class ScaleEngine:
     def attn_redo_count(self):
         """(tiles, flagged): how many (clip, split, 256-query block) tiles the LAST mem_attn call of this engine ran on the 64-query kernel and how
         many of them that kernel handed to its fix-up pass (a score more than 2^16 -- fp16 P~ -- or 2^60 -- bf16 -- above the query's softmax
-        reference).  Diagnostics (tools/parity_ab.py, bench.py); synchronises.  (0, 0) when the 64-query kernel does not serve this geometry."""
+        reference).  Diagnostics (tools/parity_ab.py, bench.py); synchronises.  (0, 0) when the 64-query kernel does not serve this geometry.
+        For exact counts over every call, taken on the device, see enable_attn_health() / attn_health()."""
         if self.n % 64:
             return 0, 0
         flags = self.ATT_WS.view(torch.int32)[self.T * self.ksel * self.n * 130:]
@@ -580,6 +584,37 @@ class ScaleEngine:
         f = flags[:used * 2:2]
         torch.cuda.synchronize()
         return int(used), int((f != 0).sum().item())
+
+    def enable_attn_health(self, on: bool = True):
+        """Fix-up accounting of the memory read-out, counted on the device: while on, every attend() enqueues ppms_attn_redo_accumulate behind
+        its ppms_mem_attn call (one small launch, no synchronisation), which adds to three int64 counters of this engine -- of this rank,
+        for a sharded engine.  Off by default: the launches of an iteration are then exactly those without this method.  The counters are
+        allocated (zeroed) on the first call and kept across on / off; read them with attn_health(), zero them with reset_attn_health()."""
+        if on and self._health is None:
+            self._health = torch.zeros(3, dtype=torch.int64, device=self.dev)
+        self._health_on = bool(on)
+
+    def attn_health(self) -> Dict[str, int]:
+        """{"calls", "tiles", "flagged"} since enable_attn_health() / the last reset_attn_health(): mem_attn calls counted, the (clip, split,
+        256-query block) tiles the 64-query kernel ran in them, and how many of those it handed to its fix-up pass (a score more than 2^16
+        -- fp16 P~ -- or 2^60 -- bf16 -- above the query's softmax reference: attention time moving onto the slower 32-query kernel).  All
+        zero where the 64-query kernel does not serve the geometry (n % 64 != 0).  The one call here that synchronises: the current stream
+        of the engine's device, nothing else."""
+        if self._health is None:
+            return {"calls": 0, "tiles": 0, "flagged": 0}
+        torch.cuda.current_stream(self.dev).synchronize()
+        calls, tiles, flagged = self._health.tolist()
+        return {"calls": calls, "tiles": tiles, "flagged": flagged}
+
+    def attn_health_snapshot(self) -> torch.Tensor:
+        """Device copy of the three counters {calls, tiles, flagged}, taken on the current stream (no synchronisation): for a caller that
+        reads them at a later synchronisation point of its own (ClipPipeline.wait)."""
+        return self._health.clone()
+
+    def reset_attn_health(self):
+        """Zeroes the counters on the current stream (ordered with the attend() calls around it; no synchronisation)."""
+        if self._health is not None:
+            self._health.zero_()
 
     def enable_attn_timing(self, launches: int):
         """HIP events (on the stream the kernel is launched on) around the next `launches` mem_attn launches."""

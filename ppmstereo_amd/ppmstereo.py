@@ -64,6 +64,15 @@ def _run_iterations(eng, iters: int, isc: int, t: int, h: int, w: int, predictio
     return flow_out
 
 
+def _add_attn_redo(diagnostics: dict, per_scale: Dict[str, Dict[str, int]]):
+    """diagnostics["attn_redo"][scale][counter] += per_scale[scale][counter] (entries already present are kept: a caller sums over windows)."""
+    total = diagnostics.setdefault("attn_redo", {})
+    for tag, counters in per_scale.items():
+        entry = total.setdefault(tag, {"calls": 0, "tiles": 0, "flagged": 0})
+        for k, v in counters.items():
+            entry[k] += int(v)
+
+
 def convex_upsample_3d(flow: torch.Tensor, mask: torch.Tensor, rate: int, T: int) -> torch.Tensor:
     """PPMStereo.convex_upsample_3d, ppmstereo.py:199-228 (NCHW in, NCHW out; one window of T frames, batch 1)."""
     if rate != 4:
@@ -189,6 +198,7 @@ class ClipPipeline:
         self.record_done = False
 
         self._results: List[torch.Tensor] = []                # tensors handed out by cascade() since the last wait()
+        self._health: List[tuple] = []                        # (completion event, diagnostics dict, {scale: device snapshot of the attention counters}) per clip
 
     def wait(self, handle: Optional[torch.cuda.Event] = None):
         """Orders the current stream behind the clips enqueued so far AND tells the caching allocator that the tensors ``cascade`` returned
@@ -201,6 +211,25 @@ class ClipPipeline:
         for t in self._results:
             t.record_stream(cur)
         self._results.clear()
+        self._read_health(handle, cur)
+
+    def _read_health(self, handle, cur):
+        """cascade(diagnostics=...) left device snapshots of the engines' attention counters for every clip enqueued: those of the clips the
+        current stream has now waited for (all, or up to ``handle``'s) are read here -- the host waits for the current stream, which the caller
+        of wait() is about to do for the results anyway -- and added to their dicts."""
+        n = len(self._health) if handle is None else next((i + 1 for i, item in enumerate(self._health) if item[0] is handle), 0)
+        done, self._health = self._health[:n], self._health[n:]
+        if not done:
+            return
+        with torch.cuda.device(self.device), torch.cuda.stream(cur):
+            for _, _, snaps in done:
+                for s in snaps.values():
+                    s.record_stream(cur)
+            table = torch.stack([s for _, _, snaps in done for s in snaps.values()])
+            cur.synchronize()
+            rows = iter(table.tolist())
+        for _, diagnostics, snaps in done:
+            _add_attn_redo(diagnostics, {tag: dict(zip(("calls", "tiles", "flagged"), next(rows))) for tag in snaps})
 
 
 class PPMStereoHotPath(nn.Module):
@@ -248,13 +277,19 @@ class PPMStereoHotPath(nn.Module):
 
     @torch.no_grad()
     def cascade(self, feats: Dict[str, torch.Tensor], iters: int, t: int, predictions: Optional[list] = None,
-                uncertainties: Optional[list] = None, shard=None, test_mode: bool = False, pipeline: Optional[ClipPipeline] = None):
+                uncertainties: Optional[list] = None, shard=None, test_mode: bool = False, pipeline: Optional[ClipPipeline] = None,
+                diagnostics: Optional[dict] = None):
         """The 1/16 -> 1/8 -> 1/4 cascade of PPMStereo.forward (ppmstereo.py:696-804), device resident: the state handed from
         scale to scale (hidden state, motion hidden state) stays in the engines' SP buffers (ppms_sp_resize_blend), only the
         2-channel flow passes through an NCHW resize.  feats: f1_s, f2_s, net_s, inp_s for s in (16, 8, 4) on the GPU
         (with ``shard``: this rank's frames only).  test_mode: only the final prediction is produced (ppmstereo.py:801-804).
         pipeline: a ``ClipPipeline`` -- the small scales and the 1/4 scale are enqueued on its two streams so that consecutive clips
         overlap (same results; see the class).
+        diagnostics: a dict -- the fix-up accounting of the memory read-out (ScaleEngine.enable_attn_health) is switched on for this call on
+        the three engines, their counters are zeroed at the start, and on return ``diagnostics["attn_redo"]`` holds {"1/16": {"calls",
+        "tiles", "flagged"}, "1/8": ..., "1/4": ...}, ADDED to entries already there (one dict over several windows sums them; with
+        ``shard``: this rank's clips).  One extra small launch per iteration and one host synchronisation at the end of the call; with a
+        ``pipeline`` there is none here: the counters are read in ``ClipPipeline.wait()``.  None (default): nothing is launched or read.
         Returns (flow_up (T,1,H,W), uncertainty (T,1,H,W)) = predictions[-1], uncertainties[-1]."""
         if iters < 2:
             raise ValueError(f"cascade: iters={iters}; the 1/16 and 1/8 scales run iters // 2 iterations each (ppmstereo.py:708,744) and need at least one")
@@ -265,6 +300,8 @@ class PPMStereoHotPath(nn.Module):
         if shard is None and tl != t:
             if tl % t or pipeline is not None:
                 raise RuntimeError(f"cascade: {tl} frames do not divide into clips of t = {t} (or a pipeline was given for a batch)")
+            if diagnostics is not None:
+                raise NotImplementedError("cascade: diagnostics are collected for one clip per call (b = 1)")
             return self._cascade_batched(feats, iters, t, preds, uncs)
         if t == 1:
             warnings.warn("PPMStereo with a single frame produces NaN disparities (reference behaviour, T must be >= 2)")
@@ -276,6 +313,7 @@ class PPMStereoHotPath(nn.Module):
                 if pipeline.serial and pipeline.last is not None:
                     pipeline.small.wait_event(pipeline.last)
             prev, fo = None, None
+            health = {}                                       # scale -> engine (read below) or device snapshot (read in ClipPipeline.wait)
             for s_, blk, ai, n_it, isc in ((16, self.update_block16, 0, iters // 2, 4), (8, self.update_block08, 1, iters // 2, 2),
                                           (4, self.update_block04, 2, iters, 1)):
                 f1, f2 = feats[f"f1_{s_}"], feats[f"f2_{s_}"]
@@ -290,6 +328,10 @@ class PPMStereoHotPath(nn.Module):
                         feats[k].record_stream(stream)            # (allocated on the caller's stream: keep the allocator from recycling them early)
                 with torch.cuda.stream(stream):
                     eng = blk.engine(tl, h, w, dev, shard)
+                    if diagnostics is not None:
+                        health_was_on = eng._health_on
+                        eng.enable_attn_health(True)
+                        eng.reset_attn_health()
                     eng.set_inp(feats[f"inp_{s_}"])
                     eng.set_net(feats[f"net_{s_}"])
                     if prev is None:
@@ -308,13 +350,21 @@ class PPMStereoHotPath(nn.Module):
                     eng.begin(CorrBlock1D(f1, f2).levels, self.att[ai].packed(dev))
                     fo = _run_iterations(eng, n_it, isc, tl, h, w, preds, uncs, "all" if not test_mode else ("last" if s_ == 4 else "none"))
                     prev = eng
+                    if diagnostics is not None:
+                        eng.enable_attn_health(health_was_on)
+                        health[f"1/{s_}"] = eng if pipeline is None else eng.attn_health_snapshot()
             if pipeline is not None:
                 pipeline.last = torch.cuda.Event(enable_timing=pipeline.record_done)
                 pipeline.last.record(pipeline.large)
+                if diagnostics is not None:
+                    pipeline._health.append((pipeline.last, diagnostics, health))
+                    del pipeline._health[:-16]                     # (as _results below: a caller that never waits)
                 if pipeline.record_done:
                     pipeline.done_events.append(pipeline.last)
                 pipeline._results += [preds[-1], uncs[-1]]         # (ClipPipeline.wait records the consuming stream on them)
                 del pipeline._results[:-16]                        # a caller that never waits (bench.py) must not accumulate references
+            elif diagnostics is not None:
+                _add_attn_redo(diagnostics, {tag: eng.attn_health() for tag, eng in health.items()})
             return preds[-1], uncs[-1]
 
 
@@ -511,11 +561,13 @@ class PPMStereo(PPMStereoHotPath):
         return feats
 
     @torch.no_grad()
-    def forward(self, image1: torch.Tensor, image2: torch.Tensor, flow_init=None, iters: int = 10, test_mode: bool = False, pipeline=None):
+    def forward(self, image1: torch.Tensor, image2: torch.Tensor, flow_init=None, iters: int = 10, test_mode: bool = False, pipeline=None,
+                diagnostics: Optional[dict] = None):
         """PPMStereo.forward (ppmstereo.py:601-804): image (b, T, 3, H, W) in [0, 255], H, W multiples of 32 (b = 1: the device-resident
         cascade; b > 1: the reference's glue around the batched forward_update_block).
         test_mode: (flow_up, uncertainty), each (b, T, 1, H, W); else (predictions (D, b, T, 1, H, W), uncertainties).
-        pipeline (test_mode only): a ``ClipPipeline`` -- the result is valid once ``pipeline.wait()`` has been called."""
+        pipeline (test_mode only): a ``ClipPipeline`` -- the result is valid once ``pipeline.wait()`` has been called.
+        diagnostics (b = 1): a dict that receives ``["attn_redo"]``, the per-scale fix-up accounting of the memory read-out (see ``cascade``)."""
         if flow_init is not None:
             raise NotImplementedError("flow_init: the reference's own path for it reads undefined state (ppmstereo.py:691-693, 763)")
         if self.fnet is None or self.cnet is None:
@@ -558,23 +610,27 @@ class PPMStereo(PPMStereoHotPath):
                 per = [self.pre_loop(*(x[bi * T:(bi + 1) * T] for x in (fmap1, fmap2, c4, c8, c16)), T) for bi in range(b)]
                 feats = {k: torch.cat([p_[k] for p_ in per]) for k in per[0]}
             preds, uncs = [], []
-            self.cascade(feats, iters, T, preds, uncs, test_mode=test_mode, pipeline=pipeline if test_mode else None)
+            self.cascade(feats, iters, T, preds, uncs, test_mode=test_mode, pipeline=pipeline if test_mode else None, diagnostics=diagnostics)
             if test_mode:
                 return preds[-1].reshape(b, T, 1, h, w), uncs[-1].reshape(b, T, 1, h, w)
             return torch.stack(preds).reshape(-1, b, T, 1, h, w), torch.stack(uncs).reshape(-1, b, T, 1, h, w)
 
     @torch.no_grad()
-    def forward_batch_test(self, batch_dict: Dict, kernel_size: int = 20, iters: int = 20, device=None, shard_ranks: bool = False):
+    def forward_batch_test(self, batch_dict: Dict, kernel_size: int = 20, iters: int = 20, device=None, shard_ranks: bool = False,
+                           diagnostics: bool = False):
         """PPMStereo.forward_batch_test (ppmstereo.py:238-320): batch_dict["stereo_video"] (N, 2, 3, H, W) on the host;
         per window: InputPadder(divis_by=32), one host->device copy, forward(test_mode=True), unpad, one device->host copy;
         windows of ``kernel_size`` frames every ``kernel_size // 2``, centre frames kept (:296-307).  Windows whose output the
         reference computes and then drops are not run.  Returns {"disparity", "uncertainties"}: (N, 1, H, W) CPU tensors.
         shard_ranks: under torch.distributed the windows are dealt round-robin over the ranks (independent units, no data-path
-        collective) and the kept frames are gathered once at the end (``dist.gather_kept_frames``); every rank returns the video."""
+        collective) and the kept frames are gathered once at the end (``dist.gather_kept_frames``); every rank returns the video.
+        diagnostics: the returned dict also has "attn_redo": the per-scale fix-up accounting of the memory read-out (see ``cascade``) summed
+        over all windows (``shard_ranks``: over this rank's windows).  False (default): the two keys above, and no extra launch."""
         video = batch_dict["stereo_video"]
         num_ims = len(video)
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         disp_preds, uncertainties = [], []
+        diag = {} if diagnostics else None
         plan = window_plan(num_ims, kernel_size)
         if shard_ranks and torch.distributed.is_available() and torch.distributed.is_initialized():
             from . import dist as D
@@ -590,14 +646,17 @@ class PPMStereo(PPMStereoHotPath):
                 left, right = win[:, 0], win[:, 1]
                 padder = InputPadder(left.shape, divis_by=32)
                 left, right = padder.pad(left, right)
-                d, u = self.forward(left[None], right[None], iters=iters, test_mode=True)
+                d, u = self.forward(left[None], right[None], iters=iters, test_mode=True, diagnostics=diag)
                 d, u = padder.unpad(d[0]), padder.unpad(u[0])               # (T, 1, H0, W0)
                 mine_d.append((firsts[wi], d[keep_from:keep_to].abs()[:, :1]))
                 mine_u.append((firsts[wi], u[keep_from:keep_to].abs()[:, :1]))
             H0, W0 = video.shape[-2:]
             disp = D.gather_kept_frames(mine_d, num_ims, H0, W0)
             unc = D.gather_kept_frames(mine_u, num_ims, H0, W0)
-            return {"disparity": disp.cpu(), "uncertainties": unc.cpu()}
+            out = {"disparity": disp.cpu(), "uncertainties": unc.cpu()}
+            if diag is not None:
+                out["attn_redo"] = diag.get("attn_redo", {})
+            return out
         # several windows: independent units -> software pipeline (ClipPipeline): window k + 1's encoders and small scales are enqueued
         # before window k's result is collected, and run under window k's 1/4 scale
         pipe = ClipPipeline(dev) if len(plan) > 1 else None
@@ -626,13 +685,16 @@ class PPMStereo(PPMStereoHotPath):
                 left, right = win[:, 0], win[:, 1]
                 padder = InputPadder(left.shape, divis_by=32)
                 left, right = padder.pad(left, right)
-                d, u = self.forward(left[None], right[None], iters=iters, test_mode=True, pipeline=pipe)
+                d, u = self.forward(left[None], right[None], iters=iters, test_mode=True, pipeline=pipe, diagnostics=diag)
                 item = (d, u, None if pipe is None else pipe.last, padder, keep_from, keep_to)
                 if pending is not None:
                     collect(pending)
                 pending = item
             collect(pending)
-        return {"disparity": torch.cat(disp_preds).squeeze(1).abs()[:, :1], "uncertainties": torch.cat(uncertainties).squeeze(1).abs()[:, :1]}
+        out = {"disparity": torch.cat(disp_preds).squeeze(1).abs()[:, :1], "uncertainties": torch.cat(uncertainties).squeeze(1).abs()[:, :1]}
+        if diag is not None:
+            out["attn_redo"] = diag.get("attn_redo", {})
+        return out
 
 
 def window_plan(num_ims: int, kernel_size: int = 20):

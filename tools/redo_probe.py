@@ -10,8 +10,7 @@ T, H, W, iters = (int(x) for x in sys.argv[1:5]) if len(sys.argv) > 4 else (5, 3
 dev = torch.device("cuda:0")
 model = PPMStereoHotPath().load_hot_path_weights(Wm.hot_path_weights()).to(dev).eval()
 feats = {k: v.to(dev) for k, v in synth_cascade_feats(T, H, W).items()}
-model.cascade(feats, iters, T, test_mode=True)
-torch.cuda.synchronize()
-for s, blk in ((16, model.update_block16), (8, model.update_block08), (4, model.update_block04)):
-    eng = blk.engine(T, H // s, W // s, dev)
-    print(f"T={T} {H}x{W} iters={iters} scale 1/{s}: (tiles, flagged) of the last attention call = {eng.attn_redo_count()}")
+diag = {}
+model.cascade(feats, iters, T, test_mode=True, diagnostics=diag)
+for scale, h in diag["attn_redo"].items():
+    print(f"T={T} {H}x{W} iters={iters} scale {scale}: {h['calls']} attention calls, {h['tiles']} tiles, {h['flagged']} handed to the fix-up pass")
