@@ -252,6 +252,14 @@ int ppms_ctx_mix(const float* fmap, const float* ctx, float* net, float* inp, in
  * dst.c == 4 * src.c.  H, W multiples of the factor. */
 int ppms_img_s2d(const float* img_nchw, ppms_sp dst, int N, int C, int H, int W, int k, void* stream);   /* k = 2 (fnet), 4 (cnet stem) */
 int ppms_sp_s2d(ppms_sp src, ppms_sp dst, int N, int H, int W, void* stream);
+/* uint8 video -> both encoders' first-layer operands, one launch: for byte frames (3, H0, W0) in CHW order -- `left` / `right` point to
+ * frame 0 of each view, consecutive frames of a view are `frame_stride` bytes apart (a (T, 2, 3, H0, W0) window: right = left + 3 H0 W0,
+ * stride 6 H0 W0; two (N, 3, H0, W0) tensors: stride 3 H0 W0) -- it writes what normalising with lut[byte] (device fp32 [256]), replicate
+ * padding to H x W (pad_left columns / pad_top rows in front, the rest behind; H, W multiples of 4), torch.cat([left, right]) and
+ * ppms_img_s2d give: dst_fnet = the k = 2 operand of the 2 N images (the N left frames first), dst_cnet = the k = 4 operand of the N left
+ * frames.  Channel order, zeroed channels >= 3 k k and the alignment contract are ppms_img_s2d's.  hi == NULL skips a destination. */
+int ppms_video_ingest_u8(const uint8_t* left, const uint8_t* right, int64_t frame_stride, int N, int H0, int W0, int pad_left, int pad_top, int H, int W,
+                         const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream);
 /* nn.InstanceNorm2d(affine=False) (extractor.py:326-329, 364): per (sample, channel) mean and 1 / sqrt(biased var + eps) over the
  * HW pixels of x (channel-last fp32 [N * HW][ld], a convolution's fp32 output) -> stats[N][C][2] (pixel slices merged in fixed
  * order: deterministic; caller-owned workspace of ppms_instnorm_workspace_bytes); then

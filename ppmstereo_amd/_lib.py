@@ -103,6 +103,7 @@ _SIGS = {
     "ppms_axpby": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_float, c_int64, c_int64, c_void_p]),
     "ppms_ctx_mix": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "ppms_img_s2d": (c_int, [c_void_p, SP, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "ppms_video_ingest_u8": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, SP, SP, c_void_p]),
     "ppms_dwconv": (c_int, [SP, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ppms_layernorm_any": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_float, SP, c_int64, c_int, c_void_p]),
     "ppms_grn_workspace_bytes": (c_int64, [c_int, c_int, c_int]),

@@ -132,6 +132,23 @@ class Feature(nn.Module):
         self._packed = (pk, vec)
         return self._packed
 
+    def plan(self, N: int, H: int, W: int, device) -> "_CnetEngine":
+        """The launch plan of N images of H x W on `device` (built on first use, the two most recent geometries are kept).  ``forward`` runs
+        it on an image batch; a caller that fills the stem's operand itself (``plan.s0_view()``, ppms_video_ingest_u8) runs
+        ``plan.run_filled()``."""
+        device = torch.device(device)
+        if H % 32 or W % 32:
+            raise ValueError(f"ppmstereo_amd Feature: H = {H}, W = {W} must be multiples of 32 (InputPadder(divis_by=32), ppmstereo.py:251)")
+        key = (N, H, W, device.index)
+        eng = self._engines.get(key)
+        if eng is None:
+            with torch.cuda.device(device):
+                eng = _CnetEngine(self._pack(device), N, H, W, device)
+            self._engines[key] = eng
+            while len(self._engines) > 2:
+                self._engines.popitem(last=False)
+        return eng
+
     # ------------------------------------------------------------------------------------------------ forward
     @torch.no_grad()
     def forward(self, x: torch.Tensor):
@@ -139,16 +156,7 @@ class Feature(nn.Module):
         if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 3):
             raise RuntimeError("ppmstereo_amd Feature: an (N, 3, H, W) fp32 tensor on the MI355X expected (no CPU path)")
         N, _, H, W = x.shape
-        if H % 32 or W % 32:
-            raise ValueError(f"ppmstereo_amd Feature: H = {H}, W = {W} must be multiples of 32 (InputPadder(divis_by=32), ppmstereo.py:251)")
-        key = (N, H, W, x.device.index)
-        eng = self._engines.get(key)
-        if eng is None:
-            with torch.cuda.device(x.device):
-                eng = _CnetEngine(self._pack(x.device), N, H, W, x.device)
-            self._engines[key] = eng
-            while len(self._engines) > 2:
-                self._engines.popitem(last=False)
+        eng = self.plan(N, H, W, x.device)
         with torch.cuda.device(x.device):                        # launches go to the current stream OF THE TENSOR'S device
             return eng.run(x.contiguous())
 
@@ -159,7 +167,7 @@ class _CnetEngine:
     def __init__(self, packed, N: int, H: int, W: int, device):
         pk, vec = packed
         self.lib = lib = L.load()
-        self.N, self.H, self.W = N, H, W
+        self.N, self.H, self.W, self.device = N, H, W, device
         d = CNET_DIMS
         hs = [H // 4, H // 8, H // 16, H // 32]
         ws = [W // 4, W // 8, W // 16, W // 32]
@@ -274,11 +282,20 @@ class _CnetEngine:
     def run(self, img: torch.Tensor):
         lib, s = self.lib, L.stream_ptr
         L.check(lib.ppms_img_s2d(img.data_ptr(), self.s0.view(), self.N, 3, self.H, self.W, 4, s()))
+        return self.run_filled()
+
+    def s0_view(self) -> L.SP:
+        """The stem's operand: the 4x4 patches of the N images, 48 values + zero padding per patch."""
+        return self.s0.view()
+
+    def run_filled(self):
+        """The step list on an ``s0`` the caller has filled (on the current stream, or ordered before it)."""
+        lib, s = self.lib, L.stream_ptr
         for st in self.steps:
             st()
         outs = []
         for fo, h_, w_ in self.finals:                              # 1/16, 1/8, 1/4
-            o = torch.empty(self.N, 256, h_, w_, device=img.device, dtype=torch.float32)
+            o = torch.empty(self.N, 256, h_, w_, device=self.device, dtype=torch.float32)
             L.check(lib.ppms_nhwc_to_nchw(fo.data_ptr(), 256, o.data_ptr(), self.N, 256, h_ * w_, s()))
             outs.append(o)
         return outs[2], outs[1], outs[0]

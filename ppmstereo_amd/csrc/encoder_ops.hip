@@ -36,6 +36,52 @@ __global__ __launch_bounds__(256) void img_s2d_kernel(const float* __restrict__ 
     *(bf16x8*)((bf16_t*)dst.lo + od) = ol;
 }
 
+// uint8 video -> the first-layer operands of both encoders in one launch (ppms_video_ingest_u8): what normalisation (a 256-entry table
+// the caller built with the float path's own torch expression), replicate padding (clamped source coordinate), torch.cat([left, right])
+// and the two img_s2d launches produce from the fp32 images.  Thread = one output pixel x 8 channels of one destination, as in
+// img_s2d_kernel: indices [0, nf) serve the k = 2 operand of the 2 N images (left frames, then right frames), [nf, total) the k = 4
+// operand of the N left frames.  Source rows have arbitrary W0: byte loads only.
+__global__ __launch_bounds__(256) void video_ingest_u8_kernel(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right, int64_t frame_stride, int N,
+                                                              int H0, int W0, int pad_left, int pad_top, int H, int W, const float* __restrict__ lut,
+                                                              ppms_sp dst_fnet, ppms_sp dst_cnet, int64_t nf, int64_t total) {
+    __shared__ float tab[256];
+    tab[threadIdx.x] = lut[threadIdx.x];
+    __syncthreads();
+    int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const bool fnet = idx < nf;
+    if (!fnet) idx -= nf;
+    const ppms_sp dst = fnet ? dst_fnet : dst_cnet;
+    const int ks = fnet ? 1 : 2, k = 1 << ks;                             // k = 2 (fnet) or 4 (cnet stem)
+    const int groups = dst.c >> 3;
+    const int g8 = (int)(idx % groups);
+    const int64_t p = idx / groups;
+    const int OW = W >> ks, OH = H >> ks;
+    const int j = (int)(p % OW), i = (int)((p / OW) % OH);
+    const int64_t m = p / ((int64_t)OW * OH);                             // image: left frames 0 .. N - 1, then the right frames
+    const uint8_t* src = m < N ? left + m * frame_stride : right + (m - N) * frame_stride;
+    bf16x8 oh, ol;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int ch = g8 * 8 + e;
+        float v = 0.0f;
+        if (ch < k * k * 3) {
+            const int ph = ch / 3, c = ch - ph * 3;
+            int y = k * i + (ph >> ks) - pad_top, x = k * j + (ph & (k - 1)) - pad_left;
+            y = y < 0 ? 0 : (y > H0 - 1 ? H0 - 1 : y);                    // replicate padding
+            x = x < 0 ? 0 : (x > W0 - 1 ? W0 - 1 : x);
+            v = tab[src[((int64_t)c * H0 + y) * W0 + x]];
+        }
+        bf16_t hh, ll;
+        split_bf16(v, hh, ll);
+        oh[e] = hh;
+        ol[e] = ll;
+    }
+    const int64_t od = p * dst.ld + g8 * 8;
+    *(bf16x8*)((bf16_t*)dst.hi + od) = oh;
+    *(bf16x8*)((bf16_t*)dst.lo + od) = ol;
+}
+
 // split-plane form: pure copies of 16-B channel groups (both planes)
 __global__ __launch_bounds__(256) void sp_s2d_kernel(ppms_sp src, ppms_sp dst, int H, int W, int64_t npix) {
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;          // one thread = one output pixel x 8 channels
@@ -526,6 +572,32 @@ extern "C" int ppms_img_s2d(const float* img, ppms_sp dst, int N, int C, int H, 
     const int64_t npix = (int64_t)N * (H / k) * (W / k);
     hipLaunchKernelGGL(img_s2d_kernel, dim3(ceil_div(npix * (dst.c / 8), 256)), dim3(256), 0, (hipStream_t)stream, img, dst, C, H, W, k, npix);
     return ppms_check_launch("img_s2d");
+}
+
+extern "C" int ppms_video_ingest_u8(const uint8_t* left, const uint8_t* right, int64_t frame_stride, int N, int H0, int W0, int pad_left, int pad_top, int H,
+                                    int W, const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream) {
+    PPMS_REQUIRE(left && right && lut, "video_ingest_u8: null source or table pointer");
+    PPMS_REQUIRE(N > 0 && H0 > 0 && W0 > 0 && H > 0 && W > 0, "video_ingest_u8: N = %d, H0 = %d, W0 = %d, H = %d, W = %d must be positive", N, H0, W0, H, W);
+    PPMS_REQUIRE(H % 4 == 0 && W % 4 == 0, "video_ingest_u8: H = %d, W = %d must be multiples of 4", H, W);
+    PPMS_REQUIRE(pad_left >= 0 && pad_top >= 0 && (int64_t)pad_top + H0 <= H && (int64_t)pad_left + W0 <= W,
+                 "video_ingest_u8: pad_left = %d, pad_top = %d with a %d x %d source do not fit the %d x %d padded image", pad_left, pad_top, H0, W0, H, W);
+    PPMS_REQUIRE(frame_stride >= (int64_t)3 * H0 * W0, "video_ingest_u8: frame_stride = %lld is less than a frame's 3 * H0 * W0 bytes", (long long)frame_stride);
+    PPMS_REQUIRE(dst_fnet.hi || dst_cnet.hi, "video_ingest_u8: both destinations skipped");
+    const ppms_sp* dsts[2] = {&dst_fnet, &dst_cnet};
+    int64_t threads[2] = {0, 0};
+    for (int s = 0; s < 2; ++s) {
+        const ppms_sp& d = *dsts[s];
+        if (!d.hi) continue;                                               // skipped
+        const int k = s == 0 ? 2 : 4;
+        PPMS_REQUIRE(d.lo && d.c >= k * k * 3 && d.c % 8 == 0 && d.ld % 8 == 0 && d.ld >= d.c && (((uintptr_t)d.hi | (uintptr_t)d.lo) & 15) == 0,
+                     "video_ingest_u8: the k = %d destination view needs >= %d channels, multiples of 8, 16-B aligned", k, k * k * 3);
+        threads[s] = (int64_t)(s == 0 ? 2 : 1) * N * (H / k) * (W / k) * (d.c / 8);
+    }
+    const int64_t total = threads[0] + threads[1];
+    PPMS_REQUIRE((total + 255) / 256 <= 0x7fffffff, "video_ingest_u8: %lld threads exceed one grid", (long long)total);
+    hipLaunchKernelGGL(video_ingest_u8_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, left, right, frame_stride, N, H0, W0, pad_left,
+                       pad_top, H, W, lut, dst_fnet, dst_cnet, threads[0], total);
+    return ppms_check_launch("video_ingest_u8");
 }
 
 extern "C" int ppms_sp_s2d(ppms_sp src, ppms_sp dst, int N, int H, int W, void* stream) {

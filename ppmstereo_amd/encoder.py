@@ -105,6 +105,23 @@ class BasicEncoder(nn.Module):
         self._packed = pk
         return pk
 
+    def plan(self, N: int, H: int, W: int, device) -> "_FnetEngine":
+        """The launch plan of N images of H x W on `device` (built on first use, the two most recent geometries are kept).  ``forward`` runs
+        it on an image batch; a caller that fills the first layer's operand itself (``plan.s0_view()``, ppms_video_ingest_u8) runs
+        ``plan.run_filled()``."""
+        device = torch.device(device)
+        if H % 4 or W % 4:
+            raise ValueError(f"ppmstereo_amd BasicEncoder: H = {H}, W = {W} must be multiples of 4 (the reference pads inputs to multiples of 32, ppmstereo.py:251)")
+        key = (N, H, W, device.index)
+        eng = self._engines.get(key)
+        if eng is None:
+            with torch.cuda.device(device):
+                eng = _FnetEngine(self._pack(device), N, H, W, device, self.output_dim)
+            self._engines[key] = eng
+            while len(self._engines) > 2:
+                self._engines.popitem(last=False)
+        return eng
+
     # ------------------------------------------------------------------------------------------------ forward
     def forward(self, x):
         """x: (N, 3, H, W) fp32 on the GPU, or a pair of such (extractor.py:398-401: concatenated on the batch axis, split back at
@@ -116,16 +133,7 @@ class BasicEncoder(nn.Module):
                 raise RuntimeError("ppmstereo_amd BasicEncoder: (N, 3, H, W) fp32 tensors on the MI355X expected (no CPU path)")
         img = torch.cat(xs, dim=0).contiguous() if is_list else xs[0].contiguous()
         N, _, H, W = img.shape
-        if H % 4 or W % 4:
-            raise ValueError(f"ppmstereo_amd BasicEncoder: H = {H}, W = {W} must be multiples of 4 (the reference pads inputs to multiples of 32, ppmstereo.py:251)")
-        key = (N, H, W, img.device.index)
-        eng = self._engines.get(key)
-        if eng is None:
-            with torch.cuda.device(img.device):
-                eng = _FnetEngine(self._pack(img.device), N, H, W, img.device, self.output_dim)
-            self._engines[key] = eng
-            while len(self._engines) > 2:
-                self._engines.popitem(last=False)
+        eng = self.plan(N, H, W, img.device)
         with torch.cuda.device(img.device):                      # launches go to the current stream OF THE TENSOR'S device
             out = eng.run(img)
         if is_list:
@@ -220,6 +228,14 @@ class _FnetEngine:
 
     def run(self, img: torch.Tensor) -> torch.Tensor:
         L.check(self.lib.ppms_img_s2d(img.data_ptr(), self.s0.view(), self.N, 3, self.H, self.W, 2, L.stream_ptr()))
+        return self.run_filled()
+
+    def s0_view(self) -> L.SP:
+        """The first convolution's operand: the 2x2 space-to-depth image, 12 values + zero padding per pixel of the N images."""
+        return self.s0.view()
+
+    def run_filled(self) -> torch.Tensor:
+        """The op list on an ``s0`` the caller has filled (on the current stream, or ordered before it)."""
         for kind, op in self.ops:
             op()
         out = torch.empty_like(self.out)

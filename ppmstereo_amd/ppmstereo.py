@@ -416,6 +416,11 @@ class InputPadder:
         left, top = extra_w // 2, (extra_h // 2 if mode == "sintel" else 0)
         self._pad = [left, extra_w - left, top, extra_h - top]          # F.pad order: left, right, top, bottom
 
+    def geometry(self):
+        """(pad_left, pad_top, H, W): the columns / rows ``pad`` adds in front and the padded size (what ppms_video_ingest_u8 takes)."""
+        left, right, top, bottom = self._pad
+        return left, top, top + self.ht + bottom, left + self.wd + right
+
     def pad(self, *inputs):
         for x in inputs:
             if x.ndim != 4:
@@ -429,6 +434,36 @@ class InputPadder:
             raise ValueError(f"InputPadder.unpad: 4-D tensor expected, got {tuple(x.shape)}")
         left, right, top, bottom = self._pad
         return x[..., top:x.shape[-2] - bottom, left:x.shape[-1] - right]
+
+
+_BYTE_LUT: Dict[int, torch.Tensor] = {}
+
+
+def byte_lut(device) -> torch.Tensor:
+    """fp32 [256] on `device`: the normalised value of every byte, from the expression ``forward`` applies to float images ON THE SAME
+    DEVICE -- torch's division by a Python scalar need not round like a division written elsewhere, so the table is what makes the uint8
+    path the float path's bits.  Built once per device (the host waits for it once)."""
+    device = torch.device(device)
+    idx = torch.cuda.current_device() if device.index is None else device.index
+    if idx not in _BYTE_LUT:
+        dev = torch.device("cuda", idx)
+        _BYTE_LUT[idx] = (2 * (torch.arange(256, dtype=torch.float32, device=dev) / 255.0) - 1.0).contiguous()
+        torch.cuda.current_stream(dev).synchronize()             # later calls may read it from any stream
+    return _BYTE_LUT[idx]
+
+
+class _ByteFrames:
+    """uint8 frames of both views on the device as ppms_video_ingest_u8 reads them: ``left`` / ``right`` start at frame 0 of a view, frame
+    n of a view lies ``frame_stride`` bytes further; (H0, W0) frames go to the padded size with ``pad_left`` / ``pad_top`` in front."""
+
+    def __init__(self, left: torch.Tensor, right: torch.Tensor, frame_stride: int, n: int, h0: int, w0: int, pad_left: int = 0, pad_top: int = 0):
+        self.left, self.right, self.frame_stride, self.n = left, right, int(frame_stride), int(n)
+        self.h0, self.w0, self.pad_left, self.pad_top = int(h0), int(w0), int(pad_left), int(pad_top)
+
+    def ingest(self, dst_fnet: L.SP, dst_cnet: L.SP, h: int, w: int) -> None:
+        """One launch on the current stream: both encoders' first-layer operands of the n frames padded to h x w."""
+        L.check(L.load().ppms_video_ingest_u8(self.left.data_ptr(), self.right.data_ptr(), self.frame_stride, self.n, self.h0, self.w0, self.pad_left,
+                                              self.pad_top, h, w, byte_lut(self.left.device).data_ptr(), dst_fnet, dst_cnet, L.stream_ptr()))
 
 
 class PPMStereo(PPMStereoHotPath):
@@ -564,7 +599,9 @@ class PPMStereo(PPMStereoHotPath):
     def forward(self, image1: torch.Tensor, image2: torch.Tensor, flow_init=None, iters: int = 10, test_mode: bool = False, pipeline=None,
                 diagnostics: Optional[dict] = None):
         """PPMStereo.forward (ppmstereo.py:601-804): image (b, T, 3, H, W) in [0, 255], H, W multiples of 32 (b = 1: the device-resident
-        cascade; b > 1: the reference's glue around the batched forward_update_block).
+        cascade; b > 1: the reference's glue around the batched forward_update_block).  Float images as in the reference, or both uint8:
+        with this package's encoders the bytes go through ONE kernel (ppms_video_ingest_u8) to the operands of the first convolutions --
+        the same bits as ``forward(image1.float(), image2.float())``; with other encoder callables they are converted to float on the device.
         test_mode: (flow_up, uncertainty), each (b, T, 1, H, W); else (predictions (D, b, T, 1, H, W), uncertainties).
         pipeline (test_mode only): a ``ClipPipeline`` -- the result is valid once ``pipeline.wait()`` has been called.
         diagnostics (b = 1): a dict that receives ``["attn_redo"]``, the per-scale fix-up accounting of the memory read-out (see ``cascade``)."""
@@ -572,23 +609,58 @@ class PPMStereo(PPMStereoHotPath):
             raise NotImplementedError("flow_init: the reference's own path for it reads undefined state (ppmstereo.py:691-693, 763)")
         if self.fnet is None or self.cnet is None:
             raise RuntimeError("PPMStereo.forward needs the encoders: pass fnet= / cnet= (outside the hot path, SURVEY.md section 8 f3-f5)")
+        if torch.is_tensor(image1) and torch.is_tensor(image2) and (image1.dtype == torch.uint8) != (image2.dtype == torch.uint8):
+            raise TypeError(f"PPMStereo.forward: image1 is {image1.dtype} and image2 is {image2.dtype}; both views must be uint8 or both floating point")
         b, T, c, h, w = image1.shape
         if b != 1 and pipeline is not None:
             raise NotImplementedError("PPMStereo.forward: a ClipPipeline overlaps consecutive batch-1 clips")
-        with torch.cuda.device(image1.device):
-            im1 = (2 * (image1 / 255.0) - 1.0).contiguous().reshape(b * T, c, h, w)
-            im2 = (2 * (image2 / 255.0) - 1.0).contiguous().reshape(b * T, c, h, w)
+        images = (image1, image2)
+        if image1.dtype == torch.uint8:
+            if self._hip_encoders() and image1.is_cuda and image2.is_cuda:
+                if image2.shape != image1.shape or c != 3:
+                    raise ValueError(f"PPMStereo.forward: two uint8 videos of one shape (b, T, 3, H, W) expected, got {tuple(image1.shape)} and {tuple(image2.shape)}")
+                images = _ByteFrames(image1.contiguous(), image2.contiguous(), 3 * h * w, b * T, h, w)
+            else:                                              # encoder callables of the caller: they get what they get for a float video
+                images = (image1.float(), image2.float())
+        return self._forward_images(images, b, T, h, w, image1.device, iters, test_mode, pipeline, diagnostics)
+
+    def _hip_encoders(self) -> bool:
+        """Both encoders are this package's: their plans take the first-layer operands ppms_video_ingest_u8 writes."""
+        from .cnet import Feature
+        from .encoder import BasicEncoder
+        return isinstance(self.fnet, BasicEncoder) and isinstance(self.cnet, Feature)
+
+    def _forward_images(self, images, b: int, T: int, h: int, w: int, dev, iters: int, test_mode: bool, pipeline, diagnostics):
+        """``forward`` behind its argument checks.  images: the two float videos (b, T, 3, h, w), or ``_ByteFrames`` holding b * T uint8 frames
+        per view that ppms_video_ingest_u8 pads to h x w (``forward_batch_test`` hands a window over unpadded)."""
+        with torch.cuda.device(dev):
             # fnet (both views) and cnet (left view) depend on the images only and are chains of small launches that leave most of the chip
             # idle: cnet runs on a second stream beside fnet (whole call -3.5 ms at config 2); its outputs are handed to the caller's
             # stream with an event + record_stream
-            cur = torch.cuda.current_stream(image1.device)
+            cur = torch.cuda.current_stream(dev)
+            if isinstance(images, _ByteFrames):
+                # bytes -> the operands of fnet's conv1 and cnet's stem, one launch on the caller's stream (ordered before the side stream's wait)
+                fplan, cplan = self.fnet.plan(2 * b * T, h, w, dev), self.cnet.plan(b * T, h, w, dev)
+                images.ingest(fplan.s0_view(), cplan.s0_view(), h, w)
+                run_fnet = lambda: torch.split(fplan.run_filled(), b * T, dim=0)
+                run_cnet = cplan.run_filled
+                held = (images.left, images.right)
+            else:
+                image1, image2 = images
+                c = image1.shape[2]
+                im1 = (2 * (image1 / 255.0) - 1.0).contiguous().reshape(b * T, c, h, w)
+                im2 = (2 * (image2 / 255.0) - 1.0).contiguous().reshape(b * T, c, h, w)
+                run_fnet = lambda: self.fnet([im1, im2])
+                run_cnet = lambda: self.cnet(im1)
+                held = (im1,)
             if self.parallel_encoders:
-                side = self._encoder_stream(image1.device)
+                side = self._encoder_stream(dev)
                 side.wait_stream(cur)
-                im1.record_stream(side)
+                for t_ in held:
+                    t_.record_stream(side)
                 with torch.cuda.stream(side):
-                    c4, c8, c16 = self.cnet(im1)
-                fmap1, fmap2 = self.fnet([im1, im2])
+                    c4, c8, c16 = run_cnet()
+                fmap1, fmap2 = run_fnet()
                 for t_ in (c4, c8, c16):
                     if torch.is_tensor(t_):
                         t_.record_stream(cur)
@@ -599,8 +671,8 @@ class PPMStereo(PPMStereoHotPath):
                         cur.wait_stream(side)
                         ready["done"] = True
             else:
-                fmap1, fmap2 = self.fnet([im1, im2])
-                c4, c8, c16 = self.cnet(im1)
+                fmap1, fmap2 = run_fnet()
+                c4, c8, c16 = run_cnet()
                 ctx_ready = None
             if b == 1:
                 feats = self.pre_loop(fmap1, fmap2, c4, c8, c16, T, ctx_ready)
@@ -620,6 +692,8 @@ class PPMStereo(PPMStereoHotPath):
                            diagnostics: bool = False):
         """PPMStereo.forward_batch_test (ppmstereo.py:238-320): batch_dict["stereo_video"] (N, 2, 3, H, W) on the host;
         per window: InputPadder(divis_by=32), one host->device copy, forward(test_mode=True), unpad, one device->host copy;
+        a uint8 video (host or device) is copied as bytes -- a quarter of the float video's -- and, with this package's encoders, padded and
+        normalised inside ppms_video_ingest_u8: the same bits as for ``stereo_video.float()``;
         windows of ``kernel_size`` frames every ``kernel_size // 2``, centre frames kept (:296-307).  Windows whose output the
         reference computes and then drops are not run.  Returns {"disparity", "uncertainties"}: (N, 1, H, W) CPU tensors.
         shard_ranks: under torch.distributed the windows are dealt round-robin over the ranks (independent units, no data-path
@@ -642,11 +716,7 @@ class PPMStereo(PPMStereoHotPath):
             for wi, (start, stop, keep_from, keep_to) in enumerate(plan):
                 if wi % world != rank:
                     continue
-                win = video[start:stop].to(dev)                              # one host -> device copy per window (see below)
-                left, right = win[:, 0], win[:, 1]
-                padder = InputPadder(left.shape, divis_by=32)
-                left, right = padder.pad(left, right)
-                d, u = self.forward(left[None], right[None], iters=iters, test_mode=True, diagnostics=diag)
+                d, u, padder = self._window_forward(video, start, stop, dev, iters, None, diag)       # one host -> device copy per window (see below)
                 d, u = padder.unpad(d[0]), padder.unpad(u[0])               # (T, 1, H0, W0)
                 mine_d.append((firsts[wi], d[keep_from:keep_to].abs()[:, :1]))
                 mine_u.append((firsts[wi], u[keep_from:keep_to].abs()[:, :1]))
@@ -679,13 +749,7 @@ class PPMStereo(PPMStereoHotPath):
 
         with torch.cuda.device(dev):
             for start, stop, keep_from, keep_to in plan:
-                # host -> device: ONE copy of the window's contiguous (T, 2, 3, H, W) block; the two views are split and padded on the
-                # device (slicing a view out on the host first costs a host-side copy of each view, padding there another one)
-                win = video[start:stop].to(dev)
-                left, right = win[:, 0], win[:, 1]
-                padder = InputPadder(left.shape, divis_by=32)
-                left, right = padder.pad(left, right)
-                d, u = self.forward(left[None], right[None], iters=iters, test_mode=True, pipeline=pipe, diagnostics=diag)
+                d, u, padder = self._window_forward(video, start, stop, dev, iters, pipe, diag)
                 item = (d, u, None if pipe is None else pipe.last, padder, keep_from, keep_to)
                 if pending is not None:
                     collect(pending)
@@ -695,6 +759,35 @@ class PPMStereo(PPMStereoHotPath):
         if diag is not None:
             out["attn_redo"] = diag.get("attn_redo", {})
         return out
+
+
+def _window_forward(self, video, start: int, stop: int, dev, iters: int, pipe, diag):
+    """One window of forward_batch_test: frames [start, stop) of the (N, 2, 3, H0, W0) video -> (disparity, uncertainty) of the padded
+    window, each (1, T, 1, H, W), and the InputPadder that crops them back."""
+    # host -> device: ONE copy of the window's contiguous (T, 2, 3, H, W) block; the two views are split and padded on the
+    # device (slicing a view out on the host first costs a host-side copy of each view, padding there another one)
+    win = video[start:stop].to(dev)
+    if win.dtype == torch.uint8:
+        if win.dim() != 5 or win.shape[1] != 2 or win.shape[2] != 3:
+            raise ValueError(f"forward_batch_test: a uint8 stereo_video is (N, 2, 3, H, W), got {tuple(video.shape)}")
+        if self._hip_encoders():
+            # the bytes stay as they are: ppms_video_ingest_u8 reads both views out of the block and pads by clamping its source coordinate
+            win = win.contiguous()
+            T, H0, W0 = win.shape[0], win.shape[3], win.shape[4]
+            padder = InputPadder((H0, W0), divis_by=32)
+            pad_left, pad_top, H, W = padder.geometry()
+            frames = _ByteFrames(win[:, 0], win[:, 1], 6 * H0 * W0, T, H0, W0, pad_left, pad_top)
+            d, u = self._forward_images(frames, 1, T, H, W, dev, iters, True, pipe, diag)
+            return d, u, padder
+        win = win.float()                                        # encoder callables of the caller: the float path from here on
+    left, right = win[:, 0], win[:, 1]
+    padder = InputPadder(left.shape, divis_by=32)
+    left, right = padder.pad(left, right)
+    d, u = self.forward(left[None], right[None], iters=iters, test_mode=True, pipeline=pipe, diagnostics=diag)
+    return d, u, padder
+
+
+PPMStereo._window_forward = _window_forward
 
 
 def window_plan(num_ims: int, kernel_size: int = 20):
