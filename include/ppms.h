@@ -260,6 +260,29 @@ int ppms_sp_s2d(ppms_sp src, ppms_sp dst, int N, int H, int W, void* stream);
  * frames.  Channel order, zeroed channels >= 3 k k and the alignment contract are ppms_img_s2d's.  hi == NULL skips a destination. */
 int ppms_video_ingest_u8(const uint8_t* left, const uint8_t* right, int64_t frame_stride, int N, int H0, int W0, int pad_left, int pad_top, int H, int W,
                          const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream);
+/* The same two operands from decoded YUV 4:2:0 frames (NV12, I420 / yuv420p; 8 bits), one launch: a view describes one eye's N frames as the
+ * decoder left them -- a pitched Y plane of H0 x W0 bytes and chroma planes of ceil(H0/2) x ceil(W0/2) samples, planar (step_c = 1) or interleaved
+ * (step_c = 2, v == u + 1 for NV12); both views of a side-by-side or top-and-bottom packed frame are two views into one surface.  Luma pixel
+ * (y, x) -- after the replicate-padding clamp -- takes chroma sample (y >> 1, x >> 1) (nearest; odd H0, W0 are legal), and its RGB bytes are,
+ * in integers (>> is the arithmetic shift, r = 1 << (shift - 1), d = Y - y_off, e = U - 128, f = V - 128):
+ *   R = clamp((cy d + crv f + r) >> shift, 0, 255), G = clamp((cy d - cgu e - cgv f + r) >> shift, 0, 255), B = clamp((cy d + cbu e + r) >> shift, 0, 255)
+ * (shift in [8, 20], y_off in [0, 255], coefficients in [0, 4 << shift): no sum leaves 32 bits).  From those bytes on -- lut, pads, H x W,
+ * destinations, hi == NULL -- the call is ppms_video_ingest_u8 on channel order R, G, B.  The three structs are HOST memory, read before the
+ * call returns; every pointer inside a view is a device pointer.  Not covered: 10-bit surfaces (P010), 4:2:2 / 4:4:4, interpolated chroma. */
+typedef struct ppms_yuv_view {        /* one view's frames, as the decoder left them */
+    const uint8_t *y, *u, *v;         /* sample (0,0) of frame 0; interleaved UV: v == u + 1 */
+    int64_t frame_stride_y, frame_stride_c;   /* bytes from frame n to frame n + 1 */
+    int32_t pitch_y, pitch_c;         /* bytes from row to row */
+    int32_t step_c;                   /* bytes from chroma sample to chroma sample: 1 (planar) or 2 (interleaved) */
+    int32_t reserved;                 /* 0 */
+} ppms_yuv_view;
+typedef struct ppms_yuv_matrix {      /* fixed-point YCbCr -> RGB, see above */
+    int32_t y_off, cy, crv, cgu, cgv, cbu, shift, reserved;
+} ppms_yuv_matrix;
+int ppms_video_ingest_yuv420(const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m,
+                             int N, int H0, int W0, int pad_left, int pad_top, int H, int W,
+                             const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream);
+int ppms_yuv_struct_sizes(int* view, int* matrix);   /* sizeof of the two structs above (56, 32): lets a binding verify its layout */
 /* nn.InstanceNorm2d(affine=False) (extractor.py:326-329, 364): per (sample, channel) mean and 1 / sqrt(biased var + eps) over the
  * HW pixels of x (channel-last fp32 [N * HW][ld], a convolution's fp32 output) -> stats[N][C][2] (pixel slices merged in fixed
  * order: deterministic; caller-owned workspace of ppms_instnorm_workspace_bytes); then

@@ -60,6 +60,17 @@ class ChainParams(C.Structure):
     _fields_ = [("inp", SP), ("out", SP), ("layer", ChainLayer * 3), ("nlayers", C.c_int32), ("P", C.c_int64)]
 
 
+class YUVView(C.Structure):
+    """ppms_yuv_view: one view's decoded 4:2:0 frames (device pointers, byte strides)."""
+    _fields_ = [("y", c_void_p), ("u", c_void_p), ("v", c_void_p), ("frame_stride_y", c_int64), ("frame_stride_c", c_int64),
+                ("pitch_y", C.c_int32), ("pitch_c", C.c_int32), ("step_c", C.c_int32), ("reserved", C.c_int32)]
+
+
+class YUVMatrix(C.Structure):
+    """ppms_yuv_matrix: the fixed-point YCbCr -> RGB conversion."""
+    _fields_ = [(n, C.c_int32) for n in ("y_off", "cy", "crv", "cgu", "cgv", "cbu", "shift", "reserved")]
+
+
 _SIGS = {
     "ppms_version": (c_int, []),
     "ppms_last_error": (C.c_char_p, []),
@@ -104,6 +115,9 @@ _SIGS = {
     "ppms_ctx_mix": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "ppms_img_s2d": (c_int, [c_void_p, SP, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "ppms_video_ingest_u8": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, SP, SP, c_void_p]),
+    "ppms_video_ingest_yuv420": (c_int, [C.POINTER(YUVView), C.POINTER(YUVView), C.POINTER(YUVMatrix), c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                         c_void_p, SP, SP, c_void_p]),
+    "ppms_yuv_struct_sizes": (c_int, [C.POINTER(c_int), C.POINTER(c_int)]),
     "ppms_dwconv": (c_int, [SP, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ppms_layernorm_any": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_float, SP, c_int64, c_int, c_void_p]),
     "ppms_grn_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
@@ -159,6 +173,9 @@ def load() -> C.CDLL:
     lib.ppms_struct_sizes(C.byref(a), C.byref(b), C.byref(c))
     if (a.value, b.value, c.value) != (C.sizeof(SP), C.sizeof(Epilogue), C.sizeof(Conv)):
         raise RuntimeError("ppmstereo_amd: ctypes struct layout differs from include/ppms.h")
+    lib.ppms_yuv_struct_sizes(C.byref(a), C.byref(b))
+    if (a.value, b.value) != (C.sizeof(YUVView), C.sizeof(YUVMatrix)):
+        raise RuntimeError("ppmstereo_amd: ctypes layout of ppms_yuv_view / ppms_yuv_matrix differs from include/ppms.h")
     if lib.ppms_pwchain_param_bytes() != C.sizeof(ChainParams):
         raise RuntimeError("ppmstereo_amd: ChainParams layout differs from pwchain.hip")
     _lib = lib

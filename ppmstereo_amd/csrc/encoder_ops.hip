@@ -36,14 +36,44 @@ __global__ __launch_bounds__(256) void img_s2d_kernel(const float* __restrict__ 
     *(bf16x8*)((bf16_t*)dst.lo + od) = ol;
 }
 
-// uint8 video -> the first-layer operands of both encoders in one launch (ppms_video_ingest_u8): what normalisation (a 256-entry table
-// the caller built with the float path's own torch expression), replicate padding (clamped source coordinate), torch.cat([left, right])
-// and the two img_s2d launches produce from the fp32 images.  Thread = one output pixel x 8 channels of one destination, as in
-// img_s2d_kernel: indices [0, nf) serve the k = 2 operand of the 2 N images (left frames, then right frames), [nf, total) the k = 4
-// operand of the N left frames.  Source rows have arbitrary W0: byte loads only.
-__global__ __launch_bounds__(256) void video_ingest_u8_kernel(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right, int64_t frame_stride, int N,
-                                                              int H0, int W0, int pad_left, int pad_top, int H, int W, const float* __restrict__ lut,
-                                                              ppms_sp dst_fnet, ppms_sp dst_cnet, int64_t nf, int64_t total) {
+// decoded video -> the first-layer operands of both encoders in one launch (ppms_video_ingest_u8 / ppms_video_ingest_yuv420): what
+// normalisation (a 256-entry table the caller built with the float path's own torch expression), replicate padding (clamped source
+// coordinate), torch.cat([left, right]) and the two img_s2d launches produce from the fp32 images.  Thread = one output pixel x 8 channels
+// of one destination, as in img_s2d_kernel: indices [0, nf) serve the k = 2 operand of the 2 N images (left frames, then right frames),
+// [nf, total) the k = 4 operand of the N left frames.  Where a byte comes from is the Source: source(m, c, y, x) = channel c (R, G, B) of
+// pixel (y, x), already clamped into the frame, of image m.  Source rows have arbitrary widths and pitches: byte loads only.
+struct rgb_planes_source {                                                // planar RGB bytes, dense rows (ppms_video_ingest_u8)
+    const uint8_t *left, *right;
+    int64_t frame_stride;
+    int N, H0, W0;
+    __device__ int operator()(int64_t m, int c, int y, int x) const {
+        const uint8_t* src = m < N ? left + m * frame_stride : right + (m - N) * frame_stride;
+        return src[((int64_t)c * H0 + y) * W0 + x];
+    }
+};
+
+struct yuv420_source {                                                    // pitched Y plane + half-resolution chroma (ppms_video_ingest_yuv420)
+    ppms_yuv_view left, right;
+    ppms_yuv_matrix mat;
+    int N;
+    __device__ int operator()(int64_t m, int c, int y, int x) const {
+        const bool r = m >= N;
+        const int64_t n = r ? m - N : m;
+        const uint8_t *py = r ? right.y : left.y, *pu = r ? right.u : left.u, *pv = r ? right.v : left.v;
+        const int64_t oy = n * (r ? right.frame_stride_y : left.frame_stride_y) + (int64_t)y * (r ? right.pitch_y : left.pitch_y) + x;
+        const int64_t oc = n * (r ? right.frame_stride_c : left.frame_stride_c) + (int64_t)(y >> 1) * (r ? right.pitch_c : left.pitch_c) +
+                           (int64_t)(x >> 1) * (r ? right.step_c : left.step_c);      // nearest chroma sample of the clamped luma pixel
+        // the three channels of a pixel repeat these loads; they are the same addresses, and the compiler merges them
+        const int d = py[oy] - mat.y_off, e = pu[oc] - 128, f = pv[oc] - 128;
+        const int acc = mat.cy * d + (c == 0 ? mat.crv * f : c == 1 ? -mat.cgu * e - mat.cgv * f : mat.cbu * e) + (1 << (mat.shift - 1));
+        const int q = acc >> mat.shift;                                   // arithmetic shift: floor
+        return q < 0 ? 0 : (q > 255 ? 255 : q);
+    }
+};
+
+template <class Source>
+__global__ __launch_bounds__(256) void video_ingest_kernel(Source source, int N, int H0, int W0, int pad_left, int pad_top, int H, int W,
+                                                           const float* __restrict__ lut, ppms_sp dst_fnet, ppms_sp dst_cnet, int64_t nf, int64_t total) {
     __shared__ float tab[256];
     tab[threadIdx.x] = lut[threadIdx.x];
     __syncthreads();
@@ -59,7 +89,6 @@ __global__ __launch_bounds__(256) void video_ingest_u8_kernel(const uint8_t* __r
     const int OW = W >> ks, OH = H >> ks;
     const int j = (int)(p % OW), i = (int)((p / OW) % OH);
     const int64_t m = p / ((int64_t)OW * OH);                             // image: left frames 0 .. N - 1, then the right frames
-    const uint8_t* src = m < N ? left + m * frame_stride : right + (m - N) * frame_stride;
     bf16x8 oh, ol;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -70,7 +99,7 @@ __global__ __launch_bounds__(256) void video_ingest_u8_kernel(const uint8_t* __r
             int y = k * i + (ph >> ks) - pad_top, x = k * j + (ph & (k - 1)) - pad_left;
             y = y < 0 ? 0 : (y > H0 - 1 ? H0 - 1 : y);                    // replicate padding
             x = x < 0 ? 0 : (x > W0 - 1 ? W0 - 1 : x);
-            v = tab[src[((int64_t)c * H0 + y) * W0 + x]];
+            v = tab[source(m, c, y, x)];
         }
         bf16_t hh, ll;
         split_bf16(v, hh, ll);
@@ -574,15 +603,16 @@ extern "C" int ppms_img_s2d(const float* img, ppms_sp dst, int N, int C, int H, 
     return ppms_check_launch("img_s2d");
 }
 
-extern "C" int ppms_video_ingest_u8(const uint8_t* left, const uint8_t* right, int64_t frame_stride, int N, int H0, int W0, int pad_left, int pad_top, int H,
-                                    int W, const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream) {
-    PPMS_REQUIRE(left && right && lut, "video_ingest_u8: null source or table pointer");
-    PPMS_REQUIRE(N > 0 && H0 > 0 && W0 > 0 && H > 0 && W > 0, "video_ingest_u8: N = %d, H0 = %d, W0 = %d, H = %d, W = %d must be positive", N, H0, W0, H, W);
-    PPMS_REQUIRE(H % 4 == 0 && W % 4 == 0, "video_ingest_u8: H = %d, W = %d must be multiples of 4", H, W);
+// what both video ingest entry points check about sizes, pads, table and destinations, and their launch (`who` names the entry point)
+template <class Source>
+static int video_ingest_launch(const char* who, const Source& source, int N, int H0, int W0, int pad_left, int pad_top, int H, int W, const float* lut,
+                               ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream) {
+    PPMS_REQUIRE(lut, "%s: null table pointer", who);
+    PPMS_REQUIRE(N > 0 && H0 > 0 && W0 > 0 && H > 0 && W > 0, "%s: N = %d, H0 = %d, W0 = %d, H = %d, W = %d must be positive", who, N, H0, W0, H, W);
+    PPMS_REQUIRE(H % 4 == 0 && W % 4 == 0, "%s: H = %d, W = %d must be multiples of 4", who, H, W);
     PPMS_REQUIRE(pad_left >= 0 && pad_top >= 0 && (int64_t)pad_top + H0 <= H && (int64_t)pad_left + W0 <= W,
-                 "video_ingest_u8: pad_left = %d, pad_top = %d with a %d x %d source do not fit the %d x %d padded image", pad_left, pad_top, H0, W0, H, W);
-    PPMS_REQUIRE(frame_stride >= (int64_t)3 * H0 * W0, "video_ingest_u8: frame_stride = %lld is less than a frame's 3 * H0 * W0 bytes", (long long)frame_stride);
-    PPMS_REQUIRE(dst_fnet.hi || dst_cnet.hi, "video_ingest_u8: both destinations skipped");
+                 "%s: pad_left = %d, pad_top = %d with a %d x %d source do not fit the %d x %d padded image", who, pad_left, pad_top, H0, W0, H, W);
+    PPMS_REQUIRE(dst_fnet.hi || dst_cnet.hi, "%s: both destinations skipped", who);
     const ppms_sp* dsts[2] = {&dst_fnet, &dst_cnet};
     int64_t threads[2] = {0, 0};
     for (int s = 0; s < 2; ++s) {
@@ -590,14 +620,58 @@ extern "C" int ppms_video_ingest_u8(const uint8_t* left, const uint8_t* right, i
         if (!d.hi) continue;                                               // skipped
         const int k = s == 0 ? 2 : 4;
         PPMS_REQUIRE(d.lo && d.c >= k * k * 3 && d.c % 8 == 0 && d.ld % 8 == 0 && d.ld >= d.c && (((uintptr_t)d.hi | (uintptr_t)d.lo) & 15) == 0,
-                     "video_ingest_u8: the k = %d destination view needs >= %d channels, multiples of 8, 16-B aligned", k, k * k * 3);
+                     "%s: the k = %d destination view needs >= %d channels, multiples of 8, 16-B aligned", who, k, k * k * 3);
         threads[s] = (int64_t)(s == 0 ? 2 : 1) * N * (H / k) * (W / k) * (d.c / 8);
     }
     const int64_t total = threads[0] + threads[1];
-    PPMS_REQUIRE((total + 255) / 256 <= 0x7fffffff, "video_ingest_u8: %lld threads exceed one grid", (long long)total);
-    hipLaunchKernelGGL(video_ingest_u8_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, left, right, frame_stride, N, H0, W0, pad_left,
-                       pad_top, H, W, lut, dst_fnet, dst_cnet, threads[0], total);
-    return ppms_check_launch("video_ingest_u8");
+    PPMS_REQUIRE((total + 255) / 256 <= 0x7fffffff, "%s: %lld threads exceed one grid", who, (long long)total);
+    hipLaunchKernelGGL(video_ingest_kernel<Source>, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, source, N, H0, W0, pad_left, pad_top, H, W,
+                       lut, dst_fnet, dst_cnet, threads[0], total);
+    return ppms_check_launch(who);
+}
+
+extern "C" int ppms_video_ingest_u8(const uint8_t* left, const uint8_t* right, int64_t frame_stride, int N, int H0, int W0, int pad_left, int pad_top, int H,
+                                    int W, const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream) {
+    PPMS_REQUIRE(left && right, "video_ingest_u8: null source pointer");
+    PPMS_REQUIRE(frame_stride >= (int64_t)3 * H0 * W0, "video_ingest_u8: frame_stride = %lld is less than a frame's 3 * H0 * W0 bytes", (long long)frame_stride);
+    return video_ingest_launch("video_ingest_u8", rgb_planes_source{left, right, frame_stride, N, H0, W0}, N, H0, W0, pad_left, pad_top, H, W, lut, dst_fnet,
+                               dst_cnet, stream);
+}
+
+extern "C" int ppms_yuv_struct_sizes(int* view, int* matrix) {
+    if (view) *view = (int)sizeof(ppms_yuv_view);
+    if (matrix) *matrix = (int)sizeof(ppms_yuv_matrix);
+    return PPMS_OK;
+}
+
+extern "C" int ppms_video_ingest_yuv420(const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m, int N, int H0, int W0, int pad_left,
+                                        int pad_top, int H, int W, const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream) {
+    PPMS_REQUIRE(left && right && m && lut, "video_ingest_yuv420: null view, matrix or table pointer");
+    PPMS_REQUIRE(N > 0 && H0 > 0 && W0 > 0, "video_ingest_yuv420: N = %d, H0 = %d, W0 = %d must be positive", N, H0, W0);
+    const int Hc = (H0 + 1) / 2, Wc = (W0 + 1) / 2;                        // chroma planes: ceil(H0 / 2) x ceil(W0 / 2)
+    const ppms_yuv_view* views[2] = {left, right};
+    for (int s = 0; s < 2; ++s) {
+        const ppms_yuv_view& v = *views[s];
+        const char* side = s == 0 ? "left" : "right";
+        PPMS_REQUIRE(v.y && v.u && v.v, "video_ingest_yuv420: null plane pointer in the %s view", side);
+        PPMS_REQUIRE(v.step_c == 1 || v.step_c == 2, "video_ingest_yuv420: %s step_c = %d must be 1 (planar) or 2 (interleaved)", side, v.step_c);
+        PPMS_REQUIRE(v.reserved == 0, "video_ingest_yuv420: %s view: reserved = %d must be 0", side, v.reserved);
+        const int64_t row_c = (int64_t)v.step_c * (Wc - 1) + 1;            // bytes from a chroma row's first sample to its last
+        PPMS_REQUIRE(v.pitch_y >= W0, "video_ingest_yuv420: %s pitch_y = %d is less than W0 = %d", side, v.pitch_y, W0);
+        PPMS_REQUIRE(v.pitch_c >= row_c, "video_ingest_yuv420: %s pitch_c = %d is less than a chroma row's %lld bytes", side, v.pitch_c, (long long)row_c);
+        PPMS_REQUIRE(v.frame_stride_y >= (int64_t)(H0 - 1) * v.pitch_y + W0, "video_ingest_yuv420: %s frame_stride_y = %lld is less than a luma plane", side,
+                     (long long)v.frame_stride_y);
+        PPMS_REQUIRE(v.frame_stride_c >= (int64_t)(Hc - 1) * v.pitch_c + row_c, "video_ingest_yuv420: %s frame_stride_c = %lld is less than a chroma plane",
+                     side, (long long)v.frame_stride_c);
+    }
+    PPMS_REQUIRE(m->shift >= 8 && m->shift <= 20, "video_ingest_yuv420: shift = %d must lie in [8, 20]", m->shift);
+    PPMS_REQUIRE(m->reserved == 0, "video_ingest_yuv420: matrix: reserved = %d must be 0", m->reserved);
+    // coefficients below 4.0 keep every sum of the conversion inside 32 bits: 2^22 (255 + 128 + 128) + 2^19 < 2^31 at shift = 20
+    const int32_t lim = 4 << m->shift;
+    PPMS_REQUIRE(m->y_off >= 0 && m->y_off <= 255 && m->cy >= 0 && m->cy < lim && m->crv >= 0 && m->crv < lim && m->cgu >= 0 && m->cgu < lim && m->cgv >= 0 &&
+                     m->cgv < lim && m->cbu >= 0 && m->cbu < lim,
+                 "video_ingest_yuv420: y_off must lie in [0, 255] and every coefficient in [0, 4 << shift)");
+    return video_ingest_launch("video_ingest_yuv420", yuv420_source{*left, *right, *m, N}, N, H0, W0, pad_left, pad_top, H, W, lut, dst_fnet, dst_cnet, stream);
 }
 
 extern "C" int ppms_sp_s2d(ppms_sp src, ppms_sp dst, int N, int H, int W, void* stream) {

@@ -465,6 +465,191 @@ class _ByteFrames:
         L.check(L.load().ppms_video_ingest_u8(self.left.data_ptr(), self.right.data_ptr(), self.frame_stride, self.n, self.h0, self.w0, self.pad_left,
                                               self.pad_top, h, w, byte_lut(self.left.device).data_ptr(), dst_fnet, dst_cnet, L.stream_ptr()))
 
+    def held(self):
+        """The tensors the launch reads (for record_stream)."""
+        return self.left, self.right
+
+
+_YUV_STANDARDS = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}       # (Kr, Kb)
+
+
+def yuv_matrix(standard: str = "bt709", full_range: bool = False, shift: int = 14) -> L.YUVMatrix:
+    """The fixed-point YCbCr -> RGB conversion ppms_video_ingest_yuv420 applies (include/ppms.h), as its ``ppms_yuv_matrix``: Python
+    ``round()`` of the double-precision coefficients times 2^shift.  Limited range: Y in [16, 235], chroma in [16, 240]."""
+    if standard not in _YUV_STANDARDS:
+        raise ValueError(f"yuv_matrix: standard {standard!r}; one of {sorted(_YUV_STANDARDS)}")
+    if not 8 <= shift <= 20:
+        raise ValueError(f"yuv_matrix: shift = {shift} must lie in [8, 20]")
+    kr, kb = _YUV_STANDARDS[standard]
+    kg = 1.0 - kr - kb
+    sy, sc = (1.0, 1.0) if full_range else (255.0 / 219.0, 255.0 / 224.0)
+    one = float(1 << shift)
+    return L.YUVMatrix(y_off=0 if full_range else 16, cy=round(sy * one), crv=round(sc * 2.0 * (1.0 - kr) * one),
+                       cgu=round(sc * 2.0 * kb * (1.0 - kb) / kg * one), cgv=round(sc * 2.0 * kr * (1.0 - kr) / kg * one),
+                       cbu=round(sc * 2.0 * (1.0 - kb) * one), shift=shift, reserved=0)
+
+
+class YUVFrames:
+    """One view's N decoded 8-bit YUV 4:2:0 frames, as a decoder leaves them: ``y`` uint8 (N, H0, W0), ``u`` / ``v`` uint8
+    (N, ceil(H0 / 2), ceil(W0 / 2)).  Each may be a strided VIEW of a decoder surface -- a pitched plane, the two halves of an interleaved
+    UV plane (``nv12``), one half of a frame that packs both views (``split_side_by_side`` / ``split_top_bottom``): the class reads
+    ``data_ptr()`` and ``stride()`` and never copies.  ``y`` needs last-dimension stride 1; ``u`` and ``v`` equal strides with
+    last-dimension stride 1 (planar: I420 / yuv420p) or 2 (interleaved: NV12); anything else raises ValueError.  Luma pixel (y, x) takes
+    chroma sample (y >> 1, x >> 1); ``standard`` ("bt709" / "bt601") and ``full_range`` choose ``yuv_matrix``; ``to_rgb_u8`` is the
+    definition of the RGB bytes.  Not covered: 10-bit surfaces (P010), 4:2:2 and 4:4:4, interpolated chroma siting, b > 1."""
+
+    def __init__(self, y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, standard: str = "bt709", full_range: bool = False):
+        for name, t in (("y", y), ("u", u), ("v", v)):
+            if not torch.is_tensor(t) or t.dtype != torch.uint8 or t.dim() != 3:
+                raise ValueError(f"YUVFrames: {name} must be a uint8 tensor (N, rows, columns)")
+        n, h0, w0 = y.shape
+        hc, wc = (h0 + 1) // 2, (w0 + 1) // 2
+        if n < 1 or h0 < 1 or w0 < 1:
+            raise ValueError(f"YUVFrames: empty y plane {tuple(y.shape)}")
+        if tuple(u.shape) != (n, hc, wc) or tuple(v.shape) != (n, hc, wc):
+            raise ValueError(f"YUVFrames: y {tuple(y.shape)} needs u and v of {(n, hc, wc)}, got {tuple(u.shape)} and {tuple(v.shape)}")
+        if u.device != y.device or v.device != y.device:
+            raise ValueError("YUVFrames: y, u and v must be on one device")
+        if w0 > 1 and y.stride(2) != 1:
+            raise ValueError(f"YUVFrames: y has last-dimension stride {y.stride(2)}; luma samples must be adjacent bytes")
+        step = u.stride(2) if wc > 1 else 1                                # (a one-column chroma plane never takes a step)
+        if u.stride() != v.stride():
+            raise ValueError(f"YUVFrames: u and v must have equal strides, got {u.stride()} and {v.stride()}")
+        if step not in (1, 2):
+            raise ValueError(f"YUVFrames: chroma last-dimension stride {step}; 1 (planar) or 2 (interleaved) expected")
+        # a size-1 dimension's stride is arbitrary: the smallest the kernel accepts stands in for it
+        self.pitch_y = y.stride(1) if h0 > 1 else w0
+        self.pitch_c = u.stride(1) if hc > 1 else step * (wc - 1) + 1
+        self.step_c = step
+        self.frame_stride_y = y.stride(0) if n > 1 else (h0 - 1) * self.pitch_y + w0
+        self.frame_stride_c = u.stride(0) if n > 1 else (hc - 1) * self.pitch_c + step * (wc - 1) + 1
+        if (self.pitch_y < w0 or self.pitch_c < step * (wc - 1) + 1 or self.frame_stride_y < (h0 - 1) * self.pitch_y + w0
+                or self.frame_stride_c < (hc - 1) * self.pitch_c + step * (wc - 1) + 1):
+            raise ValueError(f"YUVFrames: rows or frames overlap (y strides {y.stride()}, chroma strides {u.stride()})")
+        yuv_matrix(standard)                                               # (refuses an unknown standard here)
+        self.y, self.u, self.v, self.standard, self.full_range = y, u, v, standard, bool(full_range)
+        self.n, self.height, self.width = n, h0, w0
+
+    @classmethod
+    def nv12(cls, y: torch.Tensor, uv: torch.Tensor, standard: str = "bt709", full_range: bool = False) -> "YUVFrames":
+        """NV12: ``uv`` uint8 (N, ceil(H0 / 2), ceil(W0 / 2), 2), U first -- a hardware decoder's surface."""
+        if not torch.is_tensor(uv) or uv.dim() != 4 or uv.shape[-1] != 2:
+            raise ValueError("YUVFrames.nv12: uv must be (N, rows, columns, 2)")
+        return cls(y, uv[..., 0], uv[..., 1], standard, full_range)
+
+    @classmethod
+    def i420(cls, y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, standard: str = "bt709", full_range: bool = False) -> "YUVFrames":
+        """I420 / yuv420p: three planes -- a software decoder's frame."""
+        return cls(y, u, v, standard, full_range)
+
+    def __len__(self) -> int:
+        return self.n
+
+    @property
+    def device(self) -> torch.device:
+        return self.y.device
+
+    def _like(self, y, u, v) -> "YUVFrames":
+        return YUVFrames(y, u, v, self.standard, self.full_range)
+
+    def __getitem__(self, frames: slice) -> "YUVFrames":
+        if not isinstance(frames, slice):
+            raise TypeError("YUVFrames: index with a slice of frames")
+        return self._like(self.y[frames], self.u[frames], self.v[frames])
+
+    def split_side_by_side(self):
+        """(left, right): the two halves of frames that pack both views side by side; views, no copy.  The packed width must be even --
+        and each half's too, or the right half's chroma would start between two samples."""
+        w = self.width
+        if w % 2 or (w // 2) % 2:
+            raise ValueError(f"YUVFrames.split_side_by_side: a packed width of {w} does not split into two views with whole chroma samples")
+        h, q = w // 2, w // 4
+        return (self._like(self.y[:, :, :h], self.u[:, :, :q], self.v[:, :, :q]), self._like(self.y[:, :, h:], self.u[:, :, q:], self.v[:, :, q:]))
+
+    def split_top_bottom(self):
+        """(left, right) = (top, bottom) halves of frames that pack both views one above the other; views, no copy (even halves, as above)."""
+        ht = self.height
+        if ht % 2 or (ht // 2) % 2:
+            raise ValueError(f"YUVFrames.split_top_bottom: a packed height of {ht} does not split into two views with whole chroma rows")
+        h, q = ht // 2, ht // 4
+        return (self._like(self.y[:, :h], self.u[:, :q], self.v[:, :q]), self._like(self.y[:, h:], self.u[:, q:], self.v[:, q:]))
+
+    def to(self, device) -> "YUVFrames":
+        """These frames on ``device``: the planes' own bytes are copied (1.5 per pixel; an interleaved UV plane as one block) into dense
+        planes; frames already there are returned as they are."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if self.device == device:
+            return self
+        y = self.y.to(device)
+        if self.step_c == 2 and self.v.data_ptr() == self.u.data_ptr() + 1:
+            uv = torch.as_strided(self.u, (*self.u.shape, 2), (*self.u.stride(), 1)).to(device)
+            return self._like(y, uv[..., 0], uv[..., 1])
+        return self._like(y, self.u.to(device), self.v.to(device))
+
+    def matrix(self) -> L.YUVMatrix:
+        return yuv_matrix(self.standard, self.full_range)
+
+    def view_struct(self) -> L.YUVView:
+        """The ``ppms_yuv_view`` of these frames."""
+        return L.YUVView(self.y.data_ptr(), self.u.data_ptr(), self.v.data_ptr(), self.frame_stride_y, self.frame_stride_c, self.pitch_y, self.pitch_c,
+                         self.step_c, 0)
+
+    def to_rgb_u8(self) -> torch.Tensor:
+        """uint8 (N, 3, H0, W0) on the same device: the conversion of include/ppms.h in torch integer ops -- what the feature means by the
+        RGB bytes of these frames (the kernel's operands are ppms_video_ingest_u8's on them), and the path where the kernel cannot be used."""
+        m = self.matrix()
+        rows = torch.arange(self.height, device=self.device) >> 1
+        cols = torch.arange(self.width, device=self.device) >> 1
+        d = self.y.to(torch.int32) - m.y_off
+        e, f = (c.to(torch.int32)[:, rows][:, :, cols] - 128 for c in (self.u, self.v))
+        r = 1 << (m.shift - 1)
+        rgb = torch.stack([m.cy * d + m.crv * f + r, m.cy * d - m.cgu * e - m.cgv * f + r, m.cy * d + m.cbu * e + r], dim=1)
+        return (rgb >> m.shift).clamp_(0, 255).to(torch.uint8)
+
+
+class YUVStereoVideo:
+    """Both views of a decoded 4:2:0 video -- what ``batch_dict["stereo_video"]`` of ``forward_batch_test`` may be instead of a tensor:
+    two ``YUVFrames`` of one size, frame count, device and colour description.  ``len()``, slicing by frame range, ``to(device)``."""
+
+    def __init__(self, left: YUVFrames, right: YUVFrames):
+        if not isinstance(left, YUVFrames) or not isinstance(right, YUVFrames):
+            raise TypeError("YUVStereoVideo: two YUVFrames expected")
+        if (left.n, left.height, left.width) != (right.n, right.height, right.width):
+            raise ValueError(f"YUVStereoVideo: the views differ: {(left.n, left.height, left.width)} and {(right.n, right.height, right.width)}")
+        if (left.standard, left.full_range) != (right.standard, right.full_range) or left.device != right.device:
+            raise ValueError("YUVStereoVideo: both views need one standard, one range and one device")
+        self.left, self.right = left, right
+        self.height, self.width = left.height, left.width
+
+    def __len__(self) -> int:
+        return self.left.n
+
+    def __getitem__(self, frames: slice) -> "YUVStereoVideo":
+        return YUVStereoVideo(self.left[frames], self.right[frames])
+
+    def to(self, device) -> "YUVStereoVideo":
+        """The selected frames' planes on ``device`` (1.5 bytes per pixel and view)."""
+        return YUVStereoVideo(self.left.to(device), self.right.to(device))
+
+
+class _YUVPlanes:
+    """``_ByteFrames`` for a YUVStereoVideo on the device: ppms_video_ingest_yuv420 converts, pads and lays out both views in one launch."""
+
+    def __init__(self, video: YUVStereoVideo, pad_left: int = 0, pad_top: int = 0):
+        self.video, self.pad_left, self.pad_top = video, int(pad_left), int(pad_top)
+
+    def ingest(self, dst_fnet: L.SP, dst_cnet: L.SP, h: int, w: int) -> None:
+        v = self.video
+        left, right, m = v.left.view_struct(), v.right.view_struct(), v.left.matrix()      # host structs: read before the call returns
+        L.check(L.load().ppms_video_ingest_yuv420(left, right, m, len(v), v.height, v.width, self.pad_left, self.pad_top, h, w,
+                                                  byte_lut(v.left.device).data_ptr(), dst_fnet, dst_cnet, L.stream_ptr()))
+
+    def held(self):
+        v = self.video
+        return v.left.y, v.left.u, v.left.v, v.right.y, v.right.u, v.right.v
+
 
 class PPMStereo(PPMStereoHotPath):
     """``models/core/ppmstereo.py:PPMStereo`` from the encoder outputs on: same constructor arguments, ``forward`` (:601-804)
@@ -602,6 +787,8 @@ class PPMStereo(PPMStereoHotPath):
         cascade; b > 1: the reference's glue around the batched forward_update_block).  Float images as in the reference, or both uint8:
         with this package's encoders the bytes go through ONE kernel (ppms_video_ingest_u8) to the operands of the first convolutions --
         the same bits as ``forward(image1.float(), image2.float())``; with other encoder callables they are converted to float on the device.
+        Or two ``YUVFrames`` on the device (decoded 4:2:0 frames: NV12 / I420): b = 1, T = their frame count; ONE kernel
+        (ppms_video_ingest_yuv420) converts them and writes the same operands -- the bits of ``forward`` on their ``to_rgb_u8()``.
         test_mode: (flow_up, uncertainty), each (b, T, 1, H, W); else (predictions (D, b, T, 1, H, W), uncertainties).
         pipeline (test_mode only): a ``ClipPipeline`` -- the result is valid once ``pipeline.wait()`` has been called.
         diagnostics (b = 1): a dict that receives ``["attn_redo"]``, the per-scale fix-up accounting of the memory read-out (see ``cascade``)."""
@@ -609,6 +796,8 @@ class PPMStereo(PPMStereoHotPath):
             raise NotImplementedError("flow_init: the reference's own path for it reads undefined state (ppmstereo.py:691-693, 763)")
         if self.fnet is None or self.cnet is None:
             raise RuntimeError("PPMStereo.forward needs the encoders: pass fnet= / cnet= (outside the hot path, SURVEY.md section 8 f3-f5)")
+        if isinstance(image1, YUVFrames) or isinstance(image2, YUVFrames):
+            return self._forward_yuv(image1, image2, iters, test_mode, pipeline, diagnostics)
         if torch.is_tensor(image1) and torch.is_tensor(image2) and (image1.dtype == torch.uint8) != (image2.dtype == torch.uint8):
             raise TypeError(f"PPMStereo.forward: image1 is {image1.dtype} and image2 is {image2.dtype}; both views must be uint8 or both floating point")
         b, T, c, h, w = image1.shape
@@ -624,6 +813,18 @@ class PPMStereo(PPMStereoHotPath):
                 images = (image1.float(), image2.float())
         return self._forward_images(images, b, T, h, w, image1.device, iters, test_mode, pipeline, diagnostics)
 
+    def _forward_yuv(self, image1, image2, iters: int, test_mode: bool, pipeline, diagnostics):
+        """``forward`` on two ``YUVFrames`` on the device: b = 1, T = their frame count, the frame size as it is."""
+        if not (isinstance(image1, YUVFrames) and isinstance(image2, YUVFrames)):
+            raise TypeError(f"PPMStereo.forward: image1 is {type(image1).__name__} and image2 is {type(image2).__name__}; both views must be YUVFrames or both tensors")
+        video = YUVStereoVideo(image1, image2)
+        L.require_gpu(image1.y, image2.y)
+        if self._hip_encoders():
+            return self._forward_images(_YUVPlanes(video), 1, len(video), video.height, video.width, image1.device, iters, test_mode, pipeline, diagnostics)
+        # encoder callables of the caller: they get what they get for a float video
+        return self.forward(image1.to_rgb_u8().float()[None], image2.to_rgb_u8().float()[None], iters=iters, test_mode=test_mode, pipeline=pipeline,
+                            diagnostics=diagnostics)
+
     def _hip_encoders(self) -> bool:
         """Both encoders are this package's: their plans take the first-layer operands ppms_video_ingest_u8 writes."""
         from .cnet import Feature
@@ -631,20 +832,20 @@ class PPMStereo(PPMStereoHotPath):
         return isinstance(self.fnet, BasicEncoder) and isinstance(self.cnet, Feature)
 
     def _forward_images(self, images, b: int, T: int, h: int, w: int, dev, iters: int, test_mode: bool, pipeline, diagnostics):
-        """``forward`` behind its argument checks.  images: the two float videos (b, T, 3, h, w), or ``_ByteFrames`` holding b * T uint8 frames
-        per view that ppms_video_ingest_u8 pads to h x w (``forward_batch_test`` hands a window over unpadded)."""
+        """``forward`` behind its argument checks.  images: the two float videos (b, T, 3, h, w), or ``_ByteFrames`` / ``_YUVPlanes`` holding
+        b * T decoded frames per view that one ingest kernel pads to h x w (``forward_batch_test`` hands a window over unpadded)."""
         with torch.cuda.device(dev):
             # fnet (both views) and cnet (left view) depend on the images only and are chains of small launches that leave most of the chip
             # idle: cnet runs on a second stream beside fnet (whole call -3.5 ms at config 2); its outputs are handed to the caller's
             # stream with an event + record_stream
             cur = torch.cuda.current_stream(dev)
-            if isinstance(images, _ByteFrames):
+            if isinstance(images, (_ByteFrames, _YUVPlanes)):
                 # bytes -> the operands of fnet's conv1 and cnet's stem, one launch on the caller's stream (ordered before the side stream's wait)
                 fplan, cplan = self.fnet.plan(2 * b * T, h, w, dev), self.cnet.plan(b * T, h, w, dev)
                 images.ingest(fplan.s0_view(), cplan.s0_view(), h, w)
                 run_fnet = lambda: torch.split(fplan.run_filled(), b * T, dim=0)
                 run_cnet = cplan.run_filled
-                held = (images.left, images.right)
+                held = images.held()
             else:
                 image1, image2 = images
                 c = image1.shape[2]
@@ -694,6 +895,9 @@ class PPMStereo(PPMStereoHotPath):
         per window: InputPadder(divis_by=32), one host->device copy, forward(test_mode=True), unpad, one device->host copy;
         a uint8 video (host or device) is copied as bytes -- a quarter of the float video's -- and, with this package's encoders, padded and
         normalised inside ppms_video_ingest_u8: the same bits as for ``stereo_video.float()``;
+        a ``YUVStereoVideo`` (decoded 8-bit 4:2:0 frames, NV12 or I420, host or device) is copied per window as its planes -- 1.5 bytes per
+        pixel and view -- and converted, padded and normalised inside ppms_video_ingest_yuv420: the bits of the uint8 video of its
+        ``to_rgb_u8()`` frames (10-bit formats, 4:2:2 / 4:4:4, interpolated chroma siting and b > 1 are not covered);
         windows of ``kernel_size`` frames every ``kernel_size // 2``, centre frames kept (:296-307).  Windows whose output the
         reference computes and then drops are not run.  Returns {"disparity", "uncertainties"}: (N, 1, H, W) CPU tensors.
         shard_ranks: under torch.distributed the windows are dealt round-robin over the ranks (independent units, no data-path
@@ -720,7 +924,7 @@ class PPMStereo(PPMStereoHotPath):
                 d, u = padder.unpad(d[0]), padder.unpad(u[0])               # (T, 1, H0, W0)
                 mine_d.append((firsts[wi], d[keep_from:keep_to].abs()[:, :1]))
                 mine_u.append((firsts[wi], u[keep_from:keep_to].abs()[:, :1]))
-            H0, W0 = video.shape[-2:]
+            H0, W0 = (video.height, video.width) if isinstance(video, YUVStereoVideo) else video.shape[-2:]
             disp = D.gather_kept_frames(mine_d, num_ims, H0, W0)
             unc = D.gather_kept_frames(mine_u, num_ims, H0, W0)
             out = {"disparity": disp.cpu(), "uncertainties": unc.cpu()}
@@ -762,12 +966,20 @@ class PPMStereo(PPMStereoHotPath):
 
 
 def _window_forward(self, video, start: int, stop: int, dev, iters: int, pipe, diag):
-    """One window of forward_batch_test: frames [start, stop) of the (N, 2, 3, H0, W0) video -> (disparity, uncertainty) of the padded
+    """One window of forward_batch_test: frames [start, stop) of the (N, 2, 3, H0, W0) video or the YUVStereoVideo -> (disparity, uncertainty) of the padded
     window, each (1, T, 1, H, W), and the InputPadder that crops them back."""
     # host -> device: ONE copy of the window's contiguous (T, 2, 3, H, W) block; the two views are split and padded on the
     # device (slicing a view out on the host first costs a host-side copy of each view, padding there another one)
     win = video[start:stop].to(dev)
-    if win.dtype == torch.uint8:
+    if isinstance(win, YUVStereoVideo):
+        if self._hip_encoders():
+            # the planes stay as the decoder left them: ppms_video_ingest_yuv420 converts, and pads by clamping its source coordinate
+            padder = InputPadder((win.height, win.width), divis_by=32)
+            pad_left, pad_top, H, W = padder.geometry()
+            d, u = self._forward_images(_YUVPlanes(win, pad_left, pad_top), 1, len(win), H, W, dev, iters, True, pipe, diag)
+            return d, u, padder
+        win = torch.stack([win.left.to_rgb_u8(), win.right.to_rgb_u8()], dim=1).float()    # encoder callables of the caller: the float path
+    elif win.dtype == torch.uint8:
         if win.dim() != 5 or win.shape[1] != 2 or win.shape[2] != 3:
             raise ValueError(f"forward_batch_test: a uint8 stereo_video is (N, 2, 3, H, W), got {tuple(video.shape)}")
         if self._hip_encoders():
