@@ -231,6 +231,42 @@ int ppms_convex_upsample_3d(const float* flow_nhwc, const float* mask, int mask_
  * out = mul * interp(src). */
 int ppms_bilinear(const float* src, float* dst, int N, int C, int H, int W, int OH, int OW, int align_corners, float mul, void* stream);
 
+/* Quantised disparity / depth / confidence output, one launch: from the 1/4-scale engine's state after its last iteration to the caller's
+ * output planes -- what PPMStereo.forward_batch_test does after its last forward (ppmstereo.py:296-320: unpad, the kept frames, .abs()),
+ * plus the conversion every caller of a stereo model writes behind it.
+ * flow_up: fp32 (T, 2, H, W), the convex-upsampled flow; only channel 0 is read, in place (frame stride 2 H W).  unc: fp32 (T, H/4, W/4), the
+ * uncertainty head's output; the kernel upsamples it 4x itself with ppms_bilinear's align_corners = 0 expression (mul = 1): the same bits.
+ * Output pixel (f, y, x), f in [0, n_frames), y in [0, H0), x in [0, W0), reads source pixel (frame0 + f, y + pad_top, x + pad_left): the
+ * frame range a sliding window keeps and the crop of InputPadder.unpad.  With d = |flow_up[., 0, ., .]| and u = |bilinear4(unc)|, every
+ * operation below ONE fp32 operation rounded to nearest even (rint: ties to even), so that fp32 torch ops on the same inputs give the same bits:
+ *   disparity plane   F32: d.   F16: d rounded to nearest even.   U16: min(65535, rint(d * disp_scale)), NaN -> 0  (KITTI: disp_scale = 256).
+ *   depth plane       Z = fb / d, a correctly rounded fp32 division; fb = focal length in pixels * baseline, one fp32 product made by the caller.
+ *                     The pixel is INVALID when d < min_disp or d is NaN: F32 / F16 store +inf, U16 stores 0.
+ *                     Otherwise F32: Z.   F16: Z rounded to nearest even.   U16: min(65535, rint(Z * depth_scale))  (millimetres: baseline in
+ *                     metres and depth_scale = 1000) -- the division and the product are rounded separately.
+ *   uncertainty plane F32: u.   U8: min(255, rint(u * 255)), NaN -> 0  (u is a sigmoid output in [0, 1]).
+ * A plane: device pointer to element (0, 0, 0), bytes from frame to frame and from row to row (a pitch may exceed the row: the bytes between
+ * rows are not written; pointer, pitch and frame_stride multiples of the element size), its format.  ptr == NULL skips the plane.
+ * `out` is HOST memory, read before the call returns.  Refused with PPMS_EINVAL before any launch: no plane; a format unknown or not listed for
+ * its plane; a crop outside H x W, or H, W not multiples of 4; n_frames <= 0 or frame0 + n_frames > T; a pitch shorter than its row (or, with
+ * n_frames > 1, a frame_stride shorter than a plane); a depth plane with fb <= 0, depth_scale <= 0 or a non-finite min_disp; a U16 disparity with
+ * disp_scale <= 0. */
+enum { PPMS_FMT_F32 = 0, PPMS_FMT_F16 = 1, PPMS_FMT_U16 = 2, PPMS_FMT_U8 = 3 };
+typedef struct ppms_egress_plane {
+    void* ptr;                        /* element (0, 0, 0) of the output; NULL: the plane is skipped */
+    int64_t frame_stride;             /* bytes from frame f to frame f + 1 */
+    int64_t pitch;                    /* bytes from row to row */
+    int32_t format;                   /* PPMS_FMT_* */
+    int32_t reserved;                 /* 0 */
+} ppms_egress_plane;
+typedef struct ppms_egress {
+    ppms_egress_plane disparity, depth, uncertainty;
+    float disp_scale, fb, depth_scale, min_disp;
+} ppms_egress;
+int ppms_disparity_egress(const float* flow_up, const float* unc, int T, int H, int W, int frame0, int n_frames, int pad_left, int pad_top,
+                          int H0, int W0, const ppms_egress* out, void* stream);
+int ppms_egress_struct_size(void);    /* sizeof(ppms_egress) (112): lets a binding verify its layout */
+
 /* Scale-to-scale hand-over of the cascade without leaving the SP format (ppmstereo.py:726-732, 763-767): per frame,
  * dst = a * dst + b * interp(src), interp = F.interpolate(mode="bilinear", align_corners=True) from HxW to OHxOW.
  * src, dst: SP views with the same channel count (multiple of 8). */

@@ -71,6 +71,20 @@ class YUVMatrix(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("y_off", "cy", "crv", "cgu", "cgv", "cbu", "shift", "reserved")]
 
 
+FMT_F32, FMT_F16, FMT_U16, FMT_U8 = range(4)
+
+
+class EgressPlane(C.Structure):
+    """ppms_egress_plane: one output plane of ppms_disparity_egress (device pointer, byte strides, FMT_*)."""
+    _fields_ = [("ptr", c_void_p), ("frame_stride", c_int64), ("pitch", c_int64), ("format", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Egress(C.Structure):
+    """ppms_egress: the planes and the four conversion constants."""
+    _fields_ = [("disparity", EgressPlane), ("depth", EgressPlane), ("uncertainty", EgressPlane),
+                ("disp_scale", c_float), ("fb", c_float), ("depth_scale", c_float), ("min_disp", c_float)]
+
+
 _SIGS = {
     "ppms_version": (c_int, []),
     "ppms_last_error": (C.c_char_p, []),
@@ -109,6 +123,8 @@ _SIGS = {
     "ppms_convex_upsample": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ppms_convex_upsample_3d": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ppms_bilinear": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "ppms_disparity_egress": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, C.POINTER(Egress), c_void_p]),
+    "ppms_egress_struct_size": (c_int, []),
     "ppms_sp_resize_blend": (c_int, [SP, SP, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p]),
     "ppms_avgpool": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ppms_axpby": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_float, c_int64, c_int64, c_void_p]),
@@ -176,6 +192,8 @@ def load() -> C.CDLL:
     lib.ppms_yuv_struct_sizes(C.byref(a), C.byref(b))
     if (a.value, b.value) != (C.sizeof(YUVView), C.sizeof(YUVMatrix)):
         raise RuntimeError("ppmstereo_amd: ctypes layout of ppms_yuv_view / ppms_yuv_matrix differs from include/ppms.h")
+    if lib.ppms_egress_struct_size() != C.sizeof(Egress):
+        raise RuntimeError("ppmstereo_amd: ctypes layout of ppms_egress differs from include/ppms.h")
     if lib.ppms_pwchain_param_bytes() != C.sizeof(ChainParams):
         raise RuntimeError("ppmstereo_amd: ChainParams layout differs from pwchain.hip")
     _lib = lib

@@ -555,6 +555,179 @@ extern "C" int ppms_bilinear(const float* src, float* dst, int N, int C, int H, 
     return ppms_check_launch("bilinear");
 }
 
+// ------------------------------------------------------------------------------------------------ disparity egress
+// The 1/4-scale engine's state after its last iteration -> the caller's output planes, one launch (include/ppms.h: the formulas):
+// crop (InputPadder.unpad), frame range, |flow_up[:, 0]|, the 4x bilinear upsampling of the uncertainty, depth = fb / d and the
+// conversions to the planes' formats.  HBM bound: one thread = a run of EG_RUN consecutive x of one output row; the run is loaded
+// and stored 16 bytes at a time (8 for a run of bytes) where its address allows it, element by element at row ends and on
+// rows that start unaligned.  Every offset is 64-bit.
+constexpr int EG_RUN = 8;
+// bilinear_kernel's expression for output pixel (oy, ox) of one H x W source plane `s`, align_corners = 0, restated (every operation is one
+// fp32 operation in the same order, and the build contracts nothing: the same bits as ppms_bilinear with mul = 1).  bilinear_kernel does not
+// call it: routed through this function its instructions come out in another order, and its generated code is kept as it is.
+__device__ __forceinline__ float bilinear_tap(const float* __restrict__ s, int H, int W, float sh, float sw, int oy, int ox) {
+    const float fy = fmaxf(sh * (oy + 0.5f) - 0.5f, 0.0f);
+    const float fx = fmaxf(sw * (ox + 0.5f) - 0.5f, 0.0f);
+    const int y0 = (int)fy, x0 = (int)fx;
+    const int y1 = y0 + ((y0 < H - 1) ? 1 : 0), x1 = x0 + ((x0 < W - 1) ? 1 : 0);
+    const float ly = fy - y0, lx = fx - x0;
+    const float hy = 1.0f - ly, hx = 1.0f - lx;
+    return hy * (hx * s[y0 * W + x0] + lx * s[y0 * W + x1]) + ly * (hx * s[y1 * W + x0] + lx * s[y1 * W + x1]);
+}
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+// min(top, rint(v)) for v >= 0 (a magnitude times a positive scale); NaN -> 0
+__device__ __forceinline__ unsigned egress_quant(float v, float top) {
+    const float r = rintf(v);
+    return r != r ? 0u : (unsigned)fminf(r, top);
+}
+template <class T>
+__device__ __forceinline__ void egress_store_run(const ppms_egress_plane& p, int64_t frame, int y, int x0, int n, const T (&v)[EG_RUN]) {
+    T* dst = (T*)((char*)p.ptr + frame * p.frame_stride + (int64_t)y * p.pitch) + x0;
+    constexpr int BYTES = (int)sizeof(T) * EG_RUN;                       // 8 (u8), 16 (u16, f16) or 32 (f32)
+    constexpr int CHUNK = BYTES < 16 ? BYTES : 16;
+    if (n == EG_RUN && ((uintptr_t)dst & (CHUNK - 1)) == 0) {
+        if constexpr (BYTES < 16) {
+            gst<u32x2>(dst, __builtin_bit_cast(u32x2, v));
+        } else {
+            struct chunks { u32x4 q[BYTES / 16]; };
+            const chunks c = __builtin_bit_cast(chunks, v);
+#pragma unroll
+            for (int i = 0; i < BYTES / 16; ++i) gstore16((char*)dst + 16 * i, c.q[i]);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < EG_RUN; ++j)
+            if (j < n) dst[j] = v[j];
+    }
+}
+__global__ __launch_bounds__(256) void disparity_egress_kernel(const float* __restrict__ flow_up, const float* __restrict__ unc, ppms_egress o,
+                                                                int H, int W, int frame0, int pad_left, int pad_top, int H0, int W0, float sh,
+                                                                float sw, int rpr, int64_t total) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int x0 = (int)(idx % rpr) * EG_RUN;
+    const int64_t row = idx / rpr;                                       // frame * H0 + y of the output
+    const int y = (int)(row % H0);
+    const int64_t frame = row / H0;
+    const int n = W0 - x0 < EG_RUN ? W0 - x0 : EG_RUN;                   // elements of this run inside the row
+    const int sy = y + pad_top, sx = x0 + pad_left;                      // the run's first pixel in the padded H x W frame
+    if (o.disparity.ptr || o.depth.ptr) {
+        const float* s = flow_up + ((frame0 + frame) * 2 * H + sy) * W + sx;        // channel 0 of (T, 2, H, W)
+        float d[EG_RUN];
+        if (n == EG_RUN && ((uintptr_t)s & 15) == 0) {
+            const f32x4 a = gld<f32x4>(s), b = gld<f32x4>(s + 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                d[j] = a[j];
+                d[4 + j] = b[j];
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < EG_RUN; ++j) d[j] = s[j < n ? j : n - 1];
+        }
+#pragma unroll
+        for (int j = 0; j < EG_RUN; ++j) d[j] = fabsf(d[j]);
+        if (o.disparity.ptr) {
+            if (o.disparity.format == PPMS_FMT_F32) {
+                egress_store_run(o.disparity, frame, y, x0, n, d);
+            } else if (o.disparity.format == PPMS_FMT_F16) {
+                _Float16 v[EG_RUN];
+#pragma unroll
+                for (int j = 0; j < EG_RUN; ++j) v[j] = (_Float16)d[j];
+                egress_store_run(o.disparity, frame, y, x0, n, v);
+            } else {
+                uint16_t v[EG_RUN];
+#pragma unroll
+                for (int j = 0; j < EG_RUN; ++j) v[j] = (uint16_t)egress_quant(d[j] * o.disp_scale, 65535.0f);
+                egress_store_run(o.disparity, frame, y, x0, n, v);
+            }
+        }
+        if (o.depth.ptr) {
+            float z[EG_RUN];
+            bool ok[EG_RUN];
+#pragma unroll
+            for (int j = 0; j < EG_RUN; ++j) {
+                ok[j] = d[j] >= o.min_disp;                              // false for NaN
+                z[j] = ok[j] ? __fdiv_rn(o.fb, d[j]) : INFINITY;
+            }
+            if (o.depth.format == PPMS_FMT_F32) {
+                egress_store_run(o.depth, frame, y, x0, n, z);
+            } else if (o.depth.format == PPMS_FMT_F16) {
+                _Float16 v[EG_RUN];
+#pragma unroll
+                for (int j = 0; j < EG_RUN; ++j) v[j] = (_Float16)z[j];
+                egress_store_run(o.depth, frame, y, x0, n, v);
+            } else {
+                uint16_t v[EG_RUN];
+#pragma unroll
+                for (int j = 0; j < EG_RUN; ++j) v[j] = ok[j] ? (uint16_t)egress_quant(z[j] * o.depth_scale, 65535.0f) : (uint16_t)0;
+                egress_store_run(o.depth, frame, y, x0, n, v);
+            }
+        }
+    }
+    if (o.uncertainty.ptr) {
+        const int h = H / 4, w = W / 4;
+        const float* s = unc + (frame0 + frame) * h * w;
+        float u[EG_RUN];
+#pragma unroll
+        for (int j = 0; j < EG_RUN; ++j) u[j] = fabsf(bilinear_tap(s, h, w, sh, sw, sy, sx + (j < n ? j : n - 1)));
+        if (o.uncertainty.format == PPMS_FMT_F32) {
+            egress_store_run(o.uncertainty, frame, y, x0, n, u);
+        } else {
+            uint8_t v[EG_RUN];
+#pragma unroll
+            for (int j = 0; j < EG_RUN; ++j) v[j] = (uint8_t)egress_quant(u[j] * 255.0f, 255.0f);
+            egress_store_run(o.uncertainty, frame, y, x0, n, v);
+        }
+    }
+}
+extern "C" int ppms_egress_struct_size(void) { return (int)sizeof(ppms_egress); }
+extern "C" int ppms_disparity_egress(const float* flow_up, const float* unc, int T, int H, int W, int frame0, int n_frames, int pad_left, int pad_top,
+                                     int H0, int W0, const ppms_egress* out, void* stream) {
+    PPMS_REQUIRE(out, "disparity_egress: null out struct");
+    const ppms_egress& o = *out;
+    PPMS_REQUIRE(o.disparity.ptr || o.depth.ptr || o.uncertainty.ptr, "disparity_egress: no plane: disparity, depth and uncertainty are all NULL");
+    PPMS_REQUIRE(T > 0 && H > 0 && W > 0 && H0 > 0 && W0 > 0, "disparity_egress: T = %d, H = %d, W = %d, H0 = %d, W0 = %d must be positive", T, H, W, H0, W0);
+    PPMS_REQUIRE(H % 4 == 0 && W % 4 == 0, "disparity_egress: H = %d, W = %d must be multiples of 4", H, W);
+    PPMS_REQUIRE(pad_left >= 0 && pad_top >= 0 && (int64_t)pad_top + H0 <= H && (int64_t)pad_left + W0 <= W,
+                 "disparity_egress: the crop pad_left = %d, pad_top = %d, H0 = %d, W0 = %d lies outside the %d x %d frame", pad_left, pad_top, H0, W0, H, W);
+    PPMS_REQUIRE(n_frames > 0, "disparity_egress: n_frames = %d must be positive", n_frames);
+    PPMS_REQUIRE(frame0 >= 0 && (int64_t)frame0 + n_frames <= T, "disparity_egress: frame0 = %d, n_frames = %d leave the T = %d frames", frame0, n_frames, T);
+    PPMS_REQUIRE(((o.disparity.ptr || o.depth.ptr) ? flow_up != nullptr : true) && (o.uncertainty.ptr ? unc != nullptr : true),
+                 "disparity_egress: null flow_up / unc source of a requested plane");
+    const struct { const ppms_egress_plane* p; const char* name; unsigned formats; } planes[3] = {
+        {&o.disparity, "disparity", 1u << PPMS_FMT_F32 | 1u << PPMS_FMT_F16 | 1u << PPMS_FMT_U16},
+        {&o.depth, "depth", 1u << PPMS_FMT_F32 | 1u << PPMS_FMT_F16 | 1u << PPMS_FMT_U16},
+        {&o.uncertainty, "uncertainty", 1u << PPMS_FMT_F32 | 1u << PPMS_FMT_U8}};
+    for (const auto& pl : planes) {
+        const ppms_egress_plane& p = *pl.p;
+        if (!p.ptr) continue;                                            // skipped
+        PPMS_REQUIRE(p.format >= 0 && p.format <= PPMS_FMT_U8 && (pl.formats >> p.format & 1u),
+                     "disparity_egress: %s.format = %d is not a format of that plane", pl.name, p.format);
+        PPMS_REQUIRE(p.reserved == 0, "disparity_egress: %s.reserved = %d must be 0", pl.name, p.reserved);
+        const int64_t esz = p.format == PPMS_FMT_F32 ? 4 : (p.format == PPMS_FMT_U8 ? 1 : 2), rowb = esz * W0;
+        PPMS_REQUIRE(p.pitch >= rowb, "disparity_egress: %s.pitch = %lld is less than a row's %lld bytes", pl.name, (long long)p.pitch, (long long)rowb);
+        PPMS_REQUIRE(n_frames == 1 || p.frame_stride >= (int64_t)(H0 - 1) * p.pitch + rowb,
+                     "disparity_egress: %s.frame_stride = %lld is less than a plane", pl.name, (long long)p.frame_stride);
+        PPMS_REQUIRE(((uintptr_t)p.ptr | (uintptr_t)p.pitch | (uintptr_t)p.frame_stride) % esz == 0,
+                     "disparity_egress: %s: pointer, pitch and frame_stride must be multiples of the %lld-byte element", pl.name, (long long)esz);
+    }
+    if (o.depth.ptr) {
+        PPMS_REQUIRE(o.fb > 0.0f && o.fb < INFINITY, "disparity_egress: a depth plane needs fb = %g > 0", (double)o.fb);
+        PPMS_REQUIRE(o.depth_scale > 0.0f && o.depth_scale < INFINITY, "disparity_egress: a depth plane needs depth_scale = %g > 0", (double)o.depth_scale);
+        PPMS_REQUIRE(o.min_disp > -INFINITY && o.min_disp < INFINITY, "disparity_egress: a depth plane needs a finite min_disp, got %g", (double)o.min_disp);
+    }
+    if (o.disparity.ptr && o.disparity.format == PPMS_FMT_U16)
+        PPMS_REQUIRE(o.disp_scale > 0.0f && o.disp_scale < INFINITY, "disparity_egress: a u16 disparity needs disp_scale = %g > 0", (double)o.disp_scale);
+    const int rpr = (W0 + EG_RUN - 1) / EG_RUN;                          // runs per output row
+    const int64_t total = (int64_t)n_frames * H0 * rpr;
+    PPMS_REQUIRE((total + 255) / 256 <= 0x7fffffff, "disparity_egress: %lld threads exceed one grid", (long long)total);
+    const float sh = (float)(H / 4) / (float)H, sw = (float)(W / 4) / (float)W;      // ppms_bilinear's scales for (H/4, W/4) -> (H, W): 0.25
+    hipLaunchKernelGGL(disparity_egress_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, flow_up, unc, o, H, W, frame0, pad_left,
+                       pad_top, H0, W0, sh, sw, rpr, total);
+    return ppms_check_launch("disparity_egress");
+}
+
 // Scale-to-scale hand-over of the cascade on SP (channel-last split-bf16) tensors, no NCHW round trip:
 // dst = a * dst + b * interp(src) with F.interpolate(mode="bilinear", align_corners=True) semantics per frame
 // (ppmstereo.py:726-732,763-767: hidden state x2, net = (net_s + interp(net_2s)) / 2).  One thread = one output pixel x 8 channels.

@@ -697,6 +697,14 @@ class ScaleEngine:
         self.hbm["convex_upsample"]()
         return self.FLOW_OUT
 
+    def egress(self, out: L.Egress, frame0: int, n_frames: int, pad_left: int, pad_top: int, h0: int, w0: int):
+        """ppms_disparity_egress on the current stream: the state the last iteration left -- FLOW_OUT (read in place, channel 0) and the
+        1/4-resolution UNC -- to the caller's planes: frames [frame0, frame0 + n_frames), the h0 x w0 crop at (pad_top, pad_left).  Valid
+        behind an iterate(need_up=True) of an unsharded engine at the 1/4 scale (full resolution = 4 h x 4 w)."""
+        if self.shard is not None:
+            raise NotImplementedError("ScaleEngine.egress: a frame-sharded engine holds a part of the window")
+        disparity_egress(self.FLOW_OUT, self.UNC.view(self.T, self.h, self.w), out, frame0, n_frames, pad_left, pad_top, h0, w0)
+
     def _prep_k(self):
         key, key_ld, sel, shat = self._prep_k_args
         L.check(self.lib.ppms_attn_prep_k(key, key_ld, self.PE.data_ptr(), sel, shat, self.KB.data_ptr(), self.T, self.ksel, self.n, self._s()))
@@ -731,3 +739,15 @@ def bilinear(x: torch.Tensor, size, align_corners: bool, mul: float = 1.0) -> to
     out = torch.empty(N, Cc, size[0], size[1], dtype=torch.float32, device=x.device)
     L.check(L.load().ppms_bilinear(x.data_ptr(), out.data_ptr(), N, Cc, H, W, size[0], size[1], int(align_corners), mul, L.stream_ptr()))
     return out
+
+
+def disparity_egress(flow_up: torch.Tensor, unc: torch.Tensor, out: L.Egress, frame0: int, n_frames: int, pad_left: int, pad_top: int, h0: int, w0: int):
+    """One ppms_disparity_egress launch on the current stream (include/ppms.h): flow_up fp32 (T, 2, H, W), unc fp32 (T, H/4, W/4), both
+    contiguous on the GPU; ``out``: the planes (device pointers, byte strides, formats) and conversion constants."""
+    L.require_gpu(flow_up, unc)
+    T, two, H, W = flow_up.shape
+    if (flow_up.dtype != torch.float32 or unc.dtype != torch.float32 or two != 2 or tuple(unc.shape) != (T, H // 4, W // 4)
+            or not flow_up.is_contiguous() or not unc.is_contiguous()):
+        raise ValueError(f"disparity_egress: contiguous fp32 flow_up (T, 2, H, W) and unc (T, H/4, W/4) expected, got {tuple(flow_up.shape)} and {tuple(unc.shape)}")
+    L.check(L.load().ppms_disparity_egress(flow_up.data_ptr(), unc.data_ptr(), T, H, W, frame0, n_frames, pad_left, pad_top, h0, w0, C.byref(out),
+                                           L.stream_ptr()))

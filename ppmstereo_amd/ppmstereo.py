@@ -170,6 +170,112 @@ def _forward_update_block_batched(update_block, corr_fn, flow, net, inp, motion_
         return flow_out, torch.cat([e.get_net() for e in engs]), torch.cat([e.get_mhs() for e in engs])
 
 
+_PLANE_FORMATS = {"f32": (L.FMT_F32, torch.float32), "f16": (L.FMT_F16, torch.float16), "u16": (L.FMT_U16, torch.uint16), "u8": (L.FMT_U8, torch.uint8)}
+
+
+class OutputSpec:
+    """What ``forward(output=...)`` / ``forward_batch_test(output=...)`` hand back instead of float32 disparity: up to three planes that ONE
+    kernel (ppms_disparity_egress, include/ppms.h) writes from the 1/4 scale's last iteration -- crop, kept frames, ``.abs()``, the 4x
+    upsampling of the uncertainty and the conversion in one pass.
+      disparity    "f32" | "f16" | "u16": d = |disparity| in pixels; "u16" = min(65535, rint(d * disp_scale)) (KITTI: disp_scale = 256), NaN -> 0
+      depth        None | "f32" | "f16" | "u16": Z = fb / d with fb = focal_px * baseline (one fp32 product); "u16" = min(65535, rint(Z * depth_scale))
+                   (baseline in metres and depth_scale = 1000: millimetres).  A pixel with d < min_disp or d = NaN is invalid: +inf in the float
+                   formats, 0 in "u16".  (min_disp = 0 leaves only NaN invalid: d = 0 then gives +inf / 65535.)
+      uncertainty  "f32" | "u8" | None: u = |uncertainty| in [0, 1]; "u8" = min(255, rint(u * 255)), NaN -> 0
+    Every step is one fp32 operation rounded to nearest even; ``reference`` restates them in torch and is the definition the kernel is
+    tested against, bit for bit."""
+
+    def __init__(self, disparity: str = "f32", depth: Optional[str] = None, uncertainty: Optional[str] = "f32", disp_scale: float = 256.0,
+                 focal_px: Optional[float] = None, baseline: Optional[float] = None, depth_scale: float = 1000.0, min_disp: float = 2.0 ** -8):
+        if disparity not in ("f32", "f16", "u16"):
+            raise ValueError(f"OutputSpec: disparity = {disparity!r}; one of 'f32', 'f16', 'u16'")
+        if depth not in (None, "f32", "f16", "u16"):
+            raise ValueError(f"OutputSpec: depth = {depth!r}; None or one of 'f32', 'f16', 'u16'")
+        if uncertainty not in (None, "f32", "u8"):
+            raise ValueError(f"OutputSpec: uncertainty = {uncertainty!r}; None, 'f32' or 'u8'")
+        f32 = lambda x: float(torch.tensor(float(x), dtype=torch.float32))
+        self.disparity, self.depth, self.uncertainty = disparity, depth, uncertainty
+        self.disp_scale, self.depth_scale, self.min_disp = f32(disp_scale), f32(depth_scale), f32(min_disp)
+        if not (0.0 < self.disp_scale < math.inf):
+            raise ValueError(f"OutputSpec: disp_scale = {disp_scale} must be positive and finite")
+        self.focal_px, self.baseline, self.fb = focal_px, baseline, 0.0
+        if depth is not None:
+            if focal_px is None or baseline is None:
+                raise ValueError("OutputSpec: a depth plane needs focal_px (focal length in pixels) and baseline")
+            self.fb = float(torch.tensor(float(focal_px), dtype=torch.float32) * torch.tensor(float(baseline), dtype=torch.float32))
+            if not (0.0 < self.fb < math.inf):
+                raise ValueError(f"OutputSpec: focal_px * baseline = {self.fb} must be positive and finite")
+            if not (0.0 < self.depth_scale < math.inf):
+                raise ValueError(f"OutputSpec: depth_scale = {depth_scale} must be positive and finite")
+            if not math.isfinite(self.min_disp):
+                raise ValueError(f"OutputSpec: min_disp = {min_disp} must be finite")
+
+    def formats(self) -> Dict[str, str]:
+        """{result key: format} of the requested planes, in the order disparity, depth, uncertainties."""
+        named = (("disparity", self.disparity), ("depth", self.depth), ("uncertainties", self.uncertainty))
+        return {k: f for k, f in named if f is not None}
+
+    def empty(self, n: int, h0: int, w0: int, device, pin_memory: bool = False) -> Dict[str, torch.Tensor]:
+        """Dense (n, 1, h0, w0) tensors of the requested planes' dtypes."""
+        return {k: torch.empty(n, 1, h0, w0, dtype=_PLANE_FORMATS[f][1], device=device, pin_memory=pin_memory) for k, f in self.formats().items()}
+
+    def struct(self, planes: Dict[str, torch.Tensor]) -> L.Egress:
+        """The ``ppms_egress`` that writes into ``planes`` (dense (n, 1, h0, w0) device tensors from ``empty``)."""
+        def plane(key):
+            t = planes.get(key)
+            if t is None:
+                return L.EgressPlane(None, 0, 0, 0, 0)
+            es = t.element_size()
+            return L.EgressPlane(t.data_ptr(), t.stride(0) * es, t.stride(2) * es, _PLANE_FORMATS[self.formats()[key]][0], 0)
+        return L.Egress(plane("disparity"), plane("depth"), plane("uncertainties"), self.disp_scale, self.fb, self.depth_scale, self.min_disp)
+
+    def reference(self, d: torch.Tensor, u: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """The arithmetic of ppms_disparity_egress in plain torch, on CPU or device tensors of any shape: d = a float32 (signed) disparity,
+        u = a float32 uncertainty at the same resolution -> the requested planes under forward_batch_test's keys."""
+        const = lambda x: torch.full((), x, dtype=torch.float32, device=d.device)
+
+        def quant(v, scale, top, fmt):                       # min(top, rint(v * scale)), NaN -> 0: one fp32 product, ties to even
+            r = torch.round(v * const(scale))
+            r = torch.where(torch.isnan(r), torch.zeros_like(r), r).clamp(max=top)
+            return r.to(torch.int32).to(_PLANE_FORMATS[fmt][1])
+
+        d = d.float().abs()
+        out = {"disparity": d if self.disparity == "f32" else d.to(torch.float16) if self.disparity == "f16" else quant(d, self.disp_scale, 65535.0, "u16")}
+        if self.depth is not None:
+            valid = d >= const(self.min_disp)                # (false for NaN)
+            z = torch.where(valid, const(self.fb) / d, const(math.inf))          # tensor / tensor: a correctly rounded fp32 division
+            if self.depth == "u16":
+                out["depth"] = torch.where(valid, quant(z, self.depth_scale, 65535.0, "u16").to(torch.int32), 0).to(torch.uint16)
+            else:
+                out["depth"] = z if self.depth == "f32" else z.to(torch.float16)
+        if self.uncertainty is not None:
+            if u is None:
+                raise ValueError("OutputSpec.reference: an uncertainty plane is requested and no uncertainty was given")
+            u = u.float().abs()
+            out["uncertainties"] = u if self.uncertainty == "f32" else quant(u, 255.0, 255.0, "u8")
+        return out
+
+
+class _EgressCall:
+    """One egress launch as ``cascade`` makes it: the spec, the crop (pad_left, pad_top, H0, W0) inside the padded frame (None: the whole
+    frame) and the window-local frame range (None: all frames)."""
+
+    def __init__(self, spec: OutputSpec, crop=None, frames=None):
+        if not isinstance(spec, OutputSpec):
+            raise TypeError(f"output must be an OutputSpec, got {type(spec).__name__}")
+        self.spec, self.crop, self.frames = spec, (None if crop is None else tuple(int(x) for x in crop)), (None if frames is None else tuple(int(x) for x in frames))
+
+    def launch(self, eng) -> Dict[str, torch.Tensor]:
+        """Allocates the planes on the current stream and enqueues the launch there, behind the engine's last iteration."""
+        pad_left, pad_top, h0, w0 = (0, 0, 4 * eng.h, 4 * eng.w) if self.crop is None else self.crop
+        f0, f1 = (0, eng.T) if self.frames is None else self.frames
+        if not 0 <= f0 < f1 <= eng.T:
+            raise ValueError(f"output: frames = {(f0, f1)} is no range inside the window's {eng.T} frames")
+        planes = self.spec.empty(f1 - f0, h0, w0, eng.FLOW_OUT.device)
+        eng.egress(self.spec.struct(planes), f0, f1 - f0, pad_left, pad_top, h0, w0)
+        return planes
+
+
 class ClipPipeline:
     """Software pipeline over CONSECUTIVE clips / sliding windows (independent units, ppmstereo.py:277-307): the 1/16 and 1/8 scales of
     a clip are latency bound (~70 small launches per iteration, a quarter of a clip's time for 7 % of its FLOPs) and leave most of the
@@ -278,7 +384,7 @@ class PPMStereoHotPath(nn.Module):
     @torch.no_grad()
     def cascade(self, feats: Dict[str, torch.Tensor], iters: int, t: int, predictions: Optional[list] = None,
                 uncertainties: Optional[list] = None, shard=None, test_mode: bool = False, pipeline: Optional[ClipPipeline] = None,
-                diagnostics: Optional[dict] = None):
+                diagnostics: Optional[dict] = None, egress: Optional[_EgressCall] = None):
         """The 1/16 -> 1/8 -> 1/4 cascade of PPMStereo.forward (ppmstereo.py:696-804), device resident: the state handed from
         scale to scale (hidden state, motion hidden state) stays in the engines' SP buffers (ppms_sp_resize_blend), only the
         2-channel flow passes through an NCHW resize.  feats: f1_s, f2_s, net_s, inp_s for s in (16, 8, 4) on the GPU
@@ -290,7 +396,17 @@ class PPMStereoHotPath(nn.Module):
         "tiles", "flagged"}, "1/8": ..., "1/4": ...}, ADDED to entries already there (one dict over several windows sums them; with
         ``shard``: this rank's clips).  One extra small launch per iteration and one host synchronisation at the end of the call; with a
         ``pipeline`` there is none here: the counters are read in ``ClipPipeline.wait()``.  None (default): nothing is launched or read.
+        egress (test_mode, b = 1, no shard): an ``_EgressCall`` -- after the last 1/4-scale iteration ONE ppms_disparity_egress launch on that
+        scale's stream replaces the final clone + bilinear pair and writes the requested planes (crop, frame range, formats); the call
+        then returns {"disparity", "depth"?, "uncertainties"?}: device tensors (n, 1, H0, W0), and appends nothing to the lists.
         Returns (flow_up (T,1,H,W), uncertainty (T,1,H,W)) = predictions[-1], uncertainties[-1]."""
+        if egress is not None:
+            if not test_mode:
+                raise NotImplementedError("cascade: output planes replace the final prediction only; the per-iteration lists of test_mode=False stay float32")
+            if shard is not None:
+                raise NotImplementedError("cascade: output planes need the whole window on one GPU; the sharded gather moves float32")
+            if feats["f1_16"].shape[0] != t:
+                raise NotImplementedError("cascade: output planes are written for one clip per call (b = 1); the batched glue keeps float32 lists")
         if iters < 2:
             raise ValueError(f"cascade: iters={iters}; the 1/16 and 1/8 scales run iters // 2 iterations each (ppmstereo.py:708,744) and need at least one")
         preds = [] if predictions is None else predictions
@@ -348,7 +464,12 @@ class PPMStereoHotPath(nn.Module):
                         pipeline.consumed = torch.cuda.Event()
                         pipeline.consumed.record()                # the 1/8 engine's flow / hidden states have been read: the next clip may overwrite them
                     eng.begin(CorrBlock1D(f1, f2).levels, self.att[ai].packed(dev))
-                    fo = _run_iterations(eng, n_it, isc, tl, h, w, preds, uncs, "all" if not test_mode else ("last" if s_ == 4 else "none"))
+                    last_scale_emit = "none" if egress is not None else "last"       # (the last iteration upsamples its flow either way)
+                    fo = _run_iterations(eng, n_it, isc, tl, h, w, preds, uncs, "all" if not test_mode else (last_scale_emit if s_ == 4 else "none"))
+                    if egress is not None and s_ == 4:
+                        # on this scale's stream and -- with a pipeline -- before ``pipeline.last`` is recorded: the next clip's 1/4 scale
+                        # overwrites FLOW_OUT and UNC
+                        planes = egress.launch(eng)
                     prev = eng
                     if diagnostics is not None:
                         eng.enable_attn_health(health_was_on)
@@ -361,11 +482,11 @@ class PPMStereoHotPath(nn.Module):
                     del pipeline._health[:-16]                     # (as _results below: a caller that never waits)
                 if pipeline.record_done:
                     pipeline.done_events.append(pipeline.last)
-                pipeline._results += [preds[-1], uncs[-1]]         # (ClipPipeline.wait records the consuming stream on them)
+                pipeline._results += [preds[-1], uncs[-1]] if egress is None else list(planes.values())      # (ClipPipeline.wait records the consuming stream on them)
                 del pipeline._results[:-16]                        # a caller that never waits (bench.py) must not accumulate references
             elif diagnostics is not None:
                 _add_attn_redo(diagnostics, {tag: eng.attn_health() for tag, eng in health.items()})
-            return preds[-1], uncs[-1]
+            return planes if egress is not None else (preds[-1], uncs[-1])
 
 
 def _cascade_batched(self, feats, iters: int, t: int, preds: list, uncs: list):
@@ -782,7 +903,7 @@ class PPMStereo(PPMStereoHotPath):
 
     @torch.no_grad()
     def forward(self, image1: torch.Tensor, image2: torch.Tensor, flow_init=None, iters: int = 10, test_mode: bool = False, pipeline=None,
-                diagnostics: Optional[dict] = None):
+                diagnostics: Optional[dict] = None, output: Optional[OutputSpec] = None, crop=None, frames=None):
         """PPMStereo.forward (ppmstereo.py:601-804): image (b, T, 3, H, W) in [0, 255], H, W multiples of 32 (b = 1: the device-resident
         cascade; b > 1: the reference's glue around the batched forward_update_block).  Float images as in the reference, or both uint8:
         with this package's encoders the bytes go through ONE kernel (ppms_video_ingest_u8) to the operands of the first convolutions --
@@ -791,18 +912,30 @@ class PPMStereo(PPMStereoHotPath):
         (ppms_video_ingest_yuv420) converts them and writes the same operands -- the bits of ``forward`` on their ``to_rgb_u8()``.
         test_mode: (flow_up, uncertainty), each (b, T, 1, H, W); else (predictions (D, b, T, 1, H, W), uncertainties).
         pipeline (test_mode only): a ``ClipPipeline`` -- the result is valid once ``pipeline.wait()`` has been called.
-        diagnostics (b = 1): a dict that receives ``["attn_redo"]``, the per-scale fix-up accounting of the memory read-out (see ``cascade``)."""
+        diagnostics (b = 1): a dict that receives ``["attn_redo"]``, the per-scale fix-up accounting of the memory read-out (see ``cascade``).
+        output (test_mode, b = 1): an ``OutputSpec`` -- the call returns a dict of device tensors (1, n, 1, H0, W0) under "disparity", "depth"
+        and "uncertainties" as the spec asks, written by ONE ppms_disparity_egress launch behind the last iteration (no float32 full-resolution
+        tensor is made); crop = (pad_left, pad_top, H0, W0) inside the frame (default: the whole frame), frames = (from, to) (default: all)."""
         if flow_init is not None:
             raise NotImplementedError("flow_init: the reference's own path for it reads undefined state (ppmstereo.py:691-693, 763)")
         if self.fnet is None or self.cnet is None:
             raise RuntimeError("PPMStereo.forward needs the encoders: pass fnet= / cnet= (outside the hot path, SURVEY.md section 8 f3-f5)")
+        egress = None
+        if output is not None:
+            if not test_mode:
+                raise NotImplementedError("PPMStereo.forward: output= needs test_mode=True; the lists of intermediate predictions stay float32")
+            egress = _EgressCall(output, crop, frames)
+        elif crop is not None or frames is not None:
+            raise ValueError("PPMStereo.forward: crop= and frames= select what output= writes; without output= they have no meaning")
         if isinstance(image1, YUVFrames) or isinstance(image2, YUVFrames):
-            return self._forward_yuv(image1, image2, iters, test_mode, pipeline, diagnostics)
+            return self._forward_yuv(image1, image2, iters, test_mode, pipeline, diagnostics, egress)
         if torch.is_tensor(image1) and torch.is_tensor(image2) and (image1.dtype == torch.uint8) != (image2.dtype == torch.uint8):
             raise TypeError(f"PPMStereo.forward: image1 is {image1.dtype} and image2 is {image2.dtype}; both views must be uint8 or both floating point")
         b, T, c, h, w = image1.shape
         if b != 1 and pipeline is not None:
             raise NotImplementedError("PPMStereo.forward: a ClipPipeline overlaps consecutive batch-1 clips")
+        if b != 1 and egress is not None:
+            raise NotImplementedError("PPMStereo.forward: output= serves b = 1; the batched glue keeps float32 lists of predictions")
         images = (image1, image2)
         if image1.dtype == torch.uint8:
             if self._hip_encoders() and image1.is_cuda and image2.is_cuda:
@@ -811,19 +944,21 @@ class PPMStereo(PPMStereoHotPath):
                 images = _ByteFrames(image1.contiguous(), image2.contiguous(), 3 * h * w, b * T, h, w)
             else:                                              # encoder callables of the caller: they get what they get for a float video
                 images = (image1.float(), image2.float())
-        return self._forward_images(images, b, T, h, w, image1.device, iters, test_mode, pipeline, diagnostics)
+        return self._forward_images(images, b, T, h, w, image1.device, iters, test_mode, pipeline, diagnostics, egress)
 
-    def _forward_yuv(self, image1, image2, iters: int, test_mode: bool, pipeline, diagnostics):
+    def _forward_yuv(self, image1, image2, iters: int, test_mode: bool, pipeline, diagnostics, egress=None):
         """``forward`` on two ``YUVFrames`` on the device: b = 1, T = their frame count, the frame size as it is."""
         if not (isinstance(image1, YUVFrames) and isinstance(image2, YUVFrames)):
             raise TypeError(f"PPMStereo.forward: image1 is {type(image1).__name__} and image2 is {type(image2).__name__}; both views must be YUVFrames or both tensors")
         video = YUVStereoVideo(image1, image2)
         L.require_gpu(image1.y, image2.y)
         if self._hip_encoders():
-            return self._forward_images(_YUVPlanes(video), 1, len(video), video.height, video.width, image1.device, iters, test_mode, pipeline, diagnostics)
+            return self._forward_images(_YUVPlanes(video), 1, len(video), video.height, video.width, image1.device, iters, test_mode, pipeline, diagnostics,
+                                        egress)
         # encoder callables of the caller: they get what they get for a float video
+        out = {} if egress is None else dict(output=egress.spec, crop=egress.crop, frames=egress.frames)
         return self.forward(image1.to_rgb_u8().float()[None], image2.to_rgb_u8().float()[None], iters=iters, test_mode=test_mode, pipeline=pipeline,
-                            diagnostics=diagnostics)
+                            diagnostics=diagnostics, **out)
 
     def _hip_encoders(self) -> bool:
         """Both encoders are this package's: their plans take the first-layer operands ppms_video_ingest_u8 writes."""
@@ -831,9 +966,10 @@ class PPMStereo(PPMStereoHotPath):
         from .encoder import BasicEncoder
         return isinstance(self.fnet, BasicEncoder) and isinstance(self.cnet, Feature)
 
-    def _forward_images(self, images, b: int, T: int, h: int, w: int, dev, iters: int, test_mode: bool, pipeline, diagnostics):
+    def _forward_images(self, images, b: int, T: int, h: int, w: int, dev, iters: int, test_mode: bool, pipeline, diagnostics, egress=None):
         """``forward`` behind its argument checks.  images: the two float videos (b, T, 3, h, w), or ``_ByteFrames`` / ``_YUVPlanes`` holding
-        b * T decoded frames per view that one ingest kernel pads to h x w (``forward_batch_test`` hands a window over unpadded)."""
+        b * T decoded frames per view that one ingest kernel pads to h x w (``forward_batch_test`` hands a window over unpadded).
+        egress (an ``_EgressCall``; test_mode, b = 1): the result is ``cascade``'s dict of output planes, each (1, n, 1, H0, W0)."""
         with torch.cuda.device(dev):
             # fnet (both views) and cnet (left view) depend on the images only and are chains of small launches that leave most of the chip
             # idle: cnet runs on a second stream beside fnet (whole call -3.5 ms at config 2); its outputs are handed to the caller's
@@ -883,6 +1019,9 @@ class PPMStereo(PPMStereoHotPath):
                 per = [self.pre_loop(*(x[bi * T:(bi + 1) * T] for x in (fmap1, fmap2, c4, c8, c16)), T) for bi in range(b)]
                 feats = {k: torch.cat([p_[k] for p_ in per]) for k in per[0]}
             preds, uncs = [], []
+            if egress is not None:
+                planes = self.cascade(feats, iters, T, test_mode=True, pipeline=pipeline, diagnostics=diagnostics, egress=egress)
+                return {k: p[None] for k, p in planes.items()}
             self.cascade(feats, iters, T, preds, uncs, test_mode=test_mode, pipeline=pipeline if test_mode else None, diagnostics=diagnostics)
             if test_mode:
                 return preds[-1].reshape(b, T, 1, h, w), uncs[-1].reshape(b, T, 1, h, w)
@@ -890,7 +1029,7 @@ class PPMStereo(PPMStereoHotPath):
 
     @torch.no_grad()
     def forward_batch_test(self, batch_dict: Dict, kernel_size: int = 20, iters: int = 20, device=None, shard_ranks: bool = False,
-                           diagnostics: bool = False):
+                           diagnostics: bool = False, output: Optional[OutputSpec] = None):
         """PPMStereo.forward_batch_test (ppmstereo.py:238-320): batch_dict["stereo_video"] (N, 2, 3, H, W) on the host;
         per window: InputPadder(divis_by=32), one host->device copy, forward(test_mode=True), unpad, one device->host copy;
         a uint8 video (host or device) is copied as bytes -- a quarter of the float video's -- and, with this package's encoders, padded and
@@ -903,7 +1042,17 @@ class PPMStereo(PPMStereoHotPath):
         shard_ranks: under torch.distributed the windows are dealt round-robin over the ranks (independent units, no data-path
         collective) and the kept frames are gathered once at the end (``dist.gather_kept_frames``); every rank returns the video.
         diagnostics: the returned dict also has "attn_redo": the per-scale fix-up accounting of the memory read-out (see ``cascade``) summed
-        over all windows (``shard_ranks``: over this rank's windows).  False (default): the two keys above, and no extra launch."""
+        over all windows (``shard_ranks``: over this rank's windows).  False (default): the two keys above, and no extra launch.
+        output: an ``OutputSpec`` -- per window ONE ppms_disparity_egress launch writes the kept frames, cropped and converted, and only
+        those are copied device -> host, straight into their slice of pinned (N, 1, H, W) results of the planes' dtypes (uint16 disparity and
+        uint8 confidence: 3 bytes per pixel and kept frame, where the default path copies 8 for every frame of the window).  Returns
+        {"disparity", "depth" when asked, "uncertainties" unless its format is None}.  Not with ``shard_ranks``.  None (default): the float32
+        path above, launch for launch."""
+        if output is not None:
+            if not isinstance(output, OutputSpec):
+                raise TypeError(f"forward_batch_test: output must be an OutputSpec, got {type(output).__name__}")
+            if shard_ranks:
+                raise NotImplementedError("forward_batch_test: output= with shard_ranks=True is not served: dist.gather_kept_frames moves float32")
         video = batch_dict["stereo_video"]
         num_ims = len(video)
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -935,6 +1084,29 @@ class PPMStereo(PPMStereoHotPath):
         # before window k's result is collected, and run under window k's 1/4 scale
         pipe = ClipPipeline(dev) if len(plan) > 1 else None
         pending = None
+        if output is not None:
+            H0, W0 = (video.height, video.width) if isinstance(video, YUVStereoVideo) else video.shape[-2:]
+            host = output.empty(num_ims, int(H0), int(W0), "cpu", pin_memory=True)           # allocated once; every window fills its slice
+
+            def collect_planes(item):
+                planes, handle, dst_from, dst_to = item
+                if pipe is not None:
+                    pipe.wait(handle)
+                torch.cuda.current_stream(dev).synchronize()               # in front of the copy, as in collect() below
+                for key, plane in planes.items():
+                    host[key][dst_from:dst_to].copy_(plane[0])             # kept frames only, device -> their slice of the pinned result
+
+            with torch.cuda.device(dev):
+                for start, stop, keep_from, keep_to, dst_from, dst_to in egress_plan(plan):
+                    planes = self._window_forward(video, start, stop, dev, iters, pipe, diag, output, (keep_from, keep_to))
+                    item = (planes, None if pipe is None else pipe.last, dst_from, dst_to)
+                    if pending is not None:
+                        collect_planes(pending)
+                    pending = item
+                collect_planes(pending)
+            if diag is not None:
+                host["attn_redo"] = diag.get("attn_redo", {})
+            return host
 
         def collect(item):
             d, u, handle, padder, keep_from, keep_to = item
@@ -965,9 +1137,16 @@ class PPMStereo(PPMStereoHotPath):
         return out
 
 
-def _window_forward(self, video, start: int, stop: int, dev, iters: int, pipe, diag):
+def _window_forward(self, video, start: int, stop: int, dev, iters: int, pipe, diag, output: Optional[OutputSpec] = None, keep=None):
     """One window of forward_batch_test: frames [start, stop) of the (N, 2, 3, H0, W0) video or the YUVStereoVideo -> (disparity, uncertainty) of the padded
-    window, each (1, T, 1, H, W), and the InputPadder that crops them back."""
+    window, each (1, T, 1, H, W), and the InputPadder that crops them back.  output (an OutputSpec): the window's egress launch crops with that
+    padder's geometry and writes the window-local frames keep = (from, to); the result is then the dict of planes, each (1, n, 1, H0, W0)."""
+    def egress(padder):
+        if output is None:
+            return None
+        pad_left, pad_top, _, _ = padder.geometry()
+        return _EgressCall(output, (pad_left, pad_top, padder.ht, padder.wd), keep)
+
     # host -> device: ONE copy of the window's contiguous (T, 2, 3, H, W) block; the two views are split and padded on the
     # device (slicing a view out on the host first costs a host-side copy of each view, padding there another one)
     win = video[start:stop].to(dev)
@@ -976,6 +1155,8 @@ def _window_forward(self, video, start: int, stop: int, dev, iters: int, pipe, d
             # the planes stay as the decoder left them: ppms_video_ingest_yuv420 converts, and pads by clamping its source coordinate
             padder = InputPadder((win.height, win.width), divis_by=32)
             pad_left, pad_top, H, W = padder.geometry()
+            if output is not None:
+                return self._forward_images(_YUVPlanes(win, pad_left, pad_top), 1, len(win), H, W, dev, iters, True, pipe, diag, egress(padder))
             d, u = self._forward_images(_YUVPlanes(win, pad_left, pad_top), 1, len(win), H, W, dev, iters, True, pipe, diag)
             return d, u, padder
         win = torch.stack([win.left.to_rgb_u8(), win.right.to_rgb_u8()], dim=1).float()    # encoder callables of the caller: the float path
@@ -989,12 +1170,17 @@ def _window_forward(self, video, start: int, stop: int, dev, iters: int, pipe, d
             padder = InputPadder((H0, W0), divis_by=32)
             pad_left, pad_top, H, W = padder.geometry()
             frames = _ByteFrames(win[:, 0], win[:, 1], 6 * H0 * W0, T, H0, W0, pad_left, pad_top)
+            if output is not None:
+                return self._forward_images(frames, 1, T, H, W, dev, iters, True, pipe, diag, egress(padder))
             d, u = self._forward_images(frames, 1, T, H, W, dev, iters, True, pipe, diag)
             return d, u, padder
         win = win.float()                                        # encoder callables of the caller: the float path from here on
     left, right = win[:, 0], win[:, 1]
     padder = InputPadder(left.shape, divis_by=32)
     left, right = padder.pad(left, right)
+    if output is not None:
+        return self.forward(left[None], right[None], iters=iters, test_mode=True, pipeline=pipe, diagnostics=diag, output=output,
+                            crop=egress(padder).crop, frames=keep)
     d, u = self.forward(left[None], right[None], iters=iters, test_mode=True, pipeline=pipe, diagnostics=diag)
     return d, u, padder
 
@@ -1017,6 +1203,12 @@ def window_plan(num_ims: int, kernel_size: int = 20):
         elif not plan:
             plan.append((i, i + n, 0, n + (-stride // 2)))
     return plan
+
+
+def egress_plan(plan):
+    """``window_plan`` with the destination of every window's kept frames: (start, stop, keep_from, keep_to, dst_from, dst_to) -- the egress
+    launch of the window writes its frames [keep_from, keep_to), and they are frames [dst_from, dst_to) of the video."""
+    return [(start, stop, keep_from, keep_to, start + keep_from, start + keep_to) for start, stop, keep_from, keep_to in plan]
 
 
 def shard_windows(plan, rank: int, world: int):

@@ -1,0 +1,170 @@
+"""Same-box A/B of the back door: PPMStereo.forward_batch_test on a float32 host video with output=None (tree A, --parent DIR: a checkout of the
+parent commit with its library built; default: this tree, whose default path is the parent's) against this tree's with
+output=OutputSpec(disparity="u16", uncertainty="u8").
+    python tools/egress_probe.py --parent DIR [--runs 12] [--windows] > profiles/rNN_egress_ab.txt
+Two worker processes (one per tree) stay alive and take turns, one whole call each, so both see the same box, clocks and host load.  Per side:
+median / min / max whole-call ms (host video -> host results), the device->host bytes of a call, and what is enqueued behind the last convex
+upsampling of a one-window call (library launches and torch ops that launch; counted in one extra call after the timed ones, with Python-level
+hooks that the timed calls never see).  Config 2: T = 5, 320x512, iters = 10 (one window); --windows adds T = 30 at kernel_size = 20 (three
+windows through the ClipPipeline: only kept frames cross on side B).  The bar: B's median is not above A's by more than the
++-2 % same-box spread."""
+import argparse
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LAUNCHES = ("ppms_convex_upsample", "ppms_convex_upsample_3d", "ppms_bilinear", "ppms_disparity_egress")
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ worker
+def worker(tree: str, side: str):
+    sys.path.insert(0, tree)
+    import torch
+    from ppmstereo_amd import _lib as L
+    from ppmstereo_amd import ppmstereo as P
+    from ppmstereo_amd import weights as Wm
+    assert os.path.dirname(os.path.dirname(os.path.abspath(L.__file__))) == os.path.abspath(tree), (L.__file__, tree)
+    dev = torch.device("cuda:0")
+    m = P.PPMStereo.shipped()
+    m.load_hot_path_weights(Wm.hot_path_weights())
+    m.fnet.load_state_dict(Wm.fnet_weights(), strict=True), m.cnet.load_state_dict(Wm.cnet_weights(), strict=True)
+    sd = m.state_dict()
+    sd.update(Wm.sst_weights())
+    m.load_state_dict(sd, strict=True)
+    m = m.to(dev).eval()
+    kw = {"output": P.OutputSpec(disparity="u16", uncertainty="u8")} if side == "egress" else {}
+    say = lambda *a: print(*a, flush=True)
+    state = {}
+
+    def setup(T, H, W, iters):
+        state["video"] = Wm.hash_uniform((T, 2, 3, H, W), 613, 0.0, 255.0).round().contiguous()
+        state["call"] = lambda: m.forward_batch_test({"stereo_video": state["video"]}, kernel_size=20, iters=iters, **kw)
+        for _ in range(3):
+            state["call"]()
+        torch.cuda.synchronize()
+
+    def count():
+        """One call with hooks: device->host bytes, and every library launch of LAUNCHES / torch op with a device or host result behind the
+        last convex upsampling."""
+        from torch.utils._python_dispatch import TorchDispatchMode
+        events, d2h = [], [0]
+
+        class Mode(TorchDispatchMode):
+            def __torch_dispatch__(self, func, types, args=(), kwargs=None):
+                out = func(*args, **(kwargs or {}))
+                name = func._schema.name
+                view = any(r.alias_info is not None and not r.alias_info.is_write for r in func._schema.returns)
+                tensors = [a for a in args if torch.is_tensor(a)]
+                if name == "aten::copy_" and len(tensors) == 2 and tensors[1].is_cuda and not tensors[0].is_cuda:
+                    d2h[0] += tensors[1].numel() * tensors[1].element_size()
+                    events.append("d2h:copy_")
+                elif name == "aten::_to_copy" and tensors and tensors[0].is_cuda and torch.is_tensor(out) and not out.is_cuda:
+                    d2h[0] += tensors[0].numel() * tensors[0].element_size()
+                    events.append("d2h:_to_copy")
+                elif not view and torch.is_tensor(out) and not name.startswith(("aten::empty", "aten::new_empty")):
+                    events.append(("gpu:" if out.is_cuda else "host:") + name.replace("aten::", ""))
+                return out
+
+        lib = L.load()
+        for name in LAUNCHES:
+            if hasattr(lib, name):
+                fn = getattr(lib, name)
+                setattr(lib, name, (lambda fn, name: lambda *a: (events.append("lib:" + name), fn(*a))[1])(fn, name))
+        with Mode():
+            state["call"]()
+        last = max((i for i, e in enumerate(events) if e.startswith("lib:ppms_convex_upsample")), default=-1)
+        tail = events[last + 1:]
+        say("count", d2h[0], sum(e.startswith(("lib:", "gpu:")) for e in tail), sum(e.startswith("host:") for e in tail), ",".join(tail))
+
+    for line in sys.stdin:
+        cmd = line.split()
+        if not cmd:
+            continue
+        if cmd[0] == "setup":
+            setup(*map(int, cmd[1:5]))
+            say("ready", state["video"].numel() * state["video"].element_size())
+        elif cmd[0] == "run":
+            t0 = time.perf_counter()
+            state["out"] = state["call"]()
+            say("ms", f"{1e3 * (time.perf_counter() - t0):.3f}")
+        elif cmd[0] == "shape":
+            o = state["out"]
+            say("shape", ";".join(f"{k}:{str(v.dtype).replace('torch.', '')}{list(v.shape)}" for k, v in o.items() if torch.is_tensor(v)))
+        elif cmd[0] == "count":
+            count()
+        elif cmd[0] == "quit":
+            break
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ driver
+class Side:
+    def __init__(self, label, tree, side):
+        self.label = label
+        self.p = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--worker", side, "--tree", tree], stdin=subprocess.PIPE,
+                                  stdout=subprocess.PIPE, text=True, bufsize=1)
+
+    def ask(self, *cmd):
+        self.p.stdin.write(" ".join(map(str, cmd)) + "\n")
+        self.p.stdin.flush()
+        while True:
+            line = self.p.stdout.readline()
+            if not line:
+                raise RuntimeError(f"worker '{self.label}' ended (exit {self.p.wait()})")
+            parts = line.split()
+            if parts and parts[0] in ("ready", "ms", "shape", "count"):
+                return parts[1:]
+
+    def close(self):
+        try:
+            self.p.stdin.write("quit\n")
+            self.p.stdin.close()
+        except OSError:
+            pass
+        self.p.wait(timeout=60)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parent", default=None, help="tree of the parent commit with its libppms.so built (default: this tree's default path)")
+    ap.add_argument("--runs", type=int, default=12)
+    ap.add_argument("--windows", action="store_true", help="also T = 30 at kernel_size = 20: three windows through the ClipPipeline")
+    ap.add_argument("--worker", default=None)
+    ap.add_argument("--tree", default=HERE)
+    a = ap.parse_args()
+    if a.worker:
+        return worker(os.path.abspath(a.tree), a.worker)
+    ptree = os.path.abspath(a.parent) if a.parent else HERE
+    A = Side("output=None, " + ("parent commit's tree" if a.parent else "this tree (default path as in the parent)"), ptree, "default")
+    B = Side('output=OutputSpec(disparity="u16", uncertainty="u8"), this tree', HERE, "egress")
+    try:
+        for T, H, W, iters, runs in [(5, 320, 512, 10, a.runs)] + ([(30, 320, 512, 10, max(3, a.runs // 3))] if a.windows else []):
+            for s in (A, B):
+                s.ask("setup", T, H, W, iters)
+            ms = {A: [], B: []}
+            for _ in range(runs):
+                for s in (A, B):                                # alternate: one whole call each
+                    ms[s].append(float(s.ask("run")[0]))
+            print(f"== T = {T}, {H}x{W}, iters = {iters}, kernel_size = 20: forward_batch_test(host video) -> host results, {runs} alternating calls per side")
+            for s in (A, B):
+                v = ms[s]
+                shape = s.ask("shape")[0]
+                d2h, n_dev, n_host, names = (s.ask("count") + [""])[:4]
+                print(f"{s.label}:")
+                print(f"    whole call ms: median {statistics.median(v):.2f}  min {min(v):.2f}  max {max(v):.2f}   [{' '.join(f'{x:.1f}' for x in v)}]")
+                print(f"    results: {shape}")
+                print(f"    device->host bytes per call: {int(d2h)} ({int(d2h) / (T * H * W):.2f} per pixel and frame of the video)")
+                print(f"    behind the last convex upsampling: {n_dev} device launches / copies, {n_host} host torch ops  ({names})")
+            ma, mb = statistics.median(ms[A]), statistics.median(ms[B])
+            print(f"egress median / default median = {mb / ma:.4f} ({mb - ma:+.2f} ms)")
+            print()
+        print("host: cpus", os.cpu_count(), "loadavg", os.getloadavg())
+    finally:
+        for s in (A, B):
+            s.close()
+
+
+if __name__ == "__main__":
+    main()
