@@ -319,6 +319,41 @@ int ppms_video_ingest_yuv420(const ppms_yuv_view* left, const ppms_yuv_view* rig
                              int N, int H0, int W0, int pad_left, int pad_top, int H, int W,
                              const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream);
 int ppms_yuv_struct_sizes(int* view, int* matrix);   /* sizeof of the two structs above (56, 32): lets a binding verify its layout */
+/* Both calls above on the frames of an UNRECTIFIED rig, one launch: the undistort + rectify (+ resize) remap every caller runs between the
+ * decoder and a stereo model happens where the byte is fetched.  H0 x W0 is now the RECTIFIED frame; the source frames are hs x ws.  One view's
+ * map covers the rectified frame and holds, for rectified pixel (y, x) at element y * pitch + x,
+ *   xy:   int16 (x0, y0), interleaved, x first -- the integer part of the source coordinate;
+ *   frac: a 16-bit word, fx = frac & 31, fy = (frac >> 5) & 31 -- its fraction in 1/32 pixel; bits 10 and up must be 0, and the kernel masks them.
+ * (The layout OpenCV's convertMaps(..., CV_16SC2) documents for its fixed-point maps; nothing here has been compared with OpenCV.)
+ * The taps are source pixels (y0, x0), (y0, x0 + 1), (y0 + 1, x0), (y0 + 1, x0 + 1) -- coordinates in 32-bit arithmetic -- with the weights
+ *   w00 = (32 - fx)(32 - fy),  w01 = fx (32 - fy),  w10 = (32 - fx) fy,  w11 = fx fy          (their sum is 1024)
+ * and, for each of R, G, B,   out = (w00 p00 + w01 p01 + w10 p10 + w11 p11 + 512) >> 10,   which lies in [0, 255] without a clamp; a map
+ * whose frac is 0 everywhere copies bytes.  border = 0 (replicate): every tap coordinate is clamped into the source frame; border = 1
+ * (constant): a tap outside the frame contributes `fill` (one byte for R, G and B).  In both modes every load address is clamped into the
+ * frame first, whatever the map holds: a nonsense map gives nonsense pixels, never a read outside the surface.  For YUV sources a tap is
+ * the RGB byte of that source pixel -- the conversion above, with the pixel's nearest chroma sample -- and the blend happens in RGB: the
+ * result is by definition the remap of the converted frames.  From the rectified bytes on (lut, pads, H x W, destinations) the calls are
+ * ppms_video_ingest_u8: the same bits as rectifying first and calling it.  The map structs are HOST memory, read before the call returns;
+ * xy (4-byte aligned) and frac (2-byte aligned) are device pointers to at least (H0 - 1) * pitch + W0 elements, shared by all N frames of
+ * the view.  _u8_remap: dense planar RGB source frames (3, hs, ws), frame_stride >= 3 hs ws.  _yuv420_remap: the views are checked as
+ * ppms_video_ingest_yuv420 checks them, against hs x ws.  Refused with PPMS_EINVAL before any launch: a null map or a null pointer in one,
+ * pitch < W0, hs or ws outside [1, 32768], the two maps' hs / ws differing, border not 0 or 1, fill outside [0, 255], reserved != 0, a
+ * misaligned pointer.  Not covered: interpolation other than bilinear, computing maps from calibration data. */
+typedef struct ppms_remap_view {      /* one view's rectification map */
+    const int16_t* xy;                /* (x0, y0) of rectified pixel (0, 0); device pointer */
+    const uint16_t* frac;             /* fx | fy << 5 of rectified pixel (0, 0); device pointer */
+    int32_t pitch;                    /* map pixels from row to row, >= W0 */
+    int32_t hs, ws;                   /* source frame size, 1..32768 */
+    int32_t border, fill, reserved;   /* 0 = replicate, 1 = constant; the constant's byte; 0 */
+} ppms_remap_view;
+int ppms_video_ingest_u8_remap(const uint8_t* left, const uint8_t* right, int64_t frame_stride, const ppms_remap_view* lmap, const ppms_remap_view* rmap,
+                               int N, int H0, int W0, int pad_left, int pad_top, int H, int W,
+                               const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream);
+int ppms_video_ingest_yuv420_remap(const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m,
+                                   const ppms_remap_view* lmap, const ppms_remap_view* rmap,
+                                   int N, int H0, int W0, int pad_left, int pad_top, int H, int W,
+                                   const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream);
+int ppms_remap_struct_size(int* view);               /* sizeof(ppms_remap_view) (40): lets a binding verify its layout */
 /* nn.InstanceNorm2d(affine=False) (extractor.py:326-329, 364): per (sample, channel) mean and 1 / sqrt(biased var + eps) over the
  * HW pixels of x (channel-last fp32 [N * HW][ld], a convolution's fp32 output) -> stats[N][C][2] (pixel slices merged in fixed
  * order: deterministic; caller-owned workspace of ppms_instnorm_workspace_bytes); then

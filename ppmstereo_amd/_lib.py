@@ -71,6 +71,13 @@ class YUVMatrix(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("y_off", "cy", "crv", "cgu", "cgv", "cbu", "shift", "reserved")]
 
 
+class RemapView(C.Structure):
+    """ppms_remap_view: one view's fixed-point rectification map (device pointers, pitch in map pixels, the source frame size)."""
+    _fields_ = [("xy", c_void_p), ("frac", c_void_p), ("pitch", C.c_int32), ("hs", C.c_int32), ("ws", C.c_int32),
+                ("border", C.c_int32), ("fill", C.c_int32), ("reserved", C.c_int32)]
+
+
+BORDER_REPLICATE, BORDER_CONSTANT = 0, 1
 FMT_F32, FMT_F16, FMT_U16, FMT_U8 = range(4)
 
 
@@ -134,6 +141,11 @@ _SIGS = {
     "ppms_video_ingest_yuv420": (c_int, [C.POINTER(YUVView), C.POINTER(YUVView), C.POINTER(YUVMatrix), c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                          c_void_p, SP, SP, c_void_p]),
     "ppms_yuv_struct_sizes": (c_int, [C.POINTER(c_int), C.POINTER(c_int)]),
+    "ppms_video_ingest_u8_remap": (c_int, [c_void_p, c_void_p, c_int64, C.POINTER(RemapView), C.POINTER(RemapView), c_int, c_int, c_int, c_int, c_int, c_int,
+                                           c_int, c_void_p, SP, SP, c_void_p]),
+    "ppms_video_ingest_yuv420_remap": (c_int, [C.POINTER(YUVView), C.POINTER(YUVView), C.POINTER(YUVMatrix), C.POINTER(RemapView), C.POINTER(RemapView),
+                                               c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, SP, SP, c_void_p]),
+    "ppms_remap_struct_size": (c_int, [C.POINTER(c_int)]),
     "ppms_dwconv": (c_int, [SP, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ppms_layernorm_any": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_float, SP, c_int64, c_int, c_void_p]),
     "ppms_grn_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
@@ -192,6 +204,9 @@ def load() -> C.CDLL:
     lib.ppms_yuv_struct_sizes(C.byref(a), C.byref(b))
     if (a.value, b.value) != (C.sizeof(YUVView), C.sizeof(YUVMatrix)):
         raise RuntimeError("ppmstereo_amd: ctypes layout of ppms_yuv_view / ppms_yuv_matrix differs from include/ppms.h")
+    lib.ppms_remap_struct_size(C.byref(a))
+    if a.value != C.sizeof(RemapView):
+        raise RuntimeError("ppmstereo_amd: ctypes layout of ppms_remap_view differs from include/ppms.h")
     if lib.ppms_egress_struct_size() != C.sizeof(Egress):
         raise RuntimeError("ppmstereo_amd: ctypes layout of ppms_egress differs from include/ppms.h")
     if lib.ppms_pwchain_param_bytes() != C.sizeof(ChainParams):

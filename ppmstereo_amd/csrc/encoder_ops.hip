@@ -71,6 +71,36 @@ struct yuv420_source {                                                    // pit
     }
 };
 
+// a source behind a rectification map (ppms_video_ingest_u8_remap / ppms_video_ingest_yuv420_remap; the arithmetic: include/ppms.h): (y, x) is a
+// pixel of the RECTIFIED frame, the view's map names its four taps in the inner source's frame of hs x ws, and the blend is integer.  Every
+// tap coordinate is clamped into that frame before the inner source sees it, whatever the map holds: in constant mode a tap outside the frame
+// contributes `fill` instead of what lies at the clamped address.
+template <class Inner>
+struct remapped_source {
+    Inner inner;                                                          // built with the source frame size
+    ppms_remap_view left, right;
+    int N;
+    __device__ int operator()(int64_t m, int c, int y, int x) const {
+        const bool r = m >= N;
+        const int64_t o = (int64_t)y * (r ? right.pitch : left.pitch) + x;
+        // the three channels of a pixel repeat these loads; they are the same addresses, and the compiler merges them
+        const short2 xy = ((const short2*)(r ? right.xy : left.xy))[o];
+        const int fr = (r ? right.frac : left.frac)[o];
+        const int fx = fr & 31, fy = (fr >> 5) & 31;
+        const int hs = left.hs, ws = left.ws, border = r ? right.border : left.border, fill = r ? right.fill : left.fill;
+        int acc = 512;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int yy = (int)xy.y + (t >> 1), xx = (int)xy.x + (t & 1);    // int16 + 1: 32-bit arithmetic
+            const bool outside = yy < 0 || yy > hs - 1 || xx < 0 || xx > ws - 1;
+            const int cy = yy < 0 ? 0 : (yy > hs - 1 ? hs - 1 : yy), cx = xx < 0 ? 0 : (xx > ws - 1 ? ws - 1 : xx);
+            const int p = border && outside ? fill : inner(m, c, cy, cx);
+            acc += ((t & 1) ? fx : 32 - fx) * ((t >> 1) ? fy : 32 - fy) * p;
+        }
+        return acc >> 10;                                                 // weights sum to 1024: in [0, 255]
+    }
+};
+
 template <class Source>
 __global__ __launch_bounds__(256) void video_ingest_kernel(Source source, int N, int H0, int W0, int pad_left, int pad_top, int H, int W,
                                                            const float* __restrict__ lut, ppms_sp dst_fnet, ppms_sp dst_cnet, int64_t nf, int64_t total) {
@@ -644,34 +674,89 @@ extern "C" int ppms_yuv_struct_sizes(int* view, int* matrix) {
     return PPMS_OK;
 }
 
-extern "C" int ppms_video_ingest_yuv420(const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m, int N, int H0, int W0, int pad_left,
-                                        int pad_top, int H, int W, const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream) {
-    PPMS_REQUIRE(left && right && m && lut, "video_ingest_yuv420: null view, matrix or table pointer");
-    PPMS_REQUIRE(N > 0 && H0 > 0 && W0 > 0, "video_ingest_yuv420: N = %d, H0 = %d, W0 = %d must be positive", N, H0, W0);
+// what both YUV entry points check about the views (frames of H0 x W0, named `hname` x `wname` in the messages) and the matrix
+static int yuv420_check(const char* who, const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m, const float* lut, int N, int H0,
+                        int W0, const char* hname, const char* wname) {
+    PPMS_REQUIRE(left && right && m && lut, "%s: null view, matrix or table pointer", who);
+    PPMS_REQUIRE(N > 0 && H0 > 0 && W0 > 0, "%s: N = %d, %s = %d, %s = %d must be positive", who, N, hname, H0, wname, W0);
     const int Hc = (H0 + 1) / 2, Wc = (W0 + 1) / 2;                        // chroma planes: ceil(H0 / 2) x ceil(W0 / 2)
     const ppms_yuv_view* views[2] = {left, right};
     for (int s = 0; s < 2; ++s) {
         const ppms_yuv_view& v = *views[s];
         const char* side = s == 0 ? "left" : "right";
-        PPMS_REQUIRE(v.y && v.u && v.v, "video_ingest_yuv420: null plane pointer in the %s view", side);
-        PPMS_REQUIRE(v.step_c == 1 || v.step_c == 2, "video_ingest_yuv420: %s step_c = %d must be 1 (planar) or 2 (interleaved)", side, v.step_c);
-        PPMS_REQUIRE(v.reserved == 0, "video_ingest_yuv420: %s view: reserved = %d must be 0", side, v.reserved);
+        PPMS_REQUIRE(v.y && v.u && v.v, "%s: null plane pointer in the %s view", who, side);
+        PPMS_REQUIRE(v.step_c == 1 || v.step_c == 2, "%s: %s step_c = %d must be 1 (planar) or 2 (interleaved)", who, side, v.step_c);
+        PPMS_REQUIRE(v.reserved == 0, "%s: %s view: reserved = %d must be 0", who, side, v.reserved);
         const int64_t row_c = (int64_t)v.step_c * (Wc - 1) + 1;            // bytes from a chroma row's first sample to its last
-        PPMS_REQUIRE(v.pitch_y >= W0, "video_ingest_yuv420: %s pitch_y = %d is less than W0 = %d", side, v.pitch_y, W0);
-        PPMS_REQUIRE(v.pitch_c >= row_c, "video_ingest_yuv420: %s pitch_c = %d is less than a chroma row's %lld bytes", side, v.pitch_c, (long long)row_c);
-        PPMS_REQUIRE(v.frame_stride_y >= (int64_t)(H0 - 1) * v.pitch_y + W0, "video_ingest_yuv420: %s frame_stride_y = %lld is less than a luma plane", side,
+        PPMS_REQUIRE(v.pitch_y >= W0, "%s: %s pitch_y = %d is less than %s = %d", who, side, v.pitch_y, wname, W0);
+        PPMS_REQUIRE(v.pitch_c >= row_c, "%s: %s pitch_c = %d is less than a chroma row's %lld bytes", who, side, v.pitch_c, (long long)row_c);
+        PPMS_REQUIRE(v.frame_stride_y >= (int64_t)(H0 - 1) * v.pitch_y + W0, "%s: %s frame_stride_y = %lld is less than a luma plane", who, side,
                      (long long)v.frame_stride_y);
-        PPMS_REQUIRE(v.frame_stride_c >= (int64_t)(Hc - 1) * v.pitch_c + row_c, "video_ingest_yuv420: %s frame_stride_c = %lld is less than a chroma plane",
-                     side, (long long)v.frame_stride_c);
+        PPMS_REQUIRE(v.frame_stride_c >= (int64_t)(Hc - 1) * v.pitch_c + row_c, "%s: %s frame_stride_c = %lld is less than a chroma plane", who, side,
+                     (long long)v.frame_stride_c);
     }
-    PPMS_REQUIRE(m->shift >= 8 && m->shift <= 20, "video_ingest_yuv420: shift = %d must lie in [8, 20]", m->shift);
-    PPMS_REQUIRE(m->reserved == 0, "video_ingest_yuv420: matrix: reserved = %d must be 0", m->reserved);
+    PPMS_REQUIRE(m->shift >= 8 && m->shift <= 20, "%s: shift = %d must lie in [8, 20]", who, m->shift);
+    PPMS_REQUIRE(m->reserved == 0, "%s: matrix: reserved = %d must be 0", who, m->reserved);
     // coefficients below 4.0 keep every sum of the conversion inside 32 bits: 2^22 (255 + 128 + 128) + 2^19 < 2^31 at shift = 20
     const int32_t lim = 4 << m->shift;
     PPMS_REQUIRE(m->y_off >= 0 && m->y_off <= 255 && m->cy >= 0 && m->cy < lim && m->crv >= 0 && m->crv < lim && m->cgu >= 0 && m->cgu < lim && m->cgv >= 0 &&
                      m->cgv < lim && m->cbu >= 0 && m->cbu < lim,
-                 "video_ingest_yuv420: y_off must lie in [0, 255] and every coefficient in [0, 4 << shift)");
+                 "%s: y_off must lie in [0, 255] and every coefficient in [0, 4 << shift)", who);
+    return PPMS_OK;
+}
+
+extern "C" int ppms_video_ingest_yuv420(const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m, int N, int H0, int W0, int pad_left,
+                                        int pad_top, int H, int W, const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream) {
+    if (const int rc = yuv420_check("video_ingest_yuv420", left, right, m, lut, N, H0, W0, "H0", "W0")) return rc;
     return video_ingest_launch("video_ingest_yuv420", yuv420_source{*left, *right, *m, N}, N, H0, W0, pad_left, pad_top, H, W, lut, dst_fnet, dst_cnet, stream);
+}
+
+extern "C" int ppms_remap_struct_size(int* view) {
+    if (view) *view = (int)sizeof(ppms_remap_view);
+    return PPMS_OK;
+}
+
+// what both remap entry points check about the two maps of a W0 columns wide rectified frame
+static int remap_check(const char* who, const ppms_remap_view* lmap, const ppms_remap_view* rmap, int W0) {
+    PPMS_REQUIRE(lmap && rmap, "%s: null map pointer (lmap, rmap)", who);
+    const ppms_remap_view* maps[2] = {lmap, rmap};
+    for (int s = 0; s < 2; ++s) {
+        const ppms_remap_view& v = *maps[s];
+        const char* side = s == 0 ? "lmap" : "rmap";
+        PPMS_REQUIRE(v.xy && v.frac, "%s: null xy or frac pointer in %s", who, side);
+        PPMS_REQUIRE(v.pitch >= W0, "%s: %s pitch = %d is less than W0 = %d", who, side, v.pitch, W0);
+        PPMS_REQUIRE(v.hs >= 1 && v.hs <= 32768 && v.ws >= 1 && v.ws <= 32768, "%s: %s source frame hs = %d, ws = %d must lie in [1, 32768]", who, side,
+                     v.hs, v.ws);
+        PPMS_REQUIRE(v.border == 0 || v.border == 1, "%s: %s border = %d must be 0 (replicate) or 1 (constant)", who, side, v.border);
+        PPMS_REQUIRE(v.fill >= 0 && v.fill <= 255, "%s: %s fill = %d must lie in [0, 255]", who, side, v.fill);
+        PPMS_REQUIRE(v.reserved == 0, "%s: %s reserved = %d must be 0", who, side, v.reserved);
+        PPMS_REQUIRE(((uintptr_t)v.xy & 3) == 0 && ((uintptr_t)v.frac & 1) == 0, "%s: %s misaligned pointer: xy needs 4 bytes, frac 2", who, side);
+    }
+    PPMS_REQUIRE(lmap->hs == rmap->hs && lmap->ws == rmap->ws, "%s: lmap and rmap differ in hs, ws: %d x %d and %d x %d", who, lmap->hs, lmap->ws, rmap->hs,
+                 rmap->ws);
+    return PPMS_OK;
+}
+
+extern "C" int ppms_video_ingest_u8_remap(const uint8_t* left, const uint8_t* right, int64_t frame_stride, const ppms_remap_view* lmap,
+                                          const ppms_remap_view* rmap, int N, int H0, int W0, int pad_left, int pad_top, int H, int W, const float* lut,
+                                          ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream) {
+    const char* who = "video_ingest_u8_remap";
+    PPMS_REQUIRE(left && right, "%s: null source pointer", who);
+    if (const int rc = remap_check(who, lmap, rmap, W0)) return rc;
+    const int hs = lmap->hs, ws = lmap->ws;
+    PPMS_REQUIRE(frame_stride >= (int64_t)3 * hs * ws, "%s: frame_stride = %lld is less than a source frame's 3 * hs * ws bytes", who, (long long)frame_stride);
+    const remapped_source<rgb_planes_source> source{rgb_planes_source{left, right, frame_stride, N, hs, ws}, *lmap, *rmap, N};
+    return video_ingest_launch(who, source, N, H0, W0, pad_left, pad_top, H, W, lut, dst_fnet, dst_cnet, stream);
+}
+
+extern "C" int ppms_video_ingest_yuv420_remap(const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m, const ppms_remap_view* lmap,
+                                              const ppms_remap_view* rmap, int N, int H0, int W0, int pad_left, int pad_top, int H, int W, const float* lut,
+                                              ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream) {
+    const char* who = "video_ingest_yuv420_remap";
+    if (const int rc = remap_check(who, lmap, rmap, W0)) return rc;
+    if (const int rc = yuv420_check(who, left, right, m, lut, N, lmap->hs, lmap->ws, "hs", "ws")) return rc;
+    const remapped_source<yuv420_source> source{yuv420_source{*left, *right, *m, N}, *lmap, *rmap, N};
+    return video_ingest_launch(who, source, N, H0, W0, pad_left, pad_top, H, W, lut, dst_fnet, dst_cnet, stream);
 }
 
 extern "C" int ppms_sp_s2d(ppms_sp src, ppms_sp dst, int N, int H, int W, void* stream) {

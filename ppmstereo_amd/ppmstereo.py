@@ -577,17 +577,27 @@ class _ByteFrames:
     """uint8 frames of both views on the device as ppms_video_ingest_u8 reads them: ``left`` / ``right`` start at frame 0 of a view, frame
     n of a view lies ``frame_stride`` bytes further; (H0, W0) frames go to the padded size with ``pad_left`` / ``pad_top`` in front."""
 
-    def __init__(self, left: torch.Tensor, right: torch.Tensor, frame_stride: int, n: int, h0: int, w0: int, pad_left: int = 0, pad_top: int = 0):
+    def __init__(self, left: torch.Tensor, right: torch.Tensor, frame_stride: int, n: int, h0: int, w0: int, pad_left: int = 0, pad_top: int = 0,
+                 rectify: Optional["StereoRectifier"] = None):
         self.left, self.right, self.frame_stride, self.n = left, right, int(frame_stride), int(n)
         self.h0, self.w0, self.pad_left, self.pad_top = int(h0), int(w0), int(pad_left), int(pad_top)
+        self.rectify = rectify                                  # on the frames' device: they are raw frames of its source size, (h0, w0) its rectified size
 
     def ingest(self, dst_fnet: L.SP, dst_cnet: L.SP, h: int, w: int) -> None:
         """One launch on the current stream: both encoders' first-layer operands of the n frames padded to h x w."""
+        if self.rectify is not None:
+            lmap, rmap = self.rectify.left.view_struct(), self.rectify.right.view_struct()       # host structs: read before the call returns
+            L.check(L.load().ppms_video_ingest_u8_remap(self.left.data_ptr(), self.right.data_ptr(), self.frame_stride, lmap, rmap, self.n, self.h0, self.w0,
+                                                        self.pad_left, self.pad_top, h, w, byte_lut(self.left.device).data_ptr(), dst_fnet, dst_cnet,
+                                                        L.stream_ptr()))
+            return
         L.check(L.load().ppms_video_ingest_u8(self.left.data_ptr(), self.right.data_ptr(), self.frame_stride, self.n, self.h0, self.w0, self.pad_left,
                                               self.pad_top, h, w, byte_lut(self.left.device).data_ptr(), dst_fnet, dst_cnet, L.stream_ptr()))
 
     def held(self):
         """The tensors the launch reads (for record_stream)."""
+        if self.rectify is not None:
+            return (self.left, self.right) + self.rectify.tensors()
         return self.left, self.right
 
 
@@ -758,18 +768,175 @@ class YUVStereoVideo:
 class _YUVPlanes:
     """``_ByteFrames`` for a YUVStereoVideo on the device: ppms_video_ingest_yuv420 converts, pads and lays out both views in one launch."""
 
-    def __init__(self, video: YUVStereoVideo, pad_left: int = 0, pad_top: int = 0):
+    def __init__(self, video: YUVStereoVideo, pad_left: int = 0, pad_top: int = 0, rectify: Optional["StereoRectifier"] = None):
         self.video, self.pad_left, self.pad_top = video, int(pad_left), int(pad_top)
+        self.rectify = rectify                                  # on the video's device: the video holds raw frames of its source size
 
     def ingest(self, dst_fnet: L.SP, dst_cnet: L.SP, h: int, w: int) -> None:
         v = self.video
         left, right, m = v.left.view_struct(), v.right.view_struct(), v.left.matrix()      # host structs: read before the call returns
+        if self.rectify is not None:
+            r = self.rectify
+            L.check(L.load().ppms_video_ingest_yuv420_remap(left, right, m, r.left.view_struct(), r.right.view_struct(), len(v), r.height, r.width,
+                                                            self.pad_left, self.pad_top, h, w, byte_lut(v.left.device).data_ptr(), dst_fnet, dst_cnet,
+                                                            L.stream_ptr()))
+            return
         L.check(L.load().ppms_video_ingest_yuv420(left, right, m, len(v), v.height, v.width, self.pad_left, self.pad_top, h, w,
                                                   byte_lut(v.left.device).data_ptr(), dst_fnet, dst_cnet, L.stream_ptr()))
 
     def held(self):
         v = self.video
-        return v.left.y, v.left.u, v.left.v, v.right.y, v.right.u, v.right.v
+        planes = (v.left.y, v.left.u, v.left.v, v.right.y, v.right.u, v.right.v)
+        return planes if self.rectify is None else planes + self.rectify.tensors()
+
+
+_BORDERS = {"replicate": L.BORDER_REPLICATE, "constant": L.BORDER_CONSTANT}
+
+
+class RectifyMap:
+    """One view's undistort + rectify (+ resize) map in fixed point, as ppms_video_ingest_u8_remap / _yuv420_remap read it (the arithmetic:
+    include/ppms.h): for every pixel of the RECTIFIED frame H0 x W0, ``xy`` int16 (H0, W0, 2) holds the integer source coordinate (x0, y0), x
+    first, and ``frac`` int16 or uint16 (H0, W0) its fraction in 1/32 pixel, fx | fy << 5 -- the layout OpenCV documents for
+    ``convertMaps(..., CV_16SC2)`` (not compared with OpenCV).  ``source_size`` = (Hs, Ws) of the raw frames; ``border`` "replicate" or
+    "constant" (a tap outside the frame is ``fill``, one byte for R, G and B).  Both tensors may be row-pitched views with ONE pitch
+    (``xy.stride(0) == 2 * frac.stride(0)``): the class reads ``data_ptr()`` and ``stride()`` and never copies.  ``apply_u8`` is the definition
+    of the remap.  Not covered: computing maps from calibration data, interpolation other than bilinear."""
+
+    def __init__(self, xy: torch.Tensor, frac: torch.Tensor, source_size, border: str = "replicate", fill: int = 0, _checked: bool = False):
+        if not torch.is_tensor(xy) or xy.dtype != torch.int16 or xy.dim() != 3 or xy.shape[2] != 2:
+            raise ValueError("RectifyMap: xy must be an int16 tensor (H0, W0, 2)")
+        if not torch.is_tensor(frac) or frac.dtype not in (torch.int16, torch.uint16) or frac.dim() != 2:
+            raise ValueError("RectifyMap: frac must be an int16 or uint16 tensor (H0, W0)")
+        h0, w0 = frac.shape
+        if h0 < 1 or w0 < 1 or tuple(xy.shape[:2]) != (h0, w0):
+            raise ValueError(f"RectifyMap: xy {tuple(xy.shape)} and frac {tuple(frac.shape)} must cover one non-empty frame")
+        if xy.device != frac.device:
+            raise ValueError("RectifyMap: xy and frac must be on one device")
+        frac = frac.view(torch.int16)                               # the same 16 bits
+        if xy.stride(2) != 1 or (w0 > 1 and (xy.stride(1) != 2 or frac.stride(1) != 1)):
+            raise ValueError(f"RectifyMap: the last dimensions must be contiguous (xy strides {xy.stride()}, frac strides {frac.stride()})")
+        # a size-1 dimension's stride is arbitrary: the smallest the kernel accepts stands in for it
+        pitch = frac.stride(0) if h0 > 1 else w0
+        if pitch < w0 or (h0 > 1 and xy.stride(0) != 2 * pitch):
+            raise ValueError(f"RectifyMap: xy and frac need one row pitch >= W0 (xy strides {xy.stride()}, frac strides {frac.stride()})")
+        if xy.data_ptr() % 4 or frac.data_ptr() % 2:
+            raise ValueError("RectifyMap: xy must start at a multiple of 4 bytes, frac of 2")
+        try:
+            hs, ws = (int(v) for v in source_size)
+        except (TypeError, ValueError):
+            raise ValueError(f"RectifyMap: source_size = {source_size!r} must be (Hs, Ws)") from None
+        if not (1 <= hs <= 32768 and 1 <= ws <= 32768):
+            raise ValueError(f"RectifyMap: source_size = ({hs}, {ws}) must lie in 1..32768")
+        if border not in _BORDERS:
+            raise ValueError(f"RectifyMap: border {border!r}; one of {sorted(_BORDERS)}")
+        if not 0 <= int(fill) <= 255:
+            raise ValueError(f"RectifyMap: fill = {fill} must be a byte")
+        if not _checked and bool(((frac < 0) | (frac > 1023)).any()):      # once: copies made by ``to`` hold the same values
+            raise ValueError("RectifyMap: frac holds values above 1023 (fx | fy << 5 with fx, fy in 0..31)")
+        self.xy, self.frac, self.pitch = xy, frac, int(pitch)
+        self.height, self.width, self.source_height, self.source_width = int(h0), int(w0), hs, ws
+        self.border, self.fill = border, int(fill)
+        self._on: Dict[torch.device, "RectifyMap"] = {xy.device: self}
+
+    @classmethod
+    def from_float(cls, map_x: torch.Tensor, map_y: torch.Tensor, source_size, border: str = "replicate", fill: int = 0) -> "RectifyMap":
+        """From float source coordinates (H0, W0) per rectified pixel (what ``initUndistortRectifyMap`` gives as CV_32FC1): per coordinate
+        q = round_half_even(v * 32), saturated so that q >> 5 stays an int16; then x0 = q >> 5, fx = q & 31 (floor and remainder)."""
+        if not (torch.is_tensor(map_x) and torch.is_tensor(map_y) and map_x.is_floating_point() and map_y.is_floating_point()
+                and map_x.dim() == 2 and map_x.shape == map_y.shape):
+            raise ValueError("RectifyMap.from_float: map_x and map_y must be floating-point tensors of one shape (H0, W0)")
+        if bool(torch.isnan(map_x).any()) or bool(torch.isnan(map_y).any()):
+            raise ValueError("RectifyMap.from_float: a coordinate is NaN")
+        qx, qy = (torch.round(m.double() * 32.0).clamp(-32768 * 32, 32767 * 32 + 31).to(torch.int64) for m in (map_x, map_y))
+        xy = torch.stack([qx >> 5, qy >> 5], dim=-1).to(torch.int16)
+        frac = ((qx & 31) | ((qy & 31) << 5)).to(torch.int16)
+        return cls(xy, frac, source_size, border, fill, _checked=True)
+
+    @classmethod
+    def identity(cls, h: int, w: int, device=None) -> "RectifyMap":
+        """The map that copies an h x w frame."""
+        ys, xs = torch.meshgrid(torch.arange(h, device=device), torch.arange(w, device=device), indexing="ij")
+        return cls(torch.stack([xs, ys], dim=-1).to(torch.int16), torch.zeros((h, w), dtype=torch.int16, device=device), (h, w), _checked=True)
+
+    @property
+    def device(self) -> torch.device:
+        return self.xy.device
+
+    def to(self, device) -> "RectifyMap":
+        """This map on ``device`` (6 bytes per rectified pixel, dense); made once per device and kept."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device not in self._on:
+            there = RectifyMap(self.xy.to(device).contiguous(), self.frac.to(device).contiguous(), (self.source_height, self.source_width), self.border,
+                               self.fill, _checked=True)
+            there._on = self._on
+            self._on[device] = there
+        return self._on[device]
+
+    def view_struct(self) -> L.RemapView:
+        """The ``ppms_remap_view`` of this map."""
+        return L.RemapView(self.xy.data_ptr(), self.frac.data_ptr(), self.pitch, self.source_height, self.source_width, _BORDERS[self.border], self.fill, 0)
+
+    def apply_u8(self, rgb: torch.Tensor) -> torch.Tensor:
+        """uint8 (N, 3, Hs, Ws) -> uint8 (N, 3, H0, W0) on ``rgb``'s device: the remap of include/ppms.h in torch integer ops -- what the feature
+        means by the rectified bytes (the kernels' operands are ppms_video_ingest_u8's on them), and the path where the kernels cannot be used."""
+        hs, ws = self.source_height, self.source_width
+        if not torch.is_tensor(rgb) or rgb.dtype != torch.uint8 or rgb.dim() != 4 or tuple(rgb.shape[1:]) != (3, hs, ws):
+            raise ValueError(f"RectifyMap.apply_u8: uint8 frames (N, 3, {hs}, {ws}) expected, got "
+                             f"{tuple(rgb.shape) if torch.is_tensor(rgb) else type(rgb).__name__}")
+        m = self.to(rgb.device)
+        x0, y0 = m.xy[..., 0].to(torch.int64), m.xy[..., 1].to(torch.int64)
+        f = m.frac.to(torch.int32)
+        fx, fy = f & 31, (f >> 5) & 31
+        acc = torch.full((rgb.shape[0], 3, self.height, self.width), 512, dtype=torch.int32, device=rgb.device)
+        for dy in (0, 1):
+            for dx in (0, 1):
+                yy, xx = y0 + dy, x0 + dx
+                cy, cx = yy.clamp(0, hs - 1), xx.clamp(0, ws - 1)
+                p = rgb[:, :, cy, cx].to(torch.int32)             # clamped addresses in both modes
+                if self.border == "constant":
+                    p = torch.where((cy != yy) | (cx != xx), torch.full_like(p, self.fill), p)
+                acc += ((fx if dx else 32 - fx) * (fy if dy else 32 - fy)) * p
+        return (acc >> 10).to(torch.uint8)
+
+
+class StereoRectifier:
+    """The two views' ``RectifyMap``s of one rig -- what ``rectify=`` of ``PPMStereo.forward`` / ``forward_batch_test`` takes: one rectified size
+    (``height`` x ``width``), one source size (``source_height`` x ``source_width``), one device.  ``to(device)`` is kept per device."""
+
+    def __init__(self, left: RectifyMap, right: RectifyMap):
+        if not isinstance(left, RectifyMap) or not isinstance(right, RectifyMap):
+            raise TypeError("StereoRectifier: two RectifyMaps expected")
+        if (left.height, left.width) != (right.height, right.width):
+            raise ValueError(f"StereoRectifier: the rectified sizes differ: {(left.height, left.width)} and {(right.height, right.width)}")
+        if (left.source_height, left.source_width) != (right.source_height, right.source_width):
+            raise ValueError(f"StereoRectifier: the source sizes differ: {(left.source_height, left.source_width)} and "
+                             f"{(right.source_height, right.source_width)}")
+        if left.device != right.device:
+            raise ValueError("StereoRectifier: both maps must be on one device")
+        self.left, self.right = left, right
+        self.height, self.width = left.height, left.width
+        self.source_height, self.source_width = left.source_height, left.source_width
+
+    @property
+    def device(self) -> torch.device:
+        return self.left.device
+
+    def to(self, device) -> "StereoRectifier":
+        left, right = self.left.to(device), self.right.to(device)
+        return self if left is self.left and right is self.right else StereoRectifier(left, right)
+
+    def tensors(self):
+        """The four map tensors (for record_stream)."""
+        return self.left.xy, self.left.frac, self.right.xy, self.right.frac
+
+    def apply_u8(self, left: torch.Tensor, right: torch.Tensor):
+        return self.left.apply_u8(left), self.right.apply_u8(right)
+
+    def check_source(self, who: str, h: int, w: int) -> None:
+        if (int(h), int(w)) != (self.source_height, self.source_width):
+            raise ValueError(f"{who}: the frames are {int(h)} x {int(w)}, the rectification maps were made for {self.source_height} x {self.source_width}")
 
 
 class PPMStereo(PPMStereoHotPath):
@@ -903,7 +1070,8 @@ class PPMStereo(PPMStereoHotPath):
 
     @torch.no_grad()
     def forward(self, image1: torch.Tensor, image2: torch.Tensor, flow_init=None, iters: int = 10, test_mode: bool = False, pipeline=None,
-                diagnostics: Optional[dict] = None, output: Optional[OutputSpec] = None, crop=None, frames=None):
+                diagnostics: Optional[dict] = None, output: Optional[OutputSpec] = None, crop=None, frames=None,
+                rectify: Optional[StereoRectifier] = None):
         """PPMStereo.forward (ppmstereo.py:601-804): image (b, T, 3, H, W) in [0, 255], H, W multiples of 32 (b = 1: the device-resident
         cascade; b > 1: the reference's glue around the batched forward_update_block).  Float images as in the reference, or both uint8:
         with this package's encoders the bytes go through ONE kernel (ppms_video_ingest_u8) to the operands of the first convolutions --
@@ -915,9 +1083,16 @@ class PPMStereo(PPMStereoHotPath):
         diagnostics (b = 1): a dict that receives ``["attn_redo"]``, the per-scale fix-up accounting of the memory read-out (see ``cascade``).
         output (test_mode, b = 1): an ``OutputSpec`` -- the call returns a dict of device tensors (1, n, 1, H0, W0) under "disparity", "depth"
         and "uncertainties" as the spec asks, written by ONE ppms_disparity_egress launch behind the last iteration (no float32 full-resolution
-        tensor is made); crop = (pad_left, pad_top, H0, W0) inside the frame (default: the whole frame), frames = (from, to) (default: all)."""
+        tensor is made); crop = (pad_left, pad_top, H0, W0) inside the frame (default: the whole frame), frames = (from, to) (default: all).
+        rectify: a ``StereoRectifier`` -- the images are the RAW frames of an unrectified rig, two uint8 device tensors (1, T, 3, Hs, Ws) or two
+        ``YUVFrames`` of its source size Hs x Ws; ONE kernel (ppms_video_ingest_u8_remap / ppms_video_ingest_yuv420_remap) undistorts, rectifies and
+        writes the same operands -- the bits of ``forward`` on ``RectifyMap.apply_u8`` of each view's RGB bytes.  H, W above are then the rectified
+        size, and so are the outputs'.  Float images raise TypeError (the remap reads decoded bytes), b > 1 NotImplementedError, another frame
+        size than the maps' ValueError.  None (default): the calls above, launch for launch."""
         if flow_init is not None:
             raise NotImplementedError("flow_init: the reference's own path for it reads undefined state (ppmstereo.py:691-693, 763)")
+        if rectify is not None:
+            self._check_rectify("PPMStereo.forward", rectify, image1, image2)
         if self.fnet is None or self.cnet is None:
             raise RuntimeError("PPMStereo.forward needs the encoders: pass fnet= / cnet= (outside the hot path, SURVEY.md section 8 f3-f5)")
         egress = None
@@ -928,7 +1103,9 @@ class PPMStereo(PPMStereoHotPath):
         elif crop is not None or frames is not None:
             raise ValueError("PPMStereo.forward: crop= and frames= select what output= writes; without output= they have no meaning")
         if isinstance(image1, YUVFrames) or isinstance(image2, YUVFrames):
-            return self._forward_yuv(image1, image2, iters, test_mode, pipeline, diagnostics, egress)
+            return self._forward_yuv(image1, image2, iters, test_mode, pipeline, diagnostics, egress, rectify)
+        if rectify is not None:
+            return self._forward_raw_u8(image1, image2, iters, test_mode, pipeline, diagnostics, egress, rectify)
         if torch.is_tensor(image1) and torch.is_tensor(image2) and (image1.dtype == torch.uint8) != (image2.dtype == torch.uint8):
             raise TypeError(f"PPMStereo.forward: image1 is {image1.dtype} and image2 is {image2.dtype}; both views must be uint8 or both floating point")
         b, T, c, h, w = image1.shape
@@ -946,17 +1123,58 @@ class PPMStereo(PPMStereoHotPath):
                 images = (image1.float(), image2.float())
         return self._forward_images(images, b, T, h, w, image1.device, iters, test_mode, pipeline, diagnostics, egress)
 
-    def _forward_yuv(self, image1, image2, iters: int, test_mode: bool, pipeline, diagnostics, egress=None):
-        """``forward`` on two ``YUVFrames`` on the device: b = 1, T = their frame count, the frame size as it is."""
+    @staticmethod
+    def _check_rectify(who: str, rectify, *views) -> None:
+        """What ``rectify=`` asks of the raw views (tensors (..., 3, Hs, Ws), ``YUVFrames`` or a ``YUVStereoVideo``); touches no device."""
+        if not isinstance(rectify, StereoRectifier):
+            raise TypeError(f"{who}: rectify must be a StereoRectifier, got {type(rectify).__name__}")
+        for v in views:
+            if isinstance(v, (YUVFrames, YUVStereoVideo)):
+                rectify.check_source(who, v.height, v.width)
+            elif torch.is_tensor(v):
+                if v.dtype != torch.uint8:
+                    raise TypeError(f"{who}: rectify= reads decoded bytes (uint8 frames or YUVFrames), got {v.dtype}; rectify float images before the call")
+                if v.dim() != 5:
+                    raise ValueError(f"{who}: a raw uint8 video has 5 dimensions, got {tuple(v.shape)}")
+                rectify.check_source(who, v.shape[-2], v.shape[-1])
+            else:
+                raise TypeError(f"{who}: rectify= takes uint8 tensors or YUV frames, got {type(v).__name__}")
+
+    def _forward_raw_u8(self, image1, image2, iters: int, test_mode: bool, pipeline, diagnostics, egress, rectify: StereoRectifier):
+        """``forward`` on two raw uint8 videos (1, T, 3, Hs, Ws) on the device with ``rectify=`` (checked by ``_check_rectify``)."""
+        b, T, c, hs, ws = image1.shape
+        if image2.shape != image1.shape or c != 3:
+            raise ValueError(f"PPMStereo.forward: two uint8 videos of one shape (1, T, 3, Hs, Ws) expected, got {tuple(image1.shape)} and {tuple(image2.shape)}")
+        if b != 1:
+            raise NotImplementedError("PPMStereo.forward: rectify= serves b = 1")
+        L.require_gpu(image1, image2)
+        rectify = rectify.to(image1.device)
+        if self._hip_encoders():
+            images = _ByteFrames(image1.contiguous(), image2.contiguous(), 3 * hs * ws, T, rectify.height, rectify.width, rectify=rectify)
+            return self._forward_images(images, 1, T, rectify.height, rectify.width, image1.device, iters, test_mode, pipeline, diagnostics, egress)
+        # encoder callables of the caller: the frames are rectified on the device and take the float path
+        out = {} if egress is None else dict(output=egress.spec, crop=egress.crop, frames=egress.frames)
+        left, right = rectify.apply_u8(image1[0], image2[0])
+        return self.forward(left.float()[None], right.float()[None], iters=iters, test_mode=test_mode, pipeline=pipeline, diagnostics=diagnostics, **out)
+
+    def _forward_yuv(self, image1, image2, iters: int, test_mode: bool, pipeline, diagnostics, egress=None, rectify: Optional[StereoRectifier] = None):
+        """``forward`` on two ``YUVFrames`` on the device: b = 1, T = their frame count, the frame size as it is (with ``rectify``: its rectified size)."""
         if not (isinstance(image1, YUVFrames) and isinstance(image2, YUVFrames)):
             raise TypeError(f"PPMStereo.forward: image1 is {type(image1).__name__} and image2 is {type(image2).__name__}; both views must be YUVFrames or both tensors")
         video = YUVStereoVideo(image1, image2)
         L.require_gpu(image1.y, image2.y)
+        out = {} if egress is None else dict(output=egress.spec, crop=egress.crop, frames=egress.frames)
+        if rectify is not None:
+            rectify = rectify.to(image1.device)
+            if self._hip_encoders():
+                return self._forward_images(_YUVPlanes(video, rectify=rectify), 1, len(video), rectify.height, rectify.width, image1.device, iters, test_mode,
+                                            pipeline, diagnostics, egress)
+            left, right = rectify.apply_u8(image1.to_rgb_u8(), image2.to_rgb_u8())
+            return self.forward(left.float()[None], right.float()[None], iters=iters, test_mode=test_mode, pipeline=pipeline, diagnostics=diagnostics, **out)
         if self._hip_encoders():
             return self._forward_images(_YUVPlanes(video), 1, len(video), video.height, video.width, image1.device, iters, test_mode, pipeline, diagnostics,
                                         egress)
         # encoder callables of the caller: they get what they get for a float video
-        out = {} if egress is None else dict(output=egress.spec, crop=egress.crop, frames=egress.frames)
         return self.forward(image1.to_rgb_u8().float()[None], image2.to_rgb_u8().float()[None], iters=iters, test_mode=test_mode, pipeline=pipeline,
                             diagnostics=diagnostics, **out)
 
@@ -1029,7 +1247,7 @@ class PPMStereo(PPMStereoHotPath):
 
     @torch.no_grad()
     def forward_batch_test(self, batch_dict: Dict, kernel_size: int = 20, iters: int = 20, device=None, shard_ranks: bool = False,
-                           diagnostics: bool = False, output: Optional[OutputSpec] = None):
+                           diagnostics: bool = False, output: Optional[OutputSpec] = None, rectify: Optional[StereoRectifier] = None):
         """PPMStereo.forward_batch_test (ppmstereo.py:238-320): batch_dict["stereo_video"] (N, 2, 3, H, W) on the host;
         per window: InputPadder(divis_by=32), one host->device copy, forward(test_mode=True), unpad, one device->host copy;
         a uint8 video (host or device) is copied as bytes -- a quarter of the float video's -- and, with this package's encoders, padded and
@@ -1047,15 +1265,24 @@ class PPMStereo(PPMStereoHotPath):
         those are copied device -> host, straight into their slice of pinned (N, 1, H, W) results of the planes' dtypes (uint16 disparity and
         uint8 confidence: 3 bytes per pixel and kept frame, where the default path copies 8 for every frame of the window).  Returns
         {"disparity", "depth" when asked, "uncertainties" unless its format is None}.  Not with ``shard_ranks``.  None (default): the float32
-        path above, launch for launch."""
+        path above, launch for launch.
+        rectify: a ``StereoRectifier`` -- the video holds the RAW frames of an unrectified rig, (N, 2, 3, Hs, Ws) uint8 or a ``YUVStereoVideo`` of
+        its source size Hs x Ws.  Each window's raw bytes are copied as above, the maps once per call (6 bytes per rectified pixel and view), and
+        ppms_video_ingest_u8_remap / ppms_video_ingest_yuv420_remap undistort, rectify, pad and normalise in the one ingest launch: the bits of
+        the call on the uint8 video of ``RectifyMap.apply_u8``.  H x W of the results (and of the ``InputPadder``) is the rectified size.  A float
+        video raises TypeError, another frame size than the maps' ValueError.  None (default): the paths above, launch for launch."""
         if output is not None:
             if not isinstance(output, OutputSpec):
                 raise TypeError(f"forward_batch_test: output must be an OutputSpec, got {type(output).__name__}")
             if shard_ranks:
                 raise NotImplementedError("forward_batch_test: output= with shard_ranks=True is not served: dist.gather_kept_frames moves float32")
         video = batch_dict["stereo_video"]
+        if rectify is not None:
+            self._check_rectify("forward_batch_test", rectify, video)
         num_ims = len(video)
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if rectify is not None:
+            rectify = rectify.to(dev)                             # the maps cross once per call, not once per window
         disp_preds, uncertainties = [], []
         diag = {} if diagnostics else None
         plan = window_plan(num_ims, kernel_size)
@@ -1069,11 +1296,11 @@ class PPMStereo(PPMStereoHotPath):
             for wi, (start, stop, keep_from, keep_to) in enumerate(plan):
                 if wi % world != rank:
                     continue
-                d, u, padder = self._window_forward(video, start, stop, dev, iters, None, diag)       # one host -> device copy per window (see below)
+                d, u, padder = self._window_forward(video, start, stop, dev, iters, None, diag, rectify=rectify)   # one host -> device copy per window (see below)
                 d, u = padder.unpad(d[0]), padder.unpad(u[0])               # (T, 1, H0, W0)
                 mine_d.append((firsts[wi], d[keep_from:keep_to].abs()[:, :1]))
                 mine_u.append((firsts[wi], u[keep_from:keep_to].abs()[:, :1]))
-            H0, W0 = (video.height, video.width) if isinstance(video, YUVStereoVideo) else video.shape[-2:]
+            H0, W0 = self._result_size(video, rectify)
             disp = D.gather_kept_frames(mine_d, num_ims, H0, W0)
             unc = D.gather_kept_frames(mine_u, num_ims, H0, W0)
             out = {"disparity": disp.cpu(), "uncertainties": unc.cpu()}
@@ -1085,7 +1312,7 @@ class PPMStereo(PPMStereoHotPath):
         pipe = ClipPipeline(dev) if len(plan) > 1 else None
         pending = None
         if output is not None:
-            H0, W0 = (video.height, video.width) if isinstance(video, YUVStereoVideo) else video.shape[-2:]
+            H0, W0 = self._result_size(video, rectify)
             host = output.empty(num_ims, int(H0), int(W0), "cpu", pin_memory=True)           # allocated once; every window fills its slice
 
             def collect_planes(item):
@@ -1098,7 +1325,7 @@ class PPMStereo(PPMStereoHotPath):
 
             with torch.cuda.device(dev):
                 for start, stop, keep_from, keep_to, dst_from, dst_to in egress_plan(plan):
-                    planes = self._window_forward(video, start, stop, dev, iters, pipe, diag, output, (keep_from, keep_to))
+                    planes = self._window_forward(video, start, stop, dev, iters, pipe, diag, output, (keep_from, keep_to), rectify=rectify)
                     item = (planes, None if pipe is None else pipe.last, dst_from, dst_to)
                     if pending is not None:
                         collect_planes(pending)
@@ -1125,7 +1352,7 @@ class PPMStereo(PPMStereoHotPath):
 
         with torch.cuda.device(dev):
             for start, stop, keep_from, keep_to in plan:
-                d, u, padder = self._window_forward(video, start, stop, dev, iters, pipe, diag)
+                d, u, padder = self._window_forward(video, start, stop, dev, iters, pipe, diag, rectify=rectify)
                 item = (d, u, None if pipe is None else pipe.last, padder, keep_from, keep_to)
                 if pending is not None:
                     collect(pending)
@@ -1137,10 +1364,22 @@ class PPMStereo(PPMStereoHotPath):
         return out
 
 
-def _window_forward(self, video, start: int, stop: int, dev, iters: int, pipe, diag, output: Optional[OutputSpec] = None, keep=None):
+def _result_size(video, rectify: Optional[StereoRectifier]):
+    """(H0, W0) of forward_batch_test's results: the rectified size, or the video's own."""
+    if rectify is not None:
+        return rectify.height, rectify.width
+    return (video.height, video.width) if isinstance(video, YUVStereoVideo) else video.shape[-2:]
+
+
+PPMStereo._result_size = staticmethod(_result_size)
+
+
+def _window_forward(self, video, start: int, stop: int, dev, iters: int, pipe, diag, output: Optional[OutputSpec] = None, keep=None,
+                    rectify: Optional[StereoRectifier] = None):
     """One window of forward_batch_test: frames [start, stop) of the (N, 2, 3, H0, W0) video or the YUVStereoVideo -> (disparity, uncertainty) of the padded
     window, each (1, T, 1, H, W), and the InputPadder that crops them back.  output (an OutputSpec): the window's egress launch crops with that
-    padder's geometry and writes the window-local frames keep = (from, to); the result is then the dict of planes, each (1, n, 1, H0, W0)."""
+    padder's geometry and writes the window-local frames keep = (from, to); the result is then the dict of planes, each (1, n, 1, H0, W0).
+    rectify (a StereoRectifier on dev): the video holds raw frames of its source size; H0 x W0, and so the padder, is its rectified size."""
     def egress(padder):
         if output is None:
             return None
@@ -1153,13 +1392,17 @@ def _window_forward(self, video, start: int, stop: int, dev, iters: int, pipe, d
     if isinstance(win, YUVStereoVideo):
         if self._hip_encoders():
             # the planes stay as the decoder left them: ppms_video_ingest_yuv420 converts, and pads by clamping its source coordinate
-            padder = InputPadder((win.height, win.width), divis_by=32)
+            padder = InputPadder(_result_size(win, rectify), divis_by=32)
             pad_left, pad_top, H, W = padder.geometry()
+            planes = _YUVPlanes(win, pad_left, pad_top, rectify)
             if output is not None:
-                return self._forward_images(_YUVPlanes(win, pad_left, pad_top), 1, len(win), H, W, dev, iters, True, pipe, diag, egress(padder))
-            d, u = self._forward_images(_YUVPlanes(win, pad_left, pad_top), 1, len(win), H, W, dev, iters, True, pipe, diag)
+                return self._forward_images(planes, 1, len(win), H, W, dev, iters, True, pipe, diag, egress(padder))
+            d, u = self._forward_images(planes, 1, len(win), H, W, dev, iters, True, pipe, diag)
             return d, u, padder
-        win = torch.stack([win.left.to_rgb_u8(), win.right.to_rgb_u8()], dim=1).float()    # encoder callables of the caller: the float path
+        rgb = win.left.to_rgb_u8(), win.right.to_rgb_u8()
+        if rectify is not None:
+            rgb = rectify.apply_u8(*rgb)
+        win = torch.stack(rgb, dim=1).float()                   # encoder callables of the caller: the float path
     elif win.dtype == torch.uint8:
         if win.dim() != 5 or win.shape[1] != 2 or win.shape[2] != 3:
             raise ValueError(f"forward_batch_test: a uint8 stereo_video is (N, 2, 3, H, W), got {tuple(video.shape)}")
@@ -1167,13 +1410,18 @@ def _window_forward(self, video, start: int, stop: int, dev, iters: int, pipe, d
             # the bytes stay as they are: ppms_video_ingest_u8 reads both views out of the block and pads by clamping its source coordinate
             win = win.contiguous()
             T, H0, W0 = win.shape[0], win.shape[3], win.shape[4]
+            stride = 6 * H0 * W0
+            if rectify is not None:                              # the block holds raw frames; what is padded is the rectified frame
+                H0, W0 = rectify.height, rectify.width
             padder = InputPadder((H0, W0), divis_by=32)
             pad_left, pad_top, H, W = padder.geometry()
-            frames = _ByteFrames(win[:, 0], win[:, 1], 6 * H0 * W0, T, H0, W0, pad_left, pad_top)
+            frames = _ByteFrames(win[:, 0], win[:, 1], stride, T, H0, W0, pad_left, pad_top, rectify)
             if output is not None:
                 return self._forward_images(frames, 1, T, H, W, dev, iters, True, pipe, diag, egress(padder))
             d, u = self._forward_images(frames, 1, T, H, W, dev, iters, True, pipe, diag)
             return d, u, padder
+        if rectify is not None:
+            win = torch.stack(rectify.apply_u8(win[:, 0], win[:, 1]), dim=1)
         win = win.float()                                        # encoder callables of the caller: the float path from here on
     left, right = win[:, 0], win[:, 1]
     padder = InputPadder(left.shape, divis_by=32)
