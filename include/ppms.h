@@ -356,10 +356,10 @@ int ppms_video_ingest_yuv420_remap(const ppms_yuv_view* left, const ppms_yuv_vie
 int ppms_remap_struct_size(int* view);               /* sizeof(ppms_remap_view) (40): lets a binding verify its layout */
 /* nn.InstanceNorm2d(affine=False) (extractor.py:326-329, 364): per (sample, channel) mean and 1 / sqrt(biased var + eps) over the
  * HW pixels of x (channel-last fp32 [N * HW][ld], a convolution's fp32 output) -> stats[N][C][2] (pixel slices merged in fixed
- * order: deterministic; caller-owned workspace of ppms_instnorm_workspace_bytes); then
+ * order: deterministic; caller-owned 16-B aligned workspace of ppms_instnorm_workspace_bytes); then
  * out = relu?( (x - mean) * rstd + res? ) as split planes (res: optional residual view, e.g. relu(x + y) of extractor.py:345;
  * channels >= C of out are zeroed). */
-int64_t ppms_instnorm_workspace_bytes(int N, int HW, int C);       /* per-slice partial statistics of ppms_instnorm_stats */
+int64_t ppms_instnorm_workspace_bytes(int N, int HW, int C);       /* per-slice partial statistics of ppms_instnorm_stats: 16 bytes per (n, slice, c) */
 int ppms_instnorm_stats(const float* x, int ld, int N, int HW, int C, float eps, float* stats, void* workspace, void* stream);
 int ppms_instnorm_apply(const float* x, int ld, const float* stats, ppms_sp res, int relu, ppms_sp out, int N, int HW, int C, void* stream);
 

@@ -160,10 +160,13 @@ __global__ __launch_bounds__(256) void sp_s2d_kernel(ppms_sp src, ppms_sp dst, i
 
 // ---- InstanceNorm2d(affine=False, eps): per (sample, channel) mean and biased variance over the H*W pixels -------------------
 // x: channel-last fp32 [N*HW][ld] (a conv's fp32 output).  Two launches, deterministic:
-//  1. one workgroup = one sample x 32 channels x one of S pixel slices: slice mean, then slice sum of centred squares (two passes
-//     over an L2-resident slice: no cancellation) -> part[n][s][c] = (mean_s, M2_s);
-//  2. one thread per (sample, channel) merges the S slices in slice order with Chan's update
-//     (mean += d n_b / n, M2 += M2_b + d^2 n_a n_b / n) -> stats[n][c] = (mean, 1 / sqrt(M2 / HW + eps)).
+//  1. one workgroup = one sample x 32 channels x one of S pixel slices: slice mean m_s as fp32 rounds it, then the slice sums of
+//     d = x - m_s and of d^2 (two passes over an L2-resident slice: no cancellation) -> part[n][s][c] = (m_s, M2_s, r_s, -);
+//  2. one thread per (sample, channel) merges the S slices in slice order, in float64, about the first slice's mean m_0:
+//     with e = m_s - m_0: A += n_s e + r_s, Q += M2_s + 2 e r_s + n_s e^2 (the sums of x - m_0 and of its square over the slice, exactly),
+//     mean = m_0 + A / HW, M2 = Q - A^2 / HW -> stats[n][c] = (mean, 1 / sqrt(M2 / HW + eps)).
+// r_s is what fp32 drops from the slice mean.  Without it a map whose mean is large against its spread (|mean| = 1000 sigma) lost 1e-5 of
+// rstd: the differences between slice means, which carry 1 / n_s of the variance, were taken between values rounded at the mean's magnitude.
 static int in_slices_host(int N, int HW, int C) {                      // enough workgroups to fill the chip, >= 64 pixels each
     const int per = (int)ceil_div(C, 32) * N;
     int S = 1024 / (per > 0 ? per : 1);
@@ -175,10 +178,11 @@ static int in_slices_host(int N, int HW, int C) {                      // enough
 // thread = 4 channels (one 16-byte load) of every 32nd pixel of the slice: 8 threads cover the workgroup's 32 channels, 32 pixel rows per step
 // (the 4-byte-per-lane form of round 2 ran at 2.4 TB/s: 4x the load instructions)
 __global__ __launch_bounds__(256) void instnorm_part_kernel(const float* __restrict__ x, int ld, int HW, int C, int S, float* __restrict__ part) {
-    __shared__ float red[32][33];
+    __shared__ float red[2][4][32];                                        // [quantity][wave][channel]
     __shared__ float mean_s[32];
     const int n = blockIdx.y, c0 = blockIdx.x * 32, s = blockIdx.z;
     const int q = threadIdx.x & 7, row = threadIdx.x >> 3;                // channels c0 + 4 q .. + 3, pixel rows row, row + 32, ...
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;           // a wave = 8 pixel rows x the 8 channel quads
     const int c = c0 + 4 * q;
     const int chunk = (HW + S - 1) / S;
     const int p0 = s * chunk, p1 = (p0 + chunk < HW) ? p0 + chunk : HW;
@@ -194,17 +198,20 @@ __global__ __launch_bounds__(256) void instnorm_part_kernel(const float* __restr
             for (int j = 0; j < 4; ++j) v[j] = (c + j < C) ? xp[(int64_t)p * ld + j] : 0.0f;
         }
     };
-    auto reduce_rows = [&](const float (&acc)[4], float scale_by, float* dst) {   // sum over the 32 row groups in row order -> dst[32 channels]
+    // sum over the 32 row groups, fixed order: a butterfly over the 8 rows of a wave, then (once the workgroup has synchronised) the 4
+    // waves in wave order by sum_waves.  The second pass has two quantities to sum: in this form they share one barrier and one small
+    // LDS array (measured: instnorm_stats takes what it took with the serial 32-row LDS sum of one quantity, within 1 us at the product's shapes).
+    auto rows_to_lds = [&](float (&acc)[4], int k) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) red[row][4 * q + j] = acc[j];
-        __syncthreads();
-        if (threadIdx.x < 32) {
-            float t = 0.0f;
-            for (int r = 0; r < 32; ++r) t += red[r][threadIdx.x];
-            dst[threadIdx.x] = t * scale_by;
+        for (int j = 0; j < 4; ++j) {
+            float t = acc[j];
+            t += __shfl_xor(t, 8);
+            t += __shfl_xor(t, 16);
+            t += __shfl_xor(t, 32);
+            if (lane < 8) red[k][wave][4 * q + j] = t;
         }
-        __syncthreads();
     };
+    auto sum_waves = [&](int k) { return ((red[k][0][threadIdx.x] + red[k][1][threadIdx.x]) + red[k][2][threadIdx.x]) + red[k][3][threadIdx.x]; };
     float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     for (int p = p0 + row; p < p1; p += 32) {
         float v[4];
@@ -212,8 +219,11 @@ __global__ __launch_bounds__(256) void instnorm_part_kernel(const float* __restr
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[j] += v[j];
     }
-    reduce_rows(acc, cnt > 0 ? 1.0f / (float)cnt : 0.0f, mean_s);
-    float mean[4];
+    rows_to_lds(acc, 0);
+    __syncthreads();
+    if (threadIdx.x < 32) mean_s[threadIdx.x] = sum_waves(0) * (cnt > 0 ? 1.0f / (float)cnt : 0.0f);
+    __syncthreads();
+    float mean[4], rem[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
     for (int j = 0; j < 4; ++j) mean[j] = mean_s[4 * q + j], acc[j] = 0.0f;
     for (int p = p0 + row; p < p1; p += 32) {                            // second pass: the slice is L2 resident
@@ -223,14 +233,14 @@ __global__ __launch_bounds__(256) void instnorm_part_kernel(const float* __restr
         for (int j = 0; j < 4; ++j) {
             const float d = v[j] - mean[j];
             acc[j] += d * d;
+            rem[j] += d;
         }
     }
-    __shared__ float m2_s[32];
-    reduce_rows(acc, 1.0f, m2_s);
+    rows_to_lds(acc, 0);
+    rows_to_lds(rem, 1);
+    __syncthreads();
     if (threadIdx.x < 32 && c0 + (int)threadIdx.x < C) {
-        float* o = part + (((int64_t)n * S + s) * C + c0 + threadIdx.x) * 2;
-        o[0] = mean_s[threadIdx.x];
-        o[1] = m2_s[threadIdx.x];
+        *(f32x4*)(part + (((int64_t)n * S + s) * C + c0 + threadIdx.x) * 4) = (f32x4){mean_s[threadIdx.x], sum_waves(0), sum_waves(1), 0.0f};
     }
 }
 
@@ -239,26 +249,27 @@ __global__ __launch_bounds__(256) void instnorm_merge_kernel(const float* __rest
     if (idx >= total) return;
     const int n = idx / C, c = idx - n * C;
     const int chunk = (HW + S - 1) / S;
-    float na = 0.0f, mean = 0.0f, m2 = 0.0f;
-    const f32x2* pp = (const f32x2*)(part + ((int64_t)n * S * C + c) * 2);            // slice s at pp[s * C]
+    const f32x4* pp = (const f32x4*)part + (int64_t)n * S * C + c;                    // slice s at pp[s * C]: (m_s, M2_s, r_s, -)
+    const double m0 = (double)pp[0][0];                                               // (slice 0 is never empty)
+    double a = 0.0, q = 0.0;
     for (int s0 = 0; s0 < S; s0 += 8) {          // the 8 loads of a group are in flight together (one by one the S ~ 50 dependent-looking
-        f32x2 o[8];                              // round trips were the kernel: 13.6 us); the update order stays slice order
+        f32x4 o[8];                              // round trips were the kernel: 13.6 us); the sums stay in slice order
 #pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = (s0 + j < S) ? pp[(int64_t)(s0 + j) * C] : (f32x2){0.0f, 0.0f};
+        for (int j = 0; j < 8; ++j) o[j] = pp[(int64_t)(s0 + j < S ? s0 + j : S - 1) * C];      // unconditional (a branch per load serialises them)
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int s = s0 + j;
             const int p0 = s * chunk, p1 = (p0 + chunk < HW) ? p0 + chunk : HW;
-            const float nb = (float)(p1 - p0);
-            if (s >= S || nb <= 0.0f) continue;
-            const float d = o[j][0] - mean, nn = na + nb;
-            mean += d * (nb / nn);
-            m2 += o[j][1] + d * d * (na * nb / nn);
-            na = nn;
+            const double nb = (double)(p1 - p0);
+            if (s >= S || nb <= 0.0) continue;
+            const double e = (double)o[j][0] - m0, rs = (double)o[j][2];
+            a += nb * e + rs;
+            q += (double)o[j][1] + 2.0 * e * rs + nb * e * e;
         }
     }
-    stats[(int64_t)idx * 2] = mean;
-    stats[(int64_t)idx * 2 + 1] = 1.0f / sqrtf(m2 / (float)HW + eps);
+    const double m2 = q - a * a / (double)HW;
+    stats[(int64_t)idx * 2] = (float)(m0 + a / (double)HW);
+    stats[(int64_t)idx * 2 + 1] = (float)(1.0 / sqrt((m2 > 0.0 ? m2 : 0.0) / (double)HW + (double)eps));
 }
 
 // y = (x - mean) * rstd  [+ res]  [relu]  -> split planes; channels >= C of `out` (padding of the next conv's input) are zeroed
@@ -588,7 +599,7 @@ extern "C" int ppms_sp_upsample2(ppms_sp src, ppms_sp dst, int N, int H, int W, 
 
 extern "C" int ppms_dwconv(ppms_sp x, float* y, int ldy, const float* w, const float* b, int k, int N, int H, int W, void* stream) {
     PPMS_REQUIRE(x.hi && x.lo && y && w && b && N > 0 && H > 0 && W > 0 && k == 7, "dwconv: bad arguments (k = 7: ConvNeXt's depthwise kernel)");
-    PPMS_REQUIRE(x.c % 8 == 0 && x.ld % 8 == 0 && ldy >= x.c && ldy % 4 == 0 && (((uintptr_t)x.hi | (uintptr_t)x.lo | (uintptr_t)y) & 15) == 0,
+    PPMS_REQUIRE(x.c % 8 == 0 && x.ld % 8 == 0 && ldy >= x.c && ldy % 4 == 0 && (((uintptr_t)x.hi | (uintptr_t)x.lo | (uintptr_t)y | (uintptr_t)b) & 15) == 0,
                  "dwconv: channel counts multiples of 8, 16-B aligned operands");
     const int64_t rows = (int64_t)N * H;
     const int cblocks = (int)ceil_div(x.c, 64);
@@ -771,11 +782,12 @@ extern "C" int ppms_sp_s2d(ppms_sp src, ppms_sp dst, int N, int H, int W, void* 
 
 extern "C" int64_t ppms_instnorm_workspace_bytes(int N, int HW, int C) {
     if (N <= 0 || HW <= 0 || C <= 0) return 0;
-    return (int64_t)N * in_slices_host(N, HW, C) * C * 2 * 4;
+    return (int64_t)N * in_slices_host(N, HW, C) * C * 4 * 4;             // one 16-byte record (m_s, M2_s, r_s, -) per (n, slice, c)
 }
 
 extern "C" int ppms_instnorm_stats(const float* x, int ld, int N, int HW, int C, float eps, float* stats, void* workspace, void* stream) {
     PPMS_REQUIRE(x && stats && workspace && N > 0 && HW > 0 && C > 0 && ld >= C && eps > 0.0f, "instnorm_stats: bad arguments");
+    PPMS_REQUIRE(((uintptr_t)workspace & 15) == 0, "instnorm_stats: the workspace must be 16-B aligned");
     const int S = in_slices_host(N, HW, C);
     hipLaunchKernelGGL(instnorm_part_kernel, dim3(ceil_div(C, 32), N, S), dim3(256), 0, (hipStream_t)stream, x, ld, HW, C, S, (float*)workspace);
     hipLaunchKernelGGL(instnorm_merge_kernel, dim3(ceil_div(N * C, 256)), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, HW, C, S, eps, N * C,

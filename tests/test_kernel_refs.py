@@ -1,0 +1,240 @@
+"""CPU: the float64 references of tests/kernel_refs.py against the corresponding torch ops (to float64 rounding), and -- on the exact
+inputs and with the tolerance rule of every GPU case of test_gpu_encoder_ops.py / test_gpu_glue_ops.py -- shown sensitive to the mistakes
+they exist to catch: every named wrong variant exceeds the tolerance on at least one case of its kernel, while the reference itself and
+the plain fp32 torch form stay inside it.  That is a condition on the cases, not a measurement: where a variant slips through, the inputs
+change, not the tolerance."""
+import pytest
+import torch
+import torch.nn.functional as F
+
+import kernel_refs as R
+from ppmstereo_amd.weights import hash_normal
+
+F64 = torch.float64
+
+
+def close(a, b, tol=1e-12):
+    assert a.shape == b.shape, (a.shape, b.shape)
+    err = (a.double() - b.double()).abs().max().item()
+    assert err <= tol * max(1.0, b.abs().max().item()), err
+
+
+# ------------------------------------------------------------------------------------------------ references vs torch
+def test_slices_rederived():
+    """the shape arithmetic of the instnorm / GRN cases: (S, chunk) of in_slices_host"""
+    assert R.in_slices(1, 4225, 64) == (66, 65) and 65 * 65 == 4225            # A: slice 65 is empty; 66 = 8 * 8 + 2
+    assert R.in_slices(2, 35, 96) == (1, 35)                                    # B
+    assert R.in_slices(3, 700, 40) == (10, 70)                                  # C
+    assert R.in_slices(1, 130, 30) == (2, 65)                                   # D
+    assert R.in_slices(1, 130, 3072) == (2, 65)                                 # GRN, C > 256
+
+
+def test_instnorm_vs_torch():
+    x = hash_normal((2, 45, 24), 1).double() * 3 + 1
+    res = hash_normal((2, 45, 24), 2).double()
+    mean, rstd, y = R.instnorm(x, 1e-5)
+    close(y, F.instance_norm(x.permute(0, 2, 1), eps=1e-5).permute(0, 2, 1))
+    close(mean, x.mean(1))
+    close(rstd, 1.0 / torch.sqrt(x.var(1, unbiased=False) + 1e-5))
+    close(R.instnorm(x, 1e-5, res, True)[2], F.relu(F.instance_norm(x.permute(0, 2, 1), eps=1e-5).permute(0, 2, 1) + res))
+
+
+def test_layernorm_vs_torch():
+    x, w, b = hash_normal((37, 40), 3).double() * 2 + 5, hash_normal((40,), 4).double(), hash_normal((40,), 5).double()
+    close(R.layernorm(x, w, b, 1e-6), F.layer_norm(x, (40,), w, b, 1e-6))
+
+
+def test_grn_vs_oracle_expression():
+    """the expression of oracle.ppm_oracle.convnext_block, on its (N, H, W, C) layout"""
+    h = hash_normal((2, 5, 7, 24), 6).double()
+    gamma, beta = hash_normal((24,), 7).double(), hash_normal((24,), 8).double()
+    gx = torch.norm(h, p=2, dim=(1, 2), keepdim=True)
+    nx = gx / (gx.mean(dim=-1, keepdim=True) + 1e-6)
+    want = gamma * (h * nx) + beta + h
+    close(R.grn(h.reshape(2, 35, 24), gamma, beta), want.reshape(2, 35, 24))
+
+
+def test_dwconv_vs_torch():
+    x, w, b = hash_normal((2, 5, 9, 16), 9).double(), hash_normal((16, 49), 10).double(), hash_normal((16,), 11).double()
+    want = F.conv2d(x.permute(0, 3, 1, 2), w.reshape(16, 1, 7, 7), b, padding=3, groups=16).permute(0, 2, 3, 1)
+    close(R.dwconv(x, w, b), want)
+
+
+@pytest.mark.parametrize("k", [2, 4])
+def test_s2d_vs_pixel_unshuffle(k):
+    x = hash_normal((2, 8, 12, 5), 12).double()
+    pu = F.pixel_unshuffle(x.permute(0, 3, 1, 2), k)                            # channel c k k + (k dy + dx)
+    want = pu.reshape(2, 5, k * k, 8 // k, 12 // k).permute(0, 3, 4, 2, 1).reshape(2, 8 // k, 12 // k, k * k * 5)      # -> phase C + c
+    assert torch.equal(R.s2d(x, k), want)
+
+
+def test_upsample_vs_interpolate():
+    x = hash_normal((2, 3, 5, 4), 13).double()
+    want = F.interpolate(x.permute(0, 3, 1, 2), scale_factor=2, mode="nearest").permute(0, 2, 3, 1)
+    assert torch.equal(R.upsample2(x), want)
+
+
+def test_flow_patch_vs_unfold():
+    flow = hash_normal((2, 5, 9, 2), 14).double()
+    u = F.unfold(flow.permute(0, 3, 1, 2), 7, padding=3)                        # (BT, c 49 + tap, HW)
+    want = u.reshape(2, 2, 49, 45).permute(0, 3, 2, 1).reshape(2, 5, 9, 98)
+    got = R.flow_patch(flow)
+    assert torch.equal(got[..., :98], want) and (got[..., 98:] == 0).all() and got.shape[-1] == 128
+
+
+@pytest.mark.parametrize("case", R.RESIZE_CASES)
+def test_resize_vs_interpolate(case):
+    N, H, W, OH, OW = case
+    dst, src = (t.double() for t in R.resize_inputs(case))
+    want = F.interpolate(src.permute(0, 3, 1, 2), size=(OH, OW), mode="bilinear", align_corners=True).permute(0, 2, 3, 1)
+    close(R.resize_blend(dst, src, OH, OW, 0.0, 1.0), want)
+    close(R.resize_blend(dst, src, OH, OW, 0.5, 0.5), 0.5 * dst + 0.5 * want)
+    nan = torch.full_like(dst, float("nan"))
+    assert torch.isfinite(R.resize_blend(nan, src, OH, OW, 0.0, 1.0)).all()
+
+
+@pytest.mark.parametrize("case", R.AVGPOOL_CASES)
+def test_avgpool_vs_torch(case):
+    x = R.avgpool_input(case).double()
+    close(R.avgpool(x, case[0]), F.avg_pool2d(x[None], case[0], stride=case[0])[0])
+
+
+def test_small_refs_vs_torch():
+    x, y = hash_normal((12,), 15).double(), hash_normal((4,), 16).double()
+    close(R.axpby(x, y, 0.5, 2.0, 4), 0.5 * x + 2.0 * y.repeat(3))
+    f, c = hash_normal((2, 256, 35), 17).double(), hash_normal((2, 256, 35), 18).double()
+    net, inp = R.ctx_mix(f, c)
+    close(net, torch.tanh((f[:, :128] + c[:, :128]) / 2))
+    close(inp, F.relu((f[:, 128:] + c[:, 128:]) / 2))
+    xs, w, b = R.unc_inputs((2, 700))
+    unc, part = R.unc_tail(xs, w, b)
+    close(unc, torch.sigmoid(F.linear(xs.double(), w.double()[None]).squeeze(-1) + b))
+    assert part.shape == (2, 3)
+    close(part[:, 2], unc[:, 512:].sum(1))
+    close(part.sum(1), unc.sum(1))
+
+
+def test_sp_split_bound():
+    """the split planes: |hi + lo - x| <= 2^-16 |x|, and a pair read back is reproduced exactly"""
+    x = hash_normal((1 << 14,), 19) * 5
+    hi, lo = R.sp_split(x)
+    assert R.split_check(R.Check(), "x", hi, lo, x).ok
+    assert torch.equal(R.sp_round(R.sp_round(x)), R.sp_round(x))
+
+
+# ------------------------------------------------------------------------------------------------ every wrong variant is caught
+def _instnorm_runs(fn):
+    """Check of fn over every (case, data, residual, relu) the GPU test runs; None where the variant does not apply"""
+    out = []
+    for case in R.INSTNORM_CASES:
+        for data in ("unit", "offset"):
+            x, res = R.instnorm_inputs(case, data)
+            for with_res in (False, True):
+                for relu in (False, True):
+                    got = fn(x, R.IN_EPS, res[:, :, :x.shape[2]] if with_res else None, relu)
+                    if got is not None:
+                        out.append(R.instnorm_check(case, data, with_res, relu, *got))
+    return out
+
+
+def test_instnorm_cases_pass_the_reference_and_fp32():
+    assert all(c.ok for c in _instnorm_runs(R.instnorm))
+    runs = _instnorm_runs(R.instnorm_f32)
+    assert all(c.ok for c in runs), [str(c) for c in runs if not c.ok]
+
+
+@pytest.mark.parametrize("name", list(R.INSTNORM_WRONG))
+def test_instnorm_wrong_variant_is_caught(name):
+    runs = _instnorm_runs(R.INSTNORM_WRONG[name])
+    assert runs and any(not c.ok for c in runs), name
+
+
+def test_instnorm_needs_both_kinds_of_data():
+    """on unit data the applied result lets eps = 1e-6 through (only the rstd column of the stats shows it) and catches the unbiased variance;
+    on offset data the applied result catches eps = 1e-6 and the one-pass variance"""
+    y_ok = lambda ck: all(e <= t for n, e, t in ck.items if n == "y")
+    unit = lambda fn: [R.instnorm_check("A", "unit", False, False, *fn(R.instnorm_inputs("A", "unit")[0], R.IN_EPS))]
+    offs = lambda fn: [R.instnorm_check("A", "offset", False, False, *fn(R.instnorm_inputs("A", "offset")[0], R.IN_EPS))]
+    assert not unit(R.INSTNORM_WRONG["unbiased"])[0].ok
+    eps_unit, eps_offs = unit(R.INSTNORM_WRONG["eps_1e-6"])[0], offs(R.INSTNORM_WRONG["eps_1e-6"])[0]
+    assert y_ok(eps_unit) and not eps_unit.ok and not y_ok(eps_offs)
+    assert not y_ok(unit(R.INSTNORM_WRONG["unbiased"])[0]) and not y_ok(offs(R.INSTNORM_WRONG["one_pass_fp32"])[0])
+    assert not offs(R.INSTNORM_WRONG["eps_1e-6"])[0].ok and not offs(R.INSTNORM_WRONG["one_pass_fp32"])[0].ok
+
+
+@pytest.mark.parametrize("name", list(R.GRN_WRONG))
+def test_grn_wrong_variant_is_caught(name):
+    runs = [R.grn_check(case, R.GRN_WRONG[name](*R.grn_inputs(case))) for case in R.GRN_CASES]
+    assert any(not c.ok for c in runs), name
+
+
+def test_grn_cases_pass_the_reference_and_fp32():
+    for case in R.GRN_CASES:
+        assert R.grn_check(case, R.grn(*R.grn_inputs(case))).ok
+        ck = R.grn_check(case, R.grn_f32(*R.grn_inputs(case)))
+        assert ck.ok, str(ck)
+
+
+def test_grn_eps_needs_the_tiny_case():
+    assert not R.grn_check("tiny", R.GRN_WRONG["eps_1e-5"](*R.grn_inputs("tiny"))).ok
+    assert R.grn_check("small", R.GRN_WRONG["eps_1e-5"](*R.grn_inputs("small"))).ok      # invisible at unit magnitude
+
+
+@pytest.mark.parametrize("name", list(R.LN_WRONG))
+def test_layernorm_wrong_variant_is_caught(name):
+    for C in R.LN_CASES:                                                                  # (here: on every case)
+        ck = R.layernorm_check(C, R.LN_WRONG[name](*R.layernorm_inputs(C), R.LN_EPS))
+        assert not ck.ok, (name, C)
+
+
+def test_layernorm_cases_pass_the_reference_and_fp32():
+    for C in R.LN_CASES:
+        assert R.layernorm_check(C, R.layernorm(*R.layernorm_inputs(C), R.LN_EPS)).ok
+        ck = R.layernorm_check(C, R.layernorm_f32(*R.layernorm_inputs(C), R.LN_EPS))
+        assert ck.ok, str(ck)
+
+
+@pytest.mark.parametrize("name", list(R.DW_WRONG))
+def test_dwconv_wrong_variant_is_caught(name):
+    runs = [R.dwconv_check(case, R.DW_WRONG[name](*R.dwconv_inputs(case))) for case in R.DW_CASES]
+    assert all(not c.ok for c in runs), name
+
+
+def test_dwconv_cases_pass_fp32():
+    for case in R.DW_CASES:
+        ck = R.dwconv_check(case, R.dwconv_f32(*R.dwconv_inputs(case)))
+        assert ck.ok, str(ck)
+
+
+def test_layout_wrong_variants_are_caught():
+    for case in R.S2D_CASES:
+        N, H, W, C = case
+        x = R.s2d_input(case).reshape(N, H, W, C)
+        assert not R.Check().exact("s2d", R.S2D_WRONG["dy_dx_swapped"](x, 2), R.s2d(x, 2)).ok
+    for k, shape, c in R.IMG_S2D_CASES:
+        x = R.img_input(shape).permute(0, 2, 3, 1)
+        assert not R.Check().exact("img_s2d", R.S2D_WRONG["dy_dx_swapped"](x, k), R.s2d(x, k)).ok
+    x = R.upsample_input().reshape(*R.UP_CASE, 32)[..., 8:24]
+    assert not R.Check().exact("up", R.UP_WRONG["(y+1)>>1"](x), R.upsample2(x)).ok
+    for case in R.PATCH_CASES:
+        flow = R.flow_input(case)
+        assert not R.Check().exact("patch", R.PATCH_WRONG["tap=kx*7+ky"](flow), R.flow_patch(flow)).ok
+
+
+def test_resize_wrong_variant_is_caught():
+    caught = 0
+    for case in R.RESIZE_CASES:
+        for a, b in R.RESIZE_AB:
+            dst, src = R.resize_inputs(case)
+            ref = R.resize_blend(dst, src, case[3], case[4], a, b)
+            caught += not R.Check().add("y", R.RESIZE_WRONG["align_corners=False"](dst, src, case[3], case[4], a, b), ref, R.tol_sp(ref)).ok
+    assert caught >= 4                                                        # every case but the identity, both blends
+
+
+def test_avgpool_wrong_variant_is_caught():
+    runs = []
+    for case in R.AVGPOOL_CASES:
+        x = R.avgpool_input(case)
+        ref = R.avgpool(x, case[0])
+        runs.append(R.Check().add("y", R.AVGPOOL_WRONG["clipped_divisor"](x, case[0]), ref, R.tol_reduce(ref, R.avgpool_f32(x, case[0]), False)))
+    assert any(not c.ok for c in runs)
