@@ -19,6 +19,9 @@ from . import _lib as L
 from .corr import CorrBlock1D
 from .engine import bilinear
 from .update import Attention_qk, SequenceUpdateBlock3D
+from .video import (InputPadder, OutputSpec, RectifyMap, StereoRectifier, YUVFrames, YUVStereoVideo, byte_lut, egress_plan,  # noqa: F401  (the public names are
+                    shard_windows, window_plan, yuv_matrix)                                                                 #  importable from here as before)
+from .video import _ByteSource, _EgressCall, stereo_source
 
 
 def interp(x: torch.Tensor, size) -> torch.Tensor:
@@ -168,112 +171,6 @@ def _forward_update_block_batched(update_block, corr_fn, flow, net, inp, motion_
             uncertainties.append(bilinear(unc, (4 * isc * h, 4 * isc * w), False))
             predictions.append(bilinear(flow_out[:, :1], (isc * 4 * h, isc * 4 * w), True, float(isc)) if isc > 1 else flow_out[:, :1].clone())
         return flow_out, torch.cat([e.get_net() for e in engs]), torch.cat([e.get_mhs() for e in engs])
-
-
-_PLANE_FORMATS = {"f32": (L.FMT_F32, torch.float32), "f16": (L.FMT_F16, torch.float16), "u16": (L.FMT_U16, torch.uint16), "u8": (L.FMT_U8, torch.uint8)}
-
-
-class OutputSpec:
-    """What ``forward(output=...)`` / ``forward_batch_test(output=...)`` hand back instead of float32 disparity: up to three planes that ONE
-    kernel (ppms_disparity_egress, include/ppms.h) writes from the 1/4 scale's last iteration -- crop, kept frames, ``.abs()``, the 4x
-    upsampling of the uncertainty and the conversion in one pass.
-      disparity    "f32" | "f16" | "u16": d = |disparity| in pixels; "u16" = min(65535, rint(d * disp_scale)) (KITTI: disp_scale = 256), NaN -> 0
-      depth        None | "f32" | "f16" | "u16": Z = fb / d with fb = focal_px * baseline (one fp32 product); "u16" = min(65535, rint(Z * depth_scale))
-                   (baseline in metres and depth_scale = 1000: millimetres).  A pixel with d < min_disp or d = NaN is invalid: +inf in the float
-                   formats, 0 in "u16".  (min_disp = 0 leaves only NaN invalid: d = 0 then gives +inf / 65535.)
-      uncertainty  "f32" | "u8" | None: u = |uncertainty| in [0, 1]; "u8" = min(255, rint(u * 255)), NaN -> 0
-    Every step is one fp32 operation rounded to nearest even; ``reference`` restates them in torch and is the definition the kernel is
-    tested against, bit for bit."""
-
-    def __init__(self, disparity: str = "f32", depth: Optional[str] = None, uncertainty: Optional[str] = "f32", disp_scale: float = 256.0,
-                 focal_px: Optional[float] = None, baseline: Optional[float] = None, depth_scale: float = 1000.0, min_disp: float = 2.0 ** -8):
-        if disparity not in ("f32", "f16", "u16"):
-            raise ValueError(f"OutputSpec: disparity = {disparity!r}; one of 'f32', 'f16', 'u16'")
-        if depth not in (None, "f32", "f16", "u16"):
-            raise ValueError(f"OutputSpec: depth = {depth!r}; None or one of 'f32', 'f16', 'u16'")
-        if uncertainty not in (None, "f32", "u8"):
-            raise ValueError(f"OutputSpec: uncertainty = {uncertainty!r}; None, 'f32' or 'u8'")
-        f32 = lambda x: float(torch.tensor(float(x), dtype=torch.float32))
-        self.disparity, self.depth, self.uncertainty = disparity, depth, uncertainty
-        self.disp_scale, self.depth_scale, self.min_disp = f32(disp_scale), f32(depth_scale), f32(min_disp)
-        if not (0.0 < self.disp_scale < math.inf):
-            raise ValueError(f"OutputSpec: disp_scale = {disp_scale} must be positive and finite")
-        self.focal_px, self.baseline, self.fb = focal_px, baseline, 0.0
-        if depth is not None:
-            if focal_px is None or baseline is None:
-                raise ValueError("OutputSpec: a depth plane needs focal_px (focal length in pixels) and baseline")
-            self.fb = float(torch.tensor(float(focal_px), dtype=torch.float32) * torch.tensor(float(baseline), dtype=torch.float32))
-            if not (0.0 < self.fb < math.inf):
-                raise ValueError(f"OutputSpec: focal_px * baseline = {self.fb} must be positive and finite")
-            if not (0.0 < self.depth_scale < math.inf):
-                raise ValueError(f"OutputSpec: depth_scale = {depth_scale} must be positive and finite")
-            if not math.isfinite(self.min_disp):
-                raise ValueError(f"OutputSpec: min_disp = {min_disp} must be finite")
-
-    def formats(self) -> Dict[str, str]:
-        """{result key: format} of the requested planes, in the order disparity, depth, uncertainties."""
-        named = (("disparity", self.disparity), ("depth", self.depth), ("uncertainties", self.uncertainty))
-        return {k: f for k, f in named if f is not None}
-
-    def empty(self, n: int, h0: int, w0: int, device, pin_memory: bool = False) -> Dict[str, torch.Tensor]:
-        """Dense (n, 1, h0, w0) tensors of the requested planes' dtypes."""
-        return {k: torch.empty(n, 1, h0, w0, dtype=_PLANE_FORMATS[f][1], device=device, pin_memory=pin_memory) for k, f in self.formats().items()}
-
-    def struct(self, planes: Dict[str, torch.Tensor]) -> L.Egress:
-        """The ``ppms_egress`` that writes into ``planes`` (dense (n, 1, h0, w0) device tensors from ``empty``)."""
-        def plane(key):
-            t = planes.get(key)
-            if t is None:
-                return L.EgressPlane(None, 0, 0, 0, 0)
-            es = t.element_size()
-            return L.EgressPlane(t.data_ptr(), t.stride(0) * es, t.stride(2) * es, _PLANE_FORMATS[self.formats()[key]][0], 0)
-        return L.Egress(plane("disparity"), plane("depth"), plane("uncertainties"), self.disp_scale, self.fb, self.depth_scale, self.min_disp)
-
-    def reference(self, d: torch.Tensor, u: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
-        """The arithmetic of ppms_disparity_egress in plain torch, on CPU or device tensors of any shape: d = a float32 (signed) disparity,
-        u = a float32 uncertainty at the same resolution -> the requested planes under forward_batch_test's keys."""
-        const = lambda x: torch.full((), x, dtype=torch.float32, device=d.device)
-
-        def quant(v, scale, top, fmt):                       # min(top, rint(v * scale)), NaN -> 0: one fp32 product, ties to even
-            r = torch.round(v * const(scale))
-            r = torch.where(torch.isnan(r), torch.zeros_like(r), r).clamp(max=top)
-            return r.to(torch.int32).to(_PLANE_FORMATS[fmt][1])
-
-        d = d.float().abs()
-        out = {"disparity": d if self.disparity == "f32" else d.to(torch.float16) if self.disparity == "f16" else quant(d, self.disp_scale, 65535.0, "u16")}
-        if self.depth is not None:
-            valid = d >= const(self.min_disp)                # (false for NaN)
-            z = torch.where(valid, const(self.fb) / d, const(math.inf))          # tensor / tensor: a correctly rounded fp32 division
-            if self.depth == "u16":
-                out["depth"] = torch.where(valid, quant(z, self.depth_scale, 65535.0, "u16").to(torch.int32), 0).to(torch.uint16)
-            else:
-                out["depth"] = z if self.depth == "f32" else z.to(torch.float16)
-        if self.uncertainty is not None:
-            if u is None:
-                raise ValueError("OutputSpec.reference: an uncertainty plane is requested and no uncertainty was given")
-            u = u.float().abs()
-            out["uncertainties"] = u if self.uncertainty == "f32" else quant(u, 255.0, 255.0, "u8")
-        return out
-
-
-class _EgressCall:
-    """One egress launch as ``cascade`` makes it: the spec, the crop (pad_left, pad_top, H0, W0) inside the padded frame (None: the whole
-    frame) and the window-local frame range (None: all frames)."""
-
-    def __init__(self, spec: OutputSpec, crop=None, frames=None):
-        if not isinstance(spec, OutputSpec):
-            raise TypeError(f"output must be an OutputSpec, got {type(spec).__name__}")
-        self.spec, self.crop, self.frames = spec, (None if crop is None else tuple(int(x) for x in crop)), (None if frames is None else tuple(int(x) for x in frames))
-
-    def launch(self, eng) -> Dict[str, torch.Tensor]:
-        """Allocates the planes on the current stream and enqueues the launch there, behind the engine's last iteration."""
-        pad_left, pad_top, h0, w0 = (0, 0, 4 * eng.h, 4 * eng.w) if self.crop is None else self.crop
-        f0, f1 = (0, eng.T) if self.frames is None else self.frames
-        if not 0 <= f0 < f1 <= eng.T:
-            raise ValueError(f"output: frames = {(f0, f1)} is no range inside the window's {eng.T} frames")
-        planes = self.spec.empty(f1 - f0, h0, w0, eng.FLOW_OUT.device)
-        eng.egress(self.spec.struct(planes), f0, f1 - f0, pad_left, pad_top, h0, w0)
-        return planes
 
 
 class ClipPipeline:
@@ -488,28 +385,24 @@ class PPMStereoHotPath(nn.Module):
                 _add_attn_redo(diagnostics, {tag: eng.attn_health() for tag, eng in health.items()})
             return planes if egress is not None else (preds[-1], uncs[-1])
 
-
-def _cascade_batched(self, feats, iters: int, t: int, preds: list, uncs: list):
-    """cascade for b > 1 clips (frame index = bi * t + ti, ppmstereo.py:443-449): the reference's glue between the three
-    forward_update_block calls (:696-791) on NCHW tensors -- every iteration's prediction is produced, as test_mode=False does.  The batch
-    elements meet in one scalar per clip index only (the mean of the picked scores, :533), which forward_update_block reproduces; b = 1 --
-    the reference's inference entry -- takes the device-resident path above instead."""
-    f16 = feats["f1_16"]
-    fo, net16, mhs16 = self.forward_update_block(None, self.update_block16, CorrBlock1D(f16, feats["f2_16"]), self.zero_init(f16), feats["net_16"],
-                                                 feats["inp_16"], None, self.att[0], preds, uncs, iters // 2, 4, t)                 # :707-722
-    nets, mhs = {16: net16}, {16: mhs16}
-    for s_, blk, ai, n_it, isc in ((8, self.update_block08, 1, iters // 2, 2), (4, self.update_block04, 2, iters, 1)):
-        f1, f2 = feats[f"f1_{s_}"], feats[f"f2_{s_}"]
-        h, w = f1.shape[2:]
-        flow = bilinear(fo, (h, w), True, -(h / fo.shape[2]))                                                                       # :724-725, :760-761
-        m_up = bilinear(mhs[2 * s_], (h, w), True)                                                                                   # :726-727, :763-764
-        net = (feats[f"net_{s_}"] + bilinear(nets[2 * s_], (h, w), True)) / 2.0                                                     # :729-732, :765-767
-        fo, nets[s_], mhs[s_] = self.forward_update_block(None, blk, CorrBlock1D(f1, f2), flow, net, feats[f"inp_{s_}"], m_up, self.att[ai],
-                                                          preds, uncs, n_it, isc, t)                                                # :743-758, :776-791
-    return preds[-1], uncs[-1]
-
-
-PPMStereoHotPath._cascade_batched = _cascade_batched
+    def _cascade_batched(self, feats, iters: int, t: int, preds: list, uncs: list):
+        """cascade for b > 1 clips (frame index = bi * t + ti, ppmstereo.py:443-449): the reference's glue between the three
+        forward_update_block calls (:696-791) on NCHW tensors -- every iteration's prediction is produced, as test_mode=False does.  The batch
+        elements meet in one scalar per clip index only (the mean of the picked scores, :533), which forward_update_block reproduces; b = 1 --
+        the reference's inference entry -- takes the device-resident path above instead."""
+        f16 = feats["f1_16"]
+        fo, net16, mhs16 = self.forward_update_block(None, self.update_block16, CorrBlock1D(f16, feats["f2_16"]), self.zero_init(f16), feats["net_16"],
+                                                     feats["inp_16"], None, self.att[0], preds, uncs, iters // 2, 4, t)                 # :707-722
+        nets, mhs = {16: net16}, {16: mhs16}
+        for s_, blk, ai, n_it, isc in ((8, self.update_block08, 1, iters // 2, 2), (4, self.update_block04, 2, iters, 1)):
+            f1, f2 = feats[f"f1_{s_}"], feats[f"f2_{s_}"]
+            h, w = f1.shape[2:]
+            flow = bilinear(fo, (h, w), True, -(h / fo.shape[2]))                                                                       # :724-725, :760-761
+            m_up = bilinear(mhs[2 * s_], (h, w), True)                                                                                   # :726-727, :763-764
+            net = (feats[f"net_{s_}"] + bilinear(nets[2 * s_], (h, w), True)) / 2.0                                                     # :729-732, :765-767
+            fo, nets[s_], mhs[s_] = self.forward_update_block(None, blk, CorrBlock1D(f1, f2), flow, net, feats[f"inp_{s_}"], m_up, self.att[ai],
+                                                              preds, uncs, n_it, isc, t)                                                # :743-758, :776-791
+        return preds[-1], uncs[-1]
 
 
 def position_encoding_sine(d_model: int, h: int, w: int) -> torch.Tensor:
@@ -524,419 +417,6 @@ def position_encoding_sine(d_model: int, h: int, w: int) -> torch.Tensor:
     pe[2::4, :, :] = torch.sin(y_position * div_term)
     pe[3::4, :, :] = torch.cos(y_position * div_term)
     return pe
-
-
-class InputPadder:
-    """Replicate-pads the last two dimensions up to multiples of ``divis_by`` and crops results back (the reference's helper,
-    models/core/utils/utils.py:19-44).  "sintel" mode centres the image (the extra row / column of an odd pad goes to the bottom /
-    right); any other mode pads the height at the bottom only."""
-
-    def __init__(self, dims, mode: str = "sintel", divis_by: int = 8):
-        self.ht, self.wd = int(dims[-2]), int(dims[-1])
-        extra_h, extra_w = -self.ht % divis_by, -self.wd % divis_by
-        left, top = extra_w // 2, (extra_h // 2 if mode == "sintel" else 0)
-        self._pad = [left, extra_w - left, top, extra_h - top]          # F.pad order: left, right, top, bottom
-
-    def geometry(self):
-        """(pad_left, pad_top, H, W): the columns / rows ``pad`` adds in front and the padded size (what ppms_video_ingest_u8 takes)."""
-        left, right, top, bottom = self._pad
-        return left, top, top + self.ht + bottom, left + self.wd + right
-
-    def pad(self, *inputs):
-        for x in inputs:
-            if x.ndim != 4:
-                raise ValueError(f"InputPadder.pad: 4-D tensors expected, got {tuple(x.shape)}")
-        if not any(self._pad):
-            return list(inputs)                                           # (already a multiple: nothing to copy)
-        return [torch.nn.functional.pad(x, self._pad, mode="replicate") for x in inputs]
-
-    def unpad(self, x):
-        if x.ndim != 4:
-            raise ValueError(f"InputPadder.unpad: 4-D tensor expected, got {tuple(x.shape)}")
-        left, right, top, bottom = self._pad
-        return x[..., top:x.shape[-2] - bottom, left:x.shape[-1] - right]
-
-
-_BYTE_LUT: Dict[int, torch.Tensor] = {}
-
-
-def byte_lut(device) -> torch.Tensor:
-    """fp32 [256] on `device`: the normalised value of every byte, from the expression ``forward`` applies to float images ON THE SAME
-    DEVICE -- torch's division by a Python scalar need not round like a division written elsewhere, so the table is what makes the uint8
-    path the float path's bits.  Built once per device (the host waits for it once)."""
-    device = torch.device(device)
-    idx = torch.cuda.current_device() if device.index is None else device.index
-    if idx not in _BYTE_LUT:
-        dev = torch.device("cuda", idx)
-        _BYTE_LUT[idx] = (2 * (torch.arange(256, dtype=torch.float32, device=dev) / 255.0) - 1.0).contiguous()
-        torch.cuda.current_stream(dev).synchronize()             # later calls may read it from any stream
-    return _BYTE_LUT[idx]
-
-
-class _ByteFrames:
-    """uint8 frames of both views on the device as ppms_video_ingest_u8 reads them: ``left`` / ``right`` start at frame 0 of a view, frame
-    n of a view lies ``frame_stride`` bytes further; (H0, W0) frames go to the padded size with ``pad_left`` / ``pad_top`` in front."""
-
-    def __init__(self, left: torch.Tensor, right: torch.Tensor, frame_stride: int, n: int, h0: int, w0: int, pad_left: int = 0, pad_top: int = 0,
-                 rectify: Optional["StereoRectifier"] = None):
-        self.left, self.right, self.frame_stride, self.n = left, right, int(frame_stride), int(n)
-        self.h0, self.w0, self.pad_left, self.pad_top = int(h0), int(w0), int(pad_left), int(pad_top)
-        self.rectify = rectify                                  # on the frames' device: they are raw frames of its source size, (h0, w0) its rectified size
-
-    def ingest(self, dst_fnet: L.SP, dst_cnet: L.SP, h: int, w: int) -> None:
-        """One launch on the current stream: both encoders' first-layer operands of the n frames padded to h x w."""
-        if self.rectify is not None:
-            lmap, rmap = self.rectify.left.view_struct(), self.rectify.right.view_struct()       # host structs: read before the call returns
-            L.check(L.load().ppms_video_ingest_u8_remap(self.left.data_ptr(), self.right.data_ptr(), self.frame_stride, lmap, rmap, self.n, self.h0, self.w0,
-                                                        self.pad_left, self.pad_top, h, w, byte_lut(self.left.device).data_ptr(), dst_fnet, dst_cnet,
-                                                        L.stream_ptr()))
-            return
-        L.check(L.load().ppms_video_ingest_u8(self.left.data_ptr(), self.right.data_ptr(), self.frame_stride, self.n, self.h0, self.w0, self.pad_left,
-                                              self.pad_top, h, w, byte_lut(self.left.device).data_ptr(), dst_fnet, dst_cnet, L.stream_ptr()))
-
-    def held(self):
-        """The tensors the launch reads (for record_stream)."""
-        if self.rectify is not None:
-            return (self.left, self.right) + self.rectify.tensors()
-        return self.left, self.right
-
-
-_YUV_STANDARDS = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}       # (Kr, Kb)
-
-
-def yuv_matrix(standard: str = "bt709", full_range: bool = False, shift: int = 14) -> L.YUVMatrix:
-    """The fixed-point YCbCr -> RGB conversion ppms_video_ingest_yuv420 applies (include/ppms.h), as its ``ppms_yuv_matrix``: Python
-    ``round()`` of the double-precision coefficients times 2^shift.  Limited range: Y in [16, 235], chroma in [16, 240]."""
-    if standard not in _YUV_STANDARDS:
-        raise ValueError(f"yuv_matrix: standard {standard!r}; one of {sorted(_YUV_STANDARDS)}")
-    if not 8 <= shift <= 20:
-        raise ValueError(f"yuv_matrix: shift = {shift} must lie in [8, 20]")
-    kr, kb = _YUV_STANDARDS[standard]
-    kg = 1.0 - kr - kb
-    sy, sc = (1.0, 1.0) if full_range else (255.0 / 219.0, 255.0 / 224.0)
-    one = float(1 << shift)
-    return L.YUVMatrix(y_off=0 if full_range else 16, cy=round(sy * one), crv=round(sc * 2.0 * (1.0 - kr) * one),
-                       cgu=round(sc * 2.0 * kb * (1.0 - kb) / kg * one), cgv=round(sc * 2.0 * kr * (1.0 - kr) / kg * one),
-                       cbu=round(sc * 2.0 * (1.0 - kb) * one), shift=shift, reserved=0)
-
-
-class YUVFrames:
-    """One view's N decoded 8-bit YUV 4:2:0 frames, as a decoder leaves them: ``y`` uint8 (N, H0, W0), ``u`` / ``v`` uint8
-    (N, ceil(H0 / 2), ceil(W0 / 2)).  Each may be a strided VIEW of a decoder surface -- a pitched plane, the two halves of an interleaved
-    UV plane (``nv12``), one half of a frame that packs both views (``split_side_by_side`` / ``split_top_bottom``): the class reads
-    ``data_ptr()`` and ``stride()`` and never copies.  ``y`` needs last-dimension stride 1; ``u`` and ``v`` equal strides with
-    last-dimension stride 1 (planar: I420 / yuv420p) or 2 (interleaved: NV12); anything else raises ValueError.  Luma pixel (y, x) takes
-    chroma sample (y >> 1, x >> 1); ``standard`` ("bt709" / "bt601") and ``full_range`` choose ``yuv_matrix``; ``to_rgb_u8`` is the
-    definition of the RGB bytes.  Not covered: 10-bit surfaces (P010), 4:2:2 and 4:4:4, interpolated chroma siting, b > 1."""
-
-    def __init__(self, y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, standard: str = "bt709", full_range: bool = False):
-        for name, t in (("y", y), ("u", u), ("v", v)):
-            if not torch.is_tensor(t) or t.dtype != torch.uint8 or t.dim() != 3:
-                raise ValueError(f"YUVFrames: {name} must be a uint8 tensor (N, rows, columns)")
-        n, h0, w0 = y.shape
-        hc, wc = (h0 + 1) // 2, (w0 + 1) // 2
-        if n < 1 or h0 < 1 or w0 < 1:
-            raise ValueError(f"YUVFrames: empty y plane {tuple(y.shape)}")
-        if tuple(u.shape) != (n, hc, wc) or tuple(v.shape) != (n, hc, wc):
-            raise ValueError(f"YUVFrames: y {tuple(y.shape)} needs u and v of {(n, hc, wc)}, got {tuple(u.shape)} and {tuple(v.shape)}")
-        if u.device != y.device or v.device != y.device:
-            raise ValueError("YUVFrames: y, u and v must be on one device")
-        if w0 > 1 and y.stride(2) != 1:
-            raise ValueError(f"YUVFrames: y has last-dimension stride {y.stride(2)}; luma samples must be adjacent bytes")
-        step = u.stride(2) if wc > 1 else 1                                # (a one-column chroma plane never takes a step)
-        if u.stride() != v.stride():
-            raise ValueError(f"YUVFrames: u and v must have equal strides, got {u.stride()} and {v.stride()}")
-        if step not in (1, 2):
-            raise ValueError(f"YUVFrames: chroma last-dimension stride {step}; 1 (planar) or 2 (interleaved) expected")
-        # a size-1 dimension's stride is arbitrary: the smallest the kernel accepts stands in for it
-        self.pitch_y = y.stride(1) if h0 > 1 else w0
-        self.pitch_c = u.stride(1) if hc > 1 else step * (wc - 1) + 1
-        self.step_c = step
-        self.frame_stride_y = y.stride(0) if n > 1 else (h0 - 1) * self.pitch_y + w0
-        self.frame_stride_c = u.stride(0) if n > 1 else (hc - 1) * self.pitch_c + step * (wc - 1) + 1
-        if (self.pitch_y < w0 or self.pitch_c < step * (wc - 1) + 1 or self.frame_stride_y < (h0 - 1) * self.pitch_y + w0
-                or self.frame_stride_c < (hc - 1) * self.pitch_c + step * (wc - 1) + 1):
-            raise ValueError(f"YUVFrames: rows or frames overlap (y strides {y.stride()}, chroma strides {u.stride()})")
-        yuv_matrix(standard)                                               # (refuses an unknown standard here)
-        self.y, self.u, self.v, self.standard, self.full_range = y, u, v, standard, bool(full_range)
-        self.n, self.height, self.width = n, h0, w0
-
-    @classmethod
-    def nv12(cls, y: torch.Tensor, uv: torch.Tensor, standard: str = "bt709", full_range: bool = False) -> "YUVFrames":
-        """NV12: ``uv`` uint8 (N, ceil(H0 / 2), ceil(W0 / 2), 2), U first -- a hardware decoder's surface."""
-        if not torch.is_tensor(uv) or uv.dim() != 4 or uv.shape[-1] != 2:
-            raise ValueError("YUVFrames.nv12: uv must be (N, rows, columns, 2)")
-        return cls(y, uv[..., 0], uv[..., 1], standard, full_range)
-
-    @classmethod
-    def i420(cls, y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, standard: str = "bt709", full_range: bool = False) -> "YUVFrames":
-        """I420 / yuv420p: three planes -- a software decoder's frame."""
-        return cls(y, u, v, standard, full_range)
-
-    def __len__(self) -> int:
-        return self.n
-
-    @property
-    def device(self) -> torch.device:
-        return self.y.device
-
-    def _like(self, y, u, v) -> "YUVFrames":
-        return YUVFrames(y, u, v, self.standard, self.full_range)
-
-    def __getitem__(self, frames: slice) -> "YUVFrames":
-        if not isinstance(frames, slice):
-            raise TypeError("YUVFrames: index with a slice of frames")
-        return self._like(self.y[frames], self.u[frames], self.v[frames])
-
-    def split_side_by_side(self):
-        """(left, right): the two halves of frames that pack both views side by side; views, no copy.  The packed width must be even --
-        and each half's too, or the right half's chroma would start between two samples."""
-        w = self.width
-        if w % 2 or (w // 2) % 2:
-            raise ValueError(f"YUVFrames.split_side_by_side: a packed width of {w} does not split into two views with whole chroma samples")
-        h, q = w // 2, w // 4
-        return (self._like(self.y[:, :, :h], self.u[:, :, :q], self.v[:, :, :q]), self._like(self.y[:, :, h:], self.u[:, :, q:], self.v[:, :, q:]))
-
-    def split_top_bottom(self):
-        """(left, right) = (top, bottom) halves of frames that pack both views one above the other; views, no copy (even halves, as above)."""
-        ht = self.height
-        if ht % 2 or (ht // 2) % 2:
-            raise ValueError(f"YUVFrames.split_top_bottom: a packed height of {ht} does not split into two views with whole chroma rows")
-        h, q = ht // 2, ht // 4
-        return (self._like(self.y[:, :h], self.u[:, :q], self.v[:, :q]), self._like(self.y[:, h:], self.u[:, q:], self.v[:, q:]))
-
-    def to(self, device) -> "YUVFrames":
-        """These frames on ``device``: the planes' own bytes are copied (1.5 per pixel; an interleaved UV plane as one block) into dense
-        planes; frames already there are returned as they are."""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        if self.device == device:
-            return self
-        y = self.y.to(device)
-        if self.step_c == 2 and self.v.data_ptr() == self.u.data_ptr() + 1:
-            uv = torch.as_strided(self.u, (*self.u.shape, 2), (*self.u.stride(), 1)).to(device)
-            return self._like(y, uv[..., 0], uv[..., 1])
-        return self._like(y, self.u.to(device), self.v.to(device))
-
-    def matrix(self) -> L.YUVMatrix:
-        return yuv_matrix(self.standard, self.full_range)
-
-    def view_struct(self) -> L.YUVView:
-        """The ``ppms_yuv_view`` of these frames."""
-        return L.YUVView(self.y.data_ptr(), self.u.data_ptr(), self.v.data_ptr(), self.frame_stride_y, self.frame_stride_c, self.pitch_y, self.pitch_c,
-                         self.step_c, 0)
-
-    def to_rgb_u8(self) -> torch.Tensor:
-        """uint8 (N, 3, H0, W0) on the same device: the conversion of include/ppms.h in torch integer ops -- what the feature means by the
-        RGB bytes of these frames (the kernel's operands are ppms_video_ingest_u8's on them), and the path where the kernel cannot be used."""
-        m = self.matrix()
-        rows = torch.arange(self.height, device=self.device) >> 1
-        cols = torch.arange(self.width, device=self.device) >> 1
-        d = self.y.to(torch.int32) - m.y_off
-        e, f = (c.to(torch.int32)[:, rows][:, :, cols] - 128 for c in (self.u, self.v))
-        r = 1 << (m.shift - 1)
-        rgb = torch.stack([m.cy * d + m.crv * f + r, m.cy * d - m.cgu * e - m.cgv * f + r, m.cy * d + m.cbu * e + r], dim=1)
-        return (rgb >> m.shift).clamp_(0, 255).to(torch.uint8)
-
-
-class YUVStereoVideo:
-    """Both views of a decoded 4:2:0 video -- what ``batch_dict["stereo_video"]`` of ``forward_batch_test`` may be instead of a tensor:
-    two ``YUVFrames`` of one size, frame count, device and colour description.  ``len()``, slicing by frame range, ``to(device)``."""
-
-    def __init__(self, left: YUVFrames, right: YUVFrames):
-        if not isinstance(left, YUVFrames) or not isinstance(right, YUVFrames):
-            raise TypeError("YUVStereoVideo: two YUVFrames expected")
-        if (left.n, left.height, left.width) != (right.n, right.height, right.width):
-            raise ValueError(f"YUVStereoVideo: the views differ: {(left.n, left.height, left.width)} and {(right.n, right.height, right.width)}")
-        if (left.standard, left.full_range) != (right.standard, right.full_range) or left.device != right.device:
-            raise ValueError("YUVStereoVideo: both views need one standard, one range and one device")
-        self.left, self.right = left, right
-        self.height, self.width = left.height, left.width
-
-    def __len__(self) -> int:
-        return self.left.n
-
-    def __getitem__(self, frames: slice) -> "YUVStereoVideo":
-        return YUVStereoVideo(self.left[frames], self.right[frames])
-
-    def to(self, device) -> "YUVStereoVideo":
-        """The selected frames' planes on ``device`` (1.5 bytes per pixel and view)."""
-        return YUVStereoVideo(self.left.to(device), self.right.to(device))
-
-
-class _YUVPlanes:
-    """``_ByteFrames`` for a YUVStereoVideo on the device: ppms_video_ingest_yuv420 converts, pads and lays out both views in one launch."""
-
-    def __init__(self, video: YUVStereoVideo, pad_left: int = 0, pad_top: int = 0, rectify: Optional["StereoRectifier"] = None):
-        self.video, self.pad_left, self.pad_top = video, int(pad_left), int(pad_top)
-        self.rectify = rectify                                  # on the video's device: the video holds raw frames of its source size
-
-    def ingest(self, dst_fnet: L.SP, dst_cnet: L.SP, h: int, w: int) -> None:
-        v = self.video
-        left, right, m = v.left.view_struct(), v.right.view_struct(), v.left.matrix()      # host structs: read before the call returns
-        if self.rectify is not None:
-            r = self.rectify
-            L.check(L.load().ppms_video_ingest_yuv420_remap(left, right, m, r.left.view_struct(), r.right.view_struct(), len(v), r.height, r.width,
-                                                            self.pad_left, self.pad_top, h, w, byte_lut(v.left.device).data_ptr(), dst_fnet, dst_cnet,
-                                                            L.stream_ptr()))
-            return
-        L.check(L.load().ppms_video_ingest_yuv420(left, right, m, len(v), v.height, v.width, self.pad_left, self.pad_top, h, w,
-                                                  byte_lut(v.left.device).data_ptr(), dst_fnet, dst_cnet, L.stream_ptr()))
-
-    def held(self):
-        v = self.video
-        planes = (v.left.y, v.left.u, v.left.v, v.right.y, v.right.u, v.right.v)
-        return planes if self.rectify is None else planes + self.rectify.tensors()
-
-
-_BORDERS = {"replicate": L.BORDER_REPLICATE, "constant": L.BORDER_CONSTANT}
-
-
-class RectifyMap:
-    """One view's undistort + rectify (+ resize) map in fixed point, as ppms_video_ingest_u8_remap / _yuv420_remap read it (the arithmetic:
-    include/ppms.h): for every pixel of the RECTIFIED frame H0 x W0, ``xy`` int16 (H0, W0, 2) holds the integer source coordinate (x0, y0), x
-    first, and ``frac`` int16 or uint16 (H0, W0) its fraction in 1/32 pixel, fx | fy << 5 -- the layout OpenCV documents for
-    ``convertMaps(..., CV_16SC2)`` (not compared with OpenCV).  ``source_size`` = (Hs, Ws) of the raw frames; ``border`` "replicate" or
-    "constant" (a tap outside the frame is ``fill``, one byte for R, G and B).  Both tensors may be row-pitched views with ONE pitch
-    (``xy.stride(0) == 2 * frac.stride(0)``): the class reads ``data_ptr()`` and ``stride()`` and never copies.  ``apply_u8`` is the definition
-    of the remap.  Not covered: computing maps from calibration data, interpolation other than bilinear."""
-
-    def __init__(self, xy: torch.Tensor, frac: torch.Tensor, source_size, border: str = "replicate", fill: int = 0, _checked: bool = False):
-        if not torch.is_tensor(xy) or xy.dtype != torch.int16 or xy.dim() != 3 or xy.shape[2] != 2:
-            raise ValueError("RectifyMap: xy must be an int16 tensor (H0, W0, 2)")
-        if not torch.is_tensor(frac) or frac.dtype not in (torch.int16, torch.uint16) or frac.dim() != 2:
-            raise ValueError("RectifyMap: frac must be an int16 or uint16 tensor (H0, W0)")
-        h0, w0 = frac.shape
-        if h0 < 1 or w0 < 1 or tuple(xy.shape[:2]) != (h0, w0):
-            raise ValueError(f"RectifyMap: xy {tuple(xy.shape)} and frac {tuple(frac.shape)} must cover one non-empty frame")
-        if xy.device != frac.device:
-            raise ValueError("RectifyMap: xy and frac must be on one device")
-        frac = frac.view(torch.int16)                               # the same 16 bits
-        if xy.stride(2) != 1 or (w0 > 1 and (xy.stride(1) != 2 or frac.stride(1) != 1)):
-            raise ValueError(f"RectifyMap: the last dimensions must be contiguous (xy strides {xy.stride()}, frac strides {frac.stride()})")
-        # a size-1 dimension's stride is arbitrary: the smallest the kernel accepts stands in for it
-        pitch = frac.stride(0) if h0 > 1 else w0
-        if pitch < w0 or (h0 > 1 and xy.stride(0) != 2 * pitch):
-            raise ValueError(f"RectifyMap: xy and frac need one row pitch >= W0 (xy strides {xy.stride()}, frac strides {frac.stride()})")
-        if xy.data_ptr() % 4 or frac.data_ptr() % 2:
-            raise ValueError("RectifyMap: xy must start at a multiple of 4 bytes, frac of 2")
-        try:
-            hs, ws = (int(v) for v in source_size)
-        except (TypeError, ValueError):
-            raise ValueError(f"RectifyMap: source_size = {source_size!r} must be (Hs, Ws)") from None
-        if not (1 <= hs <= 32768 and 1 <= ws <= 32768):
-            raise ValueError(f"RectifyMap: source_size = ({hs}, {ws}) must lie in 1..32768")
-        if border not in _BORDERS:
-            raise ValueError(f"RectifyMap: border {border!r}; one of {sorted(_BORDERS)}")
-        if not 0 <= int(fill) <= 255:
-            raise ValueError(f"RectifyMap: fill = {fill} must be a byte")
-        if not _checked and bool(((frac < 0) | (frac > 1023)).any()):      # once: copies made by ``to`` hold the same values
-            raise ValueError("RectifyMap: frac holds values above 1023 (fx | fy << 5 with fx, fy in 0..31)")
-        self.xy, self.frac, self.pitch = xy, frac, int(pitch)
-        self.height, self.width, self.source_height, self.source_width = int(h0), int(w0), hs, ws
-        self.border, self.fill = border, int(fill)
-        self._on: Dict[torch.device, "RectifyMap"] = {xy.device: self}
-
-    @classmethod
-    def from_float(cls, map_x: torch.Tensor, map_y: torch.Tensor, source_size, border: str = "replicate", fill: int = 0) -> "RectifyMap":
-        """From float source coordinates (H0, W0) per rectified pixel (what ``initUndistortRectifyMap`` gives as CV_32FC1): per coordinate
-        q = round_half_even(v * 32), saturated so that q >> 5 stays an int16; then x0 = q >> 5, fx = q & 31 (floor and remainder)."""
-        if not (torch.is_tensor(map_x) and torch.is_tensor(map_y) and map_x.is_floating_point() and map_y.is_floating_point()
-                and map_x.dim() == 2 and map_x.shape == map_y.shape):
-            raise ValueError("RectifyMap.from_float: map_x and map_y must be floating-point tensors of one shape (H0, W0)")
-        if bool(torch.isnan(map_x).any()) or bool(torch.isnan(map_y).any()):
-            raise ValueError("RectifyMap.from_float: a coordinate is NaN")
-        qx, qy = (torch.round(m.double() * 32.0).clamp(-32768 * 32, 32767 * 32 + 31).to(torch.int64) for m in (map_x, map_y))
-        xy = torch.stack([qx >> 5, qy >> 5], dim=-1).to(torch.int16)
-        frac = ((qx & 31) | ((qy & 31) << 5)).to(torch.int16)
-        return cls(xy, frac, source_size, border, fill, _checked=True)
-
-    @classmethod
-    def identity(cls, h: int, w: int, device=None) -> "RectifyMap":
-        """The map that copies an h x w frame."""
-        ys, xs = torch.meshgrid(torch.arange(h, device=device), torch.arange(w, device=device), indexing="ij")
-        return cls(torch.stack([xs, ys], dim=-1).to(torch.int16), torch.zeros((h, w), dtype=torch.int16, device=device), (h, w), _checked=True)
-
-    @property
-    def device(self) -> torch.device:
-        return self.xy.device
-
-    def to(self, device) -> "RectifyMap":
-        """This map on ``device`` (6 bytes per rectified pixel, dense); made once per device and kept."""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        if device not in self._on:
-            there = RectifyMap(self.xy.to(device).contiguous(), self.frac.to(device).contiguous(), (self.source_height, self.source_width), self.border,
-                               self.fill, _checked=True)
-            there._on = self._on
-            self._on[device] = there
-        return self._on[device]
-
-    def view_struct(self) -> L.RemapView:
-        """The ``ppms_remap_view`` of this map."""
-        return L.RemapView(self.xy.data_ptr(), self.frac.data_ptr(), self.pitch, self.source_height, self.source_width, _BORDERS[self.border], self.fill, 0)
-
-    def apply_u8(self, rgb: torch.Tensor) -> torch.Tensor:
-        """uint8 (N, 3, Hs, Ws) -> uint8 (N, 3, H0, W0) on ``rgb``'s device: the remap of include/ppms.h in torch integer ops -- what the feature
-        means by the rectified bytes (the kernels' operands are ppms_video_ingest_u8's on them), and the path where the kernels cannot be used."""
-        hs, ws = self.source_height, self.source_width
-        if not torch.is_tensor(rgb) or rgb.dtype != torch.uint8 or rgb.dim() != 4 or tuple(rgb.shape[1:]) != (3, hs, ws):
-            raise ValueError(f"RectifyMap.apply_u8: uint8 frames (N, 3, {hs}, {ws}) expected, got "
-                             f"{tuple(rgb.shape) if torch.is_tensor(rgb) else type(rgb).__name__}")
-        m = self.to(rgb.device)
-        x0, y0 = m.xy[..., 0].to(torch.int64), m.xy[..., 1].to(torch.int64)
-        f = m.frac.to(torch.int32)
-        fx, fy = f & 31, (f >> 5) & 31
-        acc = torch.full((rgb.shape[0], 3, self.height, self.width), 512, dtype=torch.int32, device=rgb.device)
-        for dy in (0, 1):
-            for dx in (0, 1):
-                yy, xx = y0 + dy, x0 + dx
-                cy, cx = yy.clamp(0, hs - 1), xx.clamp(0, ws - 1)
-                p = rgb[:, :, cy, cx].to(torch.int32)             # clamped addresses in both modes
-                if self.border == "constant":
-                    p = torch.where((cy != yy) | (cx != xx), torch.full_like(p, self.fill), p)
-                acc += ((fx if dx else 32 - fx) * (fy if dy else 32 - fy)) * p
-        return (acc >> 10).to(torch.uint8)
-
-
-class StereoRectifier:
-    """The two views' ``RectifyMap``s of one rig -- what ``rectify=`` of ``PPMStereo.forward`` / ``forward_batch_test`` takes: one rectified size
-    (``height`` x ``width``), one source size (``source_height`` x ``source_width``), one device.  ``to(device)`` is kept per device."""
-
-    def __init__(self, left: RectifyMap, right: RectifyMap):
-        if not isinstance(left, RectifyMap) or not isinstance(right, RectifyMap):
-            raise TypeError("StereoRectifier: two RectifyMaps expected")
-        if (left.height, left.width) != (right.height, right.width):
-            raise ValueError(f"StereoRectifier: the rectified sizes differ: {(left.height, left.width)} and {(right.height, right.width)}")
-        if (left.source_height, left.source_width) != (right.source_height, right.source_width):
-            raise ValueError(f"StereoRectifier: the source sizes differ: {(left.source_height, left.source_width)} and "
-                             f"{(right.source_height, right.source_width)}")
-        if left.device != right.device:
-            raise ValueError("StereoRectifier: both maps must be on one device")
-        self.left, self.right = left, right
-        self.height, self.width = left.height, left.width
-        self.source_height, self.source_width = left.source_height, left.source_width
-
-    @property
-    def device(self) -> torch.device:
-        return self.left.device
-
-    def to(self, device) -> "StereoRectifier":
-        left, right = self.left.to(device), self.right.to(device)
-        return self if left is self.left and right is self.right else StereoRectifier(left, right)
-
-    def tensors(self):
-        """The four map tensors (for record_stream)."""
-        return self.left.xy, self.left.frac, self.right.xy, self.right.frac
-
-    def apply_u8(self, left: torch.Tensor, right: torch.Tensor):
-        return self.left.apply_u8(left), self.right.apply_u8(right)
-
-    def check_source(self, who: str, h: int, w: int) -> None:
-        if (int(h), int(w)) != (self.source_height, self.source_width):
-            raise ValueError(f"{who}: the frames are {int(h)} x {int(w)}, the rectification maps were made for {self.source_height} x {self.source_width}")
 
 
 class PPMStereo(PPMStereoHotPath):
@@ -1069,30 +549,29 @@ class PPMStereo(PPMStereoHotPath):
         return feats
 
     @torch.no_grad()
-    def forward(self, image1: torch.Tensor, image2: torch.Tensor, flow_init=None, iters: int = 10, test_mode: bool = False, pipeline=None,
+    def forward(self, image1, image2, flow_init=None, iters: int = 10, test_mode: bool = False, pipeline=None,
                 diagnostics: Optional[dict] = None, output: Optional[OutputSpec] = None, crop=None, frames=None,
                 rectify: Optional[StereoRectifier] = None):
         """PPMStereo.forward (ppmstereo.py:601-804): image (b, T, 3, H, W) in [0, 255], H, W multiples of 32 (b = 1: the device-resident
-        cascade; b > 1: the reference's glue around the batched forward_update_block).  Float images as in the reference, or both uint8:
-        with this package's encoders the bytes go through ONE kernel (ppms_video_ingest_u8) to the operands of the first convolutions --
-        the same bits as ``forward(image1.float(), image2.float())``; with other encoder callables they are converted to float on the device.
-        Or two ``YUVFrames`` on the device (decoded 4:2:0 frames: NV12 / I420): b = 1, T = their frame count; ONE kernel
-        (ppms_video_ingest_yuv420) converts them and writes the same operands -- the bits of ``forward`` on their ``to_rgb_u8()``.
+        cascade; b > 1: the reference's glue around the batched forward_update_block).  The two views are (``video.stereo_source``)
+          float tensors, as in the reference; or
+          uint8 tensors: the bits of ``forward(image1.float(), image2.float())``; or
+          two ``YUVFrames`` on the device (decoded 4:2:0 frames, NV12 / I420; b = 1, T = their frame count): the bits of ``forward`` on their
+          ``to_rgb_u8()``; or
+          with rectify (a ``StereoRectifier``) the RAW frames of an unrectified rig, uint8 device tensors (1, T, 3, Hs, Ws) or ``YUVFrames`` of its
+          source size Hs x Ws: the bits of ``forward`` on ``RectifyMap.apply_u8`` of each view's RGB bytes.  H, W above are then the rectified size,
+          and so are the outputs'.  Float images raise TypeError (the remap reads decoded bytes), b > 1 NotImplementedError, another frame size
+          than the maps' ValueError.
+        Bytes reach this package's encoders through ONE ingest kernel; other encoder callables get the float video made of them on the device.
         test_mode: (flow_up, uncertainty), each (b, T, 1, H, W); else (predictions (D, b, T, 1, H, W), uncertainties).
         pipeline (test_mode only): a ``ClipPipeline`` -- the result is valid once ``pipeline.wait()`` has been called.
         diagnostics (b = 1): a dict that receives ``["attn_redo"]``, the per-scale fix-up accounting of the memory read-out (see ``cascade``).
         output (test_mode, b = 1): an ``OutputSpec`` -- the call returns a dict of device tensors (1, n, 1, H0, W0) under "disparity", "depth"
         and "uncertainties" as the spec asks, written by ONE ppms_disparity_egress launch behind the last iteration (no float32 full-resolution
         tensor is made); crop = (pad_left, pad_top, H0, W0) inside the frame (default: the whole frame), frames = (from, to) (default: all).
-        rectify: a ``StereoRectifier`` -- the images are the RAW frames of an unrectified rig, two uint8 device tensors (1, T, 3, Hs, Ws) or two
-        ``YUVFrames`` of its source size Hs x Ws; ONE kernel (ppms_video_ingest_u8_remap / ppms_video_ingest_yuv420_remap) undistorts, rectifies and
-        writes the same operands -- the bits of ``forward`` on ``RectifyMap.apply_u8`` of each view's RGB bytes.  H, W above are then the rectified
-        size, and so are the outputs'.  Float images raise TypeError (the remap reads decoded bytes), b > 1 NotImplementedError, another frame
-        size than the maps' ValueError.  None (default): the calls above, launch for launch."""
+        rectify=None and output=None (the defaults) add no launch to the calls above."""
         if flow_init is not None:
             raise NotImplementedError("flow_init: the reference's own path for it reads undefined state (ppmstereo.py:691-693, 763)")
-        if rectify is not None:
-            self._check_rectify("PPMStereo.forward", rectify, image1, image2)
         if self.fnet is None or self.cnet is None:
             raise RuntimeError("PPMStereo.forward needs the encoders: pass fnet= / cnet= (outside the hot path, SURVEY.md section 8 f3-f5)")
         egress = None
@@ -1102,109 +581,46 @@ class PPMStereo(PPMStereoHotPath):
             egress = _EgressCall(output, crop, frames)
         elif crop is not None or frames is not None:
             raise ValueError("PPMStereo.forward: crop= and frames= select what output= writes; without output= they have no meaning")
-        if isinstance(image1, YUVFrames) or isinstance(image2, YUVFrames):
-            return self._forward_yuv(image1, image2, iters, test_mode, pipeline, diagnostics, egress, rectify)
-        if rectify is not None:
-            return self._forward_raw_u8(image1, image2, iters, test_mode, pipeline, diagnostics, egress, rectify)
-        if torch.is_tensor(image1) and torch.is_tensor(image2) and (image1.dtype == torch.uint8) != (image2.dtype == torch.uint8):
-            raise TypeError(f"PPMStereo.forward: image1 is {image1.dtype} and image2 is {image2.dtype}; both views must be uint8 or both floating point")
-        b, T, c, h, w = image1.shape
-        if b != 1 and pipeline is not None:
+        source = stereo_source("PPMStereo.forward", image1, image2, rectify)
+        if source.b != 1 and pipeline is not None:
             raise NotImplementedError("PPMStereo.forward: a ClipPipeline overlaps consecutive batch-1 clips")
-        if b != 1 and egress is not None:
+        if source.b != 1 and egress is not None:
             raise NotImplementedError("PPMStereo.forward: output= serves b = 1; the batched glue keeps float32 lists of predictions")
-        images = (image1, image2)
-        if image1.dtype == torch.uint8:
-            if self._hip_encoders() and image1.is_cuda and image2.is_cuda:
-                if image2.shape != image1.shape or c != 3:
-                    raise ValueError(f"PPMStereo.forward: two uint8 videos of one shape (b, T, 3, H, W) expected, got {tuple(image1.shape)} and {tuple(image2.shape)}")
-                images = _ByteFrames(image1.contiguous(), image2.contiguous(), 3 * h * w, b * T, h, w)
-            else:                                              # encoder callables of the caller: they get what they get for a float video
-                images = (image1.float(), image2.float())
-        return self._forward_images(images, b, T, h, w, image1.device, iters, test_mode, pipeline, diagnostics, egress)
-
-    @staticmethod
-    def _check_rectify(who: str, rectify, *views) -> None:
-        """What ``rectify=`` asks of the raw views (tensors (..., 3, Hs, Ws), ``YUVFrames`` or a ``YUVStereoVideo``); touches no device."""
-        if not isinstance(rectify, StereoRectifier):
-            raise TypeError(f"{who}: rectify must be a StereoRectifier, got {type(rectify).__name__}")
-        for v in views:
-            if isinstance(v, (YUVFrames, YUVStereoVideo)):
-                rectify.check_source(who, v.height, v.width)
-            elif torch.is_tensor(v):
-                if v.dtype != torch.uint8:
-                    raise TypeError(f"{who}: rectify= reads decoded bytes (uint8 frames or YUVFrames), got {v.dtype}; rectify float images before the call")
-                if v.dim() != 5:
-                    raise ValueError(f"{who}: a raw uint8 video has 5 dimensions, got {tuple(v.shape)}")
-                rectify.check_source(who, v.shape[-2], v.shape[-1])
-            else:
-                raise TypeError(f"{who}: rectify= takes uint8 tensors or YUV frames, got {type(v).__name__}")
-
-    def _forward_raw_u8(self, image1, image2, iters: int, test_mode: bool, pipeline, diagnostics, egress, rectify: StereoRectifier):
-        """``forward`` on two raw uint8 videos (1, T, 3, Hs, Ws) on the device with ``rectify=`` (checked by ``_check_rectify``)."""
-        b, T, c, hs, ws = image1.shape
-        if image2.shape != image1.shape or c != 3:
-            raise ValueError(f"PPMStereo.forward: two uint8 videos of one shape (1, T, 3, Hs, Ws) expected, got {tuple(image1.shape)} and {tuple(image2.shape)}")
-        if b != 1:
-            raise NotImplementedError("PPMStereo.forward: rectify= serves b = 1")
-        L.require_gpu(image1, image2)
-        rectify = rectify.to(image1.device)
-        if self._hip_encoders():
-            images = _ByteFrames(image1.contiguous(), image2.contiguous(), 3 * hs * ws, T, rectify.height, rectify.width, rectify=rectify)
-            return self._forward_images(images, 1, T, rectify.height, rectify.width, image1.device, iters, test_mode, pipeline, diagnostics, egress)
-        # encoder callables of the caller: the frames are rectified on the device and take the float path
-        out = {} if egress is None else dict(output=egress.spec, crop=egress.crop, frames=egress.frames)
-        left, right = rectify.apply_u8(image1[0], image2[0])
-        return self.forward(left.float()[None], right.float()[None], iters=iters, test_mode=test_mode, pipeline=pipeline, diagnostics=diagnostics, **out)
-
-    def _forward_yuv(self, image1, image2, iters: int, test_mode: bool, pipeline, diagnostics, egress=None, rectify: Optional[StereoRectifier] = None):
-        """``forward`` on two ``YUVFrames`` on the device: b = 1, T = their frame count, the frame size as it is (with ``rectify``: its rectified size)."""
-        if not (isinstance(image1, YUVFrames) and isinstance(image2, YUVFrames)):
-            raise TypeError(f"PPMStereo.forward: image1 is {type(image1).__name__} and image2 is {type(image2).__name__}; both views must be YUVFrames or both tensors")
-        video = YUVStereoVideo(image1, image2)
-        L.require_gpu(image1.y, image2.y)
-        out = {} if egress is None else dict(output=egress.spec, crop=egress.crop, frames=egress.frames)
-        if rectify is not None:
-            rectify = rectify.to(image1.device)
-            if self._hip_encoders():
-                return self._forward_images(_YUVPlanes(video, rectify=rectify), 1, len(video), rectify.height, rectify.width, image1.device, iters, test_mode,
-                                            pipeline, diagnostics, egress)
-            left, right = rectify.apply_u8(image1.to_rgb_u8(), image2.to_rgb_u8())
-            return self.forward(left.float()[None], right.float()[None], iters=iters, test_mode=test_mode, pipeline=pipeline, diagnostics=diagnostics, **out)
-        if self._hip_encoders():
-            return self._forward_images(_YUVPlanes(video), 1, len(video), video.height, video.width, image1.device, iters, test_mode, pipeline, diagnostics,
-                                        egress)
-        # encoder callables of the caller: they get what they get for a float video
-        return self.forward(image1.to_rgb_u8().float()[None], image2.to_rgb_u8().float()[None], iters=iters, test_mode=test_mode, pipeline=pipeline,
-                            diagnostics=diagnostics, **out)
+        return self._forward_images(source, source.n // source.b, None, iters, test_mode, pipeline, diagnostics, egress)
 
     def _hip_encoders(self) -> bool:
-        """Both encoders are this package's: their plans take the first-layer operands ppms_video_ingest_u8 writes."""
+        """Both encoders are this package's: their plans take the first-layer operands the ingest kernels write."""
         from .cnet import Feature
         from .encoder import BasicEncoder
         return isinstance(self.fnet, BasicEncoder) and isinstance(self.cnet, Feature)
 
-    def _forward_images(self, images, b: int, T: int, h: int, w: int, dev, iters: int, test_mode: bool, pipeline, diagnostics, egress=None):
-        """``forward`` behind its argument checks.  images: the two float videos (b, T, 3, h, w), or ``_ByteFrames`` / ``_YUVPlanes`` holding
-        b * T decoded frames per view that one ingest kernel pads to h x w (``forward_batch_test`` hands a window over unpadded).
+    def _forward_images(self, source, T: int, padder: Optional[InputPadder], iters: int, test_mode: bool, pipeline, diagnostics, egress=None):
+        """``forward`` behind its argument checks: ``source`` (``video.stereo_source``) holds n = b * T frames per view, which ``padder`` brings to the
+        model's size (None: they have it; ``forward_batch_test`` hands a window over unpadded).
         egress (an ``_EgressCall``; test_mode, b = 1): the result is ``cascade``'s dict of output planes, each (1, n, 1, H0, W0)."""
+        pad_left, pad_top, h, w = (0, 0, *source.size) if padder is None else padder.geometry()
+        n, dev = source.n, source.device
+        b = n // T
+        decoded = isinstance(source, _ByteSource)
+        if decoded:
+            L.require_gpu(*source.held())
         with torch.cuda.device(dev):
             # fnet (both views) and cnet (left view) depend on the images only and are chains of small launches that leave most of the chip
             # idle: cnet runs on a second stream beside fnet (whole call -3.5 ms at config 2); its outputs are handed to the caller's
             # stream with an event + record_stream
             cur = torch.cuda.current_stream(dev)
-            if isinstance(images, (_ByteFrames, _YUVPlanes)):
+            if decoded and self._hip_encoders():
                 # bytes -> the operands of fnet's conv1 and cnet's stem, one launch on the caller's stream (ordered before the side stream's wait)
-                fplan, cplan = self.fnet.plan(2 * b * T, h, w, dev), self.cnet.plan(b * T, h, w, dev)
-                images.ingest(fplan.s0_view(), cplan.s0_view(), h, w)
-                run_fnet = lambda: torch.split(fplan.run_filled(), b * T, dim=0)
+                fplan, cplan = self.fnet.plan(2 * n, h, w, dev), self.cnet.plan(n, h, w, dev)
+                source.ingest(fplan.s0_view(), cplan.s0_view(), pad_left, pad_top, h, w)
+                run_fnet = lambda: torch.split(fplan.run_filled(), n, dim=0)
                 run_cnet = cplan.run_filled
-                held = images.held()
-            else:
-                image1, image2 = images
-                c = image1.shape[2]
-                im1 = (2 * (image1 / 255.0) - 1.0).contiguous().reshape(b * T, c, h, w)
-                im2 = (2 * (image2 / 255.0) - 1.0).contiguous().reshape(b * T, c, h, w)
+                held = source.held()
+            else:                                              # float images, or encoder callables of the caller: pad, normalise, encoders
+                im1, im2 = source.float_views()
+                if padder is not None:
+                    im1, im2 = padder.pad(im1, im2)
+                im1, im2 = ((2 * (x / 255.0) - 1.0).contiguous() for x in (im1, im2))
                 run_fnet = lambda: self.fnet([im1, im2])
                 run_cnet = lambda: self.cnet(im1)
                 held = (im1,)
@@ -1245,16 +661,27 @@ class PPMStereo(PPMStereoHotPath):
                 return preds[-1].reshape(b, T, 1, h, w), uncs[-1].reshape(b, T, 1, h, w)
             return torch.stack(preds).reshape(-1, b, T, 1, h, w), torch.stack(uncs).reshape(-1, b, T, 1, h, w)
 
+    def _window_forward(self, video, start: int, stop: int, dev, iters: int, pipe, diag, output: Optional[OutputSpec] = None, keep=None,
+                        rectify: Optional[StereoRectifier] = None):
+        """One window of forward_batch_test: frames [start, stop) of the video -> ((disparity, uncertainty) of the padded window, each (1, T, 1, H, W),
+        the InputPadder that crops them back).  output (an OutputSpec): the window's egress launch crops with that padder's geometry and writes the
+        window-local frames keep = (from, to); the result is then the dict of planes, each (1, n, 1, H0, W0), in place of the pair."""
+        # host -> device: ONE copy of the window's contiguous block (a tensor's (T, 2, 3, H, W), a YUV video's planes); the views are split and
+        # padded on the device (slicing a view out on the host first costs a host-side copy of each view, padding there another one)
+        source = stereo_source("forward_batch_test", video[start:stop].to(dev), rectify=rectify)
+        padder = InputPadder(source.size, divis_by=32)
+        egress = None if output is None else _EgressCall(output, padder.geometry()[:2] + (padder.ht, padder.wd), keep)
+        return self._forward_images(source, source.n, padder, iters, True, pipe, diag, egress), padder
+
     @torch.no_grad()
     def forward_batch_test(self, batch_dict: Dict, kernel_size: int = 20, iters: int = 20, device=None, shard_ranks: bool = False,
                            diagnostics: bool = False, output: Optional[OutputSpec] = None, rectify: Optional[StereoRectifier] = None):
         """PPMStereo.forward_batch_test (ppmstereo.py:238-320): batch_dict["stereo_video"] (N, 2, 3, H, W) on the host;
         per window: InputPadder(divis_by=32), one host->device copy, forward(test_mode=True), unpad, one device->host copy;
-        a uint8 video (host or device) is copied as bytes -- a quarter of the float video's -- and, with this package's encoders, padded and
-        normalised inside ppms_video_ingest_u8: the same bits as for ``stereo_video.float()``;
+        a uint8 video (host or device) is copied as bytes -- a quarter of the float video's: the same bits as for ``stereo_video.float()``;
         a ``YUVStereoVideo`` (decoded 8-bit 4:2:0 frames, NV12 or I420, host or device) is copied per window as its planes -- 1.5 bytes per
-        pixel and view -- and converted, padded and normalised inside ppms_video_ingest_yuv420: the bits of the uint8 video of its
-        ``to_rgb_u8()`` frames (10-bit formats, 4:2:2 / 4:4:4, interpolated chroma siting and b > 1 are not covered);
+        pixel and view: the bits of the uint8 video of its ``to_rgb_u8()`` frames (10-bit formats, 4:2:2 / 4:4:4, interpolated chroma siting
+        and b > 1 are not covered).  With this package's encoders the bytes are converted, padded and normalised inside the one ingest launch;
         windows of ``kernel_size`` frames every ``kernel_size // 2``, centre frames kept (:296-307).  Windows whose output the
         reference computes and then drops are not run.  Returns {"disparity", "uncertainties"}: (N, 1, H, W) CPU tensors.
         shard_ranks: under torch.distributed the windows are dealt round-robin over the ranks (independent units, no data-path
@@ -1264,202 +691,84 @@ class PPMStereo(PPMStereoHotPath):
         output: an ``OutputSpec`` -- per window ONE ppms_disparity_egress launch writes the kept frames, cropped and converted, and only
         those are copied device -> host, straight into their slice of pinned (N, 1, H, W) results of the planes' dtypes (uint16 disparity and
         uint8 confidence: 3 bytes per pixel and kept frame, where the default path copies 8 for every frame of the window).  Returns
-        {"disparity", "depth" when asked, "uncertainties" unless its format is None}.  Not with ``shard_ranks``.  None (default): the float32
-        path above, launch for launch.
+        {"disparity", "depth" when asked, "uncertainties" unless its format is None}.  Not with ``shard_ranks``.
         rectify: a ``StereoRectifier`` -- the video holds the RAW frames of an unrectified rig, (N, 2, 3, Hs, Ws) uint8 or a ``YUVStereoVideo`` of
-        its source size Hs x Ws.  Each window's raw bytes are copied as above, the maps once per call (6 bytes per rectified pixel and view), and
-        ppms_video_ingest_u8_remap / ppms_video_ingest_yuv420_remap undistort, rectify, pad and normalise in the one ingest launch: the bits of
-        the call on the uint8 video of ``RectifyMap.apply_u8``.  H x W of the results (and of the ``InputPadder``) is the rectified size.  A float
-        video raises TypeError, another frame size than the maps' ValueError.  None (default): the paths above, launch for launch."""
+        its source size Hs x Ws.  Each window's raw bytes are copied as above, the maps once per device (6 bytes per rectified pixel and view):
+        the bits of the call on the uint8 video of ``RectifyMap.apply_u8``.  H x W of the results (and of the ``InputPadder``) is the rectified
+        size.  A float video raises TypeError, another frame size than the maps' ValueError.
+        output=None and rectify=None (the defaults) add no launch to the paths above."""
         if output is not None:
             if not isinstance(output, OutputSpec):
                 raise TypeError(f"forward_batch_test: output must be an OutputSpec, got {type(output).__name__}")
             if shard_ranks:
                 raise NotImplementedError("forward_batch_test: output= with shard_ranks=True is not served: dist.gather_kept_frames moves float32")
         video = batch_dict["stereo_video"]
-        if rectify is not None:
-            self._check_rectify("forward_batch_test", rectify, video)
+        # every argument check, on one frame where the video lies: before any device work.  (H0, W0): the results' size
+        H0, W0 = stereo_source("forward_batch_test", video[:1], rectify=rectify).size
         num_ims = len(video)
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if rectify is not None:
-            rectify = rectify.to(dev)                             # the maps cross once per call, not once per window
-        disp_preds, uncertainties = [], []
         diag = {} if diagnostics else None
-        plan = window_plan(num_ims, kernel_size)
-        if shard_ranks and torch.distributed.is_available() and torch.distributed.is_initialized():
-            from . import dist as D
-            rank, world = torch.distributed.get_rank(), torch.distributed.get_world_size()
-            mine_d, mine_u, first = [], [], 0
-            firsts = []
-            for start, stop, keep_from, keep_to in plan:          # first kept frame of every window in video coordinates
-                firsts.append(start + keep_from)
-            for wi, (start, stop, keep_from, keep_to) in enumerate(plan):
-                if wi % world != rank:
-                    continue
-                d, u, padder = self._window_forward(video, start, stop, dev, iters, None, diag, rectify=rectify)   # one host -> device copy per window (see below)
-                d, u = padder.unpad(d[0]), padder.unpad(u[0])               # (T, 1, H0, W0)
-                mine_d.append((firsts[wi], d[keep_from:keep_to].abs()[:, :1]))
-                mine_u.append((firsts[wi], u[keep_from:keep_to].abs()[:, :1]))
-            H0, W0 = self._result_size(video, rectify)
-            disp = D.gather_kept_frames(mine_d, num_ims, H0, W0)
-            unc = D.gather_kept_frames(mine_u, num_ims, H0, W0)
-            out = {"disparity": disp.cpu(), "uncertainties": unc.cpu()}
+        plan = egress_plan(window_plan(num_ims, kernel_size))    # (start, stop, keep_from, keep_to, dst_from, dst_to) per window
+
+        def finish(out):
             if diag is not None:
                 out["attn_redo"] = diag.get("attn_redo", {})
             return out
-        # several windows: independent units -> software pipeline (ClipPipeline): window k + 1's encoders and small scales are enqueued
-        # before window k's result is collected, and run under window k's 1/4 scale
-        pipe = ClipPipeline(dev) if len(plan) > 1 else None
-        pending = None
-        if output is not None:
-            H0, W0 = self._result_size(video, rectify)
-            host = output.empty(num_ims, int(H0), int(W0), "cpu", pin_memory=True)           # allocated once; every window fills its slice
 
-            def collect_planes(item):
-                planes, handle, dst_from, dst_to = item
-                if pipe is not None:
-                    pipe.wait(handle)
-                torch.cuda.current_stream(dev).synchronize()               # in front of the copy, as in collect() below
-                for key, plane in planes.items():
-                    host[key][dst_from:dst_to].copy_(plane[0])             # kept frames only, device -> their slice of the pinned result
+        if shard_ranks and torch.distributed.is_available() and torch.distributed.is_initialized():
+            from . import dist as D
+            mine_d, mine_u = [], []
+            for start, stop, keep_from, keep_to, first, _ in shard_windows(plan, torch.distributed.get_rank(), torch.distributed.get_world_size()):
+                (d, u), padder = self._window_forward(video, start, stop, dev, iters, None, diag, rectify=rectify)    # one host -> device copy per window
+                d, u = padder.unpad(d[0]), padder.unpad(u[0])               # (T, 1, H0, W0)
+                mine_d.append((first, d[keep_from:keep_to].abs()[:, :1]))   # first: the window's first kept frame in video coordinates
+                mine_u.append((first, u[keep_from:keep_to].abs()[:, :1]))
+            disp, unc = D.gather_kept_frames(mine_d, num_ims, H0, W0), D.gather_kept_frames(mine_u, num_ims, H0, W0)
+            return finish({"disparity": disp.cpu(), "uncertainties": unc.cpu()})
 
-            with torch.cuda.device(dev):
-                for start, stop, keep_from, keep_to, dst_from, dst_to in egress_plan(plan):
-                    planes = self._window_forward(video, start, stop, dev, iters, pipe, diag, output, (keep_from, keep_to), rectify=rectify)
-                    item = (planes, None if pipe is None else pipe.last, dst_from, dst_to)
-                    if pending is not None:
-                        collect_planes(pending)
-                    pending = item
-                collect_planes(pending)
-            if diag is not None:
-                host["attn_redo"] = diag.get("attn_redo", {})
-            return host
-
-        def collect(item):
-            d, u, handle, padder, keep_from, keep_to = item
-            if pipe is not None:
-                pipe.wait(handle)
+        def idle_stream():
             # device -> host.  The stream is synchronised FIRST (a spinning wait): a pageable copy issued while the clip's ~900 launches are
             # still queued blocks inside the runtime on an interrupt-driven wait, and on a loaded host (the GPU boxes: load average 50-60)
             # the thread was rescheduled 50-150 ms late in every other call (whole call 50 / 100 / 195 ms alternating; with the
             # synchronisation in front the copy finds an idle stream: 49-50 ms every time, tools/whole_call_probe.py)
+            torch.cuda.current_stream(dev).synchronize()
+
+        kept_d, kept_u = [], []
+
+        def keep_float32(result, padder, keep_from, keep_to, dst_from, dst_to):
+            d, u = result
             du = torch.cat([padder.unpad(d[0])[:, None], padder.unpad(u[0])[:, None]])                        # one copy for both results
-            torch.cuda.current_stream(du.device).synchronize()
+            idle_stream()
             du = du.cpu()
             d, u = du[:du.shape[0] // 2], du[du.shape[0] // 2:]
-            disp_preds.append(d[keep_from:keep_to])
-            uncertainties.append(u[keep_from:keep_to])
+            kept_d.append(d[keep_from:keep_to])
+            kept_u.append(u[keep_from:keep_to])
 
+        def keep_planes(planes, padder, keep_from, keep_to, dst_from, dst_to):
+            idle_stream()
+            for key, plane in planes.items():
+                host[key][dst_from:dst_to].copy_(plane[0])                 # kept frames only, device -> their slice of the pinned result
+
+        if output is not None:
+            host = output.empty(num_ims, int(H0), int(W0), "cpu", pin_memory=True)           # allocated once; every window fills its slice
+        sink = keep_float32 if output is None else keep_planes
+
+        def collect(result, padder, handle, span):
+            if pipe is not None:
+                pipe.wait(handle)
+            sink(result, padder, *span)
+
+        # several windows: independent units -> software pipeline (ClipPipeline): window k + 1's encoders and small scales are enqueued
+        # before window k's result is collected, and run under window k's 1/4 scale
+        pipe = ClipPipeline(dev) if len(plan) > 1 else None
+        pending = None
         with torch.cuda.device(dev):
-            for start, stop, keep_from, keep_to in plan:
-                d, u, padder = self._window_forward(video, start, stop, dev, iters, pipe, diag, rectify=rectify)
-                item = (d, u, None if pipe is None else pipe.last, padder, keep_from, keep_to)
+            for start, stop, *span in plan:
+                item = (*self._window_forward(video, start, stop, dev, iters, pipe, diag, output, span[:2], rectify), None if pipe is None else pipe.last, span)
                 if pending is not None:
-                    collect(pending)
+                    collect(*pending)
                 pending = item
-            collect(pending)
-        out = {"disparity": torch.cat(disp_preds).squeeze(1).abs()[:, :1], "uncertainties": torch.cat(uncertainties).squeeze(1).abs()[:, :1]}
-        if diag is not None:
-            out["attn_redo"] = diag.get("attn_redo", {})
-        return out
-
-
-def _result_size(video, rectify: Optional[StereoRectifier]):
-    """(H0, W0) of forward_batch_test's results: the rectified size, or the video's own."""
-    if rectify is not None:
-        return rectify.height, rectify.width
-    return (video.height, video.width) if isinstance(video, YUVStereoVideo) else video.shape[-2:]
-
-
-PPMStereo._result_size = staticmethod(_result_size)
-
-
-def _window_forward(self, video, start: int, stop: int, dev, iters: int, pipe, diag, output: Optional[OutputSpec] = None, keep=None,
-                    rectify: Optional[StereoRectifier] = None):
-    """One window of forward_batch_test: frames [start, stop) of the (N, 2, 3, H0, W0) video or the YUVStereoVideo -> (disparity, uncertainty) of the padded
-    window, each (1, T, 1, H, W), and the InputPadder that crops them back.  output (an OutputSpec): the window's egress launch crops with that
-    padder's geometry and writes the window-local frames keep = (from, to); the result is then the dict of planes, each (1, n, 1, H0, W0).
-    rectify (a StereoRectifier on dev): the video holds raw frames of its source size; H0 x W0, and so the padder, is its rectified size."""
-    def egress(padder):
-        if output is None:
-            return None
-        pad_left, pad_top, _, _ = padder.geometry()
-        return _EgressCall(output, (pad_left, pad_top, padder.ht, padder.wd), keep)
-
-    # host -> device: ONE copy of the window's contiguous (T, 2, 3, H, W) block; the two views are split and padded on the
-    # device (slicing a view out on the host first costs a host-side copy of each view, padding there another one)
-    win = video[start:stop].to(dev)
-    if isinstance(win, YUVStereoVideo):
-        if self._hip_encoders():
-            # the planes stay as the decoder left them: ppms_video_ingest_yuv420 converts, and pads by clamping its source coordinate
-            padder = InputPadder(_result_size(win, rectify), divis_by=32)
-            pad_left, pad_top, H, W = padder.geometry()
-            planes = _YUVPlanes(win, pad_left, pad_top, rectify)
-            if output is not None:
-                return self._forward_images(planes, 1, len(win), H, W, dev, iters, True, pipe, diag, egress(padder))
-            d, u = self._forward_images(planes, 1, len(win), H, W, dev, iters, True, pipe, diag)
-            return d, u, padder
-        rgb = win.left.to_rgb_u8(), win.right.to_rgb_u8()
-        if rectify is not None:
-            rgb = rectify.apply_u8(*rgb)
-        win = torch.stack(rgb, dim=1).float()                   # encoder callables of the caller: the float path
-    elif win.dtype == torch.uint8:
-        if win.dim() != 5 or win.shape[1] != 2 or win.shape[2] != 3:
-            raise ValueError(f"forward_batch_test: a uint8 stereo_video is (N, 2, 3, H, W), got {tuple(video.shape)}")
-        if self._hip_encoders():
-            # the bytes stay as they are: ppms_video_ingest_u8 reads both views out of the block and pads by clamping its source coordinate
-            win = win.contiguous()
-            T, H0, W0 = win.shape[0], win.shape[3], win.shape[4]
-            stride = 6 * H0 * W0
-            if rectify is not None:                              # the block holds raw frames; what is padded is the rectified frame
-                H0, W0 = rectify.height, rectify.width
-            padder = InputPadder((H0, W0), divis_by=32)
-            pad_left, pad_top, H, W = padder.geometry()
-            frames = _ByteFrames(win[:, 0], win[:, 1], stride, T, H0, W0, pad_left, pad_top, rectify)
-            if output is not None:
-                return self._forward_images(frames, 1, T, H, W, dev, iters, True, pipe, diag, egress(padder))
-            d, u = self._forward_images(frames, 1, T, H, W, dev, iters, True, pipe, diag)
-            return d, u, padder
-        if rectify is not None:
-            win = torch.stack(rectify.apply_u8(win[:, 0], win[:, 1]), dim=1)
-        win = win.float()                                        # encoder callables of the caller: the float path from here on
-    left, right = win[:, 0], win[:, 1]
-    padder = InputPadder(left.shape, divis_by=32)
-    left, right = padder.pad(left, right)
-    if output is not None:
-        return self.forward(left[None], right[None], iters=iters, test_mode=True, pipeline=pipe, diagnostics=diag, output=output,
-                            crop=egress(padder).crop, frames=keep)
-    d, u = self.forward(left[None], right[None], iters=iters, test_mode=True, pipeline=pipe, diagnostics=diag)
-    return d, u, padder
-
-
-PPMStereo._window_forward = _window_forward
-
-
-def window_plan(num_ims: int, kernel_size: int = 20):
-    """Sliding-window schedule of PPMStereo.forward_batch_test (ppmstereo.py:242-310): list of
-    (start, stop, keep_from, keep_to) with keep_* window-local.  Trailing windows whose output the reference
-    discards (:296) are not scheduled at all."""
-    stride = kernel_size // 2
-    if kernel_size > num_ims:
-        return [(0, num_ims, 0, num_ims)]
-    plan = []
-    for i in range(0, num_ims, stride):
-        n = min(i + kernel_size, num_ims) - i
-        if plan and n >= stride:
-            plan.append((i, i + n, stride // 2, n if n < kernel_size else n + (-stride // 2)))
-        elif not plan:
-            plan.append((i, i + n, 0, n + (-stride // 2)))
-    return plan
-
-
-def egress_plan(plan):
-    """``window_plan`` with the destination of every window's kept frames: (start, stop, keep_from, keep_to, dst_from, dst_to) -- the egress
-    launch of the window writes its frames [keep_from, keep_to), and they are frames [dst_from, dst_to) of the video."""
-    return [(start, stop, keep_from, keep_to, start + keep_from, start + keep_to) for start, stop, keep_from, keep_to in plan]
-
-
-def shard_windows(plan, rank: int, world: int):
-    """Window-level sharding across GPUs (SURVEY.md section 8e level 1): windows are independent units; rank r takes
-    windows r, r+world, ...  No data-path collective; the kept disparities are gathered once at the end."""
-    return [w for i, w in enumerate(plan) if i % world == rank]
+            collect(*pending)
+        if output is not None:
+            return finish(host)
+        return finish({"disparity": torch.cat(kept_d).squeeze(1).abs()[:, :1], "uncertainties": torch.cat(kept_u).squeeze(1).abs()[:, :1]})

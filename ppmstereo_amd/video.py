@@ -1,0 +1,634 @@
+"""Video in and out of the model: what ``PPMStereo.forward`` / ``forward_batch_test`` accept beside the reference's float tensors (uint8 and decoded
+YUV 4:2:0 frames, raw frames with a ``StereoRectifier``), the one private family of sources that stands for all of them behind the front doors
+(``stereo_source``), the output planes they can hand back (``OutputSpec``) and the sliding-window schedule.  Nothing here knows the model."""
+from __future__ import annotations
+
+import math
+from typing import Dict, Optional
+
+import torch
+
+from . import _lib as L
+
+
+class InputPadder:
+    """Replicate-pads the last two dimensions up to multiples of ``divis_by`` and crops results back (the reference's helper,
+    models/core/utils/utils.py:19-44).  "sintel" mode centres the image (the extra row / column of an odd pad goes to the bottom /
+    right); any other mode pads the height at the bottom only."""
+
+    def __init__(self, dims, mode: str = "sintel", divis_by: int = 8):
+        self.ht, self.wd = int(dims[-2]), int(dims[-1])
+        extra_h, extra_w = -self.ht % divis_by, -self.wd % divis_by
+        left, top = extra_w // 2, (extra_h // 2 if mode == "sintel" else 0)
+        self._pad = [left, extra_w - left, top, extra_h - top]          # F.pad order: left, right, top, bottom
+
+    def geometry(self):
+        """(pad_left, pad_top, H, W): the columns / rows ``pad`` adds in front and the padded size (what ppms_video_ingest_u8 takes)."""
+        left, right, top, bottom = self._pad
+        return left, top, top + self.ht + bottom, left + self.wd + right
+
+    def pad(self, *inputs):
+        for x in inputs:
+            if x.ndim != 4:
+                raise ValueError(f"InputPadder.pad: 4-D tensors expected, got {tuple(x.shape)}")
+        if not any(self._pad):
+            return list(inputs)                                           # (already a multiple: nothing to copy)
+        return [torch.nn.functional.pad(x, self._pad, mode="replicate") for x in inputs]
+
+    def unpad(self, x):
+        if x.ndim != 4:
+            raise ValueError(f"InputPadder.unpad: 4-D tensor expected, got {tuple(x.shape)}")
+        left, right, top, bottom = self._pad
+        return x[..., top:x.shape[-2] - bottom, left:x.shape[-1] - right]
+
+
+_BYTE_LUT: Dict[int, torch.Tensor] = {}
+
+
+def byte_lut(device) -> torch.Tensor:
+    """fp32 [256] on `device`: the normalised value of every byte, from the expression ``forward`` applies to float images ON THE SAME
+    DEVICE -- torch's division by a Python scalar need not round like a division written elsewhere, so the table is what makes the uint8
+    path the float path's bits.  Built once per device (the host waits for it once)."""
+    device = torch.device(device)
+    idx = torch.cuda.current_device() if device.index is None else device.index
+    if idx not in _BYTE_LUT:
+        dev = torch.device("cuda", idx)
+        _BYTE_LUT[idx] = (2 * (torch.arange(256, dtype=torch.float32, device=dev) / 255.0) - 1.0).contiguous()
+        torch.cuda.current_stream(dev).synchronize()             # later calls may read it from any stream
+    return _BYTE_LUT[idx]
+
+
+_YUV_STANDARDS = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}       # (Kr, Kb)
+
+
+def yuv_matrix(standard: str = "bt709", full_range: bool = False, shift: int = 14) -> L.YUVMatrix:
+    """The fixed-point YCbCr -> RGB conversion ppms_video_ingest_yuv420 applies (include/ppms.h), as its ``ppms_yuv_matrix``: Python
+    ``round()`` of the double-precision coefficients times 2^shift.  Limited range: Y in [16, 235], chroma in [16, 240]."""
+    if standard not in _YUV_STANDARDS:
+        raise ValueError(f"yuv_matrix: standard {standard!r}; one of {sorted(_YUV_STANDARDS)}")
+    if not 8 <= shift <= 20:
+        raise ValueError(f"yuv_matrix: shift = {shift} must lie in [8, 20]")
+    kr, kb = _YUV_STANDARDS[standard]
+    kg = 1.0 - kr - kb
+    sy, sc = (1.0, 1.0) if full_range else (255.0 / 219.0, 255.0 / 224.0)
+    one = float(1 << shift)
+    return L.YUVMatrix(y_off=0 if full_range else 16, cy=round(sy * one), crv=round(sc * 2.0 * (1.0 - kr) * one),
+                       cgu=round(sc * 2.0 * kb * (1.0 - kb) / kg * one), cgv=round(sc * 2.0 * kr * (1.0 - kr) / kg * one),
+                       cbu=round(sc * 2.0 * (1.0 - kb) * one), shift=shift, reserved=0)
+
+
+class YUVFrames:
+    """One view's N decoded 8-bit YUV 4:2:0 frames, as a decoder leaves them: ``y`` uint8 (N, H0, W0), ``u`` / ``v`` uint8
+    (N, ceil(H0 / 2), ceil(W0 / 2)).  Each may be a strided VIEW of a decoder surface -- a pitched plane, the two halves of an interleaved
+    UV plane (``nv12``), one half of a frame that packs both views (``split_side_by_side`` / ``split_top_bottom``): the class reads
+    ``data_ptr()`` and ``stride()`` and never copies.  ``y`` needs last-dimension stride 1; ``u`` and ``v`` equal strides with
+    last-dimension stride 1 (planar: I420 / yuv420p) or 2 (interleaved: NV12); anything else raises ValueError.  Luma pixel (y, x) takes
+    chroma sample (y >> 1, x >> 1); ``standard`` ("bt709" / "bt601") and ``full_range`` choose ``yuv_matrix``; ``to_rgb_u8`` is the
+    definition of the RGB bytes.  Not covered: 10-bit surfaces (P010), 4:2:2 and 4:4:4, interpolated chroma siting, b > 1."""
+
+    def __init__(self, y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, standard: str = "bt709", full_range: bool = False):
+        for name, t in (("y", y), ("u", u), ("v", v)):
+            if not torch.is_tensor(t) or t.dtype != torch.uint8 or t.dim() != 3:
+                raise ValueError(f"YUVFrames: {name} must be a uint8 tensor (N, rows, columns)")
+        n, h0, w0 = y.shape
+        hc, wc = (h0 + 1) // 2, (w0 + 1) // 2
+        if n < 1 or h0 < 1 or w0 < 1:
+            raise ValueError(f"YUVFrames: empty y plane {tuple(y.shape)}")
+        if tuple(u.shape) != (n, hc, wc) or tuple(v.shape) != (n, hc, wc):
+            raise ValueError(f"YUVFrames: y {tuple(y.shape)} needs u and v of {(n, hc, wc)}, got {tuple(u.shape)} and {tuple(v.shape)}")
+        if u.device != y.device or v.device != y.device:
+            raise ValueError("YUVFrames: y, u and v must be on one device")
+        if w0 > 1 and y.stride(2) != 1:
+            raise ValueError(f"YUVFrames: y has last-dimension stride {y.stride(2)}; luma samples must be adjacent bytes")
+        step = u.stride(2) if wc > 1 else 1                                # (a one-column chroma plane never takes a step)
+        if u.stride() != v.stride():
+            raise ValueError(f"YUVFrames: u and v must have equal strides, got {u.stride()} and {v.stride()}")
+        if step not in (1, 2):
+            raise ValueError(f"YUVFrames: chroma last-dimension stride {step}; 1 (planar) or 2 (interleaved) expected")
+        # a size-1 dimension's stride is arbitrary: the smallest the kernel accepts stands in for it
+        self.pitch_y = y.stride(1) if h0 > 1 else w0
+        self.pitch_c = u.stride(1) if hc > 1 else step * (wc - 1) + 1
+        self.step_c = step
+        self.frame_stride_y = y.stride(0) if n > 1 else (h0 - 1) * self.pitch_y + w0
+        self.frame_stride_c = u.stride(0) if n > 1 else (hc - 1) * self.pitch_c + step * (wc - 1) + 1
+        if (self.pitch_y < w0 or self.pitch_c < step * (wc - 1) + 1 or self.frame_stride_y < (h0 - 1) * self.pitch_y + w0
+                or self.frame_stride_c < (hc - 1) * self.pitch_c + step * (wc - 1) + 1):
+            raise ValueError(f"YUVFrames: rows or frames overlap (y strides {y.stride()}, chroma strides {u.stride()})")
+        yuv_matrix(standard)                                               # (refuses an unknown standard here)
+        self.y, self.u, self.v, self.standard, self.full_range = y, u, v, standard, bool(full_range)
+        self.n, self.height, self.width = n, h0, w0
+
+    @classmethod
+    def nv12(cls, y: torch.Tensor, uv: torch.Tensor, standard: str = "bt709", full_range: bool = False) -> "YUVFrames":
+        """NV12: ``uv`` uint8 (N, ceil(H0 / 2), ceil(W0 / 2), 2), U first -- a hardware decoder's surface."""
+        if not torch.is_tensor(uv) or uv.dim() != 4 or uv.shape[-1] != 2:
+            raise ValueError("YUVFrames.nv12: uv must be (N, rows, columns, 2)")
+        return cls(y, uv[..., 0], uv[..., 1], standard, full_range)
+
+    @classmethod
+    def i420(cls, y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, standard: str = "bt709", full_range: bool = False) -> "YUVFrames":
+        """I420 / yuv420p: three planes -- a software decoder's frame."""
+        return cls(y, u, v, standard, full_range)
+
+    def __len__(self) -> int:
+        return self.n
+
+    @property
+    def device(self) -> torch.device:
+        return self.y.device
+
+    def _like(self, y, u, v) -> "YUVFrames":
+        return YUVFrames(y, u, v, self.standard, self.full_range)
+
+    def __getitem__(self, frames: slice) -> "YUVFrames":
+        if not isinstance(frames, slice):
+            raise TypeError("YUVFrames: index with a slice of frames")
+        return self._like(self.y[frames], self.u[frames], self.v[frames])
+
+    def split_side_by_side(self):
+        """(left, right): the two halves of frames that pack both views side by side; views, no copy.  The packed width must be even --
+        and each half's too, or the right half's chroma would start between two samples."""
+        w = self.width
+        if w % 2 or (w // 2) % 2:
+            raise ValueError(f"YUVFrames.split_side_by_side: a packed width of {w} does not split into two views with whole chroma samples")
+        h, q = w // 2, w // 4
+        return (self._like(self.y[:, :, :h], self.u[:, :, :q], self.v[:, :, :q]), self._like(self.y[:, :, h:], self.u[:, :, q:], self.v[:, :, q:]))
+
+    def split_top_bottom(self):
+        """(left, right) = (top, bottom) halves of frames that pack both views one above the other; views, no copy (even halves, as above)."""
+        ht = self.height
+        if ht % 2 or (ht // 2) % 2:
+            raise ValueError(f"YUVFrames.split_top_bottom: a packed height of {ht} does not split into two views with whole chroma rows")
+        h, q = ht // 2, ht // 4
+        return (self._like(self.y[:, :h], self.u[:, :q], self.v[:, :q]), self._like(self.y[:, h:], self.u[:, q:], self.v[:, q:]))
+
+    def to(self, device) -> "YUVFrames":
+        """These frames on ``device``: the planes' own bytes are copied (1.5 per pixel; an interleaved UV plane as one block) into dense
+        planes; frames already there are returned as they are."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if self.device == device:
+            return self
+        y = self.y.to(device)
+        if self.step_c == 2 and self.v.data_ptr() == self.u.data_ptr() + 1:
+            uv = torch.as_strided(self.u, (*self.u.shape, 2), (*self.u.stride(), 1)).to(device)
+            return self._like(y, uv[..., 0], uv[..., 1])
+        return self._like(y, self.u.to(device), self.v.to(device))
+
+    def matrix(self) -> L.YUVMatrix:
+        return yuv_matrix(self.standard, self.full_range)
+
+    def view_struct(self) -> L.YUVView:
+        """The ``ppms_yuv_view`` of these frames."""
+        return L.YUVView(self.y.data_ptr(), self.u.data_ptr(), self.v.data_ptr(), self.frame_stride_y, self.frame_stride_c, self.pitch_y, self.pitch_c,
+                         self.step_c, 0)
+
+    def to_rgb_u8(self) -> torch.Tensor:
+        """uint8 (N, 3, H0, W0) on the same device: the conversion of include/ppms.h in torch integer ops -- what the feature means by the
+        RGB bytes of these frames (the kernel's operands are ppms_video_ingest_u8's on them), and the path where the kernel cannot be used."""
+        m = self.matrix()
+        rows = torch.arange(self.height, device=self.device) >> 1
+        cols = torch.arange(self.width, device=self.device) >> 1
+        d = self.y.to(torch.int32) - m.y_off
+        e, f = (c.to(torch.int32)[:, rows][:, :, cols] - 128 for c in (self.u, self.v))
+        r = 1 << (m.shift - 1)
+        rgb = torch.stack([m.cy * d + m.crv * f + r, m.cy * d - m.cgu * e - m.cgv * f + r, m.cy * d + m.cbu * e + r], dim=1)
+        return (rgb >> m.shift).clamp_(0, 255).to(torch.uint8)
+
+
+class YUVStereoVideo:
+    """Both views of a decoded 4:2:0 video -- what ``batch_dict["stereo_video"]`` of ``forward_batch_test`` may be instead of a tensor:
+    two ``YUVFrames`` of one size, frame count, device and colour description.  ``len()``, slicing by frame range, ``to(device)``."""
+
+    def __init__(self, left: YUVFrames, right: YUVFrames):
+        if not isinstance(left, YUVFrames) or not isinstance(right, YUVFrames):
+            raise TypeError("YUVStereoVideo: two YUVFrames expected")
+        if (left.n, left.height, left.width) != (right.n, right.height, right.width):
+            raise ValueError(f"YUVStereoVideo: the views differ: {(left.n, left.height, left.width)} and {(right.n, right.height, right.width)}")
+        if (left.standard, left.full_range) != (right.standard, right.full_range) or left.device != right.device:
+            raise ValueError("YUVStereoVideo: both views need one standard, one range and one device")
+        self.left, self.right = left, right
+        self.height, self.width = left.height, left.width
+
+    def __len__(self) -> int:
+        return self.left.n
+
+    def __getitem__(self, frames: slice) -> "YUVStereoVideo":
+        return YUVStereoVideo(self.left[frames], self.right[frames])
+
+    def to(self, device) -> "YUVStereoVideo":
+        """The selected frames' planes on ``device`` (1.5 bytes per pixel and view)."""
+        return YUVStereoVideo(self.left.to(device), self.right.to(device))
+
+
+_BORDERS = {"replicate": L.BORDER_REPLICATE, "constant": L.BORDER_CONSTANT}
+
+
+class RectifyMap:
+    """One view's undistort + rectify (+ resize) map in fixed point, as ppms_video_ingest_u8_remap / _yuv420_remap read it (the arithmetic:
+    include/ppms.h): for every pixel of the RECTIFIED frame H0 x W0, ``xy`` int16 (H0, W0, 2) holds the integer source coordinate (x0, y0), x
+    first, and ``frac`` int16 or uint16 (H0, W0) its fraction in 1/32 pixel, fx | fy << 5 -- the layout OpenCV documents for
+    ``convertMaps(..., CV_16SC2)`` (not compared with OpenCV).  ``source_size`` = (Hs, Ws) of the raw frames; ``border`` "replicate" or
+    "constant" (a tap outside the frame is ``fill``, one byte for R, G and B).  Both tensors may be row-pitched views with ONE pitch
+    (``xy.stride(0) == 2 * frac.stride(0)``): the class reads ``data_ptr()`` and ``stride()`` and never copies.  ``apply_u8`` is the definition
+    of the remap.  Not covered: computing maps from calibration data, interpolation other than bilinear."""
+
+    def __init__(self, xy: torch.Tensor, frac: torch.Tensor, source_size, border: str = "replicate", fill: int = 0, _checked: bool = False):
+        if not torch.is_tensor(xy) or xy.dtype != torch.int16 or xy.dim() != 3 or xy.shape[2] != 2:
+            raise ValueError("RectifyMap: xy must be an int16 tensor (H0, W0, 2)")
+        if not torch.is_tensor(frac) or frac.dtype not in (torch.int16, torch.uint16) or frac.dim() != 2:
+            raise ValueError("RectifyMap: frac must be an int16 or uint16 tensor (H0, W0)")
+        h0, w0 = frac.shape
+        if h0 < 1 or w0 < 1 or tuple(xy.shape[:2]) != (h0, w0):
+            raise ValueError(f"RectifyMap: xy {tuple(xy.shape)} and frac {tuple(frac.shape)} must cover one non-empty frame")
+        if xy.device != frac.device:
+            raise ValueError("RectifyMap: xy and frac must be on one device")
+        frac = frac.view(torch.int16)                               # the same 16 bits
+        if xy.stride(2) != 1 or (w0 > 1 and (xy.stride(1) != 2 or frac.stride(1) != 1)):
+            raise ValueError(f"RectifyMap: the last dimensions must be contiguous (xy strides {xy.stride()}, frac strides {frac.stride()})")
+        # a size-1 dimension's stride is arbitrary: the smallest the kernel accepts stands in for it
+        pitch = frac.stride(0) if h0 > 1 else w0
+        if pitch < w0 or (h0 > 1 and xy.stride(0) != 2 * pitch):
+            raise ValueError(f"RectifyMap: xy and frac need one row pitch >= W0 (xy strides {xy.stride()}, frac strides {frac.stride()})")
+        if xy.data_ptr() % 4 or frac.data_ptr() % 2:
+            raise ValueError("RectifyMap: xy must start at a multiple of 4 bytes, frac of 2")
+        try:
+            hs, ws = (int(v) for v in source_size)
+        except (TypeError, ValueError):
+            raise ValueError(f"RectifyMap: source_size = {source_size!r} must be (Hs, Ws)") from None
+        if not (1 <= hs <= 32768 and 1 <= ws <= 32768):
+            raise ValueError(f"RectifyMap: source_size = ({hs}, {ws}) must lie in 1..32768")
+        if border not in _BORDERS:
+            raise ValueError(f"RectifyMap: border {border!r}; one of {sorted(_BORDERS)}")
+        if not 0 <= int(fill) <= 255:
+            raise ValueError(f"RectifyMap: fill = {fill} must be a byte")
+        if not _checked and bool(((frac < 0) | (frac > 1023)).any()):      # once: copies made by ``to`` hold the same values
+            raise ValueError("RectifyMap: frac holds values above 1023 (fx | fy << 5 with fx, fy in 0..31)")
+        self.xy, self.frac, self.pitch = xy, frac, int(pitch)
+        self.height, self.width, self.source_height, self.source_width = int(h0), int(w0), hs, ws
+        self.border, self.fill = border, int(fill)
+        self._on: Dict[torch.device, "RectifyMap"] = {xy.device: self}
+
+    @classmethod
+    def from_float(cls, map_x: torch.Tensor, map_y: torch.Tensor, source_size, border: str = "replicate", fill: int = 0) -> "RectifyMap":
+        """From float source coordinates (H0, W0) per rectified pixel (what ``initUndistortRectifyMap`` gives as CV_32FC1): per coordinate
+        q = round_half_even(v * 32), saturated so that q >> 5 stays an int16; then x0 = q >> 5, fx = q & 31 (floor and remainder)."""
+        if not (torch.is_tensor(map_x) and torch.is_tensor(map_y) and map_x.is_floating_point() and map_y.is_floating_point()
+                and map_x.dim() == 2 and map_x.shape == map_y.shape):
+            raise ValueError("RectifyMap.from_float: map_x and map_y must be floating-point tensors of one shape (H0, W0)")
+        if bool(torch.isnan(map_x).any()) or bool(torch.isnan(map_y).any()):
+            raise ValueError("RectifyMap.from_float: a coordinate is NaN")
+        qx, qy = (torch.round(m.double() * 32.0).clamp(-32768 * 32, 32767 * 32 + 31).to(torch.int64) for m in (map_x, map_y))
+        xy = torch.stack([qx >> 5, qy >> 5], dim=-1).to(torch.int16)
+        frac = ((qx & 31) | ((qy & 31) << 5)).to(torch.int16)
+        return cls(xy, frac, source_size, border, fill, _checked=True)
+
+    @classmethod
+    def identity(cls, h: int, w: int, device=None) -> "RectifyMap":
+        """The map that copies an h x w frame."""
+        ys, xs = torch.meshgrid(torch.arange(h, device=device), torch.arange(w, device=device), indexing="ij")
+        return cls(torch.stack([xs, ys], dim=-1).to(torch.int16), torch.zeros((h, w), dtype=torch.int16, device=device), (h, w), _checked=True)
+
+    @property
+    def device(self) -> torch.device:
+        return self.xy.device
+
+    def to(self, device) -> "RectifyMap":
+        """This map on ``device`` (6 bytes per rectified pixel, dense); made once per device and kept."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device not in self._on:
+            there = RectifyMap(self.xy.to(device).contiguous(), self.frac.to(device).contiguous(), (self.source_height, self.source_width), self.border,
+                               self.fill, _checked=True)
+            there._on = self._on
+            self._on[device] = there
+        return self._on[device]
+
+    def view_struct(self) -> L.RemapView:
+        """The ``ppms_remap_view`` of this map."""
+        return L.RemapView(self.xy.data_ptr(), self.frac.data_ptr(), self.pitch, self.source_height, self.source_width, _BORDERS[self.border], self.fill, 0)
+
+    def apply_u8(self, rgb: torch.Tensor) -> torch.Tensor:
+        """uint8 (N, 3, Hs, Ws) -> uint8 (N, 3, H0, W0) on ``rgb``'s device: the remap of include/ppms.h in torch integer ops -- what the feature
+        means by the rectified bytes (the kernels' operands are ppms_video_ingest_u8's on them), and the path where the kernels cannot be used."""
+        hs, ws = self.source_height, self.source_width
+        if not torch.is_tensor(rgb) or rgb.dtype != torch.uint8 or rgb.dim() != 4 or tuple(rgb.shape[1:]) != (3, hs, ws):
+            raise ValueError(f"RectifyMap.apply_u8: uint8 frames (N, 3, {hs}, {ws}) expected, got "
+                             f"{tuple(rgb.shape) if torch.is_tensor(rgb) else type(rgb).__name__}")
+        m = self.to(rgb.device)
+        x0, y0 = m.xy[..., 0].to(torch.int64), m.xy[..., 1].to(torch.int64)
+        f = m.frac.to(torch.int32)
+        fx, fy = f & 31, (f >> 5) & 31
+        acc = torch.full((rgb.shape[0], 3, self.height, self.width), 512, dtype=torch.int32, device=rgb.device)
+        for dy in (0, 1):
+            for dx in (0, 1):
+                yy, xx = y0 + dy, x0 + dx
+                cy, cx = yy.clamp(0, hs - 1), xx.clamp(0, ws - 1)
+                p = rgb[:, :, cy, cx].to(torch.int32)             # clamped addresses in both modes
+                if self.border == "constant":
+                    p = torch.where((cy != yy) | (cx != xx), torch.full_like(p, self.fill), p)
+                acc += ((fx if dx else 32 - fx) * (fy if dy else 32 - fy)) * p
+        return (acc >> 10).to(torch.uint8)
+
+
+class StereoRectifier:
+    """The two views' ``RectifyMap``s of one rig -- what ``rectify=`` of ``PPMStereo.forward`` / ``forward_batch_test`` takes: one rectified size
+    (``height`` x ``width``), one source size (``source_height`` x ``source_width``), one device.  ``to(device)`` is kept per device."""
+
+    def __init__(self, left: RectifyMap, right: RectifyMap):
+        if not isinstance(left, RectifyMap) or not isinstance(right, RectifyMap):
+            raise TypeError("StereoRectifier: two RectifyMaps expected")
+        if (left.height, left.width) != (right.height, right.width):
+            raise ValueError(f"StereoRectifier: the rectified sizes differ: {(left.height, left.width)} and {(right.height, right.width)}")
+        if (left.source_height, left.source_width) != (right.source_height, right.source_width):
+            raise ValueError(f"StereoRectifier: the source sizes differ: {(left.source_height, left.source_width)} and "
+                             f"{(right.source_height, right.source_width)}")
+        if left.device != right.device:
+            raise ValueError("StereoRectifier: both maps must be on one device")
+        self.left, self.right = left, right
+        self.height, self.width = left.height, left.width
+        self.source_height, self.source_width = left.source_height, left.source_width
+
+    @property
+    def device(self) -> torch.device:
+        return self.left.device
+
+    def to(self, device) -> "StereoRectifier":
+        left, right = self.left.to(device), self.right.to(device)
+        return self if left is self.left and right is self.right else StereoRectifier(left, right)
+
+    def tensors(self):
+        """The four map tensors (for record_stream)."""
+        return self.left.xy, self.left.frac, self.right.xy, self.right.frac
+
+    def apply_u8(self, left: torch.Tensor, right: torch.Tensor):
+        return self.left.apply_u8(left), self.right.apply_u8(right)
+
+    def check_source(self, who: str, h: int, w: int) -> None:
+        if (int(h), int(w)) != (self.source_height, self.source_width):
+            raise ValueError(f"{who}: the frames are {int(h)} x {int(w)}, the rectification maps were made for {self.source_height} x {self.source_width}")
+
+
+class _FloatViews:
+    """The source of a float video: ``left`` / ``right`` (n, 3, H0, W0) as the reference takes them; torch pads and normalises them.
+    A source -- this class and the two below -- is what the model reads its n frames per view (b clips of n / b) of ``size`` = (H0, W0) from."""
+
+    def __init__(self, left: torch.Tensor, right: torch.Tensor, b: int = 1):
+        self.left, self.right, self.device = left, right, left.device
+        self.n, self.b, self.size = int(left.shape[0]), int(b), (int(left.shape[-2]), int(left.shape[-1]))
+
+    def float_views(self):
+        """The two float32 (n, 3, H0, W0) videos for encoder callables of the caller."""
+        return self.left, self.right
+
+
+class _ByteSource:
+    """Decoded bytes of both views, optionally the RAW frames of a ``StereoRectifier`` (``size`` is then its rectified size): with this package's
+    encoders ONE launch (``ingest``) rectifies, pads, normalises and lays out both encoders' first-layer operands; ``float_views`` is the path
+    of other encoder callables.  The entry point and its ``_remap`` twin differ by the two maps in front of n: chosen here, once."""
+
+    def __init__(self, entry: str, n: int, frame_size, device, rectify: Optional[StereoRectifier], b: int = 1):
+        self.n, self.b, self.device, self.rectify = int(n), int(b), device, rectify
+        if rectify is None:
+            self.size, self._entry, self._maps, self._map_tensors = (int(frame_size[0]), int(frame_size[1])), entry, (), ()
+        else:
+            self.size, self._entry = (rectify.height, rectify.width), entry + "_remap"
+            self._maps, self._map_tensors = (rectify.left.view_struct(), rectify.right.view_struct()), rectify.tensors()
+
+    def ingest(self, dst_fnet: L.SP, dst_cnet: L.SP, pad_left: int, pad_top: int, h: int, w: int) -> None:
+        """One launch on the current stream: both encoders' first-layer operands of the n frames, ``pad_left`` / ``pad_top`` in front, h x w."""
+        L.check(getattr(L.load(), self._entry)(*self._frames(), *self._maps, self.n, *self.size, pad_left, pad_top, h, w,
+                                               byte_lut(self.device).data_ptr(), dst_fnet, dst_cnet, L.stream_ptr()))
+
+    def held(self):
+        """The tensors the launch reads (for record_stream)."""
+        return self._planes() + self._map_tensors
+
+
+class _RGBBytes(_ByteSource):
+    """Planar RGB bytes as ppms_video_ingest_u8 reads them: ``left`` / ``right`` uint8 (n, 3, Hs, Ws) with dense frames ``frame_stride`` bytes apart
+    (two tensors, or the two views inside one window's block)."""
+
+    def __init__(self, left: torch.Tensor, right: torch.Tensor, frame_stride: int, rectify: Optional[StereoRectifier] = None, b: int = 1):
+        super().__init__("ppms_video_ingest_u8", left.shape[0], left.shape[-2:], left.device, rectify, b)
+        self.left, self.right, self.frame_stride = left, right, int(frame_stride)
+
+    def _frames(self):
+        # (kept as it was: without a rectifier, two videos of ``forward`` are compared here only -- encoder callables of the caller get what they get)
+        if self.right.shape != self.left.shape or self.left.shape[1] != 3:
+            raise ValueError(f"PPMStereo.forward: two uint8 videos of one shape (b, T, 3, H, W) expected, got frames {tuple(self.left.shape)} and {tuple(self.right.shape)}")
+        return self.left.data_ptr(), self.right.data_ptr(), self.frame_stride
+
+    def _planes(self):
+        return self.left, self.right
+
+    def float_views(self):
+        left, right = (self.left, self.right) if self.rectify is None else self.rectify.apply_u8(self.left, self.right)
+        return left.float(), right.float()
+
+
+class _YUVPlanes(_ByteSource):
+    """A YUVStereoVideo: ppms_video_ingest_yuv420 converts the planes as the decoder left them."""
+
+    def __init__(self, video: YUVStereoVideo, rectify: Optional[StereoRectifier] = None):
+        super().__init__("ppms_video_ingest_yuv420", len(video), (video.height, video.width), video.left.device, rectify)
+        self.video = video
+
+    def _frames(self):
+        v = self.video
+        return v.left.view_struct(), v.right.view_struct(), v.left.matrix()      # host structs: read before the call returns
+
+    def _planes(self):
+        v = self.video
+        return v.left.y, v.left.u, v.left.v, v.right.y, v.right.u, v.right.v
+
+    def float_views(self):
+        rgb = self.video.left.to_rgb_u8(), self.video.right.to_rgb_u8()
+        left, right = rgb if self.rectify is None else self.rectify.apply_u8(*rgb)
+        return left.float(), right.float()
+
+
+def _checked_rectifier(who: str, rectify, device, h: int, w: int) -> StereoRectifier:
+    """``rectify`` for raw frames h x w on ``device`` (host frames are only measured: the maps stay where they are)."""
+    rectify.check_source(who, h, w)
+    return rectify.to(device) if device.type == "cuda" else rectify
+
+
+def stereo_source(who: str, left, right=None, rectify: Optional[StereoRectifier] = None):
+    """The source of two views -- float or uint8 tensors (b, T, 3, H, W), or two ``YUVFrames`` -- or, with ``right`` None, of a window ``left`` of
+    a video: a tensor (T, 2, 3, H, W) or a ``YUVStereoVideo``.  Every argument check of the front doors is made here, under the name ``who``,
+    and touches no device: rectify= reads decoded bytes (TypeError for float frames), of its source size (ValueError), b = 1."""
+    if rectify is not None and not isinstance(rectify, StereoRectifier):
+        raise TypeError(f"{who}: rectify must be a StereoRectifier, got {type(rectify).__name__}")
+    if isinstance(left, YUVFrames) or isinstance(right, YUVFrames):
+        if not (isinstance(left, YUVFrames) and isinstance(right, YUVFrames)):
+            raise TypeError(f"{who}: image1 is {type(left).__name__} and image2 is {type(right).__name__}; both views must be YUVFrames or both tensors")
+        left, right = YUVStereoVideo(left, right), None
+    if isinstance(left, YUVStereoVideo):
+        if rectify is not None:
+            rectify = _checked_rectifier(who, rectify, left.left.device, left.height, left.width)
+        return _YUVPlanes(left, rectify)
+    views = (left,) if right is None else (left, right)
+    for v in views:
+        if not torch.is_tensor(v):
+            raise TypeError(f"{who}: uint8 or float tensors, YUVFrames or a YUVStereoVideo expected, got {type(v).__name__}")
+        if rectify is not None and v.dtype != torch.uint8:
+            raise TypeError(f"{who}: rectify= reads decoded bytes (uint8 frames or YUVFrames), got {v.dtype}; rectify float images before the call")
+    if len({v.dtype == torch.uint8 for v in views}) > 1:
+        raise TypeError(f"{who}: image1 is {left.dtype} and image2 is {right.dtype}; both views must be uint8 or both floating point")
+    if left.dim() != 5:
+        raise ValueError(f"{who}: a video has 5 dimensions, got {tuple(left.shape)}")
+    if left.dtype != torch.uint8:
+        return _FloatViews(left[:, 0], left[:, 1]) if right is None else _FloatViews(left.flatten(0, 1), right.flatten(0, 1), left.shape[0])
+    if rectify is not None:
+        for v in views:
+            rectify = _checked_rectifier(who, rectify, v.device, v.shape[-2], v.shape[-1])
+    h, w = left.shape[-2:]
+    if right is None:
+        if left.shape[1] != 2 or left.shape[2] != 3:
+            raise ValueError(f"{who}: a uint8 stereo_video is (N, 2, 3, H, W), got {tuple(left.shape)}")
+        left = left.contiguous()                                 # one block: both views are read out of it, 6 * h * w bytes from frame to frame
+        return _RGBBytes(left[:, 0], left[:, 1], 6 * h * w, rectify)
+    if rectify is not None:
+        if right.shape != left.shape or left.shape[2] != 3:
+            raise ValueError(f"{who}: two uint8 videos of one shape (1, T, 3, Hs, Ws) expected, got {tuple(left.shape)} and {tuple(right.shape)}")
+        if left.shape[0] != 1:
+            raise NotImplementedError(f"{who}: rectify= serves b = 1")
+    return _RGBBytes(left.contiguous().flatten(0, 1), right.contiguous().flatten(0, 1), 3 * h * w, rectify, left.shape[0])
+
+
+_PLANE_FORMATS = {"f32": (L.FMT_F32, torch.float32), "f16": (L.FMT_F16, torch.float16), "u16": (L.FMT_U16, torch.uint16), "u8": (L.FMT_U8, torch.uint8)}
+
+
+class OutputSpec:
+    """What ``forward(output=...)`` / ``forward_batch_test(output=...)`` hand back instead of float32 disparity: up to three planes that ONE
+    kernel (ppms_disparity_egress, include/ppms.h) writes from the 1/4 scale's last iteration -- crop, kept frames, ``.abs()``, the 4x
+    upsampling of the uncertainty and the conversion in one pass.
+      disparity    "f32" | "f16" | "u16": d = |disparity| in pixels; "u16" = min(65535, rint(d * disp_scale)) (KITTI: disp_scale = 256), NaN -> 0
+      depth        None | "f32" | "f16" | "u16": Z = fb / d with fb = focal_px * baseline (one fp32 product); "u16" = min(65535, rint(Z * depth_scale))
+                   (baseline in metres and depth_scale = 1000: millimetres).  A pixel with d < min_disp or d = NaN is invalid: +inf in the float
+                   formats, 0 in "u16".  (min_disp = 0 leaves only NaN invalid: d = 0 then gives +inf / 65535.)
+      uncertainty  "f32" | "u8" | None: u = |uncertainty| in [0, 1]; "u8" = min(255, rint(u * 255)), NaN -> 0
+    Every step is one fp32 operation rounded to nearest even; ``reference`` restates them in torch and is the definition the kernel is
+    tested against, bit for bit."""
+
+    def __init__(self, disparity: str = "f32", depth: Optional[str] = None, uncertainty: Optional[str] = "f32", disp_scale: float = 256.0,
+                 focal_px: Optional[float] = None, baseline: Optional[float] = None, depth_scale: float = 1000.0, min_disp: float = 2.0 ** -8):
+        if disparity not in ("f32", "f16", "u16"):
+            raise ValueError(f"OutputSpec: disparity = {disparity!r}; one of 'f32', 'f16', 'u16'")
+        if depth not in (None, "f32", "f16", "u16"):
+            raise ValueError(f"OutputSpec: depth = {depth!r}; None or one of 'f32', 'f16', 'u16'")
+        if uncertainty not in (None, "f32", "u8"):
+            raise ValueError(f"OutputSpec: uncertainty = {uncertainty!r}; None, 'f32' or 'u8'")
+        f32 = lambda x: float(torch.tensor(float(x), dtype=torch.float32))
+        self.disparity, self.depth, self.uncertainty = disparity, depth, uncertainty
+        self.disp_scale, self.depth_scale, self.min_disp = f32(disp_scale), f32(depth_scale), f32(min_disp)
+        if not (0.0 < self.disp_scale < math.inf):
+            raise ValueError(f"OutputSpec: disp_scale = {disp_scale} must be positive and finite")
+        self.focal_px, self.baseline, self.fb = focal_px, baseline, 0.0
+        if depth is not None:
+            if focal_px is None or baseline is None:
+                raise ValueError("OutputSpec: a depth plane needs focal_px (focal length in pixels) and baseline")
+            self.fb = float(torch.tensor(float(focal_px), dtype=torch.float32) * torch.tensor(float(baseline), dtype=torch.float32))
+            if not (0.0 < self.fb < math.inf):
+                raise ValueError(f"OutputSpec: focal_px * baseline = {self.fb} must be positive and finite")
+            if not (0.0 < self.depth_scale < math.inf):
+                raise ValueError(f"OutputSpec: depth_scale = {depth_scale} must be positive and finite")
+            if not math.isfinite(self.min_disp):
+                raise ValueError(f"OutputSpec: min_disp = {min_disp} must be finite")
+
+    def formats(self) -> Dict[str, str]:
+        """{result key: format} of the requested planes, in the order disparity, depth, uncertainties."""
+        named = (("disparity", self.disparity), ("depth", self.depth), ("uncertainties", self.uncertainty))
+        return {k: f for k, f in named if f is not None}
+
+    def empty(self, n: int, h0: int, w0: int, device, pin_memory: bool = False) -> Dict[str, torch.Tensor]:
+        """Dense (n, 1, h0, w0) tensors of the requested planes' dtypes."""
+        return {k: torch.empty(n, 1, h0, w0, dtype=_PLANE_FORMATS[f][1], device=device, pin_memory=pin_memory) for k, f in self.formats().items()}
+
+    def struct(self, planes: Dict[str, torch.Tensor]) -> L.Egress:
+        """The ``ppms_egress`` that writes into ``planes`` (dense (n, 1, h0, w0) device tensors from ``empty``)."""
+        def plane(key):
+            t = planes.get(key)
+            if t is None:
+                return L.EgressPlane(None, 0, 0, 0, 0)
+            es = t.element_size()
+            return L.EgressPlane(t.data_ptr(), t.stride(0) * es, t.stride(2) * es, _PLANE_FORMATS[self.formats()[key]][0], 0)
+        return L.Egress(plane("disparity"), plane("depth"), plane("uncertainties"), self.disp_scale, self.fb, self.depth_scale, self.min_disp)
+
+    def reference(self, d: torch.Tensor, u: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """The arithmetic of ppms_disparity_egress in plain torch, on CPU or device tensors of any shape: d = a float32 (signed) disparity,
+        u = a float32 uncertainty at the same resolution -> the requested planes under forward_batch_test's keys."""
+        const = lambda x: torch.full((), x, dtype=torch.float32, device=d.device)
+
+        def quant(v, scale, top, fmt):                       # min(top, rint(v * scale)), NaN -> 0: one fp32 product, ties to even
+            r = torch.round(v * const(scale))
+            r = torch.where(torch.isnan(r), torch.zeros_like(r), r).clamp(max=top)
+            return r.to(torch.int32).to(_PLANE_FORMATS[fmt][1])
+
+        d = d.float().abs()
+        out = {"disparity": d if self.disparity == "f32" else d.to(torch.float16) if self.disparity == "f16" else quant(d, self.disp_scale, 65535.0, "u16")}
+        if self.depth is not None:
+            valid = d >= const(self.min_disp)                # (false for NaN)
+            z = torch.where(valid, const(self.fb) / d, const(math.inf))          # tensor / tensor: a correctly rounded fp32 division
+            if self.depth == "u16":
+                out["depth"] = torch.where(valid, quant(z, self.depth_scale, 65535.0, "u16").to(torch.int32), 0).to(torch.uint16)
+            else:
+                out["depth"] = z if self.depth == "f32" else z.to(torch.float16)
+        if self.uncertainty is not None:
+            if u is None:
+                raise ValueError("OutputSpec.reference: an uncertainty plane is requested and no uncertainty was given")
+            u = u.float().abs()
+            out["uncertainties"] = u if self.uncertainty == "f32" else quant(u, 255.0, 255.0, "u8")
+        return out
+
+
+class _EgressCall:
+    """One egress launch as ``cascade`` makes it: the spec, the crop (pad_left, pad_top, H0, W0) inside the padded frame (None: the whole
+    frame) and the window-local frame range (None: all frames)."""
+
+    def __init__(self, spec: OutputSpec, crop=None, frames=None):
+        if not isinstance(spec, OutputSpec):
+            raise TypeError(f"output must be an OutputSpec, got {type(spec).__name__}")
+        self.spec, self.crop, self.frames = spec, (None if crop is None else tuple(int(x) for x in crop)), (None if frames is None else tuple(int(x) for x in frames))
+
+    def launch(self, eng) -> Dict[str, torch.Tensor]:
+        """Allocates the planes on the current stream and enqueues the launch there, behind the engine's last iteration."""
+        pad_left, pad_top, h0, w0 = (0, 0, 4 * eng.h, 4 * eng.w) if self.crop is None else self.crop
+        f0, f1 = (0, eng.T) if self.frames is None else self.frames
+        if not 0 <= f0 < f1 <= eng.T:
+            raise ValueError(f"output: frames = {(f0, f1)} is no range inside the window's {eng.T} frames")
+        planes = self.spec.empty(f1 - f0, h0, w0, eng.FLOW_OUT.device)
+        eng.egress(self.spec.struct(planes), f0, f1 - f0, pad_left, pad_top, h0, w0)
+        return planes
+
+
+def window_plan(num_ims: int, kernel_size: int = 20):
+    """Sliding-window schedule of PPMStereo.forward_batch_test (ppmstereo.py:242-310): list of
+    (start, stop, keep_from, keep_to) with keep_* window-local.  Trailing windows whose output the reference
+    discards (:296) are not scheduled at all."""
+    stride = kernel_size // 2
+    if kernel_size > num_ims:
+        return [(0, num_ims, 0, num_ims)]
+    plan = []
+    for i in range(0, num_ims, stride):
+        n = min(i + kernel_size, num_ims) - i
+        if plan and n >= stride:
+            plan.append((i, i + n, stride // 2, n if n < kernel_size else n + (-stride // 2)))
+        elif not plan:
+            plan.append((i, i + n, 0, n + (-stride // 2)))
+    return plan
+
+
+def egress_plan(plan):
+    """``window_plan`` with the destination of every window's kept frames: (start, stop, keep_from, keep_to, dst_from, dst_to) -- the egress
+    launch of the window writes its frames [keep_from, keep_to), and they are frames [dst_from, dst_to) of the video."""
+    return [(start, stop, keep_from, keep_to, start + keep_from, start + keep_to) for start, stop, keep_from, keep_to in plan]
+
+
+def shard_windows(plan, rank: int, world: int):
+    """Window-level sharding across GPUs (SURVEY.md section 8e level 1): windows are independent units; rank r takes
+    windows r, r+world, ...  No data-path collective; the kept disparities are gathered once at the end."""
+    return [w for i, w in enumerate(plan) if i % world == rank]

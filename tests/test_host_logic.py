@@ -457,3 +457,52 @@ def test_drop_in_constructor_keeps_the_reference_defaults():
         PPMStereo()
     assert PPMStereo.WRAPPER_CONFIG == dict(mixed_precision=True, num_frames=5, attention_type="self_stereo_temporal_update_time_update_space",
                                             use_3d_update_block=True, different_update_blocks=True)
+
+
+def test_stereo_source_refusals_and_measures():
+    """The one factory behind ``forward`` / ``forward_batch_test`` (ppmstereo_amd/video.py) on CPU tensors -- no GPU, no library: the exception type
+    of what it refuses; n = frames per view and size = what the model sees (with a rectifier: its rectified size) of every kind it accepts."""
+    from ppmstereo_amd.video import RectifyMap, StereoRectifier, YUVFrames, YUVStereoVideo, stereo_source
+    u8 = lambda *s: torch.arange(math.prod(s), dtype=torch.int64).remainder(251).to(torch.uint8).reshape(s)
+    f32 = lambda *s: u8(*s).float()
+    yuv = lambda n, h, w: YUVFrames.i420(u8(n, h, w), u8(n, (h + 1) // 2, (w + 1) // 2), u8(n, (h + 1) // 2, (w + 1) // 2))
+    ys, xs = torch.meshgrid(torch.arange(20, dtype=torch.float32), torch.arange(36, dtype=torch.float32), indexing="ij")
+    maps = [RectifyMap.from_float(xs + 2.25 + i, ys + 1.5, (24, 40)) for i in range(2)]          # raw 24 x 40 -> rectified 20 x 36
+    r = StereoRectifier(*maps)
+    raw, rect = (1, 3, 3, 24, 40), (1, 3, 3, 20, 36)
+    refused = [
+        (u8(*raw), f32(*raw), None, TypeError), (f32(*raw), u8(*raw), None, TypeError),                          # one view uint8, the other float
+        (yuv(3, 24, 40), u8(*raw), None, TypeError), (u8(*raw), yuv(3, 24, 40), None, TypeError),                # one view YUVFrames, the other a tensor
+        (f32(*raw), f32(*raw), r, TypeError), (u8(*raw), f32(*raw), r, TypeError),                               # float views with a rectifier
+        (u8(*rect), u8(*rect), r, ValueError), (yuv(3, 20, 36), yuv(3, 20, 36), r, ValueError),                  # not the rectifier's source size
+        (u8(2, 3, 3, 24, 40), u8(2, 3, 3, 24, 40), r, NotImplementedError),                                      # b = 2 with a rectifier
+        (u8(*raw), u8(*raw), (maps[0], maps[1]), TypeError), (u8(*raw), u8(*raw), maps[0], TypeError),           # no StereoRectifier
+        (yuv(3, 24, 40), yuv(2, 24, 40), None, ValueError), (u8(3, 3, 24, 40), u8(3, 3, 24, 40), None, ValueError),
+        (f32(3, 2, 3, 24, 40), None, r, TypeError), (u8(3, 2, 3, 20, 36), None, r, ValueError),                  # windows of a video
+        (YUVStereoVideo(yuv(3, 20, 36), yuv(3, 20, 36)), None, r, ValueError), (u8(3, 3, 3, 24, 40), None, None, ValueError),
+        (u8(3, 2, 3, 24, 40), None, maps[0], TypeError), ([u8(2, 3, 24, 40)] * 3, None, None, TypeError),
+    ]
+    for left, right, rectify, exc in refused:
+        with pytest.raises(exc):
+            stereo_source("test", left, right, rectify)
+    video = YUVStereoVideo(yuv(3, 24, 40), yuv(3, 24, 40))
+    accepted = [
+        (f32(2, 3, 3, 24, 40), f32(2, 3, 3, 24, 40), None, 6, 2, (24, 40)), (u8(2, 3, 3, 24, 40), u8(2, 3, 3, 24, 40), None, 6, 2, (24, 40)),
+        (u8(*raw), u8(*raw), r, 3, 1, (20, 36)), (video.left, video.right, None, 3, 1, (24, 40)), (video.left, video.right, r, 3, 1, (20, 36)),
+        (f32(3, 2, 3, 24, 40), None, None, 3, 1, (24, 40)), (u8(3, 2, 3, 24, 40), None, None, 3, 1, (24, 40)), (u8(3, 2, 3, 24, 40), None, r, 3, 1, (20, 36)),
+        (video, None, None, 3, 1, (24, 40)), (video, None, r, 3, 1, (20, 36)), (video[:1], None, r, 1, 1, (20, 36)),
+    ]
+    for left, right, rectify, n, b, size in accepted:
+        s = stereo_source("test", left, right, rectify)
+        assert (s.n, s.b, tuple(s.size)) == (n, b, size)
+        views = s.float_views()
+        assert all(v.dtype == torch.float32 and tuple(v.shape) == (n, 3, *size) for v in views)
+    # what encoder callables of the caller get: to_rgb_u8, then apply_u8, then .float()
+    got = stereo_source("test", video, None, r).float_views()
+    want = r.apply_u8(video.left.to_rgb_u8(), video.right.to_rgb_u8())
+    assert torch.equal(got[0], want[0].float()) and torch.equal(got[1], want[1].float()) and not torch.equal(got[0], got[1])
+    block = u8(3, 2, 3, 24, 40)
+    got = stereo_source("test", block, None, r).float_views()
+    assert torch.equal(got[1], maps[1].apply_u8(block[:, 1]).float())
+    got = stereo_source("test", block[None, :, 0], block[None, :, 1]).float_views()
+    assert torch.equal(got[0], block[:, 0].float()) and torch.equal(got[1], block[:, 1].float())
