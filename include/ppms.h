@@ -397,6 +397,12 @@ int ppms_attn_prep_q(const float* q, int ld, const float* pe, void* qb, int T, i
 /* K' = bf16(K_j * s_hat_ij + PE_j) for the picked frames (ppmstereo.py:541,547); kb: bf16 [T][ksel][n][128] */
 int ppms_attn_prep_k(const float* key, int ld, const float* pe, const int32_t* sel, const float* shat, void* kb, int T, int ksel,
                      int n, void* stream);
+/* ppms_qam_select + ppms_attn_prep_k as ONE launch, for a window held by one device (sel / shat / kb cover all T clips; ksel = min(5, T)):
+ * the same SEL, SHAT, SCORE, counter and K', bit for bit.  The usage counter is a ping-pong pair: strive_in is read (by every workgroup),
+ * strive_out -- another fp32 [T][T] table -- receives all T x T new values; the caller swaps the two after the call.  Every fp32 key is
+ * read once however many clips picked its frame.  score is optional. */
+int ppms_pick_prep_k(const float* sim, const float* strive_in, float* strive_out, const float* conf_partial, int nblk, int HW, int32_t* sel,
+                     float* shat, float* score, const float* key, int ld, const float* pe, void* kb, int T, int n, void* stream);
 enum { PPMS_ATTN_P_BF16 = 0, PPMS_ATTN_P_FP16 = 1 };   /* ppms_mem_attn: p_format */
 /* flash_attn_func call of ppmstereo.py:550 for all T clips + the aggregation of :552:
  * hid = bf16(softmax(Q K'^T * scale) V); mfg = mf + beta * hid.

@@ -215,6 +215,7 @@ class ScaleEngine:
         self.UNC, self.PART = f32(P), f32(T, self.nblk)
         self.PARTG = self.PART if shard is None else f32(Tg, self.nblk)
         self.SIM, self.STRIVE, self.SCORE = f32(Tg, Tg), f32(Tg, Tg), f32(Tg, Tg)
+        self._STRIVE_next = f32(Tg, Tg)     # the merged pick + key modulation launch writes the new usage counter here; then the two swap
         self.SEL = torch.zeros(Tg, 5, dtype=torch.int32, device=device)
         self.SHAT = f32(Tg, 5)
         self.cells = max(1, (h // 4) * (w // 4))
@@ -529,7 +530,9 @@ class ScaleEngine:
         L.check(self.lib.ppms_qam_select(self.SIM.data_ptr(), self.STRIVE.data_ptr(), self.PARTG.data_ptr(), self.nblk, self.n, self.SEL.data_ptr(),
                                          self.SHAT.data_ptr(), self.SCORE.data_ptr(), self.Tg, self._s()))
 
-    def attend(self, out_bf16: Optional[torch.Tensor] = None):
+    def attend(self, out_bf16: Optional[torch.Tensor] = None, with_pick: bool = False):
+        """with_pick (unsharded engines, iterate()): the key modulation launch also does what pick() does -- one launch, the same SEL, SHAT,
+        SCORE, usage counter and K' -- so pick() is not called in front of it."""
         s = self._s()
         sel = self.SEL.data_ptr() + self.f0 * 5 * 4                   # rows of this engine's clips
         shat = self.SHAT.data_ptr() + self.f0 * 5 * 4
@@ -537,7 +540,7 @@ class ScaleEngine:
             key, key_ld = self.QK.data_ptr() + 128 * 4, 256
         else:
             key, key_ld = self.KG.data_ptr(), 128                      # (the values of every frame arrived with the confidences: pick())
-        self._prep_k_args = (key, key_ld, sel, shat)
+        self._prep_k_args = (key, key_ld, sel, shat, with_pick)
         self.hbm["attn_prep_k"]()
         ev = None
         if KERNEL_TIMING["on"] and self._ev is not None and self._ev_i < len(self._ev):
@@ -706,7 +709,15 @@ class ScaleEngine:
         disparity_egress(self.FLOW_OUT, self.UNC.view(self.T, self.h, self.w), out, frame0, n_frames, pad_left, pad_top, h0, w0)
 
     def _prep_k(self):
-        key, key_ld, sel, shat = self._prep_k_args
+        key, key_ld, sel, shat, with_pick = self._prep_k_args
+        if with_pick:
+            if self.shard is not None:
+                raise RuntimeError("ScaleEngine: the merged pick + key modulation launch serves unsharded engines only")
+            L.check(self.lib.ppms_pick_prep_k(self.SIM.data_ptr(), self.STRIVE.data_ptr(), self._STRIVE_next.data_ptr(), self.PART.data_ptr(), self.nblk,
+                                              self.n, self.SEL.data_ptr(), self.SHAT.data_ptr(), self.SCORE.data_ptr(), key, key_ld, self.PE.data_ptr(),
+                                              self.KB.data_ptr(), self.T, self.n, self._s()))
+            self.STRIVE, self._STRIVE_next = self._STRIVE_next, self.STRIVE        # STRIVE stays "the current counter"
+            return
         L.check(self.lib.ppms_attn_prep_k(key, key_ld, self.PE.data_ptr(), sel, shat, self.KB.data_ptr(), self.T, self.ksel, self.n, self._s()))
 
     def _upsample(self):
@@ -725,8 +736,11 @@ class ScaleEngine:
         self.lookup()
         self.motion_and_value()
         self.uncertainty()
-        self.pick()
-        self.attend()
+        if self.shard is None:
+            self.attend(with_pick=True)           # QAM pick inside the key modulation launch
+        else:
+            self.pick()
+            self.attend()
         self.update(need_mask=need_up)
         return self.upsample() if need_up else None
 
