@@ -197,7 +197,11 @@ int ppms_struct_sizes(int* sp, int* epilogue, int* conv);
 
 /* ---------------------------------------------------------------- small ops of the update block */
 /* depthwise k x k conv + residual GELU of PCBlock4_Deep_nopool_res (ppmtereo_update.py:1026-1027):
- * y = gelu(x + dw(x) + b) on an SP tensor; w: fp32 [C][k*k], b: fp32 [C]; k in {1,7}. */
+ * y = gelu(x + dw(x) + b) on an SP tensor; w: fp32 [C][k*k], b: fp32 [C]; k in {1,7}.  x, y: views of the same c <= 64 channels, c and both
+ * ld multiples of 8; only the c channels of y are written.  The kernel moves 8 channels of a plane and 4 floats of the bias per load, so
+ * the four plane pointers and b must be 16-byte aligned (a view of a 16-byte aligned tensor that starts at a multiple of 8 channels is): a
+ * view starting at channel 4, or a bias pointer one float into its allocation, is refused with PPMS_EINVAL before any launch -- as are a
+ * NULL w or b and a map with BT, H or W <= 0. */
 int ppms_dwconv_gelu(ppms_sp x, ppms_sp y, const float* w, const float* b, int k, int BT, int H, int W, void* stream);
 /* im2col of the 2-channel flow for convf1 (7x7, ppmtereo_update.py:452,477): patch[pixel][tap*2+c], 98 -> 128 zero padded */
 int ppms_flow_patch7(const float* flow_nhwc, ppms_sp patch, int BT, int H, int W, void* stream);
@@ -444,14 +448,19 @@ int ppms_attn_redo_accumulate(const void* split_ws, int T, int ksel, int n, int 
 /* Fused chain of up to three per-pixel (1x1, <= 64 input channels) layers with GELU, optional residual from the chain
  * input and optional depthwise-1x1 post step: the ffn1 / pw / ffn2 parts of PCBlock4_Deep_nopool_res
  * (ppmtereo_update.py:1024-1030).  dev_params: device copy of the parameter block built by the host
- * (ppmstereo_amd/engine.py: PwChain; layout checked with ppms_pwchain_param_bytes). */
+ * (ppmstereo_amd/engine.py: PwChain; layout checked with ppms_pwchain_param_bytes).  The input view is read 64 channels wide (channels
+ * beyond a layer's real inputs meet zero weights: they must hold finite values).  Of the last layer only channels [0, n_valid) of the
+ * `pixels` rows are stored: channels >= n_valid of the output view (its padding up to M) and rows >= pixels are NOT written -- they keep
+ * what the buffer held (a caller that feeds them to a convolution zeroes the buffer once).  Maps of <= 16 384 pixels run a 32-pixel-tile
+ * kernel, larger ones a 128-pixel-tile kernel: the same bits per pixel either way. */
 int ppms_pwchain(const void* dev_params, int64_t pixels, void* stream);
 int ppms_pwchain_param_bytes(void);
 
 /* ---------------------------------------------------------------- update_block16 time / space attention pieces */
 /* TimeAttnBlock core (ppmtereo_update.py:603-606 with Attention.forward :409-417): per pixel, tokens = its T frames;
- * y = LayerNorm(x); out_t = sum_t2 softmax(y_t . y_t2 / sqrt(48)) y_t2 per head (q = k = v = y).  x, out: SP, 384 channels
- * (update_block16) or 256 (the SST block's TimeAttnBlock, ppmstereo.py:392-393). */
+ * y = LayerNorm(x); out_t = sum_t2 softmax(y_t . y_t2 / sqrt(C / 8)) y_t2 per head (q = k = v = y; 8 heads).  x, out: SP, 384 channels
+ * (update_block16) or 256 (the SST block's TimeAttnBlock, ppmstereo.py:392-393).  A pixel's T normalised frames are held in T * C * 4 bytes of
+ * LDS, at most 64 KiB: T <= 42 at C = 384, T <= 64 at C = 256; a larger T is refused with PPMS_EINVAL before any launch. */
 int ppms_time_attn(ppms_sp x, const float* ln_w, const float* ln_b, ppms_sp out, int T, int n, int heads, void* stream);
 /* out = resid + LayerNorm(x) (resid.hi == NULL: no residual); x fp32 [pixel][ld]; C = 384 or 256 (attention.py:186-190) */
 int ppms_layernorm(const float* x, int ld, const float* w, const float* b, ppms_sp resid, ppms_sp out, int64_t pixels, int C, void* stream);

@@ -101,6 +101,9 @@ extern "C" int ppms_time_attn(ppms_sp x, const float* ln_w, const float* ln_b, p
     PPMS_REQUIRE((x.c == 384 || x.c == 256) && out.c == x.c && heads == 8,
                  "time_attn: C = 384 (update_block16) or 256 (SST block), 8 heads expected, got C=%d heads=%d", x.c, heads);
     PPMS_REQUIRE(T >= 1 && T <= 64 && n >= 1, "time_attn: bad T=%d n=%d", T, n);
+    // the T normalised frames of a pixel sit in T * C * 4 bytes of dynamic LDS; the kernel's limit is the default 64 KiB
+    PPMS_REQUIRE((size_t)T * x.c * 4 <= 65536, "time_attn: T=%d frames of C=%d channels need %d bytes of LDS, more than 64 KiB (T <= %d)", T, x.c,
+                 T * x.c * 4, 65536 / (x.c * 4));
     // the kernel reads a lane's channels as 32-bit pairs: rows must start on 4-byte boundaries
     PPMS_REQUIRE(x.ld % 2 == 0 && out.ld % 2 == 0 && ((uintptr_t)x.hi & 3) == 0 && ((uintptr_t)x.lo & 3) == 0,
                  "time_attn: x must be a 4-byte aligned SP view with an even row stride (ld=%d)", x.ld);

@@ -1,6 +1,6 @@
 // One tap of CorrBlock1D.__call__ (/root/reference/models/core/corr.py:74-94 with bilinear_sampler :8-21): linear interpolation of a
-// pyramid row at (kk - 4) + xs / 2^lvl, zero padding, align_corners=True -- shared by the lookup kernels (corr.hip) and the fused
-// correlation-encoder chain that looks its taps up itself (pwchain.hip).
+// pyramid row at (kk - 4) + xs / 2^lvl, zero padding, align_corners=True -- shared by the two lookup kernels of corr.hip (SP and NCHW
+// output).
 #pragma once
 
 __device__ __forceinline__ float lookup_tap(const float* __restrict__ L, int Wl, float xs, int lvl, int kk) {

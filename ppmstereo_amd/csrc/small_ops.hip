@@ -134,6 +134,11 @@ extern "C" int ppms_dwconv_gelu(ppms_sp x, ppms_sp y, const float* w, const floa
     PPMS_REQUIRE(k == 1 || k == 7, "dwconv_gelu: k=%d (only 1 and 7)", k);
     PPMS_REQUIRE(x.hi && x.lo && y.hi && y.lo && x.c == y.c && x.c > 0 && x.c <= 64 && x.c % 8 == 0 && x.ld % 8 == 0 && y.ld % 8 == 0,
                  "dwconv_gelu: views must have c <= 64 and c, ld multiples of 8");
+    // the kernel loads the planes 16 bytes (8 channels) and the bias 16 bytes (4 floats) at a time
+    PPMS_REQUIRE((((uintptr_t)x.hi | (uintptr_t)x.lo | (uintptr_t)y.hi | (uintptr_t)y.lo) & 15) == 0,
+                 "dwconv_gelu: the planes of x and y must be 16-byte aligned (a view starts at a multiple of 8 channels)");
+    PPMS_REQUIRE(w != nullptr && b != nullptr && ((uintptr_t)b & 15) == 0, "dwconv_gelu: w and a 16-byte aligned bias expected");
+    PPMS_REQUIRE(BT > 0 && H > 0 && W > 0, "dwconv_gelu: bad shape BT=%d H=%d W=%d", BT, H, W);
     const int64_t rows = (int64_t)BT * H;
     const int groups = x.c / 8;
     const dim3 grid(ceil_div(rows * ((W + DW_PX - 1) / DW_PX) * groups, 256));

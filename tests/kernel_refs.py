@@ -1,6 +1,7 @@
-"""Plain float64 CPU references of the non-convolution kernels of the two encoders (encoder_ops.hip) and of the glue kernels around the
-loop (small_ops.hip), one function per operation, each with the named wrong variants its test exists to catch; the cases (shapes and
-seeded inputs) of tests/test_gpu_encoder_ops.py and tests/test_gpu_glue_ops.py; and the tolerance rule both they and the CPU test
+"""Plain float64 CPU references of the non-convolution kernels of the two encoders (encoder_ops.hip), of the glue kernels around the
+loop (small_ops.hip) and of the kernels inside every update iteration (corr.hip's lookup, pwchain.hip, ppms_dwconv_gelu, attn16.hip), one
+function per operation, each with the named wrong variants its test exists to catch; the cases (shapes and seeded inputs) of
+tests/test_gpu_encoder_ops.py, tests/test_gpu_glue_ops.py and tests/test_gpu_update_ops.py; and the tolerance rule they and the CPU test
 tests/test_kernel_refs.py apply.  The formulas are those of oracle/ppm_oracle.py and of the kernel comments.
 
 Tolerances, three kinds, none taken from the code under test:
@@ -525,6 +526,395 @@ def split_check(ck, name, hi, lo, ref):
     return ck.bound(name + ".hi+lo", hi.float().double() + lo.float().double(), ref, ref.double().abs() * 2.0 ** -16)
 
 
+# ================================================================================================ kernels of the update iteration
+# The correlation lookup (corr.hip), the correlation encoder (pwchain.hip, ppms_dwconv_gelu) and the block16 / SST attention helpers
+# (attn16.hip): tests/test_gpu_update_ops.py.  Same three tolerance kinds; the pwchain cases keep the bounds the suite already uses for
+# that kernel (PW_ACC for one layer -- conv_audit.ACC_MAX --, 3e-5 / 5e-5 for the engine's chains), now against float64.
+def _gelu(v, form="erf"):
+    return F.gelu(v, approximate="tanh" if form == "tanh" else "none")
+
+
+# ------------------------------------------------------------------------------------------------ correlation lookup
+LOOKUP_CASES = {  # B, H, W
+    "P54": (1, 3, 18),                         # P % 4 = 2, W % 4 != 0, widths 18 / 9 / 4 / 2
+    "W16": (2, 2, 16),                         # the narrowest map the entry point accepts: level 3 has two columns
+    "W40": (1, 1, 40),                         # widths 40 / 20 / 10 / 5
+}
+
+
+def corr_lookup(levels, flow_x, W, tap_shift=0, scaled=True, half_pixel=False, clamp=False):
+    """levels: 4 pyramid levels (P, W >> l); flow_x (P,) -> (P, 36) float64, channel 9 l + kk: linear interpolation of the pixel's row of
+    level l at p = (kk - 4) + (x + flow_x) / 2^l, taps outside [0, Wl - 1] contribute 0 (corr.py:74-94: grid_sample, align_corners=True,
+    zero padding).  The keyword arguments are the wrong variants."""
+    P = flow_x.shape[0]
+    xs = (torch.arange(P) % W).double() + flow_x.double()
+    outs = []
+    for l, L in enumerate(levels):
+        L, Wl = L.double(), L.shape[1]
+        p = (torch.arange(9, dtype=F64) - 4 + tap_shift)[None] + xs[:, None] / (2 ** l if scaled else 1)
+        if half_pixel:
+            p = p * Wl / (Wl - 1) - 0.5                                   # g = 2 p / (Wl - 1) - 1 un-normalised as ((g + 1) Wl - 1) / 2
+        if clamp:
+            p = p.clamp(0, Wl - 1)
+        p0 = p.floor()
+        a, i0 = p - p0, p0.long()
+        tap = lambda i: torch.gather(L, 1, i.clamp(0, Wl - 1)) * ((i >= 0) & (i <= Wl - 1))
+        outs.append((1 - a) * tap(i0) + a * tap(i0 + 1))
+    return torch.cat(outs, 1)
+
+
+def corr_lookup_f32(levels, flow, B, H, W):
+    """the oracle's fp32 op sequence (normalise, un-normalise as the reference does): flow (P, 2) -> (P, 36)"""
+    from oracle import ppm_oracle as O
+    out = O.corr_lookup([L.float() for L in levels], flow.float().reshape(B, H, W, 2).permute(0, 3, 1, 2))
+    return out.permute(0, 2, 3, 1).reshape(B * H * W, 36)
+
+
+LOOKUP_WRONG = {
+    "tap_shifted": lambda lv, fx, W: corr_lookup(lv, fx, W, tap_shift=1),
+    "no_level_scale": lambda lv, fx, W: corr_lookup(lv, fx, W, scaled=False),
+    "half_pixel": lambda lv, fx, W: corr_lookup(lv, fx, W, half_pixel=True),
+    "border_clamp": lambda lv, fx, W: corr_lookup(lv, fx, W, clamp=True),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def lookup_inputs(case):
+    """levels: 4 x (P, W >> l) fp32; flow (P, 2) fp32 = 3 hash_normal, every 5th column rounded to an integer (a = 0), every 7th column x 8
+    (out of range); then pixels 1-8: the outermost tap of level l lands exactly on column Wl - 1 (pixel 1 + 2 l: tap kk = 0) and on column 0
+    (pixel 2 + 2 l: tap kk = 8); pixels 9, 10: +1e9, -1e9"""
+    B, H, W = LOOKUP_CASES[case]
+    P, seed = B * H * W, 8000 + 10 * list(LOOKUP_CASES).index(case)
+    levels = tuple(hash_normal((P, W >> l), seed + l) for l in range(4))
+    flow = 3.0 * hash_normal((P, 2), seed + 5)
+    x = torch.arange(P) % W
+    flow[x % 5 == 0] = flow[x % 5 == 0].round()
+    flow[x % 7 == 0] *= 8.0
+    for l in range(4):
+        Wl = W >> l
+        flow[1 + 2 * l, 0] = float(2 ** l * (Wl - 1 + 4) - x[1 + 2 * l])      # (x + fx) / 2^l - 4 = Wl - 1
+        flow[2 + 2 * l, 0] = float(-4 * 2 ** l - x[2 + 2 * l])                # (x + fx) / 2^l + 4 = 0
+    flow[9, 0], flow[10, 0] = 1e9, -1e9
+    return levels, flow
+
+
+@functools.lru_cache(maxsize=None)
+def lookup_refs(case):
+    B, H, W = LOOKUP_CASES[case]
+    levels, flow = lookup_inputs(case)
+    return corr_lookup(levels, flow[:, 0], W), corr_lookup_f32(levels, flow, B, H, W)
+
+
+def lookup_check(case, got, split, label=None):
+    """got (P, 36)"""
+    ref, f32 = lookup_refs(case)
+    return Check(label or f"corr_lookup {case}").add("corr", got, ref, tol_reduce(ref, f32, split))
+
+
+# ------------------------------------------------------------------------------------------------ depthwise k x k + residual GELU
+DWG_CASES = {  # BT, H, W, channels of the view, ld, k
+    "edges": (2, 3, 5, 8, 16, 7),              # every window crosses the top and bottom of its frame and both row ends; the last run of a row holds one pixel
+    "view40": (1, 9, 17, 40, 64, 7),           # the engine's view: channels 40-63 of x hold junk, those of y keep the sentinel
+    "full64": (3, 8, 16, 64, 72, 7),
+    "view40_k1": (1, 9, 17, 40, 64, 1),
+}
+
+
+def dwconv_gelu(x, w, b, k, pad="zeros", flip=False, transpose=False, residual=True, bias=True, gelu="erf", frames=True):
+    """x (BT, H, W, C), w (C, k k), b (C,) -> gelu_erf(x + dw_k(x) + b) (BT, H, W, C) float64, tap by tap: cross-correlation, zero padding
+    inside each frame (ppmtereo_update.py:1026-1027).  The keyword arguments are the wrong variants."""
+    BT, H, W, C = x.shape
+    if not frames:                                                          # taps read the neighbouring frame: one frame of BT H rows
+        return dwconv_gelu(x.reshape(1, BT * H, W, C), w, b, k, pad, flip, transpose, residual, bias, gelu).reshape(BT, H, W, C)
+    R, P = k // 2, BT * H * W
+    xd, wd = x.double(), w.double().reshape(C, k, k)
+    if flip:
+        wd = wd.flip(1, 2)
+    if transpose:
+        wd = wd.transpose(1, 2)
+    flat = xd.reshape(P, C)
+    f, y, xx0 = torch.arange(BT).reshape(BT, 1, 1), torch.arange(H).reshape(1, H, 1), torch.arange(W).reshape(1, 1, W)
+    acc = torch.zeros(BT, H, W, C, dtype=F64)
+    for ky in range(k):
+        for kx in range(k):
+            yy, xx = y + ky - R, xx0 + kx - R
+            if pad == "replicate":
+                yy, xx = yy.clamp(0, H - 1), xx.clamp(0, W - 1)
+            q = ((f * H + yy) * W + xx).expand(BT, H, W)
+            if pad == "zeros":
+                ok = (yy >= 0) & (yy < H) & (xx >= 0) & (xx < W)
+            elif pad == "y_only":                                           # no test along x: the tap wraps into the neighbouring row
+                ok = (yy >= 0) & (yy < H) & (q >= 0) & (q < P)
+            else:
+                ok = torch.ones(1, 1, 1, dtype=torch.bool)
+            v = flat[q.clamp(0, P - 1).reshape(-1)].reshape(BT, H, W, C) * ok.expand(BT, H, W)[..., None]
+            acc += v * wd[:, ky, kx]
+    v = acc + (b.double() if bias else 0.0) + (xd if residual else 0.0)
+    return _gelu(v, gelu)
+
+
+def dwconv_gelu_f32(x, w, b, k):
+    C = x.shape[3]
+    xi = x.float().permute(0, 3, 1, 2)
+    return F.gelu(xi + F.conv2d(xi, w.float().reshape(C, 1, k, k), b.float(), padding=k // 2, groups=C)).permute(0, 2, 3, 1)
+
+
+DWG_WRONG = {
+    "flipped": dict(flip=True), "ky_kx_transposed": dict(transpose=True), "no_residual": dict(residual=False), "no_bias": dict(bias=False),
+    "tanh_gelu": dict(gelu="tanh"), "replicate_padding": dict(pad="replicate"), "zero_padding_in_y_only": dict(pad="y_only"),
+    "no_frame_boundary": dict(frames=False),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def dwg_inputs(case):
+    BT, H, W, c, ld, k = DWG_CASES[case]
+    seed = 8100 + 10 * list(DWG_CASES).index(case)
+    return sp_round(hash_normal((BT, H, W, c), seed)), hash_normal((c, k * k), seed + 1) / k, hash_normal((c,), seed + 2) * 0.1
+
+
+@functools.lru_cache(maxsize=None)
+def dwg_refs(case):
+    x, w, b = dwg_inputs(case)
+    k = DWG_CASES[case][5]
+    return dwconv_gelu(x, w, b, k), dwconv_gelu_f32(x, w, b, k)
+
+
+def dwg_check(case, y):
+    ref, f32 = dwg_refs(case)
+    return Check(f"dwconv_gelu {case}").add("y", y, ref, tol_reduce(ref, f32, True))
+
+
+# ------------------------------------------------------------------------------------------------ fused per-pixel chains
+PW_ACC = 3e-5                                                              # conv_audit.ACC_MAX, the project's bound for one conv layer
+PW_PIXELS = [1, 318, 16384, 16385]                                         # 16384: the last count of the 32-pixel-tile kernel; 16385: the 128-pixel
+#                                                                            kernel, whose last tile holds one pixel
+PW_CHAINS = {  # input channels, [(cout, cin, residual, post affine)], bound relative to max(1, max|ref|)
+    "s64": (64, [(64, 64, False, False)], PW_ACC),
+    "s64_res": (64, [(64, 64, True, False)], PW_ACC),
+    "s64_post": (64, [(64, 64, False, True)], PW_ACC),
+    "s64_res_post": (64, [(64, 64, True, True)], PW_ACC),
+    "s256": (64, [(256, 64, False, False)], PW_ACC),
+    "A": (36, [(54, 36, False, False), (36, 54, True, True)], 3e-5),                                  # ffn1 + the depthwise 1x1 (engine.py chainA)
+    "B": (36, [(36, 36, True, False), (54, 36, False, False), (256, 54, False, False)], 5e-5),         # pw + ffn2 + the outer gelu (chainB)
+}
+
+
+def pwchain(x, layers, gelu="erf", resid_from="input", post_first=False, bias=True):
+    """x (P, cin); layers: [(w (cout, cin), b (cout,), residual, (s, t) or None)] -> (P, cout of the last layer) float64.  Per layer
+    y = gelu(w v + b [+ the chain INPUT at the same channel]); with a post step y = gelu(y + (y s + t)) (pwchain.hip).  The keyword
+    arguments are the wrong variants."""
+    x0 = x.double()
+    v = x0
+    for w, b, resid, post in layers:
+        co = w.shape[0]
+        y = v[:, :w.shape[1]] @ w.double().t() + (b.double() if bias else 0.0)
+        if resid:
+            y = y + (x0 if resid_from == "input" else v)[:, :co]
+        if post is not None and post_first:
+            y = y + (y * post[0].double() + post[1].double())
+            v = _gelu(_gelu(y, gelu), gelu)
+            continue
+        y = _gelu(y, gelu)
+        if post is not None:
+            y = _gelu(y + (y * post[0].double() + post[1].double()), gelu)
+        v = y
+    return v
+
+
+def pwchain_f32(x, layers):
+    x0 = x.float()
+    v = x0
+    for w, b, resid, post in layers:
+        y = v[:, :w.shape[1]] @ w.float().t() + b.float()
+        if resid:
+            y = y + x0[:, :w.shape[0]]
+        y = F.gelu(y)
+        v = F.gelu(y + (y * post[0].float() + post[1].float())) if post is not None else y
+    return v
+
+
+PW_WRONG = {"tanh_gelu": dict(gelu="tanh"), "residual_from_previous_layer": dict(resid_from="previous"),
+            "post_before_activation": dict(post_first=True), "no_bias": dict(bias=False)}
+
+
+@functools.lru_cache(maxsize=None)
+def pwchain_layers(chain):
+    """weights as the packs hold them (split bf16), fp32 bias and post affine"""
+    cin, spec, _ = PW_CHAINS[chain]
+    seed = 8200 + 20 * list(PW_CHAINS).index(chain)
+    layers = []
+    for i, (co, ci, resid, post) in enumerate(spec):
+        w = sp_round(hash_normal((co, ci), seed + 4 * i) / math.sqrt(ci))
+        st = (hash_normal((co,), seed + 4 * i + 2) * 0.5, hash_normal((co,), seed + 4 * i + 3) * 0.1) if post else None
+        layers.append((w, hash_normal((co,), seed + 4 * i + 1) * 0.1, resid, st))
+    return tuple(layers)
+
+
+@functools.lru_cache(maxsize=None)
+def pwchain_input():
+    """(max P, 64): every case reads its first P rows and its first cin channels"""
+    return sp_round(hash_normal((max(PW_PIXELS), 64), 8190))
+
+
+@functools.lru_cache(maxsize=None)
+def pwchain_ref(chain):
+    """the reference of all max(PW_PIXELS) rows (the operation is per pixel: a case of P pixels compares with the first P rows)"""
+    cin = PW_CHAINS[chain][0]
+    return pwchain(pwchain_input()[:, :cin], pwchain_layers(chain))
+
+
+def pwchain_check(chain, P, y):
+    ref = pwchain_ref(chain)[:P]
+    return Check(f"pwchain {chain} P={P}").add("y", y, ref, PW_CHAINS[chain][2] * max(1.0, ref.abs().max().item()))
+
+
+# ------------------------------------------------------------------------------------------------ time attention, LayerNorm (+ residual)
+A16_EPS = 1e-5
+A16_DATA = ("unit", "flat")                                                # hash_normal; 0.5 + 0.01 hash_normal (per-pixel std 0.01: eps matters)
+TA_CASES = [(1, 3), (5, 77), (9, 5)]                                       # T, n: T = 9 crosses the load loop's unroll of 8
+TA_MAX_T = {384: 42, 256: 64}                                              # the largest T whose T * C * 4 bytes fit the 64 KiB of LDS (include/ppms.h)
+LN16_PIXELS = 231                                                          # leaves a 4-pixel-block tail of 3
+
+
+def _ln(x, w, b, eps, unbiased=False):
+    mean, var = x.mean(-1, keepdim=True), x.var(-1, unbiased=unbiased, keepdim=True)
+    return (x - mean) * (var + eps).rsqrt() * w.double() + b.double()
+
+
+def time_attn(x, w, b, eps=A16_EPS, unbiased=False, dh=None, heads=8):
+    """x (T, n, C) -> (T, n, C) float64: per pixel, tokens = its T frames; y = LayerNorm(x); per head out_t = sum_t2 softmax_t2(y_t . y_t2 /
+    sqrt(dh)) y_t2 with q = k = v = y (ppmtereo_update.py:603-606, :409-417).  dh: the head width of the scale (default C / heads)."""
+    T, n, C = x.shape
+    d = C // heads
+    y = _ln(x.double().transpose(0, 1), w, b, eps, unbiased).reshape(n, T, heads, d).permute(0, 2, 1, 3)
+    att = torch.softmax((y @ y.transpose(-2, -1)) * (dh or d) ** -0.5, dim=-1)
+    return (att @ y).transpose(1, 2).reshape(n, T, C).transpose(0, 1)
+
+
+def time_attn_f32(x, w, b, heads=8):
+    T, n, C = x.shape
+    d = C // heads
+    y = F.layer_norm(x.float().transpose(0, 1), (C,), w.float(), b.float(), A16_EPS).reshape(n, T, heads, d).permute(0, 2, 1, 3)
+    att = torch.softmax((y @ y.transpose(-2, -1)) * d ** -0.5, dim=-1)
+    return (att @ y).transpose(1, 2).reshape(n, T, C).transpose(0, 1)
+
+
+TA_WRONG = {"eps_1e-6": lambda x, w, b: time_attn(x, w, b, eps=1e-6), "unbiased": lambda x, w, b: time_attn(x, w, b, unbiased=True),
+            "other_head_width": lambda x, w, b: time_attn(x, w, b, dh=48 if x.shape[2] == 256 else 32)}
+
+
+def _a16_data(shape, seed, data):
+    x = hash_normal(shape, seed)
+    return (0.5 + 0.01 * x).float() if data == "flat" else x
+
+
+@functools.lru_cache(maxsize=None)
+def time_attn_inputs(C, case, data):
+    T, n = case
+    seed = 8400 + C + 10 * (TA_CASES.index(case) if case in TA_CASES else len(TA_CASES))      # (else: the largest accepted T, one pixel)
+    return sp_round(_a16_data((T, n, C), seed, data)), 1.0 + 0.1 * hash_normal((C,), seed + 1), 0.1 * hash_normal((C,), seed + 2)
+
+
+def time_attn_check(C, case, data, y):
+    x, w, b = time_attn_inputs(C, case, data)
+    ref = time_attn(x, w, b)
+    return Check(f"time_attn C={C} T,n={case} {data}").add("y", y, ref, tol_reduce(ref, time_attn_f32(x, w, b), True))
+
+
+def layernorm16(x, w, b, res=None, eps=A16_EPS, unbiased=False):
+    """x (P, C), res (P, C) or None -> res + LayerNorm(x) float64, eps 1e-5 (attention.py:186-190)"""
+    y = _ln(x.double(), w, b, eps, unbiased)
+    return y if res is None else y + res.double()
+
+
+def layernorm16_f32(x, w, b, res=None):
+    y = F.layer_norm(x.float(), (x.shape[1],), w.float(), b.float(), A16_EPS)
+    return y if res is None else y + res.float()
+
+
+LN16_WRONG = {"eps_1e-6": lambda x, w, b, r: layernorm16(x, w, b, r, eps=1e-6), "unbiased": lambda x, w, b, r: layernorm16(x, w, b, r, unbiased=True),
+              "residual_lo_plane_ignored": lambda x, w, b, r: None if r is None else layernorm16(x, w, b, r.to(torch.bfloat16).float())}
+
+
+@functools.lru_cache(maxsize=None)
+def layernorm16_inputs(C, data):
+    """x, w, b and the residual as split bf16 holds it"""
+    seed = 8500 + C
+    return (_a16_data((LN16_PIXELS, C), seed, data), 1.0 + 0.1 * hash_normal((C,), seed + 1), 0.1 * hash_normal((C,), seed + 2),
+            sp_round(hash_normal((LN16_PIXELS, C), seed + 3)))
+
+
+def layernorm16_check(C, data, with_res, y):
+    x, w, b, res = layernorm16_inputs(C, data)
+    r = res if with_res else None
+    ref = layernorm16(x, w, b, r)
+    return Check(f"layernorm C={C} {data} res={int(with_res)}").add("y", y, ref, tol_reduce(ref, layernorm16_f32(x, w, b, r), True))
+
+
+# ------------------------------------------------------------------------------------------------ linear attention
+LA_EPS = 1e-6
+LA_SPLITS, LA_PASS = 4, 160                                                # pixel splits of the kv kernel; pixels it stages per pass
+LA_CASES = [(1, 3), (2, 77), (1, 644)]                                     # T, n: split 3 empty; a 32-pixel apply tail of 13; share 161 = one pass + 1
+LA_DATA = ("unit", "tiny")                                                 # tiny: K x 1e-6, Q . sum K a few 1e-3 and less: the 1e-6 of the divisor shows
+
+
+def linear_attention(Q, K, V, eps=LA_EPS, times_n=True, keep=None):
+    """Q, K, V (T, n, heads, dh), Q and K already elu() + 1, V already / n -> (Q KV) / (Q . sum K + 1e-6) n float64 (attention.py:73-100).
+    keep: (n,) mask of the source pixels the sums run over (the wrong variants)."""
+    Q, K, V = Q.double(), K.double(), V.double()
+    n = Q.shape[1]
+    if keep is not None:
+        K, V = K * keep.reshape(1, n, 1, 1), V * keep.reshape(1, n, 1, 1)
+    KV = torch.einsum("nshd,nshv->nhdv", K, V)
+    Z = 1 / (torch.einsum("nlhd,nhd->nlh", Q, K.sum(1)) + eps)
+    out = torch.einsum("nlhd,nhdv,nlh->nlhv", Q, KV, Z)
+    return out * n if times_n else out
+
+
+def linear_attention_f32(Q, K, V):
+    """oracle.ppm_oracle.loftr_layer's expression in fp32"""
+    Q, K, V = Q.float(), K.float(), V.float()
+    KV = torch.einsum("nshd,nshv->nhdv", K, V)
+    Z = 1 / (torch.einsum("nlhd,nhd->nlh", Q, K.sum(1)) + 1e-6)
+    return torch.einsum("nlhd,nhdv,nlh->nlhv", Q, KV, Z) * Q.shape[1]
+
+
+def _la_keep(n, what):
+    per = (n + LA_SPLITS - 1) // LA_SPLITS
+    s = torch.arange(n)
+    keep = (s < (LA_SPLITS - 1) * per) if what == "last_split" else ((s % per) < LA_PASS)
+    return None if bool(keep.all()) else keep.double()                      # None: the variant does not apply to this n
+
+
+def _la_with_keep(what):
+    def fn(Q, K, V):
+        keep = _la_keep(Q.shape[1], what)
+        return None if keep is None else linear_attention(Q, K, V, keep=keep)
+    return fn
+
+
+LA_WRONG = {"no_divisor_eps": lambda Q, K, V: linear_attention(Q, K, V, eps=0.0), "last_split_dropped": _la_with_keep("last_split"),
+            "first_pass_only": _la_with_keep("first_pass"), "times_n_omitted": lambda Q, K, V: linear_attention(Q, K, V, times_n=False)}
+
+
+@functools.lru_cache(maxsize=None)
+def linattn_inputs(dh, case, data):
+    T, n = case
+    seed = 8600 + dh + 10 * LA_CASES.index(case)
+    shape = (T, n, 8, dh)
+    Q, K = F.elu(hash_normal(shape, seed)) + 1, F.elu(hash_normal(shape, seed + 1)) + 1
+    if data == "tiny":
+        K = (K * 1e-6).float()
+    return Q, K, hash_normal(shape, seed + 2) / n
+
+
+def linattn_check(dh, case, data, y, label=None):
+    Q, K, V = linattn_inputs(dh, case, data)
+    ref = linear_attention(Q, K, V)
+    return Check(label or f"linear_attention dh={dh} T,n={case} {data}").add("y", y, ref, tol_reduce(ref, linear_attention_f32(Q, K, V), True))
+
+
 # ------------------------------------------------------------------------------------------------ device buffers of the GPU tests
 GPU = "cuda:0"
 
@@ -539,6 +929,16 @@ def sp_in(L, values, extra=8, c0=0):
     """SP tensor whose channels [c0, c0 + C) hold `values` (P, C); the other channels hold the sentinel"""
     P, C = values.shape
     t = sp_out(L, P, c0 + C + extra)
+    t.set_f32(values.to(GPU), c0)
+    assert torch.equal(t.to_f32(c0, C).cpu(), values), "the reference must see what the kernel sees"
+    return t
+
+
+def sp_in_junk(L, values, channels, c0=0):
+    """SP tensor of `channels` channels whose channels [c0, c0 + C) hold `values` (P, C); every other channel holds JUNK in both planes"""
+    P, C = values.shape
+    t = L.SPTensor(P, channels, GPU)
+    t.data.fill_(JUNK)
     t.set_f32(values.to(GPU), c0)
     assert torch.equal(t.to_f32(c0, C).cpu(), values), "the reference must see what the kernel sees"
     return t

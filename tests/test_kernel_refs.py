@@ -238,3 +238,243 @@ def test_avgpool_wrong_variant_is_caught():
         ref = R.avgpool(x, case[0])
         runs.append(R.Check().add("y", R.AVGPOOL_WRONG["clipped_divisor"](x, case[0]), ref, R.tol_reduce(ref, R.avgpool_f32(x, case[0]), False)))
     assert any(not c.ok for c in runs)
+
+
+# ================================================================================================ kernels of the update iteration
+# ------------------------------------------------------------------------------------------------ references vs torch / the oracle
+@pytest.mark.parametrize("case", list(R.LOOKUP_CASES))
+def test_corr_lookup_vs_grid_sample_and_oracle(case):
+    """the float64 lookup against F.grid_sample (align_corners=True, zero padding) on the normalised positions, and against the oracle's
+    corr_lookup fed float64 (which returns fp32: compared at fp32 rounding)"""
+    from oracle import ppm_oracle as O
+    B, H, W = R.LOOKUP_CASES[case]
+    levels, flow = R.lookup_inputs(case)
+    got = R.corr_lookup(levels, flow[:, 0], W)
+    P = B * H * W
+    xs = (torch.arange(P) % W).double() + flow[:, 0].double()
+    for l, L in enumerate(levels):
+        Wl = L.shape[1]
+        p = (torch.arange(9, dtype=F64) - 4)[None] + xs[:, None] / 2 ** l
+        grid = torch.stack([2 * p / (Wl - 1) - 1, torch.zeros_like(p)], -1).reshape(P, 1, 9, 2)
+        want = F.grid_sample(L.double().reshape(P, 1, 1, Wl), grid, mode="bilinear", padding_mode="zeros", align_corners=True).reshape(P, 9)
+        close(got[:, 9 * l:9 * l + 9], want, 1e-9)
+    pyr = [L.double() for L in levels]
+    want = O.corr_lookup(pyr, flow.double().reshape(B, H, W, 2).permute(0, 3, 1, 2)).permute(0, 2, 3, 1).reshape(P, 36)
+    close(got, want, 1e-6)
+
+
+def test_lookup_flow_recipe():
+    """what the flow of the lookup cases is built to contain"""
+    for case, (B, H, W) in R.LOOKUP_CASES.items():
+        levels, flow = R.lookup_inputs(case)
+        P = B * H * W
+        assert P >= 11 and torch.isfinite(flow).all()
+        ref = R.lookup_refs(case)[0]
+        for l in range(4):
+            assert ref[1 + 2 * l, 9 * l] == levels[l][1 + 2 * l, -1].double() and (ref[1 + 2 * l, 9 * l + 1:9 * l + 9] == 0).all()      # tap 0 on column Wl - 1
+            assert ref[2 + 2 * l, 9 * l + 8] == levels[l][2 + 2 * l, 0].double() and (ref[2 + 2 * l, 9 * l:9 * l + 8] == 0).all()        # tap 8 on column 0
+        assert (ref[9] == 0).all() and (ref[10] == 0).all() and flow[9, 0] == 1e9 and flow[10, 0] == -1e9
+        x = torch.arange(P) % W
+        plain = torch.ones(P, dtype=torch.bool)
+        plain[1:11] = False
+        assert (flow[(x % 5 == 0) & (x % 7 != 0) & plain, 0] % 1 == 0).all()
+    assert [R.LOOKUP_CASES["P54"][2] >> l for l in range(4)] == [18, 9, 4, 2] and (1 * 3 * 18) % 4 == 2
+
+
+def _pcblock_weights(c, hid, cout):
+    mk = lambda shape, seed, fan: hash_normal(shape, seed).double() / fan ** 0.5
+    W, p = {}, "p."
+    for name, shape, fan, seed in (("ffn1.0", (hid, c, 1, 1), c, 30), ("ffn1.2", (c, hid, 1, 1), hid, 32), ("conv_list.0", (c, 1, 1, 1), 4, 34),
+                                   ("conv_list.1", (c, 1, 7, 7), 49, 36), ("pw", (c, c, 1, 1), c, 38), ("ffn2.0", (hid, c, 1, 1), c, 40),
+                                   ("ffn2.2", (cout, hid, 1, 1), hid, 42)):
+        W[p + name + ".weight"], W[p + name + ".bias"] = mk(shape, seed, fan), 0.1 * hash_normal((shape[0],), seed + 1).double()
+    return W
+
+
+def test_pwchain_and_dwconv_gelu_vs_oracle_pcblock():
+    """chain A, the depthwise 7 x 7 + GELU and chain B in sequence are gelu(PCBlock4_Deep_nopool_res.forward) of the oracle"""
+    from oracle import ppm_oracle as O
+    c, hid, cout, BT, H, Wd = 12, 20, 24, 2, 5, 9
+    W = _pcblock_weights(c, hid, cout)
+    x = hash_normal((BT, c, H, Wd), 29).double()
+    want = F.gelu(O.pcblock(W, "p", x)).permute(0, 2, 3, 1)
+    g = lambda n: (W[f"p.{n}.weight"].reshape(W[f"p.{n}.weight"].shape[0], -1), W[f"p.{n}.bias"])
+    rows = x.permute(0, 2, 3, 1).reshape(-1, c)
+    a = R.pwchain(rows, [(*g("ffn1.0"), False, None), (*g("ffn1.2"), True, (W["p.conv_list.0.weight"].reshape(c), W["p.conv_list.0.bias"]))])
+    d = R.dwconv_gelu(a.reshape(BT, H, Wd, c), *g("conv_list.1"), 7)
+    b = R.pwchain(d.reshape(-1, c), [(*g("pw"), True, None), (*g("ffn2.0"), False, None), (*g("ffn2.2"), False, None)])
+    close(b.reshape(BT, H, Wd, cout), want)
+    close(R.dwconv_gelu(x.permute(0, 2, 3, 1), W["p.conv_list.0.weight"].reshape(c, 1), W["p.conv_list.0.bias"], 1),
+          F.gelu(x + O._c2(W, "p.conv_list.0", x, 0, groups=c)).permute(0, 2, 3, 1))
+
+
+@pytest.mark.parametrize("C", [256, 384])
+def test_time_attn_vs_oracle(C):
+    """the oracle's TimeAttnBlock with identity proj / fc layers is x + the attention core"""
+    from oracle import ppm_oracle as O
+    T, h, w = 3, 2, 5
+    x = hash_normal((T, C, h, w), 50 + C).double()
+    W = {"time_attn.temporal_norm1.weight": 1 + 0.1 * hash_normal((C,), 51).double(), "time_attn.temporal_norm1.bias": 0.1 * hash_normal((C,), 52).double(),
+         "time_attn.temporal_attn.proj.weight": torch.eye(C, dtype=F64), "time_attn.temporal_attn.proj.bias": torch.zeros(C, dtype=F64),
+         "time_attn.temporal_fc.weight": torch.eye(C, dtype=F64), "time_attn.temporal_fc.bias": torch.zeros(C, dtype=F64)}
+    want = (O.time_attn(W, x, T) - x).permute(0, 2, 3, 1).reshape(T, h * w, C)
+    got = R.time_attn(x.permute(0, 2, 3, 1).reshape(T, h * w, C), W["time_attn.temporal_norm1.weight"], W["time_attn.temporal_norm1.bias"])
+    close(got, want, 1e-11)
+
+
+def test_layernorm16_and_linear_attention_vs_torch():
+    from oracle import ppm_oracle as O
+    x, w, b, r = (hash_normal(s, 60 + i).double() for i, s in enumerate([(7, 256), (256,), (256,), (7, 256)]))
+    close(R.layernorm16(x, w, b), O.layer_norm(x, w, b))
+    close(R.layernorm16(x, w, b, r), r + F.layer_norm(x, (256,), w, b, 1e-5))
+    Q, K, V = (t.double() for t in R.linattn_inputs(32, (2, 77), "unit"))
+    S = 77                                                                     # LinearAttention.forward as the oracle's loftr_layer states it
+    KV = torch.einsum("nshd,nshv->nhdv", K, V)
+    Z = 1 / (torch.einsum("nlhd,nhd->nlh", Q, K.sum(1)) + 1e-6)
+    close(R.linear_attention(Q, K, V), torch.einsum("nlhd,nhdv,nlh->nlhv", Q, KV, Z) * S)
+
+
+def test_update_case_arithmetic():
+    """the shape arithmetic the case tables rely on"""
+    assert [(n + 3) // 4 for _, n in R.LA_CASES] == [1, 20, 161] and 161 == R.LA_PASS + 1 and 77 % 32 == 13
+    assert R._la_keep(3, "last_split") is None and R._la_keep(77, "first_pass") is None and R._la_keep(644, "first_pass").sum() == 640
+    assert R.LN16_PIXELS % 4 == 3 and 16384 in R.PW_PIXELS and 16385 % 128 == 1
+    BT, H, W, c, ld, k = R.DWG_CASES["edges"]
+    assert H <= k // 2 and W <= k and W % 2 == 1 and BT > 1
+
+
+# ------------------------------------------------------------------------------------------------ every wrong variant is caught
+def _lookup_runs(fn):
+    out = []
+    for case, (B, H, W) in R.LOOKUP_CASES.items():
+        levels, flow = R.lookup_inputs(case)
+        got = fn(levels, flow, B, H, W)
+        out += [R.lookup_check(case, got, True), R.lookup_check(case, got, False)]      # the SP outputs' tolerance and the fp32 output's
+    return out
+
+
+def test_lookup_cases_pass_the_reference_and_fp32():
+    assert all(c.ok for c in _lookup_runs(lambda lv, fl, B, H, W: R.corr_lookup(lv, fl[:, 0], W)))
+    runs = _lookup_runs(R.corr_lookup_f32)
+    assert all(c.ok for c in runs), [str(c) for c in runs if not c.ok]
+
+
+@pytest.mark.parametrize("name", list(R.LOOKUP_WRONG))
+def test_lookup_wrong_variant_is_caught(name):
+    runs = _lookup_runs(lambda lv, fl, B, H, W: R.LOOKUP_WRONG[name](lv, fl[:, 0], W))
+    assert all(not c.ok for c in runs), name                                            # (here: on every case)
+
+
+def test_dwg_cases_pass_the_reference_and_fp32():
+    for case in R.DWG_CASES:
+        ref, f32 = R.dwg_refs(case)
+        assert R.dwg_check(case, ref).ok
+        ck = R.dwg_check(case, f32)
+        assert ck.ok, str(ck)
+
+
+@pytest.mark.parametrize("name", list(R.DWG_WRONG))
+def test_dwg_wrong_variant_is_caught(name):
+    runs = [R.dwg_check(case, R.dwconv_gelu(*R.dwg_inputs(case), R.DWG_CASES[case][5], **R.DWG_WRONG[name])) for case in R.DWG_CASES]
+    assert any(not c.ok for c in runs), name
+    if name in ("zero_padding_in_y_only", "no_frame_boundary", "replicate_padding"):
+        assert not runs[list(R.DWG_CASES).index("edges")].ok                           # what the "edges" case is for
+
+
+def test_pwchain_cases_pass_the_reference_and_fp32():
+    for chain, (cin, _, _) in R.PW_CHAINS.items():
+        for P in R.PW_PIXELS:
+            assert R.pwchain_check(chain, P, R.pwchain_ref(chain)[:P]).ok
+        ck = R.pwchain_check(chain, 16385, R.pwchain_f32(R.pwchain_input()[:, :cin], R.pwchain_layers(chain)))
+        assert ck.ok, str(ck)
+
+
+@pytest.mark.parametrize("name", list(R.PW_WRONG))
+def test_pwchain_wrong_variant_is_caught(name):
+    runs = []
+    for chain, (cin, _, _) in R.PW_CHAINS.items():
+        got = R.pwchain(R.pwchain_input()[:318, :cin], R.pwchain_layers(chain), **R.PW_WRONG[name])
+        runs.append(R.pwchain_check(chain, 318, got))
+    assert any(not c.ok for c in runs), name
+
+
+def _ta_runs(fn, data_kinds=R.A16_DATA):
+    return [R.time_attn_check(C, case, data, fn(*R.time_attn_inputs(C, case, data))) for C in (256, 384) for case in R.TA_CASES for data in data_kinds]
+
+
+def test_time_attn_cases_pass_the_reference_and_fp32():
+    assert all(c.ok for c in _ta_runs(R.time_attn))
+    runs = _ta_runs(R.time_attn_f32)
+    assert all(c.ok for c in runs), [str(c) for c in runs if not c.ok]
+
+
+@pytest.mark.parametrize("name", list(R.TA_WRONG))
+def test_time_attn_wrong_variant_is_caught(name):
+    runs = _ta_runs(R.TA_WRONG[name])
+    assert any(not c.ok for c in runs), name
+    for C in (256, 384):                                                                # both instantiations see every mistake
+        assert any(not c.ok for c in runs if f"C={C}" in c.label), (name, C)
+
+
+def test_time_attn_eps_needs_the_flat_data():
+    assert all(not c.ok for c in _ta_runs(R.TA_WRONG["eps_1e-6"], ("flat",)))
+    assert all(c.ok for c in _ta_runs(R.TA_WRONG["eps_1e-6"], ("unit",)))               # invisible at unit variance
+
+
+def _ln16_runs(fn, data_kinds=R.A16_DATA):
+    out = []
+    for C in (256, 384):
+        for data in data_kinds:
+            x, w, b, res = R.layernorm16_inputs(C, data)
+            for with_res in (False, True):
+                got = fn(x, w, b, res if with_res else None)
+                if got is not None:
+                    out.append(R.layernorm16_check(C, data, with_res, got))
+    return out
+
+
+def test_layernorm16_cases_pass_the_reference_and_fp32():
+    assert all(c.ok for c in _ln16_runs(R.layernorm16))
+    runs = _ln16_runs(R.layernorm16_f32)
+    assert all(c.ok for c in runs), [str(c) for c in runs if not c.ok]
+
+
+@pytest.mark.parametrize("name", list(R.LN16_WRONG))
+def test_layernorm16_wrong_variant_is_caught(name):
+    runs = _ln16_runs(R.LN16_WRONG[name])
+    assert runs and any(not c.ok for c in runs), name
+    for C in (256, 384):
+        assert any(not c.ok for c in runs if f"C={C}" in c.label), (name, C)
+    if name == "eps_1e-6":
+        assert all(not c.ok for c in _ln16_runs(R.LN16_WRONG[name], ("flat",)))
+
+
+def _la_runs(fn, data_kinds=R.LA_DATA):
+    out = []
+    for dh in (32, 48):
+        for case in R.LA_CASES:
+            for data in data_kinds:
+                got = fn(*R.linattn_inputs(dh, case, data))
+                if got is not None:
+                    out.append(R.linattn_check(dh, case, data, got))
+    return out
+
+
+def test_linattn_cases_pass_the_reference_and_fp32():
+    assert all(c.ok for c in _la_runs(R.linear_attention))
+    runs = _la_runs(R.linear_attention_f32)
+    assert all(c.ok for c in runs), [str(c) for c in runs if not c.ok]
+
+
+@pytest.mark.parametrize("name", list(R.LA_WRONG))
+def test_linattn_wrong_variant_is_caught(name):
+    runs = _la_runs(R.LA_WRONG[name])
+    assert runs and any(not c.ok for c in runs), name
+    for dh in (32, 48):
+        assert any(not c.ok for c in runs if f"dh={dh}" in c.label), (name, dh)
+
+
+def test_linattn_eps_needs_the_tiny_data():
+    runs = _la_runs(R.LA_WRONG["no_divisor_eps"], ("tiny",))
+    assert all(not c.ok for c in runs if "644" not in c.label)                          # n = 3 and 77; at n = 644 Q . sum K is 0.03, the eps 3e-5 of it
+    assert all(c.ok for c in _la_runs(R.LA_WRONG["no_divisor_eps"], ("unit",)))         # invisible at unit-scale K
