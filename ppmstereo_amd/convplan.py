@@ -8,22 +8,16 @@ result is a ``ConvOp``: the host descriptor, its device copy and the resolved en
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional, Sequence
+from typing import Callable, Dict, NamedTuple, Optional, Sequence
 
 import torch
 
 from . import _lib as L
 from . import packing as _packing
+# Kernel identities (ConvOp.version; bench.py and the tests read the plain ints).  KERNELS below holds the record of each.
+from .packing import CONV2, CONV5, CONV6, GEMM1, STREAM
 
-# Kernel identities (ConvOp.version; bench.py and the tests read the plain ints)
-CONV2 = 2           # conv_gemm2.hip: implicit GEMM through LDS, optionally K-sliced (+ a reduce launch)
-CONV5 = 5           # conv_gemm5.hip: one 8-wave workgroup per CU, weights in MFMA-fragment order
-GEMM1 = 6           # gemm1.hip: thin GEMM of the 1x1 convolutions / Linear layers
-STREAM = 7          # conv_stream.hip: register-streamed small-map kernel (no K slices, no reduce launch)
-CONV6 = 8           # conv_gemm6.hip: one wave per SIMD on the 16x16x32 MFMA
 CONV2_SWEPT = "2s"  # (pack key only) conv_gemm2's one-window form: the swept weight order of a (kt, kh, 1) conv, launched as CONV2 with ysweep
-KERNEL_NAMES = {CONV2: "conv_gemm2", CONV5: "conv_gemm5", GEMM1: "gemm1", STREAM: "conv_stream", CONV6: "conv_gemm6"}
-ALL_KERNELS = frozenset((CONV2, CONV2_SWEPT, CONV5, GEMM1, STREAM, CONV6))
 
 # The measured-best settings that are still switches.  The product reads no environment variable.
 TUNING = dict(
@@ -71,34 +65,14 @@ class ConvOp:
         self.keep = keep            # tensors whose storage the descriptor points at
         self.events = None          # list collecting (start, stop) HIP events per launch when kernel timing is on
         lib, ref = L.load(), C.byref(desc)
+        self._kernel = k = kernel_record(self.version, ysweep)
         # small maps: K-sliced launch + reduce kernel (nslice None: ask the library; own workspace per op because ops
-        # of the two streams run concurrently)
-        self.nslice, self.ws = 1, None
-        if version == CONV5 and nslice is not None and nslice > 1:      # conv_gemm5's K-sliced form (same workspace layout as conv_gemm2's)
-            self.nslice = int(nslice)
-        elif version == CONV2 and wm_hint == 0:
-            plan = lib.ppms_conv_gemm2_ysweep_slices if ysweep else lib.ppms_conv_gemm2_slices
-            self.nslice = max(1, int(plan(ref))) if nslice is None else nslice
+        # of the two streams run concurrently; conv_gemm5's sliced form has the same workspace layout as conv_gemm2's)
+        self.nslice, self.ws = k.slices(lib, ref, wm_hint, nslice), None
         if self.nslice > 1:
             self.ws = torch.empty(int(lib.ppms_conv_gemm2_slice_workspace_bytes(ref, self.nslice)), dtype=torch.uint8, device=device)
         # the entry point and every argument but the stream, resolved once: the small scales are chains of short launches
-        dp, ws = self.dev.data_ptr(), L.ptr(self.ws)
-        if version == CONV5 and self.nslice > 1:
-            self._fn, self._args = lib.ppms_conv_gemm5_sliced, (ref, dp, wm_hint, self.nslice, ws)
-        elif version == CONV5:
-            self._fn, self._args = lib.ppms_conv_gemm5, (ref, dp, wm_hint)
-        elif version == CONV6:
-            self._fn, self._args = lib.ppms_conv_gemm6, (ref, dp)
-        elif version == GEMM1:
-            self._fn, self._args = lib.ppms_gemm1, (ref, dp, wm_hint)
-        elif version == STREAM:
-            self._fn, self._args = lib.ppms_conv_stream, (ref, dp, wm_hint)
-        elif ysweep:
-            self._fn, self._args = lib.ppms_conv_gemm2_ysweep, (ref, dp, self.nslice, ws)
-        elif self.nslice > 1:
-            self._fn, self._args = lib.ppms_conv_gemm2_sliced, (ref, dp, self.nslice, ws)
-        else:
-            self._fn, self._args = lib.ppms_conv_gemm2, (ref, dp, wm_hint)
+        self._fn, self._args = k.bind(lib, ref, self.dev.data_ptr(), wm_hint, self.nslice, L.ptr(self.ws))
 
     def flops(self) -> float:
         """Algorithmic FLOPs of one launch: 2 * pixels * stored couts * input channels of the launch * taps (zero-padding
@@ -112,17 +86,16 @@ class ConvOp:
         """MFMAs the kernel issues per algorithmic bf16x3 product: 3 (hi*hi, lo*hi, hi*lo), less the hi*lo products conv_gemm5 / conv_gemm6 leave out for the
         input channels from `lo_zero_from` on (bf16-exact activations: their lo plane is all zero).  bench.py prices a launch against
         dense bf16 / this."""
-        d = self.desc
+        d, k = self.desc, self._kernel
         cin = sum(d.seg[i].c for i in range(d.nseg))
         lz = int(d.lo_zero_from)
-        if self.version not in (CONV5, CONV6) or lz <= 0 or lz >= cin or lz % (16 if self.version == CONV5 else 32):
+        if not k.lo_steps or lz <= 0 or lz >= cin or lz % k.granule:
             return 3.0
-        if self.version == CONV6:
-            # conv_gemm6's K loop runs the windows with a lo plane first (phase 0) and needs an EVEN number of k32-steps there (its weight registers
-            # alternate between two stages): plan6 (conv_gemm6.hip) ignores lo_zero_from when (lo_zero_from / 32) * (k32-steps per window) is odd
-            nsweep = d.kh * d.kw if (d.kh > 1 or d.kw > 1) else 1
-            if ((lz // 32) * nsweep) & 1:
-                return 3.0
+        # conv_gemm6's K loop runs the windows with a lo plane first (phase 0) and needs an EVEN number of k32-steps there (its weight registers
+        # alternate between two stages): plan6 (conv_gemm6.hip) ignores lo_zero_from when (lo_zero_from / 32) * (k32-steps per window) is odd
+        nsweep = d.kh * d.kw if (d.kh > 1 or d.kw > 1) else 1
+        if ((lz // k.granule) * nsweep) % k.lo_steps:
+            return 3.0
         return 3.0 - (cin - lz) / cin
 
     def __call__(self):
@@ -172,7 +145,7 @@ class PwChain:
         assert not any(resid for _, _, resid, _ in layers[2:]), "pwchain: a residual layer must be the first or the second of its chain"
         for i, (pack, n_valid, resid, post) in enumerate(layers):
             packed, bias, meta = pack
-            assert meta["nk"] == 2 and meta["version"] == 2, "chain layers are 1x1 convs with 64 (padded) input channels"
+            assert meta["nk"] == 2 and meta["kernel"] == CONV2,"chain layers are 1x1 convs with 64 (padded) input channels"
             ly = cp.layer[i]
             ly.w, ly.bias, ly.M, ly.n_valid, ly.resid = packed.data_ptr(), bias.data_ptr(), meta["M"], n_valid, int(resid)
             ly.post_s = None if post is None else post[0].data_ptr()
@@ -186,9 +159,129 @@ class PwChain:
         _timed(lambda: L.check(L.load().ppms_pwchain(self.dev.data_ptr(), self.pixels, L.stream_ptr())), self.events)
 
 
+# ------------------------------------------------------------------------------------------------ the kernels
+class _Shape(NamedTuple):
+    """What decides which packs pack_conv builds for a weight."""
+    taps: tuple         # (kt, kh, kw)
+    pads: list          # padded input channels per segment
+    rows: int           # output rows in use
+    m2: int             # conv_gemm2's padded rows (gemm1 / conv_stream use the same)
+
+    @property
+    def swept(self) -> bool:
+        return self.taps[1] > 1 or self.taps[2] > 1
+
+    @property
+    def k32(self) -> bool:
+        return all(p % 32 == 0 for p in self.pads)
+
+    @property
+    def m_waves(self) -> int:
+        """conv_gemm5 / conv_gemm6 deal 128, 192 (three 64-cout blocks: convc2's 192, final_conv's 190 couts) or 256 rows to their waves"""
+        return 128 if self.rows <= 128 else (192 if self.rows <= 192 else 256)
+
+
+def _rows_conv6(s: _Shape) -> Optional[int]:
+    # conv_gemm6 without a spatial sweep: its STREAM form, for the (kt,1,1) convs to 256 couts (the z/r conv of the GRU's pass T: 131 us against
+    # conv_gemm5's 155 at the 1/4 scale; the 128-cout q conv stays on conv_gemm2: 85 us against 89 there)
+    return s.m_waves if s.k32 and (s.swept or (s.taps[0] > 1 and s.rows > 128)) else None
+
+
+def _rows_conv5(s: _Shape) -> Optional[int]:
+    if s.swept:
+        return s.m_waves
+    # no spatial sweep: conv_gemm5's GEMM mode (windows of 64 channels), for > 128 couts only (GRU pass-T z/r 197 -> 164 us, mask_2d.2 62 -> 46 us
+    # at the 1/4 scale); with 128 couts the two K-groups get 32-channel windows, too short a DMA lookahead (pass-T q 110 -> 122 us, to_v 44 -> 66 us)
+    return (s.rows + 127) // 128 * 128 if s.rows > 128 and s.k32 else None
+
+
+def _fills_half(d: L.Conv) -> bool:
+    """The stored couts fill more than half of the padded rows."""
+    return 2 * (d.epi[0].n_valid + (d.epi[1].n_valid if d.m_split < d.M else 0)) > d.M
+
+
+def _slices_conv2(plan: str):
+    """conv_gemm2's K slices: the library's plan (grid-level slicing of the small maps' convs) or the caller's; none under a tile hint."""
+    return lambda lib, ref, wm_hint, nslice: 1 if wm_hint != 0 else (max(1, int(getattr(lib, plan)(ref))) if nslice is None else nslice)
+
+
+class Kernel(NamedTuple):
+    """One conv kernel as pack_conv, plan_conv and ConvOp see it."""
+    key: object             # pack key: the id, or CONV2_SWEPT
+    id: int                 # ConvOp.version
+    name: str
+    layout: Callable        # packing.py: (weight, bias, segs, seg_pad, cout_map, m) -> (packed, bias, meta)
+    granule: int            # input channels per k-step
+    swept: bool             # reads its taps in sweep_order
+    rows: Callable          # _Shape -> padded rows of the pack pack_conv builds, None: no pack for this weight
+    accepts: Callable       # (lib, descriptor with this pack) -> plan_conv launches it here
+    bind: Callable          # (lib, ref, dev, wm_hint, nslice, ws) -> (entry point, arguments before the stream)
+    slices: Callable = lambda lib, ref, wm_hint, nslice: 1     # -> K slices of the launch
+    lo_steps: int = 0       # skips the hi*lo products from ppms_conv.lo_zero_from on when the k-steps before it are a multiple of this (0: never)
+
+    @property
+    def ysweep(self) -> bool:
+        return self.key == CONV2_SWEPT
+
+
+# In planning order: plan_conv takes the first whose pack exists and which accepts the descriptor.
+KERNELS = (
+    # 1x1 convs / Linear layers where the thin GEMM is rated faster (2: served, but the implicit GEMM is as fast on a map this large)
+    Kernel(GEMM1, GEMM1, "gemm1", _packing.pack_gemm1, 16, False,
+           rows=lambda s: s.m2 if s.taps == (1, 1, 1) and sum(s.pads) % 64 == 0 else None,
+           accepts=lambda lib, d: lib.ppms_gemm1_applicable(C.byref(d)) == 1,
+           bind=lambda lib, ref, dev, wm_hint, nslice, ws: (lib.ppms_gemm1, (ref, dev, wm_hint))),
+    # small maps (1/8, 1/16 scales): the register-streamed kernel where the library rates it faster -- no K slices, no reduce launch
+    Kernel(STREAM, STREAM, "conv_stream", _packing.pack_stream, 16, False,
+           rows=lambda s: s.m2 if sum(s.pads) % 64 == 0 else None,
+           accepts=lambda lib, d: lib.ppms_conv_stream_applicable(C.byref(d)) == 1,
+           bind=lambda lib, ref, dev, wm_hint, nslice, ws: (lib.ppms_conv_stream, (ref, dev, wm_hint))),
+    # conv_gemm6 (one wave per SIMD on the 16x16x32 MFMA) where the library rates its tile fill -- not for couts filling only half of the padded
+    # rows (convf2's 64 of 128: 50 us instead of 63 + 117 us of K-sliced launch + reduce, but on the side stream it takes whole CUs from convc2:
+    # 35.5 vs 35.4 ms per clip)
+    Kernel(CONV6, CONV6, "conv_gemm6", _packing.pack_conv6, 32, True, _rows_conv6, lo_steps=2,
+           accepts=lambda lib, d: _fills_half(d) and lib.ppms_conv_gemm6_applicable(C.byref(d)) == 1,
+           bind=lambda lib, ref, dev, wm_hint, nslice, ws: (lib.ppms_conv_gemm6, (ref, dev))),
+    # conv_gemm5 (one 8-wave workgroup per CU, weights in MFMA-fragment order) where it serves the map, same fill rule (convf2 on it: 78 us instead
+    # of 65 + 143 us, clip time unchanged, 40.8 ms); K-sliced only on the caller's request
+    Kernel(CONV5, CONV5, "conv_gemm5", _packing.pack_conv5, 16, True, _rows_conv5, lo_steps=1,
+           accepts=lambda lib, d: _fills_half(d) and bool(lib.ppms_conv_gemm5_applicable(C.byref(d))),
+           slices=lambda lib, ref, wm_hint, nslice: int(nslice) if nslice is not None and nslice > 1 else 1,
+           bind=lambda lib, ref, dev, wm_hint, nslice, ws: (lib.ppms_conv_gemm5_sliced, (ref, dev, wm_hint, nslice, ws)) if nslice > 1 else
+                                                            (lib.ppms_conv_gemm5, (ref, dev, wm_hint))),
+    # (kt, kh, 1) convs the faster kernels do not take: conv_gemm2 with one y-swept window for all taps of a (dt, chunk), when the halo'd window fits
+    Kernel(CONV2_SWEPT, CONV2, "conv_gemm2", _packing.pack_conv2, 32, True,
+           rows=lambda s: s.m2 if s.taps[1] > 1 and s.taps[2] == 1 else None,
+           accepts=lambda lib, d: d.kh > 1 and d.kw == 1 and lib.ppms_conv_gemm2_ysweep_slices(C.byref(d)) > 0,
+           slices=_slices_conv2("ppms_conv_gemm2_ysweep_slices"),
+           bind=lambda lib, ref, dev, wm_hint, nslice, ws: (lib.ppms_conv_gemm2_ysweep, (ref, dev, nslice, ws))),
+    # conv_gemm2 (implicit GEMM through LDS) serves every conv: always packed, optionally K-sliced (+ a reduce launch)
+    Kernel(CONV2, CONV2, "conv_gemm2", _packing.pack_conv2, 32, False,
+           rows=lambda s: s.m2,
+           accepts=lambda lib, d: True,
+           slices=_slices_conv2("ppms_conv_gemm2_slices"),
+           bind=lambda lib, ref, dev, wm_hint, nslice, ws: (lib.ppms_conv_gemm2_sliced, (ref, dev, nslice, ws)) if nslice > 1 else
+                                                            (lib.ppms_conv_gemm2, (ref, dev, wm_hint))),
+)
+_BY_KEY = {k.key: k for k in KERNELS}
+KERNEL_NAMES = {k.id: k.name for k in KERNELS}
+ALL_KERNELS = frozenset(_BY_KEY)
+
+
+def kernel_record(version: int, ysweep: bool = False) -> Kernel:
+    """The record a ConvOp of this version launches through (ysweep: conv_gemm2's one-window form; no other kernel has one)."""
+    k = _BY_KEY[version]
+    return _BY_KEY[CONV2_SWEPT] if ysweep and k is _BY_KEY[CONV2] else k
+
+
 # ------------------------------------------------------------------------------------------------ packing
 def _pad32(c: int) -> int:
     return (c + 31) // 32 * 32
+
+
+def sweep_taps(kt: int, kh: int, kw: int) -> tuple:
+    """The tap shape of a sweep-ordered (kt, kh, kw) weight: the LAST axis is the swept one."""
+    return (kt, 1, kh * kw) if kh > 1 and kw > 1 else ((kt, kw, kh) if kh > 1 else (kt, kh, kw))
 
 
 def sweep_order(w5: torch.Tensor) -> torch.Tensor:
@@ -202,50 +295,42 @@ def sweep_order(w5: torch.Tensor) -> torch.Tensor:
     return w5
 
 
+def sweep_inverse(ws: torch.Tensor, taps) -> torch.Tensor:
+    """sweep_order undone: a (cout, cin, *sweep_taps(*taps)) weight back in its natural (cout, cin, kt, kh, kw) order."""
+    kt, kh, kw = taps
+    if kh > 1 and kw > 1:
+        return ws.reshape(*ws.shape[:2], kt, kh, kw)
+    if kh > 1:
+        return ws.transpose(3, 4)
+    return ws
+
+
 def pack_for(kernel, weight: torch.Tensor, bias: Optional[torch.Tensor], segs: Sequence[int], seg_pad: Optional[Sequence[int]] = None,
              cout_map: Optional[Sequence[int]] = None, m: Optional[int] = None) -> tuple:
     """ONE kernel's pack (packed, bias, meta) of a 4-D / 5-D weight: the layout function of packing.py, on the sweep-ordered weight for the
     swept kernels.  m: the padded cout rows (None: the layout's own default)."""
-    w5 = weight if weight.dim() == 5 else weight[:, :, None]
-    if kernel in (CONV5, CONV6, CONV2_SWEPT) and (w5.shape[3] > 1 or w5.shape[4] > 1):
-        weight = sweep_order(w5)
-    fn = {CONV2: _packing.pack_conv2, CONV2_SWEPT: _packing.pack_conv2, CONV5: _packing.pack_conv4, CONV6: _packing.pack_conv6,
-          GEMM1: _packing.pack_gemm1, STREAM: _packing.pack_stream}[kernel]
-    return fn(weight, bias, segs, seg_pad, cout_map, m)
+    k = _BY_KEY[kernel]
+    if k.swept:
+        weight = sweep_order(weight if weight.dim() == 5 else weight[:, :, None])
+    return k.layout(weight, bias, segs, seg_pad, cout_map, m)
 
 
 def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor], segs: Sequence[int], seg_pad: Optional[Sequence[int]] = None,
               cout_map: Optional[Sequence[int]] = None, m_pad: Optional[int] = None, kernels=ALL_KERNELS) -> Dict[object, tuple]:
     """kernel -> (packed, bias, meta) of every kernel in `kernels` that can serve a conv of this weight (2-D Linear (cout, cin), 4-D Conv2d or
-    5-D Conv3d).  segs: input channels per segment, each zero-padded to seg_pad (default: a multiple of 32); cout_map: the output row of each
-    cout; m_pad: conv_gemm2's padded rows (gemm1 / conv_stream use the same)."""
+    5-D Conv3d), and always conv_gemm2's.  segs: input channels per segment, each zero-padded to seg_pad (default: a multiple of 32);
+    cout_map: the output row of each cout; m_pad: conv_gemm2's padded rows (gemm1 / conv_stream use the same)."""
     if weight.dim() == 2:
         weight = weight[:, :, None, None]
     w5 = weight if weight.dim() == 5 else weight[:, :, None]
-    kt, kh, kw = w5.shape[2:]
     pads = list(seg_pad) if seg_pad is not None else [_pad32(c) for c in segs]
     rows = (max(cout_map) + 1) if cout_map is not None else w5.shape[0]
-    packs = {CONV2: pack_for(CONV2, weight, bias, segs, pads, cout_map, m_pad)}
-    m2 = packs[CONV2][2]["M"]
-    if GEMM1 in kernels and (kt, kh, kw) == (1, 1, 1) and sum(pads) % 64 == 0:
-        packs[GEMM1] = pack_for(GEMM1, weight, bias, segs, pads, cout_map, m2)
-    if STREAM in kernels and sum(pads) % 64 == 0:
-        packs[STREAM] = pack_for(STREAM, weight, bias, segs, pads, cout_map, m2)
-    if CONV2_SWEPT in kernels and kh > 1 and kw == 1:
-        packs[CONV2_SWEPT] = pack_for(CONV2_SWEPT, weight, bias, segs, pads, cout_map, m_pad)
-    # conv_gemm5 / conv_gemm6 deal 128, 192 (three 64-cout blocks: convc2's 192, final_conv's 190 couts) or 256 rows to their waves
-    m = 128 if rows <= 128 else (192 if rows <= 192 else 256)
-    swept, k32 = kh > 1 or kw > 1, all(p % 32 == 0 for p in pads)
-    # conv_gemm6 without a spatial sweep: its STREAM form, for the (kt,1,1) convs to 256 couts (the z/r conv of the GRU's pass T: 131 us against
-    # conv_gemm5's 155 at the 1/4 scale; the 128-cout q conv stays on conv_gemm2: 85 us against 89 there)
-    if CONV6 in kernels and k32 and (swept or (kt > 1 and rows > 128)):
-        packs[CONV6] = pack_for(CONV6, weight, bias, segs, pads, cout_map, m)
-    if CONV5 in kernels and swept:
-        packs[CONV5] = pack_for(CONV5, weight, bias, segs, pads, cout_map, m)
-    elif CONV5 in kernels and rows > 128 and k32:
-        # no spatial sweep: conv_gemm5's GEMM mode (windows of 64 channels), for > 128 couts only (GRU pass-T z/r 197 -> 164 us, mask_2d.2 62 -> 46 us
-        # at the 1/4 scale); with 128 couts the two K-groups get 32-channel windows, too short a DMA lookahead (pass-T q 110 -> 122 us, to_v 44 -> 66 us)
-        packs[CONV5] = pack_for(CONV5, weight, bias, segs, pads, cout_map, (rows + 127) // 128 * 128)
+    shape = _Shape(tuple(w5.shape[2:]), pads, rows, (rows + 63) // 64 * 64 if m_pad is None else m_pad)
+    packs = {}
+    for k in KERNELS:
+        m = k.rows(shape) if (k.key in kernels or k is _BY_KEY[CONV2]) else None
+        if m is not None:
+            packs[k.key] = pack_for(k.key, weight, bias, segs, pads, cout_map, m)
     return packs
 
 
@@ -276,47 +361,17 @@ def _with_pack(desc: L.Conv, pack: tuple, keep) -> tuple:
     return d, [packed, bias, *keep]
 
 
-def _fills_half(d: L.Conv) -> bool:
-    """The stored couts fill more than half of the padded rows."""
-    return 2 * (d.epi[0].n_valid + (d.epi[1].n_valid if d.m_split < d.M else 0)) > d.M
-
-
 def plan_conv(desc: L.Conv, packs: Dict[object, tuple], keep=(), nslice: Optional[int] = None, device=None) -> Optional[ConvOp]:
-    """The launch of `desc` (conv_desc) on the first kernel whose pack exists and which the library rates for it.  None when no pack serves
-    it (a caller without a conv_gemm2 pack).  nslice: conv_gemm2's K slices (None: the library's plan)."""
+    """The launch of `desc` (conv_desc) on the first kernel (in the order of KERNELS) whose pack exists and which accepts it.  None when no
+    pack serves it (a caller without a conv_gemm2 pack).  nslice: conv_gemm2's K slices (None: the library's plan)."""
     lib = L.load()
     if CONV2 in packs:
         meta = packs[CONV2][2]
         assert [desc.seg[i].c for i in range(desc.nseg)] == meta["seg_padded"], ([desc.seg[i].c for i in range(desc.nseg)], meta["seg_padded"])
         assert (desc.kt, desc.kh, desc.kw) == meta["taps"], ((desc.kt, desc.kh, desc.kw), meta["taps"])
-    # 1. 1x1 convs where the thin GEMM is rated faster (2: served, but the implicit GEMM is as fast on a map this large)
-    if GEMM1 in packs:
-        d, k = _with_pack(desc, packs[GEMM1], keep)
-        if lib.ppms_gemm1_applicable(C.byref(d)) == 1:
-            return ConvOp(d, k, GEMM1, device=device)
-    # 2. small maps (1/8, 1/16 scales): the register-streamed kernel where the library rates it faster -- no K slices, no reduce launch
-    if STREAM in packs:
-        d, k = _with_pack(desc, packs[STREAM], keep)
-        if lib.ppms_conv_stream_applicable(C.byref(d)) == 1:
-            return ConvOp(d, k, STREAM, device=device)
-    # 3. conv_gemm6 where the library rates its tile fill -- not for couts filling only half of the padded rows (convf2's 64 of 128: 50 us instead
-    #    of 63 + 117 us of K-sliced launch + reduce, but on the side stream it takes whole CUs from convc2: 35.5 vs 35.4 ms per clip)
-    if CONV6 in packs:
-        d, k = _with_pack(desc, packs[CONV6], keep)
-        if _fills_half(d) and lib.ppms_conv_gemm6_applicable(C.byref(d)) == 1:
-            return ConvOp(d, k, CONV6, device=device)
-    # 4. conv_gemm5 where it serves the map, same fill rule (convf2 on it: 78 us instead of 65 + 143 us, clip time unchanged, 40.8 ms)
-    if CONV5 in packs:
-        d, k = _with_pack(desc, packs[CONV5], keep)
-        if _fills_half(d) and lib.ppms_conv_gemm5_applicable(C.byref(d)):
-            return ConvOp(d, k, CONV5, device=device)
-    # 5. (kt, kh, 1) convs the faster kernels do not take: conv_gemm2 with one y-swept window for all taps of a (dt, chunk), when the halo'd window fits
-    if CONV2_SWEPT in packs and desc.kh > 1 and desc.kw == 1:
-        d, k = _with_pack(desc, packs[CONV2_SWEPT], keep)
-        if lib.ppms_conv_gemm2_ysweep_slices(C.byref(d)) > 0:
-            return ConvOp(d, k, CONV2, ysweep=True, device=device)
-    # 6. conv_gemm2: the library's K-slice plan (grid-level slicing of the small maps' convs) or the caller's
-    if CONV2 in packs:
-        d, k = _with_pack(desc, packs[CONV2], keep)
-        return ConvOp(d, k, CONV2, nslice=nslice, device=device)
+    for k in KERNELS:
+        if k.key in packs:
+            d, kept = _with_pack(desc, packs[k.key], keep)
+            if k.accepts(lib, d):
+                return ConvOp(d, kept, k.id, nslice=nslice if k is _BY_KEY[CONV2] else None, ysweep=k.ysweep, device=device)
     return None

@@ -25,7 +25,8 @@ import torch
 
 from ppmstereo_amd import _lib as L
 from ppmstereo_amd import packing as P
-from ppmstereo_amd.convplan import CONV2, CONV5, CONV6, GEMM1, KERNEL_NAMES, STREAM, ConvOp
+from ppmstereo_amd import convplan
+from ppmstereo_amd.convplan import CONV2, CONV5, CONV6, GEMM1, KERNEL_NAMES, STREAM, ConvOp, kernel_record, sweep_taps
 
 ACC_MAX = 3e-5      # per epilogue half: max |got - ref| <= ACC_MAX * max(1, max |ref|)  (the kernel tests' bound, tests/test_gpu_ops.py)
 ACC_RMS = 2e-5      # and rms(got - ref) <= ACC_RMS * rms(ref)
@@ -234,7 +235,17 @@ def bind_regions(d, pool: Pool, allowed_overlaps=()) -> (List[Region], List[str]
 
 # ------------------------------------------------------------------------------------------------ weights from the pack
 def swept(version: int, ysweep: bool, d) -> bool:
-    return (version in (CONV5, CONV6) or ysweep) and (d.kh > 1 or d.kw > 1)
+    return kernel_record(version, ysweep).swept and (d.kh > 1 or d.kw > 1)
+
+
+# the hand-written inverse of every layout (packing.py) as (packed, M, tap shape of the pack, chunks of the kernel's granule) -> fp32 [M][K]
+UNPACK = {
+    CONV2: lambda p, M, pt, n: P.unpack_conv2_reference(p, M, math.prod(pt) * n, pt, n),
+    CONV5: lambda p, M, pt, n: P.unpack_conv5_reference(p, M, math.prod(pt) * n, pt, n),
+    CONV6: lambda p, M, pt, n: P.unpack_conv6_reference(p, M, math.prod(pt) * n, pt, n),
+    GEMM1: lambda p, M, pt, n: P.unpack_gemm1_reference(p, M, n),
+    STREAM: lambda p, M, pt, n: P.unpack_stream_reference(p, M, math.prod(pt), n),
+}
 
 
 def unpack_weights(version: int, ysweep: bool, d, packed: torch.Tensor, sweep_inverse: bool = True) -> torch.Tensor:
@@ -246,26 +257,15 @@ def unpack_weights(version: int, ysweep: bool, d, packed: torch.Tensor, sweep_in
     taps = kt * kh * kw
     packed = packed.reshape(-1)
     assert packed.numel() == weight_elems(d)
-    sw = swept(version, ysweep, d) and sweep_inverse
-    pt = (kt, 1, kh * kw) if (sw and kh > 1 and kw > 1) else ((kt, kw, kh) if (sw and kh > 1) else (kt, kh, kw))
-    if version == CONV2:
-        wm = P.unpack_conv2_reference(packed, M, taps * K // 32, pt, K // 32)
-    elif version == CONV5:
-        wm = P.unpack_conv4_reference(packed, M, taps * K // 16, pt, K // 16)
-    elif version == CONV6:
-        wm = P.unpack_conv6_reference(packed, M, taps * K // 32, pt, K // 32)
-    elif version == GEMM1:
-        assert taps == 1
-        wm = P.unpack_gemm1_reference(packed, M, K // 16)
-    elif version == STREAM:
-        wm = P.unpack_stream_reference(packed, M, taps, K // 16)
-    else:
+    if version not in UNPACK:
         raise AuditError(f"unknown kernel version {version}")
+    sw = swept(version, ysweep, d) and sweep_inverse
+    pt = sweep_taps(kt, kh, kw) if sw else (kt, kh, kw)
+    assert version != GEMM1 or taps == 1
+    wm = UNPACK[version](packed, M, pt, K // kernel_record(version, ysweep).granule)
     w = wm.double().reshape(M, *pt, K).permute(0, 4, 1, 2, 3)          # (M, K, kt, pt1, pt2): the pack's own (sweep) order
-    if sw and kh > 1 and kw > 1:
-        w = w.reshape(M, K, kt, kh, kw)                                  # inverse of convplan.sweep_order: un-flatten (ky, kx)
-    elif sw and kh > 1:
-        w = w.transpose(3, 4)                                            # ... or swap kh / kw back
+    if sw:
+        w = convplan.sweep_inverse(w, (kt, kh, kw))
     return w.contiguous()
 
 

@@ -7,7 +7,8 @@ import torch.nn.functional as F
 
 from oracle import ppm_oracle as O
 from ppmstereo_amd import weights as Wm
-from ppmstereo_amd.packing import BK, pack_conv2, pack_conv4, unpack_conv2_reference, unpack_conv4_reference
+from ppmstereo_amd.convplan import sweep_inverse, sweep_order, sweep_taps
+from ppmstereo_amd.packing import BK, pack_conv2, pack_conv5, unpack_conv2_reference, unpack_conv5_reference
 from ppmstereo_amd.weights import hash_normal
 
 
@@ -59,7 +60,7 @@ def test_packing_reproduces_the_convolution(segs, cout, k3):
 @pytest.mark.parametrize("segs,cout,k3,m_pad", [([128, 384], 256, (1, 1, 15), None), ([48, 16], 190, (1, 3, 3), None), ([128], 256, (3, 3, 3), None),
                                                 ([64], 128, (1, 5, 1), None), ([48, 16], 190, (1, 3, 3), 192), ([32], 160, (1, 1, 5), 192)])
 def test_fragment_order_packing_reproduces_the_convolution(segs, cout, k3, m_pad):
-    """pack_conv4 (conv_gemm5.hip: weights in MFMA-fragment order, 16-channel k-steps, taps in sweep order) unpacks to the same
+    """pack_conv5 (conv_gemm5.hip: weights in MFMA-fragment order, 16-channel k-steps, taps in sweep order) unpacks to the same
     weight matrix: checked against F.conv3d, with the sweep-axis conventions the engine uses (y sweep: kh / kw swapped; 2-D
     sweep: (ky, kx) flattened into x)."""
     T, H, W = 2, 5, 6
@@ -69,22 +70,15 @@ def test_fragment_order_packing_reproduces_the_convolution(segs, cout, k3, m_pad
     wt = hash_normal((cout, cin, *k3), 20) / math.sqrt(cin * k3[0] * k3[1] * k3[2])
     bs = hash_normal((cout,), 21)
     kt, kh, kw = k3
-    sweep = wt
-    if kh > 1 and kw > 1:
-        sweep = wt.reshape(cout, cin, kt, 1, kh * kw)
-    elif kh > 1:
-        sweep = wt.transpose(3, 4).contiguous()
+    sweep = sweep_order(wt)
     seg_pad = [((c + 15) // 16) * 16 for c in segs]
-    packed, bias, meta = pack_conv4(sweep, bs, segs, seg_pad, None, m_pad)            # (m_pad 192: conv_gemm5's three-cout-block layout)
+    packed, bias, meta = pack_conv5(sweep, bs, segs, seg_pad, None, m_pad)            # (m_pad 192: conv_gemm5's three-cout-block layout)
     assert packed.dtype == torch.bfloat16 and meta["M"] == (m_pad or (cout + 127) // 128 * 128) and packed.numel() == 2 * meta["M"] * meta["nk"] * 16
-    Wm_ = unpack_conv4_reference(packed, meta["M"], meta["nk"], meta["taps"], meta["cpad"] // 16)      # [M][taps of the packed view * cpad]
+    Wm_ = unpack_conv5_reference(packed, meta["M"], meta["nk"], meta["taps"], meta["cpad"] // 16)      # [M][taps of the packed view * cpad]
     # bring the packed view's tap order back to (kz, ky, kx) of the true kernel
     cp = meta["cpad"]
-    Wv = Wm_.reshape(meta["M"], kt, meta["taps"][1], meta["taps"][2], cp)
-    if kh > 1 and kw > 1:
-        Wv = Wv.reshape(meta["M"], kt, kh, kw, cp)
-    elif kh > 1:
-        Wv = Wv.transpose(2, 3)
+    assert meta["taps"] == sweep_taps(*k3)
+    Wv = sweep_inverse(Wm_.reshape(meta["M"], *meta["taps"], cp).permute(0, 4, 1, 2, 3), k3).permute(0, 2, 3, 4, 1)     # [M][kz][ky][kx][ci]
     cols, xp = [], []
     for x, c_ in zip(xs, seg_pad):
         xp.append(F.pad(x, (0, c_ - x.shape[1])))

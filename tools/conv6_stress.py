@@ -7,8 +7,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 import ctypes as C
 import torch
 from ppmstereo_amd import _lib as L
-from ppmstereo_amd.engine import ConvOp, epilogue
-from ppmstereo_amd.packing import pack_conv4, pack_conv6
+from ppmstereo_amd.convplan import ConvOp, epilogue, pack_for
 from ppmstereo_amd.weights import hash_normal
 DEV = "cuda:0"
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 40
@@ -30,12 +29,7 @@ for name, segs, cout, k3 in cases:
         t.set_f32(hash_normal((P, t.channels), 100 + i).to(DEV))
     cin = sum(segs)
     wt = hash_normal((cout, cin, *k3), 200) / math.sqrt(cin * k3[0] * k3[1] * k3[2])
-    w5 = wt
-    if k3[1] > 1 and k3[2] > 1:
-        w5 = wt.reshape(cout, cin, k3[0], 1, k3[1] * k3[2])
-    elif k3[1] > 1:
-        w5 = wt.transpose(3, 4).contiguous()
-    packed, b, meta = (pack_conv6 if VER == 8 else pack_conv4)(w5.to(DEV), (hash_normal((cout,), 201) * 0.1).to(DEV), segs, segs, None, 128 if cout <= 128 else 192 if cout <= 192 else 256)
+    packed, b, meta = pack_for(VER, wt.to(DEV), (hash_normal((cout,), 201) * 0.1).to(DEV), segs, segs, None, 128 if cout <= 128 else 192 if cout <= 192 else 256)
     outs = [L.SPTensor(P, meta['M'], DEV) for _ in range(2)]
     ops = []
     for o in outs:

@@ -7,12 +7,12 @@ import collections, ctypes as C, hashlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from ppmstereo_amd import weights as Wm
+from ppmstereo_amd.convplan import KERNEL_NAMES as names
 from ppmstereo_amd.engine import ConvOp
 from ppmstereo_amd.ppmstereo import PPMStereoHotPath
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 T, H, W = (int(x) for x in args[:3]) if len(args) >= 3 else (5, 320, 512)
 dev = torch.device("cuda:0")
-names = {2: "conv_gemm2", 5: "conv_gemm5", 6: "gemm1", 7: "conv_stream", 8: "conv_gemm6"}
 
 
 def fields(s):
