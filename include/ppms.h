@@ -308,7 +308,7 @@ int ppms_video_ingest_u8(const uint8_t* left, const uint8_t* right, int64_t fram
  *   R = clamp((cy d + crv f + r) >> shift, 0, 255), G = clamp((cy d - cgu e - cgv f + r) >> shift, 0, 255), B = clamp((cy d + cbu e + r) >> shift, 0, 255)
  * (shift in [8, 20], y_off in [0, 255], coefficients in [0, 4 << shift): no sum leaves 32 bits).  From those bytes on -- lut, pads, H x W,
  * destinations, hi == NULL -- the call is ppms_video_ingest_u8 on channel order R, G, B.  The three structs are HOST memory, read before the
- * call returns; every pointer inside a view is a device pointer.  Not covered: 10-bit surfaces (P010), 4:2:2 / 4:4:4, interpolated chroma. */
+ * call returns; every pointer inside a view is a device pointer.  10- and 12-bit surfaces (P010 ...) and 4:2:2 / 4:4:4: ppms_video_ingest_yuv below. */
 typedef struct ppms_yuv_view {        /* one view's frames, as the decoder left them */
     const uint8_t *y, *u, *v;         /* sample (0,0) of frame 0; interleaved UV: v == u + 1 */
     int64_t frame_stride_y, frame_stride_c;   /* bytes from frame n to frame n + 1 */
@@ -358,6 +358,41 @@ int ppms_video_ingest_yuv420_remap(const ppms_yuv_view* left, const ppms_yuv_vie
                                    int N, int H0, int W0, int pad_left, int pad_top, int H, int W,
                                    const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream);
 int ppms_remap_struct_size(int* view);               /* sizeof(ppms_remap_view) (40): lets a binding verify its layout */
+/* ppms_video_ingest_yuv420 and its _remap twin for the other surfaces decoders deliver: 10- and 12-bit samples in little-endian 16-bit words
+ * (P010 / P012 / P210: bits at the top; yuv420p10le / yuv422p10le / yuv444p12le ...: bits at the bottom) and 4:2:2 / 4:4:4 chroma at any depth (NV16,
+ * yuv422p, yuv444p).  `fmt` (HOST memory, read before the call returns) says how to read the views; the views and the matrix are the structs above.
+ *   Samples and strides.  A sample is (word >> lsb) & ((1 << depth) - 1): with lsb = 16 - depth the low bits of the word are dropped whatever they
+ * hold, with lsb = 0 the high bits are masked.  Every stride of a view stays in BYTES; step_c = sample_bytes (planar) or 2 * sample_bytes
+ * (interleaved, v == u + sample_bytes); with sample_bytes = 2 every pointer, pitch and frame stride must be even.  The chroma planes hold
+ * ceil(H0 / 2^sub_y) x ceil(W0 / 2^sub_x) samples, and luma pixel (y, x) -- after the replicate-padding clamp -- takes chroma sample
+ * (y >> sub_y, x >> sub_x) (nearest; odd H0, W0 are legal).
+ *   Conversion.  The integer formula of ppms_video_ingest_yuv420 with e = U - (1 << (depth - 1)), f = V - (1 << (depth - 1)) and the results clamped
+ * to [0, 2^depth - 1]: RGB LEVELS of `depth` bits.  y_off in [0, 2^depth), shift in [8, 26 - depth], coefficients in [0, 4 << shift): no sum leaves
+ * 32 bits (three terms below 4 * 2^shift * 2^depth <= 2^28 each, plus the rounding term, stay below 2^31).
+ *   Level table.  lut is a device fp32 array of 1 << depth entries, indexed by the RGB level; from the levels on -- lut, pads, H x W, destinations,
+ * hi == NULL -- the call is ppms_video_ingest_u8.  With fmt = {1, 8, 0, 1, 1} it writes ppms_video_ingest_yuv420's bits.
+ *   _remap.  The remap contract above on the source's levels: a tap is the RGB level of that source pixel, the blend (sum w p + 512) >> 10 lies in
+ * [0, 2^depth - 1] without a clamp, and `fill` is a level in [0, 2^depth - 1].
+ *   Refused with PPMS_EINVAL before any launch: whatever ppms_video_ingest_yuv420 (_remap) refuses, restated for these samples; sample_bytes not 1
+ * or 2; a depth that does not go with it (8 with 1; 10 or 12 with 2); lsb not 0 or 16 - depth; (sub_x, sub_y) not (1,1), (1,0) or (0,0) -- (0,1)
+ * included; non-zero reserved; an odd pointer or stride with 16-bit samples; a pitch or frame stride too small for the sample size and the
+ * subsampling; shift, y_off or fill outside the bounds above.
+ * Not covered: interpolated chroma siting, 16-bit depth, packed formats (YUYV / Y210 / v210), BT.2020 and HDR transfer functions, high-depth RGB. */
+typedef struct ppms_yuv_format {
+    int32_t sample_bytes;             /* 1, or 2 (little-endian 16-bit words) */
+    int32_t depth;                    /* 8 with sample_bytes 1; 10 or 12 with sample_bytes 2 */
+    int32_t lsb;                      /* bit of the word that holds the sample's lowest bit: 0 (yuv420p10le ...) or 16 - depth (P010, P012, P210 ...); 0 for bytes */
+    int32_t sub_x, sub_y;             /* log2 chroma subsampling: (1,1) 4:2:0, (1,0) 4:2:2, (0,0) 4:4:4 */
+    int32_t reserved[3];              /* 0 */
+} ppms_yuv_format;
+int ppms_video_ingest_yuv(const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m, const ppms_yuv_format* fmt,
+                          int N, int H0, int W0, int pad_left, int pad_top, int H, int W,
+                          const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream);
+int ppms_video_ingest_yuv_remap(const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m, const ppms_yuv_format* fmt,
+                                const ppms_remap_view* lmap, const ppms_remap_view* rmap,
+                                int N, int H0, int W0, int pad_left, int pad_top, int H, int W,
+                                const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream);
+int ppms_yuv_format_struct_size(int* fmt);           /* sizeof(ppms_yuv_format) (32): lets a binding verify its layout */
 /* nn.InstanceNorm2d(affine=False) (extractor.py:326-329, 364): per (sample, channel) mean and 1 / sqrt(biased var + eps) over the
  * HW pixels of x (channel-last fp32 [N * HW][ld], a convolution's fp32 output) -> stats[N][C][2] (pixel slices merged in fixed
  * order: deterministic; caller-owned 16-B aligned workspace of ppms_instnorm_workspace_bytes); then

@@ -71,6 +71,11 @@ class YUVMatrix(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("y_off", "cy", "crv", "cgu", "cgv", "cbu", "shift", "reserved")]
 
 
+class YUVFormat(C.Structure):
+    """ppms_yuv_format: how ppms_video_ingest_yuv reads a view's samples (width, depth, alignment in the word, chroma subsampling)."""
+    _fields_ = [(n, C.c_int32) for n in ("sample_bytes", "depth", "lsb", "sub_x", "sub_y")] + [("reserved", C.c_int32 * 3)]
+
+
 class RemapView(C.Structure):
     """ppms_remap_view: one view's fixed-point rectification map (device pointers, pitch in map pixels, the source frame size)."""
     _fields_ = [("xy", c_void_p), ("frac", c_void_p), ("pitch", C.c_int32), ("hs", C.c_int32), ("ws", C.c_int32),
@@ -146,6 +151,11 @@ _SIGS = {
     "ppms_video_ingest_yuv420_remap": (c_int, [C.POINTER(YUVView), C.POINTER(YUVView), C.POINTER(YUVMatrix), C.POINTER(RemapView), C.POINTER(RemapView),
                                                c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, SP, SP, c_void_p]),
     "ppms_remap_struct_size": (c_int, [C.POINTER(c_int)]),
+    "ppms_video_ingest_yuv": (c_int, [C.POINTER(YUVView), C.POINTER(YUVView), C.POINTER(YUVMatrix), C.POINTER(YUVFormat), c_int, c_int, c_int, c_int, c_int,
+                                      c_int, c_int, c_void_p, SP, SP, c_void_p]),
+    "ppms_video_ingest_yuv_remap": (c_int, [C.POINTER(YUVView), C.POINTER(YUVView), C.POINTER(YUVMatrix), C.POINTER(YUVFormat), C.POINTER(RemapView),
+                                            C.POINTER(RemapView), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, SP, SP, c_void_p]),
+    "ppms_yuv_format_struct_size": (c_int, [C.POINTER(c_int)]),
     "ppms_dwconv": (c_int, [SP, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ppms_layernorm_any": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_float, SP, c_int64, c_int, c_void_p]),
     "ppms_grn_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
@@ -209,6 +219,9 @@ def load() -> C.CDLL:
     lib.ppms_remap_struct_size(C.byref(a))
     if a.value != C.sizeof(RemapView):
         raise RuntimeError("ppmstereo_amd: ctypes layout of ppms_remap_view differs from include/ppms.h")
+    lib.ppms_yuv_format_struct_size(C.byref(a))
+    if a.value != C.sizeof(YUVFormat):
+        raise RuntimeError("ppmstereo_amd: ctypes layout of ppms_yuv_format differs from include/ppms.h")
     if lib.ppms_egress_struct_size() != C.sizeof(Egress):
         raise RuntimeError("ppmstereo_amd: ctypes layout of ppms_egress differs from include/ppms.h")
     if lib.ppms_pwchain_param_bytes() != C.sizeof(ChainParams):

@@ -36,8 +36,9 @@ __global__ __launch_bounds__(256) void img_s2d_kernel(const float* __restrict__ 
     *(bf16x8*)((bf16_t*)dst.lo + od) = ol;
 }
 
-// decoded video -> the first-layer operands of both encoders in one launch (ppms_video_ingest_u8 / ppms_video_ingest_yuv420): what
-// normalisation (a 256-entry table the caller built with the float path's own torch expression), replicate padding (clamped source
+// decoded video -> the first-layer operands of both encoders in one launch (ppms_video_ingest_u8 / ppms_video_ingest_yuv420 / ppms_video_ingest_yuv):
+// what normalisation (a table the caller built with the float path's own torch expression: 256 entries, or 1 << depth for a source whose
+// table_by_depth is true, which also answers levels()), replicate padding (clamped source
 // coordinate), torch.cat([left, right]) and the two img_s2d launches produce from the fp32 images.  Thread = one output pixel x 8 channels
 // of one destination, as in img_s2d_kernel: indices [0, nf) serve the k = 2 operand of the 2 N images (left frames, then right frames),
 // [nf, total) the k = 4 operand of the N left frames.  Where a byte comes from is the Source: source(m, c, y, x) = channel c (R, G, B) of
@@ -46,6 +47,7 @@ struct rgb_planes_source {                                                // pla
     const uint8_t *left, *right;
     int64_t frame_stride;
     int N, H0, W0;
+    static constexpr bool table_by_depth = false;                         // RGB bytes: the kernel's static 256-entry table
     __device__ int operator()(int64_t m, int c, int y, int x) const {
         const uint8_t* src = m < N ? left + m * frame_stride : right + (m - N) * frame_stride;
         return src[((int64_t)c * H0 + y) * W0 + x];
@@ -56,6 +58,7 @@ struct yuv420_source {                                                    // pit
     ppms_yuv_view left, right;
     ppms_yuv_matrix mat;
     int N;
+    static constexpr bool table_by_depth = false;
     __device__ int operator()(int64_t m, int c, int y, int x) const {
         const bool r = m >= N;
         const int64_t n = r ? m - N : m;
@@ -71,6 +74,34 @@ struct yuv420_source {                                                    // pit
     }
 };
 
+// samples of T (bytes, or little-endian 16-bit words holding 10 or 12 bits) with any of the three chroma subsamplings (ppms_video_ingest_yuv):
+// yuv420_source's conversion on `depth`-bit samples, RGB levels in [0, 2^depth - 1].  Every stride of the views is in bytes, every offset 64-bit;
+// loads are of one T (rows have arbitrary pitches; the host checks that they are even for 16-bit samples).  A sample is masked to `depth` bits
+// and the result clamped, so the level is always an index inside the table of 1 << depth entries.
+template <class T>
+struct yuv_source {
+    ppms_yuv_view left, right;
+    ppms_yuv_matrix mat;
+    int N, depth, lsb, sub_x, sub_y;                                      // uniform: the ppms_yuv_format
+    static constexpr bool table_by_depth = true;
+    __host__ __device__ int levels() const { return 1 << depth; }
+    __device__ int sample(const uint8_t* p, int64_t o) const { return ((int)*(const T*)(p + o) >> lsb) & ((1 << depth) - 1); }
+    __device__ int operator()(int64_t m, int c, int y, int x) const {
+        const bool r = m >= N;
+        const int64_t n = r ? m - N : m;
+        const uint8_t *py = r ? right.y : left.y, *pu = r ? right.u : left.u, *pv = r ? right.v : left.v;
+        const int64_t oy = n * (r ? right.frame_stride_y : left.frame_stride_y) + (int64_t)y * (r ? right.pitch_y : left.pitch_y) + (int64_t)x * (int)sizeof(T);
+        const int64_t oc = n * (r ? right.frame_stride_c : left.frame_stride_c) + (int64_t)(y >> sub_y) * (r ? right.pitch_c : left.pitch_c) +
+                           (int64_t)(x >> sub_x) * (r ? right.step_c : left.step_c);  // nearest chroma sample of the clamped luma pixel
+        // the three channels of a pixel repeat these loads; they are the same addresses, and the compiler merges them
+        const int mid = 1 << (depth - 1), top = (1 << depth) - 1;
+        const int d = sample(py, oy) - mat.y_off, e = sample(pu, oc) - mid, f = sample(pv, oc) - mid;
+        const int acc = mat.cy * d + (c == 0 ? mat.crv * f : c == 1 ? -mat.cgu * e - mat.cgv * f : mat.cbu * e) + (1 << (mat.shift - 1));
+        const int q = acc >> mat.shift;                                   // arithmetic shift: floor
+        return q < 0 ? 0 : (q > top ? top : q);
+    }
+};
+
 // a source behind a rectification map (ppms_video_ingest_u8_remap / ppms_video_ingest_yuv420_remap; the arithmetic: include/ppms.h): (y, x) is a
 // pixel of the RECTIFIED frame, the view's map names its four taps in the inner source's frame of hs x ws, and the blend is integer.  Every
 // tap coordinate is clamped into that frame before the inner source sees it, whatever the map holds: in constant mode a tap outside the frame
@@ -80,6 +111,8 @@ struct remapped_source {
     Inner inner;                                                          // built with the source frame size
     ppms_remap_view left, right;
     int N;
+    static constexpr bool table_by_depth = Inner::table_by_depth;
+    __host__ __device__ int levels() const { return inner.levels(); }      // (asked of a table_by_depth source only)
     __device__ int operator()(int64_t m, int c, int y, int x) const {
         const bool r = m >= N;
         const int64_t o = (int64_t)y * (r ? right.pitch : left.pitch) + x;
@@ -97,15 +130,23 @@ struct remapped_source {
             const int p = border && outside ? fill : inner(m, c, cy, cx);
             acc += ((t & 1) ? fx : 32 - fx) * ((t >> 1) ? fy : 32 - fy) * p;
         }
-        return acc >> 10;                                                 // weights sum to 1024: in [0, 255]
+        return acc >> 10;                                                 // weights sum to 1024: in [0, the inner source's top level]
     }
 };
 
 template <class Source>
 __global__ __launch_bounds__(256) void video_ingest_kernel(Source source, int N, int H0, int W0, int pad_left, int pad_top, int H, int W,
                                                            const float* __restrict__ lut, ppms_sp dst_fnet, ppms_sp dst_cnet, int64_t nf, int64_t total) {
-    __shared__ float tab[256];
-    tab[threadIdx.x] = lut[threadIdx.x];
+    const float* tab;
+    if constexpr (Source::table_by_depth) {                               // 1 << depth entries of dynamic LDS (sized by the launch): every thread fills
+        extern __shared__ float level_tab[];                              // its stride of the table, and leaves only behind the barrier
+        for (int i = threadIdx.x, n = source.levels(); i < n; i += 256) level_tab[i] = lut[i];
+        tab = level_tab;
+    } else {
+        __shared__ float byte_tab[256];
+        byte_tab[threadIdx.x] = lut[threadIdx.x];
+        tab = byte_tab;
+    }
     __syncthreads();
     int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= total) return;
@@ -666,7 +707,9 @@ static int video_ingest_launch(const char* who, const Source& source, int N, int
     }
     const int64_t total = threads[0] + threads[1];
     PPMS_REQUIRE((total + 255) / 256 <= 0x7fffffff, "%s: %lld threads exceed one grid", who, (long long)total);
-    hipLaunchKernelGGL(video_ingest_kernel<Source>, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, source, N, H0, W0, pad_left, pad_top, H, W,
+    size_t table_bytes = 0;                                                // dynamic LDS: the level table of a source that sizes it by depth
+    if constexpr (Source::table_by_depth) table_bytes = sizeof(float) * (size_t)source.levels();
+    hipLaunchKernelGGL(video_ingest_kernel<Source>, dim3(ceil_div(total, 256)), dim3(256), table_bytes, (hipStream_t)stream, source, N, H0, W0, pad_left, pad_top, H, W,
                        lut, dst_fnet, dst_cnet, threads[0], total);
     return ppms_check_launch(who);
 }
@@ -722,13 +765,77 @@ extern "C" int ppms_video_ingest_yuv420(const ppms_yuv_view* left, const ppms_yu
     return video_ingest_launch("video_ingest_yuv420", yuv420_source{*left, *right, *m, N}, N, H0, W0, pad_left, pad_top, H, W, lut, dst_fnet, dst_cnet, stream);
 }
 
+extern "C" int ppms_yuv_format_struct_size(int* fmt) {
+    if (fmt) *fmt = (int)sizeof(ppms_yuv_format);
+    return PPMS_OK;
+}
+
+// what both ppms_video_ingest_yuv entry points check about the format, the views (frames of H0 x W0, named `hname` x `wname` in the messages)
+// and the matrix: everything yuv420_check refuses, restated for `sample_bytes`-wide samples of `depth` bits and the format's subsampling
+static int yuv_check(const char* who, const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m, const ppms_yuv_format* fmt,
+                     const float* lut, int N, int H0, int W0, const char* hname, const char* wname) {
+    PPMS_REQUIRE(left && right && m && fmt && lut, "%s: null view, matrix, format or table pointer", who);
+    PPMS_REQUIRE(N > 0 && H0 > 0 && W0 > 0, "%s: N = %d, %s = %d, %s = %d must be positive", who, N, hname, H0, wname, W0);
+    const ppms_yuv_format& f = *fmt;
+    const int sb = f.sample_bytes;
+    PPMS_REQUIRE(sb == 1 || sb == 2, "%s: sample_bytes = %d must be 1 or 2", who, sb);
+    PPMS_REQUIRE(sb == 1 ? f.depth == 8 : (f.depth == 10 || f.depth == 12),
+                 "%s: depth = %d does not go with sample_bytes = %d (8 with 1; 10 or 12 with 2)", who, f.depth, sb);
+    PPMS_REQUIRE(f.lsb == 0 || (sb == 2 && f.lsb == 16 - f.depth), "%s: lsb = %d must be 0, or 16 - depth for 16-bit words", who, f.lsb);
+    PPMS_REQUIRE((f.sub_x == 1 && f.sub_y == 1) || (f.sub_x == 1 && f.sub_y == 0) || (f.sub_x == 0 && f.sub_y == 0),
+                 "%s: sub_x = %d, sub_y = %d must be (1, 1) 4:2:0, (1, 0) 4:2:2 or (0, 0) 4:4:4", who, f.sub_x, f.sub_y);
+    PPMS_REQUIRE(f.reserved[0] == 0 && f.reserved[1] == 0 && f.reserved[2] == 0, "%s: format: reserved must be 0", who);
+    const int Hc = (H0 + (1 << f.sub_y) - 1) >> f.sub_y, Wc = (W0 + (1 << f.sub_x) - 1) >> f.sub_x;      // chroma planes: ceil(H0 / 2^sub_y) x ceil(W0 / 2^sub_x)
+    const ppms_yuv_view* views[2] = {left, right};
+    for (int s = 0; s < 2; ++s) {
+        const ppms_yuv_view& v = *views[s];
+        const char* side = s == 0 ? "left" : "right";
+        PPMS_REQUIRE(v.y && v.u && v.v, "%s: null plane pointer in the %s view", who, side);
+        PPMS_REQUIRE(v.step_c == sb || v.step_c == 2 * sb, "%s: %s step_c = %d must be %d (planar) or %d (interleaved)", who, side, v.step_c, sb, 2 * sb);
+        PPMS_REQUIRE(v.reserved == 0, "%s: %s view: reserved = %d must be 0", who, side, v.reserved);
+        if (sb == 2)
+            PPMS_REQUIRE((((uintptr_t)v.y | (uintptr_t)v.u | (uintptr_t)v.v | (uintptr_t)v.frame_stride_y | (uintptr_t)v.frame_stride_c | (uintptr_t)v.pitch_y |
+                           (uintptr_t)v.pitch_c) & 1) == 0,
+                         "%s: %s view: an odd pointer or stride; 16-bit samples need even pointers, pitches and frame strides", who, side);
+        const int64_t row_y = (int64_t)W0 * sb, row_c = (int64_t)v.step_c * (Wc - 1) + sb;     // bytes from a row's first sample to the end of its last
+        PPMS_REQUIRE(v.pitch_y >= row_y, "%s: %s pitch_y = %d is less than a luma row's %lld bytes (%s = %d)", who, side, v.pitch_y, (long long)row_y, wname, W0);
+        PPMS_REQUIRE(v.pitch_c >= row_c, "%s: %s pitch_c = %d is less than a chroma row's %lld bytes", who, side, v.pitch_c, (long long)row_c);
+        PPMS_REQUIRE(v.frame_stride_y >= (int64_t)(H0 - 1) * v.pitch_y + row_y, "%s: %s frame_stride_y = %lld is less than a luma plane", who, side,
+                     (long long)v.frame_stride_y);
+        PPMS_REQUIRE(v.frame_stride_c >= (int64_t)(Hc - 1) * v.pitch_c + row_c, "%s: %s frame_stride_c = %lld is less than a chroma plane", who, side,
+                     (long long)v.frame_stride_c);
+    }
+    PPMS_REQUIRE(m->shift >= 8 && m->shift <= 26 - f.depth, "%s: shift = %d must lie in [8, %d] at depth %d", who, m->shift, 26 - f.depth, f.depth);
+    PPMS_REQUIRE(m->reserved == 0, "%s: matrix: reserved = %d must be 0", who, m->reserved);
+    // coefficients below 4.0 keep every sum of the conversion inside 32 bits: three terms below 4 * 2^shift * 2^depth <= 2^28 each, plus 2^(shift - 1)
+    const int32_t lim = 4 << m->shift;
+    PPMS_REQUIRE(m->y_off >= 0 && m->y_off < (1 << f.depth) && m->cy >= 0 && m->cy < lim && m->crv >= 0 && m->crv < lim && m->cgu >= 0 && m->cgu < lim &&
+                     m->cgv >= 0 && m->cgv < lim && m->cbu >= 0 && m->cbu < lim,
+                 "%s: y_off must lie in [0, %d] and every coefficient in [0, 4 << shift)", who, (1 << f.depth) - 1);
+    return PPMS_OK;
+}
+
+template <class T>
+static yuv_source<T> make_yuv_source(const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m, const ppms_yuv_format* f, int N) {
+    return yuv_source<T>{*left, *right, *m, N, f->depth, f->lsb, f->sub_x, f->sub_y};
+}
+
+extern "C" int ppms_video_ingest_yuv(const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m, const ppms_yuv_format* fmt, int N, int H0,
+                                     int W0, int pad_left, int pad_top, int H, int W, const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream) {
+    const char* who = "video_ingest_yuv";
+    if (const int rc = yuv_check(who, left, right, m, fmt, lut, N, H0, W0, "H0", "W0")) return rc;
+    if (fmt->sample_bytes == 1)
+        return video_ingest_launch(who, make_yuv_source<uint8_t>(left, right, m, fmt, N), N, H0, W0, pad_left, pad_top, H, W, lut, dst_fnet, dst_cnet, stream);
+    return video_ingest_launch(who, make_yuv_source<uint16_t>(left, right, m, fmt, N), N, H0, W0, pad_left, pad_top, H, W, lut, dst_fnet, dst_cnet, stream);
+}
+
 extern "C" int ppms_remap_struct_size(int* view) {
     if (view) *view = (int)sizeof(ppms_remap_view);
     return PPMS_OK;
 }
 
-// what both remap entry points check about the two maps of a W0 columns wide rectified frame
-static int remap_check(const char* who, const ppms_remap_view* lmap, const ppms_remap_view* rmap, int W0) {
+// what the remap entry points check about the two maps of a W0 columns wide rectified frame (`fill_max`: the top level of the source's samples)
+static int remap_check(const char* who, const ppms_remap_view* lmap, const ppms_remap_view* rmap, int W0, int fill_max = 255) {
     PPMS_REQUIRE(lmap && rmap, "%s: null map pointer (lmap, rmap)", who);
     const ppms_remap_view* maps[2] = {lmap, rmap};
     for (int s = 0; s < 2; ++s) {
@@ -739,7 +846,7 @@ static int remap_check(const char* who, const ppms_remap_view* lmap, const ppms_
         PPMS_REQUIRE(v.hs >= 1 && v.hs <= 32768 && v.ws >= 1 && v.ws <= 32768, "%s: %s source frame hs = %d, ws = %d must lie in [1, 32768]", who, side,
                      v.hs, v.ws);
         PPMS_REQUIRE(v.border == 0 || v.border == 1, "%s: %s border = %d must be 0 (replicate) or 1 (constant)", who, side, v.border);
-        PPMS_REQUIRE(v.fill >= 0 && v.fill <= 255, "%s: %s fill = %d must lie in [0, 255]", who, side, v.fill);
+        PPMS_REQUIRE(v.fill >= 0 && v.fill <= fill_max, "%s: %s fill = %d must lie in [0, %d]", who, side, v.fill, fill_max);
         PPMS_REQUIRE(v.reserved == 0, "%s: %s reserved = %d must be 0", who, side, v.reserved);
         PPMS_REQUIRE(((uintptr_t)v.xy & 3) == 0 && ((uintptr_t)v.frac & 1) == 0, "%s: %s misaligned pointer: xy needs 4 bytes, frac 2", who, side);
     }
@@ -767,6 +874,22 @@ extern "C" int ppms_video_ingest_yuv420_remap(const ppms_yuv_view* left, const p
     if (const int rc = remap_check(who, lmap, rmap, W0)) return rc;
     if (const int rc = yuv420_check(who, left, right, m, lut, N, lmap->hs, lmap->ws, "hs", "ws")) return rc;
     const remapped_source<yuv420_source> source{yuv420_source{*left, *right, *m, N}, *lmap, *rmap, N};
+    return video_ingest_launch(who, source, N, H0, W0, pad_left, pad_top, H, W, lut, dst_fnet, dst_cnet, stream);
+}
+
+extern "C" int ppms_video_ingest_yuv_remap(const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m, const ppms_yuv_format* fmt,
+                                           const ppms_remap_view* lmap, const ppms_remap_view* rmap, int N, int H0, int W0, int pad_left, int pad_top, int H,
+                                           int W, const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream) {
+    const char* who = "video_ingest_yuv_remap";
+    // `fill` is a level of the format's depth (a format that names no depth is refused right behind the maps, which bound hs and ws for that check)
+    const int top = fmt && (fmt->depth == 10 || fmt->depth == 12) ? (1 << fmt->depth) - 1 : 255;
+    if (const int rc = remap_check(who, lmap, rmap, W0, top)) return rc;
+    if (const int rc = yuv_check(who, left, right, m, fmt, lut, N, lmap->hs, lmap->ws, "hs", "ws")) return rc;
+    if (fmt->sample_bytes == 1) {
+        const remapped_source<yuv_source<uint8_t>> source{make_yuv_source<uint8_t>(left, right, m, fmt, N), *lmap, *rmap, N};
+        return video_ingest_launch(who, source, N, H0, W0, pad_left, pad_top, H, W, lut, dst_fnet, dst_cnet, stream);
+    }
+    const remapped_source<yuv_source<uint16_t>> source{make_yuv_source<uint16_t>(left, right, m, fmt, N), *lmap, *rmap, N};
     return video_ingest_launch(who, source, N, H0, W0, pad_left, pad_top, H, W, lut, dst_fnet, dst_cnet, stream);
 }
 

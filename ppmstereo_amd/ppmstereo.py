@@ -20,7 +20,7 @@ from .corr import CorrBlock1D
 from .engine import bilinear
 from .update import Attention_qk, SequenceUpdateBlock3D
 from .video import (InputPadder, OutputSpec, RectifyMap, StereoRectifier, YUVFrames, YUVStereoVideo, byte_lut, egress_plan,  # noqa: F401  (the public names are
-                    shard_windows, window_plan, yuv_matrix)                                                                 #  importable from here as before)
+                    level_lut, shard_windows, window_plan, yuv_matrix)                                                                 #  importable from here as before)
 from .video import _ByteSource, _EgressCall, stereo_source
 
 
@@ -556,10 +556,10 @@ class PPMStereo(PPMStereoHotPath):
         cascade; b > 1: the reference's glue around the batched forward_update_block).  The two views are (``video.stereo_source``)
           float tensors, as in the reference; or
           uint8 tensors: the bits of ``forward(image1.float(), image2.float())``; or
-          two ``YUVFrames`` on the device (decoded 4:2:0 frames, NV12 / I420; b = 1, T = their frame count): the bits of ``forward`` on their
-          ``to_rgb_u8()``; or
+          two ``YUVFrames`` on the device (decoded frames of 8, 10 or 12 bits, 4:2:0 / 4:2:2 / 4:4:4: NV12, I420, P010, NV16 ...; b = 1, T = their
+          frame count): the bits of ``forward`` on their ``to_float()`` (8-bit frames: on their ``to_rgb_u8()``); or
           with rectify (a ``StereoRectifier``) the RAW frames of an unrectified rig, uint8 device tensors (1, T, 3, Hs, Ws) or ``YUVFrames`` of its
-          source size Hs x Ws: the bits of ``forward`` on ``RectifyMap.apply_u8`` of each view's RGB bytes.  H, W above are then the rectified size,
+          source size Hs x Ws: the bits of ``forward`` on ``RectifyMap.apply_u8`` of each view's RGB bytes (deep frames: ``apply_levels`` of their levels).  H, W above are then the rectified size,
           and so are the outputs'.  Float images raise TypeError (the remap reads decoded bytes), b > 1 NotImplementedError, another frame size
           than the maps' ValueError.
         Bytes reach this package's encoders through ONE ingest kernel; other encoder callables get the float video made of them on the device.
@@ -679,9 +679,10 @@ class PPMStereo(PPMStereoHotPath):
         """PPMStereo.forward_batch_test (ppmstereo.py:238-320): batch_dict["stereo_video"] (N, 2, 3, H, W) on the host;
         per window: InputPadder(divis_by=32), one host->device copy, forward(test_mode=True), unpad, one device->host copy;
         a uint8 video (host or device) is copied as bytes -- a quarter of the float video's: the same bits as for ``stereo_video.float()``;
-        a ``YUVStereoVideo`` (decoded 8-bit 4:2:0 frames, NV12 or I420, host or device) is copied per window as its planes -- 1.5 bytes per
-        pixel and view: the bits of the uint8 video of its ``to_rgb_u8()`` frames (10-bit formats, 4:2:2 / 4:4:4, interpolated chroma siting
-        and b > 1 are not covered).  With this package's encoders the bytes are converted, padded and normalised inside the one ingest launch;
+        a ``YUVStereoVideo`` (decoded frames, host or device) is copied per window as its planes -- 8-bit 4:2:0 (NV12, I420): 1.5 bytes per
+        pixel and view, 8-bit 4:2:2: 2, 8-bit 4:4:4 and P010: 3 -- and gives the bits of the float video of its ``to_float()`` frames (8-bit: of
+        the uint8 video of ``to_rgb_u8()``).  Not covered: interpolated chroma siting, 16-bit depth, packed formats (YUYV / Y210 / v210), BT.2020
+        and HDR transfer functions, high-depth RGB, b > 1.  With this package's encoders the bytes are converted, padded and normalised inside the one ingest launch;
         windows of ``kernel_size`` frames every ``kernel_size // 2``, centre frames kept (:296-307).  Windows whose output the
         reference computes and then drops are not run.  Returns {"disparity", "uncertainties"}: (N, 1, H, W) CPU tensors.
         shard_ranks: under torch.distributed the windows are dealt round-robin over the ranks (independent units, no data-path

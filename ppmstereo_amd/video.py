@@ -1,5 +1,5 @@
 """Video in and out of the model: what ``PPMStereo.forward`` / ``forward_batch_test`` accept beside the reference's float tensors (uint8 and decoded
-YUV 4:2:0 frames, raw frames with a ``StereoRectifier``), the one private family of sources that stands for all of them behind the front doors
+YUV frames of 8, 10 or 12 bits with 4:2:0 / 4:2:2 / 4:4:4 chroma, raw frames with a ``StereoRectifier``), the one private family of sources that stands for all of them behind the front doors
 (``stereo_source``), the output planes they can hand back (``OutputSpec``) and the sliding-window schedule.  Nothing here knows the model."""
 from __future__ import annotations
 
@@ -58,40 +58,90 @@ def byte_lut(device) -> torch.Tensor:
     return _BYTE_LUT[idx]
 
 
+_LEVEL_LUT: Dict[tuple, torch.Tensor] = {}
+_DEPTHS = (8, 10, 12)
+
+
+def _check_depth(who: str, depth) -> int:
+    if depth not in _DEPTHS:
+        raise ValueError(f"{who}: depth = {depth!r}; one of {_DEPTHS}")
+    return int(depth)
+
+
+def level_lut(device, depth: int = 8) -> torch.Tensor:
+    """fp32 [2^depth] on `device`: the normalised value of every RGB level of ``depth`` bits, from the expressions a level meets on the float
+    path ON THE SAME DEVICE -- ``YUVFrames.to_float``'s ``level * (255.0 / (2^depth - 1))``, then ``forward``'s ``2 * (x / 255.0) - 1.0`` -- for
+    ``byte_lut``'s reason: the table is what makes the deep path the float path's bits.  Depth 8: ``byte_lut``'s tensor.  Kept per (device, depth)."""
+    depth = _check_depth("level_lut", depth)
+    if depth == 8:
+        return byte_lut(device)
+    device = torch.device(device)
+    idx = torch.cuda.current_device() if device.index is None else device.index
+    if (idx, depth) not in _LEVEL_LUT:
+        dev = torch.device("cuda", idx)
+        x = torch.arange(1 << depth, dtype=torch.float32, device=dev) * (255.0 / ((1 << depth) - 1))
+        _LEVEL_LUT[idx, depth] = (2 * (x / 255.0) - 1.0).contiguous()
+        torch.cuda.current_stream(dev).synchronize()             # later calls may read it from any stream
+    return _LEVEL_LUT[idx, depth]
+
+
+def _levels_to_float(levels: torch.Tensor, depth: int) -> torch.Tensor:
+    """RGB levels of ``depth`` bits -> the float32 video in [0, 255] that stands for them (depth 8: the bytes' values)."""
+    return levels.float() if depth == 8 else levels.float() * (255.0 / ((1 << depth) - 1))
+
+
 _YUV_STANDARDS = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}       # (Kr, Kb)
+_CHROMA = {"420": (1, 1), "422": (1, 0), "444": (0, 0)}                      # (sub_x, sub_y): log2 of the chroma subsampling
 
 
-def yuv_matrix(standard: str = "bt709", full_range: bool = False, shift: int = 14) -> L.YUVMatrix:
-    """The fixed-point YCbCr -> RGB conversion ppms_video_ingest_yuv420 applies (include/ppms.h), as its ``ppms_yuv_matrix``: Python
-    ``round()`` of the double-precision coefficients times 2^shift.  Limited range: Y in [16, 235], chroma in [16, 240]."""
+def yuv_matrix(standard: str = "bt709", full_range: bool = False, shift: int = 14, depth: int = 8) -> L.YUVMatrix:
+    """The fixed-point YCbCr -> RGB conversion ppms_video_ingest_yuv420 / ppms_video_ingest_yuv apply (include/ppms.h), as their
+    ``ppms_yuv_matrix``: Python ``round()`` of the double-precision coefficients times 2^shift.  Limited range at depth 8: Y in [16, 235], chroma
+    in [16, 240]; at depth d those bounds times 2^(d - 8), stretched to [0, 2^d - 1].  Not covered: "bt2020" (refused)."""
     if standard not in _YUV_STANDARDS:
         raise ValueError(f"yuv_matrix: standard {standard!r}; one of {sorted(_YUV_STANDARDS)}")
-    if not 8 <= shift <= 20:
-        raise ValueError(f"yuv_matrix: shift = {shift} must lie in [8, 20]")
+    depth = _check_depth("yuv_matrix", depth)
+    top_shift = 20 if depth == 8 else 26 - depth
+    if not 8 <= shift <= top_shift:
+        raise ValueError(f"yuv_matrix: shift = {shift} must lie in [8, {top_shift}]")
     kr, kb = _YUV_STANDARDS[standard]
     kg = 1.0 - kr - kb
-    sy, sc = (1.0, 1.0) if full_range else (255.0 / 219.0, 255.0 / 224.0)
+    maxv, up = (1 << depth) - 1, depth - 8
+    sy, sc = (1.0, 1.0) if full_range else (maxv / (219 << up), maxv / (224 << up))
     one = float(1 << shift)
-    return L.YUVMatrix(y_off=0 if full_range else 16, cy=round(sy * one), crv=round(sc * 2.0 * (1.0 - kr) * one),
+    return L.YUVMatrix(y_off=0 if full_range else 16 << up, cy=round(sy * one), crv=round(sc * 2.0 * (1.0 - kr) * one),
                        cgu=round(sc * 2.0 * kb * (1.0 - kb) / kg * one), cgv=round(sc * 2.0 * kr * (1.0 - kr) / kg * one),
                        cbu=round(sc * 2.0 * (1.0 - kb) * one), shift=shift, reserved=0)
 
 
 class YUVFrames:
-    """One view's N decoded 8-bit YUV 4:2:0 frames, as a decoder leaves them: ``y`` uint8 (N, H0, W0), ``u`` / ``v`` uint8
-    (N, ceil(H0 / 2), ceil(W0 / 2)).  Each may be a strided VIEW of a decoder surface -- a pitched plane, the two halves of an interleaved
+    """One view's N decoded YUV frames, as a decoder leaves them: ``y`` (N, H0, W0), ``u`` / ``v`` (N, ceil(H0 / 2), ceil(W0 / 2)) for
+    ``chroma="420"`` (the default), (N, H0, ceil(W0 / 2)) for "422", (N, H0, W0) for "444".  ``depth=8`` (the default): uint8 planes; ``depth`` 10 or 12:
+    ``torch.uint16`` planes whose words hold the sample at the top (``align="msb"``: P010 / P012 / P210; the low bits are dropped whatever they hold)
+    or at the bottom (``align="lsb"``: yuv420p10le ...; the high bits are masked).  Each may be a strided VIEW of a decoder surface -- a pitched plane, the two halves of an interleaved
     UV plane (``nv12``), one half of a frame that packs both views (``split_side_by_side`` / ``split_top_bottom``): the class reads
     ``data_ptr()`` and ``stride()`` and never copies.  ``y`` needs last-dimension stride 1; ``u`` and ``v`` equal strides with
-    last-dimension stride 1 (planar: I420 / yuv420p) or 2 (interleaved: NV12); anything else raises ValueError.  Luma pixel (y, x) takes
-    chroma sample (y >> 1, x >> 1); ``standard`` ("bt709" / "bt601") and ``full_range`` choose ``yuv_matrix``; ``to_rgb_u8`` is the
-    definition of the RGB bytes.  Not covered: 10-bit surfaces (P010), 4:2:2 and 4:4:4, interpolated chroma siting, b > 1."""
+    last-dimension stride 1 (planar: I420 / yuv420p) or 2 (interleaved: NV12); anything else raises ValueError.  Strides are read in elements
+    and kept in BYTES (``pitch_y`` ..., what ``ppms_yuv_view`` holds).  Luma pixel (y, x) takes chroma sample (y >> sub_y, x >> sub_x), nearest;
+    ``standard`` ("bt709" / "bt601") and ``full_range`` choose ``yuv_matrix``; ``to_rgb`` is the definition of the RGB levels (``to_rgb_u8``: of the
+    bytes at depth 8).  Not covered: interpolated chroma siting, 16-bit depth, packed formats (YUYV / Y210 / v210), BT.2020 and HDR transfer
+    functions, b > 1."""
 
-    def __init__(self, y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, standard: str = "bt709", full_range: bool = False):
+    def __init__(self, y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, standard: str = "bt709", full_range: bool = False, depth: int = 8,
+                 align: str = "msb", chroma: str = "420"):
+        depth = _check_depth("YUVFrames", depth)
+        if align not in ("msb", "lsb"):
+            raise ValueError(f"YUVFrames: align {align!r}; 'msb' or 'lsb'")
+        if chroma not in _CHROMA:
+            raise ValueError(f"YUVFrames: chroma {chroma!r}; one of {sorted(_CHROMA)}")
+        dtype, es = (torch.uint8, 1) if depth == 8 else (torch.uint16, 2)
         for name, t in (("y", y), ("u", u), ("v", v)):
-            if not torch.is_tensor(t) or t.dtype != torch.uint8 or t.dim() != 3:
-                raise ValueError(f"YUVFrames: {name} must be a uint8 tensor (N, rows, columns)")
+            if not torch.is_tensor(t) or t.dtype != dtype or t.dim() != 3:
+                raise ValueError(f"YUVFrames: {name} must be a {'uint8' if es == 1 else 'uint16'} tensor (N, rows, columns)" +
+                                 ("" if es == 1 else f" at depth {depth}"))
         n, h0, w0 = y.shape
-        hc, wc = (h0 + 1) // 2, (w0 + 1) // 2
+        sub_x, sub_y = _CHROMA[chroma]
+        hc, wc = (h0 + (1 << sub_y) - 1) >> sub_y, (w0 + (1 << sub_x) - 1) >> sub_x
         if n < 1 or h0 < 1 or w0 < 1:
             raise ValueError(f"YUVFrames: empty y plane {tuple(y.shape)}")
         if tuple(u.shape) != (n, hc, wc) or tuple(v.shape) != (n, hc, wc):
@@ -105,18 +155,23 @@ class YUVFrames:
             raise ValueError(f"YUVFrames: u and v must have equal strides, got {u.stride()} and {v.stride()}")
         if step not in (1, 2):
             raise ValueError(f"YUVFrames: chroma last-dimension stride {step}; 1 (planar) or 2 (interleaved) expected")
-        # a size-1 dimension's stride is arbitrary: the smallest the kernel accepts stands in for it
-        self.pitch_y = y.stride(1) if h0 > 1 else w0
-        self.pitch_c = u.stride(1) if hc > 1 else step * (wc - 1) + 1
-        self.step_c = step
-        self.frame_stride_y = y.stride(0) if n > 1 else (h0 - 1) * self.pitch_y + w0
-        self.frame_stride_c = u.stride(0) if n > 1 else (hc - 1) * self.pitch_c + step * (wc - 1) + 1
-        if (self.pitch_y < w0 or self.pitch_c < step * (wc - 1) + 1 or self.frame_stride_y < (h0 - 1) * self.pitch_y + w0
-                or self.frame_stride_c < (hc - 1) * self.pitch_c + step * (wc - 1) + 1):
+        if es == 2 and any(t.data_ptr() % 2 for t in (y, u, v)):
+            raise ValueError("YUVFrames: 16-bit planes must start at even addresses")
+        # a size-1 dimension's stride is arbitrary: the smallest the kernel accepts stands in for it (elements here, bytes below)
+        pitch_y = y.stride(1) if h0 > 1 else w0
+        pitch_c = u.stride(1) if hc > 1 else step * (wc - 1) + 1
+        frame_y = y.stride(0) if n > 1 else (h0 - 1) * pitch_y + w0
+        frame_c = u.stride(0) if n > 1 else (hc - 1) * pitch_c + step * (wc - 1) + 1
+        if (pitch_y < w0 or pitch_c < step * (wc - 1) + 1 or frame_y < (h0 - 1) * pitch_y + w0 or frame_c < (hc - 1) * pitch_c + step * (wc - 1) + 1):
             raise ValueError(f"YUVFrames: rows or frames overlap (y strides {y.stride()}, chroma strides {u.stride()})")
+        self.pitch_y, self.pitch_c, self.step_c = pitch_y * es, pitch_c * es, step * es
+        self.frame_stride_y, self.frame_stride_c = frame_y * es, frame_c * es
         yuv_matrix(standard)                                               # (refuses an unknown standard here)
         self.y, self.u, self.v, self.standard, self.full_range = y, u, v, standard, bool(full_range)
         self.n, self.height, self.width = n, h0, w0
+        self.depth, self.align, self.chroma, self.sample_bytes = depth, align, chroma, es
+        self.sub_x, self.sub_y = sub_x, sub_y
+        self.lsb = 16 - depth if (es == 2 and align == "msb") else 0        # bit of the word that holds the sample's lowest bit
 
     @classmethod
     def nv12(cls, y: torch.Tensor, uv: torch.Tensor, standard: str = "bt709", full_range: bool = False) -> "YUVFrames":
@@ -124,6 +179,34 @@ class YUVFrames:
         if not torch.is_tensor(uv) or uv.dim() != 4 or uv.shape[-1] != 2:
             raise ValueError("YUVFrames.nv12: uv must be (N, rows, columns, 2)")
         return cls(y, uv[..., 0], uv[..., 1], standard, full_range)
+
+    @classmethod
+    def nv16(cls, y: torch.Tensor, uv: torch.Tensor, standard: str = "bt709", full_range: bool = False) -> "YUVFrames":
+        """NV16: 8-bit 4:2:2, ``uv`` uint8 (N, H0, ceil(W0 / 2), 2), U first -- what an MJPEG decoder leaves."""
+        return cls._interleaved("nv16", y, uv, standard, full_range, 8, "422")
+
+    @classmethod
+    def p010(cls, y: torch.Tensor, uv: torch.Tensor, standard: str = "bt709", full_range: bool = False) -> "YUVFrames":
+        """P010: 10-bit 4:2:0 in 16-bit words, the sample in the top 10 bits; ``uv`` uint16 (N, ceil(H0 / 2), ceil(W0 / 2), 2), U first -- a
+        hardware decoder's HEVC / AV1 Main10 surface."""
+        return cls._interleaved("p010", y, uv, standard, full_range, 10, "420")
+
+    @classmethod
+    def p210(cls, y: torch.Tensor, uv: torch.Tensor, standard: str = "bt709", full_range: bool = False) -> "YUVFrames":
+        """P210: P010's words with 4:2:2 chroma; ``uv`` uint16 (N, H0, ceil(W0 / 2), 2)."""
+        return cls._interleaved("p210", y, uv, standard, full_range, 10, "422")
+
+    @classmethod
+    def _interleaved(cls, name, y, uv, standard, full_range, depth, chroma) -> "YUVFrames":
+        if not torch.is_tensor(uv) or uv.dim() != 4 or uv.shape[-1] != 2:
+            raise ValueError(f"YUVFrames.{name}: uv must be (N, rows, columns, 2)")
+        return cls(y, uv[..., 0], uv[..., 1], standard, full_range, depth, "msb", chroma)
+
+    @classmethod
+    def planar(cls, y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, depth: int = 8, chroma: str = "420", align: str = "lsb",
+               standard: str = "bt709", full_range: bool = False) -> "YUVFrames":
+        """Three planes of any covered depth and subsampling -- a software decoder's yuv420p10le / yuv422p10le / yuv444p12le / yuv422p / yuv444p."""
+        return cls(y, u, v, standard, full_range, depth, align, chroma)
 
     @classmethod
     def i420(cls, y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, standard: str = "bt709", full_range: bool = False) -> "YUVFrames":
@@ -138,7 +221,7 @@ class YUVFrames:
         return self.y.device
 
     def _like(self, y, u, v) -> "YUVFrames":
-        return YUVFrames(y, u, v, self.standard, self.full_range)
+        return YUVFrames(y, u, v, self.standard, self.full_range, self.depth, self.align, self.chroma)
 
     def __getitem__(self, frames: slice) -> "YUVFrames":
         if not isinstance(frames, slice):
@@ -147,59 +230,76 @@ class YUVFrames:
 
     def split_side_by_side(self):
         """(left, right): the two halves of frames that pack both views side by side; views, no copy.  The packed width must be even --
-        and each half's too, or the right half's chroma would start between two samples."""
+        and with subsampled chroma each half's too, or the right half's chroma would start between two samples."""
         w = self.width
-        if w % 2 or (w // 2) % 2:
+        if w % 2 or (w // 2) % (1 << self.sub_x):
             raise ValueError(f"YUVFrames.split_side_by_side: a packed width of {w} does not split into two views with whole chroma samples")
-        h, q = w // 2, w // 4
+        h, q = w // 2, (w // 2) >> self.sub_x
         return (self._like(self.y[:, :, :h], self.u[:, :, :q], self.v[:, :, :q]), self._like(self.y[:, :, h:], self.u[:, :, q:], self.v[:, :, q:]))
 
     def split_top_bottom(self):
         """(left, right) = (top, bottom) halves of frames that pack both views one above the other; views, no copy (even halves, as above)."""
         ht = self.height
-        if ht % 2 or (ht // 2) % 2:
+        if ht % 2 or (ht // 2) % (1 << self.sub_y):
             raise ValueError(f"YUVFrames.split_top_bottom: a packed height of {ht} does not split into two views with whole chroma rows")
-        h, q = ht // 2, ht // 4
+        h, q = ht // 2, (ht // 2) >> self.sub_y
         return (self._like(self.y[:, :h], self.u[:, :q], self.v[:, :q]), self._like(self.y[:, h:], self.u[:, q:], self.v[:, q:]))
 
     def to(self, device) -> "YUVFrames":
-        """These frames on ``device``: the planes' own bytes are copied (1.5 per pixel; an interleaved UV plane as one block) into dense
-        planes; frames already there are returned as they are."""
+        """These frames on ``device``: the planes' own bytes are copied (8-bit 4:2:0: 1.5 per pixel, 4:2:2: 2, 4:4:4: 3; twice that for 16-bit
+        samples; an interleaved UV plane as one block) into dense planes; frames already there are returned as they are."""
         device = torch.device(device)
         if device.type == "cuda" and device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
         if self.device == device:
             return self
         y = self.y.to(device)
-        if self.step_c == 2 and self.v.data_ptr() == self.u.data_ptr() + 1:
+        if self.step_c == 2 * self.sample_bytes and self.v.data_ptr() == self.u.data_ptr() + self.sample_bytes:
             uv = torch.as_strided(self.u, (*self.u.shape, 2), (*self.u.stride(), 1)).to(device)
             return self._like(y, uv[..., 0], uv[..., 1])
         return self._like(y, self.u.to(device), self.v.to(device))
 
     def matrix(self) -> L.YUVMatrix:
-        return yuv_matrix(self.standard, self.full_range)
+        return yuv_matrix(self.standard, self.full_range, depth=self.depth)
+
+    def format_struct(self) -> L.YUVFormat:
+        """The ``ppms_yuv_format`` of these frames."""
+        return L.YUVFormat(self.sample_bytes, self.depth, self.lsb, self.sub_x, self.sub_y, (0, 0, 0))
 
     def view_struct(self) -> L.YUVView:
         """The ``ppms_yuv_view`` of these frames."""
         return L.YUVView(self.y.data_ptr(), self.u.data_ptr(), self.v.data_ptr(), self.frame_stride_y, self.frame_stride_c, self.pitch_y, self.pitch_c,
                          self.step_c, 0)
 
-    def to_rgb_u8(self) -> torch.Tensor:
-        """uint8 (N, 3, H0, W0) on the same device: the conversion of include/ppms.h in torch integer ops -- what the feature means by the
-        RGB bytes of these frames (the kernel's operands are ppms_video_ingest_u8's on them), and the path where the kernel cannot be used."""
+    def to_rgb(self) -> torch.Tensor:
+        """(N, 3, H0, W0) on the same device, uint8 at depth 8 and int16 levels in [0, 2^depth - 1] otherwise: the conversion of include/ppms.h in
+        torch integer ops -- what the feature means by the RGB levels of these frames (the kernels' operands are ppms_video_ingest_u8's on them,
+        with the table of that depth), and the path where the kernels cannot be used."""
         m = self.matrix()
-        rows = torch.arange(self.height, device=self.device) >> 1
-        cols = torch.arange(self.width, device=self.device) >> 1
-        d = self.y.to(torch.int32) - m.y_off
-        e, f = (c.to(torch.int32)[:, rows][:, :, cols] - 128 for c in (self.u, self.v))
+        top = (1 << self.depth) - 1
+        rows = torch.arange(self.height, device=self.device) >> self.sub_y
+        cols = torch.arange(self.width, device=self.device) >> self.sub_x
+        sample = lambda t: (t.to(torch.int32) >> self.lsb) & top
+        d = sample(self.y) - m.y_off
+        e, f = (sample(c)[:, rows][:, :, cols] - (1 << (self.depth - 1)) for c in (self.u, self.v))
         r = 1 << (m.shift - 1)
         rgb = torch.stack([m.cy * d + m.crv * f + r, m.cy * d - m.cgu * e - m.cgv * f + r, m.cy * d + m.cbu * e + r], dim=1)
-        return (rgb >> m.shift).clamp_(0, 255).to(torch.uint8)
+        return (rgb >> m.shift).clamp_(0, top).to(torch.uint8 if self.depth == 8 else torch.int16)
+
+    def to_rgb_u8(self) -> torch.Tensor:
+        """``to_rgb`` of 8-bit frames: uint8 (N, 3, H0, W0).  Deep frames have no RGB bytes (ValueError): their levels are ``to_rgb``'s."""
+        if self.depth != 8:
+            raise ValueError(f"YUVFrames.to_rgb_u8: the frames hold {self.depth}-bit samples; to_rgb() gives their levels, to_float() the float video")
+        return self.to_rgb()
+
+    def to_float(self) -> torch.Tensor:
+        """float32 (N, 3, H0, W0) in [0, 255]: ``levels.float() * (255.0 / (2^depth - 1))`` -- the video the reference would be given."""
+        return _levels_to_float(self.to_rgb(), self.depth)
 
 
 class YUVStereoVideo:
-    """Both views of a decoded 4:2:0 video -- what ``batch_dict["stereo_video"]`` of ``forward_batch_test`` may be instead of a tensor:
-    two ``YUVFrames`` of one size, frame count, device and colour description.  ``len()``, slicing by frame range, ``to(device)``."""
+    """Both views of a decoded YUV video -- what ``batch_dict["stereo_video"]`` of ``forward_batch_test`` may be instead of a tensor:
+    two ``YUVFrames`` of one size, frame count, device, colour description and sample format (depth, alignment, chroma subsampling).  ``len()``, slicing by frame range, ``to(device)``."""
 
     def __init__(self, left: YUVFrames, right: YUVFrames):
         if not isinstance(left, YUVFrames) or not isinstance(right, YUVFrames):
@@ -208,7 +308,11 @@ class YUVStereoVideo:
             raise ValueError(f"YUVStereoVideo: the views differ: {(left.n, left.height, left.width)} and {(right.n, right.height, right.width)}")
         if (left.standard, left.full_range) != (right.standard, right.full_range) or left.device != right.device:
             raise ValueError("YUVStereoVideo: both views need one standard, one range and one device")
+        if (left.depth, left.lsb, left.chroma) != (right.depth, right.lsb, right.chroma):
+            raise ValueError(f"YUVStereoVideo: the views differ in depth, alignment or chroma: {(left.depth, left.align, left.chroma)} and "
+                             f"{(right.depth, right.align, right.chroma)}")
         self.left, self.right = left, right
+        self.depth = left.depth
         self.height, self.width = left.height, left.width
 
     def __len__(self) -> int:
@@ -218,7 +322,7 @@ class YUVStereoVideo:
         return YUVStereoVideo(self.left[frames], self.right[frames])
 
     def to(self, device) -> "YUVStereoVideo":
-        """The selected frames' planes on ``device`` (1.5 bytes per pixel and view)."""
+        """The selected frames' planes on ``device`` (8-bit 4:2:0: 1.5 bytes per pixel and view; P010: 3)."""
         return YUVStereoVideo(self.left.to(device), self.right.to(device))
 
 
@@ -226,13 +330,13 @@ _BORDERS = {"replicate": L.BORDER_REPLICATE, "constant": L.BORDER_CONSTANT}
 
 
 class RectifyMap:
-    """One view's undistort + rectify (+ resize) map in fixed point, as ppms_video_ingest_u8_remap / _yuv420_remap read it (the arithmetic:
+    """One view's undistort + rectify (+ resize) map in fixed point, as ppms_video_ingest_u8_remap / _yuv420_remap / _yuv_remap read it (the arithmetic:
     include/ppms.h): for every pixel of the RECTIFIED frame H0 x W0, ``xy`` int16 (H0, W0, 2) holds the integer source coordinate (x0, y0), x
     first, and ``frac`` int16 or uint16 (H0, W0) its fraction in 1/32 pixel, fx | fy << 5 -- the layout OpenCV documents for
     ``convertMaps(..., CV_16SC2)`` (not compared with OpenCV).  ``source_size`` = (Hs, Ws) of the raw frames; ``border`` "replicate" or
-    "constant" (a tap outside the frame is ``fill``, one byte for R, G and B).  Both tensors may be row-pitched views with ONE pitch
-    (``xy.stride(0) == 2 * frac.stride(0)``): the class reads ``data_ptr()`` and ``stride()`` and never copies.  ``apply_u8`` is the definition
-    of the remap.  Not covered: computing maps from calibration data, interpolation other than bilinear."""
+    "constant" (a tap outside the frame is ``fill``, one byte for R, G and B; for sources of depth d its level ``level_fill(d)``).  Both tensors may be row-pitched views with ONE pitch
+    (``xy.stride(0) == 2 * frac.stride(0)``): the class reads ``data_ptr()`` and ``stride()`` and never copies.  ``apply_levels`` is the definition
+    of the remap (``apply_u8``: its depth-8 case).  Not covered: computing maps from calibration data, interpolation other than bilinear."""
 
     def __init__(self, xy: torch.Tensor, frac: torch.Tensor, source_size, border: str = "replicate", fill: int = 0, _checked: bool = False):
         if not torch.is_tensor(xy) or xy.dtype != torch.int16 or xy.dim() != 3 or xy.shape[2] != 2:
@@ -306,17 +410,34 @@ class RectifyMap:
             self._on[device] = there
         return self._on[device]
 
-    def view_struct(self) -> L.RemapView:
-        """The ``ppms_remap_view`` of this map."""
-        return L.RemapView(self.xy.data_ptr(), self.frac.data_ptr(), self.pitch, self.source_height, self.source_width, _BORDERS[self.border], self.fill, 0)
+    def level_fill(self, depth: int = 8) -> int:
+        """``fill`` as a level of ``depth`` bits: the byte's bits repeated below it, (fill << (d - 8)) | (fill >> (16 - d)) -- 0 stays 0, 255
+        becomes the top level."""
+        depth = _check_depth("RectifyMap.level_fill", depth)
+        return (self.fill << (depth - 8)) | (self.fill >> (16 - depth))
+
+    def view_struct(self, depth: int = 8) -> L.RemapView:
+        """The ``ppms_remap_view`` of this map for a source of ``depth`` bits."""
+        return L.RemapView(self.xy.data_ptr(), self.frac.data_ptr(), self.pitch, self.source_height, self.source_width, _BORDERS[self.border],
+                           self.level_fill(depth), 0)
 
     def apply_u8(self, rgb: torch.Tensor) -> torch.Tensor:
         """uint8 (N, 3, Hs, Ws) -> uint8 (N, 3, H0, W0) on ``rgb``'s device: the remap of include/ppms.h in torch integer ops -- what the feature
         means by the rectified bytes (the kernels' operands are ppms_video_ingest_u8's on them), and the path where the kernels cannot be used."""
+        return self._apply("apply_u8", rgb, 8)
+
+    def apply_levels(self, rgb: torch.Tensor, depth: int = 8) -> torch.Tensor:
+        """The same remap on RGB levels of ``depth`` bits as ``YUVFrames.to_rgb`` gives them (uint8 at depth 8, int16 otherwise), same dtype out:
+        a tap outside the frame is ``level_fill(depth)`` in constant mode, and the blend (sum w p + 512) >> 10 stays inside the levels."""
+        return self._apply("apply_levels", rgb, _check_depth("RectifyMap.apply_levels", depth))
+
+    def _apply(self, who: str, rgb: torch.Tensor, depth: int) -> torch.Tensor:
         hs, ws = self.source_height, self.source_width
-        if not torch.is_tensor(rgb) or rgb.dtype != torch.uint8 or rgb.dim() != 4 or tuple(rgb.shape[1:]) != (3, hs, ws):
-            raise ValueError(f"RectifyMap.apply_u8: uint8 frames (N, 3, {hs}, {ws}) expected, got "
+        dtype, name = (torch.uint8, "uint8") if depth == 8 else (torch.int16, "int16")
+        if not torch.is_tensor(rgb) or rgb.dtype != dtype or rgb.dim() != 4 or tuple(rgb.shape[1:]) != (3, hs, ws):
+            raise ValueError(f"RectifyMap.{who}: {name} frames (N, 3, {hs}, {ws}) expected, got "
                              f"{tuple(rgb.shape) if torch.is_tensor(rgb) else type(rgb).__name__}")
+        fill = self.level_fill(depth)
         m = self.to(rgb.device)
         x0, y0 = m.xy[..., 0].to(torch.int64), m.xy[..., 1].to(torch.int64)
         f = m.frac.to(torch.int32)
@@ -328,9 +449,9 @@ class RectifyMap:
                 cy, cx = yy.clamp(0, hs - 1), xx.clamp(0, ws - 1)
                 p = rgb[:, :, cy, cx].to(torch.int32)             # clamped addresses in both modes
                 if self.border == "constant":
-                    p = torch.where((cy != yy) | (cx != xx), torch.full_like(p, self.fill), p)
+                    p = torch.where((cy != yy) | (cx != xx), torch.full_like(p, fill), p)
                 acc += ((fx if dx else 32 - fx) * (fy if dy else 32 - fy)) * p
-        return (acc >> 10).to(torch.uint8)
+        return (acc >> 10).to(dtype)
 
 
 class StereoRectifier:
@@ -366,6 +487,9 @@ class StereoRectifier:
     def apply_u8(self, left: torch.Tensor, right: torch.Tensor):
         return self.left.apply_u8(left), self.right.apply_u8(right)
 
+    def apply_levels(self, left: torch.Tensor, right: torch.Tensor, depth: int = 8):
+        return self.left.apply_levels(left, depth), self.right.apply_levels(right, depth)
+
     def check_source(self, who: str, h: int, w: int) -> None:
         if (int(h), int(w)) != (self.source_height, self.source_width):
             raise ValueError(f"{who}: the frames are {int(h)} x {int(w)}, the rectification maps were made for {self.source_height} x {self.source_width}")
@@ -386,21 +510,22 @@ class _FloatViews:
 
 class _ByteSource:
     """Decoded bytes of both views, optionally the RAW frames of a ``StereoRectifier`` (``size`` is then its rectified size): with this package's
-    encoders ONE launch (``ingest``) rectifies, pads, normalises and lays out both encoders' first-layer operands; ``float_views`` is the path
+    encoders ONE launch (``ingest``) rectifies, pads, normalises (the level table of the source's ``depth``) and lays out both encoders' first-layer
+    operands; ``float_views`` is the path
     of other encoder callables.  The entry point and its ``_remap`` twin differ by the two maps in front of n: chosen here, once."""
 
-    def __init__(self, entry: str, n: int, frame_size, device, rectify: Optional[StereoRectifier], b: int = 1):
-        self.n, self.b, self.device, self.rectify = int(n), int(b), device, rectify
+    def __init__(self, entry: str, n: int, frame_size, device, rectify: Optional[StereoRectifier], b: int = 1, depth: int = 8):
+        self.n, self.b, self.device, self.rectify, self.depth = int(n), int(b), device, rectify, int(depth)
         if rectify is None:
             self.size, self._entry, self._maps, self._map_tensors = (int(frame_size[0]), int(frame_size[1])), entry, (), ()
         else:
             self.size, self._entry = (rectify.height, rectify.width), entry + "_remap"
-            self._maps, self._map_tensors = (rectify.left.view_struct(), rectify.right.view_struct()), rectify.tensors()
+            self._maps, self._map_tensors = (rectify.left.view_struct(depth), rectify.right.view_struct(depth)), rectify.tensors()
 
     def ingest(self, dst_fnet: L.SP, dst_cnet: L.SP, pad_left: int, pad_top: int, h: int, w: int) -> None:
         """One launch on the current stream: both encoders' first-layer operands of the n frames, ``pad_left`` / ``pad_top`` in front, h x w."""
         L.check(getattr(L.load(), self._entry)(*self._frames(), *self._maps, self.n, *self.size, pad_left, pad_top, h, w,
-                                               byte_lut(self.device).data_ptr(), dst_fnet, dst_cnet, L.stream_ptr()))
+                                               level_lut(self.device, self.depth).data_ptr(), dst_fnet, dst_cnet, L.stream_ptr()))
 
     def held(self):
         """The tensors the launch reads (for record_stream)."""
@@ -430,24 +555,28 @@ class _RGBBytes(_ByteSource):
 
 
 class _YUVPlanes(_ByteSource):
-    """A YUVStereoVideo: ppms_video_ingest_yuv420 converts the planes as the decoder left them."""
+    """A YUVStereoVideo: ppms_video_ingest_yuv420 (8-bit 4:2:0) or ppms_video_ingest_yuv (every other depth and subsampling, with the level table
+    of that depth) converts the planes as the decoder left them."""
 
     def __init__(self, video: YUVStereoVideo, rectify: Optional[StereoRectifier] = None):
-        super().__init__("ppms_video_ingest_yuv420", len(video), (video.height, video.width), video.left.device, rectify)
+        self._generic = (video.left.depth, video.left.chroma) != (8, "420")
+        super().__init__("ppms_video_ingest_yuv" if self._generic else "ppms_video_ingest_yuv420", len(video), (video.height, video.width),
+                         video.left.device, rectify, depth=video.left.depth)
         self.video = video
 
     def _frames(self):
         v = self.video
-        return v.left.view_struct(), v.right.view_struct(), v.left.matrix()      # host structs: read before the call returns
+        frames = v.left.view_struct(), v.right.view_struct(), v.left.matrix()    # host structs: read before the call returns
+        return frames + (v.left.format_struct(),) if self._generic else frames
 
     def _planes(self):
         v = self.video
         return v.left.y, v.left.u, v.left.v, v.right.y, v.right.u, v.right.v
 
     def float_views(self):
-        rgb = self.video.left.to_rgb_u8(), self.video.right.to_rgb_u8()
-        left, right = rgb if self.rectify is None else self.rectify.apply_u8(*rgb)
-        return left.float(), right.float()
+        rgb = self.video.left.to_rgb(), self.video.right.to_rgb()
+        left, right = rgb if self.rectify is None else self.rectify.apply_levels(*rgb, self.depth)
+        return _levels_to_float(left, self.depth), _levels_to_float(right, self.depth)
 
 
 def _checked_rectifier(who: str, rectify, device, h: int, w: int) -> StereoRectifier:
@@ -459,7 +588,8 @@ def _checked_rectifier(who: str, rectify, device, h: int, w: int) -> StereoRecti
 def stereo_source(who: str, left, right=None, rectify: Optional[StereoRectifier] = None):
     """The source of two views -- float or uint8 tensors (b, T, 3, H, W), or two ``YUVFrames`` -- or, with ``right`` None, of a window ``left`` of
     a video: a tensor (T, 2, 3, H, W) or a ``YUVStereoVideo``.  Every argument check of the front doors is made here, under the name ``who``,
-    and touches no device: rectify= reads decoded bytes (TypeError for float frames), of its source size (ValueError), b = 1."""
+    and touches no device: rectify= reads decoded bytes (TypeError for float frames), of its source size (ValueError), b = 1; two ``YUVFrames`` that
+    differ in depth, alignment or chroma subsampling are no stereo pair (ValueError)."""
     if rectify is not None and not isinstance(rectify, StereoRectifier):
         raise TypeError(f"{who}: rectify must be a StereoRectifier, got {type(rectify).__name__}")
     if isinstance(left, YUVFrames) or isinstance(right, YUVFrames):

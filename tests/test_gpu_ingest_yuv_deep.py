@@ -1,0 +1,378 @@
+"""GPU: the decoded-video front door for 10- / 12-bit samples and 4:2:2 / 4:4:4 chroma.  ppms_video_ingest_yuv (+ _remap) against the float path's
+own op chain (test_gpu_ingest_u8.float_path_operands) fed ``levels.float() * (255 / (2^depth - 1))`` of the levels that this file's own
+restatement of the conversion and of the remap (include/ppms.h; not YUVFrames.to_rgb / RectifyMap.apply_levels) gives -- bit-exact, both bf16
+planes as int16 -- and PPMStereo.forward / forward_batch_test on deep YUVFrames / a YUVStereoVideo against the same calls on that float video
+(torch.equal)."""
+import pytest
+import torch
+
+from ppmstereo_amd import _lib as L
+from ppmstereo_amd.ppmstereo import OutputSpec, RectifyMap, StereoRectifier, YUVFrames, YUVStereoVideo
+from test_gpu_block import DEV, W
+from test_gpu_ingest_u8 import bits, float_path_operands, ingest, model, patterned, rand_u8, same  # noqa: F401  (model: the fixture)
+from test_gpu_ingest_yuv import COMBOS, ingest_yuv, nv12_surfaces
+from test_gpu_ingest_remap import smooth_rectifier
+
+pytestmark = pytest.mark.gpu
+
+
+def rand_u16(shape, seed, top=1 << 16):
+    return torch.randint(0, top, shape, dtype=torch.int32, generator=torch.Generator().manual_seed(seed)).to(torch.uint16)
+
+
+# ---- the expectation: the conversion and the remap restated, then the float path ---------------------------------------------------------
+def restated_levels(frames: YUVFrames, shift=14):
+    """(N, 3, H0, W0) int64 levels of `frames` by the header's integer formula on int64 tensors: the sample cut out of its word by division and
+    remainder, coefficients rounded from doubles, every chroma sample repeated over its luma pixels, floor division by 2^shift."""
+    depth, top = frames.depth, 2 ** frames.depth - 1
+    low = {("msb", 10): 64, ("msb", 12): 16}.get((frames.align, depth), 1)                   # 2^lsb
+    sx, sy_ = {"420": (2, 2), "422": (2, 1), "444": (1, 1)}[frames.chroma]
+    kr, kb = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}[frames.standard]
+    kg = 1.0 - kr - kb
+    up = 2 ** (depth - 8)
+    sy, sc, y_off = (1.0, 1.0, 0) if frames.full_range else (top / (219.0 * up), top / (224.0 * up), 16 * up)
+    one = 2.0 ** shift
+    cy, crv, cbu = round(sy * one), round(sc * 2 * (1 - kr) * one), round(sc * 2 * (1 - kb) * one)
+    cgu, cgv = round(sc * 2 * kb * (1 - kb) / kg * one), round(sc * 2 * kr * (1 - kr) / kg * one)
+    H0, W0 = frames.height, frames.width
+    sample = lambda t: torch.div(t.to(torch.int32).long(), low, rounding_mode="floor") % (top + 1)
+    rep = lambda c: sample(c).repeat_interleave(sy_, dim=1).repeat_interleave(sx, dim=2)[:, :H0, :W0]
+    d, e, f = sample(frames.y) - y_off, rep(frames.u) - 128 * up, rep(frames.v) - 128 * up
+    half, div = 1 << (shift - 1), 1 << shift
+    sums = torch.stack([cy * d + crv * f + half, cy * d - cgu * e - cgv * f + half, cy * d + cbu * e + half], dim=1)
+    return torch.div(sums, div, rounding_mode="floor").clamp(0, top).contiguous()
+
+
+def restated_remap_levels(levels, m: RectifyMap, depth):
+    """levels (N, 3, Hs, Ws) int64 -> (N, 3, H0, W0) int64 by the header's formula on flat pixel indices with torch.gather and a floor division;
+    a tap outside the frame is, in constant mode, the byte `fill` with its top bits repeated below it."""
+    N, _, hs, ws = levels.shape
+    H0, W0 = m.frac.shape
+    fill = m.fill * 2 ** (depth - 8) + m.fill // 2 ** (16 - depth)
+    flat = levels.reshape(N, 3, hs * ws)
+    x0, y0 = m.xy[..., 0].reshape(-1).long(), m.xy[..., 1].reshape(-1).long()
+    fr = m.frac.reshape(-1).long() & 0xFFFF
+    fx, fy = fr % 32, (fr // 32) % 32
+    total = torch.zeros((N, 3, H0 * W0), dtype=torch.int64, device=levels.device)
+    for (dy, dx), w in zip(((0, 0), (0, 1), (1, 0), (1, 1)), [(32 - fx) * (32 - fy), fx * (32 - fy), (32 - fx) * fy, fx * fy]):
+        yy, xx = y0 + dy, x0 + dx
+        inside = (yy >= 0) & (yy < hs) & (xx >= 0) & (xx < ws)
+        tap = torch.gather(flat, 2, (yy.clamp(0, hs - 1) * ws + xx.clamp(0, ws - 1)).expand(N, 3, -1))
+        if m.border == "constant":
+            tap = tap * inside + fill * (~inside)
+        total += w * tap
+    out = torch.div(total + 512, 1024, rounding_mode="floor")
+    assert int(out.min()) >= 0 and int(out.max()) <= 2 ** depth - 1                          # no clamp is needed
+    return out.reshape(N, 3, H0, W0)
+
+
+def as_float(levels, depth):
+    """What the reference would be given: the float video of the levels."""
+    return levels.float() * (255.0 / (2 ** depth - 1))
+
+
+def expected_operands(l_levels, r_levels, depth, pad):
+    """The float path's two operands (float_path_operands: its ``.float()`` finds float32 and changes nothing) for the float video of the levels."""
+    f, c, H, Wd = float_path_operands(as_float(l_levels, depth), as_float(r_levels, depth), pad)
+    torch.cuda.synchronize()
+    return f, c, H, Wd
+
+
+def fresh(N, H, Wd):
+    return patterned(2 * N * (H // 2) * (Wd // 2), 32), patterned(N * (H // 4) * (Wd // 4), 64)
+
+
+def ingest_deep(left: YUVFrames, right: YUVFrames, pad_left, pad_top, H, Wd, fview, cview, maps=None):
+    from ppmstereo_amd.ppmstereo import level_lut
+    lv, rv, m, fmt = left.view_struct(), right.view_struct(), left.matrix(), left.format_struct()
+    assert (fmt.sample_bytes, fmt.depth, fmt.lsb, fmt.sub_x, fmt.sub_y) == (right.sample_bytes, right.depth, right.lsb, right.sub_x, right.sub_y)
+    lut = level_lut(DEV, left.depth)
+    assert lut.numel() == 1 << left.depth
+    with torch.cuda.device(DEV):
+        if maps is None:
+            rc = L.load().ppms_video_ingest_yuv(lv, rv, m, fmt, left.n, left.height, left.width, pad_left, pad_top, H, Wd, lut.data_ptr(), fview, cview,
+                                                L.stream_ptr())
+        else:
+            d = left.depth
+            rc = L.load().ppms_video_ingest_yuv_remap(lv, rv, m, fmt, maps[0].view_struct(d), maps[1].view_struct(d), left.n, maps[0].height, maps[0].width,
+                                                      pad_left, pad_top, H, Wd, lut.data_ptr(), fview, cview, L.stream_ptr())
+    L.check(rc)
+
+
+def check_both(left, right, pad, maps=None):
+    """pad = F.pad's [left, right, top, bottom]; maps: the two views' RectifyMaps (the _remap twin)."""
+    ll, rl = restated_levels(left), restated_levels(right)
+    if maps is not None:
+        ll, rl = restated_remap_levels(ll, maps[0], left.depth), restated_remap_levels(rl, maps[1], left.depth)
+    ef, ec, H, Wd = expected_operands(ll, rl, left.depth, pad)
+    f, c = fresh(left.n, H, Wd)
+    ingest_deep(left, right, pad[0], pad[2], H, Wd, f.view(), c.view(), maps)
+    assert torch.equal(bits(f), bits(ef)) and torch.equal(bits(c), bits(ec))
+    return f, c
+
+
+def p010_surfaces(N, H0, W0, pitch, seed, chroma="420", **kw):
+    """P010 / P210 frames of H0 x W0 in surfaces whose rows are `pitch` samples (luma and UV alike), on the device: every word random, so the
+    6 bits below the sample are dirty."""
+    hc, wc = ((H0 + 1) // 2 if chroma == "420" else H0), (W0 + 1) // 2
+    y, uv = rand_u16((N, H0, pitch), seed).to(DEV), rand_u16((N, hc, pitch // 2, 2), seed + 100).to(DEV)
+    assert bool((y.to(torch.int32) & 63).any())
+    make = YUVFrames.p010 if chroma == "420" else YUVFrames.p210
+    return make(y[:, :, :W0], uv[:, :, :wc], **kw)
+
+
+def planar_frames(N, H0, W0, seed, depth, chroma, **kw):
+    """Three dense lsb-aligned planes on the device (uint8 at depth 8), every sample below 2^depth."""
+    hc, wc = ((H0 + 1) // 2 if chroma == "420" else H0), (W0 if chroma == "444" else (W0 + 1) // 2)
+    plane = lambda shape, s: (rand_u8(shape, s) if depth == 8 else rand_u16(shape, s, 1 << depth)).to(DEV)
+    return YUVFrames.planar(plane((N, H0, W0), seed), plane((N, hc, wc), seed + 100), plane((N, hc, wc), seed + 200), depth=depth, chroma=chroma, **kw)
+
+
+# ---- the table ------------------------------------------------------------------------------------------------------------------------------
+def test_level_table_is_the_float_paths_expression():
+    from ppmstereo_amd.ppmstereo import byte_lut, level_lut
+    for depth in (10, 12):
+        n = 1 << depth
+        lut = level_lut(DEV, depth)
+        x = torch.arange(n, dtype=torch.int16, device=DEV).reshape(1, 1, n // 32, 32).float() * (255.0 / (n - 1))       # to_float of every level
+        assert lut.dtype == torch.float32 and tuple(lut.shape) == (n,) and torch.equal(lut, (2 * (x / 255.0) - 1.0).reshape(-1))
+        assert level_lut(DEV, depth) is lut and float(lut[0]) == -1.0 and bool((lut[1:] > lut[:-1]).all())
+    assert level_lut(DEV, 8) is byte_lut(DEV)
+
+
+# ---- the kernel -----------------------------------------------------------------------------------------------------------------------------
+def test_bytes_420_through_the_generic_entry_are_the_yuv420_calls_bits():
+    """NV12 37 x 50 in surfaces of pitch 64 -> 64 x 64, pads 7 / 7 / 13 / 14: fmt = {1, 8, 0, 1, 1} writes ppms_video_ingest_yuv420's operands."""
+    left, right = nv12_surfaces(2, 37, 50, 64, 131), nv12_surfaces(2, 37, 50, 64, 132)
+    fmt = left.format_struct()
+    assert (fmt.sample_bytes, fmt.depth, fmt.lsb, fmt.sub_x, fmt.sub_y) == (1, 8, 0, 1, 1)
+    ef, ec = fresh(2, 64, 64)
+    ingest_yuv(left, right, 7, 13, 64, 64, ef.view(), ec.view())
+    f, c = fresh(2, 64, 64)
+    ingest_deep(left, right, 7, 13, 64, 64, f.view(), c.view())
+    assert torch.equal(bits(f), bits(ef)) and torch.equal(bits(c), bits(ec))
+
+
+def test_p010_with_odd_sizes_padding_and_dirty_low_bits():
+    """37 x 50 per view in surfaces of pitch 64 samples (19 x 25 chroma pairs) -> 64 x 64, pads 7 / 7 / 13 / 14."""
+    from ppmstereo_amd.ppmstereo import InputPadder
+    left, right = p010_surfaces(2, 37, 50, 64, 133), p010_surfaces(2, 37, 50, 64, 134)
+    s = left.view_struct()
+    assert (s.pitch_y, s.pitch_c, s.step_c, s.v - s.u, s.frame_stride_y, s.frame_stride_c) == (128, 128, 4, 2, 37 * 128, 19 * 128)
+    padder = InputPadder((37, 50), divis_by=32)
+    assert padder._pad == [7, 7, 13, 14] and padder.geometry() == (7, 13, 64, 64)
+    f, c = check_both(left, right, padder._pad)
+    assert not bits(f)[:, :, 12:].any() and not bits(c)[:, :, 48:].any() and bits(f)[:, :, :12].any()       # tail channels zeroed
+
+
+def test_p010_skipped_destinations():
+    """32 x 64, T = 3, no padding; a destination with hi == NULL is skipped and stays as it was."""
+    left, right = p010_surfaces(3, 32, 64, 64, 135), p010_surfaces(3, 32, 64, 64, 136)
+    ef, ec, H, Wd = expected_operands(restated_levels(left), restated_levels(right), 10, [0, 0, 0, 0])
+    for skip in ("cnet", "fnet"):
+        f, c = fresh(3, 32, 64)
+        before_f, before_c = bits(f).clone(), bits(c).clone()
+        fv, cv = f.view(), c.view()
+        if skip == "cnet":
+            cv.hi = None                                         # (lo, ld, c stay set: hi == NULL alone must be enough to skip)
+        else:
+            fv.hi = None
+        ingest_deep(left, right, 0, 0, H, Wd, fv, cv)
+        if skip == "cnet":
+            assert torch.equal(bits(f), bits(ef)) and torch.equal(bits(c), before_c)
+        else:
+            assert torch.equal(bits(c), bits(ec)) and torch.equal(bits(f), before_f)
+
+
+@pytest.mark.parametrize("depth,chroma", [(10, "422"), (12, "444")])
+def test_planar_lsb_frames_in_a_block_straddling_both_destinations(depth, chroma):
+    """36 x 36 from 33 x 35 with pads [1, 0, 2, 1]: the k = 2 part is 2592 threads, so one 256-thread block serves the end of one destination and
+    the start of the other; the odd pad_left and the even pad_top shift the luma / chroma parity against the output's 2 x 2 phases."""
+    left, right = planar_frames(1, 33, 35, 137, depth, chroma), planar_frames(1, 33, 35, 138, depth, chroma)
+    assert (2 * 18 * 18 * 4) % 256 and left.lsb == 0 and left.sample_bytes == 2
+    check_both(left, right, [1, 0, 2, 1])
+    check_both(right, left, [1, 0, 1, 2])                       # both pads odd: pad_top = 1 of the 3 spare rows
+
+
+def every_level_frame(depth, seed, **kw):
+    """One 4:4:4 frame whose three planes each hold every level of `depth` bits exactly once, each in its own order (32 x 32 at 10 bits, 64 x 64
+    at 12): levels below the black level and above the white level meet saturated chroma, so both clamps act."""
+    g = torch.Generator().manual_seed(seed)
+    side = 1 << (depth // 2)
+    planes = [torch.randperm(1 << depth, generator=g).to(torch.int32).to(torch.uint16).reshape(1, side, side) for _ in range(3)]
+    for p in planes:
+        assert sorted(p.reshape(-1).to(torch.int32).tolist()) == list(range(1 << depth))
+    return YUVFrames.planar(*planes, depth=depth, chroma="444", **kw)
+
+
+@pytest.mark.parametrize("depth", [10, 12])
+@pytest.mark.parametrize("standard,full_range", COMBOS)
+def test_every_level_every_standard_and_range(standard, full_range, depth):
+    host = [every_level_frame(depth, 141 + i, standard=standard, full_range=full_range) for i in range(2)]
+    top = 2 ** depth - 1
+    for frames in host:                                          # on the CPU: the restatement alone reaches both clamps, so the table's two ends are used
+        levels = restated_levels(frames)
+        assert not levels.is_cuda and int((levels == 0).sum()) > 8 and int((levels == top).sum()) > 8
+    left, right = (f.to(DEV) for f in host)
+    for frames, there in zip(host, (left, right)):               # the device holds the same samples: index 2^depth - 1, the table's last entry, is looked up
+        assert torch.equal(restated_levels(there).cpu(), restated_levels(frames))
+    check_both(left, right, [0, 0, 0, 0])
+
+
+def test_bytes_422_and_444_against_the_uint8_kernel():
+    """8-bit 4:2:2 interleaved (NV16, pitch 64) and 8-bit 4:4:4 planar, 37 x 50 -> 64 x 64: ppms_video_ingest_u8's operands on the restated bytes."""
+    def nv16(seed):
+        y, uv = rand_u8((2, 37, 64), seed).to(DEV), rand_u8((2, 37, 32, 2), seed + 100).to(DEV)
+        return YUVFrames.nv16(y[:, :, :50], uv[:, :, :25], "bt601", True)
+    for left, right in ((nv16(145), nv16(146)), (planar_frames(2, 37, 50, 147, 8, "444"), planar_frames(2, 37, 50, 148, 8, "444"))):
+        assert left.sample_bytes == 1 and left.format_struct().sub_y == 0
+        l, r = (restated_levels(v).to(torch.uint8).contiguous() for v in (left, right))
+        ef, ec = fresh(2, 64, 64)
+        ingest(l.data_ptr(), r.data_ptr(), 3 * 37 * 50, 2, 37, 50, 7, 13, 64, 64, ef.view(), ec.view())
+        torch.cuda.synchronize()
+        f, c = fresh(2, 64, 64)
+        ingest_deep(left, right, 7, 13, 64, 64, f.view(), c.view())
+        assert torch.equal(bits(f), bits(ef)) and torch.equal(bits(c), bits(ec))
+
+
+def test_frame_strides_past_2_to_31_bytes():
+    """Frame 1 of every 16-bit plane lies more than 2^31 bytes behind frame 0: the source offsets are 64-bit arithmetic.  One buffer for luma, one
+    for both chroma planes (u at 0, v behind it), shared by the two views' (different) pictures at different offsets."""
+    H0, W0, sy, sc = 8, 12, (1 << 30) + 2049, (1 << 30) + 2051                                # in 16-bit elements
+    ny, nc = H0 * W0, (H0 // 2) * (W0 // 2)
+    ybuf = torch.empty(sy + 2 * ny, dtype=torch.uint16, device=DEV)
+    cbuf = torch.empty(sc + 4 * nc, dtype=torch.uint16, device=DEV)
+    views = []
+    for i in range(2):                                          # view i: luma at i * ny, u at 2 i nc, v at (2 i + 1) nc
+        src = planar_frames(2, H0, W0, 149 + i, 10, "420")
+        y = torch.as_strided(ybuf, (2, H0, W0), (sy, W0, 1), i * ny)
+        u, v = (torch.as_strided(cbuf, (2, H0 // 2, W0 // 2), (sc, W0 // 2, 1), (2 * i + j) * nc) for j in range(2))
+        y.copy_(src.y), u.copy_(src.u), v.copy_(src.v)
+        views.append(YUVFrames.planar(y, u, v, depth=10))
+        s = views[-1].view_struct()
+        assert (s.frame_stride_y, s.frame_stride_c) == (2 * sy, 2 * sc) and 2 * sy > 1 << 31
+        assert torch.equal(restated_levels(views[-1]), restated_levels(src))
+    check_both(views[0], views[1], [0, 0, 0, 0])
+
+
+# ---- the _remap twin ------------------------------------------------------------------------------------------------------------------------
+def test_remap_identity_maps_give_the_plain_calls_operands():
+    ident = RectifyMap.identity(37, 50, device=DEV)
+    left, right = p010_surfaces(2, 37, 50, 64, 133), p010_surfaces(2, 37, 50, 64, 134)       # the frames of the P010 test above
+    ef, ec = fresh(2, 64, 64)
+    ingest_deep(left, right, 7, 13, 64, 64, ef.view(), ec.view())
+    f, c = check_both(left, right, [7, 7, 13, 14], (ident, ident))
+    assert torch.equal(bits(f), bits(ef)) and torch.equal(bits(c), bits(ec))
+
+
+def rotated_map(H0, W0, hs, ws, angle, scale, border, fill):
+    """The rectified frame H0 x W0 as a rotated, scaled window around the centre of the hs x ws raw frame: its corners lie outside the raw frame."""
+    import math
+    ys, xs = torch.meshgrid(torch.arange(H0, dtype=torch.float32), torch.arange(W0, dtype=torch.float32), indexing="ij")
+    dx, dy = xs - (W0 - 1) / 2, ys - (H0 - 1) / 2
+    mx = (ws - 1) / 2 + scale * (math.cos(angle) * dx - math.sin(angle) * dy)
+    my = (hs - 1) / 2 + scale * (math.sin(angle) * dx + math.cos(angle) * dy)
+    m = RectifyMap.from_float(mx, my, (hs, ws), border, fill).to(DEV)
+    x0, y0 = m.xy[..., 0], m.xy[..., 1]
+    assert bool((x0 < 0).any()) and bool((x0 + 1 > ws - 1).any()) and bool((y0 < 0).any()) and bool((y0 + 1 > hs - 1).any())      # taps outside
+    assert len(set(m.frac.reshape(-1).tolist())) > 500
+    return m
+
+
+@pytest.mark.parametrize("border,fill", [("replicate", 0), ("constant", 0), ("constant", 255)])
+def test_remap_rotated_scaled_map_on_p010(border, fill):
+    """Raw 40 x 56 P010 frames (pitch 64) -> rectified 37 x 50 -> 64 x 64; the two views turn in opposite directions."""
+    lmap, rmap = rotated_map(37, 50, 40, 56, 0.21, 1.2, border, fill), rotated_map(37, 50, 40, 56, -0.17, 1.25, border, fill)
+    assert lmap.view_struct(10).fill == (1023 if fill else 0)
+    left, right = p010_surfaces(2, 40, 56, 64, 151), p010_surfaces(2, 40, 56, 64, 152)
+    check_both(left, right, [7, 7, 13, 14], (lmap, rmap))
+    got = lmap.apply_levels(left.to_rgb(), 10)                   # and the package's own definitions are the restatements
+    assert got.dtype == torch.int16 and torch.equal(got.long(), restated_remap_levels(restated_levels(left), lmap, 10))
+
+
+# ---- the model ------------------------------------------------------------------------------------------------------------------------------
+def host_p010(N, H0, W0, seed):
+    """A P010 YUVStereoVideo on the host and the (N, 2, 3, H0, W0) levels the restatement makes of it."""
+    hc, wc = (H0 + 1) // 2, (W0 + 1) // 2
+    views = [YUVFrames.p010(rand_u16((N, H0, W0), seed + i), rand_u16((N, hc, wc, 2), seed + 10 + i)) for i in range(2)]
+    return YUVStereoVideo(*views), torch.stack([restated_levels(v) for v in views], dim=1).contiguous()
+
+
+def test_model_single_window(model):
+    """(3, 60, 250) P010 frames -> 64 x 256, one window: the bits of the float video of the levels, from the host and from the device."""
+    video, levels = host_p010(3, 60, 250, 161)
+    fl = as_float(levels, 10)
+    run = lambda v: model.forward_batch_test({"stereo_video": v}, kernel_size=20, iters=4)
+    ref, ref2 = run(fl), run(fl)
+    assert same(ref, ref2), "the float path itself is not repeatable: nothing can be said about the P010 path"
+    out = run(video)
+    assert tuple(out["disparity"].shape) == (3, 1, 60, 250) and not out["disparity"].is_cuda and out["disparity"].dtype == torch.float32
+    assert torch.isfinite(out["disparity"]).all() and same(out, ref)
+    on_device = video.to(DEV)
+    assert on_device.left.y.is_cuda and on_device.left.y.dtype == torch.uint16 and (on_device.left.step_c, on_device.left.lsb) == (4, 6)
+    assert torch.equal(restated_levels(on_device.right).cpu(), levels[:, 1])
+    assert same(run(on_device), ref)
+
+
+def test_model_several_windows_take_the_clip_pipeline(model):
+    from ppmstereo_amd.ppmstereo import window_plan
+    video, levels = host_p010(7, 60, 250, 162)
+    assert len(window_plan(7, 4)) > 1
+    run = lambda v: model.forward_batch_test({"stereo_video": v}, kernel_size=4, iters=2)
+    ref = run(as_float(levels, 10))
+    out = run(video)
+    assert tuple(out["disparity"].shape) == (7, 1, 60, 250) and same(out, ref)
+
+
+def test_model_forward_directly(model):
+    video, levels = host_p010(3, 64, 256, 163)
+    left, right = video.left.to(DEV), video.right.to(DEV)
+    d, u = model.forward(left, right, iters=4, test_mode=True)
+    fl = as_float(levels, 10).to(DEV)
+    rd, ru = model.forward(fl[None, :, 0], fl[None, :, 1], iters=4, test_mode=True)
+    assert tuple(d.shape) == (1, 3, 1, 64, 256) and torch.equal(d, rd) and torch.equal(u, ru)
+    with pytest.raises(ValueError):                              # the two views must be one kind of surface
+        model.forward(left, YUVFrames.planar(right.y, right.u, right.v, depth=10), iters=4, test_mode=True)
+
+
+def test_model_rectify_and_quantised_output(model):
+    """Raw 70 x 262 P010 -> rectified 60 x 250: rectify= gives the bits of the float video made with apply_levels; output= those of the same call on
+    the float video."""
+    r = smooth_rectifier(60, 250, 70, 262, 6, "constant", 200)
+    video, levels = host_p010(3, 70, 262, 164)
+    rect = torch.stack(r.apply_levels(levels[:, 0].to(torch.int16), levels[:, 1].to(torch.int16), 10), dim=1)
+    assert tuple(rect.shape) == (3, 2, 3, 60, 250) and rect.dtype == torch.int16
+    assert torch.equal(rect[:, 0].long(), restated_remap_levels(levels[:, 0], r.left, 10))
+    run = lambda v, **kw: model.forward_batch_test({"stereo_video": v}, kernel_size=20, iters=4, **kw)
+    assert same(run(video, rectify=r), run(as_float(rect, 10)))
+    plain, lv = host_p010(3, 60, 250, 165)
+    spec = OutputSpec(disparity="u16", uncertainty="u8")
+    q, qref = run(plain, output=spec), run(as_float(lv, 10), output=spec)
+    assert q["disparity"].dtype == torch.uint16 and q["uncertainties"].dtype == torch.uint8 and tuple(q["disparity"].shape) == (3, 1, 60, 250)
+    for k in ("disparity", "uncertainties"):
+        assert torch.equal(q[k].view(torch.uint8), qref[k].view(torch.uint8))
+
+
+def test_user_supplied_encoders_get_to_float():
+    """Encoder callables of the caller (the stand-ins of stub_encoders.py, keyed on a frame's grey level): the deep video is converted on the device
+    with to_float() and takes the float path.  Full-range grey frames of level 4 f: (Y, 512, 512) is the RGB grey Y, 4 f * 255 / 1023 rounds to f."""
+    from ppmstereo_amd.ppmstereo import PPMStereo
+    from stub_encoders import StubCNet, StubFNet
+    m = PPMStereo.shipped(fnet=StubFNet(), cnet=StubCNet(), sst=None).load_hot_path_weights(W).to(DEV).eval()
+
+    def grey(N, H0, W0):
+        y = (4 * torch.arange(N, dtype=torch.int32))[:, None, None].expand(N, H0, W0).contiguous().to(torch.uint16)
+        c = torch.full((N, (H0 + 1) // 2, (W0 + 1) // 2), 512, dtype=torch.int32).to(torch.uint16)
+        view = lambda: YUVFrames.planar(y.clone(), c.clone(), c.clone(), depth=10, full_range=True)
+        return YUVStereoVideo(view(), view())
+
+    video = grey(7, 60, 250)
+    fl = torch.stack([video.left.to_float(), video.right.to_float()], dim=1)
+    assert torch.equal(fl, torch.stack([as_float(restated_levels(v), 10) for v in (video.left, video.right)], dim=1))
+    assert [round(float(x)) for x in fl[:, 0, 0, 0, 0]] == list(range(7))
+    run = lambda v: m.forward_batch_test({"stereo_video": v}, kernel_size=20, iters=4)
+    assert same(run(video), run(fl))
+    v = grey(3, 64, 256).to(DEV)
+    d, u = m.forward(v.left, v.right, iters=4, test_mode=True)
+    rd, ru = m.forward(v.left.to_float()[None], v.right.to_float()[None], iters=4, test_mode=True)
+    assert torch.equal(d, rd) and torch.equal(u, ru)
