@@ -393,6 +393,64 @@ int ppms_video_ingest_yuv_remap(const ppms_yuv_view* left, const ppms_yuv_view* 
                                 int N, int H0, int W0, int pad_left, int pad_top, int H, int W,
                                 const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream);
 int ppms_yuv_format_struct_size(int* fmt);           /* sizeof(ppms_yuv_format) (32): lets a binding verify its layout */
+/* The same two operands from the RAW frames of a sensor that has no decoder behind it (machine-vision heads: GigE / USB3-Vision, MIPI), one launch:
+ * a Bayer colour-filter mosaic (BayerRG8, BayerGB10, BayerRG12 ...) or a monochrome plane (Mono8 / Mono10 / Mono12), one sample per pixel.  A view
+ * describes one eye's N frames as the camera driver left them: one pitched plane of H0 x W0 samples; both views of a side-by-side or top-and-bottom
+ * packed frame are two views into one surface.  `fmt` (HOST memory, read before the call returns) is shared by both views; every pointer inside a
+ * view is a device pointer.
+ *   Samples and strides.  ppms_yuv_format's: sample_bytes = 1 with depth 8, or 2 (little-endian 16-bit words) with depth 10 or 12; lsb = 0 or
+ * 16 - depth; a sample is (word >> lsb) & ((1 << depth) - 1).  pitch and frame_stride are in BYTES, and even -- as the pointer -- for 16-bit samples.
+ *   Mosaic.  pattern 0 = RGGB, 1 = BGGR, 2 = GRBG, 3 = GBRG, 4 = MONO: the name spells the 2 x 2 tile at the frame's origin in row-major order, and
+ * the colour of source pixel (y, x) is tile[(y & 1) * 2 + (x & 1)].  Let s(y, x) be the sample at source coordinate (y, x) of a frame of hs x ws
+ * (H0 x W0 without a map).  A NEIGHBOUR coordinate outside the frame is reflected without repeating the edge, t < 0 -> -t, t > n - 1 ->
+ * 2 (n - 1) - t, which keeps the colour-filter parity for every frame size (hence hs, ws >= 2 for the four colour patterns).  For a site of
+ * colour k and the wanted channel c:
+ *   c == k:                                   v = s(y, x)
+ *   k in {R, B}, c == G:                      v = (s(y-1, x) + s(y+1, x) + s(y, x-1) + s(y, x+1) + 2) >> 2
+ *   k in {R, B}, c the other of R / B:        v = (s(y-1, x-1) + s(y-1, x+1) + s(y+1, x-1) + s(y+1, x+1) + 2) >> 2
+ *   k == G, c in {R, B}:                      v = (s(y, x-1) + s(y, x+1) + 1) >> 1 if this row's horizontal neighbours carry c,
+ *                                             v = (s(y-1, x) + s(y+1, x) + 1) >> 1 otherwise
+ *   MONO:                                     v = s(y, x) for all three channels
+ * (bilinear demosaicing; nothing here has been compared with OpenCV's demosaic).
+ *   Black level and white balance.  The RGB LEVEL of channel c is, in integers (>> is the arithmetic shift, as in the YUV formula),
+ *   level = clamp(((v - black) * gain[c] + (1 << (shift - 1))) >> shift, 0, 2^depth - 1)
+ * with black in [0, 2^depth), shift in [4, 14] and gain[0..2] (R, G, B) in [0, 16 << shift): no sum leaves 32 bits (2^12 * 2^18 + 2^13 < 2^31).
+ *   Level table.  lut is a device fp32 array of 1 << depth entries, indexed by the RGB level; from the levels on -- lut, pads, H x W, destinations,
+ * hi == NULL -- the call is ppms_video_ingest_yuv.  The table is the caller's: a tone curve (gamma / sRGB encoding of linear sensor data) is
+ * another table and costs nothing.
+ *   _remap.  The remap contract above on these levels: a tap is the RGB level of that source pixel, demosaiced in the SOURCE frame (its neighbours
+ * reflected at the source frame's edges); the blend (sum w p + 512) >> 10 lies in [0, 2^depth - 1] without a clamp, and `fill` is a level in
+ * [0, 2^depth - 1].  Every load address comes from a coordinate clamped or reflected into the frame, whatever the map holds.
+ *   Refused with PPMS_EINVAL before any launch: a null pointer; non-zero reserved; sample_bytes not 1 or 2; a depth that does not go with it; lsb
+ * not 0 or 16 - depth; pattern outside 0..4; black, a gain or shift outside the bounds above; an odd pointer, pitch or frame stride with 16-bit
+ * samples; a pitch shorter than a row; with N > 1 a frame_stride shorter than a frame; a frame smaller than 2 x 2 with a colour pattern; what
+ * ppms_video_ingest_u8 refuses about sizes, pads and destinations; for _remap, whatever the _remap calls above refuse.
+ * Not covered: packed 10p / 12p transport formats, 14- and 16-bit sensors (the level table would not fit LDS), demosaicing better than bilinear,
+ * colour-correction matrices, lens shading and defect pixels, patterns that differ between the two views. */
+typedef struct ppms_raw_view {        /* one view's frames, as the camera driver left them */
+    const uint8_t* data;              /* sample (0,0) of frame 0 */
+    int64_t frame_stride;             /* bytes from frame n to frame n + 1 */
+    int32_t pitch;                    /* bytes from row to row */
+    int32_t reserved;                 /* 0 */
+} ppms_raw_view;
+typedef struct ppms_raw_format {
+    int32_t sample_bytes;             /* 1, or 2 (little-endian 16-bit words) */
+    int32_t depth;                    /* 8 with sample_bytes 1; 10 or 12 with sample_bytes 2 */
+    int32_t lsb;                      /* bit of the word that holds the sample's lowest bit: 0 or 16 - depth; 0 for bytes */
+    int32_t pattern;                  /* 0 RGGB, 1 BGGR, 2 GRBG, 3 GBRG, 4 MONO */
+    int32_t black;                    /* black level, [0, 2^depth) */
+    int32_t gain[3];                  /* white balance for R, G, B times 2^shift, [0, 16 << shift) */
+    int32_t shift;                    /* [4, 14] */
+    int32_t reserved[3];              /* 0 */
+} ppms_raw_format;
+int ppms_video_ingest_raw(const ppms_raw_view* left, const ppms_raw_view* right, const ppms_raw_format* fmt,
+                          int N, int H0, int W0, int pad_left, int pad_top, int H, int W,
+                          const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream);
+int ppms_video_ingest_raw_remap(const ppms_raw_view* left, const ppms_raw_view* right, const ppms_raw_format* fmt,
+                                const ppms_remap_view* lmap, const ppms_remap_view* rmap,
+                                int N, int H0, int W0, int pad_left, int pad_top, int H, int W,
+                                const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream);
+int ppms_raw_struct_sizes(int* view, int* format);   /* sizeof of the two structs above (24, 48): lets a binding verify its layout */
 /* nn.InstanceNorm2d(affine=False) (extractor.py:326-329, 364): per (sample, channel) mean and 1 / sqrt(biased var + eps) over the
  * HW pixels of x (channel-last fp32 [N * HW][ld], a convolution's fp32 output) -> stats[N][C][2] (pixel slices merged in fixed
  * order: deterministic; caller-owned 16-B aligned workspace of ppms_instnorm_workspace_bytes); then

@@ -76,6 +76,17 @@ class YUVFormat(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("sample_bytes", "depth", "lsb", "sub_x", "sub_y")] + [("reserved", C.c_int32 * 3)]
 
 
+class RawView(C.Structure):
+    """ppms_raw_view: one view's raw sensor frames (device pointer, byte strides)."""
+    _fields_ = [("data", c_void_p), ("frame_stride", c_int64), ("pitch", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RawFormat(C.Structure):
+    """ppms_raw_format: how ppms_video_ingest_raw reads a view's samples (width, depth, alignment in the word, mosaic, black level, white balance)."""
+    _fields_ = [(n, C.c_int32) for n in ("sample_bytes", "depth", "lsb", "pattern", "black")] + [("gain", C.c_int32 * 3), ("shift", C.c_int32),
+                                                                                                  ("reserved", C.c_int32 * 3)]
+
+
 class RemapView(C.Structure):
     """ppms_remap_view: one view's fixed-point rectification map (device pointers, pitch in map pixels, the source frame size)."""
     _fields_ = [("xy", c_void_p), ("frac", c_void_p), ("pitch", C.c_int32), ("hs", C.c_int32), ("ws", C.c_int32),
@@ -156,6 +167,11 @@ _SIGS = {
     "ppms_video_ingest_yuv_remap": (c_int, [C.POINTER(YUVView), C.POINTER(YUVView), C.POINTER(YUVMatrix), C.POINTER(YUVFormat), C.POINTER(RemapView),
                                             C.POINTER(RemapView), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, SP, SP, c_void_p]),
     "ppms_yuv_format_struct_size": (c_int, [C.POINTER(c_int)]),
+    "ppms_video_ingest_raw": (c_int, [C.POINTER(RawView), C.POINTER(RawView), C.POINTER(RawFormat), c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                      c_void_p, SP, SP, c_void_p]),
+    "ppms_video_ingest_raw_remap": (c_int, [C.POINTER(RawView), C.POINTER(RawView), C.POINTER(RawFormat), C.POINTER(RemapView), C.POINTER(RemapView),
+                                            c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, SP, SP, c_void_p]),
+    "ppms_raw_struct_sizes": (c_int, [C.POINTER(c_int), C.POINTER(c_int)]),
     "ppms_dwconv": (c_int, [SP, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ppms_layernorm_any": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_float, SP, c_int64, c_int, c_void_p]),
     "ppms_grn_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
@@ -222,6 +238,9 @@ def load() -> C.CDLL:
     lib.ppms_yuv_format_struct_size(C.byref(a))
     if a.value != C.sizeof(YUVFormat):
         raise RuntimeError("ppmstereo_amd: ctypes layout of ppms_yuv_format differs from include/ppms.h")
+    lib.ppms_raw_struct_sizes(C.byref(a), C.byref(b))
+    if (a.value, b.value) != (C.sizeof(RawView), C.sizeof(RawFormat)):
+        raise RuntimeError("ppmstereo_amd: ctypes layout of ppms_raw_view / ppms_raw_format differs from include/ppms.h")
     if lib.ppms_egress_struct_size() != C.sizeof(Egress):
         raise RuntimeError("ppmstereo_amd: ctypes layout of ppms_egress differs from include/ppms.h")
     if lib.ppms_pwchain_param_bytes() != C.sizeof(ChainParams):

@@ -36,7 +36,7 @@ __global__ __launch_bounds__(256) void img_s2d_kernel(const float* __restrict__ 
     *(bf16x8*)((bf16_t*)dst.lo + od) = ol;
 }
 
-// decoded video -> the first-layer operands of both encoders in one launch (ppms_video_ingest_u8 / ppms_video_ingest_yuv420 / ppms_video_ingest_yuv):
+// decoded video -> the first-layer operands of both encoders in one launch (ppms_video_ingest_u8 / ppms_video_ingest_yuv420 / ppms_video_ingest_yuv / ppms_video_ingest_raw):
 // what normalisation (a table the caller built with the float path's own torch expression: 256 entries, or 1 << depth for a source whose
 // table_by_depth is true, which also answers levels()), replicate padding (clamped source
 // coordinate), torch.cat([left, right]) and the two img_s2d launches produce from the fp32 images.  Thread = one output pixel x 8 channels
@@ -98,6 +98,45 @@ struct yuv_source {
         const int d = sample(py, oy) - mat.y_off, e = sample(pu, oc) - mid, f = sample(pv, oc) - mid;
         const int acc = mat.cy * d + (c == 0 ? mat.crv * f : c == 1 ? -mat.cgu * e - mat.cgv * f : mat.cbu * e) + (1 << (mat.shift - 1));
         const int q = acc >> mat.shift;                                   // arithmetic shift: floor
+        return q < 0 ? 0 : (q > top ? top : q);
+    }
+};
+
+// a sensor's raw frames (ppms_video_ingest_raw): one pitched plane of T samples under a 2 x 2 colour-filter mosaic, or monochrome.  The missing
+// colours of a pixel are bilinear means of its neighbours (the arithmetic: include/ppms.h); a neighbour outside the frame is REFLECTED without
+// repeating the edge (-1 -> 1, n -> n - 2), which keeps its colour.  `pattern` is uniform, and which colour a site carries is parity arithmetic:
+// a site is green where (x ^ y ^ (pattern >> 1)) is odd, and rows with (y ^ pattern) even hold the red sites.  (y, x) arrives inside the hs x ws
+// frame, and with hs, ws >= 2 (the host refuses less for a colour pattern) so does every reflected neighbour: no load leaves the frame.
+template <class T>
+struct raw_source {
+    ppms_raw_view left, right;
+    int N, hs, ws;                                                        // frames per view, the SOURCE frame size
+    int depth, lsb, pattern, black, gain_r, gain_g, gain_b, shift;        // uniform: the ppms_raw_format
+    static constexpr bool table_by_depth = true;
+    __host__ __device__ int levels() const { return 1 << depth; }
+    __device__ int operator()(int64_t m, int c, int y, int x) const {
+        const bool r = m >= N;
+        const uint8_t* p = (r ? right.data : left.data) + (r ? m - N : m) * (r ? right.frame_stride : left.frame_stride);
+        const int64_t pitch = r ? right.pitch : left.pitch;
+        const int top = (1 << depth) - 1;
+        // the three channels of a pixel repeat these loads; they are the same addresses, and the compiler merges them
+        const auto s = [&](int yy, int xx) { return ((int)*(const T*)(p + yy * pitch + (int64_t)xx * (int)sizeof(T)) >> lsb) & top; };
+        int v;
+        if (pattern == 4) {                                               // MONO
+            v = s(y, x);
+        } else {
+            const int ym = y > 0 ? y - 1 : 1, yp = y < hs - 1 ? y + 1 : hs - 2, xm = x > 0 ? x - 1 : 1, xp = x < ws - 1 ? x + 1 : ws - 2;
+            const bool green = ((x ^ y ^ (pattern >> 1)) & 1) != 0, red_row = ((y ^ pattern) & 1) == 0;
+            if (c == (green ? 1 : (red_row ? 0 : 2)))
+                v = s(y, x);
+            else if (green)                                               // R or B at a green site: the two neighbours that carry it
+                v = (c == 0) == red_row ? (s(y, xm) + s(y, xp) + 1) >> 1 : (s(ym, x) + s(yp, x) + 1) >> 1;
+            else if (c == 1)                                              // G at a red or blue site
+                v = (s(ym, x) + s(yp, x) + s(y, xm) + s(y, xp) + 2) >> 2;
+            else                                                          // B at a red site, R at a blue site
+                v = (s(ym, xm) + s(ym, xp) + s(yp, xm) + s(yp, xp) + 2) >> 2;
+        }
+        const int q = ((v - black) * (c == 0 ? gain_r : c == 1 ? gain_g : gain_b) + (1 << (shift - 1))) >> shift;     // arithmetic shift: floor
         return q < 0 ? 0 : (q > top ? top : q);
     }
 };
@@ -890,6 +929,80 @@ extern "C" int ppms_video_ingest_yuv_remap(const ppms_yuv_view* left, const ppms
         return video_ingest_launch(who, source, N, H0, W0, pad_left, pad_top, H, W, lut, dst_fnet, dst_cnet, stream);
     }
     const remapped_source<yuv_source<uint16_t>> source{make_yuv_source<uint16_t>(left, right, m, fmt, N), *lmap, *rmap, N};
+    return video_ingest_launch(who, source, N, H0, W0, pad_left, pad_top, H, W, lut, dst_fnet, dst_cnet, stream);
+}
+
+extern "C" int ppms_raw_struct_sizes(int* view, int* format) {
+    if (view) *view = (int)sizeof(ppms_raw_view);
+    if (format) *format = (int)sizeof(ppms_raw_format);
+    return PPMS_OK;
+}
+
+// what both ppms_video_ingest_raw entry points check about the format and the views (frames of H0 x W0, named `hname` x `wname` in the messages)
+static int raw_check(const char* who, const ppms_raw_view* left, const ppms_raw_view* right, const ppms_raw_format* fmt, const float* lut, int N, int H0,
+                     int W0, const char* hname, const char* wname) {
+    PPMS_REQUIRE(left && right && fmt && lut, "%s: null view, format or table pointer", who);
+    PPMS_REQUIRE(N > 0 && H0 > 0 && W0 > 0, "%s: N = %d, %s = %d, %s = %d must be positive", who, N, hname, H0, wname, W0);
+    const ppms_raw_format& f = *fmt;
+    const int sb = f.sample_bytes;
+    PPMS_REQUIRE(sb == 1 || sb == 2, "%s: sample_bytes = %d must be 1 or 2", who, sb);
+    PPMS_REQUIRE(sb == 1 ? f.depth == 8 : (f.depth == 10 || f.depth == 12),
+                 "%s: depth = %d does not go with sample_bytes = %d (8 with 1; 10 or 12 with 2)", who, f.depth, sb);
+    PPMS_REQUIRE(f.lsb == 0 || (sb == 2 && f.lsb == 16 - f.depth), "%s: lsb = %d must be 0, or 16 - depth for 16-bit words", who, f.lsb);
+    PPMS_REQUIRE(f.pattern >= 0 && f.pattern <= 4, "%s: pattern = %d must be 0 (RGGB), 1 (BGGR), 2 (GRBG), 3 (GBRG) or 4 (MONO)", who, f.pattern);
+    PPMS_REQUIRE(f.black >= 0 && f.black < (1 << f.depth), "%s: black = %d must lie in [0, %d]", who, f.black, (1 << f.depth) - 1);
+    PPMS_REQUIRE(f.shift >= 4 && f.shift <= 14, "%s: shift = %d must lie in [4, 14]", who, f.shift);
+    // gains below 16.0 keep every sum inside 32 bits: 2^12 * 2^18 + 2^13 < 2^31 at depth 12 and shift = 14
+    const int32_t lim = 16 << f.shift;
+    PPMS_REQUIRE(f.gain[0] >= 0 && f.gain[0] < lim && f.gain[1] >= 0 && f.gain[1] < lim && f.gain[2] >= 0 && f.gain[2] < lim,
+                 "%s: every gain must lie in [0, 16 << shift)", who);
+    PPMS_REQUIRE(f.reserved[0] == 0 && f.reserved[1] == 0 && f.reserved[2] == 0, "%s: format: reserved must be 0", who);
+    PPMS_REQUIRE(f.pattern == 4 || (H0 >= 2 && W0 >= 2), "%s: a colour pattern needs a frame of at least 2 x 2, got %s = %d, %s = %d", who, hname, H0, wname, W0);
+    const ppms_raw_view* views[2] = {left, right};
+    for (int s = 0; s < 2; ++s) {
+        const ppms_raw_view& v = *views[s];
+        const char* side = s == 0 ? "left" : "right";
+        PPMS_REQUIRE(v.data, "%s: null data pointer in the %s view", who, side);
+        PPMS_REQUIRE(v.reserved == 0, "%s: %s view: reserved = %d must be 0", who, side, v.reserved);
+        if (sb == 2)
+            PPMS_REQUIRE((((uintptr_t)v.data | (uintptr_t)v.frame_stride | (uintptr_t)v.pitch) & 1) == 0,
+                         "%s: %s view: an odd pointer or stride; 16-bit samples need even pointers, pitches and frame strides", who, side);
+        const int64_t row = (int64_t)W0 * sb;                              // bytes from a row's first sample to the end of its last
+        PPMS_REQUIRE(v.pitch >= row, "%s: %s pitch = %d is less than a row's %lld bytes (%s = %d)", who, side, v.pitch, (long long)row, wname, W0);
+        PPMS_REQUIRE(N == 1 || v.frame_stride >= (int64_t)(H0 - 1) * v.pitch + row, "%s: %s frame_stride = %lld is less than a frame", who, side,
+                     (long long)v.frame_stride);
+    }
+    return PPMS_OK;
+}
+
+template <class T>
+static raw_source<T> make_raw_source(const ppms_raw_view* left, const ppms_raw_view* right, const ppms_raw_format* f, int N, int hs, int ws) {
+    return raw_source<T>{*left, *right, N, hs, ws, f->depth, f->lsb, f->pattern, f->black, f->gain[0], f->gain[1], f->gain[2], f->shift};
+}
+
+extern "C" int ppms_video_ingest_raw(const ppms_raw_view* left, const ppms_raw_view* right, const ppms_raw_format* fmt, int N, int H0, int W0, int pad_left,
+                                     int pad_top, int H, int W, const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream) {
+    const char* who = "video_ingest_raw";
+    if (const int rc = raw_check(who, left, right, fmt, lut, N, H0, W0, "H0", "W0")) return rc;
+    if (fmt->sample_bytes == 1)
+        return video_ingest_launch(who, make_raw_source<uint8_t>(left, right, fmt, N, H0, W0), N, H0, W0, pad_left, pad_top, H, W, lut, dst_fnet, dst_cnet, stream);
+    return video_ingest_launch(who, make_raw_source<uint16_t>(left, right, fmt, N, H0, W0), N, H0, W0, pad_left, pad_top, H, W, lut, dst_fnet, dst_cnet, stream);
+}
+
+extern "C" int ppms_video_ingest_raw_remap(const ppms_raw_view* left, const ppms_raw_view* right, const ppms_raw_format* fmt, const ppms_remap_view* lmap,
+                                           const ppms_remap_view* rmap, int N, int H0, int W0, int pad_left, int pad_top, int H, int W, const float* lut,
+                                           ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream) {
+    const char* who = "video_ingest_raw_remap";
+    // `fill` is a level of the format's depth (a format that names no depth is refused right behind the maps, which bound hs and ws for that check)
+    const int top = fmt && (fmt->depth == 10 || fmt->depth == 12) ? (1 << fmt->depth) - 1 : 255;
+    if (const int rc = remap_check(who, lmap, rmap, W0, top)) return rc;
+    const int hs = lmap->hs, ws = lmap->ws;
+    if (const int rc = raw_check(who, left, right, fmt, lut, N, hs, ws, "hs", "ws")) return rc;
+    if (fmt->sample_bytes == 1) {
+        const remapped_source<raw_source<uint8_t>> source{make_raw_source<uint8_t>(left, right, fmt, N, hs, ws), *lmap, *rmap, N};
+        return video_ingest_launch(who, source, N, H0, W0, pad_left, pad_top, H, W, lut, dst_fnet, dst_cnet, stream);
+    }
+    const remapped_source<raw_source<uint16_t>> source{make_raw_source<uint16_t>(left, right, fmt, N, hs, ws), *lmap, *rmap, N};
     return video_ingest_launch(who, source, N, H0, W0, pad_left, pad_top, H, W, lut, dst_fnet, dst_cnet, stream);
 }
 

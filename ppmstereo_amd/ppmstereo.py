@@ -19,8 +19,8 @@ from . import _lib as L
 from .corr import CorrBlock1D
 from .engine import bilinear
 from .update import Attention_qk, SequenceUpdateBlock3D
-from .video import (InputPadder, OutputSpec, RectifyMap, StereoRectifier, YUVFrames, YUVStereoVideo, byte_lut, egress_plan,  # noqa: F401  (the public names are
-                    level_lut, shard_windows, window_plan, yuv_matrix)                                                                 #  importable from here as before)
+from .video import (InputPadder, OutputSpec, RawFrames, RawStereoVideo, RectifyMap, StereoRectifier, YUVFrames, YUVStereoVideo, byte_lut,  # noqa: F401  (the public names are
+                    egress_plan, level_lut, shard_windows, window_plan, yuv_matrix)                                                    #  importable from here as before)
 from .video import _ByteSource, _EgressCall, stereo_source
 
 
@@ -558,6 +558,8 @@ class PPMStereo(PPMStereoHotPath):
           uint8 tensors: the bits of ``forward(image1.float(), image2.float())``; or
           two ``YUVFrames`` on the device (decoded frames of 8, 10 or 12 bits, 4:2:0 / 4:2:2 / 4:4:4: NV12, I420, P010, NV16 ...; b = 1, T = their
           frame count): the bits of ``forward`` on their ``to_float()`` (8-bit frames: on their ``to_rgb_u8()``); or
+          two ``RawFrames`` on the device (a sensor's Bayer-mosaic or monochrome frames of 8, 10 or 12 bits; b = 1, T = their frame count): the bits
+          of ``forward`` on their ``to_float()``; or
           with rectify (a ``StereoRectifier``) the RAW frames of an unrectified rig, uint8 device tensors (1, T, 3, Hs, Ws) or ``YUVFrames`` of its
           source size Hs x Ws: the bits of ``forward`` on ``RectifyMap.apply_u8`` of each view's RGB bytes (deep frames: ``apply_levels`` of their levels).  H, W above are then the rectified size,
           and so are the outputs'.  Float images raise TypeError (the remap reads decoded bytes), b > 1 NotImplementedError, another frame size
@@ -681,7 +683,8 @@ class PPMStereo(PPMStereoHotPath):
         a uint8 video (host or device) is copied as bytes -- a quarter of the float video's: the same bits as for ``stereo_video.float()``;
         a ``YUVStereoVideo`` (decoded frames, host or device) is copied per window as its planes -- 8-bit 4:2:0 (NV12, I420): 1.5 bytes per
         pixel and view, 8-bit 4:2:2: 2, 8-bit 4:4:4 and P010: 3 -- and gives the bits of the float video of its ``to_float()`` frames (8-bit: of
-        the uint8 video of ``to_rgb_u8()``).  Not covered: interpolated chroma siting, 16-bit depth, packed formats (YUYV / Y210 / v210), BT.2020
+        the uint8 video of ``to_rgb_u8()``); a ``RawStereoVideo`` (a sensor's raw frames, host or device) as its samples -- 1 byte per pixel and
+        view, 2 for 10- and 12-bit words -- and gives the bits of the float video of its ``to_float()`` frames.  Not covered: interpolated chroma siting, 16-bit depth, packed formats (YUYV / Y210 / v210), BT.2020
         and HDR transfer functions, high-depth RGB, b > 1.  With this package's encoders the bytes are converted, padded and normalised inside the one ingest launch;
         windows of ``kernel_size`` frames every ``kernel_size // 2``, centre frames kept (:296-307).  Windows whose output the
         reference computes and then drops are not run.  Returns {"disparity", "uncertainties"}: (N, 1, H, W) CPU tensors.

@@ -1,5 +1,5 @@
 """Video in and out of the model: what ``PPMStereo.forward`` / ``forward_batch_test`` accept beside the reference's float tensors (uint8 and decoded
-YUV frames of 8, 10 or 12 bits with 4:2:0 / 4:2:2 / 4:4:4 chroma, raw frames with a ``StereoRectifier``), the one private family of sources that stands for all of them behind the front doors
+YUV frames of 8, 10 or 12 bits with 4:2:0 / 4:2:2 / 4:4:4 chroma, a sensor's Bayer-mosaic or monochrome frames, unrectified frames with a ``StereoRectifier``), the one private family of sources that stands for all of them behind the front doors
 (``stereo_source``), the output planes they can hand back (``OutputSpec``) and the sliding-window schedule.  Nothing here knows the model."""
 from __future__ import annotations
 
@@ -326,6 +326,216 @@ class YUVStereoVideo:
         return YUVStereoVideo(self.left.to(device), self.right.to(device))
 
 
+_RAW_PATTERNS = {"rggb": 0, "bggr": 1, "grbg": 2, "gbrg": 3, "mono": 4}           # ppms_raw_format.pattern
+_RAW_SHIFT = 10                                                                    # the white-balance gains' fixed point
+
+
+class RawFrames:
+    """One view's N raw sensor frames, as a camera driver leaves them: ``data`` (N, H0, W0), one sample per pixel under the colour-filter mosaic
+    ``pattern`` ("rggb" / "bggr" / "grbg" / "gbrg": the 2 x 2 tile at the frame's origin, row-major -- BayerRG8, BayerGB10 ...) or "mono"
+    (Mono8 / Mono10 / Mono12).  ``depth=8``: a uint8 plane; ``depth`` 10 or 12: a ``torch.uint16`` plane whose words hold the sample at the bottom
+    (``align="lsb"``, the default: the high bits are masked) or at the top (``align="msb"``: the low bits are dropped whatever they hold).  ``data`` may
+    be a strided VIEW of a driver's buffer -- pitched rows, one half of a frame that packs both views (``split_side_by_side`` /
+    ``split_top_bottom``): the class reads ``data_ptr()`` and ``stride()`` and never copies; last-dimension stride 1, rows and frames that do not
+    overlap, anything else raises ValueError.  Strides are kept in BYTES (what ``ppms_raw_view`` holds).  ``black`` is the sensor's black level,
+    ``gains`` the white balance for (R, G, B), quantised with ``round(g * 1024)``; ``to_rgb`` is the definition of the RGB levels (bilinear
+    demosaic with reflected borders, include/ppms.h).  ``tone``: None -- a level stands for ``level * 255 / (2^depth - 1)`` -- or a float tensor of
+    2^depth values in [0, 255], the value each level stands for: where the gamma / sRGB encoding of linear sensor data goes, at no cost (the
+    kernel looks every level up in a table anyway).  Not covered: packed 10p / 12p transport formats, 14- and 16-bit sensors, demosaicing
+    better than bilinear, colour-correction matrices, lens shading and defect pixels, per-view differing patterns, b > 1."""
+
+    def __init__(self, data: torch.Tensor, pattern: str = "rggb", depth: int = 8, align: str = "lsb", black: int = 0, gains=(1.0, 1.0, 1.0),
+                 tone: Optional[torch.Tensor] = None, _shared: Optional[dict] = None):
+        depth = _check_depth("RawFrames", depth)
+        if pattern not in _RAW_PATTERNS:
+            raise ValueError(f"RawFrames: pattern {pattern!r}; one of {sorted(_RAW_PATTERNS)}")
+        if align not in ("msb", "lsb"):
+            raise ValueError(f"RawFrames: align {align!r}; 'msb' or 'lsb'")
+        dtype, es = (torch.uint8, 1) if depth == 8 else (torch.uint16, 2)
+        if not torch.is_tensor(data) or data.dtype != dtype or data.dim() != 3:
+            raise ValueError(f"RawFrames: data must be a {'uint8' if es == 1 else 'uint16'} tensor (N, rows, columns)" + ("" if es == 1 else f" at depth {depth}"))
+        n, h0, w0 = data.shape
+        if n < 1 or h0 < 1 or w0 < 1:
+            raise ValueError(f"RawFrames: empty plane {tuple(data.shape)}")
+        if pattern != "mono" and (h0 < 2 or w0 < 2):
+            raise ValueError(f"RawFrames: a colour pattern needs frames of at least 2 x 2, got {h0} x {w0}")
+        if w0 > 1 and data.stride(2) != 1:
+            raise ValueError(f"RawFrames: data has last-dimension stride {data.stride(2)}; samples must be adjacent")
+        if es == 2 and data.data_ptr() % 2:
+            raise ValueError("RawFrames: a 16-bit plane must start at an even address")
+        # a size-1 dimension's stride is arbitrary: the smallest the kernel accepts stands in for it (elements here, bytes below)
+        pitch = data.stride(1) if h0 > 1 else w0
+        frame = data.stride(0) if n > 1 else (h0 - 1) * pitch + w0
+        if pitch < w0 or frame < (h0 - 1) * pitch + w0:
+            raise ValueError(f"RawFrames: rows or frames overlap (strides {data.stride()})")
+        if not (isinstance(black, int) and 0 <= black < (1 << depth)):
+            raise ValueError(f"RawFrames: black = {black!r} must be an integer level in [0, {(1 << depth) - 1}]")
+        try:
+            gains = tuple(float(g) for g in gains)
+        except (TypeError, ValueError):
+            raise ValueError(f"RawFrames: gains = {gains!r} must be three numbers (R, G, B)") from None
+        if len(gains) != 3 or not all(0.0 <= g < 16.0 and 0 <= round(g * (1 << _RAW_SHIFT)) < (16 << _RAW_SHIFT) for g in gains):
+            raise ValueError(f"RawFrames: gains = {gains!r} must be three numbers (R, G, B) in [0, 16)")
+        if tone is not None and _shared is None:                           # (checked once: slices and copies hold the same tensor)
+            if not torch.is_tensor(tone) or not tone.is_floating_point() or tuple(tone.shape) != (1 << depth,):
+                raise ValueError(f"RawFrames: tone must be a floating-point tensor of {1 << depth} values, one per level of {depth} bits")
+            tone = tone.detach().to(torch.float32)
+            if not bool(((tone >= 0.0) & (tone <= 255.0)).all()):
+                raise ValueError("RawFrames: tone holds values outside [0, 255]")
+        self.data, self.pattern, self.depth, self.align, self.black, self.gains, self.tone = data, pattern, depth, align, black, gains, tone
+        self.n, self.height, self.width, self.sample_bytes = n, h0, w0, es
+        self.pitch, self.frame_stride = pitch * es, frame * es
+        self.lsb = 16 - depth if (es == 2 and align == "msb") else 0        # bit of the word that holds the sample's lowest bit
+        self.gain_q = tuple(round(g * (1 << _RAW_SHIFT)) for g in gains)
+        # what every slice, half and copy of these frames shares: the tone curve and the ingest table per device, each made once
+        self._shared = {"tone": {}, "table": {}} if _shared is None else _shared
+
+    def __len__(self) -> int:
+        return self.n
+
+    @property
+    def device(self) -> torch.device:
+        return self.data.device
+
+    def _like(self, data) -> "RawFrames":
+        return RawFrames(data, self.pattern, self.depth, self.align, self.black, self.gains, self.tone, _shared=self._shared)
+
+    def __getitem__(self, frames: slice) -> "RawFrames":
+        if not isinstance(frames, slice):
+            raise TypeError("RawFrames: index with a slice of frames")
+        return self._like(self.data[frames])
+
+    def split_side_by_side(self):
+        """(left, right): the two halves of frames that pack both views side by side; views, no copy.  The packed width must be even -- and with a
+        colour pattern each half's too: a right half that starts on an odd column has another pattern than the left one."""
+        w = self.width
+        if w % 2 or (self.pattern != "mono" and (w // 2) % 2):
+            raise ValueError(f"RawFrames.split_side_by_side: a packed width of {w} does not split into two views of one {self.pattern} pattern")
+        return self._like(self.data[:, :, :w // 2]), self._like(self.data[:, :, w // 2:])
+
+    def split_top_bottom(self):
+        """(left, right) = (top, bottom) halves of frames that pack both views one above the other; views, no copy (even halves, as above)."""
+        h = self.height
+        if h % 2 or (self.pattern != "mono" and (h // 2) % 2):
+            raise ValueError(f"RawFrames.split_top_bottom: a packed height of {h} does not split into two views of one {self.pattern} pattern")
+        return self._like(self.data[:, :h // 2]), self._like(self.data[:, h // 2:])
+
+    def to(self, device) -> "RawFrames":
+        """These frames on ``device``: the samples' own bytes are copied (1 per pixel, 2 for 16-bit words) into a dense plane; frames already
+        there are returned as they are."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        return self if self.device == device else self._like(self.data.to(device))
+
+    def same_format(self, other: "RawFrames") -> bool:
+        """Both hold one kind of sample, under one pattern, with one black level, white balance and tone curve."""
+        if (self.pattern, self.depth, self.lsb, self.black, self.gain_q) != (other.pattern, other.depth, other.lsb, other.black, other.gain_q):
+            return False
+        if self.tone is None or other.tone is None or self.tone is other.tone:
+            return self.tone is other.tone
+        return torch.equal(self.tone.cpu(), other.tone.cpu())
+
+    def format_struct(self) -> L.RawFormat:
+        """The ``ppms_raw_format`` of these frames."""
+        return L.RawFormat(self.sample_bytes, self.depth, self.lsb, _RAW_PATTERNS[self.pattern], self.black, self.gain_q, _RAW_SHIFT, (0, 0, 0))
+
+    def view_struct(self) -> L.RawView:
+        """The ``ppms_raw_view`` of these frames."""
+        return L.RawView(self.data.data_ptr(), self.frame_stride, self.pitch, 0)
+
+    def to_rgb(self) -> torch.Tensor:
+        """(N, 3, H0, W0) on the same device, uint8 at depth 8 and int16 levels in [0, 2^depth - 1] otherwise: the demosaic, black level and white
+        balance of include/ppms.h in torch integer ops -- what the feature means by the RGB levels of these frames (the kernels' operands are
+        ppms_video_ingest_u8's on them, with ``table``), and the path where the kernels cannot be used."""
+        top, h, w, dev = (1 << self.depth) - 1, self.height, self.width, self.device
+        s = (self.data.to(torch.int32) >> self.lsb) & top
+        if self.pattern == "mono":
+            v = torch.stack([s, s, s], dim=1)
+        else:
+            # one sample of margin all round, reflected without repeating the edge: row -1 is row 1, row h is row h - 2
+            ri = torch.tensor([1, *range(h), h - 2], device=dev)
+            ci = torch.tensor([1, *range(w), w - 2], device=dev)
+            p = s[:, ri][:, :, ci]
+            at = lambda dy, dx: p[:, 1 + dy:1 + dy + h, 1 + dx:1 + dx + w]
+            hor, ver = (at(0, -1) + at(0, 1) + 1) >> 1, (at(-1, 0) + at(1, 0) + 1) >> 1
+            cross = (at(-1, 0) + at(1, 0) + at(0, -1) + at(0, 1) + 2) >> 2
+            diag = (at(-1, -1) + at(-1, 1) + at(1, -1) + at(1, 1) + 2) >> 2
+            code = _RAW_PATTERNS[self.pattern]
+            py, px = (torch.arange(h, device=dev) & 1)[:, None], (torch.arange(w, device=dev) & 1)[None, :]
+            green = ((px ^ py ^ (code >> 1)) == 1).expand(h, w)
+            red_row = ((py ^ (code & 1)) == 0).expand(h, w)               # rows whose non-green sites are red
+            v = torch.stack([torch.where(green, torch.where(red_row, hor, ver), torch.where(red_row, s, diag)),
+                             torch.where(green, s, cross),
+                             torch.where(green, torch.where(red_row, ver, hor), torch.where(red_row, diag, s))], dim=1)
+        gain = torch.tensor(self.gain_q, dtype=torch.int32, device=dev).reshape(1, 3, 1, 1)
+        levels = ((v - self.black) * gain + (1 << (_RAW_SHIFT - 1))) >> _RAW_SHIFT
+        return levels.clamp_(0, top).to(torch.uint8 if self.depth == 8 else torch.int16)
+
+    def tone_on(self, device) -> Optional[torch.Tensor]:
+        """``tone`` on ``device`` (None stays None); copied there once."""
+        if self.tone is None:
+            return None
+        device = torch.device(device)
+        if device not in self._shared["tone"]:
+            self._shared["tone"][device] = self.tone.to(device).contiguous()
+        return self._shared["tone"][device]
+
+    def levels_to_float(self, levels: torch.Tensor) -> torch.Tensor:
+        """RGB levels (``to_rgb``'s, or their remap) -> the float32 video in [0, 255] they stand for: ``tone[level]``, or without a tone curve
+        ``level * (255.0 / (2^depth - 1))``."""
+        tone = self.tone_on(levels.device)
+        return _levels_to_float(levels, self.depth) if tone is None else tone[levels.long()]
+
+    def to_float(self) -> torch.Tensor:
+        """float32 (N, 3, H0, W0) in [0, 255]: the video the reference would be given."""
+        return self.levels_to_float(self.to_rgb())
+
+    def table(self, device) -> torch.Tensor:
+        """fp32 [2^depth] on ``device``: the normalised value of every level, what the ingest kernel looks up.  Without a tone curve
+        ``level_lut``'s tensor; with one ``2 * (tone / 255.0) - 1.0`` computed ON THE DEVICE, ``forward``'s own expression on ``to_float``'s
+        values -- for ``byte_lut``'s reason.  Built once per device and kept with the frames (the host waits for it once)."""
+        if self.tone is None:
+            return level_lut(device, self.depth)
+        device = torch.device(device)
+        dev = torch.device("cuda", torch.cuda.current_device() if device.index is None else device.index)
+        if dev not in self._shared["table"]:
+            self._shared["table"][dev] = (2 * (self.tone_on(dev) / 255.0) - 1.0).contiguous()
+            torch.cuda.current_stream(dev).synchronize()         # later calls may read it from any stream
+        return self._shared["table"][dev]
+
+
+class RawStereoVideo:
+    """Both views of a raw sensor video -- what ``batch_dict["stereo_video"]`` of ``forward_batch_test`` may be instead of a tensor: two
+    ``RawFrames`` of one size, frame count, device, pattern, sample format (depth, alignment), black level, white balance and tone curve.
+    ``len()``, slicing by frame range, ``to(device)``."""
+
+    def __init__(self, left: RawFrames, right: RawFrames):
+        if not isinstance(left, RawFrames) or not isinstance(right, RawFrames):
+            raise TypeError("RawStereoVideo: two RawFrames expected")
+        if (left.n, left.height, left.width) != (right.n, right.height, right.width):
+            raise ValueError(f"RawStereoVideo: the views differ: {(left.n, left.height, left.width)} and {(right.n, right.height, right.width)}")
+        if left.device != right.device:
+            raise ValueError("RawStereoVideo: both views need one device")
+        if not left.same_format(right):
+            raise ValueError("RawStereoVideo: the views differ in pattern, depth, alignment, black level, gains or tone curve: "
+                             f"{(left.pattern, left.depth, left.align, left.black, left.gains)} and "
+                             f"{(right.pattern, right.depth, right.align, right.black, right.gains)}")
+        self.left, self.right = left, right
+        self.depth = left.depth
+        self.height, self.width = left.height, left.width
+
+    def __len__(self) -> int:
+        return self.left.n
+
+    def __getitem__(self, frames: slice) -> "RawStereoVideo":
+        return RawStereoVideo(self.left[frames], self.right[frames])
+
+    def to(self, device) -> "RawStereoVideo":
+        """The selected frames' samples on ``device`` (1 byte per pixel and view; 2 for 10- and 12-bit samples)."""
+        return RawStereoVideo(self.left.to(device), self.right.to(device))
+
+
 _BORDERS = {"replicate": L.BORDER_REPLICATE, "constant": L.BORDER_CONSTANT}
 
 
@@ -525,7 +735,12 @@ class _ByteSource:
     def ingest(self, dst_fnet: L.SP, dst_cnet: L.SP, pad_left: int, pad_top: int, h: int, w: int) -> None:
         """One launch on the current stream: both encoders' first-layer operands of the n frames, ``pad_left`` / ``pad_top`` in front, h x w."""
         L.check(getattr(L.load(), self._entry)(*self._frames(), *self._maps, self.n, *self.size, pad_left, pad_top, h, w,
-                                               level_lut(self.device, self.depth).data_ptr(), dst_fnet, dst_cnet, L.stream_ptr()))
+                                               self._table().data_ptr(), dst_fnet, dst_cnet, L.stream_ptr()))
+
+    def _table(self) -> torch.Tensor:
+        """The level table of the launch: the float path's normalisation of every level of the source's depth (a source with a table of its own
+        answers with that)."""
+        return level_lut(self.device, self.depth)
 
     def held(self):
         """The tensors the launch reads (for record_stream)."""
@@ -579,6 +794,31 @@ class _YUVPlanes(_ByteSource):
         return _levels_to_float(left, self.depth), _levels_to_float(right, self.depth)
 
 
+class _RawPlanes(_ByteSource):
+    """A RawStereoVideo: ppms_video_ingest_raw demosaics, balances and looks up the samples as the camera driver left them; the level table is the
+    frames' own (their tone curve)."""
+
+    def __init__(self, video: RawStereoVideo, rectify: Optional[StereoRectifier] = None):
+        super().__init__("ppms_video_ingest_raw", len(video), (video.height, video.width), video.left.device, rectify, depth=video.depth)
+        self.video = video
+
+    def _frames(self):
+        v = self.video
+        return v.left.view_struct(), v.right.view_struct(), v.left.format_struct()      # host structs: read before the call returns
+
+    def _planes(self):
+        return self.video.left.data, self.video.right.data
+
+    def _table(self) -> torch.Tensor:
+        return self.video.left.table(self.device)
+
+    def float_views(self):
+        v = self.video
+        rgb = v.left.to_rgb(), v.right.to_rgb()
+        left, right = rgb if self.rectify is None else self.rectify.apply_levels(*rgb, self.depth)
+        return v.left.levels_to_float(left), v.right.levels_to_float(right)    # (the tone curve behind the blend, as in the kernel)
+
+
 def _checked_rectifier(who: str, rectify, device, h: int, w: int) -> StereoRectifier:
     """``rectify`` for raw frames h x w on ``device`` (host frames are only measured: the maps stay where they are)."""
     rectify.check_source(who, h, w)
@@ -586,10 +826,11 @@ def _checked_rectifier(who: str, rectify, device, h: int, w: int) -> StereoRecti
 
 
 def stereo_source(who: str, left, right=None, rectify: Optional[StereoRectifier] = None):
-    """The source of two views -- float or uint8 tensors (b, T, 3, H, W), or two ``YUVFrames`` -- or, with ``right`` None, of a window ``left`` of
-    a video: a tensor (T, 2, 3, H, W) or a ``YUVStereoVideo``.  Every argument check of the front doors is made here, under the name ``who``,
-    and touches no device: rectify= reads decoded bytes (TypeError for float frames), of its source size (ValueError), b = 1; two ``YUVFrames`` that
-    differ in depth, alignment or chroma subsampling are no stereo pair (ValueError)."""
+    """The source of two views -- float or uint8 tensors (b, T, 3, H, W), two ``YUVFrames`` or two ``RawFrames`` -- or, with ``right`` None, of a
+    window ``left`` of a video: a tensor (T, 2, 3, H, W), a ``YUVStereoVideo`` or a ``RawStereoVideo``.  Every argument check of the front doors is
+    made here, under the name ``who``, and touches no device: rectify= reads decoded bytes (TypeError for float frames), of its source size
+    (ValueError), b = 1; two ``YUVFrames`` that differ in depth, alignment or chroma subsampling, or two ``RawFrames`` that differ in pattern,
+    sample format, black level, gains or tone curve, are no stereo pair (ValueError)."""
     if rectify is not None and not isinstance(rectify, StereoRectifier):
         raise TypeError(f"{who}: rectify must be a StereoRectifier, got {type(rectify).__name__}")
     if isinstance(left, YUVFrames) or isinstance(right, YUVFrames):
@@ -600,6 +841,14 @@ def stereo_source(who: str, left, right=None, rectify: Optional[StereoRectifier]
         if rectify is not None:
             rectify = _checked_rectifier(who, rectify, left.left.device, left.height, left.width)
         return _YUVPlanes(left, rectify)
+    if isinstance(left, RawFrames) or isinstance(right, RawFrames):
+        if not (isinstance(left, RawFrames) and isinstance(right, RawFrames)):
+            raise TypeError(f"{who}: image1 is {type(left).__name__} and image2 is {type(right).__name__}; both views must be RawFrames or both tensors")
+        left, right = RawStereoVideo(left, right), None
+    if isinstance(left, RawStereoVideo):
+        if rectify is not None:
+            rectify = _checked_rectifier(who, rectify, left.left.device, left.height, left.width)
+        return _RawPlanes(left, rectify)
     views = (left,) if right is None else (left, right)
     for v in views:
         if not torch.is_tensor(v):
