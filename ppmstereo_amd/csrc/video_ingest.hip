@@ -1,0 +1,499 @@
+// The video doors of the C ABI (include/ppms.h: ppms_video_ingest_*): decoded or raw stereo video -> the first-layer operands of both encoders.
+// One kernel template over a Source, one check-and-launch path on the host.
+#include "common.h"
+
+namespace {
+
+// decoded video -> the first-layer operands of both encoders in one launch (ppms_video_ingest_u8 / ppms_video_ingest_yuv420 / ppms_video_ingest_yuv / ppms_video_ingest_raw):
+// what normalisation (a table the caller built with the float path's own torch expression: 256 entries, or 1 << depth for a source whose
+// table_by_depth is true, which also answers levels()), replicate padding (clamped source
+// coordinate), torch.cat([left, right]) and the two img_s2d launches produce from the fp32 images.  Thread = one output pixel x 8 channels
+// of one destination, as in img_s2d_kernel (encoder_ops.hip): indices [0, nf) serve the k = 2 operand of the 2 N images (left frames, then right frames),
+// [nf, total) the k = 4 operand of the N left frames.  Where a byte comes from is the Source: source(m, c, y, x) = channel c (R, G, B) of
+// pixel (y, x), already clamped into the frame, of image m.  Source rows have arbitrary widths and pitches: byte loads only.
+struct rgb_planes_source {                                                // planar RGB bytes, dense rows (ppms_video_ingest_u8)
+    const uint8_t *left, *right;
+    int64_t frame_stride;
+    int N, H0, W0;
+    static constexpr bool table_by_depth = false;                         // RGB bytes: the kernel's static 256-entry table
+    __device__ int operator()(int64_t m, int c, int y, int x) const {
+        const uint8_t* src = m < N ? left + m * frame_stride : right + (m - N) * frame_stride;
+        return src[((int64_t)c * H0 + y) * W0 + x];
+    }
+};
+
+struct yuv420_source {                                                    // pitched Y plane + half-resolution chroma (ppms_video_ingest_yuv420)
+    ppms_yuv_view left, right;
+    ppms_yuv_matrix mat;
+    int N;
+    static constexpr bool table_by_depth = false;
+    __device__ int operator()(int64_t m, int c, int y, int x) const {
+        const bool r = m >= N;
+        const int64_t n = r ? m - N : m;
+        const uint8_t *py = r ? right.y : left.y, *pu = r ? right.u : left.u, *pv = r ? right.v : left.v;
+        const int64_t oy = n * (r ? right.frame_stride_y : left.frame_stride_y) + (int64_t)y * (r ? right.pitch_y : left.pitch_y) + x;
+        const int64_t oc = n * (r ? right.frame_stride_c : left.frame_stride_c) + (int64_t)(y >> 1) * (r ? right.pitch_c : left.pitch_c) +
+                           (int64_t)(x >> 1) * (r ? right.step_c : left.step_c);      // nearest chroma sample of the clamped luma pixel
+        // the three channels of a pixel repeat these loads; they are the same addresses, and the compiler merges them
+        const int d = py[oy] - mat.y_off, e = pu[oc] - 128, f = pv[oc] - 128;
+        const int acc = mat.cy * d + (c == 0 ? mat.crv * f : c == 1 ? -mat.cgu * e - mat.cgv * f : mat.cbu * e) + (1 << (mat.shift - 1));
+        const int q = acc >> mat.shift;                                   // arithmetic shift: floor
+        return q < 0 ? 0 : (q > 255 ? 255 : q);
+    }
+};
+
+// samples of T (bytes, or little-endian 16-bit words holding 10 or 12 bits) with any of the three chroma subsamplings (ppms_video_ingest_yuv):
+// yuv420_source's conversion on `depth`-bit samples, RGB levels in [0, 2^depth - 1].  Every stride of the views is in bytes, every offset 64-bit;
+// loads are of one T (rows have arbitrary pitches; the host checks that they are even for 16-bit samples).  A sample is masked to `depth` bits
+// and the result clamped, so the level is always an index inside the table of 1 << depth entries.
+template <class T>
+struct yuv_source {
+    ppms_yuv_view left, right;
+    ppms_yuv_matrix mat;
+    int N, depth, lsb, sub_x, sub_y;                                      // uniform: the ppms_yuv_format
+    static constexpr bool table_by_depth = true;
+    __host__ __device__ int levels() const { return 1 << depth; }
+    __device__ int sample(const uint8_t* p, int64_t o) const { return ((int)*(const T*)(p + o) >> lsb) & ((1 << depth) - 1); }
+    __device__ int operator()(int64_t m, int c, int y, int x) const {
+        const bool r = m >= N;
+        const int64_t n = r ? m - N : m;
+        const uint8_t *py = r ? right.y : left.y, *pu = r ? right.u : left.u, *pv = r ? right.v : left.v;
+        const int64_t oy = n * (r ? right.frame_stride_y : left.frame_stride_y) + (int64_t)y * (r ? right.pitch_y : left.pitch_y) + (int64_t)x * (int)sizeof(T);
+        const int64_t oc = n * (r ? right.frame_stride_c : left.frame_stride_c) + (int64_t)(y >> sub_y) * (r ? right.pitch_c : left.pitch_c) +
+                           (int64_t)(x >> sub_x) * (r ? right.step_c : left.step_c);  // nearest chroma sample of the clamped luma pixel
+        // the three channels of a pixel repeat these loads; they are the same addresses, and the compiler merges them
+        const int mid = 1 << (depth - 1), top = (1 << depth) - 1;
+        const int d = sample(py, oy) - mat.y_off, e = sample(pu, oc) - mid, f = sample(pv, oc) - mid;
+        const int acc = mat.cy * d + (c == 0 ? mat.crv * f : c == 1 ? -mat.cgu * e - mat.cgv * f : mat.cbu * e) + (1 << (mat.shift - 1));
+        const int q = acc >> mat.shift;                                   // arithmetic shift: floor
+        return q < 0 ? 0 : (q > top ? top : q);
+    }
+};
+
+// a sensor's raw frames (ppms_video_ingest_raw): one pitched plane of T samples under a 2 x 2 colour-filter mosaic, or monochrome.  The missing
+// colours of a pixel are bilinear means of its neighbours (the arithmetic: include/ppms.h); a neighbour outside the frame is REFLECTED without
+// repeating the edge (-1 -> 1, n -> n - 2), which keeps its colour.  `pattern` is uniform, and which colour a site carries is parity arithmetic:
+// a site is green where (x ^ y ^ (pattern >> 1)) is odd, and rows with (y ^ pattern) even hold the red sites.  (y, x) arrives inside the hs x ws
+// frame, and with hs, ws >= 2 (the host refuses less for a colour pattern) so does every reflected neighbour: no load leaves the frame.
+template <class T>
+struct raw_source {
+    ppms_raw_view left, right;
+    int N, hs, ws;                                                        // frames per view, the SOURCE frame size
+    int depth, lsb, pattern, black, gain_r, gain_g, gain_b, shift;        // uniform: the ppms_raw_format
+    static constexpr bool table_by_depth = true;
+    __host__ __device__ int levels() const { return 1 << depth; }
+    __device__ int operator()(int64_t m, int c, int y, int x) const {
+        const bool r = m >= N;
+        const uint8_t* p = (r ? right.data : left.data) + (r ? m - N : m) * (r ? right.frame_stride : left.frame_stride);
+        const int64_t pitch = r ? right.pitch : left.pitch;
+        const int top = (1 << depth) - 1;
+        // the three channels of a pixel repeat these loads; they are the same addresses, and the compiler merges them
+        const auto s = [&](int yy, int xx) { return ((int)*(const T*)(p + yy * pitch + (int64_t)xx * (int)sizeof(T)) >> lsb) & top; };
+        int v;
+        if (pattern == 4) {                                               // MONO
+            v = s(y, x);
+        } else {
+            const int ym = y > 0 ? y - 1 : 1, yp = y < hs - 1 ? y + 1 : hs - 2, xm = x > 0 ? x - 1 : 1, xp = x < ws - 1 ? x + 1 : ws - 2;
+            const bool green = ((x ^ y ^ (pattern >> 1)) & 1) != 0, red_row = ((y ^ pattern) & 1) == 0;
+            if (c == (green ? 1 : (red_row ? 0 : 2)))
+                v = s(y, x);
+            else if (green)                                               // R or B at a green site: the two neighbours that carry it
+                v = (c == 0) == red_row ? (s(y, xm) + s(y, xp) + 1) >> 1 : (s(ym, x) + s(yp, x) + 1) >> 1;
+            else if (c == 1)                                              // G at a red or blue site
+                v = (s(ym, x) + s(yp, x) + s(y, xm) + s(y, xp) + 2) >> 2;
+            else                                                          // B at a red site, R at a blue site
+                v = (s(ym, xm) + s(ym, xp) + s(yp, xm) + s(yp, xp) + 2) >> 2;
+        }
+        const int q = ((v - black) * (c == 0 ? gain_r : c == 1 ? gain_g : gain_b) + (1 << (shift - 1))) >> shift;     // arithmetic shift: floor
+        return q < 0 ? 0 : (q > top ? top : q);
+    }
+};
+
+// a source behind a rectification map (ppms_video_ingest_u8_remap / ppms_video_ingest_yuv420_remap; the arithmetic: include/ppms.h): (y, x) is a
+// pixel of the RECTIFIED frame, the view's map names its four taps in the inner source's frame of hs x ws, and the blend is integer.  Every
+// tap coordinate is clamped into that frame before the inner source sees it, whatever the map holds: in constant mode a tap outside the frame
+// contributes `fill` instead of what lies at the clamped address.
+template <class Inner>
+struct remapped_source {
+    Inner inner;                                                          // built with the source frame size
+    ppms_remap_view left, right;
+    int N;
+    static constexpr bool table_by_depth = Inner::table_by_depth;
+    __host__ __device__ int levels() const { return inner.levels(); }      // (asked of a table_by_depth source only)
+    __device__ int operator()(int64_t m, int c, int y, int x) const {
+        const bool r = m >= N;
+        const int64_t o = (int64_t)y * (r ? right.pitch : left.pitch) + x;
+        // the three channels of a pixel repeat these loads; they are the same addresses, and the compiler merges them
+        const short2 xy = ((const short2*)(r ? right.xy : left.xy))[o];
+        const int fr = (r ? right.frac : left.frac)[o];
+        const int fx = fr & 31, fy = (fr >> 5) & 31;
+        const int hs = left.hs, ws = left.ws, border = r ? right.border : left.border, fill = r ? right.fill : left.fill;
+        int acc = 512;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int yy = (int)xy.y + (t >> 1), xx = (int)xy.x + (t & 1);    // int16 + 1: 32-bit arithmetic
+            const bool outside = yy < 0 || yy > hs - 1 || xx < 0 || xx > ws - 1;
+            const int cy = yy < 0 ? 0 : (yy > hs - 1 ? hs - 1 : yy), cx = xx < 0 ? 0 : (xx > ws - 1 ? ws - 1 : xx);
+            const int p = border && outside ? fill : inner(m, c, cy, cx);
+            acc += ((t & 1) ? fx : 32 - fx) * ((t >> 1) ? fy : 32 - fy) * p;
+        }
+        return acc >> 10;                                                 // weights sum to 1024: in [0, the inner source's top level]
+    }
+};
+
+template <class Source>
+__global__ __launch_bounds__(256) void video_ingest_kernel(Source source, int N, int H0, int W0, int pad_left, int pad_top, int H, int W,
+                                                           const float* __restrict__ lut, ppms_sp dst_fnet, ppms_sp dst_cnet, int64_t nf, int64_t total) {
+    const float* tab;
+    if constexpr (Source::table_by_depth) {                               // 1 << depth entries of dynamic LDS (sized by the launch): every thread fills
+        extern __shared__ float level_tab[];                              // its stride of the table, and leaves only behind the barrier
+        for (int i = threadIdx.x, n = source.levels(); i < n; i += 256) level_tab[i] = lut[i];
+        tab = level_tab;
+    } else {
+        __shared__ float byte_tab[256];
+        byte_tab[threadIdx.x] = lut[threadIdx.x];
+        tab = byte_tab;
+    }
+    __syncthreads();
+    int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const bool fnet = idx < nf;
+    if (!fnet) idx -= nf;
+    const ppms_sp dst = fnet ? dst_fnet : dst_cnet;
+    const int ks = fnet ? 1 : 2, k = 1 << ks;                             // k = 2 (fnet) or 4 (cnet stem)
+    const int groups = dst.c >> 3;
+    const int g8 = (int)(idx % groups);
+    const int64_t p = idx / groups;
+    const int OW = W >> ks, OH = H >> ks;
+    const int j = (int)(p % OW), i = (int)((p / OW) % OH);
+    const int64_t m = p / ((int64_t)OW * OH);                             // image: left frames 0 .. N - 1, then the right frames
+    bf16x8 oh, ol;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int ch = g8 * 8 + e;
+        float v = 0.0f;
+        if (ch < k * k * 3) {
+            const int ph = ch / 3, c = ch - ph * 3;
+            int y = k * i + (ph >> ks) - pad_top, x = k * j + (ph & (k - 1)) - pad_left;
+            y = y < 0 ? 0 : (y > H0 - 1 ? H0 - 1 : y);                    // replicate padding
+            x = x < 0 ? 0 : (x > W0 - 1 ? W0 - 1 : x);
+            v = tab[source(m, c, y, x)];
+        }
+        bf16_t hh, ll;
+        split_bf16(v, hh, ll);
+        oh[e] = hh;
+        ol[e] = ll;
+    }
+    const int64_t od = p * dst.ld + g8 * 8;
+    *(bf16x8*)((bf16_t*)dst.hi + od) = oh;
+    *(bf16x8*)((bf16_t*)dst.lo + od) = ol;
+}
+
+}  // namespace
+
+// ---- host side: every entry point fills one ingest_call, runs its door's checks and goes through ingest_samples() to the one launch ----------
+
+// what all 8 entry points take behind their source: the entry's name for the messages, geometry, table, destinations and stream
+struct ingest_call {
+    const char* who;
+    int N, H0, W0, pad_left, pad_top, H, W;
+    const float* lut;
+    ppms_sp dst_fnet, dst_cnet;
+    void* stream;
+};
+
+// what every entry point checks about sizes, pads, table and destinations, and its launch
+template <class Source>
+static int video_ingest_launch(const ingest_call& a, const Source& source) {
+    const char* who = a.who;
+    const int N = a.N, H0 = a.H0, W0 = a.W0, pad_left = a.pad_left, pad_top = a.pad_top, H = a.H, W = a.W;
+    PPMS_REQUIRE(a.lut, "%s: null table pointer", who);
+    PPMS_REQUIRE(N > 0 && H0 > 0 && W0 > 0 && H > 0 && W > 0, "%s: N = %d, H0 = %d, W0 = %d, H = %d, W = %d must be positive", who, N, H0, W0, H, W);
+    PPMS_REQUIRE(H % 4 == 0 && W % 4 == 0, "%s: H = %d, W = %d must be multiples of 4", who, H, W);
+    PPMS_REQUIRE(pad_left >= 0 && pad_top >= 0 && (int64_t)pad_top + H0 <= H && (int64_t)pad_left + W0 <= W,
+                 "%s: pad_left = %d, pad_top = %d with a %d x %d source do not fit the %d x %d padded image", who, pad_left, pad_top, H0, W0, H, W);
+    PPMS_REQUIRE(a.dst_fnet.hi || a.dst_cnet.hi, "%s: both destinations skipped", who);
+    const ppms_sp* dsts[2] = {&a.dst_fnet, &a.dst_cnet};
+    int64_t threads[2] = {0, 0};
+    for (int s = 0; s < 2; ++s) {
+        const ppms_sp& d = *dsts[s];
+        if (!d.hi) continue;                                               // skipped
+        const int k = s == 0 ? 2 : 4;
+        PPMS_REQUIRE(d.lo && d.c >= k * k * 3 && d.c % 8 == 0 && d.ld % 8 == 0 && d.ld >= d.c && (((uintptr_t)d.hi | (uintptr_t)d.lo) & 15) == 0,
+                     "%s: the k = %d destination view needs >= %d channels, multiples of 8, 16-B aligned", who, k, k * k * 3);
+        threads[s] = (int64_t)(s == 0 ? 2 : 1) * N * (H / k) * (W / k) * (d.c / 8);
+    }
+    const int64_t total = threads[0] + threads[1];
+    PPMS_REQUIRE((total + 255) / 256 <= 0x7fffffff, "%s: %lld threads exceed one grid", who, (long long)total);
+    size_t table_bytes = 0;                                                // dynamic LDS: the level table of a source that sizes it by depth
+    if constexpr (Source::table_by_depth) table_bytes = sizeof(float) * (size_t)source.levels();
+    hipLaunchKernelGGL(video_ingest_kernel<Source>, dim3(ceil_div(total, 256)), dim3(256), table_bytes, (hipStream_t)a.stream, source, N, H0, W0, pad_left, pad_top,
+                       H, W, a.lut, a.dst_fnet, a.dst_cnet, threads[0], total);
+    return ppms_check_launch(who);
+}
+
+// what the remap entry points check about the two maps of a W0 columns wide rectified frame (`fill_max`: the top level of the source's samples)
+static int remap_check(const char* who, const ppms_remap_view* lmap, const ppms_remap_view* rmap, int W0, int fill_max) {
+    PPMS_REQUIRE(lmap && rmap, "%s: null map pointer (lmap, rmap)", who);
+    const ppms_remap_view* maps[2] = {lmap, rmap};
+    for (int s = 0; s < 2; ++s) {
+        const ppms_remap_view& v = *maps[s];
+        const char* side = s == 0 ? "lmap" : "rmap";
+        PPMS_REQUIRE(v.xy && v.frac, "%s: null xy or frac pointer in %s", who, side);
+        PPMS_REQUIRE(v.pitch >= W0, "%s: %s pitch = %d is less than W0 = %d", who, side, v.pitch, W0);
+        PPMS_REQUIRE(v.hs >= 1 && v.hs <= 32768 && v.ws >= 1 && v.ws <= 32768, "%s: %s source frame hs = %d, ws = %d must lie in [1, 32768]", who, side,
+                     v.hs, v.ws);
+        PPMS_REQUIRE(v.border == 0 || v.border == 1, "%s: %s border = %d must be 0 (replicate) or 1 (constant)", who, side, v.border);
+        PPMS_REQUIRE(v.fill >= 0 && v.fill <= fill_max, "%s: %s fill = %d must lie in [0, %d]", who, side, v.fill, fill_max);
+        PPMS_REQUIRE(v.reserved == 0, "%s: %s reserved = %d must be 0", who, side, v.reserved);
+        PPMS_REQUIRE(((uintptr_t)v.xy & 3) == 0 && ((uintptr_t)v.frac & 1) == 0, "%s: %s misaligned pointer: xy needs 4 bytes, frac 2", who, side);
+    }
+    PPMS_REQUIRE(lmap->hs == rmap->hs && lmap->ws == rmap->ws, "%s: lmap and rmap differ in hs, ws: %d x %d and %d x %d", who, lmap->hs, lmap->ws, rmap->hs,
+                 rmap->ws);
+    return PPMS_OK;
+}
+
+// how a door's samples are stored: the head that ppms_yuv_format and ppms_raw_format share
+struct sample_format {
+    int sample_bytes, depth, lsb;
+};
+template <class Format>
+static sample_format sample_format_of(const Format* f) {                  // (a null format reads as bytes here and is refused by the door's own check)
+    return f ? sample_format{f->sample_bytes, f->depth, f->lsb} : sample_format{1, 8, 0};
+}
+
+static int sample_format_check(const char* who, const sample_format& f) {
+    const int sb = f.sample_bytes;
+    PPMS_REQUIRE(sb == 1 || sb == 2, "%s: sample_bytes = %d must be 1 or 2", who, sb);
+    PPMS_REQUIRE(sb == 1 ? f.depth == 8 : (f.depth == 10 || f.depth == 12),
+                 "%s: depth = %d does not go with sample_bytes = %d (8 with 1; 10 or 12 with 2)", who, f.depth, sb);
+    PPMS_REQUIRE(f.lsb == 0 || (sb == 2 && f.lsb == 16 - f.depth), "%s: lsb = %d must be 0, or 16 - depth for 16-bit words", who, f.lsb);
+    return PPMS_OK;
+}
+
+// one pitched plane of a view's frames -- `rows` rows of `row_bytes` (a row's first sample to the end of its last) -- and how the messages name it
+struct plane_extent {
+    const char *suffix, *kind, *whole;                                    // "_y", "luma ", "luma plane" / "_c", "chroma ", "chroma plane" / "", "", "frame"
+    int64_t frame_stride;
+    int pitch, rows;
+    int64_t row_bytes;
+    const char* wname;                                                    // the row's width in samples, named in the pitch message (nullptr: left out)
+    int width;
+};
+
+// the planes of one view (`pointers`: all their base pointers or-ed together): even pointers and strides under 16-bit samples, every pitch >= its
+// row, every frame stride >= its plane -- in that order over all planes.  `any_stride_of_one_frame`: the raw door never adds a single frame's stride
+static int plane_extent_check(const char* who, const char* side, int sample_bytes, uintptr_t pointers, const plane_extent* planes, int count,
+                              bool any_stride_of_one_frame) {
+    if (sample_bytes == 2) {
+        uintptr_t bits = pointers;
+        for (int i = 0; i < count; ++i) bits |= (uintptr_t)planes[i].frame_stride | (uintptr_t)planes[i].pitch;
+        PPMS_REQUIRE((bits & 1) == 0, "%s: %s view: an odd pointer or stride; 16-bit samples need even pointers, pitches and frame strides", who, side);
+    }
+    for (int i = 0; i < count; ++i) {
+        const plane_extent& p = planes[i];
+        char width[48] = "";
+        if (p.wname) snprintf(width, sizeof(width), " (%s = %d)", p.wname, p.width);
+        PPMS_REQUIRE(p.pitch >= p.row_bytes, "%s: %s pitch%s = %d is less than a %srow's %lld bytes%s", who, side, p.suffix, p.pitch, p.kind, (long long)p.row_bytes,
+                     width);
+    }
+    for (int i = 0; i < count; ++i) {
+        const plane_extent& p = planes[i];
+        PPMS_REQUIRE(any_stride_of_one_frame || p.frame_stride >= (int64_t)(p.rows - 1) * p.pitch + p.row_bytes, "%s: %s frame_stride%s = %lld is less than a %s",
+                     who, side, p.suffix, (long long)p.frame_stride, p.whole);
+    }
+    return PPMS_OK;
+}
+
+// what the four YUV entry points check about the format, the views (frames of H0 x W0, named `hname` x `wname` in the messages) and the matrix.
+// `shift_max`: the 4:2:0 entries accept shift up to 20, the generic ones up to 26 - depth (18 at depth 8); both keep every sum inside 32 bits
+static int yuv_check(const ingest_call& a, const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m, const ppms_yuv_format* fmt,
+                     int shift_max, int H0, int W0, const char* hname, const char* wname) {
+    const char* who = a.who;
+    const int N = a.N;
+    PPMS_REQUIRE(left && right && m && fmt && a.lut, "%s: null view, matrix, format or table pointer", who);
+    PPMS_REQUIRE(N > 0 && H0 > 0 && W0 > 0, "%s: N = %d, %s = %d, %s = %d must be positive", who, N, hname, H0, wname, W0);
+    const ppms_yuv_format& f = *fmt;
+    const int sb = f.sample_bytes;
+    if (const int rc = sample_format_check(who, sample_format_of(fmt))) return rc;
+    PPMS_REQUIRE((f.sub_x == 1 && f.sub_y == 1) || (f.sub_x == 1 && f.sub_y == 0) || (f.sub_x == 0 && f.sub_y == 0),
+                 "%s: sub_x = %d, sub_y = %d must be (1, 1) 4:2:0, (1, 0) 4:2:2 or (0, 0) 4:4:4", who, f.sub_x, f.sub_y);
+    PPMS_REQUIRE(f.reserved[0] == 0 && f.reserved[1] == 0 && f.reserved[2] == 0, "%s: format: reserved must be 0", who);
+    const int Hc = (H0 + (1 << f.sub_y) - 1) >> f.sub_y, Wc = (W0 + (1 << f.sub_x) - 1) >> f.sub_x;      // chroma planes: ceil(H0 / 2^sub_y) x ceil(W0 / 2^sub_x)
+    const ppms_yuv_view* views[2] = {left, right};
+    for (int s = 0; s < 2; ++s) {
+        const ppms_yuv_view& v = *views[s];
+        const char* side = s == 0 ? "left" : "right";
+        PPMS_REQUIRE(v.y && v.u && v.v, "%s: null plane pointer in the %s view", who, side);
+        PPMS_REQUIRE(v.step_c == sb || v.step_c == 2 * sb, "%s: %s step_c = %d must be %d (planar) or %d (interleaved)", who, side, v.step_c, sb, 2 * sb);
+        PPMS_REQUIRE(v.reserved == 0, "%s: %s view: reserved = %d must be 0", who, side, v.reserved);
+        const plane_extent planes[2] = {{"_y", "luma ", "luma plane", v.frame_stride_y, v.pitch_y, H0, (int64_t)W0 * sb, wname, W0},
+                                        {"_c", "chroma ", "chroma plane", v.frame_stride_c, v.pitch_c, Hc, (int64_t)v.step_c * (Wc - 1) + sb, nullptr, 0}};
+        if (const int rc = plane_extent_check(who, side, sb, (uintptr_t)v.y | (uintptr_t)v.u | (uintptr_t)v.v, planes, 2, false)) return rc;
+    }
+    PPMS_REQUIRE(m->shift >= 8 && m->shift <= shift_max, "%s: shift = %d must lie in [8, %d] at depth %d", who, m->shift, shift_max, f.depth);
+    PPMS_REQUIRE(m->reserved == 0, "%s: matrix: reserved = %d must be 0", who, m->reserved);
+    // coefficients below 4.0 keep every sum of the conversion inside 32 bits: three terms below 4 * 2^shift * 2^depth <= 2^28 each, plus 2^(shift - 1)
+    // (the 4:2:0 entries' shift = 20: 2^22 (255 + 128 + 128) + 2^19 < 2^31)
+    const int32_t lim = 4 << m->shift;
+    PPMS_REQUIRE(m->y_off >= 0 && m->y_off < (1 << f.depth) && m->cy >= 0 && m->cy < lim && m->crv >= 0 && m->crv < lim && m->cgu >= 0 && m->cgu < lim &&
+                     m->cgv >= 0 && m->cgv < lim && m->cbu >= 0 && m->cbu < lim,
+                 "%s: y_off must lie in [0, %d] and every coefficient in [0, 4 << shift)", who, (1 << f.depth) - 1);
+    return PPMS_OK;
+}
+
+// what both ppms_video_ingest_raw entry points check about the format and the views (frames of H0 x W0, named `hname` x `wname` in the messages)
+static int raw_check(const ingest_call& a, const ppms_raw_view* left, const ppms_raw_view* right, const ppms_raw_format* fmt, int H0, int W0,
+                     const char* hname, const char* wname) {
+    const char* who = a.who;
+    const int N = a.N;
+    PPMS_REQUIRE(left && right && fmt && a.lut, "%s: null view, format or table pointer", who);
+    PPMS_REQUIRE(N > 0 && H0 > 0 && W0 > 0, "%s: N = %d, %s = %d, %s = %d must be positive", who, N, hname, H0, wname, W0);
+    const ppms_raw_format& f = *fmt;
+    if (const int rc = sample_format_check(who, sample_format_of(fmt))) return rc;
+    PPMS_REQUIRE(f.pattern >= 0 && f.pattern <= 4, "%s: pattern = %d must be 0 (RGGB), 1 (BGGR), 2 (GRBG), 3 (GBRG) or 4 (MONO)", who, f.pattern);
+    PPMS_REQUIRE(f.black >= 0 && f.black < (1 << f.depth), "%s: black = %d must lie in [0, %d]", who, f.black, (1 << f.depth) - 1);
+    PPMS_REQUIRE(f.shift >= 4 && f.shift <= 14, "%s: shift = %d must lie in [4, 14]", who, f.shift);
+    // gains below 16.0 keep every sum inside 32 bits: 2^12 * 2^18 + 2^13 < 2^31 at depth 12 and shift = 14
+    const int32_t lim = 16 << f.shift;
+    PPMS_REQUIRE(f.gain[0] >= 0 && f.gain[0] < lim && f.gain[1] >= 0 && f.gain[1] < lim && f.gain[2] >= 0 && f.gain[2] < lim,
+                 "%s: every gain must lie in [0, 16 << shift)", who);
+    PPMS_REQUIRE(f.reserved[0] == 0 && f.reserved[1] == 0 && f.reserved[2] == 0, "%s: format: reserved must be 0", who);
+    PPMS_REQUIRE(f.pattern == 4 || (H0 >= 2 && W0 >= 2), "%s: a colour pattern needs a frame of at least 2 x 2, got %s = %d, %s = %d", who, hname, H0, wname, W0);
+    const ppms_raw_view* views[2] = {left, right};
+    for (int s = 0; s < 2; ++s) {
+        const ppms_raw_view& v = *views[s];
+        const char* side = s == 0 ? "left" : "right";
+        PPMS_REQUIRE(v.data, "%s: null data pointer in the %s view", who, side);
+        PPMS_REQUIRE(v.reserved == 0, "%s: %s view: reserved = %d must be 0", who, side, v.reserved);
+        const plane_extent plane{"", "", "frame", v.frame_stride, v.pitch, H0, (int64_t)W0 * f.sample_bytes, wname, W0};
+        if (const int rc = plane_extent_check(who, side, f.sample_bytes, (uintptr_t)v.data, &plane, 1, N == 1)) return rc;
+    }
+    return PPMS_OK;
+}
+
+// the rectification maps of a _remap entry point (a plain entry point passes none: nullptr)
+struct remap_maps {
+    const ppms_remap_view *left, *right;
+};
+
+// the way of all 8 entry points: the maps' check (with them the source frames are the maps' hs x ws, not H0 x W0), the door's own `check(hs, ws,
+// hname, wname)` of its views against those frames, then the launch of `make(T{}, hs, ws)` -- the door's source reading samples of T from frames of
+// hs x ws -- behind the maps if there are any.  `fill` of a map is a level of the format's depth (a format that names no depth is refused by
+// `check`, right behind the maps, which bound hs and ws for it)
+template <class Check, class Make>
+static int ingest_samples(const ingest_call& a, const sample_format& f, const remap_maps* maps, Check check, Make make) {
+    int hs = a.H0, ws = a.W0;
+    if (maps) {
+        if (const int rc = remap_check(a.who, maps->left, maps->right, a.W0, f.depth == 10 || f.depth == 12 ? (1 << f.depth) - 1 : 255)) return rc;
+        hs = maps->left->hs, ws = maps->left->ws;
+    }
+    if (const int rc = check(hs, ws, maps ? "hs" : "H0", maps ? "ws" : "W0")) return rc;
+    const auto launch = [&](auto sample) {
+        auto inner = make(sample, hs, ws);
+        if (!maps) return video_ingest_launch(a, inner);
+        return video_ingest_launch(a, remapped_source<decltype(inner)>{inner, *maps->left, *maps->right, a.N});
+    };
+    return f.sample_bytes == 1 ? launch(uint8_t{}) : launch(uint16_t{});
+}
+
+static int ingest_u8(const ingest_call& a, const uint8_t* left, const uint8_t* right, int64_t frame_stride, const remap_maps* maps) {
+    PPMS_REQUIRE(left && right, "%s: null source pointer", a.who);
+    return ingest_samples(
+        a, sample_format{1, 8, 0}, maps,
+        [&](int hs, int ws, const char* hname, const char* wname) -> int {
+            PPMS_REQUIRE(frame_stride >= (int64_t)3 * hs * ws, "%s: frame_stride = %lld is less than a %sframe's 3 * %s * %s bytes", a.who, (long long)frame_stride,
+                         maps ? "source " : "", hname, wname);
+            return PPMS_OK;
+        },
+        [&](auto, int hs, int ws) { return rgb_planes_source{left, right, frame_stride, a.N, hs, ws}; });
+}
+
+template <class Make>
+static int ingest_yuv(const ingest_call& a, const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m, const ppms_yuv_format* fmt,
+                      int shift_max, const remap_maps* maps, Make make) {
+    return ingest_samples(
+        a, sample_format_of(fmt), maps,
+        [&](int hs, int ws, const char* hname, const char* wname) { return yuv_check(a, left, right, m, fmt, shift_max, hs, ws, hname, wname); }, make);
+}
+
+// the yuv420 entry points: checked as the format {1, 8, 0, 1, 1} with shift up to 20 (the generic entries stop at 26 - 8), read by yuv420_source --
+// yuv_source<uint8_t> writes the same bits and takes a tenth longer (docs/LOG_r10.md)
+static int ingest_yuv420(const ingest_call& a, const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m, const remap_maps* maps) {
+    static const ppms_yuv_format bytes_420 = {1, 8, 0, 1, 1, {0, 0, 0}};
+    return ingest_yuv(a, left, right, m, &bytes_420, 20, maps, [&](auto, int, int) { return yuv420_source{*left, *right, *m, a.N}; });
+}
+
+static int ingest_yuv_format(const ingest_call& a, const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m, const ppms_yuv_format* f,
+                             const remap_maps* maps) {
+    return ingest_yuv(a, left, right, m, f, 26 - sample_format_of(f).depth, maps,
+                      [&](auto sample, int, int) { return yuv_source<decltype(sample)>{*left, *right, *m, a.N, f->depth, f->lsb, f->sub_x, f->sub_y}; });
+}
+
+static int ingest_raw(const ingest_call& a, const ppms_raw_view* left, const ppms_raw_view* right, const ppms_raw_format* f, const remap_maps* maps) {
+    return ingest_samples(
+        a, sample_format_of(f), maps,
+        [&](int hs, int ws, const char* hname, const char* wname) { return raw_check(a, left, right, f, hs, ws, hname, wname); },
+        [&](auto sample, int hs, int ws) {
+            return raw_source<decltype(sample)>{*left, *right, a.N, hs, ws, f->depth, f->lsb, f->pattern, f->black, f->gain[0], f->gain[1], f->gain[2], f->shift};
+        });
+}
+
+// the trailing arguments every entry point declares, and the ingest_call they fill
+#define INGEST_TAIL int N, int H0, int W0, int pad_left, int pad_top, int H, int W, const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream
+#define INGEST_CALL(name) ingest_call{name, N, H0, W0, pad_left, pad_top, H, W, lut, dst_fnet, dst_cnet, stream}
+
+extern "C" int ppms_video_ingest_u8(const uint8_t* left, const uint8_t* right, int64_t frame_stride, INGEST_TAIL) {
+    return ingest_u8(INGEST_CALL("video_ingest_u8"), left, right, frame_stride, nullptr);
+}
+extern "C" int ppms_video_ingest_u8_remap(const uint8_t* left, const uint8_t* right, int64_t frame_stride, const ppms_remap_view* lmap,
+                                          const ppms_remap_view* rmap, INGEST_TAIL) {
+    const remap_maps maps{lmap, rmap};
+    return ingest_u8(INGEST_CALL("video_ingest_u8_remap"), left, right, frame_stride, &maps);
+}
+
+extern "C" int ppms_video_ingest_yuv420(const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m, INGEST_TAIL) {
+    return ingest_yuv420(INGEST_CALL("video_ingest_yuv420"), left, right, m, nullptr);
+}
+extern "C" int ppms_video_ingest_yuv420_remap(const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m, const ppms_remap_view* lmap,
+                                              const ppms_remap_view* rmap, INGEST_TAIL) {
+    const remap_maps maps{lmap, rmap};
+    return ingest_yuv420(INGEST_CALL("video_ingest_yuv420_remap"), left, right, m, &maps);
+}
+
+extern "C" int ppms_video_ingest_yuv(const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m, const ppms_yuv_format* fmt, INGEST_TAIL) {
+    return ingest_yuv_format(INGEST_CALL("video_ingest_yuv"), left, right, m, fmt, nullptr);
+}
+extern "C" int ppms_video_ingest_yuv_remap(const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m, const ppms_yuv_format* fmt,
+                                           const ppms_remap_view* lmap, const ppms_remap_view* rmap, INGEST_TAIL) {
+    const remap_maps maps{lmap, rmap};
+    return ingest_yuv_format(INGEST_CALL("video_ingest_yuv_remap"), left, right, m, fmt, &maps);
+}
+
+extern "C" int ppms_video_ingest_raw(const ppms_raw_view* left, const ppms_raw_view* right, const ppms_raw_format* fmt, INGEST_TAIL) {
+    return ingest_raw(INGEST_CALL("video_ingest_raw"), left, right, fmt, nullptr);
+}
+extern "C" int ppms_video_ingest_raw_remap(const ppms_raw_view* left, const ppms_raw_view* right, const ppms_raw_format* fmt, const ppms_remap_view* lmap,
+                                           const ppms_remap_view* rmap, INGEST_TAIL) {
+    const remap_maps maps{lmap, rmap};
+    return ingest_raw(INGEST_CALL("video_ingest_raw_remap"), left, right, fmt, &maps);
+}
+
+extern "C" int ppms_yuv_struct_sizes(int* view, int* matrix) {
+    if (view) *view = (int)sizeof(ppms_yuv_view);
+    if (matrix) *matrix = (int)sizeof(ppms_yuv_matrix);
+    return PPMS_OK;
+}
+extern "C" int ppms_yuv_format_struct_size(int* fmt) {
+    if (fmt) *fmt = (int)sizeof(ppms_yuv_format);
+    return PPMS_OK;
+}
+extern "C" int ppms_remap_struct_size(int* view) {
+    if (view) *view = (int)sizeof(ppms_remap_view);
+    return PPMS_OK;
+}
+extern "C" int ppms_raw_struct_sizes(int* view, int* format) {
+    if (view) *view = (int)sizeof(ppms_raw_view);
+    if (format) *format = (int)sizeof(ppms_raw_format);
+    return PPMS_OK;
+}

@@ -42,23 +42,7 @@ class InputPadder:
         return x[..., top:x.shape[-2] - bottom, left:x.shape[-1] - right]
 
 
-_BYTE_LUT: Dict[int, torch.Tensor] = {}
-
-
-def byte_lut(device) -> torch.Tensor:
-    """fp32 [256] on `device`: the normalised value of every byte, from the expression ``forward`` applies to float images ON THE SAME
-    DEVICE -- torch's division by a Python scalar need not round like a division written elsewhere, so the table is what makes the uint8
-    path the float path's bits.  Built once per device (the host waits for it once)."""
-    device = torch.device(device)
-    idx = torch.cuda.current_device() if device.index is None else device.index
-    if idx not in _BYTE_LUT:
-        dev = torch.device("cuda", idx)
-        _BYTE_LUT[idx] = (2 * (torch.arange(256, dtype=torch.float32, device=dev) / 255.0) - 1.0).contiguous()
-        torch.cuda.current_stream(dev).synchronize()             # later calls may read it from any stream
-    return _BYTE_LUT[idx]
-
-
-_LEVEL_LUT: Dict[tuple, torch.Tensor] = {}
+_LEVEL_LUT: Dict[tuple, torch.Tensor] = {}                                   # (device index, depth) -> table
 _DEPTHS = (8, 10, 12)
 
 
@@ -68,26 +52,85 @@ def _check_depth(who: str, depth) -> int:
     return int(depth)
 
 
+def _levels_to_float(levels: torch.Tensor, depth: int) -> torch.Tensor:
+    """RGB levels of ``depth`` bits -> the float32 video in [0, 255] that stands for them (depth 8: the bytes' values, no multiply)."""
+    return levels.float() if depth == 8 else levels.float() * (255.0 / ((1 << depth) - 1))
+
+
 def level_lut(device, depth: int = 8) -> torch.Tensor:
     """fp32 [2^depth] on `device`: the normalised value of every RGB level of ``depth`` bits, from the expressions a level meets on the float
-    path ON THE SAME DEVICE -- ``YUVFrames.to_float``'s ``level * (255.0 / (2^depth - 1))``, then ``forward``'s ``2 * (x / 255.0) - 1.0`` -- for
-    ``byte_lut``'s reason: the table is what makes the deep path the float path's bits.  Depth 8: ``byte_lut``'s tensor.  Kept per (device, depth)."""
+    path ON THE SAME DEVICE -- ``to_float``'s ``level * (255.0 / (2^depth - 1))`` (depth 8: the byte's value as it is), then ``forward``'s
+    ``2 * (x / 255.0) - 1.0``.  torch's division by a Python scalar need not round like a division written elsewhere, so the table is what makes
+    the decoded paths the float path's bits.  Built once per (device, depth) and kept (the host waits for it once)."""
     depth = _check_depth("level_lut", depth)
-    if depth == 8:
-        return byte_lut(device)
     device = torch.device(device)
     idx = torch.cuda.current_device() if device.index is None else device.index
     if (idx, depth) not in _LEVEL_LUT:
         dev = torch.device("cuda", idx)
-        x = torch.arange(1 << depth, dtype=torch.float32, device=dev) * (255.0 / ((1 << depth) - 1))
+        x = _levels_to_float(torch.arange(1 << depth, dtype=torch.float32, device=dev), depth)
         _LEVEL_LUT[idx, depth] = (2 * (x / 255.0) - 1.0).contiguous()
         torch.cuda.current_stream(dev).synchronize()             # later calls may read it from any stream
     return _LEVEL_LUT[idx, depth]
 
 
-def _levels_to_float(levels: torch.Tensor, depth: int) -> torch.Tensor:
-    """RGB levels of ``depth`` bits -> the float32 video in [0, 255] that stands for them (depth 8: the bytes' values)."""
-    return levels.float() if depth == 8 else levels.float() * (255.0 / ((1 << depth) - 1))
+def byte_lut(device) -> torch.Tensor:
+    """fp32 [256] on `device`: the normalised value of every byte -- ``level_lut``'s depth-8 entry."""
+    return level_lut(device, 8)
+
+
+class _Frames:
+    """What ``YUVFrames`` and ``RawFrames`` share: N frames of one view, sliced by frame range only and moved as a whole.  A subclass has ``n``,
+    ``_tensors()`` (its planes; the first names the device), ``_like(*planes)`` and ``_moved(device)``."""
+
+    def __len__(self) -> int:
+        return self.n
+
+    @property
+    def device(self) -> torch.device:
+        return self._tensors()[0].device
+
+    def __getitem__(self, frames: slice):
+        if not isinstance(frames, slice):
+            raise TypeError(f"{type(self).__name__}: index with a slice of frames")
+        return self._like(*(t[frames] for t in self._tensors()))
+
+    def to(self, device):
+        """These frames on ``device`` ("cuda" without an index: the current device), dense; frames already there are returned as they are."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        return self if self.device == device else self._moved(device)
+
+
+class _StereoVideo:
+    """What ``YUVStereoVideo`` and ``RawStereoVideo`` share: two frame objects of class ``_views`` with one size, frame count and device (a fault
+    there is reported as "both views need ``_one``") and one format -- ``_format_fault(left, right)``: what differs, or None.  ``len()``, slicing
+    by frame range, ``to(device)``."""
+    _views: type
+    _one = "one device"
+
+    def __init__(self, left, right):
+        name = type(self).__name__
+        if not isinstance(left, self._views) or not isinstance(right, self._views):
+            raise TypeError(f"{name}: two {self._views.__name__} expected")
+        if (left.n, left.height, left.width) != (right.n, right.height, right.width):
+            raise ValueError(f"{name}: the views differ: {(left.n, left.height, left.width)} and {(right.n, right.height, right.width)}")
+        fault = f"both views need {self._one}" if left.device != right.device else self._format_fault(left, right)
+        if fault:
+            raise ValueError(f"{name}: {fault}")
+        self.left, self.right = left, right
+        self.depth = left.depth
+        self.height, self.width = left.height, left.width
+
+    def __len__(self) -> int:
+        return self.left.n
+
+    def __getitem__(self, frames: slice):
+        return type(self)(self.left[frames], self.right[frames])
+
+    def to(self, device):
+        """The selected frames on ``device``: each view's own bytes are copied (``YUVFrames.to`` / ``RawFrames.to``)."""
+        return type(self)(self.left.to(device), self.right.to(device))
 
 
 _YUV_STANDARDS = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}       # (Kr, Kb)
@@ -114,7 +157,7 @@ def yuv_matrix(standard: str = "bt709", full_range: bool = False, shift: int = 1
                        cbu=round(sc * 2.0 * (1.0 - kb) * one), shift=shift, reserved=0)
 
 
-class YUVFrames:
+class YUVFrames(_Frames):
     """One view's N decoded YUV frames, as a decoder leaves them: ``y`` (N, H0, W0), ``u`` / ``v`` (N, ceil(H0 / 2), ceil(W0 / 2)) for
     ``chroma="420"`` (the default), (N, H0, ceil(W0 / 2)) for "422", (N, H0, W0) for "444".  ``depth=8`` (the default): uint8 planes; ``depth`` 10 or 12:
     ``torch.uint16`` planes whose words hold the sample at the top (``align="msb"``: P010 / P012 / P210; the low bits are dropped whatever they hold)
@@ -213,20 +256,11 @@ class YUVFrames:
         """I420 / yuv420p: three planes -- a software decoder's frame."""
         return cls(y, u, v, standard, full_range)
 
-    def __len__(self) -> int:
-        return self.n
-
-    @property
-    def device(self) -> torch.device:
-        return self.y.device
+    def _tensors(self):
+        return self.y, self.u, self.v
 
     def _like(self, y, u, v) -> "YUVFrames":
         return YUVFrames(y, u, v, self.standard, self.full_range, self.depth, self.align, self.chroma)
-
-    def __getitem__(self, frames: slice) -> "YUVFrames":
-        if not isinstance(frames, slice):
-            raise TypeError("YUVFrames: index with a slice of frames")
-        return self._like(self.y[frames], self.u[frames], self.v[frames])
 
     def split_side_by_side(self):
         """(left, right): the two halves of frames that pack both views side by side; views, no copy.  The packed width must be even --
@@ -245,14 +279,9 @@ class YUVFrames:
         h, q = ht // 2, (ht // 2) >> self.sub_y
         return (self._like(self.y[:, :h], self.u[:, :q], self.v[:, :q]), self._like(self.y[:, h:], self.u[:, q:], self.v[:, q:]))
 
-    def to(self, device) -> "YUVFrames":
-        """These frames on ``device``: the planes' own bytes are copied (8-bit 4:2:0: 1.5 per pixel, 4:2:2: 2, 4:4:4: 3; twice that for 16-bit
-        samples; an interleaved UV plane as one block) into dense planes; frames already there are returned as they are."""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        if self.device == device:
-            return self
+    def _moved(self, device) -> "YUVFrames":
+        """``to``: the planes' own bytes are copied (8-bit 4:2:0: 1.5 per pixel, 4:2:2: 2, 4:4:4: 3; twice that for 16-bit samples; an
+        interleaved UV plane as one block) into dense planes."""
         y = self.y.to(device)
         if self.step_c == 2 * self.sample_bytes and self.v.data_ptr() == self.u.data_ptr() + self.sample_bytes:
             uv = torch.as_strided(self.u, (*self.u.shape, 2), (*self.u.stride(), 1)).to(device)
@@ -297,40 +326,25 @@ class YUVFrames:
         return _levels_to_float(self.to_rgb(), self.depth)
 
 
-class YUVStereoVideo:
+class YUVStereoVideo(_StereoVideo):
     """Both views of a decoded YUV video -- what ``batch_dict["stereo_video"]`` of ``forward_batch_test`` may be instead of a tensor:
-    two ``YUVFrames`` of one size, frame count, device, colour description and sample format (depth, alignment, chroma subsampling).  ``len()``, slicing by frame range, ``to(device)``."""
+    two ``YUVFrames`` of one size, frame count, device, colour description and sample format (depth, alignment, chroma subsampling).  ``len()``,
+    slicing by frame range, ``to(device)`` (8-bit 4:2:0: 1.5 bytes per pixel and view; P010: 3)."""
+    _views, _one = YUVFrames, "one standard, one range and one device"
 
-    def __init__(self, left: YUVFrames, right: YUVFrames):
-        if not isinstance(left, YUVFrames) or not isinstance(right, YUVFrames):
-            raise TypeError("YUVStereoVideo: two YUVFrames expected")
-        if (left.n, left.height, left.width) != (right.n, right.height, right.width):
-            raise ValueError(f"YUVStereoVideo: the views differ: {(left.n, left.height, left.width)} and {(right.n, right.height, right.width)}")
-        if (left.standard, left.full_range) != (right.standard, right.full_range) or left.device != right.device:
-            raise ValueError("YUVStereoVideo: both views need one standard, one range and one device")
+    def _format_fault(self, left: YUVFrames, right: YUVFrames) -> Optional[str]:
+        if (left.standard, left.full_range) != (right.standard, right.full_range):
+            return f"both views need {self._one}"
         if (left.depth, left.lsb, left.chroma) != (right.depth, right.lsb, right.chroma):
-            raise ValueError(f"YUVStereoVideo: the views differ in depth, alignment or chroma: {(left.depth, left.align, left.chroma)} and "
-                             f"{(right.depth, right.align, right.chroma)}")
-        self.left, self.right = left, right
-        self.depth = left.depth
-        self.height, self.width = left.height, left.width
-
-    def __len__(self) -> int:
-        return self.left.n
-
-    def __getitem__(self, frames: slice) -> "YUVStereoVideo":
-        return YUVStereoVideo(self.left[frames], self.right[frames])
-
-    def to(self, device) -> "YUVStereoVideo":
-        """The selected frames' planes on ``device`` (8-bit 4:2:0: 1.5 bytes per pixel and view; P010: 3)."""
-        return YUVStereoVideo(self.left.to(device), self.right.to(device))
+            return f"the views differ in depth, alignment or chroma: {(left.depth, left.align, left.chroma)} and {(right.depth, right.align, right.chroma)}"
+        return None
 
 
 _RAW_PATTERNS = {"rggb": 0, "bggr": 1, "grbg": 2, "gbrg": 3, "mono": 4}           # ppms_raw_format.pattern
 _RAW_SHIFT = 10                                                                    # the white-balance gains' fixed point
 
 
-class RawFrames:
+class RawFrames(_Frames):
     """One view's N raw sensor frames, as a camera driver leaves them: ``data`` (N, H0, W0), one sample per pixel under the colour-filter mosaic
     ``pattern`` ("rggb" / "bggr" / "grbg" / "gbrg": the 2 x 2 tile at the frame's origin, row-major -- BayerRG8, BayerGB10 ...) or "mono"
     (Mono8 / Mono10 / Mono12).  ``depth=8``: a uint8 plane; ``depth`` 10 or 12: a ``torch.uint16`` plane whose words hold the sample at the bottom
@@ -390,20 +404,11 @@ class RawFrames:
         # what every slice, half and copy of these frames shares: the tone curve and the ingest table per device, each made once
         self._shared = {"tone": {}, "table": {}} if _shared is None else _shared
 
-    def __len__(self) -> int:
-        return self.n
-
-    @property
-    def device(self) -> torch.device:
-        return self.data.device
+    def _tensors(self):
+        return (self.data,)
 
     def _like(self, data) -> "RawFrames":
         return RawFrames(data, self.pattern, self.depth, self.align, self.black, self.gains, self.tone, _shared=self._shared)
-
-    def __getitem__(self, frames: slice) -> "RawFrames":
-        if not isinstance(frames, slice):
-            raise TypeError("RawFrames: index with a slice of frames")
-        return self._like(self.data[frames])
 
     def split_side_by_side(self):
         """(left, right): the two halves of frames that pack both views side by side; views, no copy.  The packed width must be even -- and with a
@@ -420,13 +425,9 @@ class RawFrames:
             raise ValueError(f"RawFrames.split_top_bottom: a packed height of {h} does not split into two views of one {self.pattern} pattern")
         return self._like(self.data[:, :h // 2]), self._like(self.data[:, h // 2:])
 
-    def to(self, device) -> "RawFrames":
-        """These frames on ``device``: the samples' own bytes are copied (1 per pixel, 2 for 16-bit words) into a dense plane; frames already
-        there are returned as they are."""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        return self if self.device == device else self._like(self.data.to(device))
+    def _moved(self, device) -> "RawFrames":
+        """``to``: the samples' own bytes are copied (1 per pixel, 2 for 16-bit words) into a dense plane."""
+        return self._like(self.data.to(device))
 
     def same_format(self, other: "RawFrames") -> bool:
         """Both hold one kind of sample, under one pattern, with one black level, white balance and tone curve."""
@@ -505,35 +506,17 @@ class RawFrames:
         return self._shared["table"][dev]
 
 
-class RawStereoVideo:
+class RawStereoVideo(_StereoVideo):
     """Both views of a raw sensor video -- what ``batch_dict["stereo_video"]`` of ``forward_batch_test`` may be instead of a tensor: two
     ``RawFrames`` of one size, frame count, device, pattern, sample format (depth, alignment), black level, white balance and tone curve.
-    ``len()``, slicing by frame range, ``to(device)``."""
+    ``len()``, slicing by frame range, ``to(device)`` (1 byte per pixel and view; 2 for 10- and 12-bit samples)."""
+    _views = RawFrames
 
-    def __init__(self, left: RawFrames, right: RawFrames):
-        if not isinstance(left, RawFrames) or not isinstance(right, RawFrames):
-            raise TypeError("RawStereoVideo: two RawFrames expected")
-        if (left.n, left.height, left.width) != (right.n, right.height, right.width):
-            raise ValueError(f"RawStereoVideo: the views differ: {(left.n, left.height, left.width)} and {(right.n, right.height, right.width)}")
-        if left.device != right.device:
-            raise ValueError("RawStereoVideo: both views need one device")
-        if not left.same_format(right):
-            raise ValueError("RawStereoVideo: the views differ in pattern, depth, alignment, black level, gains or tone curve: "
-                             f"{(left.pattern, left.depth, left.align, left.black, left.gains)} and "
-                             f"{(right.pattern, right.depth, right.align, right.black, right.gains)}")
-        self.left, self.right = left, right
-        self.depth = left.depth
-        self.height, self.width = left.height, left.width
-
-    def __len__(self) -> int:
-        return self.left.n
-
-    def __getitem__(self, frames: slice) -> "RawStereoVideo":
-        return RawStereoVideo(self.left[frames], self.right[frames])
-
-    def to(self, device) -> "RawStereoVideo":
-        """The selected frames' samples on ``device`` (1 byte per pixel and view; 2 for 10- and 12-bit samples)."""
-        return RawStereoVideo(self.left.to(device), self.right.to(device))
+    def _format_fault(self, left: RawFrames, right: RawFrames) -> Optional[str]:
+        if left.same_format(right):
+            return None
+        return ("the views differ in pattern, depth, alignment, black level, gains or tone curve: "
+                f"{(left.pattern, left.depth, left.align, left.black, left.gains)} and {(right.pattern, right.depth, right.align, right.black, right.gains)}")
 
 
 _BORDERS = {"replicate": L.BORDER_REPLICATE, "constant": L.BORDER_CONSTANT}
@@ -833,22 +816,15 @@ def stereo_source(who: str, left, right=None, rectify: Optional[StereoRectifier]
     sample format, black level, gains or tone curve, are no stereo pair (ValueError)."""
     if rectify is not None and not isinstance(rectify, StereoRectifier):
         raise TypeError(f"{who}: rectify must be a StereoRectifier, got {type(rectify).__name__}")
-    if isinstance(left, YUVFrames) or isinstance(right, YUVFrames):
-        if not (isinstance(left, YUVFrames) and isinstance(right, YUVFrames)):
-            raise TypeError(f"{who}: image1 is {type(left).__name__} and image2 is {type(right).__name__}; both views must be YUVFrames or both tensors")
-        left, right = YUVStereoVideo(left, right), None
-    if isinstance(left, YUVStereoVideo):
-        if rectify is not None:
-            rectify = _checked_rectifier(who, rectify, left.left.device, left.height, left.width)
-        return _YUVPlanes(left, rectify)
-    if isinstance(left, RawFrames) or isinstance(right, RawFrames):
-        if not (isinstance(left, RawFrames) and isinstance(right, RawFrames)):
-            raise TypeError(f"{who}: image1 is {type(left).__name__} and image2 is {type(right).__name__}; both views must be RawFrames or both tensors")
-        left, right = RawStereoVideo(left, right), None
-    if isinstance(left, RawStereoVideo):
-        if rectify is not None:
-            rectify = _checked_rectifier(who, rectify, left.left.device, left.height, left.width)
-        return _RawPlanes(left, rectify)
+    for frames, video, source in ((YUVFrames, YUVStereoVideo, _YUVPlanes), (RawFrames, RawStereoVideo, _RawPlanes)):
+        if isinstance(left, frames) or isinstance(right, frames):
+            if not (isinstance(left, frames) and isinstance(right, frames)):
+                raise TypeError(f"{who}: image1 is {type(left).__name__} and image2 is {type(right).__name__}; both views must be {frames.__name__} or both tensors")
+            left, right = video(left, right), None
+        if isinstance(left, video):
+            if rectify is not None:
+                rectify = _checked_rectifier(who, rectify, left.left.device, left.height, left.width)
+            return source(left, rectify)
     views = (left,) if right is None else (left, right)
     for v in views:
         if not torch.is_tensor(v):

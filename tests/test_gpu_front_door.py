@@ -9,7 +9,7 @@ from stub_encoders import StubCNet, StubFNet, frame_video
 from test_gpu_block import DEV, W
 from test_gpu_egress import same as same_tensor
 from test_gpu_ingest_remap import raw_video, rectified_video, smooth_rectifier
-from test_gpu_ingest_u8 import model, same  # noqa: F401  (model: the fixture)
+from ingest_util import model, same  # noqa: F401  (model: the fixture)
 
 pytestmark = pytest.mark.gpu
 SPEC = dict(disparity="u16", uncertainty="u8")

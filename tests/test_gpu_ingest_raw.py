@@ -5,11 +5,10 @@ on RawFrames / a RawStereoVideo against the same calls on that float video (torc
 import pytest
 import torch
 
-from ppmstereo_amd import _lib as L
 from ppmstereo_amd.ppmstereo import OutputSpec, RawFrames, RawStereoVideo, RectifyMap, StereoRectifier
-from test_gpu_block import DEV, W
-from test_gpu_ingest_u8 import bits, float_path_operands, ingest, model, rand_u8, same  # noqa: F401  (model: the fixture)
-from test_gpu_ingest_yuv_deep import fresh, rand_u16, restated_remap_levels, rotated_map
+from ingest_util import DEV, bits, float_path_operands, fresh, ingest, ingest_raw, model, rand_u8, rand_u16, rotated_map, same  # noqa: F401  (model: the fixture)
+from test_gpu_block import W
+from test_gpu_ingest_yuv_deep import restated_remap_levels
 from test_gpu_ingest_remap import smooth_rectifier
 
 pytestmark = pytest.mark.gpu
@@ -26,22 +25,6 @@ def raw_surface(N, H0, W0, pitch, seed, pattern, depth, align, **kw):
         unused = surface.to(torch.int32) & ((1 << (16 - depth)) - 1) if align == "msb" else surface.to(torch.int32) >> depth
         assert bool(unused.any())
     return RawFrames(surface[:, :, :W0], pattern, depth, align, **kw)
-
-
-def ingest_raw(left: RawFrames, right: RawFrames, pad_left, pad_top, H, Wd, fview, cview, maps=None):
-    lv, rv, fmt = left.view_struct(), right.view_struct(), left.format_struct()
-    assert left.same_format(right)
-    lut = left.table(DEV)
-    assert lut.numel() == 1 << left.depth and lut.is_cuda and lut.dtype == torch.float32
-    with torch.cuda.device(DEV):
-        if maps is None:
-            rc = L.load().ppms_video_ingest_raw(lv, rv, fmt, left.n, left.height, left.width, pad_left, pad_top, H, Wd, lut.data_ptr(), fview, cview,
-                                                L.stream_ptr())
-        else:
-            d = left.depth
-            rc = L.load().ppms_video_ingest_raw_remap(lv, rv, fmt, maps[0].view_struct(d), maps[1].view_struct(d), left.n, maps[0].height, maps[0].width,
-                                                      pad_left, pad_top, H, Wd, lut.data_ptr(), fview, cview, L.stream_ptr())
-    L.check(rc)
 
 
 def float_video(frames: RawFrames, m: RectifyMap = None):

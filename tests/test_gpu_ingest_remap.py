@@ -5,12 +5,11 @@ the same calls on that rectified uint8 video (torch.equal)."""
 import pytest
 import torch
 
-from ppmstereo_amd import _lib as L
 from ppmstereo_amd.ppmstereo import OutputSpec, RectifyMap, StereoRectifier, YUVFrames, YUVStereoVideo
-from test_gpu_block import DEV, W
-from test_gpu_ingest_u8 import bits, ingest, model, patterned, rand_u8, same  # noqa: F401  (model: the fixture)
-from test_gpu_ingest_yuv import COMBOS, i420_planes, ingest_yuv, nv12_surfaces, rgb_of
-from test_ingest_remap import random_map, restated_remap
+from ingest_util import DEV, bits, fresh, ingest, ingest_yuv, model, rand_u8, restated_remap, same  # noqa: F401  (model: the fixture)
+from test_gpu_block import W
+from test_gpu_ingest_yuv import COMBOS, i420_planes, nv12_surfaces, rgb_of
+from test_ingest_remap import random_map
 
 pytestmark = pytest.mark.gpu
 BORDERS = [("replicate", 0), ("constant", 0), ("constant", 200)]
@@ -34,7 +33,7 @@ def rectified(rgb, m: RectifyMap):
 def expected_operands(l_rect, r_rect, pad_left, pad_top, H, Wd):
     """The two operands ppms_video_ingest_u8 writes for rectified bytes (N, 3, H0, W0) of both views."""
     N, _, H0, W0 = l_rect.shape
-    f, c = patterned(2 * N * (H // 2) * (Wd // 2), 32), patterned(N * (H // 4) * (Wd // 4), 64)
+    f, c = fresh(N, H, Wd)
     ingest(l_rect.data_ptr(), r_rect.data_ptr(), 3 * H0 * W0, N, H0, W0, pad_left, pad_top, H, Wd, f.view(), c.view())
     torch.cuda.synchronize()
     return f, c
@@ -42,26 +41,12 @@ def expected_operands(l_rect, r_rect, pad_left, pad_top, H, Wd):
 
 def ingest_u8_remap(left, right, lmap: RectifyMap, rmap: RectifyMap, pad_left, pad_top, H, Wd, fview, cview):
     """left / right: raw (N, 3, hs, ws) uint8 on the device."""
-    from ppmstereo_amd.ppmstereo import byte_lut
     N, _, hs, ws = left.shape
-    with torch.cuda.device(DEV):
-        rc = L.load().ppms_video_ingest_u8_remap(left.data_ptr(), right.data_ptr(), 3 * hs * ws, lmap.view_struct(), rmap.view_struct(), N, lmap.height,
-                                                 lmap.width, pad_left, pad_top, H, Wd, byte_lut(DEV).data_ptr(), fview, cview, L.stream_ptr())
-    L.check(rc)
-    return rc
+    return ingest(left.data_ptr(), right.data_ptr(), 3 * hs * ws, N, None, None, pad_left, pad_top, H, Wd, fview, cview, (lmap, rmap))
 
 
 def ingest_yuv_remap(left: YUVFrames, right: YUVFrames, lmap: RectifyMap, rmap: RectifyMap, pad_left, pad_top, H, Wd, fview, cview):
-    from ppmstereo_amd.ppmstereo import byte_lut
-    with torch.cuda.device(DEV):
-        rc = L.load().ppms_video_ingest_yuv420_remap(left.view_struct(), right.view_struct(), left.matrix(), lmap.view_struct(), rmap.view_struct(), left.n,
-                                                     lmap.height, lmap.width, pad_left, pad_top, H, Wd, byte_lut(DEV).data_ptr(), fview, cview, L.stream_ptr())
-    L.check(rc)
-    return rc
-
-
-def fresh(N, H, Wd):
-    return patterned(2 * N * (H // 2) * (Wd // 2), 32), patterned(N * (H // 4) * (Wd // 4), 64)
+    return ingest_yuv(left, right, pad_left, pad_top, H, Wd, fview, cview, (lmap, rmap))
 
 
 def check_u8(left, right, lmap, rmap, pad_left, pad_top, H, Wd):

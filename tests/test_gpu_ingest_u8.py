@@ -6,48 +6,11 @@ import pytest
 import torch
 
 from ppmstereo_amd import _lib as L
-from ppmstereo_amd import weights as Wm
-from test_gpu_block import DEV, W
+from ingest_util import DEV, bits, float_path_operands, ingest, model, patterned, rand_u8, same  # noqa: F401  (model: the fixture)
+from test_gpu_block import W
 
 pytestmark = pytest.mark.gpu
 NONE_SP = L.SP(None, None, 0, 0)
-
-
-def rand_u8(shape, seed):
-    return torch.randint(0, 256, shape, dtype=torch.uint8, generator=torch.Generator().manual_seed(seed))
-
-
-def patterned(pixels, channels):
-    """A destination whose every 16-bit word is non-zero before the launch (so the zeroed tail channels are seen to be written)."""
-    t = L.SPTensor(pixels, channels, DEV, zero=False)
-    t.data.view(torch.int16).copy_((torch.arange(t.data.numel(), device=DEV) % 251 + 1).to(torch.int16).view(t.data.shape))
-    return t
-
-
-def bits(t: L.SPTensor):
-    return t.data.view(torch.int16)
-
-
-def float_path_operands(left_u8, right_u8, pad):
-    """left / right (N, 3, H0, W0) uint8 on the device, pad = F.pad's [left, right, top, bottom] -> the k = 2 operand of cat([left, right])
-    and the k = 4 operand of left, as the float path produces them."""
-    lib = L.load()
-    l, r = left_u8.float(), right_u8.float()
-    if any(pad):
-        l, r = (torch.nn.functional.pad(x, pad, mode="replicate") for x in (l, r))
-    im1, im2 = (2 * (l / 255.0) - 1.0).contiguous(), (2 * (r / 255.0) - 1.0).contiguous()
-    N, _, H, Wd = im1.shape
-    both = torch.cat([im1, im2], dim=0).contiguous()
-    f, c = patterned(2 * N * (H // 2) * (Wd // 2), 32), patterned(N * (H // 4) * (Wd // 4), 64)
-    L.check(lib.ppms_img_s2d(both.data_ptr(), f.view(), 2 * N, 3, H, Wd, 2, L.stream_ptr()))
-    L.check(lib.ppms_img_s2d(im1.data_ptr(), c.view(), N, 3, H, Wd, 4, L.stream_ptr()))
-    return f, c, H, Wd
-
-
-def ingest(left, right, stride, N, H0, W0, pad_left, pad_top, H, Wd, fview, cview):
-    from ppmstereo_amd.ppmstereo import byte_lut
-    with torch.cuda.device(DEV):
-        L.check(L.load().ppms_video_ingest_u8(left, right, stride, N, H0, W0, pad_left, pad_top, H, Wd, byte_lut(DEV).data_ptr(), fview, cview, L.stream_ptr()))
 
 
 def test_byte_table_is_the_float_paths_expression():
@@ -114,25 +77,6 @@ def test_kernel_frame_stride_past_2_to_31():
     f, c = patterned(4 * 4 * 6, 32), patterned(2 * 2 * 3, 64)
     ingest(buf.data_ptr(), buf.data_ptr() + n, stride, 2, H0, W0, 0, 0, H, Wd, f.view(), c.view())
     assert torch.equal(bits(f), bits(ef)) and torch.equal(bits(c), bits(ec))
-
-
-@pytest.fixture(scope="module")
-def model():
-    """PPMStereo.shipped() with this package's encoders and the procedural weights (as tests/test_gpu_block.py builds the whole model)."""
-    assert torch.cuda.is_available(), "these tests need the MI355X (no CPU fallback exists)"
-    from ppmstereo_amd.ppmstereo import PPMStereo
-    m = PPMStereo.shipped()
-    m.load_hot_path_weights(W)
-    m.fnet.load_state_dict(Wm.fnet_weights(), strict=True)
-    m.cnet.load_state_dict(Wm.cnet_weights(), strict=True)
-    sd = m.state_dict()
-    sd.update(Wm.sst_weights())
-    m.load_state_dict(sd, strict=True)
-    return m.to(DEV).eval()
-
-
-def same(a, b):
-    return all(a[k].shape == b[k].shape and torch.equal(a[k], b[k]) for k in ("disparity", "uncertainties"))
 
 
 def test_model_single_window(model):

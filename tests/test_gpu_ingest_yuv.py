@@ -6,10 +6,9 @@ import itertools
 import pytest
 import torch
 
-from ppmstereo_amd import _lib as L
 from ppmstereo_amd.ppmstereo import YUVFrames, YUVStereoVideo
-from test_gpu_block import DEV, W
-from test_gpu_ingest_u8 import bits, ingest, model, patterned, rand_u8, same  # noqa: F401  (model: the fixture)
+from ingest_util import DEV, bits, fresh, ingest, ingest_yuv, model, patterned, rand_u8, same  # noqa: F401  (model: the fixture)
+from test_gpu_block import W
 
 pytestmark = pytest.mark.gpu
 COMBOS = list(itertools.product(("bt709", "bt601"), (False, True)))
@@ -41,24 +40,15 @@ def expected_operands(left: YUVFrames, right: YUVFrames, pad_left, pad_top, H, W
     """The two operands ppms_video_ingest_u8 writes for the restated RGB bytes of both views."""
     l, r = rgb_of(left), rgb_of(right)
     N, _, H0, W0 = l.shape
-    f, c = patterned(2 * N * (H // 2) * (Wd // 2), 32), patterned(N * (H // 4) * (Wd // 4), 64)
+    f, c = fresh(N, H, Wd)
     ingest(l.data_ptr(), r.data_ptr(), 3 * H0 * W0, N, H0, W0, pad_left, pad_top, H, Wd, f.view(), c.view())
     torch.cuda.synchronize()                                    # (l, r are released on return)
     return f, c
 
 
-def ingest_yuv(left: YUVFrames, right: YUVFrames, pad_left, pad_top, H, Wd, fview, cview):
-    from ppmstereo_amd.ppmstereo import byte_lut
-    lv, rv, m = left.view_struct(), right.view_struct(), left.matrix()
-    with torch.cuda.device(DEV):
-        L.check(L.load().ppms_video_ingest_yuv420(lv, rv, m, left.n, left.height, left.width, pad_left, pad_top, H, Wd, byte_lut(DEV).data_ptr(), fview, cview,
-                                                  L.stream_ptr()))
-
-
 def check_both(left, right, pad_left, pad_top, H, Wd):
     ef, ec = expected_operands(left, right, pad_left, pad_top, H, Wd)
-    N = left.n
-    f, c = patterned(2 * N * (H // 2) * (Wd // 2), 32), patterned(N * (H // 4) * (Wd // 4), 64)
+    f, c = fresh(left.n, H, Wd)
     ingest_yuv(left, right, pad_left, pad_top, H, Wd, f.view(), c.view())
     assert torch.equal(bits(f), bits(ef)) and torch.equal(bits(c), bits(ec))
     return f, c

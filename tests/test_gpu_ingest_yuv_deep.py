@@ -6,18 +6,14 @@ planes as int16 -- and PPMStereo.forward / forward_batch_test on deep YUVFrames 
 import pytest
 import torch
 
-from ppmstereo_amd import _lib as L
 from ppmstereo_amd.ppmstereo import OutputSpec, RectifyMap, StereoRectifier, YUVFrames, YUVStereoVideo
-from test_gpu_block import DEV, W
-from test_gpu_ingest_u8 import bits, float_path_operands, ingest, model, patterned, rand_u8, same  # noqa: F401  (model: the fixture)
-from test_gpu_ingest_yuv import COMBOS, ingest_yuv, nv12_surfaces
+from ingest_util import (DEV, bits, float_path_operands, fresh, ingest, ingest_deep, ingest_yuv, model, rand_u8, rand_u16, restated_remap,  # noqa: F401
+                         rotated_map, same)                                                                                        # (model: the fixture)
+from test_gpu_block import W
+from test_gpu_ingest_yuv import COMBOS, nv12_surfaces
 from test_gpu_ingest_remap import smooth_rectifier
 
 pytestmark = pytest.mark.gpu
-
-
-def rand_u16(shape, seed, top=1 << 16):
-    return torch.randint(0, top, shape, dtype=torch.int32, generator=torch.Generator().manual_seed(seed)).to(torch.uint16)
 
 
 # ---- the expectation: the conversion and the remap restated, then the float path ---------------------------------------------------------
@@ -44,26 +40,9 @@ def restated_levels(frames: YUVFrames, shift=14):
 
 
 def restated_remap_levels(levels, m: RectifyMap, depth):
-    """levels (N, 3, Hs, Ws) int64 -> (N, 3, H0, W0) int64 by the header's formula on flat pixel indices with torch.gather and a floor division;
-    a tap outside the frame is, in constant mode, the byte `fill` with its top bits repeated below it."""
-    N, _, hs, ws = levels.shape
-    H0, W0 = m.frac.shape
-    fill = m.fill * 2 ** (depth - 8) + m.fill // 2 ** (16 - depth)
-    flat = levels.reshape(N, 3, hs * ws)
-    x0, y0 = m.xy[..., 0].reshape(-1).long(), m.xy[..., 1].reshape(-1).long()
-    fr = m.frac.reshape(-1).long() & 0xFFFF
-    fx, fy = fr % 32, (fr // 32) % 32
-    total = torch.zeros((N, 3, H0 * W0), dtype=torch.int64, device=levels.device)
-    for (dy, dx), w in zip(((0, 0), (0, 1), (1, 0), (1, 1)), [(32 - fx) * (32 - fy), fx * (32 - fy), (32 - fx) * fy, fx * fy]):
-        yy, xx = y0 + dy, x0 + dx
-        inside = (yy >= 0) & (yy < hs) & (xx >= 0) & (xx < ws)
-        tap = torch.gather(flat, 2, (yy.clamp(0, hs - 1) * ws + xx.clamp(0, ws - 1)).expand(N, 3, -1))
-        if m.border == "constant":
-            tap = tap * inside + fill * (~inside)
-        total += w * tap
-    out = torch.div(total + 512, 1024, rounding_mode="floor")
-    assert int(out.min()) >= 0 and int(out.max()) <= 2 ** depth - 1                          # no clamp is needed
-    return out.reshape(N, 3, H0, W0)
+    """levels (N, 3, Hs, Ws) int64 -> (N, 3, H0, W0) int64 by the restated remap; a tap outside the frame is, in constant mode, the byte `fill`
+    with its top bits repeated below it."""
+    return restated_remap(levels, m.xy, m.frac, m.border, m.fill * 2 ** (depth - 8) + m.fill // 2 ** (16 - depth), 2 ** depth - 1)
 
 
 def as_float(levels, depth):
@@ -76,27 +55,6 @@ def expected_operands(l_levels, r_levels, depth, pad):
     f, c, H, Wd = float_path_operands(as_float(l_levels, depth), as_float(r_levels, depth), pad)
     torch.cuda.synchronize()
     return f, c, H, Wd
-
-
-def fresh(N, H, Wd):
-    return patterned(2 * N * (H // 2) * (Wd // 2), 32), patterned(N * (H // 4) * (Wd // 4), 64)
-
-
-def ingest_deep(left: YUVFrames, right: YUVFrames, pad_left, pad_top, H, Wd, fview, cview, maps=None):
-    from ppmstereo_amd.ppmstereo import level_lut
-    lv, rv, m, fmt = left.view_struct(), right.view_struct(), left.matrix(), left.format_struct()
-    assert (fmt.sample_bytes, fmt.depth, fmt.lsb, fmt.sub_x, fmt.sub_y) == (right.sample_bytes, right.depth, right.lsb, right.sub_x, right.sub_y)
-    lut = level_lut(DEV, left.depth)
-    assert lut.numel() == 1 << left.depth
-    with torch.cuda.device(DEV):
-        if maps is None:
-            rc = L.load().ppms_video_ingest_yuv(lv, rv, m, fmt, left.n, left.height, left.width, pad_left, pad_top, H, Wd, lut.data_ptr(), fview, cview,
-                                                L.stream_ptr())
-        else:
-            d = left.depth
-            rc = L.load().ppms_video_ingest_yuv_remap(lv, rv, m, fmt, maps[0].view_struct(d), maps[1].view_struct(d), left.n, maps[0].height, maps[0].width,
-                                                      pad_left, pad_top, H, Wd, lut.data_ptr(), fview, cview, L.stream_ptr())
-    L.check(rc)
 
 
 def check_both(left, right, pad, maps=None):
@@ -263,20 +221,6 @@ def test_remap_identity_maps_give_the_plain_calls_operands():
     ingest_deep(left, right, 7, 13, 64, 64, ef.view(), ec.view())
     f, c = check_both(left, right, [7, 7, 13, 14], (ident, ident))
     assert torch.equal(bits(f), bits(ef)) and torch.equal(bits(c), bits(ec))
-
-
-def rotated_map(H0, W0, hs, ws, angle, scale, border, fill):
-    """The rectified frame H0 x W0 as a rotated, scaled window around the centre of the hs x ws raw frame: its corners lie outside the raw frame."""
-    import math
-    ys, xs = torch.meshgrid(torch.arange(H0, dtype=torch.float32), torch.arange(W0, dtype=torch.float32), indexing="ij")
-    dx, dy = xs - (W0 - 1) / 2, ys - (H0 - 1) / 2
-    mx = (ws - 1) / 2 + scale * (math.cos(angle) * dx - math.sin(angle) * dy)
-    my = (hs - 1) / 2 + scale * (math.sin(angle) * dx + math.cos(angle) * dy)
-    m = RectifyMap.from_float(mx, my, (hs, ws), border, fill).to(DEV)
-    x0, y0 = m.xy[..., 0], m.xy[..., 1]
-    assert bool((x0 < 0).any()) and bool((x0 + 1 > ws - 1).any()) and bool((y0 < 0).any()) and bool((y0 + 1 > hs - 1).any())      # taps outside
-    assert len(set(m.frac.reshape(-1).tolist())) > 500
-    return m
 
 
 @pytest.mark.parametrize("border,fill", [("replicate", 0), ("constant", 0), ("constant", 255)])

@@ -3,24 +3,18 @@ the C ABI, their ctypes bindings have the header's argument lists and struct siz
 RawFrames.to_rgb is the demosaic, black level and white balance the header states (against a per-pixel restatement in plain Python), RawFrames reads
 byte strides from views without copying, and stereo_source dispatches raw frames without a device.  No device compute."""
 import ctypes
+import functools
 import itertools
 
 import pytest
 import torch
 
-from test_ingest_yuv import EINVAL, header_args, rand_u8
-from test_ingest_yuv_deep import rand_u16
+from ingest_util import EINVAL, call, header_args, lib, rand_u8, rand_u16, raw_view, remap_view  # noqa: F401  (lib: the fixture)
 
 NAME, REMAP, SIZES = "ppms_video_ingest_raw", "ppms_video_ingest_raw_remap", "ppms_raw_struct_sizes"
 PATTERNS = ["rggb", "bggr", "grbg", "gbrg", "mono"]
 COLOURS = PATTERNS[:4]
 FORMATS = [(8, "lsb"), (10, "lsb"), (10, "msb"), (12, "lsb"), (12, "msb")]            # (depth, align)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from ppmstereo_amd import _lib as L
-    return L.load()
 
 
 # ---- the ABI -------------------------------------------------------------------------------------------------------------------------------
@@ -57,31 +51,20 @@ def test_bindings_match_the_header(lib):
 
 
 # ---- argument refusal: BayerRG10 frames (bits at the top) of 37 x 50 in surfaces of pitch 128 bytes, two frames, padded to 64 x 64 ---------------
-def _view(data=0x100000, fs=37 * 128, pitch=128, reserved=0):
+_view = functools.partial(raw_view, data=0x100000, fs=37 * 128, pitch=128)
+_map = functools.partial(remap_view, border=1)
+
+
+def _call(lib, left=None, right=None, fmt=None, null=(), lmap=None, rmap=None, null_rmap=False, **geometry):
+    """geometry: ingest_util.call's.  lmap / rmap (dicts): the _remap twin."""
     from ppmstereo_amd import _lib as L
-    return L.RawView(data or None, fs, pitch, reserved)
-
-
-def _map(xy=0x400000, frac=0x500000, pitch=50, hs=37, ws=50, border=1, fill=0, reserved=0):
-    from ppmstereo_amd import _lib as L
-    return L.RemapView(xy or None, frac or None, pitch, hs, ws, border, fill, reserved)
-
-
-def _call(lib, left=None, right=None, fmt=None, null=(), N=2, H0=37, W0=50, pad_left=7, pad_top=13, H=64, W=64, lut=0x3000, fnet=True, cnet=True,
-          lmap=None, rmap=None, null_rmap=False):
-    """Pointers into device memory are never dereferenced on the host: every check comes before the launch.  lmap / rmap (dicts): the _remap twin."""
-    from ppmstereo_amd import _lib as L
-    sp = lambda on, c: L.SP(0x10000 if on else None, 0x20000 if on else None, c, c)
     f = dict(sample_bytes=2, depth=10, lsb=6, pattern=0, black=64, gain=(1536, 1024, 1300), shift=10, reserved=(0, 0, 0))
     f.update(fmt or {})
-    args = [_view(**(left or {})), _view(**(right or {})),
+    head = [_view(**(left or {})), _view(**(right or {})),
             L.RawFormat(f["sample_bytes"], f["depth"], f["lsb"], f["pattern"], f["black"], f["gain"], f["shift"], f["reserved"])]
-    ptrs = [None if i in null else ctypes.byref(x) for i, x in enumerate(args)]
-    rest = (N, H0, W0, pad_left, pad_top, H, W, lut or None, sp(fnet, 32), sp(cnet, 64), None)
     if lmap is None and rmap is None and not null_rmap:
-        return lib.ppms_video_ingest_raw(*ptrs, *rest)
-    maps = [_map(**(lmap or {})), _map(**(rmap or {}))]
-    return lib.ppms_video_ingest_raw_remap(*ptrs, ctypes.byref(maps[0]), None if null_rmap else ctypes.byref(maps[1]), *rest)
+        return call(lib, NAME, head, null=null, **geometry)
+    return call(lib, REMAP, head, [_map(**(lmap or {})), _map(**(rmap or {}))], null=null, null_maps=(1,) if null_rmap else (), **geometry)
 
 
 BYTES = dict(sample_bytes=1, depth=8, lsb=0)                          # (with the 16-bit views' strides, which are large enough for bytes too)

@@ -1,32 +1,17 @@
 """CPU: rectification inside the ingest kernel.  ppms_video_ingest_u8_remap / ppms_video_ingest_yuv420_remap (raw frames of an unrectified rig
 + one fixed-point map per view -> the first-layer operands of both encoders) are part of the C ABI, their ctypes bindings have the header's
 argument lists and struct size, they refuse bad arguments before touching a device; RectifyMap quantises float maps as stated, reads pointers
-and pitches from views without copying, and RectifyMap.apply_u8 is the arithmetic of include/ppms.h (against this file's own restatement).
+and pitches from views without copying, and RectifyMap.apply_u8 is the arithmetic of include/ppms.h (against ingest_util.restated_remap).
 No device compute."""
 import ctypes
-import os
-import re
+import functools
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EINVAL = -1
+from ingest_util import EINVAL, call, header_args, lib, rand_u8, remap_view, restated_remap, yuv_view  # noqa: F401  (lib: the fixture)
+
 NAMES = {"u8": "ppms_video_ingest_u8_remap", "yuv": "ppms_video_ingest_yuv420_remap"}
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from ppmstereo_amd import _lib as L
-    return L.load()
-
-
-def header_args(name):
-    src = open(os.path.join(ROOT, "include", "ppms.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\((.*?)\)\s*;", src, flags=re.S)
-    assert m, f"{name} is not declared in include/ppms.h"
-    return [" ".join(a.split()) for a in m.group(1).split(",")]
 
 
 def test_declared_exported_and_abi_version_unchanged(lib):
@@ -57,29 +42,15 @@ def test_binding_matches_the_header(lib):
 
 
 # ---- argument refusal: raw frames of 41 x 53, rectified 37 x 50 with map rows of pitch 56, two frames, padded to 64 x 64 -------------------
-def _map(xy=0x400000, frac=0x500000, pitch=56, hs=41, ws=53, border=0, fill=0, reserved=0):
-    from ppmstereo_amd import _lib as L
-    return L.RemapView(xy or None, frac or None, pitch, hs, ws, border, fill, reserved)
+_map = functools.partial(remap_view, pitch=56, hs=41, ws=53)
+_view = functools.partial(yuv_view, y=0x100000, u=0x200000, v=0x200001, fsy=41 * 64, fsc=21 * 64, pitch_y=64, pitch_c=64, step_c=2)      # NV12, chroma 21 x 27
 
 
-def _view(y=0x100000, u=0x200000, v=0x200001, fsy=41 * 64, fsc=21 * 64, pitch_y=64, pitch_c=64, step_c=2, reserved=0):
-    from ppmstereo_amd import _lib as L                          # NV12, chroma 21 x 27 in surfaces of pitch 64
-    return L.YUVView(y or None, u or None, v or None, fsy, fsc, pitch_y, pitch_c, step_c, reserved)
-
-
-def _call(lib, entry, lmap=None, rmap=None, null=(), left=0x100000, right=0x180000, frame_stride=3 * 41 * 53, lview=None, rview=None, N=2, H0=37, W0=50,
-          pad_left=7, pad_top=13, H=64, W=64, lut=0x3000, fnet=True, cnet=True):
-    """Pointers into device memory are never dereferenced on the host: every check comes before the launch."""
-    from ppmstereo_amd import _lib as L
+def _call(lib, entry, lmap=None, rmap=None, null=(), left=0x100000, right=0x180000, frame_stride=3 * 41 * 53, lview=None, rview=None, **geometry):
+    """null: indices of the maps that are NULL; geometry: ingest_util.call's."""
     from ppmstereo_amd.ppmstereo import yuv_matrix
-    sp = lambda on, c: L.SP(0x10000 if on else None, 0x20000 if on else None, c, c)
-    maps = [_map(**(lmap or {})), _map(**(rmap or {}))]
-    mptrs = [None if i in null else ctypes.byref(x) for i, x in enumerate(maps)]
-    rest = (N, H0, W0, pad_left, pad_top, H, W, lut or None, sp(fnet, 32), sp(cnet, 64), None)
-    if entry == "u8":
-        return lib.ppms_video_ingest_u8_remap(left or None, right or None, frame_stride, *mptrs, *rest)
-    views = [_view(**(lview or {})), _view(**(rview or {})), yuv_matrix()]
-    return lib.ppms_video_ingest_yuv420_remap(*(ctypes.byref(x) for x in views), *mptrs, *rest)
+    head = [left or None, right or None, frame_stride] if entry == "u8" else [_view(**(lview or {})), _view(**(rview or {})), yuv_matrix()]
+    return call(lib, NAMES[entry], head, [_map(**(lmap or {})), _map(**(rmap or {}))], null_maps=null, **geometry)
 
 
 # (what the call's message must speak of, the one thing that is wrong with the call) -- the refusals both entry points share
@@ -122,36 +93,6 @@ def test_yuv_views_are_checked_against_the_source_frame(lib):
 
 
 # ---- the arithmetic, restated ------------------------------------------------------------------------------------------------------------
-def restated_remap(rgb, xy, frac, border="replicate", fill=0):
-    """rgb (N, 3, Hs, Ws) uint8, xy (H0, W0, 2) int16, frac (H0, W0) 16-bit -> (N, 3, H0, W0) uint8 by the header's formula, written on flat
-    pixel indices with torch.gather and a floor division (not RectifyMap.apply_u8's indexing and shift).  Shared with tests/test_gpu_ingest_remap.py."""
-    N, _, hs, ws = rgb.shape
-    H0, W0 = frac.shape
-    flat = rgb.reshape(N, 3, hs * ws).to(torch.int64)
-    x0, y0 = xy[..., 0].reshape(-1).to(torch.int64), xy[..., 1].reshape(-1).to(torch.int64)
-    f = frac.reshape(-1).to(torch.int64) & 0xFFFF
-    fx, fy = f % 32, (f // 32) % 32
-    weights = [(32 - fx) * (32 - fy), fx * (32 - fy), (32 - fx) * fy, fx * fy]
-    assert bool((sum(weights) == 1024).all())
-    total = torch.zeros((N, 3, H0 * W0), dtype=torch.int64, device=rgb.device)
-    for (dy, dx), w in zip(((0, 0), (0, 1), (1, 0), (1, 1)), weights):
-        yy, xx = y0 + dy, x0 + dx
-        inside = (yy >= 0) & (yy < hs) & (xx >= 0) & (xx < ws)
-        index = torch.minimum(torch.maximum(yy, torch.zeros_like(yy)), torch.full_like(yy, hs - 1)) * ws + \
-            torch.minimum(torch.maximum(xx, torch.zeros_like(xx)), torch.full_like(xx, ws - 1))
-        tap = torch.gather(flat, 2, index.expand(N, 3, -1))
-        if border == "constant":
-            tap = tap * inside + fill * (~inside)
-        total += w * tap
-    out = torch.div(total + 512, 1024, rounding_mode="floor")
-    assert int(out.min()) >= 0 and int(out.max()) <= 255          # no clamp is needed
-    return out.to(torch.uint8).reshape(N, 3, H0, W0)
-
-
-def rand_u8(shape, seed):
-    return torch.randint(0, 256, shape, dtype=torch.uint8, generator=torch.Generator().manual_seed(seed))
-
-
 def random_map(H0, W0, hs, ws, seed, pitch=None):
     """xy (H0, W0, 2) int16 with x0 in [-3, ws + 2], y0 in [-3, hs + 2] and frac (H0, W0) int16 holding every one of the 1024 values (H0 W0 >= 1024),
     as views of rows of `pitch` map pixels."""

@@ -1,41 +1,25 @@
 """CPU: ppms_video_ingest_u8 (uint8 video -> the first-layer operands of both encoders) is part of the C ABI, its ctypes binding has the
 header's argument list, it refuses bad arguments before touching a device, and the pad geometry handed to it is InputPadder's.  No compute."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EINVAL = -1
+from ingest_util import EINVAL, call, header_args, lib, remap_view  # noqa: F401  (lib: the fixture)
+
 NAME = "ppms_video_ingest_u8"
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from ppmstereo_amd import _lib as L
-    return L.load()
-
-
-def header_args():
-    src = open(os.path.join(ROOT, "include", "ppms.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    m = re.search(r"\bint\s+" + NAME + r"\s*\((.*?)\)\s*;", src, flags=re.S)
-    assert m, f"{NAME} is not declared in include/ppms.h"
-    return [" ".join(a.split()) for a in m.group(1).split(",")]
 
 
 def test_declared_exported_and_abi_version_unchanged(lib):
     from ppmstereo_amd import _lib as L
-    assert header_args()
+    assert header_args(NAME)
     assert NAME in L.EXPORTS and hasattr(lib, NAME)
     assert lib.ppms_version() == 4
 
 
 def test_binding_matches_the_header():
     from ppmstereo_amd import _lib as L
-    args = header_args()
+    args = header_args(NAME)
     assert args == ["const uint8_t* left", "const uint8_t* right", "int64_t frame_stride", "int N", "int H0", "int W0", "int pad_left", "int pad_top",
                     "int H", "int W", "const float* lut", "ppms_sp dst_fnet", "ppms_sp dst_cnet", "void* stream"]
     ctype = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "ppms_sp": L.SP}
@@ -44,11 +28,10 @@ def test_binding_matches_the_header():
     assert res is ctypes.c_int and bound == expect
 
 
-def _call(lib, left=0x1000, right=0x2000, stride=3 * 37 * 50, N=2, H0=37, W0=50, pad_left=7, pad_top=13, H=64, W=64, lut=0x3000, fnet=True, cnet=True):
-    """Pointers are never dereferenced on the host: every check comes before the launch."""
-    from ppmstereo_amd import _lib as L
-    sp = lambda on, c: L.SP(0x10000 if on else None, 0x20000 if on else None, c, c)
-    return lib.ppms_video_ingest_u8(left or None, right or None, stride, N, H0, W0, pad_left, pad_top, H, W, lut or None, sp(fnet, 32), sp(cnet, 64), None)
+def _call(lib, left=0x1000, right=0x2000, stride=3 * 37 * 50, twin=False, **geometry):
+    """Two frames of 37 x 50 padded to 64 x 64 (ingest_util.call).  twin: through the _remap twin, with maps whose source frame is H0 x W0."""
+    maps = [remap_view(hs=geometry.get("H0", 37), ws=geometry.get("W0", 50))] * 2 if twin else ()
+    return call(lib, NAME + "_remap" * twin, [left or None, right or None, stride], maps, **geometry)
 
 
 @pytest.mark.parametrize("bad", [dict(left=0, right=0, lut=0), dict(left=0), dict(right=0), dict(lut=0),      # NULL pointers

@@ -3,30 +3,15 @@ the C ABI, its ctypes binding has the header's argument list and struct sizes, i
 yuv_matrix / YUVFrames.to_rgb_u8 are the conversion the header states (against float64), and YUVFrames / YUVStereoVideo read pointers and
 strides from views without copying.  No device compute."""
 import ctypes
+import functools
 import itertools
-import os
-import re
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EINVAL = -1
+from ingest_util import EINVAL, call, header_args, lib, rand_u8, remap_view, yuv_view  # noqa: F401  (lib: the fixture)
+
 NAME = "ppms_video_ingest_yuv420"
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from ppmstereo_amd import _lib as L
-    return L.load()
-
-
-def header_args(name=NAME):
-    src = open(os.path.join(ROOT, "include", "ppms.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\((.*?)\)\s*;", src, flags=re.S)
-    assert m, f"{name} is not declared in include/ppms.h"
-    return [" ".join(a.split()) for a in m.group(1).split(",")]
 
 
 def test_declared_exported_and_abi_version_unchanged(lib):
@@ -39,7 +24,7 @@ def test_declared_exported_and_abi_version_unchanged(lib):
 
 def test_binding_matches_the_header(lib):
     from ppmstereo_amd import _lib as L
-    args = header_args()
+    args = header_args(NAME)
     assert args == ["const ppms_yuv_view* left", "const ppms_yuv_view* right", "const ppms_yuv_matrix* m", "int N", "int H0", "int W0", "int pad_left",
                     "int pad_top", "int H", "int W", "const float* lut", "ppms_sp dst_fnet", "ppms_sp dst_cnet", "void* stream"]
     ctype = {"int": ctypes.c_int, "ppms_sp": L.SP, "const ppms_yuv_view*": ctypes.POINTER(L.YUVView), "const ppms_yuv_matrix*": ctypes.POINTER(L.YUVMatrix),
@@ -57,22 +42,17 @@ def test_binding_matches_the_header(lib):
 
 
 # ---- argument refusal: NV12 frames of 37 x 50 (chroma 19 x 25) in surfaces of pitch 64, two frames, padded to 64 x 64 ----------------
-def _view(y=0x100000, u=0x200000, v=0x200001, fsy=37 * 64, fsc=19 * 64, pitch_y=64, pitch_c=64, step_c=2, reserved=0):
-    from ppmstereo_amd import _lib as L
-    return L.YUVView(y or None, u or None, v or None, fsy, fsc, pitch_y, pitch_c, step_c, reserved)
+_view = functools.partial(yuv_view, y=0x100000, u=0x200000, v=0x200001, fsy=37 * 64, fsc=19 * 64, pitch_y=64, pitch_c=64, step_c=2)
 
 
-def _call(lib, left=None, right=None, null=(), N=2, H0=37, W0=50, pad_left=7, pad_top=13, H=64, W=64, lut=0x3000, fnet=True, cnet=True, **m):
-    """Pointers into device memory are never dereferenced on the host: every check comes before the launch."""
-    from ppmstereo_amd import _lib as L
+def _call(lib, left=None, right=None, null=(), twin=False, **kw):
+    """kw: fields of the matrix, and the call's geometry (ingest_util.call).  twin: through the _remap twin, with maps whose source frame is H0 x W0."""
     from ppmstereo_amd.ppmstereo import yuv_matrix
-    sp = lambda on, c: L.SP(0x10000 if on else None, 0x20000 if on else None, c, c)
     mat = yuv_matrix()
-    for k, val in m.items():
-        setattr(mat, k, val)
-    views = [_view(**(left or {})), _view(**(right or {})), mat]
-    ptrs = [None if i in null else ctypes.byref(x) for i, x in enumerate(views)]
-    return lib.ppms_video_ingest_yuv420(*ptrs, N, H0, W0, pad_left, pad_top, H, W, lut or None, sp(fnet, 32), sp(cnet, 64), None)
+    for k in [k for k in kw if hasattr(mat, k)]:
+        setattr(mat, k, kw.pop(k))
+    maps = [remap_view(hs=kw.get("H0", 37), ws=kw.get("W0", 50))] * 2 if twin else ()
+    return call(lib, NAME + "_remap" * twin, [_view(**(left or {})), _view(**(right or {})), mat], maps, null=null, **kw)
 
 
 # (what the call's message must speak of, the one thing that is wrong with the call)
@@ -176,10 +156,6 @@ def test_yuv_matrix_refuses_what_the_kernel_refuses():
 
 
 # ---- YUVFrames / YUVStereoVideo on host tensors ----------------------------------------------------------------------------------------
-def rand_u8(shape, seed):
-    return torch.randint(0, 256, shape, dtype=torch.uint8, generator=torch.Generator().manual_seed(seed))
-
-
 def test_strides_are_read_from_views():
     from ppmstereo_amd.ppmstereo import YUVFrames
     surface = rand_u8((2, 37, 64), 1)                           # a pitched luma surface: 50 of 64 bytes per row are picture

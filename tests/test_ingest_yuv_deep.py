@@ -3,24 +3,16 @@ C ABI, their ctypes bindings have the header's argument lists and struct size, t
 / YUVFrames.to_rgb are the conversion the header states (against float64), YUVFrames reads byte strides, alignment and subsampling from views
 without copying, and RectifyMap.apply_levels / level_fill are the remap on levels.  No device compute."""
 import ctypes
+import functools
 import itertools
 
 import pytest
 import torch
 
-from test_ingest_yuv import COMBOS, EINVAL, STANDARDS, header_args, rand_u8
+from ingest_util import EINVAL, call, header_args, lib, rand_u8, rand_u16, remap_view, yuv_view  # noqa: F401  (lib: the fixture)
+from test_ingest_yuv import COMBOS, STANDARDS
 
 NAME, REMAP, SIZE = "ppms_video_ingest_yuv", "ppms_video_ingest_yuv_remap", "ppms_yuv_format_struct_size"
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from ppmstereo_amd import _lib as L
-    return L.load()
-
-
-def rand_u16(shape, seed, top=1 << 16):
-    return torch.randint(0, top, shape, dtype=torch.int32, generator=torch.Generator().manual_seed(seed)).to(torch.uint16)
 
 
 def test_declared_exported_and_abi_version_unchanged(lib):
@@ -53,34 +45,23 @@ def test_bindings_match_the_header(lib):
 
 
 # ---- argument refusal: P010 frames of 37 x 50 (chroma 19 x 25 pairs) in surfaces of pitch 128 bytes, two frames, padded to 64 x 64 -----------
-def _view(y=0x100000, u=0x200000, v=0x200002, fsy=37 * 128, fsc=19 * 128, pitch_y=128, pitch_c=128, step_c=4, reserved=0):
-    from ppmstereo_amd import _lib as L
-    return L.YUVView(y or None, u or None, v or None, fsy, fsc, pitch_y, pitch_c, step_c, reserved)
+_view = functools.partial(yuv_view, y=0x100000, u=0x200000, v=0x200002, fsy=37 * 128, fsc=19 * 128, pitch_y=128, pitch_c=128, step_c=4)
+_map = functools.partial(remap_view, border=1)
 
 
-def _map(xy=0x400000, frac=0x500000, pitch=50, hs=37, ws=50, border=1, fill=0, reserved=0):
-    from ppmstereo_amd import _lib as L
-    return L.RemapView(xy or None, frac or None, pitch, hs, ws, border, fill, reserved)
-
-
-def _call(lib, left=None, right=None, fmt=None, null=(), N=2, H0=37, W0=50, pad_left=7, pad_top=13, H=64, W=64, lut=0x3000, fnet=True, cnet=True,
-          lmap=None, rmap=None, **m):
-    """Pointers into device memory are never dereferenced on the host: every check comes before the launch.  lmap / rmap (dicts): the _remap twin."""
+def _call(lib, left=None, right=None, fmt=None, null=(), lmap=None, rmap=None, **kw):
+    """kw: fields of the matrix, and the call's geometry (ingest_util.call).  lmap / rmap (dicts): the _remap twin."""
     from ppmstereo_amd import _lib as L
     from ppmstereo_amd.ppmstereo import yuv_matrix
-    sp = lambda on, c: L.SP(0x10000 if on else None, 0x20000 if on else None, c, c)
     f = dict(sample_bytes=2, depth=10, lsb=6, sub_x=1, sub_y=1, reserved=(0, 0, 0))
     f.update(fmt or {})
     mat = yuv_matrix(depth=f["depth"] if f["depth"] in (8, 10, 12) else 10)
-    for k, val in m.items():
-        setattr(mat, k, val)
-    args = [_view(**(left or {})), _view(**(right or {})), mat, L.YUVFormat(f["sample_bytes"], f["depth"], f["lsb"], f["sub_x"], f["sub_y"], f["reserved"])]
-    ptrs = [None if i in null else ctypes.byref(x) for i, x in enumerate(args)]
-    rest = (N, H0, W0, pad_left, pad_top, H, W, lut or None, sp(fnet, 32), sp(cnet, 64), None)
+    for k in [k for k in kw if hasattr(mat, k)]:
+        setattr(mat, k, kw.pop(k))
+    head = [_view(**(left or {})), _view(**(right or {})), mat, L.YUVFormat(f["sample_bytes"], f["depth"], f["lsb"], f["sub_x"], f["sub_y"], f["reserved"])]
     if lmap is None and rmap is None:
-        return lib.ppms_video_ingest_yuv(*ptrs, *rest)
-    maps = [_map(**(lmap or {})), _map(**(rmap or {}))]
-    return lib.ppms_video_ingest_yuv_remap(*ptrs, *(ctypes.byref(x) for x in maps), *rest)
+        return call(lib, NAME, head, null=null, **kw)
+    return call(lib, REMAP, head, [_map(**(lmap or {})), _map(**(rmap or {}))], null=null, **kw)
 
 
 BYTES = dict(sample_bytes=1, depth=8, lsb=0)                          # (with the P010 views' strides, which are large enough for bytes too)
