@@ -486,10 +486,14 @@ int ppms_qk_pool(const float* q, const float* k, int ld, float* pooled, int T, i
 int ppms_qk_cos(const float* pooled, float* sim, int T, int cells, void* stream);
 /* QAM score + top-k pick + usage counter, ppmstereo.py:501-513, and the normalised play scores of :532-533.
  * conf_partial: output of ppms_unc_tail; strive: fp32 [T][T] in/out; sel: int32 [T][5] ascending frame ids;
- * shat: fp32 [T][5]; score (optional): fp32 [T][T]. */
+ * shat: fp32 [T][5]; score (optional): fp32 [T][T].  1 <= T <= 64.  The pick is the min(5, T) highest scores of a row; among equal
+ * scores the LOWEST frame index wins (torch's argsort leaves that order open).  Slots >= min(5, T) of sel / shat are written as 0. */
 int ppms_qam_select(const float* sim, float* strive, const float* conf_partial, int nblk, int HW, int32_t* sel, float* shat,
                     float* score, int T, void* stream);
-/* Q = bf16(q_i + PE_i) (ppmstereo.py:518-522); qb: bf16 [T][n][128] */
+/* Q = bf16(q_i + PE_i) (ppmstereo.py:518-522); qb: bf16 [T][n][128].  ppms_attn_prep_q / ppms_attn_prep_k / ppms_pick_prep_k read q / key
+ * / pe and write qb / kb 16 bytes at a time: those pointers must be 16-byte aligned (and ld % 4 == 0), T and n must be > 0; anything else
+ * is refused with PPMS_EINVAL before any launch.  Each value is ONE fp32 operation (a sum; a product, then a sum: not contracted) rounded
+ * to bf16. */
 int ppms_attn_prep_q(const float* q, int ld, const float* pe, void* qb, int T, int n, void* stream);
 /* K' = bf16(K_j * s_hat_ij + PE_j) for the picked frames (ppmstereo.py:541,547); kb: bf16 [T][ksel][n][128] */
 int ppms_attn_prep_k(const float* key, int ld, const float* pe, const int32_t* sel, const float* shat, void* kb, int T, int ksel,
@@ -511,7 +515,11 @@ enum { PPMS_ATTN_P_BF16 = 0, PPMS_ATTN_P_FP16 = 1 };   /* ppms_mem_attn: p_forma
  * image of the bf16-rounded values (ppms_epilogue.vt_f16 = 1): V is still "cast to bf16" as ppmstereo.py:550 does, Q K'^T is computed on
  * bf16 operands either way, the MFMA count is the same -- an eighth of the P~ rounding error (what keeps the iters = 20 cascade inside 1e-3 px).
  * mf.hi == NULL: no aggregation -- the `mfg` view receives hid itself (hi plane = hid, lo plane = 0: bf16-exact channels, see
- * ppms_conv.lo_zero_from; the caller then feeds the convolutions [mf | hid] with weights (W_mf + W_mfg | beta W_mfg), the same sum). */
+ * ppms_conv.lo_zero_from; the caller then feeds the convolutions [mf | hid] with weights (W_mf + W_mfg | beta W_mfg), the same sum).
+ * Alignment: qb, kb, out_bf16, split_ws and the four planes of mf / mfg are accessed 16 bytes at a time and must be 16-byte aligned (views: a
+ * multiple of 8 channels, ld % 8 == 0); so must vt where n % 8 == 0 (other n read it element by element).  A call that is not is refused with
+ * PPMS_EINVAL before any launch.  sel rows hold frame indices into vt, which may hold more frames than the T clips of the call (a sharded
+ * window: T clips of this rank, all frames of the window). */
 int ppms_mem_attn(const void* qb, const void* kb, const void* vt, const int32_t* sel, int ksel, float scale, const float* beta,
                   ppms_sp mf, ppms_sp mfg, void* out_bf16, int T, int n, void* split_ws, int frames_per_workgroup, int p_format, void* stream);
 /* split_ws (optional, caller-owned, ppms_mem_attn_workspace_bytes(T, ksel, n) bytes, contents need not be

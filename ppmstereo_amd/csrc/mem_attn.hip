@@ -739,8 +739,11 @@ extern "C" int ppms_mem_attn(const void* qb, const void* kb, const void* vt, con
     PPMS_REQUIRE(ksel >= 1 && ksel <= 5 && T >= 1 && n >= 1, "mem_attn: bad sizes ksel=%d T=%d n=%d", ksel, T, n);
     PPMS_REQUIRE(frames_per_workgroup >= 0 && frames_per_workgroup <= 5, "mem_attn: frames_per_workgroup must be 0 (automatic) or 1 .. 5, got %d", frames_per_workgroup);
     PPMS_REQUIRE(p_format == PPMS_ATTN_P_BF16 || p_format == PPMS_ATTN_P_FP16, "mem_attn: p_format must be PPMS_ATTN_P_BF16 (0) or PPMS_ATTN_P_FP16 (1), got %d", p_format);
-    PPMS_REQUIRE(((mf.hi && mf.lo && mf.ld % 8 == 0) || (!mf.hi && !mf.lo)) && mfg.hi && mfg.lo && mfg.ld % 8 == 0,
+    PPMS_REQUIRE(((mf.hi && mf.lo && mf.ld % 8 == 0) || (!mf.hi && !mf.lo)) && mfg.hi && mfg.lo && mfg.ld % 8 == 0 &&
+                     (((uintptr_t)mf.hi | (uintptr_t)mf.lo | (uintptr_t)mfg.hi | (uintptr_t)mfg.lo) & 15) == 0,
                  "mem_attn: mf (or a NULL view: the output is hid itself) / mfg must be 16-B aligned SP views");
+    PPMS_REQUIRE((((uintptr_t)qb | (uintptr_t)kb | (uintptr_t)out_bf16 | (uintptr_t)split_ws) & 15) == 0 && (n % 8 != 0 || ((uintptr_t)vt & 15) == 0),
+                 "mem_attn: qb, kb, out_bf16, split_ws (and vt where n %% 8 == 0) must be 16-byte aligned");
     const float scale_log2 = scale * 1.4426950408889634f;
     if (p_format == PPMS_ATTN_P_FP16)
         launch_mem_attn<true>(qb, kb, vt, sel, ksel, scale_log2, beta, mf, mfg, out_bf16, T, n, split_ws, frames_per_workgroup, (hipStream_t)stream);

@@ -1034,7 +1034,8 @@ __global__ __launch_bounds__(256) void attn_prep_q_kernel(const float* __restric
     *(bf16x8*)(qb + pix * 128 + g * 8) = o;
 }
 extern "C" int ppms_attn_prep_q(const float* q, int ld, const float* pe, void* qb, int T, int n, void* stream) {
-    PPMS_REQUIRE(q && pe && qb && ld % 4 == 0, "attn_prep_q: bad arguments");
+    PPMS_REQUIRE(q && pe && qb && ld % 4 == 0 && T > 0 && n > 0, "attn_prep_q: bad arguments (T, n > 0, ld %% 4 == 0)");
+    PPMS_REQUIRE((((uintptr_t)q | (uintptr_t)pe | (uintptr_t)qb) & 15) == 0, "attn_prep_q: q, pe and qb must be 16-byte aligned");
     const int64_t total = (int64_t)T * n * 16;
     hipLaunchKernelGGL(attn_prep_q_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, q, ld, pe, (bf16_t*)qb, n, total);
     return ppms_check_launch("attn_prep_q");
@@ -1065,7 +1066,9 @@ __global__ __launch_bounds__(256) void attn_prep_k_kernel(const float* __restric
 }
 extern "C" int ppms_attn_prep_k(const float* key, int ld, const float* pe, const int32_t* sel, const float* shat, void* kb, int T, int ksel,
                                 int n, void* stream) {
-    PPMS_REQUIRE(key && pe && sel && shat && kb && ksel >= 1 && ksel <= 5 && ld % 4 == 0, "attn_prep_k: bad arguments");
+    PPMS_REQUIRE(key && pe && sel && shat && kb && ksel >= 1 && ksel <= 5 && ld % 4 == 0 && T > 0 && n > 0,
+                 "attn_prep_k: bad arguments (T, n > 0, 1 <= ksel <= 5, ld %% 4 == 0)");
+    PPMS_REQUIRE((((uintptr_t)key | (uintptr_t)pe | (uintptr_t)kb) & 15) == 0, "attn_prep_k: key, pe and kb must be 16-byte aligned");
     const int64_t total = (int64_t)T * ksel * n * 16;
     hipLaunchKernelGGL(attn_prep_k_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, key, ld, pe, sel, shat,
                        (bf16_t*)kb, ksel, n, total);
@@ -1165,6 +1168,7 @@ extern "C" int ppms_pick_prep_k(const float* sim, const float* strive_in, float*
     PPMS_REQUIRE(sim && strive_in && strive_out && strive_in != strive_out && conf_partial && sel && shat && T > 0 && T <= 64 && nblk >= 0,
                  "pick_prep_k: bad arguments (1 <= T <= 64, two distinct counter tables)");
     PPMS_REQUIRE(key && pe && kb && n > 0 && ld % 4 == 0, "pick_prep_k: bad key operands");
+    PPMS_REQUIRE((((uintptr_t)key | (uintptr_t)pe | (uintptr_t)kb) & 15) == 0, "pick_prep_k: key, pe and kb must be 16-byte aligned");
     const int64_t total = (int64_t)T * n * 16;
     // few, fat workgroups: every workgroup pays the pick once, so all of them are resident at once (a CU holds 8 of these) and each streams
     // several items behind it.  Measured: 2, 4, 8 or 16 per CU give the same clip time (profiles/r08_pick_chain_ab.txt)

@@ -1,7 +1,8 @@
 """Plain float64 CPU references of the non-convolution kernels of the two encoders (encoder_ops.hip), of the glue kernels around the
-loop (small_ops.hip) and of the kernels inside every update iteration (corr.hip's lookup, pwchain.hip, ppms_dwconv_gelu, attn16.hip), one
-function per operation, each with the named wrong variants its test exists to catch; the cases (shapes and seeded inputs) of
-tests/test_gpu_encoder_ops.py, tests/test_gpu_glue_ops.py and tests/test_gpu_update_ops.py; and the tolerance rule they and the CPU test
+loop (small_ops.hip), of the kernels inside every update iteration (corr.hip's lookup, pwchain.hip, ppms_dwconv_gelu, attn16.hip) and of
+the pick-and-play memory read-out (frame similarity, QAM pick, attention operands, mem_attn.hip), one function per operation, each with
+the named wrong variants its test exists to catch; the cases (shapes and seeded inputs) of tests/test_gpu_encoder_ops.py,
+tests/test_gpu_glue_ops.py, tests/test_gpu_update_ops.py and tests/test_gpu_memory_ops.py; and the tolerance rule they and the CPU test
 tests/test_kernel_refs.py apply.  The formulas are those of oracle/ppm_oracle.py and of the kernel comments.
 
 Tolerances, three kinds, none taken from the code under test:
@@ -913,6 +914,446 @@ def linattn_check(dh, case, data, y, label=None):
     Q, K, V = linattn_inputs(dh, case, data)
     ref = linear_attention(Q, K, V)
     return Check(label or f"linear_attention dh={dh} T,n={case} {data}").add("y", y, ref, tol_reduce(ref, linear_attention_f32(Q, K, V), True))
+
+
+# ================================================================================================ memory read-out
+# The pick-and-play chain (small_ops.hip: qk_pool / qk_cos, the QAM pick, the operand kernels; mem_attn.hip): tests/test_gpu_memory_ops.py.
+# Similarity, score and s_hat are reductions (kind c); SEL and the usage counter are exact; the operands are one fp32 operation rounded to
+# bf16 (exact: the build does not contract a * s + p, -ffp-contract=off); the read-out keeps the per-element bound tests/test_gpu_ops.py
+# derives for it, restated here against the float64 read-out.
+MEM_SCALE = 128 ** -0.5 * math.log(256, 12000)                            # engine.softmax_scale(128), ppmstereo.py:494
+
+
+# ------------------------------------------------------------------------------------------------ frame similarity
+SIM_CASES = [(1, 4, 4), (2, 5, 7), (3, 10, 18), (5, 8, 32), (9, 13, 22), (2, 23, 40)]      # T, H, W: one cell; one cell row of unequal windows; ...
+SIM_EXTRA = 3                                                              # the inputs hold Tg = T + 3 frames: the other ranks' of a sharded window
+SIM_DATA = ("unit", "edge")                                                # edge: frame 0 constant zero (norm 0: the eps branch), frame 1 x 1e-6
+
+
+def _windows(n, o, adaptive=True):
+    """torch's adaptive windows: [floor(i n / o), ceil((i + 1) n / o)); or fixed windows of 4 that drop the remainder"""
+    return [((i * n) // o, -((-(i + 1) * n) // o)) for i in range(o)] if adaptive else [(4 * i, 4 * i + 4) for i in range(o)]
+
+
+def qk_pool(x, pool="max", adaptive=True, mean_first=False):
+    """x (T, H, W, 128) -> (T, (H // 4) (W // 4)) float64: the maximum of every channel over the adaptive window, then the mean over the
+    channels (ppmstereo.py:397-423).  The keyword arguments are the wrong variants."""
+    T, H, W, C = x.shape
+    OH, OW = H // 4, W // 4
+    x = x.double()
+    out = torch.empty(T, OH, OW, dtype=F64)
+    for oy, (ys, ye) in enumerate(_windows(H, OH, adaptive)):
+        for ox, (xs, xe) in enumerate(_windows(W, OW, adaptive)):
+            win = x[:, ys:ye, xs:xe].reshape(T, -1, C)
+            if mean_first:
+                out[:, oy, ox] = win.mean(2).max(1).values                 # the channel mean of every pixel, then the window's maximum
+            elif pool == "avg":
+                out[:, oy, ox] = win.mean(1).mean(1)
+            else:
+                out[:, oy, ox] = win.max(1).values.mean(1)
+    return out.reshape(T, OH * OW)
+
+
+def qk_cos(qbar, kbar, eps_each=True, transposed=False):
+    """sim[i][j] = cos(kbar_i, qbar_j), each norm clamped at 1e-8 (F.cosine_similarity)"""
+    a, b = (qbar.double(), kbar.double()) if transposed else (kbar.double(), qbar.double())
+    na, nb = a.norm(dim=1)[:, None], b.norm(dim=1)[None]
+    den = na.clamp_min(1e-8) * nb.clamp_min(1e-8) if eps_each else (na * nb).clamp_min(1e-8)
+    return (a @ b.t()) / den
+
+
+def qk_similarity(q, k, pool_kw=None, cos_kw=None):
+    """q, k (T, H, W, 128) -> qbar, kbar (T, cells), sim (T, T) float64"""
+    qbar, kbar = qk_pool(q, **(pool_kw or {})), qk_pool(k, **(pool_kw or {}))
+    return qbar, kbar, qk_cos(qbar, kbar, **(cos_kw or {}))
+
+
+def qk_similarity_f32(q, k):
+    """oracle.ppm_oracle.qk_similarity's op sequence in fp32"""
+    T, H, W, C = q.shape
+    pool = lambda x: F.adaptive_max_pool2d(x.float().permute(0, 3, 1, 2), (H // 4, W // 4)).mean(1).reshape(T, -1)
+    qbar, kbar = pool(q), pool(k)
+    return qbar, kbar, F.cosine_similarity(qbar.unsqueeze(0), kbar.unsqueeze(1), dim=-1)
+
+
+SIM_WRONG = {
+    "transposed": dict(cos_kw=dict(transposed=True)), "average_pool": dict(pool_kw=dict(pool="avg")),
+    "fixed_4x4_windows": dict(pool_kw=dict(adaptive=False)), "mean_before_max": dict(pool_kw=dict(mean_first=True)),
+    "eps_on_the_product": dict(cos_kw=dict(eps_each=False)),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def sim_inputs(case, data):
+    """q, k (T + 3, H, W, 128) fp32; k shares 0.3 of q, so the similarities are not all near 0"""
+    T, H, W = case
+    seed = 9000 + 10 * SIM_CASES.index(case)
+    q = hash_normal((T + SIM_EXTRA, H, W, 128), seed)
+    k = (hash_normal((T + SIM_EXTRA, H, W, 128), seed + 1) + 0.3 * q).float()
+    if data == "edge":
+        q[0], k[0] = 0.0, 0.0
+        q[1], k[1] = q[1] * 1e-6, k[1] * 1e-6
+    return q, k
+
+
+@functools.lru_cache(maxsize=None)
+def sim_refs(case, data, frames):
+    """(reference, fp32 torch) of the first `frames` frames: each (qbar, kbar, sim)"""
+    q, k = sim_inputs(case, data)
+    return qk_similarity(q[:frames], k[:frames]), qk_similarity_f32(q[:frames], k[:frames])
+
+
+def sim_check(case, data, frames, sim, pooled=None, label=None):
+    """sim (frames, frames); pooled (2, frames, cells) or None"""
+    ref, f32 = sim_refs(case, data, frames)
+    ck = Check(label or f"qk_similarity {case} {data} frames={frames}")
+    if pooled is not None:
+        ck.add("qbar", pooled[0], ref[0], tol_reduce(ref[0], f32[0], False)).add("kbar", pooled[1], ref[1], tol_reduce(ref[1], f32[1], False))
+    return ck.add("sim", sim, ref[2], tol_reduce(ref[2], f32[2], False))
+
+
+# ------------------------------------------------------------------------------------------------ QAM pick
+TOP_K = 5
+PICK_ITERS = 6                                                             # consecutive picks with the evolving usage counter
+PICK_CASES = {1: 1, 2: 3, 4: 64, 5: 80, 6: 1, 8: 3, 9: 65, 16: 64, 17: 80, 40: 130, 64: 65}      # T -> nblk.  T > 8: the second group of eight
+#   frames of the confidence sums; nblk > 64: a lane takes a second block; 9 / 65 and 40 / 130 have both at once; 40: the window of BASELINE
+#   config 4; 64: the documented maximum (48 KiB of dynamic LDS, bit 63 of the masks)
+PICK_SEEDS = {1: 9100, 2: 9110, 4: 9120, 5: 9130, 6: 9140, 8: 9150, 9: 9160, 16: 9170, 17: 9180, 40: 9197, 64: 9205}     # chosen so that
+#   pick_near_tie holds on every row (tests/test_kernel_refs.py asserts it): a seed that fails is replaced, no row is left out
+PICK_TIES = {  # T, tied frames, frames every clip picks first, frames picked, iterations -- an exact tie that straddles rank 5 / 6
+    "pair": (8, (2, 6), (0, 3, 5, 7), (0, 2, 3, 5, 7)),
+    "triple_two_in": (9, (1, 4, 8), (0, 2, 5), (0, 1, 2, 4, 5)),
+    "triple_one_in": (17, (3, 9, 16), (0, 5, 11, 12), (0, 3, 5, 11, 12)),
+}
+TIE_NBLK, TIE_HW = 3, 700
+
+
+def pick_hw(nblk):
+    """pixels of a map with nblk blocks of 256, the last one partly filled"""
+    return 256 * nblk - 68
+
+
+def qam_pick(sim, strive, part, HW, dtype=F64, plus_T=True, pen_axis=1, conf_op="add", shat_over="picked", count="picked", order="ascending",
+             divisor=None, ties="lowest"):
+    """sim, strive (T, T), part (T, nblk) block sums of the uncertainty map -> score (T, T), sel (T, 5) int64 ascending, shat (T, 5), the new
+    counter (T, T).  conf_j = sum_b part[j][b] / HW; score_ij = exp(-S_ij / (sum_j S_ij + T)) sim_ij + conf_j; the pick of row i: its
+    min(5, T) highest scores, the lowest frame index first among equal ones; S_i,picked += 1; shat = score_i,picked / mean(score_i,picked)
+    (ppmstereo.py:501-513, 532-533).  Slots >= min(5, T) hold 0.  dtype = float32: the plain-torch form.  The other keyword arguments are
+    the wrong variants."""
+    T = sim.shape[0]
+    sim, strive, part = sim.to(dtype), strive.to(dtype), part.to(dtype)
+    conf = part.sum(1) / (HW if divisor is None else divisor)
+    pen = torch.exp(-strive / (strive.sum(pen_axis, keepdim=True) + (T if plus_T else 0)))
+    score = pen * sim * conf[None] if conf_op == "mul" else pen * sim + conf[None]
+    k = min(TOP_K, T)
+    if ties == "lowest":
+        idx = torch.sort(score, dim=1, descending=True, stable=True).indices[:, :k]
+    else:
+        idx = T - 1 - torch.sort(score.flip(1), dim=1, descending=True, stable=True).indices[:, :k]
+    if order == "ascending":
+        idx = idx.sort(1).values
+    s = torch.gather(score, 1, idx)
+    shat = s / (score.mean(1, keepdim=True) if shat_over == "all" else s.mean(1, keepdim=True))
+    new = strive + 1 if count == "all" else strive.clone().scatter_add_(1, idx, torch.ones_like(s))
+    sel = torch.zeros(T, 5, dtype=torch.int64)
+    sh = torch.zeros(T, 5, dtype=dtype)
+    sel[:, :k], sh[:, :k] = idx, shat
+    return score, sel, sh, new
+
+
+PICK_WRONG = {
+    "penalty_without_T": dict(plus_T=False), "penalty_over_the_other_axis": dict(pen_axis=0), "confidence_multiplied": dict(conf_op="mul"),
+    "shat_over_all_frames": dict(shat_over="all"), "counter_for_every_frame": dict(count="all"), "sel_in_score_order": dict(order="score"),
+    "confidence_over_nblk_256": dict(divisor="nblk256"), "ties_to_the_highest_index": dict(ties="highest"),
+}
+
+
+def _block_sums(T, nblk, HW, seed):
+    """fp32 (T, nblk): 256 x a sigmoid per block (the sum of 256 uncertainties), the last block scaled to its pixel count"""
+    part = 256.0 * torch.sigmoid(hash_normal((T, nblk), seed))
+    part[:, -1] *= (HW - 256 * (nblk - 1)) / 256.0
+    return part.float()
+
+
+@functools.lru_cache(maxsize=None)
+def pick_inputs(T):
+    """sim (T, T) = tanh(hash_normal) (T = 1: NaN, as the product's is there), [part (T, nblk)] per iteration, HW"""
+    nblk, seed = PICK_CASES[T], PICK_SEEDS[T]
+    HW = pick_hw(nblk)
+    sim = torch.tanh(hash_normal((T, T), seed))
+    if T == 1:
+        sim.fill_(float("nan"))
+    return sim, tuple(_block_sums(T, nblk, HW, seed + 1 + it) for it in range(PICK_ITERS)), HW
+
+
+def pick_sequence(T, **wrong):
+    """the PICK_ITERS consecutive picks from a counter of ones: per iteration (counter before, reference, fp32 torch) -- both fed the
+    reference's counter (small integers: exact in either type) -- or, with a wrong variant, (counter before, its result) evolving its own"""
+    sim, parts, HW = pick_inputs(T)
+    if wrong.get("divisor") == "nblk256":
+        wrong = dict(wrong, divisor=PICK_CASES[T] * 256)
+    strive, out = torch.ones(T, T, dtype=F64), []
+    for part in parts:
+        if wrong:
+            res = qam_pick(sim, strive, part, HW, **wrong)
+            out.append((strive, res))
+        else:
+            res = qam_pick(sim, strive, part, HW)
+            out.append((strive, res, qam_pick(sim, strive, part, HW, dtype=torch.float32)))
+        strive = res[3]
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def pick_refs(T):
+    return tuple(pick_sequence(T))
+
+
+def pick_near_tie(T):
+    """(the smallest float64 gap between the 5th and the 6th score over every iteration and row, the largest |fp32 - float64| score of the
+    case): the pick is safe from an ulp of expf where the first is at least 256 x the second"""
+    gap, err = math.inf, 0.0
+    for _, ref, f32 in pick_refs(T):
+        if T > TOP_K:
+            s = ref[0].sort(1, descending=True).values
+            gap = min(gap, (s[:, TOP_K - 1] - s[:, TOP_K]).min().item())
+        if T > 1:
+            err = max(err, (f32[0].double() - ref[0]).abs().max().item())
+    return gap, err
+
+
+def pick_check(T, it, score, sel, shat, strive_new, label=None, ck=None):
+    """one iteration's results against the reference; score and shat by tol_reduce of that iteration: 8 x the fp32-torch error of the same
+    pick on the same input (T = 1: NaN scores; frame 0 is picked, the counter counts)"""
+    _, ref, f32 = pick_refs(T)[it]
+    ck = ck or Check(label or f"qam pick T={T}")
+    ck.exact(f"sel[{it}]", sel.long(), ref[1]).exact(f"counter[{it}]", strive_new.double(), ref[3])
+    if T == 1:
+        bad = float(not (torch.isnan(score).all() and torch.isnan(shat[:, 0]).all() and (shat[:, 1:] == 0).all()))
+        ck.items.append((f"nan[{it}]", bad, 0.0))
+        return ck
+    return ck.add(f"score[{it}]", score, ref[0], tol_reduce(ref[0], f32[0], False)).add(f"shat[{it}]", shat, ref[2], tol_reduce(ref[2], f32[2], False))
+
+
+@functools.lru_cache(maxsize=None)
+def tie_inputs(name):
+    """sim, counter, part with bit-equal columns / rows at the tied frames; the frames of `first` carry confidence ~10, the tied ones ~5,
+    the rest ~0.5, so that in every row the tie occupies the ranks from len(first) + 1 on"""
+    T, tied, first, _ = PICK_TIES[name]
+    seed = 9300 + 10 * list(PICK_TIES).index(name)
+    sim = torch.tanh(hash_normal((T, T), seed))
+    strive = 1.0 + torch.floor(3.0 * torch.sigmoid(hash_normal((T, T), seed + 1)))
+    part = _block_sums(T, TIE_NBLK, TIE_HW, seed + 2)
+    part[list(first)] += 10.0 * TIE_HW / TIE_NBLK
+    part[list(tied)] += 5.0 * TIE_HW / TIE_NBLK
+    for t in tied[1:]:
+        sim[:, t], strive[:, t], part[t] = sim[:, tied[0]], strive[:, tied[0]], part[tied[0]]
+    return sim, strive, part.float()
+
+
+def tie_check(name, score, sel, shat, strive_new, label=None):
+    sim, strive, part = tie_inputs(name)
+    T, tied, first, picked = PICK_TIES[name]
+    ref = qam_pick(sim, strive, part, TIE_HW)
+    f32 = qam_pick(sim, strive, part, TIE_HW, dtype=torch.float32)
+    ck = Check(label or f"qam pick tie {name}")
+    ck.exact("sel", sel.long(), torch.tensor(picked).expand(T, 5)).exact("sel=ref", sel.long(), ref[1]).exact("counter", strive_new.double(), ref[3])
+    return ck.add("score", score, ref[0], tol_reduce(ref[0], f32[0], False)).add("shat", shat, ref[2], tol_reduce(ref[2], f32[2], False))
+
+
+# ------------------------------------------------------------------------------------------------ attention operands
+PREP_N = [1, 5, 64, 100]
+PREP_LD = (128, 256)
+PREP_KSEL = (1, 3, 5)
+PREP_T, PREP_TG = 2, 7                                                     # clips of this rank, frames of the window (the sharded form)
+
+
+def prep_q(q, pe):
+    """q (T, n, 128), pe (T, 128) fp32 -> bf16(q + pe): one fp32 addition (ppmstereo.py:518-522)"""
+    return (q.float() + pe.float()[:, None]).to(torch.bfloat16)
+
+
+def prep_k(key, pe, sel, shat, ksel):
+    """key (Tg, n, 128), pe (Tg, 128), sel (T, 5), shat (T, 5) -> (T, ksel, n, 128) bf16(key[sel] * shat + pe[sel]): an fp32 product rounded,
+    then an fp32 sum rounded (ppmstereo.py:541, 547)"""
+    J = sel[:, :ksel].long()
+    return (key.float()[J] * shat.float()[:, :ksel, None, None] + pe.float()[J][:, :, None]).to(torch.bfloat16)
+
+
+@functools.lru_cache(maxsize=None)
+def prep_inputs(n):
+    """q, key (Tg, n, 128), pe (Tg, 128) -- finite, unlike temporal_pe at T = 1 --, sel (T, 5) rows ascending over the Tg frames, shat (T, 5)"""
+    seed = 9400 + n
+    q, key = hash_normal((PREP_TG, n, 128), seed), hash_normal((PREP_TG, n, 128), seed + 1)
+    pe = torch.sin(hash_normal((PREP_TG, 128), seed + 2) * 3.0)
+    sel = torch.tensor([[1, 2, 4, 5, 6], [0, 3, 4, 5, 6]], dtype=torch.int32)
+    shat = (1.0 + 0.3 * torch.tanh(hash_normal((PREP_T, 5), seed + 3))).float()
+    return q, key, pe.float(), sel, shat
+
+
+# ------------------------------------------------------------------------------------------------ memory attention
+ATTN_BETA = 0.5
+ATTN32_T, ATTN32_N, ATTN32_KSEL = 2, [4, 20, 36, 60, 72, 100], (1, 3, 5)   # 60: n % 8 != 0 (element-wise V loads); 72: vector rows, a partial tile
+ATTN64_T, ATTN64_N, ATTN64_KSEL = 3, [64, 128, 192, 320], (1, 2, 3, 4, 5)  # 1, 2, 3 and 5 key tiles per frame; waves without a query
+ATTN64_FRAMES = (0, 1, 2, 3, 4, 5)                                         # frames_per_workgroup, values above ksel included
+ATTN_SHARDED = {32: (2, 6, 100, 3, ((1, 3, 5), (0, 2, 5))), 64: (2, 6, 128, 3, ((1, 3, 5), (0, 2, 5)))}      # kernel -> T clips, Tg frames of vt, n, ksel, sel
+FIXUP_T, FIXUP_N, FIXUP_KSEL, FIXUP_SLOT, FIXUP_FRAMES = 2, 320, 5, 2, (1, 2, 3)
+
+
+def attn_eps_p(p_format):
+    """half an ulp of the format the probabilities are rounded to: 2^-8 (bf16), 2^-11 (fp16)"""
+    return 2.0 ** -11 if p_format == 1 else 2.0 ** -8
+
+
+def mem_attn(q, k, v, sel, ksel, scale, v_from="sel", softmax="joint", pad_keys=False):
+    """q (T, n, 128), k (T, ksel, n, 128), v (Tg, 128, n) -- the values the 16-bit operands hold --, sel (T, 5) -> x (T, n, 128) float64 =
+    softmax(Q K^T scale) V over the ksel n keys of the picked frames, and P |V| (T, n, 128), the weight of the probability rounding in
+    the bound.  The keyword arguments are the wrong variants."""
+    T, n, _ = q.shape
+    xs, pvs = [], []
+    for i in range(T):
+        J = [int(sel[i, s]) if v_from == "sel" else s for s in range(ksel)]
+        Q, K = q[i].double(), k[i].double()                               # (n, 128), (ksel, n, 128)
+        V = torch.stack([v[j].double().t() for j in J])                   # (ksel, n, 128)
+        if pad_keys:                                                      # the keys up to the next multiple of 64: zero keys, zero values
+            pad = -n % 64
+            K, V = F.pad(K, (0, 0, 0, pad)), F.pad(V, (0, 0, 0, pad))
+        S = torch.einsum("qc,skc->qsk", Q, K) * scale                     # (n, ksel, keys)
+        if softmax == "joint":
+            P = torch.softmax(S.reshape(n, -1), dim=-1).reshape(S.shape)
+        else:                                                             # per frame, then averaged: the 2^(m_s - m) l_s weights left out
+            P = torch.softmax(S, dim=-1) / ksel
+        xs.append(torch.einsum("qsk,skc->qc", P, V))
+        pvs.append(torch.einsum("qsk,skc->qc", P, V.abs()))
+    return torch.stack(xs), torch.stack(pvs)
+
+
+def mem_attn_f32(q, k, v, sel, ksel, scale):
+    """oracle.ppm_oracle.flash_attn_math's op sequence: fp32 softmax and product on the 16-bit operands, bf16 result"""
+    out = []
+    for i in range(q.shape[0]):
+        K = k[i].float().reshape(-1, 128)
+        V = torch.cat([v[int(sel[i, s])].float().t() for s in range(ksel)], 0)
+        out.append((torch.softmax((q[i].float() @ K.t()) * scale, dim=-1) @ V).to(torch.bfloat16))
+    return torch.stack(out)
+
+
+def mfg_of(mf, hid, beta=ATTN_BETA):
+    """mf (T n, 128), hid (T, n, 128) bf16 -> mf + beta hid, float64"""
+    return mf.double() + beta * hid.float().double().reshape(mf.shape)
+
+
+ATTN_WRONG = {
+    "v_from_slot": dict(kw=dict(v_from="slot")), "per_frame_softmax_averaged": dict(kw=dict(softmax="per_frame")),
+    "tail_keys_unmasked": dict(kw=dict(pad_keys=True), needs_tail=True), "scale_without_log2e": dict(scale=math.log(2.0)),
+    "scale_with_log2e_twice": dict(scale=1.0 / math.log(2.0)), "beta_dropped": dict(beta=1.0), "hid_rounded_before_the_division": dict(round_first=True),
+}
+
+
+def mem_attn_wrong(name, case):
+    """(hid bf16, mfg float64) of a wrong variant on the inputs attn_named_inputs(*case), or None where it does not apply"""
+    w = ATTN_WRONG[name]
+    (q, k, v, sel, ksel, mf), scale = attn_named_inputs(*case)
+    if w.get("needs_tail") and q.shape[1] % 64 == 0:
+        return None
+    if w.get("round_first"):                                              # O = P~ V and l = sum P~ with P~ = exp(S - max); bf16(O) / l
+        x, _ = mem_attn(q, k, v, sel, ksel, scale)
+        S = torch.einsum("tqc,tskc->tqsk", q.double(), k.double()).reshape(q.shape[0], q.shape[1], -1) * scale
+        l = torch.exp(S - S.max(-1, keepdim=True).values).sum(-1, keepdim=True)
+        hid = ((x * l).float().to(torch.bfloat16).double() / l).float().to(torch.bfloat16)
+    else:
+        hid = mem_attn(q, k, v, sel, ksel, scale * w.get("scale", 1.0), **w.get("kw", {}))[0].float().to(torch.bfloat16)
+    return hid, mfg_of(mf, hid, w.get("beta", ATTN_BETA))
+
+
+def _v16(x):
+    """x rounded to bf16, as fp32; the few values too small for fp16 to hold exactly (|v| < 2^-14, off its 2^-24 grid) become 0, so that the
+    bf16 and the fp16 image of V^T (ppms_mem_attn's two p_formats) hold the same numbers and one reference serves both"""
+    v = x.to(torch.bfloat16).float()
+    return torch.where(v.half().float() == v, v, torch.zeros_like(v))
+
+
+def _attn_sel(T, Tg, ksel, seed):
+    """(T, 5) int32: per clip ksel distinct frames of the Tg, ascending; no row is the identity 0 .. ksel - 1"""
+    g = torch.Generator().manual_seed(seed)
+    sel = torch.zeros(T, 5, dtype=torch.int32)
+    for i in range(T):
+        while True:
+            row = torch.randperm(Tg, generator=g)[:ksel].sort().values
+            if row.tolist() != list(range(ksel)):
+                break
+        sel[i, :ksel] = row.int()
+    return sel
+
+
+@functools.lru_cache(maxsize=None)
+def attn_inputs(T, Tg, n, ksel, rows=None):
+    """q (T, n, 128), k (T, ksel, n, 128), v (Tg, 128, n): hash_normal rounded to bf16 (what the operand buffers hold); sel (T, 5); ksel;
+    mf (T n, 128) as split bf16 holds it"""
+    seed = 9500 + 7 * n + ksel + 100 * Tg
+    r = lambda shape, s: hash_normal(shape, s).to(torch.bfloat16).float()
+    sel = _attn_sel(T, Tg, ksel, seed + 3)
+    if rows is not None:
+        sel[:, :ksel] = torch.tensor(rows, dtype=torch.int32)
+    return (r((T, n, 128), seed), r((T, ksel, n, 128), seed + 1), _v16(hash_normal((Tg, 128, n), seed + 2)), sel, ksel,
+            sp_round(hash_normal((T * n, 128), seed + 4)))
+
+
+@functools.lru_cache(maxsize=None)
+def fixup_inputs():
+    """test_mem_attn_sharp_softmax's construction, confined to one tile: the keys are 0.1 hash_normal; every query i of the partly filled second
+    256-query block of clip 0 has ONE key, in slot 2, that carries 40 x the unit vector of the query's channels 64-127, and the queries of
+    the first block are zero in those channels (they meet the boosted keys with a score of exactly 0 from them).  Clip 1 has no such key.
+    scale = 1: the boosted score is ~650 log2 units above the others."""
+    T, n, ksel = FIXUP_T, FIXUP_N, FIXUP_KSEL
+    q = hash_normal((T, n, 128), 9600)
+    k = hash_normal((T, ksel, n, 128), 9601) * 0.1
+    q[:, :256, 64:] = 0.0
+    for i in range(256, n):
+        u = q[0, i].clone()
+        u[:64] = 0.0
+        k[0, FIXUP_SLOT, (i * 7 + 300) % n] += 40.0 * u / u.norm()
+    r = lambda t: t.to(torch.bfloat16).float()
+    q, k = r(q), r(k)
+    assert (q[:, :256, 64:] == 0).all()
+    v = _v16(hash_normal((ksel + 1, 128, n), 9602))
+    return q, k, v, _attn_sel(T, ksel + 1, ksel, 9603), ksel, sp_round(hash_normal((T * n, 128), 9604))
+
+
+def attn_named_inputs(kind, *args):
+    """("table", kernel, n, ksel): a case of the 32- / 64-query tables -- vt holds max(T, ksel + 1) frames, so that no sel row is the identity;
+    ("sharded", kernel): T clips of this rank, sel rows over the Tg frames of vt; ("fixup",): fixup_inputs.  -> (inputs, softmax scale)"""
+    if kind == "table":
+        kernel, n, ksel = args
+        T = ATTN32_T if kernel == 32 else ATTN64_T
+        return attn_inputs(T, max(T, ksel + 1), n, ksel), MEM_SCALE
+    if kind == "sharded":
+        return attn_inputs(*ATTN_SHARDED[args[0]]), MEM_SCALE
+    return fixup_inputs(), 1.0
+
+
+@functools.lru_cache(maxsize=None)
+def attn_ref(kind, *args):
+    """(x, P |V|) of the named inputs: computed once, shared by the formats and launch forms of the case"""
+    inp, scale = attn_named_inputs(kind, *args)
+    return mem_attn(*inp[:5], scale)
+
+
+def attn_check(name, p_format, raw, mfg, label=None):
+    """name: the arguments of attn_named_inputs; raw (T, n, 128) bf16 hid, mfg (T n, 128) fp32 (hi + lo).  Per element |raw - x| <=
+    eps_P (P |V|) (the probabilities rounded to the P~ format before the product, all errors aligned) + 2^-8 |x| (the bf16 result: half an
+    ulp) + 1e-6; per clip the mean error at most half the mean bound (rounding errors do not line up: the final rounding alone averages ~0.35 of
+    its term); mfg = mf + beta raw as split bf16."""
+    x, pv = attn_ref(*name)
+    mf = attn_named_inputs(*name)[0][5]
+    bound = attn_eps_p(p_format) * pv + 2.0 ** -8 * x.abs() + 1e-6
+    ck = Check(label or f"mem_attn {name} p_format={p_format}")
+    got = raw.detach().cpu().float().double()
+    finite = got.shape == x.shape and bool(torch.isfinite(got).all())
+    ck.items.append(("hid/bound", ((got - x).abs() / bound).max().item() if finite else math.inf, 1.0))
+    ck.items.append(("mean", ((got - x).abs().mean((1, 2)) / bound.mean((1, 2))).max().item() if finite else math.inf, 0.5))      # per clip
+    want = mfg_of(mf, raw.detach().cpu())
+    return ck.add("mfg", mfg, want, tol_sp(want))
 
 
 # ------------------------------------------------------------------------------------------------ device buffers of the GPU tests

@@ -3,6 +3,8 @@ inputs and with the tolerance rule of every GPU case of test_gpu_encoder_ops.py 
 they exist to catch: every named wrong variant exceeds the tolerance on at least one case of its kernel, while the reference itself and
 the plain fp32 torch form stay inside it.  That is a condition on the cases, not a measurement: where a variant slips through, the inputs
 change, not the tolerance."""
+import math
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -478,3 +480,230 @@ def test_linattn_eps_needs_the_tiny_data():
     runs = _la_runs(R.LA_WRONG["no_divisor_eps"], ("tiny",))
     assert all(not c.ok for c in runs if "644" not in c.label)                          # n = 3 and 77; at n = 644 Q . sum K is 0.03, the eps 3e-5 of it
     assert all(c.ok for c in _la_runs(R.LA_WRONG["no_divisor_eps"], ("unit",)))         # invisible at unit-scale K
+
+
+# ================================================================================================ memory read-out
+# ------------------------------------------------------------------------------------------------ references vs the oracle
+def test_mem_scale():
+    from oracle import ppm_oracle as O
+    from ppmstereo_amd.engine import softmax_scale
+    assert R.MEM_SCALE == O.softmax_scale(128) == softmax_scale(128)
+
+
+@pytest.mark.parametrize("case", [(2, 5, 7), (9, 13, 22), (2, 23, 40)])
+def test_similarity_vs_oracle(case):
+    """the float64 windows, channel mean and cosine against oracle.qk_similarity fed float64 (F.adaptive_max_pool2d, F.cosine_similarity)"""
+    from oracle import ppm_oracle as O
+    q, k = R.sim_inputs(case, "unit")
+    qbar, kbar, sim = R.qk_similarity(q, k)
+    nchw = lambda x: x.double().permute(0, 3, 1, 2)
+    close(sim, O.qk_similarity(nchw(q), nchw(k)))
+    H, W = case[1:]
+    close(qbar, F.adaptive_max_pool2d(nchw(q), (H // 4, W // 4)).mean(1).reshape(q.shape[0], -1))
+    q, k = R.sim_inputs(case, "edge")                                      # a zero frame: cos = 0 by the clamp of each norm, as torch gives it
+    sim = R.qk_similarity(q, k)[2]
+    close(sim, O.qk_similarity(nchw(q), nchw(k)))
+    assert torch.isfinite(sim).all() and (sim[0] == 0).all() and (sim[:, 0] == 0).all() and sim[1, 1].abs() > 0.1
+
+
+@pytest.mark.parametrize("T", [6, 9, 40])
+def test_pick_vs_oracle(T):
+    """every iteration of the case against oracle.qam_select and the s_hat of oracle.play_inputs, fed float64 (no ties in these inputs)"""
+    from oracle import ppm_oracle as O
+    sim, parts, HW = R.pick_inputs(T)
+    for (strive, ref, _), part in zip(R.pick_refs(T), parts):
+        score, mask, new = O.qam_select(sim.double(), strive, part.double().sum(1) / HW)
+        close(ref[0], score)
+        assert torch.equal(ref[3], new)
+        for i in range(T):
+            J = torch.nonzero(mask[i]).flatten()
+            assert ref[1][i].tolist() == J.tolist()
+            z = torch.zeros(T, 4, 1, 1, dtype=F64)
+            s_hat = O.play_inputs(z, z, torch.zeros(T, 4, dtype=F64), z, score, mask, i)[4]
+            close(ref[2][i], s_hat)
+
+
+def test_operands_vs_oracle_play_inputs():
+    """prep_q / prep_k are bit for bit the bf16 rounding of play_inputs' fp32 Q and K'"""
+    from oracle import ppm_oracle as O
+    T, h, w = 6, 2, 5
+    q, key, pe = hash_normal((T, 128, h, w), 70), hash_normal((T, 128, h, w), 71), torch.sin(hash_normal((T, 128), 72))
+    score = 1.0 + 0.3 * torch.tanh(hash_normal((T, T), 73))
+    mask = torch.zeros(T, T, dtype=torch.bool).scatter_(1, torch.argsort(score, 1, descending=True)[:, :5], True)
+    cl = lambda x: x.permute(0, 2, 3, 1).reshape(T, h * w, 128)
+    sel, shat = torch.zeros(T, 5, dtype=torch.int32), torch.zeros(T, 5)
+    ops = [O.play_inputs(q, key, pe, key, score, mask, i) for i in range(T)]
+    for i, (_, _, _, J, s_hat) in enumerate(ops):
+        sel[i], shat[i] = J.int(), s_hat
+    qb, kb = R.prep_q(cl(q), pe), R.prep_k(cl(key), pe, sel, shat, 5)
+    for i, (Q, K, _, _, _) in enumerate(ops):
+        assert torch.equal(qb[i], Q.to(torch.bfloat16)) and torch.equal(kb[i].reshape(-1, 128), K.to(torch.bfloat16))
+
+
+def test_mem_attn_vs_oracle_flash_attn_math():
+    from oracle import ppm_oracle as O
+    name = ("table", 32, 36, 3)
+    (q, k, v, sel, ksel, mf), scale = R.attn_named_inputs(*name)
+    x, _ = R.attn_ref(*name)
+    f32 = R.mem_attn_f32(q, k, v, sel, ksel, scale)
+    for i in range(q.shape[0]):
+        V = torch.cat([v[int(sel[i, s])].t() for s in range(ksel)], 0)
+        want = O.flash_attn_math(q[i], k[i].reshape(-1, 128), V, scale)
+        assert torch.equal(f32[i].float(), want)
+        assert ((want.double() - x[i]).abs() <= 2.0 ** -8 * x[i].abs() + 1e-6).all()       # the oracle's result is the bf16 rounding of x
+
+
+def test_memory_case_arithmetic():
+    """what the case tables are built to contain"""
+    assert all(R.pick_hw(nb) > 256 * (nb - 1) for nb in R.PICK_CASES.values()) and R.pick_hw(3) == 700
+    assert R.PICK_CASES[9] == 65 and R.PICK_CASES[40] == 130 and set(R.PICK_CASES.values()) == {1, 3, 64, 65, 80, 130}
+    assert [n // 64 for n in R.ATTN64_N] == [1, 2, 3, 5] and 60 % 8 and not 72 % 8 and 72 % 64
+    # n = 320, ksel = 5, two frames per workgroup: 2 query blocks x 3 clips x 3 splits = 18 workgroups, 12 of them with two frames
+    gx, nsp, nfull = (320 + 255) // 256, (5 + 1) // 2, 5 // 2
+    assert gx * R.ATTN64_T * nsp == 18 and gx * R.ATTN64_T * nfull == 12 and 18 & 7 and 12 & 7
+    for kernel in (32, 64):
+        T, Tg, n, ksel, _ = R.ATTN_SHARDED[kernel]
+        sel = R.attn_named_inputs("sharded", kernel)[0][3]
+        assert Tg > T and int(sel.max()) == Tg - 1 and (n % 64 == 0) == (kernel == 64)
+    for name in (("table", 32, 4, 5), ("table", 64, 320, 3), ("fixup",)):
+        sel, ksel = R.attn_named_inputs(*name)[0][3:5]
+        for row in sel[:, :ksel].tolist():
+            assert row == sorted(set(row)) and row != list(range(ksel))
+    # the 64-query kernel flags a tile whose scores rise 2^16 (fp16 P~) above the first keys' maximum: no score of its table's inputs can
+    for name in [("table", 64, n, ksel) for n in R.ATTN64_N for ksel in R.ATTN64_KSEL] + [("sharded", 64)]:
+        (q, k, *_), scale = R.attn_named_inputs(*name)
+        s = torch.einsum("tqc,tskc->tqsk", q.double(), k.double()) * (scale / math.log(2.0))
+        assert (s.amax((2, 3)) - s.amin((2, 3))).max() < 16.0, name
+    q, k = R.fixup_inputs()[:2]
+    s = torch.einsum("qc,skc->qsk", q[0].double(), k[0].double())
+    assert s[:256].abs().max() < 8 and (s[256:, R.FIXUP_SLOT].max(1).values > 250).all() and s[256:, [0, 1, 3, 4]].abs().max() < 8
+    assert torch.einsum("qc,skc->qsk", q[1].double(), k[1].double()).abs().max() < 8
+
+
+# ------------------------------------------------------------------------------------------------ similarity: cases and wrong variants
+def _sim_runs(fn, data_kinds=R.SIM_DATA):
+    out = []
+    for case in R.SIM_CASES:
+        for data in data_kinds:
+            for frames in (case[0], case[0] + R.SIM_EXTRA):
+                q, k = R.sim_inputs(case, data)
+                qbar, kbar, sim = fn(q[:frames], k[:frames])
+                out.append(R.sim_check(case, data, frames, sim, torch.stack([qbar, kbar])))
+    return out
+
+
+def test_similarity_cases_pass_the_reference_and_fp32():
+    assert all(c.ok for c in _sim_runs(R.qk_similarity))
+    runs = _sim_runs(R.qk_similarity_f32)
+    assert all(c.ok for c in runs), [str(c) for c in runs if not c.ok]
+
+
+@pytest.mark.parametrize("name", list(R.SIM_WRONG))
+def test_similarity_wrong_variant_is_caught(name):
+    runs = _sim_runs(lambda q, k: R.qk_similarity(q, k, **R.SIM_WRONG[name]))
+    assert any(not c.ok for c in runs), name
+    if name == "eps_on_the_product":                                       # only the tiny frame shows it
+        assert all(c.ok for c in _sim_runs(lambda q, k: R.qk_similarity(q, k, **R.SIM_WRONG[name]), ("unit",)))
+    if name == "fixed_4x4_windows":                                        # the maps with a remainder
+        assert all(c.ok == (case[1] % 4 == 0 and case[2] % 4 == 0) for c, case in zip(runs[::4], R.SIM_CASES))
+
+
+# ------------------------------------------------------------------------------------------------ pick: cases, near ties, wrong variants
+def _pick_runs(results_of):
+    """results_of(T) -> per iteration (score, sel, shat, new counter)"""
+    out = []
+    for T in R.PICK_CASES:
+        ck = R.Check(f"qam pick T={T}")
+        for it, res in enumerate(results_of(T)):
+            R.pick_check(T, it, *res, ck=ck)
+        out.append(ck)
+    return out
+
+
+def test_pick_cases_pass_the_reference_and_fp32():
+    assert all(c.ok for c in _pick_runs(lambda T: [ref for _, ref, _ in R.pick_refs(T)]))
+    runs = _pick_runs(lambda T: [f32 for _, _, f32 in R.pick_refs(T)])
+    assert all(c.ok for c in runs), [str(c) for c in runs if not c.ok]
+    for T in R.PICK_CASES:                                                 # the counter really evolved
+        assert R.pick_refs(T)[-1][1][3].sum().item() == T * T + R.PICK_ITERS * T * min(5, T)
+
+
+@pytest.mark.parametrize("T", list(R.PICK_CASES))
+def test_pick_cases_have_no_near_tie(T):
+    """every case, iteration and row with T > 5: the float64 gap between the 5th and the 6th score is at least 256 x the largest fp32-torch
+    score error of the case, so an ulp of expf cannot change a pick.  A seed that fails is replaced; no row is left out."""
+    gap, err = R.pick_near_tie(T)
+    print(f"T={T}: gap {gap:.3e}, fp32 score error {err:.3e}")
+    assert err < 2.5e-7
+    assert T <= R.TOP_K or gap >= 256.0 * err, (T, gap, err)
+
+
+def test_tie_cases_are_exact_ties_across_the_fifth_rank():
+    for name, (T, tied, first, picked) in R.PICK_TIES.items():
+        sim, strive, part = R.tie_inputs(name)
+        for dtype in (F64, torch.float32):
+            score, sel, shat, new = R.qam_pick(sim, strive, part, R.TIE_HW, dtype=dtype)
+            assert all(torch.equal(score[:, t], score[:, tied[0]]) for t in tied)
+            rank = (score > score[:, tied[0]][:, None]).sum(1)             # scores above the tie: the same count in every row
+            assert (rank == len(first)).all() and len(first) < 5 < len(first) + len(tied)
+            assert sel.tolist() == [list(picked)] * T
+            assert R.tie_check(name, score, sel, shat, new).ok
+        keep = [t for t in tied if t in picked]
+        assert keep == list(tied[:len(keep)]) and len(keep) == 5 - len(first)                  # the lowest indices of the tie
+
+
+@pytest.mark.parametrize("name", list(R.PICK_WRONG))
+def test_pick_wrong_variant_is_caught(name):
+    kw = R.PICK_WRONG[name]
+    ties = []
+    for tie in R.PICK_TIES:
+        sim, strive, part = R.tie_inputs(tie)
+        k2 = dict(kw, divisor=R.TIE_NBLK * 256) if name == "confidence_over_nblk_256" else kw
+        ties.append(R.tie_check(tie, *R.qam_pick(sim, strive, part, R.TIE_HW, **k2)))
+    if name == "ties_to_the_highest_index":                               # visible at exact ties only, and at every one of them
+        assert all(not c.ok for c in ties)
+        return
+    runs = _pick_runs(lambda T: [res for _, res in R.pick_sequence(T, **kw)])
+    assert any(not c.ok for c in runs), name
+    caught = [T for T, c in zip(R.PICK_CASES, runs) if not c.ok]
+    assert any(T > 8 for T in caught) and any(T <= 8 for T in caught), (name, caught)
+
+
+# ------------------------------------------------------------------------------------------------ attention: cases and wrong variants
+ATTN_NAMES = ([("table", 32, n, ksel) for n in R.ATTN32_N for ksel in R.ATTN32_KSEL] + [("table", 64, n, ksel) for n in R.ATTN64_N for ksel in R.ATTN64_KSEL]
+              + [("sharded", 32), ("sharded", 64), ("fixup",)])
+
+
+def _attn_runs(fn, names=ATTN_NAMES):
+    out = []
+    for name in names:
+        res = fn(name)
+        if res is not None:
+            hid, mfg = res
+            out += [R.attn_check(name, p, hid, mfg) for p in (0, 1)]
+    return out
+
+
+def _attn_exact(name):
+    hid = R.attn_ref(*name)[0].float().to(torch.bfloat16)
+    return hid, R.mfg_of(R.attn_named_inputs(*name)[0][5], hid)
+
+
+def _attn_f32(name):
+    (q, k, v, sel, ksel, mf), scale = R.attn_named_inputs(*name)
+    hid = R.mem_attn_f32(q, k, v, sel, ksel, scale)
+    return hid, R.sp_round(mf + R.ATTN_BETA * hid.float().reshape(mf.shape))
+
+
+def test_attn_cases_pass_the_reference_and_fp32():
+    runs = _attn_runs(_attn_exact) + _attn_runs(_attn_f32)
+    assert all(c.ok for c in runs), [str(c) for c in runs if not c.ok]
+
+
+@pytest.mark.parametrize("name", list(R.ATTN_WRONG))
+def test_attn_wrong_variant_is_caught(name):
+    runs = _attn_runs(lambda case: R.mem_attn_wrong(name, case))
+    assert runs and any(not c.ok for c in runs), name
+    for kernel in (32, 64):                                                # both kernels' tables see every mistake that applies to them
+        mine = [c for c in runs if f"'table', {kernel}" in c.label]
+        assert not mine or any(not c.ok for c in mine), (name, kernel)
