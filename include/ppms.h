@@ -377,7 +377,8 @@ int ppms_remap_struct_size(int* view);               /* sizeof(ppms_remap_view) 
  * or 2; a depth that does not go with it (8 with 1; 10 or 12 with 2); lsb not 0 or 16 - depth; (sub_x, sub_y) not (1,1), (1,0) or (0,0) -- (0,1)
  * included; non-zero reserved; an odd pointer or stride with 16-bit samples; a pitch or frame stride too small for the sample size and the
  * subsampling; shift, y_off or fill outside the bounds above.
- * Not covered: interpolated chroma siting, 16-bit depth, packed formats (YUYV / Y210 / v210), BT.2020 and HDR transfer functions, high-depth RGB. */
+ * Not covered: interpolated chroma siting, 16-bit depth, BT.2020 and HDR transfer functions, high-depth RGB.  (Packed YUYV / Y210 / v210:
+ * ppms_video_ingest_yuv_packed below.) */
 typedef struct ppms_yuv_format {
     int32_t sample_bytes;             /* 1, or 2 (little-endian 16-bit words) */
     int32_t depth;                    /* 8 with sample_bytes 1; 10 or 12 with sample_bytes 2 */
@@ -425,8 +426,8 @@ int ppms_yuv_format_struct_size(int* fmt);           /* sizeof(ppms_yuv_format) 
  * not 0 or 16 - depth; pattern outside 0..4; black, a gain or shift outside the bounds above; an odd pointer, pitch or frame stride with 16-bit
  * samples; a pitch shorter than a row; with N > 1 a frame_stride shorter than a frame; a frame smaller than 2 x 2 with a colour pattern; what
  * ppms_video_ingest_u8 refuses about sizes, pads and destinations; for _remap, whatever the _remap calls above refuse.
- * Not covered: packed 10p / 12p transport formats, 14- and 16-bit sensors (the level table would not fit LDS), demosaicing better than bilinear,
- * colour-correction matrices, lens shading and defect pixels, patterns that differ between the two views. */
+ * Not covered: 14- and 16-bit sensors (the level table would not fit LDS), demosaicing better than bilinear, colour-correction matrices, lens
+ * shading and defect pixels, patterns that differ between the two views.  (Packed 10p / 12p transport formats: ppms_video_ingest_raw_packed below.) */
 typedef struct ppms_raw_view {        /* one view's frames, as the camera driver left them */
     const uint8_t* data;              /* sample (0,0) of frame 0 */
     int64_t frame_stride;             /* bytes from frame n to frame n + 1 */
@@ -451,6 +452,82 @@ int ppms_video_ingest_raw_remap(const ppms_raw_view* left, const ppms_raw_view* 
                                 int N, int H0, int W0, int pad_left, int pad_top, int H, int W,
                                 const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream);
 int ppms_raw_struct_sizes(int* view, int* format);   /* sizeof of the two structs above (24, 48): lets a binding verify its layout */
+/* ppms_video_ingest_yuv and ppms_video_ingest_raw (and their _remap twins) for the PACKED formats cameras and capture cards put on the wire, one
+ * launch, no unpacked intermediate: YUYV / UYVY / YVYU / VYUY (UVC cameras), Y210 / Y212, v210 (SDI capture), MIPI CSI-2 RAW10 / RAW12 (V4L2
+ * SRGGB10P ...) and GenICam PFNC Mono10p / BayerRG12p ....  A packed format is another way of fetching sample (y, x): each call below is DEFINED by
+ * the unpacked call on the frames that hold the same samples, and writes its bits.
+ *   The view.  One pitched surface per view: row y of frame n starts at data + n * frame_stride + y * pitch (BYTES).  Column x of the view is
+ * surface column p = x + x0: the right half of a side-by-side frame is the same surface with another x0, which may lie in the middle of a v210 or
+ * RAW10 group.  x0 must be even for YUV (a chroma pair may not be split) and may be any value >= 0 for raw (the pattern is that of the view's own
+ * pixel (0, 0)); x0 + ws <= 65536.  The views and formats are HOST memory, read before the call returns; `data` is a device pointer.
+ *   Packed 4:2:2 YUV.  A row is a stream of components.  For pixel p and its pair j = p >> 1 the component indices are Y = 2 p + a, U = 4 j + b,
+ * V = 4 j + c with (a, b, c) = (0, 1, 3) for order 0 (yuyv), (1, 0, 2) for 1 (uyvy), (0, 3, 1) for 2 (yvyu), (1, 2, 0) for 3 (vyuy): chroma comes
+ * from the pixel's own pair (nearest).  `container` says where component i lies:
+ *   0   byte i of the row; depth 8 (YUY2 / YUYV, UYVY, YVYU, VYUY);
+ *   1   little-endian 16-bit word i, the sample (word >> lsb) & ((1 << depth) - 1); depth 10 or 12, lsb = 16 - depth (Y210 / Y212: bits at the top, the
+ *       low bits dropped whatever they hold) or 0 (bits at the bottom, the high bits masked); pointer, pitch and frame stride even;
+ *   2   v210: bits [10 (i % 3), 10 (i % 3) + 10) of little-endian 32-bit word i / 3 (bits 30, 31 are ignored); depth 10, order uyvy only, lsb 0;
+ *       pointer, pitch and frame stride multiples of 4.  A 16-byte group of four words therefore holds, lowest bits first,
+ *           Cb0 Y0 Cr0 | Y1 Cb1 Y2 | Cr1 Y3 Cb2 | Y4 Cr2 Y5
+ *       -- six pixels.  (This layout is the definition here; nothing has been compared with ffmpeg or a capture card.)
+ * A row of P = x0 + ws columns holds row_bytes = 4 ceil(P / 2) (bytes), 8 ceil(P / 2) (words) or 16 ceil(P / 6) (v210): the last pair or group must
+ * be whole in memory, since its chroma is read.  From the three `depth`-bit samples on -- the matrix and its bounds, the clamp, lut of 1 << depth
+ * entries, pads, destinations -- the call is ppms_video_ingest_yuv with sub_x = 1, sub_y = 0 on the planar surface that holds the same samples.
+ *   Packed raw.  ppms_raw_format without sample_bytes and lsb; depth 10 or 12.  Sample s(y, p) of a row of bytes:
+ *   packing 0 (MIPI CSI-2; V4L2 *10P, *12P):  RAW10: g = p >> 2, k = p & 3, s = row[5 g + k] << 2 | (row[5 g + 4] >> 2 k) & 3;
+ *                                             RAW12: g = p >> 1, k = p & 1, s = row[3 g + k] << 4 | (row[3 g + 2] >> 4 k) & 15;
+ *   packing 1 (GenICam PFNC 10p / 12p, an lsb-first bit stream):  bit = p * depth, o = bit >> 3,
+ *                                             s = ((row[o] | row[o + 1] << 8) >> (bit & 7)) & ((1 << depth) - 1)
+ * (both bytes hold bits of the pixel itself: the last pixel of a row reads nothing behind the row).  row_bytes = 5 ceil(P / 4), 3 ceil(P / 2) or
+ * ceil(P depth / 8).  From s on -- reflected neighbours, bilinear demosaic or mono, black level and gains, the caller's table, pads, destinations --
+ * the call is ppms_video_ingest_raw on the unpacked 16-bit, lsb-aligned frames.  (Nothing has been compared with a sensor or a GenICam producer.)
+ *   _remap.  The remap contract above on these levels, as for the unpacked calls; every load address comes from a coordinate clamped or reflected
+ * into the frame, and with the pitch check below no load leaves [row, row + row_bytes).
+ *   Refused with PPMS_EINVAL before any launch: a null pointer; non-zero reserved; container, order, packing or depth out of range or not going
+ * together (v210 with anything but depth 10 and uyvy; container 0 with anything but depth 8); lsb not 0 or 16 - depth (and not 0 outside container
+ * 1); x0 < 0, x0 odd for YUV, x0 + ws > 65536; an odd pointer or stride with container 1, one that is no multiple of 4 with v210; pitch <
+ * row_bytes(x0 + ws); with N > 1 a frame_stride < (hs - 1) * pitch + row_bytes; a colour pattern on a frame smaller than 2 x 2; shift in [8, 26 -
+ * depth], y_off and the coefficients as ppms_video_ingest_yuv bounds them; pattern, black, shift and gains as ppms_video_ingest_raw bounds them;
+ * what ppms_video_ingest_u8 refuses about sizes, pads and destinations; for _remap, whatever the _remap calls above refuse.
+ * Not covered: Y216 and other 16-bit depths, 14-bit packed raw, 4:4:4 packed (v410, Y410, AYUV), big-endian containers, packed RGB, interpolated
+ * chroma siting, patterns or layouts that differ between the two views. */
+typedef struct ppms_packed_view {     /* one view's frames inside a packed surface */
+    const uint8_t* data;              /* column 0 of row 0 of frame 0 of the SURFACE */
+    int64_t frame_stride;             /* bytes from frame n to frame n + 1 */
+    int32_t pitch;                    /* bytes from row to row */
+    int32_t x0;                       /* surface column of the view's column 0 */
+} ppms_packed_view;
+typedef struct ppms_yuv_packed_format {
+    int32_t container;                /* 0 bytes, 1 little-endian 16-bit words, 2 v210 */
+    int32_t depth;                    /* 8 with container 0; 10 or 12 with 1; 10 with 2 */
+    int32_t lsb;                      /* container 1: 0 or 16 - depth (Y210, Y212); 0 otherwise */
+    int32_t order;                    /* 0 yuyv, 1 uyvy, 2 yvyu, 3 vyuy */
+    int32_t reserved[4];              /* 0 */
+} ppms_yuv_packed_format;
+typedef struct ppms_raw_packed_format {
+    int32_t packing;                  /* 0 MIPI CSI-2, 1 PFNC lsb-first */
+    int32_t depth;                    /* 10 or 12 */
+    int32_t pattern;                  /* 0 RGGB, 1 BGGR, 2 GRBG, 3 GBRG, 4 MONO */
+    int32_t black;                    /* black level, [0, 2^depth) */
+    int32_t gain[3];                  /* white balance for R, G, B times 2^shift, [0, 16 << shift) */
+    int32_t shift;                    /* [4, 14] */
+    int32_t reserved[4];              /* 0 */
+} ppms_raw_packed_format;
+int ppms_video_ingest_yuv_packed(const ppms_packed_view* left, const ppms_packed_view* right, const ppms_yuv_matrix* m, const ppms_yuv_packed_format* fmt,
+                                 int N, int H0, int W0, int pad_left, int pad_top, int H, int W,
+                                 const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream);
+int ppms_video_ingest_yuv_packed_remap(const ppms_packed_view* left, const ppms_packed_view* right, const ppms_yuv_matrix* m, const ppms_yuv_packed_format* fmt,
+                                       const ppms_remap_view* lmap, const ppms_remap_view* rmap,
+                                       int N, int H0, int W0, int pad_left, int pad_top, int H, int W,
+                                       const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream);
+int ppms_video_ingest_raw_packed(const ppms_packed_view* left, const ppms_packed_view* right, const ppms_raw_packed_format* fmt,
+                                 int N, int H0, int W0, int pad_left, int pad_top, int H, int W,
+                                 const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream);
+int ppms_video_ingest_raw_packed_remap(const ppms_packed_view* left, const ppms_packed_view* right, const ppms_raw_packed_format* fmt,
+                                       const ppms_remap_view* lmap, const ppms_remap_view* rmap,
+                                       int N, int H0, int W0, int pad_left, int pad_top, int H, int W,
+                                       const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream);
+int ppms_packed_struct_sizes(int* view, int* yuv_format, int* raw_format);   /* sizeof of the three structs above (24, 32, 48): lets a binding verify its layout */
 /* nn.InstanceNorm2d(affine=False) (extractor.py:326-329, 364): per (sample, channel) mean and 1 / sqrt(biased var + eps) over the
  * HW pixels of x (channel-last fp32 [N * HW][ld], a convolution's fp32 output) -> stats[N][C][2] (pixel slices merged in fixed
  * order: deterministic; caller-owned 16-B aligned workspace of ppms_instnorm_workspace_bytes); then

@@ -87,6 +87,22 @@ class RawFormat(C.Structure):
                                                                                                   ("reserved", C.c_int32 * 3)]
 
 
+class PackedView(C.Structure):
+    """ppms_packed_view: one view's frames inside a packed surface (device pointer, byte strides, the surface column of the view's column 0)."""
+    _fields_ = [("data", c_void_p), ("frame_stride", c_int64), ("pitch", C.c_int32), ("x0", C.c_int32)]
+
+
+class YUVPackedFormat(C.Structure):
+    """ppms_yuv_packed_format: how ppms_video_ingest_yuv_packed reads a row's components (container, depth, alignment in the word, order)."""
+    _fields_ = [(n, C.c_int32) for n in ("container", "depth", "lsb", "order")] + [("reserved", C.c_int32 * 4)]
+
+
+class RawPackedFormat(C.Structure):
+    """ppms_raw_packed_format: how ppms_video_ingest_raw_packed reads a row's samples (packing, depth, mosaic, black level, white balance)."""
+    _fields_ = [(n, C.c_int32) for n in ("packing", "depth", "pattern", "black")] + [("gain", C.c_int32 * 3), ("shift", C.c_int32),
+                                                                                    ("reserved", C.c_int32 * 4)]
+
+
 class RemapView(C.Structure):
     """ppms_remap_view: one view's fixed-point rectification map (device pointers, pitch in map pixels, the source frame size)."""
     _fields_ = [("xy", c_void_p), ("frac", c_void_p), ("pitch", C.c_int32), ("hs", C.c_int32), ("ws", C.c_int32),
@@ -172,6 +188,16 @@ _SIGS = {
     "ppms_video_ingest_raw_remap": (c_int, [C.POINTER(RawView), C.POINTER(RawView), C.POINTER(RawFormat), C.POINTER(RemapView), C.POINTER(RemapView),
                                             c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, SP, SP, c_void_p]),
     "ppms_raw_struct_sizes": (c_int, [C.POINTER(c_int), C.POINTER(c_int)]),
+    "ppms_video_ingest_yuv_packed": (c_int, [C.POINTER(PackedView), C.POINTER(PackedView), C.POINTER(YUVMatrix), C.POINTER(YUVPackedFormat), c_int, c_int,
+                                             c_int, c_int, c_int, c_int, c_int, c_void_p, SP, SP, c_void_p]),
+    "ppms_video_ingest_yuv_packed_remap": (c_int, [C.POINTER(PackedView), C.POINTER(PackedView), C.POINTER(YUVMatrix), C.POINTER(YUVPackedFormat),
+                                                   C.POINTER(RemapView), C.POINTER(RemapView), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, SP,
+                                                   SP, c_void_p]),
+    "ppms_video_ingest_raw_packed": (c_int, [C.POINTER(PackedView), C.POINTER(PackedView), C.POINTER(RawPackedFormat), c_int, c_int, c_int, c_int, c_int,
+                                             c_int, c_int, c_void_p, SP, SP, c_void_p]),
+    "ppms_video_ingest_raw_packed_remap": (c_int, [C.POINTER(PackedView), C.POINTER(PackedView), C.POINTER(RawPackedFormat), C.POINTER(RemapView),
+                                                   C.POINTER(RemapView), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, SP, SP, c_void_p]),
+    "ppms_packed_struct_sizes": (c_int, [C.POINTER(c_int), C.POINTER(c_int), C.POINTER(c_int)]),
     "ppms_dwconv": (c_int, [SP, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ppms_layernorm_any": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_float, SP, c_int64, c_int, c_void_p]),
     "ppms_grn_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
@@ -241,6 +267,9 @@ def load() -> C.CDLL:
     lib.ppms_raw_struct_sizes(C.byref(a), C.byref(b))
     if (a.value, b.value) != (C.sizeof(RawView), C.sizeof(RawFormat)):
         raise RuntimeError("ppmstereo_amd: ctypes layout of ppms_raw_view / ppms_raw_format differs from include/ppms.h")
+    lib.ppms_packed_struct_sizes(C.byref(a), C.byref(b), C.byref(c))
+    if (a.value, b.value, c.value) != (C.sizeof(PackedView), C.sizeof(YUVPackedFormat), C.sizeof(RawPackedFormat)):
+        raise RuntimeError("ppmstereo_amd: ctypes layout of ppms_packed_view / ppms_yuv_packed_format / ppms_raw_packed_format differs from include/ppms.h")
     if lib.ppms_egress_struct_size() != C.sizeof(Egress):
         raise RuntimeError("ppmstereo_amd: ctypes layout of ppms_egress differs from include/ppms.h")
     if lib.ppms_pwchain_param_bytes() != C.sizeof(ChainParams):

@@ -4,7 +4,8 @@
 
 namespace {
 
-// decoded video -> the first-layer operands of both encoders in one launch (ppms_video_ingest_u8 / ppms_video_ingest_yuv420 / ppms_video_ingest_yuv / ppms_video_ingest_raw):
+// decoded video -> the first-layer operands of both encoders in one launch (ppms_video_ingest_u8 / ppms_video_ingest_yuv420 / ppms_video_ingest_yuv / ppms_video_ingest_raw
+// and the packed doors ppms_video_ingest_yuv_packed / ppms_video_ingest_raw_packed):
 // what normalisation (a table the caller built with the float path's own torch expression: 256 entries, or 1 << depth for a source whose
 // table_by_depth is true, which also answers levels()), replicate padding (clamped source
 // coordinate), torch.cat([left, right]) and the two img_s2d launches produce from the fp32 images.  Thread = one output pixel x 8 channels
@@ -70,6 +71,66 @@ struct yuv_source {
     }
 };
 
+// packed 4:2:2 (ppms_video_ingest_yuv_packed): one pitched surface per view whose rows are streams of components.  Column x of the view is
+// surface column p = x + x0 (x0 even: the host refuses a split chroma pair), its pair j = p >> 1, and with `order` yuyv | uyvy | yvyu | vyuy the
+// components are Y = 2 p + a, U = 4 j + b, V = 4 j + c for (a, b, c) = (0, 1, 3), (1, 0, 2), (0, 3, 1), (1, 2, 0): a = order & 1,
+// b = 1 - a + (order & 2), c = 3 - order.  Container says where component i lies: 0 byte i, 1 little-endian 16-bit word i, (word >> lsb) masked to
+// `depth` bits, 2 (v210) bits [10 (i % 3), 10 (i % 3) + 10) of 32-bit word i / 3.  Loads are of one container element (the host checks the
+// alignment of pointers and strides for 16- and 32-bit elements).  (y, x) arrives clamped into the hs x ws frame, so p <= P - 1 with P = x0 + ws,
+// and the largest component index is that of the last pair, 4 ceil(P / 2) - 1: inside the 4 ceil(P / 2) bytes, 8 ceil(P / 2) bytes or -- 12 components
+// to 16 bytes -- 16 ceil(P / 6) bytes the host demands of the pitch.  No load leaves [row, row + row_bytes).  From the three samples on it is yuv_source's
+// conversion, restated (a helper shared with yuv_source changed the schedule of its four kernels; they keep their code).
+template <int Container>
+struct yuv_packed_source {
+    ppms_packed_view left, right;
+    ppms_yuv_matrix mat;
+    int N, depth, lsb, order;                                             // uniform: the ppms_yuv_packed_format
+    static constexpr bool table_by_depth = true;
+    __host__ __device__ int levels() const { return 1 << depth; }
+    __device__ int component(const uint8_t* row, int i) const {
+        if constexpr (Container == 0) return row[i];
+        if constexpr (Container == 1) return ((int)((const uint16_t*)row)[i] >> lsb) & ((1 << depth) - 1);
+        if constexpr (Container == 2) return (int)(((const uint32_t*)row)[i / 3] >> (10 * (i % 3))) & 1023;
+    }
+    __device__ int operator()(int64_t m, int c, int y, int x) const {
+        const bool r = m >= N;
+        const uint8_t* row = (r ? right.data : left.data) + (r ? m - N : m) * (r ? right.frame_stride : left.frame_stride) + (int64_t)y * (r ? right.pitch : left.pitch);
+        const int p = x + (r ? right.x0 : left.x0), pair = (p >> 1) * 4, a = order & 1;
+        // the three channels of a pixel repeat these loads; they are the same addresses, and the compiler merges them
+        const int mid = 1 << (depth - 1), top = (1 << depth) - 1;          // from here on: yuv_source's conversion, statement for statement
+        const int d = component(row, 2 * p + a) - mat.y_off, e = component(row, pair + 1 - a + (order & 2)) - mid, f = component(row, pair + 3 - order) - mid;
+        const int acc = mat.cy * d + (c == 0 ? mat.crv * f : c == 1 ? -mat.cgu * e - mat.cgv * f : mat.cbu * e) + (1 << (mat.shift - 1));
+        const int q = acc >> mat.shift;                                   // arithmetic shift: floor
+        return q < 0 ? 0 : (q > top ? top : q);
+    }
+};
+
+// channel c of pixel (y, x) of a raw source `f` (its hs, ws, depth, pattern, black, gains and shift) whose sample at a frame coordinate is s(yy, xx):
+// the demosaic, black level and white balance of the raw sources, unpacked and packed.  With (y, x) inside the hs x ws frame and hs, ws >= 2 (the
+// host refuses less for a colour pattern) every coordinate handed to s lies inside the frame.
+template <class Source, class Sample>
+__device__ __forceinline__ int raw_level(const Source& f, int c, int y, int x, Sample s) {
+    const int hs = f.hs, ws = f.ws, pattern = f.pattern;
+    int v;
+    if (pattern == 4) {                                                   // MONO
+        v = s(y, x);
+    } else {
+        const int ym = y > 0 ? y - 1 : 1, yp = y < hs - 1 ? y + 1 : hs - 2, xm = x > 0 ? x - 1 : 1, xp = x < ws - 1 ? x + 1 : ws - 2;
+        const bool green = ((x ^ y ^ (pattern >> 1)) & 1) != 0, red_row = ((y ^ pattern) & 1) == 0;
+        if (c == (green ? 1 : (red_row ? 0 : 2)))
+            v = s(y, x);
+        else if (green)                                                   // R or B at a green site: the two neighbours that carry it
+            v = (c == 0) == red_row ? (s(y, xm) + s(y, xp) + 1) >> 1 : (s(ym, x) + s(yp, x) + 1) >> 1;
+        else if (c == 1)                                                  // G at a red or blue site
+            v = (s(ym, x) + s(yp, x) + s(y, xm) + s(y, xp) + 2) >> 2;
+        else                                                              // B at a red site, R at a blue site
+            v = (s(ym, xm) + s(ym, xp) + s(yp, xm) + s(yp, xp) + 2) >> 2;
+    }
+    const int top = (1 << f.depth) - 1;
+    const int q = ((v - f.black) * (c == 0 ? f.gain_r : c == 1 ? f.gain_g : f.gain_b) + (1 << (f.shift - 1))) >> f.shift;     // arithmetic shift: floor
+    return q < 0 ? 0 : (q > top ? top : q);
+}
+
 // a sensor's raw frames (ppms_video_ingest_raw): one pitched plane of T samples under a 2 x 2 colour-filter mosaic, or monochrome.  The missing
 // colours of a pixel are bilinear means of its neighbours (the arithmetic: include/ppms.h); a neighbour outside the frame is REFLECTED without
 // repeating the edge (-1 -> 1, n -> n - 2), which keeps its colour.  `pattern` is uniform, and which colour a site carries is parity arithmetic:
@@ -88,24 +149,47 @@ struct raw_source {
         const int64_t pitch = r ? right.pitch : left.pitch;
         const int top = (1 << depth) - 1;
         // the three channels of a pixel repeat these loads; they are the same addresses, and the compiler merges them
-        const auto s = [&](int yy, int xx) { return ((int)*(const T*)(p + yy * pitch + (int64_t)xx * (int)sizeof(T)) >> lsb) & top; };
-        int v;
-        if (pattern == 4) {                                               // MONO
-            v = s(y, x);
-        } else {
-            const int ym = y > 0 ? y - 1 : 1, yp = y < hs - 1 ? y + 1 : hs - 2, xm = x > 0 ? x - 1 : 1, xp = x < ws - 1 ? x + 1 : ws - 2;
-            const bool green = ((x ^ y ^ (pattern >> 1)) & 1) != 0, red_row = ((y ^ pattern) & 1) == 0;
-            if (c == (green ? 1 : (red_row ? 0 : 2)))
-                v = s(y, x);
-            else if (green)                                               // R or B at a green site: the two neighbours that carry it
-                v = (c == 0) == red_row ? (s(y, xm) + s(y, xp) + 1) >> 1 : (s(ym, x) + s(yp, x) + 1) >> 1;
-            else if (c == 1)                                              // G at a red or blue site
-                v = (s(ym, x) + s(yp, x) + s(y, xm) + s(y, xp) + 2) >> 2;
-            else                                                          // B at a red site, R at a blue site
-                v = (s(ym, xm) + s(ym, xp) + s(yp, xm) + s(yp, xp) + 2) >> 2;
-        }
-        const int q = ((v - black) * (c == 0 ? gain_r : c == 1 ? gain_g : gain_b) + (1 << (shift - 1))) >> shift;     // arithmetic shift: floor
-        return q < 0 ? 0 : (q > top ? top : q);
+        return raw_level(*this, c, y, x, [&](int yy, int xx) { return ((int)*(const T*)(p + yy * pitch + (int64_t)xx * (int)sizeof(T)) >> lsb) & top; });
+    }
+};
+
+// the same frames in a packed transport format (ppms_video_ingest_raw_packed): 10- or 12-bit samples without padding bits, one pitched surface per
+// view.  Column xx of the view is surface column q = xx + x0 (any x0 >= 0: the pattern is that of the view's own pixel (0, 0)).
+//   Packing 0 (MIPI CSI-2): RAW10 keeps the top 8 bits of pixels 4 g .. 4 g + 3 in bytes 5 g .. 5 g + 3 and their low 2 bits in byte 5 g + 4, pixel
+// k's at bits [2 k, 2 k + 2); RAW12 the top 8 bits of pixels 2 g, 2 g + 1 in bytes 3 g, 3 g + 1 and their low 4 bits in the nibbles of byte 3 g + 2.
+//   Packing 1 (PFNC 10p / 12p): an lsb-first bit stream, pixel q at bits [q depth, q depth + depth): with depth in {10, 12} that is (bit & 7) in
+// {0, 2, 4, 6} or {0, 4}, so the pixel lies in exactly the two bytes o, o + 1 of o = bit >> 3, and both hold bits of the pixel itself.
+// Byte loads only.  raw_level hands over coordinates inside the hs x ws frame, so q <= P - 1 with P = x0 + ws: the last byte read is that of the
+// last group, 5 ceil(P / 4) - 1 or 3 ceil(P / 2) - 1, or the last byte of pixel P - 1, ceil(P depth / 8) - 1 -- inside the row_bytes the host demands
+// of the pitch.  No load leaves [row, row + row_bytes).
+template <int Packing>
+struct raw_packed_source {
+    ppms_packed_view left, right;
+    int N, hs, ws;                                                        // frames per view, the SOURCE frame size
+    int depth, pattern, black, gain_r, gain_g, gain_b, shift;             // uniform: the ppms_raw_packed_format
+    static constexpr bool table_by_depth = true;
+    __host__ __device__ int levels() const { return 1 << depth; }
+    __device__ int operator()(int64_t m, int c, int y, int x) const {
+        const bool r = m >= N;
+        const uint8_t* p = (r ? right.data : left.data) + (r ? m - N : m) * (r ? right.frame_stride : left.frame_stride);
+        const int64_t pitch = r ? right.pitch : left.pitch;
+        const int x0 = r ? right.x0 : left.x0;
+        // the three channels of a pixel repeat these loads; they are the same addresses, and the compiler merges them
+        return raw_level(*this, c, y, x, [&](int yy, int xx) {
+            const uint8_t* row = p + yy * pitch;
+            const int q = xx + x0;
+            if constexpr (Packing == 0) {
+                if (depth == 10) {
+                    const int g = (q >> 2) * 5, k = q & 3;
+                    return (int)row[g + k] << 2 | (((int)row[g + 4] >> (2 * k)) & 3);
+                }
+                const int g = (q >> 1) * 3, k = q & 1;
+                return (int)row[g + k] << 4 | (((int)row[g + 2] >> (4 * k)) & 15);
+            } else {
+                const int bit = q * depth, o = bit >> 3;
+                return (((int)row[o] | (int)row[o + 1] << 8) >> (bit & 7)) & ((1 << depth) - 1);
+            }
+        });
     }
 };
 
@@ -193,7 +277,7 @@ __global__ __launch_bounds__(256) void video_ingest_kernel(Source source, int N,
 
 // ---- host side: every entry point fills one ingest_call, runs its door's checks and goes through ingest_samples() to the one launch ----------
 
-// what all 8 entry points take behind their source: the entry's name for the messages, geometry, table, destinations and stream
+// what all 12 entry points take behind their source: the entry's name for the messages, geometry, table, destinations and stream
 struct ingest_call {
     const char* who;
     int N, H0, W0, pad_left, pad_top, H, W;
@@ -377,24 +461,30 @@ struct remap_maps {
     const ppms_remap_view *left, *right;
 };
 
-// the way of all 8 entry points: the maps' check (with them the source frames are the maps' hs x ws, not H0 x W0), the door's own `check(hs, ws,
-// hname, wname)` of its views against those frames, then the launch of `make(T{}, hs, ws)` -- the door's source reading samples of T from frames of
-// hs x ws -- behind the maps if there are any.  `fill` of a map is a level of the format's depth (a format that names no depth is refused by
-// `check`, right behind the maps, which bound hs and ws for it)
-template <class Check, class Make>
-static int ingest_samples(const ingest_call& a, const sample_format& f, const remap_maps* maps, Check check, Make make) {
+// the way of all 12 entry points: the maps' check (with them the source frames are the maps' hs x ws, not H0 x W0), the door's own `check(hs, ws,
+// hname, wname)` of its views against those frames, then `pick(launch, hs, ws)`, which hands the door's source for frames of hs x ws to `launch` --
+// the one launch, behind the maps if there are any.  `fill` of a map is a level of the format's `depth` (a format that names no depth is refused
+// by `check`, right behind the maps, which bound hs and ws for it)
+template <class Check, class Pick>
+static int ingest_frames(const ingest_call& a, int depth, const remap_maps* maps, Check check, Pick pick) {
     int hs = a.H0, ws = a.W0;
     if (maps) {
-        if (const int rc = remap_check(a.who, maps->left, maps->right, a.W0, f.depth == 10 || f.depth == 12 ? (1 << f.depth) - 1 : 255)) return rc;
+        if (const int rc = remap_check(a.who, maps->left, maps->right, a.W0, depth == 10 || depth == 12 ? (1 << depth) - 1 : 255)) return rc;
         hs = maps->left->hs, ws = maps->left->ws;
     }
     if (const int rc = check(hs, ws, maps ? "hs" : "H0", maps ? "ws" : "W0")) return rc;
-    const auto launch = [&](auto sample) {
-        auto inner = make(sample, hs, ws);
+    const auto launch = [&](auto inner) {
         if (!maps) return video_ingest_launch(a, inner);
         return video_ingest_launch(a, remapped_source<decltype(inner)>{inner, *maps->left, *maps->right, a.N});
     };
-    return f.sample_bytes == 1 ? launch(uint8_t{}) : launch(uint16_t{});
+    return pick(launch, hs, ws);
+}
+
+// the unpacked doors: `make(T{}, hs, ws)` is the door's source reading samples of T
+template <class Check, class Make>
+static int ingest_samples(const ingest_call& a, const sample_format& f, const remap_maps* maps, Check check, Make make) {
+    return ingest_frames(a, f.depth, maps, check,
+                         [&](auto launch, int hs, int ws) { return f.sample_bytes == 1 ? launch(make(uint8_t{}, hs, ws)) : launch(make(uint16_t{}, hs, ws)); });
 }
 
 static int ingest_u8(const ingest_call& a, const uint8_t* left, const uint8_t* right, int64_t frame_stride, const remap_maps* maps) {
@@ -439,6 +529,106 @@ static int ingest_raw(const ingest_call& a, const ppms_raw_view* left, const ppm
         });
 }
 
+// what the four packed entry points check about one view's surface: x0 (even where `pair` says that a chroma pair may not be split), `align`-byte
+// pointers and strides (`unit` names the container that needs them), a pitch that holds the row of P = x0 + W0 columns, and with N > 1 a frame
+// stride that holds a frame.  `row_bytes(P)`: the format's row of P columns
+template <class RowBytes>
+static int packed_view_check(const ingest_call& a, const char* side, const ppms_packed_view& v, bool pair, int align, const char* unit, int H0, int W0,
+                             const char* wname, RowBytes row_bytes) {
+    const char* who = a.who;
+    PPMS_REQUIRE(v.data, "%s: null data pointer in the %s view", who, side);
+    PPMS_REQUIRE(v.x0 >= 0, "%s: %s x0 = %d must not be negative", who, side, v.x0);
+    PPMS_REQUIRE(!pair || v.x0 % 2 == 0, "%s: %s x0 = %d must be even: a chroma pair may not be split", who, side, v.x0);
+    PPMS_REQUIRE((int64_t)v.x0 + W0 <= 65536, "%s: %s x0 + %s = %d + %d exceeds 65536 columns", who, side, wname, v.x0, W0);
+    PPMS_REQUIRE((((uintptr_t)v.data | (uintptr_t)v.frame_stride | (uintptr_t)v.pitch) & (uintptr_t)(align - 1)) == 0,
+                 "%s: %s view: a misaligned pointer or stride; %s need pointers, pitches and frame strides that are multiples of %d", who, side, unit, align);
+    const int64_t row = row_bytes(v.x0 + W0);
+    PPMS_REQUIRE(v.pitch >= row, "%s: %s pitch = %d is less than a row's %lld bytes (x0 + %s = %d)", who, side, v.pitch, (long long)row, wname, v.x0 + W0);
+    PPMS_REQUIRE(a.N == 1 || v.frame_stride >= (int64_t)(H0 - 1) * v.pitch + row, "%s: %s frame_stride = %lld is less than a frame", who, side,
+                 (long long)v.frame_stride);
+    return PPMS_OK;
+}
+
+// what both ppms_video_ingest_yuv_packed entry points check about the format, the views (frames of H0 x W0, named `hname` x `wname` in the messages)
+// and the matrix (ppms_video_ingest_yuv's bounds, restated)
+static int yuv_packed_check(const ingest_call& a, const ppms_packed_view* left, const ppms_packed_view* right, const ppms_yuv_matrix* m,
+                            const ppms_yuv_packed_format* fmt, int H0, int W0, const char* hname, const char* wname) {
+    const char* who = a.who;
+    PPMS_REQUIRE(left && right && m && fmt && a.lut, "%s: null view, matrix, format or table pointer", who);
+    PPMS_REQUIRE(a.N > 0 && H0 > 0 && W0 > 0, "%s: N = %d, %s = %d, %s = %d must be positive", who, a.N, hname, H0, wname, W0);
+    const ppms_yuv_packed_format& f = *fmt;
+    PPMS_REQUIRE(f.container >= 0 && f.container <= 2, "%s: container = %d must be 0 (bytes), 1 (16-bit words) or 2 (v210)", who, f.container);
+    PPMS_REQUIRE(f.order >= 0 && f.order <= 3, "%s: order = %d must be 0 (yuyv), 1 (uyvy), 2 (yvyu) or 3 (vyuy)", who, f.order);
+    PPMS_REQUIRE(f.container == 0 ? f.depth == 8 : f.container == 1 ? (f.depth == 10 || f.depth == 12) : f.depth == 10,
+                 "%s: depth = %d does not go with container = %d (8 with 0; 10 or 12 with 1; 10 with 2)", who, f.depth, f.container);
+    PPMS_REQUIRE(f.container != 2 || f.order == 1, "%s: order = %d does not go with container = 2: v210 is uyvy (1)", who, f.order);
+    PPMS_REQUIRE(f.lsb == 0 || (f.container == 1 && f.lsb == 16 - f.depth), "%s: lsb = %d must be 0, or 16 - depth for 16-bit words", who, f.lsb);
+    PPMS_REQUIRE(f.reserved[0] == 0 && f.reserved[1] == 0 && f.reserved[2] == 0 && f.reserved[3] == 0, "%s: format: reserved must be 0", who);
+    const int align = f.container == 0 ? 1 : f.container == 1 ? 2 : 4;
+    const char* unit = f.container == 1 ? "16-bit words" : "v210's 32-bit words";
+    const auto row_bytes = [&](int P) { return f.container == 2 ? (int64_t)16 * ((P + 5) / 6) : (int64_t)4 * align * ((P + 1) / 2); };
+    if (const int rc = packed_view_check(a, "left", *left, true, align, unit, H0, W0, wname, row_bytes)) return rc;
+    if (const int rc = packed_view_check(a, "right", *right, true, align, unit, H0, W0, wname, row_bytes)) return rc;
+    PPMS_REQUIRE(m->shift >= 8 && m->shift <= 26 - f.depth, "%s: shift = %d must lie in [8, %d] at depth %d", who, m->shift, 26 - f.depth, f.depth);
+    PPMS_REQUIRE(m->reserved == 0, "%s: matrix: reserved = %d must be 0", who, m->reserved);
+    const int32_t lim = 4 << m->shift;                                     // (yuv_check's bound: no sum of the conversion leaves 32 bits)
+    PPMS_REQUIRE(m->y_off >= 0 && m->y_off < (1 << f.depth) && m->cy >= 0 && m->cy < lim && m->crv >= 0 && m->crv < lim && m->cgu >= 0 && m->cgu < lim &&
+                     m->cgv >= 0 && m->cgv < lim && m->cbu >= 0 && m->cbu < lim,
+                 "%s: y_off must lie in [0, %d] and every coefficient in [0, 4 << shift)", who, (1 << f.depth) - 1);
+    return PPMS_OK;
+}
+
+// what both ppms_video_ingest_raw_packed entry points check about the format (ppms_video_ingest_raw's bounds, restated) and the views
+static int raw_packed_check(const ingest_call& a, const ppms_packed_view* left, const ppms_packed_view* right, const ppms_raw_packed_format* fmt, int H0,
+                            int W0, const char* hname, const char* wname) {
+    const char* who = a.who;
+    PPMS_REQUIRE(left && right && fmt && a.lut, "%s: null view, format or table pointer", who);
+    PPMS_REQUIRE(a.N > 0 && H0 > 0 && W0 > 0, "%s: N = %d, %s = %d, %s = %d must be positive", who, a.N, hname, H0, wname, W0);
+    const ppms_raw_packed_format& f = *fmt;
+    PPMS_REQUIRE(f.packing == 0 || f.packing == 1, "%s: packing = %d must be 0 (MIPI CSI-2) or 1 (PFNC, lsb first)", who, f.packing);
+    PPMS_REQUIRE(f.depth == 10 || f.depth == 12, "%s: depth = %d must be 10 or 12", who, f.depth);
+    PPMS_REQUIRE(f.pattern >= 0 && f.pattern <= 4, "%s: pattern = %d must be 0 (RGGB), 1 (BGGR), 2 (GRBG), 3 (GBRG) or 4 (MONO)", who, f.pattern);
+    PPMS_REQUIRE(f.black >= 0 && f.black < (1 << f.depth), "%s: black = %d must lie in [0, %d]", who, f.black, (1 << f.depth) - 1);
+    PPMS_REQUIRE(f.shift >= 4 && f.shift <= 14, "%s: shift = %d must lie in [4, 14]", who, f.shift);
+    const int32_t lim = 16 << f.shift;                                     // (raw_check's bound: no sum leaves 32 bits)
+    PPMS_REQUIRE(f.gain[0] >= 0 && f.gain[0] < lim && f.gain[1] >= 0 && f.gain[1] < lim && f.gain[2] >= 0 && f.gain[2] < lim,
+                 "%s: every gain must lie in [0, 16 << shift)", who);
+    PPMS_REQUIRE(f.reserved[0] == 0 && f.reserved[1] == 0 && f.reserved[2] == 0 && f.reserved[3] == 0, "%s: format: reserved must be 0", who);
+    PPMS_REQUIRE(f.pattern == 4 || (H0 >= 2 && W0 >= 2), "%s: a colour pattern needs a frame of at least 2 x 2, got %s = %d, %s = %d", who, hname, H0, wname, W0);
+    const auto row_bytes = [&](int P) {
+        return f.packing == 1 ? ((int64_t)P * f.depth + 7) / 8 : f.depth == 10 ? (int64_t)5 * ((P + 3) / 4) : (int64_t)3 * ((P + 1) / 2);
+    };
+    if (const int rc = packed_view_check(a, "left", *left, false, 1, "", H0, W0, wname, row_bytes)) return rc;
+    return packed_view_check(a, "right", *right, false, 1, "", H0, W0, wname, row_bytes);
+}
+
+// (a null format reads as depth 8 here and is refused by the door's own check)
+static int ingest_yuv_packed(const ingest_call& a, const ppms_packed_view* left, const ppms_packed_view* right, const ppms_yuv_matrix* m,
+                             const ppms_yuv_packed_format* f, const remap_maps* maps) {
+    return ingest_frames(
+        a, f ? f->depth : 8, maps,
+        [&](int hs, int ws, const char* hname, const char* wname) { return yuv_packed_check(a, left, right, m, f, hs, ws, hname, wname); },
+        [&](auto launch, int, int) {
+            const auto source = [&](auto container) { return yuv_packed_source<decltype(container)::value>{*left, *right, *m, a.N, f->depth, f->lsb, f->order}; };
+            if (f->container == 0) return launch(source(std::integral_constant<int, 0>{}));
+            if (f->container == 1) return launch(source(std::integral_constant<int, 1>{}));
+            return launch(source(std::integral_constant<int, 2>{}));
+        });
+}
+
+static int ingest_raw_packed(const ingest_call& a, const ppms_packed_view* left, const ppms_packed_view* right, const ppms_raw_packed_format* f,
+                             const remap_maps* maps) {
+    return ingest_frames(
+        a, f ? f->depth : 8, maps,
+        [&](int hs, int ws, const char* hname, const char* wname) { return raw_packed_check(a, left, right, f, hs, ws, hname, wname); },
+        [&](auto launch, int hs, int ws) {
+            const auto source = [&](auto packing) {
+                return raw_packed_source<decltype(packing)::value>{*left, *right, a.N, hs, ws, f->depth, f->pattern, f->black, f->gain[0], f->gain[1], f->gain[2], f->shift};
+            };
+            return f->packing == 0 ? launch(source(std::integral_constant<int, 0>{})) : launch(source(std::integral_constant<int, 1>{}));
+        });
+}
+
 // the trailing arguments every entry point declares, and the ingest_call they fill
 #define INGEST_TAIL int N, int H0, int W0, int pad_left, int pad_top, int H, int W, const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream
 #define INGEST_CALL(name) ingest_call{name, N, H0, W0, pad_left, pad_top, H, W, lut, dst_fnet, dst_cnet, stream}
@@ -479,6 +669,31 @@ extern "C" int ppms_video_ingest_raw_remap(const ppms_raw_view* left, const ppms
     return ingest_raw(INGEST_CALL("video_ingest_raw_remap"), left, right, fmt, &maps);
 }
 
+extern "C" int ppms_video_ingest_yuv_packed(const ppms_packed_view* left, const ppms_packed_view* right, const ppms_yuv_matrix* m,
+                                            const ppms_yuv_packed_format* fmt, INGEST_TAIL) {
+    return ingest_yuv_packed(INGEST_CALL("video_ingest_yuv_packed"), left, right, m, fmt, nullptr);
+}
+extern "C" int ppms_video_ingest_yuv_packed_remap(const ppms_packed_view* left, const ppms_packed_view* right, const ppms_yuv_matrix* m,
+                                                  const ppms_yuv_packed_format* fmt, const ppms_remap_view* lmap, const ppms_remap_view* rmap, INGEST_TAIL) {
+    const remap_maps maps{lmap, rmap};
+    return ingest_yuv_packed(INGEST_CALL("video_ingest_yuv_packed_remap"), left, right, m, fmt, &maps);
+}
+
+extern "C" int ppms_video_ingest_raw_packed(const ppms_packed_view* left, const ppms_packed_view* right, const ppms_raw_packed_format* fmt, INGEST_TAIL) {
+    return ingest_raw_packed(INGEST_CALL("video_ingest_raw_packed"), left, right, fmt, nullptr);
+}
+extern "C" int ppms_video_ingest_raw_packed_remap(const ppms_packed_view* left, const ppms_packed_view* right, const ppms_raw_packed_format* fmt,
+                                                  const ppms_remap_view* lmap, const ppms_remap_view* rmap, INGEST_TAIL) {
+    const remap_maps maps{lmap, rmap};
+    return ingest_raw_packed(INGEST_CALL("video_ingest_raw_packed_remap"), left, right, fmt, &maps);
+}
+
+extern "C" int ppms_packed_struct_sizes(int* view, int* yuv_format, int* raw_format) {
+    if (view) *view = (int)sizeof(ppms_packed_view);
+    if (yuv_format) *yuv_format = (int)sizeof(ppms_yuv_packed_format);
+    if (raw_format) *raw_format = (int)sizeof(ppms_raw_packed_format);
+    return PPMS_OK;
+}
 extern "C" int ppms_yuv_struct_sizes(int* view, int* matrix) {
     if (view) *view = (int)sizeof(ppms_yuv_view);
     if (matrix) *matrix = (int)sizeof(ppms_yuv_matrix);

@@ -21,6 +21,7 @@ from .engine import bilinear
 from .update import Attention_qk, SequenceUpdateBlock3D
 from .video import (InputPadder, OutputSpec, RawFrames, RawStereoVideo, RectifyMap, StereoRectifier, YUVFrames, YUVStereoVideo, byte_lut,  # noqa: F401  (the public names are
                     egress_plan, level_lut, shard_windows, window_plan, yuv_matrix)                                                    #  importable from here as before)
+from .video import PackedRawFrames, PackedRawStereoVideo, PackedYUVFrames, PackedYUVStereoVideo  # noqa: F401
 from .video import _ByteSource, _EgressCall, stereo_source
 
 
@@ -560,6 +561,8 @@ class PPMStereo(PPMStereoHotPath):
           frame count): the bits of ``forward`` on their ``to_float()`` (8-bit frames: on their ``to_rgb_u8()``); or
           two ``RawFrames`` on the device (a sensor's Bayer-mosaic or monochrome frames of 8, 10 or 12 bits; b = 1, T = their frame count): the bits
           of ``forward`` on their ``to_float()``; or
+          two ``PackedYUVFrames`` or two ``PackedRawFrames`` on the device (YUYV / UYVY / Y210 / v210 ...; MIPI RAW10 / RAW12 or PFNC 10p / 12p
+          rows, e.g. the ``split_side_by_side()`` halves of one surface; b = 1, T = their frame count): the bits of ``forward`` on their ``unpack()``; or
           with rectify (a ``StereoRectifier``) the RAW frames of an unrectified rig, uint8 device tensors (1, T, 3, Hs, Ws) or ``YUVFrames`` of its
           source size Hs x Ws: the bits of ``forward`` on ``RectifyMap.apply_u8`` of each view's RGB bytes (deep frames: ``apply_levels`` of their levels).  H, W above are then the rectified size,
           and so are the outputs'.  Float images raise TypeError (the remap reads decoded bytes), b > 1 NotImplementedError, another frame size
@@ -684,7 +687,10 @@ class PPMStereo(PPMStereoHotPath):
         a ``YUVStereoVideo`` (decoded frames, host or device) is copied per window as its planes -- 8-bit 4:2:0 (NV12, I420): 1.5 bytes per
         pixel and view, 8-bit 4:2:2: 2, 8-bit 4:4:4 and P010: 3 -- and gives the bits of the float video of its ``to_float()`` frames (8-bit: of
         the uint8 video of ``to_rgb_u8()``); a ``RawStereoVideo`` (a sensor's raw frames, host or device) as its samples -- 1 byte per pixel and
-        view, 2 for 10- and 12-bit words -- and gives the bits of the float video of its ``to_float()`` frames.  Not covered: interpolated chroma siting, 16-bit depth, packed formats (YUYV / Y210 / v210), BT.2020
+        view, 2 for 10- and 12-bit words -- and gives the bits of the float video of its ``to_float()`` frames; a ``PackedYUVStereoVideo`` or
+        ``PackedRawStereoVideo`` (packed rows as the camera or capture card left them, host or device) as the packed bytes of each view's own
+        columns -- YUYV 2 per pixel and view, v210 2.67, RAW10p 1.25, RAW12p 1.5 -- and gives the bits of the call on its views' ``unpack()``.
+        Not covered: interpolated chroma siting, 16-bit depth, 4:4:4 packed and packed RGB, BT.2020
         and HDR transfer functions, high-depth RGB, b > 1.  With this package's encoders the bytes are converted, padded and normalised inside the one ingest launch;
         windows of ``kernel_size`` frames every ``kernel_size // 2``, centre frames kept (:296-307).  Windows whose output the
         reference computes and then drops are not run.  Returns {"disparity", "uncertainties"}: (N, 1, H, W) CPU tensors.

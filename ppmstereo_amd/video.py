@@ -1,5 +1,6 @@
 """Video in and out of the model: what ``PPMStereo.forward`` / ``forward_batch_test`` accept beside the reference's float tensors (uint8 and decoded
-YUV frames of 8, 10 or 12 bits with 4:2:0 / 4:2:2 / 4:4:4 chroma, a sensor's Bayer-mosaic or monochrome frames, unrectified frames with a ``StereoRectifier``), the one private family of sources that stands for all of them behind the front doors
+YUV frames of 8, 10 or 12 bits with 4:2:0 / 4:2:2 / 4:4:4 chroma, a sensor's Bayer-mosaic or monochrome frames, both in the packed formats cameras put
+on the wire (YUYV, Y210, v210, RAW10p / RAW12p), unrectified frames with a ``StereoRectifier``), the one private family of sources that stands for all of them behind the front doors
 (``stereo_source``), the output planes they can hand back (``OutputSpec``) and the sliding-window schedule.  Nothing here knows the model."""
 from __future__ import annotations
 
@@ -79,7 +80,7 @@ def byte_lut(device) -> torch.Tensor:
 
 
 class _Frames:
-    """What ``YUVFrames`` and ``RawFrames`` share: N frames of one view, sliced by frame range only and moved as a whole.  A subclass has ``n``,
+    """What ``YUVFrames``, ``RawFrames`` and the packed frames share: N frames of one view, sliced by frame range only and moved as a whole.  A subclass has ``n``,
     ``_tensors()`` (its planes; the first names the device), ``_like(*planes)`` and ``_moved(device)``."""
 
     def __len__(self) -> int:
@@ -103,7 +104,7 @@ class _Frames:
 
 
 class _StereoVideo:
-    """What ``YUVStereoVideo`` and ``RawStereoVideo`` share: two frame objects of class ``_views`` with one size, frame count and device (a fault
+    """What ``YUVStereoVideo``, ``RawStereoVideo`` and their packed twins share: two frame objects of class ``_views`` with one size, frame count and device (a fault
     there is reported as "both views need ``_one``") and one format -- ``_format_fault(left, right)``: what differs, or None.  ``len()``, slicing
     by frame range, ``to(device)``."""
     _views: type
@@ -167,8 +168,8 @@ class YUVFrames(_Frames):
     last-dimension stride 1 (planar: I420 / yuv420p) or 2 (interleaved: NV12); anything else raises ValueError.  Strides are read in elements
     and kept in BYTES (``pitch_y`` ..., what ``ppms_yuv_view`` holds).  Luma pixel (y, x) takes chroma sample (y >> sub_y, x >> sub_x), nearest;
     ``standard`` ("bt709" / "bt601") and ``full_range`` choose ``yuv_matrix``; ``to_rgb`` is the definition of the RGB levels (``to_rgb_u8``: of the
-    bytes at depth 8).  Not covered: interpolated chroma siting, 16-bit depth, packed formats (YUYV / Y210 / v210), BT.2020 and HDR transfer
-    functions, b > 1."""
+    bytes at depth 8).  Packed 4:2:2 (YUYV / Y210 / v210): ``PackedYUVFrames``.  Not covered: interpolated chroma siting, 16-bit depth, BT.2020
+    and HDR transfer functions, b > 1."""
 
     def __init__(self, y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, standard: str = "bt709", full_range: bool = False, depth: int = 8,
                  align: str = "msb", chroma: str = "420"):
@@ -355,8 +356,8 @@ class RawFrames(_Frames):
     ``gains`` the white balance for (R, G, B), quantised with ``round(g * 1024)``; ``to_rgb`` is the definition of the RGB levels (bilinear
     demosaic with reflected borders, include/ppms.h).  ``tone``: None -- a level stands for ``level * 255 / (2^depth - 1)`` -- or a float tensor of
     2^depth values in [0, 255], the value each level stands for: where the gamma / sRGB encoding of linear sensor data goes, at no cost (the
-    kernel looks every level up in a table anyway).  Not covered: packed 10p / 12p transport formats, 14- and 16-bit sensors, demosaicing
-    better than bilinear, colour-correction matrices, lens shading and defect pixels, per-view differing patterns, b > 1."""
+    kernel looks every level up in a table anyway).  Packed 10p / 12p transport formats: ``PackedRawFrames``.  Not covered: 14- and 16-bit sensors,
+    demosaicing better than bilinear, colour-correction matrices, lens shading and defect pixels, per-view differing patterns, b > 1."""
 
     def __init__(self, data: torch.Tensor, pattern: str = "rggb", depth: int = 8, align: str = "lsb", black: int = 0, gains=(1.0, 1.0, 1.0),
                  tone: Optional[torch.Tensor] = None, _shared: Optional[dict] = None):
@@ -517,6 +518,300 @@ class RawStereoVideo(_StereoVideo):
             return None
         return ("the views differ in pattern, depth, alignment, black level, gains or tone curve: "
                 f"{(left.pattern, left.depth, left.align, left.black, left.gains)} and {(right.pattern, right.depth, right.align, right.black, right.gains)}")
+
+
+class _PackedFrames(_Frames):
+    """What ``PackedYUVFrames`` and ``PackedRawFrames`` share: ``data`` (N, H0, row elements) is the driver's own buffer -- a pitched SURFACE whose
+    rows hold whole groups of ``_group`` = (pixels, elements) -- and the view is its columns [x0, x0 + width): nothing is copied, and the two halves
+    of a side-by-side frame are one surface with two ``x0``.  A subclass has ``_name``, ``_group``, ``_align`` (bytes: what pointer and strides must
+    be multiples of), ``_row_elements(P)`` (the elements of a row of P columns) and ``_with(data, x0, width)``."""
+
+    def _surface(self, data: torch.Tensor, width, x0, dtype, pair: bool) -> None:
+        name = self._name
+        if not torch.is_tensor(data) or data.dtype != dtype or data.dim() != 3:
+            raise ValueError(f"{name}: data must be a {str(dtype).replace('torch.', '')} tensor (N, rows, row elements)")
+        if not (isinstance(width, int) and isinstance(x0, int) and width >= 1 and x0 >= 0 and x0 + width <= 65536):
+            raise ValueError(f"{name}: width = {width!r}, x0 = {x0!r} must be integers with width >= 1, x0 >= 0 and x0 + width <= 65536")
+        if pair and x0 % 2:
+            raise ValueError(f"{name}: x0 = {x0} must be even: a chroma pair may not be split")
+        n, h0, row = data.shape
+        need = self._row_elements(x0 + width)
+        if n < 1 or h0 < 1:
+            raise ValueError(f"{name}: empty surface {tuple(data.shape)}")
+        if row < need:
+            raise ValueError(f"{name}: rows of {row} elements do not hold columns [{x0}, {x0 + width}): {need} are needed")
+        if row > 1 and data.stride(2) != 1:
+            raise ValueError(f"{name}: data has last-dimension stride {data.stride(2)}; a row's elements must be adjacent")
+        es = data.element_size()
+        # a size-1 dimension's stride is arbitrary: the smallest the kernel accepts stands in for it (elements here, bytes below)
+        pitch = data.stride(1) if h0 > 1 else need
+        frame = data.stride(0) if n > 1 else (h0 - 1) * pitch + need
+        if pitch < need or frame < (h0 - 1) * pitch + need:
+            raise ValueError(f"{name}: rows or frames overlap (strides {data.stride()})")
+        if data.data_ptr() % self._align or (pitch * es) % self._align or (frame * es) % self._align:
+            raise ValueError(f"{name}: the surface's address, pitch and frame stride must be multiples of {self._align} bytes")
+        self.data, self.x0, self.n, self.height, self.width = data, x0, n, h0, width
+        self.pitch, self.frame_stride = pitch * es, frame * es
+
+    def _tensors(self):
+        return (self.data,)
+
+    def _like(self, data):
+        return self._with(data, self.x0, self.width)
+
+    def view_struct(self) -> L.PackedView:
+        """The ``ppms_packed_view`` of these frames."""
+        return L.PackedView(self.data.data_ptr(), self.frame_stride, self.pitch, self.x0)
+
+    def _half(self, what: str, size: int, even_half: bool, views: str) -> int:
+        if size % 2 or (even_half and (size // 2) % 2):
+            raise ValueError(f"{self._name}.{what}: a packed {'width' if what == 'split_side_by_side' else 'height'} of {size} does not split into two {views}")
+        return size // 2
+
+    def _moved(self, device):
+        """``to``: the packed bytes of the view's own groups are copied -- from the group that holds column x0 to the end of the row of column
+        x0 + width - 1 -- into a dense surface; ``x0`` becomes the column inside that first group."""
+        pixels, elements = self._group
+        g = self.x0 // pixels
+        return self._with(self.data[:, :, g * elements:self._row_elements(self.x0 + self.width)].to(device), self.x0 - g * pixels, self.width)
+
+    def to_rgb(self) -> torch.Tensor:
+        """``unpack().to_rgb()``: (N, 3, H0, W0) RGB levels, uint8 at depth 8 and int16 otherwise."""
+        return self.unpack().to_rgb()
+
+    def to_float(self) -> torch.Tensor:
+        """``unpack().to_float()``: float32 (N, 3, H0, W0) in [0, 255] -- the video the reference would be given."""
+        return self.unpack().to_float()
+
+
+_PACKED_YUV = {"yuyv": (0, 8, 0), "uyvy": (0, 8, 1), "yvyu": (0, 8, 2), "vyuy": (0, 8, 3),      # layout: (container, depth, order) of
+               "y210": (1, 10, 0), "y212": (1, 12, 0), "v210": (2, 10, 1)}                      # ppms_yuv_packed_format
+
+
+def _packed_yuv_row(container: int, p: int) -> int:
+    """The elements (bytes; 16-bit words for container 1) of a packed 4:2:2 row of p columns: whole pairs, for v210 whole groups of 6 pixels."""
+    return 16 * (-(-p // 6)) if container == 2 else 4 * (-(-p // 2))
+
+
+def _packed_yuv_indices(order: int, x0: int, width: int, device):
+    """The component indices of surface columns [x0, x0 + width) (x0 even): Y per pixel, U and V per pair (include/ppms.h)."""
+    a = order & 1
+    p = torch.arange(x0, x0 + width, device=device)
+    j = torch.arange(x0 // 2, (x0 + width + 1) // 2, device=device)
+    return 2 * p + a, 4 * j + (1 - a + (order & 2)), 4 * j + (3 - order)
+
+
+class PackedYUVFrames(_PackedFrames):
+    """One view's N frames of packed 4:2:2 YUV, as a UVC camera or a capture card leaves them: ``data`` (N, H0, row elements) over the driver's own
+    buffer, ``width`` pixels wide.  ``layout`` "yuyv" (YUY2) / "uyvy" / "yvyu" / "vyuy": uint8, 4 bytes per pixel pair in that order; "y210" /
+    "y212": ``torch.uint16`` words in yuyv order holding 10 / 12 bits at the top (``align="msb"``, the default: Y210 / Y212; the low bits are
+    dropped whatever they hold) or at the bottom (``align="lsb"``); "v210": uint8, 6 pixels in 16 bytes -- three 10-bit components per
+    little-endian 32-bit word, Cb0 Y0 Cr0 | Y1 Cb1 Y2 | Cr1 Y3 Cb2 | Y4 Cr2 Y5 (include/ppms.h is the definition; not compared with ffmpeg); its
+    address, pitch and frame stride are multiples of 4.  A row holds whole pairs (v210: whole groups).  ``data`` may be a strided view; the class
+    reads ``data_ptr()`` and ``stride()`` and never copies.  ``unpack`` is the definition of the samples, ``to_rgb`` / ``to_float`` those of the
+    planar frames it returns (chroma from the pixel's own pair, nearest).  Not covered: Y216 and other 16-bit depths, 4:4:4 packed (v410, Y410,
+    AYUV), big-endian containers, packed RGB, interpolated chroma siting, b > 1."""
+    _name = "PackedYUVFrames"
+
+    def __init__(self, data: torch.Tensor, width: int, layout: str = "yuyv", align: str = "msb", standard: str = "bt709", full_range: bool = False,
+                 x0: int = 0):
+        if layout not in _PACKED_YUV:
+            raise ValueError(f"PackedYUVFrames: layout {layout!r}; one of {sorted(_PACKED_YUV)}")
+        if align not in ("msb", "lsb"):
+            raise ValueError(f"PackedYUVFrames: align {align!r}; 'msb' or 'lsb'")
+        self.container, self.depth, self.order = _PACKED_YUV[layout]
+        self._align = (1, 2, 4)[self.container]
+        self._group = (6, 16) if self.container == 2 else (2, 4)
+        self._surface(data, width, x0, torch.uint16 if self.container == 1 else torch.uint8, True)
+        yuv_matrix(standard)                                               # (refuses an unknown standard here)
+        self.layout, self.align, self.standard, self.full_range = layout, align, standard, bool(full_range)
+        self.lsb = 16 - self.depth if (self.container == 1 and align == "msb") else 0
+
+    def _row_elements(self, p: int) -> int:
+        return _packed_yuv_row(self.container, p)
+
+    def _with(self, data, x0, width) -> "PackedYUVFrames":
+        return PackedYUVFrames(data, width, self.layout, self.align, self.standard, self.full_range, x0)
+
+    def split_side_by_side(self):
+        """(left, right): the two halves of frames that pack both views side by side -- the same surface with two ``x0``.  The packed width and
+        each half must be even, or the right half would start inside a chroma pair."""
+        h = self._half("split_side_by_side", self.width, True, "views with whole chroma pairs")
+        return self._with(self.data, self.x0, h), self._with(self.data, self.x0 + h, h)
+
+    def split_top_bottom(self):
+        """(left, right) = (top, bottom) halves of frames that pack both views one above the other; views, no copy."""
+        h = self._half("split_top_bottom", self.height, False, "views")
+        return self._like(self.data[:, :h]), self._like(self.data[:, h:])
+
+    def matrix(self) -> L.YUVMatrix:
+        return yuv_matrix(self.standard, self.full_range, depth=self.depth)
+
+    def format_struct(self) -> L.YUVPackedFormat:
+        """The ``ppms_yuv_packed_format`` of these frames."""
+        return L.YUVPackedFormat(self.container, self.depth, self.lsb, self.order, (0, 0, 0, 0))
+
+    def unpack(self) -> YUVFrames:
+        """The ``YUVFrames.planar(..., chroma="422")`` holding the same samples (uint8, or uint16 with the bits at the bottom), in torch integer
+        ops: the definition of the format on this side, and the path of encoder callables of the caller."""
+        if self.container == 2:
+            b = self.data.to(torch.int64).unflatten(2, (-1, 4))
+            words = b[..., 0] | b[..., 1] << 8 | b[..., 2] << 16 | b[..., 3] << 24
+            component = lambda i: (words[:, :, i // 3] >> (10 * (i % 3))) & 1023
+        else:
+            component = lambda i: (self.data[:, :, i].to(torch.int32) >> self.lsb) & ((1 << self.depth) - 1)
+        indices = _packed_yuv_indices(self.order, self.x0, self.width, self.device)
+        y, u, v = (component(i).to(torch.uint8 if self.depth == 8 else torch.uint16) for i in indices)
+        return YUVFrames.planar(y, u, v, self.depth, "422", "lsb", self.standard, self.full_range)
+
+    @classmethod
+    def pack(cls, frames: YUVFrames, layout: str = "yuyv", align: str = "msb") -> "PackedYUVFrames":
+        """The inverse of ``unpack`` for simulators: 4:2:2 ``YUVFrames`` of the layout's depth -> dense packed rows (unused bits, and the second
+        luma of an odd width's last pair, are 0)."""
+        if not isinstance(frames, YUVFrames) or layout not in _PACKED_YUV or frames.chroma != "422" or frames.depth != _PACKED_YUV[layout][1]:
+            raise ValueError(f"PackedYUVFrames.pack: 4:2:2 YUVFrames of the depth of layout {layout!r} (one of {sorted(_PACKED_YUV)}) expected")
+        container, _, order = _PACKED_YUV[layout]
+        top = (1 << frames.depth) - 1
+        count = _packed_yuv_row(container, frames.width) * (3 if container == 2 else 4) // 4                  # components of a row (v210: 12 in 16 bytes)
+        comp = torch.zeros((frames.n, frames.height, count), dtype=torch.int64, device=frames.device)
+        for i, plane in zip(_packed_yuv_indices(order, 0, frames.width, frames.device), (frames.y, frames.u, frames.v)):
+            comp[:, :, i] = (plane.to(torch.int64) >> frames.lsb) & top
+        if container == 2:
+            t = comp.unflatten(2, (-1, 3))
+            words = t[..., 0] | t[..., 1] << 10 | t[..., 2] << 20
+            data = torch.stack([(words >> s) & 255 for s in (0, 8, 16, 24)], dim=-1).flatten(2).to(torch.uint8)
+        elif container == 1:
+            data = (comp << (16 - frames.depth if align == "msb" else 0)).to(torch.int32).to(torch.uint16)
+        else:
+            data = comp.to(torch.uint8)
+        return cls(data, frames.width, layout, align, frames.standard, frames.full_range)
+
+    def to_rgb_u8(self) -> torch.Tensor:
+        """``to_rgb`` of 8-bit layouts: uint8 (N, 3, H0, W0).  Deep layouts have no RGB bytes (ValueError)."""
+        return self.unpack().to_rgb_u8()
+
+
+class PackedYUVStereoVideo(_StereoVideo):
+    """Both views of a packed 4:2:2 video -- what ``batch_dict["stereo_video"]`` of ``forward_batch_test`` may be instead of a tensor: two
+    ``PackedYUVFrames`` of one size, frame count, device, colour description, layout and alignment.  ``len()``, slicing by frame range,
+    ``to(device)`` (the packed bytes: YUYV 2 per pixel and view, v210 2.67, Y210 4)."""
+    _views, _one = PackedYUVFrames, "one standard, one range and one device"
+
+    def _format_fault(self, left: PackedYUVFrames, right: PackedYUVFrames) -> Optional[str]:
+        if (left.standard, left.full_range) != (right.standard, right.full_range):
+            return f"both views need {self._one}"
+        if (left.layout, left.lsb) != (right.layout, right.lsb):
+            return f"the views differ in layout or alignment: {(left.layout, left.align)} and {(right.layout, right.align)}"
+        return None
+
+
+_RAW_PACKINGS = {"mipi": 0, "pfnc": 1}                                             # ppms_raw_packed_format.packing
+
+
+class PackedRawFrames(_PackedFrames):
+    """One view's N raw sensor frames in a packed transport format: ``data`` uint8 (N, H0, row bytes) over the driver's own buffer, ``width``
+    pixels wide, ``depth`` 10 or 12 bits without padding.  ``packing="mipi"``: MIPI CSI-2 RAW10 / RAW12 as V4L2's SRGGB10P / SRGGB12P ... leave
+    them -- the top 8 bits of 4 (2) pixels in 4 (2) bytes, their low bits together in a fifth (third); ``packing="pfnc"``: GenICam PFNC
+    Mono10p / BayerRG12p ... -- an lsb-first bit stream, pixel p at bits [p depth, p depth + depth) of the row.  A row holds whole groups (pfnc:
+    whole bytes).  ``pattern``, ``black``, ``gains`` and ``tone`` are ``RawFrames``'; ``x0`` may be any column, and the pattern is that of the
+    view's own pixel (0, 0).  ``unpack`` is the definition of the samples, ``to_rgb`` / ``to_float`` those of the ``RawFrames`` it returns.  Not
+    covered: 14-bit packed depths, packings whose rows are padded inside, patterns that differ between the views, b > 1."""
+    _name, _align = "PackedRawFrames", 1
+
+    def __init__(self, data: torch.Tensor, width: int, pattern: str = "rggb", depth: int = 10, packing: str = "mipi", black: int = 0,
+                 gains=(1.0, 1.0, 1.0), tone: Optional[torch.Tensor] = None, x0: int = 0, _proto: Optional[RawFrames] = None):
+        if depth not in (10, 12):
+            raise ValueError(f"PackedRawFrames: depth = {depth!r}; 10 or 12")
+        if packing not in _RAW_PACKINGS:
+            raise ValueError(f"PackedRawFrames: packing {packing!r}; one of {sorted(_RAW_PACKINGS)}")
+        self.depth, self.packing = depth, packing
+        self._group = (4, 5) if depth == 10 else (2, 3)
+        self._surface(data, width, x0, torch.uint8, False)
+        # pattern, black level, gains and tone curve are checked and kept by a RawFrames of the same format, shared by every slice, half and copy
+        self._proto = RawFrames(torch.zeros((1, 2, 2), dtype=torch.uint16), pattern, depth, "lsb", black, gains, tone) if _proto is None else _proto
+        if self._proto.pattern != "mono" and (self.height < 2 or width < 2):
+            raise ValueError(f"PackedRawFrames: a colour pattern needs frames of at least 2 x 2, got {self.height} x {width}")
+        self.pattern, self.black, self.gains, self.gain_q, self.tone = (getattr(self._proto, k) for k in ("pattern", "black", "gains", "gain_q", "tone"))
+
+    def _row_elements(self, p: int) -> int:
+        return -(-p * self.depth // 8) if self.packing == "pfnc" else 5 * (-(-p // 4)) if self.depth == 10 else 3 * (-(-p // 2))
+
+    def _with(self, data, x0, width) -> "PackedRawFrames":
+        return PackedRawFrames(data, width, depth=self.depth, packing=self.packing, x0=x0, _proto=self._proto)
+
+    def split_side_by_side(self):
+        """(left, right): the two halves of frames that pack both views side by side -- the same surface with two ``x0``.  The packed width must
+        be even, and with a colour pattern each half's too (``RawFrames.split_side_by_side``)."""
+        h = self._half("split_side_by_side", self.width, self.pattern != "mono", f"views of one {self.pattern} pattern")
+        return self._with(self.data, self.x0, h), self._with(self.data, self.x0 + h, h)
+
+    def split_top_bottom(self):
+        """(left, right) = (top, bottom) halves of frames that pack both views one above the other; views, no copy (even halves, as above)."""
+        h = self._half("split_top_bottom", self.height, self.pattern != "mono", f"views of one {self.pattern} pattern")
+        return self._like(self.data[:, :h]), self._like(self.data[:, h:])
+
+    def same_format(self, other: "PackedRawFrames") -> bool:
+        """Both hold one packing of one depth, under one pattern, with one black level, white balance and tone curve."""
+        return self.packing == other.packing and self._proto.same_format(other._proto)
+
+    def format_struct(self) -> L.RawPackedFormat:
+        """The ``ppms_raw_packed_format`` of these frames."""
+        return L.RawPackedFormat(_RAW_PACKINGS[self.packing], self.depth, _RAW_PATTERNS[self.pattern], self.black, self.gain_q, _RAW_SHIFT, (0, 0, 0, 0))
+
+    def unpack(self) -> RawFrames:
+        """The ``RawFrames`` holding the same samples (uint16, bits at the bottom), in torch integer ops: the definition of the format on this
+        side, and the path of encoder callables of the caller."""
+        row = self.data.to(torch.int32)
+        p = torch.arange(self.x0, self.x0 + self.width, device=self.device)
+        if self.packing == "pfnc":
+            bit = p * self.depth
+            s = ((row[:, :, bit >> 3] | row[:, :, (bit >> 3) + 1] << 8) >> (bit & 7)) & ((1 << self.depth) - 1)
+        elif self.depth == 10:
+            s = row[:, :, 5 * (p >> 2) + (p & 3)] << 2 | (row[:, :, 5 * (p >> 2) + 4] >> (2 * (p & 3))) & 3
+        else:
+            s = row[:, :, 3 * (p >> 1) + (p & 1)] << 4 | (row[:, :, 3 * (p >> 1) + 2] >> (4 * (p & 1))) & 15
+        return self._proto._like(s.to(torch.uint16))
+
+    @classmethod
+    def pack(cls, frames: RawFrames, packing: str = "mipi") -> "PackedRawFrames":
+        """The inverse of ``unpack`` for simulators: 10- or 12-bit ``RawFrames`` -> dense packed rows (the bits of a last group behind the last
+        pixel are 0)."""
+        if not isinstance(frames, RawFrames) or frames.depth not in (10, 12) or packing not in _RAW_PACKINGS:
+            raise ValueError("PackedRawFrames.pack: RawFrames of depth 10 or 12 and packing 'mipi' or 'pfnc' expected")
+        depth, (pixels, elements) = frames.depth, ((4, 5) if frames.depth == 10 else (2, 3))
+        s = (frames.data.to(torch.int64) >> frames.lsb) & ((1 << depth) - 1)
+        s = torch.nn.functional.pad(s, (0, -frames.width % pixels)).unflatten(2, (-1, pixels))                  # whole groups
+        if packing == "pfnc":                                              # a group is one little-endian number of pixels * depth bits
+            number = sum(s[..., k] << (depth * k) for k in range(pixels))
+            data = torch.stack([(number >> (8 * i)) & 255 for i in range(elements)], dim=-1).flatten(2)[:, :, :-(-frames.width * depth // 8)]
+        else:
+            low = sum((s[..., k] & ((1 << (depth - 8)) - 1)) << ((depth - 8) * k) for k in range(pixels))
+            data = torch.cat([s >> (depth - 8), low[..., None]], dim=-1).flatten(2)
+        proto = RawFrames(torch.zeros((1, 2, 2), dtype=torch.uint16), frames.pattern, depth, "lsb", frames.black, frames.gains, frames.tone)
+        return cls(data.to(torch.uint8), frames.width, depth=depth, packing=packing, _proto=proto)
+
+    def tone_on(self, device) -> Optional[torch.Tensor]:
+        return self._proto.tone_on(device)
+
+    def levels_to_float(self, levels: torch.Tensor) -> torch.Tensor:
+        return self._proto.levels_to_float(levels)
+
+    def table(self, device) -> torch.Tensor:
+        """``RawFrames.table``: the frames' own level table on ``device``, built once and shared by every slice, half and copy."""
+        return self._proto.table(device)
+
+
+class PackedRawStereoVideo(_StereoVideo):
+    """Both views of a packed raw sensor video -- what ``batch_dict["stereo_video"]`` of ``forward_batch_test`` may be instead of a tensor: two
+    ``PackedRawFrames`` of one size, frame count, device, packing, depth, pattern, black level, white balance and tone curve.  ``len()``, slicing
+    by frame range, ``to(device)`` (the packed bytes: 1.25 per pixel and view at depth 10, 1.5 at depth 12)."""
+    _views = PackedRawFrames
+
+    def _format_fault(self, left: PackedRawFrames, right: PackedRawFrames) -> Optional[str]:
+        if left.same_format(right):
+            return None
+        return ("the views differ in packing, depth, pattern, black level, gains or tone curve: "
+                f"{(left.packing, left.depth, left.pattern, left.black, left.gains)} and {(right.packing, right.depth, right.pattern, right.black, right.gains)}")
 
 
 _BORDERS = {"replicate": L.BORDER_REPLICATE, "constant": L.BORDER_CONSTANT}
@@ -802,6 +1097,52 @@ class _RawPlanes(_ByteSource):
         return v.left.levels_to_float(left), v.right.levels_to_float(right)    # (the tone curve behind the blend, as in the kernel)
 
 
+class _PackedYUVPlanes(_ByteSource):
+    """A PackedYUVStereoVideo: ppms_video_ingest_yuv_packed fetches the three samples of a pixel out of the packed rows as the camera or capture
+    card left them; from there on it is ppms_video_ingest_yuv."""
+
+    def __init__(self, video: PackedYUVStereoVideo, rectify: Optional[StereoRectifier] = None):
+        super().__init__("ppms_video_ingest_yuv_packed", len(video), (video.height, video.width), video.left.device, rectify, depth=video.depth)
+        self.video = video
+
+    def _frames(self):
+        v = self.video
+        return v.left.view_struct(), v.right.view_struct(), v.left.matrix(), v.left.format_struct()       # host structs: read before the call returns
+
+    def _planes(self):
+        return self.video.left.data, self.video.right.data
+
+    def float_views(self):
+        rgb = self.video.left.to_rgb(), self.video.right.to_rgb()
+        left, right = rgb if self.rectify is None else self.rectify.apply_levels(*rgb, self.depth)
+        return _levels_to_float(left, self.depth), _levels_to_float(right, self.depth)
+
+
+class _PackedRawPlanes(_ByteSource):
+    """A PackedRawStereoVideo: ppms_video_ingest_raw_packed fetches every sample out of the packed rows as the camera driver left them; from there
+    on it is ppms_video_ingest_raw, with the frames' own level table."""
+
+    def __init__(self, video: PackedRawStereoVideo, rectify: Optional[StereoRectifier] = None):
+        super().__init__("ppms_video_ingest_raw_packed", len(video), (video.height, video.width), video.left.device, rectify, depth=video.depth)
+        self.video = video
+
+    def _frames(self):
+        v = self.video
+        return v.left.view_struct(), v.right.view_struct(), v.left.format_struct()      # host structs: read before the call returns
+
+    def _planes(self):
+        return self.video.left.data, self.video.right.data
+
+    def _table(self) -> torch.Tensor:
+        return self.video.left.table(self.device)
+
+    def float_views(self):
+        v = self.video
+        rgb = v.left.to_rgb(), v.right.to_rgb()
+        left, right = rgb if self.rectify is None else self.rectify.apply_levels(*rgb, self.depth)
+        return v.left.levels_to_float(left), v.right.levels_to_float(right)    # (the tone curve behind the blend, as in the kernel)
+
+
 def _checked_rectifier(who: str, rectify, device, h: int, w: int) -> StereoRectifier:
     """``rectify`` for raw frames h x w on ``device`` (host frames are only measured: the maps stay where they are)."""
     rectify.check_source(who, h, w)
@@ -809,14 +1150,17 @@ def _checked_rectifier(who: str, rectify, device, h: int, w: int) -> StereoRecti
 
 
 def stereo_source(who: str, left, right=None, rectify: Optional[StereoRectifier] = None):
-    """The source of two views -- float or uint8 tensors (b, T, 3, H, W), two ``YUVFrames`` or two ``RawFrames`` -- or, with ``right`` None, of a
-    window ``left`` of a video: a tensor (T, 2, 3, H, W), a ``YUVStereoVideo`` or a ``RawStereoVideo``.  Every argument check of the front doors is
+    """The source of two views -- float or uint8 tensors (b, T, 3, H, W), two ``YUVFrames``, ``RawFrames``, ``PackedYUVFrames`` or
+    ``PackedRawFrames`` -- or, with ``right`` None, of a window ``left`` of a video: a tensor (T, 2, 3, H, W), a ``YUVStereoVideo``, a
+    ``RawStereoVideo``, a ``PackedYUVStereoVideo`` or a ``PackedRawStereoVideo``.  Every argument check of the front doors is
     made here, under the name ``who``, and touches no device: rectify= reads decoded bytes (TypeError for float frames), of its source size
-    (ValueError), b = 1; two ``YUVFrames`` that differ in depth, alignment or chroma subsampling, or two ``RawFrames`` that differ in pattern,
-    sample format, black level, gains or tone curve, are no stereo pair (ValueError)."""
+    (ValueError), b = 1; two ``YUVFrames`` that differ in depth, alignment or chroma subsampling, two ``RawFrames`` that differ in pattern,
+    sample format, black level, gains or tone curve, or two packed views that differ in layout, packing, depth or any of those, are no stereo pair
+    (ValueError); two views of different classes are none either (TypeError)."""
     if rectify is not None and not isinstance(rectify, StereoRectifier):
         raise TypeError(f"{who}: rectify must be a StereoRectifier, got {type(rectify).__name__}")
-    for frames, video, source in ((YUVFrames, YUVStereoVideo, _YUVPlanes), (RawFrames, RawStereoVideo, _RawPlanes)):
+    for frames, video, source in ((YUVFrames, YUVStereoVideo, _YUVPlanes), (RawFrames, RawStereoVideo, _RawPlanes),
+                                  (PackedYUVFrames, PackedYUVStereoVideo, _PackedYUVPlanes), (PackedRawFrames, PackedRawStereoVideo, _PackedRawPlanes)):
         if isinstance(left, frames) or isinstance(right, frames):
             if not (isinstance(left, frames) and isinstance(right, frames)):
                 raise TypeError(f"{who}: image1 is {type(left).__name__} and image2 is {type(right).__name__}; both views must be {frames.__name__} or both tensors")

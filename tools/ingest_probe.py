@@ -5,6 +5,7 @@
     python tools/ingest_probe.py --door remap [--yuv] [--runs 12]                                       > profiles/rNN_ingest_remap_ab.txt
     python tools/ingest_probe.py --door deep  [--depth 10] [--chroma 420] [--align msb] [--runs 12]     > profiles/rNN_ingest_deep_ab.txt
     python tools/ingest_probe.py --door raw   [--depth 10] [--pattern rggb] [--align lsb] [--runs 12]   > profiles/rNN_ingest_raw_ab.txt
+    python tools/ingest_probe.py --door packed [--layout yuyv | ... | v210 | mipi | pfnc] [--depth 10]  > profiles/rNN_ingest_packed_ab.txt
     python tools/ingest_probe.py --kernels --parent DIR [--runs 7]                                      > profiles/rNN_ingest_kernels_ab.txt
 
 --door: PPMStereo.forward_batch_test on one video through two ways in.  Side B is the door itself; side A is what a caller did before the door
@@ -96,6 +97,32 @@ def raw_video(a, torch, P, Wm, dev, h, w):
     return P.RawStereoVideo(view(0), view(1)), {}
 
 
+YUV_LAYOUTS = {"yuyv": 8, "uyvy": 8, "yvyu": 8, "vyuy": 8, "y210": 10, "y212": 12, "v210": 10}            # layout: depth
+RAW_PACKINGS = ("mipi", "pfnc")                                  # (--depth 10 | 12, --pattern)
+
+
+def packed_video(a, torch, P, Wm, dev, h, w):
+    """The frames of --door deep (4:2:2) or --door raw, packed on the host with the classes' own pack() and moved to the device as packed bytes."""
+    if a.layout in RAW_PACKINGS:
+        depth = a.depth if a.depth in (10, 12) else 10
+        top = (1 << depth) - 1
+        samples = Wm.hash_uniform((T, 2, h, w), 618, 0.0, float(top)).round().to(torch.int32)
+        view = lambda s: P.PackedRawFrames.pack(P.RawFrames(samples[:, s].to(torch.uint16).contiguous(), a.pattern, depth, "lsb", black=top // 16,
+                                                            gains=(1.8, 1.0, 1.5)), a.layout).to(dev)
+        return P.PackedRawStereoVideo(view(0), view(1)), {}
+    depth = YUV_LAYOUTS[a.layout]
+    raw = Wm.hash_uniform((T, 2, 3, h, w), 617, 0.0, float((1 << depth) - 1)).round().to(torch.int32)
+    plane = lambda s, c, rx: words(torch, raw[:, s, c, :, ::rx], depth, "lsb").contiguous()
+    view = lambda s: P.PackedYUVFrames.pack(P.YUVFrames.planar(plane(s, 0, 1), plane(s, 1, 2), plane(s, 2, 2), depth=depth, chroma="422"), a.layout).to(dev)
+    return P.PackedYUVStereoVideo(view(0), view(1)), {}
+
+
+def packed_side_a(a, torch, P, video, kw):                      # what a caller did before the door: unpack in torch, then the unpacked door
+    video_of = P.PackedRawStereoVideo if a.layout in RAW_PACKINGS else P.PackedYUVStereoVideo
+    assert isinstance(video, video_of)
+    return (P.RawStereoVideo if a.layout in RAW_PACKINGS else P.YUVStereoVideo)(video.left.unpack(), video.right.unpack()), {}
+
+
 def levels_side_a(a, torch, P, video, kw):                      # the uint8 door where the levels are bytes, the float door on to_float() otherwise
     frames = (lambda v: v.to_rgb()) if a.depth == 8 else (lambda v: v.to_float())
     return torch.stack([frames(video.left), frames(video.right)], dim=1), {}
@@ -110,6 +137,8 @@ DOORS = {  # door: (video, side_a, what side A is, what side B is[, side A's vid
              "YUVFrames.to_float() on the device, then the float door", "the YUVStereoVideo itself (ppms_video_ingest_yuv)"),
     "raw": (raw_video, levels_side_a, "RawFrames.to_rgb() / to_float() on the device, then the uint8 / float door",
             "the RawStereoVideo itself (ppms_video_ingest_raw)"),
+    "packed": (packed_video, packed_side_a, "unpack() in torch on the device, then the unpacked door (ppms_video_ingest_yuv / ppms_video_ingest_raw)",
+               "the packed stereo video itself (ppms_video_ingest_yuv_packed / ppms_video_ingest_raw_packed)"),
 }
 
 
@@ -282,7 +311,7 @@ class Side:
     def __init__(self, label, a, side, tree):
         self.label = label
         cmd = [sys.executable, os.path.abspath(__file__), "--worker", side, "--tree", tree, "--depth", str(a.depth), "--chroma", a.chroma,
-               "--pattern", a.pattern] + (["--door", a.door] if a.door else ["--kernels"]) + (["--align", a.align] if a.align else []) + (["--yuv"] if a.yuv else [])
+               "--pattern", a.pattern, "--layout", a.layout] + (["--door", a.door] if a.door else ["--kernels"]) + (["--align", a.align] if a.align else []) + (["--yuv"] if a.yuv else [])
         self.p = subprocess.Popen(cmd, stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True, bufsize=1)
 
     def ask(self, limit, *cmd):
@@ -329,7 +358,8 @@ def door_report(a, A, B):
                 ms[s].append(float(s.ask(CALL_S, "run")[0]))
         sums = {s: s.ask(CALL_S, "sum")[0] for s in (A, B)}
         fmt = {"u8": "", "yuv": "NV12 ", "remap": f"{'NV12' if a.yuv else 'RGB'} source {HS}x{WS} -> rectified ",
-               "deep": f"{a.depth}-bit {a.chroma} planar frames ({a.align}) ", "raw": f"{a.depth}-bit {a.pattern} frames ({a.align}) "}[a.door]
+               "deep": f"{a.depth}-bit {a.chroma} planar frames ({a.align}) ", "raw": f"{a.depth}-bit {a.pattern} frames ({a.align}) ",
+               "packed": f"{a.layout} frames " + (f"({a.depth if a.depth in (10, 12) else 10}-bit {a.pattern}) " if a.layout in RAW_PACKINGS else "")}[a.door]
         print(f"== --door {a.door}: T = {T}, {fmt}{h}x{w}, iters = {ITERS}: forward_batch_test(video) -> host disparity, {runs} alternating calls per side")
         for s in (A, B):
             v = ms[s]
@@ -377,6 +407,7 @@ def main():
     ap.add_argument("--chroma", default="420", choices=("420", "422", "444"), help="--door deep")
     ap.add_argument("--align", default=None, choices=("msb", "lsb"), help="--door deep (default msb) / raw (default lsb)")
     ap.add_argument("--pattern", default="rggb", choices=("rggb", "bggr", "grbg", "gbrg", "mono"), help="--door raw")
+    ap.add_argument("--layout", default="yuyv", choices=sorted(YUV_LAYOUTS) + list(RAW_PACKINGS), help="--door packed (mipi / pfnc: with --depth 10 | 12, --pattern)")
     ap.add_argument("--worker", default=None)
     ap.add_argument("--tree", default=HERE)
     a = ap.parse_args()
