@@ -169,34 +169,10 @@ _SIGS = {
     "ppms_axpby": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_float, c_int64, c_int64, c_void_p]),
     "ppms_ctx_mix": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "ppms_img_s2d": (c_int, [c_void_p, SP, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "ppms_video_ingest_u8": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, SP, SP, c_void_p]),
-    "ppms_video_ingest_yuv420": (c_int, [C.POINTER(YUVView), C.POINTER(YUVView), C.POINTER(YUVMatrix), c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                         c_void_p, SP, SP, c_void_p]),
     "ppms_yuv_struct_sizes": (c_int, [C.POINTER(c_int), C.POINTER(c_int)]),
-    "ppms_video_ingest_u8_remap": (c_int, [c_void_p, c_void_p, c_int64, C.POINTER(RemapView), C.POINTER(RemapView), c_int, c_int, c_int, c_int, c_int, c_int,
-                                           c_int, c_void_p, SP, SP, c_void_p]),
-    "ppms_video_ingest_yuv420_remap": (c_int, [C.POINTER(YUVView), C.POINTER(YUVView), C.POINTER(YUVMatrix), C.POINTER(RemapView), C.POINTER(RemapView),
-                                               c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, SP, SP, c_void_p]),
     "ppms_remap_struct_size": (c_int, [C.POINTER(c_int)]),
-    "ppms_video_ingest_yuv": (c_int, [C.POINTER(YUVView), C.POINTER(YUVView), C.POINTER(YUVMatrix), C.POINTER(YUVFormat), c_int, c_int, c_int, c_int, c_int,
-                                      c_int, c_int, c_void_p, SP, SP, c_void_p]),
-    "ppms_video_ingest_yuv_remap": (c_int, [C.POINTER(YUVView), C.POINTER(YUVView), C.POINTER(YUVMatrix), C.POINTER(YUVFormat), C.POINTER(RemapView),
-                                            C.POINTER(RemapView), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, SP, SP, c_void_p]),
     "ppms_yuv_format_struct_size": (c_int, [C.POINTER(c_int)]),
-    "ppms_video_ingest_raw": (c_int, [C.POINTER(RawView), C.POINTER(RawView), C.POINTER(RawFormat), c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                      c_void_p, SP, SP, c_void_p]),
-    "ppms_video_ingest_raw_remap": (c_int, [C.POINTER(RawView), C.POINTER(RawView), C.POINTER(RawFormat), C.POINTER(RemapView), C.POINTER(RemapView),
-                                            c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, SP, SP, c_void_p]),
     "ppms_raw_struct_sizes": (c_int, [C.POINTER(c_int), C.POINTER(c_int)]),
-    "ppms_video_ingest_yuv_packed": (c_int, [C.POINTER(PackedView), C.POINTER(PackedView), C.POINTER(YUVMatrix), C.POINTER(YUVPackedFormat), c_int, c_int,
-                                             c_int, c_int, c_int, c_int, c_int, c_void_p, SP, SP, c_void_p]),
-    "ppms_video_ingest_yuv_packed_remap": (c_int, [C.POINTER(PackedView), C.POINTER(PackedView), C.POINTER(YUVMatrix), C.POINTER(YUVPackedFormat),
-                                                   C.POINTER(RemapView), C.POINTER(RemapView), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, SP,
-                                                   SP, c_void_p]),
-    "ppms_video_ingest_raw_packed": (c_int, [C.POINTER(PackedView), C.POINTER(PackedView), C.POINTER(RawPackedFormat), c_int, c_int, c_int, c_int, c_int,
-                                             c_int, c_int, c_void_p, SP, SP, c_void_p]),
-    "ppms_video_ingest_raw_packed_remap": (c_int, [C.POINTER(PackedView), C.POINTER(PackedView), C.POINTER(RawPackedFormat), C.POINTER(RemapView),
-                                                   C.POINTER(RemapView), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, SP, SP, c_void_p]),
     "ppms_packed_struct_sizes": (c_int, [C.POINTER(c_int), C.POINTER(c_int), C.POINTER(c_int)]),
     "ppms_dwconv": (c_int, [SP, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ppms_layernorm_any": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_float, SP, c_int64, c_int, c_void_p]),
@@ -226,7 +202,30 @@ _SIGS = {
     "ppms_mem_attn_splits": (c_int, [c_int, c_int, c_int, c_int]),
     "ppms_attn_redo_accumulate": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
 }
+# the 12 ingest entry points: ppms_video_ingest_<door>(head, tail) and its _remap twin, which takes the two views' maps between head and tail
+_INGEST_HEADS = {
+    "u8": [c_void_p, c_void_p, c_int64],
+    "yuv420": [C.POINTER(YUVView), C.POINTER(YUVView), C.POINTER(YUVMatrix)],
+    "yuv": [C.POINTER(YUVView), C.POINTER(YUVView), C.POINTER(YUVMatrix), C.POINTER(YUVFormat)],
+    "raw": [C.POINTER(RawView), C.POINTER(RawView), C.POINTER(RawFormat)],
+    "yuv_packed": [C.POINTER(PackedView), C.POINTER(PackedView), C.POINTER(YUVMatrix), C.POINTER(YUVPackedFormat)],
+    "raw_packed": [C.POINTER(PackedView), C.POINTER(PackedView), C.POINTER(RawPackedFormat)],
+}
+_INGEST_TAIL = [c_int] * 7 + [c_void_p, SP, SP, c_void_p]       # N, H0, W0, pad_left, pad_top, H, W, lut, dst_fnet, dst_cnet, stream
+for _door, _head in _INGEST_HEADS.items():
+    _SIGS["ppms_video_ingest_" + _door] = (c_int, _head + _INGEST_TAIL)
+    _SIGS["ppms_video_ingest_" + _door + "_remap"] = (c_int, _head + [C.POINTER(RemapView)] * 2 + _INGEST_TAIL)
 EXPORTS = tuple(_SIGS)
+
+# (the export that reports sizeof of the header's structs, their ctypes twins, how the message names them)
+_STRUCT_SIZES = (
+    ("ppms_struct_sizes", (SP, Epilogue, Conv), "struct layout"),
+    ("ppms_yuv_struct_sizes", (YUVView, YUVMatrix), "layout of ppms_yuv_view / ppms_yuv_matrix"),
+    ("ppms_remap_struct_size", (RemapView,), "layout of ppms_remap_view"),
+    ("ppms_yuv_format_struct_size", (YUVFormat,), "layout of ppms_yuv_format"),
+    ("ppms_raw_struct_sizes", (RawView, RawFormat), "layout of ppms_raw_view / ppms_raw_format"),
+    ("ppms_packed_struct_sizes", (PackedView, YUVPackedFormat, RawPackedFormat), "layout of ppms_packed_view / ppms_yuv_packed_format / ppms_raw_packed_format"),
+)
 
 _lib: Optional[C.CDLL] = None
 
@@ -251,25 +250,11 @@ def load() -> C.CDLL:
         fn.restype, fn.argtypes = res, args
     if lib.ppms_version() != 4:
         raise RuntimeError("ppmstereo_amd: libppms.so ABI version mismatch")
-    a, b, c = c_int(), c_int(), c_int()
-    lib.ppms_struct_sizes(C.byref(a), C.byref(b), C.byref(c))
-    if (a.value, b.value, c.value) != (C.sizeof(SP), C.sizeof(Epilogue), C.sizeof(Conv)):
-        raise RuntimeError("ppmstereo_amd: ctypes struct layout differs from include/ppms.h")
-    lib.ppms_yuv_struct_sizes(C.byref(a), C.byref(b))
-    if (a.value, b.value) != (C.sizeof(YUVView), C.sizeof(YUVMatrix)):
-        raise RuntimeError("ppmstereo_amd: ctypes layout of ppms_yuv_view / ppms_yuv_matrix differs from include/ppms.h")
-    lib.ppms_remap_struct_size(C.byref(a))
-    if a.value != C.sizeof(RemapView):
-        raise RuntimeError("ppmstereo_amd: ctypes layout of ppms_remap_view differs from include/ppms.h")
-    lib.ppms_yuv_format_struct_size(C.byref(a))
-    if a.value != C.sizeof(YUVFormat):
-        raise RuntimeError("ppmstereo_amd: ctypes layout of ppms_yuv_format differs from include/ppms.h")
-    lib.ppms_raw_struct_sizes(C.byref(a), C.byref(b))
-    if (a.value, b.value) != (C.sizeof(RawView), C.sizeof(RawFormat)):
-        raise RuntimeError("ppmstereo_amd: ctypes layout of ppms_raw_view / ppms_raw_format differs from include/ppms.h")
-    lib.ppms_packed_struct_sizes(C.byref(a), C.byref(b), C.byref(c))
-    if (a.value, b.value, c.value) != (C.sizeof(PackedView), C.sizeof(YUVPackedFormat), C.sizeof(RawPackedFormat)):
-        raise RuntimeError("ppmstereo_amd: ctypes layout of ppms_packed_view / ppms_yuv_packed_format / ppms_raw_packed_format differs from include/ppms.h")
+    for export, structs, what in _STRUCT_SIZES:
+        sizes = [c_int() for _ in structs]
+        getattr(lib, export)(*(C.byref(x) for x in sizes))
+        if [x.value for x in sizes] != [C.sizeof(t) for t in structs]:
+            raise RuntimeError(f"ppmstereo_amd: ctypes {what} differs from include/ppms.h")
     if lib.ppms_egress_struct_size() != C.sizeof(Egress):
         raise RuntimeError("ppmstereo_amd: ctypes layout of ppms_egress differs from include/ppms.h")
     if lib.ppms_pwchain_param_bytes() != C.sizeof(ChainParams):

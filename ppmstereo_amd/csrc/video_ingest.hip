@@ -342,8 +342,20 @@ struct sample_format {
     int sample_bytes, depth, lsb;
 };
 template <class Format>
-static sample_format sample_format_of(const Format* f) {                  // (a null format reads as bytes here and is refused by the door's own check)
+static int depth_of(const Format* f) {                                    // (a null format reads as bytes here and is refused by the door's own check)
+    return f ? f->depth : 8;
+}
+template <class Format>
+static sample_format sample_format_of(const Format* f) {
     return f ? sample_format{f->sample_bytes, f->depth, f->lsb} : sample_format{1, 8, 0};
+}
+
+// how every format door's check opens: the pointers it needs (`pointers`: what the door's message calls them) and frames of a positive size, named
+// `hname` x `wname` in the messages
+static int opening_check(const ingest_call& a, bool all_there, const char* pointers, int H0, int W0, const char* hname, const char* wname) {
+    PPMS_REQUIRE(all_there, "%s: null %s pointer", a.who, pointers);
+    PPMS_REQUIRE(a.N > 0 && H0 > 0 && W0 > 0, "%s: N = %d, %s = %d, %s = %d must be positive", a.who, a.N, hname, H0, wname, W0);
+    return PPMS_OK;
 }
 
 static int sample_format_check(const char* who, const sample_format& f) {
@@ -389,14 +401,44 @@ static int plane_extent_check(const char* who, const char* side, int sample_byte
     return PPMS_OK;
 }
 
+// the matrix of all six YUV entry points at samples of `depth` bits.  `shift_max`: the 4:2:0 entries accept shift up to 20, every other one up to
+// 26 - depth (18 at depth 8); both keep every sum inside 32 bits
+static int yuv_matrix_check(const char* who, const ppms_yuv_matrix* m, int depth, int shift_max) {
+    PPMS_REQUIRE(m->shift >= 8 && m->shift <= shift_max, "%s: shift = %d must lie in [8, %d] at depth %d", who, m->shift, shift_max, depth);
+    PPMS_REQUIRE(m->reserved == 0, "%s: matrix: reserved = %d must be 0", who, m->reserved);
+    // coefficients below 4.0 keep every sum of the conversion inside 32 bits: three terms below 4 * 2^shift * 2^depth <= 2^28 each, plus 2^(shift - 1)
+    // (the 4:2:0 entries' shift = 20: 2^22 (255 + 128 + 128) + 2^19 < 2^31)
+    const int32_t lim = 4 << m->shift;
+    PPMS_REQUIRE(m->y_off >= 0 && m->y_off < (1 << depth) && m->cy >= 0 && m->cy < lim && m->crv >= 0 && m->crv < lim && m->cgu >= 0 && m->cgu < lim &&
+                     m->cgv >= 0 && m->cgv < lim && m->cbu >= 0 && m->cbu < lim,
+                 "%s: y_off must lie in [0, %d] and every coefficient in [0, 4 << shift)", who, (1 << depth) - 1);
+    return PPMS_OK;
+}
+
+// what ppms_raw_format and ppms_raw_packed_format share (their `depth` is checked before): pattern, black level, shift and gains, the format's
+// reserved words (3 and 4 of them), and the 2 x 2 rule of a colour pattern for frames of H0 x W0 -- in that order
+template <class Format>
+static int raw_format_check(const char* who, const Format& f, int H0, int W0, const char* hname, const char* wname) {
+    PPMS_REQUIRE(f.pattern >= 0 && f.pattern <= 4, "%s: pattern = %d must be 0 (RGGB), 1 (BGGR), 2 (GRBG), 3 (GBRG) or 4 (MONO)", who, f.pattern);
+    PPMS_REQUIRE(f.black >= 0 && f.black < (1 << f.depth), "%s: black = %d must lie in [0, %d]", who, f.black, (1 << f.depth) - 1);
+    PPMS_REQUIRE(f.shift >= 4 && f.shift <= 14, "%s: shift = %d must lie in [4, 14]", who, f.shift);
+    // gains below 16.0 keep every sum inside 32 bits: 2^12 * 2^18 + 2^13 < 2^31 at depth 12 and shift = 14
+    const int32_t lim = 16 << f.shift;
+    PPMS_REQUIRE(f.gain[0] >= 0 && f.gain[0] < lim && f.gain[1] >= 0 && f.gain[1] < lim && f.gain[2] >= 0 && f.gain[2] < lim,
+                 "%s: every gain must lie in [0, 16 << shift)", who);
+    int32_t reserved = 0;
+    for (const int32_t r : f.reserved) reserved |= r;
+    PPMS_REQUIRE(reserved == 0, "%s: format: reserved must be 0", who);
+    PPMS_REQUIRE(f.pattern == 4 || (H0 >= 2 && W0 >= 2), "%s: a colour pattern needs a frame of at least 2 x 2, got %s = %d, %s = %d", who, hname, H0, wname, W0);
+    return PPMS_OK;
+}
+
 // what the four YUV entry points check about the format, the views (frames of H0 x W0, named `hname` x `wname` in the messages) and the matrix.
-// `shift_max`: the 4:2:0 entries accept shift up to 20, the generic ones up to 26 - depth (18 at depth 8); both keep every sum inside 32 bits
+// (`shift_max`: yuv_matrix_check's)
 static int yuv_check(const ingest_call& a, const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m, const ppms_yuv_format* fmt,
                      int shift_max, int H0, int W0, const char* hname, const char* wname) {
     const char* who = a.who;
-    const int N = a.N;
-    PPMS_REQUIRE(left && right && m && fmt && a.lut, "%s: null view, matrix, format or table pointer", who);
-    PPMS_REQUIRE(N > 0 && H0 > 0 && W0 > 0, "%s: N = %d, %s = %d, %s = %d must be positive", who, N, hname, H0, wname, W0);
+    if (const int rc = opening_check(a, left && right && m && fmt && a.lut, "view, matrix, format or table", H0, W0, hname, wname)) return rc;
     const ppms_yuv_format& f = *fmt;
     const int sb = f.sample_bytes;
     if (const int rc = sample_format_check(who, sample_format_of(fmt))) return rc;
@@ -415,35 +457,17 @@ static int yuv_check(const ingest_call& a, const ppms_yuv_view* left, const ppms
                                         {"_c", "chroma ", "chroma plane", v.frame_stride_c, v.pitch_c, Hc, (int64_t)v.step_c * (Wc - 1) + sb, nullptr, 0}};
         if (const int rc = plane_extent_check(who, side, sb, (uintptr_t)v.y | (uintptr_t)v.u | (uintptr_t)v.v, planes, 2, false)) return rc;
     }
-    PPMS_REQUIRE(m->shift >= 8 && m->shift <= shift_max, "%s: shift = %d must lie in [8, %d] at depth %d", who, m->shift, shift_max, f.depth);
-    PPMS_REQUIRE(m->reserved == 0, "%s: matrix: reserved = %d must be 0", who, m->reserved);
-    // coefficients below 4.0 keep every sum of the conversion inside 32 bits: three terms below 4 * 2^shift * 2^depth <= 2^28 each, plus 2^(shift - 1)
-    // (the 4:2:0 entries' shift = 20: 2^22 (255 + 128 + 128) + 2^19 < 2^31)
-    const int32_t lim = 4 << m->shift;
-    PPMS_REQUIRE(m->y_off >= 0 && m->y_off < (1 << f.depth) && m->cy >= 0 && m->cy < lim && m->crv >= 0 && m->crv < lim && m->cgu >= 0 && m->cgu < lim &&
-                     m->cgv >= 0 && m->cgv < lim && m->cbu >= 0 && m->cbu < lim,
-                 "%s: y_off must lie in [0, %d] and every coefficient in [0, 4 << shift)", who, (1 << f.depth) - 1);
-    return PPMS_OK;
+    return yuv_matrix_check(who, m, f.depth, shift_max);
 }
 
 // what both ppms_video_ingest_raw entry points check about the format and the views (frames of H0 x W0, named `hname` x `wname` in the messages)
 static int raw_check(const ingest_call& a, const ppms_raw_view* left, const ppms_raw_view* right, const ppms_raw_format* fmt, int H0, int W0,
                      const char* hname, const char* wname) {
     const char* who = a.who;
-    const int N = a.N;
-    PPMS_REQUIRE(left && right && fmt && a.lut, "%s: null view, format or table pointer", who);
-    PPMS_REQUIRE(N > 0 && H0 > 0 && W0 > 0, "%s: N = %d, %s = %d, %s = %d must be positive", who, N, hname, H0, wname, W0);
+    if (const int rc = opening_check(a, left && right && fmt && a.lut, "view, format or table", H0, W0, hname, wname)) return rc;
     const ppms_raw_format& f = *fmt;
     if (const int rc = sample_format_check(who, sample_format_of(fmt))) return rc;
-    PPMS_REQUIRE(f.pattern >= 0 && f.pattern <= 4, "%s: pattern = %d must be 0 (RGGB), 1 (BGGR), 2 (GRBG), 3 (GBRG) or 4 (MONO)", who, f.pattern);
-    PPMS_REQUIRE(f.black >= 0 && f.black < (1 << f.depth), "%s: black = %d must lie in [0, %d]", who, f.black, (1 << f.depth) - 1);
-    PPMS_REQUIRE(f.shift >= 4 && f.shift <= 14, "%s: shift = %d must lie in [4, 14]", who, f.shift);
-    // gains below 16.0 keep every sum inside 32 bits: 2^12 * 2^18 + 2^13 < 2^31 at depth 12 and shift = 14
-    const int32_t lim = 16 << f.shift;
-    PPMS_REQUIRE(f.gain[0] >= 0 && f.gain[0] < lim && f.gain[1] >= 0 && f.gain[1] < lim && f.gain[2] >= 0 && f.gain[2] < lim,
-                 "%s: every gain must lie in [0, 16 << shift)", who);
-    PPMS_REQUIRE(f.reserved[0] == 0 && f.reserved[1] == 0 && f.reserved[2] == 0, "%s: format: reserved must be 0", who);
-    PPMS_REQUIRE(f.pattern == 4 || (H0 >= 2 && W0 >= 2), "%s: a colour pattern needs a frame of at least 2 x 2, got %s = %d, %s = %d", who, hname, H0, wname, W0);
+    if (const int rc = raw_format_check(who, f, H0, W0, hname, wname)) return rc;
     const ppms_raw_view* views[2] = {left, right};
     for (int s = 0; s < 2; ++s) {
         const ppms_raw_view& v = *views[s];
@@ -451,7 +475,7 @@ static int raw_check(const ingest_call& a, const ppms_raw_view* left, const ppms
         PPMS_REQUIRE(v.data, "%s: null data pointer in the %s view", who, side);
         PPMS_REQUIRE(v.reserved == 0, "%s: %s view: reserved = %d must be 0", who, side, v.reserved);
         const plane_extent plane{"", "", "frame", v.frame_stride, v.pitch, H0, (int64_t)W0 * f.sample_bytes, wname, W0};
-        if (const int rc = plane_extent_check(who, side, f.sample_bytes, (uintptr_t)v.data, &plane, 1, N == 1)) return rc;
+        if (const int rc = plane_extent_check(who, side, f.sample_bytes, (uintptr_t)v.data, &plane, 1, a.N == 1)) return rc;
     }
     return PPMS_OK;
 }
@@ -516,7 +540,7 @@ static int ingest_yuv420(const ingest_call& a, const ppms_yuv_view* left, const 
 
 static int ingest_yuv_format(const ingest_call& a, const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m, const ppms_yuv_format* f,
                              const remap_maps* maps) {
-    return ingest_yuv(a, left, right, m, f, 26 - sample_format_of(f).depth, maps,
+    return ingest_yuv(a, left, right, m, f, 26 - depth_of(f), maps,
                       [&](auto sample, int, int) { return yuv_source<decltype(sample)>{*left, *right, *m, a.N, f->depth, f->lsb, f->sub_x, f->sub_y}; });
 }
 
@@ -550,12 +574,11 @@ static int packed_view_check(const ingest_call& a, const char* side, const ppms_
 }
 
 // what both ppms_video_ingest_yuv_packed entry points check about the format, the views (frames of H0 x W0, named `hname` x `wname` in the messages)
-// and the matrix (ppms_video_ingest_yuv's bounds, restated)
+// and the matrix (ppms_video_ingest_yuv's bounds: yuv_matrix_check)
 static int yuv_packed_check(const ingest_call& a, const ppms_packed_view* left, const ppms_packed_view* right, const ppms_yuv_matrix* m,
                             const ppms_yuv_packed_format* fmt, int H0, int W0, const char* hname, const char* wname) {
     const char* who = a.who;
-    PPMS_REQUIRE(left && right && m && fmt && a.lut, "%s: null view, matrix, format or table pointer", who);
-    PPMS_REQUIRE(a.N > 0 && H0 > 0 && W0 > 0, "%s: N = %d, %s = %d, %s = %d must be positive", who, a.N, hname, H0, wname, W0);
+    if (const int rc = opening_check(a, left && right && m && fmt && a.lut, "view, matrix, format or table", H0, W0, hname, wname)) return rc;
     const ppms_yuv_packed_format& f = *fmt;
     PPMS_REQUIRE(f.container >= 0 && f.container <= 2, "%s: container = %d must be 0 (bytes), 1 (16-bit words) or 2 (v210)", who, f.container);
     PPMS_REQUIRE(f.order >= 0 && f.order <= 3, "%s: order = %d must be 0 (yuyv), 1 (uyvy), 2 (yvyu) or 3 (vyuy)", who, f.order);
@@ -569,32 +592,18 @@ static int yuv_packed_check(const ingest_call& a, const ppms_packed_view* left, 
     const auto row_bytes = [&](int P) { return f.container == 2 ? (int64_t)16 * ((P + 5) / 6) : (int64_t)4 * align * ((P + 1) / 2); };
     if (const int rc = packed_view_check(a, "left", *left, true, align, unit, H0, W0, wname, row_bytes)) return rc;
     if (const int rc = packed_view_check(a, "right", *right, true, align, unit, H0, W0, wname, row_bytes)) return rc;
-    PPMS_REQUIRE(m->shift >= 8 && m->shift <= 26 - f.depth, "%s: shift = %d must lie in [8, %d] at depth %d", who, m->shift, 26 - f.depth, f.depth);
-    PPMS_REQUIRE(m->reserved == 0, "%s: matrix: reserved = %d must be 0", who, m->reserved);
-    const int32_t lim = 4 << m->shift;                                     // (yuv_check's bound: no sum of the conversion leaves 32 bits)
-    PPMS_REQUIRE(m->y_off >= 0 && m->y_off < (1 << f.depth) && m->cy >= 0 && m->cy < lim && m->crv >= 0 && m->crv < lim && m->cgu >= 0 && m->cgu < lim &&
-                     m->cgv >= 0 && m->cgv < lim && m->cbu >= 0 && m->cbu < lim,
-                 "%s: y_off must lie in [0, %d] and every coefficient in [0, 4 << shift)", who, (1 << f.depth) - 1);
-    return PPMS_OK;
+    return yuv_matrix_check(who, m, f.depth, 26 - f.depth);
 }
 
-// what both ppms_video_ingest_raw_packed entry points check about the format (ppms_video_ingest_raw's bounds, restated) and the views
+// what both ppms_video_ingest_raw_packed entry points check about the format (ppms_video_ingest_raw's bounds: raw_format_check) and the views
 static int raw_packed_check(const ingest_call& a, const ppms_packed_view* left, const ppms_packed_view* right, const ppms_raw_packed_format* fmt, int H0,
                             int W0, const char* hname, const char* wname) {
     const char* who = a.who;
-    PPMS_REQUIRE(left && right && fmt && a.lut, "%s: null view, format or table pointer", who);
-    PPMS_REQUIRE(a.N > 0 && H0 > 0 && W0 > 0, "%s: N = %d, %s = %d, %s = %d must be positive", who, a.N, hname, H0, wname, W0);
+    if (const int rc = opening_check(a, left && right && fmt && a.lut, "view, format or table", H0, W0, hname, wname)) return rc;
     const ppms_raw_packed_format& f = *fmt;
     PPMS_REQUIRE(f.packing == 0 || f.packing == 1, "%s: packing = %d must be 0 (MIPI CSI-2) or 1 (PFNC, lsb first)", who, f.packing);
     PPMS_REQUIRE(f.depth == 10 || f.depth == 12, "%s: depth = %d must be 10 or 12", who, f.depth);
-    PPMS_REQUIRE(f.pattern >= 0 && f.pattern <= 4, "%s: pattern = %d must be 0 (RGGB), 1 (BGGR), 2 (GRBG), 3 (GBRG) or 4 (MONO)", who, f.pattern);
-    PPMS_REQUIRE(f.black >= 0 && f.black < (1 << f.depth), "%s: black = %d must lie in [0, %d]", who, f.black, (1 << f.depth) - 1);
-    PPMS_REQUIRE(f.shift >= 4 && f.shift <= 14, "%s: shift = %d must lie in [4, 14]", who, f.shift);
-    const int32_t lim = 16 << f.shift;                                     // (raw_check's bound: no sum leaves 32 bits)
-    PPMS_REQUIRE(f.gain[0] >= 0 && f.gain[0] < lim && f.gain[1] >= 0 && f.gain[1] < lim && f.gain[2] >= 0 && f.gain[2] < lim,
-                 "%s: every gain must lie in [0, 16 << shift)", who);
-    PPMS_REQUIRE(f.reserved[0] == 0 && f.reserved[1] == 0 && f.reserved[2] == 0 && f.reserved[3] == 0, "%s: format: reserved must be 0", who);
-    PPMS_REQUIRE(f.pattern == 4 || (H0 >= 2 && W0 >= 2), "%s: a colour pattern needs a frame of at least 2 x 2, got %s = %d, %s = %d", who, hname, H0, wname, W0);
+    if (const int rc = raw_format_check(who, f, H0, W0, hname, wname)) return rc;
     const auto row_bytes = [&](int P) {
         return f.packing == 1 ? ((int64_t)P * f.depth + 7) / 8 : f.depth == 10 ? (int64_t)5 * ((P + 3) / 4) : (int64_t)3 * ((P + 1) / 2);
     };
@@ -602,11 +611,10 @@ static int raw_packed_check(const ingest_call& a, const ppms_packed_view* left, 
     return packed_view_check(a, "right", *right, false, 1, "", H0, W0, wname, row_bytes);
 }
 
-// (a null format reads as depth 8 here and is refused by the door's own check)
 static int ingest_yuv_packed(const ingest_call& a, const ppms_packed_view* left, const ppms_packed_view* right, const ppms_yuv_matrix* m,
                              const ppms_yuv_packed_format* f, const remap_maps* maps) {
     return ingest_frames(
-        a, f ? f->depth : 8, maps,
+        a, depth_of(f), maps,
         [&](int hs, int ws, const char* hname, const char* wname) { return yuv_packed_check(a, left, right, m, f, hs, ws, hname, wname); },
         [&](auto launch, int, int) {
             const auto source = [&](auto container) { return yuv_packed_source<decltype(container)::value>{*left, *right, *m, a.N, f->depth, f->lsb, f->order}; };
@@ -619,7 +627,7 @@ static int ingest_yuv_packed(const ingest_call& a, const ppms_packed_view* left,
 static int ingest_raw_packed(const ingest_call& a, const ppms_packed_view* left, const ppms_packed_view* right, const ppms_raw_packed_format* f,
                              const remap_maps* maps) {
     return ingest_frames(
-        a, f ? f->depth : 8, maps,
+        a, depth_of(f), maps,
         [&](int hs, int ws, const char* hname, const char* wname) { return raw_packed_check(a, left, right, f, hs, ws, hname, wname); },
         [&](auto launch, int hs, int ws) {
             const auto source = [&](auto packing) {

@@ -58,14 +58,46 @@ def _levels_to_float(levels: torch.Tensor, depth: int) -> torch.Tensor:
     return levels.float() if depth == 8 else levels.float() * (255.0 / ((1 << depth) - 1))
 
 
+def _cuda_index(device) -> int:
+    """The index of the GPU a ``device`` argument means: "cuda" without an index is the current device."""
+    index = torch.device(device).index
+    return torch.cuda.current_device() if index is None else index
+
+
+def _moved_to(device) -> torch.device:
+    """Where ``to(device)`` of frames and maps goes: the indexed GPU of ``_cuda_index``, or the host device as it is."""
+    device = torch.device(device)
+    return torch.device("cuda", _cuda_index(device)) if device.type == "cuda" else device
+
+
+def _sample_lsb(who: str, align, depth: int, words: bool) -> int:
+    """``align`` checked, as the bit of a 16-bit word that holds the sample's lowest bit (bytes, and words read from the bottom: 0)."""
+    if align not in ("msb", "lsb"):
+        raise ValueError(f"{who}: align {align!r}; 'msb' or 'lsb'")
+    return 16 - depth if (words and align == "msb") else 0
+
+
+def _check_plane(who: str, name: str, t, dtype, dims: str = "(N, rows, columns)", depth: int = 8) -> None:
+    if not torch.is_tensor(t) or t.dtype != dtype or t.dim() != 3:
+        raise ValueError(f"{who}: {name} must be a {str(dtype).replace('torch.', '')} tensor {dims}" + ("" if depth == 8 else f" at depth {depth}"))
+
+
+def _strides(t: torch.Tensor, row: int):
+    """(pitch, frame stride) in elements of a plane (N, rows, .) whose rows span ``row`` elements, first to the end of the last -- or None where
+    rows or frames overlap.  A size-1 dimension's stride is arbitrary: the smallest the kernel accepts stands in for it."""
+    n, rows = t.shape[:2]
+    pitch = t.stride(1) if rows > 1 else row
+    frame = t.stride(0) if n > 1 else (rows - 1) * pitch + row
+    return None if pitch < row or frame < (rows - 1) * pitch + row else (pitch, frame)
+
+
 def level_lut(device, depth: int = 8) -> torch.Tensor:
     """fp32 [2^depth] on `device`: the normalised value of every RGB level of ``depth`` bits, from the expressions a level meets on the float
     path ON THE SAME DEVICE -- ``to_float``'s ``level * (255.0 / (2^depth - 1))`` (depth 8: the byte's value as it is), then ``forward``'s
     ``2 * (x / 255.0) - 1.0``.  torch's division by a Python scalar need not round like a division written elsewhere, so the table is what makes
     the decoded paths the float path's bits.  Built once per (device, depth) and kept (the host waits for it once)."""
     depth = _check_depth("level_lut", depth)
-    device = torch.device(device)
-    idx = torch.cuda.current_device() if device.index is None else device.index
+    idx = _cuda_index(device)
     if (idx, depth) not in _LEVEL_LUT:
         dev = torch.device("cuda", idx)
         x = _levels_to_float(torch.arange(1 << depth, dtype=torch.float32, device=dev), depth)
@@ -81,7 +113,9 @@ def byte_lut(device) -> torch.Tensor:
 
 class _Frames:
     """What ``YUVFrames``, ``RawFrames`` and the packed frames share: N frames of one view, sliced by frame range only and moved as a whole.  A subclass has ``n``,
-    ``_tensors()`` (its planes; the first names the device), ``_like(*planes)`` and ``_moved(device)``."""
+    ``_tensors()`` (its planes; the first names the device), ``_like(*planes)`` and ``_moved(device)`` -- and for its front door ``_entry`` (the
+    entry point's name), ``view_struct()``, ``_structs()`` (the structs that follow the two views), ``table(device)`` (the level table of the launch),
+    ``levels_to_float(levels)`` and ``format_fault(other)`` (why ``other`` is no second view beside these frames, or None)."""
 
     def __len__(self) -> int:
         return self.n
@@ -97,15 +131,13 @@ class _Frames:
 
     def to(self, device):
         """These frames on ``device`` ("cuda" without an index: the current device), dense; frames already there are returned as they are."""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
+        device = _moved_to(device)
         return self if self.device == device else self._moved(device)
 
 
 class _StereoVideo:
     """What ``YUVStereoVideo``, ``RawStereoVideo`` and their packed twins share: two frame objects of class ``_views`` with one size, frame count and device (a fault
-    there is reported as "both views need ``_one``") and one format -- ``_format_fault(left, right)``: what differs, or None.  ``len()``, slicing
+    there is reported as "both views need ``_one``") and one format -- ``left.format_fault(right)``: what differs, or None.  ``len()``, slicing
     by frame range, ``to(device)``."""
     _views: type
     _one = "one device"
@@ -116,7 +148,7 @@ class _StereoVideo:
             raise TypeError(f"{name}: two {self._views.__name__} expected")
         if (left.n, left.height, left.width) != (right.n, right.height, right.width):
             raise ValueError(f"{name}: the views differ: {(left.n, left.height, left.width)} and {(right.n, right.height, right.width)}")
-        fault = f"both views need {self._one}" if left.device != right.device else self._format_fault(left, right)
+        fault = f"both views need {self._one}" if left.device != right.device else left.format_fault(right)
         if fault:
             raise ValueError(f"{name}: {fault}")
         self.left, self.right = left, right
@@ -158,7 +190,26 @@ def yuv_matrix(standard: str = "bt709", full_range: bool = False, shift: int = 1
                        cbu=round(sc * 2.0 * (1.0 - kb) * one), shift=shift, reserved=0)
 
 
-class YUVFrames(_Frames):
+class _YUVColour:
+    """What ``YUVFrames`` and ``PackedYUVFrames`` share: ``standard``, ``full_range`` and ``depth`` choose the matrix, the level table is ``level_lut``'s
+    of that depth, and two views need one standard and one range."""
+
+    def matrix(self) -> L.YUVMatrix:
+        return yuv_matrix(self.standard, self.full_range, depth=self.depth)
+
+    def table(self, device) -> torch.Tensor:
+        return level_lut(device, self.depth)
+
+    def levels_to_float(self, levels: torch.Tensor) -> torch.Tensor:
+        return _levels_to_float(levels, self.depth)
+
+    def _colour_fault(self, other) -> Optional[str]:
+        if (self.standard, self.full_range) != (other.standard, other.full_range):
+            return "both views need one standard, one range and one device"
+        return None
+
+
+class YUVFrames(_YUVColour, _Frames):
     """One view's N decoded YUV frames, as a decoder leaves them: ``y`` (N, H0, W0), ``u`` / ``v`` (N, ceil(H0 / 2), ceil(W0 / 2)) for
     ``chroma="420"`` (the default), (N, H0, ceil(W0 / 2)) for "422", (N, H0, W0) for "444".  ``depth=8`` (the default): uint8 planes; ``depth`` 10 or 12:
     ``torch.uint16`` planes whose words hold the sample at the top (``align="msb"``: P010 / P012 / P210; the low bits are dropped whatever they hold)
@@ -174,15 +225,12 @@ class YUVFrames(_Frames):
     def __init__(self, y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, standard: str = "bt709", full_range: bool = False, depth: int = 8,
                  align: str = "msb", chroma: str = "420"):
         depth = _check_depth("YUVFrames", depth)
-        if align not in ("msb", "lsb"):
-            raise ValueError(f"YUVFrames: align {align!r}; 'msb' or 'lsb'")
+        dtype, es = (torch.uint8, 1) if depth == 8 else (torch.uint16, 2)
+        lsb = _sample_lsb("YUVFrames", align, depth, es == 2)
         if chroma not in _CHROMA:
             raise ValueError(f"YUVFrames: chroma {chroma!r}; one of {sorted(_CHROMA)}")
-        dtype, es = (torch.uint8, 1) if depth == 8 else (torch.uint16, 2)
         for name, t in (("y", y), ("u", u), ("v", v)):
-            if not torch.is_tensor(t) or t.dtype != dtype or t.dim() != 3:
-                raise ValueError(f"YUVFrames: {name} must be a {'uint8' if es == 1 else 'uint16'} tensor (N, rows, columns)" +
-                                 ("" if es == 1 else f" at depth {depth}"))
+            _check_plane("YUVFrames", name, t, dtype, depth=depth)
         n, h0, w0 = y.shape
         sub_x, sub_y = _CHROMA[chroma]
         hc, wc = (h0 + (1 << sub_y) - 1) >> sub_y, (w0 + (1 << sub_x) - 1) >> sub_x
@@ -201,21 +249,18 @@ class YUVFrames(_Frames):
             raise ValueError(f"YUVFrames: chroma last-dimension stride {step}; 1 (planar) or 2 (interleaved) expected")
         if es == 2 and any(t.data_ptr() % 2 for t in (y, u, v)):
             raise ValueError("YUVFrames: 16-bit planes must start at even addresses")
-        # a size-1 dimension's stride is arbitrary: the smallest the kernel accepts stands in for it (elements here, bytes below)
-        pitch_y = y.stride(1) if h0 > 1 else w0
-        pitch_c = u.stride(1) if hc > 1 else step * (wc - 1) + 1
-        frame_y = y.stride(0) if n > 1 else (h0 - 1) * pitch_y + w0
-        frame_c = u.stride(0) if n > 1 else (hc - 1) * pitch_c + step * (wc - 1) + 1
-        if (pitch_y < w0 or pitch_c < step * (wc - 1) + 1 or frame_y < (h0 - 1) * pitch_y + w0 or frame_c < (hc - 1) * pitch_c + step * (wc - 1) + 1):
+        luma, chroma_strides = _strides(y, w0), _strides(u, step * (wc - 1) + 1)      # (elements here, bytes below)
+        if luma is None or chroma_strides is None:
             raise ValueError(f"YUVFrames: rows or frames overlap (y strides {y.stride()}, chroma strides {u.stride()})")
-        self.pitch_y, self.pitch_c, self.step_c = pitch_y * es, pitch_c * es, step * es
-        self.frame_stride_y, self.frame_stride_c = frame_y * es, frame_c * es
+        (self.pitch_y, self.frame_stride_y), (self.pitch_c, self.frame_stride_c) = ((p * es, f * es) for p, f in (luma, chroma_strides))
+        self.step_c = step * es
         yuv_matrix(standard)                                               # (refuses an unknown standard here)
         self.y, self.u, self.v, self.standard, self.full_range = y, u, v, standard, bool(full_range)
         self.n, self.height, self.width = n, h0, w0
         self.depth, self.align, self.chroma, self.sample_bytes = depth, align, chroma, es
-        self.sub_x, self.sub_y = sub_x, sub_y
-        self.lsb = 16 - depth if (es == 2 and align == "msb") else 0        # bit of the word that holds the sample's lowest bit
+        self.sub_x, self.sub_y, self.lsb = sub_x, sub_y, lsb
+        # the door: 8-bit 4:2:0 has an entry point of its own, which takes no format (it writes ppms_video_ingest_yuv's bits a tenth sooner)
+        self._entry = "ppms_video_ingest_yuv420" if (depth, chroma) == (8, "420") else "ppms_video_ingest_yuv"
 
     @classmethod
     def nv12(cls, y: torch.Tensor, uv: torch.Tensor, standard: str = "bt709", full_range: bool = False) -> "YUVFrames":
@@ -289,12 +334,18 @@ class YUVFrames(_Frames):
             return self._like(y, uv[..., 0], uv[..., 1])
         return self._like(y, self.u.to(device), self.v.to(device))
 
-    def matrix(self) -> L.YUVMatrix:
-        return yuv_matrix(self.standard, self.full_range, depth=self.depth)
+    def format_fault(self, other: "YUVFrames") -> Optional[str]:
+        fault = self._colour_fault(other)
+        if fault is None and (self.depth, self.lsb, self.chroma) != (other.depth, other.lsb, other.chroma):
+            fault = f"the views differ in depth, alignment or chroma: {(self.depth, self.align, self.chroma)} and {(other.depth, other.align, other.chroma)}"
+        return fault
 
     def format_struct(self) -> L.YUVFormat:
         """The ``ppms_yuv_format`` of these frames."""
         return L.YUVFormat(self.sample_bytes, self.depth, self.lsb, self.sub_x, self.sub_y, (0, 0, 0))
+
+    def _structs(self):
+        return (self.matrix(),) if self._entry.endswith("420") else (self.matrix(), self.format_struct())
 
     def view_struct(self) -> L.YUVView:
         """The ``ppms_yuv_view`` of these frames."""
@@ -333,19 +384,94 @@ class YUVStereoVideo(_StereoVideo):
     slicing by frame range, ``to(device)`` (8-bit 4:2:0: 1.5 bytes per pixel and view; P010: 3)."""
     _views, _one = YUVFrames, "one standard, one range and one device"
 
-    def _format_fault(self, left: YUVFrames, right: YUVFrames) -> Optional[str]:
-        if (left.standard, left.full_range) != (right.standard, right.full_range):
-            return f"both views need {self._one}"
-        if (left.depth, left.lsb, left.chroma) != (right.depth, right.lsb, right.chroma):
-            return f"the views differ in depth, alignment or chroma: {(left.depth, left.align, left.chroma)} and {(right.depth, right.align, right.chroma)}"
-        return None
-
 
 _RAW_PATTERNS = {"rggb": 0, "bggr": 1, "grbg": 2, "gbrg": 3, "mono": 4}           # ppms_raw_format.pattern
 _RAW_SHIFT = 10                                                                    # the white-balance gains' fixed point
 
 
-class RawFrames(_Frames):
+class _RawFormat:
+    """What ``RawFrames`` and ``PackedRawFrames`` say about the sensor, checked once: ``pattern``, ``depth``, ``black``, ``gains`` (``gain_q``:
+    quantised), ``tone`` -- and the tone curve and the ingest table per device, each made once.  Every slice, half and copy of the frames holds
+    the same object.  (The messages name ``RawFrames``, whose arguments these are, for the packed frames too.)"""
+
+    def __init__(self, pattern: str, depth: int, black: int, gains, tone: Optional[torch.Tensor]):
+        if pattern not in _RAW_PATTERNS:
+            raise ValueError(f"RawFrames: pattern {pattern!r}; one of {sorted(_RAW_PATTERNS)}")
+        if not (isinstance(black, int) and 0 <= black < (1 << depth)):
+            raise ValueError(f"RawFrames: black = {black!r} must be an integer level in [0, {(1 << depth) - 1}]")
+        try:
+            gains = tuple(float(g) for g in gains)
+        except (TypeError, ValueError):
+            raise ValueError(f"RawFrames: gains = {gains!r} must be three numbers (R, G, B)") from None
+        if len(gains) != 3 or not all(0.0 <= g < 16.0 and 0 <= round(g * (1 << _RAW_SHIFT)) < (16 << _RAW_SHIFT) for g in gains):
+            raise ValueError(f"RawFrames: gains = {gains!r} must be three numbers (R, G, B) in [0, 16)")
+        if tone is not None:
+            if not torch.is_tensor(tone) or not tone.is_floating_point() or tuple(tone.shape) != (1 << depth,):
+                raise ValueError(f"RawFrames: tone must be a floating-point tensor of {1 << depth} values, one per level of {depth} bits")
+            tone = tone.detach().to(torch.float32)
+            if not bool(((tone >= 0.0) & (tone <= 255.0)).all()):
+                raise ValueError("RawFrames: tone holds values outside [0, 255]")
+        self.pattern, self.depth, self.black, self.gains, self.tone = pattern, depth, black, gains, tone
+        self.gain_q = tuple(round(g * (1 << _RAW_SHIFT)) for g in gains)
+        self._tone_on: Dict[torch.device, torch.Tensor] = {}
+        self._table_on: Dict[torch.device, torch.Tensor] = {}
+
+    def same_format(self, other: "_RawFormat") -> bool:
+        """One pattern, depth, black level, white balance and tone curve."""
+        if (self.pattern, self.depth, self.black, self.gain_q) != (other.pattern, other.depth, other.black, other.gain_q):
+            return False
+        if self.tone is None or other.tone is None or self.tone is other.tone:
+            return self.tone is other.tone
+        return torch.equal(self.tone.cpu(), other.tone.cpu())
+
+    def tone_on(self, device) -> Optional[torch.Tensor]:
+        """``tone`` on ``device`` (None stays None); copied there once."""
+        if self.tone is None:
+            return None
+        device = torch.device(device)
+        if device not in self._tone_on:
+            self._tone_on[device] = self.tone.to(device).contiguous()
+        return self._tone_on[device]
+
+    def levels_to_float(self, levels: torch.Tensor) -> torch.Tensor:
+        """RGB levels (``to_rgb``'s, or their remap) -> the float32 video in [0, 255] they stand for: ``tone[level]``, or without a tone curve
+        ``level * (255.0 / (2^depth - 1))``."""
+        tone = self.tone_on(levels.device)
+        return _levels_to_float(levels, self.depth) if tone is None else tone[levels.long()]
+
+    def table(self, device) -> torch.Tensor:
+        """fp32 [2^depth] on ``device``: the normalised value of every level, what the ingest kernel looks up.  Without a tone curve
+        ``level_lut``'s tensor; with one ``2 * (tone / 255.0) - 1.0`` computed ON THE DEVICE, ``forward``'s own expression on ``to_float``'s
+        values -- for ``byte_lut``'s reason.  Built once per device and kept with the frames (the host waits for it once)."""
+        if self.tone is None:
+            return level_lut(device, self.depth)
+        dev = torch.device("cuda", _cuda_index(device))
+        if dev not in self._table_on:
+            self._table_on[dev] = (2 * (self.tone_on(dev) / 255.0) - 1.0).contiguous()
+            torch.cuda.current_stream(dev).synchronize()         # later calls may read it from any stream
+        return self._table_on[dev]
+
+
+class _RawSensor:
+    """What ``RawFrames`` and ``PackedRawFrames`` share: one ``_RawFormat``, whose ``pattern``, ``black``, ``gains``, ``gain_q`` and ``tone`` are
+    the frames' own attributes and whose tone curve and table are the frames'."""
+
+    def _describe(self, fmt: _RawFormat) -> None:
+        self._format = fmt
+        self.pattern, self.black, self.gains, self.gain_q, self.tone = fmt.pattern, fmt.black, fmt.gains, fmt.gain_q, fmt.tone
+
+    def tone_on(self, device) -> Optional[torch.Tensor]:
+        return self._format.tone_on(device)
+
+    def levels_to_float(self, levels: torch.Tensor) -> torch.Tensor:
+        return self._format.levels_to_float(levels)
+
+    def table(self, device) -> torch.Tensor:
+        """The frames' own level table on ``device`` (``_RawFormat.table``), built once and shared by every slice, half and copy."""
+        return self._format.table(device)
+
+
+class RawFrames(_RawSensor, _Frames):
     """One view's N raw sensor frames, as a camera driver leaves them: ``data`` (N, H0, W0), one sample per pixel under the colour-filter mosaic
     ``pattern`` ("rggb" / "bggr" / "grbg" / "gbrg": the 2 x 2 tile at the frame's origin, row-major -- BayerRG8, BayerGB10 ...) or "mono"
     (Mono8 / Mono10 / Mono12).  ``depth=8``: a uint8 plane; ``depth`` 10 or 12: a ``torch.uint16`` plane whose words hold the sample at the bottom
@@ -359,57 +485,37 @@ class RawFrames(_Frames):
     kernel looks every level up in a table anyway).  Packed 10p / 12p transport formats: ``PackedRawFrames``.  Not covered: 14- and 16-bit sensors,
     demosaicing better than bilinear, colour-correction matrices, lens shading and defect pixels, per-view differing patterns, b > 1."""
 
+    _entry = "ppms_video_ingest_raw"
+
     def __init__(self, data: torch.Tensor, pattern: str = "rggb", depth: int = 8, align: str = "lsb", black: int = 0, gains=(1.0, 1.0, 1.0),
-                 tone: Optional[torch.Tensor] = None, _shared: Optional[dict] = None):
+                 tone: Optional[torch.Tensor] = None, _format: Optional[_RawFormat] = None):
         depth = _check_depth("RawFrames", depth)
-        if pattern not in _RAW_PATTERNS:
-            raise ValueError(f"RawFrames: pattern {pattern!r}; one of {sorted(_RAW_PATTERNS)}")
-        if align not in ("msb", "lsb"):
-            raise ValueError(f"RawFrames: align {align!r}; 'msb' or 'lsb'")
+        # (a slice, half or copy passes its frames' own format on: checked once, one tone curve and one table per device for all of them)
+        self._describe(_RawFormat(pattern, depth, black, gains, tone) if _format is None else _format)
         dtype, es = (torch.uint8, 1) if depth == 8 else (torch.uint16, 2)
-        if not torch.is_tensor(data) or data.dtype != dtype or data.dim() != 3:
-            raise ValueError(f"RawFrames: data must be a {'uint8' if es == 1 else 'uint16'} tensor (N, rows, columns)" + ("" if es == 1 else f" at depth {depth}"))
+        lsb = _sample_lsb("RawFrames", align, depth, es == 2)
+        _check_plane("RawFrames", "data", data, dtype, depth=depth)
         n, h0, w0 = data.shape
         if n < 1 or h0 < 1 or w0 < 1:
             raise ValueError(f"RawFrames: empty plane {tuple(data.shape)}")
-        if pattern != "mono" and (h0 < 2 or w0 < 2):
+        if self.pattern != "mono" and (h0 < 2 or w0 < 2):
             raise ValueError(f"RawFrames: a colour pattern needs frames of at least 2 x 2, got {h0} x {w0}")
         if w0 > 1 and data.stride(2) != 1:
             raise ValueError(f"RawFrames: data has last-dimension stride {data.stride(2)}; samples must be adjacent")
         if es == 2 and data.data_ptr() % 2:
             raise ValueError("RawFrames: a 16-bit plane must start at an even address")
-        # a size-1 dimension's stride is arbitrary: the smallest the kernel accepts stands in for it (elements here, bytes below)
-        pitch = data.stride(1) if h0 > 1 else w0
-        frame = data.stride(0) if n > 1 else (h0 - 1) * pitch + w0
-        if pitch < w0 or frame < (h0 - 1) * pitch + w0:
+        strides = _strides(data, w0)                                       # (elements here, bytes below)
+        if strides is None:
             raise ValueError(f"RawFrames: rows or frames overlap (strides {data.stride()})")
-        if not (isinstance(black, int) and 0 <= black < (1 << depth)):
-            raise ValueError(f"RawFrames: black = {black!r} must be an integer level in [0, {(1 << depth) - 1}]")
-        try:
-            gains = tuple(float(g) for g in gains)
-        except (TypeError, ValueError):
-            raise ValueError(f"RawFrames: gains = {gains!r} must be three numbers (R, G, B)") from None
-        if len(gains) != 3 or not all(0.0 <= g < 16.0 and 0 <= round(g * (1 << _RAW_SHIFT)) < (16 << _RAW_SHIFT) for g in gains):
-            raise ValueError(f"RawFrames: gains = {gains!r} must be three numbers (R, G, B) in [0, 16)")
-        if tone is not None and _shared is None:                           # (checked once: slices and copies hold the same tensor)
-            if not torch.is_tensor(tone) or not tone.is_floating_point() or tuple(tone.shape) != (1 << depth,):
-                raise ValueError(f"RawFrames: tone must be a floating-point tensor of {1 << depth} values, one per level of {depth} bits")
-            tone = tone.detach().to(torch.float32)
-            if not bool(((tone >= 0.0) & (tone <= 255.0)).all()):
-                raise ValueError("RawFrames: tone holds values outside [0, 255]")
-        self.data, self.pattern, self.depth, self.align, self.black, self.gains, self.tone = data, pattern, depth, align, black, gains, tone
+        self.data, self.depth, self.align, self.lsb = data, depth, align, lsb
         self.n, self.height, self.width, self.sample_bytes = n, h0, w0, es
-        self.pitch, self.frame_stride = pitch * es, frame * es
-        self.lsb = 16 - depth if (es == 2 and align == "msb") else 0        # bit of the word that holds the sample's lowest bit
-        self.gain_q = tuple(round(g * (1 << _RAW_SHIFT)) for g in gains)
-        # what every slice, half and copy of these frames shares: the tone curve and the ingest table per device, each made once
-        self._shared = {"tone": {}, "table": {}} if _shared is None else _shared
+        self.pitch, self.frame_stride = strides[0] * es, strides[1] * es
 
     def _tensors(self):
         return (self.data,)
 
     def _like(self, data) -> "RawFrames":
-        return RawFrames(data, self.pattern, self.depth, self.align, self.black, self.gains, self.tone, _shared=self._shared)
+        return RawFrames(data, depth=self.depth, align=self.align, _format=self._format)
 
     def split_side_by_side(self):
         """(left, right): the two halves of frames that pack both views side by side; views, no copy.  The packed width must be even -- and with a
@@ -432,15 +538,20 @@ class RawFrames(_Frames):
 
     def same_format(self, other: "RawFrames") -> bool:
         """Both hold one kind of sample, under one pattern, with one black level, white balance and tone curve."""
-        if (self.pattern, self.depth, self.lsb, self.black, self.gain_q) != (other.pattern, other.depth, other.lsb, other.black, other.gain_q):
-            return False
-        if self.tone is None or other.tone is None or self.tone is other.tone:
-            return self.tone is other.tone
-        return torch.equal(self.tone.cpu(), other.tone.cpu())
+        return self.lsb == other.lsb and self._format.same_format(other._format)
+
+    def format_fault(self, other: "RawFrames") -> Optional[str]:
+        if self.same_format(other):
+            return None
+        return ("the views differ in pattern, depth, alignment, black level, gains or tone curve: "
+                f"{(self.pattern, self.depth, self.align, self.black, self.gains)} and {(other.pattern, other.depth, other.align, other.black, other.gains)}")
 
     def format_struct(self) -> L.RawFormat:
         """The ``ppms_raw_format`` of these frames."""
         return L.RawFormat(self.sample_bytes, self.depth, self.lsb, _RAW_PATTERNS[self.pattern], self.black, self.gain_q, _RAW_SHIFT, (0, 0, 0))
+
+    def _structs(self):
+        return (self.format_struct(),)
 
     def view_struct(self) -> L.RawView:
         """The ``ppms_raw_view`` of these frames."""
@@ -474,37 +585,9 @@ class RawFrames(_Frames):
         levels = ((v - self.black) * gain + (1 << (_RAW_SHIFT - 1))) >> _RAW_SHIFT
         return levels.clamp_(0, top).to(torch.uint8 if self.depth == 8 else torch.int16)
 
-    def tone_on(self, device) -> Optional[torch.Tensor]:
-        """``tone`` on ``device`` (None stays None); copied there once."""
-        if self.tone is None:
-            return None
-        device = torch.device(device)
-        if device not in self._shared["tone"]:
-            self._shared["tone"][device] = self.tone.to(device).contiguous()
-        return self._shared["tone"][device]
-
-    def levels_to_float(self, levels: torch.Tensor) -> torch.Tensor:
-        """RGB levels (``to_rgb``'s, or their remap) -> the float32 video in [0, 255] they stand for: ``tone[level]``, or without a tone curve
-        ``level * (255.0 / (2^depth - 1))``."""
-        tone = self.tone_on(levels.device)
-        return _levels_to_float(levels, self.depth) if tone is None else tone[levels.long()]
-
     def to_float(self) -> torch.Tensor:
         """float32 (N, 3, H0, W0) in [0, 255]: the video the reference would be given."""
         return self.levels_to_float(self.to_rgb())
-
-    def table(self, device) -> torch.Tensor:
-        """fp32 [2^depth] on ``device``: the normalised value of every level, what the ingest kernel looks up.  Without a tone curve
-        ``level_lut``'s tensor; with one ``2 * (tone / 255.0) - 1.0`` computed ON THE DEVICE, ``forward``'s own expression on ``to_float``'s
-        values -- for ``byte_lut``'s reason.  Built once per device and kept with the frames (the host waits for it once)."""
-        if self.tone is None:
-            return level_lut(device, self.depth)
-        device = torch.device(device)
-        dev = torch.device("cuda", torch.cuda.current_device() if device.index is None else device.index)
-        if dev not in self._shared["table"]:
-            self._shared["table"][dev] = (2 * (self.tone_on(dev) / 255.0) - 1.0).contiguous()
-            torch.cuda.current_stream(dev).synchronize()         # later calls may read it from any stream
-        return self._shared["table"][dev]
 
 
 class RawStereoVideo(_StereoVideo):
@@ -512,12 +595,6 @@ class RawStereoVideo(_StereoVideo):
     ``RawFrames`` of one size, frame count, device, pattern, sample format (depth, alignment), black level, white balance and tone curve.
     ``len()``, slicing by frame range, ``to(device)`` (1 byte per pixel and view; 2 for 10- and 12-bit samples)."""
     _views = RawFrames
-
-    def _format_fault(self, left: RawFrames, right: RawFrames) -> Optional[str]:
-        if left.same_format(right):
-            return None
-        return ("the views differ in pattern, depth, alignment, black level, gains or tone curve: "
-                f"{(left.pattern, left.depth, left.align, left.black, left.gains)} and {(right.pattern, right.depth, right.align, right.black, right.gains)}")
 
 
 class _PackedFrames(_Frames):
@@ -528,8 +605,7 @@ class _PackedFrames(_Frames):
 
     def _surface(self, data: torch.Tensor, width, x0, dtype, pair: bool) -> None:
         name = self._name
-        if not torch.is_tensor(data) or data.dtype != dtype or data.dim() != 3:
-            raise ValueError(f"{name}: data must be a {str(dtype).replace('torch.', '')} tensor (N, rows, row elements)")
+        _check_plane(name, "data", data, dtype, "(N, rows, row elements)")
         if not (isinstance(width, int) and isinstance(x0, int) and width >= 1 and x0 >= 0 and x0 + width <= 65536):
             raise ValueError(f"{name}: width = {width!r}, x0 = {x0!r} must be integers with width >= 1, x0 >= 0 and x0 + width <= 65536")
         if pair and x0 % 2:
@@ -543,11 +619,10 @@ class _PackedFrames(_Frames):
         if row > 1 and data.stride(2) != 1:
             raise ValueError(f"{name}: data has last-dimension stride {data.stride(2)}; a row's elements must be adjacent")
         es = data.element_size()
-        # a size-1 dimension's stride is arbitrary: the smallest the kernel accepts stands in for it (elements here, bytes below)
-        pitch = data.stride(1) if h0 > 1 else need
-        frame = data.stride(0) if n > 1 else (h0 - 1) * pitch + need
-        if pitch < need or frame < (h0 - 1) * pitch + need:
+        strides = _strides(data, need)                                     # (elements here, bytes below)
+        if strides is None:
             raise ValueError(f"{name}: rows or frames overlap (strides {data.stride()})")
+        pitch, frame = strides
         if data.data_ptr() % self._align or (pitch * es) % self._align or (frame * es) % self._align:
             raise ValueError(f"{name}: the surface's address, pitch and frame stride must be multiples of {self._align} bytes")
         self.data, self.x0, self.n, self.height, self.width = data, x0, n, h0, width
@@ -601,7 +676,7 @@ def _packed_yuv_indices(order: int, x0: int, width: int, device):
     return 2 * p + a, 4 * j + (1 - a + (order & 2)), 4 * j + (3 - order)
 
 
-class PackedYUVFrames(_PackedFrames):
+class PackedYUVFrames(_YUVColour, _PackedFrames):
     """One view's N frames of packed 4:2:2 YUV, as a UVC camera or a capture card leaves them: ``data`` (N, H0, row elements) over the driver's own
     buffer, ``width`` pixels wide.  ``layout`` "yuyv" (YUY2) / "uyvy" / "yvyu" / "vyuy": uint8, 4 bytes per pixel pair in that order; "y210" /
     "y212": ``torch.uint16`` words in yuyv order holding 10 / 12 bits at the top (``align="msb"``, the default: Y210 / Y212; the low bits are
@@ -611,21 +686,19 @@ class PackedYUVFrames(_PackedFrames):
     reads ``data_ptr()`` and ``stride()`` and never copies.  ``unpack`` is the definition of the samples, ``to_rgb`` / ``to_float`` those of the
     planar frames it returns (chroma from the pixel's own pair, nearest).  Not covered: Y216 and other 16-bit depths, 4:4:4 packed (v410, Y410,
     AYUV), big-endian containers, packed RGB, interpolated chroma siting, b > 1."""
-    _name = "PackedYUVFrames"
+    _name, _entry = "PackedYUVFrames", "ppms_video_ingest_yuv_packed"
 
     def __init__(self, data: torch.Tensor, width: int, layout: str = "yuyv", align: str = "msb", standard: str = "bt709", full_range: bool = False,
                  x0: int = 0):
         if layout not in _PACKED_YUV:
             raise ValueError(f"PackedYUVFrames: layout {layout!r}; one of {sorted(_PACKED_YUV)}")
-        if align not in ("msb", "lsb"):
-            raise ValueError(f"PackedYUVFrames: align {align!r}; 'msb' or 'lsb'")
         self.container, self.depth, self.order = _PACKED_YUV[layout]
+        self.lsb = _sample_lsb("PackedYUVFrames", align, self.depth, self.container == 1)
         self._align = (1, 2, 4)[self.container]
         self._group = (6, 16) if self.container == 2 else (2, 4)
         self._surface(data, width, x0, torch.uint16 if self.container == 1 else torch.uint8, True)
         yuv_matrix(standard)                                               # (refuses an unknown standard here)
         self.layout, self.align, self.standard, self.full_range = layout, align, standard, bool(full_range)
-        self.lsb = 16 - self.depth if (self.container == 1 and align == "msb") else 0
 
     def _row_elements(self, p: int) -> int:
         return _packed_yuv_row(self.container, p)
@@ -644,12 +717,18 @@ class PackedYUVFrames(_PackedFrames):
         h = self._half("split_top_bottom", self.height, False, "views")
         return self._like(self.data[:, :h]), self._like(self.data[:, h:])
 
-    def matrix(self) -> L.YUVMatrix:
-        return yuv_matrix(self.standard, self.full_range, depth=self.depth)
+    def format_fault(self, other: "PackedYUVFrames") -> Optional[str]:
+        fault = self._colour_fault(other)
+        if fault is None and (self.layout, self.lsb) != (other.layout, other.lsb):
+            fault = f"the views differ in layout or alignment: {(self.layout, self.align)} and {(other.layout, other.align)}"
+        return fault
 
     def format_struct(self) -> L.YUVPackedFormat:
         """The ``ppms_yuv_packed_format`` of these frames."""
         return L.YUVPackedFormat(self.container, self.depth, self.lsb, self.order, (0, 0, 0, 0))
+
+    def _structs(self):
+        return self.matrix(), self.format_struct()
 
     def unpack(self) -> YUVFrames:
         """The ``YUVFrames.planar(..., chroma="422")`` holding the same samples (uint8, or uint16 with the bits at the bottom), in torch integer
@@ -697,18 +776,11 @@ class PackedYUVStereoVideo(_StereoVideo):
     ``to(device)`` (the packed bytes: YUYV 2 per pixel and view, v210 2.67, Y210 4)."""
     _views, _one = PackedYUVFrames, "one standard, one range and one device"
 
-    def _format_fault(self, left: PackedYUVFrames, right: PackedYUVFrames) -> Optional[str]:
-        if (left.standard, left.full_range) != (right.standard, right.full_range):
-            return f"both views need {self._one}"
-        if (left.layout, left.lsb) != (right.layout, right.lsb):
-            return f"the views differ in layout or alignment: {(left.layout, left.align)} and {(right.layout, right.align)}"
-        return None
-
 
 _RAW_PACKINGS = {"mipi": 0, "pfnc": 1}                                             # ppms_raw_packed_format.packing
 
 
-class PackedRawFrames(_PackedFrames):
+class PackedRawFrames(_RawSensor, _PackedFrames):
     """One view's N raw sensor frames in a packed transport format: ``data`` uint8 (N, H0, row bytes) over the driver's own buffer, ``width``
     pixels wide, ``depth`` 10 or 12 bits without padding.  ``packing="mipi"``: MIPI CSI-2 RAW10 / RAW12 as V4L2's SRGGB10P / SRGGB12P ... leave
     them -- the top 8 bits of 4 (2) pixels in 4 (2) bytes, their low bits together in a fifth (third); ``packing="pfnc"``: GenICam PFNC
@@ -716,10 +788,10 @@ class PackedRawFrames(_PackedFrames):
     whole bytes).  ``pattern``, ``black``, ``gains`` and ``tone`` are ``RawFrames``'; ``x0`` may be any column, and the pattern is that of the
     view's own pixel (0, 0).  ``unpack`` is the definition of the samples, ``to_rgb`` / ``to_float`` those of the ``RawFrames`` it returns.  Not
     covered: 14-bit packed depths, packings whose rows are padded inside, patterns that differ between the views, b > 1."""
-    _name, _align = "PackedRawFrames", 1
+    _name, _align, _entry = "PackedRawFrames", 1, "ppms_video_ingest_raw_packed"
 
     def __init__(self, data: torch.Tensor, width: int, pattern: str = "rggb", depth: int = 10, packing: str = "mipi", black: int = 0,
-                 gains=(1.0, 1.0, 1.0), tone: Optional[torch.Tensor] = None, x0: int = 0, _proto: Optional[RawFrames] = None):
+                 gains=(1.0, 1.0, 1.0), tone: Optional[torch.Tensor] = None, x0: int = 0, _format: Optional[_RawFormat] = None):
         if depth not in (10, 12):
             raise ValueError(f"PackedRawFrames: depth = {depth!r}; 10 or 12")
         if packing not in _RAW_PACKINGS:
@@ -727,17 +799,16 @@ class PackedRawFrames(_PackedFrames):
         self.depth, self.packing = depth, packing
         self._group = (4, 5) if depth == 10 else (2, 3)
         self._surface(data, width, x0, torch.uint8, False)
-        # pattern, black level, gains and tone curve are checked and kept by a RawFrames of the same format, shared by every slice, half and copy
-        self._proto = RawFrames(torch.zeros((1, 2, 2), dtype=torch.uint16), pattern, depth, "lsb", black, gains, tone) if _proto is None else _proto
-        if self._proto.pattern != "mono" and (self.height < 2 or width < 2):
+        # (a slice, half or copy passes its frames' own format on, as RawFrames does)
+        self._describe(_RawFormat(pattern, depth, black, gains, tone) if _format is None else _format)
+        if self.pattern != "mono" and (self.height < 2 or width < 2):
             raise ValueError(f"PackedRawFrames: a colour pattern needs frames of at least 2 x 2, got {self.height} x {width}")
-        self.pattern, self.black, self.gains, self.gain_q, self.tone = (getattr(self._proto, k) for k in ("pattern", "black", "gains", "gain_q", "tone"))
 
     def _row_elements(self, p: int) -> int:
         return -(-p * self.depth // 8) if self.packing == "pfnc" else 5 * (-(-p // 4)) if self.depth == 10 else 3 * (-(-p // 2))
 
     def _with(self, data, x0, width) -> "PackedRawFrames":
-        return PackedRawFrames(data, width, depth=self.depth, packing=self.packing, x0=x0, _proto=self._proto)
+        return PackedRawFrames(data, width, depth=self.depth, packing=self.packing, x0=x0, _format=self._format)
 
     def split_side_by_side(self):
         """(left, right): the two halves of frames that pack both views side by side -- the same surface with two ``x0``.  The packed width must
@@ -752,11 +823,20 @@ class PackedRawFrames(_PackedFrames):
 
     def same_format(self, other: "PackedRawFrames") -> bool:
         """Both hold one packing of one depth, under one pattern, with one black level, white balance and tone curve."""
-        return self.packing == other.packing and self._proto.same_format(other._proto)
+        return self.packing == other.packing and self._format.same_format(other._format)
+
+    def format_fault(self, other: "PackedRawFrames") -> Optional[str]:
+        if self.same_format(other):
+            return None
+        return ("the views differ in packing, depth, pattern, black level, gains or tone curve: "
+                f"{(self.packing, self.depth, self.pattern, self.black, self.gains)} and {(other.packing, other.depth, other.pattern, other.black, other.gains)}")
 
     def format_struct(self) -> L.RawPackedFormat:
         """The ``ppms_raw_packed_format`` of these frames."""
         return L.RawPackedFormat(_RAW_PACKINGS[self.packing], self.depth, _RAW_PATTERNS[self.pattern], self.black, self.gain_q, _RAW_SHIFT, (0, 0, 0, 0))
+
+    def _structs(self):
+        return (self.format_struct(),)
 
     def unpack(self) -> RawFrames:
         """The ``RawFrames`` holding the same samples (uint16, bits at the bottom), in torch integer ops: the definition of the format on this
@@ -770,7 +850,7 @@ class PackedRawFrames(_PackedFrames):
             s = row[:, :, 5 * (p >> 2) + (p & 3)] << 2 | (row[:, :, 5 * (p >> 2) + 4] >> (2 * (p & 3))) & 3
         else:
             s = row[:, :, 3 * (p >> 1) + (p & 1)] << 4 | (row[:, :, 3 * (p >> 1) + 2] >> (4 * (p & 1))) & 15
-        return self._proto._like(s.to(torch.uint16))
+        return RawFrames(s.to(torch.uint16), depth=self.depth, _format=self._format)        # (one format: the unpacked frames share tone and table)
 
     @classmethod
     def pack(cls, frames: RawFrames, packing: str = "mipi") -> "PackedRawFrames":
@@ -787,18 +867,7 @@ class PackedRawFrames(_PackedFrames):
         else:
             low = sum((s[..., k] & ((1 << (depth - 8)) - 1)) << ((depth - 8) * k) for k in range(pixels))
             data = torch.cat([s >> (depth - 8), low[..., None]], dim=-1).flatten(2)
-        proto = RawFrames(torch.zeros((1, 2, 2), dtype=torch.uint16), frames.pattern, depth, "lsb", frames.black, frames.gains, frames.tone)
-        return cls(data.to(torch.uint8), frames.width, depth=depth, packing=packing, _proto=proto)
-
-    def tone_on(self, device) -> Optional[torch.Tensor]:
-        return self._proto.tone_on(device)
-
-    def levels_to_float(self, levels: torch.Tensor) -> torch.Tensor:
-        return self._proto.levels_to_float(levels)
-
-    def table(self, device) -> torch.Tensor:
-        """``RawFrames.table``: the frames' own level table on ``device``, built once and shared by every slice, half and copy."""
-        return self._proto.table(device)
+        return cls(data.to(torch.uint8), frames.width, frames.pattern, depth, packing, frames.black, frames.gains, frames.tone)
 
 
 class PackedRawStereoVideo(_StereoVideo):
@@ -806,12 +875,6 @@ class PackedRawStereoVideo(_StereoVideo):
     ``PackedRawFrames`` of one size, frame count, device, packing, depth, pattern, black level, white balance and tone curve.  ``len()``, slicing
     by frame range, ``to(device)`` (the packed bytes: 1.25 per pixel and view at depth 10, 1.5 at depth 12)."""
     _views = PackedRawFrames
-
-    def _format_fault(self, left: PackedRawFrames, right: PackedRawFrames) -> Optional[str]:
-        if left.same_format(right):
-            return None
-        return ("the views differ in packing, depth, pattern, black level, gains or tone curve: "
-                f"{(left.packing, left.depth, left.pattern, left.black, left.gains)} and {(right.packing, right.depth, right.pattern, right.black, right.gains)}")
 
 
 _BORDERS = {"replicate": L.BORDER_REPLICATE, "constant": L.BORDER_CONSTANT}
@@ -888,9 +951,7 @@ class RectifyMap:
 
     def to(self, device) -> "RectifyMap":
         """This map on ``device`` (6 bytes per rectified pixel, dense); made once per device and kept."""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
+        device = _moved_to(device)
         if device not in self._on:
             there = RectifyMap(self.xy.to(device).contiguous(), self.frac.to(device).contiguous(), (self.source_height, self.source_width), self.border,
                                self.fill, _checked=True)
@@ -1047,45 +1108,21 @@ class _RGBBytes(_ByteSource):
         return left.float(), right.float()
 
 
-class _YUVPlanes(_ByteSource):
-    """A YUVStereoVideo: ppms_video_ingest_yuv420 (8-bit 4:2:0) or ppms_video_ingest_yuv (every other depth and subsampling, with the level table
-    of that depth) converts the planes as the decoder left them."""
+class _FramePlanes(_ByteSource):
+    """A stereo video of one of the frame classes: the launch is what the frames say about their door -- ``_entry`` converts the planes or packed
+    rows as the decoder, camera or driver left them, reading the two ``view_struct()``s and the frames' ``_structs()``, with the frames' own level
+    table (``level_lut``'s of their depth, or a raw format's tone curve)."""
 
-    def __init__(self, video: YUVStereoVideo, rectify: Optional[StereoRectifier] = None):
-        self._generic = (video.left.depth, video.left.chroma) != (8, "420")
-        super().__init__("ppms_video_ingest_yuv" if self._generic else "ppms_video_ingest_yuv420", len(video), (video.height, video.width),
-                         video.left.device, rectify, depth=video.left.depth)
+    def __init__(self, video: _StereoVideo, rectify: Optional[StereoRectifier] = None):
+        super().__init__(video.left._entry, len(video), (video.height, video.width), video.left.device, rectify, depth=video.depth)
         self.video = video
 
     def _frames(self):
         v = self.video
-        frames = v.left.view_struct(), v.right.view_struct(), v.left.matrix()    # host structs: read before the call returns
-        return frames + (v.left.format_struct(),) if self._generic else frames
+        return (v.left.view_struct(), v.right.view_struct(), *v.left._structs())      # host structs: read before the call returns
 
     def _planes(self):
-        v = self.video
-        return v.left.y, v.left.u, v.left.v, v.right.y, v.right.u, v.right.v
-
-    def float_views(self):
-        rgb = self.video.left.to_rgb(), self.video.right.to_rgb()
-        left, right = rgb if self.rectify is None else self.rectify.apply_levels(*rgb, self.depth)
-        return _levels_to_float(left, self.depth), _levels_to_float(right, self.depth)
-
-
-class _RawPlanes(_ByteSource):
-    """A RawStereoVideo: ppms_video_ingest_raw demosaics, balances and looks up the samples as the camera driver left them; the level table is the
-    frames' own (their tone curve)."""
-
-    def __init__(self, video: RawStereoVideo, rectify: Optional[StereoRectifier] = None):
-        super().__init__("ppms_video_ingest_raw", len(video), (video.height, video.width), video.left.device, rectify, depth=video.depth)
-        self.video = video
-
-    def _frames(self):
-        v = self.video
-        return v.left.view_struct(), v.right.view_struct(), v.left.format_struct()      # host structs: read before the call returns
-
-    def _planes(self):
-        return self.video.left.data, self.video.right.data
+        return self.video.left._tensors() + self.video.right._tensors()
 
     def _table(self) -> torch.Tensor:
         return self.video.left.table(self.device)
@@ -1094,53 +1131,7 @@ class _RawPlanes(_ByteSource):
         v = self.video
         rgb = v.left.to_rgb(), v.right.to_rgb()
         left, right = rgb if self.rectify is None else self.rectify.apply_levels(*rgb, self.depth)
-        return v.left.levels_to_float(left), v.right.levels_to_float(right)    # (the tone curve behind the blend, as in the kernel)
-
-
-class _PackedYUVPlanes(_ByteSource):
-    """A PackedYUVStereoVideo: ppms_video_ingest_yuv_packed fetches the three samples of a pixel out of the packed rows as the camera or capture
-    card left them; from there on it is ppms_video_ingest_yuv."""
-
-    def __init__(self, video: PackedYUVStereoVideo, rectify: Optional[StereoRectifier] = None):
-        super().__init__("ppms_video_ingest_yuv_packed", len(video), (video.height, video.width), video.left.device, rectify, depth=video.depth)
-        self.video = video
-
-    def _frames(self):
-        v = self.video
-        return v.left.view_struct(), v.right.view_struct(), v.left.matrix(), v.left.format_struct()       # host structs: read before the call returns
-
-    def _planes(self):
-        return self.video.left.data, self.video.right.data
-
-    def float_views(self):
-        rgb = self.video.left.to_rgb(), self.video.right.to_rgb()
-        left, right = rgb if self.rectify is None else self.rectify.apply_levels(*rgb, self.depth)
-        return _levels_to_float(left, self.depth), _levels_to_float(right, self.depth)
-
-
-class _PackedRawPlanes(_ByteSource):
-    """A PackedRawStereoVideo: ppms_video_ingest_raw_packed fetches every sample out of the packed rows as the camera driver left them; from there
-    on it is ppms_video_ingest_raw, with the frames' own level table."""
-
-    def __init__(self, video: PackedRawStereoVideo, rectify: Optional[StereoRectifier] = None):
-        super().__init__("ppms_video_ingest_raw_packed", len(video), (video.height, video.width), video.left.device, rectify, depth=video.depth)
-        self.video = video
-
-    def _frames(self):
-        v = self.video
-        return v.left.view_struct(), v.right.view_struct(), v.left.format_struct()      # host structs: read before the call returns
-
-    def _planes(self):
-        return self.video.left.data, self.video.right.data
-
-    def _table(self) -> torch.Tensor:
-        return self.video.left.table(self.device)
-
-    def float_views(self):
-        v = self.video
-        rgb = v.left.to_rgb(), v.right.to_rgb()
-        left, right = rgb if self.rectify is None else self.rectify.apply_levels(*rgb, self.depth)
-        return v.left.levels_to_float(left), v.right.levels_to_float(right)    # (the tone curve behind the blend, as in the kernel)
+        return v.left.levels_to_float(left), v.right.levels_to_float(right)    # (a tone curve behind the blend, as in the kernel)
 
 
 def _checked_rectifier(who: str, rectify, device, h: int, w: int) -> StereoRectifier:
@@ -1159,8 +1150,8 @@ def stereo_source(who: str, left, right=None, rectify: Optional[StereoRectifier]
     (ValueError); two views of different classes are none either (TypeError)."""
     if rectify is not None and not isinstance(rectify, StereoRectifier):
         raise TypeError(f"{who}: rectify must be a StereoRectifier, got {type(rectify).__name__}")
-    for frames, video, source in ((YUVFrames, YUVStereoVideo, _YUVPlanes), (RawFrames, RawStereoVideo, _RawPlanes),
-                                  (PackedYUVFrames, PackedYUVStereoVideo, _PackedYUVPlanes), (PackedRawFrames, PackedRawStereoVideo, _PackedRawPlanes)):
+    for frames, video in ((YUVFrames, YUVStereoVideo), (RawFrames, RawStereoVideo), (PackedYUVFrames, PackedYUVStereoVideo),
+                          (PackedRawFrames, PackedRawStereoVideo)):
         if isinstance(left, frames) or isinstance(right, frames):
             if not (isinstance(left, frames) and isinstance(right, frames)):
                 raise TypeError(f"{who}: image1 is {type(left).__name__} and image2 is {type(right).__name__}; both views must be {frames.__name__} or both tensors")
@@ -1168,7 +1159,7 @@ def stereo_source(who: str, left, right=None, rectify: Optional[StereoRectifier]
         if isinstance(left, video):
             if rectify is not None:
                 rectify = _checked_rectifier(who, rectify, left.left.device, left.height, left.width)
-            return source(left, rectify)
+            return _FramePlanes(left, rectify)
     views = (left,) if right is None else (left, right)
     for v in views:
         if not torch.is_tensor(v):

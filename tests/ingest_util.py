@@ -28,6 +28,47 @@ def header_args(name):
     return [" ".join(a.split()) for a in m.group(1).split(",")]
 
 
+# ---- the ABI of the 12 entry points and the 5 size exports, as include/ppms.h states it -----------------------------------------------------------
+_VIEWS = {"yuv": "const ppms_yuv_view*", "raw": "const ppms_raw_view*", "packed": "const ppms_packed_view*"}
+_head = lambda view, *rest: [f"{_VIEWS[view]} left", f"{_VIEWS[view]} right", *rest]
+HEADS = {"u8": ["const uint8_t* left", "const uint8_t* right", "int64_t frame_stride"],
+         "yuv420": _head("yuv", "const ppms_yuv_matrix* m"),
+         "yuv": _head("yuv", "const ppms_yuv_matrix* m", "const ppms_yuv_format* fmt"),
+         "raw": _head("raw", "const ppms_raw_format* fmt"),
+         "yuv_packed": _head("packed", "const ppms_yuv_matrix* m", "const ppms_yuv_packed_format* fmt"),
+         "raw_packed": _head("packed", "const ppms_raw_packed_format* fmt")}
+MAPS = ["const ppms_remap_view* lmap", "const ppms_remap_view* rmap"]
+TAIL = ["int N", "int H0", "int W0", "int pad_left", "int pad_top", "int H", "int W", "const float* lut", "ppms_sp dst_fnet", "ppms_sp dst_cnet", "void* stream"]
+ENTRY_ARGS = {"ppms_video_ingest_" + door + "_remap" * twin: head + MAPS * twin + TAIL for door, head in HEADS.items() for twin in (0, 1)}
+# size export: (its arguments, the ctypes structs it measures, their sizes)
+SIZE_EXPORTS = {"ppms_yuv_struct_sizes": (["int* view", "int* matrix"], ("YUVView", "YUVMatrix"), (56, 32)),
+                "ppms_yuv_format_struct_size": (["int* fmt"], ("YUVFormat",), (32,)),
+                "ppms_remap_struct_size": (["int* view"], ("RemapView",), (40,)),
+                "ppms_raw_struct_sizes": (["int* view", "int* format"], ("RawView", "RawFormat"), (24, 48)),
+                "ppms_packed_struct_sizes": (["int* view", "int* yuv_format", "int* raw_format"], ("PackedView", "YUVPackedFormat", "RawPackedFormat"), (24, 32, 48))}
+# struct: (its fields in the header's order, the offsets of those behind the first 64-bit member or array)
+FIELDS = {"YUVView": (["y", "u", "v", "frame_stride_y", "frame_stride_c", "pitch_y", "pitch_c", "step_c", "reserved"], {}),
+          "YUVMatrix": (["y_off", "cy", "crv", "cgu", "cgv", "cbu", "shift", "reserved"], {}),
+          "YUVFormat": (["sample_bytes", "depth", "lsb", "sub_x", "sub_y", "reserved"], {}),
+          "RemapView": (["xy", "frac", "pitch", "hs", "ws", "border", "fill", "reserved"], {}),
+          "RawView": (["data", "frame_stride", "pitch", "reserved"], dict(frame_stride=8, pitch=16, reserved=20)),
+          "RawFormat": (["sample_bytes", "depth", "lsb", "pattern", "black", "gain", "shift", "reserved"], dict(gain=20, shift=32, reserved=36)),
+          "PackedView": (["data", "frame_stride", "pitch", "x0"], dict(frame_stride=8, pitch=16, x0=20)),
+          "YUVPackedFormat": (["container", "depth", "lsb", "order", "reserved"], dict(reserved=16)),
+          "RawPackedFormat": (["packing", "depth", "pattern", "black", "gain", "shift", "reserved"], dict(gain=16, shift=28, reserved=32))}
+
+
+def ctype_of(arg):
+    """The ctypes type that binds the header's argument `arg` ("const ppms_raw_view* left")."""
+    from ppmstereo_amd import _lib as L
+    struct = {"yuv_view": L.YUVView, "yuv_matrix": L.YUVMatrix, "yuv_format": L.YUVFormat, "raw_view": L.RawView, "raw_format": L.RawFormat,
+              "packed_view": L.PackedView, "yuv_packed_format": L.YUVPackedFormat, "raw_packed_format": L.RawPackedFormat, "remap_view": L.RemapView}
+    plain = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "ppms_sp": L.SP, "const float*": ctypes.c_void_p, "const uint8_t*": ctypes.c_void_p,
+             "void*": ctypes.c_void_p, "int*": ctypes.POINTER(ctypes.c_int)}
+    plain.update({f"const ppms_{k}*": ctypes.POINTER(v) for k, v in struct.items()})
+    return plain[arg.rsplit(" ", 1)[0]]
+
+
 # ---- calls on fake pointers: pointers into device memory are never dereferenced on the host, every check comes before the launch --------------
 def yuv_view(y, u, v, fsy, fsc, pitch_y, pitch_c, step_c, reserved=0):
     from ppmstereo_amd import _lib as L
@@ -37,6 +78,11 @@ def yuv_view(y, u, v, fsy, fsc, pitch_y, pitch_c, step_c, reserved=0):
 def raw_view(data, fs, pitch, reserved=0):
     from ppmstereo_amd import _lib as L
     return L.RawView(data or None, fs, pitch, reserved)
+
+
+def packed_view(data=0x100000, fs=37 * 256, pitch=256, x0=0):
+    from ppmstereo_amd import _lib as L
+    return L.PackedView(data or None, fs, pitch, x0)
 
 
 def remap_view(xy=0x400000, frac=0x500000, pitch=50, hs=37, ws=50, border=0, fill=0, reserved=0):
@@ -51,6 +97,38 @@ def call(lib, entry, head, maps=(), null=(), null_maps=(), N=2, H0=37, W0=50, pa
     ref = lambda xs, nulls: [None if i in nulls else (ctypes.byref(x) if isinstance(x, ctypes.Structure) else x) for i, x in enumerate(xs)]
     sp = lambda on, c: L.SP(0x10000 if on else None, 0x20000 if on else None, c, c)
     return getattr(lib, entry)(*ref(head, null), *ref(maps, null_maps), N, H0, W0, pad_left, pad_top, H, W, lut or None, sp(fnet, 32), sp(cnet, 64), None)
+
+
+def call_twin(lib, entry, head, null=(), lmap=None, rmap=None, null_rmap=False, **geometry):
+    """`call` of `entry` -- or, with lmap / rmap (dicts: fields of remap_view over border = 1) or null_rmap, of its _remap twin."""
+    if lmap is None and rmap is None and not null_rmap:
+        return call(lib, entry, head, null=null, **geometry)
+    maps = [remap_view(**{"border": 1, **(m or {})}) for m in (lmap, rmap)]
+    return call(lib, entry + "_remap", head, maps, null=null, null_maps=(1,) if null_rmap else (), **geometry)
+
+
+def sized_maps(bad):
+    """lmap / rmap of the _remap twin whose source frame is the case's own H0 x W0."""
+    m = dict(hs=bad.get("H0", 37), ws=bad.get("W0", 50))
+    return dict(lmap=m, rmap=m)
+
+
+def not_about_the_maps(bad):
+    """The case names no map, and its frame is one a map can name as its source frame (hs, ws >= 1)."""
+    return not {"lmap", "rmap", "null_rmap"} & set(bad) and bad.get("H0", 1) >= 1 and bad.get("W0", 1) >= 1
+
+
+def one_message(lib, door, plain, twin, bad):
+    """The rule of the doors: whatever is wrong with a call that is not about the maps, the plain entry and its _remap twin refuse it with one code
+    and one message.  The twin reads its frames' size from the maps and calls it hs x ws, the frames "source" frames: the only words that may differ."""
+    said = []
+    for entry in (plain, twin):
+        lib.ppms_mem_attn_splits(3, 3, 256, 1)                  # (a successful call in between: the message below is this call's)
+        assert entry(lib, **bad) == EINVAL, bad
+        said.append(lib.ppms_last_error().decode())
+    (name, text), (twin_name, twin_text) = (m.split(": ", 1) for m in said)
+    assert twin_name == name + "_remap" and name == "video_ingest_" + door
+    assert re.sub(r"\bws\b", "W0", re.sub(r"\bhs\b", "H0", twin_text)).replace("a source frame's", "a frame's") == text, said
 
 
 def refused(lib, rc, *about):
@@ -180,6 +258,19 @@ def ingest_raw(left, right, pad_left, pad_top, H, Wd, fview, cview, maps=None):
     assert lut.numel() == 1 << left.depth and lut.is_cuda and lut.dtype == torch.float32
     head = left.view_struct(), right.view_struct(), left.format_struct()
     return ingest_door("raw", head, maps, left.n, (left.height, left.width), pad_left, pad_top, H, Wd, lut, fview, cview)
+
+
+def ingest_packed(left, right, pad_left, pad_top, H, Wd, fview, cview, maps=None):
+    """The packed door of two PackedYUVFrames or two PackedRawFrames of one format."""
+    from ppmstereo_amd.ppmstereo import PackedRawFrames, level_lut
+    if isinstance(left, PackedRawFrames):
+        assert left.same_format(right)
+        entry, head, lut = "raw_packed", (left.view_struct(), right.view_struct(), left.format_struct()), left.table(DEV)
+    else:
+        assert (left.layout, left.lsb) == (right.layout, right.lsb)
+        entry, head, lut = "yuv_packed", (left.view_struct(), right.view_struct(), left.matrix(), left.format_struct()), level_lut(DEV, left.depth)
+    assert lut.numel() == 1 << left.depth
+    return ingest_door(entry, head, maps, left.n, (left.height, left.width), pad_left, pad_top, H, Wd, lut, fview, cview)
 
 
 def rotated_map(H0, W0, hs, ws, angle, scale, border, fill):

@@ -8,7 +8,7 @@ import torch
 
 from ppmstereo_amd.ppmstereo import (OutputSpec, PackedRawFrames, PackedRawStereoVideo, PackedYUVFrames, PackedYUVStereoVideo, RawFrames, RawStereoVideo,
                                      YUVFrames, YUVStereoVideo)
-from ingest_util import DEV, bits, fresh, ingest_deep, ingest_door, ingest_raw, model, rotated_map, same  # noqa: F401  (model: the fixture)
+from ingest_util import DEV, bits, fresh, ingest_deep, ingest_packed, ingest_raw, model, rotated_map, same  # noqa: F401  (model: the fixture)
 from test_gpu_ingest_remap import smooth_rectifier
 from test_ingest_packed import LAYOUTS, PATTERNS, RAW_FORMATS, YUV_FORMATS, packed_raw, packed_yuv
 
@@ -32,19 +32,6 @@ def raw_pair(packing, depth, pattern, N, H, W, x0, P, seed, junk_seed=None, **kw
     data, S = packed_raw(packing, depth, N, H, P, 7, seed, junk_seed)
     plane = torch.from_numpy(S[:, :, x0:x0 + W]).to(torch.int32).to(torch.uint16).contiguous().to(DEV)
     return PackedRawFrames(data.to(DEV), W, pattern, depth, packing, x0=x0, **kw), RawFrames(plane, pattern, depth, "lsb", **kw)
-
-
-def ingest_packed(left, right, pad_left, pad_top, H, Wd, fview, cview, maps=None):
-    """The packed door of two PackedYUVFrames or two PackedRawFrames of one format."""
-    from ppmstereo_amd.ppmstereo import level_lut
-    if isinstance(left, PackedRawFrames):
-        assert left.same_format(right)
-        entry, head, lut = "raw_packed", (left.view_struct(), right.view_struct(), left.format_struct()), left.table(DEV)
-    else:
-        assert (left.layout, left.lsb) == (right.layout, right.lsb)
-        entry, head, lut = "yuv_packed", (left.view_struct(), right.view_struct(), left.matrix(), left.format_struct()), level_lut(DEV, left.depth)
-    assert lut.numel() == 1 << left.depth
-    return ingest_door(entry, head, maps, left.n, (left.height, left.width), pad_left, pad_top, H, Wd, lut, fview, cview)
 
 
 def door_equals_door(packed, planar, pad=(7, 13), size=(64, 64), maps=None):

@@ -1,66 +1,24 @@
 """CPU: the packed front doors (YUYV / UYVY / YVYU / VYUY, Y210 / Y212, v210; MIPI CSI-2 RAW10 / RAW12 and PFNC 10p / 12p).  The four
-ppms_video_ingest_*_packed entry points are part of the C ABI, their ctypes bindings have the header's argument lists and struct sizes, and they
-refuse bad arguments before touching a device, a plain entry and its _remap twin with one message; ``unpack()`` of the frame classes gives the
+ppms_video_ingest_*_packed entry points refuse bad arguments before touching a device, a plain entry and its _remap twin with one message (their
+ABI: tests/test_ingest_doors.py); ``unpack()`` of the frame classes gives the
 samples that were packed -- by this file's own packer, which writes every row as a list of (value, bits) fields into one Python integer, and by
 literal vectors written out by hand; stereo_source dispatches packed frames without a device.  No device compute."""
 import ctypes
 import functools
-import re
 
 import numpy as np
 import pytest
 import torch
 
-from ingest_util import EINVAL, call, header_args, lib, remap_view  # noqa: F401  (lib: the fixture)
+from ingest_util import EINVAL, call_twin, lib, not_about_the_maps, one_message, packed_view, sized_maps  # noqa: F401  (lib: the fixture)
 
 YUV, YUV_REMAP = "ppms_video_ingest_yuv_packed", "ppms_video_ingest_yuv_packed_remap"
 RAW, RAW_REMAP = "ppms_video_ingest_raw_packed", "ppms_video_ingest_raw_packed_remap"
-SIZES = "ppms_packed_struct_sizes"
 LAYOUTS = {"yuyv": (8, "YUYV"), "uyvy": (8, "UYVY"), "yvyu": (8, "YVYU"), "vyuy": (8, "VYUY"), "y210": (10, "YUYV"), "y212": (12, "YUYV"),
            "v210": (10, "UYVY")}                                       # layout: (depth, the four components of a pixel pair in memory order)
 YUV_FORMATS = [(l, "msb") for l in LAYOUTS] + [("y210", "lsb"), ("y212", "lsb")]
 RAW_FORMATS = [(p, d) for p in ("mipi", "pfnc") for d in (10, 12)]
 PATTERNS = ["rggb", "bggr", "grbg", "gbrg", "mono"]
-
-
-# ---- the ABI -------------------------------------------------------------------------------------------------------------------------------
-def test_declared_exported_and_abi_version_unchanged(lib):
-    from ppmstereo_amd import _lib as L
-    for name in (YUV, YUV_REMAP, RAW, RAW_REMAP, SIZES):
-        assert header_args(name)
-        assert name in L.EXPORTS and hasattr(lib, name)
-    assert lib.ppms_version() == 4
-
-
-def test_bindings_match_the_header(lib):
-    from ppmstereo_amd import _lib as L
-    view = ["const ppms_packed_view* left", "const ppms_packed_view* right"]
-    maps = ["const ppms_remap_view* lmap", "const ppms_remap_view* rmap"]
-    tail = ["int N", "int H0", "int W0", "int pad_left", "int pad_top", "int H", "int W", "const float* lut", "ppms_sp dst_fnet", "ppms_sp dst_cnet",
-            "void* stream"]
-    yuv = view + ["const ppms_yuv_matrix* m", "const ppms_yuv_packed_format* fmt"]
-    raw = view + ["const ppms_raw_packed_format* fmt"]
-    assert header_args(YUV) == yuv + tail and header_args(YUV_REMAP) == yuv + maps + tail
-    assert header_args(RAW) == raw + tail and header_args(RAW_REMAP) == raw + maps + tail
-    ctype = {"int": ctypes.c_int, "ppms_sp": L.SP, "const ppms_packed_view*": ctypes.POINTER(L.PackedView), "const ppms_yuv_matrix*": ctypes.POINTER(L.YUVMatrix),
-             "const ppms_yuv_packed_format*": ctypes.POINTER(L.YUVPackedFormat), "const ppms_raw_packed_format*": ctypes.POINTER(L.RawPackedFormat),
-             "const ppms_remap_view*": ctypes.POINTER(L.RemapView), "const float*": ctypes.c_void_p, "void*": ctypes.c_void_p}
-    for name in (YUV, YUV_REMAP, RAW, RAW_REMAP):
-        res, bound = L._SIGS[name]
-        assert res is ctypes.c_int and bound == [ctype[a.rsplit(" ", 1)[0]] for a in header_args(name)]
-    assert header_args(SIZES) == ["int* view", "int* yuv_format", "int* raw_format"]
-    a, b, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    assert lib.ppms_packed_struct_sizes(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)) == 0
-    assert (a.value, b.value, c.value) == (ctypes.sizeof(L.PackedView), ctypes.sizeof(L.YUVPackedFormat), ctypes.sizeof(L.RawPackedFormat)) == (24, 32, 48)
-    assert lib.ppms_packed_struct_sizes(None, None, None) == 0
-    # the fields, in the header's order
-    assert [n for n, _ in L.PackedView._fields_] == ["data", "frame_stride", "pitch", "x0"]
-    assert (L.PackedView.frame_stride.offset, L.PackedView.pitch.offset, L.PackedView.x0.offset) == (8, 16, 20)
-    assert [n for n, _ in L.YUVPackedFormat._fields_] == ["container", "depth", "lsb", "order", "reserved"] and L.YUVPackedFormat.reserved.offset == 16
-    assert [n for n, _ in L.RawPackedFormat._fields_] == ["packing", "depth", "pattern", "black", "gain", "shift", "reserved"]
-    assert (L.RawPackedFormat.gain.offset, L.RawPackedFormat.shift.offset, L.RawPackedFormat.reserved.offset) == (16, 28, 32)
-    # (additive: the unpacked doors' structs keep their sizes)
-    assert (ctypes.sizeof(L.YUVView), ctypes.sizeof(L.YUVMatrix), ctypes.sizeof(L.YUVFormat), ctypes.sizeof(L.RawView), ctypes.sizeof(L.RawFormat)) == (56, 32, 32, 24, 48)
 
 
 # ---- this file's packer: a row is a list of (value, bits) fields, lowest bit first, summed into one Python integer ------------------------------
@@ -376,20 +334,6 @@ def test_stereo_source_routes_packed_frames_without_a_device():
 
 
 # ---- argument refusal through the C ABI: frames of 37 x 50, two of them, padded to 64 x 64 ------------------------------------------------------
-def packed_view(data=0x100000, fs=37 * 256, pitch=256, x0=0):
-    from ppmstereo_amd import _lib as L
-    return L.PackedView(data or None, fs, pitch, x0)
-
-
-_map = functools.partial(remap_view, border=1)
-
-
-def _finish(lib, names, head, null, lmap, rmap, null_rmap, geometry):
-    if lmap is None and rmap is None and not null_rmap:
-        return call(lib, names[0], head, null=null, **geometry)
-    return call(lib, names[1], head, [_map(**(lmap or {})), _map(**(rmap or {}))], null=null, null_maps=(1,) if null_rmap else (), **geometry)
-
-
 def yuv_call(lib, left=None, right=None, fmt=None, mat=None, null=(), lmap=None, rmap=None, null_rmap=False, **geometry):
     """Y210 frames (row: 8 * 25 = 200 bytes) in surfaces of pitch 256.  geometry: ingest_util.call's.  lmap / rmap (dicts): the _remap twin."""
     from ppmstereo_amd import _lib as L
@@ -398,7 +342,7 @@ def yuv_call(lib, left=None, right=None, fmt=None, mat=None, null=(), lmap=None,
     m = dict(y_off=64, cy=19131, crv=29454, cgu=3504, cgv=8755, cbu=34707, shift=14, reserved=0)
     m.update(mat or {})
     head = [packed_view(**(left or {})), packed_view(**(right or {})), L.YUVMatrix(**m), L.YUVPackedFormat(f["container"], f["depth"], f["lsb"], f["order"], f["reserved"])]
-    return _finish(lib, (YUV, YUV_REMAP), head, null, lmap, rmap, null_rmap, geometry)
+    return call_twin(lib, YUV, head, null, lmap, rmap, null_rmap, **geometry)
 
 
 def raw_call(lib, left=None, right=None, fmt=None, null=(), lmap=None, rmap=None, null_rmap=False, **geometry):
@@ -408,7 +352,7 @@ def raw_call(lib, left=None, right=None, fmt=None, null=(), lmap=None, rmap=None
     f.update(fmt or {})
     view = functools.partial(packed_view, data=0x100001, fs=37 * 80, pitch=80)
     head = [view(**(left or {})), view(**(right or {})), L.RawPackedFormat(f["packing"], f["depth"], f["pattern"], f["black"], f["gain"], f["shift"], f["reserved"])]
-    return _finish(lib, (RAW, RAW_REMAP), head, null, lmap, rmap, null_rmap, geometry)
+    return call_twin(lib, RAW, head, null, lmap, rmap, null_rmap, **geometry)
 
 
 OFF = dict(fnet=False, cnet=False)                                    # (a call that passes every check of its door gets as far as the destinations)
@@ -525,24 +469,14 @@ def test_bad_arguments_return_einval_with_a_message_and_no_device(lib, door, abo
     assert (b"video_ingest_" + door.encode() + b"_remap" in msg) == ("lmap" in bad or "rmap" in bad or "null_rmap" in bad), msg
 
 
-# not about the maps: the case names none, and its frame is one a map can name as its source frame (hs, ws >= 1)
-PARITY = [(door, bad) for door, _, bad in CASES if not {"lmap", "rmap", "null_rmap"} & set(bad) and bad.get("H0", 1) >= 1 and bad.get("W0", 1) >= 1]
+PARITY = [(door, bad) for door, _, bad in CASES if not_about_the_maps(bad)]
 
 
 @pytest.mark.parametrize("door,bad", PARITY, ids=[f"{d}:{i}:" + ",".join(f"{k}={v}" for k, v in b.items()) for i, (d, b) in enumerate(PARITY)])
 def test_plain_entry_and_remap_twin_refuse_with_one_message(lib, door, bad):
-    """The rule of tests/test_ingest_doors.py: whatever is wrong with a call that is not about the maps, both refuse it with one code and one
-    message; the twin reads its frames' size from the maps and calls it hs x ws."""
+    """The rule of tests/test_ingest_doors.py (ingest_util.one_message), on this file's two doors."""
     entry = DOORS[door][0]
-    m = dict(hs=bad.get("H0", 37), ws=bad.get("W0", 50))
-    said = []
-    for maps in ({}, dict(lmap=m, rmap=m)):
-        lib.ppms_mem_attn_splits(3, 3, 256, 1)
-        assert entry(lib, **bad, **maps) == EINVAL, bad
-        said.append(lib.ppms_last_error().decode())
-    (name, text), (twin_name, twin_text) = (s.split(": ", 1) for s in said)
-    assert twin_name == name + "_remap" and name == "video_ingest_" + door
-    assert re.sub(r"\bws\b", "W0", re.sub(r"\bhs\b", "H0", twin_text)) == text, said
+    one_message(lib, door, entry, lambda lib, **b: entry(lib, **b, **sized_maps(b)), bad)
 
 
 def test_destination_views_follow_img_s2d_contract(lib):

@@ -1,5 +1,5 @@
-"""CPU: the raw-sensor front door (Bayer mosaics and monochrome planes of 8, 10 or 12 bits).  ppms_video_ingest_raw and its _remap twin are part of
-the C ABI, their ctypes bindings have the header's argument lists and struct sizes, they refuse bad arguments before touching a device;
+"""CPU: the raw-sensor front door (Bayer mosaics and monochrome planes of 8, 10 or 12 bits).  ppms_video_ingest_raw and its _remap twin refuse bad
+arguments before touching a device (their ABI: tests/test_ingest_doors.py);
 RawFrames.to_rgb is the demosaic, black level and white balance the header states (against a per-pixel restatement in plain Python), RawFrames reads
 byte strides from views without copying, and stereo_source dispatches raw frames without a device.  No device compute."""
 import ctypes
@@ -9,50 +9,16 @@ import itertools
 import pytest
 import torch
 
-from ingest_util import EINVAL, call, header_args, lib, rand_u8, rand_u16, raw_view, remap_view  # noqa: F401  (lib: the fixture)
+from ingest_util import EINVAL, call_twin, lib, rand_u8, rand_u16, raw_view  # noqa: F401  (lib: the fixture)
 
-NAME, REMAP, SIZES = "ppms_video_ingest_raw", "ppms_video_ingest_raw_remap", "ppms_raw_struct_sizes"
+NAME, REMAP = "ppms_video_ingest_raw", "ppms_video_ingest_raw_remap"
 PATTERNS = ["rggb", "bggr", "grbg", "gbrg", "mono"]
 COLOURS = PATTERNS[:4]
 FORMATS = [(8, "lsb"), (10, "lsb"), (10, "msb"), (12, "lsb"), (12, "msb")]            # (depth, align)
 
 
-# ---- the ABI -------------------------------------------------------------------------------------------------------------------------------
-def test_declared_exported_and_abi_version_unchanged(lib):
-    from ppmstereo_amd import _lib as L
-    for name in (NAME, REMAP, SIZES):
-        assert header_args(name)
-        assert name in L.EXPORTS and hasattr(lib, name)
-    assert lib.ppms_version() == 4
-
-
-def test_bindings_match_the_header(lib):
-    from ppmstereo_amd import _lib as L
-    head = ["const ppms_raw_view* left", "const ppms_raw_view* right", "const ppms_raw_format* fmt"]
-    tail = ["int N", "int H0", "int W0", "int pad_left", "int pad_top", "int H", "int W", "const float* lut", "ppms_sp dst_fnet", "ppms_sp dst_cnet",
-            "void* stream"]
-    assert header_args(NAME) == head + tail
-    assert header_args(REMAP) == head + ["const ppms_remap_view* lmap", "const ppms_remap_view* rmap"] + tail
-    ctype = {"int": ctypes.c_int, "ppms_sp": L.SP, "const ppms_raw_view*": ctypes.POINTER(L.RawView), "const ppms_raw_format*": ctypes.POINTER(L.RawFormat),
-             "const ppms_remap_view*": ctypes.POINTER(L.RemapView), "const float*": ctypes.c_void_p, "void*": ctypes.c_void_p}
-    for name in (NAME, REMAP):
-        res, bound = L._SIGS[name]
-        assert res is ctypes.c_int and bound == [ctype[a.rsplit(" ", 1)[0]] for a in header_args(name)]
-    assert header_args(SIZES) == ["int* view", "int* format"]
-    a, b = ctypes.c_int(), ctypes.c_int()
-    assert lib.ppms_raw_struct_sizes(ctypes.byref(a), ctypes.byref(b)) == 0
-    assert (a.value, b.value) == (ctypes.sizeof(L.RawView), ctypes.sizeof(L.RawFormat)) == (24, 48)
-    assert lib.ppms_raw_struct_sizes(None, None) == 0
-    # the fields, in the header's order
-    assert [n for n, _ in L.RawView._fields_] == ["data", "frame_stride", "pitch", "reserved"]
-    assert [n for n, _ in L.RawFormat._fields_] == ["sample_bytes", "depth", "lsb", "pattern", "black", "gain", "shift", "reserved"]
-    assert (L.RawFormat.gain.offset, L.RawFormat.shift.offset, L.RawFormat.reserved.offset) == (20, 32, 36)
-    assert (L.RawView.frame_stride.offset, L.RawView.pitch.offset, L.RawView.reserved.offset) == (8, 16, 20)
-
-
 # ---- argument refusal: BayerRG10 frames (bits at the top) of 37 x 50 in surfaces of pitch 128 bytes, two frames, padded to 64 x 64 ---------------
 _view = functools.partial(raw_view, data=0x100000, fs=37 * 128, pitch=128)
-_map = functools.partial(remap_view, border=1)
 
 
 def _call(lib, left=None, right=None, fmt=None, null=(), lmap=None, rmap=None, null_rmap=False, **geometry):
@@ -62,9 +28,7 @@ def _call(lib, left=None, right=None, fmt=None, null=(), lmap=None, rmap=None, n
     f.update(fmt or {})
     head = [_view(**(left or {})), _view(**(right or {})),
             L.RawFormat(f["sample_bytes"], f["depth"], f["lsb"], f["pattern"], f["black"], f["gain"], f["shift"], f["reserved"])]
-    if lmap is None and rmap is None and not null_rmap:
-        return call(lib, NAME, head, null=null, **geometry)
-    return call(lib, REMAP, head, [_map(**(lmap or {})), _map(**(rmap or {}))], null=null, null_maps=(1,) if null_rmap else (), **geometry)
+    return call_twin(lib, NAME, head, null, lmap, rmap, null_rmap, **geometry)
 
 
 BYTES = dict(sample_bytes=1, depth=8, lsb=0)                          # (with the 16-bit views' strides, which are large enough for bytes too)

@@ -1,44 +1,16 @@
 """CPU: rectification inside the ingest kernel.  ppms_video_ingest_u8_remap / ppms_video_ingest_yuv420_remap (raw frames of an unrectified rig
-+ one fixed-point map per view -> the first-layer operands of both encoders) are part of the C ABI, their ctypes bindings have the header's
-argument lists and struct size, they refuse bad arguments before touching a device; RectifyMap quantises float maps as stated, reads pointers
++ one fixed-point map per view -> the first-layer operands of both encoders) refuse bad arguments before touching a device (their ABI:
+tests/test_ingest_doors.py); RectifyMap quantises float maps as stated, reads pointers
 and pitches from views without copying, and RectifyMap.apply_u8 is the arithmetic of include/ppms.h (against ingest_util.restated_remap).
 No device compute."""
-import ctypes
 import functools
 
 import pytest
 import torch
 
-from ingest_util import EINVAL, call, header_args, lib, rand_u8, remap_view, restated_remap, yuv_view  # noqa: F401  (lib: the fixture)
+from ingest_util import EINVAL, call, lib, rand_u8, remap_view, restated_remap, yuv_view  # noqa: F401  (lib: the fixture)
 
 NAMES = {"u8": "ppms_video_ingest_u8_remap", "yuv": "ppms_video_ingest_yuv420_remap"}
-
-
-def test_declared_exported_and_abi_version_unchanged(lib):
-    from ppmstereo_amd import _lib as L
-    for name in (*NAMES.values(), "ppms_remap_struct_size"):
-        assert header_args(name)
-        assert name in L.EXPORTS and hasattr(lib, name)
-    assert lib.ppms_version() == 4
-
-
-def test_binding_matches_the_header(lib):
-    from ppmstereo_amd import _lib as L
-    tail = ["const ppms_remap_view* lmap", "const ppms_remap_view* rmap", "int N", "int H0", "int W0", "int pad_left", "int pad_top", "int H", "int W",
-            "const float* lut", "ppms_sp dst_fnet", "ppms_sp dst_cnet", "void* stream"]
-    assert header_args(NAMES["u8"]) == ["const uint8_t* left", "const uint8_t* right", "int64_t frame_stride"] + tail
-    assert header_args(NAMES["yuv"]) == ["const ppms_yuv_view* left", "const ppms_yuv_view* right", "const ppms_yuv_matrix* m"] + tail
-    ctype = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "ppms_sp": L.SP, "const ppms_yuv_view*": ctypes.POINTER(L.YUVView),
-             "const ppms_yuv_matrix*": ctypes.POINTER(L.YUVMatrix), "const ppms_remap_view*": ctypes.POINTER(L.RemapView), "const float*": ctypes.c_void_p,
-             "const uint8_t*": ctypes.c_void_p, "void*": ctypes.c_void_p}
-    for name in NAMES.values():
-        res, bound = L._SIGS[name]
-        assert res is ctypes.c_int and bound == [ctype[a.rsplit(" ", 1)[0]] for a in header_args(name)]
-    assert header_args("ppms_remap_struct_size") == ["int* view"]
-    a = ctypes.c_int()
-    assert lib.ppms_remap_struct_size(ctypes.byref(a)) == 0
-    assert a.value == ctypes.sizeof(L.RemapView) == 40
-    assert [n for n, _ in L.RemapView._fields_] == ["xy", "frac", "pitch", "hs", "ws", "border", "fill", "reserved"]      # the header's order
 
 
 # ---- argument refusal: raw frames of 41 x 53, rectified 37 x 50 with map rows of pitch 56, two frames, padded to 64 x 64 -------------------

@@ -1,31 +1,11 @@
-"""CPU: ppms_video_ingest_u8 (uint8 video -> the first-layer operands of both encoders) is part of the C ABI, its ctypes binding has the
-header's argument list, it refuses bad arguments before touching a device, and the pad geometry handed to it is InputPadder's.  No compute."""
-import ctypes
-
+"""CPU: ppms_video_ingest_u8 (uint8 video -> the first-layer operands of both encoders) refuses bad arguments before touching a
+device (its ABI: tests/test_ingest_doors.py), and the pad geometry handed to it is InputPadder's.  No compute."""
 import pytest
 import torch
 
-from ingest_util import EINVAL, call, header_args, lib, remap_view  # noqa: F401  (lib: the fixture)
+from ingest_util import EINVAL, call, lib, remap_view  # noqa: F401  (lib: the fixture)
 
 NAME = "ppms_video_ingest_u8"
-
-
-def test_declared_exported_and_abi_version_unchanged(lib):
-    from ppmstereo_amd import _lib as L
-    assert header_args(NAME)
-    assert NAME in L.EXPORTS and hasattr(lib, NAME)
-    assert lib.ppms_version() == 4
-
-
-def test_binding_matches_the_header():
-    from ppmstereo_amd import _lib as L
-    args = header_args(NAME)
-    assert args == ["const uint8_t* left", "const uint8_t* right", "int64_t frame_stride", "int N", "int H0", "int W0", "int pad_left", "int pad_top",
-                    "int H", "int W", "const float* lut", "ppms_sp dst_fnet", "ppms_sp dst_cnet", "void* stream"]
-    ctype = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "ppms_sp": L.SP}
-    expect = [ctypes.c_void_p if "*" in a else ctype[a.rsplit(" ", 1)[0]] for a in args]
-    res, bound = L._SIGS[NAME]
-    assert res is ctypes.c_int and bound == expect
 
 
 def _call(lib, left=0x1000, right=0x2000, stride=3 * 37 * 50, twin=False, **geometry):

@@ -1,5 +1,5 @@
-"""CPU: the decoded-video front door.  ppms_video_ingest_yuv420 (NV12 / I420 frames -> the first-layer operands of both encoders) is part of
-the C ABI, its ctypes binding has the header's argument list and struct sizes, it refuses bad arguments before touching a device;
+"""CPU: the decoded-video front door.  ppms_video_ingest_yuv420 (NV12 / I420 frames -> the first-layer operands of both encoders)
+refuses bad arguments before touching a device (its ABI: tests/test_ingest_doors.py);
 yuv_matrix / YUVFrames.to_rgb_u8 are the conversion the header states (against float64), and YUVFrames / YUVStereoVideo read pointers and
 strides from views without copying.  No device compute."""
 import ctypes
@@ -9,36 +9,9 @@ import itertools
 import pytest
 import torch
 
-from ingest_util import EINVAL, call, header_args, lib, rand_u8, remap_view, yuv_view  # noqa: F401  (lib: the fixture)
+from ingest_util import EINVAL, call, lib, rand_u8, remap_view, yuv_view  # noqa: F401  (lib: the fixture)
 
 NAME = "ppms_video_ingest_yuv420"
-
-
-def test_declared_exported_and_abi_version_unchanged(lib):
-    from ppmstereo_amd import _lib as L
-    for name in (NAME, "ppms_yuv_struct_sizes"):
-        assert header_args(name)
-        assert name in L.EXPORTS and hasattr(lib, name)
-    assert lib.ppms_version() == 4
-
-
-def test_binding_matches_the_header(lib):
-    from ppmstereo_amd import _lib as L
-    args = header_args(NAME)
-    assert args == ["const ppms_yuv_view* left", "const ppms_yuv_view* right", "const ppms_yuv_matrix* m", "int N", "int H0", "int W0", "int pad_left",
-                    "int pad_top", "int H", "int W", "const float* lut", "ppms_sp dst_fnet", "ppms_sp dst_cnet", "void* stream"]
-    ctype = {"int": ctypes.c_int, "ppms_sp": L.SP, "const ppms_yuv_view*": ctypes.POINTER(L.YUVView), "const ppms_yuv_matrix*": ctypes.POINTER(L.YUVMatrix),
-             "const float*": ctypes.c_void_p, "void*": ctypes.c_void_p}
-    expect = [ctype[a.rsplit(" ", 1)[0]] for a in args]
-    res, bound = L._SIGS[NAME]
-    assert res is ctypes.c_int and bound == expect
-    assert header_args("ppms_yuv_struct_sizes") == ["int* view", "int* matrix"]
-    a, b = ctypes.c_int(), ctypes.c_int()
-    assert lib.ppms_yuv_struct_sizes(ctypes.byref(a), ctypes.byref(b)) == 0
-    assert (a.value, b.value) == (ctypes.sizeof(L.YUVView), ctypes.sizeof(L.YUVMatrix)) == (56, 32)
-    # the fields, in the header's order
-    assert [n for n, _ in L.YUVView._fields_] == ["y", "u", "v", "frame_stride_y", "frame_stride_c", "pitch_y", "pitch_c", "step_c", "reserved"]
-    assert [n for n, _ in L.YUVMatrix._fields_] == ["y_off", "cy", "crv", "cgu", "cgv", "cbu", "shift", "reserved"]
 
 
 # ---- argument refusal: NV12 frames of 37 x 50 (chroma 19 x 25) in surfaces of pitch 64, two frames, padded to 64 x 64 ----------------

@@ -1,5 +1,5 @@
-"""CPU: the decoded-video front door for 10- / 12-bit samples and 4:2:2 / 4:4:4 chroma.  ppms_video_ingest_yuv and its _remap twin are part of the
-C ABI, their ctypes bindings have the header's argument lists and struct size, they refuse bad arguments before touching a device; yuv_matrix(depth=)
+"""CPU: the decoded-video front door for 10- / 12-bit samples and 4:2:2 / 4:4:4 chroma.  ppms_video_ingest_yuv and its _remap twin refuse bad
+arguments before touching a device (their ABI: tests/test_ingest_doors.py); yuv_matrix(depth=)
 / YUVFrames.to_rgb are the conversion the header states (against float64), YUVFrames reads byte strides, alignment and subsampling from views
 without copying, and RectifyMap.apply_levels / level_fill are the remap on levels.  No device compute."""
 import ctypes
@@ -9,39 +9,10 @@ import itertools
 import pytest
 import torch
 
-from ingest_util import EINVAL, call, header_args, lib, rand_u8, rand_u16, remap_view, yuv_view  # noqa: F401  (lib: the fixture)
+from ingest_util import EINVAL, call_twin, lib, rand_u8, rand_u16, remap_view, yuv_view  # noqa: F401  (lib: the fixture)
 from test_ingest_yuv import COMBOS, STANDARDS
 
-NAME, REMAP, SIZE = "ppms_video_ingest_yuv", "ppms_video_ingest_yuv_remap", "ppms_yuv_format_struct_size"
-
-
-def test_declared_exported_and_abi_version_unchanged(lib):
-    from ppmstereo_amd import _lib as L
-    for name in (NAME, REMAP, SIZE):
-        assert header_args(name)
-        assert name in L.EXPORTS and hasattr(lib, name)
-    assert lib.ppms_version() == 4
-
-
-def test_bindings_match_the_header(lib):
-    from ppmstereo_amd import _lib as L
-    head = ["const ppms_yuv_view* left", "const ppms_yuv_view* right", "const ppms_yuv_matrix* m", "const ppms_yuv_format* fmt"]
-    tail = ["int N", "int H0", "int W0", "int pad_left", "int pad_top", "int H", "int W", "const float* lut", "ppms_sp dst_fnet", "ppms_sp dst_cnet",
-            "void* stream"]
-    assert header_args(NAME) == head + tail
-    assert header_args(REMAP) == head + ["const ppms_remap_view* lmap", "const ppms_remap_view* rmap"] + tail
-    ctype = {"int": ctypes.c_int, "ppms_sp": L.SP, "const ppms_yuv_view*": ctypes.POINTER(L.YUVView), "const ppms_yuv_matrix*": ctypes.POINTER(L.YUVMatrix),
-             "const ppms_yuv_format*": ctypes.POINTER(L.YUVFormat), "const ppms_remap_view*": ctypes.POINTER(L.RemapView), "const float*": ctypes.c_void_p,
-             "void*": ctypes.c_void_p}
-    for name in (NAME, REMAP):
-        res, bound = L._SIGS[name]
-        assert res is ctypes.c_int and bound == [ctype[a.rsplit(" ", 1)[0]] for a in header_args(name)]
-    assert header_args(SIZE) == ["int* fmt"]
-    a = ctypes.c_int()
-    assert lib.ppms_yuv_format_struct_size(ctypes.byref(a)) == 0
-    assert a.value == ctypes.sizeof(L.YUVFormat) == 32
-    assert [n for n, _ in L.YUVFormat._fields_] == ["sample_bytes", "depth", "lsb", "sub_x", "sub_y", "reserved"]      # the header's order
-    assert ctypes.sizeof(L.YUVView) == 56 and ctypes.sizeof(L.YUVMatrix) == 32                                           # (reused as they are)
+NAME, REMAP = "ppms_video_ingest_yuv", "ppms_video_ingest_yuv_remap"
 
 
 # ---- argument refusal: P010 frames of 37 x 50 (chroma 19 x 25 pairs) in surfaces of pitch 128 bytes, two frames, padded to 64 x 64 -----------
@@ -59,9 +30,7 @@ def _call(lib, left=None, right=None, fmt=None, null=(), lmap=None, rmap=None, *
     for k in [k for k in kw if hasattr(mat, k)]:
         setattr(mat, k, kw.pop(k))
     head = [_view(**(left or {})), _view(**(right or {})), mat, L.YUVFormat(f["sample_bytes"], f["depth"], f["lsb"], f["sub_x"], f["sub_y"], f["reserved"])]
-    if lmap is None and rmap is None:
-        return call(lib, NAME, head, null=null, **kw)
-    return call(lib, REMAP, head, [_map(**(lmap or {})), _map(**(rmap or {}))], null=null, **kw)
+    return call_twin(lib, NAME, head, null, lmap, rmap, **kw)
 
 
 BYTES = dict(sample_bytes=1, depth=8, lsb=0)                          # (with the P010 views' strides, which are large enough for bytes too)

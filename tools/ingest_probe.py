@@ -10,7 +10,8 @@
 
 --door: PPMStereo.forward_batch_test on one video through two ways in.  Side B is the door itself; side A is what a caller did before the door
 existed (DOORS below says it per door).  Config 2: T = 5, 320x512, iters = 10; whole-call ms (video -> host disparity) and a digest of the
-results, which must be equal.  --parent DIR (u8 only; a checkout of an earlier commit with its library built) runs side A in that tree; --large
+results, which must be equal.  --parent DIR (a checkout of an earlier commit with its library built): --door u8 runs side A in that tree, every other door runs the door
+itself in both trees (A: the parent's host path, B: this tree's); --large
 (u8 only) adds one window of 720x1280.  No ratio is promised; nothing gates on these numbers.
 
 --kernels: no whole calls.  A worker in --parent DIR and one in this tree time each of the 8 ppms_video_ingest_* entry points alone through the C ABI,
@@ -399,7 +400,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--door", choices=sorted(DOORS))
     ap.add_argument("--kernels", action="store_true", help="time the 8 entry points alone, --parent DIR against this tree")
-    ap.add_argument("--parent", default=None, help="tree of an earlier commit with its libppms.so built (--door u8: side A runs there; --kernels: the yardstick)")
+    ap.add_argument("--parent", default=None, help="tree of an earlier commit with its libppms.so built (--door u8: side A runs there; other doors: the door itself; --kernels: the yardstick)")
     ap.add_argument("--runs", type=int, default=None, help="alternating calls per side (12), or with --kernels windows per side (7)")
     ap.add_argument("--large", action="store_true", help="--door u8: also one T = 5 window of 720x1280")
     ap.add_argument("--yuv", action="store_true", help="--door remap: NV12 raw frames instead of planar RGB bytes")
@@ -425,10 +426,10 @@ def main():
     if a.kernels:
         labels = [("the parent's tree", ptree), ("this tree", HERE)]
     else:
-        labels = [(DOORS[a.door][2] + (", the parent's tree" if a.parent and a.door == "u8" else ""), ptree if a.door == "u8" else HERE), (DOORS[a.door][3], HERE)]
+        labels = [(DOORS[a.door][2 if a.door == "u8" or not a.parent else 3] + (", the parent's tree" if a.parent else ""), ptree), (DOORS[a.door][3], HERE)]
     sides, failed = [], True
     try:
-        for (label, tree), side in zip(labels, "AB"):           # one worker at a time is started and warmed: the second only once the first has answered
+        for (label, tree), side in zip(labels, "AB" if a.kernels or a.door == "u8" or not a.parent else "BB"):           # one worker at a time is started and warmed: the second only once the first has answered
             sides.append(Side(label, a, side, tree))
             sides[-1].ask(START_S)                              # "ready"
         (kernels_report if a.kernels else door_report)(a, *sides)
