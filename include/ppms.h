@@ -271,6 +271,38 @@ int ppms_disparity_egress(const float* flow_up, const float* unc, int T, int H, 
                           int H0, int W0, const ppms_egress* out, void* stream);
 int ppms_egress_struct_size(void);    /* sizeof(ppms_egress) (112): lets a binding verify its layout */
 
+/* Point-cloud output: ppms_disparity_egress with one more plane and two gates, still ONE launch -- what a caller of a stereo model does with the
+ * Q matrix of its calibration behind the network (cv2.reprojectImageTo3D and a validity mask).  Arguments, sources, crop, frame range and the three
+ * planes of `base` are ppms_disparity_egress's; a struct whose points.ptr is NULL and whose gates are off writes the same bits as that call.
+ * With x, y = the column and row of the pixel in the cropped H0 x W0 output plane (exact fp32 integers), d and u as above, q row major,
+ * every operation ONE fp32 operation rounded to nearest even, in this order:
+ *   v_i  = ((q[4i] * x + q[4i+1] * y) + q[4i+2] * d) + q[4i+3]          i = 0..3
+ *   X, Y, Z = v_0 / v_3, v_1 / v_3, v_2 / v_3                            correctly rounded divisions, as the depth plane's
+ *   valid_d = d >= min_disp                                              (false for NaN)
+ *   valid_u = max_uncertainty is +inf (gate off), or u <= max_uncertainty (false for NaN)
+ *   a point is valid when valid_d and valid_u and (max_depth is +inf (gate off), or Z > 0 and Z <= max_depth)
+ *   a depth pixel is valid when valid_d and valid_u and (max_depth is +inf, or fb / d <= max_depth)
+ * points plane: points_components (3 or 4) elements per pixel, X, Y, Z[, w], pixel after pixel along the row: F32 the values, F16 their rounding
+ * to nearest even (overflow: inf).  An invalid point carries NaN in X, Y and Z (the payload is unspecified); w = u, written for valid and invalid
+ * points alike.  pitch and frame_stride are bytes as for the other planes; a row is W0 * points_components elements.  An invalid depth pixel is
+ * +inf (U16: 0) as above.  The gates never touch the disparity and uncertainty planes.  q is the caller's (cv2.stereoRectify's Q for the left camera
+ * with a positive disparity has the rows [1 0 0 -cx], [0 1 0 -cy], [0 0 0 f], [0 0 1/B (cx_right - cx)/B]); nothing here is compared with OpenCV.
+ * Refused with PPMS_EINVAL before any launch: everything ppms_disparity_egress refuses (one shared check); no plane at all; points.format other than
+ * F32 / F16; points_components other than 3 or 4 with a points plane; a points pitch shorter than W0 * points_components elements; a pitch or
+ * frame_stride that is no multiple of the element; frames that overlap; a non-finite entry of q or min_disp with a points plane; a NaN max_uncertainty;
+ * max_depth <= 0 or NaN; unc == NULL where a gate on u or points_components = 4 reads it; a depth plane without fb > 0; reserved != 0. */
+typedef struct ppms_egress3d {
+    ppms_egress base;                 /* the three planes and four constants of ppms_disparity_egress */
+    ppms_egress_plane points;         /* format PPMS_FMT_F32 or PPMS_FMT_F16; ptr == NULL: no points */
+    float q[16];                      /* the 4x4 reprojection matrix, row major */
+    float max_uncertainty, max_depth; /* +inf: the gate is off */
+    int32_t points_components;        /* 3: X Y Z.  4: X Y Z w */
+    int32_t reserved;                 /* 0 */
+} ppms_egress3d;
+int ppms_scene_egress(const float* flow_up, const float* unc, int T, int H, int W, int frame0, int n_frames, int pad_left, int pad_top,
+                      int H0, int W0, const ppms_egress3d* out, void* stream);
+int ppms_egress3d_struct_size(void);  /* sizeof(ppms_egress3d) (224) */
+
 /* Scale-to-scale hand-over of the cascade without leaving the SP format (ppmstereo.py:726-732, 763-767): per frame,
  * dst = a * dst + b * interp(src), interp = F.interpolate(mode="bilinear", align_corners=True) from HxW to OHxOW.
  * src, dst: SP views with the same channel count (multiple of 8). */

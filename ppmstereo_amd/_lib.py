@@ -124,6 +124,12 @@ class Egress(C.Structure):
                 ("disp_scale", c_float), ("fb", c_float), ("depth_scale", c_float), ("min_disp", c_float)]
 
 
+class Egress3D(C.Structure):
+    """ppms_egress3d: a ppms_egress, the points plane, the reprojection matrix (row major), the two gates (+inf: off), 3 or 4 components."""
+    _fields_ = [("base", Egress), ("points", EgressPlane), ("q", c_float * 16), ("max_uncertainty", c_float), ("max_depth", c_float),
+                ("points_components", C.c_int32), ("reserved", C.c_int32)]
+
+
 _SIGS = {
     "ppms_version": (c_int, []),
     "ppms_last_error": (C.c_char_p, []),
@@ -164,6 +170,8 @@ _SIGS = {
     "ppms_bilinear": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "ppms_disparity_egress": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, C.POINTER(Egress), c_void_p]),
     "ppms_egress_struct_size": (c_int, []),
+    "ppms_scene_egress": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, C.POINTER(Egress3D), c_void_p]),
+    "ppms_egress3d_struct_size": (c_int, []),
     "ppms_sp_resize_blend": (c_int, [SP, SP, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p]),
     "ppms_avgpool": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ppms_axpby": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_float, c_int64, c_int64, c_void_p]),
@@ -257,6 +265,8 @@ def load() -> C.CDLL:
             raise RuntimeError(f"ppmstereo_amd: ctypes {what} differs from include/ppms.h")
     if lib.ppms_egress_struct_size() != C.sizeof(Egress):
         raise RuntimeError("ppmstereo_amd: ctypes layout of ppms_egress differs from include/ppms.h")
+    if lib.ppms_egress3d_struct_size() != C.sizeof(Egress3D):
+        raise RuntimeError("ppmstereo_amd: ctypes layout of ppms_egress3d differs from include/ppms.h")
     if lib.ppms_pwchain_param_bytes() != C.sizeof(ChainParams):
         raise RuntimeError("ppmstereo_amd: ChainParams layout differs from pwchain.hip")
     _lib = lib

@@ -686,51 +686,238 @@ __global__ __launch_bounds__(256) void disparity_egress_kernel(const float* __re
         }
     }
 }
+// ---- point-cloud egress (include/ppms.h: the formulas).  disparity_egress_kernel's thread mapping, loads and plane stores, plus the two gates
+// and the reprojection with q: a run of points is EG_RUN * C contiguous elements (48 to 128 bytes), stored 16 bytes at a time where the run is
+// whole and its address 16-byte aligned, element by element otherwise.  The upsampled uncertainty is computed once per pixel, where a plane,
+// a gate or w needs it.  Every branch on the struct's fields is wave-uniform.  The three older planes' sections are restated here, not shared
+// with disparity_egress_kernel: that kernel's source stays as it is, and so does its generated code (tools/isa_digest.py --keep).
+template <class T, int C>
+__device__ __forceinline__ void egress_store_points(const ppms_egress_plane& p, int64_t frame, int y, int x0, int n, const float (&X)[EG_RUN],
+                                                    const float (&Y)[EG_RUN], const float (&Z)[EG_RUN], const float (&u)[EG_RUN]) {
+    T v[EG_RUN * C];
+#pragma unroll
+    for (int j = 0; j < EG_RUN; ++j) {
+        v[j * C] = (T)X[j];
+        v[j * C + 1] = (T)Y[j];
+        v[j * C + 2] = (T)Z[j];
+        if constexpr (C == 4) v[j * C + 3] = (T)u[j];
+    }
+    T* dst = (T*)((char*)p.ptr + frame * p.frame_stride + (int64_t)y * p.pitch) + (int64_t)x0 * C;
+    constexpr int BYTES = (int)sizeof(T) * EG_RUN * C;                   // 48, 64 (f16), 96 or 128 (f32)
+    if (n == EG_RUN && ((uintptr_t)dst & 15) == 0) {
+        struct chunks { u32x4 q[BYTES / 16]; };
+        const chunks c = __builtin_bit_cast(chunks, v);
+#pragma unroll
+        for (int i = 0; i < BYTES / 16; ++i) gstore16((char*)dst + 16 * i, c.q[i]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < EG_RUN; ++j)
+            if (j < n) {
+#pragma unroll
+                for (int c = 0; c < C; ++c) dst[j * C + c] = v[j * C + c];
+            }
+    }
+}
+__global__ __launch_bounds__(256) void scene_egress_kernel(const float* __restrict__ flow_up, const float* __restrict__ unc, ppms_egress3d e, int H,
+                                                            int W, int frame0, int pad_left, int pad_top, int H0, int W0, float sh, float sw, int rpr,
+                                                            int64_t total) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const ppms_egress& o = e.base;
+    const int x0 = (int)(idx % rpr) * EG_RUN;
+    const int64_t row = idx / rpr;                                       // frame * H0 + y of the output
+    const int y = (int)(row % H0);
+    const int64_t frame = row / H0;
+    const int n = W0 - x0 < EG_RUN ? W0 - x0 : EG_RUN;                   // elements of this run inside the row
+    const int sy = y + pad_top, sx = x0 + pad_left;                      // the run's first pixel in the padded H x W frame
+    const bool gated = o.depth.ptr || e.points.ptr;                      // a plane the gates act on
+    const bool gate_u = e.max_uncertainty < INFINITY, gate_z = e.max_depth < INFINITY;
+    float u[EG_RUN];
+    if (o.uncertainty.ptr || (gated && gate_u) || (e.points.ptr && e.points_components == 4)) {
+        const int h = H / 4, w = W / 4;
+        const float* s = unc + (frame0 + frame) * h * w;
+#pragma unroll
+        for (int j = 0; j < EG_RUN; ++j) u[j] = fabsf(bilinear_tap(s, h, w, sh, sw, sy, sx + (j < n ? j : n - 1)));
+    } else {
+#pragma unroll
+        for (int j = 0; j < EG_RUN; ++j) u[j] = 0.0f;
+    }
+    if (o.uncertainty.ptr) {
+        if (o.uncertainty.format == PPMS_FMT_F32) {
+            egress_store_run(o.uncertainty, frame, y, x0, n, u);
+        } else {
+            uint8_t v[EG_RUN];
+#pragma unroll
+            for (int j = 0; j < EG_RUN; ++j) v[j] = (uint8_t)egress_quant(u[j] * 255.0f, 255.0f);
+            egress_store_run(o.uncertainty, frame, y, x0, n, v);
+        }
+    }
+    if (!o.disparity.ptr && !gated) return;
+    const float* s = flow_up + ((frame0 + frame) * 2 * H + sy) * W + sx;            // channel 0 of (T, 2, H, W)
+    float d[EG_RUN];
+    if (n == EG_RUN && ((uintptr_t)s & 15) == 0) {
+        const f32x4 a = gld<f32x4>(s), b = gld<f32x4>(s + 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            d[j] = a[j];
+            d[4 + j] = b[j];
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < EG_RUN; ++j) d[j] = s[j < n ? j : n - 1];
+    }
+#pragma unroll
+    for (int j = 0; j < EG_RUN; ++j) d[j] = fabsf(d[j]);
+    if (o.disparity.ptr) {
+        if (o.disparity.format == PPMS_FMT_F32) {
+            egress_store_run(o.disparity, frame, y, x0, n, d);
+        } else if (o.disparity.format == PPMS_FMT_F16) {
+            _Float16 v[EG_RUN];
+#pragma unroll
+            for (int j = 0; j < EG_RUN; ++j) v[j] = (_Float16)d[j];
+            egress_store_run(o.disparity, frame, y, x0, n, v);
+        } else {
+            uint16_t v[EG_RUN];
+#pragma unroll
+            for (int j = 0; j < EG_RUN; ++j) v[j] = (uint16_t)egress_quant(d[j] * o.disp_scale, 65535.0f);
+            egress_store_run(o.disparity, frame, y, x0, n, v);
+        }
+    }
+    bool ok[EG_RUN];                                                     // valid_d and valid_u (both false for NaN)
+#pragma unroll
+    for (int j = 0; j < EG_RUN; ++j) ok[j] = d[j] >= o.min_disp && (!gate_u || u[j] <= e.max_uncertainty);
+    if (o.depth.ptr) {
+        float z[EG_RUN];
+        bool okz[EG_RUN];
+#pragma unroll
+        for (int j = 0; j < EG_RUN; ++j) {
+            const float q = __fdiv_rn(o.fb, d[j]);
+            okz[j] = ok[j] && (!gate_z || q <= e.max_depth);
+            z[j] = okz[j] ? q : INFINITY;
+        }
+        if (o.depth.format == PPMS_FMT_F32) {
+            egress_store_run(o.depth, frame, y, x0, n, z);
+        } else if (o.depth.format == PPMS_FMT_F16) {
+            _Float16 v[EG_RUN];
+#pragma unroll
+            for (int j = 0; j < EG_RUN; ++j) v[j] = (_Float16)z[j];
+            egress_store_run(o.depth, frame, y, x0, n, v);
+        } else {
+            uint16_t v[EG_RUN];
+#pragma unroll
+            for (int j = 0; j < EG_RUN; ++j) v[j] = okz[j] ? (uint16_t)egress_quant(z[j] * o.depth_scale, 65535.0f) : (uint16_t)0;
+            egress_store_run(o.depth, frame, y, x0, n, v);
+        }
+    }
+    if (e.points.ptr) {
+        const float yf = (float)y;                                       // the pixel's row and column in the cropped plane
+        float qy[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) qy[i] = e.q[4 * i + 1] * yf;
+        float X[EG_RUN], Y[EG_RUN], Z[EG_RUN];
+#pragma unroll
+        for (int j = 0; j < EG_RUN; ++j) {
+            const float xf = (float)(x0 + j);
+            float v[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[i] = ((e.q[4 * i] * xf + qy[i]) + e.q[4 * i + 2] * d[j]) + e.q[4 * i + 3];
+            const float pz = __fdiv_rn(v[2], v[3]);
+            const bool okp = ok[j] && (!gate_z || (pz > 0.0f && pz <= e.max_depth));
+            X[j] = okp ? __fdiv_rn(v[0], v[3]) : __builtin_nanf("");
+            Y[j] = okp ? __fdiv_rn(v[1], v[3]) : __builtin_nanf("");
+            Z[j] = okp ? pz : __builtin_nanf("");
+        }
+        if (e.points.format == PPMS_FMT_F32) {
+            if (e.points_components == 3) egress_store_points<float, 3>(e.points, frame, y, x0, n, X, Y, Z, u);
+            else egress_store_points<float, 4>(e.points, frame, y, x0, n, X, Y, Z, u);
+        } else {
+            if (e.points_components == 3) egress_store_points<_Float16, 3>(e.points, frame, y, x0, n, X, Y, Z, u);
+            else egress_store_points<_Float16, 4>(e.points, frame, y, x0, n, X, Y, Z, u);
+        }
+    }
+}
 extern "C" int ppms_egress_struct_size(void) { return (int)sizeof(ppms_egress); }
+extern "C" int ppms_egress3d_struct_size(void) { return (int)sizeof(ppms_egress3d); }
+// What both egress entry points check, under the name `who` of the one called: the geometry, the three planes and their constants, and -- from
+// ppms_scene_egress (e != nullptr) -- the points plane, q and the gates.  On success the launch geometry.
+struct egress_launch { int rpr; int64_t total; float sh, sw; };
+static int egress_check(const char* who, const float* flow_up, const float* unc, int T, int H, int W, int frame0, int n_frames, int pad_left, int pad_top,
+                        int H0, int W0, const ppms_egress& o, const ppms_egress3d* e, egress_launch* g) {
+    const bool points = e && e->points.ptr;
+    if (e)
+        PPMS_REQUIRE(o.disparity.ptr || o.depth.ptr || o.uncertainty.ptr || points, "%s: no plane: disparity, depth, uncertainty and points are all NULL", who);
+    else
+        PPMS_REQUIRE(o.disparity.ptr || o.depth.ptr || o.uncertainty.ptr, "%s: no plane: disparity, depth and uncertainty are all NULL", who);
+    PPMS_REQUIRE(T > 0 && H > 0 && W > 0 && H0 > 0 && W0 > 0, "%s: T = %d, H = %d, W = %d, H0 = %d, W0 = %d must be positive", who, T, H, W, H0, W0);
+    PPMS_REQUIRE(H % 4 == 0 && W % 4 == 0, "%s: H = %d, W = %d must be multiples of 4", who, H, W);
+    PPMS_REQUIRE(pad_left >= 0 && pad_top >= 0 && (int64_t)pad_top + H0 <= H && (int64_t)pad_left + W0 <= W,
+                 "%s: the crop pad_left = %d, pad_top = %d, H0 = %d, W0 = %d lies outside the %d x %d frame", who, pad_left, pad_top, H0, W0, H, W);
+    PPMS_REQUIRE(n_frames > 0, "%s: n_frames = %d must be positive", who, n_frames);
+    PPMS_REQUIRE(frame0 >= 0 && (int64_t)frame0 + n_frames <= T, "%s: frame0 = %d, n_frames = %d leave the T = %d frames", who, frame0, n_frames, T);
+    PPMS_REQUIRE(((o.disparity.ptr || o.depth.ptr || points) ? flow_up != nullptr : true) && (o.uncertainty.ptr ? unc != nullptr : true),
+                 "%s: null flow_up / unc source of a requested plane", who);
+    if (points)
+        PPMS_REQUIRE(e->points_components == 3 || e->points_components == 4, "%s: points_components = %d must be 3 or 4", who, e->points_components);
+    const struct { const ppms_egress_plane* p; const char* name; unsigned formats; int comps; } planes[4] = {
+        {&o.disparity, "disparity", 1u << PPMS_FMT_F32 | 1u << PPMS_FMT_F16 | 1u << PPMS_FMT_U16, 1},
+        {&o.depth, "depth", 1u << PPMS_FMT_F32 | 1u << PPMS_FMT_F16 | 1u << PPMS_FMT_U16, 1},
+        {&o.uncertainty, "uncertainty", 1u << PPMS_FMT_F32 | 1u << PPMS_FMT_U8, 1},
+        {points ? &e->points : nullptr, "points", 1u << PPMS_FMT_F32 | 1u << PPMS_FMT_F16, points ? e->points_components : 0}};
+    for (const auto& pl : planes) {
+        if (!pl.p || !pl.p->ptr) continue;                               // skipped
+        const ppms_egress_plane& p = *pl.p;
+        PPMS_REQUIRE(p.format >= 0 && p.format <= PPMS_FMT_U8 && (pl.formats >> p.format & 1u),
+                     "%s: %s.format = %d is not a format of that plane", who, pl.name, p.format);
+        PPMS_REQUIRE(p.reserved == 0, "%s: %s.reserved = %d must be 0", who, pl.name, p.reserved);
+        const int64_t esz = p.format == PPMS_FMT_F32 ? 4 : (p.format == PPMS_FMT_U8 ? 1 : 2), rowb = esz * W0 * pl.comps;
+        PPMS_REQUIRE(p.pitch >= rowb, "%s: %s.pitch = %lld is less than a row's %lld bytes", who, pl.name, (long long)p.pitch, (long long)rowb);
+        PPMS_REQUIRE(n_frames == 1 || p.frame_stride >= (int64_t)(H0 - 1) * p.pitch + rowb,
+                     "%s: %s.frame_stride = %lld is less than a plane", who, pl.name, (long long)p.frame_stride);
+        PPMS_REQUIRE(((uintptr_t)p.ptr | (uintptr_t)p.pitch | (uintptr_t)p.frame_stride) % esz == 0,
+                     "%s: %s: pointer, pitch and frame_stride must be multiples of the %lld-byte element", who, pl.name, (long long)esz);
+    }
+    if (o.depth.ptr) {
+        PPMS_REQUIRE(o.fb > 0.0f && o.fb < INFINITY, "%s: a depth plane needs fb = %g > 0", who, (double)o.fb);
+        PPMS_REQUIRE(o.depth_scale > 0.0f && o.depth_scale < INFINITY, "%s: a depth plane needs depth_scale = %g > 0", who, (double)o.depth_scale);
+        PPMS_REQUIRE(o.min_disp > -INFINITY && o.min_disp < INFINITY, "%s: a depth plane needs a finite min_disp, got %g", who, (double)o.min_disp);
+    }
+    if (o.disparity.ptr && o.disparity.format == PPMS_FMT_U16)
+        PPMS_REQUIRE(o.disp_scale > 0.0f && o.disp_scale < INFINITY, "%s: a u16 disparity needs disp_scale = %g > 0", who, (double)o.disp_scale);
+    if (e) {
+        PPMS_REQUIRE(e->reserved == 0, "%s: reserved = %d must be 0", who, e->reserved);
+        PPMS_REQUIRE(e->max_uncertainty == e->max_uncertainty, "%s: max_uncertainty is NaN (+inf switches the gate off)", who);
+        PPMS_REQUIRE(e->max_depth > 0.0f, "%s: max_depth = %g must be positive (+inf switches the gate off)", who, (double)e->max_depth);
+        if (points) {
+            for (int i = 0; i < 16; ++i)
+                PPMS_REQUIRE(e->q[i] > -INFINITY && e->q[i] < INFINITY, "%s: q[%d] = %g is not finite", who, i, (double)e->q[i]);
+            PPMS_REQUIRE(o.min_disp > -INFINITY && o.min_disp < INFINITY, "%s: points need a finite min_disp, got %g", who, (double)o.min_disp);
+        }
+        const bool reads_u = ((o.depth.ptr || points) && e->max_uncertainty < INFINITY) || (points && e->points_components == 4);
+        PPMS_REQUIRE(!reads_u || unc != nullptr, "%s: null unc: the max_uncertainty gate and points_components = 4 read it", who);
+    }
+    g->rpr = (W0 + EG_RUN - 1) / EG_RUN;                                 // runs per output row
+    g->total = (int64_t)n_frames * H0 * g->rpr;
+    PPMS_REQUIRE((g->total + 255) / 256 <= 0x7fffffff, "%s: %lld threads exceed one grid", who, (long long)g->total);
+    g->sh = (float)(H / 4) / (float)H, g->sw = (float)(W / 4) / (float)W;            // ppms_bilinear's scales for (H/4, W/4) -> (H, W): 0.25
+    return PPMS_OK;
+}
 extern "C" int ppms_disparity_egress(const float* flow_up, const float* unc, int T, int H, int W, int frame0, int n_frames, int pad_left, int pad_top,
                                      int H0, int W0, const ppms_egress* out, void* stream) {
     PPMS_REQUIRE(out, "disparity_egress: null out struct");
-    const ppms_egress& o = *out;
-    PPMS_REQUIRE(o.disparity.ptr || o.depth.ptr || o.uncertainty.ptr, "disparity_egress: no plane: disparity, depth and uncertainty are all NULL");
-    PPMS_REQUIRE(T > 0 && H > 0 && W > 0 && H0 > 0 && W0 > 0, "disparity_egress: T = %d, H = %d, W = %d, H0 = %d, W0 = %d must be positive", T, H, W, H0, W0);
-    PPMS_REQUIRE(H % 4 == 0 && W % 4 == 0, "disparity_egress: H = %d, W = %d must be multiples of 4", H, W);
-    PPMS_REQUIRE(pad_left >= 0 && pad_top >= 0 && (int64_t)pad_top + H0 <= H && (int64_t)pad_left + W0 <= W,
-                 "disparity_egress: the crop pad_left = %d, pad_top = %d, H0 = %d, W0 = %d lies outside the %d x %d frame", pad_left, pad_top, H0, W0, H, W);
-    PPMS_REQUIRE(n_frames > 0, "disparity_egress: n_frames = %d must be positive", n_frames);
-    PPMS_REQUIRE(frame0 >= 0 && (int64_t)frame0 + n_frames <= T, "disparity_egress: frame0 = %d, n_frames = %d leave the T = %d frames", frame0, n_frames, T);
-    PPMS_REQUIRE(((o.disparity.ptr || o.depth.ptr) ? flow_up != nullptr : true) && (o.uncertainty.ptr ? unc != nullptr : true),
-                 "disparity_egress: null flow_up / unc source of a requested plane");
-    const struct { const ppms_egress_plane* p; const char* name; unsigned formats; } planes[3] = {
-        {&o.disparity, "disparity", 1u << PPMS_FMT_F32 | 1u << PPMS_FMT_F16 | 1u << PPMS_FMT_U16},
-        {&o.depth, "depth", 1u << PPMS_FMT_F32 | 1u << PPMS_FMT_F16 | 1u << PPMS_FMT_U16},
-        {&o.uncertainty, "uncertainty", 1u << PPMS_FMT_F32 | 1u << PPMS_FMT_U8}};
-    for (const auto& pl : planes) {
-        const ppms_egress_plane& p = *pl.p;
-        if (!p.ptr) continue;                                            // skipped
-        PPMS_REQUIRE(p.format >= 0 && p.format <= PPMS_FMT_U8 && (pl.formats >> p.format & 1u),
-                     "disparity_egress: %s.format = %d is not a format of that plane", pl.name, p.format);
-        PPMS_REQUIRE(p.reserved == 0, "disparity_egress: %s.reserved = %d must be 0", pl.name, p.reserved);
-        const int64_t esz = p.format == PPMS_FMT_F32 ? 4 : (p.format == PPMS_FMT_U8 ? 1 : 2), rowb = esz * W0;
-        PPMS_REQUIRE(p.pitch >= rowb, "disparity_egress: %s.pitch = %lld is less than a row's %lld bytes", pl.name, (long long)p.pitch, (long long)rowb);
-        PPMS_REQUIRE(n_frames == 1 || p.frame_stride >= (int64_t)(H0 - 1) * p.pitch + rowb,
-                     "disparity_egress: %s.frame_stride = %lld is less than a plane", pl.name, (long long)p.frame_stride);
-        PPMS_REQUIRE(((uintptr_t)p.ptr | (uintptr_t)p.pitch | (uintptr_t)p.frame_stride) % esz == 0,
-                     "disparity_egress: %s: pointer, pitch and frame_stride must be multiples of the %lld-byte element", pl.name, (long long)esz);
-    }
-    if (o.depth.ptr) {
-        PPMS_REQUIRE(o.fb > 0.0f && o.fb < INFINITY, "disparity_egress: a depth plane needs fb = %g > 0", (double)o.fb);
-        PPMS_REQUIRE(o.depth_scale > 0.0f && o.depth_scale < INFINITY, "disparity_egress: a depth plane needs depth_scale = %g > 0", (double)o.depth_scale);
-        PPMS_REQUIRE(o.min_disp > -INFINITY && o.min_disp < INFINITY, "disparity_egress: a depth plane needs a finite min_disp, got %g", (double)o.min_disp);
-    }
-    if (o.disparity.ptr && o.disparity.format == PPMS_FMT_U16)
-        PPMS_REQUIRE(o.disp_scale > 0.0f && o.disp_scale < INFINITY, "disparity_egress: a u16 disparity needs disp_scale = %g > 0", (double)o.disp_scale);
-    const int rpr = (W0 + EG_RUN - 1) / EG_RUN;                          // runs per output row
-    const int64_t total = (int64_t)n_frames * H0 * rpr;
-    PPMS_REQUIRE((total + 255) / 256 <= 0x7fffffff, "disparity_egress: %lld threads exceed one grid", (long long)total);
-    const float sh = (float)(H / 4) / (float)H, sw = (float)(W / 4) / (float)W;      // ppms_bilinear's scales for (H/4, W/4) -> (H, W): 0.25
-    hipLaunchKernelGGL(disparity_egress_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, flow_up, unc, o, H, W, frame0, pad_left,
-                       pad_top, H0, W0, sh, sw, rpr, total);
+    egress_launch g;
+    if (const int rc = egress_check("disparity_egress", flow_up, unc, T, H, W, frame0, n_frames, pad_left, pad_top, H0, W0, *out, nullptr, &g)) return rc;
+    hipLaunchKernelGGL(disparity_egress_kernel, dim3(ceil_div(g.total, 256)), dim3(256), 0, (hipStream_t)stream, flow_up, unc, *out, H, W, frame0, pad_left,
+                       pad_top, H0, W0, g.sh, g.sw, g.rpr, g.total);
     return ppms_check_launch("disparity_egress");
+}
+extern "C" int ppms_scene_egress(const float* flow_up, const float* unc, int T, int H, int W, int frame0, int n_frames, int pad_left, int pad_top,
+                                 int H0, int W0, const ppms_egress3d* out, void* stream) {
+    PPMS_REQUIRE(out, "scene_egress: null out struct");
+    egress_launch g;
+    if (const int rc = egress_check("scene_egress", flow_up, unc, T, H, W, frame0, n_frames, pad_left, pad_top, H0, W0, out->base, out, &g)) return rc;
+    hipLaunchKernelGGL(scene_egress_kernel, dim3(ceil_div(g.total, 256)), dim3(256), 0, (hipStream_t)stream, flow_up, unc, *out, H, W, frame0, pad_left,
+                       pad_top, H0, W0, g.sh, g.sw, g.rpr, g.total);
+    return ppms_check_launch("scene_egress");
 }
 
 // Scale-to-scale hand-over of the cascade on SP (channel-last split-bf16) tensors, no NCHW round trip:

@@ -700,8 +700,9 @@ class ScaleEngine:
         self.hbm["convex_upsample"]()
         return self.FLOW_OUT
 
-    def egress(self, out: L.Egress, frame0: int, n_frames: int, pad_left: int, pad_top: int, h0: int, w0: int):
-        """ppms_disparity_egress on the current stream: the state the last iteration left -- FLOW_OUT (read in place, channel 0) and the
+    def egress(self, out, frame0: int, n_frames: int, pad_left: int, pad_top: int, h0: int, w0: int):
+        """ppms_disparity_egress (``out``: an L.Egress) or ppms_scene_egress (an L.Egress3D: points, gates) on the current stream: the state the
+        last iteration left -- FLOW_OUT (read in place, channel 0) and the
         1/4-resolution UNC -- to the caller's planes: frames [frame0, frame0 + n_frames), the h0 x w0 crop at (pad_top, pad_left).  Valid
         behind an iterate(need_up=True) of an unsharded engine at the 1/4 scale (full resolution = 4 h x 4 w)."""
         if self.shard is not None:
@@ -755,13 +756,16 @@ def bilinear(x: torch.Tensor, size, align_corners: bool, mul: float = 1.0) -> to
     return out
 
 
-def disparity_egress(flow_up: torch.Tensor, unc: torch.Tensor, out: L.Egress, frame0: int, n_frames: int, pad_left: int, pad_top: int, h0: int, w0: int):
+def disparity_egress(flow_up: torch.Tensor, unc: torch.Tensor, out, frame0: int, n_frames: int, pad_left: int, pad_top: int, h0: int, w0: int):
     """One ppms_disparity_egress launch on the current stream (include/ppms.h): flow_up fp32 (T, 2, H, W), unc fp32 (T, H/4, W/4), both
-    contiguous on the GPU; ``out``: the planes (device pointers, byte strides, formats) and conversion constants."""
+    contiguous on the GPU; ``out``: the planes (device pointers, byte strides, formats) and conversion constants.  An ``L.Egress3D`` (the same
+    with a points plane, Q and the gates) makes it one ppms_scene_egress launch."""
     L.require_gpu(flow_up, unc)
     T, two, H, W = flow_up.shape
     if (flow_up.dtype != torch.float32 or unc.dtype != torch.float32 or two != 2 or tuple(unc.shape) != (T, H // 4, W // 4)
             or not flow_up.is_contiguous() or not unc.is_contiguous()):
         raise ValueError(f"disparity_egress: contiguous fp32 flow_up (T, 2, H, W) and unc (T, H/4, W/4) expected, got {tuple(flow_up.shape)} and {tuple(unc.shape)}")
-    L.check(L.load().ppms_disparity_egress(flow_up.data_ptr(), unc.data_ptr(), T, H, W, frame0, n_frames, pad_left, pad_top, h0, w0, C.byref(out),
-                                           L.stream_ptr()))
+    if not isinstance(out, (L.Egress, L.Egress3D)):
+        raise TypeError(f"disparity_egress: out must be an L.Egress or an L.Egress3D, got {type(out).__name__}")
+    entry = L.load().ppms_scene_egress if isinstance(out, L.Egress3D) else L.load().ppms_disparity_egress
+    L.check(entry(flow_up.data_ptr(), unc.data_ptr(), T, H, W, frame0, n_frames, pad_left, pad_top, h0, w0, C.byref(out), L.stream_ptr()))

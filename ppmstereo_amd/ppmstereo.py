@@ -296,7 +296,8 @@ class PPMStereoHotPath(nn.Module):
         ``pipeline`` there is none here: the counters are read in ``ClipPipeline.wait()``.  None (default): nothing is launched or read.
         egress (test_mode, b = 1, no shard): an ``_EgressCall`` -- after the last 1/4-scale iteration ONE ppms_disparity_egress launch on that
         scale's stream replaces the final clone + bilinear pair and writes the requested planes (crop, frame range, formats); the call
-        then returns {"disparity", "depth"?, "uncertainties"?}: device tensors (n, 1, H0, W0), and appends nothing to the lists.
+        then returns {"disparity", "depth"?, "uncertainties"?}: device tensors (n, 1, H0, W0), and appends nothing to the lists.  A spec with
+        points or a gate (``OutputSpec.scene``) makes that launch ppms_scene_egress and adds "points": (n, H0, W0, C).
         Returns (flow_up (T,1,H,W), uncertainty (T,1,H,W)) = predictions[-1], uncertainties[-1]."""
         if egress is not None:
             if not test_mode:
@@ -574,6 +575,8 @@ class PPMStereo(PPMStereoHotPath):
         output (test_mode, b = 1): an ``OutputSpec`` -- the call returns a dict of device tensors (1, n, 1, H0, W0) under "disparity", "depth"
         and "uncertainties" as the spec asks, written by ONE ppms_disparity_egress launch behind the last iteration (no float32 full-resolution
         tensor is made); crop = (pad_left, pad_top, H0, W0) inside the frame (default: the whole frame), frames = (from, to) (default: all).
+        With ``OutputSpec(points=..., Q=...)`` the dict also has "points", the organised cloud (1, n, H0, W0, C) of ``cv2.reprojectImageTo3D`` with
+        the spec's gates applied (x, y count from the crop's corner), written by the same single launch (then ppms_scene_egress).
         rectify=None and output=None (the defaults) add no launch to the calls above."""
         if flow_init is not None:
             raise NotImplementedError("flow_init: the reference's own path for it reads undefined state (ppmstereo.py:691-693, 763)")
@@ -701,7 +704,10 @@ class PPMStereo(PPMStereoHotPath):
         output: an ``OutputSpec`` -- per window ONE ppms_disparity_egress launch writes the kept frames, cropped and converted, and only
         those are copied device -> host, straight into their slice of pinned (N, 1, H, W) results of the planes' dtypes (uint16 disparity and
         uint8 confidence: 3 bytes per pixel and kept frame, where the default path copies 8 for every frame of the window).  Returns
-        {"disparity", "depth" when asked, "uncertainties" unless its format is None}.  Not with ``shard_ranks``.
+        {"disparity", "depth" when asked, "uncertainties" unless its format is None, "points" when asked}.  Not with ``shard_ranks``.
+        ``OutputSpec(points="f32", Q=Q, max_uncertainty=..., max_depth=...)``: "points" is the organised cloud (N, H, W, C) -- X, Y, Z[, w] per pixel
+        of the caller's image, NaN where a gate or min_disp takes the pixel -- from the same launch per window (ppms_scene_egress), 12 bytes per pixel
+        of the kept frames for "xyz" f32; ``rectify=`` in front and points behind need the one calibration's maps and Q.
         rectify: a ``StereoRectifier`` -- the video holds the RAW frames of an unrectified rig, (N, 2, 3, Hs, Ws) uint8 or a ``YUVStereoVideo`` of
         its source size Hs x Ws.  Each window's raw bytes are copied as above, the maps once per device (6 bytes per rectified pixel and view):
         the bits of the call on the uint8 video of ``RectifyMap.apply_u8``.  H x W of the results (and of the ``InputPadder``) is the rectified

@@ -1202,10 +1202,26 @@ class OutputSpec:
                    formats, 0 in "u16".  (min_disp = 0 leaves only NaN invalid: d = 0 then gives +inf / 65535.)
       uncertainty  "f32" | "u8" | None: u = |uncertainty| in [0, 1]; "u8" = min(255, rint(u * 255)), NaN -> 0
     Every step is one fp32 operation rounded to nearest even; ``reference`` restates them in torch and is the definition the kernel is
-    tested against, bit for bit."""
+    tested against, bit for bit.
+    Keyword only, all off by default (a spec that uses none of them makes the launch above, the same bits):
+      points           None | "f32" | "f16": an organised point cloud, one record per pixel of the cropped frame, result key "points" with the
+                       shape (n, h0, w0, C) -- ``cv2.reprojectImageTo3D(d, Q)`` and the validity mask behind it, in the same launch
+                       (ppms_scene_egress).  With x, y the pixel's column and row in the cropped plane (the image the caller fed in):
+                       v_i = ((Q[i][0] * x + Q[i][1] * y) + Q[i][2] * d) + Q[i][3], X, Y, Z = v_0 / v_3, v_1 / v_3, v_2 / v_3.  "f16" is the
+                       rounding to nearest even of the fp32 value (overflow: inf).
+      points_layout    "xyz": C = 3 (12-byte records in f32).  "xyzw": C = 4, w = u, the upsampled |uncertainty| (16-byte records in f32, a float4).
+      Q                the 4x4 reprojection matrix of the rig's calibration: anything ``torch.as_tensor`` takes with 16 elements, rounded once to
+                       fp32, every entry finite.  Required with points.  ``q_matrix`` builds the one ``cv2.stereoRectify`` documents.
+      max_uncertainty  None | float: a point / depth pixel with u > max_uncertainty (or u = NaN) is invalid.
+      max_depth        None | float > 0: a point with Z <= 0 or Z > max_depth (or NaN), a depth pixel with fb / d > max_depth is invalid.
+                       (For both gates +inf means None.)
+    An invalid point carries NaN in X, Y and Z (a pixel with d < min_disp or d = NaN is one, as for depth); w is written for valid and invalid points
+    alike; an invalid depth pixel is +inf (0 in "u16") as above.  The gates never touch the disparity and uncertainty planes."""
 
     def __init__(self, disparity: str = "f32", depth: Optional[str] = None, uncertainty: Optional[str] = "f32", disp_scale: float = 256.0,
-                 focal_px: Optional[float] = None, baseline: Optional[float] = None, depth_scale: float = 1000.0, min_disp: float = 2.0 ** -8):
+                 focal_px: Optional[float] = None, baseline: Optional[float] = None, depth_scale: float = 1000.0, min_disp: float = 2.0 ** -8,
+                 *, points: Optional[str] = None, points_layout: str = "xyz", Q=None, max_uncertainty: Optional[float] = None,
+                 max_depth: Optional[float] = None):
         if disparity not in ("f32", "f16", "u16"):
             raise ValueError(f"OutputSpec: disparity = {disparity!r}; one of 'f32', 'f16', 'u16'")
         if depth not in (None, "f32", "f16", "u16"):
@@ -1228,15 +1244,57 @@ class OutputSpec:
                 raise ValueError(f"OutputSpec: depth_scale = {depth_scale} must be positive and finite")
             if not math.isfinite(self.min_disp):
                 raise ValueError(f"OutputSpec: min_disp = {min_disp} must be finite")
+        if points not in (None, "f32", "f16"):
+            raise ValueError(f"OutputSpec: points = {points!r}; None, 'f32' or 'f16'")
+        if points_layout not in ("xyz", "xyzw"):
+            raise ValueError(f"OutputSpec: points_layout = {points_layout!r}; 'xyz' or 'xyzw'")
+        self.points, self.points_layout, self.Q = points, points_layout, None
+        if Q is not None:
+            q = torch.as_tensor(Q).detach().to("cpu", torch.float32)                            # rounded once to fp32
+            if q.numel() != 16 or not torch.isfinite(q).all():
+                raise ValueError(f"OutputSpec: Q must have 16 finite elements (a 4x4 reprojection matrix), got {tuple(q.shape)}: {q.flatten().tolist()}")
+            self.Q = q.reshape(4, 4).clone()
+        if points is not None and self.Q is None:
+            raise ValueError("OutputSpec: points need Q, the 4x4 reprojection matrix of the rig's calibration (OutputSpec.q_matrix builds one)")
+        if points is not None and not math.isfinite(self.min_disp):
+            raise ValueError(f"OutputSpec: min_disp = {min_disp} must be finite")
+        gate_u, gate_z = (None if g is None else f32(g) for g in (max_uncertainty, max_depth))
+        if gate_u is not None and math.isnan(gate_u):
+            raise ValueError("OutputSpec: max_uncertainty is NaN")
+        if gate_z is not None and not gate_z > 0.0:
+            raise ValueError(f"OutputSpec: max_depth = {max_depth} must be positive")
+        self.max_uncertainty, self.max_depth = (None if g == math.inf else g for g in (gate_u, gate_z))          # +inf: the gate is off
+
+    @staticmethod
+    def q_matrix(focal_px: float, baseline: float, cx: float, cy: float, cx_right: Optional[float] = None) -> torch.Tensor:
+        """The 4x4 float64 matrix ``cv2.stereoRectify`` documents as Q, for the left camera and a POSITIVE disparity (this package's d = |flow|):
+        rows [1, 0, 0, -cx], [0, 1, 0, -cy], [0, 0, 0, f], [0, 0, 1 / B, (cx_right - cx) / B]; cx_right = None: cx.  With it Z = f B / (d + cx_right - cx)
+        in the baseline's unit.  A layout claim restated from OpenCV's documentation: nothing in this package is compared with OpenCV (OpenCV's own
+        Q carries -1 / Tx with the sign of its translation; check the sign of Z on a rig before relying on it)."""
+        f, b, cx, cy = (float(v) for v in (focal_px, baseline, cx, cy))
+        if not (b != 0.0 and math.isfinite(b)):
+            raise ValueError(f"OutputSpec.q_matrix: baseline = {baseline} must be finite and not 0")
+        cxr = cx if cx_right is None else float(cx_right)
+        return torch.tensor([[1.0, 0.0, 0.0, -cx], [0.0, 1.0, 0.0, -cy], [0.0, 0.0, 0.0, f], [0.0, 0.0, 1.0 / b, (cxr - cx) / b]], dtype=torch.float64)
+
+    @property
+    def points_components(self) -> int:
+        return 4 if self.points_layout == "xyzw" else 3
+
+    @property
+    def scene(self) -> bool:
+        """The spec asks for points or a gate: its launch is ppms_scene_egress (otherwise ppms_disparity_egress, as ever)."""
+        return self.points is not None or self.max_uncertainty is not None or self.max_depth is not None
 
     def formats(self) -> Dict[str, str]:
-        """{result key: format} of the requested planes, in the order disparity, depth, uncertainties."""
-        named = (("disparity", self.disparity), ("depth", self.depth), ("uncertainties", self.uncertainty))
+        """{result key: format} of the requested planes, in the order disparity, depth, uncertainties, points."""
+        named = (("disparity", self.disparity), ("depth", self.depth), ("uncertainties", self.uncertainty), ("points", self.points))
         return {k: f for k, f in named if f is not None}
 
     def empty(self, n: int, h0: int, w0: int, device, pin_memory: bool = False) -> Dict[str, torch.Tensor]:
-        """Dense (n, 1, h0, w0) tensors of the requested planes' dtypes."""
-        return {k: torch.empty(n, 1, h0, w0, dtype=_PLANE_FORMATS[f][1], device=device, pin_memory=pin_memory) for k, f in self.formats().items()}
+        """Dense (n, 1, h0, w0) tensors of the requested planes' dtypes; "points": (n, h0, w0, C)."""
+        shape = lambda k: (n, h0, w0, self.points_components) if k == "points" else (n, 1, h0, w0)
+        return {k: torch.empty(shape(k), dtype=_PLANE_FORMATS[f][1], device=device, pin_memory=pin_memory) for k, f in self.formats().items()}
 
     def struct(self, planes: Dict[str, torch.Tensor]) -> L.Egress:
         """The ``ppms_egress`` that writes into ``planes`` (dense (n, 1, h0, w0) device tensors from ``empty``)."""
@@ -1248,9 +1306,25 @@ class OutputSpec:
             return L.EgressPlane(t.data_ptr(), t.stride(0) * es, t.stride(2) * es, _PLANE_FORMATS[self.formats()[key]][0], 0)
         return L.Egress(plane("disparity"), plane("depth"), plane("uncertainties"), self.disp_scale, self.fb, self.depth_scale, self.min_disp)
 
+    def scene_struct(self, planes: Dict[str, torch.Tensor]) -> L.Egress3D:
+        """The ``ppms_egress3d`` that writes into ``planes`` (from ``empty``): ``struct``'s planes and constants, the (n, h0, w0, C) points, Q and
+        the gates (None: +inf, off)."""
+        t = planes.get("points")
+        if t is None:
+            points = L.EgressPlane(None, 0, 0, 0, 0)
+        else:
+            es = t.element_size()
+            points = L.EgressPlane(t.data_ptr(), t.stride(0) * es, t.stride(1) * es, _PLANE_FORMATS[self.points][0], 0)
+        q = (L.c_float * 16)(*(self.Q.flatten().tolist() if self.Q is not None else [0.0] * 16))
+        off = lambda g: math.inf if g is None else g
+        return L.Egress3D(self.struct(planes), points, q, off(self.max_uncertainty), off(self.max_depth), self.points_components, 0)
+
     def reference(self, d: torch.Tensor, u: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
-        """The arithmetic of ppms_disparity_egress in plain torch, on CPU or device tensors of any shape: d = a float32 (signed) disparity,
-        u = a float32 uncertainty at the same resolution -> the requested planes under forward_batch_test's keys."""
+        """The arithmetic of ppms_disparity_egress / ppms_scene_egress in plain torch, on CPU or device tensors of any shape: d = a float32 (signed)
+        disparity, u = a float32 uncertainty at the same resolution -> the requested planes under forward_batch_test's keys.  With points, d has at
+        least two dimensions and its last two are the pixel grid (row y, column x of the cropped plane); "points" has d's shape with the components
+        appended -- and, for a d of four or more dimensions whose third last is 1 (the planes' (..., 1, h, w)), without that 1: (..., h, w, C).
+        u is needed for an uncertainty plane, a max_uncertainty gate and the "xyzw" layout."""
         const = lambda x: torch.full((), x, dtype=torch.float32, device=d.device)
 
         def quant(v, scale, top, fmt):                       # min(top, rint(v * scale)), NaN -> 0: one fp32 product, ties to even
@@ -1258,20 +1332,41 @@ class OutputSpec:
             r = torch.where(torch.isnan(r), torch.zeros_like(r), r).clamp(max=top)
             return r.to(torch.int32).to(_PLANE_FORMATS[fmt][1])
 
+        gated = self.depth is not None or self.points is not None
+        if u is None and (self.uncertainty is not None or (gated and self.max_uncertainty is not None) or (self.points and self.points_layout == "xyzw")):
+            raise ValueError("OutputSpec.reference: an uncertainty plane, a max_uncertainty gate or the 'xyzw' layout is requested and no uncertainty was given")
         d = d.float().abs()
+        if u is not None:
+            u = u.float().abs()
         out = {"disparity": d if self.disparity == "f32" else d.to(torch.float16) if self.disparity == "f16" else quant(d, self.disp_scale, 65535.0, "u16")}
+        if gated:
+            ok = d >= const(self.min_disp)                   # (false for NaN)
+            if self.max_uncertainty is not None:
+                ok = ok & (u <= const(self.max_uncertainty))                     # (false for NaN)
         if self.depth is not None:
-            valid = d >= const(self.min_disp)                # (false for NaN)
-            z = torch.where(valid, const(self.fb) / d, const(math.inf))          # tensor / tensor: a correctly rounded fp32 division
+            z = const(self.fb) / d                           # tensor / tensor: a correctly rounded fp32 division
+            valid = ok if self.max_depth is None else ok & (z <= const(self.max_depth))
+            z = torch.where(valid, z, const(math.inf))
             if self.depth == "u16":
                 out["depth"] = torch.where(valid, quant(z, self.depth_scale, 65535.0, "u16").to(torch.int32), 0).to(torch.uint16)
             else:
                 out["depth"] = z if self.depth == "f32" else z.to(torch.float16)
         if self.uncertainty is not None:
-            if u is None:
-                raise ValueError("OutputSpec.reference: an uncertainty plane is requested and no uncertainty was given")
-            u = u.float().abs()
             out["uncertainties"] = u if self.uncertainty == "f32" else quant(u, 255.0, 255.0, "u8")
+        if self.points is not None:
+            if d.dim() < 2:
+                raise ValueError(f"OutputSpec.reference: points take the pixel grid from d's last two dimensions, got {tuple(d.shape)}")
+            x = torch.arange(d.shape[-1], dtype=torch.float32, device=d.device)
+            y = torch.arange(d.shape[-2], dtype=torch.float32, device=d.device)[:, None]
+            q = self.Q.to(d.device)
+            v = [((q[i, 0] * x + q[i, 1] * y) + q[i, 2] * d) + q[i, 3] for i in range(4)]       # one fp32 operation each, in this order
+            xyz = [v[i] / v[3] for i in range(3)]
+            valid = ok if self.max_depth is None else ok & (xyz[2] > 0) & (xyz[2] <= const(self.max_depth))
+            comps = [torch.where(valid, c, const(math.nan)) for c in xyz] + ([u.expand_as(d)] if self.points_layout == "xyzw" else [])
+            pts = torch.stack(comps, dim=-1)
+            if d.dim() >= 4 and d.shape[-3] == 1:
+                pts = pts.squeeze(-4)
+            out["points"] = pts if self.points == "f32" else pts.to(torch.float16)
         return out
 
 
@@ -1291,7 +1386,8 @@ class _EgressCall:
         if not 0 <= f0 < f1 <= eng.T:
             raise ValueError(f"output: frames = {(f0, f1)} is no range inside the window's {eng.T} frames")
         planes = self.spec.empty(f1 - f0, h0, w0, eng.FLOW_OUT.device)
-        eng.egress(self.spec.struct(planes), f0, f1 - f0, pad_left, pad_top, h0, w0)
+        out = self.spec.scene_struct(planes) if self.spec.scene else self.spec.struct(planes)      # ppms_scene_egress / ppms_disparity_egress
+        eng.egress(out, f0, f1 - f0, pad_left, pad_top, h0, w0)
         return planes
 
 

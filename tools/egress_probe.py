@@ -7,7 +7,11 @@ median / min / max whole-call ms (host video -> host results), the device->host 
 upsampling of a one-window call (library launches and torch ops that launch; counted in one extra call after the timed ones, with Python-level
 hooks that the timed calls never see).  Config 2: T = 5, 320x512, iters = 10 (one window); --windows adds T = 30 at kernel_size = 20 (three
 windows through the ClipPipeline: only kept frames cross on side B).  The bar: B's median is not above A's by more than the
-+-2 % same-box spread."""
++-2 % same-box spread.
+    python tools/egress_probe.py --points [--runs 12]
+The point-cloud A/B, both sides on this tree and on a uint8 video that lies on the device: A = forward(test_mode=True), then the same arithmetic
+in torch on the device (OutputSpec.reference on the float32 results) and the cloud's copy to the host; B = forward(..., output=spec) -- "xyz" f32
+points with both gates, from the one ppms_scene_egress launch -- and the same copy.  The two clouds are compared bit for bit (NaN = NaN)."""
 import argparse
 import os
 import statistics
@@ -16,7 +20,7 @@ import sys
 import time
 
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LAUNCHES = ("ppms_convex_upsample", "ppms_convex_upsample_3d", "ppms_bilinear", "ppms_disparity_egress")
+LAUNCHES = ("ppms_convex_upsample", "ppms_convex_upsample_3d", "ppms_bilinear", "ppms_disparity_egress", "ppms_scene_egress")
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ worker
@@ -42,6 +46,13 @@ def worker(tree: str, side: str):
     def setup(T, H, W, iters):
         state["video"] = Wm.hash_uniform((T, 2, 3, H, W), 613, 0.0, 255.0).round().contiguous()
         state["call"] = lambda: m.forward_batch_test({"stereo_video": state["video"]}, kernel_size=20, iters=iters, **kw)
+        if side.startswith("points"):
+            spec = P.OutputSpec(uncertainty=None, points="f32", Q=P.OutputSpec.q_matrix(721.5377, 0.54, W / 2, H / 2), max_uncertainty=0.5, max_depth=50.0)
+            i1, i2 = (state["video"][:, k][None].to(torch.uint8).to(dev) for k in (0, 1))
+            if side == "points":
+                state["call"] = lambda: {"points": m.forward(i1, i2, iters=iters, test_mode=True, output=spec)["points"].cpu()}
+            else:
+                state["call"] = lambda: {"points": spec.reference(*m.forward(i1, i2, iters=iters, test_mode=True))["points"].cpu()}
         for _ in range(3):
             state["call"]()
         torch.cuda.synchronize()
@@ -92,7 +103,10 @@ def worker(tree: str, side: str):
             say("ms", f"{1e3 * (time.perf_counter() - t0):.3f}")
         elif cmd[0] == "shape":
             o = state["out"]
-            say("shape", ";".join(f"{k}:{str(v.dtype).replace('torch.', '')}{list(v.shape)}" for k, v in o.items() if torch.is_tensor(v)))
+            say("shape", ";".join(f"{k}:{str(v.dtype).replace('torch.', '')}{list(v.shape)}".replace(" ", "") for k, v in o.items() if torch.is_tensor(v)))
+        elif cmd[0] == "digest":
+            import hashlib
+            say("digest", hashlib.sha256(state["out"]["points"].nan_to_num(nan=-1.0).numpy().tobytes()).hexdigest()[:16])
         elif cmd[0] == "count":
             count()
         elif cmd[0] == "quit":
@@ -114,7 +128,7 @@ class Side:
             if not line:
                 raise RuntimeError(f"worker '{self.label}' ended (exit {self.p.wait()})")
             parts = line.split()
-            if parts and parts[0] in ("ready", "ms", "shape", "count"):
+            if parts and parts[0] in ("ready", "ms", "shape", "count", "digest"):
                 return parts[1:]
 
     def close(self):
@@ -131,14 +145,19 @@ def main():
     ap.add_argument("--parent", default=None, help="tree of the parent commit with its libppms.so built (default: this tree's default path)")
     ap.add_argument("--runs", type=int, default=12)
     ap.add_argument("--windows", action="store_true", help="also T = 30 at kernel_size = 20: three windows through the ClipPipeline")
+    ap.add_argument("--points", action="store_true", help="the point-cloud A/B instead: the reprojection in torch on the device against ppms_scene_egress")
     ap.add_argument("--worker", default=None)
     ap.add_argument("--tree", default=HERE)
     a = ap.parse_args()
     if a.worker:
         return worker(os.path.abspath(a.tree), a.worker)
     ptree = os.path.abspath(a.parent) if a.parent else HERE
-    A = Side("output=None, " + ("parent commit's tree" if a.parent else "this tree (default path as in the parent)"), ptree, "default")
-    B = Side('output=OutputSpec(disparity="u16", uncertainty="u8"), this tree', HERE, "egress")
+    if a.points:
+        A = Side("forward(), then OutputSpec.reference in torch on the device, points -> host", HERE, "points_torch")
+        B = Side('forward(output=OutputSpec(points="f32", Q=..., max_uncertainty=0.5, max_depth=50)), points -> host', HERE, "points")
+    else:
+        A = Side("output=None, " + ("parent commit's tree" if a.parent else "this tree (default path as in the parent)"), ptree, "default")
+        B = Side('output=OutputSpec(disparity="u16", uncertainty="u8"), this tree', HERE, "egress")
     try:
         for T, H, W, iters, runs in [(5, 320, 512, 10, a.runs)] + ([(30, 320, 512, 10, max(3, a.runs // 3))] if a.windows else []):
             for s in (A, B):
@@ -147,7 +166,8 @@ def main():
             for _ in range(runs):
                 for s in (A, B):                                # alternate: one whole call each
                     ms[s].append(float(s.ask("run")[0]))
-            print(f"== T = {T}, {H}x{W}, iters = {iters}, kernel_size = 20: forward_batch_test(host video) -> host results, {runs} alternating calls per side")
+            what = "forward(device uint8 video) -> host points" if a.points else "forward_batch_test(host video) -> host results"
+            print(f"== T = {T}, {H}x{W}, iters = {iters}, kernel_size = 20: {what}, {runs} alternating calls per side")
             for s in (A, B):
                 v = ms[s]
                 shape = s.ask("shape")[0]
@@ -159,6 +179,9 @@ def main():
                 print(f"    behind the last convex upsampling: {n_dev} device launches / copies, {n_host} host torch ops  ({names})")
             ma, mb = statistics.median(ms[A]), statistics.median(ms[B])
             print(f"egress median / default median = {mb / ma:.4f} ({mb - ma:+.2f} ms)")
+            if a.points:
+                da, db = A.ask("digest")[0], B.ask("digest")[0]
+                print(f"points digest A {da}  B {db}: {'bit-identical' if da == db else 'DIFFERENT'}")
             print()
         print("host: cpus", os.cpu_count(), "loadavg", os.getloadavg())
     finally:
