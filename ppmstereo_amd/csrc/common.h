@@ -93,9 +93,11 @@ __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf
 
 // Branch-free transcendentals of the fused epilogues (GRU gates, GELU): the ocml erff / tanhf / expf + IEEE division cost
 // 25-60 instructions per element with divergent range branches, which made the activation the longest part of the
-// per-pixel layer chains and ~3 % of an iteration.  These use the raw v_exp_f32 / v_rcp_f32 (1 ulp each); absolute
-// errors: sigmoid, tanh <= ~1e-7, erf <= 1.5e-7 (Abramowitz & Stegun 7.1.26), i.e. the rounding level of fp32 values
-// of magnitude 1, far inside the 3e-5 tolerance the bf16x3 convolutions are tested to.  NaN propagates.
+// per-pixel layer chains and ~3 % of an iteration.  These use the raw v_exp_f32 / v_rcp_f32 (1 ulp each).  Absolute
+// errors measured on the MI355X over the whole fp32 range, NaN and +-inf included (tests/test_gpu_act_sweep.py, docs/LOG_r14.md):
+// sigmoid 7.7e-8, tanh 1.7e-7 (x ~ -0.6; an fp32 emulation with exact exp2 / rcp reaches 1.9e-7 at x ~ -1.55), GELU
+// 1.9e-7 max(1, |x|) (erf: Abramowitz & Stegun 7.1.26, 1.5e-7) -- the rounding level of fp32 values of magnitude 1,
+// inside the 2^-20 max(1, |x|) those tests hold them to and far inside the 3e-5 of the bf16x3 convolutions.  NaN propagates.
 __device__ __forceinline__ float exp_fast(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
 __device__ __forceinline__ float sigmoid_fast(float x) { return __builtin_amdgcn_rcpf(1.0f + exp_fast(-x)); }
 __device__ __forceinline__ float tanh_fast(float x) {
