@@ -1,5 +1,5 @@
-"""Descriptor-driven float64 reference for the planned convolution launches (helper of tests/test_gpu_plan_audit.py and
-tests/test_conv_audit_ref.py; not a test module itself).
+"""Descriptor-driven float64 reference for the planned convolution launches (helper of tests/test_gpu_plan_audit.py,
+tests/test_gpu_plan_audit_geometries.py and tests/test_conv_audit_ref.py; not a test module itself).
 
 Given a ``ConvOp`` (or a bare ``ppms_conv`` descriptor with its kernel identity) and the objects that own its buffers, this module
 
@@ -13,13 +13,18 @@ Given a ``ConvOp`` (or a bare ``ppms_conv`` descriptor with its kernel identity)
   columns cross every tile boundary of any tiling;
 * and checks a launch: accuracy on the sample, no byte changed outside the declared output regions, no read/write overlap, the split-bf16
   representation of SP outputs, bitwise determinism.
+
+The last section audits whole engines: every planned launch of the engines of one geometry (``audit_geometry``), with a census of what the
+planner chose for which conv (``Census``), which the geometry audit's conditions read.
 """
 from __future__ import annotations
 
 import bisect
+import collections
 import ctypes as C
+import gc
 import math
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import torch
 
@@ -27,6 +32,7 @@ from ppmstereo_amd import _lib as L
 from ppmstereo_amd import packing as P
 from ppmstereo_amd import convplan
 from ppmstereo_amd.convplan import CONV2, CONV5, CONV6, GEMM1, KERNEL_NAMES, STREAM, ConvOp, kernel_record, sweep_taps
+from ppmstereo_amd.dist import FrameShard
 
 ACC_MAX = 3e-5      # per epilogue half: max |got - ref| <= ACC_MAX * max(1, max |ref|)  (the kernel tests' bound, tests/test_gpu_ops.py)
 ACC_RMS = 2e-5      # and rms(got - ref) <= ACC_RMS * rms(ref)
@@ -462,8 +468,8 @@ def got_values(d, pool: Pool, rs: List[Region], pix: torch.Tensor) -> Dict[str, 
     return got
 
 
-def compare(exp: Dict[str, torch.Tensor], got: Dict[str, torch.Tensor], d) -> (List[str], Dict[str, List[int]]):
-    """(failures, bad couts per output) under the per-half bounds."""
+def compare(exp: Dict[str, torch.Tensor], got: Dict[str, torch.Tensor], d, ratios: Optional[dict] = None) -> (List[str], Dict[str, List[int]]):
+    """(failures, bad couts per output) under the per-half bounds.  ratios (optional dict): receives output name -> the measured max error / its bound."""
     fails, bad = [], {}
     for name, ref in exp.items():
         g = got[name]
@@ -474,6 +480,8 @@ def compare(exp: Dict[str, torch.Tensor], got: Dict[str, torch.Tensor], d) -> (L
             err = err - (ref.abs() * 2.0 ** -8 + 2.0 ** -24)
         colmax = torch.where(torch.isnan(err), torch.full_like(err, float("inf")), err).amax(0) if err.numel() else err
         cols = torch.nonzero(~(colmax <= tol)).reshape(-1).tolist()
+        if ratios is not None and err.numel():
+            ratios[name] = colmax.max().item() / tol
         if cols:
             bad[name] = cols
             fails.append(f"{name}: max err {colmax.max().item():.3e} > {tol:.3e} at couts {cols[:16]}{' ...' if len(cols) > 16 else ''}")
@@ -494,9 +502,17 @@ class Report:
     def __init__(self, name, op):
         d = op.desc
         self.name, self.kernel = name, kernel_name(op)
+        self.conv = name.rsplit(":", 1)[-1]          # the conv's own name ("engine tag:conv")
         self.sliced = op.nslice > 1
         self.swept = swept(op.version, op.ysweep, d)
         self.halo = d.t_halo > 0
+        # what the planner decided, and the facts of the descriptor its thresholds look at (the census conditions of the geometry audit)
+        self.nslice, self.ysweep = int(op.nslice), bool(op.ysweep)
+        self.pixels = d.T * d.H * d.W
+        self.taps = (d.kt, d.kh, d.kw)
+        self.couts = d.epi[0].n_valid + (d.epi[1].n_valid if d.m_split < d.M else 0)
+        self.vt = any(d.epi[h].kind == L.EPI_STORE and bool(d.epi[h].out_vt) for h in _halves(d))
+        self.worst = 0.0                             # worst max-error / bound over the outputs of the launch (compare())
         self.launched = False
         self.failures: List[str] = []
         self.bad: Dict[str, List[int]] = {}
@@ -531,9 +547,11 @@ def audit_op(name: str, op: ConvOp, pool: Pool, seed: int = 0, ref_desc=None, wc
     torch.cuda.synchronize()
     rep.launched = True
     # 1. accuracy on the sample
-    f, bad = compare(exp, got_values(d, pool, rs, pix), d)
+    ratios = {}
+    f, bad = compare(exp, got_values(d, pool, rs, pix), d, ratios)
     rep.failures += f
     rep.bad = bad
+    rep.worst = max(ratios.values(), default=0.0)
     # 2. no byte changed outside the declared output regions (inputs, halo rows, padded couts, neighbouring channels)
     outs = [r for r in rs if r.role in ("out", "inout")]
     for r in outs:
@@ -613,3 +631,181 @@ def conv_ops(obj) -> Dict[str, ConvOp]:
     else:
         seq = obj.steps
     return {f"{type(obj).__name__}[{i}]": v for i, v in enumerate(seq) if isinstance(v, ConvOp)}
+
+
+# ------------------------------------------------------------------------------------------------ whole engines (the plan audits)
+class HaloGeometry:
+    """What a ScaleEngine reads from a dist.FrameShard to lay out a rank's window (f of f * world frames, halo slabs of FrameShard.HALO frames
+    on both sides) -- and nothing else: the audit never exchanges data, so any other attribute access is an error."""
+
+    HALO = FrameShard.HALO
+
+    def __init__(self, f=5, world=8, rank=3):
+        self.rank, self.world, self.f, self.T = rank, world, f, f * world
+        self.lo, self.hi = rank * f, (rank + 1) * f
+        self.group, self.force_comm = None, False
+
+    def __getattr__(self, name):
+        raise AssertionError(f"the plan audit must not exchange data (FrameShard.{name})")
+
+
+def release():
+    """Free released engines now: a ScaleEngine sits in reference cycles (bound methods and closures in its launch table), so dropping the
+    last reference frees its gigabytes only when the cyclic collector runs."""
+    torch.cuda.synchronize()
+    gc.collect()
+    torch.cuda.empty_cache()
+
+
+class Launch(NamedTuple):
+    """One audited launch as the census keeps it: what the planner chose for which conv, and the descriptor facts its thresholds read."""
+    conv: str           # the conv's name in its engine ("zr1_0_x", "final_0", "_FnetEngine[3]")
+    scale: int          # map divisor of the update block (4, 8, 16); 0: an encoder engine
+    convex3d: bool
+    kernel: str
+    nslice: int
+    ysweep: bool
+    pixels: int         # P = T * H * W of the launch
+    taps: tuple         # (kt, kh, kw)
+    couts: int          # stored couts (both halves)
+    vt: bool            # writes V^T
+    halo: bool          # t_halo > 0
+    worst: float        # max error / bound
+
+
+class Census:
+    def __init__(self):
+        self.k = collections.OrderedDict()
+        self.launches: List[Launch] = []
+
+    def add(self, rep: Report, scale: int = 0, convex3d: bool = False):
+        c = self.k.setdefault(rep.kernel, collections.Counter())
+        c["n"] += 1
+        c["sliced"] += rep.sliced
+        c["swept"] += rep.swept
+        c["halo"] += rep.halo
+        self.launches.append(Launch(rep.conv, scale, convex3d, rep.kernel, rep.nslice, rep.ysweep, rep.pixels, rep.taps, rep.couts, rep.vt,
+                                    rep.halo, rep.worst))
+
+    def line(self):
+        total = sum(c["n"] for c in self.k.values())
+        return f"{total} launches: " + ", ".join(f"{k} {c['n']} (sliced {c['sliced']}, swept {c['swept']}, halo'd {c['halo']})" for k, c in sorted(self.k.items()))
+
+    def served(self, kernel: str, scale: int) -> List[str]:
+        """The convs `kernel` serves at an update block's scale, in launch order, each name once."""
+        return list(dict.fromkeys(l.conv for l in self.launches if l.kernel == kernel and l.scale == scale))
+
+    def plans(self) -> str:
+        """What the thresholds decided: per kernel the K-slice plans in use (y: the y-swept form), the launches on either side of the 4096-pixel
+        threshold of conv_stream / gemm1, and the worst measured max-error / bound."""
+        by = collections.OrderedDict()
+        for l in sorted(self.launches, key=lambda l: l.kernel):
+            e = by.setdefault(l.kernel, dict(s=collections.Counter(), small=0, n=0, worst=0.0))
+            e["s"][f"{'y' if l.ysweep else ''}s{l.nslice}"] += 1
+            e["small"] += l.pixels <= 4096
+            e["n"] += 1
+            e["worst"] = max(e["worst"], l.worst)
+        out = []
+        for k, e in by.items():
+            s = " ".join(f"{p} x{n}" for p, n in sorted(e["s"].items()))
+            small = f", P <= 4096: {e['small']} of {e['n']}" if k in ("conv_stream", "gemm1") else ""
+            out.append(f"{k} [{s}{small}; worst err/bound {e['worst']:.3f}]")
+        return "; ".join(out)
+
+
+def audit_engine(tag: str, eng, census: Census, fails: list, seed: int, scale: int = 0, convex3d: bool = False) -> int:
+    ops = conv_ops(eng)
+    pool = Pool(eng)
+    present = {id(o) for o in pool.convops}
+    assert len(present) == len(ops) and present == {id(o) for o in ops.values()}, \
+        f"{tag}: {len(present)} ConvOps in the engine, {len(ops)} listed for the audit"
+    wcache = {}
+    for i, (name, op) in enumerate(ops.items()):
+        rep = audit_op(f"{tag}:{name}", op, pool, seed=seed + i, wcache=wcache)
+        census.add(rep, scale, convex3d)
+        if rep.failures:
+            fails.append(str(rep))
+    return len(ops)
+
+
+def audit_with_bias_entry_off(name: str, op: ConvOp, eng, k: int, out: str, seed: int) -> Report:
+    """The audit's sensitivity on one launch of an engine: `op` must pass as it is; then the same descriptor is launched with a test-owned
+    bias copy whose entry k (a row of the pack) is off by 2^-10 max |ref of output `out`| -- an in-bounds descriptor -- and audited against
+    the reference of the ORIGINAL bias.  -> the report of that second audit (the caller asserts that it fails and names the cout)."""
+    pool = Pool(eng)
+    dev = pix_device(pool)
+    rep = audit_op(name, op, pool, seed=seed)
+    assert rep.launched and not rep.failures, str(rep)
+    rs, errs = bind_regions(op.desc, pool)
+    assert not errs
+    fill_storages(pool, rs, op.desc, seed)
+    pix = pixel_sample(op.desc.T, op.desc.H, op.desc.W, seed, dev)
+    amax = reference(op.desc, op.version, op.ysweep, pool, rs, pix)[out].abs().max().item()
+    bias = next(r for r in rs if r.name == "bias").view(pool)[0].clone()
+    bias[k] += 2.0 ** -10 * amax
+    d2 = L.Conv.from_buffer_copy(bytes(op.desc))
+    d2.bias = bias.data_ptr()
+    op2 = ConvOp(d2, op.keep + [bias], op.version, op.wm_hint, nslice=op.nslice, ysweep=op.ysweep, device=dev)
+    assert (op2.version, op2.nslice, op2.ysweep) == (op.version, op.nslice, op.ysweep)
+    return audit_op(f"{name} (bias entry {k} perturbed)", op2, Pool(eng, extra=[bias]), seed=seed, ref_desc=op.desc)
+
+
+SCALES = (("update_block16", 16, 0), ("update_block08", 8, 1), ("update_block04", 4, 2))     # block, map divisor, Attention_qk index
+
+
+def load_models(device) -> dict:
+    """The hot path for both use_convex_3d values and the three encoder modules, with the synthetic weights, on `device`."""
+    assert torch.cuda.is_available(), "these tests need the MI355X (no CPU fallback exists)"
+    from ppmstereo_amd import weights as Wm
+    from ppmstereo_amd.cnet import Feature
+    from ppmstereo_amd.encoder import BasicEncoder
+    from ppmstereo_amd.ppmstereo import PPMStereoHotPath
+    from ppmstereo_amd.sst import SSTBlock
+    hot = {c3: PPMStereoHotPath(use_convex_3d=c3).load_hot_path_weights(Wm.hot_path_weights(use_convex_3d=c3)).to(device).eval() for c3 in (False, True)}
+    fnet = BasicEncoder(output_dim=256, norm_fn="instance")
+    fnet.load_state_dict(Wm.fnet_weights(), strict=True)
+    cnet = Feature("tiny", 256)
+    cnet.load_state_dict(Wm.cnet_weights(), strict=True)
+    sst = SSTBlock()
+    sst.load_state_dict(Wm.sst_weights(), strict=True)
+    return dict(hot=hot, fnet=fnet.to(device).eval(), cnet=cnet.to(device).eval(), sst=sst.to(device).eval())
+
+
+def audit_geometry(models: dict, name: str, T: int, H: int, W: int, convex=(False, True), encoders: bool = False, shard=None, device="cuda:0"):
+    """Every planned conv launch of one geometry: the three ScaleEngines of each use_convex_3d value with their q/k projection, and (encoders)
+    the fnet / cnet / SST engines.  T: frames this engine holds; shard: (world, rank) of a frame-sharded window whose rank holds T frames
+    between halo slabs.  -> (census, failure lines, launches audited)."""
+    from ppmstereo_amd.cnet import _CnetEngine
+    from ppmstereo_amd.encoder import _FnetEngine
+    from ppmstereo_amd.sst import _SstEngine
+    release()                      # (also whatever engines earlier test files left to the cyclic collector)
+    census, fails, audited = Census(), [], 0
+    dev = torch.device(device)
+    for c3 in convex:
+        hot = models["hot"][c3]
+        for blk_name, s, ai in SCALES:
+            blk = getattr(hot, blk_name)
+            geo = HaloGeometry(f=T, world=shard[0], rank=shard[1]) if shard is not None else None
+            eng = blk.engine(T, H // s, W // s, dev, shard=geo)
+            assert eng.halo == (FrameShard.HALO if shard is not None else 0)
+            eng.qk_op(hot.att[ai].packed(dev))                   # the q/k projection begin() launches
+            audited += audit_engine(f"{name}/{blk_name}{'/convex3d' if c3 else ''}", eng, census, fails, seed=1000 * s + 7 * c3, scale=s, convex3d=c3)
+            del eng
+            blk._engines.clear()
+            release()
+    if encoders:
+        fnet, cnet, sst = models["fnet"], models["cnet"], models["sst"]
+        eng = _FnetEngine(fnet._pack(dev), 2 * T, H, W, dev, 256)          # left + right images in one call (ppmstereo.py:618)
+        audited += audit_engine(f"{name}/fnet", eng, census, fails, seed=11)
+        del eng
+        release()
+        eng = _CnetEngine(cnet._pack(dev), T, H, W, dev)
+        audited += audit_engine(f"{name}/cnet", eng, census, fails, seed=12)
+        del eng
+        release()
+        eng = _SstEngine(sst._pack(dev), sst.time_embed.detach().float()[0], T, H // 16, W // 16, dev)
+        audited += audit_engine(f"{name}/sst", eng, census, fails, seed=13)
+        del eng
+        release()
+    assert audited == len(census.launches) == sum(c["n"] for c in census.k.values())
+    return census, fails, audited

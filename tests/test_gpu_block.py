@@ -379,6 +379,30 @@ def test_config2_full_size_vs_oracle(model):
     assert maxdiff(c1, rc) < 2e-4
 
 
+@pytest.mark.parametrize("T,H,Wd", [(3, 96, 288), (7, 128, 416)], ids=["T3_96x288", "T7_128x416"])
+def test_ragged_geometry_vs_oracle(model, T, H, Wd):
+    """The same comparison, with the same bounds, at two geometries off the baseline: T = 3 on 96x288 (maps 24x72, 12x36, 6x18) and T = 7
+    on 128x416 (maps 32x104, 16x52, 8x26: n = 208 at the 1/16 scale is no multiple of 64, and the window has more frames than the memory
+    pick keeps).  What the conv plan audit does not see at such sizes runs here: the correlation lookup, the per-pixel chains, the
+    depthwise 7x7, the memory read-out's tail masking, the time / space attention, the convex upsampling."""
+    feats = synth_cascade_feats(T, H, Wd)
+    rp, ru = [], []
+    rd, rc = O.cascade(W, feats, 2, T, rp, ru)
+    p1, u1 = [], []
+    d1, c1 = model.cascade({k: v.to(DEV) for k, v in feats.items()}, 2, T, p1, u1)
+    assert len(p1) == len(rp) == 4
+    worst = []
+    for i, (a, b) in enumerate(zip(p1, rp)):            # every prediction of the cascade, coarse to fine
+        assert torch.isfinite(a).all(), "non-finite GPU output"
+        err = (a.cpu() - b).abs()
+        worst.append((i, err.mean().item(), err.max().item()))
+        print(f"T = {T}, {H}x{Wd}, prediction {i}: mean |d disparity| {err.mean().item():.3e} px, max {err.max().item():.3e} px")
+    unc = maxdiff(c1, rc)
+    print(f"T = {T}, {H}x{Wd}: max |d uncertainty| {unc:.3e}")
+    assert all(mean < 2e-4 and mx < 1e-3 for _, mean, mx in worst), worst
+    assert unc < 2e-4
+
+
 def test_config3_geometry_vs_oracle(model):
     """BASELINE config 3 geometry (720x1280 -> 736x1280): (a) one iteration of the 1/16 scale (46x80, n = 3 680: not a multiple
     of 64, so the tail-masking attention kernel and the conv planners of that map run) against the oracle; (b) the whole
