@@ -225,14 +225,19 @@ for _door, _head in _INGEST_HEADS.items():
     _SIGS["ppms_video_ingest_" + _door + "_remap"] = (c_int, _head + [C.POINTER(RemapView)] * 2 + _INGEST_TAIL)
 EXPORTS = tuple(_SIGS)
 
-# (the export that reports sizeof of the header's structs, their ctypes twins, how the message names them)
+# (the export that reports sizeof of the structs, their ctypes twins, the message when they differ).  An export takes one int* per struct; one
+# without parameters (a single struct) returns the size.
 _STRUCT_SIZES = (
-    ("ppms_struct_sizes", (SP, Epilogue, Conv), "struct layout"),
-    ("ppms_yuv_struct_sizes", (YUVView, YUVMatrix), "layout of ppms_yuv_view / ppms_yuv_matrix"),
-    ("ppms_remap_struct_size", (RemapView,), "layout of ppms_remap_view"),
-    ("ppms_yuv_format_struct_size", (YUVFormat,), "layout of ppms_yuv_format"),
-    ("ppms_raw_struct_sizes", (RawView, RawFormat), "layout of ppms_raw_view / ppms_raw_format"),
-    ("ppms_packed_struct_sizes", (PackedView, YUVPackedFormat, RawPackedFormat), "layout of ppms_packed_view / ppms_yuv_packed_format / ppms_raw_packed_format"),
+    ("ppms_struct_sizes", (SP, Epilogue, Conv), "ctypes struct layout differs from include/ppms.h"),
+    ("ppms_yuv_struct_sizes", (YUVView, YUVMatrix), "ctypes layout of ppms_yuv_view / ppms_yuv_matrix differs from include/ppms.h"),
+    ("ppms_remap_struct_size", (RemapView,), "ctypes layout of ppms_remap_view differs from include/ppms.h"),
+    ("ppms_yuv_format_struct_size", (YUVFormat,), "ctypes layout of ppms_yuv_format differs from include/ppms.h"),
+    ("ppms_raw_struct_sizes", (RawView, RawFormat), "ctypes layout of ppms_raw_view / ppms_raw_format differs from include/ppms.h"),
+    ("ppms_packed_struct_sizes", (PackedView, YUVPackedFormat, RawPackedFormat),
+     "ctypes layout of ppms_packed_view / ppms_yuv_packed_format / ppms_raw_packed_format differs from include/ppms.h"),
+    ("ppms_egress_struct_size", (Egress,), "ctypes layout of ppms_egress differs from include/ppms.h"),
+    ("ppms_egress3d_struct_size", (Egress3D,), "ctypes layout of ppms_egress3d differs from include/ppms.h"),
+    ("ppms_pwchain_param_bytes", (ChainParams,), "ChainParams layout differs from pwchain.hip"),
 )
 
 _lib: Optional[C.CDLL] = None
@@ -258,17 +263,15 @@ def load() -> C.CDLL:
         fn.restype, fn.argtypes = res, args
     if lib.ppms_version() != 4:
         raise RuntimeError("ppmstereo_amd: libppms.so ABI version mismatch")
-    for export, structs, what in _STRUCT_SIZES:
-        sizes = [c_int() for _ in structs]
-        getattr(lib, export)(*(C.byref(x) for x in sizes))
-        if [x.value for x in sizes] != [C.sizeof(t) for t in structs]:
-            raise RuntimeError(f"ppmstereo_amd: ctypes {what} differs from include/ppms.h")
-    if lib.ppms_egress_struct_size() != C.sizeof(Egress):
-        raise RuntimeError("ppmstereo_amd: ctypes layout of ppms_egress differs from include/ppms.h")
-    if lib.ppms_egress3d_struct_size() != C.sizeof(Egress3D):
-        raise RuntimeError("ppmstereo_amd: ctypes layout of ppms_egress3d differs from include/ppms.h")
-    if lib.ppms_pwchain_param_bytes() != C.sizeof(ChainParams):
-        raise RuntimeError("ppmstereo_amd: ChainParams layout differs from pwchain.hip")
+    for export, structs, message in _STRUCT_SIZES:
+        if _SIGS[export][1]:
+            sizes = [c_int() for _ in structs]
+            getattr(lib, export)(*(C.byref(x) for x in sizes))
+            sizes = [x.value for x in sizes]
+        else:
+            sizes = [getattr(lib, export)()]
+        if sizes != [C.sizeof(t) for t in structs]:
+            raise RuntimeError("ppmstereo_amd: " + message)
     _lib = lib
     return lib
 

@@ -1,0 +1,332 @@
+// Output egress (ppmstereo_amd/engine.py: disparity_egress, driven by video.py's OutputSpec): the two one-launch-per-window kernels that
+// write the caller's disparity / depth / uncertainty planes and the point cloud, their shared pieces, checks and entry points.
+#include "common.h"
+
+// ------------------------------------------------------------------------------------------------ disparity egress
+// The 1/4-scale engine's state after its last iteration -> the caller's output planes, one launch (include/ppms.h: the formulas):
+// crop (InputPadder.unpad), frame range, |flow_up[:, 0]|, the 4x bilinear upsampling of the uncertainty, depth = fb / d and the
+// conversions to the planes' formats.  HBM bound: one thread = a run of EG_RUN consecutive x of one output row; the run is loaded
+// and stored 16 bytes at a time (8 for a run of bytes) where its address allows it, element by element at row ends and on
+// rows that start unaligned.  Every offset is 64-bit.
+constexpr int EG_RUN = 8;
+// bilinear_kernel's expression for output pixel (oy, ox) of one H x W source plane `s`, align_corners = 0, restated (every operation is one
+// fp32 operation in the same order, and the build contracts nothing: the same bits as ppms_bilinear with mul = 1).  bilinear_kernel does not
+// call it: routed through this function its instructions come out in another order, and its generated code is kept as it is.
+__device__ __forceinline__ float bilinear_tap(const float* __restrict__ s, int H, int W, float sh, float sw, int oy, int ox) {
+    const float fy = fmaxf(sh * (oy + 0.5f) - 0.5f, 0.0f);
+    const float fx = fmaxf(sw * (ox + 0.5f) - 0.5f, 0.0f);
+    const int y0 = (int)fy, x0 = (int)fx;
+    const int y1 = y0 + ((y0 < H - 1) ? 1 : 0), x1 = x0 + ((x0 < W - 1) ? 1 : 0);
+    const float ly = fy - y0, lx = fx - x0;
+    const float hy = 1.0f - ly, hx = 1.0f - lx;
+    return hy * (hx * s[y0 * W + x0] + lx * s[y0 * W + x1]) + ly * (hx * s[y1 * W + x0] + lx * s[y1 * W + x1]);
+}
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+// min(top, rint(v)) for v >= 0 (a magnitude times a positive scale); NaN -> 0
+__device__ __forceinline__ unsigned egress_quant(float v, float top) {
+    const float r = rintf(v);
+    return r != r ? 0u : (unsigned)fminf(r, top);
+}
+template <class T>
+__device__ __forceinline__ void egress_store_run(const ppms_egress_plane& p, int64_t frame, int y, int x0, int n, const T (&v)[EG_RUN]) {
+    T* dst = (T*)((char*)p.ptr + frame * p.frame_stride + (int64_t)y * p.pitch) + x0;
+    constexpr int BYTES = (int)sizeof(T) * EG_RUN;                       // 8 (u8), 16 (u16, f16) or 32 (f32)
+    constexpr int CHUNK = BYTES < 16 ? BYTES : 16;
+    if (n == EG_RUN && ((uintptr_t)dst & (CHUNK - 1)) == 0) {
+        if constexpr (BYTES < 16) {
+            gst<u32x2>(dst, __builtin_bit_cast(u32x2, v));
+        } else {
+            struct chunks { u32x4 q[BYTES / 16]; };
+            const chunks c = __builtin_bit_cast(chunks, v);
+#pragma unroll
+            for (int i = 0; i < BYTES / 16; ++i) gstore16((char*)dst + 16 * i, c.q[i]);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < EG_RUN; ++j)
+            if (j < n) dst[j] = v[j];
+    }
+}
+// ---- the pieces both kernels are built from
+// thread idx -> its run: n elements from column x0 of row y of output frame `frame`; (sy, sx) = the run's first pixel in the padded H x W frame
+struct egress_run { int x0, y, n, sy, sx; int64_t frame; };
+__device__ __forceinline__ egress_run egress_map(int64_t idx, int rpr, int H0, int W0, int pad_left, int pad_top) {
+    egress_run r;
+    r.x0 = (int)(idx % rpr) * EG_RUN;
+    const int64_t row = idx / rpr;                                       // frame * H0 + y of the output
+    r.y = (int)(row % H0);
+    r.frame = row / H0;
+    r.n = W0 - r.x0 < EG_RUN ? W0 - r.x0 : EG_RUN;                       // elements of this run inside the row
+    r.sy = r.y + pad_top, r.sx = r.x0 + pad_left;
+    return r;
+}
+// d = |flow_up[frame0 + frame, 0]| over the run (past the row's end the last element again)
+__device__ __forceinline__ void egress_load_disparity(const float* __restrict__ flow_up, int H, int W, int frame0, const egress_run& r,
+                                                      float (&d)[EG_RUN]) {
+    const float* s = flow_up + ((frame0 + r.frame) * 2 * H + r.sy) * W + r.sx;      // channel 0 of (T, 2, H, W)
+    if (r.n == EG_RUN && ((uintptr_t)s & 15) == 0) {
+        const f32x4 a = gld<f32x4>(s), b = gld<f32x4>(s + 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            d[j] = a[j];
+            d[4 + j] = b[j];
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < EG_RUN; ++j) d[j] = s[j < r.n ? j : r.n - 1];
+    }
+#pragma unroll
+    for (int j = 0; j < EG_RUN; ++j) d[j] = fabsf(d[j]);
+}
+// u = |the 4x bilinear upsampling of unc[frame0 + frame]| over the run
+__device__ __forceinline__ void egress_load_uncertainty(const float* __restrict__ unc, int H, int W, int frame0, float sh, float sw,
+                                                        const egress_run& r, float (&u)[EG_RUN]) {
+    const int h = H / 4, w = W / 4;
+    const float* s = unc + (frame0 + r.frame) * h * w;
+#pragma unroll
+    for (int j = 0; j < EG_RUN; ++j) u[j] = fabsf(bilinear_tap(s, h, w, sh, sw, r.sy, r.sx + (j < r.n ? j : r.n - 1)));
+}
+__device__ __forceinline__ void egress_store_disparity(const ppms_egress& o, const egress_run& r, const float (&d)[EG_RUN]) {
+    if (o.disparity.format == PPMS_FMT_F32) {
+        egress_store_run(o.disparity, r.frame, r.y, r.x0, r.n, d);
+    } else if (o.disparity.format == PPMS_FMT_F16) {
+        _Float16 v[EG_RUN];
+#pragma unroll
+        for (int j = 0; j < EG_RUN; ++j) v[j] = (_Float16)d[j];
+        egress_store_run(o.disparity, r.frame, r.y, r.x0, r.n, v);
+    } else {
+        uint16_t v[EG_RUN];
+#pragma unroll
+        for (int j = 0; j < EG_RUN; ++j) v[j] = (uint16_t)egress_quant(d[j] * o.disp_scale, 65535.0f);
+        egress_store_run(o.disparity, r.frame, r.y, r.x0, r.n, v);
+    }
+}
+// z and its validity come from the caller (the gates differ between the kernels): z = +inf where !ok
+__device__ __forceinline__ void egress_store_depth(const ppms_egress& o, const egress_run& r, const float (&z)[EG_RUN], const bool (&ok)[EG_RUN]) {
+    if (o.depth.format == PPMS_FMT_F32) {
+        egress_store_run(o.depth, r.frame, r.y, r.x0, r.n, z);
+    } else if (o.depth.format == PPMS_FMT_F16) {
+        _Float16 v[EG_RUN];
+#pragma unroll
+        for (int j = 0; j < EG_RUN; ++j) v[j] = (_Float16)z[j];
+        egress_store_run(o.depth, r.frame, r.y, r.x0, r.n, v);
+    } else {
+        uint16_t v[EG_RUN];
+#pragma unroll
+        for (int j = 0; j < EG_RUN; ++j) v[j] = ok[j] ? (uint16_t)egress_quant(z[j] * o.depth_scale, 65535.0f) : (uint16_t)0;
+        egress_store_run(o.depth, r.frame, r.y, r.x0, r.n, v);
+    }
+}
+__device__ __forceinline__ void egress_store_uncertainty(const ppms_egress& o, const egress_run& r, const float (&u)[EG_RUN]) {
+    if (o.uncertainty.format == PPMS_FMT_F32) {
+        egress_store_run(o.uncertainty, r.frame, r.y, r.x0, r.n, u);
+    } else {
+        uint8_t v[EG_RUN];
+#pragma unroll
+        for (int j = 0; j < EG_RUN; ++j) v[j] = (uint8_t)egress_quant(u[j] * 255.0f, 255.0f);
+        egress_store_run(o.uncertainty, r.frame, r.y, r.x0, r.n, v);
+    }
+}
+__global__ __launch_bounds__(256) void disparity_egress_kernel(const float* __restrict__ flow_up, const float* __restrict__ unc, ppms_egress o,
+                                                                int H, int W, int frame0, int pad_left, int pad_top, int H0, int W0, float sh,
+                                                                float sw, int rpr, int64_t total) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const egress_run r = egress_map(idx, rpr, H0, W0, pad_left, pad_top);
+    if (o.disparity.ptr || o.depth.ptr) {
+        float d[EG_RUN];
+        egress_load_disparity(flow_up, H, W, frame0, r, d);
+        if (o.disparity.ptr) egress_store_disparity(o, r, d);
+        if (o.depth.ptr) {
+            float z[EG_RUN];
+            bool ok[EG_RUN];
+#pragma unroll
+            for (int j = 0; j < EG_RUN; ++j) {
+                ok[j] = d[j] >= o.min_disp;                              // false for NaN
+                z[j] = ok[j] ? __fdiv_rn(o.fb, d[j]) : INFINITY;
+            }
+            egress_store_depth(o, r, z, ok);
+        }
+    }
+    if (o.uncertainty.ptr) {
+        float u[EG_RUN];
+        egress_load_uncertainty(unc, H, W, frame0, sh, sw, r, u);
+        egress_store_uncertainty(o, r, u);
+    }
+}
+// ---- point-cloud egress (include/ppms.h: the formulas).  disparity_egress_kernel's thread mapping, loads and plane stores, plus the two gates
+// and the reprojection with q: a run of points is EG_RUN * C contiguous elements (48 to 128 bytes), stored 16 bytes at a time where the run is
+// whole and its address 16-byte aligned, element by element otherwise.  The upsampled uncertainty is computed once per pixel, where a plane,
+// a gate or w needs it.  Every branch on the struct's fields is wave-uniform.  The mapping, loads and plane stores are the shared pieces above.
+template <class T, int C>
+__device__ __forceinline__ void egress_store_points(const ppms_egress_plane& p, int64_t frame, int y, int x0, int n, const float (&X)[EG_RUN],
+                                                    const float (&Y)[EG_RUN], const float (&Z)[EG_RUN], const float (&u)[EG_RUN]) {
+    T v[EG_RUN * C];
+#pragma unroll
+    for (int j = 0; j < EG_RUN; ++j) {
+        v[j * C] = (T)X[j];
+        v[j * C + 1] = (T)Y[j];
+        v[j * C + 2] = (T)Z[j];
+        if constexpr (C == 4) v[j * C + 3] = (T)u[j];
+    }
+    T* dst = (T*)((char*)p.ptr + frame * p.frame_stride + (int64_t)y * p.pitch) + (int64_t)x0 * C;
+    constexpr int BYTES = (int)sizeof(T) * EG_RUN * C;                   // 48, 64 (f16), 96 or 128 (f32)
+    if (n == EG_RUN && ((uintptr_t)dst & 15) == 0) {
+        struct chunks { u32x4 q[BYTES / 16]; };
+        const chunks c = __builtin_bit_cast(chunks, v);
+#pragma unroll
+        for (int i = 0; i < BYTES / 16; ++i) gstore16((char*)dst + 16 * i, c.q[i]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < EG_RUN; ++j)
+            if (j < n) {
+#pragma unroll
+                for (int c = 0; c < C; ++c) dst[j * C + c] = v[j * C + c];
+            }
+    }
+}
+__global__ __launch_bounds__(256) void scene_egress_kernel(const float* __restrict__ flow_up, const float* __restrict__ unc, ppms_egress3d e, int H,
+                                                            int W, int frame0, int pad_left, int pad_top, int H0, int W0, float sh, float sw, int rpr,
+                                                            int64_t total) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const ppms_egress& o = e.base;
+    const egress_run r = egress_map(idx, rpr, H0, W0, pad_left, pad_top);
+    const bool gated = o.depth.ptr || e.points.ptr;                      // a plane the gates act on
+    const bool gate_u = e.max_uncertainty < INFINITY, gate_z = e.max_depth < INFINITY;
+    float u[EG_RUN];
+    if (o.uncertainty.ptr || (gated && gate_u) || (e.points.ptr && e.points_components == 4)) {
+        egress_load_uncertainty(unc, H, W, frame0, sh, sw, r, u);
+    } else {
+#pragma unroll
+        for (int j = 0; j < EG_RUN; ++j) u[j] = 0.0f;
+    }
+    if (o.uncertainty.ptr) egress_store_uncertainty(o, r, u);
+    if (!o.disparity.ptr && !gated) return;
+    float d[EG_RUN];
+    egress_load_disparity(flow_up, H, W, frame0, r, d);
+    if (o.disparity.ptr) egress_store_disparity(o, r, d);
+    bool ok[EG_RUN];                                                     // valid_d and valid_u (both false for NaN)
+#pragma unroll
+    for (int j = 0; j < EG_RUN; ++j) ok[j] = d[j] >= o.min_disp && (!gate_u || u[j] <= e.max_uncertainty);
+    if (o.depth.ptr) {
+        float z[EG_RUN];
+        bool okz[EG_RUN];
+#pragma unroll
+        for (int j = 0; j < EG_RUN; ++j) {
+            const float q = __fdiv_rn(o.fb, d[j]);
+            okz[j] = ok[j] && (!gate_z || q <= e.max_depth);
+            z[j] = okz[j] ? q : INFINITY;
+        }
+        egress_store_depth(o, r, z, okz);
+    }
+    if (e.points.ptr) {
+        const float yf = (float)r.y;                                      // the pixel's row and column in the cropped plane
+        float qy[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) qy[i] = e.q[4 * i + 1] * yf;
+        float X[EG_RUN], Y[EG_RUN], Z[EG_RUN];
+#pragma unroll
+        for (int j = 0; j < EG_RUN; ++j) {
+            const float xf = (float)(r.x0 + j);
+            float v[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[i] = ((e.q[4 * i] * xf + qy[i]) + e.q[4 * i + 2] * d[j]) + e.q[4 * i + 3];
+            const float pz = __fdiv_rn(v[2], v[3]);
+            const bool okp = ok[j] && (!gate_z || (pz > 0.0f && pz <= e.max_depth));
+            X[j] = okp ? __fdiv_rn(v[0], v[3]) : __builtin_nanf("");
+            Y[j] = okp ? __fdiv_rn(v[1], v[3]) : __builtin_nanf("");
+            Z[j] = okp ? pz : __builtin_nanf("");
+        }
+        if (e.points.format == PPMS_FMT_F32) {
+            if (e.points_components == 3) egress_store_points<float, 3>(e.points, r.frame, r.y, r.x0, r.n, X, Y, Z, u);
+            else egress_store_points<float, 4>(e.points, r.frame, r.y, r.x0, r.n, X, Y, Z, u);
+        } else {
+            if (e.points_components == 3) egress_store_points<_Float16, 3>(e.points, r.frame, r.y, r.x0, r.n, X, Y, Z, u);
+            else egress_store_points<_Float16, 4>(e.points, r.frame, r.y, r.x0, r.n, X, Y, Z, u);
+        }
+    }
+}
+extern "C" int ppms_egress_struct_size(void) { return (int)sizeof(ppms_egress); }
+extern "C" int ppms_egress3d_struct_size(void) { return (int)sizeof(ppms_egress3d); }
+// What both egress entry points check, under the name `who` of the one called: the geometry, the three planes and their constants, and -- from
+// ppms_scene_egress (e != nullptr) -- the points plane, q and the gates.  On success the launch geometry.
+struct egress_launch { int rpr; int64_t total; float sh, sw; };
+static int egress_check(const char* who, const float* flow_up, const float* unc, int T, int H, int W, int frame0, int n_frames, int pad_left, int pad_top,
+                        int H0, int W0, const ppms_egress& o, const ppms_egress3d* e, egress_launch* g) {
+    const bool points = e && e->points.ptr;
+    if (e)
+        PPMS_REQUIRE(o.disparity.ptr || o.depth.ptr || o.uncertainty.ptr || points, "%s: no plane: disparity, depth, uncertainty and points are all NULL", who);
+    else
+        PPMS_REQUIRE(o.disparity.ptr || o.depth.ptr || o.uncertainty.ptr, "%s: no plane: disparity, depth and uncertainty are all NULL", who);
+    PPMS_REQUIRE(T > 0 && H > 0 && W > 0 && H0 > 0 && W0 > 0, "%s: T = %d, H = %d, W = %d, H0 = %d, W0 = %d must be positive", who, T, H, W, H0, W0);
+    PPMS_REQUIRE(H % 4 == 0 && W % 4 == 0, "%s: H = %d, W = %d must be multiples of 4", who, H, W);
+    PPMS_REQUIRE(pad_left >= 0 && pad_top >= 0 && (int64_t)pad_top + H0 <= H && (int64_t)pad_left + W0 <= W,
+                 "%s: the crop pad_left = %d, pad_top = %d, H0 = %d, W0 = %d lies outside the %d x %d frame", who, pad_left, pad_top, H0, W0, H, W);
+    PPMS_REQUIRE(n_frames > 0, "%s: n_frames = %d must be positive", who, n_frames);
+    PPMS_REQUIRE(frame0 >= 0 && (int64_t)frame0 + n_frames <= T, "%s: frame0 = %d, n_frames = %d leave the T = %d frames", who, frame0, n_frames, T);
+    PPMS_REQUIRE(((o.disparity.ptr || o.depth.ptr || points) ? flow_up != nullptr : true) && (o.uncertainty.ptr ? unc != nullptr : true),
+                 "%s: null flow_up / unc source of a requested plane", who);
+    if (points)
+        PPMS_REQUIRE(e->points_components == 3 || e->points_components == 4, "%s: points_components = %d must be 3 or 4", who, e->points_components);
+    const struct { const ppms_egress_plane* p; const char* name; unsigned formats; int comps; } planes[4] = {
+        {&o.disparity, "disparity", 1u << PPMS_FMT_F32 | 1u << PPMS_FMT_F16 | 1u << PPMS_FMT_U16, 1},
+        {&o.depth, "depth", 1u << PPMS_FMT_F32 | 1u << PPMS_FMT_F16 | 1u << PPMS_FMT_U16, 1},
+        {&o.uncertainty, "uncertainty", 1u << PPMS_FMT_F32 | 1u << PPMS_FMT_U8, 1},
+        {points ? &e->points : nullptr, "points", 1u << PPMS_FMT_F32 | 1u << PPMS_FMT_F16, points ? e->points_components : 0}};
+    for (const auto& pl : planes) {
+        if (!pl.p || !pl.p->ptr) continue;                               // skipped
+        const ppms_egress_plane& p = *pl.p;
+        PPMS_REQUIRE(p.format >= 0 && p.format <= PPMS_FMT_U8 && (pl.formats >> p.format & 1u),
+                     "%s: %s.format = %d is not a format of that plane", who, pl.name, p.format);
+        PPMS_REQUIRE(p.reserved == 0, "%s: %s.reserved = %d must be 0", who, pl.name, p.reserved);
+        const int64_t esz = p.format == PPMS_FMT_F32 ? 4 : (p.format == PPMS_FMT_U8 ? 1 : 2), rowb = esz * W0 * pl.comps;
+        PPMS_REQUIRE(p.pitch >= rowb, "%s: %s.pitch = %lld is less than a row's %lld bytes", who, pl.name, (long long)p.pitch, (long long)rowb);
+        PPMS_REQUIRE(n_frames == 1 || p.frame_stride >= (int64_t)(H0 - 1) * p.pitch + rowb,
+                     "%s: %s.frame_stride = %lld is less than a plane", who, pl.name, (long long)p.frame_stride);
+        PPMS_REQUIRE(((uintptr_t)p.ptr | (uintptr_t)p.pitch | (uintptr_t)p.frame_stride) % esz == 0,
+                     "%s: %s: pointer, pitch and frame_stride must be multiples of the %lld-byte element", who, pl.name, (long long)esz);
+    }
+    if (o.depth.ptr) {
+        PPMS_REQUIRE(o.fb > 0.0f && o.fb < INFINITY, "%s: a depth plane needs fb = %g > 0", who, (double)o.fb);
+        PPMS_REQUIRE(o.depth_scale > 0.0f && o.depth_scale < INFINITY, "%s: a depth plane needs depth_scale = %g > 0", who, (double)o.depth_scale);
+        PPMS_REQUIRE(o.min_disp > -INFINITY && o.min_disp < INFINITY, "%s: a depth plane needs a finite min_disp, got %g", who, (double)o.min_disp);
+    }
+    if (o.disparity.ptr && o.disparity.format == PPMS_FMT_U16)
+        PPMS_REQUIRE(o.disp_scale > 0.0f && o.disp_scale < INFINITY, "%s: a u16 disparity needs disp_scale = %g > 0", who, (double)o.disp_scale);
+    if (e) {
+        PPMS_REQUIRE(e->reserved == 0, "%s: reserved = %d must be 0", who, e->reserved);
+        PPMS_REQUIRE(e->max_uncertainty == e->max_uncertainty, "%s: max_uncertainty is NaN (+inf switches the gate off)", who);
+        PPMS_REQUIRE(e->max_depth > 0.0f, "%s: max_depth = %g must be positive (+inf switches the gate off)", who, (double)e->max_depth);
+        if (points) {
+            for (int i = 0; i < 16; ++i)
+                PPMS_REQUIRE(e->q[i] > -INFINITY && e->q[i] < INFINITY, "%s: q[%d] = %g is not finite", who, i, (double)e->q[i]);
+            PPMS_REQUIRE(o.min_disp > -INFINITY && o.min_disp < INFINITY, "%s: points need a finite min_disp, got %g", who, (double)o.min_disp);
+        }
+        const bool reads_u = ((o.depth.ptr || points) && e->max_uncertainty < INFINITY) || (points && e->points_components == 4);
+        PPMS_REQUIRE(!reads_u || unc != nullptr, "%s: null unc: the max_uncertainty gate and points_components = 4 read it", who);
+    }
+    g->rpr = (W0 + EG_RUN - 1) / EG_RUN;                                 // runs per output row
+    g->total = (int64_t)n_frames * H0 * g->rpr;
+    PPMS_REQUIRE((g->total + 255) / 256 <= 0x7fffffff, "%s: %lld threads exceed one grid", who, (long long)g->total);
+    g->sh = (float)(H / 4) / (float)H, g->sw = (float)(W / 4) / (float)W;            // ppms_bilinear's scales for (H/4, W/4) -> (H, W): 0.25
+    return PPMS_OK;
+}
+extern "C" int ppms_disparity_egress(const float* flow_up, const float* unc, int T, int H, int W, int frame0, int n_frames, int pad_left, int pad_top,
+                                     int H0, int W0, const ppms_egress* out, void* stream) {
+    PPMS_REQUIRE(out, "disparity_egress: null out struct");
+    egress_launch g;
+    if (const int rc = egress_check("disparity_egress", flow_up, unc, T, H, W, frame0, n_frames, pad_left, pad_top, H0, W0, *out, nullptr, &g)) return rc;
+    hipLaunchKernelGGL(disparity_egress_kernel, dim3(ceil_div(g.total, 256)), dim3(256), 0, (hipStream_t)stream, flow_up, unc, *out, H, W, frame0, pad_left,
+                       pad_top, H0, W0, g.sh, g.sw, g.rpr, g.total);
+    return ppms_check_launch("disparity_egress");
+}
+extern "C" int ppms_scene_egress(const float* flow_up, const float* unc, int T, int H, int W, int frame0, int n_frames, int pad_left, int pad_top,
+                                 int H0, int W0, const ppms_egress3d* out, void* stream) {
+    PPMS_REQUIRE(out, "scene_egress: null out struct");
+    egress_launch g;
+    if (const int rc = egress_check("scene_egress", flow_up, unc, T, H, W, frame0, n_frames, pad_left, pad_top, H0, W0, out->base, out, &g)) return rc;
+    hipLaunchKernelGGL(scene_egress_kernel, dim3(ceil_div(g.total, 256)), dim3(256), 0, (hipStream_t)stream, flow_up, unc, *out, H, W, frame0, pad_left,
+                       pad_top, H0, W0, g.sh, g.sw, g.rpr, g.total);
+    return ppms_check_launch("scene_egress");
+}

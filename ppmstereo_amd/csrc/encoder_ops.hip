@@ -241,7 +241,7 @@ __global__ __launch_bounds__(256) void sp_upsample2_kernel(ppms_sp src, ppms_sp 
 }
 
 // depthwise 7 x 7 convolution + bias (Block.dwconv, :60): split planes in, fp32 channel-last out.  Same scheme as dwconv_gelu_kernel
-// (small_ops.hip): one thread = a run of 4 pixels along x times 8 channels, per kernel row the 4 + 6 window positions are loaded once
+// (loop_ops.hip): one thread = a run of 4 pixels along x times 8 channels, per kernel row the 4 + 6 window positions are loaded once
 // (16-byte loads of both planes) and the 7 taps sweep them from registers; a workgroup serves one block of <= 64 channels (blockIdx.y)
 // whose weights sit in LDS transposed to [tap][channel].  Weights [C][49] as in the state_dict.
 constexpr int DWP_PX = 4;

@@ -588,7 +588,7 @@ def convex_logits(case: str, P: int, taps: int, seed: int) -> torch.Tensor:
 def convex_upsample(flow: torch.Tensor, mask: torch.Tensor, t_halo: int = 0, dtype=F64) -> torch.Tensor:
     """flow (T + 2 t_halo, H, W, 2), mask (T, H, W, taps * 16), taps 9 (2-D: t_halo 0) or 27 -> (T, 2, 4 H, 4 W), tap by tap:
     out[t, c, 4y+i, 4x+j] = sum_k softmax_k(mask[t, y, x, 16k + 4i + j]) * 4 flow[t + kt - 1, y + ky - 1, x + kx - 1, c], k = (kt 3 + ky) 3 + kx,
-    zero outside the map and outside the frames the flow holds (small_ops.hip).  dtype float32: the same in plain fp32 torch."""
+    zero outside the map and outside the frames the flow holds (loop_ops.hip).  dtype float32: the same in plain fp32 torch."""
     T, H, W, ch = mask.shape
     taps = ch // 16
     w = torch.softmax(mask.to(dtype).reshape(T, H, W, taps, 4, 4), 3)

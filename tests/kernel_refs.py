@@ -1,5 +1,5 @@
 """Plain float64 CPU references of the non-convolution kernels of the two encoders (encoder_ops.hip), of the glue kernels around the
-loop (small_ops.hip), of the kernels inside every update iteration (corr.hip's lookup, pwchain.hip, ppms_dwconv_gelu, attn16.hip) and of
+loop (glue_ops.hip, loop_ops.hip), of the kernels inside every update iteration (corr.hip's lookup, pwchain.hip, ppms_dwconv_gelu, attn16.hip) and of
 the pick-and-play memory read-out (frame similarity, QAM pick, attention operands, mem_attn.hip), one function per operation, each with
 the named wrong variants its test exists to catch; the cases (shapes and seeded inputs) of tests/test_gpu_encoder_ops.py,
 tests/test_gpu_glue_ops.py, tests/test_gpu_update_ops.py and tests/test_gpu_memory_ops.py; and the tolerance rule they and the CPU test
@@ -917,7 +917,7 @@ def linattn_check(dh, case, data, y, label=None):
 
 
 # ================================================================================================ memory read-out
-# The pick-and-play chain (small_ops.hip: qk_pool / qk_cos, the QAM pick, the operand kernels; mem_attn.hip): tests/test_gpu_memory_ops.py.
+# The pick-and-play chain (mem_pick.hip: qk_pool / qk_cos, the QAM pick, the operand kernels; mem_attn.hip): tests/test_gpu_memory_ops.py.
 # Similarity, score and s_hat are reductions (kind c); SEL and the usage counter are exact; the operands are one fp32 operation rounded to
 # bf16 (exact: the build does not contract a * s + p, -ffp-contract=off); the read-out keeps the per-element bound tests/test_gpu_ops.py
 # derives for it, restated here against the float64 read-out.

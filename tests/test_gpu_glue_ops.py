@@ -1,4 +1,4 @@
-"""GPU: the small glue kernels around the loop (small_ops.hip), each called through the C ABI and compared with the plain float64
+"""GPU: the small glue kernels around the loop (glue_ops.hip, loop_ops.hip), each called through the C ABI and compared with the plain float64
 reference of tests/kernel_refs.py.
 
 Tolerances (kernel_refs.py states the rule; none comes from the code under test): (a) exact for copies, the relu half, flow_add and the hi

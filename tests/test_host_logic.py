@@ -500,3 +500,61 @@ def test_stereo_source_refusals_and_measures():
     assert torch.equal(got[1], maps[1].apply_u8(block[:, 1]).float())
     got = stereo_source("test", block[None, :, 0], block[None, :, 1]).float_views()
     assert torch.equal(got[0], block[:, 0].float()) and torch.equal(got[1], block[:, 1].float())
+
+
+def test_build_sources_are_the_hip_files_of_csrc():
+    """Every *.hip directly under csrc/ is compiled into the library, and every entry of build.SOURCES exists."""
+    import os
+
+    from ppmstereo_amd import build as B
+
+    assert len(set(B.SOURCES)) == len(B.SOURCES)
+    assert sorted(B.SOURCES) == sorted(f for f in os.listdir(B.CSRC) if f.endswith(".hip"))
+
+
+_ASM = """\t.protected\t_Z1kPf
+\t.type\t_Z1kPf,@function
+_Z1kPf:                                 ; @_Z1kPf
+.Lfunc_begin{f}:
+\t.cfi_startproc
+; %bb.0:
+\t.loc\t1 {line} 0
+\ts_load_dwordx2 s[0:1], s[4:5], 0x0        ; {note}
+.Ltmp{t0}:
+\tv_mov_b32_e32 v0, {imm}
+.LBB{f}_1:                                ; =>This Inner Loop Header: Depth=1
+\ts_cbranch_scc1 .LBB{f}_1
+.Ltmp{t1}:
+; %bb.2:
+\ts_endpgm
+\t.section\t.rodata,"a",@progbits
+\t.amdhsa_kernel _Z1kPf
+\t\t.amdhsa_next_free_vgpr {vgpr}
+\t\t.amdhsa_next_free_sgpr 6
+\t.end_amdhsa_kernel
+\t.text
+.Lfunc_end{f}:
+\t.size\t_Z1kPf, .Lfunc_end{f}-_Z1kPf
+\t.cfi_endproc
+\t.set __hip_cuid_{note},0
+"""
+
+
+def test_isa_digest_kernel_hash_ignores_placement_and_sees_code():
+    """tools/isa_digest.py --kernels: a kernel's hash does not depend on label indices, trailing comments, .loc lines or what stands around
+    the kernel in its file; one changed operand or a changed descriptor block changes it."""
+    import importlib.util
+    import os
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("isa_digest", os.path.join(root, "tools", "isa_digest.py"))
+    D = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(D)
+    base = dict(f=0, line=10, note="abc", t0=0, t1=1, imm=1, vgpr=4)
+    a = D.kernel_digests(_ASM.format(**base))
+    assert list(a) == ["_Z1kPf"] and len(a["_Z1kPf"]) == 64
+    moved = "\t.text\n_Z5otherv:\n\ts_endpgm\n.Lfunc_end6:\n" + _ASM.format(**dict(base, f=7, line=99, note="moved_here", t0=31, t1=40))
+    assert D.kernel_digests(moved) == a                                 # (_Z5otherv has no descriptor: not a kernel)
+    assert D.kernel_digests(_ASM.format(**dict(base, imm=2))) != a
+    assert D.kernel_digests(_ASM.format(**dict(base, vgpr=5))) != a
+    assert D.kernel_digests(_ASM.format(**dict(base, t0=1, t1=0))) == a   # .Ltmp is numbered by first appearance
