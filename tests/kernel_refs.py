@@ -1,12 +1,15 @@
 """Plain float64 CPU references of the non-convolution kernels of the two encoders (encoder_ops.hip), of the glue kernels around the
-loop (glue_ops.hip, loop_ops.hip), of the kernels inside every update iteration (corr.hip's lookup, pwchain.hip, ppms_dwconv_gelu, attn16.hip) and of
-the pick-and-play memory read-out (frame similarity, QAM pick, attention operands, mem_attn.hip), one function per operation, each with
-the named wrong variants its test exists to catch; the cases (shapes and seeded inputs) of tests/test_gpu_encoder_ops.py,
-tests/test_gpu_glue_ops.py, tests/test_gpu_update_ops.py and tests/test_gpu_memory_ops.py; and the tolerance rule they and the CPU test
-tests/test_kernel_refs.py apply.  The formulas are those of oracle/ppm_oracle.py and of the kernel comments.
+loop (glue_ops.hip, loop_ops.hip), of the kernels inside every update iteration (corr.hip's lookup, pwchain.hip, ppms_dwconv_gelu, attn16.hip), of
+the pick-and-play memory read-out (frame similarity, QAM pick, attention operands, mem_attn.hip) and of the correlation build and the flow
+output kernels (corr.hip's pyramid build, convex upsampling 2-D / 3-D, tap gather-sum, bilinear resize, the four tiled transposes), one
+function per operation, each with the named wrong variants its test exists to catch; the cases (shapes and seeded inputs) of
+tests/test_gpu_encoder_ops.py, tests/test_gpu_glue_ops.py, tests/test_gpu_update_ops.py, tests/test_gpu_memory_ops.py and
+tests/test_gpu_flow_ops.py; and the tolerance rule they and the CPU test tests/test_kernel_refs.py apply.  The formulas are those of
+oracle/ppm_oracle.py and of the kernel comments.
 
 Tolerances, three kinds, none taken from the code under test:
- (a) exact: copies, permutations, the relu half, flow_add, the hi plane of any split (Check.exact);
+ (a) exact: copies, permutations (the tiled transposes), the relu half, flow_add, the accum side of the tap gather-sum, the hi plane of
+     any split (Check.exact);
  (b) split-bf16 outputs of elementwise math: 2e-5 * max(1, max|ref|), the bound the suite uses for that storage (tol_sp);
  (c) reductions and transcendentals: 8 x the max error of the same operation in plain fp32 torch on the CPU, on the same input, against
      the float64 reference -- or (b) where the output is split bf16, whichever is larger (tol_reduce).  8: the kernels sum in a fixed
@@ -1354,6 +1357,340 @@ def attn_check(name, p_format, raw, mfg, label=None):
     ck.items.append(("mean", ((got - x).abs().mean((1, 2)) / bound.mean((1, 2))).max().item() if finite else math.inf, 0.5))      # per clip
     want = mfg_of(mf, raw.detach().cpu())
     return ck.add("mfg", mfg, want, tol_sp(want))
+
+
+# ================================================================================================ correlation build, flow output
+# The pyramid build (corr.hip: the line-resident kernel and the general one), the convex upsamplings and the tap gather-sum (loop_ops.hip),
+# the bilinear resize and the four tiled transposes (glue_ops.hip): tests/test_gpu_flow_ops.py.  Pyramid levels, upsamplings and resize are
+# kind (c); the transposes and the accum side of the gather-sum are exact; the gather-sum's out has an elementwise bound of its own.
+# ------------------------------------------------------------------------------------------------ correlation pyramid
+CORR_CASES = {  # B, C, H, W, features one float into their allocation
+    "w32_c32": (1, 32, 9, 20, False),          # the 32-wide line kernel, nch = 2: 9 lines = one full group of 8 plus one; widths 10 / 5 / 2 / 1
+    "w64_c48": (3, 48, 3, 44, False),          # the 64-wide one, nch = 3; widths 22 / 11 / 5 / 2: levels 3 and 4 drop a window
+    "w128_c16": (1, 16, 10, 132, False),       # the 128-wide one, two x1 and two x2 blocks, the last 4 wide; an epilogue after every stage
+    "w128_c64": (2, 64, 4, 260, False),        # three blocks, nch = 4, exactly 8 lines
+    "general_w70": (1, 20, 9, 70, False),      # the general kernel: W % 4 != 0, C % 16 != 0, three tiles on four waves, the regrouped branch
+    "general_c7": (2, 7, 4, 18, False),        # odd C: the channel guard splits a pair of one MFMA
+    "general_misaligned": (3, 48, 3, 44, True),      # the general kernel on a line-kernel shape
+}
+CORR_GAPS = (4, 8, 4, 8, 4)                                                # sentinel floats after each level of the pyramid buffer
+
+
+def corr_pyramid(f1, f2, dtype=F64, swap=False, div_c=False, ceil=False, offset1=False, lines_xor1=False, late_window=False):
+    """f1, f2 (B, C, H, W) -> 5 levels (B H W, W >> l): vol[b, y, x1, x2] = sum_c f1[b, c, y, x1] f2[b, c, y, x2] / sqrt(C), then four times
+    0.5 (even + odd) along x2 with floored widths (corr.py:56-72, 96-104).  dtype = float32: the plain-torch form.  The other keyword
+    arguments are the wrong variants."""
+    B, C, H, W = f1.shape
+    vol = torch.einsum("bcyi,bcyj->byij", f1.to(dtype), f2.to(dtype)) / (C if div_c else math.sqrt(C))
+    if swap:
+        vol = vol.transpose(2, 3)
+    if lines_xor1:                                                          # lines r and r ^ 1 exchanged inside every full group of 8 lines
+        r = torch.arange(B * H)
+        r = torch.where(r < (B * H) // 8 * 8, r ^ 1, r)
+        vol = vol.reshape(B * H, W, W)[r]
+    lvl = vol.reshape(B * H * W, W)
+    pyr = [lvl]
+    for l in range(1, 5):
+        if late_window:                                                     # pooled from level 0, every window one element late
+            w, k = W >> l, 1 << l
+            lvl = F.pad(pyr[0], (0, k))[:, 1:1 + w * k].reshape(-1, w, k).mean(2)
+        else:
+            src = F.pad(lvl, (0, 2))
+            w = (lvl.shape[1] + 1) // 2 if ceil else lvl.shape[1] // 2      # ceil: the incomplete last window kept (its missing half is 0)
+            o = 1 if offset1 else 0
+            lvl = 0.5 * (src[:, o:o + 2 * w:2] + src[:, o + 1:o + 1 + 2 * w:2])
+        pyr.append(lvl)
+    return pyr
+
+
+def corr_pyramid_f32(f1, f2):
+    return corr_pyramid(f1, f2, dtype=torch.float32)
+
+
+CORR_WRONG = {"x1_x2_swapped": dict(swap=True), "divided_by_C": dict(div_c=True), "ceil_widths": dict(ceil=True), "pairs_from_offset_1": dict(offset1=True),
+              "lines_r_and_r^1_exchanged": dict(lines_xor1=True), "pooled_from_level_0_one_late": dict(late_window=True)}
+
+
+@functools.lru_cache(maxsize=None)
+def corr_inputs(case):
+    """f1, f2 (B, C, H, W) fp32: 0.5 + s_c hash_normal with the per-channel scales s_c spread geometrically over 0.25 .. 4"""
+    B, C, H, W, _ = CORR_CASES[case]
+    seed = 9700 + 10 * list(CORR_CASES).index(case)
+    s = (0.25 * 16.0 ** (torch.arange(C, dtype=F64) * 3 % C / max(1, C - 1))).float().reshape(1, C, 1, 1)
+    return (0.5 + s * hash_normal((B, C, H, W), seed)).float(), (0.5 + s * hash_normal((B, C, H, W), seed + 1)).float()
+
+
+@functools.lru_cache(maxsize=None)
+def corr_refs(case):
+    f1, f2 = corr_inputs(case)
+    return tuple(corr_pyramid(f1, f2)), tuple(corr_pyramid_f32(f1, f2))
+
+
+def corr_check(case, levels, label=None):
+    """levels: 5 x (B H W, W >> l)"""
+    ref, f32 = corr_refs(case)
+    ck = Check(label or f"corr_build {case}")
+    for l in range(5):
+        ck.add(f"level{l}", levels[l], ref[l], tol_reduce(ref[l], f32[l], False))
+    return ck
+
+
+# ------------------------------------------------------------------------------------------------ convex upsampling
+CONVEX_HALO = 2                                                            # halo frames on each side of the flow buffer, as the engine's
+CONVEX2D_CASES = [(2, 5, 7, 144), (3, 6, 10, 160), (1, 1, 1, 152)]          # BT, H, W, mask_ld
+CONVEX3D_CASES = [(1, 4, 6, 0, 432), (3, 5, 9, 0, 440), (2, 5, 9, 1, 432), (4, 3, 5, 2, 432)]      # T, H, W, t_halo, mask_ld
+CONVEX_DATA = ("unit", "sharp", "bigflow")                                 # N(0, 1) logits; 100 + 30 N(0, 1): exp without the max overflows fp32; |flow| ~ 60
+
+
+def convex_upsample_3d(flow, mask, t_halo, kt=3, dtype=F64, sub_max=True, in_range_only=False, swap_ky_kx=False, swap_i_j=False, pad="zeros",
+                       factor=4.0, kt_fastest=False, halo_zero=False, one_beyond=False):
+    """flow (T + 2 t_halo, H, W, 2), mask (T, H, W, 16 ntap), ntap = 9 kt -> (T, 2, 4 H, 4 W):
+    out[t, c, 4 y + i, 4 x + j] = sum_k softmax_k(mask[t, y, x, 16 k + 4 i + j]) 4 flow[t + dt, y + dy, x + dx, c], k = (dt' 3 + dy') 3 + dx', zero
+    outside the frame and beyond the t_halo frames around the T own ones (ppmstereo.py:185-228).  dtype = float32: the plain-torch form.  The
+    other keyword arguments are the wrong variants."""
+    T, H, W, ntap = mask.shape[0], mask.shape[1], mask.shape[2], 9 * kt
+    m = mask.to(dtype).reshape(T, H, W, ntap, 4, 4)
+    if sub_max:
+        wgt = torch.softmax(m, dim=3)
+    else:                                                                   # exp of the raw logits, in fp32 as a kernel would
+        e = torch.exp(m.float())
+        wgt = (e / e.sum(3, keepdim=True)).to(dtype)
+    fl = factor * flow.to(dtype)
+    th = t_halo
+    if one_beyond:                                                          # the frame past the halo is read: NaN, as the buffer holds there
+        fl, th = torch.cat([torch.full_like(fl[:1], math.nan), fl, torch.full_like(fl[:1], math.nan)]), t_halo + 1
+    Tf = fl.shape[0]
+    fp = fl.permute(0, 3, 1, 2)
+    fp = (F.pad(fp, (1, 1, 1, 1), mode="replicate") if pad == "replicate" else F.pad(fp, (1, 1, 1, 1))).permute(0, 2, 3, 1)
+    inside = F.pad(torch.ones(H, W, dtype=dtype), (1, 1, 1, 1))
+    t = torch.arange(T)
+    out = torch.zeros(T, H, W, 4, 4, 2, dtype=dtype)
+    terms, oks = [], []
+    for k in range(ntap):
+        if kt_fastest:
+            dt, dy, dx = k % kt - kt // 2, k // kt // 3 - 1, k // kt % 3 - 1
+        else:
+            dt, dy, dx = k // 9 - kt // 2, k // 3 % 3 - 1, k % 3 - 1
+        if swap_ky_kx:
+            dy, dx = dx, dy
+        tt = t + dt
+        ok_t = ((tt >= 0) & (tt < T)) if halo_zero else ((tt + th >= 0) & (tt + th < Tf))
+        nb = fp[(tt + th).clamp(0, Tf - 1), 1 + dy:1 + dy + H, 1 + dx:1 + dx + W]                        # (T, H, W, 2)
+        nb = torch.where(ok_t.reshape(T, 1, 1, 1), nb, torch.zeros_like(nb))
+        terms.append(nb)
+        oks.append(ok_t.to(dtype).reshape(T, 1, 1) * inside[1 + dy:1 + dy + H, 1 + dx:1 + dx + W])
+    if in_range_only:                                                       # renormalised over the taps that lie inside the volume
+        ok = torch.stack(oks, 3)[..., None, None]
+        wgt = wgt * ok / (wgt * ok).sum(3, keepdim=True)
+    for k in range(ntap):
+        out += wgt[:, :, :, k, :, :, None] * terms[k][:, :, :, None, None, :]
+    if swap_i_j:
+        out = out.transpose(3, 4)
+    return out.permute(0, 5, 1, 3, 2, 4).reshape(T, 2, 4 * H, 4 * W)
+
+
+def convex_upsample(flow, mask, **kw):
+    """flow (BT, H, W, 2), mask (BT, H, W, 144) -> (BT, 2, 4 H, 4 W): the 9 taps of the frame itself"""
+    return convex_upsample_3d(flow, mask, 0, kt=1, **kw)
+
+
+def convex_upsample_f32(flow, mask):
+    return convex_upsample(flow, mask, dtype=torch.float32)
+
+
+def convex_upsample_3d_f32(flow, mask, t_halo):
+    return convex_upsample_3d(flow, mask, t_halo, dtype=torch.float32)
+
+
+CONVEX_WRONG = {"no_max_subtraction": dict(sub_max=False), "softmax_over_in_range_taps": dict(in_range_only=True), "ky_kx_swapped": dict(swap_ky_kx=True),
+                "i_j_swapped": dict(swap_i_j=True), "replicate_padding": dict(pad="replicate"), "factor_4_missing": dict(factor=1.0)}
+CONVEX3D_WRONG = dict(CONVEX_WRONG, kt_fastest=dict(kt_fastest=True), halo_frames_read_as_zero=dict(halo_zero=True),
+                      one_frame_beyond_t_halo=dict(one_beyond=True))
+
+
+@functools.lru_cache(maxsize=None)
+def convex_inputs(dim, case, data):
+    """flow (T + 2 t_halo, H, W, 2), mask (T, H, W, 144 or 432) fp32, t_halo (0 for the 2-D kernel)"""
+    T, H, W = case[:3]
+    th, ntap = (case[3], 27) if dim == 3 else (0, 9)
+    seed = 9800 + 100 * dim + 10 * (CONVEX3D_CASES if dim == 3 else CONVEX2D_CASES).index(case) + CONVEX_DATA.index(data)
+    flow = hash_normal((T + 2 * th, H, W, 2), seed) * (60.0 if data == "bigflow" else 3.0)
+    mask = hash_normal((T, H, W, 16 * ntap), seed + 5)
+    if data == "sharp":
+        mask = (100.0 + 30.0 * mask).float()
+    return flow.float(), mask, th
+
+
+@functools.lru_cache(maxsize=None)
+def convex_refs(dim, case, data):
+    flow, mask, th = convex_inputs(dim, case, data)
+    kt = 3 if dim == 3 else 1
+    return convex_upsample_3d(flow, mask, th, kt=kt), convex_upsample_3d(flow, mask, th, kt=kt, dtype=torch.float32)
+
+
+def convex_check(dim, case, data, out, label=None):
+    ref, f32 = convex_refs(dim, case, data)
+    return Check(label or f"convex_upsample{'_3d' if dim == 3 else ''} {case} {data}").add("out", out, ref, tol_reduce(ref, f32, False))
+
+
+# ------------------------------------------------------------------------------------------------ tap gather-sum
+TGS_HALO = 2
+TGS_CASES = [  # cout, (kt, kh, kw), T, H, W, t_halo, y_ld, out_ld, accum_ld (None: no accum)
+    (2, (3, 3, 3), 3, 5, 9, 0, 64, 4, 2),      # the engine's call (the unrolled kernel)
+    (2, (3, 3, 3), 1, 1, 1, 0, 64, 4, 2),      # one pixel: 26 of the 27 taps outside
+    (1, (1, 3, 3), 2, 4, 6, 0, 16, 3, None),   # the generic kernel, cout = 1, no accum
+    (3, (3, 1, 3), 2, 5, 7, 1, 32, 4, 4),      # cout = 3, a halo frame on either side
+    (2, (5, 1, 1), 4, 3, 5, 2, 16, 2, 3),      # kt = 5 reaches both halo frames; out_ld = cout
+]
+
+
+def tap_gather_sum(y, bias, cout, k3, T, H, W, t_halo, dtype=F64, order="kz_major", mirrored=False, column="tap_major", with_bias=True, halo_zero=False):
+    """y ((T + 2 t_halo) H W, y_ld), bias (cout,) -> out (T H W, cout), and sum |terms| + |bias| of every element:
+    out[p][c] = bias[c] + sum_tap y[p + d(tap)][tap cout + c], tap = (kz kh + ky) kw + kx, d(tap) = (kz - kt / 2, ky - kh / 2, kx - kw / 2), zero
+    outside the frame and beyond the t_halo frames around the T own ones (loop_ops.hip).  dtype = float32: the plain-torch form.  The other
+    keyword arguments are the wrong variants."""
+    kt, kh, kw = k3
+    ntap, Tf = kt * kh * kw, T + 2 * t_halo
+    v = F.pad(y.to(dtype).reshape(Tf, H, W, -1), (0, 0, kw // 2, kw // 2, kh // 2, kh // 2, kt // 2, kt // 2))
+    t = torch.arange(T)
+    out = (bias.to(dtype) if with_bias else torch.zeros(cout, dtype=dtype)).reshape(1, 1, 1, cout).expand(T, H, W, cout).clone()
+    mag = out.abs()
+    for kz in range(kt):
+        for ky in range(kh):
+            for kx in range(kw):
+                tap = (kz * kh + ky) * kw + kx if order == "kz_major" else (kx * kh + ky) * kt + kz
+                cols = tap * cout + torch.arange(cout) if column == "tap_major" else torch.arange(cout) * ntap + tap
+                dz, dy, dx = (kt // 2 - kz, kh // 2 - ky, kw // 2 - kx) if mirrored else (kz - kt // 2, ky - kh // 2, kx - kw // 2)
+                tt = t + t_halo + dz                                        # frame of y
+                ok = ((tt >= t_halo) & (tt < t_halo + T)) if halo_zero else ((tt >= 0) & (tt < Tf))
+                term = v[(tt + kt // 2).clamp(0, Tf + 2 * (kt // 2) - 1), kh // 2 + dy:kh // 2 + dy + H, kw // 2 + dx:kw // 2 + dx + W][..., cols]
+                term = torch.where(ok.reshape(T, 1, 1, 1), term, torch.zeros_like(term))
+                out, mag = out + term, mag + term.abs()
+    return out.reshape(T * H * W, cout), mag.reshape(T * H * W, cout)
+
+
+def tap_gather_sum_f32(y, bias, cout, k3, T, H, W, t_halo):
+    return tap_gather_sum(y, bias, cout, k3, T, H, W, t_halo, dtype=torch.float32)[0]
+
+
+TGS_WRONG = {"kx_major_taps": dict(order="kx_major"), "taps_mirrored": dict(mirrored=True), "column_c_ntap+tap": dict(column="c_major"),
+             "bias_dropped": dict(with_bias=False), "halo_frames_read_as_zero": dict(halo_zero=True), "accum_overwritten": None}      # None: accum = out, the out side is the reference's
+
+
+@functools.lru_cache(maxsize=None)
+def tgs_inputs(case):
+    """y ((T + 2 t_halo) H W, ntap cout), bias (cout,), accum before the launch (T H W, cout) -- all fp32"""
+    cout, k3, T, H, W, th = case[:6]
+    seed = 9900 + 10 * TGS_CASES.index(case)
+    ntap = k3[0] * k3[1] * k3[2]
+    return hash_normal(((T + 2 * th) * H * W, ntap * cout), seed), hash_normal((cout,), seed + 1), hash_normal((T * H * W, cout), seed + 2) * 4
+
+
+@functools.lru_cache(maxsize=None)
+def tgs_ref(case):
+    y, bias, _ = tgs_inputs(case)
+    cout, k3, T, H, W, th = case[:6]
+    return tap_gather_sum(y, bias, cout, k3, T, H, W, th)
+
+
+def tgs_check(case, out, accum=None, label=None):
+    """out (P, cout) within (ntap + 1) 2^-24 (|bias| + sum |terms|) of the reference: the first-order worst case of any-order fp32 summation
+    of ntap + 1 terms; accum (P, cout) = fp32(accum before + out as returned), exact"""
+    ref, mag = tgs_ref(case)
+    ntap = case[1][0] * case[1][1] * case[1][2]
+    bound = (ntap + 1) * 2.0 ** -24 * mag
+    ck = Check(label or f"tap_gather_sum {case}").bound("out", out, ref, bound)
+    got = out.detach().cpu().double()
+    fine = got.shape == ref.shape and bool(torch.isfinite(got).all())
+    ck.items.append(("out/bound", ((got - ref).abs() / bound).max().item() if fine else math.inf, 1.0))      # the same condition, as a ratio
+    if case[8] is not None:
+        ck.exact("accum", accum, tgs_inputs(case)[2] + out.detach().cpu().float())
+    return ck
+
+
+# ------------------------------------------------------------------------------------------------ bilinear resize
+BILINEAR_CASES = [(2, 3, 5, 7, 10, 14), (1, 2, 6, 5, 9, 11), (1, 1, 4, 4, 4, 4), (1, 2, 9, 13, 3, 5), (1, 1, 3, 8, 1, 1), (1, 1, 1, 1, 4, 4),
+                  (2, 1, 8, 32, 32, 128)]                                   # N, C, H, W, OH, OW: up, odd ratios, identity, down, one pixel out, one pixel in, 4 x
+BILINEAR_MUL = (1.0, -0.5, 2.0)
+
+
+def bilinear(x, OH, OW, align, mul):
+    """x (N, C, H, W) -> mul F.interpolate(x, (OH, OW), "bilinear", align_corners) in float64"""
+    return mul * F.interpolate(x.double(), size=(OH, OW), mode="bilinear", align_corners=bool(align))
+
+
+def bilinear_f32(x, OH, OW, align, mul):
+    return mul * F.interpolate(x.float(), size=(OH, OW), mode="bilinear", align_corners=bool(align))
+
+
+def bilinear_taps(x, OH, OW, align, mul, clamp0=True, aligned_scale="(H-1)/(OH-1)"):
+    """the same resize written out (aten/native/UpSample.h: area_pixel_compute_source_index), float64; the keyword arguments are wrong variants"""
+    N, C, H, W = x.shape
+    x = x.double()
+
+    def axis(n, o):
+        i = torch.arange(o, dtype=F64)
+        if align:
+            f = i * (((n - 1) / (o - 1) if o > 1 else 0.0) if aligned_scale == "(H-1)/(OH-1)" else n / o)
+        else:
+            f = (n / o) * (i + 0.5) - 0.5
+            if clamp0:
+                f = f.clamp_min(0.0)
+        i0 = f.trunc().long().clamp(0, n - 1)                              # (int) f, as a kernel converts
+        return i0, (i0 + 1).clamp_max(n - 1), f - i0
+    y0, y1, ly = axis(H, OH)
+    x0, x1, lx = axis(W, OW)
+    ly, lx = ly.reshape(OH, 1), lx.reshape(1, OW)
+    rows = lambda yy: x[:, :, yy][:, :, :, x0] * (1 - lx) + x[:, :, yy][:, :, :, x1] * lx
+    return mul * (rows(y0) * (1 - ly) + rows(y1) * ly)
+
+
+BILINEAR_WRONG = {
+    "align_corners_exchanged": lambda x, OH, OW, al, mul: bilinear(x, OH, OW, not al, mul),
+    "no_clamp_at_0": lambda x, OH, OW, al, mul: None if al else bilinear_taps(x, OH, OW, al, mul, clamp0=False),
+    "nearest": lambda x, OH, OW, al, mul: mul * F.interpolate(x.double(), size=(OH, OW), mode="nearest"),
+    "mul_dropped": lambda x, OH, OW, al, mul: bilinear(x, OH, OW, al, 1.0),
+    "aligned_scale_H/OH": lambda x, OH, OW, al, mul: bilinear_taps(x, OH, OW, al, mul, aligned_scale="H/OH") if al else None,
+}
+
+
+@functools.lru_cache(maxsize=None)
+def bilinear_input(case):
+    N, C, H, W, OH, OW = case
+    return hash_normal((N, C, H, W), 10000 + 10 * BILINEAR_CASES.index(case))
+
+
+@functools.lru_cache(maxsize=None)
+def bilinear_refs(case, align):
+    """(reference, fp32 torch) at mul = 1: a mul of -0.5 or 2 scales both exactly"""
+    x = bilinear_input(case)
+    return bilinear(x, case[4], case[5], align, 1.0), bilinear_f32(x, case[4], case[5], align, 1.0)
+
+
+def bilinear_check(case, align, mul, out, label=None):
+    ref, f32 = bilinear_refs(case, align)
+    return Check(label or f"bilinear {case} align={int(align)} mul={mul}").add("out", out, mul * ref, tol_reduce(mul * ref, mul * f32, False))
+
+
+# ------------------------------------------------------------------------------------------------ tiled transposes
+TRANSPOSE_CASES = [(2, 33, 65, 40), (1, 1, 31, 1), (3, 2, 45, 2), (1, 144, 60, 144), (1, 432, 35, 440), (2, 256, 33, 256)]      # BT, C, HW, ld
+TRANSPOSE_F32_SRC_EXTRA = [(3, 2, 45, 4)]                                  # the engine's DFLOW read: 2 channels at ld 4
+TRANSPOSE_SP_VIEW = (2, 33, 65, 48, 8)                                     # BT, C, HW, channels of the SP tensor, channel offset of the view
+
+
+@functools.lru_cache(maxsize=None)
+def transpose_input(BT, C, HW):
+    """(BT, C, HW) fp32, all distinct, magnitudes spread evenly in the exponent over 2^-20 .. 2^20 and shuffled, alternating signs: neighbours
+    in magnitude differ by 40 ln 2 / n > 2^-10 relative, so the values stay distinct as split bf16 holds them (16 significant bits)"""
+    n = BT * C * HW
+    g = torch.Generator().manual_seed(10100 + n)
+    mag = torch.exp2(-20.0 + 40.0 * torch.randperm(n, generator=g).double() / n)
+    return (mag * (1 - 2 * (torch.arange(n) % 2))).float().reshape(BT, C, HW)
+
+
+def to_channel_last(x):
+    """(BT, C, HW) -> (BT HW, C)"""
+    return x.permute(0, 2, 1).reshape(-1, x.shape[1])
 
 
 # ------------------------------------------------------------------------------------------------ device buffers of the GPU tests

@@ -1,8 +1,9 @@
 """CPU: the float64 references of tests/kernel_refs.py against the corresponding torch ops (to float64 rounding), and -- on the exact
-inputs and with the tolerance rule of every GPU case of test_gpu_encoder_ops.py / test_gpu_glue_ops.py -- shown sensitive to the mistakes
-they exist to catch: every named wrong variant exceeds the tolerance on at least one case of its kernel, while the reference itself and
-the plain fp32 torch form stay inside it.  That is a condition on the cases, not a measurement: where a variant slips through, the inputs
-change, not the tolerance."""
+inputs and with the tolerance rule of every GPU case of test_gpu_encoder_ops.py / test_gpu_glue_ops.py / test_gpu_update_ops.py /
+test_gpu_memory_ops.py / test_gpu_flow_ops.py -- shown sensitive to the mistakes they exist to catch: every named wrong variant exceeds the
+tolerance on at least one case of its kernel, while the reference itself and the plain fp32 torch form stay inside it.  That is a condition
+on the cases, not a measurement: where a variant slips through, the inputs change, not the tolerance.  The last part covers the correlation
+pyramid build, the convex upsamplings, the tap gather-sum, the bilinear resize and the inputs of the transposes."""
 import math
 
 import pytest
@@ -707,3 +708,203 @@ def test_attn_wrong_variant_is_caught(name):
     for kernel in (32, 64):                                                # both kernels' tables see every mistake that applies to them
         mine = [c for c in runs if f"'table', {kernel}" in c.label]
         assert not mine or any(not c.ok for c in mine), (name, kernel)
+
+
+# ================================================================================================ correlation build, flow output
+# ------------------------------------------------------------------------------------------------ references vs torch / the oracle
+@pytest.mark.parametrize("case", list(R.CORR_CASES))
+def test_corr_pyramid_vs_oracle(case):
+    """the float64 pyramid against the oracle's corr_pyramid fed float64 (its einsum runs in fp32: compared at fp32 rounding) and against
+    avg_pool2d([1, 2]) of the float64 volume level by level"""
+    from oracle import ppm_oracle as O
+    B, C, H, W, _ = R.CORR_CASES[case]
+    f1, f2 = R.corr_inputs(case)
+    got = R.corr_pyramid(f1, f2)
+    want = O.corr_pyramid(f1, f2)
+    assert len(got) == len(want) == 5
+    lvl = got[0].reshape(-1, 1, 1, W)
+    for l in range(5):
+        assert got[l].shape == (B * H * W, W >> l)
+        close(got[l], want[l].reshape(B * H * W, W >> l), 1e-5)
+        close(got[l], lvl.reshape(B * H * W, -1))
+        lvl = F.avg_pool2d(lvl, [1, 2], stride=[1, 2]) if l < 4 else None
+    vol = got[0].reshape(B, H, W, W)
+    b, y, i, j = B - 1, H // 2, 3, W - 2
+    close(vol[b, y, i, j], (f1[b, :, y, i].double() * f2[b, :, y, j].double()).sum() / math.sqrt(C))
+    assert 0.3 < f1.mean() < 0.7 and 0.3 < f2.mean() < 0.7                     # the features' mean is not zero
+    s = (f1 - 0.5).std((0, 2, 3))
+    assert s.min() < 0.4 and s.max() > 2.5                                     # per-channel scales over 0.25 .. 4
+
+
+def test_corr_case_arithmetic():
+    """which kernel a case runs and what it strains, re-derived from ppms_corr_build's dispatch"""
+    line = lambda c: c[3] % 4 == 0 and c[1] % 16 == 0 and not c[4]
+    cs = R.CORR_CASES
+    assert [k for k in cs if line(cs[k])] == ["w32_c32", "w64_c48", "w128_c16", "w128_c64"]
+    assert cs["w32_c32"][3] <= 32 < cs["w64_c48"][3] <= 64 < cs["w128_c16"][3]
+    assert [cs[k][1] // 16 for k in cs if line(cs[k])] == [2, 3, 1, 4]                             # nch
+    assert [cs["w32_c32"][3] >> l for l in range(1, 5)] == [10, 5, 2, 1] and [cs["w64_c48"][3] >> l for l in range(1, 5)] == [22, 11, 5, 2]
+    assert -(-132 // 128) == 2 and 132 - 128 == 4 and -(-260 // 128) == 3
+    lines = {k: c[0] * c[2] for k, c in cs.items()}
+    assert lines["w32_c32"] == 9 and lines["w128_c64"] == 8 and lines["w128_c16"] == 10 and lines["general_w70"] == 9 and lines["general_c7"] == 8
+    assert -(-70 // 32) == 3 and 70 % 4 and 20 % 16 and 7 % 2 and 18 % 4
+    for case, (B, C, H, W, mis) in cs.items():                                                     # the layout of the guarded pyramid buffer
+        off = 0
+        for l in range(5):
+            if line(cs[case]):
+                assert (off * 4) % (16 if l == 0 else 8 if l == 1 else 4) == 0
+            off += B * H * W * (W >> l) + R.CORR_GAPS[l]
+
+
+@pytest.mark.parametrize("dim,case", [(2, c) for c in R.CONVEX2D_CASES] + [(3, c) for c in R.CONVEX3D_CASES])
+def test_convex_upsample_vs_oracle(dim, case):
+    """on the cases' own inputs: the 2-D form against the oracle; the 3-D form against the oracle on the extended volume with the mask zero
+    outside the own frames, as tests/sharded_oracle.py states it"""
+    from oracle import ppm_oracle as O
+    flow, mask, th = R.convex_inputs(dim, case, "unit")
+    T = mask.shape[0]
+    f, m = flow.double().permute(0, 3, 1, 2), mask.double().permute(0, 3, 1, 2)
+    if dim == 2:
+        close(R.convex_upsample(flow, mask), O.convex_upsample(f, m))
+    else:
+        m_ext = torch.zeros(T + 2 * th, *m.shape[1:], dtype=F64)
+        m_ext[th:th + T] = m
+        close(R.convex_upsample_3d(flow, mask, th), O.convex_upsample_3d(f, m_ext, 4, T + 2 * th)[th:th + T])
+
+
+def test_tap_gather_sum_vs_conv3d():
+    """a 3 x 3 x 3 and a 5 x 1 x 3 conv to 3 channels as a 1 x 1 GEMM to taps x cout columns plus the shifted sum, own frames of the halo volume"""
+    for k3, th in (((3, 3, 3), 1), ((5, 1, 3), 2), ((1, 3, 3), 0)):
+        T, H, W, cin, cout = 2, 4, 5, 6, 3
+        ntap, Tf = k3[0] * k3[1] * k3[2], T + 2 * th
+        x = hash_normal((Tf, H, W, cin), 70).double()
+        wt, bias = hash_normal((cout, cin, *k3), 71).double(), hash_normal((cout,), 72).double()
+        y = x.reshape(-1, cin) @ wt.permute(2, 3, 4, 0, 1).reshape(ntap * cout, cin).t()        # column tap cout + c
+        want = F.conv3d(x.permute(3, 0, 1, 2)[None], wt, bias, padding=tuple(k // 2 for k in k3))[0].permute(1, 2, 3, 0)[th:th + T]
+        got, mag = R.tap_gather_sum(y, bias, cout, k3, T, H, W, th)
+        close(got, want.reshape(-1, cout))
+        assert (mag >= got.abs() - 1e-12).all()
+
+
+@pytest.mark.parametrize("case", R.BILINEAR_CASES)
+def test_bilinear_taps_vs_interpolate(case):
+    """the written-out resize (what the variants are made from) is F.interpolate, both conventions"""
+    x = R.bilinear_input(case)
+    for align in (False, True):
+        close(R.bilinear_taps(x, case[4], case[5], align, -0.5), R.bilinear(x, case[4], case[5], align, -0.5))
+
+
+def test_transpose_inputs_are_distinct_and_spread():
+    shapes = {c[:3] for c in R.TRANSPOSE_CASES + R.TRANSPOSE_F32_SRC_EXTRA} | {R.TRANSPOSE_SP_VIEW[:3]}
+    for BT, C, HW in shapes:
+        x = R.transpose_input(BT, C, HW)
+        n = x.numel()
+        assert x.unique().numel() == n and R.sp_round(x).unique().numel() == n and R.sp_split(x)[0].float().unique().numel() > n // 40
+        assert x.abs().min() == 2.0 ** -20 and 2.0 ** 18 < x.abs().max() < 2.0 ** 20
+    x = R.transpose_input(2, 33, 65)
+    assert not torch.equal(R.to_channel_last(x).reshape(2, 65, 33)[0], x[0]) and torch.equal(R.to_channel_last(x).reshape(2, 65, 33)[1, 7, 5], x[1, 5, 7])
+
+
+# ------------------------------------------------------------------------------------------------ the cases pass the reference and fp32, catch the variants
+def _corr_runs(fn):
+    return [R.corr_check(case, fn(*R.corr_inputs(case))) for case in R.CORR_CASES]
+
+
+def test_corr_cases_pass_the_reference_and_fp32():
+    runs = _corr_runs(R.corr_pyramid) + _corr_runs(R.corr_pyramid_f32)
+    assert all(c.ok for c in runs), [str(c) for c in runs if not c.ok]
+    print("F32 RATIO corr_build", max(c.worst() for c in _corr_runs(R.corr_pyramid_f32)))
+
+
+@pytest.mark.parametrize("name", list(R.CORR_WRONG))
+def test_corr_wrong_variant_is_caught(name):
+    runs = _corr_runs(lambda f1, f2: R.corr_pyramid(f1, f2, **R.CORR_WRONG[name]))
+    bad = [c.label.split()[1] for c in runs if not c.ok]
+    assert bad, name
+    if name != "ceil_widths":                                                  # every case has a full group of 8 lines; ceil: w128_c64's widths are
+        assert len(bad) == len(runs), (name, bad)                              # even down to level 2
+
+
+def _convex_runs(dim, fn):
+    """fn(flow, mask, t_halo) over every case and kind of data of the kernel"""
+    out = []
+    for case in (R.CONVEX3D_CASES if dim == 3 else R.CONVEX2D_CASES):
+        for data in R.CONVEX_DATA:
+            out.append(R.convex_check(dim, case, data, fn(*R.convex_inputs(dim, case, data))))
+    return out
+
+
+@pytest.mark.parametrize("dim", [2, 3])
+def test_convex_cases_pass_the_reference_and_fp32(dim):
+    kt = 3 if dim == 3 else 1
+    runs = _convex_runs(dim, lambda f, m, th: R.convex_upsample_3d(f, m, th, kt=kt))
+    f32 = _convex_runs(dim, (lambda f, m, th: R.convex_upsample_3d_f32(f, m, th)) if dim == 3 else (lambda f, m, th: R.convex_upsample_f32(f, m)))
+    assert all(c.ok for c in runs + f32), [str(c) for c in runs + f32 if not c.ok]
+    print(f"F32 RATIO convex_upsample dim={dim}", max(c.worst() for c in f32))
+
+
+@pytest.mark.parametrize("dim,name", [(2, n) for n in R.CONVEX_WRONG] + [(3, n) for n in R.CONVEX3D_WRONG])
+def test_convex_wrong_variant_is_caught(dim, name):
+    kw = R.CONVEX3D_WRONG[name]
+    runs = _convex_runs(dim, lambda f, m, th: R.convex_upsample_3d(f, m, th, kt=3 if dim == 3 else 1, **kw))
+    bad = {c.label for c in runs if not c.ok}
+    assert bad, (dim, name)
+    if name == "no_max_subtraction":                                           # only the sharp logits show it, and on every case
+        assert all(("sharp" in c.label) == (not c.ok) for c in runs), [str(c) for c in runs]
+    if name == "halo_frames_read_as_zero":                                     # only where there is a halo
+        assert all((c.label in bad) == (case[3] > 0) for c, case in zip(runs, [k for k in R.CONVEX3D_CASES for _ in R.CONVEX_DATA]))
+
+
+def _tgs_runs(fn):
+    """fn(case) -> (out, accum or None) over the cases"""
+    return [R.tgs_check(case, *fn(case)) for case in R.TGS_CASES]
+
+
+def _tgs_with(case, accum="added", **kw):
+    y, bias, acc0 = R.tgs_inputs(case)
+    out = R.tap_gather_sum(y, bias, *case[:6], **kw)[0].float()               # what a launch returns: fp32
+    return out, None if case[8] is None else (acc0 + out if accum == "added" else out)
+
+
+def test_tgs_cases_pass_the_reference_and_fp32():
+    runs = _tgs_runs(_tgs_with) + _tgs_runs(lambda case: _tgs_with(case, dtype=torch.float32))
+    assert all(c.ok for c in runs), [str(c) for c in runs if not c.ok]
+    for case in R.TGS_CASES:                                                   # the bound in units of itself: the fp32 form's share of it
+        y, bias, _ = R.tgs_inputs(case)
+        ref, mag = R.tgs_ref(case)
+        ntap = case[1][0] * case[1][1] * case[1][2]
+        err = (R.tap_gather_sum_f32(y, bias, *case[:6]).double() - ref).abs() / ((ntap + 1) * 2.0 ** -24 * mag)
+        print("F32 RATIO tap_gather_sum", case, err.max().item())
+        assert err.max() <= 1.0
+
+
+@pytest.mark.parametrize("name", list(R.TGS_WRONG))
+def test_tgs_wrong_variant_is_caught(name):
+    kw = R.TGS_WRONG[name]
+    runs = _tgs_runs((lambda case: _tgs_with(case, accum="overwritten")) if kw is None else (lambda case: _tgs_with(case, **kw)))
+    assert any(not c.ok for c in runs), name
+    if name == "bias_dropped":
+        assert all(not c.ok for c in runs)
+
+
+def _bilinear_runs(fn):
+    out = []
+    for case in R.BILINEAR_CASES:
+        for align in (False, True):
+            for mul in R.BILINEAR_MUL:
+                got = fn(R.bilinear_input(case), case[4], case[5], align, mul)
+                if got is not None:
+                    out.append(R.bilinear_check(case, align, mul, got))
+    return out
+
+
+def test_bilinear_cases_pass_the_reference_and_fp32():
+    runs = _bilinear_runs(R.bilinear) + _bilinear_runs(R.bilinear_f32)
+    assert all(c.ok for c in runs), [str(c) for c in runs if not c.ok]
+    print("F32 RATIO bilinear", max(c.worst() for c in _bilinear_runs(R.bilinear_f32)))
+
+
+@pytest.mark.parametrize("name", list(R.BILINEAR_WRONG))
+def test_bilinear_wrong_variant_is_caught(name):
+    runs = _bilinear_runs(R.BILINEAR_WRONG[name])
+    assert runs and any(not c.ok for c in runs), name
