@@ -303,6 +303,46 @@ int ppms_scene_egress(const float* flow_up, const float* unc, int T, int H, int 
                       int H0, int W0, const ppms_egress3d* out, void* stream);
 int ppms_egress3d_struct_size(void);  /* sizeof(ppms_egress3d) (224) */
 
+/* Compact point cloud: the valid points only, counted, in row order -- what every consumer of the organised cloud does first
+ * (pts[~pts[..., 2].isnan()]), done on the device, so that only the valid records need to cross the bus.  Arguments, sources, crop and frame
+ * range are ppms_scene_egress's.  For output frame f of the launch let P[f] be the organised points plane ppms_scene_egress writes for the same
+ * arguments (crop, frame range, q, min_disp, both gates, 3 or 4 components, F32 / F16) and valid[f][y][x] that call's point validity.  Then
+ *   the cloud of frame f is the records of P[f] at the valid pixels, in increasing y * W0 + x, stored densely from record 0 of the frame
+ *   (record k of frame f at records + f * frame_stride + k * components * element bytes): the same bits, and no record holds a NaN in X, Y, Z;
+ *   counts[f] = the number of valid pixels of frame f;
+ *   index[f][k] = y * W0 + x (int32) of record k, when index is not NULL (at index + f * index_frame_stride + 4 k);
+ *   with capacity < counts[f] exactly the first capacity records and indices are written; counts[f] still reports the full number, so the
+ *   caller sees the truncation;  records and indices at positions >= min(counts[f], capacity) are not written at all;
+ *   w of 4 components is u, as in the organised plane.
+ * Two launches on the stream, count and place, on one grid of (workgroups per frame, n_frames): the first writes every workgroup's number of
+ * valid pixels to block_counts, the second sums the entries in front of its own, ranks its pixels and stores.  No atomics and no workgroup
+ * waits for another: the order of the records is the pixels' order, the same in every run.  block_counts is workspace of
+ * ppms_cloud_egress_workspace(n_frames, H0, W0) int32 entries, undefined afterwards.  `out` is HOST memory, read before the call returns.
+ * Refused with PPMS_EINVAL before any launch: the geometry and the frame range ppms_disparity_egress refuses (one shared check); a null struct,
+ * records, counts or flow_up; block_counts null or shorter than the workspace; unc == NULL where the max_uncertainty gate or components = 4 reads
+ * it; a format other than F32 / F16; components other than 3 / 4; capacity <= 0 or above 2^31 - 1; with n_frames > 1 a frame_stride shorter than
+ * capacity records or an index_frame_stride shorter than capacity indices; a pointer or stride that is no multiple of its element; a non-finite
+ * entry of q or min_disp; a NaN max_uncertainty; max_depth <= 0 or NaN; reserved != 0; H0 * W0 > 2^31 - 1; n_frames > 65535. */
+typedef struct ppms_cloud {
+    void*    records;                 /* record 0 of frame 0 */
+    int64_t  frame_stride;            /* bytes from frame to frame, >= capacity * record bytes */
+    int64_t  capacity;                /* records per frame, 1 .. 2^31 - 1 */
+    int32_t* index;                   /* NULL, or (n_frames, capacity) pixel indices */
+    int64_t  index_frame_stride;      /* bytes */
+    int32_t* counts;                  /* n_frames entries, required */
+    int32_t* block_counts;            /* workspace, block_counts_len entries */
+    int64_t  block_counts_len;
+    float    q[16];                   /* the 4x4 reprojection matrix, row major */
+    float    min_disp, max_uncertainty, max_depth;   /* +inf: gate off */
+    int32_t  format;                  /* PPMS_FMT_F32 | PPMS_FMT_F16 */
+    int32_t  components;              /* 3: X Y Z.  4: X Y Z w */
+    int32_t  reserved;                /* 0 */
+} ppms_cloud;
+int     ppms_cloud_egress(const float* flow_up, const float* unc, int T, int H, int W, int frame0, int n_frames, int pad_left, int pad_top,
+                          int H0, int W0, const ppms_cloud* out, void* stream);
+int64_t ppms_cloud_egress_workspace(int n_frames, int H0, int W0);   /* entries block_counts needs; 0 for a geometry the call refuses */
+int     ppms_cloud_struct_size(void);  /* sizeof(ppms_cloud) (152) */
+
 /* Scale-to-scale hand-over of the cascade without leaving the SP format (ppmstereo.py:726-732, 763-767): per frame,
  * dst = a * dst + b * interp(src), interp = F.interpolate(mode="bilinear", align_corners=True) from HxW to OHxOW.
  * src, dst: SP views with the same channel count (multiple of 8). */

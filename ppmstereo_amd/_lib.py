@@ -130,6 +130,13 @@ class Egress3D(C.Structure):
                 ("points_components", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Cloud(C.Structure):
+    """ppms_cloud: the compact cloud's destinations (records, optional pixel indices, counts), its workspace, Q, min_disp, the gates and format."""
+    _fields_ = [("records", c_void_p), ("frame_stride", c_int64), ("capacity", c_int64), ("index", c_void_p), ("index_frame_stride", c_int64),
+                ("counts", c_void_p), ("block_counts", c_void_p), ("block_counts_len", c_int64), ("q", c_float * 16), ("min_disp", c_float),
+                ("max_uncertainty", c_float), ("max_depth", c_float), ("format", C.c_int32), ("components", C.c_int32), ("reserved", C.c_int32)]
+
+
 _SIGS = {
     "ppms_version": (c_int, []),
     "ppms_last_error": (C.c_char_p, []),
@@ -172,6 +179,9 @@ _SIGS = {
     "ppms_egress_struct_size": (c_int, []),
     "ppms_scene_egress": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, C.POINTER(Egress3D), c_void_p]),
     "ppms_egress3d_struct_size": (c_int, []),
+    "ppms_cloud_egress": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, C.POINTER(Cloud), c_void_p]),
+    "ppms_cloud_egress_workspace": (c_int64, [c_int, c_int, c_int]),
+    "ppms_cloud_struct_size": (c_int, []),
     "ppms_sp_resize_blend": (c_int, [SP, SP, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p]),
     "ppms_avgpool": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ppms_axpby": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_float, c_int64, c_int64, c_void_p]),
@@ -237,6 +247,7 @@ _STRUCT_SIZES = (
      "ctypes layout of ppms_packed_view / ppms_yuv_packed_format / ppms_raw_packed_format differs from include/ppms.h"),
     ("ppms_egress_struct_size", (Egress,), "ctypes layout of ppms_egress differs from include/ppms.h"),
     ("ppms_egress3d_struct_size", (Egress3D,), "ctypes layout of ppms_egress3d differs from include/ppms.h"),
+    ("ppms_cloud_struct_size", (Cloud,), "ctypes layout of ppms_cloud differs from include/ppms.h"),
     ("ppms_pwchain_param_bytes", (ChainParams,), "ChainParams layout differs from pwchain.hip"),
 )
 

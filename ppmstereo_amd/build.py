@@ -25,8 +25,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libppms.so")
 STAMP = LIB + ".stamp"
 LOCK = LIB + ".lock"
-SOURCES = ["corr.hip", "conv_gemm2.hip", "conv_gemm5.hip", "conv_gemm6.hip", "gemm1.hip", "conv_stream.hip", "abi.hip", "loop_ops.hip", "glue_ops.hip", "mem_pick.hip", "egress.hip", "encoder_ops.hip", "video_ingest.hip", "mem_attn.hip", "attn16.hip", "pwchain.hip"]
-HEADERS = ["common.h", "corr_lookup.h", "conv_epilogue.h", "conv_check.h", "conv5_asm.h", "conv6_asm.h", "attn64_asm.h", os.path.join("..", "..", "include", "ppms.h")]
+SOURCES = ["corr.hip", "conv_gemm2.hip", "conv_gemm5.hip", "conv_gemm6.hip", "gemm1.hip", "conv_stream.hip", "abi.hip", "loop_ops.hip", "glue_ops.hip", "mem_pick.hip", "egress.hip", "cloud_egress.hip", "encoder_ops.hip", "video_ingest.hip", "mem_attn.hip", "attn16.hip", "pwchain.hip"]
+HEADERS = ["common.h", "corr_lookup.h", "conv_epilogue.h", "conv_check.h", "conv5_asm.h", "conv6_asm.h", "attn64_asm.h", "egress_shared.h", os.path.join("..", "..", "include", "ppms.h")]
 # Packed fp32 VALU forms (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32) are disabled (NO_PK).  Measured on MI355X: such an instruction
 # with op_sel:[0,1] (low result = src0.lo op src1.hi -- the compiler picks that form freely, e.g. in the bilinear resize kernel) reads
 # src1.hi as 0 in lanes 48-63 whenever ANOTHER wave on the same SIMD is issuing MFMAs, and the engine runs MFMA kernels beside small
@@ -38,6 +38,7 @@ NO_PK = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 # -DPPMS_ATTN_TIMING; read by tools/*_phase_probe.py).  They add stores of clock values and leave the results as they are.
 EXTRA = [x for x in os.environ.get("PPMS_BUILD_DEFINES", "").split() if x]
 FLAGS = COMMON + NO_PK + EXTRA
+MAX_PROCS = 16                                     # hipcc processes at a time
 
 
 def _digest() -> str:
@@ -85,7 +86,17 @@ def build(force: bool = False, verbose: bool = True) -> str:
             try:
                 objs = []
                 procs = []
-                for src in SOURCES:                # compile the translation units in parallel (independent hipcc processes; 16 -- bound this before adding a 17th)
+                def finish(cmd, pr):
+                    _, err = pr.communicate()
+                    err = "\n".join(ln for ln in err.splitlines() if noise not in ln)
+                    if err.strip():
+                        print(err, file=sys.stderr)
+                    if pr.returncode != 0:
+                        raise subprocess.CalledProcessError(pr.returncode, cmd)
+
+                for src in SOURCES:                # compile the translation units in parallel: independent hipcc processes, at most MAX_PROCS at a time
+                    if len(procs) >= MAX_PROCS:
+                        finish(*procs.pop(0))      # (the oldest: the list is in start order)
                     obj = os.path.join(tmp, src.replace(".hip", ".o"))
                     cmd = [hipcc] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj]
                     if verbose:
@@ -93,12 +104,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
                     procs.append((cmd, subprocess.Popen(cmd, stderr=subprocess.PIPE, text=True)))
                     objs.append(obj)
                 for cmd, pr in procs:
-                    _, err = pr.communicate()
-                    err = "\n".join(ln for ln in err.splitlines() if noise not in ln)
-                    if err.strip():
-                        print(err, file=sys.stderr)
-                    if pr.returncode != 0:
-                        raise subprocess.CalledProcessError(pr.returncode, cmd)
+                    finish(cmd, pr)
                 out = os.path.join(tmp, "libppms.so")
                 run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", out])
                 stamp = os.path.join(tmp, "stamp")

@@ -1,26 +1,14 @@
 // Output egress (ppmstereo_amd/engine.py: disparity_egress, driven by video.py's OutputSpec): the two one-launch-per-window kernels that
-// write the caller's disparity / depth / uncertainty planes and the point cloud, their shared pieces, checks and entry points.
-#include "common.h"
+// write the caller's disparity / depth / uncertainty planes and the point cloud, their stores, checks and entry points.  The thread mapping,
+// the loads and the geometry check are egress_shared.h's: cloud_egress.hip (the compacted cloud) is built from the same ones.
+#include "egress_shared.h"
 
 // ------------------------------------------------------------------------------------------------ disparity egress
 // The 1/4-scale engine's state after its last iteration -> the caller's output planes, one launch (include/ppms.h: the formulas):
 // crop (InputPadder.unpad), frame range, |flow_up[:, 0]|, the 4x bilinear upsampling of the uncertainty, depth = fb / d and the
 // conversions to the planes' formats.  HBM bound: one thread = a run of EG_RUN consecutive x of one output row; the run is loaded
 // and stored 16 bytes at a time (8 for a run of bytes) where its address allows it, element by element at row ends and on
-// rows that start unaligned.  Every offset is 64-bit.
-constexpr int EG_RUN = 8;
-// bilinear_kernel's expression for output pixel (oy, ox) of one H x W source plane `s`, align_corners = 0, restated (every operation is one
-// fp32 operation in the same order, and the build contracts nothing: the same bits as ppms_bilinear with mul = 1).  bilinear_kernel does not
-// call it: routed through this function its instructions come out in another order, and its generated code is kept as it is.
-__device__ __forceinline__ float bilinear_tap(const float* __restrict__ s, int H, int W, float sh, float sw, int oy, int ox) {
-    const float fy = fmaxf(sh * (oy + 0.5f) - 0.5f, 0.0f);
-    const float fx = fmaxf(sw * (ox + 0.5f) - 0.5f, 0.0f);
-    const int y0 = (int)fy, x0 = (int)fx;
-    const int y1 = y0 + ((y0 < H - 1) ? 1 : 0), x1 = x0 + ((x0 < W - 1) ? 1 : 0);
-    const float ly = fy - y0, lx = fx - x0;
-    const float hy = 1.0f - ly, hx = 1.0f - lx;
-    return hy * (hx * s[y0 * W + x0] + lx * s[y0 * W + x1]) + ly * (hx * s[y1 * W + x0] + lx * s[y1 * W + x1]);
-}
+// rows that start unaligned.  Every offset is 64-bit.  (EG_RUN, bilinear_tap, egress_map and the two loads: egress_shared.h.)
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 // min(top, rint(v)) for v >= 0 (a magnitude times a positive scale); NaN -> 0
 __device__ __forceinline__ unsigned egress_quant(float v, float top) {
@@ -46,45 +34,6 @@ __device__ __forceinline__ void egress_store_run(const ppms_egress_plane& p, int
         for (int j = 0; j < EG_RUN; ++j)
             if (j < n) dst[j] = v[j];
     }
-}
-// ---- the pieces both kernels are built from
-// thread idx -> its run: n elements from column x0 of row y of output frame `frame`; (sy, sx) = the run's first pixel in the padded H x W frame
-struct egress_run { int x0, y, n, sy, sx; int64_t frame; };
-__device__ __forceinline__ egress_run egress_map(int64_t idx, int rpr, int H0, int W0, int pad_left, int pad_top) {
-    egress_run r;
-    r.x0 = (int)(idx % rpr) * EG_RUN;
-    const int64_t row = idx / rpr;                                       // frame * H0 + y of the output
-    r.y = (int)(row % H0);
-    r.frame = row / H0;
-    r.n = W0 - r.x0 < EG_RUN ? W0 - r.x0 : EG_RUN;                       // elements of this run inside the row
-    r.sy = r.y + pad_top, r.sx = r.x0 + pad_left;
-    return r;
-}
-// d = |flow_up[frame0 + frame, 0]| over the run (past the row's end the last element again)
-__device__ __forceinline__ void egress_load_disparity(const float* __restrict__ flow_up, int H, int W, int frame0, const egress_run& r,
-                                                      float (&d)[EG_RUN]) {
-    const float* s = flow_up + ((frame0 + r.frame) * 2 * H + r.sy) * W + r.sx;      // channel 0 of (T, 2, H, W)
-    if (r.n == EG_RUN && ((uintptr_t)s & 15) == 0) {
-        const f32x4 a = gld<f32x4>(s), b = gld<f32x4>(s + 4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            d[j] = a[j];
-            d[4 + j] = b[j];
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < EG_RUN; ++j) d[j] = s[j < r.n ? j : r.n - 1];
-    }
-#pragma unroll
-    for (int j = 0; j < EG_RUN; ++j) d[j] = fabsf(d[j]);
-}
-// u = |the 4x bilinear upsampling of unc[frame0 + frame]| over the run
-__device__ __forceinline__ void egress_load_uncertainty(const float* __restrict__ unc, int H, int W, int frame0, float sh, float sw,
-                                                        const egress_run& r, float (&u)[EG_RUN]) {
-    const int h = H / 4, w = W / 4;
-    const float* s = unc + (frame0 + r.frame) * h * w;
-#pragma unroll
-    for (int j = 0; j < EG_RUN; ++j) u[j] = fabsf(bilinear_tap(s, h, w, sh, sw, r.sy, r.sx + (j < r.n ? j : r.n - 1)));
 }
 __device__ __forceinline__ void egress_store_disparity(const ppms_egress& o, const egress_run& r, const float (&d)[EG_RUN]) {
     if (o.disparity.format == PPMS_FMT_F32) {
@@ -250,8 +199,7 @@ __global__ __launch_bounds__(256) void scene_egress_kernel(const float* __restri
 extern "C" int ppms_egress_struct_size(void) { return (int)sizeof(ppms_egress); }
 extern "C" int ppms_egress3d_struct_size(void) { return (int)sizeof(ppms_egress3d); }
 // What both egress entry points check, under the name `who` of the one called: the geometry, the three planes and their constants, and -- from
-// ppms_scene_egress (e != nullptr) -- the points plane, q and the gates.  On success the launch geometry.
-struct egress_launch { int rpr; int64_t total; float sh, sw; };
+// ppms_scene_egress (e != nullptr) -- the points plane, q and the gates.  On success the launch geometry (egress_shared.h).
 static int egress_check(const char* who, const float* flow_up, const float* unc, int T, int H, int W, int frame0, int n_frames, int pad_left, int pad_top,
                         int H0, int W0, const ppms_egress& o, const ppms_egress3d* e, egress_launch* g) {
     const bool points = e && e->points.ptr;
@@ -259,12 +207,7 @@ static int egress_check(const char* who, const float* flow_up, const float* unc,
         PPMS_REQUIRE(o.disparity.ptr || o.depth.ptr || o.uncertainty.ptr || points, "%s: no plane: disparity, depth, uncertainty and points are all NULL", who);
     else
         PPMS_REQUIRE(o.disparity.ptr || o.depth.ptr || o.uncertainty.ptr, "%s: no plane: disparity, depth and uncertainty are all NULL", who);
-    PPMS_REQUIRE(T > 0 && H > 0 && W > 0 && H0 > 0 && W0 > 0, "%s: T = %d, H = %d, W = %d, H0 = %d, W0 = %d must be positive", who, T, H, W, H0, W0);
-    PPMS_REQUIRE(H % 4 == 0 && W % 4 == 0, "%s: H = %d, W = %d must be multiples of 4", who, H, W);
-    PPMS_REQUIRE(pad_left >= 0 && pad_top >= 0 && (int64_t)pad_top + H0 <= H && (int64_t)pad_left + W0 <= W,
-                 "%s: the crop pad_left = %d, pad_top = %d, H0 = %d, W0 = %d lies outside the %d x %d frame", who, pad_left, pad_top, H0, W0, H, W);
-    PPMS_REQUIRE(n_frames > 0, "%s: n_frames = %d must be positive", who, n_frames);
-    PPMS_REQUIRE(frame0 >= 0 && (int64_t)frame0 + n_frames <= T, "%s: frame0 = %d, n_frames = %d leave the T = %d frames", who, frame0, n_frames, T);
+    if (const int rc = egress_check_geometry(who, T, H, W, frame0, n_frames, pad_left, pad_top, H0, W0, g)) return rc;
     PPMS_REQUIRE(((o.disparity.ptr || o.depth.ptr || points) ? flow_up != nullptr : true) && (o.uncertainty.ptr ? unc != nullptr : true),
                  "%s: null flow_up / unc source of a requested plane", who);
     if (points)
@@ -306,10 +249,6 @@ static int egress_check(const char* who, const float* flow_up, const float* unc,
         const bool reads_u = ((o.depth.ptr || points) && e->max_uncertainty < INFINITY) || (points && e->points_components == 4);
         PPMS_REQUIRE(!reads_u || unc != nullptr, "%s: null unc: the max_uncertainty gate and points_components = 4 read it", who);
     }
-    g->rpr = (W0 + EG_RUN - 1) / EG_RUN;                                 // runs per output row
-    g->total = (int64_t)n_frames * H0 * g->rpr;
-    PPMS_REQUIRE((g->total + 255) / 256 <= 0x7fffffff, "%s: %lld threads exceed one grid", who, (long long)g->total);
-    g->sh = (float)(H / 4) / (float)H, g->sw = (float)(W / 4) / (float)W;            // ppms_bilinear's scales for (H/4, W/4) -> (H, W): 0.25
     return PPMS_OK;
 }
 extern "C" int ppms_disparity_egress(const float* flow_up, const float* unc, int T, int H, int W, int frame0, int n_frames, int pad_left, int pad_top,

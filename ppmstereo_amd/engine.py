@@ -701,7 +701,8 @@ class ScaleEngine:
         return self.FLOW_OUT
 
     def egress(self, out, frame0: int, n_frames: int, pad_left: int, pad_top: int, h0: int, w0: int):
-        """ppms_disparity_egress (``out``: an L.Egress) or ppms_scene_egress (an L.Egress3D: points, gates) on the current stream: the state the
+        """ppms_disparity_egress (``out``: an L.Egress), ppms_scene_egress (an L.Egress3D: points, gates) or ppms_cloud_egress (an L.Cloud: the
+        compact cloud's two launches) on the current stream: the state the
         last iteration left -- FLOW_OUT (read in place, channel 0) and the
         1/4-resolution UNC -- to the caller's planes: frames [frame0, frame0 + n_frames), the h0 x w0 crop at (pad_top, pad_left).  Valid
         behind an iterate(need_up=True) of an unsharded engine at the 1/4 scale (full resolution = 4 h x 4 w)."""
@@ -759,13 +760,15 @@ def bilinear(x: torch.Tensor, size, align_corners: bool, mul: float = 1.0) -> to
 def disparity_egress(flow_up: torch.Tensor, unc: torch.Tensor, out, frame0: int, n_frames: int, pad_left: int, pad_top: int, h0: int, w0: int):
     """One ppms_disparity_egress launch on the current stream (include/ppms.h): flow_up fp32 (T, 2, H, W), unc fp32 (T, H/4, W/4), both
     contiguous on the GPU; ``out``: the planes (device pointers, byte strides, formats) and conversion constants.  An ``L.Egress3D`` (the same
-    with a points plane, Q and the gates) makes it one ppms_scene_egress launch."""
+    with a points plane, Q and the gates) makes it one ppms_scene_egress launch, an ``L.Cloud`` (the compact cloud's destinations, workspace, Q and
+    gates) the two launches of ppms_cloud_egress."""
     L.require_gpu(flow_up, unc)
     T, two, H, W = flow_up.shape
     if (flow_up.dtype != torch.float32 or unc.dtype != torch.float32 or two != 2 or tuple(unc.shape) != (T, H // 4, W // 4)
             or not flow_up.is_contiguous() or not unc.is_contiguous()):
         raise ValueError(f"disparity_egress: contiguous fp32 flow_up (T, 2, H, W) and unc (T, H/4, W/4) expected, got {tuple(flow_up.shape)} and {tuple(unc.shape)}")
-    if not isinstance(out, (L.Egress, L.Egress3D)):
-        raise TypeError(f"disparity_egress: out must be an L.Egress or an L.Egress3D, got {type(out).__name__}")
-    entry = L.load().ppms_scene_egress if isinstance(out, L.Egress3D) else L.load().ppms_disparity_egress
+    if not isinstance(out, (L.Egress, L.Egress3D, L.Cloud)):
+        raise TypeError(f"disparity_egress: out must be an L.Egress, an L.Egress3D or an L.Cloud, got {type(out).__name__}")
+    entry = {L.Egress: "ppms_disparity_egress", L.Egress3D: "ppms_scene_egress", L.Cloud: "ppms_cloud_egress"}[type(out)]
+    entry = getattr(L.load(), entry)
     L.check(entry(flow_up.data_ptr(), unc.data_ptr(), T, H, W, frame0, n_frames, pad_left, pad_top, h0, w0, C.byref(out), L.stream_ptr()))

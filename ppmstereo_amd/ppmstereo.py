@@ -297,7 +297,8 @@ class PPMStereoHotPath(nn.Module):
         egress (test_mode, b = 1, no shard): an ``_EgressCall`` -- after the last 1/4-scale iteration ONE ppms_disparity_egress launch on that
         scale's stream replaces the final clone + bilinear pair and writes the requested planes (crop, frame range, formats); the call
         then returns {"disparity", "depth"?, "uncertainties"?}: device tensors (n, 1, H0, W0), and appends nothing to the lists.  A spec with
-        points or a gate (``OutputSpec.scene``) makes that launch ppms_scene_egress and adds "points": (n, H0, W0, C).
+        points or a gate (``OutputSpec.scene``) makes that launch ppms_scene_egress and adds "points": (n, H0, W0, C); a spec with a cloud adds
+        ppms_cloud_egress's two launches behind it and "cloud", "cloud_counts", "cloud_index" (``_EgressCall.launch``).
         Returns (flow_up (T,1,H,W), uncertainty (T,1,H,W)) = predictions[-1], uncertainties[-1]."""
         if egress is not None:
             if not test_mode:
@@ -577,6 +578,10 @@ class PPMStereo(PPMStereoHotPath):
         tensor is made); crop = (pad_left, pad_top, H0, W0) inside the frame (default: the whole frame), frames = (from, to) (default: all).
         With ``OutputSpec(points=..., Q=...)`` the dict also has "points", the organised cloud (1, n, H0, W0, C) of ``cv2.reprojectImageTo3D`` with
         the spec's gates applied (x, y count from the crop's corner), written by the same single launch (then ppms_scene_egress).
+        With ``OutputSpec(cloud=..., Q=...)`` the dict also has the compact cloud, written by ppms_cloud_egress's two launches behind that one, with no
+        host synchronisation: "cloud" (1, n, capacity, C), the valid points of each frame in row-major pixel order from row 0 on, "cloud_counts"
+        (1, n) int32, their numbers, and with ``cloud_index=True`` "cloud_index" (1, n, capacity) int32, y * W0 + x of every record.  Rows past
+        min(count, capacity) of a frame are unspecified (never written); a count above the capacity tells of a truncated frame.
         rectify=None and output=None (the defaults) add no launch to the calls above."""
         if flow_init is not None:
             raise NotImplementedError("flow_init: the reference's own path for it reads undefined state (ppmstereo.py:691-693, 763)")
@@ -708,6 +713,11 @@ class PPMStereo(PPMStereoHotPath):
         ``OutputSpec(points="f32", Q=Q, max_uncertainty=..., max_depth=...)``: "points" is the organised cloud (N, H, W, C) -- X, Y, Z[, w] per pixel
         of the caller's image, NaN where a gate or min_disp takes the pixel -- from the same launch per window (ppms_scene_egress), 12 bytes per pixel
         of the kept frames for "xyz" f32; ``rectify=`` in front and points behind need the one calibration's maps and Q.
+        ``OutputSpec(cloud="f32", Q=Q, ...)``: the compact cloud, from two more launches per window (ppms_cloud_egress).  "cloud" is a list of N
+        views (min(count_f, capacity), C) of one pinned (N, capacity, C) buffer -- the valid points of frame f in row-major pixel order, the bits of
+        the organised cloud at its valid pixels --, "cloud_index" (``cloud_index=True``) likewise (…,) int32 y * W + x, "cloud_counts" (N,) int64, the
+        untruncated numbers.  Per window the counts are copied to the host first and then only min(count_f, capacity) records of each kept frame:
+        by construction count_f * C * element bytes cross the bus where the organised cloud moves H * W * C; nothing about time is measured here.
         rectify: a ``StereoRectifier`` -- the video holds the RAW frames of an unrectified rig, (N, 2, 3, Hs, Ws) uint8 or a ``YUVStereoVideo`` of
         its source size Hs x Ws.  Each window's raw bytes are copied as above, the maps once per device (6 bytes per rectified pixel and view):
         the bits of the call on the uint8 video of ``RectifyMap.apply_u8``.  H x W of the results (and of the ``InputPadder``) is the rectified
@@ -760,10 +770,19 @@ class PPMStereo(PPMStereoHotPath):
             kept_d.append(d[keep_from:keep_to])
             kept_u.append(u[keep_from:keep_to])
 
+        ragged = ("cloud", "cloud_index")                                  # per frame only the records that exist are copied
+
         def keep_planes(planes, padder, keep_from, keep_to, dst_from, dst_to):
             idle_stream()
             for key, plane in planes.items():
-                host[key][dst_from:dst_to].copy_(plane[0])                 # kept frames only, device -> their slice of the pinned result
+                if key not in ragged:
+                    host[key][dst_from:dst_to].copy_(plane[0])             # kept frames only, device -> their slice of the pinned result
+            if "cloud" in planes:                                          # the counts are on the host now: min(count, capacity) records per kept frame
+                for i, count in enumerate(host["cloud_counts"][dst_from:dst_to].tolist()):
+                    for key in ragged:
+                        if key in planes:
+                            k = min(count, planes[key].shape[2])
+                            host[key][dst_from + i, :k].copy_(planes[key][0, i, :k])
 
         if output is not None:
             host = output.empty(num_ims, int(H0), int(W0), "cpu", pin_memory=True)           # allocated once; every window fills its slice
@@ -786,5 +805,11 @@ class PPMStereo(PPMStereoHotPath):
                 pending = item
             collect(*pending)
         if output is not None:
+            if "cloud" in host:                                            # views of the pinned buffers: no row past a frame's records exists
+                counts = host["cloud_counts"].tolist()
+                for key in ragged:
+                    if key in host:
+                        host[key] = [host[key][f, :min(c, host[key].shape[1])] for f, c in enumerate(counts)]
+                host["cloud_counts"] = host["cloud_counts"].to(torch.int64)                  # the untruncated numbers
             return finish(host)
         return finish({"disparity": torch.cat(kept_d).squeeze(1).abs()[:, :1], "uncertainties": torch.cat(kept_u).squeeze(1).abs()[:, :1]})

@@ -1,0 +1,213 @@
+"""CPU: the compact point cloud.  ppms_cloud_egress (the valid points of ppms_scene_egress's organised cloud, counted, in row order) is part of
+the C ABI, its ctypes binding has the header's argument list and struct layout, it refuses bad arguments before touching a device; OutputSpec
+validates the four new options and leaves a spec without them as it was; its ``reference`` makes the cloud of its own organised points and
+validity.  No device compute; every comparison is exact."""
+import ctypes
+import math
+import os
+import re
+
+import pytest
+import torch
+
+from test_egress import EINVAL, ROOT, header_args
+from test_egress_points import IDENTITY, grid_inputs
+
+NAME = "ppms_cloud_egress"
+nan, inf = math.nan, math.inf
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from ppmstereo_amd import _lib as L
+    return L.load()
+
+
+def test_declared_exported_bound_and_struct_layout(lib):
+    from ppmstereo_amd import _lib as L
+    for name in (NAME, "ppms_cloud_egress_workspace", "ppms_cloud_struct_size"):
+        assert name in L.EXPORTS and hasattr(lib, name)
+    assert lib.ppms_version() == 4
+    args = header_args(NAME)
+    assert args == header_args("ppms_scene_egress")[:-2] + ["const ppms_cloud* out", "void* stream"]
+    ctype = {"int": ctypes.c_int, "const float*": ctypes.c_void_p, "void*": ctypes.c_void_p, "const ppms_cloud*": ctypes.POINTER(L.Cloud)}
+    res, bound = L._SIGS[NAME]
+    assert res is ctypes.c_int and bound == [ctype[a.rsplit(" ", 1)[0]] for a in args]
+    assert header_args("ppms_cloud_struct_size") == ["void"]
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ppms.h")).read(), flags=re.S)
+    assert re.search(r"\bint64_t\s+ppms_cloud_egress_workspace\s*\(\s*int n_frames,\s*int H0,\s*int W0\s*\)\s*;", src)
+    assert L._SIGS["ppms_cloud_egress_workspace"] == (ctypes.c_int64, [ctypes.c_int] * 3)
+    # the struct, field for field as the header declares it
+    body = re.search(r"typedef struct ppms_cloud \{(.*?)\} ppms_cloud;", src, flags=re.S).group(1)
+    declared = [n for decl in body.split(";") for n in re.findall(r"(\w+)(?:\[\d+\])?\s*(?:,|$)", decl.strip())]
+    assert declared == [n for n, _ in L.Cloud._fields_] == ["records", "frame_stride", "capacity", "index", "index_frame_stride", "counts", "block_counts",
+                                                          "block_counts_len", "q", "min_disp", "max_uncertainty", "max_depth", "format", "components",
+                                                          "reserved"]
+    assert lib.ppms_cloud_struct_size() == ctypes.sizeof(L.Cloud) == 8 * 8 + 64 + 3 * 4 + 3 * 4
+    assert (L.Cloud.capacity.offset, L.Cloud.counts.offset, L.Cloud.q.offset, L.Cloud.min_disp.offset, L.Cloud.format.offset) == (16, 40, 64, 128, 140)
+    # the two older doors are as they were
+    assert lib.ppms_egress_struct_size() == ctypes.sizeof(L.Egress) == 112 and lib.ppms_egress3d_struct_size() == ctypes.sizeof(L.Egress3D) == 224
+
+
+def test_workspace_entries(lib):
+    """One entry per workgroup: 256 runs of 8 pixels of one frame each, a row's last run may be short."""
+    ws = lib.ppms_cloud_egress_workspace
+    assert ws(2, 37, 50) == 2 * 2 and ws(1, 32, 64) == 1 and ws(3, 32, 64) == 3 and ws(1, 32, 65) == 2 and ws(1, 516, 1024) == 258
+    assert ws(1, 1, 1) == 1 and ws(0, 8, 8) == 0 and ws(1, 0, 8) == 0 and ws(1, 65536, 32768) == 0
+
+
+# ---- argument refusal: test_egress.py's geometry (frames [1, 3) of T = 3, the 37 x 50 crop at (13, 7) of 64 x 64), "xyz" f32 records with a
+# ---- capacity of 1000 and a gap between the frames, an index, Q = identity and both gates on ---------------------------------------------------
+def _call(lib, null_out=False, flow=0x100000, unc=0x200000, T=3, H=64, W=64, frame0=1, n_frames=2, pad_left=7, pad_top=13, H0=37, W0=50,
+          records=0x300000, frame_stride=12008, capacity=1000, index=0x400000, index_frame_stride=4004, counts=0x500000, block_counts=0x600000,
+          block_counts_len=4, q=IDENTITY, min_disp=0.25, max_uncertainty=0.5, max_depth=80.0, format=0, components=3, reserved=0):
+    """Pointers into device memory are never dereferenced on the host: every check comes before the launch."""
+    from ppmstereo_amd import _lib as L
+    out = L.Cloud(records or None, frame_stride, capacity, index or None, index_frame_stride, counts or None, block_counts or None, block_counts_len,
+                  (ctypes.c_float * 16)(*q), min_disp, max_uncertainty, max_depth, format, components, reserved)
+    return lib.ppms_cloud_egress(flow or None, unc or None, T, H, W, frame0, n_frames, pad_left, pad_top, H0, W0, None if null_out else ctypes.byref(out), None)
+
+
+def _q(i, v):
+    return [v if j == i else x for j, x in enumerate(IDENTITY)]
+
+
+# (what the call's message must speak of, the one thing that is wrong with the call)
+BAD = [("null out", dict(null_out=True)), ("null records", dict(records=0)), ("null counts", dict(counts=0)), ("null flow_up", dict(flow=0)),
+       ("block_counts", dict(block_counts=0)), ("block_counts_len", dict(block_counts_len=3)), ("block_counts_len", dict(block_counts_len=0)),
+       ("null unc", dict(unc=0)), ("null unc", dict(unc=0, max_uncertainty=inf, components=4, frame_stride=16000)),
+       ("format", dict(format=2)), ("format", dict(format=3)), ("format", dict(format=-1)), ("format", dict(format=4)),
+       ("components", dict(components=2)), ("components", dict(components=5)), ("components", dict(components=0)),
+       ("capacity", dict(capacity=0)), ("capacity", dict(capacity=-5)), ("capacity", dict(capacity=1 << 31)),
+       ("frame_stride", dict(frame_stride=11996)), ("frame_stride", dict(components=4, frame_stride=15996)),
+       ("frame_stride", dict(format=1, frame_stride=5998)), ("frame_stride", dict(frame_stride=0)),
+       ("index_frame_stride", dict(index_frame_stride=3996)), ("index_frame_stride", dict(index_frame_stride=0)),
+       ("multiples of the 4-byte element", dict(records=0x300002)), ("multiples of the 4-byte element", dict(frame_stride=12010)),
+       ("multiples of the 2-byte element", dict(format=1, records=0x300001)), ("multiples of the 2-byte element", dict(format=1, frame_stride=6001)),
+       ("multiples of the 4-byte element", dict(index=0x400002)), ("multiples of the 4-byte element", dict(index_frame_stride=4006)),
+       ("multiples of the 4-byte element", dict(counts=0x500002)), ("multiples of the 4-byte element", dict(block_counts=0x600001)),
+       ("q[5]", dict(q=_q(5, nan))), ("q[15]", dict(q=_q(15, inf))), ("q[0]", dict(q=_q(0, -inf))),
+       ("min_disp", dict(min_disp=inf)), ("min_disp", dict(min_disp=nan)), ("min_disp", dict(min_disp=-inf)),
+       ("max_uncertainty", dict(max_uncertainty=nan)),
+       ("max_depth", dict(max_depth=0.0)), ("max_depth", dict(max_depth=-1.0)), ("max_depth", dict(max_depth=nan)), ("max_depth", dict(max_depth=-inf)),
+       ("reserved", dict(reserved=1)),
+       ("H0 * W0", dict(H=65536, W=32768, H0=65536, W0=32768, pad_left=0, pad_top=0)),
+       # the shared check of the geometry and the frame range, under this entry point's name
+       ("crop", dict(pad_left=15)), ("crop", dict(H0=52)), ("crop", dict(pad_top=-1)), ("multiples of 4", dict(W=62)), ("positive", dict(W0=0)),
+       ("positive", dict(T=0)), ("frame0", dict(frame0=2)), ("frame0", dict(frame0=-1)), ("n_frames", dict(n_frames=0))]
+
+
+@pytest.mark.parametrize("about,bad", BAD, ids=[about.replace(" ", "_") + ":" + ",".join(k if k == "q" else f"{k}={v}" for k, v in b.items()) for about, b in BAD])
+def test_bad_arguments_return_einval_with_a_message_and_no_device(lib, about, bad):
+    lib.ppms_mem_attn_splits(3, 3, 256, 1)                      # (a successful call in between: the message below is this call's)
+    assert _call(lib, **bad) == EINVAL, bad
+    msg = lib.ppms_last_error()
+    assert msg and b"cloud_egress" in msg and about.encode() in msg, (bad, msg)
+
+
+# ---- OutputSpec ------------------------------------------------------------------------------------------------------------------------
+CAL = dict(focal_px=700.0, baseline=0.25)
+
+
+def test_output_spec_validation_of_the_new_options():
+    from ppmstereo_amd import _lib as L
+    from ppmstereo_amd.ppmstereo import OutputSpec
+    Q = OutputSpec.q_matrix(700.0, 0.25, 19.5, 11.25)
+    for kw in (dict(cloud="f32"), dict(cloud="f16"),                                                                 # a cloud without Q
+               dict(cloud="u16", Q=Q), dict(cloud="f64", Q=Q), dict(cloud=True, Q=Q), dict(cloud="f32", Q=Q, cloud_layout="xyzi"),
+               dict(cloud="f32", Q=Q, cloud_layout=None), dict(cloud="f32", Q=Q, cloud_index=1), dict(cloud="f32", Q=Q, cloud_index="yes"),
+               dict(cloud="f32", Q=Q, cloud_capacity=0), dict(cloud="f32", Q=Q, cloud_capacity=-3), dict(cloud="f32", Q=Q, cloud_capacity=2.5),
+               dict(cloud="f32", Q=Q, cloud_capacity=1 << 31), dict(cloud="f32", Q=Q, cloud_capacity=True),
+               dict(cloud="f32", Q=Q, min_disp=inf), dict(cloud="f32", Q=Q, min_disp=nan),
+               dict(Q=Q, cloud_layout="xyzw"), dict(Q=Q, cloud_index=True), dict(Q=Q, cloud_capacity=10)):            # the cloud's options without a cloud
+        with pytest.raises(ValueError):
+            OutputSpec(**kw)
+    with pytest.raises(TypeError):
+        OutputSpec("f32", None, "f32", 256.0, None, None, 1000.0, 2.0 ** -8, None, "xyz", Q, None, None, "f32")      # the new options are keyword only
+    s = OutputSpec(cloud="f16", cloud_layout="xyzw", cloud_index=True, cloud_capacity=20, Q=Q, max_uncertainty=0.1, max_depth=30.0, depth="u16",
+                   points="f32", **CAL)
+    assert list(s.formats().items()) == [("disparity", "f32"), ("depth", "u16"), ("uncertainties", "f32"), ("points", "f32"), ("cloud", "f16"),
+                                         ("cloud_counts", "i32"), ("cloud_index", "i32")]
+    assert s.scene and (s.cloud_components, s.points_components) == (4, 3)
+    planes = s.empty(2, 5, 7, "cpu")
+    assert [(k, tuple(v.shape), v.dtype) for k, v in planes.items()][3:] == [("points", (2, 5, 7, 3), torch.float32), ("cloud", (2, 20, 4), torch.float16),
+                                                                            ("cloud_counts", (2,), torch.int32), ("cloud_index", (2, 20), torch.int32)]
+    ws = torch.empty(6, dtype=torch.int32)
+    st = s.cloud_struct(planes, ws)
+    assert type(st) is L.Cloud and (st.records, st.frame_stride, st.capacity) == (planes["cloud"].data_ptr(), 20 * 8, 20)
+    assert (st.index, st.index_frame_stride, st.counts) == (planes["cloud_index"].data_ptr(), 80, planes["cloud_counts"].data_ptr())
+    assert (st.block_counts, st.block_counts_len) == (ws.data_ptr(), 6) and list(st.q) == Q.float().flatten().tolist()
+    assert (st.min_disp, st.max_uncertainty, st.max_depth, st.format, st.components, st.reserved) == (2.0 ** -8, s.max_uncertainty, 30.0, 1, 4, 0)
+    # the defaults: "xyz", no index, a capacity that can never truncate, the gates off; no gate and no points: the planes' launch is the oldest door's
+    d = OutputSpec(cloud="f32", Q=Q)
+    assert list(d.formats()) == ["disparity", "uncertainties", "cloud", "cloud_counts"] and not d.scene and d.cloud_capacity is None
+    planes = d.empty(3, 4, 6, "cpu")
+    assert tuple(planes["cloud"].shape) == (3, 24, 3) and planes["cloud"].dtype == torch.float32 and "cloud_index" not in planes
+    st = d.cloud_struct(planes, torch.empty(3, dtype=torch.int32))
+    assert (st.frame_stride, st.capacity, st.index, st.index_frame_stride, st.format, st.components) == (24 * 12, 24, None, 0, 0, 3)
+    assert st.max_uncertainty == inf and st.max_depth == inf
+    assert type(d.struct(planes)) is L.Egress
+
+
+def test_a_spec_without_the_new_options_is_as_before():
+    from ppmstereo_amd.ppmstereo import OutputSpec
+    Q = OutputSpec.q_matrix(700.0, 0.25, 19.5, 11.25)
+    kw = dict(disparity="u16", depth="u16", uncertainty="u8", points="f16", points_layout="xyzw", Q=Q, max_uncertainty=0.1, max_depth=30.0, **CAL)
+    old, new = OutputSpec(**kw), OutputSpec(cloud="f32", cloud_index=True, **kw)
+    assert (old.cloud, old.cloud_layout, old.cloud_index, old.cloud_capacity) == (None, "xyz", False, None)
+    assert list(old.formats().items()) == [("disparity", "u16"), ("depth", "u16"), ("uncertainties", "u8"), ("points", "f16")]
+    assert list(OutputSpec().formats().items()) == [("disparity", "f32"), ("uncertainties", "f32")] and not OutputSpec().scene
+    planes = old.empty(2, 5, 7, "cpu")
+    assert list(planes) == ["disparity", "depth", "uncertainties", "points"] and tuple(planes["points"].shape) == (2, 5, 7, 4)
+    # with a cloud beside them the planes' structs are the same bytes: the planes' launch is the one made before
+    assert old.scene and new.scene and bytes(old.scene_struct(planes)) == bytes(new.scene_struct(planes)) and bytes(old.struct(planes)) == bytes(new.struct(planes))
+    assert list(new.empty(2, 5, 7, "cpu"))[:4] == list(planes)
+    d, u = grid_inputs()
+    a, b = old.reference(d, u), new.reference(d, u)
+    assert list(a) == ["disparity", "depth", "uncertainties", "points"] and list(b) == list(a) + ["cloud", "cloud_index", "cloud_counts"]
+    bits = lambda t: t.view({2: torch.int16, 4: torch.int32}[t.element_size()]) if t.element_size() > 1 else t
+    for k in a:
+        assert a[k].dtype == b[k].dtype and torch.equal(bits(a[k]), bits(b[k])), k
+
+
+# ---- reference ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("fmt,layout", [("f32", "xyz"), ("f32", "xyzw"), ("f16", "xyz"), ("f16", "xyzw")])
+def test_reference_cloud_is_its_own_points_at_the_valid_pixels(fmt, layout):
+    from ppmstereo_amd.ppmstereo import OutputSpec
+    f, B, min_disp, max_u, max_z = 700.0, 0.3, 0.5, 0.6, 20.0
+    spec = OutputSpec(min_disp=min_disp, points=fmt, points_layout=layout, cloud=fmt, cloud_layout=layout, cloud_index=True, cloud_capacity=5,
+                      Q=OutputSpec.q_matrix(f, B, 19.5, 11.25), max_uncertainty=max_u, max_depth=max_z)
+    d, u = grid_inputs(min_disp=min_disp)
+    got = spec.reference(d, u)
+    C = 4 if layout == "xyzw" else 3
+    pts = got["points"]
+    assert tuple(pts.shape) == (2, 24, 40, C) and pts.dtype == (torch.float32 if fmt == "f32" else torch.float16)
+    valid = ~pts[..., 2].float().isnan()
+    # every kind of pixel is there: valid, gated by u, gated by Z, NaN d, d < min_disp
+    D, U = d[:, 0].abs(), u[:, 0]
+    vd, vu = D >= min_disp, U <= spec.max_uncertainty
+    assert valid.sum() > 100 and (vd & ~vu).sum() > 100 and (vd & vu & ~valid).sum() > 20 and D.isnan().sum() > 50 and (~vd & ~D.isnan()).sum() > 50
+    assert not (valid & ~(vd & vu)).any()
+    assert isinstance(got["cloud"], list) and isinstance(got["cloud_index"], list) and len(got["cloud"]) == len(got["cloud_index"]) == 2
+    assert got["cloud_counts"].dtype == torch.int64 and got["cloud_counts"].tolist() == valid.flatten(1).sum(1).tolist()
+    assert int(got["cloud_counts"].sum()) == int(valid.sum()) and min(got["cloud_counts"].tolist()) > 5          # the whole cloud, whatever the capacity
+    for fr in range(2):
+        cloud, index = got["cloud"][fr], got["cloud_index"][fr]
+        assert cloud.dtype == pts.dtype and tuple(cloud.shape) == (int(got["cloud_counts"][fr]), C) and index.dtype == torch.int32
+        assert torch.equal(cloud, pts[fr][valid[fr]]) and not cloud[:, :3].float().isnan().any()
+        assert tuple(index.shape) == (cloud.shape[0],) and (index[1:] > index[:-1]).all() and 0 <= int(index[0]) and int(index[-1]) < 24 * 40
+        assert torch.equal(pts[fr].reshape(-1, C)[index.long()], cloud)
+        if C == 4:
+            assert torch.equal(cloud[:, 3], U[fr].flatten()[index.long()].to(pts.dtype))
+    # a d of lower rank is one frame; the cloud's format and layout are its own, not the points'
+    one = spec.reference(d[1, 0], u[1, 0])
+    assert len(one["cloud"]) == 1 and torch.equal(one["cloud"][0], got["cloud"][1]) and torch.equal(one["cloud_index"][0], got["cloud_index"][1])
+    other = OutputSpec(min_disp=min_disp, points="f16", points_layout="xyz", cloud="f32", cloud_layout="xyzw", Q=spec.Q, max_uncertainty=max_u, max_depth=max_z)
+    o = other.reference(d, u)
+    assert "cloud_index" in o and o["points"].dtype == torch.float16 and o["cloud"][0].dtype == torch.float32 and o["cloud"][0].shape[1] == 4
+    if (fmt, layout) == ("f32", "xyzw"):
+        assert torch.equal(o["cloud"][0], got["cloud"][0])
+    with pytest.raises(ValueError):
+        OutputSpec(cloud="f32", cloud_layout="xyzw", Q=spec.Q).reference(d)                      # w, and no u
+    with pytest.raises(ValueError):
+        OutputSpec(cloud="f32", Q=spec.Q, uncertainty=None).reference(d[0, 0, 0])               # no pixel grid

@@ -11,7 +11,13 @@ windows through the ClipPipeline: only kept frames cross on side B).  The bar (D
     python tools/egress_probe.py --points [--runs 12]
 The point-cloud A/B, both sides on this tree and on a uint8 video that lies on the device: A = forward(test_mode=True), then the same arithmetic
 in torch on the device (OutputSpec.reference on the float32 results) and the cloud's copy to the host; B = forward(..., output=spec) -- "xyz" f32
-points with both gates, from the one ppms_scene_egress launch -- and the same copy.  The two clouds are compared bit for bit (NaN = NaN)."""
+points with both gates, from the one ppms_scene_egress launch -- and the same copy.  The two clouds are compared bit for bit (NaN = NaN).
+    python tools/egress_probe.py --cloud [--runs 12]
+The compact-cloud A/B, both sides on this tree, on the same device video and with the same gates: A = forward(..., output=spec with points), then
+pts[valid] in torch on the device and that tensor's copy to the host; B = forward(..., output=spec with cloud) -- ppms_cloud_egress's two launches
+behind the planes' one --, the counts' copy to the host and then count records per frame.  The two compact clouds are compared bit for bit, and
+the valid fraction of the pixels is printed with the times: the bytes B saves are that fraction's complement, the times are what this run
+measured on this video and nothing more."""
 import argparse
 import os
 import statistics
@@ -20,7 +26,7 @@ import sys
 import time
 
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LAUNCHES = ("ppms_convex_upsample", "ppms_convex_upsample_3d", "ppms_bilinear", "ppms_disparity_egress", "ppms_scene_egress")
+LAUNCHES = ("ppms_convex_upsample", "ppms_convex_upsample_3d", "ppms_bilinear", "ppms_disparity_egress", "ppms_scene_egress", "ppms_cloud_egress")
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ worker
@@ -53,6 +59,23 @@ def worker(tree: str, side: str):
                 state["call"] = lambda: {"points": m.forward(i1, i2, iters=iters, test_mode=True, output=spec)["points"].cpu()}
             else:
                 state["call"] = lambda: {"points": spec.reference(*m.forward(i1, i2, iters=iters, test_mode=True))["points"].cpu()}
+        if side.startswith("cloud"):                     # (the compact cloud under the key "points": one (records, 3) tensor, frame after frame)
+            gates = dict(uncertainty=None, Q=P.OutputSpec.q_matrix(721.5377, 0.54, W / 2, H / 2), max_uncertainty=0.5, max_depth=50.0)
+            i1, i2 = (state["video"][:, k][None].to(torch.uint8).to(dev) for k in (0, 1))
+            if side == "cloud":
+                spec = P.OutputSpec(cloud="f32", **gates)
+
+                def call():
+                    out = m.forward(i1, i2, iters=iters, test_mode=True, output=spec)
+                    counts = out["cloud_counts"][0].cpu().tolist()
+                    return {"points": torch.cat([out["cloud"][0, f, :c].cpu() for f, c in enumerate(counts)])}
+            else:
+                spec = P.OutputSpec(points="f32", **gates)
+
+                def call():
+                    pts = m.forward(i1, i2, iters=iters, test_mode=True, output=spec)["points"][0]
+                    return {"points": pts[~pts[..., 2].isnan()].cpu()}
+            state["call"] = call
         for _ in range(3):
             state["call"]()
         torch.cuda.synchronize()
@@ -146,13 +169,17 @@ def main():
     ap.add_argument("--runs", type=int, default=12)
     ap.add_argument("--windows", action="store_true", help="also T = 30 at kernel_size = 20: three windows through the ClipPipeline")
     ap.add_argument("--points", action="store_true", help="the point-cloud A/B instead: the reprojection in torch on the device against ppms_scene_egress")
+    ap.add_argument("--cloud", action="store_true", help="the compact-cloud A/B instead: organised points and pts[valid] in torch against ppms_cloud_egress")
     ap.add_argument("--worker", default=None)
     ap.add_argument("--tree", default=HERE)
     a = ap.parse_args()
     if a.worker:
         return worker(os.path.abspath(a.tree), a.worker)
     ptree = os.path.abspath(a.parent) if a.parent else HERE
-    if a.points:
+    if a.cloud:
+        A = Side('forward(output=OutputSpec(points="f32", Q=..., max_uncertainty=0.5, max_depth=50)), pts[valid] on the device -> host', HERE, "cloud_torch")
+        B = Side('forward(output=OutputSpec(cloud="f32", Q=..., max_uncertainty=0.5, max_depth=50)), counts -> host, count records per frame -> host', HERE, "cloud")
+    elif a.points:
         A = Side("forward(), then OutputSpec.reference in torch on the device, points -> host", HERE, "points_torch")
         B = Side('forward(output=OutputSpec(points="f32", Q=..., max_uncertainty=0.5, max_depth=50)), points -> host', HERE, "points")
     else:
@@ -166,7 +193,7 @@ def main():
             for _ in range(runs):
                 for s in (A, B):                                # alternate: one whole call each
                     ms[s].append(float(s.ask("run")[0]))
-            what = "forward(device uint8 video) -> host points" if a.points else "forward_batch_test(host video) -> host results"
+            what = "forward(device uint8 video) -> host points" if a.points or a.cloud else "forward_batch_test(host video) -> host results"
             print(f"== T = {T}, {H}x{W}, iters = {iters}, kernel_size = 20: {what}, {runs} alternating calls per side")
             for s in (A, B):
                 v = ms[s]
@@ -179,9 +206,12 @@ def main():
                 print(f"    behind the last convex upsampling: {n_dev} device launches / copies, {n_host} host torch ops  ({names})")
             ma, mb = statistics.median(ms[A]), statistics.median(ms[B])
             print(f"egress median / default median = {mb / ma:.4f} ({mb - ma:+.2f} ms)")
-            if a.points:
+            if a.points or a.cloud:
                 da, db = A.ask("digest")[0], B.ask("digest")[0]
                 print(f"points digest A {da}  B {db}: {'bit-identical' if da == db else 'DIFFERENT'}")
+            if a.cloud:
+                records = int(B.ask("shape")[0].split("[")[1].split(",")[0])
+                print(f"valid fraction: {records} of {T * H * W} pixels = {records / (T * H * W):.4f}")
             print()
         print("host: cpus", os.cpu_count(), "loadavg", os.getloadavg())
     finally:
