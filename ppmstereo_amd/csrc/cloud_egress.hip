@@ -1,4 +1,4 @@
-// Compact point-cloud egress (ppmstereo_amd/engine.py: disparity_egress with an L.Cloud, driven by video.py's OutputSpec(cloud=...)): the valid
+// Compact point-cloud egress (ppmstereo_amd/engine.py: disparity_egress with an L.Cloud, driven by output.py's OutputSpec(cloud=...)): the valid
 // points of ppms_scene_egress's organised points plane, in row-major pixel order, stored densely per frame, with their number and -- where asked --
 // their pixel indices (include/ppms.h: the definition).  Two launches on one grid, no atomics and no wait of one workgroup on another:
 //   count  every workgroup counts its valid pixels -> block_counts[frame][workgroup]
@@ -170,26 +170,18 @@ extern "C" int ppms_cloud_egress(const float* flow_up, const float* unc, int T, 
     PPMS_REQUIRE(c.components == 3 || c.components == 4, "%s: components = %d must be 3 or 4", who, c.components);
     PPMS_REQUIRE(c.reserved == 0, "%s: reserved = %d must be 0", who, c.reserved);
     PPMS_REQUIRE(c.capacity > 0 && c.capacity <= 0x7fffffff, "%s: capacity = %lld must be in 1 .. 2^31 - 1", who, (long long)c.capacity);
-    const int64_t esz = c.format == PPMS_FMT_F32 ? 4 : 2, rb = esz * c.components;
-    PPMS_REQUIRE(n_frames == 1 || c.frame_stride >= c.capacity * rb, "%s: frame_stride = %lld is less than capacity = %lld records of %lld bytes", who,
-                 (long long)c.frame_stride, (long long)c.capacity, (long long)rb);
-    PPMS_REQUIRE(((uintptr_t)c.records | (uintptr_t)c.frame_stride) % esz == 0, "%s: records and frame_stride must be multiples of the %lld-byte element",
-                 who, (long long)esz);
-    if (c.index) {
-        PPMS_REQUIRE(n_frames == 1 || c.index_frame_stride >= c.capacity * 4, "%s: index_frame_stride = %lld is less than capacity = %lld indices of 4 bytes",
-                     who, (long long)c.index_frame_stride, (long long)c.capacity);
-        PPMS_REQUIRE(((uintptr_t)c.index | (uintptr_t)c.index_frame_stride) % 4 == 0, "%s: index and index_frame_stride must be multiples of the 4-byte element", who);
-    }
+    // a frame of records, and of indices (int32: 4-byte elements, as PPMS_FMT_F32 has), is one dense row of `capacity` of them
+    if (const int rc = egress_check_strided(who, "records", "frame_stride", c.records, c.frame_stride, nullptr, c.format, n_frames, 1, c.capacity * c.components))
+        return rc;
+    if (c.index)
+        if (const int rc = egress_check_strided(who, "index", "index_frame_stride", c.index, c.index_frame_stride, nullptr, PPMS_FMT_F32, n_frames, 1, c.capacity))
+            return rc;
     PPMS_REQUIRE((uintptr_t)c.counts % 4 == 0 && (uintptr_t)c.block_counts % 4 == 0, "%s: counts and block_counts must be multiples of the 4-byte element", who);
     const int64_t blocks = cloud_blocks_per_frame(H0, W0);
     PPMS_REQUIRE(c.block_counts != nullptr && c.block_counts_len >= n_frames * blocks,
                  "%s: block_counts is null or block_counts_len = %lld is less than the %lld entries of ppms_cloud_egress_workspace", who,
                  (long long)c.block_counts_len, (long long)(n_frames * blocks));
-    for (int i = 0; i < 16; ++i) PPMS_REQUIRE(c.q[i] > -INFINITY && c.q[i] < INFINITY, "%s: q[%d] = %g is not finite", who, i, (double)c.q[i]);
-    PPMS_REQUIRE(c.min_disp > -INFINITY && c.min_disp < INFINITY, "%s: min_disp = %g must be finite", who, (double)c.min_disp);
-    PPMS_REQUIRE(c.max_uncertainty == c.max_uncertainty, "%s: max_uncertainty is NaN (+inf switches the gate off)", who);
-    PPMS_REQUIRE(c.max_depth > 0.0f, "%s: max_depth = %g must be positive (+inf switches the gate off)", who, (double)c.max_depth);
-    PPMS_REQUIRE(unc != nullptr || !(c.max_uncertainty < INFINITY || c.components == 4), "%s: null unc: the max_uncertainty gate and components = 4 read it", who);
+    if (const int rc = egress_check_reprojection(who, unc, c.q, c.min_disp, c.max_uncertainty, c.max_depth, true, true, c.components)) return rc;
     const int64_t runs = (int64_t)H0 * g.rpr;                            // runs of one frame
     const dim3 grid((unsigned)blocks, (unsigned)n_frames), wg(CLOUD_WG);
     hipStream_t s = (hipStream_t)stream;

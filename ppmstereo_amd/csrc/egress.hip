@@ -1,4 +1,4 @@
-// Output egress (ppmstereo_amd/engine.py: disparity_egress, driven by video.py's OutputSpec): the two one-launch-per-window kernels that
+// Output egress (ppmstereo_amd/engine.py: disparity_egress, driven by output.py's OutputSpec): the two one-launch-per-window kernels that
 // write the caller's disparity / depth / uncertainty planes and the point cloud, their stores, checks and entry points.  The thread mapping,
 // the loads and the geometry check are egress_shared.h's: cloud_egress.hip (the compacted cloud) is built from the same ones.
 #include "egress_shared.h"
@@ -212,23 +212,19 @@ static int egress_check(const char* who, const float* flow_up, const float* unc,
                  "%s: null flow_up / unc source of a requested plane", who);
     if (points)
         PPMS_REQUIRE(e->points_components == 3 || e->points_components == 4, "%s: points_components = %d must be 3 or 4", who, e->points_components);
-    const struct { const ppms_egress_plane* p; const char* name; unsigned formats; int comps; } planes[4] = {
-        {&o.disparity, "disparity", 1u << PPMS_FMT_F32 | 1u << PPMS_FMT_F16 | 1u << PPMS_FMT_U16, 1},
-        {&o.depth, "depth", 1u << PPMS_FMT_F32 | 1u << PPMS_FMT_F16 | 1u << PPMS_FMT_U16, 1},
-        {&o.uncertainty, "uncertainty", 1u << PPMS_FMT_F32 | 1u << PPMS_FMT_U8, 1},
-        {points ? &e->points : nullptr, "points", 1u << PPMS_FMT_F32 | 1u << PPMS_FMT_F16, points ? e->points_components : 0}};
+    const struct { const ppms_egress_plane* p; const char *name, *stride; unsigned formats; int comps; } planes[4] = {
+        {&o.disparity, "disparity", "disparity.frame_stride", 1u << PPMS_FMT_F32 | 1u << PPMS_FMT_F16 | 1u << PPMS_FMT_U16, 1},
+        {&o.depth, "depth", "depth.frame_stride", 1u << PPMS_FMT_F32 | 1u << PPMS_FMT_F16 | 1u << PPMS_FMT_U16, 1},
+        {&o.uncertainty, "uncertainty", "uncertainty.frame_stride", 1u << PPMS_FMT_F32 | 1u << PPMS_FMT_U8, 1},
+        {points ? &e->points : nullptr, "points", "points.frame_stride", 1u << PPMS_FMT_F32 | 1u << PPMS_FMT_F16, points ? e->points_components : 0}};
     for (const auto& pl : planes) {
         if (!pl.p || !pl.p->ptr) continue;                               // skipped
         const ppms_egress_plane& p = *pl.p;
         PPMS_REQUIRE(p.format >= 0 && p.format <= PPMS_FMT_U8 && (pl.formats >> p.format & 1u),
                      "%s: %s.format = %d is not a format of that plane", who, pl.name, p.format);
         PPMS_REQUIRE(p.reserved == 0, "%s: %s.reserved = %d must be 0", who, pl.name, p.reserved);
-        const int64_t esz = p.format == PPMS_FMT_F32 ? 4 : (p.format == PPMS_FMT_U8 ? 1 : 2), rowb = esz * W0 * pl.comps;
-        PPMS_REQUIRE(p.pitch >= rowb, "%s: %s.pitch = %lld is less than a row's %lld bytes", who, pl.name, (long long)p.pitch, (long long)rowb);
-        PPMS_REQUIRE(n_frames == 1 || p.frame_stride >= (int64_t)(H0 - 1) * p.pitch + rowb,
-                     "%s: %s.frame_stride = %lld is less than a plane", who, pl.name, (long long)p.frame_stride);
-        PPMS_REQUIRE(((uintptr_t)p.ptr | (uintptr_t)p.pitch | (uintptr_t)p.frame_stride) % esz == 0,
-                     "%s: %s: pointer, pitch and frame_stride must be multiples of the %lld-byte element", who, pl.name, (long long)esz);
+        if (const int rc = egress_check_strided(who, pl.name, pl.stride, p.ptr, p.frame_stride, &p.pitch, p.format, n_frames, H0, (int64_t)W0 * pl.comps))
+            return rc;
     }
     if (o.depth.ptr) {
         PPMS_REQUIRE(o.fb > 0.0f && o.fb < INFINITY, "%s: a depth plane needs fb = %g > 0", who, (double)o.fb);
@@ -239,15 +235,9 @@ static int egress_check(const char* who, const float* flow_up, const float* unc,
         PPMS_REQUIRE(o.disp_scale > 0.0f && o.disp_scale < INFINITY, "%s: a u16 disparity needs disp_scale = %g > 0", who, (double)o.disp_scale);
     if (e) {
         PPMS_REQUIRE(e->reserved == 0, "%s: reserved = %d must be 0", who, e->reserved);
-        PPMS_REQUIRE(e->max_uncertainty == e->max_uncertainty, "%s: max_uncertainty is NaN (+inf switches the gate off)", who);
-        PPMS_REQUIRE(e->max_depth > 0.0f, "%s: max_depth = %g must be positive (+inf switches the gate off)", who, (double)e->max_depth);
-        if (points) {
-            for (int i = 0; i < 16; ++i)
-                PPMS_REQUIRE(e->q[i] > -INFINITY && e->q[i] < INFINITY, "%s: q[%d] = %g is not finite", who, i, (double)e->q[i]);
-            PPMS_REQUIRE(o.min_disp > -INFINITY && o.min_disp < INFINITY, "%s: points need a finite min_disp, got %g", who, (double)o.min_disp);
-        }
-        const bool reads_u = ((o.depth.ptr || points) && e->max_uncertainty < INFINITY) || (points && e->points_components == 4);
-        PPMS_REQUIRE(!reads_u || unc != nullptr, "%s: null unc: the max_uncertainty gate and points_components = 4 read it", who);
+        if (const int rc = egress_check_reprojection(who, unc, e->q, o.min_disp, e->max_uncertainty, e->max_depth, points, o.depth.ptr || points,
+                                                     e->points_components))
+            return rc;
     }
     return PPMS_OK;
 }

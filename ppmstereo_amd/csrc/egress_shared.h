@@ -1,6 +1,6 @@
 // What the egress sources (egress.hip: the planes and the organised points; cloud_egress.hip: the compacted cloud) share: the thread mapping,
-// the loads of the engine's state, and the check of the geometry and the frame range.  Device pieces are restated nowhere else: a pixel's
-// d and u are the same bits whichever launch reads them.
+// the loads of the engine's state, and the host checks of the geometry and the frame range, of the reprojection's arguments and of a strided
+// destination.  Device pieces are restated nowhere else: a pixel's d and u are the same bits whichever launch reads them.
 #pragma once
 #include "common.h"
 
@@ -72,5 +72,33 @@ static inline int egress_check_geometry(const char* who, int T, int H, int W, in
     g->total = (int64_t)n_frames * H0 * g->rpr;
     PPMS_REQUIRE((g->total + 255) / 256 <= 0x7fffffff, "%s: %lld threads exceed one grid", who, (long long)g->total);
     g->sh = (float)(H / 4) / (float)H, g->sw = (float)(W / 4) / (float)W;            // ppms_bilinear's scales for (H/4, W/4) -> (H, W): 0.25
+    return PPMS_OK;
+}
+// ---- host: the reprojection's arguments, as ppms_scene_egress and ppms_cloud_egress refuse them.  The gates' values always; q and min_disp
+// where records are made (`records`: points or a cloud, of `components` each); unc where a gate that something obeys (`gated`: a depth plane or
+// records) or a fourth component reads it.
+static inline int egress_check_reprojection(const char* who, const float* unc, const float (&q)[16], float min_disp, float max_uncertainty,
+                                            float max_depth, bool records, bool gated, int components) {
+    PPMS_REQUIRE(max_uncertainty == max_uncertainty, "%s: max_uncertainty is NaN (+inf switches the gate off)", who);
+    PPMS_REQUIRE(max_depth > 0.0f, "%s: max_depth = %g must be positive (+inf switches the gate off)", who, (double)max_depth);
+    if (records) {
+        for (int i = 0; i < 16; ++i) PPMS_REQUIRE(q[i] > -INFINITY && q[i] < INFINITY, "%s: q[%d] = %g is not finite", who, i, (double)q[i]);
+        PPMS_REQUIRE(min_disp > -INFINITY && min_disp < INFINITY, "%s: the reprojection needs a finite min_disp, got %g", who, (double)min_disp);
+    }
+    const bool reads_u = (gated && max_uncertainty < INFINITY) || (records && components == 4);
+    PPMS_REQUIRE(!reads_u || unc != nullptr, "%s: null unc: the max_uncertainty gate and a fourth component read it", who);
+    return PPMS_OK;
+}
+// ---- host: a strided destination `name`: n_frames frames frame_stride bytes apart, each `rows` rows *pitch bytes apart of row_elems elements
+// of `format` (PPMS_FMT_F32: 4 bytes, PPMS_FMT_U8: 1, otherwise 2).  pitch == nullptr: a frame is one dense row (the cloud's records and
+// indices).  stride_name: what the caller's struct calls frame_stride.
+static inline int egress_check_strided(const char* who, const char* name, const char* stride_name, const void* ptr, int64_t frame_stride,
+                                       const int64_t* pitch, int format, int n_frames, int64_t rows, int64_t row_elems) {
+    const int64_t esz = format == PPMS_FMT_F32 ? 4 : (format == PPMS_FMT_U8 ? 1 : 2), rowb = esz * row_elems, step = pitch ? *pitch : rowb;
+    PPMS_REQUIRE(step >= rowb, "%s: %s.pitch = %lld is less than a row's %lld bytes", who, name, (long long)step, (long long)rowb);
+    PPMS_REQUIRE(n_frames == 1 || frame_stride >= (rows - 1) * step + rowb, "%s: %s = %lld is less than a frame's %lld bytes", who, stride_name,
+                 (long long)frame_stride, (long long)((rows - 1) * step + rowb));
+    PPMS_REQUIRE(((uintptr_t)ptr | (uintptr_t)step | (uintptr_t)frame_stride) % esz == 0,
+                 "%s: %s: pointer, pitch and %s must be multiples of the %lld-byte element", who, name, stride_name, (long long)esz);
     return PPMS_OK;
 }

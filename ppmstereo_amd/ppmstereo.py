@@ -19,10 +19,11 @@ from . import _lib as L
 from .corr import CorrBlock1D
 from .engine import bilinear
 from .update import Attention_qk, SequenceUpdateBlock3D
-from .video import (InputPadder, OutputSpec, RawFrames, RawStereoVideo, RectifyMap, StereoRectifier, YUVFrames, YUVStereoVideo, byte_lut,  # noqa: F401  (the public names are
-                    egress_plan, level_lut, shard_windows, window_plan, yuv_matrix)                                                    #  importable from here as before)
+from .output import OutputSpec, _EgressCall, egress_plan  # noqa: F401  (the public names are importable from here as before)
+from .video import (InputPadder, RawFrames, RawStereoVideo, RectifyMap, StereoRectifier, YUVFrames, YUVStereoVideo, byte_lut,  # noqa: F401
+                    level_lut, shard_windows, window_plan, yuv_matrix)
 from .video import PackedRawFrames, PackedRawStereoVideo, PackedYUVFrames, PackedYUVStereoVideo  # noqa: F401
-from .video import _ByteSource, _EgressCall, stereo_source
+from .video import _ByteSource, stereo_source
 
 
 def interp(x: torch.Tensor, size) -> torch.Tensor:

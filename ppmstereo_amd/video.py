@@ -1,10 +1,9 @@
-"""Video in and out of the model: what ``PPMStereo.forward`` / ``forward_batch_test`` accept beside the reference's float tensors (uint8 and decoded
+"""Video into the model: what ``PPMStereo.forward`` / ``forward_batch_test`` accept beside the reference's float tensors (uint8 and decoded
 YUV frames of 8, 10 or 12 bits with 4:2:0 / 4:2:2 / 4:4:4 chroma, a sensor's Bayer-mosaic or monochrome frames, both in the packed formats cameras put
 on the wire (YUYV, Y210, v210, RAW10p / RAW12p), unrectified frames with a ``StereoRectifier``), the one private family of sources that stands for all of them behind the front doors
-(``stereo_source``), the output planes they can hand back (``OutputSpec``) and the sliding-window schedule.  Nothing here knows the model."""
+(``stereo_source``) and the sliding-window schedule.  Nothing here knows the model.  (What the doors hand back: output.py.)"""
 from __future__ import annotations
 
-import math
 from typing import Dict, Optional
 
 import torch
@@ -1189,278 +1188,6 @@ def stereo_source(who: str, left, right=None, rectify: Optional[StereoRectifier]
     return _RGBBytes(left.contiguous().flatten(0, 1), right.contiguous().flatten(0, 1), 3 * h * w, rectify, left.shape[0])
 
 
-_PLANE_FORMATS = {"f32": (L.FMT_F32, torch.float32), "f16": (L.FMT_F16, torch.float16), "u16": (L.FMT_U16, torch.uint16), "u8": (L.FMT_U8, torch.uint8),
-                  "i32": (None, torch.int32)}      # (i32: the compact cloud's counts and pixel indices, no format of a plane)
-
-
-class OutputSpec:
-    """What ``forward(output=...)`` / ``forward_batch_test(output=...)`` hand back instead of float32 disparity: up to three planes that ONE
-    kernel (ppms_disparity_egress, include/ppms.h) writes from the 1/4 scale's last iteration -- crop, kept frames, ``.abs()``, the 4x
-    upsampling of the uncertainty and the conversion in one pass.
-      disparity    "f32" | "f16" | "u16": d = |disparity| in pixels; "u16" = min(65535, rint(d * disp_scale)) (KITTI: disp_scale = 256), NaN -> 0
-      depth        None | "f32" | "f16" | "u16": Z = fb / d with fb = focal_px * baseline (one fp32 product); "u16" = min(65535, rint(Z * depth_scale))
-                   (baseline in metres and depth_scale = 1000: millimetres).  A pixel with d < min_disp or d = NaN is invalid: +inf in the float
-                   formats, 0 in "u16".  (min_disp = 0 leaves only NaN invalid: d = 0 then gives +inf / 65535.)
-      uncertainty  "f32" | "u8" | None: u = |uncertainty| in [0, 1]; "u8" = min(255, rint(u * 255)), NaN -> 0
-    Every step is one fp32 operation rounded to nearest even; ``reference`` restates them in torch and is the definition the kernel is
-    tested against, bit for bit.
-    Keyword only, all off by default (a spec that uses none of them makes the launch above, the same bits):
-      points           None | "f32" | "f16": an organised point cloud, one record per pixel of the cropped frame, result key "points" with the
-                       shape (n, h0, w0, C) -- ``cv2.reprojectImageTo3D(d, Q)`` and the validity mask behind it, in the same launch
-                       (ppms_scene_egress).  With x, y the pixel's column and row in the cropped plane (the image the caller fed in):
-                       v_i = ((Q[i][0] * x + Q[i][1] * y) + Q[i][2] * d) + Q[i][3], X, Y, Z = v_0 / v_3, v_1 / v_3, v_2 / v_3.  "f16" is the
-                       rounding to nearest even of the fp32 value (overflow: inf).
-      points_layout    "xyz": C = 3 (12-byte records in f32).  "xyzw": C = 4, w = u, the upsampled |uncertainty| (16-byte records in f32, a float4).
-      Q                the 4x4 reprojection matrix of the rig's calibration: anything ``torch.as_tensor`` takes with 16 elements, rounded once to
-                       fp32, every entry finite.  Required with points.  ``q_matrix`` builds the one ``cv2.stereoRectify`` documents.
-      max_uncertainty  None | float: a point / depth pixel with u > max_uncertainty (or u = NaN) is invalid.
-      max_depth        None | float > 0: a point with Z <= 0 or Z > max_depth (or NaN), a depth pixel with fb / d > max_depth is invalid.
-                       (For both gates +inf means None.)
-    An invalid point carries NaN in X, Y and Z (a pixel with d < min_disp or d = NaN is one, as for depth); w is written for valid and invalid points
-    alike; an invalid depth pixel is +inf (0 in "u16") as above.  The gates never touch the disparity and uncertainty planes.
-      cloud            None | "f32" | "f16": the compact (unorganised) cloud -- per frame only the VALID points of the organised cloud that
-                       ``points=cloud, points_layout=cloud_layout`` would give, the same bits, in row-major pixel order, stored densely from
-                       record 0: what ``pts[~pts[..., 2].isnan()]`` makes of it.  Result keys "cloud" and "cloud_counts" (the number of valid
-                       points per frame).  Two more launches behind the planes' launch (ppms_cloud_egress: count, place; no atomics, the order
-                       is the same in every run); the planes' launch and its bits are what they are without ``cloud``.  Needs Q and a finite
-                       min_disp, as points do; it may stand beside any plane and beside points (whose format and layout may differ).
-      cloud_layout     "xyz" | "xyzw", as points_layout.
-      cloud_index      True: result key "cloud_index", int32 y * w0 + x of every record, to gather colour or another per-pixel attribute with.
-      cloud_capacity   None | int >= 1: records kept per frame.  None: h0 * w0, which can never truncate.  A frame with more valid points keeps
-                       its first ``cloud_capacity`` (records and indices); "cloud_counts" still reports the full number, so the truncation shows."""
-
-    def __init__(self, disparity: str = "f32", depth: Optional[str] = None, uncertainty: Optional[str] = "f32", disp_scale: float = 256.0,
-                 focal_px: Optional[float] = None, baseline: Optional[float] = None, depth_scale: float = 1000.0, min_disp: float = 2.0 ** -8,
-                 *, points: Optional[str] = None, points_layout: str = "xyz", Q=None, max_uncertainty: Optional[float] = None,
-                 max_depth: Optional[float] = None, cloud: Optional[str] = None, cloud_layout: str = "xyz", cloud_index: bool = False,
-                 cloud_capacity: Optional[int] = None):
-        if disparity not in ("f32", "f16", "u16"):
-            raise ValueError(f"OutputSpec: disparity = {disparity!r}; one of 'f32', 'f16', 'u16'")
-        if depth not in (None, "f32", "f16", "u16"):
-            raise ValueError(f"OutputSpec: depth = {depth!r}; None or one of 'f32', 'f16', 'u16'")
-        if uncertainty not in (None, "f32", "u8"):
-            raise ValueError(f"OutputSpec: uncertainty = {uncertainty!r}; None, 'f32' or 'u8'")
-        f32 = lambda x: float(torch.tensor(float(x), dtype=torch.float32))
-        self.disparity, self.depth, self.uncertainty = disparity, depth, uncertainty
-        self.disp_scale, self.depth_scale, self.min_disp = f32(disp_scale), f32(depth_scale), f32(min_disp)
-        if not (0.0 < self.disp_scale < math.inf):
-            raise ValueError(f"OutputSpec: disp_scale = {disp_scale} must be positive and finite")
-        self.focal_px, self.baseline, self.fb = focal_px, baseline, 0.0
-        if depth is not None:
-            if focal_px is None or baseline is None:
-                raise ValueError("OutputSpec: a depth plane needs focal_px (focal length in pixels) and baseline")
-            self.fb = float(torch.tensor(float(focal_px), dtype=torch.float32) * torch.tensor(float(baseline), dtype=torch.float32))
-            if not (0.0 < self.fb < math.inf):
-                raise ValueError(f"OutputSpec: focal_px * baseline = {self.fb} must be positive and finite")
-            if not (0.0 < self.depth_scale < math.inf):
-                raise ValueError(f"OutputSpec: depth_scale = {depth_scale} must be positive and finite")
-            if not math.isfinite(self.min_disp):
-                raise ValueError(f"OutputSpec: min_disp = {min_disp} must be finite")
-        if points not in (None, "f32", "f16"):
-            raise ValueError(f"OutputSpec: points = {points!r}; None, 'f32' or 'f16'")
-        if points_layout not in ("xyz", "xyzw"):
-            raise ValueError(f"OutputSpec: points_layout = {points_layout!r}; 'xyz' or 'xyzw'")
-        self.points, self.points_layout, self.Q = points, points_layout, None
-        if Q is not None:
-            q = torch.as_tensor(Q).detach().to("cpu", torch.float32)                            # rounded once to fp32
-            if q.numel() != 16 or not torch.isfinite(q).all():
-                raise ValueError(f"OutputSpec: Q must have 16 finite elements (a 4x4 reprojection matrix), got {tuple(q.shape)}: {q.flatten().tolist()}")
-            self.Q = q.reshape(4, 4).clone()
-        if points is not None and self.Q is None:
-            raise ValueError("OutputSpec: points need Q, the 4x4 reprojection matrix of the rig's calibration (OutputSpec.q_matrix builds one)")
-        if points is not None and not math.isfinite(self.min_disp):
-            raise ValueError(f"OutputSpec: min_disp = {min_disp} must be finite")
-        if cloud not in (None, "f32", "f16"):
-            raise ValueError(f"OutputSpec: cloud = {cloud!r}; None, 'f32' or 'f16'")
-        if cloud_layout not in ("xyz", "xyzw"):
-            raise ValueError(f"OutputSpec: cloud_layout = {cloud_layout!r}; 'xyz' or 'xyzw'")
-        if not isinstance(cloud_index, bool):
-            raise ValueError(f"OutputSpec: cloud_index = {cloud_index!r}; True or False")
-        if cloud_capacity is not None and (isinstance(cloud_capacity, bool) or not isinstance(cloud_capacity, int) or not 1 <= cloud_capacity < 2 ** 31):
-            raise ValueError(f"OutputSpec: cloud_capacity = {cloud_capacity!r}; None or an int in 1 .. 2^31 - 1")
-        if cloud is None and (cloud_layout != "xyz" or cloud_index or cloud_capacity is not None):
-            raise ValueError("OutputSpec: cloud_layout, cloud_index and cloud_capacity describe the cloud; without cloud= they have no meaning")
-        if cloud is not None and self.Q is None:
-            raise ValueError("OutputSpec: a cloud needs Q, the 4x4 reprojection matrix of the rig's calibration (OutputSpec.q_matrix builds one)")
-        if cloud is not None and not math.isfinite(self.min_disp):
-            raise ValueError(f"OutputSpec: min_disp = {min_disp} must be finite")
-        self.cloud, self.cloud_layout, self.cloud_index, self.cloud_capacity = cloud, cloud_layout, cloud_index, cloud_capacity
-        gate_u, gate_z = (None if g is None else f32(g) for g in (max_uncertainty, max_depth))
-        if gate_u is not None and math.isnan(gate_u):
-            raise ValueError("OutputSpec: max_uncertainty is NaN")
-        if gate_z is not None and not gate_z > 0.0:
-            raise ValueError(f"OutputSpec: max_depth = {max_depth} must be positive")
-        self.max_uncertainty, self.max_depth = (None if g == math.inf else g for g in (gate_u, gate_z))          # +inf: the gate is off
-
-    @staticmethod
-    def q_matrix(focal_px: float, baseline: float, cx: float, cy: float, cx_right: Optional[float] = None) -> torch.Tensor:
-        """The 4x4 float64 matrix ``cv2.stereoRectify`` documents as Q, for the left camera and a POSITIVE disparity (this package's d = |flow|):
-        rows [1, 0, 0, -cx], [0, 1, 0, -cy], [0, 0, 0, f], [0, 0, 1 / B, (cx_right - cx) / B]; cx_right = None: cx.  With it Z = f B / (d + cx_right - cx)
-        in the baseline's unit.  A layout claim restated from OpenCV's documentation: nothing in this package is compared with OpenCV (OpenCV's own
-        Q carries -1 / Tx with the sign of its translation; check the sign of Z on a rig before relying on it)."""
-        f, b, cx, cy = (float(v) for v in (focal_px, baseline, cx, cy))
-        if not (b != 0.0 and math.isfinite(b)):
-            raise ValueError(f"OutputSpec.q_matrix: baseline = {baseline} must be finite and not 0")
-        cxr = cx if cx_right is None else float(cx_right)
-        return torch.tensor([[1.0, 0.0, 0.0, -cx], [0.0, 1.0, 0.0, -cy], [0.0, 0.0, 0.0, f], [0.0, 0.0, 1.0 / b, (cxr - cx) / b]], dtype=torch.float64)
-
-    @property
-    def points_components(self) -> int:
-        return 4 if self.points_layout == "xyzw" else 3
-
-    @property
-    def scene(self) -> bool:
-        """The spec asks for points or a gate: its launch is ppms_scene_egress (otherwise ppms_disparity_egress, as ever)."""
-        return self.points is not None or self.max_uncertainty is not None or self.max_depth is not None
-
-    @property
-    def cloud_components(self) -> int:
-        return 4 if self.cloud_layout == "xyzw" else 3
-
-    def formats(self) -> Dict[str, str]:
-        """{result key: format} of the requested planes, in the order disparity, depth, uncertainties, points, and of the compact cloud's arrays:
-        cloud, cloud_counts, cloud_index."""
-        cloud = self.cloud is not None
-        named = (("disparity", self.disparity), ("depth", self.depth), ("uncertainties", self.uncertainty), ("points", self.points),
-                 ("cloud", self.cloud), ("cloud_counts", "i32" if cloud else None), ("cloud_index", "i32" if cloud and self.cloud_index else None))
-        return {k: f for k, f in named if f is not None}
-
-    def empty(self, n: int, h0: int, w0: int, device, pin_memory: bool = False) -> Dict[str, torch.Tensor]:
-        """Dense (n, 1, h0, w0) tensors of the requested planes' dtypes; "points": (n, h0, w0, C); "cloud": (n, capacity, C), "cloud_counts": (n,)
-        and "cloud_index": (n, capacity) int32, capacity = cloud_capacity or h0 * w0."""
-        cap = h0 * w0 if self.cloud_capacity is None else self.cloud_capacity
-        special = {"points": (n, h0, w0, self.points_components), "cloud": (n, cap, self.cloud_components), "cloud_counts": (n,), "cloud_index": (n, cap)}
-        return {k: torch.empty(special.get(k, (n, 1, h0, w0)), dtype=_PLANE_FORMATS[f][1], device=device, pin_memory=pin_memory)
-                for k, f in self.formats().items()}
-
-    def struct(self, planes: Dict[str, torch.Tensor]) -> L.Egress:
-        """The ``ppms_egress`` that writes into ``planes`` (dense (n, 1, h0, w0) device tensors from ``empty``)."""
-        def plane(key):
-            t = planes.get(key)
-            if t is None:
-                return L.EgressPlane(None, 0, 0, 0, 0)
-            es = t.element_size()
-            return L.EgressPlane(t.data_ptr(), t.stride(0) * es, t.stride(2) * es, _PLANE_FORMATS[self.formats()[key]][0], 0)
-        return L.Egress(plane("disparity"), plane("depth"), plane("uncertainties"), self.disp_scale, self.fb, self.depth_scale, self.min_disp)
-
-    def scene_struct(self, planes: Dict[str, torch.Tensor]) -> L.Egress3D:
-        """The ``ppms_egress3d`` that writes into ``planes`` (from ``empty``): ``struct``'s planes and constants, the (n, h0, w0, C) points, Q and
-        the gates (None: +inf, off)."""
-        t = planes.get("points")
-        if t is None:
-            points = L.EgressPlane(None, 0, 0, 0, 0)
-        else:
-            es = t.element_size()
-            points = L.EgressPlane(t.data_ptr(), t.stride(0) * es, t.stride(1) * es, _PLANE_FORMATS[self.points][0], 0)
-        q = (L.c_float * 16)(*(self.Q.flatten().tolist() if self.Q is not None else [0.0] * 16))
-        off = lambda g: math.inf if g is None else g
-        return L.Egress3D(self.struct(planes), points, q, off(self.max_uncertainty), off(self.max_depth), self.points_components, 0)
-
-    def cloud_struct(self, planes: Dict[str, torch.Tensor], workspace: Optional[torch.Tensor] = None) -> L.Cloud:
-        """The ``ppms_cloud`` that writes into ``planes`` (from ``empty``): the (n, capacity, C) records "cloud", the (n,) "cloud_counts", the
-        (n, capacity) "cloud_index" when there, Q, min_disp and the gates (None: +inf, off).  workspace: int32 device tensor of
-        ppms_cloud_egress_workspace entries.  ``planes`` without "cloud": a struct with null destinations (Q, gates and format as the spec has them)."""
-        t, cnt, idx = planes.get("cloud"), planes.get("cloud_counts"), planes.get("cloud_index")
-        q = (L.c_float * 16)(*(self.Q.flatten().tolist() if self.Q is not None else [0.0] * 16))
-        off = lambda g: math.inf if g is None else g
-        ptr = lambda x: None if x is None else x.data_ptr()
-        return L.Cloud(ptr(t), 0 if t is None else t.stride(0) * t.element_size(), 0 if t is None else t.shape[1], ptr(idx),
-                       0 if idx is None else idx.stride(0) * 4, ptr(cnt), ptr(workspace), 0 if workspace is None else workspace.numel(), q,
-                       self.min_disp, off(self.max_uncertainty), off(self.max_depth), _PLANE_FORMATS[self.cloud or "f32"][0], self.cloud_components, 0)
-
-    def reference(self, d: torch.Tensor, u: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
-        """The arithmetic of ppms_disparity_egress / ppms_scene_egress in plain torch, on CPU or device tensors of any shape: d = a float32 (signed)
-        disparity, u = a float32 uncertainty at the same resolution -> the requested planes under forward_batch_test's keys.  With points, d has at
-        least two dimensions and its last two are the pixel grid (row y, column x of the cropped plane); "points" has d's shape with the components
-        appended -- and, for a d of four or more dimensions whose third last is 1 (the planes' (..., 1, h, w)), without that 1: (..., h, w, C).
-        u is needed for an uncertainty plane, a max_uncertainty gate and the "xyzw" layout.
-        With cloud, every dimension in front of the pixel grid counts frames, N in all, and three keys are made of the organised points P and their
-        validity in the cloud's format and layout: "cloud", a list of N (count, C) tensors P[f][valid[f]]; "cloud_index", a list of N (count,) int32
-        y * w0 + x, increasing; "cloud_counts", (N,) int64 -- the whole cloud, whatever cloud_capacity: the definition ppms_cloud_egress is tested
-        against."""
-        const = lambda x: torch.full((), x, dtype=torch.float32, device=d.device)
-
-        def quant(v, scale, top, fmt):                       # min(top, rint(v * scale)), NaN -> 0: one fp32 product, ties to even
-            r = torch.round(v * const(scale))
-            r = torch.where(torch.isnan(r), torch.zeros_like(r), r).clamp(max=top)
-            return r.to(torch.int32).to(_PLANE_FORMATS[fmt][1])
-
-        gated = self.depth is not None or self.points is not None or self.cloud is not None
-        if u is None and (self.uncertainty is not None or (gated and self.max_uncertainty is not None) or (self.points and self.points_layout == "xyzw")
-                          or (self.cloud and self.cloud_layout == "xyzw")):
-            raise ValueError("OutputSpec.reference: an uncertainty plane, a max_uncertainty gate or the 'xyzw' layout is requested and no uncertainty was given")
-        d = d.float().abs()
-        if u is not None:
-            u = u.float().abs()
-        out = {"disparity": d if self.disparity == "f32" else d.to(torch.float16) if self.disparity == "f16" else quant(d, self.disp_scale, 65535.0, "u16")}
-        if gated:
-            ok = d >= const(self.min_disp)                   # (false for NaN)
-            if self.max_uncertainty is not None:
-                ok = ok & (u <= const(self.max_uncertainty))                     # (false for NaN)
-        if self.depth is not None:
-            z = const(self.fb) / d                           # tensor / tensor: a correctly rounded fp32 division
-            valid = ok if self.max_depth is None else ok & (z <= const(self.max_depth))
-            z = torch.where(valid, z, const(math.inf))
-            if self.depth == "u16":
-                out["depth"] = torch.where(valid, quant(z, self.depth_scale, 65535.0, "u16").to(torch.int32), 0).to(torch.uint16)
-            else:
-                out["depth"] = z if self.depth == "f32" else z.to(torch.float16)
-        if self.uncertainty is not None:
-            out["uncertainties"] = u if self.uncertainty == "f32" else quant(u, 255.0, 255.0, "u8")
-        if self.points is not None or self.cloud is not None:
-            if d.dim() < 2:
-                raise ValueError(f"OutputSpec.reference: points take the pixel grid from d's last two dimensions, got {tuple(d.shape)}")
-            x = torch.arange(d.shape[-1], dtype=torch.float32, device=d.device)
-            y = torch.arange(d.shape[-2], dtype=torch.float32, device=d.device)[:, None]
-            q = self.Q.to(d.device)
-            v = [((q[i, 0] * x + q[i, 1] * y) + q[i, 2] * d) + q[i, 3] for i in range(4)]       # one fp32 operation each, in this order
-            xyz = [v[i] / v[3] for i in range(3)]
-            valid = ok if self.max_depth is None else ok & (xyz[2] > 0) & (xyz[2] <= const(self.max_depth))
-
-            def organised(fmt, layout):                  # the organised cloud in one format and layout
-                comps = [torch.where(valid, c, const(math.nan)) for c in xyz] + ([u.expand_as(d)] if layout == "xyzw" else [])
-                pts = torch.stack(comps, dim=-1)
-                if d.dim() >= 4 and d.shape[-3] == 1:
-                    pts = pts.squeeze(-4)
-                return pts if fmt == "f32" else pts.to(torch.float16)
-
-            if self.points is not None:
-                out["points"] = organised(self.points, self.points_layout)
-            if self.cloud is not None:                   # per frame (every dimension in front of the pixel grid counts frames): the valid records
-                pts = organised(self.cloud, self.cloud_layout)
-                pts, keep = pts.reshape(-1, pts.shape[-3] * pts.shape[-2], pts.shape[-1]), valid.reshape(-1, d.shape[-2] * d.shape[-1])
-                out["cloud"] = [p[k] for p, k in zip(pts, keep)]
-                out["cloud_index"] = [k.nonzero().flatten().to(torch.int32) for k in keep]      # y * w0 + x, increasing
-                out["cloud_counts"] = keep.sum(dim=1)    # int64: the full numbers, whatever cloud_capacity
-        return out
-
-
-class _EgressCall:
-    """One egress launch as ``cascade`` makes it: the spec, the crop (pad_left, pad_top, H0, W0) inside the padded frame (None: the whole
-    frame) and the window-local frame range (None: all frames)."""
-
-    def __init__(self, spec: OutputSpec, crop=None, frames=None):
-        if not isinstance(spec, OutputSpec):
-            raise TypeError(f"output must be an OutputSpec, got {type(spec).__name__}")
-        self.spec, self.crop, self.frames = spec, (None if crop is None else tuple(int(x) for x in crop)), (None if frames is None else tuple(int(x) for x in frames))
-
-    def launch(self, eng) -> Dict[str, torch.Tensor]:
-        """Allocates the planes on the current stream and enqueues the launch there, behind the engine's last iteration.  A spec with a cloud adds
-        "cloud" (n, capacity, C), "cloud_counts" (n,) and "cloud_index" (n, capacity) when asked; rows of "cloud" and "cloud_index" past
-        min(count, capacity) of their frame are unspecified (never written)."""
-        pad_left, pad_top, h0, w0 = (0, 0, 4 * eng.h, 4 * eng.w) if self.crop is None else self.crop
-        f0, f1 = (0, eng.T) if self.frames is None else self.frames
-        if not 0 <= f0 < f1 <= eng.T:
-            raise ValueError(f"output: frames = {(f0, f1)} is no range inside the window's {eng.T} frames")
-        planes = self.spec.empty(f1 - f0, h0, w0, eng.FLOW_OUT.device)
-        out = self.spec.scene_struct(planes) if self.spec.scene else self.spec.struct(planes)      # ppms_scene_egress / ppms_disparity_egress
-        eng.egress(out, f0, f1 - f0, pad_left, pad_top, h0, w0)
-        if self.spec.cloud is not None:                          # ppms_cloud_egress: two more launches behind the planes' one, on the same stream
-            workspace = torch.empty(L.load().ppms_cloud_egress_workspace(f1 - f0, h0, w0), dtype=torch.int32, device=eng.FLOW_OUT.device)
-            eng.egress(self.spec.cloud_struct(planes, workspace), f0, f1 - f0, pad_left, pad_top, h0, w0)
-        return planes
-
-
 def window_plan(num_ims: int, kernel_size: int = 20):
     """Sliding-window schedule of PPMStereo.forward_batch_test (ppmstereo.py:242-310): list of
     (start, stop, keep_from, keep_to) with keep_* window-local.  Trailing windows whose output the reference
@@ -1476,12 +1203,6 @@ def window_plan(num_ims: int, kernel_size: int = 20):
         elif not plan:
             plan.append((i, i + n, 0, n + (-stride // 2)))
     return plan
-
-
-def egress_plan(plan):
-    """``window_plan`` with the destination of every window's kept frames: (start, stop, keep_from, keep_to, dst_from, dst_to) -- the egress
-    launch of the window writes its frames [keep_from, keep_to), and they are frames [dst_from, dst_to) of the video."""
-    return [(start, stop, keep_from, keep_to, start + keep_from, start + keep_to) for start, stop, keep_from, keep_to in plan]
 
 
 def shard_windows(plan, rank: int, world: int):

@@ -4,29 +4,13 @@ device; OutputSpec validates and its ``reference`` is the arithmetic include/ppm
 and edge values); egress_plan is the window-to-slice arithmetic of forward_batch_test(output=...).  No device compute."""
 import ctypes
 import math
-import os
-import re
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EINVAL = -1
+from egress_util import call_disparity, header_args, lib, refused  # noqa: F401  (lib: the fixture)
+
 NAME = "ppms_disparity_egress"
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from ppmstereo_amd import _lib as L
-    return L.load()
-
-
-def header_args(name=NAME):
-    src = open(os.path.join(ROOT, "include", "ppms.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\((.*?)\)\s*;", src, flags=re.S)
-    assert m, f"{name} is not declared in include/ppms.h"
-    return [" ".join(a.split()) for a in m.group(1).split(",")]
 
 
 def test_declared_exported_bound_and_abi_version_unchanged(lib):
@@ -35,7 +19,7 @@ def test_declared_exported_bound_and_abi_version_unchanged(lib):
         assert header_args(name)
         assert name in L.EXPORTS and hasattr(lib, name)
     assert lib.ppms_version() == 4
-    args = header_args()
+    args = header_args(NAME)
     assert args == ["const float* flow_up", "const float* unc", "int T", "int H", "int W", "int frame0", "int n_frames", "int pad_left", "int pad_top",
                     "int H0", "int W0", "const ppms_egress* out", "void* stream"]
     ctype = {"int": ctypes.c_int, "const float*": ctypes.c_void_p, "void*": ctypes.c_void_p, "const ppms_egress*": ctypes.POINTER(L.Egress)}
@@ -48,23 +32,7 @@ def test_declared_exported_bound_and_abi_version_unchanged(lib):
     assert (L.FMT_F32, L.FMT_F16, L.FMT_U16, L.FMT_U8) == (0, 1, 2, 3)
 
 
-# ---- argument refusal: frames [1, 3) of T = 3, the 37 x 50 crop at (13, 7) of 64 x 64, u16 / u16 / u8 planes with pitches wider than the row --
-def _call(lib, planes=("disparity", "depth", "uncertainty"), null_out=False, flow=0x100000, unc=0x200000, T=3, H=64, W=64, frame0=1, n_frames=2,
-          pad_left=7, pad_top=13, H0=37, W0=50, disp_scale=256.0, fb=500.0, depth_scale=1000.0, min_disp=0.25, **fields):
-    """Pointers into device memory are never dereferenced on the host: every check comes before the launch.  fields: "<plane>_<field>" = value."""
-    from ppmstereo_amd import _lib as L
-    default = {"disparity": dict(ptr=0x300000, frame_stride=37 * 102, pitch=102, format=L.FMT_U16, reserved=0),
-               "depth": dict(ptr=0x400000, frame_stride=37 * 106, pitch=106, format=L.FMT_U16, reserved=0),
-               "uncertainty": dict(ptr=0x500000, frame_stride=37 * 53, pitch=53, format=L.FMT_U8, reserved=0)}
-    for key, val in fields.items():
-        plane, field = key.split("_", 1)
-        default[plane][field] = val
-    pl = {k: L.EgressPlane(**{**v, "ptr": v["ptr"] or None}) if k in planes else L.EgressPlane(None, 0, 0, 0, 0) for k, v in default.items()}
-    out = L.Egress(pl["disparity"], pl["depth"], pl["uncertainty"], disp_scale, fb, depth_scale, min_disp)
-    return lib.ppms_disparity_egress(flow or None, unc or None, T, H, W, frame0, n_frames, pad_left, pad_top, H0, W0, None if null_out else ctypes.byref(out),
-                                     None)
-
-
+# ---- argument refusal: egress_util's call (frames [1, 3) of T = 3, the 37 x 50 crop at (13, 7) of 64 x 64, u16 / u16 / u8 planes) ----------------
 # (what the call's message must speak of, the one thing that is wrong with the call)
 BAD = [("no plane", dict(planes=())), ("null out", dict(null_out=True)),
        ("disparity.format", dict(disparity_format=4)), ("depth.format", dict(depth_format=-1)), ("uncertainty.format", dict(uncertainty_format=7)),
@@ -86,10 +54,7 @@ BAD = [("no plane", dict(planes=())), ("null out", dict(null_out=True)),
 
 @pytest.mark.parametrize("about,bad", BAD, ids=[",".join(f"{k}={v}" for k, v in b.items()) for _, b in BAD])
 def test_bad_arguments_return_einval_with_a_message_and_no_device(lib, about, bad):
-    lib.ppms_mem_attn_splits(3, 3, 256, 1)                      # (a successful call in between: the message below is this call's)
-    assert _call(lib, **bad) == EINVAL, bad
-    msg = lib.ppms_last_error()
-    assert msg and b"disparity_egress" in msg and about.encode() in msg, (bad, msg)
+    refused(lib, call_disparity, "disparity_egress", about, bad)
 
 
 # ---- OutputSpec ------------------------------------------------------------------------------------------------------------------------

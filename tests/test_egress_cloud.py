@@ -10,17 +10,10 @@ import re
 import pytest
 import torch
 
-from test_egress import EINVAL, ROOT, header_args
-from test_egress_points import IDENTITY, grid_inputs
+from egress_util import CAL_700, ROOT, _q, bad_ids, call_cloud, grid_inputs, header_args, lib, refused  # noqa: F401  (lib: the fixture)
 
 NAME = "ppms_cloud_egress"
 nan, inf = math.nan, math.inf
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from ppmstereo_amd import _lib as L
-    return L.load()
 
 
 def test_declared_exported_bound_and_struct_layout(lib):
@@ -56,22 +49,8 @@ def test_workspace_entries(lib):
     assert ws(1, 1, 1) == 1 and ws(0, 8, 8) == 0 and ws(1, 0, 8) == 0 and ws(1, 65536, 32768) == 0
 
 
-# ---- argument refusal: test_egress.py's geometry (frames [1, 3) of T = 3, the 37 x 50 crop at (13, 7) of 64 x 64), "xyz" f32 records with a
+# ---- argument refusal: egress_util's geometry (frames [1, 3) of T = 3, the 37 x 50 crop at (13, 7) of 64 x 64), "xyz" f32 records with a
 # ---- capacity of 1000 and a gap between the frames, an index, Q = identity and both gates on ---------------------------------------------------
-def _call(lib, null_out=False, flow=0x100000, unc=0x200000, T=3, H=64, W=64, frame0=1, n_frames=2, pad_left=7, pad_top=13, H0=37, W0=50,
-          records=0x300000, frame_stride=12008, capacity=1000, index=0x400000, index_frame_stride=4004, counts=0x500000, block_counts=0x600000,
-          block_counts_len=4, q=IDENTITY, min_disp=0.25, max_uncertainty=0.5, max_depth=80.0, format=0, components=3, reserved=0):
-    """Pointers into device memory are never dereferenced on the host: every check comes before the launch."""
-    from ppmstereo_amd import _lib as L
-    out = L.Cloud(records or None, frame_stride, capacity, index or None, index_frame_stride, counts or None, block_counts or None, block_counts_len,
-                  (ctypes.c_float * 16)(*q), min_disp, max_uncertainty, max_depth, format, components, reserved)
-    return lib.ppms_cloud_egress(flow or None, unc or None, T, H, W, frame0, n_frames, pad_left, pad_top, H0, W0, None if null_out else ctypes.byref(out), None)
-
-
-def _q(i, v):
-    return [v if j == i else x for j, x in enumerate(IDENTITY)]
-
-
 # (what the call's message must speak of, the one thing that is wrong with the call)
 BAD = [("null out", dict(null_out=True)), ("null records", dict(records=0)), ("null counts", dict(counts=0)), ("null flow_up", dict(flow=0)),
        ("block_counts", dict(block_counts=0)), ("block_counts_len", dict(block_counts_len=3)), ("block_counts_len", dict(block_counts_len=0)),
@@ -97,18 +76,12 @@ BAD = [("null out", dict(null_out=True)), ("null records", dict(records=0)), ("n
        ("positive", dict(T=0)), ("frame0", dict(frame0=2)), ("frame0", dict(frame0=-1)), ("n_frames", dict(n_frames=0))]
 
 
-@pytest.mark.parametrize("about,bad", BAD, ids=[about.replace(" ", "_") + ":" + ",".join(k if k == "q" else f"{k}={v}" for k, v in b.items()) for about, b in BAD])
+@pytest.mark.parametrize("about,bad", BAD, ids=bad_ids(BAD))
 def test_bad_arguments_return_einval_with_a_message_and_no_device(lib, about, bad):
-    lib.ppms_mem_attn_splits(3, 3, 256, 1)                      # (a successful call in between: the message below is this call's)
-    assert _call(lib, **bad) == EINVAL, bad
-    msg = lib.ppms_last_error()
-    assert msg and b"cloud_egress" in msg and about.encode() in msg, (bad, msg)
+    refused(lib, call_cloud, "cloud_egress", about, bad)
 
 
 # ---- OutputSpec ------------------------------------------------------------------------------------------------------------------------
-CAL = dict(focal_px=700.0, baseline=0.25)
-
-
 def test_output_spec_validation_of_the_new_options():
     from ppmstereo_amd import _lib as L
     from ppmstereo_amd.ppmstereo import OutputSpec
@@ -125,7 +98,7 @@ def test_output_spec_validation_of_the_new_options():
     with pytest.raises(TypeError):
         OutputSpec("f32", None, "f32", 256.0, None, None, 1000.0, 2.0 ** -8, None, "xyz", Q, None, None, "f32")      # the new options are keyword only
     s = OutputSpec(cloud="f16", cloud_layout="xyzw", cloud_index=True, cloud_capacity=20, Q=Q, max_uncertainty=0.1, max_depth=30.0, depth="u16",
-                   points="f32", **CAL)
+                   points="f32", **CAL_700)
     assert list(s.formats().items()) == [("disparity", "f32"), ("depth", "u16"), ("uncertainties", "f32"), ("points", "f32"), ("cloud", "f16"),
                                          ("cloud_counts", "i32"), ("cloud_index", "i32")]
     assert s.scene and (s.cloud_components, s.points_components) == (4, 3)
@@ -152,7 +125,7 @@ def test_output_spec_validation_of_the_new_options():
 def test_a_spec_without_the_new_options_is_as_before():
     from ppmstereo_amd.ppmstereo import OutputSpec
     Q = OutputSpec.q_matrix(700.0, 0.25, 19.5, 11.25)
-    kw = dict(disparity="u16", depth="u16", uncertainty="u8", points="f16", points_layout="xyzw", Q=Q, max_uncertainty=0.1, max_depth=30.0, **CAL)
+    kw = dict(disparity="u16", depth="u16", uncertainty="u8", points="f16", points_layout="xyzw", Q=Q, max_uncertainty=0.1, max_depth=30.0, **CAL_700)
     old, new = OutputSpec(**kw), OutputSpec(cloud="f32", cloud_index=True, **kw)
     assert (old.cloud, old.cloud_layout, old.cloud_index, old.cloud_capacity) == (None, "xyz", False, None)
     assert list(old.formats().items()) == [("disparity", "u16"), ("depth", "u16"), ("uncertainties", "u8"), ("points", "f16")]
@@ -168,6 +141,31 @@ def test_a_spec_without_the_new_options_is_as_before():
     bits = lambda t: t.view({2: torch.int16, 4: torch.int32}[t.element_size()]) if t.element_size() > 1 else t
     for k in a:
         assert a[k].dtype == b[k].dtype and torch.equal(bits(a[k]), bits(b[k])), k
+
+
+def test_one_spec_fills_the_three_structs():
+    """Every output at once: what ``struct``, ``scene_struct`` and ``cloud_struct`` make of one spec and its ``empty`` tensors -- layout arithmetic."""
+    from ppmstereo_amd import _lib as L
+    from ppmstereo_amd.ppmstereo import OutputSpec
+    Q = OutputSpec.q_matrix(700.0, 0.25, 2.5, 1.5)
+    spec = OutputSpec(disparity="u16", depth="f16", uncertainty="u8", focal_px=700.0, baseline=0.25, points="f16", points_layout="xyzw", Q=Q,
+                      max_uncertainty=0.5, cloud="f32", cloud_layout="xyz", cloud_index=True, cloud_capacity=7)
+    planes = spec.empty(2, 3, 5, "cpu")
+    assert {k: tuple(v.shape) for k, v in planes.items()} == {"disparity": (2, 1, 3, 5), "depth": (2, 1, 3, 5), "uncertainties": (2, 1, 3, 5),
+                                                             "points": (2, 3, 5, 4), "cloud": (2, 7, 3), "cloud_counts": (2,), "cloud_index": (2, 7)}
+    workspace = torch.empty(2, dtype=torch.int32)
+    st, cl = spec.scene_struct(planes), spec.cloud_struct(planes, workspace)
+    layout = lambda p: (p.frame_stride, p.pitch, p.format)
+    for plane, key, want in ((st.base.disparity, "disparity", (30, 10, L.FMT_U16)), (st.base.depth, "depth", (30, 10, L.FMT_F16)),
+                             (st.base.uncertainty, "uncertainties", (15, 5, L.FMT_U8)), (st.points, "points", (120, 40, L.FMT_F16))):
+        assert plane.ptr == planes[key].data_ptr() and layout(plane) == want and plane.reserved == 0, key
+    assert (st.points_components, st.reserved) == (4, 0)
+    assert bytes(spec.struct(planes)) == bytes(st.base)
+    assert (cl.records, cl.index, cl.counts, cl.block_counts) == tuple(t.data_ptr() for t in (planes["cloud"], planes["cloud_index"], planes["cloud_counts"], workspace))
+    assert (cl.frame_stride, cl.capacity, cl.index_frame_stride, cl.block_counts_len, cl.format, cl.components, cl.reserved) == (84, 7, 28, 2, L.FMT_F32, 3, 0)
+    for s in (st, cl):
+        assert list(s.q)[:4] == [1.0, 0.0, 0.0, -2.5] and list(s.q) == Q.float().flatten().tolist() and (s.max_uncertainty, s.max_depth) == (0.5, inf)
+    assert (st.base.fb, st.base.min_disp, cl.min_disp) == (175.0, 2.0 ** -8, 2.0 ** -8)
 
 
 # ---- reference ---------------------------------------------------------------------------------------------------------------------------

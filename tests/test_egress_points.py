@@ -8,15 +8,9 @@ import math
 import pytest
 import torch
 
-from test_egress import EINVAL, header_args
+from egress_util import CAL_700, _q, bad_ids, call_scene, grid_inputs, header_args, lib, refused  # noqa: F401  (lib: the fixture)
 
 NAME = "ppms_scene_egress"
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from ppmstereo_amd import _lib as L
-    return L.load()
 
 
 def test_declared_exported_bound_and_struct_layout(lib):
@@ -41,33 +35,8 @@ def test_declared_exported_bound_and_struct_layout(lib):
     assert [n for n, _ in L.Egress._fields_] == ["disparity", "depth", "uncertainty", "disp_scale", "fb", "depth_scale", "min_disp"]
 
 
-# ---- argument refusal: test_egress.py's call (frames [1, 3) of T = 3, the 37 x 50 crop at (13, 7) of 64 x 64, u16 / u16 / u8 planes) with an
+# ---- argument refusal: egress_util's call (frames [1, 3) of T = 3, the 37 x 50 crop at (13, 7) of 64 x 64, u16 / u16 / u8 planes) with an
 # ---- "xyz" f32 points plane whose pitch (604) is wider than the row's 600 bytes, Q = identity and both gates on --------------------------------
-IDENTITY = [1.0 if i % 5 == 0 else 0.0 for i in range(16)]
-
-
-def _call(lib, planes=("disparity", "depth", "uncertainty", "points"), null_out=False, flow=0x100000, unc=0x200000, T=3, H=64, W=64, frame0=1, n_frames=2,
-          pad_left=7, pad_top=13, H0=37, W0=50, disp_scale=256.0, fb=500.0, depth_scale=1000.0, min_disp=0.25, q=IDENTITY, max_uncertainty=0.5,
-          max_depth=80.0, comps=3, reserved=0, **fields):
-    """Pointers into device memory are never dereferenced on the host: every check comes before the launch.  fields: "<plane>_<field>" = value."""
-    from ppmstereo_amd import _lib as L
-    default = {"disparity": dict(ptr=0x300000, frame_stride=37 * 102, pitch=102, format=L.FMT_U16, reserved=0),
-               "depth": dict(ptr=0x400000, frame_stride=37 * 106, pitch=106, format=L.FMT_U16, reserved=0),
-               "uncertainty": dict(ptr=0x500000, frame_stride=37 * 53, pitch=53, format=L.FMT_U8, reserved=0),
-               "points": dict(ptr=0x600000, frame_stride=37 * 604, pitch=604, format=L.FMT_F32, reserved=0)}
-    for key, val in fields.items():
-        plane, field = key.split("_", 1)
-        default[plane][field] = val
-    pl = {k: L.EgressPlane(**{**v, "ptr": v["ptr"] or None}) if k in planes else L.EgressPlane(None, 0, 0, 0, 0) for k, v in default.items()}
-    base = L.Egress(pl["disparity"], pl["depth"], pl["uncertainty"], disp_scale, fb, depth_scale, min_disp)
-    out = L.Egress3D(base, pl["points"], (ctypes.c_float * 16)(*q), max_uncertainty, max_depth, comps, reserved)
-    return lib.ppms_scene_egress(flow or None, unc or None, T, H, W, frame0, n_frames, pad_left, pad_top, H0, W0, None if null_out else ctypes.byref(out), None)
-
-
-def _q(i, v):
-    return [v if j == i else x for j, x in enumerate(IDENTITY)]
-
-
 NO_UNC_PLANE = ("disparity", "depth", "points")
 nan, inf = math.nan, math.inf
 # (what the call's message must speak of, the one thing that is wrong with the call)
@@ -98,18 +67,12 @@ BAD = [("no plane", dict(planes=())), ("null out", dict(null_out=True)),
        ("disp_scale", dict(disp_scale=0.0)), ("null flow_up", dict(unc=0)), ("multiples of the 2-byte element", dict(depth_ptr=0x400001))]
 
 
-@pytest.mark.parametrize("about,bad", BAD, ids=[about.replace(" ", "_") + ":" + ",".join(k if k == "q" else f"{k}={v}" for k, v in b.items()) for about, b in BAD])
+@pytest.mark.parametrize("about,bad", BAD, ids=bad_ids(BAD))
 def test_bad_arguments_return_einval_with_a_message_and_no_device(lib, about, bad):
-    lib.ppms_mem_attn_splits(3, 3, 256, 1)                      # (a successful call in between: the message below is this call's)
-    assert _call(lib, **bad) == EINVAL, bad
-    msg = lib.ppms_last_error()
-    assert msg and b"scene_egress" in msg and about.encode() in msg, (bad, msg)
+    refused(lib, call_scene, "scene_egress", about, bad)
 
 
 # ---- OutputSpec ------------------------------------------------------------------------------------------------------------------------
-CAL = dict(focal_px=700.0, baseline=0.25)
-
-
 def test_output_spec_validation_of_the_new_options():
     from ppmstereo_amd.ppmstereo import OutputSpec
     Q = OutputSpec.q_matrix(700.0, 0.25, 19.5, 11.25)
@@ -125,7 +88,7 @@ def test_output_spec_validation_of_the_new_options():
             OutputSpec(**kw)
     with pytest.raises(TypeError):
         OutputSpec("f32", None, "f32", 256.0, None, None, 1000.0, 2.0 ** -8, "f32")            # the new options are keyword only
-    s = OutputSpec(points="f16", points_layout="xyzw", Q=Q.flatten().tolist(), max_uncertainty=0.1, max_depth=30.0, depth="u16", **CAL)
+    s = OutputSpec(points="f16", points_layout="xyzw", Q=Q.flatten().tolist(), max_uncertainty=0.1, max_depth=30.0, depth="u16", **CAL_700)
     assert list(s.formats().items()) == [("disparity", "f32"), ("depth", "u16"), ("uncertainties", "f32"), ("points", "f16")] and s.scene
     assert s.Q.dtype == torch.float32 and torch.equal(s.Q, Q.float()) and s.max_uncertainty == float(torch.tensor(0.1)) and s.max_depth == 30.0
     planes = s.empty(2, 5, 7, "cpu")
@@ -140,7 +103,7 @@ def test_output_spec_validation_of_the_new_options():
     st = xyz.scene_struct(xyz.empty(3, 4, 6, "cpu"))
     assert (st.points.frame_stride, st.points.pitch, st.points.format, st.points_components) == (4 * 6 * 12, 6 * 12, 0, 3)
     assert st.max_uncertainty == inf and st.max_depth == inf and st.base.uncertainty.ptr is None
-    gates = OutputSpec(depth="f32", max_depth=50.0, **CAL)                                     # a gate alone takes the new entry point too
+    gates = OutputSpec(depth="f32", max_depth=50.0, **CAL_700)                                     # a gate alone takes the new entry point too
     assert gates.scene and list(gates.formats()) == ["disparity", "depth", "uncertainties"] and gates.scene_struct(gates.empty(1, 4, 4, "cpu")).points.ptr is None
     assert OutputSpec(max_depth=inf, max_uncertainty=inf).scene is False                       # +inf is "off"
 
@@ -161,18 +124,6 @@ def test_a_spec_without_the_new_options_is_as_before():
     # and a spec WITH them hands ``struct`` the same planes and constants: ``scene_struct`` is built around it
     pts = OutputSpec(disparity="u16", depth="u16", uncertainty="u8", focal_px=721.5377, baseline=0.54, points="f32", Q=torch.eye(4))
     assert bytes(pts.struct(planes)) == bytes(st) == bytes(pts.scene_struct({**planes, "points": torch.empty(2, 5, 7, 3)}).base)
-
-
-def grid_inputs(H=24, W=40, seed=7, min_disp=0.5):
-    """(2, 1, H, W) disparities in (0, 100) with both signs, a tenth below min_disp, a twentieth NaN, some exact zeros; uncertainties in [0, 1)."""
-    g = torch.Generator().manual_seed(seed)
-    n = 2 * H * W
-    d = (torch.rand(n, generator=g) * 99.0 + 1.0) * torch.where(torch.rand(n, generator=g) < 0.5, -1.0, 1.0)
-    pick = torch.randperm(n, generator=g)
-    d[pick[:n // 10]] = torch.rand(n // 10, generator=g) * min_disp * 0.99
-    d[pick[n // 10:n // 10 + n // 20]] = nan
-    d[pick[n // 10 + n // 20:n // 10 + n // 20 + 8]] = 0.0
-    return d.reshape(2, 1, H, W), torch.rand(2, 1, H, W, generator=g)
 
 
 EPS = 4 * 2.0 ** -24

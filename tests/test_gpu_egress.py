@@ -2,111 +2,17 @@
 output and the sliced flow_up, and PPMStereo.forward / forward_batch_test with output= against the reference applied to the default call's
 float32 results.  Every comparison is exact: the kernel's steps are single fp32 operations rounded to nearest even, the reference's too
 (NaN compares equal to NaN at the same place; its payload is not part of the definition)."""
-import ctypes
-
 import pytest
 import torch
 
+from egress_util import FMT, KEYS, NO_PLANE, Dest, check, engine_state, expected, launch, model, model_refuses, planes_match, planes_struct, rand_u8, same, same_results  # noqa: F401  (model: the fixture)
 from ppmstereo_amd import _lib as L
-from ppmstereo_amd import weights as Wm
 from ppmstereo_amd.engine import bilinear
 from ppmstereo_amd.ppmstereo import OutputSpec
-from test_gpu_block import DEV, W
+from test_gpu_block import DEV
 
 pytestmark = pytest.mark.gpu
-FMT = {"f32": (L.FMT_F32, torch.float32, 4), "f16": (L.FMT_F16, torch.float16, 2), "u16": (L.FMT_U16, torch.uint16, 2), "u8": (L.FMT_U8, torch.uint8, 1)}
-KEYS = ("disparity", "depth", "uncertainties")
-
-
-def same(a, b):
-    """Equal dtype, shape and values; NaN equals NaN."""
-    if a.dtype != b.dtype or a.shape != b.shape or a.device != b.device:
-        return False
-    if a.dtype.is_floating_point:
-        a, b = (torch.where(x.isnan(), torch.full_like(x, -1.0), x) for x in (a, b))
-        return torch.equal(a, b)
-    return torch.equal(a.view(torch.int16) if a.dtype == torch.uint16 else a, b.view(torch.int16) if b.dtype == torch.uint16 else b)
-
-
-def engine_state(T, H, Wd, seed, min_disp=0.25):
-    """flow_up (T, 2, H, W): channel 0 = magnitudes in [0, 400) with both signs, exact zeros, values below min_disp, NaN and exact u16 ties k / 512
-    sprinkled in; channel 1 = another pattern (a wrong channel stride shows).  unc (T, H/4, W/4) in [0, 1)."""
-    g = torch.Generator().manual_seed(seed)
-    n = T * H * Wd
-    d = torch.rand(n, generator=g) * 400.0
-    d = d * torch.where(torch.rand(n, generator=g) < 0.5, -1.0, 1.0)
-    pick = torch.randperm(n, generator=g)
-    q = n // 16
-    d[pick[:q]] = 0.0
-    d[pick[q:2 * q]] = torch.rand(q, generator=g) * min_disp * torch.where(torch.rand(q, generator=g) < 0.5, -1.0, 1.0)
-    d[pick[2 * q:3 * q]] = float("nan")
-    d[pick[3 * q:4 * q]] = (2 * torch.randint(0, 60000, (q,), generator=g) + 1).float() / 512.0 * torch.where(torch.rand(q, generator=g) < 0.5, -1.0, 1.0)
-    flow = torch.stack([d.reshape(T, H, Wd), 1000.0 + torch.rand(T, H, Wd, generator=g)], dim=1).contiguous()
-    unc = torch.rand(T, H // 4, Wd // 4, generator=g)
-    return flow.to(DEV), unc.to(DEV)
-
-
-def expected(spec, flow, unc, f0, f1, left, top, h0, w0):
-    """OutputSpec.reference on the sliced flow_up and on ppms_bilinear's 4x upsampling of unc -- evaluated on the host, where torch's fp32
-    division and conversions are the IEEE ones beyond doubt -> CPU tensors."""
-    T, _, H, Wd = flow.shape
-    up = bilinear(unc.view(T, 1, H // 4, Wd // 4), (H, Wd), False)
-    cut = lambda x: x[f0:f1, :1, top:top + h0, left:left + w0].cpu()
-    return spec.reference(cut(flow), cut(up))
-
-
-class Dest:
-    """A byte buffer of ``frames`` output frames with a pitch, filled with a non-zero pattern; the launch writes n frames from frame ``first`` on."""
-
-    def __init__(self, fmt, frames, h0, w0, pitch_extra=0, first=0, frame_gap=0):
-        self.fmt, self.h0, self.w0, self.first = fmt, h0, w0, first
-        self.es = FMT[fmt][2]
-        self.pitch = w0 * self.es + pitch_extra
-        self.frame_stride = h0 * self.pitch + frame_gap
-        size = frames * self.frame_stride
-        self.pattern = (torch.arange(size, device=DEV) % 251 + 1).to(torch.uint8)
-        self.buf = self.pattern.clone()
-
-    def plane(self):
-        return L.EgressPlane(self.buf.data_ptr() + self.first * self.frame_stride, self.frame_stride, self.pitch, FMT[self.fmt][0], 0)
-
-    def region(self, t, n):
-        return torch.as_strided(t, (n, self.h0, self.w0 * self.es), (self.frame_stride, self.pitch, 1), self.first * self.frame_stride)
-
-    def written(self, n):
-        """(n, 1, h0, w0) tensor of the plane's dtype: what lies in the n frames' rows."""
-        return self.region(self.buf, n).contiguous().view(FMT[self.fmt][1]).reshape(n, 1, self.h0, self.w0).cpu()
-
-    def rest_untouched(self, n):
-        """Every byte outside the n frames' rows -- between rows, between frames, the frames before and after -- still holds the pattern."""
-        mask = torch.zeros_like(self.buf, dtype=torch.bool)
-        self.region(mask, n).fill_(True)
-        return torch.equal(self.buf[~mask], self.pattern[~mask])
-
-    def untouched(self):
-        return torch.equal(self.buf, self.pattern)
-
-
-NO_PLANE = L.EgressPlane(None, 0, 0, 0, 0)
-
-
-def launch(flow, unc, f0, n, left, top, h0, w0, spec, dests):
-    """dests: {key: Dest or None}"""
-    T, _, H, Wd = flow.shape
-    pl = [dests[k].plane() if dests.get(k) is not None else NO_PLANE for k in KEYS]
-    out = L.Egress(pl[0], pl[1], pl[2], spec.disp_scale, spec.fb, spec.depth_scale, spec.min_disp)
-    with torch.cuda.device(DEV):
-        L.check(L.load().ppms_disparity_egress(flow.data_ptr(), unc.data_ptr(), T, H, Wd, f0, n, left, top, h0, w0, ctypes.byref(out), L.stream_ptr()))
-        torch.cuda.synchronize()
-
-
-def check(spec, flow, unc, f0, n, left, top, h0, w0, dests):
-    want = expected(spec, flow, unc, f0, f0 + n, left, top, h0, w0)
-    launch(flow, unc, f0, n, left, top, h0, w0, spec, dests)
-    for key, dest in dests.items():
-        assert same(dest.written(n), want[key].contiguous()), key
-        assert dest.rest_untouched(n), key
-    return want
+ENTRY = "ppms_disparity_egress"
 
 
 FULL = dict(disparity="u16", depth="u16", uncertainty="u8", focal_px=721.5377, baseline=0.54, min_disp=0.25)
@@ -120,7 +26,7 @@ def test_kernel_odd_crop_pitches_and_frame_range():
     dests = {"disparity": Dest("u16", 4, 37, 50, pitch_extra=2, first=1, frame_gap=6), "depth": Dest("u16", 4, 37, 50, pitch_extra=6, first=1),
              "uncertainties": Dest("u8", 4, 37, 50, pitch_extra=3, first=1, frame_gap=5)}
     assert [d.pitch for d in dests.values()] == [102, 106, 53] and all(d.pitch % 8 for d in dests.values())
-    want = check(spec, flow, unc, 1, 2, 7, 13, 37, 50, dests)
+    want = check(ENTRY, planes_struct(spec, dests), planes_match(dests), spec, flow, unc, 1, 2, 7, 13, 37, 50)
     d16 = want["disparity"].to(torch.int32)
     assert (d16 == 0).any() and (d16 == 65535).any() and ((d16 > 0) & (d16 < 65535)).any() and (want["depth"].to(torch.int32) == 0).any()
 
@@ -130,13 +36,15 @@ def test_kernel_float_formats_uncropped():
     are flow_up[:, :1].abs() and ppms_bilinear(...).abs() themselves."""
     flow, unc = engine_state(3, 32, 64, 32)
     dests = {"disparity": Dest("f32", 3, 32, 64), "depth": Dest("f32", 3, 32, 64), "uncertainties": Dest("f32", 3, 32, 64)}
-    check(OutputSpec(disparity="f32", depth="f32", uncertainty="f32", focal_px=721.5377, baseline=0.54, min_disp=0.25), flow, unc, 0, 3, 0, 0, 32, 64, dests)
+    spec = OutputSpec(disparity="f32", depth="f32", uncertainty="f32", focal_px=721.5377, baseline=0.54, min_disp=0.25)
+    check(ENTRY, planes_struct(spec, dests), planes_match(dests), spec, flow, unc, 0, 3, 0, 0, 32, 64)
     assert same(dests["disparity"].written(3), flow[:, :1].abs().cpu())
     assert torch.equal(dests["uncertainties"].written(3), bilinear(unc.view(3, 1, 8, 16), (32, 64), False).abs().cpu())
     z = dests["depth"].written(3)
     assert torch.isposinf(z).any() and torch.isfinite(z).any() and not z.isnan().any()
     dests = {"disparity": Dest("f16", 3, 32, 64), "depth": Dest("f16", 3, 32, 64), "uncertainties": Dest("f32", 3, 32, 64)}
-    check(OutputSpec(disparity="f16", depth="f16", uncertainty="f32", focal_px=721.5377, baseline=0.54, min_disp=0.25), flow, unc, 0, 3, 0, 0, 32, 64, dests)
+    spec = OutputSpec(disparity="f16", depth="f16", uncertainty="f32", focal_px=721.5377, baseline=0.54, min_disp=0.25)
+    check(ENTRY, planes_struct(spec, dests), planes_match(dests), spec, flow, unc, 0, 3, 0, 0, 32, 64)
 
 
 @pytest.mark.parametrize("formats", [("u16", "u16", "u8"), ("f32", "f32", "f32")])
@@ -148,10 +56,10 @@ def test_kernel_vector_and_scalar_store_branches(formats):
     spec = OutputSpec(disparity=formats[0], depth=formats[1], uncertainty=formats[2], focal_px=721.5377, baseline=0.54, min_disp=0.25)
     dense = {k: Dest(f, 2, 32, 64) for k, f in zip(KEYS, formats)}
     assert all(d.buf.data_ptr() % 16 == 0 and d.pitch % 16 == 0 for d in dense.values())
-    check(spec, flow, unc, 0, 2, 0, 0, 32, 64, dense)
+    check(ENTRY, planes_struct(spec, dense), planes_match(dense), spec, flow, unc, 0, 2, 0, 0, 32, 64)
     odd = {k: Dest(f, 2, 32, 64, pitch_extra=2 * FMT[f][2]) for k, f in zip(KEYS, formats)}
     assert all(d.pitch % 16 for d in odd.values())
-    check(spec, flow, unc, 0, 2, 1, 0, 32, 64, odd)
+    check(ENTRY, planes_struct(spec, odd), planes_match(odd), spec, flow, unc, 0, 2, 1, 0, 32, 64)
 
 
 @pytest.mark.parametrize("only", KEYS)
@@ -165,7 +73,7 @@ def test_kernel_skipped_planes(only):
         spec.fb, spec.depth_scale, spec.min_disp = 0.0, 0.0, float("nan")
     if only != "disparity":
         spec.disp_scale = 0.0
-    launch(flow, unc, 0, 2, 3, 2, 27, 59, spec, {only: dests[only]})
+    launch(ENTRY, planes_struct(spec, {only: dests[only]}), flow, unc, 0, 2, 3, 2, 27, 59)
     for key, dest in dests.items():
         if key == only:
             assert same(dest.written(2), want[key].contiguous()) and dest.rest_untouched(2)
@@ -188,9 +96,7 @@ def test_kernel_output_frame_stride_past_2_to_31():
         plane = L.EgressPlane(buf.data_ptr(), stride, 12 * es, FMT[fmt][0], 0)
         planes = {"disparity": NO_PLANE, "depth": NO_PLANE, "uncertainties": NO_PLANE, key: plane}
         out = L.Egress(planes["disparity"], planes["depth"], planes["uncertainties"], spec.disp_scale, 0.0, 0.0, 0.0)
-        with torch.cuda.device(DEV):
-            L.check(L.load().ppms_disparity_egress(flow.data_ptr(), unc.data_ptr(), 2, 8, 12, 0, 2, 0, 0, 8, 12, ctypes.byref(out), L.stream_ptr()))
-            torch.cuda.synchronize()
+        launch(ENTRY, out, flow, unc, 0, 2, 0, 0, 8, 12)
         got = torch.stack([buf[t * stride:t * stride + frame].cpu().view(FMT[fmt][1]).reshape(1, 8, 12) for t in range(2)])
         assert same(got, want[key].contiguous()), key
         assert (buf[frame:frame + 64] == 0x5A).all() and (buf[stride - 64:stride] == 0x5A).all() and (buf[stride + frame:] == 0x5A).all()
@@ -198,30 +104,7 @@ def test_kernel_output_frame_stride_past_2_to_31():
 
 
 # ---- the model ---------------------------------------------------------------------------------------------------------------------------
-def rand_u8(shape, seed):
-    return torch.randint(0, 256, shape, dtype=torch.uint8, generator=torch.Generator().manual_seed(seed))
-
-
-@pytest.fixture(scope="module")
-def model():
-    """PPMStereo.shipped() with this package's encoders and the procedural weights (as tests/test_gpu_ingest_u8.py builds it)."""
-    assert torch.cuda.is_available(), "these tests need the MI355X (no CPU fallback exists)"
-    from ppmstereo_amd.ppmstereo import PPMStereo
-    m = PPMStereo.shipped()
-    m.load_hot_path_weights(W)
-    m.fnet.load_state_dict(Wm.fnet_weights(), strict=True)
-    m.cnet.load_state_dict(Wm.cnet_weights(), strict=True)
-    sd = m.state_dict()
-    sd.update(Wm.sst_weights())
-    m.load_state_dict(sd, strict=True)
-    return m.to(DEV).eval()
-
-
 QUANT = dict(disparity="u16", depth="u16", uncertainty="u8", focal_px=721.5377, baseline=0.54)
-
-
-def same_results(a, b, keys=("disparity", "uncertainties")):
-    return all(same(a[k], b[k]) for k in keys)
 
 
 def against_default(model, video, n, **kw):
@@ -285,11 +168,4 @@ def test_model_yuv_video(model):
 
 
 def test_model_refusals(model, monkeypatch):
-    v = rand_u8((1, 2, 3, 64, 256), 51).to(DEV)
-    with pytest.raises(NotImplementedError):
-        model.forward(v, v, iters=2, test_mode=False, output=OutputSpec())
-    with pytest.raises(NotImplementedError):
-        model.forward(v.expand(2, -1, -1, -1, -1), v.expand(2, -1, -1, -1, -1), iters=2, test_mode=True, output=OutputSpec())
-    monkeypatch.setattr(torch.distributed, "is_initialized", lambda: True)
-    with pytest.raises(NotImplementedError):
-        model.forward_batch_test({"stereo_video": rand_u8((3, 2, 3, 60, 250), 52)}, kernel_size=20, iters=2, shard_ranks=True, output=OutputSpec())
+    model_refuses(model, monkeypatch, OutputSpec())

@@ -1,91 +1,29 @@
-"""GPU: the compact point cloud.  ppms_cloud_egress on synthetic engine state (tests/test_gpu_egress.py's) against OutputSpec.reference evaluated
+"""GPU: the compact point cloud.  ppms_cloud_egress on synthetic engine state (tests/egress_util.py's) against OutputSpec.reference evaluated
 on the host, and PPMStereo.forward / forward_batch_test with an OutputSpec that asks for a cloud against the organised points of the same call
 without one.  Every comparison is of bytes: a record of a valid point holds no NaN.  The destinations are filled with a poison byte before the
 launch, so that "not written" is checked as well as "written"."""
-import ctypes
 from types import SimpleNamespace
 
 import pytest
 import torch
 
+from egress_util import (ALL, GATES, POISON, RIG_CAL, B, CloudDest, F, Q, all_kinds, check, engine_state, expected, launch, model, model_refuses, rand_u8,  # noqa: F401
+                         same_results)                                                                                                  # (model: the fixture)
 from ppmstereo_amd import _lib as L
 from ppmstereo_amd.ppmstereo import OutputSpec
 from test_gpu_block import DEV
-from test_gpu_egress import FMT, KEYS, engine_state, expected, model, rand_u8, same, same_results  # noqa: F401  (model: a fixture)
-from test_gpu_egress_points import ALL, CAL, GATES, B, F, Q, all_kinds
 
 pytestmark = pytest.mark.gpu
-POISON = 0x5A
-COUNT_POISON = int.from_bytes(bytes([POISON] * 4), "little")
+ENTRY = "ppms_cloud_egress"
 
 
 def cloud_spec(fmt="f32", layout="xyz", **kw):
     """Cloud and organised points of one format and layout (the points: what ``all_kinds`` and the comparisons read on the reference side)."""
-    return OutputSpec(points=fmt, points_layout=layout, cloud=fmt, cloud_layout=layout, cloud_index=True, Q=Q, **{**CAL, **GATES, **kw})
-
-
-class CloudDest:
-    """Poisoned destinations of ``frames`` frames, written from frame ``first`` on: records of ``capacity`` per frame with ``gap`` bytes between
-    the frames, starting ``lead`` bytes into their allocation; indices likewise; counts."""
-
-    def __init__(self, fmt, C, frames, capacity, first=0, gap=0, index_gap=0, lead=0, index=True):
-        self.dtype, self.C, self.frames, self.capacity, self.first, self.lead = FMT[fmt][1], C, frames, capacity, first, lead
-        self.rb = FMT[fmt][2] * C
-        self.frame_stride, self.index_frame_stride = capacity * self.rb + gap, capacity * 4 + index_gap
-        self.records = torch.full((lead + frames * self.frame_stride,), POISON, dtype=torch.uint8, device=DEV)
-        self.index = torch.full((frames * self.index_frame_stride,), POISON, dtype=torch.uint8, device=DEV) if index else None
-        self.counts = torch.full((frames,), COUNT_POISON, dtype=torch.int32, device=DEV)
-
-    def struct(self, spec, n, h0, w0):
-        self.workspace = torch.full((L.load().ppms_cloud_egress_workspace(n, h0, w0),), COUNT_POISON, dtype=torch.int32, device=DEV)
-        st = spec.cloud_struct({}, self.workspace)                # Q, min_disp, the gates, the format and the component count as the spec hands them over
-        st.records, st.frame_stride, st.capacity = self.records.data_ptr() + self.lead + self.first * self.frame_stride, self.frame_stride, self.capacity
-        if self.index is not None:
-            st.index, st.index_frame_stride = self.index.data_ptr() + self.first * self.index_frame_stride, self.index_frame_stride
-        st.counts = self.counts.data_ptr() + 4 * self.first
-        return st
-
-    def check(self, n, want, capacity_hit=False):
-        """Frame f of the launch holds the first min(count, capacity) records and indices of the reference's and poison from there to the next
-        frame's first byte; the other frames' bytes and counts are poison; the counts are the reference's (full) numbers."""
-        rec, idx, counts = self.records.cpu(), None if self.index is None else self.index.cpu(), self.counts.cpu()
-        assert (rec[:self.lead] == POISON).all()
-        hit = False
-        for fr in range(self.frames):
-            f = fr - self.first
-            r = rec[self.lead + fr * self.frame_stride:self.lead + (fr + 1) * self.frame_stride]
-            i = None if idx is None else idx[fr * self.index_frame_stride:(fr + 1) * self.index_frame_stride]
-            if not 0 <= f < n:
-                assert (r == POISON).all() and (i is None or (i == POISON).all()) and int(counts[fr]) == COUNT_POISON, fr
-                continue
-            count = int(want["cloud_counts"][f])
-            assert int(counts[fr]) == count == want["cloud"][f].shape[0], (fr, int(counts[fr]), count)
-            k = min(count, self.capacity)
-            hit |= count > self.capacity
-            assert want["cloud"][f].dtype == self.dtype and want["cloud"][f].shape[1] == self.C
-            assert torch.equal(r[:k * self.rb], want["cloud"][f][:k].contiguous().view(torch.uint8).flatten()), fr
-            assert (r[k * self.rb:] == POISON).all(), fr
-            if i is not None:
-                assert torch.equal(i[:4 * k], want["cloud_index"][f][:k].contiguous().view(torch.uint8).flatten()), fr
-                assert (i[4 * k:] == POISON).all(), fr
-        assert hit == capacity_hit
-
-
-def launch_cloud(flow, unc, f0, n, left, top, h0, w0, spec, dest):
-    T, _, H, Wd = flow.shape
-    out = dest.struct(spec, n, h0, w0)
-    with torch.cuda.device(DEV):
-        L.check(L.load().ppms_cloud_egress(flow.data_ptr(), unc.data_ptr(), T, H, Wd, f0, n, left, top, h0, w0, ctypes.byref(out), L.stream_ptr()))
-        torch.cuda.synchronize()
+    return OutputSpec(points=fmt, points_layout=layout, cloud=fmt, cloud_layout=layout, cloud_index=True, Q=Q, **{**RIG_CAL, **GATES, **kw})
 
 
 def check_cloud(spec, flow, unc, f0, n, left, top, h0, w0, dest, kinds=True, capacity_hit=False):
-    want = expected(spec, flow, unc, f0, f0 + n, left, top, h0, w0)
-    launch_cloud(flow, unc, f0, n, left, top, h0, w0, spec, dest)
-    dest.check(n, want, capacity_hit)
-    if kinds:
-        assert all_kinds(spec, want, flow, unc, f0, n, left, top, h0, w0)
-    return want
+    return check(ENTRY, dest.struct(spec, n, h0, w0), lambda want, *_: dest.check(n, want, capacity_hit), spec, flow, unc, f0, n, left, top, h0, w0, kinds)
 
 
 # ---- the kernels ---------------------------------------------------------------------------------------------------------------------------
@@ -164,9 +102,7 @@ def test_kernel_frame_stride_past_2_to_31():
     small = CloudDest("f32", 3, 2, 8 * 12)                        # its index, counts and workspace; the records go to ``buf``
     out = small.struct(spec, 2, 8, 12)
     out.records, out.frame_stride = buf.data_ptr(), stride
-    with torch.cuda.device(DEV):
-        L.check(L.load().ppms_cloud_egress(flow.data_ptr(), unc.data_ptr(), 2, 8, 12, 0, 2, 0, 0, 8, 12, ctypes.byref(out), L.stream_ptr()))
-        torch.cuda.synchronize()
+    launch(ENTRY, out, flow, unc, 0, 2, 0, 0, 8, 12)
     assert small.counts.cpu().tolist() == want["cloud_counts"].tolist() and (small.records == POISON).all()
     for f in range(2):
         k = int(want["cloud_counts"][f])
@@ -182,7 +118,7 @@ def test_kernel_two_runs_give_identical_bytes():
     runs = []
     for _ in range(2):
         dest = CloudDest("f32", 3, 4, 37 * 50, first=1, gap=40, index_gap=12, lead=4)
-        launch_cloud(flow, unc, *A_GEOMETRY, cloud_spec(), dest)
+        launch(ENTRY, dest.struct(cloud_spec(), 2, 37, 50), flow, unc, *A_GEOMETRY)
         runs.append((dest.records.cpu(), dest.index.cpu(), dest.counts.cpu()))
     assert all(torch.equal(a, b) for a, b in zip(*runs)) and not (runs[0][0] == POISON).all()
 
@@ -191,11 +127,11 @@ def test_launch_beside_the_planes_leaves_their_bits():
     """``_EgressCall.launch`` on an engine's state with a spec of three planes, organised points and a cloud: the planes and points are those of the
     same spec without the cloud, bit for bit, and the cloud is the organised plane at its valid pixels."""
     from ppmstereo_amd.engine import ScaleEngine
-    from ppmstereo_amd.video import _EgressCall
+    from ppmstereo_amd.output import _EgressCall
     flow, unc = engine_state(3, 64, 64, 78)
     eng = SimpleNamespace(FLOW_OUT=flow, UNC=unc, T=3, h=16, w=16, shard=None)
     eng.egress = lambda *a: ScaleEngine.egress(eng, *a)
-    kw = dict(disparity="u16", depth="u16", uncertainty="u8", points="f32", points_layout="xyzw", Q=Q, **CAL, **GATES)
+    kw = dict(disparity="u16", depth="u16", uncertainty="u8", points="f32", points_layout="xyzw", Q=Q, **RIG_CAL, **GATES)
     with torch.cuda.device(DEV):
         plain = _EgressCall(OutputSpec(**kw), A_GEOMETRY[2:], (1, 3)).launch(eng)
         both = _EgressCall(OutputSpec(cloud="f16", cloud_index=True, cloud_capacity=2000, **kw), A_GEOMETRY[2:], (1, 3)).launch(eng)
@@ -304,12 +240,4 @@ def test_model_rectified_uint8_video(model):
 
 
 def test_model_refusals(model, monkeypatch):
-    spec = OutputSpec(cloud="f32", Q=Q, max_uncertainty=0.5)
-    v = rand_u8((1, 2, 3, 64, 256), 51).to(DEV)
-    with pytest.raises(NotImplementedError):
-        model.forward(v, v, iters=2, test_mode=False, output=spec)
-    with pytest.raises(NotImplementedError):
-        model.forward(v.expand(2, -1, -1, -1, -1), v.expand(2, -1, -1, -1, -1), iters=2, test_mode=True, output=spec)
-    monkeypatch.setattr(torch.distributed, "is_initialized", lambda: True)
-    with pytest.raises(NotImplementedError):
-        model.forward_batch_test({"stereo_video": rand_u8((3, 2, 3, 60, 250), 52)}, kernel_size=20, iters=2, shard_ranks=True, output=spec)
+    model_refuses(model, monkeypatch, OutputSpec(cloud="f32", Q=Q, max_uncertainty=0.5))

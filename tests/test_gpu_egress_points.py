@@ -1,60 +1,18 @@
-"""GPU: the point-cloud back door.  ppms_scene_egress on synthetic engine state (built as tests/test_gpu_egress.py builds it) against
+"""GPU: the point-cloud back door.  ppms_scene_egress on synthetic engine state (tests/egress_util.py's) against
 OutputSpec.reference evaluated on the host, and PPMStereo.forward / forward_batch_test with an OutputSpec that asks for points and gates against
 the reference applied to the default call's float32 results.  Every comparison is exact (NaN equals NaN at the same place: an invalid point's
 payload is not part of the definition)."""
-import ctypes
-
 import pytest
 import torch
 
+from egress_util import (ALL, FMT, GATES, KEYS, NO_PLANE, RIG_CAL, B, Dest, F, Q, all_kinds, check, engine_state, expected, launch, model, model_refuses, planes_match,  # noqa: F401
+                         planes_struct, rand_u8, same, same_results)                                                                                # (model: the fixture)
 from ppmstereo_amd import _lib as L
-from ppmstereo_amd.engine import bilinear
 from ppmstereo_amd.ppmstereo import OutputSpec
 from test_gpu_block import DEV
-from test_gpu_egress import FMT, KEYS, NO_PLANE, Dest, engine_state, expected, launch, model, rand_u8, same, same_results  # noqa: F401  (model: a fixture)
 
 pytestmark = pytest.mark.gpu
-ALL = KEYS + ("points",)
-F, B = 721.5377, 0.54                                        # fb = 389.6: with d in [0, 400), max_depth = 5 gates d < 78
-Q = OutputSpec.q_matrix(F, B, 24.3, 17.6)
-GATES = dict(max_uncertainty=0.7, max_depth=5.0)
-CAL = dict(focal_px=F, baseline=B, min_disp=0.25)
-
-
-def launch3d(flow, unc, f0, n, left, top, h0, w0, spec, dests):
-    """dests: {key: Dest or None}; the points' Dest is a plane of w0 * C elements per row."""
-    T, _, H, Wd = flow.shape
-    pl = [dests[k].plane() if dests.get(k) is not None else NO_PLANE for k in ALL]
-    rest = spec.scene_struct({})                              # Q, the gates and the component count as the spec hands them over
-    out = L.Egress3D(L.Egress(pl[0], pl[1], pl[2], spec.disp_scale, spec.fb, spec.depth_scale, spec.min_disp), pl[3], rest.q, rest.max_uncertainty,
-                     rest.max_depth, rest.points_components, 0)
-    with torch.cuda.device(DEV):
-        L.check(L.load().ppms_scene_egress(flow.data_ptr(), unc.data_ptr(), T, H, Wd, f0, n, left, top, h0, w0, ctypes.byref(out), L.stream_ptr()))
-        torch.cuda.synchronize()
-
-
-def all_kinds(spec, want, flow, unc, f0, n, left, top, h0, w0):
-    """On the reference side: valid pixels, pixels the uncertainty gate takes, pixels the depth gate takes, and NaN disparities all occur."""
-    T, _, H, Wd = flow.shape
-    cut = lambda x: x[f0:f0 + n, 0, top:top + h0, left:left + w0].abs().cpu()
-    d, u = cut(flow), cut(bilinear(unc.view(T, 1, H // 4, Wd // 4), (H, Wd), False))
-    if "points" in want:
-        ok = ~want["points"][..., 2].float().isnan()
-    else:
-        ok = want["depth"][:, 0].to(torch.int32) != 0 if want["depth"].dtype == torch.uint16 else ~want["depth"][:, 0].float().isinf()
-    vd, vu = d >= spec.min_disp, u <= spec.max_uncertainty
-    return bool(ok.any() and (vd & ~vu).any() and (vd & vu & ~ok).any() and d.isnan().any() and (~vd & ~d.isnan()).any() and not (ok & ~(vd & vu)).any())
-
-
-def check3d(spec, flow, unc, f0, n, left, top, h0, w0, dests):
-    want = expected(spec, flow, unc, f0, f0 + n, left, top, h0, w0)
-    launch3d(flow, unc, f0, n, left, top, h0, w0, spec, dests)
-    for key, dest in dests.items():
-        got = dest.written(n)
-        assert same(got.reshape(n, h0, w0, -1) if key == "points" else got, want[key].contiguous()), key
-        assert dest.rest_untouched(n), key
-    assert all_kinds(spec, want, flow, unc, f0, n, left, top, h0, w0)
-    return want
+ENTRY = "ppms_scene_egress"
 
 
 def test_kernel_odd_crop_pitches_frame_range_and_every_plane():
@@ -62,13 +20,13 @@ def test_kernel_odd_crop_pitches_frame_range_and_every_plane():
     The points pitch (604 bytes) is wider than the row's 600 and no multiple of 16: three rows in four start off alignment and are stored element
     by element, as every row's last run (2 pixels) is.  Destinations of 4 frames with a gap between frames, written from frame 1 on."""
     flow, unc = engine_state(3, 64, 64, 61)
-    spec = OutputSpec(disparity="u16", depth="u16", uncertainty="u8", points="f32", Q=Q, **CAL, **GATES)
+    spec = OutputSpec(disparity="u16", depth="u16", uncertainty="u8", points="f32", Q=Q, **RIG_CAL, **GATES)
     dests = {"disparity": Dest("u16", 4, 37, 50, pitch_extra=2, first=1, frame_gap=6), "depth": Dest("u16", 4, 37, 50, pitch_extra=6, first=1),
              "uncertainties": Dest("u8", 4, 37, 50, pitch_extra=3, first=1, frame_gap=5), "points": Dest("f32", 4, 37, 50 * 3, pitch_extra=4, first=1, frame_gap=8)}
     assert dests["points"].pitch == 604 and dests["points"].pitch % 16 and dests["points"].frame_stride % 16
-    want = check3d(spec, flow, unc, 1, 2, 7, 13, 37, 50, dests)
+    want = check(ENTRY, planes_struct(spec, dests, True), planes_match(dests), spec, flow, unc, 1, 2, 7, 13, 37, 50, kinds=True)
     # the gates reach the depth plane and leave the other two alone
-    plain = expected(OutputSpec(disparity="u16", depth="u16", uncertainty="u8", **CAL), flow, unc, 1, 3, 7, 13, 37, 50)
+    plain = expected(OutputSpec(disparity="u16", depth="u16", uncertainty="u8", **RIG_CAL), flow, unc, 1, 3, 7, 13, 37, 50)
     assert same(want["disparity"], plain["disparity"]) and same(want["uncertainties"], plain["uncertainties"]) and not same(want["depth"], plain["depth"])
 
 
@@ -78,10 +36,10 @@ def test_kernel_dense_uncropped_formats_and_layouts(fmt, layout):
     bottom and the right are reached.  w of "xyzw" is the upsampled |uncertainty| in the points' format, for valid and invalid points alike."""
     flow, unc = engine_state(2, 32, 64, 62)
     C = 4 if layout == "xyzw" else 3
-    spec = OutputSpec(disparity="f32", uncertainty="f32", points=fmt, points_layout=layout, Q=Q, **CAL, **GATES)
+    spec = OutputSpec(disparity="f32", uncertainty="f32", points=fmt, points_layout=layout, Q=Q, **RIG_CAL, **GATES)
     dests = {"disparity": Dest("f32", 2, 32, 64), "uncertainties": Dest("f32", 2, 32, 64), "points": Dest(fmt, 2, 32, 64 * C)}
     assert dests["points"].buf.data_ptr() % 16 == 0 and dests["points"].pitch % 16 == 0 and dests["points"].frame_stride % 16 == 0
-    want = check3d(spec, flow, unc, 0, 2, 0, 0, 32, 64, dests)
+    want = check(ENTRY, planes_struct(spec, dests, True), planes_match(dests), spec, flow, unc, 0, 2, 0, 0, 32, 64, kinds=True)
     assert tuple(want["points"].shape) == (2, 32, 64, C)
     if C == 4:
         assert same(dests["points"].written(2).reshape(2, 32, 64, 4)[..., 3], dests["uncertainties"].written(2)[:, 0].to(FMT[fmt][1]))
@@ -90,12 +48,12 @@ def test_kernel_dense_uncropped_formats_and_layouts(fmt, layout):
 def test_kernel_points_alone():
     """No other plane: the three planes' buffers stay as they were and their constants are not looked at."""
     flow, unc = engine_state(2, 32, 64, 63)
-    spec = OutputSpec(points="f32", Q=Q, **CAL, **GATES)
+    spec = OutputSpec(points="f32", Q=Q, **RIG_CAL, **GATES)
     others = {"disparity": Dest("f32", 2, 27, 59), "depth": Dest("u16", 2, 27, 59), "uncertainties": Dest("u8", 2, 27, 59)}
     dests = {"points": Dest("f32", 2, 27, 59 * 3)}
     want = expected(spec, flow, unc, 0, 2, 3, 2, 27, 59)
     spec.disp_scale, spec.fb, spec.depth_scale = 0.0, 0.0, 0.0
-    launch3d(flow, unc, 0, 2, 3, 2, 27, 59, spec, dests)
+    launch(ENTRY, planes_struct(spec, dests, True), flow, unc, 0, 2, 3, 2, 27, 59)
     assert same(dests["points"].written(2).reshape(2, 27, 59, 3), want["points"].contiguous()) and dests["points"].rest_untouched(2)
     assert all(d.untouched() for d in others.values()) and all_kinds(spec, want, flow, unc, 0, 2, 3, 2, 27, 59)
 
@@ -104,18 +62,18 @@ def test_kernel_points_alone():
 def test_kernel_gates_alone(depth):
     """No points: of the three planes the depth plane alone differs from the ungated call's (ppms_disparity_egress), and it is the reference's."""
     flow, unc = engine_state(2, 32, 64, 64)
-    kw = dict(disparity="u16", depth=depth, uncertainty="u8", **CAL)
+    kw = dict(disparity="u16", depth=depth, uncertainty="u8", **RIG_CAL)
     make = lambda: {"disparity": Dest("u16", 2, 27, 59), "depth": Dest(depth, 2, 27, 59, pitch_extra=FMT[depth][2]), "uncertainties": Dest("u8", 2, 27, 59)}
     gated, plain = make(), make()
     spec = OutputSpec(**kw, **GATES)
     assert spec.scene and "points" not in spec.formats()
-    check3d(spec, flow, unc, 0, 2, 3, 2, 27, 59, gated)
-    launch(flow, unc, 0, 2, 3, 2, 27, 59, OutputSpec(**kw), plain)
+    check(ENTRY, planes_struct(spec, gated, True), planes_match(gated), spec, flow, unc, 0, 2, 3, 2, 27, 59, kinds=True)
+    launch("ppms_disparity_egress", planes_struct(OutputSpec(**kw), plain), flow, unc, 0, 2, 3, 2, 27, 59)
     assert torch.equal(gated["disparity"].buf, plain["disparity"].buf) and torch.equal(gated["uncertainties"].buf, plain["uncertainties"].buf)
     assert not torch.equal(gated["depth"].buf, plain["depth"].buf)
     # a struct with the gates off and no points: the older entry point's bits, plane for plane
     off = make()
-    launch3d(flow, unc, 0, 2, 3, 2, 27, 59, OutputSpec(**kw), off)
+    launch(ENTRY, planes_struct(OutputSpec(**kw), off, True), flow, unc, 0, 2, 3, 2, 27, 59)
     assert all(torch.equal(off[k].buf, plain[k].buf) for k in KEYS)
 
 
@@ -123,7 +81,7 @@ def test_kernel_points_frame_stride_past_2_to_31():
     """Two frames of 8 x 12 "xyz" f32 points (1152 bytes each) whose second lies (1 << 31) + 4100 bytes behind the first in one uint8 allocation:
     the destination offset is 64-bit arithmetic."""
     flow, unc = engine_state(2, 8, 12, 65)
-    spec = OutputSpec(points="f32", Q=Q, **CAL, max_uncertainty=0.5, max_depth=3.0)
+    spec = OutputSpec(points="f32", Q=Q, **RIG_CAL, max_uncertainty=0.5, max_depth=3.0)
     want = expected(spec, flow, unc, 0, 2, 0, 0, 8, 12)
     assert all_kinds(spec, want, flow, unc, 0, 2, 0, 0, 8, 12)
     stride, frame = (1 << 31) + 4100, 8 * 12 * 12
@@ -133,9 +91,7 @@ def test_kernel_points_frame_stride_past_2_to_31():
     rest = spec.scene_struct({})
     out = L.Egress3D(L.Egress(NO_PLANE, NO_PLANE, NO_PLANE, 0.0, 0.0, 0.0, spec.min_disp), L.EgressPlane(buf.data_ptr(), stride, 12 * 12, L.FMT_F32, 0), rest.q,
                      rest.max_uncertainty, rest.max_depth, 3, 0)
-    with torch.cuda.device(DEV):
-        L.check(L.load().ppms_scene_egress(flow.data_ptr(), unc.data_ptr(), 2, 8, 12, 0, 2, 0, 0, 8, 12, ctypes.byref(out), L.stream_ptr()))
-        torch.cuda.synchronize()
+    launch(ENTRY, out, flow, unc, 0, 2, 0, 0, 8, 12)
     got = torch.stack([buf[t * stride:t * stride + frame].cpu().view(torch.float32).reshape(8, 12, 3) for t in range(2)])
     assert same(got, want["points"].contiguous())
     assert (buf[frame:frame + 64] == 0x5A).all() and (buf[stride - 64:stride] == 0x5A).all() and (buf[stride + frame:] == 0x5A).all()
@@ -208,12 +164,4 @@ def test_model_rectified_uint8_video(model):
 
 
 def test_model_refusals(model, monkeypatch):
-    spec = OutputSpec(points="f32", Q=Q, max_uncertainty=0.5)
-    v = rand_u8((1, 2, 3, 64, 256), 51).to(DEV)
-    with pytest.raises(NotImplementedError):
-        model.forward(v, v, iters=2, test_mode=False, output=spec)
-    with pytest.raises(NotImplementedError):
-        model.forward(v.expand(2, -1, -1, -1, -1), v.expand(2, -1, -1, -1, -1), iters=2, test_mode=True, output=spec)
-    monkeypatch.setattr(torch.distributed, "is_initialized", lambda: True)
-    with pytest.raises(NotImplementedError):
-        model.forward_batch_test({"stereo_video": rand_u8((3, 2, 3, 60, 250), 52)}, kernel_size=20, iters=2, shard_ranks=True, output=spec)
+    model_refuses(model, monkeypatch, OutputSpec(points="f32", Q=Q, max_uncertainty=0.5))

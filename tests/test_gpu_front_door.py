@@ -7,7 +7,7 @@ import torch
 from ppmstereo_amd.ppmstereo import OutputSpec, PPMStereo, YUVFrames, YUVStereoVideo, window_plan
 from stub_encoders import StubCNet, StubFNet, frame_video
 from test_gpu_block import DEV, W
-from test_gpu_egress import same as same_tensor
+from egress_util import same as same_tensor
 from test_gpu_ingest_remap import raw_video, rectified_video, smooth_rectifier
 from ingest_util import model, same  # noqa: F401  (model: the fixture)
 
