@@ -255,7 +255,8 @@ int ppms_bilinear(const float* src, float* dst, int N, int C, int H, int W, int 
  * its plane; a crop outside H x W, or H, W not multiples of 4; n_frames <= 0 or frame0 + n_frames > T; a pitch shorter than its row (or, with
  * n_frames > 1, a frame_stride shorter than a plane); a depth plane with fb <= 0, depth_scale <= 0 or a non-finite min_disp; a U16 disparity with
  * disp_scale <= 0. */
-enum { PPMS_FMT_F32 = 0, PPMS_FMT_F16 = 1, PPMS_FMT_U16 = 2, PPMS_FMT_U8 = 3 };
+enum { PPMS_FMT_F32 = 0, PPMS_FMT_F16 = 1, PPMS_FMT_U16 = 2, PPMS_FMT_U8 = 3,
+       PPMS_FMT_RGBA8 = 4, PPMS_FMT_BGRA8 = 5 };   /* 4-byte colour pixels: the colour planes below only; every plane above refuses them */
 typedef struct ppms_egress_plane {
     void* ptr;                        /* element (0, 0, 0) of the output; NULL: the plane is skipped */
     int64_t frame_stride;             /* bytes from frame f to frame f + 1 */
@@ -342,6 +343,20 @@ int     ppms_cloud_egress(const float* flow_up, const float* unc, int T, int H, 
                           int H0, int W0, const ppms_cloud* out, void* stream);
 int64_t ppms_cloud_egress_workspace(int n_frames, int H0, int W0);   /* entries block_counts needs; 0 for a geometry the call refuses */
 int     ppms_cloud_struct_size(void);  /* sizeof(ppms_cloud) (152) */
+/* The coloured compact cloud (XYZRGB): ppms_cloud_egress for components = 4 and PPMS_FMT_F32 with ONE change -- the fourth 32-bit word of record k
+ * is the colour pixel at that record's (y, x), not the uncertainty.  `colour`: a device plane of the launch's n_frames x H0 x W0 pixels (frame f
+ * of the launch, row y and column x of the crop), 4 bytes each, PPMS_FMT_RGBA8 or PPMS_FMT_BGRA8 (what ppms_video_colour_* below writes); the
+ * word is copied as 32 bits, whichever of the two formats the plane names: read as a little-endian uint32 a BGRA8 pixel is 0xFFRRGGBB, the `rgb`
+ * of PCL's PointXYZRGB.  The word travels as an integer from its load to its store: with alpha 255 and a third byte in 0x80..0xBF it is the
+ * pattern of a signalling NaN, and no float operation may touch it.  Counts, order, indices, truncation at capacity and the bits of X, Y, Z are
+ * ppms_cloud_egress's; the count launch is the same kernel, the place launch reads one aligned 32-bit word per pixel (16-byte loads where the
+ * thread's run is whole and aligned).  unc is read only where the max_uncertainty gate needs it.
+ * Refused with PPMS_EINVAL before any launch: everything ppms_cloud_egress refuses (one shared check; unc == NULL only with the gate on);
+ * components != 4; a format other than PPMS_FMT_F32; a null colour or colour->ptr; a colour format other than the two; a colour pitch < 4 * W0;
+ * with n_frames > 1 a colour frame_stride shorter than a plane; a colour pointer, pitch or frame_stride that is no multiple of 4;
+ * colour->reserved != 0. */
+int     ppms_cloud_egress_colour(const float* flow_up, const float* unc, int T, int H, int W, int frame0, int n_frames, int pad_left, int pad_top,
+                                 int H0, int W0, const ppms_cloud* out, const ppms_egress_plane* colour, void* stream);
 
 /* Scale-to-scale hand-over of the cascade without leaving the SP format (ppmstereo.py:726-732, 763-767): per frame,
  * dst = a * dst + b * interp(src), interp = F.interpolate(mode="bilinear", align_corners=True) from HxW to OHxOW.
@@ -600,6 +615,60 @@ int ppms_video_ingest_raw_packed_remap(const ppms_packed_view* left, const ppms_
                                        int N, int H0, int W0, int pad_left, int pad_top, int H, int W,
                                        const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream);
 int ppms_packed_struct_sizes(int* view, int* yuv_format, int* raw_format);   /* sizeof of the three structs above (24, 32, 48): lets a binding verify its layout */
+/* Colour out: the LEFT view as the network saw it -- converted, demosaiced, white-balanced, tone-mapped, rectified -- as 4-byte pixels registered
+ * to the egress planes, one launch.  One entry point per ingest door above, with that door's head arguments (and maps), the same sources and the
+ * same checks of them; the right view's pointers and structs stay in the signature and are checked, and never read by the kernel.
+ * Output pixel (f, y, x), f in [0, n_frames), y in [0, h0), x in [0, w0), is the pixel (clamp(y + y0, 0, H0 - 1), clamp(x + x0, 0, W0 - 1)) of left
+ * frame frame0 + f of the H0 x W0 frame (the rectified frame for _remap): x0 = crop_left - pad_left, y0 = crop_top - pad_top of an egress crop inside
+ * the padded frame, so a crop that reaches into the padding sees the replicate padding the network saw; x0, y0 may be negative or reach past the frame.
+ * Each of the pixel's three levels (the door's own R, G, B of `depth` bits) is looked up in `table`, device uint8 [2^depth] (256 for the u8 and
+ * yuv420 doors): the byte the level stands for, built by the caller (clamp(rint(float value), 0, 255), ties to even; a raw format's tone curve goes
+ * here).  The pixel's four bytes in memory are R, G, B, 255 (PPMS_FMT_RGBA8) or B, G, R, 255 (PPMS_FMT_BGRA8).  `out`: HOST struct, a device plane of
+ * n_frames x h0 x w0 pixels with byte strides (bytes between the rows of a pitched plane are not written).
+ * Refused with PPMS_EINVAL before any launch: everything the door's ingest twin refuses about sources, formats and maps; a null table, out or
+ * out->ptr; a format other than the two; a pitch < 4 * w0; with n_frames > 1 a frame_stride shorter than a plane (frames that overlap); a pointer,
+ * pitch or frame_stride that is no multiple of 4; frame0 < 0, n_frames <= 0 or frame0 + n_frames > N; h0 or w0 not positive; reserved != 0. */
+int ppms_video_colour_u8(const uint8_t* left, const uint8_t* right, int64_t frame_stride,
+                         int N, int H0, int W0, int frame0, int n_frames, int x0, int y0, int h0, int w0,
+                         const uint8_t* table, const ppms_egress_plane* out, void* stream);
+int ppms_video_colour_u8_remap(const uint8_t* left, const uint8_t* right, int64_t frame_stride, const ppms_remap_view* lmap, const ppms_remap_view* rmap,
+                               int N, int H0, int W0, int frame0, int n_frames, int x0, int y0, int h0, int w0,
+                               const uint8_t* table, const ppms_egress_plane* out, void* stream);
+int ppms_video_colour_yuv420(const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m,
+                             int N, int H0, int W0, int frame0, int n_frames, int x0, int y0, int h0, int w0,
+                             const uint8_t* table, const ppms_egress_plane* out, void* stream);
+int ppms_video_colour_yuv420_remap(const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m,
+                                   const ppms_remap_view* lmap, const ppms_remap_view* rmap,
+                                   int N, int H0, int W0, int frame0, int n_frames, int x0, int y0, int h0, int w0,
+                                   const uint8_t* table, const ppms_egress_plane* out, void* stream);
+int ppms_video_colour_yuv(const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m, const ppms_yuv_format* fmt,
+                          int N, int H0, int W0, int frame0, int n_frames, int x0, int y0, int h0, int w0,
+                          const uint8_t* table, const ppms_egress_plane* out, void* stream);
+int ppms_video_colour_yuv_remap(const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m, const ppms_yuv_format* fmt,
+                                const ppms_remap_view* lmap, const ppms_remap_view* rmap,
+                                int N, int H0, int W0, int frame0, int n_frames, int x0, int y0, int h0, int w0,
+                                const uint8_t* table, const ppms_egress_plane* out, void* stream);
+int ppms_video_colour_raw(const ppms_raw_view* left, const ppms_raw_view* right, const ppms_raw_format* fmt,
+                          int N, int H0, int W0, int frame0, int n_frames, int x0, int y0, int h0, int w0,
+                          const uint8_t* table, const ppms_egress_plane* out, void* stream);
+int ppms_video_colour_raw_remap(const ppms_raw_view* left, const ppms_raw_view* right, const ppms_raw_format* fmt,
+                                const ppms_remap_view* lmap, const ppms_remap_view* rmap,
+                                int N, int H0, int W0, int frame0, int n_frames, int x0, int y0, int h0, int w0,
+                                const uint8_t* table, const ppms_egress_plane* out, void* stream);
+int ppms_video_colour_yuv_packed(const ppms_packed_view* left, const ppms_packed_view* right, const ppms_yuv_matrix* m, const ppms_yuv_packed_format* fmt,
+                                 int N, int H0, int W0, int frame0, int n_frames, int x0, int y0, int h0, int w0,
+                                 const uint8_t* table, const ppms_egress_plane* out, void* stream);
+int ppms_video_colour_yuv_packed_remap(const ppms_packed_view* left, const ppms_packed_view* right, const ppms_yuv_matrix* m, const ppms_yuv_packed_format* fmt,
+                                       const ppms_remap_view* lmap, const ppms_remap_view* rmap,
+                                       int N, int H0, int W0, int frame0, int n_frames, int x0, int y0, int h0, int w0,
+                                       const uint8_t* table, const ppms_egress_plane* out, void* stream);
+int ppms_video_colour_raw_packed(const ppms_packed_view* left, const ppms_packed_view* right, const ppms_raw_packed_format* fmt,
+                                 int N, int H0, int W0, int frame0, int n_frames, int x0, int y0, int h0, int w0,
+                                 const uint8_t* table, const ppms_egress_plane* out, void* stream);
+int ppms_video_colour_raw_packed_remap(const ppms_packed_view* left, const ppms_packed_view* right, const ppms_raw_packed_format* fmt,
+                                       const ppms_remap_view* lmap, const ppms_remap_view* rmap,
+                                       int N, int H0, int W0, int frame0, int n_frames, int x0, int y0, int h0, int w0,
+                                       const uint8_t* table, const ppms_egress_plane* out, void* stream);
 /* nn.InstanceNorm2d(affine=False) (extractor.py:326-329, 364): per (sample, channel) mean and 1 / sqrt(biased var + eps) over the
  * HW pixels of x (channel-last fp32 [N * HW][ld], a convolution's fp32 output) -> stats[N][C][2] (pixel slices merged in fixed
  * order: deterministic; caller-owned 16-B aligned workspace of ppms_instnorm_workspace_bytes); then

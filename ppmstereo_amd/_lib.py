@@ -110,7 +110,7 @@ class RemapView(C.Structure):
 
 
 BORDER_REPLICATE, BORDER_CONSTANT = 0, 1
-FMT_F32, FMT_F16, FMT_U16, FMT_U8 = range(4)
+FMT_F32, FMT_F16, FMT_U16, FMT_U8, FMT_RGBA8, FMT_BGRA8 = range(6)       # (the last two: 4-byte colour pixels, the colour planes only)
 
 
 class EgressPlane(C.Structure):
@@ -233,6 +233,12 @@ _INGEST_TAIL = [c_int] * 7 + [c_void_p, SP, SP, c_void_p]       # N, H0, W0, pad
 for _door, _head in _INGEST_HEADS.items():
     _SIGS["ppms_video_ingest_" + _door] = (c_int, _head + _INGEST_TAIL)
     _SIGS["ppms_video_ingest_" + _door + "_remap"] = (c_int, _head + [C.POINTER(RemapView)] * 2 + _INGEST_TAIL)
+# colour out: the same 12 doors (ppms_video_colour_<door>[_remap]) with one tail, and the coloured compact cloud (ppms_cloud_egress's list + the plane)
+_COLOUR_TAIL = [c_int] * 9 + [c_void_p, C.POINTER(EgressPlane), c_void_p]       # N, H0, W0, frame0, n_frames, x0, y0, h0, w0, table, out, stream
+for _door, _head in _INGEST_HEADS.items():
+    _SIGS["ppms_video_colour_" + _door] = (c_int, _head + _COLOUR_TAIL)
+    _SIGS["ppms_video_colour_" + _door + "_remap"] = (c_int, _head + [C.POINTER(RemapView)] * 2 + _COLOUR_TAIL)
+_SIGS["ppms_cloud_egress_colour"] = (c_int, _SIGS["ppms_cloud_egress"][1][:-1] + [C.POINTER(EgressPlane), c_void_p])
 EXPORTS = tuple(_SIGS)
 
 # (the export that reports sizeof of the structs, their ctypes twins, the message when they differ).  An export takes one int* per struct; one

@@ -1,6 +1,7 @@
 // What the egress sources (egress.hip: the planes and the organised points; cloud_egress.hip: the compacted cloud) share: the thread mapping,
 // the loads of the engine's state, and the host checks of the geometry and the frame range, of the reprojection's arguments and of a strided
-// destination.  Device pieces are restated nowhere else: a pixel's d and u are the same bits whichever launch reads them.
+// destination.  Device pieces are restated nowhere else: a pixel's d and u are the same bits whichever launch reads them.  The check of a
+// colour plane (4-byte pixels) is here too: video_ingest.hip's colour kernel writes such a plane, cloud_egress.hip's coloured cloud reads it.
 #pragma once
 #include "common.h"
 
@@ -101,4 +102,15 @@ static inline int egress_check_strided(const char* who, const char* name, const 
     PPMS_REQUIRE(((uintptr_t)ptr | (uintptr_t)step | (uintptr_t)frame_stride) % esz == 0,
                  "%s: %s: pointer, pitch and %s must be multiples of the %lld-byte element", who, name, stride_name, (long long)esz);
     return PPMS_OK;
+}
+// ---- host: a colour plane (PPMS_FMT_RGBA8 / PPMS_FMT_BGRA8: 4-byte pixels) of n_frames x rows x cols pixels, as ppms_video_colour_* (the plane it
+// writes) and ppms_cloud_egress_colour (the plane it reads) refuse it; `name`: what the message calls the plane
+static inline int egress_check_colour_plane(const char* who, const char* name, const ppms_egress_plane* p, int n_frames, int64_t rows, int64_t cols) {
+    PPMS_REQUIRE(p && p->ptr, "%s: null %s plane", who, name);
+    PPMS_REQUIRE(p->format == PPMS_FMT_RGBA8 || p->format == PPMS_FMT_BGRA8, "%s: %s.format = %d is neither PPMS_FMT_RGBA8 nor PPMS_FMT_BGRA8", who, name,
+                 p->format);
+    PPMS_REQUIRE(p->reserved == 0, "%s: %s.reserved = %d must be 0", who, name, p->reserved);
+    char stride[64];
+    snprintf(stride, sizeof(stride), "%s.frame_stride", name);
+    return egress_check_strided(who, name, stride, p->ptr, p->frame_stride, &p->pitch, PPMS_FMT_F32, n_frames, rows, cols);      // (4-byte elements)
 }

@@ -1,6 +1,7 @@
 // The video doors of the C ABI (include/ppms.h: ppms_video_ingest_*): decoded or raw stereo video -> the first-layer operands of both encoders.
-// One kernel template over a Source, one check-and-launch path on the host.
-#include "common.h"
+// One kernel template over a Source, one check-and-launch path on the host.  Colour out (ppms_video_colour_*) is a second kernel template over the
+// same Sources behind the same doors and checks: the left view as 4-byte pixels (its plane's check: egress_shared.h).
+#include "egress_shared.h"
 
 namespace {
 
@@ -273,17 +274,73 @@ __global__ __launch_bounds__(256) void video_ingest_kernel(Source source, int N,
     *(bf16x8*)((bf16_t*)dst.lo + od) = ol;
 }
 
+// colour out (ppms_video_colour_*): the left view behind the same Source as 4-byte pixels registered to the egress planes.  Thread = a run of
+// COLOUR_RUN consecutive x of one output row: output pixel (f, y, x) is source pixel (clamp(y + y0), clamp(x + x0)) of image frame0 + f < N (the
+// left view: a Source's right half is never reached), its three levels go through `table` -- uint8, 256 or source.levels() entries, the byte each
+// level stands for, the caller's arithmetic -- held in LDS as the ingest kernel holds its float table, and the pixel is R | G << 8 | B << 16 |
+// 255 << 24 (`bgr`: B and R swapped).  A whole run at a 16-byte aligned address is one 16-byte store, anything else 4-byte stores; every offset is
+// 64-bit; bytes between the rows of a pitched plane are not written.
+constexpr int COLOUR_RUN = 4;
+template <class Source>
+__global__ __launch_bounds__(256) void video_colour_kernel(Source source, int H0, int W0, int frame0, int x0, int y0, int h0, int w0, int bgr,
+                                                           const uint8_t* __restrict__ table, ppms_egress_plane out, int rpr, int64_t total) {
+    const uint8_t* tab;
+    if constexpr (Source::table_by_depth) {                               // 1 << depth bytes of dynamic LDS (sized by the launch)
+        extern __shared__ uint8_t level_bytes[];
+        for (int i = threadIdx.x, n = source.levels(); i < n; i += 256) level_bytes[i] = table[i];
+        tab = level_bytes;
+    } else {
+        __shared__ uint8_t byte_bytes[256];
+        byte_bytes[threadIdx.x] = table[threadIdx.x];
+        tab = byte_bytes;
+    }
+    __syncthreads();
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int xs = (int)(idx % rpr) * COLOUR_RUN;
+    const int64_t row = idx / rpr;                                       // f * h0 + y of the output
+    const int y = (int)(row % h0);
+    const int64_t f = row / h0;
+    const int n = w0 - xs < COLOUR_RUN ? w0 - xs : COLOUR_RUN;           // pixels of this run inside the row
+    const int64_t yy = (int64_t)y + y0;
+    const int sy = yy < 0 ? 0 : (yy > H0 - 1 ? H0 - 1 : (int)yy);       // replicate padding, as the ingest kernel clamps
+    uint32_t px[COLOUR_RUN];
+#pragma unroll
+    for (int j = 0; j < COLOUR_RUN; ++j) {
+        const int64_t xx = (int64_t)xs + (j < n ? j : n - 1) + x0;       // (past the row's end the last pixel again: never stored)
+        const int sx = xx < 0 ? 0 : (xx > W0 - 1 ? W0 - 1 : (int)xx);
+        const uint32_t r = tab[source(frame0 + f, 0, sy, sx)], g = tab[source(frame0 + f, 1, sy, sx)], b = tab[source(frame0 + f, 2, sy, sx)];
+        px[j] = (bgr ? b | r << 16 : r | b << 16) | g << 8 | 0xff000000u;
+    }
+    uint32_t* dst = (uint32_t*)((char*)out.ptr + f * out.frame_stride + (int64_t)y * out.pitch) + xs;
+    if (n == COLOUR_RUN && ((uintptr_t)dst & 15) == 0) {
+        gstore16(dst, __builtin_bit_cast(u32x4, px));
+    } else {
+#pragma unroll
+        for (int j = 0; j < COLOUR_RUN; ++j)
+            if (j < n) gst<uint32_t>(dst + j, px[j]);
+    }
+}
+
 }  // namespace
 
 // ---- host side: every entry point fills one ingest_call, runs its door's checks and goes through ingest_samples() to the one launch ----------
 
 // what all 12 entry points take behind their source: the entry's name for the messages, geometry, table, destinations and stream
+struct colour_call;
 struct ingest_call {
     const char* who;
     int N, H0, W0, pad_left, pad_top, H, W;
     const float* lut;
     ppms_sp dst_fnet, dst_cnet;
     void* stream;
+    const colour_call* colour = nullptr;                                  // a ppms_video_colour_* call: the launch behind the door's checks is the colour kernel's
+};
+// what the 12 colour entry points take behind N, H0, W0 (`lut` of their ingest_call is `table`, for the doors' null checks only)
+struct colour_call {
+    int frame0, n_frames, x0, y0, h0, w0;
+    const uint8_t* table;
+    const ppms_egress_plane* out;
 };
 
 // what every entry point checks about sizes, pads, table and destinations, and its launch
@@ -313,6 +370,27 @@ static int video_ingest_launch(const ingest_call& a, const Source& source) {
     if constexpr (Source::table_by_depth) table_bytes = sizeof(float) * (size_t)source.levels();
     hipLaunchKernelGGL(video_ingest_kernel<Source>, dim3(ceil_div(total, 256)), dim3(256), table_bytes, (hipStream_t)a.stream, source, N, H0, W0, pad_left, pad_top,
                        H, W, a.lut, a.dst_fnet, a.dst_cnet, threads[0], total);
+    return ppms_check_launch(who);
+}
+
+// what every colour entry point checks behind its door -- the table, sizes, the plane, the frame range and the rectangle -- and its launch
+template <class Source>
+static int video_colour_launch(const ingest_call& a, const Source& source) {
+    const char* who = a.who;
+    const colour_call& c = *a.colour;
+    PPMS_REQUIRE(c.table, "%s: null table pointer", who);
+    PPMS_REQUIRE(a.N > 0 && a.H0 > 0 && a.W0 > 0, "%s: N = %d, H0 = %d, W0 = %d must be positive", who, a.N, a.H0, a.W0);
+    PPMS_REQUIRE(c.n_frames > 0, "%s: n_frames = %d must be positive", who, c.n_frames);
+    PPMS_REQUIRE(c.frame0 >= 0 && (int64_t)c.frame0 + c.n_frames <= a.N, "%s: frame0 = %d, n_frames = %d leave the N = %d frames", who, c.frame0, c.n_frames, a.N);
+    PPMS_REQUIRE(c.h0 > 0 && c.w0 > 0, "%s: h0 = %d, w0 = %d must be positive", who, c.h0, c.w0);
+    if (const int rc = egress_check_colour_plane(who, "out", c.out, c.n_frames, c.h0, c.w0)) return rc;
+    const int rpr = (c.w0 + COLOUR_RUN - 1) / COLOUR_RUN;                 // runs per output row
+    const int64_t total = (int64_t)c.n_frames * c.h0 * rpr;
+    PPMS_REQUIRE((total + 255) / 256 <= 0x7fffffff, "%s: %lld threads exceed one grid", who, (long long)total);
+    size_t table_bytes = 0;                                                // dynamic LDS: the byte table of a source that sizes it by depth
+    if constexpr (Source::table_by_depth) table_bytes = (size_t)source.levels();
+    hipLaunchKernelGGL(video_colour_kernel<Source>, dim3(ceil_div(total, 256)), dim3(256), table_bytes, (hipStream_t)a.stream, source, a.H0, a.W0, c.frame0, c.x0,
+                       c.y0, c.h0, c.w0, c.out->format == PPMS_FMT_BGRA8 ? 1 : 0, c.table, *c.out, rpr, total);
     return ppms_check_launch(who);
 }
 
@@ -497,9 +575,10 @@ static int ingest_frames(const ingest_call& a, int depth, const remap_maps* maps
         hs = maps->left->hs, ws = maps->left->ws;
     }
     if (const int rc = check(hs, ws, maps ? "hs" : "H0", maps ? "ws" : "W0")) return rc;
+    const auto behind = [&](const auto& source) { return a.colour ? video_colour_launch(a, source) : video_ingest_launch(a, source); };
     const auto launch = [&](auto inner) {
-        if (!maps) return video_ingest_launch(a, inner);
-        return video_ingest_launch(a, remapped_source<decltype(inner)>{inner, *maps->left, *maps->right, a.N});
+        if (!maps) return behind(inner);
+        return behind(remapped_source<decltype(inner)>{inner, *maps->left, *maps->right, a.N});
     };
     return pick(launch, hs, ws);
 }
@@ -694,6 +773,75 @@ extern "C" int ppms_video_ingest_raw_packed_remap(const ppms_packed_view* left, 
                                                   const ppms_remap_view* lmap, const ppms_remap_view* rmap, INGEST_TAIL) {
     const remap_maps maps{lmap, rmap};
     return ingest_raw_packed(INGEST_CALL("video_ingest_raw_packed_remap"), left, right, fmt, &maps);
+}
+
+// ---- colour out: the same 12 doors in front of video_colour_kernel.  The trailing arguments every colour entry point declares, and the ingest_call
+// (its door's checks read who, N, H0, W0 and the table's null check) with the colour_call they fill
+#define COLOUR_TAIL int N, int H0, int W0, int frame0, int n_frames, int x0, int y0, int h0, int w0, const uint8_t* table, const ppms_egress_plane* out, void* stream
+#define COLOUR_CALL(name)                                                      \
+    const colour_call colour{frame0, n_frames, x0, y0, h0, w0, table, out};    \
+    const ingest_call call{name, N, H0, W0, 0, 0, 0, 0, (const float*)table, ppms_sp{}, ppms_sp{}, stream, &colour}
+
+extern "C" int ppms_video_colour_u8(const uint8_t* left, const uint8_t* right, int64_t frame_stride, COLOUR_TAIL) {
+    COLOUR_CALL("video_colour_u8");
+    return ingest_u8(call, left, right, frame_stride, nullptr);
+}
+extern "C" int ppms_video_colour_u8_remap(const uint8_t* left, const uint8_t* right, int64_t frame_stride, const ppms_remap_view* lmap,
+                                          const ppms_remap_view* rmap, COLOUR_TAIL) {
+    COLOUR_CALL("video_colour_u8_remap");
+    const remap_maps maps{lmap, rmap};
+    return ingest_u8(call, left, right, frame_stride, &maps);
+}
+extern "C" int ppms_video_colour_yuv420(const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m, COLOUR_TAIL) {
+    COLOUR_CALL("video_colour_yuv420");
+    return ingest_yuv420(call, left, right, m, nullptr);
+}
+extern "C" int ppms_video_colour_yuv420_remap(const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m, const ppms_remap_view* lmap,
+                                              const ppms_remap_view* rmap, COLOUR_TAIL) {
+    COLOUR_CALL("video_colour_yuv420_remap");
+    const remap_maps maps{lmap, rmap};
+    return ingest_yuv420(call, left, right, m, &maps);
+}
+extern "C" int ppms_video_colour_yuv(const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m, const ppms_yuv_format* fmt, COLOUR_TAIL) {
+    COLOUR_CALL("video_colour_yuv");
+    return ingest_yuv_format(call, left, right, m, fmt, nullptr);
+}
+extern "C" int ppms_video_colour_yuv_remap(const ppms_yuv_view* left, const ppms_yuv_view* right, const ppms_yuv_matrix* m, const ppms_yuv_format* fmt,
+                                           const ppms_remap_view* lmap, const ppms_remap_view* rmap, COLOUR_TAIL) {
+    COLOUR_CALL("video_colour_yuv_remap");
+    const remap_maps maps{lmap, rmap};
+    return ingest_yuv_format(call, left, right, m, fmt, &maps);
+}
+extern "C" int ppms_video_colour_raw(const ppms_raw_view* left, const ppms_raw_view* right, const ppms_raw_format* fmt, COLOUR_TAIL) {
+    COLOUR_CALL("video_colour_raw");
+    return ingest_raw(call, left, right, fmt, nullptr);
+}
+extern "C" int ppms_video_colour_raw_remap(const ppms_raw_view* left, const ppms_raw_view* right, const ppms_raw_format* fmt, const ppms_remap_view* lmap,
+                                           const ppms_remap_view* rmap, COLOUR_TAIL) {
+    COLOUR_CALL("video_colour_raw_remap");
+    const remap_maps maps{lmap, rmap};
+    return ingest_raw(call, left, right, fmt, &maps);
+}
+extern "C" int ppms_video_colour_yuv_packed(const ppms_packed_view* left, const ppms_packed_view* right, const ppms_yuv_matrix* m,
+                                            const ppms_yuv_packed_format* fmt, COLOUR_TAIL) {
+    COLOUR_CALL("video_colour_yuv_packed");
+    return ingest_yuv_packed(call, left, right, m, fmt, nullptr);
+}
+extern "C" int ppms_video_colour_yuv_packed_remap(const ppms_packed_view* left, const ppms_packed_view* right, const ppms_yuv_matrix* m,
+                                                  const ppms_yuv_packed_format* fmt, const ppms_remap_view* lmap, const ppms_remap_view* rmap, COLOUR_TAIL) {
+    COLOUR_CALL("video_colour_yuv_packed_remap");
+    const remap_maps maps{lmap, rmap};
+    return ingest_yuv_packed(call, left, right, m, fmt, &maps);
+}
+extern "C" int ppms_video_colour_raw_packed(const ppms_packed_view* left, const ppms_packed_view* right, const ppms_raw_packed_format* fmt, COLOUR_TAIL) {
+    COLOUR_CALL("video_colour_raw_packed");
+    return ingest_raw_packed(call, left, right, fmt, nullptr);
+}
+extern "C" int ppms_video_colour_raw_packed_remap(const ppms_packed_view* left, const ppms_packed_view* right, const ppms_raw_packed_format* fmt,
+                                                  const ppms_remap_view* lmap, const ppms_remap_view* rmap, COLOUR_TAIL) {
+    COLOUR_CALL("video_colour_raw_packed_remap");
+    const remap_maps maps{lmap, rmap};
+    return ingest_raw_packed(call, left, right, fmt, &maps);
 }
 
 extern "C" int ppms_packed_struct_sizes(int* view, int* yuv_format, int* raw_format) {

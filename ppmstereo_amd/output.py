@@ -9,8 +9,9 @@ import torch
 from . import _lib as L
 
 _PLANE_FORMATS = {"f32": (L.FMT_F32, torch.float32), "f16": (L.FMT_F16, torch.float16), "u16": (L.FMT_U16, torch.uint16), "u8": (L.FMT_U8, torch.uint8),
-                  "i32": (None, torch.int32)}      # (i32: the compact cloud's counts and pixel indices, no format of a plane)
-_COMPONENTS = {"xyz": 3, "xyzw": 4}                # of a record, by layout
+                  "i32": (None, torch.int32),      # (i32: the compact cloud's counts and pixel indices, no format of a plane)
+                  "rgba8": (L.FMT_RGBA8, torch.uint8), "bgra8": (L.FMT_BGRA8, torch.uint8)}      # (the colour plane: 4 bytes per pixel)
+_COMPONENTS = {"xyz": 3, "xyzw": 4, "xyzrgb": 4}   # of a record, by layout ("xyzrgb": the cloud only)
 
 
 class OutputSpec:
@@ -47,13 +48,23 @@ class OutputSpec:
       cloud_layout     "xyz" | "xyzw", as points_layout.
       cloud_index      True: result key "cloud_index", int32 y * w0 + x of every record, to gather colour or another per-pixel attribute with.
       cloud_capacity   None | int >= 1: records kept per frame.  None: h0 * w0, which can never truncate.  A frame with more valid points keeps
-                       its first ``cloud_capacity`` (records and indices); "cloud_counts" still reports the full number, so the truncation shows."""
+                       its first ``cloud_capacity`` (records and indices); "cloud_counts" still reports the full number, so the truncation shows.
+      colour           None | "rgba8" | "bgra8": result key "colour", uint8 (n, h0, w0, 4) -- the LEFT view as the network saw it (converted, demosaiced,
+                       white-balanced, tone-mapped, rectified), pixel-aligned with every plane above: ``video.colour_bytes`` of the source's left float
+                       video, per pixel R, G, B, 255 or B, G, R, 255 (a little-endian uint32 0xFFRRGGBB, PCL's PointXYZRGB ``rgb``).  One more launch
+                       (ppms_video_colour_*) behind the ingest launch; a float video makes it in torch.  A crop that reaches into the padding sees
+                       the replicate padding.  Beside the organised ``points`` it is that cloud's colour.
+      cloud_layout     also "xyzrgb": C = 4, the fourth 32-bit word of a record is the colour pixel at the record's (y, x), in ``colour``'s byte order
+                       -- copied as an integer (ppms_cloud_egress_colour), never through a float operation.  Needs cloud="f32" and colour=.
+                       ``points_layout="xyzrgb"`` does not exist (ValueError): the "colour" plane beside the points is their colour.
+      colour_plane     True | False: False keeps the device plane as workspace of the "xyzrgb" cloud and leaves "colour" out of the result and of
+                       the device -> host copies.  Only with cloud_layout="xyzrgb"."""
 
     def __init__(self, disparity: str = "f32", depth: Optional[str] = None, uncertainty: Optional[str] = "f32", disp_scale: float = 256.0,
                  focal_px: Optional[float] = None, baseline: Optional[float] = None, depth_scale: float = 1000.0, min_disp: float = 2.0 ** -8,
                  *, points: Optional[str] = None, points_layout: str = "xyz", Q=None, max_uncertainty: Optional[float] = None,
                  max_depth: Optional[float] = None, cloud: Optional[str] = None, cloud_layout: str = "xyz", cloud_index: bool = False,
-                 cloud_capacity: Optional[int] = None):
+                 cloud_capacity: Optional[int] = None, colour: Optional[str] = None, colour_plane: bool = True):
         if disparity not in ("f32", "f16", "u16"):
             raise ValueError(f"OutputSpec: disparity = {disparity!r}; one of 'f32', 'f16', 'u16'")
         if depth not in (None, "f32", "f16", "u16"):
@@ -86,8 +97,9 @@ class OutputSpec:
         def records(name, needs, fmt, layout):           # what either record output, points or cloud, asks of its options and of the spec
             if fmt not in (None, "f32", "f16"):
                 raise ValueError(f"OutputSpec: {name} = {fmt!r}; None, 'f32' or 'f16'")
-            if layout not in tuple(_COMPONENTS):
-                raise ValueError(f"OutputSpec: {name}_layout = {layout!r}; 'xyz' or 'xyzw'")
+            if layout not in (("xyz", "xyzw", "xyzrgb") if name == "cloud" else ("xyz", "xyzw")):
+                raise ValueError(f"OutputSpec: {name}_layout = {layout!r}; 'xyz' or 'xyzw'" + (" or 'xyzrgb'" if name == "cloud" else
+                                 " (colour per point: the 'colour' plane beside the points, or cloud_layout='xyzrgb')"))
             if fmt is not None and self.Q is None:
                 raise ValueError(f"OutputSpec: {needs} Q, the 4x4 reprojection matrix of the rig's calibration (OutputSpec.q_matrix builds one)")
             if fmt is not None and not math.isfinite(self.min_disp):
@@ -102,6 +114,15 @@ class OutputSpec:
         if cloud is None and (cloud_layout != "xyz" or cloud_index or cloud_capacity is not None):
             raise ValueError("OutputSpec: cloud_layout, cloud_index and cloud_capacity describe the cloud; without cloud= they have no meaning")
         self.cloud, self.cloud_layout, self.cloud_index, self.cloud_capacity = cloud, cloud_layout, cloud_index, cloud_capacity
+        if colour not in (None, "rgba8", "bgra8"):
+            raise ValueError(f"OutputSpec: colour = {colour!r}; None, 'rgba8' or 'bgra8'")
+        if not isinstance(colour_plane, bool):
+            raise ValueError(f"OutputSpec: colour_plane = {colour_plane!r}; True or False")
+        if cloud_layout == "xyzrgb" and (cloud != "f32" or colour is None):
+            raise ValueError("OutputSpec: cloud_layout = 'xyzrgb' needs cloud = 'f32' (the colour pixel is the record's fourth 32-bit word) and colour=")
+        if not colour_plane and cloud_layout != "xyzrgb":
+            raise ValueError("OutputSpec: colour_plane = False keeps the colour plane as the 'xyzrgb' cloud's workspace; without cloud_layout = 'xyzrgb' it has no meaning")
+        self.colour, self.colour_plane = colour, colour_plane
         gate_u, gate_z = (None if g is None else f32(g) for g in (max_uncertainty, max_depth))
         if gate_u is not None and math.isnan(gate_u):
             raise ValueError("OutputSpec: max_uncertainty is NaN")
@@ -130,20 +151,20 @@ class OutputSpec:
         return self.points is not None or self.max_uncertainty is not None or self.max_depth is not None
 
     def formats(self) -> Dict[str, str]:
-        """{result key: format} of the requested planes, in the order disparity, depth, uncertainties, points, and of the compact cloud's arrays:
-        cloud, cloud_counts, cloud_index."""
+        """{result key: format} of the requested planes, in the order disparity, depth, uncertainties, points, colour (unless colour_plane is
+        False), and of the compact cloud's arrays: cloud, cloud_counts, cloud_index."""
         cloud = self.cloud is not None
         named = (("disparity", self.disparity), ("depth", self.depth), ("uncertainties", self.uncertainty), ("points", self.points),
-                 ("cloud", self.cloud), ("cloud_counts", "i32" if cloud else None), ("cloud_index", "i32" if cloud and self.cloud_index else None))
+                 ("colour", self.colour if self.colour_plane else None), ("cloud", self.cloud), ("cloud_counts", "i32" if cloud else None), ("cloud_index", "i32" if cloud and self.cloud_index else None))
         return {k: f for k, f in named if f is not None}
 
-    def empty(self, n: int, h0: int, w0: int, device, pin_memory: bool = False) -> Dict[str, torch.Tensor]:
+    def empty(self, n: int, h0: int, w0: int, device, pin_memory: bool = False, without=()) -> Dict[str, torch.Tensor]:
         """Dense (n, 1, h0, w0) tensors of the requested planes' dtypes; "points": (n, h0, w0, C); "cloud": (n, capacity, C), "cloud_counts": (n,)
-        and "cloud_index": (n, capacity) int32, capacity = cloud_capacity or h0 * w0."""
+        and "cloud_index": (n, capacity) int32, capacity = cloud_capacity or h0 * w0; "colour": uint8 (n, h0, w0, 4)."""
         cap = h0 * w0 if self.cloud_capacity is None else self.cloud_capacity
-        special = {"points": (n, h0, w0, self.points_components), "cloud": (n, cap, self.cloud_components), "cloud_counts": (n,), "cloud_index": (n, cap)}
+        special = {"points": (n, h0, w0, self.points_components), "colour": (n, h0, w0, 4), "cloud": (n, cap, self.cloud_components), "cloud_counts": (n,), "cloud_index": (n, cap)}
         return {k: torch.empty(special.get(k, (n, 1, h0, w0)), dtype=_PLANE_FORMATS[f][1], device=device, pin_memory=pin_memory)
-                for k, f in self.formats().items()}
+                for k, f in self.formats().items() if k not in without}      # (without: keys the caller holds tensors for already)
 
     @staticmethod
     def _plane(t: Optional[torch.Tensor], row_dim: int, fmt: Optional[str]) -> L.EgressPlane:
@@ -179,7 +200,7 @@ class OutputSpec:
                        0 if idx is None else idx.stride(0) * 4, ptr(cnt), ptr(workspace), 0 if workspace is None else workspace.numel(), q,
                        self.min_disp, max_uncertainty, max_depth, _PLANE_FORMATS[self.cloud or "f32"][0], self.cloud_components, 0)
 
-    def reference(self, d: torch.Tensor, u: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    def reference(self, d: torch.Tensor, u: Optional[torch.Tensor] = None, colour: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """The arithmetic of ppms_disparity_egress / ppms_scene_egress in plain torch, on CPU or device tensors of any shape: d = a float32 (signed)
         disparity, u = a float32 uncertainty at the same resolution -> the requested planes under forward_batch_test's keys.  With points, d has at
         least two dimensions and its last two are the pixel grid (row y, column x of the cropped plane); "points" has d's shape with the components
@@ -188,7 +209,16 @@ class OutputSpec:
         With cloud, every dimension in front of the pixel grid counts frames, N in all, and three keys are made of the organised points P and their
         validity in the cloud's format and layout: "cloud", a list of N (count, C) tensors P[f][valid[f]]; "cloud_index", a list of N (count,) int32
         y * w0 + x, increasing; "cloud_counts", (N,) int64 -- the whole cloud, whatever cloud_capacity: the definition ppms_cloud_egress is tested
-        against."""
+        against.
+        colour: the uint8 (..., h, w, 4) colour plane of the same pixels (``video.colour_bytes`` of the source's left float video; the spec's
+        ``colour`` names its byte order).  A spec with colour= returns it under "colour" (unless colour_plane is False), and the "xyzrgb" cloud's
+        fourth component is that plane's 32 bits per pixel viewed as float32 -- the definition ppms_cloud_egress_colour is tested against.  A spec
+        that needs it and gets none raises ValueError."""
+        if self.colour is not None:
+            if colour is None:
+                raise ValueError("OutputSpec.reference: the spec has colour= and no colour plane was given")
+            if colour.dtype != torch.uint8 or colour.dim() < 3 or tuple(colour.shape[-3:]) != (*d.shape[-2:], 4):
+                raise ValueError(f"OutputSpec.reference: colour must be uint8 (..., {d.shape[-2]}, {d.shape[-1]}, 4), got {colour.dtype} {tuple(colour.shape)}")
         const = lambda x: torch.full((), x, dtype=torch.float32, device=d.device)
 
         def quant(v, scale, top, fmt):                       # min(top, rint(v * scale)), NaN -> 0: one fp32 product, ties to even
@@ -218,6 +248,9 @@ class OutputSpec:
                 out["depth"] = z if self.depth == "f32" else z.to(torch.float16)
         if self.uncertainty is not None:
             out["uncertainties"] = u if self.uncertainty == "f32" else quant(u, 255.0, 255.0, "u8")
+        with_colour = self.colour is not None and self.colour_plane       # ("colour" stands behind "points", as in ``formats``)
+        if with_colour and self.points is None:
+            out["colour"] = colour
         if self.points is not None or self.cloud is not None:
             if d.dim() < 2:
                 raise ValueError(f"OutputSpec.reference: points take the pixel grid from d's last two dimensions, got {tuple(d.shape)}")
@@ -237,10 +270,17 @@ class OutputSpec:
 
             if self.points is not None:
                 out["points"] = organised(self.points, self.points_layout)
-            if self.cloud is not None:                   # per frame (every dimension in front of the pixel grid counts frames): the valid records
-                pts = organised(self.cloud, self.cloud_layout)
+                if with_colour:
+                    out["colour"] = colour
+            if self.cloud is not None:                  # per frame (every dimension in front of the pixel grid counts frames): the valid records
+                if self.cloud_layout == "xyzrgb":        # X, Y, Z and the colour pixel's 32 bits, joined and selected as int32 words: no float
+                    xyz32 = organised("f32", "xyz").contiguous().view(torch.int32)                 # operation ever sees the colour word
+                    words = colour.contiguous().view(torch.int32).reshape(*xyz32.shape[:-1], 1)
+                    pts = torch.cat([xyz32, words], dim=-1)
+                else:
+                    pts = organised(self.cloud, self.cloud_layout)
                 pts, keep = pts.reshape(-1, pts.shape[-3] * pts.shape[-2], pts.shape[-1]), valid.reshape(-1, d.shape[-2] * d.shape[-1])
-                out["cloud"] = [p[k] for p, k in zip(pts, keep)]
+                out["cloud"] = [p[k].view(torch.float32) if p.dtype == torch.int32 else p[k] for p, k in zip(pts, keep)]
                 out["cloud_index"] = [k.nonzero().flatten().to(torch.int32) for k in keep]      # y * w0 + x, increasing
                 out["cloud_counts"] = keep.sum(dim=1)    # int64: the full numbers, whatever cloud_capacity
         return out
@@ -254,21 +294,46 @@ class _EgressCall:
         if not isinstance(spec, OutputSpec):
             raise TypeError(f"output must be an OutputSpec, got {type(spec).__name__}")
         self.spec, self.crop, self.frames = spec, (None if crop is None else tuple(int(x) for x in crop)), (None if frames is None else tuple(int(x) for x in frames))
+        self.colour: Optional[torch.Tensor] = None               # the colour plane of this call's region, written in front of the encoders (``fill_colour``)
+
+    def region(self, T: int, H: int, W: int):
+        """(pad_left, pad_top, h0, w0, f0, f1) of this call in a window of T padded frames H x W."""
+        pad_left, pad_top, h0, w0 = (0, 0, H, W) if self.crop is None else self.crop
+        f0, f1 = (0, T) if self.frames is None else self.frames
+        if not 0 <= f0 < f1 <= T:
+            raise ValueError(f"output: frames = {(f0, f1)} is no range inside the window's {T} frames")
+        return pad_left, pad_top, h0, w0, f0, f1
+
+    def fill_colour(self, source, T: int, H: int, W: int, pad_left: int, pad_top: int) -> None:
+        """A spec with colour=: allocates the (n, h0, w0, 4) colour plane of this call's region on the current stream and enqueues ``source.colour``
+        there (one launch; a float video: torch ops).  ``pad_left`` / ``pad_top``: what the ingest of the T frames to H x W put in front, so the
+        crop's pixel (y, x) is source pixel (y + crop_top - pad_top, x + crop_left - pad_left), clamped: the replicate padding the network saw."""
+        if self.spec.colour is None:
+            return
+        crop_left, crop_top, h0, w0, f0, f1 = self.region(T, H, W)
+        self.colour = torch.empty((f1 - f0, h0, w0, 4), dtype=torch.uint8, device=source.device)
+        source.colour(self.colour, f0, f1 - f0, crop_left - pad_left, crop_top - pad_top, h0, w0, self.spec.colour)
 
     def launch(self, eng) -> Dict[str, torch.Tensor]:
         """Allocates the planes on the current stream and enqueues the launch there, behind the engine's last iteration.  A spec with a cloud adds
         "cloud" (n, capacity, C), "cloud_counts" (n,) and "cloud_index" (n, capacity) when asked; rows of "cloud" and "cloud_index" past
-        min(count, capacity) of their frame are unspecified (never written)."""
-        pad_left, pad_top, h0, w0 = (0, 0, 4 * eng.h, 4 * eng.w) if self.crop is None else self.crop
-        f0, f1 = (0, eng.T) if self.frames is None else self.frames
-        if not 0 <= f0 < f1 <= eng.T:
-            raise ValueError(f"output: frames = {(f0, f1)} is no range inside the window's {eng.T} frames")
-        planes = self.spec.empty(f1 - f0, h0, w0, eng.FLOW_OUT.device)
-        out = self.spec.scene_struct(planes) if self.spec.scene else self.spec.struct(planes)      # ppms_scene_egress / ppms_disparity_egress
+        min(count, capacity) of their frame are unspecified (never written).  A spec with colour= puts the plane ``fill_colour`` wrote into the
+        result ("colour"; not with colour_plane=False) and hands it to the "xyzrgb" cloud's launches (ppms_cloud_egress_colour)."""
+        spec = self.spec
+        pad_left, pad_top, h0, w0, f0, f1 = self.region(eng.T, 4 * eng.h, 4 * eng.w)
+        planes = spec.empty(f1 - f0, h0, w0, eng.FLOW_OUT.device, without=("colour",))
+        if spec.colour is not None:
+            if self.colour is None or tuple(self.colour.shape) != (f1 - f0, h0, w0, 4):
+                raise RuntimeError("output: the spec has colour= and no colour plane of this call's region was written (fill_colour) in front of the cascade")
+            self.colour.record_stream(torch.cuda.current_stream())      # allocated on the caller's stream, read by the cloud's launch here
+            if spec.colour_plane:
+                planes = {k: (self.colour if k == "colour" else planes[k]) for k in spec.formats()}
+        out = spec.scene_struct(planes) if spec.scene else spec.struct(planes)      # ppms_scene_egress / ppms_disparity_egress
         eng.egress(out, f0, f1 - f0, pad_left, pad_top, h0, w0)
-        if self.spec.cloud is not None:                          # ppms_cloud_egress: two more launches behind the planes' one, on the same stream
+        if spec.cloud is not None:                               # ppms_cloud_egress: two more launches behind the planes' one, on the same stream
             workspace = torch.empty(L.load().ppms_cloud_egress_workspace(f1 - f0, h0, w0), dtype=torch.int32, device=eng.FLOW_OUT.device)
-            eng.egress(self.spec.cloud_struct(planes, workspace), f0, f1 - f0, pad_left, pad_top, h0, w0)
+            colour = spec._plane(self.colour, 1, spec.colour) if spec.cloud_layout == "xyzrgb" else None
+            eng.egress(spec.cloud_struct(planes, workspace), f0, f1 - f0, pad_left, pad_top, h0, w0, colour)
         return planes
 
 

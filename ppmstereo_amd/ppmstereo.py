@@ -23,7 +23,7 @@ from .output import OutputSpec, _EgressCall, egress_plan  # noqa: F401  (the pub
 from .video import (InputPadder, RawFrames, RawStereoVideo, RectifyMap, StereoRectifier, YUVFrames, YUVStereoVideo, byte_lut,  # noqa: F401
                     level_lut, shard_windows, window_plan, yuv_matrix)
 from .video import PackedRawFrames, PackedRawStereoVideo, PackedYUVFrames, PackedYUVStereoVideo  # noqa: F401
-from .video import _ByteSource, stereo_source
+from .video import _ByteSource, colour_bytes, colour_lut, stereo_source  # noqa: F401
 
 
 def interp(x: torch.Tensor, size) -> torch.Tensor:
@@ -583,6 +583,11 @@ class PPMStereo(PPMStereoHotPath):
         host synchronisation: "cloud" (1, n, capacity, C), the valid points of each frame in row-major pixel order from row 0 on, "cloud_counts"
         (1, n) int32, their numbers, and with ``cloud_index=True`` "cloud_index" (1, n, capacity) int32, y * W0 + x of every record.  Rows past
         min(count, capacity) of a frame are unspecified (never written); a count above the capacity tells of a truncated frame.
+        With ``OutputSpec(colour="rgba8" | "bgra8")`` the dict also has "colour", uint8 (1, n, H0, W0, 4): the left view as the network saw it
+        (converted, demosaiced, tone-mapped, rectified; ``video.colour_bytes`` of the source's left float video), pixel-aligned with the planes --
+        one launch (ppms_video_colour_*) directly behind the ingest launch and in front of both encoders; float images make it in torch.  A crop
+        that reaches into the padding sees the replicate padding.  ``cloud_layout="xyzrgb"`` puts that pixel's 32 bits into the fourth word of
+        every record of the compact cloud (ppms_cloud_egress_colour); ``colour_plane=False`` then leaves "colour" out of the dict.
         rectify=None and output=None (the defaults) add no launch to the calls above."""
         if flow_init is not None:
             raise NotImplementedError("flow_init: the reference's own path for it reads undefined state (ppmstereo.py:691-693, 763)")
@@ -627,11 +632,15 @@ class PPMStereo(PPMStereoHotPath):
                 # bytes -> the operands of fnet's conv1 and cnet's stem, one launch on the caller's stream (ordered before the side stream's wait)
                 fplan, cplan = self.fnet.plan(2 * n, h, w, dev), self.cnet.plan(n, h, w, dev)
                 source.ingest(fplan.s0_view(), cplan.s0_view(), pad_left, pad_top, h, w)
+                if egress is not None:                          # colour=: one launch directly behind the ingest launch, in front of both encoders
+                    egress.fill_colour(source, T, h, w, pad_left, pad_top)
                 run_fnet = lambda: torch.split(fplan.run_filled(), n, dim=0)
                 run_cnet = cplan.run_filled
                 held = source.held()
             else:                                              # float images, or encoder callables of the caller: pad, normalise, encoders
                 im1, im2 = source.float_views()
+                if egress is not None:                          # colour=: in front of the encoders here too (bytes: the kernel; a float video: torch)
+                    egress.fill_colour(source, T, h, w, pad_left, pad_top)
                 if padder is not None:
                     im1, im2 = padder.pad(im1, im2)
                 im1, im2 = ((2 * (x / 255.0) - 1.0).contiguous() for x in (im1, im2))
@@ -719,6 +728,10 @@ class PPMStereo(PPMStereoHotPath):
         the organised cloud at its valid pixels --, "cloud_index" (``cloud_index=True``) likewise (…,) int32 y * W + x, "cloud_counts" (N,) int64, the
         untruncated numbers.  Per window the counts are copied to the host first and then only min(count_f, capacity) records of each kept frame:
         by construction count_f * C * element bytes cross the bus where the organised cloud moves H * W * C; nothing about time is measured here.
+        ``OutputSpec(colour="bgra8", ...)``: "colour" is a pinned uint8 (N, H, W, 4) -- the left view as the network saw it, registered to every other
+        plane, 4 bytes per pixel of the kept frames, from one more launch per window (ppms_video_colour_*) behind the ingest launch.  With
+        ``cloud="f32", cloud_layout="xyzrgb"`` the fourth word of a cloud record is that pixel (XYZRGB: 16 bytes per valid point, where "xyz" with
+        ``cloud_index`` moves 12 + 4 and leaves the gather to the host); ``colour_plane=False`` keeps the plane on the device.  Nothing is timed.
         rectify: a ``StereoRectifier`` -- the video holds the RAW frames of an unrectified rig, (N, 2, 3, Hs, Ws) uint8 or a ``YUVStereoVideo`` of
         its source size Hs x Ws.  Each window's raw bytes are copied as above, the maps once per device (6 bytes per rectified pixel and view):
         the bits of the call on the uint8 video of ``RectifyMap.apply_u8``.  H x W of the results (and of the ``InputPadder``) is the rectified

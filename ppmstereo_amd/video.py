@@ -1,9 +1,11 @@
 """Video into the model: what ``PPMStereo.forward`` / ``forward_batch_test`` accept beside the reference's float tensors (uint8 and decoded
 YUV frames of 8, 10 or 12 bits with 4:2:0 / 4:2:2 / 4:4:4 chroma, a sensor's Bayer-mosaic or monochrome frames, both in the packed formats cameras put
 on the wire (YUYV, Y210, v210, RAW10p / RAW12p), unrectified frames with a ``StereoRectifier``), the one private family of sources that stands for all of them behind the front doors
-(``stereo_source``) and the sliding-window schedule.  Nothing here knows the model.  (What the doors hand back: output.py.)"""
+(``stereo_source``) and the sliding-window schedule.  A source also hands the left view back as colour bytes (``colour``; ``colour_bytes`` is the
+definition), for output.py's "colour" plane.  Nothing here knows the model.  (What the doors hand back: output.py.)"""
 from __future__ import annotations
 
+import ctypes as C
 from typing import Dict, Optional
 
 import torch
@@ -110,6 +112,47 @@ def byte_lut(device) -> torch.Tensor:
     return level_lut(device, 8)
 
 
+_COLOUR_ORDERS = {"rgba8": ((0, 1, 2), L.FMT_RGBA8), "bgra8": ((2, 1, 0), L.FMT_BGRA8)}      # order: (channels of the first three bytes, PPMS_FMT_*)
+_COLOUR_LUT: Dict[tuple, torch.Tensor] = {}                                  # (device, depth) -> table
+
+
+def _check_colour_order(who: str, order) -> str:
+    if order not in _COLOUR_ORDERS:
+        raise ValueError(f"{who}: colour order {order!r}; one of {sorted(_COLOUR_ORDERS)}")
+    return order
+
+
+def _to_bytes(values: torch.Tensor) -> torch.Tensor:
+    """clamp(rint(values), 0, 255) as uint8: ties to even, NaN -> 0 -- the colour byte a float value in [0, 255] stands for."""
+    r = torch.round(values.float())
+    return torch.where(torch.isnan(r), torch.zeros_like(r), r).clamp(0.0, 255.0).to(torch.uint8)
+
+
+def colour_bytes(float_left: torch.Tensor, order: str = "rgba8") -> torch.Tensor:
+    """The colour plane of a float video: ``float_left`` (..., 3, H, W) in [0, 255] (a source's ``float_views()[0]``: the left view as the network is
+    defined on it) -> uint8 (..., H, W, 4), per pixel R, G, B, 255 ("rgba8") or B, G, R, 255 ("bgra8": read as a little-endian uint32 0xFFRRGGBB, the
+    packing of PCL's PointXYZRGB).  A byte is clamp(rint(value), 0, 255), ties to even, NaN -> 0.  The definition the colour kernels are tested
+    against, and the float path's own arithmetic."""
+    channels, _ = _COLOUR_ORDERS[_check_colour_order("colour_bytes", order)]
+    if not torch.is_tensor(float_left) or float_left.dim() < 3 or float_left.shape[-3] != 3:
+        raise ValueError(f"colour_bytes: a video (..., 3, H, W) expected, got {tuple(float_left.shape) if torch.is_tensor(float_left) else type(float_left).__name__}")
+    c = _to_bytes(float_left)
+    return torch.stack([c[..., i, :, :] for i in channels] + [torch.full_like(c[..., 0, :, :], 255)], dim=-1)
+
+
+def colour_lut(device, depth: int = 8) -> torch.Tensor:
+    """uint8 [2^depth] on ``device`` (a GPU, or the host): the colour byte of every RGB level of ``depth`` bits -- ``_to_bytes`` of the float value
+    the level stands for on the float path on the same device (depth 8: the level itself).  What the colour kernel looks levels up in.  Built once
+    per (device, depth) and kept (on a GPU the host waits for it once)."""
+    depth = _check_depth("colour_lut", depth)
+    dev = _moved_to(device)
+    if (dev, depth) not in _COLOUR_LUT:
+        _COLOUR_LUT[dev, depth] = _to_bytes(_levels_to_float(torch.arange(1 << depth, dtype=torch.float32, device=dev), depth)).contiguous()
+        if dev.type == "cuda":
+            torch.cuda.current_stream(dev).synchronize()         # later calls may read it from any stream
+    return _COLOUR_LUT[dev, depth]
+
+
 class _Frames:
     """What ``YUVFrames``, ``RawFrames`` and the packed frames share: N frames of one view, sliced by frame range only and moved as a whole.  A subclass has ``n``,
     ``_tensors()`` (its planes; the first names the device), ``_like(*planes)`` and ``_moved(device)`` -- and for its front door ``_entry`` (the
@@ -198,6 +241,9 @@ class _YUVColour:
 
     def table(self, device) -> torch.Tensor:
         return level_lut(device, self.depth)
+
+    def colour_table(self, device) -> torch.Tensor:
+        return colour_lut(device, self.depth)
 
     def levels_to_float(self, levels: torch.Tensor) -> torch.Tensor:
         return _levels_to_float(levels, self.depth)
@@ -414,6 +460,7 @@ class _RawFormat:
         self.gain_q = tuple(round(g * (1 << _RAW_SHIFT)) for g in gains)
         self._tone_on: Dict[torch.device, torch.Tensor] = {}
         self._table_on: Dict[torch.device, torch.Tensor] = {}
+        self._colour_on: Dict[torch.device, torch.Tensor] = {}
 
     def same_format(self, other: "_RawFormat") -> bool:
         """One pattern, depth, black level, white balance and tone curve."""
@@ -450,6 +497,18 @@ class _RawFormat:
             torch.cuda.current_stream(dev).synchronize()         # later calls may read it from any stream
         return self._table_on[dev]
 
+    def colour_table(self, device) -> torch.Tensor:
+        """uint8 [2^depth] on ``device`` (a GPU, or the host): the colour byte of every level, what the colour kernel looks up.  Without a tone
+        curve ``colour_lut``'s tensor; with one clamp(rint(tone), 0, 255).  Built once per device and kept with the frames."""
+        if self.tone is None:
+            return colour_lut(device, self.depth)
+        dev = _moved_to(device)
+        if dev not in self._colour_on:
+            self._colour_on[dev] = _to_bytes(self.tone_on(dev)).contiguous()
+            if dev.type == "cuda":
+                torch.cuda.current_stream(dev).synchronize()     # later calls may read it from any stream
+        return self._colour_on[dev]
+
 
 class _RawSensor:
     """What ``RawFrames`` and ``PackedRawFrames`` share: one ``_RawFormat``, whose ``pattern``, ``black``, ``gains``, ``gain_q`` and ``tone`` are
@@ -468,6 +527,10 @@ class _RawSensor:
     def table(self, device) -> torch.Tensor:
         """The frames' own level table on ``device`` (``_RawFormat.table``), built once and shared by every slice, half and copy."""
         return self._format.table(device)
+
+    def colour_table(self, device) -> torch.Tensor:
+        """The frames' own colour-byte table on ``device`` (``_RawFormat.colour_table``), shared likewise."""
+        return self._format.colour_table(device)
 
 
 class RawFrames(_RawSensor, _Frames):
@@ -1055,6 +1118,19 @@ class _FloatViews:
         """The two float32 (n, 3, H0, W0) videos for encoder callables of the caller."""
         return self.left, self.right
 
+    def colour(self, plane: torch.Tensor, frame0: int, n: int, x0: int, y0: int, h0: int, w0: int, order: str) -> None:
+        """``_ByteSource.colour`` in torch, no kernel: ``colour_bytes`` of the left frames at the clamped coordinates, on the current stream."""
+        _check_colour_plane(plane, n, h0, w0)
+        ys = (torch.arange(h0, device=self.device) + y0).clamp_(0, self.size[0] - 1)
+        xs = (torch.arange(w0, device=self.device) + x0).clamp_(0, self.size[1] - 1)
+        plane.copy_(colour_bytes(self.left[frame0:frame0 + n][:, :, ys][:, :, :, xs], order))
+
+
+def _check_colour_plane(plane: torch.Tensor, n: int, h0: int, w0: int) -> None:
+    if not torch.is_tensor(plane) or plane.dtype != torch.uint8 or tuple(plane.shape) != (n, h0, w0, 4) or plane.stride(3) != 1 or (w0 > 1 and plane.stride(2) != 4):
+        raise ValueError(f"colour: the plane must be uint8 ({n}, {h0}, {w0}, 4) with dense pixels, got "
+                         f"{(plane.dtype, tuple(plane.shape), plane.stride()) if torch.is_tensor(plane) else type(plane).__name__}")
+
 
 class _ByteSource:
     """Decoded bytes of both views, optionally the RAW frames of a ``StereoRectifier`` (``size`` is then its rectified size): with this package's
@@ -1079,6 +1155,20 @@ class _ByteSource:
         """The level table of the launch: the float path's normalisation of every level of the source's depth (a source with a table of its own
         answers with that)."""
         return level_lut(self.device, self.depth)
+
+    def colour(self, plane: torch.Tensor, frame0: int, n: int, x0: int, y0: int, h0: int, w0: int, order: str) -> None:
+        """One launch on the current stream (the door's ppms_video_colour_* twin): ``plane`` uint8 (n, h0, w0, 4) on the device receives the left
+        view as the network sees it -- pixel (f, y, x) is pixel (clamp(y + y0), clamp(x + x0)) of left frame frame0 + f, so a rectangle that
+        reaches past the frame sees the replicate padding -- as "rgba8" or "bgra8" pixels: ``colour_bytes(float_views()[0], order)``, the same bits."""
+        _check_colour_plane(plane, n, h0, w0)
+        out = L.EgressPlane(plane.data_ptr(), plane.stride(0), plane.stride(1), _COLOUR_ORDERS[_check_colour_order("colour", order)][1], 0)
+        entry = self._entry.replace("ppms_video_ingest_", "ppms_video_colour_")
+        L.check(getattr(L.load(), entry)(*self._frames(), *self._maps, self.n, *self.size, frame0, n, x0, y0, h0, w0,
+                                         self._colour_table().data_ptr(), C.byref(out), L.stream_ptr()))
+
+    def _colour_table(self) -> torch.Tensor:
+        """The byte table of the colour launch: ``colour_lut``'s of the source's depth (a source with a table of its own answers with that)."""
+        return colour_lut(self.device, self.depth)
 
     def held(self):
         """The tensors the launch reads (for record_stream)."""
@@ -1125,6 +1215,9 @@ class _FramePlanes(_ByteSource):
 
     def _table(self) -> torch.Tensor:
         return self.video.left.table(self.device)
+
+    def _colour_table(self) -> torch.Tensor:
+        return self.video.left.colour_table(self.device)
 
     def float_views(self):
         v = self.video

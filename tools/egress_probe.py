@@ -17,7 +17,11 @@ The compact-cloud A/B, both sides on this tree, on the same device video and wit
 pts[valid] in torch on the device and that tensor's copy to the host; B = forward(..., output=spec with cloud) -- ppms_cloud_egress's two launches
 behind the planes' one --, the counts' copy to the host and then count records per frame.  The two compact clouds are compared bit for bit, and
 the valid fraction of the pixels is printed with the times: the bytes B saves are that fraction's complement, the times are what this run
-measured on this video and nothing more."""
+measured on this video and nothing more.
+    python tools/egress_probe.py --colour [--runs 12]
+The coloured-cloud A/B, both sides on this tree with colour="bgra8": A = the "xyz" cloud with its indices, then rgba.view(-1)[cloud_index] in torch
+on the device, joined to the records, and their copy to the host; B = cloud_layout="xyzrgb" (ppms_cloud_egress_colour), colour_plane=False, and
+the same copy.  The records are compared as int32 words.  No claim rests on its times."""
 import argparse
 import os
 import statistics
@@ -26,7 +30,8 @@ import sys
 import time
 
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LAUNCHES = ("ppms_convex_upsample", "ppms_convex_upsample_3d", "ppms_bilinear", "ppms_disparity_egress", "ppms_scene_egress", "ppms_cloud_egress")
+LAUNCHES = ("ppms_convex_upsample", "ppms_convex_upsample_3d", "ppms_bilinear", "ppms_disparity_egress", "ppms_scene_egress", "ppms_cloud_egress",
+            "ppms_cloud_egress_colour")
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ worker
@@ -75,6 +80,27 @@ def worker(tree: str, side: str):
                 def call():
                     pts = m.forward(i1, i2, iters=iters, test_mode=True, output=spec)["points"][0]
                     return {"points": pts[~pts[..., 2].isnan()].cpu()}
+            state["call"] = call
+        if side.startswith("colour"):                    # (the coloured cloud under the key "points": one int32 (records, 4) tensor of words, frame after frame)
+            gates = dict(uncertainty=None, colour="bgra8", cloud="f32", Q=P.OutputSpec.q_matrix(721.5377, 0.54, W / 2, H / 2), max_uncertainty=0.5, max_depth=50.0)
+            i1, i2 = (state["video"][:, k][None].to(torch.uint8).to(dev) for k in (0, 1))
+            if side == "colour":
+                spec = P.OutputSpec(cloud_layout="xyzrgb", colour_plane=False, **gates)
+
+                def call():
+                    out = m.forward(i1, i2, iters=iters, test_mode=True, output=spec)
+                    counts = out["cloud_counts"][0].cpu().tolist()
+                    return {"points": torch.cat([out["cloud"][0, f, :c].cpu() for f, c in enumerate(counts)]).view(torch.int32)}
+            else:
+                spec = P.OutputSpec(cloud_index=True, **gates)
+
+                def call():
+                    out = m.forward(i1, i2, iters=iters, test_mode=True, output=spec)
+                    counts = out["cloud_counts"][0].cpu().tolist()
+                    words = out["colour"][0].view(torch.int32).flatten(1)
+                    recs = [torch.cat([out["cloud"][0, f, :c].view(torch.int32), words[f][out["cloud_index"][0, f, :c].long()][:, None]], dim=1).cpu()
+                            for f, c in enumerate(counts)]
+                    return {"points": torch.cat(recs)}
             state["call"] = call
         for _ in range(3):
             state["call"]()
@@ -129,7 +155,8 @@ def worker(tree: str, side: str):
             say("shape", ";".join(f"{k}:{str(v.dtype).replace('torch.', '')}{list(v.shape)}".replace(" ", "") for k, v in o.items() if torch.is_tensor(v)))
         elif cmd[0] == "digest":
             import hashlib
-            say("digest", hashlib.sha256(state["out"]["points"].nan_to_num(nan=-1.0).numpy().tobytes()).hexdigest()[:16])
+            pts = state["out"]["points"]                 # (float points: NaN = NaN; the coloured cloud's int32 words as they are)
+            say("digest", hashlib.sha256((pts.nan_to_num(nan=-1.0) if pts.is_floating_point() else pts).numpy().tobytes()).hexdigest()[:16])
         elif cmd[0] == "count":
             count()
         elif cmd[0] == "quit":
@@ -170,13 +197,19 @@ def main():
     ap.add_argument("--windows", action="store_true", help="also T = 30 at kernel_size = 20: three windows through the ClipPipeline")
     ap.add_argument("--points", action="store_true", help="the point-cloud A/B instead: the reprojection in torch on the device against ppms_scene_egress")
     ap.add_argument("--cloud", action="store_true", help="the compact-cloud A/B instead: organised points and pts[valid] in torch against ppms_cloud_egress")
+    ap.add_argument("--colour", action="store_true", help='the coloured-cloud A/B instead: "xyz" records, indices and a gather of the colour plane in torch against "xyzrgb"')
     ap.add_argument("--worker", default=None)
     ap.add_argument("--tree", default=HERE)
     a = ap.parse_args()
     if a.worker:
         return worker(os.path.abspath(a.tree), a.worker)
     ptree = os.path.abspath(a.parent) if a.parent else HERE
-    if a.cloud:
+    if a.colour:
+        A = Side('forward(output=OutputSpec(colour="bgra8", cloud="f32", cloud_index=True, ...)), rgba.view(-1)[cloud_index] on the device, records -> host', HERE, "colour_torch")
+        B = Side('forward(output=OutputSpec(colour="bgra8", cloud="f32", cloud_layout="xyzrgb", colour_plane=False, ...)), counts -> host, count records per frame -> host',
+                 HERE, "colour")
+        a.cloud = True                                   # (from here on: the compact cloud's report)
+    elif a.cloud:
         A = Side('forward(output=OutputSpec(points="f32", Q=..., max_uncertainty=0.5, max_depth=50)), pts[valid] on the device -> host', HERE, "cloud_torch")
         B = Side('forward(output=OutputSpec(cloud="f32", Q=..., max_uncertainty=0.5, max_depth=50)), counts -> host, count records per frame -> host', HERE, "cloud")
     elif a.points:
