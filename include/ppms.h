@@ -464,8 +464,8 @@ int ppms_remap_struct_size(int* view);               /* sizeof(ppms_remap_view) 
  * or 2; a depth that does not go with it (8 with 1; 10 or 12 with 2); lsb not 0 or 16 - depth; (sub_x, sub_y) not (1,1), (1,0) or (0,0) -- (0,1)
  * included; non-zero reserved; an odd pointer or stride with 16-bit samples; a pitch or frame stride too small for the sample size and the
  * subsampling; shift, y_off or fill outside the bounds above.
- * Not covered: interpolated chroma siting, 16-bit depth, BT.2020 and HDR transfer functions, high-depth RGB.  (Packed YUYV / Y210 / v210:
- * ppms_video_ingest_yuv_packed below.) */
+ * Not covered: interpolated chroma siting, 16-bit depth, BT.2020 and HDR transfer functions, planar high-depth RGB.  (Packed YUYV / Y210 / v210:
+ * ppms_video_ingest_yuv_packed below; interleaved RGB of 8, 10 or 12 bits: ppms_video_ingest_rgb_packed.) */
 typedef struct ppms_yuv_format {
     int32_t sample_bytes;             /* 1, or 2 (little-endian 16-bit words) */
     int32_t depth;                    /* 8 with sample_bytes 1; 10 or 12 with sample_bytes 2 */
@@ -576,7 +576,7 @@ int ppms_raw_struct_sizes(int* view, int* format);   /* sizeof of the two struct
  * row_bytes(x0 + ws); with N > 1 a frame_stride < (hs - 1) * pitch + row_bytes; a colour pattern on a frame smaller than 2 x 2; shift in [8, 26 -
  * depth], y_off and the coefficients as ppms_video_ingest_yuv bounds them; pattern, black, shift and gains as ppms_video_ingest_raw bounds them;
  * what ppms_video_ingest_u8 refuses about sizes, pads and destinations; for _remap, whatever the _remap calls above refuse.
- * Not covered: Y216 and other 16-bit depths, 14-bit packed raw, 4:4:4 packed (v410, Y410, AYUV), big-endian containers, packed RGB, interpolated
+ * Not covered: Y216 and other 16-bit depths, 14-bit packed raw, 4:4:4 packed (v410, Y410, AYUV), big-endian containers, interpolated
  * chroma siting, patterns or layouts that differ between the two views. */
 typedef struct ppms_packed_view {     /* one view's frames inside a packed surface */
     const uint8_t* data;              /* column 0 of row 0 of frame 0 of the SURFACE */
@@ -615,6 +615,50 @@ int ppms_video_ingest_raw_packed_remap(const ppms_packed_view* left, const ppms_
                                        int N, int H0, int W0, int pad_left, int pad_top, int H, int W,
                                        const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream);
 int ppms_packed_struct_sizes(int* view, int* yuv_format, int* raw_format);   /* sizeof of the three structs above (24, 32, 48): lets a binding verify its layout */
+/* Interleaved RGB, (H, W, C) with the channels adjacent -- what cv2.VideoCapture / imread, PIL and numpy, GStreamer video/x-raw BGR, ROS bgr8 / rgba8,
+ * DXGI / DRM capture and ffmpeg rgb24 / bgr0 / rgb48le / x2rgb10le hand over -- read where it lies: one launch, no planar intermediate.  The view is the
+ * ppms_packed_view above (one pitched surface per view, column x of the view is surface column p = x + x0); x0 may be any value >= 0, since there is
+ * no chroma pair to split; x0 + ws <= 65536.  `fmt` (HOST memory, read before the call returns) is shared by both views.
+ *   How a level is read.  A pixel is `step` components; channel c (0 R, 1 G, 2 B) is component step * p + offset[c] of the row:
+ *   container 0   byte i of the row; depth 8; step 3 (rgb24, bgr24) or 4 (rgba, bgra, argb, abgr and their x forms);
+ *   container 1   little-endian 16-bit word i, the sample (word >> lsb) & ((1 << depth) - 1); depth 10 or 12, lsb = 16 - depth (bits at the top, the low
+ *                 bits dropped whatever they hold) or 0 (bits at the bottom, the high bits masked); step 3 (rgb48, bgr48) or 4 (rgba64, bgra64);
+ *                 pointer, pitch and frame stride even;
+ *   container 2   one little-endian 32-bit word per pixel (step 1), channel c in field offset[c]: bits [10 f, 10 f + 10) of word p; bits 30 and 31 are
+ *                 ignored; depth 10, lsb 0; pointer, pitch and frame stride multiples of 4.  offset = (2, 1, 0) puts R in bits 29..20, G in 19..10, B in
+ *                 9..0: ffmpeg's x2rgb10le and DRM's XRGB2101010 as those projects document them; offset = (0, 1, 2) puts R in bits 9..0: DXGI's
+ *                 R10G10B10A2 and ffmpeg's x2bgr10le likewise.  (The layouts are restated from that documentation: nothing has been compared with
+ *                 ffmpeg, a compositor or a capture API.)
+ * The component that no offset names -- the fourth of a step-4 pixel: alpha or padding -- is never loaded.  A row of P = x0 + ws columns holds
+ * row_bytes = step * P (bytes), 2 * step * P (words) or 4 * P (container 2).  The sample IS the level: from it on -- lut of 1 << depth entries, replicate
+ * padding, destinations -- the call is ppms_video_ingest_u8 on the planar frames that hold the same levels, with the table of that depth; at depth 8 it
+ * writes ppms_video_ingest_u8's bits.
+ *   _remap.  The remap contract above on these levels with fill in [0, 2^depth - 1]; every load address comes from a coordinate clamped into the frame,
+ * and with the pitch check below no load leaves [row, row + row_bytes).
+ *   Refused with PPMS_EINVAL before any launch: a null pointer; non-zero reserved; container, depth, lsb or step out of range or not going together
+ * (container 0 with anything but depth 8, 2 with anything but depth 10, lsb 0 and step 1; lsb not 0 or 16 - depth, and not 0 outside container 1; step
+ * not 3 or 4 with containers 0 and 1); an offset outside [0, step) (container 2: outside {0, 1, 2}) or two equal offsets; x0 < 0, x0 + ws > 65536; an odd
+ * pointer or stride with container 1, one that is no multiple of 4 with container 2; pitch < row_bytes(x0 + ws); with N > 1 a frame_stride <
+ * (hs - 1) * pitch + row_bytes; what ppms_video_ingest_u8 refuses about sizes, pads and destinations; for _remap, whatever the _remap calls above refuse.
+ * Not covered: 16-bit depth (the level table would not fit LDS), planar high-depth RGB (gbrp10le), big-endian words, RGB565, premultiplied or
+ * meaningful alpha, float / half RGB surfaces, layouts that differ between the two views. */
+typedef struct ppms_rgb_packed_format {
+    int32_t container;                /* 0 bytes, 1 little-endian 16-bit words, 2 one little-endian 32-bit word of three 10-bit fields */
+    int32_t depth;                    /* 8 with container 0; 10 or 12 with 1; 10 with 2 */
+    int32_t lsb;                      /* container 1: 0 or 16 - depth; 0 otherwise */
+    int32_t step;                     /* components per pixel: 3 or 4 (containers 0, 1); 1 (container 2) */
+    int32_t offset[3];                /* where R, G, B lie inside the pixel: component index in [0, step), distinct (containers 0, 1);
+                                         field index in {0, 1, 2}, distinct: bits [10 f, 10 f + 10) of the word (container 2; bits 30, 31 ignored) */
+    int32_t reserved;                 /* 0 */
+} ppms_rgb_packed_format;
+int ppms_video_ingest_rgb_packed(const ppms_packed_view* left, const ppms_packed_view* right, const ppms_rgb_packed_format* fmt,
+                                 int N, int H0, int W0, int pad_left, int pad_top, int H, int W,
+                                 const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream);
+int ppms_video_ingest_rgb_packed_remap(const ppms_packed_view* left, const ppms_packed_view* right, const ppms_rgb_packed_format* fmt,
+                                       const ppms_remap_view* lmap, const ppms_remap_view* rmap,
+                                       int N, int H0, int W0, int pad_left, int pad_top, int H, int W,
+                                       const float* lut, ppms_sp dst_fnet, ppms_sp dst_cnet, void* stream);
+int ppms_rgb_packed_struct_size(int* fmt);   /* sizeof of ppms_rgb_packed_format (32): lets a binding verify its layout */
 /* Colour out: the LEFT view as the network saw it -- converted, demosaiced, white-balanced, tone-mapped, rectified -- as 4-byte pixels registered
  * to the egress planes, one launch.  One entry point per ingest door above, with that door's head arguments (and maps), the same sources and the
  * same checks of them; the right view's pointers and structs stay in the signature and are checked, and never read by the kernel.
@@ -666,6 +710,13 @@ int ppms_video_colour_raw_packed(const ppms_packed_view* left, const ppms_packed
                                  int N, int H0, int W0, int frame0, int n_frames, int x0, int y0, int h0, int w0,
                                  const uint8_t* table, const ppms_egress_plane* out, void* stream);
 int ppms_video_colour_raw_packed_remap(const ppms_packed_view* left, const ppms_packed_view* right, const ppms_raw_packed_format* fmt,
+                                       const ppms_remap_view* lmap, const ppms_remap_view* rmap,
+                                       int N, int H0, int W0, int frame0, int n_frames, int x0, int y0, int h0, int w0,
+                                       const uint8_t* table, const ppms_egress_plane* out, void* stream);
+int ppms_video_colour_rgb_packed(const ppms_packed_view* left, const ppms_packed_view* right, const ppms_rgb_packed_format* fmt,
+                                 int N, int H0, int W0, int frame0, int n_frames, int x0, int y0, int h0, int w0,
+                                 const uint8_t* table, const ppms_egress_plane* out, void* stream);
+int ppms_video_colour_rgb_packed_remap(const ppms_packed_view* left, const ppms_packed_view* right, const ppms_rgb_packed_format* fmt,
                                        const ppms_remap_view* lmap, const ppms_remap_view* rmap,
                                        int N, int H0, int W0, int frame0, int n_frames, int x0, int y0, int h0, int w0,
                                        const uint8_t* table, const ppms_egress_plane* out, void* stream);

@@ -103,6 +103,12 @@ class RawPackedFormat(C.Structure):
                                                                                     ("reserved", C.c_int32 * 4)]
 
 
+class RGBPackedFormat(C.Structure):
+    """ppms_rgb_packed_format: how ppms_video_ingest_rgb_packed reads a pixel's channels (container, depth, alignment in the word, components per
+    pixel, where R, G and B lie among them)."""
+    _fields_ = [(n, C.c_int32) for n in ("container", "depth", "lsb", "step")] + [("offset", C.c_int32 * 3), ("reserved", C.c_int32)]
+
+
 class RemapView(C.Structure):
     """ppms_remap_view: one view's fixed-point rectification map (device pointers, pitch in map pixels, the source frame size)."""
     _fields_ = [("xy", c_void_p), ("frac", c_void_p), ("pitch", C.c_int32), ("hs", C.c_int32), ("ws", C.c_int32),
@@ -192,6 +198,7 @@ _SIGS = {
     "ppms_yuv_format_struct_size": (c_int, [C.POINTER(c_int)]),
     "ppms_raw_struct_sizes": (c_int, [C.POINTER(c_int), C.POINTER(c_int)]),
     "ppms_packed_struct_sizes": (c_int, [C.POINTER(c_int), C.POINTER(c_int), C.POINTER(c_int)]),
+    "ppms_rgb_packed_struct_size": (c_int, [C.POINTER(c_int)]),
     "ppms_dwconv": (c_int, [SP, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ppms_layernorm_any": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_float, SP, c_int64, c_int, c_void_p]),
     "ppms_grn_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
@@ -220,7 +227,7 @@ _SIGS = {
     "ppms_mem_attn_splits": (c_int, [c_int, c_int, c_int, c_int]),
     "ppms_attn_redo_accumulate": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
 }
-# the 12 ingest entry points: ppms_video_ingest_<door>(head, tail) and its _remap twin, which takes the two views' maps between head and tail
+# the 14 ingest entry points: ppms_video_ingest_<door>(head, tail) and its _remap twin, which takes the two views' maps between head and tail
 _INGEST_HEADS = {
     "u8": [c_void_p, c_void_p, c_int64],
     "yuv420": [C.POINTER(YUVView), C.POINTER(YUVView), C.POINTER(YUVMatrix)],
@@ -228,12 +235,13 @@ _INGEST_HEADS = {
     "raw": [C.POINTER(RawView), C.POINTER(RawView), C.POINTER(RawFormat)],
     "yuv_packed": [C.POINTER(PackedView), C.POINTER(PackedView), C.POINTER(YUVMatrix), C.POINTER(YUVPackedFormat)],
     "raw_packed": [C.POINTER(PackedView), C.POINTER(PackedView), C.POINTER(RawPackedFormat)],
+    "rgb_packed": [C.POINTER(PackedView), C.POINTER(PackedView), C.POINTER(RGBPackedFormat)],
 }
 _INGEST_TAIL = [c_int] * 7 + [c_void_p, SP, SP, c_void_p]       # N, H0, W0, pad_left, pad_top, H, W, lut, dst_fnet, dst_cnet, stream
 for _door, _head in _INGEST_HEADS.items():
     _SIGS["ppms_video_ingest_" + _door] = (c_int, _head + _INGEST_TAIL)
     _SIGS["ppms_video_ingest_" + _door + "_remap"] = (c_int, _head + [C.POINTER(RemapView)] * 2 + _INGEST_TAIL)
-# colour out: the same 12 doors (ppms_video_colour_<door>[_remap]) with one tail, and the coloured compact cloud (ppms_cloud_egress's list + the plane)
+# colour out: the same 14 doors (ppms_video_colour_<door>[_remap]) with one tail, and the coloured compact cloud (ppms_cloud_egress's list + the plane)
 _COLOUR_TAIL = [c_int] * 9 + [c_void_p, C.POINTER(EgressPlane), c_void_p]       # N, H0, W0, frame0, n_frames, x0, y0, h0, w0, table, out, stream
 for _door, _head in _INGEST_HEADS.items():
     _SIGS["ppms_video_colour_" + _door] = (c_int, _head + _COLOUR_TAIL)
@@ -251,6 +259,7 @@ _STRUCT_SIZES = (
     ("ppms_raw_struct_sizes", (RawView, RawFormat), "ctypes layout of ppms_raw_view / ppms_raw_format differs from include/ppms.h"),
     ("ppms_packed_struct_sizes", (PackedView, YUVPackedFormat, RawPackedFormat),
      "ctypes layout of ppms_packed_view / ppms_yuv_packed_format / ppms_raw_packed_format differs from include/ppms.h"),
+    ("ppms_rgb_packed_struct_size", (RGBPackedFormat,), "ctypes layout of ppms_rgb_packed_format differs from include/ppms.h"),
     ("ppms_egress_struct_size", (Egress,), "ctypes layout of ppms_egress differs from include/ppms.h"),
     ("ppms_egress3d_struct_size", (Egress3D,), "ctypes layout of ppms_egress3d differs from include/ppms.h"),
     ("ppms_cloud_struct_size", (Cloud,), "ctypes layout of ppms_cloud differs from include/ppms.h"),

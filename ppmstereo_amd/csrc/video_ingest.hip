@@ -6,7 +6,7 @@
 namespace {
 
 // decoded video -> the first-layer operands of both encoders in one launch (ppms_video_ingest_u8 / ppms_video_ingest_yuv420 / ppms_video_ingest_yuv / ppms_video_ingest_raw
-// and the packed doors ppms_video_ingest_yuv_packed / ppms_video_ingest_raw_packed):
+// and the packed doors ppms_video_ingest_yuv_packed / ppms_video_ingest_raw_packed / ppms_video_ingest_rgb_packed):
 // what normalisation (a table the caller built with the float path's own torch expression: 256 entries, or 1 << depth for a source whose
 // table_by_depth is true, which also answers levels()), replicate padding (clamped source
 // coordinate), torch.cat([left, right]) and the two img_s2d launches produce from the fp32 images.  Thread = one output pixel x 8 channels
@@ -103,6 +103,31 @@ struct yuv_packed_source {
         const int acc = mat.cy * d + (c == 0 ? mat.crv * f : c == 1 ? -mat.cgu * e - mat.cgv * f : mat.cbu * e) + (1 << (mat.shift - 1));
         const int q = acc >> mat.shift;                                   // arithmetic shift: floor
         return q < 0 ? 0 : (q > top ? top : q);
+    }
+};
+
+// interleaved RGB (ppms_video_ingest_rgb_packed): one pitched surface per view whose rows are streams of pixels, `step` components each (3, or 4 with
+// a fourth that is never loaded: alpha travels nowhere).  Column x of the view is surface column p = x + x0 (any x0 >= 0: there is no chroma pair to
+// split), and channel c is component step p + offset[c] of the row: container 0 byte i, 1 little-endian 16-bit word i, (word >> lsb) masked to `depth`
+// bits, as yuv_packed_source::component reads them; container 2 (step 1) field offset[c] -- bits [10 f, 10 f + 10) -- of 32-bit word p, bits 30 and 31
+// ignored.  Loads are of one container element (the host checks the alignment of pointers and strides for 16- and 32-bit elements); every offset is
+// 64-bit.  (y, x) arrives clamped into the hs x ws frame, so p <= P - 1 with P = x0 + ws, and with offset[c] <= step - 1 the largest component index is
+// step P - 1 (container 2: word P - 1): inside the step P bytes, 2 step P bytes or 4 P bytes the host demands of the pitch.  No load leaves
+// [row, row + row_bytes).  The sample is the level: no conversion follows.
+template <int Container>
+struct rgb_packed_source {
+    ppms_packed_view left, right;
+    int N, depth, lsb, step, offset_r, offset_g, offset_b;                // uniform: the ppms_rgb_packed_format
+    static constexpr bool table_by_depth = true;
+    __host__ __device__ int levels() const { return 1 << depth; }
+    __device__ int operator()(int64_t m, int c, int y, int x) const {
+        const bool r = m >= N;
+        const uint8_t* row = (r ? right.data : left.data) + (r ? m - N : m) * (r ? right.frame_stride : left.frame_stride) + (int64_t)y * (r ? right.pitch : left.pitch);
+        const int64_t p = x + (r ? right.x0 : left.x0);
+        const int o = c == 0 ? offset_r : c == 1 ? offset_g : offset_b;
+        if constexpr (Container == 0) return row[step * p + o];
+        if constexpr (Container == 1) return ((int)((const uint16_t*)row)[step * p + o] >> lsb) & ((1 << depth) - 1);
+        if constexpr (Container == 2) return (int)(((const uint32_t*)row)[p] >> (10 * o)) & 1023;
     }
 };
 
@@ -326,7 +351,7 @@ __global__ __launch_bounds__(256) void video_colour_kernel(Source source, int H0
 
 // ---- host side: every entry point fills one ingest_call, runs its door's checks and goes through ingest_samples() to the one launch ----------
 
-// what all 12 entry points take behind their source: the entry's name for the messages, geometry, table, destinations and stream
+// what all 14 entry points take behind their source: the entry's name for the messages, geometry, table, destinations and stream
 struct colour_call;
 struct ingest_call {
     const char* who;
@@ -336,7 +361,7 @@ struct ingest_call {
     void* stream;
     const colour_call* colour = nullptr;                                  // a ppms_video_colour_* call: the launch behind the door's checks is the colour kernel's
 };
-// what the 12 colour entry points take behind N, H0, W0 (`lut` of their ingest_call is `table`, for the doors' null checks only)
+// what the 14 colour entry points take behind N, H0, W0 (`lut` of their ingest_call is `table`, for the doors' null checks only)
 struct colour_call {
     int frame0, n_frames, x0, y0, h0, w0;
     const uint8_t* table;
@@ -563,7 +588,7 @@ struct remap_maps {
     const ppms_remap_view *left, *right;
 };
 
-// the way of all 12 entry points: the maps' check (with them the source frames are the maps' hs x ws, not H0 x W0), the door's own `check(hs, ws,
+// the way of all 14 entry points: the maps' check (with them the source frames are the maps' hs x ws, not H0 x W0), the door's own `check(hs, ws,
 // hname, wname)` of its views against those frames, then `pick(launch, hs, ws)`, which hands the door's source for frames of hs x ws to `launch` --
 // the one launch, behind the maps if there are any.  `fill` of a map is a level of the format's `depth` (a format that names no depth is refused
 // by `check`, right behind the maps, which bound hs and ws for it)
@@ -632,7 +657,7 @@ static int ingest_raw(const ingest_call& a, const ppms_raw_view* left, const ppm
         });
 }
 
-// what the four packed entry points check about one view's surface: x0 (even where `pair` says that a chroma pair may not be split), `align`-byte
+// what the six packed entry points check about one view's surface: x0 (even where `pair` says that a chroma pair may not be split), `align`-byte
 // pointers and strides (`unit` names the container that needs them), a pitch that holds the row of P = x0 + W0 columns, and with N > 1 a frame
 // stride that holds a frame.  `row_bytes(P)`: the format's row of P columns
 template <class RowBytes>
@@ -690,6 +715,32 @@ static int raw_packed_check(const ingest_call& a, const ppms_packed_view* left, 
     return packed_view_check(a, "right", *right, false, 1, "", H0, W0, wname, row_bytes);
 }
 
+// what both ppms_video_ingest_rgb_packed entry points check about the format and the views (frames of H0 x W0, named `hname` x `wname` in the messages)
+static int rgb_packed_check(const ingest_call& a, const ppms_packed_view* left, const ppms_packed_view* right, const ppms_rgb_packed_format* fmt, int H0,
+                            int W0, const char* hname, const char* wname) {
+    const char* who = a.who;
+    if (const int rc = opening_check(a, left && right && fmt && a.lut, "view, format or table", H0, W0, hname, wname)) return rc;
+    const ppms_rgb_packed_format& f = *fmt;
+    PPMS_REQUIRE(f.container >= 0 && f.container <= 2, "%s: container = %d must be 0 (bytes), 1 (16-bit words) or 2 (one 32-bit word of three 10-bit fields)", who,
+                 f.container);
+    PPMS_REQUIRE(f.container == 0 ? f.depth == 8 : f.container == 1 ? (f.depth == 10 || f.depth == 12) : f.depth == 10,
+                 "%s: depth = %d does not go with container = %d (8 with 0; 10 or 12 with 1; 10 with 2)", who, f.depth, f.container);
+    PPMS_REQUIRE(f.lsb == 0 || (f.container == 1 && f.lsb == 16 - f.depth), "%s: lsb = %d must be 0, or 16 - depth for 16-bit words", who, f.lsb);
+    PPMS_REQUIRE(f.container == 2 ? f.step == 1 : (f.step == 3 || f.step == 4), "%s: step = %d does not go with container = %d (3 or 4 with 0 and 1; 1 with 2)", who,
+                 f.step, f.container);
+    const int places = f.container == 2 ? 3 : f.step;                    // where a channel may lie: a component of the pixel, or a field of the word
+    for (const int32_t o : f.offset)
+        PPMS_REQUIRE(o >= 0 && o < places, "%s: offset = (%d, %d, %d) must lie in [0, %d)", who, f.offset[0], f.offset[1], f.offset[2], places);
+    PPMS_REQUIRE(f.offset[0] != f.offset[1] && f.offset[0] != f.offset[2] && f.offset[1] != f.offset[2], "%s: offset = (%d, %d, %d): two channels in one place", who,
+                 f.offset[0], f.offset[1], f.offset[2]);
+    PPMS_REQUIRE(f.reserved == 0, "%s: format: reserved = %d must be 0", who, f.reserved);
+    const int align = f.container == 0 ? 1 : f.container == 1 ? 2 : 4;
+    const char* unit = f.container == 1 ? "16-bit words" : "32-bit words";
+    const auto row_bytes = [&](int P) { return (int64_t)align * f.step * P; };
+    if (const int rc = packed_view_check(a, "left", *left, false, align, unit, H0, W0, wname, row_bytes)) return rc;
+    return packed_view_check(a, "right", *right, false, align, unit, H0, W0, wname, row_bytes);
+}
+
 static int ingest_yuv_packed(const ingest_call& a, const ppms_packed_view* left, const ppms_packed_view* right, const ppms_yuv_matrix* m,
                              const ppms_yuv_packed_format* f, const remap_maps* maps) {
     return ingest_frames(
@@ -713,6 +764,21 @@ static int ingest_raw_packed(const ingest_call& a, const ppms_packed_view* left,
                 return raw_packed_source<decltype(packing)::value>{*left, *right, a.N, hs, ws, f->depth, f->pattern, f->black, f->gain[0], f->gain[1], f->gain[2], f->shift};
             };
             return f->packing == 0 ? launch(source(std::integral_constant<int, 0>{})) : launch(source(std::integral_constant<int, 1>{}));
+        });
+}
+
+static int ingest_rgb_packed(const ingest_call& a, const ppms_packed_view* left, const ppms_packed_view* right, const ppms_rgb_packed_format* f,
+                             const remap_maps* maps) {
+    return ingest_frames(
+        a, depth_of(f), maps,
+        [&](int hs, int ws, const char* hname, const char* wname) { return rgb_packed_check(a, left, right, f, hs, ws, hname, wname); },
+        [&](auto launch, int, int) {
+            const auto source = [&](auto container) {
+                return rgb_packed_source<decltype(container)::value>{*left, *right, a.N, f->depth, f->lsb, f->step, f->offset[0], f->offset[1], f->offset[2]};
+            };
+            if (f->container == 0) return launch(source(std::integral_constant<int, 0>{}));
+            if (f->container == 1) return launch(source(std::integral_constant<int, 1>{}));
+            return launch(source(std::integral_constant<int, 2>{}));
         });
 }
 
@@ -775,7 +841,16 @@ extern "C" int ppms_video_ingest_raw_packed_remap(const ppms_packed_view* left, 
     return ingest_raw_packed(INGEST_CALL("video_ingest_raw_packed_remap"), left, right, fmt, &maps);
 }
 
-// ---- colour out: the same 12 doors in front of video_colour_kernel.  The trailing arguments every colour entry point declares, and the ingest_call
+extern "C" int ppms_video_ingest_rgb_packed(const ppms_packed_view* left, const ppms_packed_view* right, const ppms_rgb_packed_format* fmt, INGEST_TAIL) {
+    return ingest_rgb_packed(INGEST_CALL("video_ingest_rgb_packed"), left, right, fmt, nullptr);
+}
+extern "C" int ppms_video_ingest_rgb_packed_remap(const ppms_packed_view* left, const ppms_packed_view* right, const ppms_rgb_packed_format* fmt,
+                                                  const ppms_remap_view* lmap, const ppms_remap_view* rmap, INGEST_TAIL) {
+    const remap_maps maps{lmap, rmap};
+    return ingest_rgb_packed(INGEST_CALL("video_ingest_rgb_packed_remap"), left, right, fmt, &maps);
+}
+
+// ---- colour out: the same 14 doors in front of video_colour_kernel.  The trailing arguments every colour entry point declares, and the ingest_call
 // (its door's checks read who, N, H0, W0 and the table's null check) with the colour_call they fill
 #define COLOUR_TAIL int N, int H0, int W0, int frame0, int n_frames, int x0, int y0, int h0, int w0, const uint8_t* table, const ppms_egress_plane* out, void* stream
 #define COLOUR_CALL(name)                                                      \
@@ -844,6 +919,21 @@ extern "C" int ppms_video_colour_raw_packed_remap(const ppms_packed_view* left, 
     return ingest_raw_packed(call, left, right, fmt, &maps);
 }
 
+extern "C" int ppms_video_colour_rgb_packed(const ppms_packed_view* left, const ppms_packed_view* right, const ppms_rgb_packed_format* fmt, COLOUR_TAIL) {
+    COLOUR_CALL("video_colour_rgb_packed");
+    return ingest_rgb_packed(call, left, right, fmt, nullptr);
+}
+extern "C" int ppms_video_colour_rgb_packed_remap(const ppms_packed_view* left, const ppms_packed_view* right, const ppms_rgb_packed_format* fmt,
+                                                  const ppms_remap_view* lmap, const ppms_remap_view* rmap, COLOUR_TAIL) {
+    COLOUR_CALL("video_colour_rgb_packed_remap");
+    const remap_maps maps{lmap, rmap};
+    return ingest_rgb_packed(call, left, right, fmt, &maps);
+}
+
+extern "C" int ppms_rgb_packed_struct_size(int* fmt) {
+    if (fmt) *fmt = (int)sizeof(ppms_rgb_packed_format);
+    return PPMS_OK;
+}
 extern "C" int ppms_packed_struct_sizes(int* view, int* yuv_format, int* raw_format) {
     if (view) *view = (int)sizeof(ppms_packed_view);
     if (yuv_format) *yuv_format = (int)sizeof(ppms_yuv_packed_format);

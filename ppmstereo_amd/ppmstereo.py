@@ -23,6 +23,7 @@ from .output import OutputSpec, _EgressCall, egress_plan  # noqa: F401  (the pub
 from .video import (InputPadder, RawFrames, RawStereoVideo, RectifyMap, StereoRectifier, YUVFrames, YUVStereoVideo, byte_lut,  # noqa: F401
                     level_lut, shard_windows, window_plan, yuv_matrix)
 from .video import PackedRawFrames, PackedRawStereoVideo, PackedYUVFrames, PackedYUVStereoVideo  # noqa: F401
+from .video import PackedRGBFrames, PackedRGBStereoVideo  # noqa: F401
 from .video import _ByteSource, colour_bytes, colour_lut, stereo_source  # noqa: F401
 
 
@@ -566,6 +567,8 @@ class PPMStereo(PPMStereoHotPath):
           of ``forward`` on their ``to_float()``; or
           two ``PackedYUVFrames`` or two ``PackedRawFrames`` on the device (YUYV / UYVY / Y210 / v210 ...; MIPI RAW10 / RAW12 or PFNC 10p / 12p
           rows, e.g. the ``split_side_by_side()`` halves of one surface; b = 1, T = their frame count): the bits of ``forward`` on their ``unpack()``; or
+          two ``PackedRGBFrames`` on the device (interleaved BGR24 / BGRA / RGB48 / X2RGB10 ..., e.g. ``PackedRGBFrames.from_hwc`` of an (N, H, W, C)
+          tensor; b = 1, T = their frame count): at depth 8 the bits of ``forward`` on their ``unpack()``, at depth 10 / 12 on their ``to_float()``; or
           with rectify (a ``StereoRectifier``) the RAW frames of an unrectified rig, uint8 device tensors (1, T, 3, Hs, Ws) or ``YUVFrames`` of its
           source size Hs x Ws: the bits of ``forward`` on ``RectifyMap.apply_u8`` of each view's RGB bytes (deep frames: ``apply_levels`` of their levels).  H, W above are then the rectified size,
           and so are the outputs'.  Float images raise TypeError (the remap reads decoded bytes), b > 1 NotImplementedError, another frame size
@@ -707,9 +710,12 @@ class PPMStereo(PPMStereoHotPath):
         the uint8 video of ``to_rgb_u8()``); a ``RawStereoVideo`` (a sensor's raw frames, host or device) as its samples -- 1 byte per pixel and
         view, 2 for 10- and 12-bit words -- and gives the bits of the float video of its ``to_float()`` frames; a ``PackedYUVStereoVideo`` or
         ``PackedRawStereoVideo`` (packed rows as the camera or capture card left them, host or device) as the packed bytes of each view's own
-        columns -- YUYV 2 per pixel and view, v210 2.67, RAW10p 1.25, RAW12p 1.5 -- and gives the bits of the call on its views' ``unpack()``.
-        Not covered: interpolated chroma siting, 16-bit depth, 4:4:4 packed and packed RGB, BT.2020
-        and HDR transfer functions, high-depth RGB, b > 1.  With this package's encoders the bytes are converted, padded and normalised inside the one ingest launch;
+        columns -- YUYV 2 per pixel and view, v210 2.67, RAW10p 1.25, RAW12p 1.5 -- and gives the bits of the call on its views' ``unpack()``;
+        a ``PackedRGBStereoVideo`` (interleaved pixels, host or device; ``from_hwc`` of an (N, 2, H, W, C) tensor) as the pixels' own bytes -- bgr24 3
+        per pixel and view, bgra and x2rgb10 4 -- and gives the bits of the call on the planar uint8 video of ``unpack()`` (depth 10 / 12: on the
+        float video of ``to_float()``).
+        Not covered: interpolated chroma siting, 16-bit depth, 4:4:4 packed YUV, BT.2020
+        and HDR transfer functions, planar high-depth RGB, b > 1.  With this package's encoders the bytes are converted, padded and normalised inside the one ingest launch;
         windows of ``kernel_size`` frames every ``kernel_size // 2``, centre frames kept (:296-307).  Windows whose output the
         reference computes and then drops are not run.  Returns {"disparity", "uncertainties"}: (N, 1, H, W) CPU tensors.
         shard_ranks: under torch.distributed the windows are dealt round-robin over the ranks (independent units, no data-path

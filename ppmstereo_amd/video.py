@@ -1,6 +1,6 @@
 """Video into the model: what ``PPMStereo.forward`` / ``forward_batch_test`` accept beside the reference's float tensors (uint8 and decoded
 YUV frames of 8, 10 or 12 bits with 4:2:0 / 4:2:2 / 4:4:4 chroma, a sensor's Bayer-mosaic or monochrome frames, both in the packed formats cameras put
-on the wire (YUYV, Y210, v210, RAW10p / RAW12p), unrectified frames with a ``StereoRectifier``), the one private family of sources that stands for all of them behind the front doors
+on the wire (YUYV, Y210, v210, RAW10p / RAW12p), interleaved RGB of 8, 10 or 12 bits (BGR24, BGRA, RGB48, X2RGB10), unrectified frames with a ``StereoRectifier``), the one private family of sources that stands for all of them behind the front doors
 (``stereo_source``) and the sliding-window schedule.  A source also hands the left view back as colour bytes (``colour``; ``colour_bytes`` is the
 definition), for output.py's "colour" plane.  Nothing here knows the model.  (What the doors hand back: output.py.)"""
 from __future__ import annotations
@@ -660,7 +660,7 @@ class RawStereoVideo(_StereoVideo):
 
 
 class _PackedFrames(_Frames):
-    """What ``PackedYUVFrames`` and ``PackedRawFrames`` share: ``data`` (N, H0, row elements) is the driver's own buffer -- a pitched SURFACE whose
+    """What ``PackedYUVFrames``, ``PackedRawFrames`` and ``PackedRGBFrames`` share: ``data`` (N, H0, row elements) is the driver's own buffer -- a pitched SURFACE whose
     rows hold whole groups of ``_group`` = (pixels, elements) -- and the view is its columns [x0, x0 + width): nothing is copied, and the two halves
     of a side-by-side frame are one surface with two ``x0``.  A subclass has ``_name``, ``_group``, ``_align`` (bytes: what pointer and strides must
     be multiples of), ``_row_elements(P)`` (the elements of a row of P columns) and ``_with(data, x0, width)``."""
@@ -747,7 +747,7 @@ class PackedYUVFrames(_YUVColour, _PackedFrames):
     address, pitch and frame stride are multiples of 4.  A row holds whole pairs (v210: whole groups).  ``data`` may be a strided view; the class
     reads ``data_ptr()`` and ``stride()`` and never copies.  ``unpack`` is the definition of the samples, ``to_rgb`` / ``to_float`` those of the
     planar frames it returns (chroma from the pixel's own pair, nearest).  Not covered: Y216 and other 16-bit depths, 4:4:4 packed (v410, Y410,
-    AYUV), big-endian containers, packed RGB, interpolated chroma siting, b > 1."""
+    AYUV), big-endian containers, interpolated chroma siting, b > 1.  (Interleaved RGB: ``PackedRGBFrames``.)"""
     _name, _entry = "PackedYUVFrames", "ppms_video_ingest_yuv_packed"
 
     def __init__(self, data: torch.Tensor, width: int, layout: str = "yuyv", align: str = "msb", standard: str = "bt709", full_range: bool = False,
@@ -939,7 +939,172 @@ class PackedRawStereoVideo(_StereoVideo):
     _views = PackedRawFrames
 
 
-_BORDERS = {"replicate": L.BORDER_REPLICATE, "constant": L.BORDER_CONSTANT}
+# layout: (container, step, where R, G, B lie) of ppms_rgb_packed_format -- component indices of the pixel; for container 2 fields of its 32-bit word
+_PACKED_RGB = {"rgb24": (0, 3, (0, 1, 2)), "bgr24": (0, 3, (2, 1, 0)),
+               "rgba": (0, 4, (0, 1, 2)), "bgra": (0, 4, (2, 1, 0)), "argb": (0, 4, (1, 2, 3)), "abgr": (0, 4, (3, 2, 1)),
+               "rgb48": (1, 3, (0, 1, 2)), "bgr48": (1, 3, (2, 1, 0)), "rgba64": (1, 4, (0, 1, 2)), "bgra64": (1, 4, (2, 1, 0)),
+               "x2rgb10": (2, 1, (2, 1, 0)), "x2bgr10": (2, 1, (0, 1, 2))}
+_PACKED_RGB.update({name.replace("a", "x"): _PACKED_RGB[name] for name in ("rgba", "bgra", "argb", "abgr")})      # a fourth byte that is padding: the same reads
+_HWC_ORDERS = {(1, "rgb"): "rgb24", (1, "bgr"): "bgr24", (2, "rgb"): "rgb48", (2, "bgr"): "bgr48", (2, "rgba"): "rgba64", (2, "bgra"): "bgra64"}
+_HWC_ORDERS.update({(1, name): name for name, (container, step, _) in _PACKED_RGB.items() if (container, step) == (0, 4)})
+
+
+class PackedRGBFrames(_PackedFrames):
+    """One view's N frames of interleaved RGB, (H, W, C) with the channels adjacent, as ``cv2.VideoCapture`` / ``imread``, PIL and numpy, GStreamer
+    ``video/x-raw,format=BGR``, ROS ``bgr8`` / ``rgba8``, DXGI / DRM capture and ffmpeg ``rgb24`` / ``bgr0`` / ``rgb48le`` / ``x2rgb10le`` leave them:
+    ``data`` (N, H0, row elements) over the caller's own buffer, ``width`` pixels wide from surface column ``x0`` (any column).  ``layout``
+      "rgb24" / "bgr24": uint8, 3 bytes per pixel in that order; "rgba" = "rgbx", "bgra" = "bgrx", "argb" = "xrgb", "abgr" = "xbgr": uint8, 4 bytes
+      per pixel -- the fourth is never read, whatever it holds;
+      "rgb48" / "bgr48" / "rgba64" / "bgra64": ``torch.uint16`` words holding ``depth`` = 10 or 12 bits at the top (``align="msb"``, the default: the
+      low bits are dropped whatever they hold) or at the bottom (``align="lsb"``: the high bits are masked);
+      "x2rgb10": one little-endian 32-bit word per pixel, R in bits 29..20, G in 19..10, B in 9..0 (ffmpeg's x2rgb10le, DRM's XRGB2101010);
+      "x2bgr10": R in bits 9..0, G in 19..10, B in 29..20 (DXGI's R10G10B10A2); bits 30 and 31 are ignored; ``data`` uint8 (4 bytes per pixel) or int32
+      rows, its address, pitch and frame stride multiples of 4.
+    (The layouts restate those projects' documentation; include/ppms.h is the definition here, and nothing has been compared with ffmpeg.)  ``data``
+    may be a strided view; the class reads ``data_ptr()`` and ``stride()`` and never copies -- ``from_hwc`` takes the (N, H, W, C) tensor as it is.
+    ``unpack`` is the definition of the levels: planar (N, 3, H0, W0), which ``to_rgb`` returns and ``to_float`` turns into the float video.  Not
+    covered: 16-bit depth, planar high-depth RGB (gbrp10le), big-endian words, RGB565, premultiplied or meaningful alpha, float / half surfaces,
+    layouts that differ between the two views, b > 1."""
+    _name, _entry = "PackedRGBFrames", "ppms_video_ingest_rgb_packed"
+
+    def __init__(self, data: torch.Tensor, width: int, layout: str = "bgr24", depth: Optional[int] = None, align: str = "msb", x0: int = 0):
+        if layout not in _PACKED_RGB:
+            raise ValueError(f"PackedRGBFrames: layout {layout!r}; one of {sorted(_PACKED_RGB)}")
+        self.container, self.step, self.offset = _PACKED_RGB[layout]
+        depths = ((8,), (10, 12), (10,))[self.container]
+        if depth is None and len(depths) == 1:
+            depth = depths[0]
+        if depth not in depths:
+            raise ValueError(f"PackedRGBFrames: depth = {depth!r} does not go with layout {layout!r}; {' or '.join(map(str, depths))}")
+        self.depth = int(depth)
+        self.lsb = _sample_lsb("PackedRGBFrames", align, self.depth, self.container == 1)
+        self._align = (1, 2, 4)[self.container]
+        dtype = (torch.uint8, torch.uint16, torch.int32 if torch.is_tensor(data) and data.dtype == torch.int32 else torch.uint8)[self.container]
+        self._group = (1, 4 if (self.container, dtype) == (2, torch.uint8) else self.step)      # the elements of one pixel
+        self._surface(data, width, x0, dtype, False)
+        self.layout, self.align = layout, align
+
+    @classmethod
+    def from_hwc(cls, frames: torch.Tensor, order: str = "bgr", depth: Optional[int] = None, align: str = "msb") -> "PackedRGBFrames":
+        """``frames`` (N, H, W, 3 | 4), uint8 or ``torch.uint16``, the channels in ``order`` ("bgr" / "rgb"; "bgra", "rgba", "argb", "abgr" and their
+        x forms; 16-bit words: "rgb", "bgr", "rgba", "bgra" with ``depth`` 10 or 12) -- an OpenCV, PIL or numpy image stack as it is.  The innermost
+        stride must be 1 and the pixel stride C; rows and frames may have any strides that do not overlap: a crop ``t[:, 3:40, 5:55]`` of a larger
+        tensor is read where it lies.  Nothing is copied."""
+        if not torch.is_tensor(frames) or frames.dim() != 4 or frames.dtype not in (torch.uint8, torch.uint16):
+            raise ValueError("PackedRGBFrames.from_hwc: frames must be a uint8 or uint16 tensor (N, H, W, C)")
+        layout = _HWC_ORDERS.get((frames.element_size(), order))
+        n, h, w, c = frames.shape
+        if layout is None or _PACKED_RGB[layout][1] != c:
+            raise ValueError(f"PackedRGBFrames.from_hwc: order {order!r} does not name the {c} channels of {frames.dtype} pixels; one of "
+                             f"{sorted(o for es, o in _HWC_ORDERS if es == frames.element_size())}")
+        if frames.stride(3) != 1 or (w > 1 and frames.stride(2) != c):
+            raise ValueError(f"PackedRGBFrames.from_hwc: strides {frames.stride()}; a pixel's channels must be adjacent and the pixels of a row {c} elements apart")
+        rows = torch.as_strided(frames, (n, h, w * c), (frames.stride(0), frames.stride(1), 1), frames.storage_offset())
+        return cls(rows, w, layout, depth, align)
+
+    def _row_elements(self, p: int) -> int:
+        return self._group[1] * p
+
+    def _with(self, data, x0, width) -> "PackedRGBFrames":
+        return PackedRGBFrames(data, width, self.layout, self.depth, self.align, x0)
+
+    def split_side_by_side(self):
+        """(left, right): the two halves of frames that pack both views side by side -- the same surface with two ``x0``.  The packed width must
+        be even; a half may be odd (no pixel shares anything with its neighbour)."""
+        h = self._half("split_side_by_side", self.width, False, "views")
+        return self._with(self.data, self.x0, h), self._with(self.data, self.x0 + h, h)
+
+    def split_top_bottom(self):
+        """(left, right) = (top, bottom) halves of frames that pack both views one above the other; views, no copy."""
+        h = self._half("split_top_bottom", self.height, False, "views")
+        return self._like(self.data[:, :h]), self._like(self.data[:, h:])
+
+    def format_fault(self, other: "PackedRGBFrames") -> Optional[str]:
+        if (self.container, self.step, self.offset, self.depth, self.lsb) == (other.container, other.step, other.offset, other.depth, other.lsb):
+            return None
+        return f"the views differ in layout, depth or alignment: {(self.layout, self.depth, self.align)} and {(other.layout, other.depth, other.align)}"
+
+    def format_struct(self) -> L.RGBPackedFormat:
+        """The ``ppms_rgb_packed_format`` of these frames."""
+        return L.RGBPackedFormat(self.container, self.depth, self.lsb, self.step, self.offset, 0)
+
+    def _structs(self):
+        return (self.format_struct(),)
+
+    def table(self, device) -> torch.Tensor:
+        return level_lut(device, self.depth)
+
+    def colour_table(self, device) -> torch.Tensor:
+        return colour_lut(device, self.depth)
+
+    def levels_to_float(self, levels: torch.Tensor) -> torch.Tensor:
+        return _levels_to_float(levels, self.depth)
+
+    def unpack(self) -> torch.Tensor:
+        """Planar (N, 3, H0, W0) R, G, B levels on the same device, uint8 at depth 8 and int16 in [0, 2^depth - 1] otherwise, in torch integer ops:
+        the definition of the layouts on this side -- what the feature means by the levels of these frames (the kernels' operands are
+        ppms_video_ingest_u8's on them, with the table of their depth) -- and the path of encoder callables of the caller."""
+        p = torch.arange(self.x0, self.x0 + self.width, device=self.device)
+        if self.container == 2:
+            if self.data.dtype == torch.uint8:
+                words = sum(self.data[:, :, 4 * p + k].to(torch.int64) << (8 * k) for k in range(4))
+            else:
+                words = self.data[:, :, p].to(torch.int64)
+            channels = [(words >> (10 * f)) & 1023 for f in self.offset]
+        else:
+            # (16-bit words are gathered as the int16 with the same bits and widened to their unsigned value: uint16 tensors cannot be indexed on a GPU)
+            row = self.data.view(torch.int16) if self.container == 1 else self.data
+            channels = [((row[:, :, self.step * p + o].to(torch.int32) & 0xFFFF) >> self.lsb) & ((1 << self.depth) - 1) for o in self.offset]
+        return torch.stack(channels, dim=1).to(torch.uint8 if self.depth == 8 else torch.int16)
+
+    def to_rgb(self) -> torch.Tensor:
+        """``unpack()``: the frames' RGB levels."""
+        return self.unpack()
+
+    def to_float(self) -> torch.Tensor:
+        """float32 (N, 3, H0, W0) in [0, 255]: ``levels.float() * (255.0 / (2^depth - 1))`` (depth 8: the bytes' values) -- the video the reference
+        would be given."""
+        return self.levels_to_float(self.unpack())
+
+    @classmethod
+    def pack(cls, levels: torch.Tensor, layout: str = "bgr24", depth: Optional[int] = None, align: str = "msb") -> "PackedRGBFrames":
+        """The inverse of ``unpack`` for simulators: planar levels (N, 3, H0, W0) as ``unpack`` gives them (uint8 for the byte layouts, int16 in
+        [0, 2^depth - 1] otherwise) -> dense interleaved rows; the fourth component, spare bits of words and bits 30, 31 are 0 (the 10-bit words
+        come as int32 rows)."""
+        if layout not in _PACKED_RGB or not torch.is_tensor(levels) or levels.dim() != 4 or levels.shape[1] != 3:
+            raise ValueError(f"PackedRGBFrames.pack: planar levels (N, 3, H0, W0) and a layout of {sorted(_PACKED_RGB)} expected")
+        container, step, offset = _PACKED_RGB[layout]
+        probe = cls(torch.zeros((1, 1, 4), dtype=(torch.uint8, torch.uint16, torch.int32)[container]), 1, layout, depth, align)      # (checks depth and align)
+        if levels.dtype != (torch.uint8 if probe.depth == 8 else torch.int16) or bool(((levels < 0) | (levels.to(torch.int32) >> probe.depth != 0)).any()):
+            raise ValueError(f"PackedRGBFrames.pack: {'uint8' if probe.depth == 8 else 'int16'} levels of {probe.depth} bits expected for layout {layout!r}")
+        n, _, h, w = levels.shape
+        v = levels.to(torch.int64)
+        if container == 2:
+            words = sum(v[:, c] << (10 * f) for c, f in enumerate(offset))
+            data = words.to(torch.int32)
+        else:
+            pixels = torch.zeros((n, h, w, step), dtype=torch.int64, device=levels.device)
+            for c, o in enumerate(offset):
+                pixels[..., o] = v[:, c] << probe.lsb
+            data = pixels.flatten(2).to(torch.uint8) if container == 0 else pixels.flatten(2).to(torch.int32).to(torch.uint16)
+        return cls(data, w, layout, probe.depth, align)
+
+
+class PackedRGBStereoVideo(_StereoVideo):
+    """Both views of an interleaved RGB video -- what ``batch_dict["stereo_video"]`` of ``forward_batch_test`` may be instead of a tensor: two
+    ``PackedRGBFrames`` of one size, frame count, device, layout, depth and alignment.  ``len()``, slicing by frame range, ``to(device)`` (the
+    pixels' own bytes: bgr24 3 per pixel and view, bgra and x2rgb10 4, rgb48 6); ``from_hwc`` takes a (N, 2, H, W, C) tensor as it is."""
+    _views = PackedRGBFrames
+
+    @classmethod
+    def from_hwc(cls, video: torch.Tensor, order: str = "bgr", depth: Optional[int] = None, align: str = "msb") -> "PackedRGBStereoVideo":
+        """``video`` (N, 2, H, W, 3 | 4): both views' ``PackedRGBFrames.from_hwc``, over the one tensor; nothing is copied."""
+        if not torch.is_tensor(video) or video.dim() != 5 or video.shape[1] != 2:
+            raise ValueError("PackedRGBStereoVideo.from_hwc: video must be a tensor (N, 2, H, W, C)")
+        return cls(*(PackedRGBFrames.from_hwc(video[:, i], order, depth, align) for i in (0, 1)))
+
+
+_BORDERS ={"replicate": L.BORDER_REPLICATE, "constant": L.BORDER_CONSTANT}
 
 
 class RectifyMap:
@@ -1233,9 +1398,9 @@ def _checked_rectifier(who: str, rectify, device, h: int, w: int) -> StereoRecti
 
 
 def stereo_source(who: str, left, right=None, rectify: Optional[StereoRectifier] = None):
-    """The source of two views -- float or uint8 tensors (b, T, 3, H, W), two ``YUVFrames``, ``RawFrames``, ``PackedYUVFrames`` or
-    ``PackedRawFrames`` -- or, with ``right`` None, of a window ``left`` of a video: a tensor (T, 2, 3, H, W), a ``YUVStereoVideo``, a
-    ``RawStereoVideo``, a ``PackedYUVStereoVideo`` or a ``PackedRawStereoVideo``.  Every argument check of the front doors is
+    """The source of two views -- float or uint8 tensors (b, T, 3, H, W), two ``YUVFrames``, ``RawFrames``, ``PackedYUVFrames``,
+    ``PackedRawFrames`` or ``PackedRGBFrames`` -- or, with ``right`` None, of a window ``left`` of a video: a tensor (T, 2, 3, H, W), a
+    ``YUVStereoVideo``, a ``RawStereoVideo``, a ``PackedYUVStereoVideo``, a ``PackedRawStereoVideo`` or a ``PackedRGBStereoVideo``.  Every argument check of the front doors is
     made here, under the name ``who``, and touches no device: rectify= reads decoded bytes (TypeError for float frames), of its source size
     (ValueError), b = 1; two ``YUVFrames`` that differ in depth, alignment or chroma subsampling, two ``RawFrames`` that differ in pattern,
     sample format, black level, gains or tone curve, or two packed views that differ in layout, packing, depth or any of those, are no stereo pair
@@ -1243,7 +1408,7 @@ def stereo_source(who: str, left, right=None, rectify: Optional[StereoRectifier]
     if rectify is not None and not isinstance(rectify, StereoRectifier):
         raise TypeError(f"{who}: rectify must be a StereoRectifier, got {type(rectify).__name__}")
     for frames, video in ((YUVFrames, YUVStereoVideo), (RawFrames, RawStereoVideo), (PackedYUVFrames, PackedYUVStereoVideo),
-                          (PackedRawFrames, PackedRawStereoVideo)):
+                          (PackedRawFrames, PackedRawStereoVideo), (PackedRGBFrames, PackedRGBStereoVideo)):
         if isinstance(left, frames) or isinstance(right, frames):
             if not (isinstance(left, frames) and isinstance(right, frames)):
                 raise TypeError(f"{who}: image1 is {type(left).__name__} and image2 is {type(right).__name__}; both views must be {frames.__name__} or both tensors")

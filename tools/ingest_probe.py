@@ -6,6 +6,7 @@
     python tools/ingest_probe.py --door deep  [--depth 10] [--chroma 420] [--align msb] [--runs 12]     > profiles/rNN_ingest_deep_ab.txt
     python tools/ingest_probe.py --door raw   [--depth 10] [--pattern rggb] [--align lsb] [--runs 12]   > profiles/rNN_ingest_raw_ab.txt
     python tools/ingest_probe.py --door packed [--layout yuyv | ... | v210 | mipi | pfnc] [--depth 10]  > profiles/rNN_ingest_packed_ab.txt
+    python tools/ingest_probe.py --door rgb   [--layout bgr24 | bgra | ... | rgb48 | x2rgb10] [--depth 10] > profiles/rNN_ingest_rgb_ab.txt
     python tools/ingest_probe.py --kernels --parent DIR [--runs 7]                                      > profiles/rNN_ingest_kernels_ab.txt
 
 --door: PPMStereo.forward_batch_test on one video through two ways in.  Side B is the door itself; side A is what a caller did before the door
@@ -124,6 +125,38 @@ def packed_side_a(a, torch, P, video, kw):                      # what a caller 
     return (P.RawStereoVideo if a.layout in RAW_PACKINGS else P.YUVStereoVideo)(video.left.unpack(), video.right.unpack()), {}
 
 
+RGB_LAYOUTS = {"rgb24": 8, "bgr24": 8, "rgba": 8, "bgra": 8, "argb": 8, "abgr": 8, "rgb48": 0, "bgr48": 0, "rgba64": 0, "bgra64": 0,
+               "x2rgb10": 10, "x2bgr10": 10}                    # layout: depth (0: --depth 10 | 12, in 16-bit words, --align)
+
+
+def rgb_depth(a):
+    return RGB_LAYOUTS[a.layout] or (a.depth if a.depth in (10, 12) else 10)
+
+
+def rgb_bytes(a):
+    """Bytes per pixel and view that cross into the ingest launch, by construction: side B's own pixels, and what side A's planar video (uint8,
+    or float32 for the deep layouts) is written and read with on top of them."""
+    step = 3 if a.layout in ("rgb24", "bgr24", "rgb48", "bgr48") else 4
+    own = 4 if a.layout.startswith("x2") else step * (1 if rgb_depth(a) == 8 else 2)
+    return own, 3 if rgb_depth(a) == 8 else 12
+
+
+def rgb_video(a, torch, P, Wm, dev, h, w):
+    """Interleaved frames, packed on the host with the class's own pack() and moved to the device as they are."""
+    depth = rgb_depth(a)
+    levels = Wm.hash_uniform((T, 2, 3, h, w), 619, 0.0, float((1 << depth) - 1)).round().to(torch.uint8 if depth == 8 else torch.int16)
+    view = lambda s: P.PackedRGBFrames.pack(levels[:, s].contiguous(), a.layout, depth, a.align).to(dev)
+    return P.PackedRGBStereoVideo(view(0), view(1)), {}
+
+
+def rgb_side_a(a, torch, P, video, kw):                         # what a caller did before the door: the transposing copy in front of forward
+    assert isinstance(video, P.PackedRGBStereoVideo)
+    if video.depth > 8:
+        return torch.stack([video.left.to_float(), video.right.to_float()], dim=1), {}
+    hwc = lambda v: v.data.unflatten(2, (v.width, v.step))       # (N, H, W, C): the caller's own tensor
+    return torch.stack([hwc(v).permute(0, 3, 1, 2)[:, list(v.offset)].contiguous() for v in (video.left, video.right)], dim=1), {}
+
+
 def levels_side_a(a, torch, P, video, kw):                      # the uint8 door where the levels are bytes, the float door on to_float() otherwise
     frames = (lambda v: v.to_rgb()) if a.depth == 8 else (lambda v: v.to_float())
     return torch.stack([frames(video.left), frames(video.right)], dim=1), {}
@@ -140,6 +173,8 @@ DOORS = {  # door: (video, side_a, what side A is, what side B is[, side A's vid
             "the RawStereoVideo itself (ppms_video_ingest_raw)"),
     "packed": (packed_video, packed_side_a, "unpack() in torch on the device, then the unpacked door (ppms_video_ingest_yuv / ppms_video_ingest_raw)",
                "the packed stereo video itself (ppms_video_ingest_yuv_packed / ppms_video_ingest_raw_packed)"),
+    "rgb": (rgb_video, rgb_side_a, "frames.permute(0, 3, 1, 2)[:, order].contiguous() on the device, then the uint8 door (deep layouts: to_float(), the float door)",
+            "the interleaved frames themselves (ppms_video_ingest_rgb_packed)"),
 }
 
 
@@ -360,8 +395,13 @@ def door_report(a, A, B):
         sums = {s: s.ask(CALL_S, "sum")[0] for s in (A, B)}
         fmt = {"u8": "", "yuv": "NV12 ", "remap": f"{'NV12' if a.yuv else 'RGB'} source {HS}x{WS} -> rectified ",
                "deep": f"{a.depth}-bit {a.chroma} planar frames ({a.align}) ", "raw": f"{a.depth}-bit {a.pattern} frames ({a.align}) ",
-               "packed": f"{a.layout} frames " + (f"({a.depth if a.depth in (10, 12) else 10}-bit {a.pattern}) " if a.layout in RAW_PACKINGS else "")}[a.door]
+               "packed": f"{a.layout} frames " + (f"({a.depth if a.depth in (10, 12) else 10}-bit {a.pattern}) " if a.layout in RAW_PACKINGS else ""),
+               "rgb": f"{a.layout} frames " + (f"({rgb_depth(a)}-bit, {a.align}) " if a.layout in RGB_LAYOUTS and not RGB_LAYOUTS[a.layout] else "")}[a.door]
         print(f"== --door {a.door}: T = {T}, {fmt}{h}x{w}, iters = {ITERS}: forward_batch_test(video) -> host disparity, {runs} alternating calls per side")
+        if a.door == "rgb":
+            own, planar = rgb_bytes(a)
+            print(f"by construction, not measured: per pixel and view the ingest launch of side B reads the frames' own {own} bytes; side A reads them too, "
+                  f"writes {planar} bytes of planar video and its ingest reads those {planar} again")
         for s in (A, B):
             v = ms[s]
             print(f"{s.label}:")
@@ -408,7 +448,8 @@ def main():
     ap.add_argument("--chroma", default="420", choices=("420", "422", "444"), help="--door deep")
     ap.add_argument("--align", default=None, choices=("msb", "lsb"), help="--door deep (default msb) / raw (default lsb)")
     ap.add_argument("--pattern", default="rggb", choices=("rggb", "bggr", "grbg", "gbrg", "mono"), help="--door raw")
-    ap.add_argument("--layout", default="yuyv", choices=sorted(YUV_LAYOUTS) + list(RAW_PACKINGS), help="--door packed (mipi / pfnc: with --depth 10 | 12, --pattern)")
+    ap.add_argument("--layout", default=None, choices=sorted(YUV_LAYOUTS) + list(RAW_PACKINGS) + sorted(RGB_LAYOUTS),
+                    help="--door packed (default yuyv; mipi / pfnc: with --depth 10 | 12, --pattern) / rgb (default bgr24; rgb48 ...: with --depth 10 | 12, --align)")
     ap.add_argument("--worker", default=None)
     ap.add_argument("--tree", default=HERE)
     a = ap.parse_args()
@@ -418,7 +459,10 @@ def main():
         ap.error("--kernels compares against --parent DIR")
     if a.door == "deep" and (a.depth, a.chroma) == (8, "420"):
         ap.error("8-bit 4:2:0 is --door yuv (ppms_video_ingest_yuv420); choose another --depth or --chroma")
-    a.align = a.align or ("msb" if a.door == "deep" else "lsb")
+    a.align = a.align or ("msb" if a.door in ("deep", "rgb") else "lsb")
+    a.layout = a.layout or ("bgr24" if a.door == "rgb" else "yuyv")
+    if not a.worker and (a.door == "rgb") != (a.layout in RGB_LAYOUTS) and a.door in ("rgb", "packed"):
+        ap.error(f"--layout {a.layout} does not go with --door {a.door}")
     a.runs = a.runs or (7 if a.kernels else 12)
     if a.worker:
         return (kernels_worker if a.kernels else door_worker)(a, os.path.abspath(a.tree))
