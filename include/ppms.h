@@ -358,6 +358,59 @@ int     ppms_cloud_struct_size(void);  /* sizeof(ppms_cloud) (152) */
 int     ppms_cloud_egress_colour(const float* flow_up, const float* unc, int T, int H, int W, int frame0, int n_frames, int pad_left, int pad_top,
                                  int H0, int W0, const ppms_cloud* out, const ppms_egress_plane* colour, void* stream);
 
+/* Surface normals: one unit normal per pixel of the cropped plane, from a 3 x 3 stencil (its cross: left, right, up, down) over the organised
+ * points -- what a caller computes on the host from the points plane before ICP, fusion, segmentation or meshing.  One launch; arguments,
+ * sources, crop and frame range are ppms_scene_egress's.  Per frame, over the CROPPED H0 x W0 plane only: a neighbour outside the crop does not
+ * exist, even where the padded frame has a value there.  P(y, x) = (X, Y, Z): the fp32 organised points exactly as ppms_scene_egress defines
+ * them (v_i, three divisions), whatever format a points plane or a cloud has; ok(y, x): their validity (d >= min_disp, the max_uncertainty gate,
+ * the max_depth gate Z > 0 && Z <= max_depth).  Every step ONE fp32 operation rounded to nearest even, in the order written:
+ *   1. neighbour N of centre C is usable iff N is inside the crop, ok(N) and ok(C), and (max_jump is +inf (gate off, not evaluated), or
+ *      fabsf(Z_N - Z_C) <= max_jump * fabsf(Z_C))
+ *   2. tangents.  Horizontal, L = (y, x - 1), R = (y, x + 1): both usable tx = P_R - P_L; only R: tx = P_R - P_C; only L: tx = P_C - P_L; neither:
+ *      the normal is invalid.  Vertical ty likewise with U = (y - 1, x) as the minus side and D = (y + 1, x) as the plus side.
+ *   3. n = ty x tx, each component two products and one subtraction:
+ *      n0 = ty1 * tx2 - ty2 * tx1,  n1 = ty2 * tx0 - ty0 * tx2,  n2 = ty0 * tx1 - ty1 * tx0
+ *   4. orientation towards the origin: s = (n0 * X + n1 * Y) + n2 * Z of the centre; if s > 0 then n = -n
+ *   5. l = sqrt((n0 * n0 + n1 * n1) + n2 * n2), correctly rounded.  The normal is valid iff ok(C), both tangents exist, l > 0 and l is finite;
+ *      a valid normal is n_i / l (correctly rounded divisions), an invalid one carries NaN in all three components (payload unspecified).
+ * normals plane: 3 elements per pixel, nx, ny, nz, pixel after pixel along the row (a row: W0 * 3 elements; pitch and frame_stride in bytes):
+ * F32 the values, F16 their rounding to nearest even.  The kernel computes every point of a 16 x 128 tile and its one-pixel rim once, keeps them
+ * in LDS and forms the stencil from there; nobody has timed it.  `out` is HOST memory, read before the call returns.
+ * Refused with PPMS_EINVAL before any launch: the geometry and the frame range ppms_disparity_egress refuses (one shared check); a null struct,
+ * normals.ptr or flow_up; normals.format other than F32 / F16; a pitch shorter than the row, with n_frames > 1 a frame_stride shorter than a
+ * plane, a pointer, pitch or frame_stride that is no multiple of the element; normals.reserved != 0; a non-finite entry of q or min_disp; a NaN
+ * max_uncertainty; max_depth <= 0 or NaN; max_jump <= 0 or NaN; unc == NULL with the max_uncertainty gate on; reserved != 0; n_frames > 65535.
+ * Not covered: larger stencils or smoothing, curvature, the right view, integer-packed normals. */
+typedef struct ppms_normals {
+    ppms_egress_plane normals;        /* n_frames x H0 rows of W0 * 3 elements, PPMS_FMT_F32 or PPMS_FMT_F16 */
+    float q[16];                      /* the 4x4 reprojection matrix, row major */
+    float min_disp, max_uncertainty, max_depth;   /* +inf: gate off (the last two) */
+    float max_jump;                   /* > 0; +inf: the jump gate is off */
+    int32_t reserved;                 /* 0 */
+} ppms_normals;
+int     ppms_normals_egress(const float* flow_up, const float* unc, int T, int H, int W, int frame0, int n_frames, int pad_left, int pad_top,
+                            int H0, int W0, const ppms_normals* out, void* stream);
+int     ppms_normals_struct_size(void);   /* sizeof(ppms_normals) (120) */
+/* The oriented compact cloud (PCL's PointNormal / PointXYZRGBNormal): ppms_cloud_egress with the normal behind every record.  `normals`: the device
+ * plane ppms_normals_egress wrote for the same arguments (n_frames x H0 x W0 x 3, frame f of the launch); the cloud's launches READ it, as the
+ * coloured cloud reads the colour plane, and do not recompute the stencil.
+ *   out->components = 6: records X, Y, Z, nx, ny, nz in out->format (F32: 24 bytes, F16: 12); normals->format must equal out->format; colour
+ *                        must be NULL
+ *   out->components = 7: records X, Y, Z, colour word, nx, ny, nz (28 bytes); out->format and normals->format PPMS_FMT_F32; colour is required
+ *                        (ppms_cloud_egress_colour's plane)
+ * A record is kept iff its point is valid AND its normal is valid: the first component of the normals plane is not NaN at that pixel.  Point
+ * validity and the bits of X, Y, Z are ppms_cloud_egress's; the normal's words and the colour word travel as integers from their loads to their
+ * stores.  counts, order, index, truncation at capacity: as ppms_cloud_egress (counts report the full number; rows past min(count, capacity) are
+ * never written).  Two launches, count then place, no atomics, the same order in every run.  A workgroup takes half the pixels of
+ * ppms_cloud_egress's (its staged records are up to 28 bytes), so block_counts is workspace of ppms_cloud_egress_normals_workspace entries.
+ * Refused with PPMS_EINVAL before any launch: everything ppms_cloud_egress refuses (one shared check; unc == NULL only with the gate on), with
+ * components other than 6 / 7 in the place of 3 / 4; a null normals or normals->ptr; a normals format other than F32 / F16 or other than
+ * out->format; a normals pitch, frame_stride or alignment egress planes are refused for; normals->reserved != 0; components = 6 with a colour
+ * plane; components = 7 without one, with a format other than F32, or with a colour plane ppms_cloud_egress_colour refuses. */
+int     ppms_cloud_egress_normals(const float* flow_up, const float* unc, int T, int H, int W, int frame0, int n_frames, int pad_left, int pad_top,
+                                  int H0, int W0, const ppms_cloud* out, const ppms_egress_plane* normals, const ppms_egress_plane* colour, void* stream);
+int64_t ppms_cloud_egress_normals_workspace(int n_frames, int H0, int W0);   /* entries block_counts needs; 0 for a geometry the call refuses */
+
 /* Scale-to-scale hand-over of the cascade without leaving the SP format (ppmstereo.py:726-732, 763-767): per frame,
  * dst = a * dst + b * interp(src), interp = F.interpolate(mode="bilinear", align_corners=True) from HxW to OHxOW.
  * src, dst: SP views with the same channel count (multiple of 8). */

@@ -143,6 +143,12 @@ class Cloud(C.Structure):
                 ("max_uncertainty", c_float), ("max_depth", c_float), ("format", C.c_int32), ("components", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Normals(C.Structure):
+    """ppms_normals: the normals plane (3 elements per pixel), Q, min_disp, the two gates and the jump gate (+inf: off)."""
+    _fields_ = [("normals", EgressPlane), ("q", c_float * 16), ("min_disp", c_float), ("max_uncertainty", c_float), ("max_depth", c_float),
+                ("max_jump", c_float), ("reserved", C.c_int32)]
+
+
 _SIGS = {
     "ppms_version": (c_int, []),
     "ppms_last_error": (C.c_char_p, []),
@@ -247,6 +253,11 @@ for _door, _head in _INGEST_HEADS.items():
     _SIGS["ppms_video_colour_" + _door] = (c_int, _head + _COLOUR_TAIL)
     _SIGS["ppms_video_colour_" + _door + "_remap"] = (c_int, _head + [C.POINTER(RemapView)] * 2 + _COLOUR_TAIL)
 _SIGS["ppms_cloud_egress_colour"] = (c_int, _SIGS["ppms_cloud_egress"][1][:-1] + [C.POINTER(EgressPlane), c_void_p])
+# normals out: the plane's launch (ppms_cloud_egress's list with its own struct) and the oriented compact cloud (that list + the normals and colour planes)
+_SIGS["ppms_normals_egress"] = (c_int, _SIGS["ppms_cloud_egress"][1][:-2] + [C.POINTER(Normals), c_void_p])
+_SIGS["ppms_normals_struct_size"] = (c_int, [])
+_SIGS["ppms_cloud_egress_normals"] = (c_int, _SIGS["ppms_cloud_egress"][1][:-1] + [C.POINTER(EgressPlane), C.POINTER(EgressPlane), c_void_p])
+_SIGS["ppms_cloud_egress_normals_workspace"] = (c_int64, [c_int, c_int, c_int])
 EXPORTS = tuple(_SIGS)
 
 # (the export that reports sizeof of the structs, their ctypes twins, the message when they differ).  An export takes one int* per struct; one
@@ -263,6 +274,7 @@ _STRUCT_SIZES = (
     ("ppms_egress_struct_size", (Egress,), "ctypes layout of ppms_egress differs from include/ppms.h"),
     ("ppms_egress3d_struct_size", (Egress3D,), "ctypes layout of ppms_egress3d differs from include/ppms.h"),
     ("ppms_cloud_struct_size", (Cloud,), "ctypes layout of ppms_cloud differs from include/ppms.h"),
+    ("ppms_normals_struct_size", (Normals,), "ctypes layout of ppms_normals differs from include/ppms.h"),
     ("ppms_pwchain_param_bytes", (ChainParams,), "ChainParams layout differs from pwchain.hip"),
 )
 

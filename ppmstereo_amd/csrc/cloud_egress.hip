@@ -6,81 +6,10 @@
 //          thread, a wave64 scan of __shfl_up, a four-wave scan through LDS) and writes record k of its own at base + k.
 // The grid is (workgroups per frame, n_frames): a workgroup takes 256 consecutive runs of ONE frame with egress_map's mapping, so thread order is
 // row-major pixel order.  Validity and X, Y, Z come from cloud_points in both launches: every operation one fp32 operation in ppms_scene_egress's
-// order, so the two launches agree on every pixel and the records carry the organised plane's bits.
+// order, so the two launches agree on every pixel and the records carry the organised plane's bits.  (cloud_points, cloud_thread, the scan, the
+// flush and cloud_check: egress_shared.h -- normals_egress.hip's oriented cloud is built from the same ones.)
 #include "egress_shared.h"
 
-constexpr int CLOUD_WG = 256;
-constexpr int CLOUD_PIXELS = CLOUD_WG * EG_RUN;                          // pixels of a workgroup: the most records it places (2048)
-
-// d, u (where a gate or w reads it), X, Y, Z of the run's pixels; returns the validity mask, bit j = pixel j of the run (0 past the row's end).
-// scene_egress_kernel's arithmetic, restated: that kernel does not call this function, its generated code stays as it is.
-__device__ __forceinline__ unsigned cloud_points(const float* __restrict__ flow_up, const float* __restrict__ unc, const ppms_cloud& c, bool want_w,
-                                                 int H, int W, int frame0, float sh, float sw, const egress_run& r, float (&X)[EG_RUN],
-                                                 float (&Y)[EG_RUN], float (&Z)[EG_RUN], float (&u)[EG_RUN]) {
-    const bool gate_u = c.max_uncertainty < INFINITY, gate_z = c.max_depth < INFINITY;
-    if (gate_u || want_w) {
-        egress_load_uncertainty(unc, H, W, frame0, sh, sw, r, u);
-    } else {
-#pragma unroll
-        for (int j = 0; j < EG_RUN; ++j) u[j] = 0.0f;
-    }
-    float d[EG_RUN];
-    egress_load_disparity(flow_up, H, W, frame0, r, d);
-    const float yf = (float)r.y;                                          // the pixel's row and column in the cropped plane
-    float qy[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) qy[i] = c.q[4 * i + 1] * yf;
-    unsigned mask = 0;
-#pragma unroll
-    for (int j = 0; j < EG_RUN; ++j) {
-        const bool ok = d[j] >= c.min_disp && (!gate_u || u[j] <= c.max_uncertainty);     // valid_d and valid_u (both false for NaN)
-        const float xf = (float)(r.x0 + j);
-        float v[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = ((c.q[4 * i] * xf + qy[i]) + c.q[4 * i + 2] * d[j]) + c.q[4 * i + 3];
-        const float pz = __fdiv_rn(v[2], v[3]);
-        const bool okp = ok && (!gate_z || (pz > 0.0f && pz <= c.max_depth));
-        X[j] = __fdiv_rn(v[0], v[3]);
-        Y[j] = __fdiv_rn(v[1], v[3]);
-        Z[j] = pz;
-        mask |= (okp && j < r.n) ? 1u << j : 0u;
-    }
-    return mask;
-}
-// the thread's run of frame blockIdx.y (ridx: its number inside the frame) and its points; an idle thread past the frame's last run has no pixel
-__device__ __forceinline__ unsigned cloud_thread(const float* __restrict__ flow_up, const float* __restrict__ unc, const ppms_cloud& c, bool want_w,
-                                                 int H, int W, int frame0, int pad_left, int pad_top, int H0, int W0, float sh, float sw, int rpr,
-                                                 int64_t runs, egress_run& r, float (&X)[EG_RUN], float (&Y)[EG_RUN], float (&Z)[EG_RUN],
-                                                 float (&u)[EG_RUN]) {
-    const int64_t ridx = (int64_t)blockIdx.x * CLOUD_WG + threadIdx.x;
-    if (ridx >= runs) return 0u;
-    r = egress_map((int64_t)blockIdx.y * runs + ridx, rpr, H0, W0, pad_left, pad_top);
-    return cloud_points(flow_up, unc, c, want_w, H, W, frame0, sh, sw, r, X, Y, Z, u);
-}
-// exclusive prefix sum of v over the workgroup's 256 threads in thread order, and the workgroup's total: a wave64 scan, then the four waves'
-// totals through LDS (ws: 4 ints).  Integer sums in a fixed order; ws may be used again after the call.
-struct cloud_scan { int before, total; };
-__device__ __forceinline__ cloud_scan cloud_block_scan(int v, int* ws) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int s = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(s, off);
-        if (lane >= off) s += t;
-    }
-    if (lane == 63) ws[wave] = s;
-    __syncthreads();
-    cloud_scan out;
-    out.before = s - v;
-    out.total = 0;
-#pragma unroll
-    for (int i = 0; i < CLOUD_WG / 64; ++i) {
-        if (i < wave) out.before += ws[i];
-        out.total += ws[i];
-    }
-    __syncthreads();
-    return out;
-}
 __global__ __launch_bounds__(CLOUD_WG) void cloud_count_kernel(const float* __restrict__ flow_up, const float* __restrict__ unc, ppms_cloud c, int H, int W,
                                                                int frame0, int pad_left, int pad_top, int H0, int W0, float sh, float sw, int rpr,
                                                                int64_t runs) {
@@ -90,18 +19,6 @@ __global__ __launch_bounds__(CLOUD_WG) void cloud_count_kernel(const float* __re
     const unsigned mask = cloud_thread(flow_up, unc, c, false, H, W, frame0, pad_left, pad_top, H0, W0, sh, sw, rpr, runs, r, X, Y, Z, u);
     const cloud_scan s = cloud_block_scan(__popc(mask), ws);
     if (threadIdx.x == 0) c.block_counts[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = s.total;
-}
-// The workgroup's staged bytes [lo, hi) of `smem` -> global `gbase + the same offset`.  smem and gbase are congruent mod 16 (the staging is
-// shifted by the destination's misalignment), so the whole 16-byte slots inside the range go out as 16-byte stores; the head in front of the
-// first whole slot and the tail behind the last one element by element (E: the element, which lo and hi are multiples of).
-template <class E>
-__device__ __forceinline__ void cloud_flush(const char* smem, char* gbase, int lo, int hi) {
-    int first = (lo + 15) & ~15, last = hi & ~15;
-    if (last < first) first = last = hi;                                 // no whole slot: all of it element by element
-    for (int off = first + (int)threadIdx.x * 16; off < last; off += CLOUD_WG * 16) gstore16(gbase + off, *(const u32x4*)(smem + off));
-    const int head = (first - lo) / (int)sizeof(E), tail = (hi - last) / (int)sizeof(E);         // fewer than 16 / sizeof(E) elements each
-    if ((int)threadIdx.x < head) *(E*)(gbase + lo + threadIdx.x * sizeof(E)) = *(const E*)(smem + lo + threadIdx.x * sizeof(E));
-    if ((int)threadIdx.x < tail) *(E*)(gbase + last + threadIdx.x * sizeof(E)) = *(const E*)(smem + last + threadIdx.x * sizeof(E));
 }
 template <class T, int C>
 __global__ __launch_bounds__(CLOUD_WG) void cloud_place_kernel(const float* __restrict__ flow_up, const float* __restrict__ unc, ppms_cloud c, int H, int W,
@@ -208,47 +125,12 @@ __global__ __launch_bounds__(CLOUD_WG) void cloud_place_colour_kernel(const floa
     if (dsti) cloud_flush<int32_t>(sidx, dsti - shifti, shifti, shifti + n * 4);
 }
 extern "C" int ppms_cloud_struct_size(void) { return (int)sizeof(ppms_cloud); }
-// workgroups per frame; 0 for a geometry the entry point refuses
-static int64_t cloud_blocks_per_frame(int H0, int W0) {
-    if (H0 <= 0 || W0 <= 0 || (int64_t)H0 * W0 > 0x7fffffff) return 0;
-    return ((int64_t)H0 * ((W0 + EG_RUN - 1) / EG_RUN) + CLOUD_WG - 1) / CLOUD_WG;
-}
 extern "C" int64_t ppms_cloud_egress_workspace(int n_frames, int H0, int W0) { return n_frames <= 0 ? 0 : n_frames * cloud_blocks_per_frame(H0, W0); }
-// what both entry points check, under the name `who` of the one called; on success the launch geometry and the workgroups per frame.
-// `colour`: ppms_cloud_egress_colour -- the fourth component is the colour word, so nothing but the max_uncertainty gate reads unc
-static int cloud_check(const char* who, const float* flow_up, const float* unc, int T, int H, int W, int frame0, int n_frames, int pad_left, int pad_top,
-                       int H0, int W0, const ppms_cloud* out, bool colour, egress_launch& g, int64_t* blocks_out) {
-    PPMS_REQUIRE(out, "%s: null out struct", who);
-    const ppms_cloud& c = *out;
-    if (const int rc = egress_check_geometry(who, T, H, W, frame0, n_frames, pad_left, pad_top, H0, W0, &g)) return rc;
-    PPMS_REQUIRE((int64_t)H0 * W0 <= 0x7fffffff, "%s: H0 * W0 = %lld pixel indices exceed int32", who, (long long)H0 * W0);
-    PPMS_REQUIRE(n_frames <= 65535, "%s: n_frames = %d exceeds one grid", who, n_frames);
-    PPMS_REQUIRE(flow_up != nullptr, "%s: null flow_up", who);
-    PPMS_REQUIRE(c.records != nullptr, "%s: null records", who);
-    PPMS_REQUIRE(c.counts != nullptr, "%s: null counts", who);
-    PPMS_REQUIRE(c.format == PPMS_FMT_F32 || c.format == PPMS_FMT_F16, "%s: format = %d is neither PPMS_FMT_F32 nor PPMS_FMT_F16", who, c.format);
-    PPMS_REQUIRE(c.components == 3 || c.components == 4, "%s: components = %d must be 3 or 4", who, c.components);
-    PPMS_REQUIRE(c.reserved == 0, "%s: reserved = %d must be 0", who, c.reserved);
-    PPMS_REQUIRE(c.capacity > 0 && c.capacity <= 0x7fffffff, "%s: capacity = %lld must be in 1 .. 2^31 - 1", who, (long long)c.capacity);
-    // a frame of records, and of indices (int32: 4-byte elements, as PPMS_FMT_F32 has), is one dense row of `capacity` of them
-    if (const int rc = egress_check_strided(who, "records", "frame_stride", c.records, c.frame_stride, nullptr, c.format, n_frames, 1, c.capacity * c.components))
-        return rc;
-    if (c.index)
-        if (const int rc = egress_check_strided(who, "index", "index_frame_stride", c.index, c.index_frame_stride, nullptr, PPMS_FMT_F32, n_frames, 1, c.capacity))
-            return rc;
-    PPMS_REQUIRE((uintptr_t)c.counts % 4 == 0 && (uintptr_t)c.block_counts % 4 == 0, "%s: counts and block_counts must be multiples of the 4-byte element", who);
-    const int64_t blocks = cloud_blocks_per_frame(H0, W0);
-    PPMS_REQUIRE(c.block_counts != nullptr && c.block_counts_len >= n_frames * blocks,
-                 "%s: block_counts is null or block_counts_len = %lld is less than the %lld entries of ppms_cloud_egress_workspace", who,
-                 (long long)c.block_counts_len, (long long)(n_frames * blocks));
-    *blocks_out = blocks;
-    return egress_check_reprojection(who, unc, c.q, c.min_disp, c.max_uncertainty, c.max_depth, true, true, colour ? 3 : c.components);
-}
 extern "C" int ppms_cloud_egress(const float* flow_up, const float* unc, int T, int H, int W, int frame0, int n_frames, int pad_left, int pad_top, int H0,
                                  int W0, const ppms_cloud* out, void* stream) {
     egress_launch g;
     int64_t blocks;
-    if (const int rc = cloud_check("cloud_egress", flow_up, unc, T, H, W, frame0, n_frames, pad_left, pad_top, H0, W0, out, false, g, &blocks)) return rc;
+    if (const int rc = cloud_check("cloud_egress", flow_up, unc, T, H, W, frame0, n_frames, pad_left, pad_top, H0, W0, out, CLOUD_PLAIN, g, &blocks)) return rc;
     const ppms_cloud& c = *out;
     const int64_t runs = (int64_t)H0 * g.rpr;                            // runs of one frame
     const dim3 grid((unsigned)blocks, (unsigned)n_frames), wg(CLOUD_WG);
@@ -271,7 +153,7 @@ extern "C" int ppms_cloud_egress_colour(const float* flow_up, const float* unc, 
     const char* who = "cloud_egress_colour";
     egress_launch g;
     int64_t blocks;
-    if (const int rc = cloud_check(who, flow_up, unc, T, H, W, frame0, n_frames, pad_left, pad_top, H0, W0, out, true, g, &blocks)) return rc;
+    if (const int rc = cloud_check(who, flow_up, unc, T, H, W, frame0, n_frames, pad_left, pad_top, H0, W0, out, CLOUD_COLOUR, g, &blocks)) return rc;
     const ppms_cloud& c = *out;
     PPMS_REQUIRE(c.components == 4, "%s: components = %d must be 4: X, Y, Z and the colour word", who, c.components);
     PPMS_REQUIRE(c.format == PPMS_FMT_F32, "%s: format = %d must be PPMS_FMT_F32: the colour word is the fourth 32-bit word of a record", who, c.format);

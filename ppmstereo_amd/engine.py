@@ -700,16 +700,17 @@ class ScaleEngine:
         self.hbm["convex_upsample"]()
         return self.FLOW_OUT
 
-    def egress(self, out, frame0: int, n_frames: int, pad_left: int, pad_top: int, h0: int, w0: int, colour=None):
+    def egress(self, out, frame0: int, n_frames: int, pad_left: int, pad_top: int, h0: int, w0: int, colour=None, normals=None):
         """ppms_disparity_egress (``out``: an L.Egress), ppms_scene_egress (an L.Egress3D: points, gates) or ppms_cloud_egress (an L.Cloud: the
         compact cloud's two launches) on the current stream: the state the
         last iteration left -- FLOW_OUT (read in place, channel 0) and the
         1/4-resolution UNC -- to the caller's planes: frames [frame0, frame0 + n_frames), the h0 x w0 crop at (pad_top, pad_left).  Valid
         behind an iterate(need_up=True) of an unsharded engine at the 1/4 scale (full resolution = 4 h x 4 w).  colour (with an L.Cloud): the
-        L.EgressPlane of the crop's colour pixels -- ppms_cloud_egress_colour, the coloured cloud."""
+        L.EgressPlane of the crop's colour pixels -- ppms_cloud_egress_colour, the coloured cloud.  An L.Normals: ppms_normals_egress, the normals
+        plane; normals (with an L.Cloud): the L.EgressPlane of that plane -- ppms_cloud_egress_normals, the oriented cloud."""
         if self.shard is not None:
             raise NotImplementedError("ScaleEngine.egress: a frame-sharded engine holds a part of the window")
-        disparity_egress(self.FLOW_OUT, self.UNC.view(self.T, self.h, self.w), out, frame0, n_frames, pad_left, pad_top, h0, w0, colour)
+        disparity_egress(self.FLOW_OUT, self.UNC.view(self.T, self.h, self.w), out, frame0, n_frames, pad_left, pad_top, h0, w0, colour, normals)
 
     def _prep_k(self):
         key, key_ld, sel, shat, with_pick = self._prep_k_args
@@ -759,22 +760,29 @@ def bilinear(x: torch.Tensor, size, align_corners: bool, mul: float = 1.0) -> to
 
 
 def disparity_egress(flow_up: torch.Tensor, unc: torch.Tensor, out, frame0: int, n_frames: int, pad_left: int, pad_top: int, h0: int, w0: int,
-                     colour=None):
+                     colour=None, normals=None):
     """One ppms_disparity_egress launch on the current stream (include/ppms.h): flow_up fp32 (T, 2, H, W), unc fp32 (T, H/4, W/4), both
     contiguous on the GPU; ``out``: the planes (device pointers, byte strides, formats) and conversion constants.  An ``L.Egress3D`` (the same
     with a points plane, Q and the gates) makes it one ppms_scene_egress launch, an ``L.Cloud`` (the compact cloud's destinations, workspace, Q and
     gates) the two launches of ppms_cloud_egress -- or, with ``colour`` (an ``L.EgressPlane``: the n_frames x h0 x w0 colour pixels of the crop, on
-    the device), of ppms_cloud_egress_colour: the coloured cloud, whose fourth word is the colour pixel."""
+    the device), of ppms_cloud_egress_colour: the coloured cloud, whose fourth word is the colour pixel.  An ``L.Normals`` (the normals plane, Q, the
+    gates and the jump gate) makes it one ppms_normals_egress launch; an ``L.Cloud`` with ``normals`` (an ``L.EgressPlane``: the plane that launch
+    wrote for the same crop and frames) the two launches of ppms_cloud_egress_normals, the oriented cloud -- with ``colour`` beside it for 7 components."""
     L.require_gpu(flow_up, unc)
     T, two, H, W = flow_up.shape
     if (flow_up.dtype != torch.float32 or unc.dtype != torch.float32 or two != 2 or tuple(unc.shape) != (T, H // 4, W // 4)
             or not flow_up.is_contiguous() or not unc.is_contiguous()):
         raise ValueError(f"disparity_egress: contiguous fp32 flow_up (T, 2, H, W) and unc (T, H/4, W/4) expected, got {tuple(flow_up.shape)} and {tuple(unc.shape)}")
-    if not isinstance(out, (L.Egress, L.Egress3D, L.Cloud)):
-        raise TypeError(f"disparity_egress: out must be an L.Egress, an L.Egress3D or an L.Cloud, got {type(out).__name__}")
+    if not isinstance(out, (L.Egress, L.Egress3D, L.Cloud, L.Normals)):
+        raise TypeError(f"disparity_egress: out must be an L.Egress, an L.Egress3D, an L.Cloud or an L.Normals, got {type(out).__name__}")
     if colour is not None and not (isinstance(out, L.Cloud) and isinstance(colour, L.EgressPlane)):
         raise TypeError(f"disparity_egress: colour is an L.EgressPlane beside an L.Cloud, got {type(colour).__name__} beside {type(out).__name__}")
-    entry = {L.Egress: "ppms_disparity_egress", L.Egress3D: "ppms_scene_egress", L.Cloud: "ppms_cloud_egress"}[type(out)]
-    entry = getattr(L.load(), entry + ("" if colour is None else "_colour"))
-    extra = () if colour is None else (C.byref(colour),)
+    if normals is not None and not (isinstance(out, L.Cloud) and isinstance(normals, L.EgressPlane)):
+        raise TypeError(f"disparity_egress: normals is an L.EgressPlane beside an L.Cloud, got {type(normals).__name__} beside {type(out).__name__}")
+    entry = {L.Egress: "ppms_disparity_egress", L.Egress3D: "ppms_scene_egress", L.Cloud: "ppms_cloud_egress", L.Normals: "ppms_normals_egress"}[type(out)]
+    if normals is not None:                                  # the oriented cloud: the normals plane, then the colour plane or NULL
+        entry, extra = getattr(L.load(), entry + "_normals"), (C.byref(normals), None if colour is None else C.byref(colour))
+    else:
+        entry = getattr(L.load(), entry + ("" if colour is None else "_colour"))
+        extra = () if colour is None else (C.byref(colour),)
     L.check(entry(flow_up.data_ptr(), unc.data_ptr(), T, H, W, frame0, n_frames, pad_left, pad_top, h0, w0, C.byref(out), *extra, L.stream_ptr()))

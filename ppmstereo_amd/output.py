@@ -11,7 +11,9 @@ from . import _lib as L
 _PLANE_FORMATS = {"f32": (L.FMT_F32, torch.float32), "f16": (L.FMT_F16, torch.float16), "u16": (L.FMT_U16, torch.uint16), "u8": (L.FMT_U8, torch.uint8),
                   "i32": (None, torch.int32),      # (i32: the compact cloud's counts and pixel indices, no format of a plane)
                   "rgba8": (L.FMT_RGBA8, torch.uint8), "bgra8": (L.FMT_BGRA8, torch.uint8)}      # (the colour plane: 4 bytes per pixel)
-_COMPONENTS = {"xyz": 3, "xyzw": 4, "xyzrgb": 4}   # of a record, by layout ("xyzrgb": the cloud only)
+_COMPONENTS = {"xyz": 3, "xyzw": 4, "xyzrgb": 4, "xyzn": 6, "xyzrgbn": 7}   # of a record, by layout ("xyzrgb" and the two with normals: the cloud only)
+_CLOUD_LAYOUTS = ("xyz", "xyzw", "xyzrgb", "xyzn", "xyzrgbn")
+_COLOURED, _ORIENTED = ("xyzrgb", "xyzrgbn"), ("xyzn", "xyzrgbn")       # cloud layouts whose records carry the colour word / the normal
 
 
 class OutputSpec:
@@ -58,13 +60,31 @@ class OutputSpec:
                        -- copied as an integer (ppms_cloud_egress_colour), never through a float operation.  Needs cloud="f32" and colour=.
                        ``points_layout="xyzrgb"`` does not exist (ValueError): the "colour" plane beside the points is their colour.
       colour_plane     True | False: False keeps the device plane as workspace of the "xyzrgb" cloud and leaves "colour" out of the result and of
-                       the device -> host copies.  Only with cloud_layout="xyzrgb"."""
+                       the device -> host copies.  Only with cloud_layout="xyzrgb" (or "xyzrgbn").
+      normals          None | "f32" | "f16": the surface normal per pixel -- a stereo SDK's NORMALS measure, what ``IntegralImageNormalEstimation`` or
+                       ``estimate_normals`` make of "points" on the host --, result key "normals" with the shape (n, h0, w0, 3), from one more launch
+                       (ppms_normals_egress) behind the planes' one.  A unit vector from the cross stencil (left, right, up, down) over the fp32
+                       organised points of the cropped plane, whatever format ``points`` or ``cloud`` have: per direction the central difference
+                       where both neighbours are usable, a one-sided one where one is; n = ty x tx, turned towards the camera, divided by its
+                       length (include/ppms.h and ``reference``: every step, in order).  A neighbour is usable when it lies inside the crop, it and
+                       the centre are valid points (min_disp and both gates) and it passes the jump gate.  A pixel without a tangent in either
+                       direction, with an invalid centre or with a length that is 0 or not finite carries NaN in all three components.  Needs Q
+                       and a finite min_disp, as points do.  Beside "points" it is that cloud's normals, record for record.
+      normal_max_jump  float > 0 | None: the jump gate, |Z_N - Z_C| <= normal_max_jump * |Z_C| for neighbour N of centre C, keeps a tangent from
+                       spanning a depth edge.  None or +inf: off.
+      cloud_layout     also "xyzn": C = 6, X, Y, Z, nx, ny, nz in the cloud's format (PCL's PointNormal; 24-byte records in f32, 12 in f16), and
+                       "xyzrgbn": C = 7, X, Y, Z, the colour word, nx, ny, nz (PointXYZRGBNormal; 28 bytes; needs cloud="f32" and colour=).  Both
+                       need normals= in the cloud's format.  A record is kept iff its point AND its normal are valid; the cloud's launches
+                       (ppms_cloud_egress_normals) read the normals plane, they do not recompute it.
+      normals_plane    True | False: False keeps the device plane as workspace of those two clouds and leaves "normals" out of the result and of
+                       the device -> host copies.  Only with cloud_layout="xyzn" or "xyzrgbn"."""
 
     def __init__(self, disparity: str = "f32", depth: Optional[str] = None, uncertainty: Optional[str] = "f32", disp_scale: float = 256.0,
                  focal_px: Optional[float] = None, baseline: Optional[float] = None, depth_scale: float = 1000.0, min_disp: float = 2.0 ** -8,
                  *, points: Optional[str] = None, points_layout: str = "xyz", Q=None, max_uncertainty: Optional[float] = None,
                  max_depth: Optional[float] = None, cloud: Optional[str] = None, cloud_layout: str = "xyz", cloud_index: bool = False,
-                 cloud_capacity: Optional[int] = None, colour: Optional[str] = None, colour_plane: bool = True):
+                 cloud_capacity: Optional[int] = None, colour: Optional[str] = None, colour_plane: bool = True, normals: Optional[str] = None,
+                 normal_max_jump: Optional[float] = 0.05, normals_plane: bool = True):
         if disparity not in ("f32", "f16", "u16"):
             raise ValueError(f"OutputSpec: disparity = {disparity!r}; one of 'f32', 'f16', 'u16'")
         if depth not in (None, "f32", "f16", "u16"):
@@ -97,15 +117,16 @@ class OutputSpec:
         def records(name, needs, fmt, layout):           # what either record output, points or cloud, asks of its options and of the spec
             if fmt not in (None, "f32", "f16"):
                 raise ValueError(f"OutputSpec: {name} = {fmt!r}; None, 'f32' or 'f16'")
-            if layout not in (("xyz", "xyzw", "xyzrgb") if name == "cloud" else ("xyz", "xyzw")):
-                raise ValueError(f"OutputSpec: {name}_layout = {layout!r}; 'xyz' or 'xyzw'" + (" or 'xyzrgb'" if name == "cloud" else
-                                 " (colour per point: the 'colour' plane beside the points, or cloud_layout='xyzrgb')"))
+            if layout not in (_CLOUD_LAYOUTS if name == "cloud" else ("xyz", "xyzw")):
+                raise ValueError(f"OutputSpec: {name}_layout = {layout!r}; 'xyz' or 'xyzw'" + (" or 'xyzrgb', 'xyzn' or 'xyzrgbn'" if name == "cloud" else
+                                 " (colour per point: the 'colour' plane beside the points, or cloud_layout='xyzrgb'; normals: the 'normals' plane)"))
             if fmt is not None and self.Q is None:
                 raise ValueError(f"OutputSpec: {needs} Q, the 4x4 reprojection matrix of the rig's calibration (OutputSpec.q_matrix builds one)")
             if fmt is not None and not math.isfinite(self.min_disp):
                 raise ValueError(f"OutputSpec: min_disp = {min_disp} must be finite")
         records("points", "points need", points, points_layout)
         records("cloud", "a cloud needs", cloud, cloud_layout)
+        records("normals", "normals need", normals, "xyz")
         self.points, self.points_layout = points, points_layout
         if not isinstance(cloud_index, bool):
             raise ValueError(f"OutputSpec: cloud_index = {cloud_index!r}; True or False")
@@ -118,11 +139,23 @@ class OutputSpec:
             raise ValueError(f"OutputSpec: colour = {colour!r}; None, 'rgba8' or 'bgra8'")
         if not isinstance(colour_plane, bool):
             raise ValueError(f"OutputSpec: colour_plane = {colour_plane!r}; True or False")
-        if cloud_layout == "xyzrgb" and (cloud != "f32" or colour is None):
-            raise ValueError("OutputSpec: cloud_layout = 'xyzrgb' needs cloud = 'f32' (the colour pixel is the record's fourth 32-bit word) and colour=")
-        if not colour_plane and cloud_layout != "xyzrgb":
+        if cloud_layout in _COLOURED and (cloud != "f32" or colour is None):
+            raise ValueError(f"OutputSpec: cloud_layout = {cloud_layout!r} needs cloud = 'f32' (the colour pixel is the record's fourth 32-bit word) and colour=")
+        if not colour_plane and cloud_layout not in _COLOURED:
             raise ValueError("OutputSpec: colour_plane = False keeps the colour plane as the 'xyzrgb' cloud's workspace; without cloud_layout = 'xyzrgb' it has no meaning")
         self.colour, self.colour_plane = colour, colour_plane
+        if not isinstance(normals_plane, bool):
+            raise ValueError(f"OutputSpec: normals_plane = {normals_plane!r}; True or False")
+        jump = None if normal_max_jump is None else f32(normal_max_jump)
+        if jump is not None and not jump > 0.0:
+            raise ValueError(f"OutputSpec: normal_max_jump = {normal_max_jump} must be positive (None or +inf: the jump gate is off)")
+        if normals is None and (normal_max_jump is None or jump != f32(0.05)):
+            raise ValueError("OutputSpec: normal_max_jump describes the normals; without normals= it has no meaning")
+        if cloud_layout in _ORIENTED and normals != cloud:
+            raise ValueError(f"OutputSpec: cloud_layout = {cloud_layout!r} needs normals= in the cloud's format {cloud!r} (a record's elements have one size), got {normals!r}")
+        if not normals_plane and cloud_layout not in _ORIENTED:
+            raise ValueError("OutputSpec: normals_plane = False keeps the normals plane as the 'xyzn' / 'xyzrgbn' cloud's workspace; without one of those layouts it has no meaning")
+        self.normals, self.normals_plane, self.normal_max_jump = normals, normals_plane, (None if jump == math.inf else jump)       # +inf: the gate is off
         gate_u, gate_z = (None if g is None else f32(g) for g in (max_uncertainty, max_depth))
         if gate_u is not None and math.isnan(gate_u):
             raise ValueError("OutputSpec: max_uncertainty is NaN")
@@ -151,18 +184,20 @@ class OutputSpec:
         return self.points is not None or self.max_uncertainty is not None or self.max_depth is not None
 
     def formats(self) -> Dict[str, str]:
-        """{result key: format} of the requested planes, in the order disparity, depth, uncertainties, points, colour (unless colour_plane is
-        False), and of the compact cloud's arrays: cloud, cloud_counts, cloud_index."""
+        """{result key: format} of the requested planes, in the order disparity, depth, uncertainties, points, normals (unless normals_plane is
+        False), colour (unless colour_plane is False), and of the compact cloud's arrays: cloud, cloud_counts, cloud_index."""
         cloud = self.cloud is not None
         named = (("disparity", self.disparity), ("depth", self.depth), ("uncertainties", self.uncertainty), ("points", self.points),
+                 ("normals", self.normals if self.normals_plane else None),
                  ("colour", self.colour if self.colour_plane else None), ("cloud", self.cloud), ("cloud_counts", "i32" if cloud else None), ("cloud_index", "i32" if cloud and self.cloud_index else None))
         return {k: f for k, f in named if f is not None}
 
     def empty(self, n: int, h0: int, w0: int, device, pin_memory: bool = False, without=()) -> Dict[str, torch.Tensor]:
         """Dense (n, 1, h0, w0) tensors of the requested planes' dtypes; "points": (n, h0, w0, C); "cloud": (n, capacity, C), "cloud_counts": (n,)
-        and "cloud_index": (n, capacity) int32, capacity = cloud_capacity or h0 * w0; "colour": uint8 (n, h0, w0, 4)."""
+        and "cloud_index": (n, capacity) int32, capacity = cloud_capacity or h0 * w0; "colour": uint8 (n, h0, w0, 4); "normals": (n, h0, w0, 3)."""
         cap = h0 * w0 if self.cloud_capacity is None else self.cloud_capacity
-        special = {"points": (n, h0, w0, self.points_components), "colour": (n, h0, w0, 4), "cloud": (n, cap, self.cloud_components), "cloud_counts": (n,), "cloud_index": (n, cap)}
+        special = {"points": (n, h0, w0, self.points_components), "normals": (n, h0, w0, 3), "colour": (n, h0, w0, 4), "cloud": (n, cap, self.cloud_components),
+                   "cloud_counts": (n,), "cloud_index": (n, cap)}
         return {k: torch.empty(special.get(k, (n, 1, h0, w0)), dtype=_PLANE_FORMATS[f][1], device=device, pin_memory=pin_memory)
                 for k, f in self.formats().items() if k not in without}      # (without: keys the caller holds tensors for already)
 
@@ -200,6 +235,13 @@ class OutputSpec:
                        0 if idx is None else idx.stride(0) * 4, ptr(cnt), ptr(workspace), 0 if workspace is None else workspace.numel(), q,
                        self.min_disp, max_uncertainty, max_depth, _PLANE_FORMATS[self.cloud or "f32"][0], self.cloud_components, 0)
 
+    def normals_struct(self, planes: Dict[str, torch.Tensor]) -> L.Normals:
+        """The ``ppms_normals`` that writes into ``planes["normals"]`` ((n, h0, w0, 3), from ``empty`` or the cloud's workspace): Q, min_disp, the
+        gates and the jump gate (None: +inf, off).  ``planes`` without "normals": a struct with a null plane."""
+        q, max_uncertainty, max_depth = self._reprojection()
+        return L.Normals(self._plane(planes.get("normals"), 1, self.normals), q, self.min_disp, max_uncertainty, max_depth,
+                         math.inf if self.normal_max_jump is None else self.normal_max_jump, 0)
+
     def reference(self, d: torch.Tensor, u: Optional[torch.Tensor] = None, colour: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """The arithmetic of ppms_disparity_egress / ppms_scene_egress in plain torch, on CPU or device tensors of any shape: d = a float32 (signed)
         disparity, u = a float32 uncertainty at the same resolution -> the requested planes under forward_batch_test's keys.  With points, d has at
@@ -213,7 +255,11 @@ class OutputSpec:
         colour: the uint8 (..., h, w, 4) colour plane of the same pixels (``video.colour_bytes`` of the source's left float video; the spec's
         ``colour`` names its byte order).  A spec with colour= returns it under "colour" (unless colour_plane is False), and the "xyzrgb" cloud's
         fourth component is that plane's 32 bits per pixel viewed as float32 -- the definition ppms_cloud_egress_colour is tested against.  A spec
-        that needs it and gets none raises ValueError."""
+        that needs it and gets none raises ValueError.
+        With normals, "normals" has the shape of "points" with 3 components (unless normals_plane is False): the definition of include/ppms.h step by
+        step over the fp32 points and their validity, every step one fp32 torch operation -- what ppms_normals_egress is tested against.  The pixel
+        grid is the crop: a neighbour outside d's last two dimensions does not exist.  The "xyzn" / "xyzrgbn" cloud keeps the pixels whose point and
+        normal are valid and appends the normal (in the cloud's format) to X, Y, Z[, the colour word]; "xyzrgbn" is joined as int32 words."""
         if self.colour is not None:
             if colour is None:
                 raise ValueError("OutputSpec.reference: the spec has colour= and no colour plane was given")
@@ -226,7 +272,7 @@ class OutputSpec:
             r = torch.where(torch.isnan(r), torch.zeros_like(r), r).clamp(max=top)
             return r.to(torch.int32).to(_PLANE_FORMATS[fmt][1])
 
-        gated = self.depth is not None or self.points is not None or self.cloud is not None
+        gated = self.depth is not None or self.points is not None or self.cloud is not None or self.normals is not None
         if u is None and (self.uncertainty is not None or (gated and self.max_uncertainty is not None) or (self.points and self.points_layout == "xyzw")
                           or (self.cloud and self.cloud_layout == "xyzw")):
             raise ValueError("OutputSpec.reference: an uncertainty plane, a max_uncertainty gate or the 'xyzw' layout is requested and no uncertainty was given")
@@ -248,10 +294,9 @@ class OutputSpec:
                 out["depth"] = z if self.depth == "f32" else z.to(torch.float16)
         if self.uncertainty is not None:
             out["uncertainties"] = u if self.uncertainty == "f32" else quant(u, 255.0, 255.0, "u8")
-        with_colour = self.colour is not None and self.colour_plane       # ("colour" stands behind "points", as in ``formats``)
-        if with_colour and self.points is None:
-            out["colour"] = colour
-        if self.points is not None or self.cloud is not None:
+        with_colour = self.colour is not None and self.colour_plane       # ("colour" stands behind "points" and "normals", as in ``formats``)
+        keep = None
+        if self.points is not None or self.cloud is not None or self.normals is not None:
             if d.dim() < 2:
                 raise ValueError(f"OutputSpec.reference: points take the pixel grid from d's last two dimensions, got {tuple(d.shape)}")
             x = torch.arange(d.shape[-1], dtype=torch.float32, device=d.device)
@@ -260,29 +305,62 @@ class OutputSpec:
             v = [((q[i, 0] * x + q[i, 1] * y) + q[i, 2] * d) + q[i, 3] for i in range(4)]       # one fp32 operation each, in this order
             xyz = [v[i] / v[3] for i in range(3)]
             valid = ok if self.max_depth is None else ok & (xyz[2] > 0) & (xyz[2] <= const(self.max_depth))
+            squeeze = lambda t: t.squeeze(-4) if d.dim() >= 4 and d.shape[-3] == 1 else t          # (the planes' (..., 1, h, w) -> (..., h, w, C))
 
             def organised(fmt, layout):                  # the organised cloud in one format and layout
                 comps = [torch.where(valid, c, const(math.nan)) for c in xyz] + ([u.expand_as(d)] if layout == "xyzw" else [])
-                pts = torch.stack(comps, dim=-1)
-                if d.dim() >= 4 and d.shape[-3] == 1:
-                    pts = pts.squeeze(-4)
+                pts = squeeze(torch.stack(comps, dim=-1))
                 return pts if fmt == "f32" else pts.to(torch.float16)
 
             if self.points is not None:
                 out["points"] = organised(self.points, self.points_layout)
-                if with_colour:
-                    out["colour"] = colour
-            if self.cloud is not None:                  # per frame (every dimension in front of the pixel grid counts frames): the valid records
-                if self.cloud_layout == "xyzrgb":        # X, Y, Z and the colour pixel's 32 bits, joined and selected as int32 words: no float
-                    xyz32 = organised("f32", "xyz").contiguous().view(torch.int32)                 # operation ever sees the colour word
-                    words = colour.contiguous().view(torch.int32).reshape(*xyz32.shape[:-1], 1)
-                    pts = torch.cat([xyz32, words], dim=-1)
-                else:
-                    pts = organised(self.cloud, self.cloud_layout)
-                pts, keep = pts.reshape(-1, pts.shape[-3] * pts.shape[-2], pts.shape[-1]), valid.reshape(-1, d.shape[-2] * d.shape[-1])
-                out["cloud"] = [p[k].view(torch.float32) if p.dtype == torch.int32 else p[k] for p, k in zip(pts, keep)]
-                out["cloud_index"] = [k.nonzero().flatten().to(torch.int32) for k in keep]      # y * w0 + x, increasing
-                out["cloud_counts"] = keep.sum(dim=1)    # int64: the full numbers, whatever cloud_capacity
+            keep = valid
+            if self.normals is not None:                 # include/ppms.h, steps 1 to 5: one fp32 operation each, in that order
+                h, w = d.shape[-2:]
+
+                def at(t, dy, dx):                       # t at (y + dy, x + dx); outside the crop: 0 / False (such a neighbour is never usable)
+                    o = torch.zeros_like(t)
+                    o[..., max(0, -dy):h - max(0, dy), max(0, -dx):w - max(0, dx)] = t[..., max(0, dy):h + min(0, dy), max(0, dx):w + min(0, dx)]
+                    return o
+
+                def tangent(dy, dx):                     # plus side (dy, dx), minus side (-dy, -dx): (the three differences, a tangent exists)
+                    use = []
+                    for sy, sx in ((dy, dx), (-dy, -dx)):
+                        ok_n = at(valid, sy, sx) & valid
+                        if self.normal_max_jump is not None:
+                            ok_n = ok_n & ((at(xyz[2], sy, sx) - xyz[2]).abs() <= const(self.normal_max_jump) * xyz[2].abs())
+                        use.append(ok_n)
+                    return [torch.where(use[0], at(c, dy, dx), c) - torch.where(use[1], at(c, -dy, -dx), c) for c in xyz], use[0] | use[1]
+
+                (tx, has_x), (ty, has_y) = tangent(0, 1), tangent(1, 0)
+                n = [ty[1] * tx[2] - ty[2] * tx[1], ty[2] * tx[0] - ty[0] * tx[2], ty[0] * tx[1] - ty[1] * tx[0]]
+                flip = ((n[0] * xyz[0] + n[1] * xyz[1]) + n[2] * xyz[2]) > 0                       # towards the origin
+                n = [torch.where(flip, -c, c) for c in n]
+                # the correctly rounded fp32 square root, whatever the host's vector math does: taken in float64 and rounded once (53 >= 2 * 24 + 2
+                # bits: the double rounding is innocuous).  torch's own fp32 sqrt on a CPU is a vector library's, off by one ulp now and then.
+                length = torch.sqrt(((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]).double()).float()
+                keep = valid & has_x & has_y & (length > 0) & torch.isfinite(length)              # the normal is valid
+                normals = squeeze(torch.stack([torch.where(keep, c / length, const(math.nan)) for c in n], dim=-1))
+                if self.normals_plane:
+                    out["normals"] = normals if self.normals == "f32" else normals.to(torch.float16)
+        if with_colour:
+            out["colour"] = colour
+        if self.cloud is not None:                      # per frame (every dimension in front of the pixel grid counts frames): the valid records
+            if self.cloud_layout not in _ORIENTED:
+                keep = valid
+            if self.cloud_layout in _COLOURED:           # X, Y, Z, the colour pixel's 32 bits [and the normal], joined and selected as int32 words:
+                xyz32 = organised("f32", "xyz").contiguous().view(torch.int32)                     # no float operation ever sees the colour word
+                words = colour.contiguous().view(torch.int32).reshape(*xyz32.shape[:-1], 1)
+                pts = torch.cat([xyz32, words] + ([normals.contiguous().view(torch.int32)] if self.cloud_layout == "xyzrgbn" else []), dim=-1)
+            elif self.cloud_layout == "xyzn":
+                pts = torch.cat([organised(self.cloud, "xyz"), normals if self.cloud == "f32" else normals.to(torch.float16)], dim=-1)
+            else:
+                pts = organised(self.cloud, self.cloud_layout)
+            pts, keep = pts.reshape(-1, pts.shape[-3] * pts.shape[-2], pts.shape[-1]), keep.reshape(-1, d.shape[-2] * d.shape[-1])
+            out["cloud"] = [p[k].view(torch.float32) if p.dtype == torch.int32 else p[k] for p, k in zip(pts, keep)]
+            out["cloud_index"] = [k.nonzero().flatten().to(torch.int32) for k in keep]      # y * w0 + x, increasing
+            out["cloud_counts"] = keep.sum(dim=1)    # int64: the full numbers, whatever cloud_capacity
+        return out
         return out
 
 
@@ -318,7 +396,9 @@ class _EgressCall:
         """Allocates the planes on the current stream and enqueues the launch there, behind the engine's last iteration.  A spec with a cloud adds
         "cloud" (n, capacity, C), "cloud_counts" (n,) and "cloud_index" (n, capacity) when asked; rows of "cloud" and "cloud_index" past
         min(count, capacity) of their frame are unspecified (never written).  A spec with colour= puts the plane ``fill_colour`` wrote into the
-        result ("colour"; not with colour_plane=False) and hands it to the "xyzrgb" cloud's launches (ppms_cloud_egress_colour)."""
+        result ("colour"; not with colour_plane=False) and hands it to the "xyzrgb" cloud's launches (ppms_cloud_egress_colour).  A spec with
+        normals= adds ppms_normals_egress's launch between the planes' and the cloud's and "normals" (n, h0, w0, 3) (not with normals_plane=False);
+        the "xyzn" / "xyzrgbn" cloud's launches (ppms_cloud_egress_normals) read that plane."""
         spec = self.spec
         pad_left, pad_top, h0, w0, f0, f1 = self.region(eng.T, 4 * eng.h, 4 * eng.w)
         planes = spec.empty(f1 - f0, h0, w0, eng.FLOW_OUT.device, without=("colour",))
@@ -330,10 +410,20 @@ class _EgressCall:
                 planes = {k: (self.colour if k == "colour" else planes[k]) for k in spec.formats()}
         out = spec.scene_struct(planes) if spec.scene else spec.struct(planes)      # ppms_scene_egress / ppms_disparity_egress
         eng.egress(out, f0, f1 - f0, pad_left, pad_top, h0, w0)
+        normals = None
+        if spec.normals is not None:                             # ppms_normals_egress: one launch behind the planes' one, in front of the cloud's
+            normals = planes["normals"] if spec.normals_plane else torch.empty((f1 - f0, h0, w0, 3), dtype=_PLANE_FORMATS[spec.normals][1],
+                                                                                device=eng.FLOW_OUT.device)      # (the oriented cloud's workspace)
+            eng.egress(spec.normals_struct({"normals": normals}), f0, f1 - f0, pad_left, pad_top, h0, w0)
         if spec.cloud is not None:                               # ppms_cloud_egress: two more launches behind the planes' one, on the same stream
-            workspace = torch.empty(L.load().ppms_cloud_egress_workspace(f1 - f0, h0, w0), dtype=torch.int32, device=eng.FLOW_OUT.device)
-            colour = spec._plane(self.colour, 1, spec.colour) if spec.cloud_layout == "xyzrgb" else None
-            eng.egress(spec.cloud_struct(planes, workspace), f0, f1 - f0, pad_left, pad_top, h0, w0, colour)
+            oriented = spec.cloud_layout in _ORIENTED            # (ppms_cloud_egress_normals: its workgroups and its workspace are its own)
+            query = L.load().ppms_cloud_egress_normals_workspace if oriented else L.load().ppms_cloud_egress_workspace
+            workspace = torch.empty(query(f1 - f0, h0, w0), dtype=torch.int32, device=eng.FLOW_OUT.device)
+            colour = spec._plane(self.colour, 1, spec.colour) if spec.cloud_layout in _COLOURED else None
+            if oriented:
+                eng.egress(spec.cloud_struct(planes, workspace), f0, f1 - f0, pad_left, pad_top, h0, w0, colour, spec._plane(normals, 1, spec.normals))
+            else:
+                eng.egress(spec.cloud_struct(planes, workspace), f0, f1 - f0, pad_left, pad_top, h0, w0, colour)
         return planes
 
 

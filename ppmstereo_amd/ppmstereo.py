@@ -300,7 +300,8 @@ class PPMStereoHotPath(nn.Module):
         scale's stream replaces the final clone + bilinear pair and writes the requested planes (crop, frame range, formats); the call
         then returns {"disparity", "depth"?, "uncertainties"?}: device tensors (n, 1, H0, W0), and appends nothing to the lists.  A spec with
         points or a gate (``OutputSpec.scene``) makes that launch ppms_scene_egress and adds "points": (n, H0, W0, C); a spec with a cloud adds
-        ppms_cloud_egress's two launches behind it and "cloud", "cloud_counts", "cloud_index" (``_EgressCall.launch``).
+        ppms_cloud_egress's two launches behind it and "cloud", "cloud_counts", "cloud_index" (``_EgressCall.launch``); a spec with normals adds
+        ppms_normals_egress's launch between the two and "normals": (n, H0, W0, 3).
         Returns (flow_up (T,1,H,W), uncertainty (T,1,H,W)) = predictions[-1], uncertainties[-1]."""
         if egress is not None:
             if not test_mode:
@@ -591,6 +592,10 @@ class PPMStereo(PPMStereoHotPath):
         one launch (ppms_video_colour_*) directly behind the ingest launch and in front of both encoders; float images make it in torch.  A crop
         that reaches into the padding sees the replicate padding.  ``cloud_layout="xyzrgb"`` puts that pixel's 32 bits into the fourth word of
         every record of the compact cloud (ppms_cloud_egress_colour); ``colour_plane=False`` then leaves "colour" out of the dict.
+        With ``OutputSpec(normals="f32" | "f16", Q=Q)`` the dict also has "normals" (1, n, H0, W0, 3): the unit surface normal per pixel from the cross
+        stencil over the organised points of the cropped plane, towards the camera, NaN where there is none -- one launch (ppms_normals_egress)
+        behind the planes' one.  ``cloud_layout="xyzn"`` / ``"xyzrgbn"`` appends it to every record of the compact cloud, which then keeps the
+        pixels whose point and normal are valid (ppms_cloud_egress_normals); ``normals_plane=False`` leaves "normals" out of the dict.
         rectify=None and output=None (the defaults) add no launch to the calls above."""
         if flow_init is not None:
             raise NotImplementedError("flow_init: the reference's own path for it reads undefined state (ppmstereo.py:691-693, 763)")
@@ -738,6 +743,10 @@ class PPMStereo(PPMStereoHotPath):
         plane, 4 bytes per pixel of the kept frames, from one more launch per window (ppms_video_colour_*) behind the ingest launch.  With
         ``cloud="f32", cloud_layout="xyzrgb"`` the fourth word of a cloud record is that pixel (XYZRGB: 16 bytes per valid point, where "xyz" with
         ``cloud_index`` moves 12 + 4 and leaves the gather to the host); ``colour_plane=False`` keeps the plane on the device.  Nothing is timed.
+        ``OutputSpec(normals="f32", Q=Q, ...)``: "normals" is a pinned (N, H, W, 3) -- the unit surface normal per pixel (``OutputSpec``: the
+        definition), 12 bytes per pixel of the kept frames in f32 and 6 in f16, from one more launch per window (ppms_normals_egress).  With
+        ``cloud_layout="xyzn"`` (24-byte records in f32, 12 in f16) or ``"xyzrgbn"`` (28 bytes) every record of the compact cloud carries its normal
+        and the cloud keeps the pixels that have one; ``normals_plane=False`` keeps the plane on the device.  Nobody has timed it.
         rectify: a ``StereoRectifier`` -- the video holds the RAW frames of an unrectified rig, (N, 2, 3, Hs, Ws) uint8 or a ``YUVStereoVideo`` of
         its source size Hs x Ws.  Each window's raw bytes are copied as above, the maps once per device (6 bytes per rectified pixel and view):
         the bits of the call on the uint8 video of ``RectifyMap.apply_u8``.  H x W of the results (and of the ``InputPadder``) is the rectified
