@@ -402,9 +402,6 @@ class ScaleEngine:
     def mhs_view(self) -> L.SP:
         return self.CF[self.parity].view(256, 64)
 
-    def UNC_local(self) -> torch.Tensor:
-        return self.UNC
-
     def get_net(self):
         return self.store_nchw(self.Hb[0].view(), 128)
 

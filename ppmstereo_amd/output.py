@@ -77,7 +77,24 @@ class OutputSpec:
                        need normals= in the cloud's format.  A record is kept iff its point AND its normal are valid; the cloud's launches
                        (ppms_cloud_egress_normals) read the normals plane, they do not recompute it.
       normals_plane    True | False: False keeps the device plane as workspace of those two clouds and leaves "normals" out of the result and of
-                       the device -> host copies.  Only with cloud_layout="xyzn" or "xyzrgbn"."""
+                       the device -> host copies.  Only with cloud_layout="xyzn" or "xyzrgbn".
+    What the two entry points hand back for a spec (n frames written, h0 x w0 the crop; keys in the order of ``formats``):
+      ``forward(output=, crop=, frames=)``  device tensors with the batch axis of 1 in front: the planes (1, n, 1, h0, w0), "points" (1, n, h0, w0, C),
+                       "normals" (1, n, h0, w0, 3), "colour" (1, n, h0, w0, 4), "cloud" (1, n, capacity, C), "cloud_counts" (1, n) int32 and
+                       "cloud_index" (1, n, capacity) int32.  No float32 full-resolution tensor is made and the host is never synchronised.  Rows of
+                       "cloud" / "cloud_index" past min(count, capacity) of a frame are unspecified (never written); a count above the
+                       capacity tells of a truncated frame.
+      ``forward_batch_test(output=)``  host tensors over the N frames of the video, pinned: each window's launches write its KEPT frames only, and only
+                       those are copied device -> host, straight into their slice of the result -- uint16 disparity and uint8 confidence: 3 bytes
+                       per pixel and kept frame, where the default path copies 8 for every frame of the window.  Planes (N, 1, H, W); "points"
+                       (N, H, W, C), NaN where a gate or min_disp takes the pixel, 12 bytes per pixel in "xyz" f32 (``rectify=`` in front and points
+                       behind need the one calibration's maps and Q); "normals" (N, H, W, 3), 12 bytes per pixel in f32 and 6 in f16; "colour"
+                       (N, H, W, 4), 4 bytes per pixel.  "cloud" is a LIST of N views (min(count_f, capacity), C) of one (N, capacity, C) buffer,
+                       "cloud_index" likewise (...,) int32, "cloud_counts" (N,) int64, the untruncated numbers: per window the counts are copied
+                       to the host first and then only min(count_f, capacity) records of each kept frame, so by construction count_f * C *
+                       element bytes cross the bus where the organised cloud moves H * W * C ("xyzrgb": 16 bytes per valid point, where "xyz" with
+                       ``cloud_index`` moves 12 + 4 and leaves the gather to the host; "xyzn": 24 in f32, 12 in f16; "xyzrgbn": 28).
+                       ``colour_plane=False`` / ``normals_plane=False`` keep their plane on the device.  None of this has been timed."""
 
     def __init__(self, disparity: str = "f32", depth: Optional[str] = None, uncertainty: Optional[str] = "f32", disp_scale: float = 256.0,
                  focal_px: Optional[float] = None, baseline: Optional[float] = None, depth_scale: float = 1000.0, min_disp: float = 2.0 ** -8,
@@ -361,7 +378,6 @@ class OutputSpec:
             out["cloud_index"] = [k.nonzero().flatten().to(torch.int32) for k in keep]      # y * w0 + x, increasing
             out["cloud_counts"] = keep.sum(dim=1)    # int64: the full numbers, whatever cloud_capacity
         return out
-        return out
 
 
 class _EgressCall:
@@ -431,3 +447,81 @@ def egress_plan(plan):
     """``window_plan`` with the destination of every window's kept frames: (start, stop, keep_from, keep_to, dst_from, dst_to) -- the egress
     launch of the window writes its frames [keep_from, keep_to), and they are frames [dst_from, dst_to) of the video."""
     return [(start, stop, keep_from, keep_to, start + keep_from, start + keep_to) for start, stop, keep_from, keep_to in plan]
+
+
+# ------------------------------------------------------------------ the sinks of forward_batch_test: what becomes of a window's result
+# take(result, padder, keep_from, keep_to, dst_from, dst_to) per window -- the window's ``_forward_images`` result, the InputPadder that crops it
+# back and its span of ``egress_plan`` --, result() once behind the last window: the dict the call returns.
+
+def _idle_stream(device) -> None:
+    # device -> host.  The stream is synchronised FIRST (a spinning wait): a pageable copy issued while the clip's ~900 launches are
+    # still queued blocks inside the runtime on an interrupt-driven wait, and on a loaded host (the GPU boxes: load average 50-60)
+    # the thread was rescheduled 50-150 ms late in every other call (whole call 50 / 100 / 195 ms alternating; with the
+    # synchronisation in front the copy finds an idle stream: 49-50 ms every time, tools/whole_call_probe.py)
+    if device.type == "cuda":
+        torch.cuda.current_stream(device).synchronize()
+
+
+class _Float32Sink:
+    """The default: the window's float32 (disparity, uncertainty), each (1, T, 1, H, W), unpadded and copied to the host in one piece."""
+
+    def __init__(self):
+        self.kept = ([], [])
+
+    def take(self, result, padder, keep_from, keep_to, dst_from, dst_to):
+        du = torch.cat([padder.unpad(x[0])[:, None] for x in result])                                     # one copy for both results
+        _idle_stream(du.device)
+        du = du.cpu()
+        for kept, x in zip(self.kept, du.chunk(2)):
+            kept.append(x[keep_from:keep_to])
+
+    def result(self) -> Dict[str, torch.Tensor]:
+        return {key: torch.cat(kept).squeeze(1).abs()[:, :1] for key, kept in zip(("disparity", "uncertainties"), self.kept)}
+
+
+class _PlaneSink:
+    """output=: the planes a window's egress launches wrote for its kept frames, each (1, n, ...), copied straight into their slice of host
+    buffers allocated once (pinned by default).  Per frame only the records of the compact cloud that exist are copied."""
+    RAGGED = ("cloud", "cloud_index")
+
+    def __init__(self, spec: OutputSpec, n: int, h0: int, w0: int, pin_memory: bool = True):
+        self.host = spec.empty(n, h0, w0, "cpu", pin_memory=pin_memory)
+
+    def take(self, planes, padder, keep_from, keep_to, dst_from, dst_to):
+        host, ragged = self.host, [key for key in self.RAGGED if key in planes]
+        _idle_stream(next(iter(planes.values())).device)
+        for key, plane in planes.items():
+            if key not in ragged:
+                host[key][dst_from:dst_to].copy_(plane[0])             # kept frames only, device -> their slice of the result
+        if ragged:                                                     # the counts are on the host now: min(count, capacity) records per kept frame
+            for i, count in enumerate(host["cloud_counts"][dst_from:dst_to].tolist()):
+                for key in ragged:
+                    k = min(count, planes[key].shape[2])
+                    host[key][dst_from + i, :k].copy_(planes[key][0, i, :k])
+
+    def result(self) -> Dict:
+        host = self.host
+        if "cloud" in host:                                            # views of the buffers: no row past a frame's records exists
+            counts = host["cloud_counts"].tolist()
+            for key in self.RAGGED:
+                if key in host:
+                    host[key] = [host[key][f, :min(c, host[key].shape[1])] for f, c in enumerate(counts)]
+            host["cloud_counts"] = host["cloud_counts"].to(torch.int64)                      # the untruncated numbers
+        return host
+
+
+class _KeptOnDevice:
+    """shard_ranks: this rank's kept float32 frames stay on the device, each piece with its first frame in video coordinates, and every rank
+    gets the video in one gather at the end (``dist.gather_kept_frames``)."""
+
+    def __init__(self, n: int, h0: int, w0: int):
+        self.kept, self.shape = ([], []), (n, h0, w0)
+
+    def take(self, result, padder, keep_from, keep_to, dst_from, dst_to):
+        for kept, x in zip(self.kept, result):
+            kept.append((dst_from, padder.unpad(x[0])[keep_from:keep_to].abs()[:, :1]))      # (n, 1, H0, W0)
+
+    def result(self) -> Dict[str, torch.Tensor]:
+        from .dist import gather_kept_frames
+        disp, unc = (gather_kept_frames(kept, *self.shape) for kept in self.kept)
+        return {"disparity": disp.cpu(), "uncertainties": unc.cpu()}

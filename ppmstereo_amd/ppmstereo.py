@@ -19,7 +19,7 @@ from . import _lib as L
 from .corr import CorrBlock1D
 from .engine import bilinear
 from .update import Attention_qk, SequenceUpdateBlock3D
-from .output import OutputSpec, _EgressCall, egress_plan  # noqa: F401  (the public names are importable from here as before)
+from .output import OutputSpec, _EgressCall, _Float32Sink, _KeptOnDevice, _PlaneSink, egress_plan  # noqa: F401  (the public names are importable from here as before)
 from .video import (InputPadder, RawFrames, RawStereoVideo, RectifyMap, StereoRectifier, YUVFrames, YUVStereoVideo, byte_lut,  # noqa: F401
                     level_lut, shard_windows, window_plan, yuv_matrix)
 from .video import PackedRawFrames, PackedRawStereoVideo, PackedYUVFrames, PackedYUVStereoVideo  # noqa: F401
@@ -32,21 +32,56 @@ def interp(x: torch.Tensor, size) -> torch.Tensor:
     return bilinear(x, (int(size[0]), int(size[1])), True)
 
 
-def convex_upsample(flow: torch.Tensor, mask: torch.Tensor, rate: int = 4) -> torch.Tensor:
-    """PPMStereo.convex_upsample, ppmstereo.py:185-197 (NCHW in, NCHW out)."""
+def _convex_upsample(name: str, flow: torch.Tensor, mask: torch.Tensor, rate: int, T: Optional[int] = None) -> torch.Tensor:
+    """The body of both convex upsamplings: T None: the 2-D one (144 mask channels), else the 3-D one over a window of T frames (432)."""
     if rate != 4:
-        raise NotImplementedError("convex_upsample: rate 4 only")
+        raise NotImplementedError(f"{name}: rate 4 only")
     L.require_gpu(flow, mask)
     N, _, H, W = flow.shape
+    if T is not None and N != T:
+        raise NotImplementedError(f"{name}: batch size 1 (N == T)")
+    C = 144 if T is None else 432
     lib, s = L.load(), L.stream_ptr()
     f = torch.empty(N * H * W, 2, dtype=torch.float32, device=flow.device)
-    m = torch.empty(N * H * W, 144, dtype=torch.float32, device=flow.device)
+    m = torch.empty(N * H * W, C, dtype=torch.float32, device=flow.device)
     fc, mc = flow.contiguous().float(), mask.contiguous().float()
     L.check(lib.ppms_nchw_to_nhwc(fc.data_ptr(), f.data_ptr(), 2, N, 2, H * W, s))
-    L.check(lib.ppms_nchw_to_nhwc(mc.data_ptr(), m.data_ptr(), 144, N, 144, H * W, s))
+    L.check(lib.ppms_nchw_to_nhwc(mc.data_ptr(), m.data_ptr(), C, N, C, H * W, s))
     out = torch.empty(N, 2, 4 * H, 4 * W, dtype=torch.float32, device=flow.device)
-    L.check(lib.ppms_convex_upsample(f.data_ptr(), m.data_ptr(), 144, out.data_ptr(), N, H, W, s))
+    if T is None:
+        L.check(lib.ppms_convex_upsample(f.data_ptr(), m.data_ptr(), C, out.data_ptr(), N, H, W, s))
+    else:
+        L.check(lib.ppms_convex_upsample_3d(f.data_ptr(), m.data_ptr(), C, out.data_ptr(), T, H, W, 0, s))
     return out
+
+
+def convex_upsample(flow: torch.Tensor, mask: torch.Tensor, rate: int = 4) -> torch.Tensor:
+    """PPMStereo.convex_upsample, ppmstereo.py:185-197 (NCHW in, NCHW out)."""
+    return _convex_upsample("convex_upsample", flow, mask, rate)
+
+
+def convex_upsample_3d(flow: torch.Tensor, mask: torch.Tensor, rate: int, T: int) -> torch.Tensor:
+    """PPMStereo.convex_upsample_3d, ppmstereo.py:199-228 (NCHW in, NCHW out; one window of T frames, batch 1)."""
+    return _convex_upsample("convex_upsample_3d", flow, mask, rate, T)
+
+
+def _check_clip(t: int, channels: int = 128, interp_scale: float = 1) -> int:
+    """What every entry to the iteration loop asks of its clip -> int(interp_scale)."""
+    if channels != 128:
+        raise RuntimeError("forward_update_block: 128 context channels expected")
+    if int(interp_scale) not in (1, 2, 4):
+        raise NotImplementedError("interp_scale must be 4, 2 or 1 (the reference's only live branches)")
+    if t == 1:
+        # the reference divides 0/0 in the temporal encoding (ppmtereo_update.py:34-36): every output is NaN
+        warnings.warn("PPMStereo with a single frame produces NaN disparities (reference behaviour, T must be >= 2)")
+    return int(interp_scale)
+
+
+def _emit(flow_out: torch.Tensor, unc: torch.Tensor, isc: int, predictions: List, uncertainties: List) -> None:
+    """Appends an iteration's prediction and uncertainty at full resolution (ppmstereo.py:578-591): flow_out (n, 2, 4h, 4w), unc (n, 1, h, w)."""
+    h4, w4 = flow_out.shape[2:]
+    uncertainties.append(bilinear(unc, (isc * h4, isc * w4), False))
+    predictions.append(bilinear(flow_out[:, :1], (isc * h4, isc * w4), True, float(isc)) if isc > 1 else flow_out[:, :1].clone())
 
 
 def _run_iterations(eng, iters: int, isc: int, t: int, h: int, w: int, predictions: List, uncertainties: List, emit: str = "all"):
@@ -58,15 +93,8 @@ def _run_iterations(eng, iters: int, isc: int, t: int, h: int, w: int, predictio
         # the upsampled flow of an iteration is consumed by its prediction (when emitted) and, after the last iteration, by the next
         # scale's initialisation (:724-725): anywhere else the mask head + convex upsampling are dead work and are not launched
         flow_out = eng.iterate(need_up=(emit == "all" or it + 1 == iters))
-        if emit == "none" or (emit == "last" and it + 1 < iters):
-            continue
-        unc_up = bilinear(eng.UNC_local().view(t, 1, h, w), (4 * isc * h, 4 * isc * w), False)
-        if isc > 1:
-            flow_up = bilinear(flow_out[:, :1], (isc * 4 * h, isc * 4 * w), True, float(isc))
-        else:
-            flow_up = flow_out[:, :1].clone()
-        predictions.append(flow_up)
-        uncertainties.append(unc_up)
+        if emit == "all" or (emit == "last" and it + 1 == iters):
+            _emit(flow_out, eng.UNC.view(t, 1, h, w), isc, predictions, uncertainties)
     return flow_out
 
 
@@ -77,25 +105,6 @@ def _add_attn_redo(diagnostics: dict, per_scale: Dict[str, Dict[str, int]]):
         entry = total.setdefault(tag, {"calls": 0, "tiles": 0, "flagged": 0})
         for k, v in counters.items():
             entry[k] += int(v)
-
-
-def convex_upsample_3d(flow: torch.Tensor, mask: torch.Tensor, rate: int, T: int) -> torch.Tensor:
-    """PPMStereo.convex_upsample_3d, ppmstereo.py:199-228 (NCHW in, NCHW out; one window of T frames, batch 1)."""
-    if rate != 4:
-        raise NotImplementedError("convex_upsample_3d: rate 4 only")
-    L.require_gpu(flow, mask)
-    N, _, H, W = flow.shape
-    if N != T:
-        raise NotImplementedError("convex_upsample_3d: batch size 1 (N == T)")
-    lib, s = L.load(), L.stream_ptr()
-    f = torch.empty(N * H * W, 2, dtype=torch.float32, device=flow.device)
-    m = torch.empty(N * H * W, 432, dtype=torch.float32, device=flow.device)
-    fc, mc = flow.contiguous().float(), mask.contiguous().float()
-    L.check(lib.ppms_nchw_to_nhwc(fc.data_ptr(), f.data_ptr(), 2, N, 2, H * W, s))
-    L.check(lib.ppms_nchw_to_nhwc(mc.data_ptr(), m.data_ptr(), 432, N, 432, H * W, s))
-    out = torch.empty(N, 2, 4 * H, 4 * W, dtype=torch.float32, device=flow.device)
-    L.check(lib.ppms_convex_upsample_3d(f.data_ptr(), m.data_ptr(), 432, out.data_ptr(), T, H, W, 0, s))
-    return out
 
 
 def forward_update_block(self, image1, update_block: SequenceUpdateBlock3D, corr_fn: CorrBlock1D, flow: torch.Tensor, net: torch.Tensor,
@@ -110,17 +119,10 @@ def forward_update_block(self, image1, update_block: SequenceUpdateBlock3D, corr
     bt, c, h, w = inp.shape
     if bt % t:
         raise RuntimeError(f"forward_update_block: {bt} frames do not divide into clips of t = {t}")
+    isc = _check_clip(t, c, interp_scale)
     if bt != t:
         return _forward_update_block_batched(update_block, corr_fn, flow, net, inp, motion_hidden_state, attn_block, predictions, uncertainties,
-                                             iters, interp_scale, t)
-    if c != 128:
-        raise RuntimeError("forward_update_block: 128 context channels expected")
-    if int(interp_scale) not in (1, 2, 4):
-        raise NotImplementedError("interp_scale must be 4, 2 or 1 (the reference's only live branches)")
-    if t == 1:
-        # the reference divides 0/0 in the temporal encoding (ppmtereo_update.py:34-36): every output is NaN
-        warnings.warn("PPMStereo with a single frame produces NaN disparities (reference behaviour, T must be >= 2)")
-    isc = int(interp_scale)
+                                             iters, isc, t)
     with torch.cuda.device(inp.device):         # kernels go to the current stream of the tensors' device
         eng = update_block.engine(t, h, w, inp.device)
         eng.set_inp(inp)
@@ -133,20 +135,14 @@ def forward_update_block(self, image1, update_block: SequenceUpdateBlock3D, corr
 
 
 def _forward_update_block_batched(update_block, corr_fn, flow, net, inp, motion_hidden_state, attn_block, predictions, uncertainties, iters,
-                                  interp_scale, t: int):
+                                  isc: int, t: int):
     """forward_update_block for b > 1 clips in one call (ppmstereo.py:443-449: frame index = bi * t + ti).  Everything is per batch element
     -- the 3-D convolutions, the frame similarity, the top-5 pick and the attention all see one clip -- except ONE scalar per clip index:
     ``selected_score.mean()`` at :533 averages the picked frames' scores over the batch as well, so the key modulation s_hat of clip i is
     its score divided by the mean over all b elements.  One engine per element; the stages run element by element, the normaliser is
     fixed between the pick and the attention."""
-    bt, c, h, w = inp.shape
-    b = bt // t
-    if c != 128 or int(interp_scale) not in (1, 2, 4):
-        raise RuntimeError("forward_update_block: 128 context channels and interp_scale 4, 2 or 1 expected")
-    if t == 1:
-        warnings.warn("PPMStereo with a single frame produces NaN disparities (reference behaviour, T must be >= 2)")
-    isc, dev = int(interp_scale), inp.device
-    rows = t * h * w
+    bt, _, h, w = inp.shape
+    b, dev, rows = bt // t, inp.device, t * h * w
     with torch.cuda.device(dev):
         engs = []
         for bi in range(b):
@@ -168,11 +164,9 @@ def _forward_update_block_batched(update_block, corr_fn, flow, net, inp, motion_
                 eng.SHAT[:, :k] = x / mean_all[:, None]
                 eng.attend(), eng.update(need_mask=True)
                 outs.append(eng.upsample().clone())
-                uncs.append(eng.UNC_local().view(t, 1, h, w).clone())
+                uncs.append(eng.UNC.view(t, 1, h, w).clone())
             flow_out = torch.cat(outs)
-            unc = torch.cat(uncs)
-            uncertainties.append(bilinear(unc, (4 * isc * h, 4 * isc * w), False))
-            predictions.append(bilinear(flow_out[:, :1], (isc * 4 * h, isc * 4 * w), True, float(isc)) if isc > 1 else flow_out[:, :1].clone())
+            _emit(flow_out, torch.cat(uncs), isc, predictions, uncertainties)
         return flow_out, torch.cat([e.get_net() for e in engs]), torch.cat([e.get_mhs() for e in engs])
 
 
@@ -205,6 +199,51 @@ class ClipPipeline:
 
         self._results: List[torch.Tensor] = []                # tensors handed out by cascade() since the last wait()
         self._health: List[tuple] = []                        # (completion event, diagnostics dict, {scale: device snapshot of the attention counters}) per clip
+
+    # ---- what ``cascade`` tells the pipeline, in the order of a clip.  The streams and events are plain attributes, read at every call.
+    def take_inputs(self, caller: torch.cuda.Stream):
+        """Hand-off 1, at the top of a clip: the caller's stream -> ``small``.  The inputs were produced on the caller's stream; with ``serial``
+        the clip also waits for the previous clip's completion, so that no two clips overlap."""
+        self.small.wait_stream(caller)
+        if self.serial and self.last is not None:
+            self.small.wait_event(self.last)
+
+    def state8(self, read: bool):
+        """Hand-off 2, ``consumed``: the 1/8 engine's flow, hidden state and motion hidden state are read by the 1/4 scale's prologue on ``large``
+        (the resize of the flow and the ppms_sp_resize_blend pair) while the NEXT clip's 1/8 scale, on ``small``, is free to overwrite them.
+        read=False, in front of scale 8: ``small`` waits until the previous clip's prologue has read the state.  read=True, on ``large`` behind
+        the blend pair of scale 4: the state has been read, the next clip may overwrite it."""
+        if read:
+            self.consumed = torch.cuda.Event()
+            self.consumed.record()
+        elif self.consumed is not None:
+            self.small.wait_event(self.consumed)
+
+    def enter_scale(self, scale: int, feats: Dict[str, torch.Tensor]) -> torch.cuda.Stream:
+        """-> the stream scale 1/``scale`` runs on.  Hand-off 3, in front of scale 4: ``small`` -> ``large``, this clip's 1/16 and 1/8 scales.  The
+        scale's four feature tensors were allocated on the caller's stream: the stream is recorded on them, so that the allocator does not
+        recycle them early."""
+        stream = self.large if scale == 4 else self.small
+        if scale == 4:
+            stream.wait_stream(self.small)
+        for k in (f"f1_{scale}", f"f2_{scale}", f"net_{scale}", f"inp_{scale}"):
+            feats[k].record_stream(stream)
+        return stream
+
+    def end_clip(self, result, diagnostics: Optional[dict], health: dict):
+        """Behind the last launch of a clip: ``last``, its completion on ``large`` (a timing event, kept in ``done_events``, with ``record_done``);
+        ``result``, the pair or the dict of planes ``cascade`` hands out, on whose tensors ``wait`` records the consuming stream; ``health``, the
+        device snapshots of the attention counters that ``wait`` reads into ``diagnostics``.  Both lists are capped at 16 entries: a caller that
+        never waits (bench.py) must not accumulate references."""
+        self.last = torch.cuda.Event(enable_timing=self.record_done)
+        self.last.record(self.large)
+        if diagnostics is not None:
+            self._health.append((self.last, diagnostics, health))
+            del self._health[:-16]
+        if self.record_done:
+            self.done_events.append(self.last)
+        self._results += result.values() if isinstance(result, dict) else result
+        del self._results[:-16]
 
     def wait(self, handle: Optional[torch.cuda.Event] = None):
         """Orders the current stream behind the clips enqueued so far AND tells the caching allocator that the tensors ``cascade`` returned
@@ -290,18 +329,17 @@ class PPMStereoHotPath(nn.Module):
         2-channel flow passes through an NCHW resize.  feats: f1_s, f2_s, net_s, inp_s for s in (16, 8, 4) on the GPU
         (with ``shard``: this rank's frames only).  test_mode: only the final prediction is produced (ppmstereo.py:801-804).
         pipeline: a ``ClipPipeline`` -- the small scales and the 1/4 scale are enqueued on its two streams so that consecutive clips
-        overlap (same results; see the class).
+        overlap (same results; see the class, which owns every stream, event and hand-off: this function tells it the moments).  None: every
+        scale on the caller's stream, and no event, wait or record_stream is made.
         diagnostics: a dict -- the fix-up accounting of the memory read-out (ScaleEngine.enable_attn_health) is switched on for this call on
         the three engines, their counters are zeroed at the start, and on return ``diagnostics["attn_redo"]`` holds {"1/16": {"calls",
         "tiles", "flagged"}, "1/8": ..., "1/4": ...}, ADDED to entries already there (one dict over several windows sums them; with
         ``shard``: this rank's clips).  One extra small launch per iteration and one host synchronisation at the end of the call; with a
         ``pipeline`` there is none here: the counters are read in ``ClipPipeline.wait()``.  None (default): nothing is launched or read.
-        egress (test_mode, b = 1, no shard): an ``_EgressCall`` -- after the last 1/4-scale iteration ONE ppms_disparity_egress launch on that
-        scale's stream replaces the final clone + bilinear pair and writes the requested planes (crop, frame range, formats); the call
-        then returns {"disparity", "depth"?, "uncertainties"?}: device tensors (n, 1, H0, W0), and appends nothing to the lists.  A spec with
-        points or a gate (``OutputSpec.scene``) makes that launch ppms_scene_egress and adds "points": (n, H0, W0, C); a spec with a cloud adds
-        ppms_cloud_egress's two launches behind it and "cloud", "cloud_counts", "cloud_index" (``_EgressCall.launch``); a spec with normals adds
-        ppms_normals_egress's launch between the two and "normals": (n, H0, W0, 3).
+        egress (test_mode, b = 1, no shard): an ``_EgressCall`` -- after the last 1/4-scale iteration its launches (``_EgressCall.launch``: which,
+        and in what order) on that scale's stream replace the final clone + bilinear pair and write the spec's planes (crop, frame range,
+        formats); the call then returns their dict -- device tensors, (n, 1, H0, W0) for the planes, as ``OutputSpec`` defines them without the
+        batch axis -- and appends nothing to the lists.
         Returns (flow_up (T,1,H,W), uncertainty (T,1,H,W)) = predictions[-1], uncertainties[-1]."""
         if egress is not None:
             if not test_mode:
@@ -322,29 +360,22 @@ class PPMStereoHotPath(nn.Module):
             if diagnostics is not None:
                 raise NotImplementedError("cascade: diagnostics are collected for one clip per call (b = 1)")
             return self._cascade_batched(feats, iters, t, preds, uncs)
-        if t == 1:
-            warnings.warn("PPMStereo with a single frame produces NaN disparities (reference behaviour, T must be >= 2)")
+        _check_clip(t)
         lib = L.load()
         with torch.cuda.device(dev):
-            caller = torch.cuda.current_stream()
+            stream = torch.cuda.current_stream()              # without a pipeline: every scale on the caller's stream
             if pipeline is not None:
-                pipeline.small.wait_stream(caller)        # the inputs were produced on the caller's stream
-                if pipeline.serial and pipeline.last is not None:
-                    pipeline.small.wait_event(pipeline.last)
+                pipeline.take_inputs(stream)
             prev, fo = None, None
             health = {}                                       # scale -> engine (read below) or device snapshot (read in ClipPipeline.wait)
             for s_, blk, ai, n_it, isc in ((16, self.update_block16, 0, iters // 2, 4), (8, self.update_block08, 1, iters // 2, 2),
                                           (4, self.update_block04, 2, iters, 1)):
                 f1, f2 = feats[f"f1_{s_}"], feats[f"f2_{s_}"]
                 h, w = f1.shape[2:]
-                stream = caller if pipeline is None else (pipeline.large if s_ == 4 else pipeline.small)
                 if pipeline is not None:
-                    if s_ == 8 and pipeline.consumed is not None:
-                        stream.wait_event(pipeline.consumed)      # the previous clip's 1/4 scale still reads this engine's state in its prologue
-                    if s_ == 4:
-                        stream.wait_stream(pipeline.small)        # this clip's 1/16 and 1/8 scales
-                    for k in (f"f1_{s_}", f"f2_{s_}", f"net_{s_}", f"inp_{s_}"):
-                        feats[k].record_stream(stream)            # (allocated on the caller's stream: keep the allocator from recycling them early)
+                    if s_ == 8:
+                        pipeline.state8(read=False)
+                    stream = pipeline.enter_scale(s_, feats)
                 with torch.cuda.stream(stream):
                     eng = blk.engine(tl, h, w, dev, shard)
                     if diagnostics is not None:
@@ -364,32 +395,24 @@ class PPMStereoHotPath(nn.Module):
                         # :729-732, :765-767: net = (net_s + interp(net_2s)) / 2
                         L.check(lib.ppms_sp_resize_blend(prev.net_view(), eng.net_view(), tl, ph, pw, 2 * ph, 2 * pw, 0.5, 0.5, L.stream_ptr()))
                     if pipeline is not None and s_ == 4:
-                        pipeline.consumed = torch.cuda.Event()
-                        pipeline.consumed.record()                # the 1/8 engine's flow / hidden states have been read: the next clip may overwrite them
+                        pipeline.state8(read=True)
                     eng.begin(CorrBlock1D(f1, f2).levels, self.att[ai].packed(dev))
                     last_scale_emit = "none" if egress is not None else "last"       # (the last iteration upsamples its flow either way)
                     fo = _run_iterations(eng, n_it, isc, tl, h, w, preds, uncs, "all" if not test_mode else (last_scale_emit if s_ == 4 else "none"))
                     if egress is not None and s_ == 4:
-                        # on this scale's stream and -- with a pipeline -- before ``pipeline.last`` is recorded: the next clip's 1/4 scale
-                        # overwrites FLOW_OUT and UNC
+                        # on this scale's stream and -- with a pipeline -- before the clip's completion is recorded (``end_clip``): the next
+                        # clip's 1/4 scale overwrites FLOW_OUT and UNC
                         planes = egress.launch(eng)
                     prev = eng
                     if diagnostics is not None:
                         eng.enable_attn_health(health_was_on)
                         health[f"1/{s_}"] = eng if pipeline is None else eng.attn_health_snapshot()
+            result = planes if egress is not None else (preds[-1], uncs[-1])
             if pipeline is not None:
-                pipeline.last = torch.cuda.Event(enable_timing=pipeline.record_done)
-                pipeline.last.record(pipeline.large)
-                if diagnostics is not None:
-                    pipeline._health.append((pipeline.last, diagnostics, health))
-                    del pipeline._health[:-16]                     # (as _results below: a caller that never waits)
-                if pipeline.record_done:
-                    pipeline.done_events.append(pipeline.last)
-                pipeline._results += [preds[-1], uncs[-1]] if egress is None else list(planes.values())      # (ClipPipeline.wait records the consuming stream on them)
-                del pipeline._results[:-16]                        # a caller that never waits (bench.py) must not accumulate references
+                pipeline.end_clip(result, diagnostics, health)
             elif diagnostics is not None:
                 _add_attn_redo(diagnostics, {tag: eng.attn_health() for tag, eng in health.items()})
-            return planes if egress is not None else (preds[-1], uncs[-1])
+            return result
 
     def _cascade_batched(self, feats, iters: int, t: int, preds: list, uncs: list):
         """cascade for b > 1 clips (frame index = bi * t + ti, ppmstereo.py:443-449): the reference's glue between the three
@@ -485,10 +508,10 @@ class PPMStereo(PPMStereoHotPath):
             mods[k] = mods.pop(k)                              # (re-insertion moves the key to the end)
         self.dim = 256
         self._pe_cache: Dict[tuple, torch.Tensor] = {}
-        self.parallel_encoders = True                          # cnet on a side stream beside fnet (forward)
         self._enc_streams: Dict[int, torch.cuda.Stream] = {}
 
     def _encoder_stream(self, device) -> torch.cuda.Stream:
+        """The stream cnet runs on beside fnet (``_encode``), one per device."""
         idx = torch.device(device).index or 0
         if idx not in self._enc_streams:
             self._enc_streams[idx] = torch.cuda.Stream(device=device)
@@ -559,44 +582,28 @@ class PPMStereo(PPMStereoHotPath):
                 diagnostics: Optional[dict] = None, output: Optional[OutputSpec] = None, crop=None, frames=None,
                 rectify: Optional[StereoRectifier] = None):
         """PPMStereo.forward (ppmstereo.py:601-804): image (b, T, 3, H, W) in [0, 255], H, W multiples of 32 (b = 1: the device-resident
-        cascade; b > 1: the reference's glue around the batched forward_update_block).  The two views are (``video.stereo_source``)
-          float tensors, as in the reference; or
-          uint8 tensors: the bits of ``forward(image1.float(), image2.float())``; or
-          two ``YUVFrames`` on the device (decoded frames of 8, 10 or 12 bits, 4:2:0 / 4:2:2 / 4:4:4: NV12, I420, P010, NV16 ...; b = 1, T = their
-          frame count): the bits of ``forward`` on their ``to_float()`` (8-bit frames: on their ``to_rgb_u8()``); or
-          two ``RawFrames`` on the device (a sensor's Bayer-mosaic or monochrome frames of 8, 10 or 12 bits; b = 1, T = their frame count): the bits
-          of ``forward`` on their ``to_float()``; or
-          two ``PackedYUVFrames`` or two ``PackedRawFrames`` on the device (YUYV / UYVY / Y210 / v210 ...; MIPI RAW10 / RAW12 or PFNC 10p / 12p
-          rows, e.g. the ``split_side_by_side()`` halves of one surface; b = 1, T = their frame count): the bits of ``forward`` on their ``unpack()``; or
-          two ``PackedRGBFrames`` on the device (interleaved BGR24 / BGRA / RGB48 / X2RGB10 ..., e.g. ``PackedRGBFrames.from_hwc`` of an (N, H, W, C)
-          tensor; b = 1, T = their frame count): at depth 8 the bits of ``forward`` on their ``unpack()``, at depth 10 / 12 on their ``to_float()``; or
-          with rectify (a ``StereoRectifier``) the RAW frames of an unrectified rig, uint8 device tensors (1, T, 3, Hs, Ws) or ``YUVFrames`` of its
-          source size Hs x Ws: the bits of ``forward`` on ``RectifyMap.apply_u8`` of each view's RGB bytes (deep frames: ``apply_levels`` of their levels).  H, W above are then the rectified size,
-          and so are the outputs'.  Float images raise TypeError (the remap reads decoded bytes), b > 1 NotImplementedError, another frame size
-          than the maps' ValueError.
+        cascade; b > 1: the reference's glue around the batched forward_update_block).
+        image1, image2: the two views, anything ``video.stereo_source`` takes -- it makes every argument check and defines the errors.  Float
+        tensors, as in the reference; or decoded bytes on the device, for which the call gives the bits of ``forward`` on the float video that
+        the views' class defines (the frame classes: b = 1, T = their frame count):
+          uint8 tensors                                  ``image.float()``
+          ``YUVFrames``                                  ``to_float()`` (8-bit frames: ``to_rgb_u8()``)
+          ``RawFrames``                                  ``to_float()``
+          ``PackedYUVFrames`` / ``PackedRawFrames``      ``unpack()`` (e.g. the ``split_side_by_side()`` halves of one surface)
+          ``PackedRGBFrames``                            ``unpack()`` at depth 8, ``to_float()`` at depth 10 / 12 (``from_hwc`` of an (N, H, W, C) tensor)
+        rectify: a ``StereoRectifier`` -- the views are the RAW frames of an unrectified rig, uint8 device tensors (1, T, 3, Hs, Ws) or ``YUVFrames``
+        of its source size Hs x Ws: the bits of ``forward`` on ``RectifyMap.apply_u8`` of each view's RGB bytes (deep frames: ``apply_levels`` of
+        their levels).  H, W above are then the rectified size, and so are the outputs'.  Float images raise TypeError (the remap reads decoded
+        bytes), b > 1 NotImplementedError, another frame size than the maps' ValueError.
         Bytes reach this package's encoders through ONE ingest kernel; other encoder callables get the float video made of them on the device.
         test_mode: (flow_up, uncertainty), each (b, T, 1, H, W); else (predictions (D, b, T, 1, H, W), uncertainties).
-        pipeline (test_mode only): a ``ClipPipeline`` -- the result is valid once ``pipeline.wait()`` has been called.
+        pipeline (test_mode only, b = 1): a ``ClipPipeline`` -- the result is valid once ``pipeline.wait()`` has been called.
         diagnostics (b = 1): a dict that receives ``["attn_redo"]``, the per-scale fix-up accounting of the memory read-out (see ``cascade``).
-        output (test_mode, b = 1): an ``OutputSpec`` -- the call returns a dict of device tensors (1, n, 1, H0, W0) under "disparity", "depth"
-        and "uncertainties" as the spec asks, written by ONE ppms_disparity_egress launch behind the last iteration (no float32 full-resolution
-        tensor is made); crop = (pad_left, pad_top, H0, W0) inside the frame (default: the whole frame), frames = (from, to) (default: all).
-        With ``OutputSpec(points=..., Q=...)`` the dict also has "points", the organised cloud (1, n, H0, W0, C) of ``cv2.reprojectImageTo3D`` with
-        the spec's gates applied (x, y count from the crop's corner), written by the same single launch (then ppms_scene_egress).
-        With ``OutputSpec(cloud=..., Q=...)`` the dict also has the compact cloud, written by ppms_cloud_egress's two launches behind that one, with no
-        host synchronisation: "cloud" (1, n, capacity, C), the valid points of each frame in row-major pixel order from row 0 on, "cloud_counts"
-        (1, n) int32, their numbers, and with ``cloud_index=True`` "cloud_index" (1, n, capacity) int32, y * W0 + x of every record.  Rows past
-        min(count, capacity) of a frame are unspecified (never written); a count above the capacity tells of a truncated frame.
-        With ``OutputSpec(colour="rgba8" | "bgra8")`` the dict also has "colour", uint8 (1, n, H0, W0, 4): the left view as the network saw it
-        (converted, demosaiced, tone-mapped, rectified; ``video.colour_bytes`` of the source's left float video), pixel-aligned with the planes --
-        one launch (ppms_video_colour_*) directly behind the ingest launch and in front of both encoders; float images make it in torch.  A crop
-        that reaches into the padding sees the replicate padding.  ``cloud_layout="xyzrgb"`` puts that pixel's 32 bits into the fourth word of
-        every record of the compact cloud (ppms_cloud_egress_colour); ``colour_plane=False`` then leaves "colour" out of the dict.
-        With ``OutputSpec(normals="f32" | "f16", Q=Q)`` the dict also has "normals" (1, n, H0, W0, 3): the unit surface normal per pixel from the cross
-        stencil over the organised points of the cropped plane, towards the camera, NaN where there is none -- one launch (ppms_normals_egress)
-        behind the planes' one.  ``cloud_layout="xyzn"`` / ``"xyzrgbn"`` appends it to every record of the compact cloud, which then keeps the
-        pixels whose point and normal are valid (ppms_cloud_egress_normals); ``normals_plane=False`` leaves "normals" out of the dict.
-        rectify=None and output=None (the defaults) add no launch to the calls above."""
+        output (test_mode, b = 1): an ``OutputSpec`` -- the call returns a dict of device tensors in place of the pair, written by the spec's egress
+        launches behind the last iteration (a colour plane: behind the ingest launch); the class defines every key, its shape -- (1, n, 1, H0, W0)
+        for the planes -- and its values.  crop = (pad_left, pad_top, H0, W0) inside the frame (default: the whole frame) and frames = (from, to)
+        (default: all) select what is written (x, y of the points count from the crop's corner); without output= they raise ValueError.
+        flow_init is not served (NotImplementedError).  rectify=None and output=None (the defaults) add no launch to the calls above."""
         if flow_init is not None:
             raise NotImplementedError("flow_init: the reference's own path for it reads undefined state (ppmstereo.py:691-693, 763)")
         if self.fnet is None or self.cnet is None:
@@ -621,73 +628,67 @@ class PPMStereo(PPMStereoHotPath):
         from .encoder import BasicEncoder
         return isinstance(self.fnet, BasicEncoder) and isinstance(self.cnet, Feature)
 
+    def _encode(self, source, T: int, padder: Optional[InputPadder], egress):
+        """The images' way into the model: ingest, the colour plane of ``egress`` and both encoders -> (fmap1, fmap2, c4, c8, c16, ctx_ready).
+        fnet (both views) and cnet (left view) depend on the images only and are chains of small launches that leave most of the chip idle:
+        cnet runs on a second stream beside fnet (whole call -3.5 ms at config 2); its outputs are handed to the caller's stream with
+        record_stream and ``ctx_ready()``, the wait for that stream, to be called once, in front of the first read of c4, c8, c16."""
+        pad_left, pad_top, h, w = (0, 0, *source.size) if padder is None else padder.geometry()
+        n, dev = source.n, source.device
+        decoded = isinstance(source, _ByteSource)
+        if decoded:
+            L.require_gpu(*source.held())
+        cur = torch.cuda.current_stream(dev)
+        if decoded and self._hip_encoders():
+            # bytes -> the operands of fnet's conv1 and cnet's stem, one launch on the caller's stream (ordered before the side stream's wait)
+            fplan, cplan = self.fnet.plan(2 * n, h, w, dev), self.cnet.plan(n, h, w, dev)
+            source.ingest(fplan.s0_view(), cplan.s0_view(), pad_left, pad_top, h, w)
+            if egress is not None:                          # colour=: one launch directly behind the ingest launch, in front of both encoders
+                egress.fill_colour(source, T, h, w, pad_left, pad_top)
+            run_fnet = lambda: torch.split(fplan.run_filled(), n, dim=0)
+            run_cnet = cplan.run_filled
+            held = source.held()
+        else:                                              # float images, or encoder callables of the caller: pad, normalise, encoders
+            im1, im2 = source.float_views()
+            if egress is not None:                          # colour=: in front of the encoders here too (bytes: the kernel; a float video: torch)
+                egress.fill_colour(source, T, h, w, pad_left, pad_top)
+            if padder is not None:
+                im1, im2 = padder.pad(im1, im2)
+            im1, im2 = ((2 * (x / 255.0) - 1.0).contiguous() for x in (im1, im2))
+            run_fnet = lambda: self.fnet([im1, im2])
+            run_cnet = lambda: self.cnet(im1)
+            held = (im1,)
+        side = self._encoder_stream(dev)
+        side.wait_stream(cur)
+        for t_ in held:
+            t_.record_stream(side)
+        with torch.cuda.stream(side):
+            c4, c8, c16 = run_cnet()
+        fmap1, fmap2 = run_fnet()
+        for t_ in (c4, c8, c16):
+            if torch.is_tensor(t_):
+                t_.record_stream(cur)
+        return fmap1, fmap2, c4, c8, c16, lambda: cur.wait_stream(side)     # (the pooling and the SST block need fnet's output only)
+
     def _forward_images(self, source, T: int, padder: Optional[InputPadder], iters: int, test_mode: bool, pipeline, diagnostics, egress=None):
         """``forward`` behind its argument checks: ``source`` (``video.stereo_source``) holds n = b * T frames per view, which ``padder`` brings to the
         model's size (None: they have it; ``forward_batch_test`` hands a window over unpadded).
         egress (an ``_EgressCall``; test_mode, b = 1): the result is ``cascade``'s dict of output planes, each (1, n, 1, H0, W0)."""
-        pad_left, pad_top, h, w = (0, 0, *source.size) if padder is None else padder.geometry()
-        n, dev = source.n, source.device
-        b = n // T
-        decoded = isinstance(source, _ByteSource)
-        if decoded:
-            L.require_gpu(*source.held())
-        with torch.cuda.device(dev):
-            # fnet (both views) and cnet (left view) depend on the images only and are chains of small launches that leave most of the chip
-            # idle: cnet runs on a second stream beside fnet (whole call -3.5 ms at config 2); its outputs are handed to the caller's
-            # stream with an event + record_stream
-            cur = torch.cuda.current_stream(dev)
-            if decoded and self._hip_encoders():
-                # bytes -> the operands of fnet's conv1 and cnet's stem, one launch on the caller's stream (ordered before the side stream's wait)
-                fplan, cplan = self.fnet.plan(2 * n, h, w, dev), self.cnet.plan(n, h, w, dev)
-                source.ingest(fplan.s0_view(), cplan.s0_view(), pad_left, pad_top, h, w)
-                if egress is not None:                          # colour=: one launch directly behind the ingest launch, in front of both encoders
-                    egress.fill_colour(source, T, h, w, pad_left, pad_top)
-                run_fnet = lambda: torch.split(fplan.run_filled(), n, dim=0)
-                run_cnet = cplan.run_filled
-                held = source.held()
-            else:                                              # float images, or encoder callables of the caller: pad, normalise, encoders
-                im1, im2 = source.float_views()
-                if egress is not None:                          # colour=: in front of the encoders here too (bytes: the kernel; a float video: torch)
-                    egress.fill_colour(source, T, h, w, pad_left, pad_top)
-                if padder is not None:
-                    im1, im2 = padder.pad(im1, im2)
-                im1, im2 = ((2 * (x / 255.0) - 1.0).contiguous() for x in (im1, im2))
-                run_fnet = lambda: self.fnet([im1, im2])
-                run_cnet = lambda: self.cnet(im1)
-                held = (im1,)
-            if self.parallel_encoders:
-                side = self._encoder_stream(dev)
-                side.wait_stream(cur)
-                for t_ in held:
-                    t_.record_stream(side)
-                with torch.cuda.stream(side):
-                    c4, c8, c16 = run_cnet()
-                fmap1, fmap2 = run_fnet()
-                for t_ in (c4, c8, c16):
-                    if torch.is_tensor(t_):
-                        t_.record_stream(cur)
-                ready = {"done": False}
-
-                def ctx_ready():                               # the pooling and the SST block run before this: they need fnet's output only
-                    if not ready["done"]:
-                        cur.wait_stream(side)
-                        ready["done"] = True
-            else:
-                fmap1, fmap2 = run_fnet()
-                c4, c8, c16 = run_cnet()
-                ctx_ready = None
+        h, w = source.size if padder is None else padder.geometry()[2:]
+        b = source.n // T
+        with torch.cuda.device(source.device):
+            *maps, ctx_ready = self._encode(source, T, padder, egress)
             if b == 1:
-                feats = self.pre_loop(fmap1, fmap2, c4, c8, c16, T, ctx_ready)
+                feats = self.pre_loop(*maps, T, ctx_ready)
             else:                                              # the glue in front of the loop is per clip (the SST block's time attention sees T frames)
-                if ctx_ready is not None:
-                    ctx_ready()
-                per = [self.pre_loop(*(x[bi * T:(bi + 1) * T] for x in (fmap1, fmap2, c4, c8, c16)), T) for bi in range(b)]
+                ctx_ready()
+                per = [self.pre_loop(*(x[bi * T:(bi + 1) * T] for x in maps), T) for bi in range(b)]
                 feats = {k: torch.cat([p_[k] for p_ in per]) for k in per[0]}
             preds, uncs = [], []
-            if egress is not None:
-                planes = self.cascade(feats, iters, T, test_mode=True, pipeline=pipeline, diagnostics=diagnostics, egress=egress)
+            planes = self.cascade(feats, iters, T, preds, uncs, test_mode=test_mode, pipeline=pipeline if test_mode else None, diagnostics=diagnostics,
+                                  egress=egress)
+            if egress is not None:                             # (test_mode: ``forward`` has checked it)
                 return {k: p[None] for k, p in planes.items()}
-            self.cascade(feats, iters, T, preds, uncs, test_mode=test_mode, pipeline=pipeline if test_mode else None, diagnostics=diagnostics)
             if test_mode:
                 return preds[-1].reshape(b, T, 1, h, w), uncs[-1].reshape(b, T, 1, h, w)
             return torch.stack(preds).reshape(-1, b, T, 1, h, w), torch.stack(uncs).reshape(-1, b, T, 1, h, w)
@@ -709,44 +710,28 @@ class PPMStereo(PPMStereoHotPath):
                            diagnostics: bool = False, output: Optional[OutputSpec] = None, rectify: Optional[StereoRectifier] = None):
         """PPMStereo.forward_batch_test (ppmstereo.py:238-320): batch_dict["stereo_video"] (N, 2, 3, H, W) on the host;
         per window: InputPadder(divis_by=32), one host->device copy, forward(test_mode=True), unpad, one device->host copy;
-        a uint8 video (host or device) is copied as bytes -- a quarter of the float video's: the same bits as for ``stereo_video.float()``;
-        a ``YUVStereoVideo`` (decoded frames, host or device) is copied per window as its planes -- 8-bit 4:2:0 (NV12, I420): 1.5 bytes per
-        pixel and view, 8-bit 4:2:2: 2, 8-bit 4:4:4 and P010: 3 -- and gives the bits of the float video of its ``to_float()`` frames (8-bit: of
-        the uint8 video of ``to_rgb_u8()``); a ``RawStereoVideo`` (a sensor's raw frames, host or device) as its samples -- 1 byte per pixel and
-        view, 2 for 10- and 12-bit words -- and gives the bits of the float video of its ``to_float()`` frames; a ``PackedYUVStereoVideo`` or
-        ``PackedRawStereoVideo`` (packed rows as the camera or capture card left them, host or device) as the packed bytes of each view's own
-        columns -- YUYV 2 per pixel and view, v210 2.67, RAW10p 1.25, RAW12p 1.5 -- and gives the bits of the call on its views' ``unpack()``;
-        a ``PackedRGBStereoVideo`` (interleaved pixels, host or device; ``from_hwc`` of an (N, 2, H, W, C) tensor) as the pixels' own bytes -- bgr24 3
-        per pixel and view, bgra and x2rgb10 4 -- and gives the bits of the call on the planar uint8 video of ``unpack()`` (depth 10 / 12: on the
-        float video of ``to_float()``).
-        Not covered: interpolated chroma siting, 16-bit depth, 4:4:4 packed YUV, BT.2020
-        and HDR transfer functions, planar high-depth RGB, b > 1.  With this package's encoders the bytes are converted, padded and normalised inside the one ingest launch;
         windows of ``kernel_size`` frames every ``kernel_size // 2``, centre frames kept (:296-307).  Windows whose output the
         reference computes and then drops are not run.  Returns {"disparity", "uncertainties"}: (N, 1, H, W) CPU tensors.
+        stereo_video: a float tensor, as in the reference, or any video ``video.stereo_source`` takes as a window (it makes every argument
+        check, on one frame, before any device work), on the host or the device.  A window is copied as what the video holds, and the call
+        gives the bits of the call on the float video its class defines:
+          uint8 tensor                 its bytes, a quarter of the float video's             ``stereo_video.float()``
+          ``YUVStereoVideo``           its planes: 8-bit 4:2:0 (NV12, I420) 1.5 bytes per      ``to_float()`` frames (8-bit: the uint8 video of
+                                       pixel and view, 8-bit 4:2:2 2, 8-bit 4:4:4 and P010 3   ``to_rgb_u8()``)
+          ``RawStereoVideo``           its samples: 1 byte, 2 for 10- and 12-bit words         ``to_float()`` frames
+          ``PackedYUVStereoVideo`` /   the packed bytes of each view's own columns: YUYV 2,    the call on its views' ``unpack()``
+          ``PackedRawStereoVideo``     v210 2.67, RAW10p 1.25, RAW12p 1.5
+          ``PackedRGBStereoVideo``     the pixels' own bytes: bgr24 3, bgra and x2rgb10 4      the planar uint8 video of ``unpack()`` (depth 10 / 12:
+                                       (``from_hwc`` of an (N, 2, H, W, C) tensor)             the float video of ``to_float()``)
+        Not covered: interpolated chroma siting, 16-bit depth, 4:4:4 packed YUV, BT.2020 and HDR transfer functions, planar high-depth RGB,
+        b > 1.  With this package's encoders the bytes are converted, padded and normalised inside the one ingest launch.
         shard_ranks: under torch.distributed the windows are dealt round-robin over the ranks (independent units, no data-path
         collective) and the kept frames are gathered once at the end (``dist.gather_kept_frames``); every rank returns the video.
         diagnostics: the returned dict also has "attn_redo": the per-scale fix-up accounting of the memory read-out (see ``cascade``) summed
         over all windows (``shard_ranks``: over this rank's windows).  False (default): the two keys above, and no extra launch.
-        output: an ``OutputSpec`` -- per window ONE ppms_disparity_egress launch writes the kept frames, cropped and converted, and only
-        those are copied device -> host, straight into their slice of pinned (N, 1, H, W) results of the planes' dtypes (uint16 disparity and
-        uint8 confidence: 3 bytes per pixel and kept frame, where the default path copies 8 for every frame of the window).  Returns
-        {"disparity", "depth" when asked, "uncertainties" unless its format is None, "points" when asked}.  Not with ``shard_ranks``.
-        ``OutputSpec(points="f32", Q=Q, max_uncertainty=..., max_depth=...)``: "points" is the organised cloud (N, H, W, C) -- X, Y, Z[, w] per pixel
-        of the caller's image, NaN where a gate or min_disp takes the pixel -- from the same launch per window (ppms_scene_egress), 12 bytes per pixel
-        of the kept frames for "xyz" f32; ``rectify=`` in front and points behind need the one calibration's maps and Q.
-        ``OutputSpec(cloud="f32", Q=Q, ...)``: the compact cloud, from two more launches per window (ppms_cloud_egress).  "cloud" is a list of N
-        views (min(count_f, capacity), C) of one pinned (N, capacity, C) buffer -- the valid points of frame f in row-major pixel order, the bits of
-        the organised cloud at its valid pixels --, "cloud_index" (``cloud_index=True``) likewise (…,) int32 y * W + x, "cloud_counts" (N,) int64, the
-        untruncated numbers.  Per window the counts are copied to the host first and then only min(count_f, capacity) records of each kept frame:
-        by construction count_f * C * element bytes cross the bus where the organised cloud moves H * W * C; nothing about time is measured here.
-        ``OutputSpec(colour="bgra8", ...)``: "colour" is a pinned uint8 (N, H, W, 4) -- the left view as the network saw it, registered to every other
-        plane, 4 bytes per pixel of the kept frames, from one more launch per window (ppms_video_colour_*) behind the ingest launch.  With
-        ``cloud="f32", cloud_layout="xyzrgb"`` the fourth word of a cloud record is that pixel (XYZRGB: 16 bytes per valid point, where "xyz" with
-        ``cloud_index`` moves 12 + 4 and leaves the gather to the host); ``colour_plane=False`` keeps the plane on the device.  Nothing is timed.
-        ``OutputSpec(normals="f32", Q=Q, ...)``: "normals" is a pinned (N, H, W, 3) -- the unit surface normal per pixel (``OutputSpec``: the
-        definition), 12 bytes per pixel of the kept frames in f32 and 6 in f16, from one more launch per window (ppms_normals_egress).  With
-        ``cloud_layout="xyzn"`` (24-byte records in f32, 12 in f16) or ``"xyzrgbn"`` (28 bytes) every record of the compact cloud carries its normal
-        and the cloud keeps the pixels that have one; ``normals_plane=False`` keeps the plane on the device.  Nobody has timed it.
+        output: an ``OutputSpec`` (TypeError otherwise) -- the spec's egress launches write each window's kept frames, cropped and converted,
+        and the call returns the host results the class defines: its keys, shapes and what crosses the bus.  Not with ``shard_ranks``
+        (NotImplementedError: the gather moves float32).
         rectify: a ``StereoRectifier`` -- the video holds the RAW frames of an unrectified rig, (N, 2, 3, Hs, Ws) uint8 or a ``YUVStereoVideo`` of
         its source size Hs x Ws.  Each window's raw bytes are copied as above, the maps once per device (6 bytes per rectified pixel and view):
         the bits of the call on the uint8 video of ``RectifyMap.apply_u8``.  H x W of the results (and of the ``InputPadder``) is the rectified
@@ -759,86 +744,34 @@ class PPMStereo(PPMStereoHotPath):
                 raise NotImplementedError("forward_batch_test: output= with shard_ranks=True is not served: dist.gather_kept_frames moves float32")
         video = batch_dict["stereo_video"]
         # every argument check, on one frame where the video lies: before any device work.  (H0, W0): the results' size
-        H0, W0 = stereo_source("forward_batch_test", video[:1], rectify=rectify).size
+        H0, W0 = (int(x) for x in stereo_source("forward_batch_test", video[:1], rectify=rectify).size)
         num_ims = len(video)
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         diag = {} if diagnostics else None
-        plan = egress_plan(window_plan(num_ims, kernel_size))    # (start, stop, keep_from, keep_to, dst_from, dst_to) per window
-
-        def finish(out):
-            if diag is not None:
-                out["attn_redo"] = diag.get("attn_redo", {})
-            return out
-
-        if shard_ranks and torch.distributed.is_available() and torch.distributed.is_initialized():
-            from . import dist as D
-            mine_d, mine_u = [], []
-            for start, stop, keep_from, keep_to, first, _ in shard_windows(plan, torch.distributed.get_rank(), torch.distributed.get_world_size()):
-                (d, u), padder = self._window_forward(video, start, stop, dev, iters, None, diag, rectify=rectify)    # one host -> device copy per window
-                d, u = padder.unpad(d[0]), padder.unpad(u[0])               # (T, 1, H0, W0)
-                mine_d.append((first, d[keep_from:keep_to].abs()[:, :1]))   # first: the window's first kept frame in video coordinates
-                mine_u.append((first, u[keep_from:keep_to].abs()[:, :1]))
-            disp, unc = D.gather_kept_frames(mine_d, num_ims, H0, W0), D.gather_kept_frames(mine_u, num_ims, H0, W0)
-            return finish({"disparity": disp.cpu(), "uncertainties": unc.cpu()})
-
-        def idle_stream():
-            # device -> host.  The stream is synchronised FIRST (a spinning wait): a pageable copy issued while the clip's ~900 launches are
-            # still queued blocks inside the runtime on an interrupt-driven wait, and on a loaded host (the GPU boxes: load average 50-60)
-            # the thread was rescheduled 50-150 ms late in every other call (whole call 50 / 100 / 195 ms alternating; with the
-            # synchronisation in front the copy finds an idle stream: 49-50 ms every time, tools/whole_call_probe.py)
-            torch.cuda.current_stream(dev).synchronize()
-
-        kept_d, kept_u = [], []
-
-        def keep_float32(result, padder, keep_from, keep_to, dst_from, dst_to):
-            d, u = result
-            du = torch.cat([padder.unpad(d[0])[:, None], padder.unpad(u[0])[:, None]])                        # one copy for both results
-            idle_stream()
-            du = du.cpu()
-            d, u = du[:du.shape[0] // 2], du[du.shape[0] // 2:]
-            kept_d.append(d[keep_from:keep_to])
-            kept_u.append(u[keep_from:keep_to])
-
-        ragged = ("cloud", "cloud_index")                                  # per frame only the records that exist are copied
-
-        def keep_planes(planes, padder, keep_from, keep_to, dst_from, dst_to):
-            idle_stream()
-            for key, plane in planes.items():
-                if key not in ragged:
-                    host[key][dst_from:dst_to].copy_(plane[0])             # kept frames only, device -> their slice of the pinned result
-            if "cloud" in planes:                                          # the counts are on the host now: min(count, capacity) records per kept frame
-                for i, count in enumerate(host["cloud_counts"][dst_from:dst_to].tolist()):
-                    for key in ragged:
-                        if key in planes:
-                            k = min(count, planes[key].shape[2])
-                            host[key][dst_from + i, :k].copy_(planes[key][0, i, :k])
-
-        if output is not None:
-            host = output.empty(num_ims, int(H0), int(W0), "cpu", pin_memory=True)           # allocated once; every window fills its slice
-        sink = keep_float32 if output is None else keep_planes
-
-        def collect(result, padder, handle, span):
-            if pipe is not None:
-                pipe.wait(handle)
-            sink(result, padder, *span)
-
-        # several windows: independent units -> software pipeline (ClipPipeline): window k + 1's encoders and small scales are enqueued
-        # before window k's result is collected, and run under window k's 1/4 scale
-        pipe = ClipPipeline(dev) if len(plan) > 1 else None
+        windows = egress_plan(window_plan(num_ims, kernel_size))    # (start, stop, keep_from, keep_to, dst_from, dst_to) per window
+        sharded = shard_ranks and torch.distributed.is_available() and torch.distributed.is_initialized()
+        if sharded:
+            windows = shard_windows(windows, torch.distributed.get_rank(), torch.distributed.get_world_size())
+            sink = _KeptOnDevice(num_ims, H0, W0)
+        else:
+            sink = _Float32Sink() if output is None else _PlaneSink(output, num_ims, H0, W0)
+        # several windows on one GPU: independent units -> software pipeline (ClipPipeline): window k + 1's encoders and small scales are
+        # enqueued before window k's result is collected, and run under window k's 1/4 scale
+        pipe = ClipPipeline(dev) if len(windows) > 1 and not sharded else None
         pending = None
         with torch.cuda.device(dev):
-            for start, stop, *span in plan:
-                item = (*self._window_forward(video, start, stop, dev, iters, pipe, diag, output, span[:2], rectify), None if pipe is None else pipe.last, span)
-                if pending is not None:
-                    collect(*pending)
+            for window in (*windows, None):
+                item = None
+                if window is not None:
+                    start, stop, *span = window                          # one host -> device copy per window
+                    item = (*self._window_forward(video, start, stop, dev, iters, pipe, diag, output, span[:2], rectify), None if pipe is None else pipe.last, span)
+                if pending is not None:                                  # the window before this one
+                    result, padder, handle, kept = pending
+                    if pipe is not None:
+                        pipe.wait(handle)
+                    sink.take(result, padder, *kept)
                 pending = item
-            collect(*pending)
-        if output is not None:
-            if "cloud" in host:                                            # views of the pinned buffers: no row past a frame's records exists
-                counts = host["cloud_counts"].tolist()
-                for key in ragged:
-                    if key in host:
-                        host[key] = [host[key][f, :min(c, host[key].shape[1])] for f, c in enumerate(counts)]
-                host["cloud_counts"] = host["cloud_counts"].to(torch.int64)                  # the untruncated numbers
-            return finish(host)
-        return finish({"disparity": torch.cat(kept_d).squeeze(1).abs()[:, :1], "uncertainties": torch.cat(kept_u).squeeze(1).abs()[:, :1]})
+        out = sink.result()
+        if diag is not None:
+            out["attn_redo"] = diag.get("attn_redo", {})
+        return out
