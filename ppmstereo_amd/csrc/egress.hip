@@ -1,6 +1,7 @@
 // Output egress (ppmstereo_amd/engine.py: disparity_egress, driven by output.py's OutputSpec): the two one-launch-per-window kernels that
-// write the caller's disparity / depth / uncertainty planes and the point cloud, their stores, checks and entry points.  The thread mapping,
-// the loads and the geometry check are egress_shared.h's: cloud_egress.hip (the compacted cloud) is built from the same ones.
+// write the caller's disparity / depth / uncertainty planes and the point cloud, their conversions, checks and entry points.  The thread mapping,
+// the loads, the point, the store of a run and the geometry check are egress_shared.h's: cloud_egress.hip and normals_egress.hip are built from
+// the same ones.
 #include "egress_shared.h"
 
 // ------------------------------------------------------------------------------------------------ disparity egress
@@ -8,32 +9,11 @@
 // crop (InputPadder.unpad), frame range, |flow_up[:, 0]|, the 4x bilinear upsampling of the uncertainty, depth = fb / d and the
 // conversions to the planes' formats.  HBM bound: one thread = a run of EG_RUN consecutive x of one output row; the run is loaded
 // and stored 16 bytes at a time (8 for a run of bytes) where its address allows it, element by element at row ends and on
-// rows that start unaligned.  Every offset is 64-bit.  (EG_RUN, bilinear_tap, egress_map and the two loads: egress_shared.h.)
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+// rows that start unaligned.  Every offset is 64-bit.  (EG_RUN, bilinear_tap, egress_map, the two loads and egress_store_run: egress_shared.h.)
 // min(top, rint(v)) for v >= 0 (a magnitude times a positive scale); NaN -> 0
 __device__ __forceinline__ unsigned egress_quant(float v, float top) {
     const float r = rintf(v);
     return r != r ? 0u : (unsigned)fminf(r, top);
-}
-template <class T>
-__device__ __forceinline__ void egress_store_run(const ppms_egress_plane& p, int64_t frame, int y, int x0, int n, const T (&v)[EG_RUN]) {
-    T* dst = (T*)((char*)p.ptr + frame * p.frame_stride + (int64_t)y * p.pitch) + x0;
-    constexpr int BYTES = (int)sizeof(T) * EG_RUN;                       // 8 (u8), 16 (u16, f16) or 32 (f32)
-    constexpr int CHUNK = BYTES < 16 ? BYTES : 16;
-    if (n == EG_RUN && ((uintptr_t)dst & (CHUNK - 1)) == 0) {
-        if constexpr (BYTES < 16) {
-            gst<u32x2>(dst, __builtin_bit_cast(u32x2, v));
-        } else {
-            struct chunks { u32x4 q[BYTES / 16]; };
-            const chunks c = __builtin_bit_cast(chunks, v);
-#pragma unroll
-            for (int i = 0; i < BYTES / 16; ++i) gstore16((char*)dst + 16 * i, c.q[i]);
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < EG_RUN; ++j)
-            if (j < n) dst[j] = v[j];
-    }
 }
 __device__ __forceinline__ void egress_store_disparity(const ppms_egress& o, const egress_run& r, const float (&d)[EG_RUN]) {
     if (o.disparity.format == PPMS_FMT_F32) {
@@ -104,12 +84,12 @@ __global__ __launch_bounds__(256) void disparity_egress_kernel(const float* __re
     }
 }
 // ---- point-cloud egress (include/ppms.h: the formulas).  disparity_egress_kernel's thread mapping, loads and plane stores, plus the two gates
-// and the reprojection with q: a run of points is EG_RUN * C contiguous elements (48 to 128 bytes), stored 16 bytes at a time where the run is
-// whole and its address 16-byte aligned, element by element otherwise.  The upsampled uncertainty is computed once per pixel, where a plane,
-// a gate or w needs it.  Every branch on the struct's fields is wave-uniform.  The mapping, loads and plane stores are the shared pieces above.
+// and the reprojection with q (egress_points' loop, written out in the kernel): a run of points is EG_RUN * C contiguous elements (48 to 128 bytes), which egress_store_run writes
+// like any other run.  The upsampled uncertainty is computed once per pixel, where a plane, a gate or w needs it.  Every branch on the struct's
+// fields is wave-uniform.
 template <class T, int C>
-__device__ __forceinline__ void egress_store_points(const ppms_egress_plane& p, int64_t frame, int y, int x0, int n, const float (&X)[EG_RUN],
-                                                    const float (&Y)[EG_RUN], const float (&Z)[EG_RUN], const float (&u)[EG_RUN]) {
+__device__ __forceinline__ void egress_store_points(const ppms_egress_plane& p, const egress_run& r, const float (&X)[EG_RUN], const float (&Y)[EG_RUN],
+                                                    const float (&Z)[EG_RUN], const float (&u)[EG_RUN]) {
     T v[EG_RUN * C];
 #pragma unroll
     for (int j = 0; j < EG_RUN; ++j) {
@@ -118,21 +98,7 @@ __device__ __forceinline__ void egress_store_points(const ppms_egress_plane& p, 
         v[j * C + 2] = (T)Z[j];
         if constexpr (C == 4) v[j * C + 3] = (T)u[j];
     }
-    T* dst = (T*)((char*)p.ptr + frame * p.frame_stride + (int64_t)y * p.pitch) + (int64_t)x0 * C;
-    constexpr int BYTES = (int)sizeof(T) * EG_RUN * C;                   // 48, 64 (f16), 96 or 128 (f32)
-    if (n == EG_RUN && ((uintptr_t)dst & 15) == 0) {
-        struct chunks { u32x4 q[BYTES / 16]; };
-        const chunks c = __builtin_bit_cast(chunks, v);
-#pragma unroll
-        for (int i = 0; i < BYTES / 16; ++i) gstore16((char*)dst + 16 * i, c.q[i]);
-    } else {
-#pragma unroll
-        for (int j = 0; j < EG_RUN; ++j)
-            if (j < n) {
-#pragma unroll
-                for (int c = 0; c < C; ++c) dst[j * C + c] = v[j * C + c];
-            }
-    }
+    egress_store_run<T, C>(p, r.frame, r.y, r.x0, r.n, v);
 }
 __global__ __launch_bounds__(256) void scene_egress_kernel(const float* __restrict__ flow_up, const float* __restrict__ unc, ppms_egress3d e, int H,
                                                             int W, int frame0, int pad_left, int pad_top, int H0, int W0, float sh, float sw, int rpr,
@@ -142,9 +108,8 @@ __global__ __launch_bounds__(256) void scene_egress_kernel(const float* __restri
     const ppms_egress& o = e.base;
     const egress_run r = egress_map(idx, rpr, H0, W0, pad_left, pad_top);
     const bool gated = o.depth.ptr || e.points.ptr;                      // a plane the gates act on
-    const bool gate_u = e.max_uncertainty < INFINITY, gate_z = e.max_depth < INFINITY;
     float u[EG_RUN];
-    if (o.uncertainty.ptr || (gated && gate_u) || (e.points.ptr && e.points_components == 4)) {
+    if (o.uncertainty.ptr || (gated && e.max_uncertainty < INFINITY) || (e.points.ptr && e.points_components == 4)) {
         egress_load_uncertainty(unc, H, W, frame0, sh, sw, r, u);
     } else {
 #pragma unroll
@@ -155,44 +120,49 @@ __global__ __launch_bounds__(256) void scene_egress_kernel(const float* __restri
     float d[EG_RUN];
     egress_load_disparity(flow_up, H, W, frame0, r, d);
     if (o.disparity.ptr) egress_store_disparity(o, r, d);
-    bool ok[EG_RUN];                                                     // valid_d and valid_u (both false for NaN)
-#pragma unroll
-    for (int j = 0; j < EG_RUN; ++j) ok[j] = d[j] >= o.min_disp && (!gate_u || u[j] <= e.max_uncertainty);
     if (o.depth.ptr) {
+        const bool gate_z = e.max_depth < INFINITY;
         float z[EG_RUN];
         bool okz[EG_RUN];
 #pragma unroll
         for (int j = 0; j < EG_RUN; ++j) {
             const float q = __fdiv_rn(o.fb, d[j]);
-            okz[j] = ok[j] && (!gate_z || q <= e.max_depth);
+            okz[j] = egress_valid(d[j], u[j], o.min_disp, e.max_uncertainty) && (!gate_z || q <= e.max_depth);
             z[j] = okz[j] ? q : INFINITY;
         }
         egress_store_depth(o, r, z, okz);
     }
     if (e.points.ptr) {
-        const float yf = (float)r.y;                                      // the pixel's row and column in the cropped plane
+        float X[EG_RUN], Y[EG_RUN], Z[EG_RUN];
+        // egress_points' loop (egress_shared.h) written out, with the NaN select in it: the same operations in the same order, so the same bits.
+        // Through the call, a run at a time, this kernel ran 3 % above the band of the form it had before, and a pixel at a time two samples
+        // of six with f32 points lay 0.02 and 0.06 us above it; written out those are inside (docs/LOG_r25.md, section 6: the numbers, and
+        // what f16 points show).  The kernel's 72 VGPRs and 7 waves per SIMD (64 and 8 before) are not this loop's, whose text is what it
+        // was: the kernel had 66 and 7 with the call too, and what else changed in it is the shared store of a run.
+        const bool gate_u = e.max_uncertainty < INFINITY, gate_z = e.max_depth < INFINITY;
+        const float yf = (float)r.y;
         float qy[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) qy[i] = e.q[4 * i + 1] * yf;
-        float X[EG_RUN], Y[EG_RUN], Z[EG_RUN];
 #pragma unroll
         for (int j = 0; j < EG_RUN; ++j) {
+            const bool ok = d[j] >= o.min_disp && (!gate_u || u[j] <= e.max_uncertainty);
             const float xf = (float)(r.x0 + j);
             float v[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) v[i] = ((e.q[4 * i] * xf + qy[i]) + e.q[4 * i + 2] * d[j]) + e.q[4 * i + 3];
             const float pz = __fdiv_rn(v[2], v[3]);
-            const bool okp = ok[j] && (!gate_z || (pz > 0.0f && pz <= e.max_depth));
+            const bool okp = ok && (!gate_z || (pz > 0.0f && pz <= e.max_depth));
             X[j] = okp ? __fdiv_rn(v[0], v[3]) : __builtin_nanf("");
             Y[j] = okp ? __fdiv_rn(v[1], v[3]) : __builtin_nanf("");
             Z[j] = okp ? pz : __builtin_nanf("");
         }
         if (e.points.format == PPMS_FMT_F32) {
-            if (e.points_components == 3) egress_store_points<float, 3>(e.points, r.frame, r.y, r.x0, r.n, X, Y, Z, u);
-            else egress_store_points<float, 4>(e.points, r.frame, r.y, r.x0, r.n, X, Y, Z, u);
+            if (e.points_components == 3) egress_store_points<float, 3>(e.points, r, X, Y, Z, u);
+            else egress_store_points<float, 4>(e.points, r, X, Y, Z, u);
         } else {
-            if (e.points_components == 3) egress_store_points<_Float16, 3>(e.points, r.frame, r.y, r.x0, r.n, X, Y, Z, u);
-            else egress_store_points<_Float16, 4>(e.points, r.frame, r.y, r.x0, r.n, X, Y, Z, u);
+            if (e.points_components == 3) egress_store_points<_Float16, 3>(e.points, r, X, Y, Z, u);
+            else egress_store_points<_Float16, 4>(e.points, r, X, Y, Z, u);
         }
     }
 }

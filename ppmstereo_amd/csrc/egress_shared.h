@@ -1,8 +1,9 @@
-// What the egress sources (egress.hip: the planes and the organised points; cloud_egress.hip: the compacted cloud; normals_egress.hip: the
-// normals plane and the oriented cloud, which is built from the compacted cloud's pieces at the end of this file) share: the thread mapping,
-// the loads of the engine's state, and the host checks of the geometry and the frame range, of the reprojection's arguments and of a strided
-// destination.  Device pieces are restated nowhere else: a pixel's d and u are the same bits whichever launch reads them.  The check of a
-// colour plane (4-byte pixels) is here too: video_ingest.hip's colour kernel writes such a plane, cloud_egress.hip's coloured cloud reads it.
+// What the egress sources share (egress.hip: the planes and the organised points; cloud_egress.hip: the compact clouds, plain, coloured and
+// oriented; normals_egress.hip: the normals plane): the thread mapping, the loads of the engine's state, the one point (egress_points: the
+// reprojection of a pixel and its validity), the one store of a run of records to a plane, and the host checks of the geometry and the frame
+// range, of the reprojection's arguments, of a strided destination and of the two planes a cloud reads.  Device pieces are restated nowhere
+// else: a pixel's d, u and point are the same bits whichever launch forms them.  (video_ingest.hip's colour kernel writes the colour plane
+// that is checked here.)
 #pragma once
 #include "common.h"
 
@@ -58,6 +59,75 @@ __device__ __forceinline__ void egress_load_uncertainty(const float* __restrict_
     const float* s = unc + (frame0 + r.frame) * h * w;
 #pragma unroll
     for (int j = 0; j < EG_RUN; ++j) u[j] = fabsf(bilinear_tap(s, h, w, sh, sw, r.sy, r.sx + (j < r.n ? j : r.n - 1)));
+}
+// valid_d and valid_u of a pixel (both false for NaN); u is read only with the gate on.  scene_egress_kernel's depth plane asks it.
+// egress_points holds the same line inside its loop and does not call this: with the call there, the code of every kernel that inlines the
+// loop comes out differently, and the loop keeps the form it was timed in (docs/LOG_r25.md, section 6).
+__device__ __forceinline__ bool egress_valid(float d, float u, float min_disp, float max_uncertainty) {
+    return d >= min_disp && (!(max_uncertainty < INFINITY) || u <= max_uncertainty);
+}
+// The one point (include/ppms.h: the formulas): pixels (x0 + j, y), j < N, of the cropped plane with disparities d -> X, Y, Z, computed whatever
+// the validity.  Returns the validity mask: bit j = valid_d, valid_u and the depth gate on Z of pixel j, and 0 for j >= n (the pixels of a run
+// inside its row).  N = EG_RUN: a thread's run; N = 1: one pixel.  Every operation is one fp32 operation in the documented order and the build
+// contracts nothing, so scene_egress_kernel's points plane, the clouds' records and the normals' stencil see the same bits.  The gates are
+// fields of the launch's struct: every branch on them is wave-uniform.  (A run at a time, with the row's products in front of the loop: formed
+// pixel by pixel the clouds' launches took 3 % longer.)
+template <int N>
+__device__ __forceinline__ unsigned egress_points(const float (&q)[16], float min_disp, float max_uncertainty, float max_depth, int x0, int y, int n,
+                                                  const float (&d)[N], const float (&u)[N], float (&X)[N], float (&Y)[N], float (&Z)[N]) {
+    const bool gate_u = max_uncertainty < INFINITY, gate_z = max_depth < INFINITY;
+    const float yf = (float)y;                                           // the pixel's row and column in the cropped plane
+    float qy[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) qy[i] = q[4 * i + 1] * yf;
+    unsigned mask = 0;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        const bool ok = d[j] >= min_disp && (!gate_u || u[j] <= max_uncertainty);     // valid_d and valid_u (both false for NaN)
+        const float xf = (float)(x0 + j);
+        float v[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = ((q[4 * i] * xf + qy[i]) + q[4 * i + 2] * d[j]) + q[4 * i + 3];
+        const float pz = __fdiv_rn(v[2], v[3]);
+        const bool okp = ok && (!gate_z || (pz > 0.0f && pz <= max_depth));
+        X[j] = __fdiv_rn(v[0], v[3]);
+        Y[j] = __fdiv_rn(v[1], v[3]);
+        Z[j] = pz;
+        mask |= (okp && j < n) ? 1u << j : 0u;
+    }
+    return mask;
+}
+// one pixel through the same body
+__device__ __forceinline__ bool egress_point(const float (&q)[16], float min_disp, float max_uncertainty, float max_depth, int x, int y, float d, float u,
+                                             float& X, float& Y, float& Z) {
+    const float d1[1] = {d}, u1[1] = {u};
+    float X1[1], Y1[1], Z1[1];
+    const unsigned ok = egress_points<1>(q, min_disp, max_uncertainty, max_depth, x, y, 1, d1, u1, X1, Y1, Z1);
+    X = X1[0], Y = Y1[0], Z = Z1[0];
+    return ok != 0;
+}
+// The one store: a run of EG_RUN records of C elements each -> plane `p` at (frame, y, x0), n of them inside the row.  16 bytes at a time (8
+// for a run of bytes) where the run is whole and its address allows it, element by element otherwise.
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+template <class T, int C = 1>
+__device__ __forceinline__ void egress_store_run(const ppms_egress_plane& p, int64_t frame, int y, int x0, int n, const T (&v)[EG_RUN * C]) {
+    T* dst = (T*)((char*)p.ptr + frame * p.frame_stride + (int64_t)y * p.pitch) + (int64_t)x0 * C;
+    constexpr int BYTES = (int)sizeof(T) * EG_RUN * C;                   // 8 (a u8 plane) to 128 (f32 points with w)
+    constexpr int CHUNK = BYTES < 16 ? BYTES : 16;
+    if (n == EG_RUN && ((uintptr_t)dst & (CHUNK - 1)) == 0) {
+        if constexpr (BYTES < 16) {
+            gst<u32x2>(dst, __builtin_bit_cast(u32x2, v));
+        } else {
+            struct chunks { u32x4 q[BYTES / 16]; };
+            const chunks c = __builtin_bit_cast(chunks, v);
+#pragma unroll
+            for (int i = 0; i < BYTES / 16; ++i) gstore16((char*)dst + 16 * i, c.q[i]);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < EG_RUN * C; ++j)
+            if (j < n * C) dst[j] = v[j];
+    }
 }
 // ---- host: the geometry and the frame range every egress entry point refuses alike, under the name `who` of the one called.  On success
 // the launch geometry: runs per output row, runs in all (one thread each), ppms_bilinear's scales for (H/4, W/4) -> (H, W).
@@ -115,133 +185,11 @@ static inline int egress_check_colour_plane(const char* who, const char* name, c
     snprintf(stride, sizeof(stride), "%s.frame_stride", name);
     return egress_check_strided(who, name, stride, p->ptr, p->frame_stride, &p->pitch, PPMS_FMT_F32, n_frames, rows, cols);      // (4-byte elements)
 }
-// ---- the compact clouds' pieces (cloud_egress.hip: ppms_cloud_egress and its coloured twin; normals_egress.hip: the oriented cloud).  A workgroup
-// of WG threads takes WG consecutive runs of ONE frame with egress_map's mapping, so thread order is row-major pixel order.
-constexpr int CLOUD_WG = 256;
-constexpr int CLOUD_PIXELS = CLOUD_WG * EG_RUN;                          // pixels of a workgroup: the most records it places (2048)
-
-// d, u (where a gate or w reads it), X, Y, Z of the run's pixels; returns the validity mask, bit j = pixel j of the run (0 past the row's end).
-// scene_egress_kernel's arithmetic, restated: that kernel does not call this function, its generated code stays as it is.
-__device__ __forceinline__ unsigned cloud_points(const float* __restrict__ flow_up, const float* __restrict__ unc, const ppms_cloud& c, bool want_w,
-                                                 int H, int W, int frame0, float sh, float sw, const egress_run& r, float (&X)[EG_RUN],
-                                                 float (&Y)[EG_RUN], float (&Z)[EG_RUN], float (&u)[EG_RUN]) {
-    const bool gate_u = c.max_uncertainty < INFINITY, gate_z = c.max_depth < INFINITY;
-    if (gate_u || want_w) {
-        egress_load_uncertainty(unc, H, W, frame0, sh, sw, r, u);
-    } else {
-#pragma unroll
-        for (int j = 0; j < EG_RUN; ++j) u[j] = 0.0f;
-    }
-    float d[EG_RUN];
-    egress_load_disparity(flow_up, H, W, frame0, r, d);
-    const float yf = (float)r.y;                                          // the pixel's row and column in the cropped plane
-    float qy[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) qy[i] = c.q[4 * i + 1] * yf;
-    unsigned mask = 0;
-#pragma unroll
-    for (int j = 0; j < EG_RUN; ++j) {
-        const bool ok = d[j] >= c.min_disp && (!gate_u || u[j] <= c.max_uncertainty);     // valid_d and valid_u (both false for NaN)
-        const float xf = (float)(r.x0 + j);
-        float v[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = ((c.q[4 * i] * xf + qy[i]) + c.q[4 * i + 2] * d[j]) + c.q[4 * i + 3];
-        const float pz = __fdiv_rn(v[2], v[3]);
-        const bool okp = ok && (!gate_z || (pz > 0.0f && pz <= c.max_depth));
-        X[j] = __fdiv_rn(v[0], v[3]);
-        Y[j] = __fdiv_rn(v[1], v[3]);
-        Z[j] = pz;
-        mask |= (okp && j < r.n) ? 1u << j : 0u;
-    }
-    return mask;
-}
-// the thread's run of frame blockIdx.y (ridx: its number inside the frame) and its points; an idle thread past the frame's last run has no pixel
-template <int WG = CLOUD_WG>
-__device__ __forceinline__ unsigned cloud_thread(const float* __restrict__ flow_up, const float* __restrict__ unc, const ppms_cloud& c, bool want_w,
-                                                 int H, int W, int frame0, int pad_left, int pad_top, int H0, int W0, float sh, float sw, int rpr,
-                                                 int64_t runs, egress_run& r, float (&X)[EG_RUN], float (&Y)[EG_RUN], float (&Z)[EG_RUN],
-                                                 float (&u)[EG_RUN]) {
-    const int64_t ridx = (int64_t)blockIdx.x * WG + threadIdx.x;
-    if (ridx >= runs) return 0u;
-    r = egress_map((int64_t)blockIdx.y * runs + ridx, rpr, H0, W0, pad_left, pad_top);
-    return cloud_points(flow_up, unc, c, want_w, H, W, frame0, sh, sw, r, X, Y, Z, u);
-}
-// exclusive prefix sum of v over the workgroup's WG threads in thread order, and the workgroup's total: a wave64 scan, then the waves'
-// totals through LDS (ws: WG / 64 ints).  Integer sums in a fixed order; ws may be used again after the call.
-struct cloud_scan { int before, total; };
-template <int WG = CLOUD_WG>
-__device__ __forceinline__ cloud_scan cloud_block_scan(int v, int* ws) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int s = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(s, off);
-        if (lane >= off) s += t;
-    }
-    if (lane == 63) ws[wave] = s;
-    __syncthreads();
-    cloud_scan out;
-    out.before = s - v;
-    out.total = 0;
-#pragma unroll
-    for (int i = 0; i < WG / 64; ++i) {
-        if (i < wave) out.before += ws[i];
-        out.total += ws[i];
-    }
-    __syncthreads();
-    return out;
-}
-// The workgroup's staged bytes [lo, hi) of `smem` -> global `gbase + the same offset`.  smem and gbase are congruent mod 16 (the staging is
-// shifted by the destination's misalignment), so the whole 16-byte slots inside the range go out as 16-byte stores; the head in front of the
-// first whole slot and the tail behind the last one element by element (E: the element, which lo and hi are multiples of).
-template <class E, int WG = CLOUD_WG>
-__device__ __forceinline__ void cloud_flush(const char* smem, char* gbase, int lo, int hi) {
-    int first = (lo + 15) & ~15, last = hi & ~15;
-    if (last < first) first = last = hi;                                 // no whole slot: all of it element by element
-    for (int off = first + (int)threadIdx.x * 16; off < last; off += WG * 16) gstore16(gbase + off, *(const u32x4*)(smem + off));
-    const int head = (first - lo) / (int)sizeof(E), tail = (hi - last) / (int)sizeof(E);         // fewer than 16 / sizeof(E) elements each
-    if ((int)threadIdx.x < head) *(E*)(gbase + lo + threadIdx.x * sizeof(E)) = *(const E*)(smem + lo + threadIdx.x * sizeof(E));
-    if ((int)threadIdx.x < tail) *(E*)(gbase + last + threadIdx.x * sizeof(E)) = *(const E*)(smem + last + threadIdx.x * sizeof(E));
-}
-// workgroups of `wg` threads per frame; 0 for a geometry the entry points refuse
-static inline int64_t cloud_blocks_per_frame(int H0, int W0, int wg = CLOUD_WG) {
-    if (H0 <= 0 || W0 <= 0 || (int64_t)H0 * W0 > 0x7fffffff) return 0;
-    return ((int64_t)H0 * ((W0 + EG_RUN - 1) / EG_RUN) + wg - 1) / wg;
-}
-// ---- host: what the compact clouds' entry points check, under the name `who` of the one called; on success the launch geometry and the workgroups
-// per frame.  layout: what a record holds beside X, Y, Z -- CLOUD_PLAIN (ppms_cloud_egress: 3 or 4 components, the fourth u), CLOUD_COLOUR
-// (ppms_cloud_egress_colour: the fourth component is the colour word, so nothing but the max_uncertainty gate reads unc), CLOUD_NORMALS
-// (ppms_cloud_egress_normals: 6 or 7 components, workgroups of `wg` threads; unc as for CLOUD_COLOUR)
-enum { CLOUD_PLAIN = 0, CLOUD_COLOUR = 1, CLOUD_NORMALS = 2 };
-static inline int cloud_check(const char* who, const float* flow_up, const float* unc, int T, int H, int W, int frame0, int n_frames, int pad_left,
-                              int pad_top, int H0, int W0, const ppms_cloud* out, int layout, egress_launch& g, int64_t* blocks_out, int wg = CLOUD_WG) {
-    PPMS_REQUIRE(out, "%s: null out struct", who);
-    const ppms_cloud& c = *out;
-    if (const int rc = egress_check_geometry(who, T, H, W, frame0, n_frames, pad_left, pad_top, H0, W0, &g)) return rc;
-    PPMS_REQUIRE((int64_t)H0 * W0 <= 0x7fffffff, "%s: H0 * W0 = %lld pixel indices exceed int32", who, (long long)H0 * W0);
-    PPMS_REQUIRE(n_frames <= 65535, "%s: n_frames = %d exceeds one grid", who, n_frames);
-    PPMS_REQUIRE(flow_up != nullptr, "%s: null flow_up", who);
-    PPMS_REQUIRE(c.records != nullptr, "%s: null records", who);
-    PPMS_REQUIRE(c.counts != nullptr, "%s: null counts", who);
-    PPMS_REQUIRE(c.format == PPMS_FMT_F32 || c.format == PPMS_FMT_F16, "%s: format = %d is neither PPMS_FMT_F32 nor PPMS_FMT_F16", who, c.format);
-    if (layout == CLOUD_NORMALS)
-        PPMS_REQUIRE(c.components == 6 || c.components == 7, "%s: components = %d must be 6 or 7", who, c.components);
-    else
-        PPMS_REQUIRE(c.components == 3 || c.components == 4, "%s: components = %d must be 3 or 4", who, c.components);
-    PPMS_REQUIRE(c.reserved == 0, "%s: reserved = %d must be 0", who, c.reserved);
-    PPMS_REQUIRE(c.capacity > 0 && c.capacity <= 0x7fffffff, "%s: capacity = %lld must be in 1 .. 2^31 - 1", who, (long long)c.capacity);
-    // a frame of records, and of indices (int32: 4-byte elements, as PPMS_FMT_F32 has), is one dense row of `capacity` of them
-    if (const int rc = egress_check_strided(who, "records", "frame_stride", c.records, c.frame_stride, nullptr, c.format, n_frames, 1, c.capacity * c.components))
-        return rc;
-    if (c.index)
-        if (const int rc = egress_check_strided(who, "index", "index_frame_stride", c.index, c.index_frame_stride, nullptr, PPMS_FMT_F32, n_frames, 1, c.capacity))
-            return rc;
-    PPMS_REQUIRE((uintptr_t)c.counts % 4 == 0 && (uintptr_t)c.block_counts % 4 == 0, "%s: counts and block_counts must be multiples of the 4-byte element", who);
-    const int64_t blocks = cloud_blocks_per_frame(H0, W0, wg);
-    PPMS_REQUIRE(c.block_counts != nullptr && c.block_counts_len >= n_frames * blocks,
-                 "%s: block_counts is null or block_counts_len = %lld is less than the %lld entries of %s", who,
-                 (long long)c.block_counts_len, (long long)(n_frames * blocks),
-                 layout == CLOUD_NORMALS ? "ppms_cloud_egress_normals_workspace" : "ppms_cloud_egress_workspace");
-    *blocks_out = blocks;
-    return egress_check_reprojection(who, unc, c.q, c.min_disp, c.max_uncertainty, c.max_depth, true, true, layout == CLOUD_PLAIN ? c.components : 3);
+// ---- host: a normals plane of n_frames x H0 rows of W0 * 3 elements, as ppms_normals_egress (the plane it writes) and ppms_cloud_egress_normals
+// (the plane it reads) refuse it
+static inline int egress_check_normals_plane(const char* who, const ppms_egress_plane* p, int n_frames, int H0, int W0) {
+    PPMS_REQUIRE(p && p->ptr, "%s: null normals plane", who);
+    PPMS_REQUIRE(p->format == PPMS_FMT_F32 || p->format == PPMS_FMT_F16, "%s: normals.format = %d is neither PPMS_FMT_F32 nor PPMS_FMT_F16", who, p->format);
+    PPMS_REQUIRE(p->reserved == 0, "%s: normals.reserved = %d must be 0", who, p->reserved);
+    return egress_check_strided(who, "normals", "normals.frame_stride", p->ptr, p->frame_stride, &p->pitch, p->format, n_frames, H0, (int64_t)W0 * 3);
 }

@@ -436,10 +436,8 @@ class _EgressCall:
             query = L.load().ppms_cloud_egress_normals_workspace if oriented else L.load().ppms_cloud_egress_workspace
             workspace = torch.empty(query(f1 - f0, h0, w0), dtype=torch.int32, device=eng.FLOW_OUT.device)
             colour = spec._plane(self.colour, 1, spec.colour) if spec.cloud_layout in _COLOURED else None
-            if oriented:
-                eng.egress(spec.cloud_struct(planes, workspace), f0, f1 - f0, pad_left, pad_top, h0, w0, colour, spec._plane(normals, 1, spec.normals))
-            else:
-                eng.egress(spec.cloud_struct(planes, workspace), f0, f1 - f0, pad_left, pad_top, h0, w0, colour)
+            eng.egress(spec.cloud_struct(planes, workspace), f0, f1 - f0, pad_left, pad_top, h0, w0, colour,
+                       spec._plane(normals, 1, spec.normals) if oriented else None)
         return planes
 
 

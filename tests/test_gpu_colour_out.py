@@ -162,6 +162,14 @@ def test_kernel_b_capacity_cuts_inside_the_second_workgroup():
     check_colour_cloud(spec, flow, unc, A_GEOMETRY, CloudDest("f32", 4, 4, cut, first=1, gap=24, index_gap=8), 813, capacity_hit=True)
 
 
+def test_kernel_b_more_workgroups_than_a_workgroup_has_threads():
+    """test_gpu_egress_cloud's geometry of that name: T = 1, 516 x 1024 uncropped, 258 workgroups of 256 in the frame -- the reduction that gives the
+    last workgroups their base takes more than one block count per thread."""
+    assert L.load().ppms_cloud_egress_workspace(1, 516, 1024) == 258
+    flow, unc = engine_state(1, 516, 1024, 76)
+    check_colour_cloud(colour_spec(), flow, unc, (0, 1, 0, 0, 516, 1024), CloudDest("f32", 4, 1, 516 * 1024), 818)
+
+
 def test_kernel_b_one_full_workgroup_without_the_uncertainty_gate():
     """32 x 64 uncropped, T = 2: exactly 256 whole, 16-byte aligned runs per frame -- the 16-byte loads of the colour words.  max_uncertainty off:
     nothing reads unc, and NULL is accepted for it."""

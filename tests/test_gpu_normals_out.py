@@ -234,6 +234,16 @@ def test_oriented_cloud_capacity_cuts_inside_the_second_workgroup(fmt, layout):
                    capacity_hit=True)
 
 
+@pytest.mark.parametrize("fmt,layout", [("f32", "xyzrgbn"), ("f16", "xyzn")])
+def test_oriented_cloud_more_workgroups_than_a_workgroup_has_threads(fmt, layout):
+    """T = 1, 132 x 1024 uncropped: 128 runs per row, 16 896 runs, 132 workgroups of 128 in the frame -- more than a workgroup has threads, so the
+    reduction that gives the last workgroups their base takes more than one block count per thread."""
+    assert L.load().ppms_cloud_egress_normals_workspace(1, 132, 1024) == 132
+    flow, unc = state(1, 132, 1024, seed=11)
+    dest = OrientedDest(fmt, 7 if layout == "xyzrgbn" else 6, 1, 132 * 1024)
+    check_oriented(oriented_spec(fmt, layout), flow, unc, (0, 1, 0, 0, 132, 1024), dest, seed=835)
+
+
 def test_oriented_cloud_all_invalid_frames_write_nothing():
     flow, unc = state()
     spec = oriented_spec("f32", "xyzn", min_disp=1000.0)

@@ -31,7 +31,7 @@ import time
 
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LAUNCHES = ("ppms_convex_upsample", "ppms_convex_upsample_3d", "ppms_bilinear", "ppms_disparity_egress", "ppms_scene_egress", "ppms_cloud_egress",
-            "ppms_cloud_egress_colour")
+            "ppms_cloud_egress_colour", "ppms_normals_egress", "ppms_cloud_egress_normals")
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ worker
